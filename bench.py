@@ -17,8 +17,15 @@ Prints ONE JSON line (rank 0).  Extra objects:
   roofline      dominant kernel vs the fp32 MFMA/VALU peak (157.3 TFLOP/s) -- the bound that binds this path
                 (arithmetic intensity ~1900 flop/B); `hbm_*` fields give the HBM view north_star
                 also asks for.  Kernel time is measured live with HIP events around every launch in the timed region.
-  cpu_baseline  oracle/psnode_oracle.py (PyTorch-CPU restatement of the reference, "port") timed on this host's
+  cpu_baseline  (--full) oracle/psnode_oracle.py (PyTorch-CPU restatement of the reference, "port") timed on this host's
                 cores on a bounded sample of the same workload.  A reported baseline, not the target.
+  extra         (--full, default workload) the other workloads, solvers, widths and training steps, each on its own clock
+                and checked against the oracle.
+
+A plain run sets up, warms up, times the --steps steps and prints the line; everything measured besides the headline
+(cpu_baseline, extra, and at N>1 the all-gather timed alone) runs only with --full.  --dump-outputs DIR writes the arrays
+the timed path returned in its last step as DIR/<name>.npy (float32; past 60 MiB in all, a fixed seeded sample of the
+trajectories); the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -712,6 +719,35 @@ def model_train_extra_line(workload, method, dev, steps=8, warmup=3, hidden=None
     return res
 
 
+DUMP_BYTES = 60 * 2 ** 20      # --dump-outputs: at most this much array data in all
+
+
+def dump_outputs(out_dir, w, outs, trainer=None):
+    """--dump-outputs: what a caller of the timed path receives from its last step, as <out_dir>/<name>.npy in float32 -- the
+    outputs out0, out1, ... and, for --train, the parameter gradients grad_<de|ae><layer>_<weight|bias>.  Past DUMP_BYTES in all,
+    every output keeps the same trajectories: a sorted sample drawn from a fixed seed, so that two runs with the same arguments
+    write the same elements."""
+    import numpy as np
+    bdim = 0 if w["kind"] in ("ode02_model", "dae02_model") else 1       # model outputs are [B,T,D]; the integrators' [T,B,D]
+    named = [(f"out{k}", o, bdim) for k, o in enumerate(outs)]
+    if trainer is not None:
+        nde = 2 * len(trainer.layers)
+        for k, q in enumerate(trainer.params):
+            net, j = ("de", k) if k < nde else ("ae", k - nde)
+            named.append((f"grad_{net}{j // 2}_{'weight' if j % 2 == 0 else 'bias'}", q.grad, None))
+    B = w["B"]
+    named = [(n, t.detach(), d if d is not None and t.dim() > d and t.shape[d] == B else None) for n, t, d in named if t is not None]
+    fixed = sum(4 * t.numel() for _, t, d in named if d is None)
+    per_traj = sum(4 * t.numel() for _, t, d in named if d is not None) / B
+    if fixed + per_traj * B > DUMP_BYTES:
+        nb = max(1, min(B, int((DUMP_BYTES - fixed) // per_traj)))
+        idx = torch.randperm(B, generator=torch.Generator().manual_seed(0))[:nb].sort().values
+        named = [(n, t if d is None else t.index_select(d, idx.to(t.device)), d) for n, t, d in named]
+    os.makedirs(out_dir, exist_ok=True)
+    for n, t, _ in named:
+        np.save(os.path.join(out_dir, n + ".npy"), t.float().contiguous().cpu().numpy())
+
+
 def self_launch(n):
     """`python bench.py --gpus N` without a launcher: start N ranks of this very command line under torch.distributed.run on this
     node (one process per GPU, RCCL; rendezvous on 127.0.0.1 at a free port) and return its exit code.  The children see
@@ -771,9 +807,14 @@ def main():
     ap.add_argument("--batch", type=int, default=None, help="override trajectories per GPU")
     ap.add_argument("--grid", type=int, default=None, help="override grid points T")
     ap.add_argument("--hidden", type=int, default=None, help="override the MLPs' hidden width (the scripts' --hidden)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="default run: skip the extra workloads (configs 3, 4, Euler) timed after the headline")
-    ap.add_argument("--no-train-extras", action="store_true", help="default run: skip the training-step workloads among the extras")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the CPU baseline, the extra workloads of the default workload, "
+                         "and at N>1 the all-gather timed alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the arrays the timed path returned in its last step as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the extra workloads (configs 3, 4, Euler) timed after the headline")
+    ap.add_argument("--no-train-extras", action="store_true", help="with --full: skip the training-step workloads among the extras")
     ap.add_argument("--no-gather", action="store_true", help="N>1: skip the all-gather (integrate-only scaling)")
     ap.add_argument("--train", action="store_true", help="time forward + backward (fused autograd route) instead of the forward alone")
     ap.add_argument("--loss", default="mse-fused", choices=["mse-fused", "mse-torch", "weighted-sum"],
@@ -795,6 +836,8 @@ def main():
     ap.add_argument("--chunks", default="auto", help="N>1: time chunks of the integrate/all-gather pipeline (1 = no overlap; 'auto' = chosen from "
                     "the measured integrate-only and gather-only times of the warm-up)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     requested_gpus = args.gpus
 
     if "WORLD_SIZE" not in os.environ and (args.gpus > 1 or args.force_dist):
@@ -982,9 +1025,11 @@ def main():
         tt = torch.tensor([elapsed, kern_avg_ms, kern_med_ms], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed, kern_avg_ms, kern_med_ms = float(tt[0]), float(tt[1]), float(tt[2])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, w, outs, trainer)
 
     gather_only_ms, by_algo = None, None
-    if do_gather and w["kind"] in ("ode", "dae"):
+    if do_gather and w["kind"] in ("ode", "dae") and (args.full or args.gather_algo == "both"):
         # config 5 also wants the gather alone: un-pipelined all-gathers of the full [T,B,D] shards, after the timed region -- on the timed
         # region's algorithm, and with --gather-algo both on the other one too (+ the pipelined step re-timed on it)
         flats = [torch.empty((world * T, B, o.shape[-1]), dtype=torch.float32, device=dev) for o in outs]
@@ -1091,7 +1136,7 @@ def main():
                 res["autograd_walk_gpu"] = {"value": B * (Ts - 1) / dtw, "unit": "state-steps/s", "sample": f"{Ts - 1} steps, unrolled PyTorch autograd on the same GPU",
                                             "fused_over_walk": value / (B * (Ts - 1) / dtw)}
         headline = (args.workload, args.method, B, T, w["H"], args.kernel) == ("ode01", "rk4", 4096, 1001, 64, "auto")
-        if world == 1 and dist is None and headline and not args.train and not args.no_extras:
+        if world == 1 and dist is None and headline and not args.train and args.full and not args.no_extras:
             out0 = outs[0]
             del outs
             res["extra"] = [extra_line(lib, _lib, fused, wl, m, dev) for wl, m in EXTRAS]
@@ -1110,7 +1155,7 @@ def main():
                 for wl, m, h in GENERIC_TRAIN_EXTRAS:
                     res["extra"].append(safe_line(f"{wl} {m} TRAIN", lambda: train_extra_line(fused, wl, m, h, dev, steps=3, warmup=2)))
             outs = (out0,)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(w, p_cpu, args.method, gpu_out=None if args.train else outs[0])
             res["cpu_baseline"]["gpu_over_cpu"] = value / res["cpu_baseline"]["value"]
             if "gpu_vs_oracle" in res["cpu_baseline"]:

@@ -19,7 +19,21 @@ TOL_ORACLE = 2e-6       # oracle vs goldens (rel_err): same ATen ops; allows a d
 
 
 def load(name):
-    d = np.load(os.path.join(GOLDEN, name))
+    """A golden set as {key: array}.  A set larger than a committed file may be is stored as <stem>.part0.npz, <stem>.part1.npz, ...
+    (disjoint keys, in order): read whole, or merged from its parts."""
+    path = os.path.join(GOLDEN, name)
+    if not os.path.exists(path):
+        stem = path[:-len(".npz")]
+        parts = []
+        while os.path.exists(f"{stem}.part{len(parts)}.npz"):
+            parts.append(f"{stem}.part{len(parts)}.npz")
+        if parts:
+            out = {}
+            for p in parts:
+                d = np.load(p)
+                out.update({k: d[k] for k in d.files})
+            return out
+    d = np.load(path)
     return {k: d[k] for k in d.files}
 
 

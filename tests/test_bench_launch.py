@@ -60,3 +60,37 @@ def test_multi_gpu_report_keys_and_model():
     assert r2["gather_algo"] == "rccl" and r2["by_algo"] is both
     d = bench.multi_gpu_report(dict(bench.WORKLOADS["dae01"]), 2, 4096, 1001, 5.0, 4.6, None, None, False, None)
     assert d["shard_bytes"] == 1001 * 4096 * (8 + 2) * 4 and "serial_ms" not in d
+
+
+def test_dump_outputs_names_and_seeded_sample(tmp_path):
+    """--dump-outputs (host side): out<k> in float32, the training gradients by layer, and past the size cap the same seeded trajectories
+    from every output, along the batch dimension of its layout."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    w = dict(bench.WORKLOADS["dae01"])
+    B, T = w["B"], w["T"]
+    g = torch.Generator().manual_seed(5)
+    xs, is_ = torch.randn(T, B, 8, generator=g), torch.randn(T, B, 2, generator=g)
+
+    class Tr:
+        layers = [None] * 4
+        params = [torch.full((3, 2), float(k)) for k in range(16)]
+    for k, q in enumerate(Tr.params):
+        q.grad = q + 1
+    bench.dump_outputs(str(tmp_path / "a"), w, (xs, is_), Tr)
+    bench.dump_outputs(str(tmp_path / "b"), w, (xs, is_))
+    a, b = (tmp_path / "a"), (tmp_path / "b")
+    assert sorted(os.listdir(b)) == ["out0.npy", "out1.npy"]
+    assert "grad_de0_weight.npy" in os.listdir(a) and "grad_ae3_bias.npy" in os.listdir(a) and len(os.listdir(a)) == 18
+    assert np.array_equal(np.load(a / "grad_ae0_weight.npy"), np.full((3, 2), 9.0, dtype=np.float32))
+    x0, i0 = np.load(b / "out0.npy"), np.load(b / "out1.npy")
+    assert x0.dtype == np.float32 and x0.nbytes + i0.nbytes <= bench.DUMP_BYTES and x0.shape[1] == i0.shape[1] < B
+    idx = torch.randperm(B, generator=torch.Generator().manual_seed(0))[:x0.shape[1]].sort().values
+    assert np.array_equal(x0, xs[:, idx].numpy()) and np.array_equal(i0, is_[:, idx].numpy())
+    assert np.array_equal(np.load(a / "out0.npy"), x0)
+    m = dict(bench.WORKLOADS["ode02"])                      # model outputs are [B,T,D]: small enough to be written whole
+    y = torch.randn(64, 11, 8, generator=g)
+    m["B"] = 64
+    bench.dump_outputs(str(tmp_path / "c"), m, (y,))
+    assert np.array_equal(np.load(tmp_path / "c" / "out0.npy"), y.numpy())

@@ -95,39 +95,25 @@ def test_resident_batches_feed_the_fused_model(tmp_path):
             assert torch.equal(a, b)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="reference not present (GPU box)")
 @pytest.mark.parametrize("dae", [False, True])
 def test_reference_dataset_class_loads_the_same_tensors(tmp_path, dae):
-    """Build container only: the reference's own ODE_/DAE_Curves_Sample (neural_base.py:10-40,136-166) on the same npz gives
-    the tensors our dataset mirror and the resident copy hold (incl. the seeded num_sample draw and cut_length)."""
+    """The reference's own ODE_/DAE_Curves_Sample (neural_base.py:10-40,136-166) on the same npz gives the tensors our dataset mirror
+    and the resident copy hold (incl. the seeded num_sample draw and cut_length).  What the reference loaded is recorded in
+    tests/golden/g9_dataset_<ode|dae>.npz (tests/golden/make_dataset_fixture.py); the resident copy is also built from a plain object
+    holding those tensors, as it is from the reference's own dataset (duck-typed)."""
     import types
     p = str(tmp_path / "d.npz")
     _write_npz(p, dae=dae, with_mask=dae)
-    saved = {k: v for k, v in sys.modules.items() if k in ("ray", "ray.worker") or k == "neural_dae" or k.startswith("neural_dae.")}
-    for k in list(saved):
-        del sys.modules[k]
-    ray, rw = types.ModuleType("ray"), types.ModuleType("ray.worker")
-    rw.init = lambda *a, **k: None
-    ray.worker = rw
-    sys.modules.update({"ray": ray, "ray.worker": rw})      # neural_base.py:4 imports an unused symbol from ray
-    sys.path.insert(0, "/root/reference")
-    try:
-        import importlib
-        import warnings
-        with warnings.catch_warnings():
-            warnings.simplefilter("ignore")
-            ref_nb = importlib.import_module("neural_dae.neural_base")
-        assert ref_nb.__file__.startswith("/root/reference")
-        ref_ds = (ref_nb.DAE_Curves_Sample if dae else ref_nb.ODE_Curves_Sample)(p, "cpu", num_sample=9, cut_length=10)
-    finally:
-        sys.path.remove("/root/reference")
-        for k in [k for k in sys.modules if k in ("ray", "ray.worker") or k == "neural_dae" or k.startswith("neural_dae.")]:
-            del sys.modules[k]
-        sys.modules.update(saved)
+    g = np.load(os.path.join(ROOT, "tests", "golden", f"g9_dataset_{'dae' if dae else 'ode'}.npz"))
+    fields = datapath.DAE_FIELDS if dae else datapath.ODE_FIELDS
+    ref_ds = types.SimpleNamespace(**{k: torch.from_numpy(g[k]) for k in fields})
     ours = (DAE_Curves_Sample if dae else ODE_Curves_Sample)(p, "cpu", num_sample=9, cut_length=10)
-    res = datapath.ResidentDataset(ref_ds, "cpu")            # duck-typed: accepts the reference's object as it is
-    assert len(ref_ds) == len(ours) == len(res) == 9
+    res = datapath.ResidentDataset(ref_ds, "cpu")
+    assert res.fields == fields
+    assert int(g["length"]) == len(ours) == len(res) == 9
     for k in res.fields:
         assert torch.equal(getattr(ref_ds, k), getattr(ours, k)) and torch.equal(getattr(res, k), getattr(ours, k)), k
-    for a, b in zip(ref_ds[3], ours[3]):
-        assert torch.equal(a, b)
+    item = ours[3]
+    assert len(item) == len([k for k in g.files if k.startswith("item3_")])
+    for j, b in enumerate(item):
+        assert torch.equal(torch.from_numpy(g[f"item3_{j}"]), b)

@@ -8,6 +8,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -17,7 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.parametrize("workload", ["ode01", "dae01"])
 def test_bench_force_dist_runs_the_rccl_path(workload):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--force-dist", "--workload", workload, "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--force-dist", "--full", "--workload", workload, "--steps", "2", "--warmup", "1",
            "--no-cpu-baseline", "--grid", "301", "--batch", "512"]
     if workload == "dae01":
         cmd += ["--gather-layout", "batch"]          # RCCL with the list all_gather into strided views of the final tensors
@@ -57,7 +58,7 @@ def test_bench_force_dist_gather_algorithms_and_loss_only(extra, expect):
     timed by --gather-algo both; and SURVEY 8(e)'s cheaper alternative, the sharded loss with scalar all-reduces only.  World size 1 here
     (the pairs degenerate to the local copy): the code path, the JSON keys and the RCCL group are what is under test."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--force-dist", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--grid", "301",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--force-dist", "--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--grid", "301",
            "--batch", "512"] + extra
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-2000:]
@@ -88,8 +89,8 @@ def test_bench_under_an_external_launcher():
 
 
 def test_default_bench_line_carries_the_extra_workloads():
-    """BASELINE configs 3 / 4 and the scripts' shipped Euler solver ride on the default run's JSON line (reduced grid here)."""
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline"],
+    """BASELINE configs 3 / 4 and the scripts' shipped Euler solver ride on the default workload's --full JSON line (reduced grid here)."""
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-2000:]
     d = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][-1])
@@ -145,3 +146,23 @@ def test_default_bench_line_carries_the_extra_workloads():
     assert all(e["saved_bytes"] > 0 for e in tr)       # every hidden-64 / 128 training step reads saved activations (DAE_01 Euler too since round 4)
     assert [e["roofline"]["bound"] for e in d["extra"][:4]] == ["mfma", "valu_fp32", "mfma", "mfma"]      # K3f issues no MFMA
     assert d["roofline"]["kernel_ms_median"] > 0
+
+
+def test_plain_bench_line_times_the_steps_and_dumps_the_outputs(tmp_path):
+    """A plain run of the default workload measures the headline alone (no cpu_baseline, no extra[]) over exactly --steps steps, and
+    --dump-outputs writes what the last timed step returned: the same arrays on two runs with the same arguments."""
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)],
+                             capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert res.returncode == 0, res.stderr[-2000:]
+        line = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][-1])
+        assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0 and line["unit"] == "state-steps/s"
+        assert line["higher_is_better"] is True and line["dtype"] == "f32" and line["metric"].startswith("integrated state-steps/sec")
+        assert "cpu_baseline" not in line and "extra" not in line
+        assert sorted(os.listdir(d)) == ["out0.npy"]
+        dumps.append(np.load(d / "out0.npy"))
+    a = dumps[0]
+    assert a.dtype == np.float32 and a.shape[0] == 1001 and a.shape[2] == 8 and 0 < a.shape[1] < 4096 and a.nbytes <= 64 * 10 ** 6
+    assert np.isfinite(a).all() and np.array_equal(a, dumps[1])
