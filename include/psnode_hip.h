@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define PSNODE_ABI_VERSION 10
+#define PSNODE_ABI_VERSION 10    /* 10 also carries the additive psnode_act_f32 / *_act_* entry points (end of this file) */
 #define PSNODE_MAX_LAYERS 8      /* Linear layers per MLP */
 #define PSNODE_MAX_WIDTH 1024    /* widest layer OUTPUT the kernels accept */
 #define PSNODE_MAX_IN_WIDTH 2048 /* widest first-layer INPUT (the latent DE of DAE_02 at --hidden 128 is 12 x 128 = 1536 wide) */
@@ -602,6 +602,46 @@ int32_t psnode_dae_save_hidden(const psnode_dae_args_f32* args);
  * one-wave-per-4-trajectories integrators K1x / K2x, hidden <= 64 at up to one wave per SIMD -- PSNODE_KERNEL_MFMA_WAVE. */
 int32_t psnode_ode_kernel_for(const psnode_ode_args_f32* args);
 int32_t psnode_dae_kernel_for(const psnode_dae_args_f32* args);
+
+/* Hidden-layer activations other than ELU(alpha=1) (additive within ABI 10).  The entry points above are the ELU(1) ones; the _act
+ * forms below take one activation per MLP next to the unchanged argument structs.  Every hidden layer of that MLP uses it (the last
+ * Linear has none, as in DE_Func / AE_Func).  Derivatives are taken from the layer OUTPUT h (DESIGN.md "Activations"):
+ *   PSNODE_ACT_ELU         alpha > 0                     x > 0 ? x : alpha (e^x - 1)               h > 0 ? 1 : h + alpha
+ *   PSNODE_ACT_TANH        -                             tanh x                                    1 - h^2
+ *   PSNODE_ACT_SIGMOID     -                             1 / (1 + e^-x)                            h (1 - h)
+ *   PSNODE_ACT_RELU        -                             max(x, 0)                                 h > 0 ? 1 : 0
+ *   PSNODE_ACT_LEAKY_RELU  alpha = negative slope >= 0   x > 0 ? x : alpha x                       h > 0 ? 1 : alpha
+ *   PSNODE_ACT_SOFTPLUS    beta > 0, threshold           beta x > threshold ? x : log1p(e^(beta x)) / beta
+ *                                                                                                  beta h > threshold ? 1 : 1 - e^(-beta h)
+ * Rules of every _act entry point:
+ *   - a NULL act, or ELU with alpha == 1, is ELU(1): the call behaves exactly like the entry point without _act;
+ *   - any other act runs the generic kernels only (K0 forward, K5 backward): `kernel` must be PSNODE_KERNEL_AUTO or _GENERIC (the MFMA
+ *     kinds give PSNODE_ERR_UNSUPPORTED), and so are the training side outputs save_* / saved_* and the teacher-forced backward;
+ *   - an unknown kind gives PSNODE_ERR_METHOD, a parameter outside its range (or not finite) PSNODE_ERR_DIMS.
+ * The _act_supported queries answer 1 / 0 for the same rules (dims only, like the queries without _act); an invalid act is 0.
+ * Workspace sizes are those of the entry points without _act. */
+typedef enum {
+    PSNODE_ACT_ELU = 0, PSNODE_ACT_TANH = 1, PSNODE_ACT_SIGMOID = 2, PSNODE_ACT_RELU = 3, PSNODE_ACT_LEAKY_RELU = 4, PSNODE_ACT_SOFTPLUS = 5
+} psnode_act_kind;
+
+typedef struct {
+    int32_t kind;          /* psnode_act_kind */
+    float alpha;           /* ELU: alpha; LEAKY_RELU: negative slope; otherwise ignored */
+    float beta, threshold; /* SOFTPLUS; otherwise ignored */
+} psnode_act_f32;
+
+int32_t psnode_ode_integrate_act_supported(const psnode_ode_args_f32* args, const psnode_act_f32* de_act);
+int32_t psnode_ode_integrate_act_f32(const psnode_ode_args_f32* args, const psnode_act_f32* de_act, void* workspace, size_t workspace_bytes,
+                                     void* stream);
+int32_t psnode_dae_integrate_act_supported(const psnode_dae_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act);
+int32_t psnode_dae_integrate_act_f32(const psnode_dae_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                     void* workspace, size_t workspace_bytes, void* stream);
+int32_t psnode_ode_backward_act_supported(const psnode_ode_bwd_args_f32* args, const psnode_act_f32* de_act);
+int32_t psnode_ode_backward_act_f32(const psnode_ode_bwd_args_f32* args, const psnode_act_f32* de_act, void* workspace, size_t workspace_bytes,
+                                    void* stream);
+int32_t psnode_dae_backward_act_supported(const psnode_dae_bwd_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act);
+int32_t psnode_dae_backward_act_f32(const psnode_dae_bwd_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                    void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -27,7 +27,9 @@ ABI_VERSION = 10         # == PSNODE_ABI_VERSION of include/psnode_hip.h (2: rou
                          #  9: row addressing (inner rows / outer stride) in psnode_mlp_rows_*, psnode_recon_rows_*, psnode_mlp_rows_reduce_f32 /
                          #     _backward_parts: the row kernels read [B,T,D] batches as time-major rows in place;
                          # 10: psnode_gemm_tn_* / psnode_linear_rows_*: the contraction over rows (K10) and the row-linear layer (K11) that replace library GEMMs; the `kernel` field of
-                         #     psnode_ode_bwd_args_f32 selects K4x (_MFMA_WAVE) / K4f (_MFMA_TILE, _MFMA_WIDE))
+                         #     psnode_ode_bwd_args_f32 selects K4x (_MFMA_WAVE) / K4f (_MFMA_TILE, _MFMA_WIDE);
+                         #     additive, same version: psnode_act_f32 and the psnode_{ode,dae}_{integrate,backward}_act_* entry points --
+                         #     hidden-layer activations other than ELU(1) on the generic kernels K0 / K5)
 LIB_NAME = "libpsnode_hip.so"
 # PSNODE_LIB_PATH lets kernel experiments (profiles/scripts/*) load an alternative build of the same ABI
 LIB_PATH = os.environ.get("PSNODE_LIB_PATH") or os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
@@ -51,6 +53,8 @@ EXPORTS = (
     "psnode_dae_backward_wide_ae_floats",
     "psnode_gemm_tn_supported", "psnode_gemm_tn_workspace_bytes", "psnode_gemm_tn_f32",
     "psnode_linear_rows_supported", "psnode_linear_rows_f32",
+    "psnode_ode_integrate_act_supported", "psnode_ode_integrate_act_f32", "psnode_dae_integrate_act_supported", "psnode_dae_integrate_act_f32",
+    "psnode_ode_backward_act_supported", "psnode_ode_backward_act_f32", "psnode_dae_backward_act_supported", "psnode_dae_backward_act_f32",
 )
 
 
@@ -69,6 +73,14 @@ class UnsupportedShapeError(ValueError):
 class MlpF32(ctypes.Structure):
     _fields_ = [("n_layers", c_int32), ("in_dim", c_int32), ("out_dim", c_int32 * MAX_LAYERS),
                 ("weight", c_void_p * MAX_LAYERS), ("bias", c_void_p * MAX_LAYERS)]
+
+
+class ActF32(ctypes.Structure):
+    """psnode_act_f32: a hidden-layer activation other than ELU(1) (kind = ACT_*)."""
+    _fields_ = [("kind", c_int32), ("alpha", ctypes.c_float), ("beta", ctypes.c_float), ("threshold", ctypes.c_float)]
+
+
+ACT_ELU, ACT_TANH, ACT_SIGMOID, ACT_RELU, ACT_LEAKY_RELU, ACT_SOFTPLUS = 0, 1, 2, 3, 4, 5
 
 
 class ViewF32(ctypes.Structure):
@@ -258,6 +270,13 @@ def load():
     lib.psnode_dae_backward_workspace_bytes.argtypes = [ctypes.POINTER(DaeBwdArgsF32)]
     lib.psnode_dae_backward_f32.restype = c_int32
     lib.psnode_dae_backward_f32.argtypes = [ctypes.POINTER(DaeBwdArgsF32), c_void_p, c_size_t, c_void_p]
+    act_p = ctypes.POINTER(ActF32)
+    for name, args_t, n_act in (("ode_integrate", OdeArgsF32, 1), ("dae_integrate", DaeArgsF32, 2), ("ode_backward", OdeBwdArgsF32, 1),
+                                ("dae_backward", DaeBwdArgsF32, 2)):
+        q = getattr(lib, f"psnode_{name}_act_supported")
+        q.restype, q.argtypes = c_int32, [ctypes.POINTER(args_t)] + [act_p] * n_act
+        f = getattr(lib, f"psnode_{name}_act_f32")
+        f.restype, f.argtypes = c_int32, [ctypes.POINTER(args_t)] + [act_p] * n_act + [c_void_p, c_size_t, c_void_p]
     lib.psnode_mlp_rows_backward_workspace_bytes.restype = c_size_t
     lib.psnode_mlp_rows_backward_workspace_bytes.argtypes = [ctypes.POINTER(MlpF32), c_int64]
     lib.psnode_mlp_rows_backward_f32.restype = c_int32

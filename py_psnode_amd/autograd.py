@@ -36,14 +36,20 @@ def latent_wide_training_fits(method, de, ae, hidden, T, B, dev) -> bool:
     return need <= free // 2
 
 
-def ode_training_supported(method, layers, x_dim, z_dim, T, B, kernel="auto") -> bool:
-    """What the solver asks before it routes a call that needs autograd to the fused forward + backward pair."""
+def ode_training_supported(method, layers, x_dim, z_dim, T, B, kernel="auto", act=None) -> bool:
+    """What the solver asks before it routes a call that needs autograd to the fused forward + backward pair.  act (fused.Act; None =
+    ELU(1)): an activation other than ELU(1) trains on K0 + K5 alone, so K5 answers."""
+    if act is not None:
+        return fused.ode_backward_supported(method, layers, x_dim, z_dim, kernel, act=act)
     if kernel in ("auto", "mfma") and fused.latent_wide_shape(layers, None, x_dim, z_dim):
         return latent_wide_training_fits(method, layers, None, x_dim, T, B, layers[0][0].device)
     return fused.ode_backward_supported(method, layers, x_dim, z_dim, kernel)
 
 
-def dae_training_supported(method, de, ae, x_dim, z_dim, v_dim, i_dim, T, B) -> bool:
+def dae_training_supported(method, de, ae, x_dim, z_dim, v_dim, i_dim, T, B, act=None) -> bool:
+    """act: None (both MLPs ELU(1)) or (de_act, ae_act); an activation other than ELU(1) trains on K0 + K5 alone, so K5 answers."""
+    if act is not None and any(a is not None for a in act):
+        return fused.dae_backward_supported(method, de, ae, x_dim, z_dim, v_dim, i_dim, act=act)
     if fused.latent_wide_shape(de, ae, x_dim, z_dim, v_dim, i_dim):
         return latent_wide_training_fits(method, de, ae, x_dim, T, B, de[0][0].device)
     return fused.dae_backward_supported(method, de, ae, x_dim, z_dim, v_dim, i_dim)
@@ -97,10 +103,21 @@ def _want_saved_dae(method, kernel, de, ae, x_dim, z_dim, v_dim, i_dim, T, B):
 
 class _FusedOde(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, method, kernel, event_idx, t, x0, z, all_initial, z_jump, *params):
+    def forward(ctx, method, kernel, act, event_idx, t, x0, z, all_initial, z_jump, *params):
+        # act: the MLP's activation (fused.Act), None = ELU(1).  A non-tensor argument: `layers` is rebuilt from *params here and in backward
         layers = [(params[k], params[k + 1]) for k in range(0, len(params), 2)]
         global last_saved_bytes
         ctx.x_true = False
+        ctx.act = act
+        if act is not None:      # K0 forward (it saves nothing) + K5 backward; no teacher forcing (the solver walks those calls)
+            if x0.dim() == 3:
+                raise ValueError("teacher-forced training with an activation other than ELU(1) has no fused backward")
+            xs = fused.ode_integrate(method, layers, t, x0.unsqueeze(0), z, all_initial, z_jump=z_jump, event_idx=event_idx, kernel=kernel,
+                                     act=act)
+            last_saved_bytes = 0
+            ctx.method, ctx.bwd_kernel, ctx.has_jump, ctx.has_saved, ctx.event_idx = method, "auto", z_jump is not None, False, event_idx
+            ctx.save_for_backward(t, z, all_initial, xs, *((z_jump,) if z_jump is not None else ()), *params)
+            return xs
         if x0.dim() == 3:        # teacher forcing (my_solvers.py:72-74): x0 is the whole dataset x [T,B,xd]; nothing is saved, K4f recomputes
             x_true = x0.detach().contiguous()
             xs = fused.ode_integrate(method, layers, t, x_true, z, all_initial, z_jump=z_jump, event_idx=event_idx, kernel=kernel,
@@ -148,47 +165,51 @@ class _FusedOde(torch.autograd.Function):
         pos += 1 if ctx.x_true else 0
         params = saved[pos:]
         layers = [(params[k], params[k + 1]) for k in range(0, len(params), 2)]
-        need_z = ctx.needs_input_grad[5]
+        need_z = ctx.needs_input_grad[6]
         if x_true is not None:   # teacher forcing: every step started from a dataset row -- K4f with the dataset as `xs`, no carried adjoint
             gx0, gz, gzj, ga0, gpar = fused.ode_backward(ctx.method, layers, t, z, a0, x_true, grad_xs, event_idx=ctx.event_idx,
                                                          z_jump=z_jump, need_grad_z=need_z, kernel="wide", input_true_x=True)
             if gz is None and need_z:
                 gz = torch.zeros_like(z)
-            return (None, None, None, None, None, gz, ga0, gzj if ctx.needs_input_grad[7] else None, *gpar)   # (no gradient for the dataset x)
+            return (None, None, None, None, None, None, gz, ga0, gzj if ctx.needs_input_grad[8] else None, *gpar)   # (no gradient for the dataset x)
         gx0, gz, gzj, ga0, gpar = fused.ode_backward(ctx.method, layers, t, z, a0, xs, grad_xs, event_idx=ctx.event_idx, z_jump=z_jump,
-                                                     need_grad_z=need_z, saved=acts, need_grad_zj=bool(ctx.needs_input_grad[7]),
-                                                     kernel=ctx.bwd_kernel if acts is not None else "auto")
+                                                     need_grad_z=need_z, saved=acts, need_grad_zj=bool(ctx.needs_input_grad[8]),
+                                                     kernel=ctx.bwd_kernel if acts is not None else "auto", act=ctx.act)
         if gz is None and need_z:
             gz = torch.zeros_like(z)
-        return (None, None, None, None, gx0, gz, ga0, gzj if ctx.needs_input_grad[7] else None, *gpar)
+        return (None, None, None, None, None, gx0, gz, ga0, gzj if ctx.needs_input_grad[8] else None, *gpar)
 
 
 def fused_ode_integrate(method, kernel, layers, t, x, z, all_initial, event_t=None, z_jump=None, check_events=False, input_true_x=False,
-                        x_init=None):
+                        x_init=None, act=None):
     """Differentiable fused integrate_ODE: gradients flow to x[0], z, all_initial, z_jump and the MLP.  input_true_x (teacher forcing,
     my_solvers.py:72-74): every step starts from the dataset row x[k]; gradients flow to z, all_initial, z_jump and the MLP (the dataset
-    x gets none: callers whose x requires grad take the callback walk)."""
+    x gets none: callers whose x requires grad take the callback walk).  act: the MLP's activation (fused.Act), None = ELU(1); any other
+    trains on K0 + K5 (no teacher forcing)."""
     with torch.no_grad():
         event_idx = fused.event_table(t, event_t, check_events)
     if event_idx is None:
         z_jump = None
     params = [p for wb in layers for p in wb]
     x0 = x.detach() if input_true_x else (x[0] if x_init is None else x_init)     # (x_init: integrate_ODE's extension -- no SelectBackward)
-    return _FusedOde.apply(method, kernel, event_idx, t, x0, z, all_initial, z_jump, *params)
+    return _FusedOde.apply(method, kernel, act, event_idx, t, x0, z, all_initial, z_jump, *params)
 
 
 class _FusedDae(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, method, kernel, event_idx, n_de, t, x_init, z, v, i_shape_like, all_initial, z_jump, v_jump, *params):
+    def forward(ctx, method, kernel, act, event_idx, n_de, t, x_init, z, v, i_shape_like, all_initial, z_jump, v_jump, *params):
+        # act: None or (de_act, ae_act), a non-tensor argument (see _FusedOde); with an activation other than ELU(1): K0 + K5, nothing saved
         de = [(params[k], params[k + 1]) for k in range(0, 2 * n_de, 2)]
         ae = [(params[k], params[k + 1]) for k in range(2 * n_de, len(params), 2)]
         T, B = t.shape[0], t.shape[1]
         x_dummy = x_init.new_zeros((1, B, 0))
         if kernel == "generic" and fused.latent_wide_shape(de, ae, x_init.shape[-1], z.shape[-1], v.shape[-1], i_shape_like.shape[-1]):
             kernel = "auto"
-        save = _want_saved_dae(method, kernel, de, ae, x_init.shape[-1], z.shape[-1], v.shape[-1], i_shape_like.shape[-1], T, B)
+        non_elu = act is not None and any(a is not None for a in act)
+        ctx.act = act if non_elu else None
+        save = not non_elu and _want_saved_dae(method, kernel, de, ae, x_init.shape[-1], z.shape[-1], v.shape[-1], i_shape_like.shape[-1], T, B)
         res = fused.dae_integrate(method, de, ae, x_init, t, x_dummy, z, v, i_shape_like, all_initial, z_jump=z_jump, v_jump=v_jump,
-                                  event_idx=event_idx, kernel=kernel, save=save)
+                                  event_idx=event_idx, kernel=kernel, save=save, act=ctx.act)
         xs, is_ = res[0], res[1]
         acts = [q for q in res[2] if q is not None] if save else []
         global last_saved_bytes
@@ -217,11 +238,11 @@ class _FusedDae(torch.autograd.Function):
         de = [(params[q], params[q + 1]) for q in range(0, 2 * ctx.n_de, 2)]
         ae = [(params[q], params[q + 1]) for q in range(2 * ctx.n_de, len(params), 2)]
         g = fused.dae_backward(ctx.method, de, ae, t, z, v, a0, xs, is_, grad_xs, grad_is, event_idx=ctx.event_idx, z_jump=z_jump, v_jump=v_jump,
-                               saved=acts)
-        gz = g["z"] if g["z"] is not None else (torch.zeros_like(z) if ctx.needs_input_grad[6] else None)
-        gv = g["v"] if g["v"] is not None else (torch.zeros_like(v) if ctx.needs_input_grad[7] else None)
-        return (None, None, None, None, None, g["x_init"], gz, gv, None, g["all_initial"],
-                g["z_jump"] if ctx.needs_input_grad[10] else None, g["v_jump"] if ctx.needs_input_grad[11] else None, *g["de"], *g["ae"])
+                               saved=acts, act=ctx.act)
+        gz = g["z"] if g["z"] is not None else (torch.zeros_like(z) if ctx.needs_input_grad[7] else None)
+        gv = g["v"] if g["v"] is not None else (torch.zeros_like(v) if ctx.needs_input_grad[8] else None)
+        return (None, None, None, None, None, None, g["x_init"], gz, gv, None, g["all_initial"],
+                g["z_jump"] if ctx.needs_input_grad[11] else None, g["v_jump"] if ctx.needs_input_grad[12] else None, *g["de"], *g["ae"])
 
 
 class _FusedDaeTeacherForced(torch.autograd.Function):
@@ -261,10 +282,11 @@ class _FusedDaeTeacherForced(torch.autograd.Function):
 
 
 def fused_dae_integrate(method, kernel, de_layers, ae_layers, x_init, t, z, v, i, all_initial, event_t=None, z_jump=None, v_jump=None,
-                        check_events=False, x=None, input_true_x=False, input_true_i=False):
+                        check_events=False, x=None, input_true_x=False, input_true_i=False, act=None):
     """Differentiable fused integrate_DAE: gradients flow to x_init, z, v, all_initial, the jump inputs and both MLPs.  Without teacher
     forcing `i` only provides the width of the algebraic variable.  input_true_x / input_true_i: `x` / `i` are the dataset rows the DE
-    and the heads are fed (my_solvers.py:111-121); they get no gradient."""
+    and the heads are fed (my_solvers.py:111-121); they get no gradient.  act: None or (de_act, ae_act) (fused.Act, None = ELU(1)); an
+    activation other than ELU(1) trains on K0 + K5 (no teacher forcing)."""
     with torch.no_grad():
         event_idx = fused.event_table(t, event_t, check_events)
     if event_idx is None:
@@ -277,4 +299,4 @@ def fused_dae_integrate(method, kernel, de_layers, ae_layers, x_init, t, z, v, i
         xd_ = x.detach() if input_true_x else x_init.new_zeros((1, t.shape[1], 0))
         return _FusedDaeTeacherForced.apply(method, kernel, event_idx, len(de_layers), bool(input_true_x), bool(input_true_i), t, x_init, xd_,
                                             z, v, i.detach(), all_initial, z_jump, v_jump, *params)
-    return _FusedDae.apply(method, kernel, event_idx, len(de_layers), t, x_init, z, v, i.detach(), all_initial, z_jump, v_jump, *params)
+    return _FusedDae.apply(method, kernel, act, event_idx, len(de_layers), t, x_init, z, v, i.detach(), all_initial, z_jump, v_jump, *params)

@@ -1,0 +1,147 @@
+// Hidden-layer activations other than ELU(1) for the generic kernels K0 (psnode_generic.hip) and K5 (psnode_generic_bwd.hip).
+//
+// The ELU(1) kernels of both files do not see any of this: they keep elu_quad / elu_grad_quad (psnode_common.h).  The activation kernels
+// (generic_act_kernel / generic_backward_act_kernel: the same sources compiled a second time, psnode_generic_act.hip /
+// psnode_generic_bwd_act.hip) take an ActDev per MLP as a kernel argument and switch on its kind, which is uniform over the launch
+// (scalar branches, no divergence).
+//
+// Every listed activation has a derivative that is a function of the layer OUTPUT h (K5 rebuilds and keeps layer outputs, not
+// pre-activations):
+//   ELU(alpha)              x > 0 ? x : alpha (e^x - 1)                          h > 0 ? 1 : h + alpha
+//   Tanh                    tanh x                                               1 - h^2
+//   Sigmoid                 1 / (1 + e^-x)                                       h (1 - h)
+//   ReLU                    max(x, 0)                                            h > 0 ? 1 : 0        (torch's rule at 0)
+//   LeakyReLU(s), s >= 0    x > 0 ? x : s x                                      h > 0 ? 1 : s
+//   Softplus(beta, thr)     beta x > thr ? x : log(1 + e^(beta x)) / beta        beta h > thr ? 1 : 1 - e^(-beta h)
+// Accuracy (DESIGN.md "Activations"): the exponentials go through v_exp_f32 (exp2, 1 ulp), the reciprocals through v_rcp_f32 (1 ulp),
+// the logarithm through v_log_f32.  Each value carries an ABSOLUTE error of about 1e-7, the same budget as the round-3 ELU form that the
+// ELU(1) kernels ship (psnode_common.h).
+#pragma once
+#include "psnode_common.h"
+
+namespace psnode {
+
+struct ActDev {
+    int kind;          // psnode_act_kind
+    float alpha;       // ELU: alpha, LeakyReLU: negative slope
+    float beta, thr;   // Softplus
+    float ibeta;       // Softplus: 1 / beta
+};
+struct ActPair {
+    ActDev de, ae;
+};
+
+constexpr float kLn2 = 0.693147180559945309f;
+
+__device__ __forceinline__ float act_exp(float x) { return __builtin_amdgcn_exp2f(x * kLog2e); }
+
+// one value; `a.kind` is uniform
+__device__ __forceinline__ float act1(float x, const ActDev& a) {
+    switch (a.kind) {
+        case PSNODE_ACT_ELU: {
+            // max(x, 0) + alpha (clamp(e^x, 0, 1) - 1): for x > 0 the exponential side is alpha (1 - 1) = 0 exactly (as elu_quad)
+            const float t = __builtin_amdgcn_fmed3f(act_exp(x), 0.0f, 1.0f);
+            return fmaxf(x, 0.0f) + a.alpha * (t - 1.0f);
+        }
+        case PSNODE_ACT_TANH: {
+            // tanh |x| = (1 - t) / (1 + t), t = e^(-2|x|) in (0, 1]: 1 - t is exact for t >= 0.5 (Sterbenz), no overflow for any x
+            const float t = __builtin_amdgcn_exp2f(-2.0f * kLog2e * fabsf(x));
+            return copysignf((1.0f - t) * __builtin_amdgcn_rcpf(1.0f + t), x);
+        }
+        case PSNODE_ACT_SIGMOID:
+            return __builtin_amdgcn_rcpf(1.0f + act_exp(-x));      // e^-x = inf -> rcp(inf) = 0
+        case PSNODE_ACT_RELU:
+            return fmaxf(x, 0.0f);
+        case PSNODE_ACT_LEAKY_RELU:
+            return x > 0.0f ? x : x * a.alpha;
+        default: {      // PSNODE_ACT_SOFTPLUS
+            const float y = x * a.beta;
+            // log1p(t) = log(u) t / (u - 1), u = 1 + t (exact where u rounds to 1: then log1p(t) = t to fp32 precision)
+            const float t = act_exp(y), u = 1.0f + t;
+            const float l1p = u == 1.0f ? t : __builtin_amdgcn_logf(u) * kLn2 * (t * __builtin_amdgcn_rcpf(u - 1.0f));
+            return (y > a.thr || y > 80.0f) ? x : l1p * a.ibeta;     // (y > 80: e^y overflows; the limit is x)
+        }
+    }
+}
+
+typedef float act_f4 __attribute__((ext_vector_type(4)));
+// the quad forms branch ONCE on the kind (K0 runs one wave per SIMD: nothing hides a taken branch, DESIGN.md "Activations")
+template <int KIND>
+__device__ __forceinline__ act_f4 act_quad_k(const act_f4 v, const ActDev& a) {
+    ActDev k = a;
+    k.kind = KIND;
+    return act_f4{act1(v[0], k), act1(v[1], k), act1(v[2], k), act1(v[3], k)};
+}
+__device__ __forceinline__ act_f4 act_quad(const act_f4 v, const ActDev& a) {
+    switch (a.kind) {
+        case PSNODE_ACT_ELU: return act_quad_k<PSNODE_ACT_ELU>(v, a);
+        case PSNODE_ACT_TANH: return act_quad_k<PSNODE_ACT_TANH>(v, a);
+        case PSNODE_ACT_SIGMOID: return act_quad_k<PSNODE_ACT_SIGMOID>(v, a);
+        case PSNODE_ACT_RELU: return act_quad_k<PSNODE_ACT_RELU>(v, a);
+        case PSNODE_ACT_LEAKY_RELU: return act_quad_k<PSNODE_ACT_LEAKY_RELU>(v, a);
+        default: return act_quad_k<PSNODE_ACT_SOFTPLUS>(v, a);
+    }
+}
+
+// d act / d pre-activation, from the output h
+__device__ __forceinline__ float act_grad1(float h, const ActDev& a) {
+    switch (a.kind) {
+        case PSNODE_ACT_ELU: return h > 0.0f ? 1.0f : h + a.alpha;
+        case PSNODE_ACT_TANH: return 1.0f - h * h;
+        case PSNODE_ACT_SIGMOID: return h * (1.0f - h);
+        case PSNODE_ACT_RELU: return h > 0.0f ? 1.0f : 0.0f;
+        case PSNODE_ACT_LEAKY_RELU: return h > 0.0f ? 1.0f : a.alpha;
+        default: {      // PSNODE_ACT_SOFTPLUS
+            const float y = h * a.beta;
+            return y > a.thr ? 1.0f : 1.0f - act_exp(-y);
+        }
+    }
+}
+template <int KIND>
+__device__ __forceinline__ act_f4 act_grad_quad_k(const act_f4 h, const ActDev& a) {
+    ActDev k = a;
+    k.kind = KIND;
+    return act_f4{act_grad1(h[0], k), act_grad1(h[1], k), act_grad1(h[2], k), act_grad1(h[3], k)};
+}
+__device__ __forceinline__ act_f4 act_grad_quad(const act_f4 h, const ActDev& a) {
+    switch (a.kind) {
+        case PSNODE_ACT_ELU: return act_grad_quad_k<PSNODE_ACT_ELU>(h, a);
+        case PSNODE_ACT_TANH: return act_grad_quad_k<PSNODE_ACT_TANH>(h, a);
+        case PSNODE_ACT_SIGMOID: return act_grad_quad_k<PSNODE_ACT_SIGMOID>(h, a);
+        case PSNODE_ACT_RELU: return act_grad_quad_k<PSNODE_ACT_RELU>(h, a);
+        case PSNODE_ACT_LEAKY_RELU: return act_grad_quad_k<PSNODE_ACT_LEAKY_RELU>(h, a);
+        default: return act_grad_quad_k<PSNODE_ACT_SOFTPLUS>(h, a);
+    }
+}
+
+// wave-uniform copy (the kind drives scalar branches; selects between the DE's and the AE's act stay scalar)
+__device__ __forceinline__ ActDev act_pick(bool first, const ActDev& x, const ActDev& y) {
+    auto u = [](float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); };
+    ActDev r;
+    r.kind = __builtin_amdgcn_readfirstlane(first ? x.kind : y.kind);
+    r.alpha = u(first ? x.alpha : y.alpha);
+    r.beta = u(first ? x.beta : y.beta);
+    r.thr = u(first ? x.thr : y.thr);
+    r.ibeta = u(first ? x.ibeta : y.ibeta);
+    return r;
+}
+
+// psnode_capi.hip: validates a psnode_act_f32 and converts it (NULL = ELU(1)).  Returns PSNODE_OK / PSNODE_ERR_*; `is_elu1` = the
+// existing ELU(1) routes apply.
+int act_from_abi(const psnode_act_f32* in, ActDev& out, bool& is_elu1);
+
+// psnode_generic.hip: K0's launch planning, shared by both builds
+size_t generic_plan(const IntegrateDev& a, bool dae, unsigned& mask);
+int generic_reg_mode(const IntegrateDev& a, bool dae);
+bool generic_wide_mode(const IntegrateDev& a, bool dae);
+// psnode_generic_act.hip: K0 with the activations of `act` (the ELU(1) call is launch_generic)
+hipError_t launch_generic_act(const IntegrateDev& a, bool dae, const ActPair& act, hipStream_t stream);
+// psnode_generic_bwd_act.hip: K5 with the activations of `act` (the ELU(1) call is generic_backward_launch)
+int generic_backward_launch_act(const ActPair& act, int method, int xd, int zd, int vd, int id, long long T, long long B,
+                                const psnode_mlp_f32* de, const psnode_mlp_f32* ae, ViewDev t, ViewDev z, ViewDev v, const float* a0,
+                                const int* ev, const float* zj, long long zjb, long long zje, const float* vj, long long vjb, long long vje,
+                                int n_events, const float* xs, const float* is_, const float* gxs, const float* gis, float* gx0, float* gz,
+                                float* gv, float* gzj, float* gvj, float* ga0, float* gparams_de, float* gparams_ae, float* workspace,
+                                hipStream_t stream);
+
+}  // namespace psnode

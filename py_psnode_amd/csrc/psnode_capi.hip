@@ -1,9 +1,10 @@
 // C ABI of libpsnode_hip.so (see include/psnode_hip.h): argument validation, workspace carving,
 // weight packing and kernel dispatch.  Everything is enqueued on the caller's stream.
+#include <math.h>
 #include <stdio.h>
 #include <string.h>
 
-#include "psnode_common.h"
+#include "psnode_act.h"
 
 namespace psnode {
 namespace {
@@ -76,8 +77,9 @@ __global__ void event_table_kernel(long long n_steps, const float* clock, long l
 
 ViewDev view(const psnode_view_f32& v) { return ViewDev{v.ptr, v.stride_t, v.stride_b}; }
 
+// act: the hidden layers' activations of a non-ELU(1) call (K0 only), or nullptr
 int dispatch(IntegrateDev& d, bool dae, int kernel, const psnode_mlp_f32* de, const psnode_mlp_f32* ae, void* workspace,
-             size_t workspace_bytes, hipStream_t stream) {
+             size_t workspace_bytes, hipStream_t stream, const ActPair* act = nullptr) {
     if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 255u)) return PSNODE_ERR_WORKSPACE;
     if (workspace_bytes < psnode_workspace_bytes(de, ae)) return PSNODE_ERR_WORKSPACE;
     float* ws = static_cast<float*>(workspace);
@@ -89,7 +91,7 @@ int dispatch(IntegrateDev& d, bool dae, int kernel, const psnode_mlp_f32* de, co
     for (int l = 0; l < de->n_layers; ++l) d.maxo = de->out_dim[l] > d.maxo ? de->out_dim[l] : d.maxo;
     if (dae) for (int l = 0; l < ae->n_layers; ++l) d.maxo = ae->out_dim[l] > d.maxo ? ae->out_dim[l] : d.maxo;
 
-    const bool has_mfma = dae ? mfma_dae_supported(d) : mfma_ode_supported(d);
+    const bool has_mfma = !act && (dae ? mfma_dae_supported(d) : mfma_ode_supported(d));
     const bool want_mfma = kernel == PSNODE_KERNEL_MFMA || kernel == PSNODE_KERNEL_MFMA_TILE || kernel == PSNODE_KERNEL_MFMA_WAVE;
     if (want_mfma && !has_mfma) return PSNODE_ERR_UNSUPPORTED;
     if (kernel == PSNODE_KERNEL_MFMA_WAVE && !(dae ? mfma_x_dae_supported(d) : mfma_x_ode_supported(d))) return PSNODE_ERR_UNSUPPORTED;
@@ -103,7 +105,7 @@ int dispatch(IntegrateDev& d, bool dae, int kernel, const psnode_mlp_f32* de, co
     } else {
         if (generic_lds_bytes(d, dae) > 160 * 1024) return PSNODE_ERR_UNSUPPORTED;
         e = launch_pack_image(d.de, dae ? &d.ae : nullptr, d.xd, d.xd + d.zd + (dae ? d.vd + d.id : 0), d.zd + (dae ? d.vd : 0), stream);
-        if (e == hipSuccess) e = launch_generic(d, dae, stream);
+        if (e == hipSuccess) e = act ? launch_generic_act(d, dae, *act, stream) : launch_generic(d, dae, stream);
     }
     return e == hipSuccess ? PSNODE_OK : PSNODE_ERR_HIP;
 }
@@ -190,6 +192,20 @@ int fill_dae(const psnode_dae_args_f32* a, IntegrateDev& d) {
     return PSNODE_OK;
 }
 
+// the two activations of an _act call; `elu1`: both are ELU(1), the call takes the entry point without _act
+int act_pair(const psnode_act_f32* de, const psnode_act_f32* ae, ActPair& p, bool& elu1) {
+    bool e_de = true, e_ae = true;
+    int rc = act_from_abi(de, p.de, e_de);
+    if (rc == PSNODE_OK) rc = act_from_abi(ae, p.ae, e_ae);
+    elu1 = e_de && e_ae;
+    return rc;
+}
+
+// what a non-ELU(1) act asks of the call besides the dims: K0 (AUTO / GENERIC), no training side outputs
+bool act_call_ok(int kernel, const void* save_act) {
+    return (kernel == PSNODE_KERNEL_AUTO || kernel == PSNODE_KERNEL_GENERIC) && !save_act;
+}
+
 // dims-only view of the args for the *_kernel_for queries (pointers unused)
 void bind_dims(const psnode_mlp_f32& m, MlpDev& d) {
     d.n_layers = m.n_layers;
@@ -198,6 +214,35 @@ void bind_dims(const psnode_mlp_f32& m, MlpDev& d) {
 }
 
 }  // namespace
+
+int act_from_abi(const psnode_act_f32* in, ActDev& out, bool& is_elu1) {
+    out = ActDev{PSNODE_ACT_ELU, 1.0f, 1.0f, 20.0f, 1.0f};
+    is_elu1 = true;
+    if (!in) return PSNODE_OK;
+    if (in->kind < PSNODE_ACT_ELU || in->kind > PSNODE_ACT_SOFTPLUS) return PSNODE_ERR_METHOD;
+    out.kind = in->kind;
+    out.alpha = 0.0f;
+    switch (in->kind) {
+        case PSNODE_ACT_ELU:
+            if (!isfinite(in->alpha) || !(in->alpha > 0.0f)) return PSNODE_ERR_DIMS;
+            out.alpha = in->alpha;
+            break;
+        case PSNODE_ACT_LEAKY_RELU:
+            if (!isfinite(in->alpha) || !(in->alpha >= 0.0f)) return PSNODE_ERR_DIMS;
+            out.alpha = in->alpha;
+            break;
+        case PSNODE_ACT_SOFTPLUS:
+            if (!isfinite(in->beta) || !(in->beta > 0.0f) || !isfinite(in->threshold)) return PSNODE_ERR_DIMS;
+            out.beta = in->beta;
+            out.thr = in->threshold;
+            out.ibeta = 1.0f / in->beta;
+            break;
+        default: break;
+    }
+    is_elu1 = in->kind == PSNODE_ACT_ELU && in->alpha == 1.0f;
+    return PSNODE_OK;
+}
+
 }  // namespace psnode
 
 using namespace psnode;
@@ -282,6 +327,80 @@ int32_t psnode_dae_integrate_f32(const psnode_dae_args_f32* args, void* workspac
         if (args->kernel == PSNODE_KERNEL_GENERIC || !mfma_dae_save_hidden(q)) return PSNODE_ERR_UNSUPPORTED;
     }
     return dispatch(d, true, args->kernel, &args->de, &args->ae, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+}
+
+int32_t psnode_ode_integrate_act_supported(const psnode_ode_args_f32* a, const psnode_act_f32* de_act) {
+    ActPair p;
+    bool elu1 = true;
+    if (!a || act_pair(de_act, nullptr, p, elu1)) return 0;
+    if (a->method < PSNODE_EULER || a->method > PSNODE_RK4_38 || a->x_dim < 1 || a->z_dim < 0) return 0;
+    const psnode_mlp_f32& m = a->de;
+    if (m.n_layers < 1 || m.n_layers > kMaxLayers || m.in_dim != 3 * (a->x_dim + a->z_dim) || m.in_dim > PSNODE_MAX_IN_WIDTH) return 0;
+    for (int l = 0; l < m.n_layers; ++l) if (m.out_dim[l] < 1 || m.out_dim[l] > PSNODE_MAX_WIDTH) return 0;
+    if (m.out_dim[m.n_layers - 1] != a->x_dim) return 0;
+    if (elu1) return 1;
+    if (!act_call_ok(a->kernel, a->save_act)) return 0;
+    IntegrateDev d;
+    memset(&d, 0, sizeof(d));
+    d.xd = a->x_dim; d.zd = a->z_dim;
+    bind_dims(m, d.de);
+    d.maxo = 1;
+    for (int l = 0; l < m.n_layers; ++l) d.maxo = m.out_dim[l] > d.maxo ? m.out_dim[l] : d.maxo;
+    return generic_lds_bytes(d, false) <= 160 * 1024;
+}
+
+int32_t psnode_ode_integrate_act_f32(const psnode_ode_args_f32* args, const psnode_act_f32* de_act, void* workspace, size_t workspace_bytes,
+                                     void* stream) {
+    ActPair p;
+    bool elu1 = true;
+    int rc = act_pair(de_act, nullptr, p, elu1);
+    if (rc) return rc;
+    if (elu1) return psnode_ode_integrate_f32(args, workspace, workspace_bytes, stream);
+    if (args && !act_call_ok(args->kernel, args->save_act)) return PSNODE_ERR_UNSUPPORTED;      // K0 only
+    IntegrateDev d;
+    rc = fill_ode(args, d);
+    if (rc) return rc;
+    return dispatch(d, false, args->kernel, &args->de, nullptr, workspace, workspace_bytes, static_cast<hipStream_t>(stream), &p);
+}
+
+int32_t psnode_dae_integrate_act_supported(const psnode_dae_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act) {
+    ActPair p;
+    bool elu1 = true;
+    if (!a || act_pair(de_act, ae_act, p, elu1)) return 0;
+    if (a->method < PSNODE_EULER || a->method > PSNODE_RK4_38 || a->x_dim < 1 || a->z_dim < 0 || a->v_dim < 0 || a->i_dim < 1) return 0;
+    const int n = a->x_dim + a->z_dim + a->v_dim + a->i_dim;
+    IntegrateDev d;
+    memset(&d, 0, sizeof(d));
+    d.xd = a->x_dim; d.zd = a->z_dim; d.vd = a->v_dim; d.id = a->i_dim;
+    d.maxo = 1;
+    for (int k = 0; k < 2; ++k) {
+        const psnode_mlp_f32& m = k ? a->ae : a->de;
+        const int want_in = k ? n + a->x_dim + a->z_dim + a->v_dim : 3 * n, want_out = k ? a->i_dim : a->x_dim;
+        if (m.n_layers < 1 || m.n_layers > kMaxLayers || m.in_dim != want_in || m.in_dim > PSNODE_MAX_IN_WIDTH) return 0;
+        for (int l = 0; l < m.n_layers; ++l) {
+            if (m.out_dim[l] < 1 || m.out_dim[l] > PSNODE_MAX_WIDTH) return 0;
+            d.maxo = m.out_dim[l] > d.maxo ? m.out_dim[l] : d.maxo;
+        }
+        if (m.out_dim[m.n_layers - 1] != want_out) return 0;
+        bind_dims(m, k ? d.ae : d.de);
+    }
+    if (elu1) return 1;
+    if (!act_call_ok(a->kernel, a->save_act)) return 0;
+    return generic_lds_bytes(d, true) <= 160 * 1024;
+}
+
+int32_t psnode_dae_integrate_act_f32(const psnode_dae_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                     void* workspace, size_t workspace_bytes, void* stream) {
+    ActPair p;
+    bool elu1 = true;
+    int rc = act_pair(de_act, ae_act, p, elu1);
+    if (rc) return rc;
+    if (elu1) return psnode_dae_integrate_f32(args, workspace, workspace_bytes, stream);
+    if (args && !act_call_ok(args->kernel, args->save_act)) return PSNODE_ERR_UNSUPPORTED;      // K0 only
+    IntegrateDev d;
+    rc = fill_dae(args, d);
+    if (rc) return rc;
+    return dispatch(d, true, args->kernel, &args->de, &args->ae, workspace, workspace_bytes, static_cast<hipStream_t>(stream), &p);
 }
 
 int32_t psnode_ode_kernel_for(const psnode_ode_args_f32* a) {

@@ -26,6 +26,25 @@
 // hidden layer's pad units come out of the MFMA as ELU(0 + 0) = 0.
 #include "psnode_common.h"
 
+// Activation build: psnode_generic_act.hip compiles this file once more with PSNODE_K0_ACT_BUILD defined.  Its kernels
+// (generic_act_kernel) take the DE's and the AE's activation as a second kernel argument (psnode_act.h) and apply it wherever these
+// kernels apply ELU(1); its launcher is launch_generic_act.  Without the macro the tokens below expand to exactly the ELU(1) source, so
+// the ELU(1) kernels compile to the instruction stream they always had.
+#ifdef PSNODE_K0_ACT_BUILD
+#include "psnode_act.h"
+#define K0_ACT(v) act_quad(v, ac)
+#define K0_ACT_PARAM , const ActDev& ac
+#define K0_ACT_ARG(x) , x
+#define K0_KERNEL generic_act_kernel
+#define K0_KERNEL_PARAMS const IntegrateDev a, const ActPair act
+#else
+#define K0_ACT(v) elu_quad(v)
+#define K0_ACT_PARAM
+#define K0_ACT_ARG(x)
+#define K0_KERNEL generic_kernel
+#define K0_KERNEL_PARAMS const IntegrateDev a
+#endif
+
 namespace psnode {
 
 namespace {
@@ -225,7 +244,7 @@ __device__ __forceinline__ f4 tile_any(int S4, const f4* at, const f4* bq, const
 // MLP over the TB columns: layer 0 reads the quad-row buffer at float offset `in`, the layers write `ping` / `pong` alternately; returns
 // the offset of the last layer's output.  Ends with a barrier.  `nx`: the MLP evaluated after this one.
 template <bool STREAM, int ML>
-__device__ __forceinline__ int mlp_eval(const Tab<ML>& T, float* lds, int in, const int ping, const int pong, Pref& pf, const Tab<ML>& nx) {
+__device__ __forceinline__ int mlp_eval(const Tab<ML>& T, float* lds, int in, const int ping, const int pong, Pref& pf, const Tab<ML>& nx K0_ACT_PARAM) {
     const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     // STREAM: chunk = quads q0 .. q0 + 3 of one tile, clamped inside the tile's run of the image (in bounds, unused beyond the tile's quads).
     // The address comes out of scalar selects and the four loads are unconditional straight-line code: a load inside a conditional block
@@ -262,7 +281,7 @@ __device__ __forceinline__ int mlp_eval(const Tab<ML>& T, float* lds, int in, co
         f4* oq = reinterpret_cast<f4*>(lds + out) + lane;
         auto finish = [&](f4 acc, const f4 bias, int nt) {
             acc = acc + bias;
-            const f4 e = PSNODE_K0_ABL != 2 ? elu_quad(acc) : acc;
+            const f4 e = PSNODE_K0_ABL != 2 ? K0_ACT(acc) : acc;
             oq[nt * 64] = last ? acc : e;         // a select, not a branch
         };
         if (!STREAM || tab_res(T.dims[l])) {
@@ -426,7 +445,7 @@ __device__ __forceinline__ f4 tile_reg_any(int S4, const f4* bq, const f4 (&wa)[
 
 // c0: fold0 of this wave's tile of layer 0 (bias included)
 template <int ML, int QM>
-__device__ __forceinline__ int mlp_reg(const Tab<ML>& T, float* lds, int in, const int ping, const int pong, const WReg<ML, QM>& wr, const f4 c0) {
+__device__ __forceinline__ int mlp_reg(const Tab<ML>& T, float* lds, int in, const int ping, const int pong, const WReg<ML, QM>& wr, const f4 c0 K0_ACT_PARAM) {
     const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     int out = ping;
 #pragma unroll
@@ -441,7 +460,7 @@ __device__ __forceinline__ int mlp_reg(const Tab<ML>& T, float* lds, int in, con
             f4 acc;
             if (l == 0) acc = tile_reg_any<QM>(T.qx, bq, wr.first) + c0;
             else acc = tile_reg_any<4>(S4, bq, wr.rest[l ? l - 1 : 0]) + bias;
-            const f4 e = elu_quad(acc);
+            const f4 e = K0_ACT(acc);
             reinterpret_cast<f4*>(lds + out)[w * 64 + lane] = last ? acc : e;
         }
         lds_barrier();
@@ -517,7 +536,7 @@ __device__ __forceinline__ void tile2_any(int S4, const f4* bq, const f4 (&wa)[8
 // c0a / c0b: fold0 of the wave's two tiles of layer 0 (bias included)
 template <int ML>
 __device__ __forceinline__ int mlp_regw(const Tab<ML>& T, float* lds, int in, const int ping, const int pong, const WRegW<ML>& wr, const f4 c0a,
-                                        const f4 c0b) {
+                                        const f4 c0b K0_ACT_PARAM) {
     const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     int out = ping;
 #pragma unroll
@@ -542,8 +561,8 @@ __device__ __forceinline__ int mlp_regw(const Tab<ML>& T, float* lds, int in, co
                 if (two) tile2_any<true>(S4, bq, wr.mid[mi][0], wr.mid[mi][1], ra, rb); else tile2_any<false>(S4, bq, wr.mid[mi][0], wr.mid[mi][0], ra, rb);
             }
             ra = ra + (l ? bias0 : c0a);
-            oq[w * 64] = last ? ra : elu_quad(ra);
-            if (two) { rb = rb + (l ? bias1 : c0b); oq[(w + 4) * 64] = elu_quad(rb); }
+            oq[w * 64] = last ? ra : K0_ACT(ra);
+            if (two) { rb = rb + (l ? bias1 : c0b); oq[(w + 4) * 64] = K0_ACT(rb); }
         }
         lds_barrier();
         in = out;
@@ -557,7 +576,7 @@ constexpr int PF = 4;
 // MODE 0: weights in registers (mlp_reg; QM = 4 or 8 quads per tile), 1: every image resident in LDS, 2: some layers streamed,
 // 3: the DE in the wide register form (mlp_regw)
 template <bool DAE, int MODE, int ML, int QM = 4>
-__global__ __launch_bounds__(NT) void generic_kernel(const IntegrateDev a) {
+__global__ __launch_bounds__(NT) void K0_KERNEL(K0_KERNEL_PARAMS) {
     constexpr bool STREAM = MODE == 2;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x;
@@ -732,13 +751,14 @@ __global__ __launch_bounds__(NT) void generic_kernel(const IntegrateDev a) {
                 }
             }
             if constexpr (MODE == 3) {
-                f = mlp_regw<ML>(tde, lds, inDE, ping, pong, wdw, cde, cde2);
+                f = mlp_regw<ML>(tde, lds, inDE, ping, pong, wdw, cde, cde2 K0_ACT_ARG(act.de));
             } else if constexpr (MODE == 0) {      // two call sites: the operands are two different register sets
-                if (is_ae) { if constexpr (DAE) f = mlp_reg<ML, QM>(tae, lds, inAE, ping, pong, wae, cae); else f = ping; }
-                else f = mlp_reg<ML, QM>(tde, lds, inDE, ping, pong, wde, cde);
+                if (is_ae) { if constexpr (DAE) f = mlp_reg<ML, QM>(tae, lds, inAE, ping, pong, wae, cae K0_ACT_ARG(act.ae)); else f = ping; }
+                else f = mlp_reg<ML, QM>(tde, lds, inDE, ping, pong, wde, cde K0_ACT_ARG(act.de));
             } else {
-                f = DAE ? mlp_eval<STREAM, ML>(pick_tab(is_ae, tae, tde), lds, is_ae ? inAE : inDE, ping, pong, pf, pick_tab(ae_next, tae, tde))
-                        : mlp_eval<STREAM, ML>(tde, lds, inDE, ping, pong, pf, tde);
+                f = DAE ? mlp_eval<STREAM, ML>(pick_tab(is_ae, tae, tde), lds, is_ae ? inAE : inDE, ping, pong, pf, pick_tab(ae_next, tae, tde)
+                                               K0_ACT_ARG(act_pick(is_ae, act.ae, act.de)))
+                        : mlp_eval<STREAM, ML>(tde, lds, inDE, ping, pong, pf, tde K0_ACT_ARG(act.de));
             }
             K0_PROF(2)
             if (is_ae) {
@@ -814,6 +834,7 @@ __global__ __launch_bounds__(NT) void generic_kernel(const IntegrateDev a) {
 
 }  // namespace
 
+#ifndef PSNODE_K0_ACT_BUILD
 namespace {
 struct PackArgs {
     int n;                       // layers in total (de then ae)
@@ -1004,7 +1025,13 @@ size_t generic_plan(const IntegrateDev& a, bool dae, unsigned& mask) {
     return bytes;
 }
 
+#endif  // PSNODE_K0_ACT_BUILD
+
+#ifdef PSNODE_K0_ACT_BUILD
+hipError_t launch_generic_act(const IntegrateDev& a_in, bool dae, const ActPair& act, hipStream_t stream_) {
+#else
 hipError_t launch_generic(const IntegrateDev& a_in, bool dae, hipStream_t stream_) {
+#endif
     IntegrateDev a = a_in;
     const size_t lds = generic_plan(a, dae, a.k0_res);
     const unsigned grid = (unsigned)((a.B + TB - 1) / TB);
@@ -1019,21 +1046,21 @@ hipError_t launch_generic(const IntegrateDev& a_in, bool dae, hipStream_t stream
     auto go = [&](auto kern) -> hipError_t {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_launch);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), lds_launch, stream_, a);
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), lds_launch, stream_, a K0_ACT_ARG(act));
         return hipGetLastError();
     };
     const int qm = generic_reg_mode(a, dae);
     const bool deep = a.de.n_layers > 4 || (dae && a.ae.n_layers > 4);      // the layer loop is unrolled 4 or kMaxLayers times
-    if (qm && deep) return qm == 4 ? go(&generic_kernel<false, 0, kMaxLayers, 4>) : go(&generic_kernel<false, 0, kMaxLayers, 8>);
-    if (qm == 4) return dae ? go(&generic_kernel<true, 0, 4, 4>) : go(&generic_kernel<false, 0, 4, 4>);
-    if (qm == 8) return dae ? go(&generic_kernel<true, 0, 4, 8>) : go(&generic_kernel<false, 0, 4, 8>);
-    if (generic_wide_mode(a, dae)) return go(&generic_kernel<false, 3, 4>);
+    if (qm && deep) return qm == 4 ? go(&K0_KERNEL<false, 0, kMaxLayers, 4>) : go(&K0_KERNEL<false, 0, kMaxLayers, 8>);
+    if (qm == 4) return dae ? go(&K0_KERNEL<true, 0, 4, 4>) : go(&K0_KERNEL<false, 0, 4, 4>);
+    if (qm == 8) return dae ? go(&K0_KERNEL<true, 0, 4, 8>) : go(&K0_KERNEL<false, 0, 4, 8>);
+    if (generic_wide_mode(a, dae)) return go(&K0_KERNEL<false, 3, 4>);
     if (deep) {
-        if (dae) return stream ? go(&generic_kernel<true, 2, kMaxLayers>) : go(&generic_kernel<true, 1, kMaxLayers>);
-        return stream ? go(&generic_kernel<false, 2, kMaxLayers>) : go(&generic_kernel<false, 1, kMaxLayers>);
+        if (dae) return stream ? go(&K0_KERNEL<true, 2, kMaxLayers>) : go(&K0_KERNEL<true, 1, kMaxLayers>);
+        return stream ? go(&K0_KERNEL<false, 2, kMaxLayers>) : go(&K0_KERNEL<false, 1, kMaxLayers>);
     }
-    if (dae) return stream ? go(&generic_kernel<true, 2, 4>) : go(&generic_kernel<true, 1, 4>);
-    return stream ? go(&generic_kernel<false, 2, 4>) : go(&generic_kernel<false, 1, 4>);
+    if (dae) return stream ? go(&K0_KERNEL<true, 2, 4>) : go(&K0_KERNEL<true, 1, 4>);
+    return stream ? go(&K0_KERNEL<false, 2, 4>) : go(&K0_KERNEL<false, 1, 4>);
 }
 
 }  // namespace psnode

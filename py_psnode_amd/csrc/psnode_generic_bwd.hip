@@ -16,6 +16,31 @@
 
 #include "psnode_common.h"
 
+// Activation build: psnode_generic_bwd_act.hip compiles this file once more with PSNODE_K5_ACT_BUILD defined.  Its kernels
+// (generic_backward_act_kernel) take the DE's and the AE's activation as a second kernel argument (psnode_act.h) and use it wherever these
+// kernels use ELU(1) and its derivative; its launcher is generic_backward_launch_act.  Without the macro the tokens below expand to exactly
+// the ELU(1) source, so the ELU(1) kernels compile to the instruction stream they always had.
+#ifdef PSNODE_K5_ACT_BUILD
+#include "psnode_act.h"
+#define K5_ACT1(v) act1(v, ac)
+#define K5_DACT1(h) act_grad1(h, ac)
+#define K5_ACTQ(v) act_quad(v, ac)
+#define K5_DACTQ(h) act_grad_quad(h, ac)
+#define K5_ACT_PARAM , const ActDev& ac
+#define K5_ACT_ARG(x) , x
+#define K5_KERNEL generic_backward_act_kernel
+#define K5_KERNEL_PARAMS const GBwd a, const ActPair act
+#else
+#define K5_ACT1(v) elu1(v)
+#define K5_DACT1(h) delu(h)
+#define K5_ACTQ(v) elu_quad(v)
+#define K5_DACTQ(h) elu_grad_quad(h)
+#define K5_ACT_PARAM
+#define K5_ACT_ARG(x)
+#define K5_KERNEL generic_backward_kernel
+#define K5_KERNEL_PARAMS const GBwd a
+#endif
+
 namespace psnode {
 namespace {
 
@@ -75,7 +100,7 @@ __device__ __forceinline__ f4v gm(float a, float b, f4v c) { return __builtin_am
 // out[u][traj] = sum_k W[u][k] in[k][traj]:  A[i][g] = W^T staged in `wbuf` as [k][N] (chunks of input rows, partial sums
 // of multi-chunk layers live in `out`), B[g][j] = in[k = 4q+g][traj j].  Barrier after every chunk.
 // (forceinline: as separate functions the buffers arrive as GENERIC pointers and every LDS access becomes a flat_load / flat_store)
-__device__ __forceinline__ void g_forward(const GMlp& m, float* acts, float* wbuf) {
+__device__ __forceinline__ void g_forward(const GMlp& m, float* acts, float* wbuf K5_ACT_PARAM) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, i = lane & 15;
     int K = m.in_dim;
     for (int l = 0; l < m.L; ++l) {
@@ -114,7 +139,7 @@ __device__ __forceinline__ void g_forward(const GMlp& m, float* acts, float* wbu
                     const int uu = 16 * mt + 4 * g + r;
                     if (uu < N) {
                         float v = accA[r] + accB[r];
-                        if (final && !last) v = elu1(v);
+                        if (final && !last) v = K5_ACT1(v);
                         out[uu * TP + i] = v;
                     }
                 }
@@ -130,7 +155,7 @@ __device__ __forceinline__ void g_forward(const GMlp& m, float* acts, float* wbu
 // gacc_l / gacc_g: the parameter-gradient accumulators in LDS or in this workgroup's global slice (gg, a template parameter: a runtime
 // choice between the two pointers makes every access a flat one)
 template <bool gg>
-__device__ __forceinline__ float* g_vjp(const GMlp& m, const float* acts, float* din, float* dout, float* gacc_l, float* gacc_g, float* wbuf) {
+__device__ __forceinline__ float* g_vjp(const GMlp& m, const float* acts, float* din, float* dout, float* gacc_l, float* gacc_g, float* wbuf K5_ACT_PARAM) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, i = lane & 15;
     for (int l = m.L - 1; l >= 0; --l) {
         const int N = m.out_dim[l], K = l == 0 ? m.in_dim : m.out_dim[l - 1];
@@ -195,7 +220,7 @@ __device__ __forceinline__ float* g_vjp(const GMlp& m, const float* acts, float*
                     const int kr = 16 * kt + 4 * g + r;
                     if (kr < K) {
                         float v = accA[r] + accB[r];
-                        if (final && l > 0) v *= delu(a_in[kr * TP + i]);
+                        if (final && l > 0) v *= K5_DACT1(a_in[kr * TP + i]);
                         dout[kr * TP + i] = v;
                     }
                 }
@@ -312,7 +337,7 @@ __host__ __device__ inline int tm_db_off(const GMlp& m, int l) {
 __host__ __device__ inline int tm_total(const GMlp& m) { return (tm_db_off(m, m.L) + 3) & ~3; }
 
 // forward with stored activations, the DE in registers: acts[act[0]] = input rows; writes acts[act[l + 1]] and the quad-row copies
-__device__ __forceinline__ void g_forward_reg(const GBwd& a, float* acts, float* qb, const QOff& qo, const RegFwd& fw) {
+__device__ __forceinline__ void g_forward_reg(const GBwd& a, float* acts, float* qb, const QOff& qo, const RegFwd& fw K5_ACT_PARAM) {
     const GMlp& m = a.de;
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6), g = lane >> 4, j = lane & 15;
     {   // the input rows -> quad-row, pad columns zero
@@ -334,7 +359,7 @@ __device__ __forceinline__ void g_forward_reg(const GBwd& a, float* acts, float*
             if (l == 0) acc = tile_reg_any<8>(S4, bq, fw.first);
             else acc = tile_reg_any<4>(S4, bq, fw.rest[l - 1 < 3 ? l - 1 : 0]);
             acc = acc + bias;
-            const f4 e = last ? acc : elu_quad(acc);
+            const f4 e = last ? acc : K5_ACTQ(acc);
             float* out = acts + m.act[l + 1] * TP;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -350,7 +375,7 @@ __device__ __forceinline__ void g_forward_reg(const GBwd& a, float* acts, float*
 // VJP of the DE with the delta propagation in registers (the weight-gradient part is g_vjp's)
 template <bool gg>
 __device__ __forceinline__ float* g_vjp_reg(const GBwd& a, const float* acts, float* din, float* dout, float* gacc_l, float* gacc_g, float* qb,
-                                            const QOff& qo, const RegBwd& bw) {
+                                            const QOff& qo, const RegBwd& bw K5_ACT_PARAM) {
     const GMlp& m = a.de;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, i = lane & 15;
     const int w = __builtin_amdgcn_readfirstlane(wave);
@@ -411,7 +436,7 @@ __device__ __forceinline__ float* g_vjp_reg(const GBwd& a, const float* acts, fl
                 asm volatile("s_nop 3" : "+v"(acc));
                 if (l > 0) {
                     const f4 h = reinterpret_cast<const f4*>(qb + qo.act[l - 1 >= 0 ? l - 1 : 0])[kt * 64 + lane];
-                    acc = acc * elu_grad_quad(h);
+                    acc = acc * K5_DACTQ(h);
                     reinterpret_cast<f4*>(qb + qn)[kt * 64 + lane] = acc;
                 }
 #pragma unroll
@@ -458,7 +483,7 @@ __device__ __forceinline__ f4 tile_stream(const f4* __restrict__ A, const int S4
 }
 
 // forward with stored activations, streamed: acts[act[0]] = input rows; writes acts[act[l + 1]] and the quad-row copies
-__device__ __forceinline__ void g_forward_str(const GMlp& m, const float* const* fimg, float* acts, float* qb, const QOff& qo) {
+__device__ __forceinline__ void g_forward_str(const GMlp& m, const float* const* fimg, float* acts, float* qb, const QOff& qo K5_ACT_PARAM) {
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6), g = lane >> 4, j = lane & 15;
     {
         const float* u = acts + m.act[0] * TP;
@@ -475,7 +500,7 @@ __device__ __forceinline__ void g_forward_str(const GMlp& m, const float* const*
         for (int nt = w; nt < NTL; nt += 4) {
             const f4 bias = *reinterpret_cast<const f4*>(fimg[l] + (size_t)NTL * S4 * 256 + 16 * nt + 4 * g);
             f4 acc = tile_stream(reinterpret_cast<const f4*>(fimg[l]) + (size_t)nt * S4 * 64 + lane, S4, bq) + bias;
-            const f4 e = last ? acc : elu_quad(acc);
+            const f4 e = last ? acc : K5_ACTQ(acc);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int uu = 16 * nt + 4 * g + r;
@@ -491,7 +516,7 @@ __device__ __forceinline__ void g_forward_str(const GMlp& m, const float* const*
 // transposed images
 template <bool gg>
 __device__ __forceinline__ float* g_vjp_str(const GMlp& m, const float* const* timg, const float* acts, float* din, float* dout, float* gacc_l,
-                                            float* gacc_g, float* qb, const QOff& qo) {
+                                            float* gacc_g, float* qb, const QOff& qo K5_ACT_PARAM) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, i = lane & 15;
     const int w = __builtin_amdgcn_readfirstlane(wave);
     int qd = qo.d0, qn = qo.d1;
@@ -539,7 +564,7 @@ __device__ __forceinline__ float* g_vjp_str(const GMlp& m, const float* const* t
             asm volatile("s_nop 3" : "+v"(acc));       // (as on the register path: the store below may sit on a taken branch edge)
             if (l > 0) {
                 const f4 h = reinterpret_cast<const f4*>(qb + qo.act[l - 1])[kt * 64 + lane];
-                acc = acc * elu_grad_quad(h);
+                acc = acc * K5_DACTQ(h);
                 reinterpret_cast<f4*>(qb + qn)[kt * 64 + lane] = acc;
             }
 #pragma unroll
@@ -558,7 +583,7 @@ __device__ __forceinline__ float* g_vjp_str(const GMlp& m, const float* const* t
 // gg / ggA: the DE's / the AE's accumulators live in the workgroup's global slice.  REG: the DE on the register path.  STR: 1 = the AE
 // head streamed, 2 = both MLPs streamed (0: whatever is not on the register path stages its weights through LDS).
 template <bool gg, bool REG, bool ggA = gg, int STR = 0>
-__global__ __launch_bounds__(NT) void generic_backward_kernel(const GBwd a) {
+__global__ __launch_bounds__(NT) void K5_KERNEL(K5_KERNEL_PARAMS) {
     constexpr bool DE_TM = REG || STR == 2;      // the DE's LDS accumulators are tile-major
     constexpr bool AE_TM = STR >= 1;
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -662,11 +687,11 @@ __global__ __launch_bounds__(NT) void generic_backward_kernel(const GBwd a) {
     // adds to gx_dst, ga0s, and to the z|v gradients (global gz/gv at jzv, or the jump gradients of event ev)
     auto ae_vjp = [&](const float* xrows, long long jzv, int ev, const float* gi, float* gx_dst) {
         ae_input(xrows, jzv);
-        if constexpr (STR >= 1) g_forward_str(a.ae, a.fimgA, acts, qb, qoA); else g_forward(a.ae, acts, wbuf);
+        if constexpr (STR >= 1) g_forward_str(a.ae, a.fimgA, acts, qb, qoA K5_ACT_ARG(act.ae)); else g_forward(a.ae, acts, wbuf K5_ACT_ARG(act.ae));
         TILE_LOOP(id) dA[r * TP + c] = gi[r * TP + c];
         __syncthreads();
-        const float* gu = STR >= 1 ? g_vjp_str<ggA>(a.ae, a.timgA, acts, dA, dB, gacc_l + ae_at, tmgA, qb, qoA)
-                                   : g_vjp<ggA>(a.ae, acts, dA, dB, gacc_l + ae_at, gacc_g + a.de.np, wbuf);
+        const float* gu = STR >= 1 ? g_vjp_str<ggA>(a.ae, a.timgA, acts, dA, dB, gacc_l + ae_at, tmgA, qb, qoA K5_ACT_ARG(act.ae))
+                                   : g_vjp<ggA>(a.ae, acts, dA, dB, gacc_l + ae_at, gacc_g + a.de.np, wbuf K5_ACT_ARG(act.ae));
         TILE_LOOP(n) ga0s[r * TP + c] += gu[r * TP + c];
         TILE_LOOP(xd) gx_dst[r * TP + c] += gu[(n + r) * TP + c];
         TILE_LOOP(nzv) {
@@ -738,7 +763,7 @@ __global__ __launch_bounds__(NT) void generic_backward_kernel(const GBwd a) {
             // (2) algebraic input of this step's DE
             if (ev >= 0) {
                 ae_input(x0, -1);
-                if constexpr (STR >= 1) g_forward_str(a.ae, a.fimgA, acts, qb, qoA); else g_forward(a.ae, acts, wbuf);
+                if constexpr (STR >= 1) g_forward_str(a.ae, a.fimgA, acts, qb, qoA K5_ACT_ARG(act.ae)); else g_forward(a.ae, acts, wbuf K5_ACT_ARG(act.ae));
                 const float* out = acts + a.ae.act[a.ae.L] * TP;
                 TILE_LOOP(id) ext[(nzv + r) * TP + c] = out[r * TP + c];
             } else {
@@ -756,9 +781,9 @@ __global__ __launch_bounds__(NT) void generic_backward_kernel(const GBwd a) {
             __syncthreads();
             if (s + 1 < S) {               // (the last stage's slope feeds no stage input: its evaluation is (3b)'s first, not done here)
                 de_input(xst + s * nx);
-                if constexpr (REG) g_forward_reg(a, acts, qb, qo, rfw);
-                else if constexpr (STR == 2) g_forward_str(a.de, a.fimg, acts, qb, qo);
-                else g_forward(a.de, acts, wbuf);
+                if constexpr (REG) g_forward_reg(a, acts, qb, qo, rfw K5_ACT_ARG(act.de));
+                else if constexpr (STR == 2) g_forward_str(a.de, a.fimg, acts, qb, qo K5_ACT_ARG(act.de));
+                else g_forward(a.de, acts, wbuf K5_ACT_ARG(act.de));
                 const float* out = acts + a.de.act[a.de.L] * TP;
                 TILE_LOOP(xd) ks[s * nx + r * TP + c] = out[r * TP + c];
                 __syncthreads();
@@ -774,13 +799,14 @@ __global__ __launch_bounds__(NT) void generic_backward_kernel(const GBwd a) {
         __syncthreads();
         for (int s = S - 1; s >= 0; --s) {
             de_input(xst + s * nx);
-            if constexpr (REG) { if (PSNODE_K5_ABL != 3) g_forward_reg(a, acts, qb, qo, rfw); }
-            else if constexpr (STR == 2) g_forward_str(a.de, a.fimg, acts, qb, qo);
-            else g_forward(a.de, acts, wbuf);
+            if constexpr (REG) { if (PSNODE_K5_ABL != 3) g_forward_reg(a, acts, qb, qo, rfw K5_ACT_ARG(act.de)); }
+            else if constexpr (STR == 2) g_forward_str(a.de, a.fimg, acts, qb, qo K5_ACT_ARG(act.de));
+            else g_forward(a.de, acts, wbuf K5_ACT_ARG(act.de));
             TILE_LOOP(xd) dA[r * TP + c] = gks[s * nx + r * TP + c];
             __syncthreads();
-            const float* gu = REG ? g_vjp_reg<gg>(a, acts, dA, dB, gacc_l, tmg, qb, qo, rbw)
-                                  : (STR == 2 ? g_vjp_str<gg>(a.de, a.timg, acts, dA, dB, gacc_l, tmg, qb, qo) : g_vjp<gg>(a.de, acts, dA, dB, gacc_l, gacc_g, wbuf));
+            const float* gu = REG ? g_vjp_reg<gg>(a, acts, dA, dB, gacc_l, tmg, qb, qo, rbw K5_ACT_ARG(act.de))
+                                  : (STR == 2 ? g_vjp_str<gg>(a.de, a.timg, acts, dA, dB, gacc_l, tmg, qb, qo K5_ACT_ARG(act.de))
+                                              : g_vjp<gg>(a.de, acts, dA, dB, gacc_l, gacc_g, wbuf K5_ACT_ARG(act.de)));
             TILE_LOOP(n) {
                 const float gs = gu[(n + r) * TP + c] + gu[(2 * n + r) * TP + c];
                 ga0s[r * TP + c] += gu[r * TP + c] - gu[(n + r) * TP + c];
@@ -974,6 +1000,7 @@ bool mlp_ok(const psnode_mlp_f32& m, int in_dim, int out_dim) {
 
 }  // namespace
 
+#ifndef PSNODE_K5_ACT_BUILD
 // shared by the ODE and DAE entry points (psnode_backward.hip calls this for kernel = generic / unsupported MFMA shapes)
 size_t generic_bwd_workspace_floats(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, long long B) {
     const size_t nwg = (size_t)((B + TB - 1) / TB);
@@ -998,8 +1025,15 @@ int generic_bwd_fits(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, int xd,
     return gbwd_mode(a);
 }
 
+#endif  // PSNODE_K5_ACT_BUILD
+
 // launches pack (transpose), the backward kernel and the partial reduction
-int generic_backward_launch(int method, int xd, int zd, int vd, int id, long long T, long long B, const psnode_mlp_f32* de,
+#ifdef PSNODE_K5_ACT_BUILD
+int generic_backward_launch_act(const ActPair& act, int method,
+#else
+int generic_backward_launch(int method,
+#endif
+                            int xd, int zd, int vd, int id, long long T, long long B, const psnode_mlp_f32* de,
                             const psnode_mlp_f32* ae, ViewDev t, ViewDev z, ViewDev v, const float* a0, const int* ev, const float* zj,
                             long long zjb, long long zje, const float* vj, long long vjb, long long vje, int n_events, const float* xs,
                             const float* is_, const float* gxs, const float* gis, float* gx0, float* gz, float* gv, float* gzj, float* gvj,
@@ -1061,16 +1095,16 @@ int generic_backward_launch(int method, int xd, int zd, int vd, int id, long lon
     if ((a.de_reg || a.str == 2) && launch_pack_plain_images(mde, img, imgT, stream) != hipSuccess) return PSNODE_ERR_HIP;
     if (dae && a.str >= 1 && launch_pack_plain_images(mae, imgA, imgTA, stream) != hipSuccess) return PSNODE_ERR_HIP;
     // <DE accumulators global, DE on the register path, AE accumulators global, streamed MLPs>
-    void (*kern)(const GBwd) = nullptr;
+    void (*kern)(K5_KERNEL_PARAMS) = nullptr;
     const int g = a.gacc_global;
-    if (a.de_reg && a.str == 1) kern = g == 1 ? &generic_backward_kernel<true, true, true, 1> : (g == 2 ? &generic_backward_kernel<false, true, true, 1> : &generic_backward_kernel<false, true, false, 1>);
-    else if (a.de_reg) kern = g == 1 ? &generic_backward_kernel<true, true, true, 0> : (g == 2 ? &generic_backward_kernel<false, true, true, 0> : &generic_backward_kernel<false, true, false, 0>);
-    else if (a.str == 2) kern = g == 1 ? &generic_backward_kernel<true, false, true, 2> : (g == 2 ? &generic_backward_kernel<false, false, true, 2> : &generic_backward_kernel<false, false, false, 2>);
-    else kern = g ? &generic_backward_kernel<true, false, true, 0> : &generic_backward_kernel<false, false, false, 0>;
+    if (a.de_reg && a.str == 1) kern = g == 1 ? &K5_KERNEL<true, true, true, 1> : (g == 2 ? &K5_KERNEL<false, true, true, 1> : &K5_KERNEL<false, true, false, 1>);
+    else if (a.de_reg) kern = g == 1 ? &K5_KERNEL<true, true, true, 0> : (g == 2 ? &K5_KERNEL<false, true, true, 0> : &K5_KERNEL<false, true, false, 0>);
+    else if (a.str == 2) kern = g == 1 ? &K5_KERNEL<true, false, true, 2> : (g == 2 ? &K5_KERNEL<false, false, true, 2> : &K5_KERNEL<false, false, false, 2>);
+    else kern = g ? &K5_KERNEL<true, false, true, 0> : &K5_KERNEL<false, false, false, 0>;
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         return PSNODE_ERR_HIP;
     const unsigned nwg = (unsigned)((B + TB - 1) / TB);
-    hipLaunchKernelGGL(kern, dim3(nwg), dim3(NT), lds, stream, a);
+    hipLaunchKernelGGL(kern, dim3(nwg), dim3(NT), lds, stream, a K5_ACT_ARG(act));
     if (hipGetLastError() != hipSuccess) return PSNODE_ERR_HIP;
     return launch_reduce_partials(a.wpart, gparams_de, gparams_ae, a.de.np, dae ? a.ae.np : 0, (int)nwg, stream) == hipSuccess ? PSNODE_OK : PSNODE_ERR_HIP;
 }

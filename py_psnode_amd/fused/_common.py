@@ -2,6 +2,7 @@
 C ABI structs (include/psnode_hip.h), the device-side event table, workspaces.  Nothing here computes on the CPU and nothing here
 imports oracle/."""
 import ctypes
+import math
 import os
 import weakref
 from typing import List, Optional, Sequence, Tuple
@@ -62,6 +63,136 @@ def sequential_layers(seq) -> Optional[List[Tuple[torch.Tensor, torch.Tensor]]]:
     return out
 
 
+class Act:
+    """A hidden-layer activation other than ELU(alpha=1) that the generic kernels K0 / K5 apply (psnode_act_f32, include/psnode_hip.h).
+    Everywhere in this package `act=None` means ELU(1), the activation of every specialised kernel.  Calling it applies the activation
+    with torch (the recipe probe)."""
+    __slots__ = ("kind", "alpha", "beta", "threshold", "name")
+
+    def __init__(self, kind: int, alpha: float = 0.0, beta: float = 1.0, threshold: float = 20.0, name: str = ""):
+        self.kind, self.alpha, self.beta, self.threshold, self.name = int(kind), float(alpha), float(beta), float(threshold), name
+
+    def abi(self) -> "_lib.ActF32":
+        a = _lib.ActF32()
+        a.kind, a.alpha, a.beta, a.threshold = self.kind, self.alpha, self.beta, self.threshold
+        return a
+
+    def __call__(self, u: torch.Tensor) -> torch.Tensor:
+        F = nn.functional
+        if self.kind == _lib.ACT_ELU:
+            return F.elu(u, self.alpha)
+        if self.kind == _lib.ACT_TANH:
+            return torch.tanh(u)
+        if self.kind == _lib.ACT_SIGMOID:
+            return torch.sigmoid(u)
+        if self.kind == _lib.ACT_RELU:
+            return F.relu(u)
+        if self.kind == _lib.ACT_LEAKY_RELU:
+            return F.leaky_relu(u, self.alpha)
+        return F.softplus(u, self.beta, self.threshold)
+
+    def _key(self):
+        return (self.kind, self.alpha, self.beta, self.threshold)
+
+    def __eq__(self, other):
+        return isinstance(other, Act) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        return f"Act({self.name})"
+
+
+def _act_refs(*acts):
+    """ctypes pointers of the psnode_act_f32 of `acts` (None = ELU(1): NULL), and whether any of them is not ELU(1)."""
+    refs = [ctypes.byref(a.abi()) if a is not None else None for a in acts]
+    return refs, any(a is not None for a in acts)
+
+
+def _dae_acts(act):
+    """act of a DAE call: None (both MLPs ELU(1)) or (de_act, ae_act)."""
+    if act is None:
+        return None, None
+    de_act, ae_act = act
+    return de_act, ae_act
+
+
+def act_of_module(m) -> Optional[object]:
+    """`False` if `m` is no activation the generic kernels apply, None for ELU(alpha=1), else its Act."""
+    t = type(m)
+    if t is nn.ELU:
+        a = float(m.alpha)
+        if a == 1.0:
+            return None
+        return Act(_lib.ACT_ELU, alpha=a, name=f"ELU(alpha={a})") if a > 0 and math.isfinite(a) else False
+    if t is nn.Tanh:
+        return Act(_lib.ACT_TANH, name="Tanh")
+    if t is nn.Sigmoid:
+        return Act(_lib.ACT_SIGMOID, name="Sigmoid")
+    if t is nn.ReLU:
+        return Act(_lib.ACT_RELU, name="ReLU")
+    if t is nn.LeakyReLU:
+        s = float(m.negative_slope)
+        return Act(_lib.ACT_LEAKY_RELU, alpha=s, name=f"LeakyReLU({s})") if s >= 0 and math.isfinite(s) else False
+    if t is nn.Softplus:
+        b, th = float(m.beta), float(m.threshold)
+        ok = b > 0 and math.isfinite(b) and math.isfinite(th)
+        return Act(_lib.ACT_SOFTPLUS, beta=b, threshold=th, name=f"Softplus(beta={b}, threshold={th})") if ok else False
+    return False
+
+
+def sequential_mlp(seq):
+    """(layers, act) if `seq` is nn.Sequential(Linear, A, Linear, ..., A, Linear) with ONE activation A throughout that the generic kernels
+    apply (ELU(alpha > 0), Tanh, Sigmoid, ReLU, LeakyReLU(slope >= 0), Softplus(beta > 0)); act None = ELU(1).  Else None (mixed activations
+    included)."""
+    if not isinstance(seq, nn.Sequential) or len(seq) == 0 or len(seq) % 2 == 0:
+        return None
+    out, acts = [], []
+    for k, m in enumerate(seq):
+        if k % 2 == 0:
+            if type(m) is not nn.Linear or m.bias is None:
+                return None
+            out.append((m.weight, m.bias))
+        else:
+            a = act_of_module(m)
+            if a is False:
+                return None
+            acts.append(a)
+    if any(a != acts[0] for a in acts[1:]):
+        return None
+    if len(out) > _lib.MAX_LAYERS:
+        return None
+    for (w, _), (w2, _) in zip(out[:-1], out[1:]):
+        if w2.shape[1] != w.shape[0]:
+            return None
+    return out, (acts[0] if acts else None)
+
+
+def de_mlp_of(x_func, n: int, x_dim: int):
+    """(layers, act) of a DE_Func whose MLP has any activation of `sequential_mlp` (act None = ELU(1)), else None."""
+    if not isinstance(x_func, nn.Module) or _overrides_forward_hooks(x_func):
+        return None
+    r = sequential_mlp(getattr(x_func, "x_dot", None))
+    if r is None or r[0][0][0].shape[1] != 3 * n or r[0][-1][0].shape[0] != x_dim:
+        return None
+    if not _only_params_of(x_func, x_func.x_dot):
+        return None
+    return r
+
+
+def ae_mlp_of(i_func, n: int, m: int, i_dim: int):
+    """(layers, act) of an AE_Func whose MLP has any activation of `sequential_mlp` (act None = ELU(1)), else None."""
+    if not isinstance(i_func, nn.Module) or _overrides_forward_hooks(i_func):
+        return None
+    r = sequential_mlp(getattr(i_func, "i_calculator", None))
+    if r is None or r[0][0][0].shape[1] != n + m or r[0][-1][0].shape[0] != i_dim:
+        return None
+    if not _only_params_of(i_func, i_func.i_calculator):
+        return None
+    return r
+
+
 def de_layers_of(x_func, n: int, x_dim: int):
     """Layers of a DE_Func (attribute `x_dot`, input recipe cat(a0, s-a0, s))."""
     if not isinstance(x_func, nn.Module) or _overrides_forward_hooks(x_func):
@@ -86,15 +217,15 @@ def ae_layers_of(i_func, n: int, m: int, i_dim: int):
     return layers
 
 
-def _mlp_eval(layers, u):
+def _mlp_eval(layers, u, act=None):
     for k, (w, b) in enumerate(layers):
         u = nn.functional.linear(u, w, b)
         if k + 1 < len(layers):
-            u = nn.functional.elu(u)
+            u = nn.functional.elu(u) if act is None else act(u)
     return u
 
 
-def _recipe_ok(mod: nn.Module, layers, kind: str, widths) -> bool:
+def _recipe_ok(mod: nn.Module, layers, kind: str, widths, act=None) -> bool:
     """Does `mod.forward` really compute the recipe the kernels hard-code?  The structural checks (attribute name, Sequential
     shape, no extra parameters) say nothing about forward(): a user DE_Func that scales its output, uses t0 or concatenates in
     another order would be integrated WRONGLY.  One numeric probe per (module, forward function): a few random rows through the
@@ -103,7 +234,7 @@ def _recipe_ok(mod: nn.Module, layers, kind: str, widths) -> bool:
     fwd = type(mod).forward
     if getattr(fwd, "_psnode_recipe", None) == kind:
         return True
-    key = (fwd, kind, tuple(widths))
+    key = (fwd, kind, tuple(widths), act)
     cached = mod.__dict__.get("_psnode_probe")
     if cached is not None and cached[0] == key:
         return cached[1]
@@ -120,15 +251,15 @@ def _recipe_ok(mod: nn.Module, layers, kind: str, widths) -> bool:
             if kind == "de_ode":
                 got = mod(t0=t0, xt=parts[0], zt=parts[1], all_initial=a0)
                 s_ = torch.cat(parts, -1)
-                want = _mlp_eval(layers, torch.cat((a0, s_ - a0, s_), -1))
+                want = _mlp_eval(layers, torch.cat((a0, s_ - a0, s_), -1), act)
             elif kind == "de_dae":
                 got = mod(t0=t0, xt=parts[0], zt=parts[1], vt=parts[2], it=parts[3], all_initial=a0)
                 s_ = torch.cat(parts, -1)
-                want = _mlp_eval(layers, torch.cat((a0, s_ - a0, s_), -1))
+                want = _mlp_eval(layers, torch.cat((a0, s_ - a0, s_), -1), act)
             else:   # "ae": all_initial spans x|z|v|i, the inputs x, z, v
                 a0 = torch.randn(R, widths[3], generator=g).to(device=dev, dtype=dt)
                 got = mod(xt=parts[0], zt=parts[1], vt=parts[2], all_initial=a0)
-                want = _mlp_eval(layers, torch.cat((a0, parts[0], parts[1], parts[2]), -1))
+                want = _mlp_eval(layers, torch.cat((a0, parts[0], parts[1], parts[2]), -1), act)
             ok = bool(got.shape == want.shape and torch.allclose(got, want, rtol=1e-4, atol=1e-6))
     except Exception:
         ok = False

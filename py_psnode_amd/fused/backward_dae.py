@@ -6,12 +6,21 @@ import ctypes
 import torch
 
 from .. import _lib
-from ._common import (KERNEL_ID, Layers, METHOD_ID, _aligned16, _aligned_ptr, _check_saved, _empty, _f32_dev, _jump, _mlp, _pad_rows, _padded_hidden, _split_grads, _view)
+from ._common import (KERNEL_ID, Layers, METHOD_ID, _act_refs, _dae_acts, _aligned16, _aligned_ptr, _check_saved, _empty, _f32_dev, _jump, _mlp, _pad_rows, _padded_hidden, _split_grads, _view)
 from .latent import latent_backward_wide, latent_wide_shape
 
-def dae_backward_supported(method: str, de_layers: Layers, ae_layers: Layers, x_dim, z_dim, v_dim, i_dim) -> bool:
+def dae_backward_supported(method: str, de_layers: Layers, ae_layers: Layers, x_dim, z_dim, v_dim, i_dim, act=None) -> bool:
+    """act: None (both MLPs ELU(1)) or (de_act, ae_act); an activation other than ELU(1) is K5's alone."""
     if de_layers[0][0].device.type != "cuda" or max(len(de_layers), len(ae_layers)) > _lib.MAX_LAYERS:
         return False
+    refs, non_elu = _act_refs(*_dae_acts(act))
+    if non_elu:
+        a = _lib.DaeBwdArgsF32()
+        a.method = METHOD_ID[method]
+        a.x_dim, a.z_dim, a.v_dim, a.i_dim, a.T, a.B = x_dim, z_dim, v_dim, i_dim, 2, 1
+        dev = de_layers[0][0].device
+        a.de, a.ae = _mlp(de_layers, dev, "de", []), _mlp(ae_layers, dev, "ae", [])
+        return bool(_lib.load().psnode_dae_backward_act_supported(ctypes.byref(a), *refs))
     if latent_wide_shape(de_layers, ae_layers, x_dim, z_dim, v_dim, i_dim):
         return True                          # K3w (saving) + K9w + library GEMMs
     lib = _lib.load()
@@ -291,16 +300,23 @@ def _dae_backward_wide_sliced(step, method, de_layers, ae_layers, t, z, v, all_i
 
 
 def dae_backward(method: str, de_layers: Layers, ae_layers: Layers, t, z, v, all_initial, xs, is_, grad_xs, grad_is, event_idx=None,
-                 z_jump=None, v_jump=None, kernel: str = "auto", saved=None):
+                 z_jump=None, v_jump=None, kernel: str = "auto", saved=None, act=None):
     """Backward pass of `dae_integrate` (no teacher forcing): the one-launch K7f (`dae_backward_wide`) for the DAE_01 shape class at
     hidden <= 128, K9 / K8 / K9w for the latent shapes of the direct_encode models, else the generic backward kernel (K5);
     `kernel` = "auto" | "mfma" | "generic" | "wide" (K7f or an error).
     saved = what `dae_integrate(save=True)` returned (read by K7f, K9 and K9w; K8 / K5 recompute and refuse them).
+    act: None (both MLPs ELU(1)) or (de_act, ae_act); an activation other than ELU(1) runs on K5 only (kernel "auto" / "generic").
     Returns dict(x_init, z, v, z_jump, v_jump, all_initial, de=[...], ae=[...]) of gradients."""
     lib = _lib.load()
     dev = xs.device
     T, B, xd = xs.shape
     zd, vd, idim = z.shape[-1], v.shape[-1], is_.shape[-1]
+    refs, non_elu = _act_refs(*_dae_acts(act))
+    if non_elu:
+        if kernel not in ("auto", "generic") or saved is not None:
+            raise _lib.UnsupportedShapeError("dae_backward: an activation other than ELU(alpha=1) runs on the generic backward K5 only "
+                                             "(kernel 'auto' / 'generic', no saved rows)")
+        kernel = "generic"
     if kernel in ("wide", "mfma") and T < 2 and len(de_layers) == 4:
         kernel = "generic"       # no step to sweep: K7f has no head-only form, K5 handles the single grid point
     if saved is not None and latent_wide_shape(de_layers, ae_layers, xd, zd, vd, idim):
@@ -368,7 +384,10 @@ def dae_backward(method: str, de_layers: Layers, ae_layers: Layers, t, z, v, all
         nbytes = lib.psnode_dae_backward_workspace_bytes(ctypes.byref(a))
         ws = _empty(nbytes + 256, dtype=torch.uint8, device=dev)
         wp, wn = _aligned_ptr(ws)
-        rc = lib.psnode_dae_backward_f32(ctypes.byref(a), wp, wn, torch.cuda.current_stream(dev).cuda_stream)
+        if not non_elu:
+            rc = lib.psnode_dae_backward_f32(ctypes.byref(a), wp, wn, torch.cuda.current_stream(dev).cuda_stream)
+        else:
+            rc = lib.psnode_dae_backward_act_f32(ctypes.byref(a), *refs, wp, wn, torch.cuda.current_stream(dev).cuda_stream)
     _lib.check(rc, "psnode_dae_backward_f32")
     g["de"], g["ae"] = _split_grads(gde, de_layers), _split_grads(gae, ae_layers)
     return g

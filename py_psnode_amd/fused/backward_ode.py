@@ -5,7 +5,7 @@ import ctypes
 import torch
 
 from .. import _lib
-from ._common import (KERNEL_ID, Layers, METHOD_ID, _aligned16, _aligned_ptr, _check_saved, _empty, _f32_dev, _jump, _mlp, _split_grads, _view)
+from ._common import (KERNEL_ID, Layers, METHOD_ID, _act_refs, _aligned16, _aligned_ptr, _check_saved, _empty, _f32_dev, _jump, _mlp, _split_grads, _view)
 from .latent import latent_backward_wide, latent_wide_shape
 
 def _bwd_args(method, de_layers, x_dim, z_dim, T, B, dev, keep, kernel="auto"):
@@ -17,11 +17,15 @@ def _bwd_args(method, de_layers, x_dim, z_dim, T, B, dev, keep, kernel="auto"):
     return a
 
 
-def ode_backward_supported(method: str, de_layers: Layers, x_dim: int, z_dim: int, kernel: str = "auto") -> bool:
+def ode_backward_supported(method: str, de_layers: Layers, x_dim: int, z_dim: int, kernel: str = "auto", act=None) -> bool:
     """True if a fused backward kernel covers this shape: the MFMA class (3n->64->64->64->x, x<=8, z<=4) or any MLP whose
-    activations and parameter gradients fit the LDS (generic backward)."""
+    activations and parameter gradients fit the LDS (generic backward).  act (fused.Act) other than None = ELU(1): K5 only."""
     if de_layers[0][0].device.type != "cuda" or len(de_layers) > _lib.MAX_LAYERS:
         return False
+    if act is not None:
+        a = _bwd_args(method, de_layers, x_dim, z_dim, 2, 1, de_layers[0][0].device, [], kernel)
+        refs, _ = _act_refs(act)
+        return bool(_lib.load().psnode_ode_backward_act_supported(ctypes.byref(a), *refs))
     if kernel in ("auto", "mfma") and latent_wide_shape(de_layers, None, x_dim, z_dim):
         return True                          # K3w (saving) + K9w + library GEMMs
     lib = _lib.load()
@@ -30,13 +34,15 @@ def ode_backward_supported(method: str, de_layers: Layers, x_dim: int, z_dim: in
 
 
 def ode_backward(method: str, de_layers: Layers, t, z, all_initial, xs, grad_xs, event_idx=None, z_jump=None, need_grad_z: bool = True,
-                 kernel: str = "auto", saved=None, input_true_x: bool = False, need_grad_zj: bool = True):
+                 kernel: str = "auto", saved=None, input_true_x: bool = False, need_grad_zj: bool = True, act=None):
     """Backward pass of `ode_integrate` in one launch.  `saved` = what `ode_integrate(save=True)` returned next to
     xs: K4f then skips the recompute of the stage evaluations.  input_true_x: backward of a teacher-forced call (my_solvers.py:72-74) --
     `xs` must then be the DATASET x the forward call started every step from; K4f (hidden <= 128, x_dim <= 8) only.
     need_grad_z / need_grad_zj = False: dL/dz / dL/dz_jump are not formed (the scripts' z and z_jump are dataset tensors: K4x then runs
     without its per-step dL/dz layer, and the [B,nE,zd] zero fill is not made).
     kernel: "wave" = K4x (one wave per 4 trajectories; hidden 33..64, saved rows), "wide" / "tile" = K4f; "auto" picks between them.
+    act: the hidden layers' activation (fused.Act); None = ELU(1).  Any other runs on the generic backward K5 only (kernel "auto" /
+    "generic", no saved rows, no teacher forcing).
     Returns (grad_x0 [B,xd], grad_z [T,B,zd] | None, grad_z_jump | None, grad_all_initial [B,n], [grad W1, b1, ..., W4, b4])."""
     lib = _lib.load()
     dev = xs.device
@@ -44,6 +50,9 @@ def ode_backward(method: str, de_layers: Layers, t, z, all_initial, xs, grad_xs,
     zd = z.shape[-1]
     # kernel: "auto" / "mfma" = the one-launch K4f at every hidden width <= 128 (z_dim <= 8), K8f / K9 / K9w for the latent shapes, else the
     # generic K5 ("auto" only); "wide" forces K4f
+    if act is not None and (kernel not in ("auto", "generic") or saved is not None or input_true_x):
+        raise _lib.UnsupportedShapeError("ode_backward: an activation other than ELU(alpha=1) runs on the generic backward K5 only "
+                                         "(kernel 'auto' / 'generic', no saved rows, no teacher forcing)")
     if saved is not None and not input_true_x and latent_wide_shape(de_layers, None, xd, zd):
         g = latent_backward_wide(method, de_layers, None, t, z, None, all_initial, xs, None, grad_xs, None, event_idx=event_idx,
                                  z_jump=z_jump, saved=saved, need_grad_z=need_grad_z)
@@ -87,6 +96,10 @@ def ode_backward(method: str, de_layers: Layers, t, z, all_initial, xs, grad_xs,
         nbytes = lib.psnode_ode_backward_workspace_bytes(ctypes.byref(a))
         ws = _empty(nbytes + 256, dtype=torch.uint8, device=dev)
         wp, wn = _aligned_ptr(ws)
-        rc = lib.psnode_ode_backward_f32(ctypes.byref(a), wp, wn, torch.cuda.current_stream(dev).cuda_stream)
+        if act is None:
+            rc = lib.psnode_ode_backward_f32(ctypes.byref(a), wp, wn, torch.cuda.current_stream(dev).cuda_stream)
+        else:
+            refs, _ = _act_refs(act)
+            rc = lib.psnode_ode_backward_act_f32(ctypes.byref(a), *refs, wp, wn, torch.cuda.current_stream(dev).cuda_stream)
     _lib.check(rc, "psnode_ode_backward_f32")
     return gx0, gz, gzj, ga0, _split_grads(gpar, de_layers)

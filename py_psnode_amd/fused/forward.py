@@ -6,7 +6,7 @@ from typing import Optional
 import torch
 
 from .. import _lib
-from ._common import (KERNEL_ID, Layers, METHOD_ID, _aligned16, _aligned_ptr, _check_jump, _check_tb, _empty, _f32_dev, _jump, _mlp, _view, _workspace, event_table)
+from ._common import (KERNEL_ID, Layers, METHOD_ID, _act_refs, _dae_acts, _aligned16, _aligned_ptr, _check_jump, _check_tb, _empty, _f32_dev, _jump, _mlp, _view, _workspace, event_table)
 
 _MFMA_CLASSES = ("MFMA integrators K1 / K2 cover `in -> H -> H -> H -> out` ELU-MLPs with H <= 128 (any x_dim <= 16 for the ODE, "
                  "x_dim <= 8 and z+v+i <= 8 for the DAE), and -- weights streamed from L2 -- the ODE up to H = 192 at any x_dim <= 16 and "
@@ -42,10 +42,20 @@ def _note_k0(lib, args, dae: bool, de_layers: Layers):
                       f"MFMA integrators.  {_MFMA_CLASSES}", RuntimeWarning, stacklevel=3)
 
 
+def _act_route_ok(what: str, non_elu: bool, kernel: str, save: bool):
+    """An activation other than ELU(1) runs on the generic kernels only: say so instead of a bare status."""
+    if non_elu and (kernel not in ("auto", "generic") or save):
+        raise _lib.UnsupportedShapeError(f"{what}: an activation other than ELU(alpha=1) runs on the generic kernel K0 only "
+                                         f"(kernel 'auto' / 'generic', no save=True); got kernel={kernel!r}, save={save}")
+
+
 def ode_integrate(method: str, de_layers: Layers, t, x, z, all_initial, event_t=None, z_jump=None,
                   input_true_x: bool = False, kernel: str = "auto", event_idx: Optional[torch.Tensor] = None,
-                  check_events: bool = False, out: Optional[torch.Tensor] = None, save: bool = False):
+                  check_events: bool = False, out: Optional[torch.Tensor] = None, save: bool = False, act=None):
     """Fused integrate_ODE (replaces my_solvers.py:52-80 + my_fixed_grid.py + DE_Func.forward).
+
+    act: the hidden layers' activation (fused.Act, from `sequential_mlp`); None = ELU(1).  Any other runs on the generic kernel K0 only
+    (kernel "auto" / "generic"; save=True is refused).
 
     save=True (training forward, K1 shapes only -- `ode_save_hidden`): the kernel also writes what autograd would save, the hidden
     activations [T-1,S,3,B,Hp] and the stage inputs [T-1,S,B,xd]; returns (xs, (act, xstage)) for `ode_backward(..., saved=)`.
@@ -59,6 +69,7 @@ def ode_integrate(method: str, de_layers: Layers, t, x, z, all_initial, event_t=
     dev = x.device
     if dev.type != "cuda":
         raise ValueError("fused integrator needs tensors on a HIP device")
+    _act_route_ok("ode_integrate", act is not None, kernel, save)
     T, B, xd = t.shape[0], x.shape[1], x.shape[2]
     if x.shape[0] < (T if input_true_x else 1):
         raise ValueError("x has fewer grid points than t")
@@ -110,10 +121,14 @@ def ode_integrate(method: str, de_layers: Layers, t, x, z, all_initial, event_t=
                 a.save_act, a.save_xstage = saved[0].data_ptr(), saved[1].data_ptr()
         ws = _workspace(lib, a.de, None, dev)
         wp, wn = _aligned_ptr(ws)
-        rc = lib.psnode_ode_integrate_f32(ctypes.byref(a), wp, wn, torch.cuda.current_stream(dev).cuda_stream)
+        if act is None:
+            rc = lib.psnode_ode_integrate_f32(ctypes.byref(a), wp, wn, torch.cuda.current_stream(dev).cuda_stream)
+        else:
+            refs, _ = _act_refs(act)
+            rc = lib.psnode_ode_integrate_act_f32(ctypes.byref(a), *refs, wp, wn, torch.cuda.current_stream(dev).cuda_stream)
     _mfma_miss(rc, kernel, "psnode_ode_integrate_f32", de_layers)
     _lib.check(rc, "psnode_ode_integrate_f32")
-    if kernel == "auto":
+    if kernel == "auto" and act is None:
         _note_k0(lib, a, False, de_layers)
     # the stream-ordered caching allocator keeps `keep`/`ws` storage valid until the kernel has run
     return (out, saved) if save else out
@@ -133,8 +148,10 @@ def ode_save_hidden(method: str, de_layers: Layers, x_dim: int, z_dim: int, kern
 def dae_integrate(method: str, de_layers: Layers, ae_layers: Layers, x_init, t, x, z, v, i, all_initial,
                   event_t=None, z_jump=None, v_jump=None, input_true_x: bool = False, input_true_i: bool = False,
                   kernel: str = "auto", event_idx: Optional[torch.Tensor] = None, check_events: bool = False, out=None,
-                  save: bool = False):
+                  save: bool = False, act=None):
     """Fused integrate_DAE (replaces my_solvers.py:82-131 + step functions + DE_Func/AE_Func forwards).
+    act: None (both MLPs ELU(1)) or (de_act, ae_act), each a fused.Act or None = ELU(1); an activation other than ELU(1) runs on the
+    generic kernel K0 only (kernel "auto" / "generic"; save=True is refused).
     `out` = (xs, is) contiguous [T,B,xd] / [T,B,id] tensors to write into (time-chunked launches).
     save=True (training forward, K2 shapes without teacher forcing -- `dae_save_hidden`): the kernel also writes what autograd would
     save (psnode_dae_args_f32::save_*); returns (xs, is, saved) with saved = (act [T-1,S,3,B,Hp], xstage [T-1,S,B,xd],
@@ -143,6 +160,8 @@ def dae_integrate(method: str, de_layers: Layers, ae_layers: Layers, x_init, t, 
     dev = x_init.device
     if dev.type != "cuda":
         raise ValueError("fused integrator needs tensors on a HIP device")
+    refs, non_elu = _act_refs(*_dae_acts(act))
+    _act_route_ok("dae_integrate", non_elu, kernel, save)
     T, B = t.shape[0], t.shape[1]
     xd, zd, vd, idim = x_init.shape[-1], z.shape[-1], v.shape[-1], i.shape[-1]
     if x_init.dim() != 2 or x_init.shape[0] != B:
@@ -219,10 +238,13 @@ def dae_integrate(method: str, de_layers: Layers, ae_layers: Layers, x_init, t, 
                 a.save_ev_act, a.save_ev_i = saved[3].data_ptr(), saved[4].data_ptr()
         ws = _workspace(lib, a.de, a.ae, dev)
         wp, wn = _aligned_ptr(ws)
-        rc = lib.psnode_dae_integrate_f32(ctypes.byref(a), wp, wn, torch.cuda.current_stream(dev).cuda_stream)
+        if not non_elu:
+            rc = lib.psnode_dae_integrate_f32(ctypes.byref(a), wp, wn, torch.cuda.current_stream(dev).cuda_stream)
+        else:
+            rc = lib.psnode_dae_integrate_act_f32(ctypes.byref(a), *refs, wp, wn, torch.cuda.current_stream(dev).cuda_stream)
     _mfma_miss(rc, kernel, "psnode_dae_integrate_f32", de_layers)
     _lib.check(rc, "psnode_dae_integrate_f32")
-    if kernel == "auto":
+    if kernel == "auto" and not non_elu:
         _note_k0(lib, a, True, de_layers)
     return (xs, is_, saved) if save else (xs, is_)
 

@@ -3,7 +3,7 @@ layers / event tensors."""
 
 import torch
 
-from ._common import _recipe_ok, ae_layers_of, de_layers_of
+from ._common import _recipe_ok, ae_layers_of, ae_mlp_of, de_layers_of, de_mlp_of
 
 # ----------------------------------------------------------------------------- planning for the solver classes
 def _event_tensors(event_fn, jump_change_fn, want_v: bool):
@@ -32,7 +32,8 @@ def _all_f32_on(dev, *tensors) -> bool:
 
 
 def plan_ode(x_func, x, z, all_initial, event_fn, jump_change_fn, t=None, x_init=None):
-    """None if this integrate_ODE call cannot run fused, else (de_layers, event_t, z_jump, needs_autograd)."""
+    """None if this integrate_ODE call cannot run fused, else (de_layers, event_t, z_jump, needs_autograd, de_act): de_act None = ELU(1), else
+    the MLP's activation (fused._common.Act: the generic kernels K0 / K5 only)."""
     if x.device.type != "cuda" or x.dtype != torch.float32 or x.dim() != 3 or z.dim() != 3:
         return None
     if x_init is not None and (x_init.dim() != 2 or x_init.shape != x.shape[1:]):
@@ -42,14 +43,16 @@ def plan_ode(x_func, x, z, all_initial, event_fn, jump_change_fn, t=None, x_init
     xd, zd = x.shape[-1], z.shape[-1]
     if all_initial.dim() != 2 or all_initial.shape[-1] != xd + zd:
         return None
-    layers = de_layers_of(x_func, xd + zd, xd)
-    if layers is None or not _recipe_ok(x_func, layers, "de_ode", (xd, zd)):
+    layers, act = de_layers_of(x_func, xd + zd, xd), None
+    if layers is None:
+        layers, act = de_mlp_of(x_func, xd + zd, xd) or (None, None)
+    if layers is None or not _recipe_ok(x_func, layers, "de_ode", (xd, zd), act):
         return None
     ok, event_t, z_jump, _ = _event_tensors(event_fn, jump_change_fn, False)
     if not ok or not _all_f32_on(x.device, event_t, z_jump):
         return None
     needs_grad = _needs_autograd([x if x_init is None else x_init, z, all_initial, z_jump] + [p for wb in layers for p in wb])
-    return layers, event_t, z_jump, needs_grad
+    return layers, event_t, z_jump, needs_grad, act
 
 
 def plan_dae(x_init, x_func, i_func, z, v, i, all_initial, event_fn, jump_change_fn, t=None):
@@ -61,14 +64,17 @@ def plan_dae(x_init, x_func, i_func, z, v, i, all_initial, event_fn, jump_change
     n = xd + zd + vd + idim
     if all_initial.dim() != 2 or all_initial.shape[-1] != n:
         return None
-    de = de_layers_of(x_func, n, xd)
-    ae = ae_layers_of(i_func, n, xd + zd + vd, idim)
+    de, ae, de_act, ae_act = de_layers_of(x_func, n, xd), ae_layers_of(i_func, n, xd + zd + vd, idim), None, None
+    if de is None:
+        de, de_act = de_mlp_of(x_func, n, xd) or (None, None)
+    if ae is None:
+        ae, ae_act = ae_mlp_of(i_func, n, xd + zd + vd, idim) or (None, None)
     if de is None or ae is None:
         return None
-    if not _recipe_ok(x_func, de, "de_dae", (xd, zd, vd, idim)) or not _recipe_ok(i_func, ae, "ae", (xd, zd, vd, n)):
+    if not _recipe_ok(x_func, de, "de_dae", (xd, zd, vd, idim), de_act) or not _recipe_ok(i_func, ae, "ae", (xd, zd, vd, n), ae_act):
         return None
     ok, event_t, z_jump, v_jump = _event_tensors(event_fn, jump_change_fn, True)
     if not ok or not _all_f32_on(x_init.device, event_t, z_jump, v_jump):
         return None
     needs_grad = _needs_autograd([x_init, z, v, all_initial, z_jump, v_jump] + [p for wb in list(de) + list(ae) for p in wb])
-    return de, ae, event_t, z_jump, v_jump, needs_grad
+    return de, ae, event_t, z_jump, v_jump, needs_grad, de_act, ae_act

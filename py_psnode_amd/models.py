@@ -19,12 +19,13 @@ import torch.nn as nn
 from .neural_dae import DAE_Event, Euler, ODE_Event
 
 
-def _elu_mlp(*dims):
+def _elu_mlp(*dims, activation=nn.ELU):
+    """nn.Sequential(Linear, A, ..., A, Linear) with A = activation() (a module class or factory; default ELU(alpha=1))."""
     mods = []
     for k in range(len(dims) - 1):
         mods.append(nn.Linear(int(dims[k]), int(dims[k + 1])))
         if k + 2 < len(dims):
-            mods.append(nn.ELU())
+            mods.append(activation())
     return nn.Sequential(*mods)
 
 
@@ -120,11 +121,13 @@ def accelerate(model: nn.Module, names=("_encoder", "_decoder")) -> nn.Module:
 
 class DE_Func(nn.Module):
     """ODE right-hand side: x_dot MLP over cat(a0, s - a0, s), s = cat(xt, zt).  Positional order of forward() as in
-    neural_00_ODE_01_no_encode.py:66 -- the TorchScript export (`save_model`) is called positionally downstream."""
+    neural_00_ODE_01_no_encode.py:66 -- the TorchScript export (`save_model`) is called positionally downstream.
+    `activation` (an extension): the hidden layers' module class or factory, e.g. nn.Tanh or lambda: nn.Softplus(beta=2); the
+    default nn.ELU builds the reference's modules.  ELU / Tanh / Sigmoid / ReLU / LeakyReLU / Softplus run fused (DESIGN.md "Activations")."""
 
-    def __init__(self, state_width, hidden_dims, out_dim):
+    def __init__(self, state_width, hidden_dims, out_dim, activation=nn.ELU):
         super().__init__()
-        self.x_dot = _elu_mlp(3 * state_width, *hidden_dims, out_dim)
+        self.x_dot = _elu_mlp(3 * state_width, *hidden_dims, out_dim, activation=activation)
 
     def forward(self, t0: torch.Tensor, xt: torch.Tensor, zt: torch.Tensor, all_initial: torch.Tensor):
         s = torch.cat((xt, zt), dim=-1)
@@ -134,11 +137,11 @@ class DE_Func(nn.Module):
 
 
 class DAE_DE_Func(nn.Module):
-    """DAE right-hand side, s = cat(xt, zt, vt, it); positional order of neural_01_DAE_01_no_encode.py:69."""
+    """DAE right-hand side, s = cat(xt, zt, vt, it); positional order of neural_01_DAE_01_no_encode.py:69.  `activation`: as DE_Func."""
 
-    def __init__(self, state_width, hidden_dims, out_dim):
+    def __init__(self, state_width, hidden_dims, out_dim, activation=nn.ELU):
         super().__init__()
-        self.x_dot = _elu_mlp(3 * state_width, *hidden_dims, out_dim)
+        self.x_dot = _elu_mlp(3 * state_width, *hidden_dims, out_dim, activation=activation)
 
     def forward(self, t0: torch.Tensor, xt: torch.Tensor, zt: torch.Tensor, vt: torch.Tensor, it: torch.Tensor, all_initial: torch.Tensor):
         s = torch.cat((xt, zt, vt, it), dim=-1)
@@ -166,11 +169,11 @@ def _export(model, path, names, on_cpu):
 
 
 class AE_Func(nn.Module):
-    """i_calculator MLP over cat(a0, xt, zt, vt)."""
+    """i_calculator MLP over cat(a0, xt, zt, vt).  `activation`: as DE_Func."""
 
-    def __init__(self, in_width, hidden_dims, out_dim):
+    def __init__(self, in_width, hidden_dims, out_dim, activation=nn.ELU):
         super().__init__()
-        self.i_calculator = _elu_mlp(in_width, *hidden_dims, out_dim)
+        self.i_calculator = _elu_mlp(in_width, *hidden_dims, out_dim, activation=activation)
 
     def forward(self, xt: torch.Tensor, zt: torch.Tensor, vt: torch.Tensor, all_initial: torch.Tensor):
         return self.i_calculator(torch.cat((all_initial, xt, zt, vt), dim=-1))

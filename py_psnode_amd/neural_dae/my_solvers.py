@@ -73,9 +73,21 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
         """The walk is the reference's own route, but on a HIP device it is ~100x slower than the fused one: never silent."""
         if self.fused == "auto" and tensor.device.type == "cuda" and not getattr(self, "_walk_warned", False):
             self._walk_warned = True
-            warnings.warn(f"{what}: this call is not fusable (needs fp32 HIP tensors, DE_Func/AE_Func-style ELU-MLPs, "
+            warnings.warn(f"{what}: this call is not fusable (needs fp32 HIP tensors, DE_Func/AE_Func-style MLPs with one activation "
+                          "of ELU / Tanh / Sigmoid / ReLU / LeakyReLU / Softplus -- other than ELU(1) on kernel 'auto' / 'generic' only --, "
                           "ODE_Event/DAE_Event callbacks; under autograd also a shape with a backward kernel and no teacher "
                           "forcing) -- stepping through the Python callables instead", RuntimeWarning, stacklevel=3)
+
+    def _act_kernel_ok(self, what, acts) -> bool:
+        """An activation other than ELU(1) runs on the generic kernels K0 / K5 only: kernel 'wave' / 'tile' / 'mfma' / 'wide' with one walks
+        under fused='auto' and raises under 'require'."""
+        if all(a is None for a in acts) or self.kernel in ("auto", "generic"):
+            return True
+        if self.fused == "require":
+            names = ", ".join(repr(a) for a in acts if a is not None)
+            raise UnsupportedShapeError(f"{what}: kernel={self.kernel!r} has no form for the activation {names}: activations other than "
+                                        "ELU(alpha=1) run on the generic kernels (kernel 'auto' / 'generic')")
+        return False
 
     def _check_events_now(self, event_t):
         return (self.check_events and event_t is not None and event_t.dim() == 3 and event_t.shape[1] > 1
@@ -98,32 +110,35 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
             raise ValueError("integrate_ODE: x_init and input_true_x exclude each other (teacher forcing starts every step from x[k])")
         if self.fused != "off":
             plan = _fused.plan_ode(x_func, x, z, all_initial, event_fn, jump_change_fn, t=t, x_init=x_init)
+            if plan is not None and not self._act_kernel_ok("integrate_ODE", plan[4:]):
+                plan = None
             if plan is not None:
-                layers, event_t, z_jump, needs_grad = plan
+                layers, event_t, z_jump, needs_grad, act = plan
                 if not needs_grad:
                     try:
                         return _fused.ode_integrate(self.method, layers, t, x if x_init is None else x_init.unsqueeze(0), z, all_initial,
                                                     event_t=event_t, z_jump=z_jump,
                                                     input_true_x=input_true_x, kernel=self.kernel,
-                                                    check_events=self._check_events_now(event_t))
+                                                    check_events=self._check_events_now(event_t), act=act)
                     except UnsupportedShapeError:      # no kernel covers the shape (too wide for LDS): user callables it is
                         if self.fused == "require":
                             raise
                 # training: fused forward + fused backward when the backward kernel covers the shape
                 elif not input_true_x and _autograd().ode_training_supported(self.method, layers, x.shape[-1], z.shape[-1], t.shape[0],
-                                                                             t.shape[1], kernel=self.kernel):
+                                                                             t.shape[1], kernel=self.kernel, act=act):
                     from ..autograd import fused_ode_integrate
                     return fused_ode_integrate(self.method, self.kernel, layers, t, x, z, all_initial, event_t, z_jump,
-                                               check_events=self._check_events_now(event_t), x_init=x_init)
-                # teacher-forced training (my_solvers.py:72-74): K4f in its recompute form; the dataset x gets no gradient
-                elif input_true_x and not x.requires_grad and self.kernel in ("auto", "mfma") and \
+                                               check_events=self._check_events_now(event_t), x_init=x_init, act=act)
+                # teacher-forced training (my_solvers.py:72-74): K4f in its recompute form (ELU(1) only); the dataset x gets no gradient
+                elif input_true_x and act is None and not x.requires_grad and self.kernel in ("auto", "mfma") and \
                         _fused.ode_backward_supported(self.method, layers, x.shape[-1], z.shape[-1], "wide"):
                     from ..autograd import fused_ode_integrate
                     return fused_ode_integrate(self.method, self.kernel, layers, t, x, z, all_initial, event_t, z_jump,
                                                check_events=self._check_events_now(event_t), input_true_x=True)
             if self.fused == "require":
-                raise NotFusableError("integrate_ODE: call is not fusable (needs fp32 HIP tensors, a DE_Func-style ELU-MLP "
-                                      "`x_dot`, ODE_Event callbacks; with autograd: a shape with a backward kernel, no teacher forcing)")
+                raise NotFusableError("integrate_ODE: call is not fusable (needs fp32 HIP tensors, a DE_Func-style MLP `x_dot` with one "
+                                      "activation of ELU / Tanh / Sigmoid / ReLU / LeakyReLU / Softplus, ODE_Event callbacks; with autograd: "
+                                      "a shape with a backward kernel, no teacher forcing)")
             self._note_walk("integrate_ODE", x)
         return self._walk_ode(x_func, t, x, z, all_initial, event_fn, jump_change_fn, input_true_x, x_init)
 
@@ -146,24 +161,27 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
                       input_true_x=False, input_true_i=False):
         if self.fused != "off":
             plan = _fused.plan_dae(x_init, x_func, i_func, z, v, i, all_initial, event_fn, jump_change_fn, t=t)
+            if plan is not None and not self._act_kernel_ok("integrate_DAE", plan[6:]):
+                plan = None
             if plan is not None:
-                de, ae, event_t, z_jump, v_jump, needs_grad = plan
+                de, ae, event_t, z_jump, v_jump, needs_grad, de_act, ae_act = plan
+                act = None if de_act is None and ae_act is None else (de_act, ae_act)
                 if not needs_grad:
                     try:
                         return _fused.dae_integrate(self.method, de, ae, x_init, t, x, z, v, i, all_initial, event_t=event_t,
                                                     z_jump=z_jump, v_jump=v_jump, input_true_x=input_true_x,
                                                     input_true_i=input_true_i, kernel=self.kernel,
-                                                    check_events=self._check_events_now(event_t))
+                                                    check_events=self._check_events_now(event_t), act=act)
                     except UnsupportedShapeError:
                         if self.fused == "require":
                             raise
                 elif not (input_true_x or input_true_i) and _autograd().dae_training_supported(
-                        self.method, de, ae, x_init.shape[-1], z.shape[-1], v.shape[-1], i.shape[-1], t.shape[0], t.shape[1]):
+                        self.method, de, ae, x_init.shape[-1], z.shape[-1], v.shape[-1], i.shape[-1], t.shape[0], t.shape[1], act=act):
                     from ..autograd import fused_dae_integrate
                     return fused_dae_integrate(self.method, self.kernel, de, ae, x_init, t, z, v, i, all_initial, event_t, z_jump, v_jump,
-                                               check_events=self._check_events_now(event_t))
-                # teacher-forced training (my_solvers.py:111-121): K7f in its recompute form; the dataset rows get no gradient
-                elif (input_true_x or input_true_i) and not (input_true_x and x.requires_grad) and not (input_true_i and i.requires_grad) \
+                                               check_events=self._check_events_now(event_t), act=act)
+                # teacher-forced training (my_solvers.py:111-121): K7f in its recompute form (ELU(1) only); the dataset rows get no gradient
+                elif act is None and (input_true_x or input_true_i) and not (input_true_x and x.requires_grad) and not (input_true_i and i.requires_grad) \
                         and x.shape[-1] == x_init.shape[-1] and self.kernel in ("auto", "mfma") and t.shape[0] >= 2 and \
                         _fused.dae_backward_wide_supported(self.method, de, ae, x_init.shape[-1], z.shape[-1], v.shape[-1], i.shape[-1]):
                     from ..autograd import fused_dae_integrate
@@ -172,7 +190,7 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
                                                input_true_i=input_true_i)
             if self.fused == "require":
                 raise NotFusableError("integrate_DAE: call is not fusable (needs fp32 HIP tensors, DE_Func/AE_Func-style "
-                                      "ELU-MLPs, DAE_Event callbacks; with autograd: a shape with a backward kernel; teacher forcing: hidden <= 128, dataset rows without grad)")
+                                      "MLPs with one activation each of ELU / Tanh / Sigmoid / ReLU / LeakyReLU / Softplus, DAE_Event callbacks; with autograd: a shape with a backward kernel; teacher forcing: hidden <= 128, dataset rows without grad)")
             self._note_walk("integrate_DAE", z if z.numel() else v)
         return self._walk_dae(x_init, x_func, i_func, t, x, z, v, i, all_initial, event_fn, jump_change_fn,
                               input_true_x, input_true_i)

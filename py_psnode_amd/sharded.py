@@ -245,7 +245,7 @@ def integrate_ode_sharded(method, de_layers, t, x, z, all_initial, event_t=None,
                           group=None, gather=True, local_fn: Optional[Callable] = None, table_fn: Optional[Callable] = None,
                           algo: str = "rccl", **kw):
     """Each rank passes ITS shard (t[T,Bl,1], x[T,Bl,xd], z[T,Bl,zd], all_initial[Bl,n], event_t/z_jump[Bl,nE,.]).
-    Returns the gathered [T, G*Bl, xd] (gather=True) or the local [T,Bl,xd]."""
+    Returns the gathered [T, G*Bl, xd] (gather=True) or the local [T,Bl,xd].  **kw goes to local_fn as it is (kernel=, act= ...)."""
     if local_fn is None:
         from . import fused
         local_fn = fused.ode_integrate
