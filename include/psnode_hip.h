@@ -244,7 +244,8 @@ int32_t psnode_gemm_tn_f32(const psnode_gemm_tn_args_f32* args, void* workspace,
  * --hidden 128), and the row-wise products of the latent-wide backward.  Wm[n][k] = W[n * w_stride_n + k * w_stride_k]: an nn.Linear
  * weight [N, K] as it is (w_stride_n = K, w_stride_k = 1) or read transposed (a [K, N] tensor: w_stride_n = 1, w_stride_k = N).
  * epi: 0 identity, 1 ELU(alpha = 1), 2 multiply by ELU'(Hh[r][n]) where Hh holds ELU OUTPUTS (the delta of a hidden layer).
- * bias may be NULL.  Row strides in elements; no workspace. */
+ * bias may be NULL.  Row strides in elements, ldx >= K, ldy >= N, ldh >= N; no workspace.  Any 4-byte aligned X / Hh / Y is taken:
+ * rows are read / written as float4 only where the base pointer is 16-byte aligned and the row stride a multiple of 4. */
 typedef struct {
     int64_t rows;
     int32_t K, N;

@@ -12,7 +12,8 @@
 // X[row j][16 q + 4 k .. + 3]; component c of that register is the B operand of MFMA (q, c), whose contraction slots are the columns
 // 16 q + 4 k + c -- any bijection of the columns onto (MFMA, slot) is valid as long as the weight image uses the same one, and this one makes
 // a row's loads 64 contiguous bytes per instruction.  Scalar path (K < 16 or unaligned: the encoders' first layer, the decoders' gradient):
-// column 4 m + k.  Output: lane (g, j), register r = Y[row j][16 nt + 4 g + r]: one float4 store per lane and output tile.
+// column 4 m + k.  Output: lane (g, j), register r = Y[row j][16 nt + 4 g + r]: one float4 store per lane and output tile (scalar stores
+// where Y's rows are not all 16-byte aligned; the same for the float4 loads of Hh).
 #include "psnode_common.h"
 
 namespace psnode {
@@ -25,6 +26,7 @@ struct LinRowsDev {
     float* Y;
     long long rows, ldx, ldy, ldh, w_sn, w_sk;
     int K, N, epi;
+    int vec_h, vec_y;           // float4 loads of Hh / stores of Y: row stride % 4 == 0 AND a 16-byte aligned base (host-side, lr_vec4)
 };
 
 __device__ __forceinline__ f4 lr_mfma(float a, float b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
@@ -102,7 +104,7 @@ __global__ __launch_bounds__(256) void linear_rows_kernel(const LinRowsDev a) {
                 if (a.epi == 2) {
                     const float* ph = a.Hh + row * a.ldh + n0;
                     f4 h = f4{0.f, 0.f, 0.f, 0.f};
-                    if (full && !(a.ldh & 3)) h = *reinterpret_cast<const f4*>(ph);
+                    if (full && a.vec_h) h = *reinterpret_cast<const f4*>(ph);
                     else {
 #pragma unroll
                         for (int r = 0; r < 4; ++r) h[r] = n0 + r < a.N ? ph[r] : 0.0f;
@@ -110,7 +112,7 @@ __global__ __launch_bounds__(256) void linear_rows_kernel(const LinRowsDev a) {
                     y = y * elu_grad_quad(h);
                 }
                 float* py = a.Y + row * a.ldy + n0;
-                if (full && !(a.ldy & 3)) *reinterpret_cast<f4*>(py) = y;
+                if (full && a.vec_y) *reinterpret_cast<f4*>(py) = y;
                 else {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) if (n0 + r < a.N) py[r] = y[r];
@@ -119,6 +121,10 @@ __global__ __launch_bounds__(256) void linear_rows_kernel(const LinRowsDev a) {
         }
     }
 }
+
+// A row tensor may be walked in float4 only if every row start is 16-byte aligned: the base AND the row stride (a sub-view at a 4-byte
+// offset with ld % 4 == 0 has neither property follow from the other)
+inline bool lr_vec4(const void* p, long long ld) { return !(ld & 3) && !(reinterpret_cast<uintptr_t>(p) & 15); }
 
 template <int KS, bool VEC>
 hipError_t lr_launch(const LinRowsDev& d, hipStream_t s) {
@@ -158,8 +164,10 @@ extern "C" int32_t psnode_linear_rows_f32(const psnode_linear_rows_args_f32* a, 
     d.X = a->X; d.W = a->W; d.bias = a->bias; d.Hh = a->Hh; d.Y = a->Y;
     d.rows = a->rows; d.ldx = a->ldx; d.ldy = a->ldy; d.ldh = a->ldh; d.w_sn = a->w_stride_n; d.w_sk = a->w_stride_k;
     d.K = a->K; d.N = a->N; d.epi = a->epi;
+    d.vec_h = a->epi == 2 && lr_vec4(a->Hh, a->ldh);
+    d.vec_y = lr_vec4(a->Y, a->ldy);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const bool vec = (a->K % 16 == 0) && !(a->ldx & 3) && !(reinterpret_cast<uintptr_t>(a->X) & 15);
+    const bool vec = (a->K % 16 == 0) && lr_vec4(a->X, a->ldx);
     hipError_t e;
     if (vec) {
         switch (a->K / 16) {

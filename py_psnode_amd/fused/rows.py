@@ -16,49 +16,73 @@ def _row_addressing(x: torch.Tensor):
     `x.permute(1, 0, 2)` of a [B,T,D] batch (neural_00_ODE_02_direct_encode.py:76) is read in place (two clones of the dataset per
     training step before round 5); anything else is flattened (a copy only if the flattening needs one)."""
     d = x.shape[-1]
-    if x.dim() == 3 and (d == 1 or x.stride(2) == 1) and x.stride(0) >= 0 and x.stride(1) >= d and x.shape[0] * x.shape[1] < 2 ** 32:
+    if x.dim() == 3 and (d == 1 or x.stride(2) == 1) and (x.shape[0] == 1 or x.stride(0) >= d) and x.stride(1) >= d \
+            and x.shape[0] * x.shape[1] < 2 ** 32:
         n0, n1 = x.shape[0], x.shape[1]
         if x.stride(0) == n1 * x.stride(1) or n0 == 1:
             return x, n0 * n1, x.stride(1), 0, 0
         return x, n0 * n1, x.stride(1), n1, x.stride(0)
-    x2 = x.reshape(-1, d)
-    if x2.stride(-1) != 1 and d > 1:
-        x2 = x2.contiguous()
-    return x2, x2.shape[0], max(x2.stride(0), d), 0, 0
+    x2 = _rows_arg(x.reshape(-1, d))
+    return x2, x2.shape[0], _ld(x2), 0, 0
+
+
+def _rows_arg(t2: torch.Tensor) -> torch.Tensor:
+    """A [R, n] row tensor as the row kernels read it: unit column stride, and a row stride of at least n.  A smaller row stride (the
+    stride-0 rows of an `expand`, a broadcast upstream gradient) is never handed to a kernel -- it would walk row r at r * n, past the
+    storage -- but copied once here."""
+    if (t2.shape[1] > 1 and t2.stride(1) != 1) or (t2.shape[0] > 1 and t2.stride(0) < t2.shape[1]):
+        return t2.contiguous()
+    return t2
+
+
+def _ld(t2: torch.Tensor) -> int:
+    """The row stride a kernel gets for a `_rows_arg` tensor (a single row: its width)."""
+    return t2.stride(0) if t2.shape[0] > 1 else t2.shape[1]
 
 
 # ----------------------------------------------------------------------------- K11 / K10: the row MLPs at every other width <= 128
 def linear_rows(x2: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor] = None, epi: int = 0, hh: Optional[torch.Tensor] = None,
-                transposed: bool = False, out_shape=None) -> torch.Tensor:
-    """K11 (psnode_linear_rows_f32): Y = epi(x2 @ Wm^T + bias) over the rows of a contiguous-row fp32 [R, K] tensor.  Wm = W ([N, K], an
-    nn.Linear weight) or, with transposed=True, W^T (W is [K, N]: `x2 @ W`).  epi 0 identity / 1 ELU / 2 multiply by ELU'(hh), hh = ELU
-    outputs [R, N]."""
+                transposed: bool = False, out_shape=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """K11 (psnode_linear_rows_f32): Y = epi(x2 @ Wm^T + bias) over the rows of an fp32 [R, K] tensor.  Wm = W ([N, K], an nn.Linear
+    weight) or, with transposed=True, W^T (W is [K, N]: `x2 @ W`).  epi 0 identity / 1 ELU / 2 multiply by ELU'(hh), hh = ELU outputs
+    [R, N].  out: an [R, N] row tensor to write Y into (any row stride >= N) instead of a new one.  Every tensor must be fp32 on x2's
+    device (TypeError / ValueError otherwise, before any launch)."""
     lib = _lib.load()
     dev = x2.device
-    if x2.stride(-1) != 1:
-        x2 = x2.contiguous()
+    x2 = _rows_arg(_f32_dev(x2, dev, "linear_rows: x"))
     R, K = x2.shape
-    Wc = W.detach()
+    Wc = _f32_dev(W, dev, "linear_rows: W")
+    if Wc.dim() != 2 or (Wc.shape[0] if transposed else Wc.shape[1]) != K:
+        raise ValueError(f"linear_rows: W {tuple(Wc.shape)}{' (transposed)' if transposed else ''} does not take rows of width {K}")
     N = Wc.shape[1] if transposed else Wc.shape[0]
     a = _lib.LinearRowsArgsF32()
     a.rows, a.K, a.N = R, K, N
-    a.X, a.ldx = x2.data_ptr(), x2.stride(0) if R > 1 else K
+    a.X, a.ldx = x2.data_ptr(), _ld(x2)
     a.W = Wc.data_ptr()
     a.w_stride_n, a.w_stride_k = (Wc.stride(1), Wc.stride(0)) if transposed else (Wc.stride(0), Wc.stride(1))
     bc = None
     if bias is not None:
-        bc = bias.detach().contiguous()
+        bc = _f32_dev(bias, dev, "linear_rows: bias").contiguous()
+        if bc.numel() != N:
+            raise ValueError(f"linear_rows: bias has {bc.numel()} elements, expected N = {N}")
         a.bias = bc.data_ptr()
     a.epi = epi
     if epi == 2:
-        if hh is None or hh.shape != (R, N) or hh.stride(-1) != 1:
-            raise ValueError("linear_rows(epi=2): hh must be a contiguous-row [R, N] tensor of ELU outputs")
-        a.Hh, a.ldh = hh.data_ptr(), hh.stride(0) if R > 1 else N
+        if hh is None or hh.shape != (R, N):
+            raise ValueError("linear_rows(epi=2): hh must be an [R, N] tensor of ELU outputs")
+        hh = _rows_arg(_f32_dev(hh, dev, "linear_rows: hh"))
+        a.Hh, a.ldh = hh.data_ptr(), _ld(hh)
     with torch.cuda.device(dev):
-        # (out_shape: the caller's [..., N] shape with prod(...) = R -- allocated in that shape, so that an autograd Function can hand it out
-        #  without a view created inside its forward, which autograd refuses to see modified in place: `x_pred[0] = x0` of the DAE script)
-        y = _empty(tuple(out_shape) if out_shape is not None else (R, N), dtype=torch.float32, device=dev)
-        a.Y, a.ldy = y.data_ptr(), N
+        if out is not None:         # rows written in place: [R, N] with unit column stride and row stride >= N
+            if out.shape != (R, N) or out.dtype != torch.float32 or out.device != dev or (N > 1 and out.stride(1) != 1) \
+                    or (R > 1 and out.stride(0) < N):
+                raise ValueError(f"linear_rows: out must be an fp32 [R={R}, N={N}] row tensor on {dev}")
+            y = out
+        else:
+            # (out_shape: the caller's [..., N] shape with prod(...) = R -- allocated in that shape, so that an autograd Function can hand it
+            #  out without a view created inside its forward, which autograd refuses to see modified in place: `x_pred[0] = x0` of the DAE script)
+            y = _empty(tuple(out_shape) if out_shape is not None else (R, N), dtype=torch.float32, device=dev)
+        a.Y, a.ldy = y.data_ptr(), (_ld(y) if out is not None else N)
         if not lib.psnode_linear_rows_supported(ctypes.byref(a)):
             raise ValueError(f"linear_rows: K = {K}, N = {N} outside the kernel's class (<= 128)")
         if R:
@@ -70,7 +94,8 @@ def _pad4(t2: torch.Tensor) -> torch.Tensor:
     """[R, n] -> contiguous [R, 4 ceil(n / 4)] (zero columns behind): K10 contracts float4 row segments."""
     n = t2.shape[1]
     if n % 4 == 0:
-        return t2 if t2.stride(1) == 1 and t2.stride(0) % 4 == 0 and t2.data_ptr() % 16 == 0 else t2.contiguous()
+        t2 = _rows_arg(t2)
+        return t2 if _ld(t2) % 4 == 0 and t2.data_ptr() % 16 == 0 else t2.contiguous()
     out = torch.zeros((t2.shape[0], (n + 3) // 4 * 4), dtype=t2.dtype, device=t2.device)
     out[:, :n] = t2
     return out
@@ -78,10 +103,15 @@ def _pad4(t2: torch.Tensor) -> torch.Tensor:
 
 def wide_rows_class(layers) -> bool:
     """Linear(in, H) ELU Linear(H, out) with every width <= 128: what K11 / K10 carry (any width; K3b keeps hidden 16 / 64)."""
-    if layers is None or len(layers) != 2:
+    if layers is None or len(layers) != 2 or not _params_f32_on(layers, layers[0][0].device):
         return False
     H, din, dout = layers[0][0].shape[0], layers[0][0].shape[1], layers[1][0].shape[0]
     return layers[1][0].shape[1] == H and 1 <= H <= 128 and 1 <= din <= 128 and 1 <= dout <= 128
+
+
+def _params_f32_on(layers, dev) -> bool:
+    """Every weight and bias an fp32 tensor on the HIP device `dev` (what the row kernels read; torch reports anything else)."""
+    return dev.type == "cuda" and all(p is not None and p.dtype == torch.float32 and p.device == dev for wb in layers for p in wb)
 
 
 def _k3b_class(layers) -> bool:
@@ -118,18 +148,16 @@ class _WideRowsMlp(torch.autograd.Function):
         x2, h, w1, w2 = ctx.saved_tensors
         w1, w2 = w1.detach(), w2.detach()
         dout, H, din = w2.shape[0], w2.shape[1], w1.shape[1]
-        g2 = gy.reshape(-1, dout)
-        if g2.stride(-1) != 1:
-            g2 = g2.contiguous()
+        g2 = _rows_arg(gy.reshape(-1, dout))        # (a broadcast upstream gradient -- `y.sum()` -- arrives with stride-0 rows)
         delta = linear_rows(g2, w2, None, epi=2, hh=h, transposed=True)                 # [R, H] = (g2 @ W2) * ELU'(h)
         gin = linear_rows(delta, w1, None, transposed=True, out_shape=ctx.in_shape) if ctx.needs_input_grad[0] else None
-        hp = _pad4(h)
-        if hp.shape[1] <= 128 and ((dout + 3) // 4 * 4) <= 128:
-            c2, s2 = gemm_tn(_pad4(g2), hp, want_colsum=True)
+        both2 = gemm_tn(_pad4(g2), _pad4(h), want_colsum=True)
+        both1 = gemm_tn(_pad4(delta), _pad4(x2), want_colsum=True) if both2 is not None else None
+        if both1 is not None:
+            (c2, s2), (c1, s1) = both2, both1
             dW2, db2 = c2[:dout, :H], s2[:dout]
-            c1, s1 = gemm_tn(_pad4(delta), _pad4(x2), want_colsum=True)
             dW1, db1 = c1[:H, :din], s1[:H]
-        else:
+        else:       # outside K10's class (gemm_tn said None): the library products
             dW2, db2, dW1, db1 = g2.t() @ h, g2.sum(0), delta.t() @ x2, delta.sum(0)
         return gin, dW1.contiguous(), db1.contiguous(), dW2.contiguous(), db2.contiguous()
 
@@ -166,9 +194,7 @@ def mlp_rows_backward(layers: Layers, inp: torch.Tensor, grad_out: torch.Tensor,
     if not lib.psnode_mlp_rows_supported(ctypes.byref(m)):
         raise ValueError("mlp_rows_backward: unsupported MLP shape")
     x2, rows, rstride, inner, outer = _row_addressing(_f32_dev(inp, dev, "input"))
-    g2 = _f32_dev(grad_out, dev, "grad_out").reshape(-1, grad_out.shape[-1])
-    if g2.stride(-1) != 1:
-        g2 = g2.contiguous()
+    g2 = _rows_arg(_f32_dev(grad_out, dev, "grad_out").reshape(-1, grad_out.shape[-1]))
     if g2.shape[0] != rows or g2.shape[1] != layers[-1][0].shape[0]:
         raise ValueError(f"mlp_rows_backward: grad_out {tuple(grad_out.shape)} does not match input {tuple(inp.shape)}")
     with torch.cuda.device(dev):
@@ -178,7 +204,7 @@ def mlp_rows_backward(layers: Layers, inp: torch.Tensor, grad_out: torch.Tensor,
         nbytes = lib.psnode_mlp_rows_backward_workspace_bytes(ctypes.byref(m), rows)
         ws = _empty(nbytes + 256, dtype=torch.uint8, device=dev)
         wp, wn = _aligned_ptr(ws)
-        rc = lib.psnode_mlp_rows_backward_f32(ctypes.byref(m), rows, x2.data_ptr(), rstride, inner, outer, g2.data_ptr(), g2.stride(0),
+        rc = lib.psnode_mlp_rows_backward_f32(ctypes.byref(m), rows, x2.data_ptr(), rstride, inner, outer, g2.data_ptr(), _ld(g2),
                                               gin.data_ptr() if gin is not None else None, inp.shape[-1], gp.data_ptr(), wp, wn,
                                               torch.cuda.current_stream(dev).cuda_stream)
     _lib.check(rc, "psnode_mlp_rows_backward_f32")
@@ -222,9 +248,7 @@ def mlp_rows_backward_multi(layers: Layers, inps, grad_outs, need_grad_in):
         sets = []
         for k in live:
             x2, rows, rstride, inner, outer = _row_addressing(_f32_dev(inps[k], dev, "input"))
-            g2 = _f32_dev(grad_outs[k], dev, "grad_out").reshape(-1, grad_outs[k].shape[-1])
-            if g2.stride(-1) != 1:
-                g2 = g2.contiguous()
+            g2 = _rows_arg(_f32_dev(grad_outs[k], dev, "grad_out").reshape(-1, grad_outs[k].shape[-1]))
             if g2.shape[0] != rows or g2.shape[1] != layers[-1][0].shape[0]:
                 raise ValueError(f"mlp_rows_backward_multi: grad_out {tuple(grad_outs[k].shape)} does not match input {tuple(inps[k].shape)}")
             sets.append((k, x2, rows, rstride, inner, outer, g2, int(lib.psnode_mlp_rows_backward_parts(ctypes.byref(m), rows))))
@@ -237,7 +261,7 @@ def mlp_rows_backward_multi(layers: Layers, inps, grad_outs, need_grad_in):
         for k, x2, rows, rstride, inner, outer, g2, parts in sets:
             gin = _empty(tuple(inps[k].shape), dtype=torch.float32, device=dev) if need_grad_in[k] else None
             gins[k] = gin
-            _lib.check(lib.psnode_mlp_rows_backward_f32(ctypes.byref(m), rows, x2.data_ptr(), rstride, inner, outer, g2.data_ptr(), g2.stride(0),
+            _lib.check(lib.psnode_mlp_rows_backward_f32(ctypes.byref(m), rows, x2.data_ptr(), rstride, inner, outer, g2.data_ptr(), _ld(g2),
                                                         gin.data_ptr() if gin is not None else None, inps[k].shape[-1], None, wp + off,
                                                         parts * npar * 4, st), "psnode_mlp_rows_backward_f32")
             off += parts * npar * 4
@@ -305,9 +329,7 @@ def recon_rows_backward(enc_layers: Layers, dec_layers: Layers, inp: torch.Tenso
     keep: list = []
     me, md = _mlp(enc_layers, dev, "encoder", keep), _mlp(dec_layers, dev, "decoder", keep)
     x2, rows, rstride, inner, outer = _row_addressing(_f32_dev(inp, dev, "input"))
-    g2 = _f32_dev(grad_out, dev, "grad_out").reshape(-1, grad_out.shape[-1])
-    if g2.stride(-1) != 1:
-        g2 = g2.contiguous()
+    g2 = _rows_arg(_f32_dev(grad_out, dev, "grad_out").reshape(-1, grad_out.shape[-1]))
     if g2.shape[0] != rows or g2.shape[1] != dec_layers[-1][0].shape[0]:
         raise ValueError(f"recon_rows_backward: grad_out {tuple(grad_out.shape)} does not match input {tuple(inp.shape)}")
     with torch.cuda.device(dev):
@@ -317,7 +339,7 @@ def recon_rows_backward(enc_layers: Layers, dec_layers: Layers, inp: torch.Tenso
         ws = _empty(nbytes + 256, dtype=torch.uint8, device=dev)
         wp, wn = _aligned_ptr(ws)
         _lib.check(lib.psnode_recon_rows_backward_f32(ctypes.byref(me), ctypes.byref(md), rows, x2.data_ptr(), rstride, inner, outer, g2.data_ptr(),
-                                                      g2.stride(0), gp.data_ptr(), wp, wn, torch.cuda.current_stream(dev).cuda_stream),
+                                                      _ld(g2), gp.data_ptr(), wp, wn, torch.cuda.current_stream(dev).cuda_stream),
                    "psnode_recon_rows_backward_f32")
     ne = sum(w.numel() + b.numel() for w, b in enc_layers)
     return _split_grads(gp[:ne], enc_layers), _split_grads(gp[ne:], dec_layers)
@@ -354,12 +376,15 @@ def mlp_rows_autograd(seq, inp: torch.Tensor) -> torch.Tensor:
 
 
 def rows_layers_of(seq, inp: torch.Tensor, allow_grad: bool = False):
-    """Layers if `seq(inp)` can run on the row kernel (2-layer ELU-MLP, hidden 16 / 64, fp32 HIP tensor); with autograd in play
+    """Layers if `seq(inp)` can run on the row kernels (2-layer ELU-MLP of widths <= 128, fp32 HIP input and parameters on one device,
+    input width = the first layer's); with autograd in play
     only when `allow_grad` (the caller then goes through mlp_rows_autograd)."""
     if inp.device.type != "cuda" or inp.dtype != torch.float32 or inp.numel() == 0:
         return None
     layers = sequential_layers(seq)
     if layers is None or len(layers) != 2:
+        return None
+    if not _params_f32_on(layers, inp.device) or inp.shape[-1] != layers[0][0].shape[1]:      # the plain module runs; torch raises as always
         return None
     if not _k3b_class(layers) and not wide_rows_class(layers):      # K3b at hidden 16 / 64, K11 / K10 at every other width <= 128
         return None

@@ -15,9 +15,15 @@ from py_psnode_amd import models
 from py_psnode_amd import neural_dae as nd
 
 SOLVERS = {"euler": nd.Euler, "midpoint": nd.Midpoint, "rk4": nd.RK4}
+METHODS = tuple(SOLVERS)
 TAGS = ["ode01", "dae01", "ode02", "ode02_h64", "dae02", "dae02_h64", "dae02_z0",
         # round 3 (make_goldens_r3.py): the scripts' argparse default --hidden 128 and --hidden 32 -- K4f (ODE) / K7w (DAE) on the GPU
         "ode01_h128", "ode01_h32", "dae01_h128", "dae01_h32"]
+# make_goldens_r5.py: the direct_encode models at hidden widths outside {16, 64}, with the methods each set holds (fixture size).  On the GPU:
+# row MLPs on K11 / K10 at every one of them; latent integrator K3w + K9w at 128 and 36 (H % 4 == 0), K0 + K5 at 30 (no K3w width)
+TAGS_R5 = {"ode02_h128": ("euler", "rk4"), "dae02_h128": ("euler",),
+           "ode02_h36": METHODS, "dae02_h36": METHODS, "dae02_z0_h36": METHODS, "ode02_h30": METHODS}
+CASES = [(m, t) for m in METHODS for t in TAGS] + [(m, t) for t, ms in TAGS_R5.items() for m in ms]
 TOL_CPU = 2e-5      # same ATen ops in (almost) the same order as the reference
 TOL_GPU = 1e-5      # ~6 x the worst achieved error over every model x method x tensor (1.63e-6: profiles/r05_grad_accuracy_report.txt; the reference's
                     # own fp32 gradients sit 1.2e-6 from an fp64 walk)
@@ -28,9 +34,10 @@ def _build(tag):
         return models.ODE_Model(8, 2, int(tag.split("_h")[1]) if "_h" in tag else 64)
     if tag.startswith("dae01"):
         return models.DAE_Model(8, 2, 2, 2, int(tag.split("_h")[1]) if "_h" in tag else 64)
+    H = int(tag.split("_h")[1]) if "_h" in tag else 16
     if tag.startswith("ode02"):
-        return models.ODE_Model(8, 2, 64 if tag.endswith("h64") else 16, direct_encode=True)
-    return models.DAE_Model(8, 0 if tag.endswith("z0") else 2, 2, 2, 64 if tag.endswith("h64") else 16, direct_encode=True)
+        return models.ODE_Model(8, 2, H, direct_encode=True)
+    return models.DAE_Model(8, 0 if "_z0" in tag else 2, 2, 2, H, direct_encode=True)
 
 
 def _close(a, b, what, tol):
@@ -78,29 +85,31 @@ def _check(tag, method, d, m, res, leaves, tol):
             assert a.grad is None or float(a.grad.abs().max()) == 0.0, f"{tag} {method}: reference leaves {k} without gradient"
 
 
-@pytest.mark.parametrize("tag", TAGS)
-@pytest.mark.parametrize("method", ["euler", "midpoint", "rk4"])
+@pytest.mark.parametrize("method,tag", CASES)
 def test_walk_backward_matches_reference_gradients(tag, method):
     d, m, res, leaves = _run_model(tag, method, "cpu", "auto")
     _check(tag, method, d, m, res, leaves, TOL_CPU)
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("tag", TAGS)
-@pytest.mark.parametrize("method", ["euler", "midpoint", "rk4"])
+@pytest.mark.parametrize("method,tag", CASES)
 def test_fused_backward_matches_reference_gradients(tag, method):
     """solver.fused = 'require': the fused forward + fused backward kernels must take the call (K4 ode01, K7 dae01, K8 ode02,
-    K9 ode02_h64 / dae02_h64, the single-wave latent DAE backward for dae02 / dae02_z0; encoders/decoders on the row kernels)."""
+    K9 ode02_h64 / dae02_h64, the single-wave latent DAE backward for dae02 / dae02_z0; K3w + K9w for the latent integrator at hidden
+    128 / 36, K0 + K5 at hidden 30; encoders/decoders on the row kernels K3b at hidden 16 / 64, K11 / K10 at the other widths --
+    test_direct_encode_wide_models_take_the_intended_kernels checks which ran)."""
     d, m, res, leaves = _run_model(tag, method, "cuda", "require")
     _check(tag, method, d, m, res, leaves, TOL_GPU)
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("tag", ["ode01", "dae01", "ode02_h64", "dae02_h64", "ode01_h128", "dae01_h128"])
+@pytest.mark.parametrize("tag", ["ode01", "dae01", "ode02_h64", "dae02_h64", "ode01_h128", "dae01_h128", "ode02_h30"])
 @pytest.mark.parametrize("method", ["euler", "rk4"])
 def test_fused_backward_recompute_route_matches_reference_gradients(tag, method, monkeypatch):
-    """The same with PSNODE_SAVE_ACTIVATIONS = 0: the backward kernels recompute the forward (K4 / K7 / K9 / K4f / K7f `REC = true`) instead
-    of reading what the training forward saved (the default route of these models, covered by the test above)."""
+    """The same with PSNODE_SAVE_ACTIVATIONS = 0: the backward kernels recompute the forward (K4 / K7 / K9 / K4f / K7f `REC = true`, K5 for
+    ode02_h30) instead of reading what the training forward saved (the default route of these models, covered by the test above).  The
+    latent-wide widths (ode02_h128, dae02_h128, *_h36) are not here: K9w has no recompute form -- with saving off the solver walks the
+    user's callables, which `fused="require"` refuses."""
     from py_psnode_amd import autograd as pag
     monkeypatch.setattr(pag, "SAVE_ACTIVATIONS", "0")
     d, m, res, leaves = _run_model(tag, method, "cuda", "require")
@@ -122,6 +131,68 @@ def test_latent_models_save_their_activations_by_default(tag):
     finally:
         fused.ode_backward, fused.dae_backward = orig_o, orig_d
     assert seen == [tag.endswith("_h64")], seen
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("tag", list(TAGS_R5))
+def test_direct_encode_wide_models_take_the_intended_kernels(tag, monkeypatch):
+    """The route behind the TAGS_R5 cases of test_fused_backward_matches_reference_gradients, counted at its entry points (a fixture that
+    fell back to nn.Sequential or to library GEMMs would pass the gradient check too): every encoder / decoder on K11 both ways with its
+    weight gradients on K10 (gemm_tn never None); the latent integrator on the saving forward K3w and the adjoint sweep K9w
+    (latent_backward_wide, whose contractions include K10) at H % 4 == 0, on K0 + the recomputing K5 (ode_backward without saved rows)
+    at hidden 30."""
+    from py_psnode_amd import fused
+    from py_psnode_amd.fused import _common, backward_dae, backward_ode, latent, rows
+    n = {k: 0 for k in ("rows_fwd", "rows_bwd", "k10_rows", "k10_rows_none", "k10_latent", "k10_latent_none", "k9w", "save_fwd",
+                                "plain_fwd", "k5")}
+    W = rows._WideRowsMlp
+    fwd, bwd = W.forward, W.backward
+
+    def count(key, fn, pred=lambda *a, **k: True):
+        def f(*a, **k):
+            n[key] += bool(pred(*a, **k))
+            return fn(*a, **k)
+        return f
+
+    def k10(key, fn):
+        def f(*a, **k):
+            r = fn(*a, **k)
+            if key != "k10_rows" or in_rows_bwd:
+                n[key if r is not None else key + "_none"] += 1
+            return r
+        return f
+
+    in_rows_bwd = False
+
+    def rows_bwd(*a, **k):
+        nonlocal in_rows_bwd
+        n["rows_bwd"] += 1
+        in_rows_bwd = True
+        try:
+            return bwd(*a, **k)
+        finally:
+            in_rows_bwd = False
+
+    monkeypatch.setattr(W, "forward", staticmethod(count("rows_fwd", fwd)))
+    monkeypatch.setattr(W, "backward", staticmethod(rows_bwd))
+    monkeypatch.setattr(_common, "gemm_tn", k10("k10_rows", _common.gemm_tn))          # rows.py imports it at the call (counted there only)
+    monkeypatch.setattr(latent, "gemm_tn", k10("k10_latent", latent.gemm_tn))
+    for mod in (backward_ode, backward_dae):
+        monkeypatch.setattr(mod, "latent_backward_wide", count("k9w", mod.latent_backward_wide))
+    for name in ("ode_integrate", "dae_integrate"):
+        f = getattr(fused, name)
+        monkeypatch.setattr(fused, name, count("save_fwd", count("plain_fwd", f, lambda *a, **k: not k.get("save")), lambda *a, **k: k.get("save")))
+    monkeypatch.setattr(fused, "ode_backward", count("k5", fused.ode_backward, lambda *a, **k: k.get("saved") is None))
+    method = TAGS_R5[tag][-1]
+    d, m, res, leaves = _run_model(tag, method, "cuda", "require")
+    _check(tag, method, d, m, res, leaves, TOL_GPU)
+    mlps = 3 if tag.startswith("ode") else (5 if "_z0" in tag else 6)      # ODE: x, z encoders, x decoder; DAE: x, [z,] v, i encoders, x, i decoders
+    assert n["rows_fwd"] >= mlps and n["rows_bwd"] >= mlps, n                 # (one node per row set: grid rows, first rows, jump rows)
+    assert n["k10_rows"] == 2 * n["rows_bwd"] and n["k10_rows_none"] == 0, n
+    if int(tag.split("_h")[1]) % 4 == 0:
+        assert n["save_fwd"] == 1 and n["plain_fwd"] == 0 and n["k9w"] == 1 and n["k10_latent"] >= 1 and n["k10_latent_none"] == 0, n
+    else:
+        assert n["save_fwd"] == 0 and n["plain_fwd"] == 1 and n["k9w"] == 0 and n["k5"] == 1, n
 
 
 @pytest.mark.gpu
