@@ -614,6 +614,21 @@ int32_t psnode_dae_kernel_for(const psnode_dae_args_f32* args);
  *   PSNODE_ACT_LEAKY_RELU  alpha = negative slope >= 0   x > 0 ? x : alpha x                       h > 0 ? 1 : alpha
  *   PSNODE_ACT_SOFTPLUS    beta > 0, threshold           beta x > threshold ? x : log1p(e^(beta x)) / beta
  *                                                                                                  beta h > threshold ? 1 : 1 - e^(-beta h)
+ * The pre-activation family (kind bit 5, value 32, set): no parameters (alpha / beta / threshold are ignored), and the derivative is a
+ * function of the PRE-activation u, which K5's pre-activation build keeps in LDS next to each hidden layer's output (DESIGN.md
+ * "The pre-activation build"):
+ *   PSNODE_ACT_SILU        -                             u sigma(u)                                sigma(u) (1 + u (1 - sigma(u)))
+ *   PSNODE_ACT_GELU        -    (erf form)               u Phi(u)                                  Phi(u) + u phi(u)
+ *   PSNODE_ACT_GELU_TANH   -                             u (1 + t) / 2,                            (1 + t) / 2 + u (1 - t^2) c (1 + 3 k u^2) / 2
+ *                                                        t = tanh(c (u + k u^3)), c = sqrt(2 / pi), k = 0.044715
+ *   PSNODE_ACT_MISH        -                             u tanh(sp), sp = log1p(e^u)               tanh(sp) + u (1 - tanh^2(sp)) sigma(u)
+ *   (sigma: the logistic function; Phi, phi: the standard normal CDF and density.)
+ *   The DE and AE of a DAE may use activations of different families.  Kinds 6..31 and >= 36 are unknown.
+ *   The backward of this family needs LDS for u as well (per hidden unit 20 floats on K5's staged path, 16 on its register / streamed
+ *   paths, next to the layer outputs), so its _act_supported queries answer from the pre build's own fit, which ends before the other
+ *   kinds' does: e.g. hidden 160 x 3 with z_dim 2 fits up to x_dim 24 and not at x_dim 32 (where Tanh still fits).  Such shapes answer 0
+ *   and give PSNODE_ERR_UNSUPPORTED.  The forward (K0) needs no u: it fits wherever the other kinds do (DESIGN.md "The pre-activation
+ *   build").
  * Rules of every _act entry point:
  *   - a NULL act, or ELU with alpha == 1, is ELU(1): the call behaves exactly like the entry point without _act;
  *   - any other act runs the generic kernels only (K0 forward, K5 backward): `kernel` must be PSNODE_KERNEL_AUTO or _GENERIC (the MFMA
@@ -622,7 +637,9 @@ int32_t psnode_dae_kernel_for(const psnode_dae_args_f32* args);
  * The _act_supported queries answer 1 / 0 for the same rules (dims only, like the queries without _act); an invalid act is 0.
  * Workspace sizes are those of the entry points without _act. */
 typedef enum {
-    PSNODE_ACT_ELU = 0, PSNODE_ACT_TANH = 1, PSNODE_ACT_SIGMOID = 2, PSNODE_ACT_RELU = 3, PSNODE_ACT_LEAKY_RELU = 4, PSNODE_ACT_SOFTPLUS = 5
+    PSNODE_ACT_ELU = 0, PSNODE_ACT_TANH = 1, PSNODE_ACT_SIGMOID = 2, PSNODE_ACT_RELU = 3, PSNODE_ACT_LEAKY_RELU = 4, PSNODE_ACT_SOFTPLUS = 5,
+    PSNODE_ACT_PRE_FAMILY = 32,   /* bit 5: the derivative needs the pre-activation */
+    PSNODE_ACT_SILU = 32, PSNODE_ACT_GELU = 33, PSNODE_ACT_GELU_TANH = 34, PSNODE_ACT_MISH = 35
 } psnode_act_kind;
 
 typedef struct {

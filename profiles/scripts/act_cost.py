@@ -1,8 +1,9 @@
 """Cost of hidden-layer activations other than ELU(1) on the generic kernels (DESIGN.md "Activations").
 
 ODE_01 shape (x 8, z 2, 3 x 64 hidden), RK4, B = 4096, T = 1000, kernel = "generic" on both sides: the forward K0 alone and a training
-step (K0 forward + K5 backward, `fused.ode_integrate` + `fused.ode_backward`) for ELU(1), Tanh, Softplus and ReLU, and the same Tanh
-model stepped through the Python callables (the route such a model took before the activation kernels: one forward, one backward).
+step (K0 forward + K5 backward, `fused.ode_integrate` + `fused.ode_backward`) for ELU(1), Tanh, Softplus and ReLU, the pre-activation
+family SiLU, GELU, GELU(tanh) and Mish (K0 / K5's pre builds), and the same Tanh and SiLU models stepped through the Python callables (the
+route such a model took before its kernels: one forward, one backward).
 
     python profiles/scripts/act_cost.py [--reps 5] [--out FILE]
 """
@@ -50,12 +51,14 @@ def main():
     a0 = torch.cat((x[0], z[0]), -1)
     G = torch.randn(T, B, xd, generator=g).cuda()
     lines = [f"# {torch.cuda.get_device_name(0)}  ODE_01 RK4 B={B} T={T} kernel=generic, median (min) of {args.reps} runs, ms"]
-    acts = {"ELU(1)": nn.ELU, "Tanh": nn.Tanh, "Softplus": nn.Softplus, "ReLU": nn.ReLU}
+    acts = {"ELU(1)": nn.ELU, "Tanh": nn.Tanh, "Softplus": nn.Softplus, "ReLU": nn.ReLU, "SiLU": nn.SiLU, "GELU": nn.GELU,
+            "GELU(tanh)": lambda: nn.GELU(approximate="tanh"), "Mish": nn.Mish}
+    fused_ms = {}
     base = {}
     for name, A in acts.items():
         torch.manual_seed(0)
         de = models.DE_Func(xd + zd, (64, 64, 64), xd, activation=A).cuda()
-        layers, act = fused.sequential_mlp(de.x_dot)
+        layers, act = fused.sequential_mlp_any(de.x_dot)
         layers = [(w.detach(), b.detach()) for w, b in layers]
         fwd = lambda: fused.ode_integrate("rk4", layers, t, x, z, a0, kernel="generic", act=act)
         xs = fwd()
@@ -65,30 +68,31 @@ def main():
             fused.ode_backward("rk4", layers, t, z, a0, xs_, G, kernel="generic", act=act)
         f_med, f_min = timed(fwd, args.reps)
         s_med, s_min = timed(step, args.reps)
+        fused_ms[name] = (f_med, s_med)
         base.setdefault("fwd", f_med)
         base.setdefault("step", s_med)
         lines.append(f"{name:10s} forward K0 {f_med:8.2f} ({f_min:8.2f})  x{f_med / base['fwd']:.3f} of ELU(1)   "
                      f"training step K0+K5 {s_med:8.2f} ({s_min:8.2f})  x{s_med / base['step']:.3f} of ELU(1)")
         assert torch.isfinite(xs).all()
-    # the same Tanh model through the Python callables (fused = "off"): one forward, one training step
-    torch.manual_seed(0)
-    de = models.DE_Func(xd + zd, (64, 64, 64), xd, activation=nn.Tanh).cuda()
-    s = nd.RK4()
-    s.fused = "off"
-    with torch.no_grad():
+    # the same Tanh / SiLU models through the Python callables (fused = "off"): one forward, one training step
+    for name, A in (("Tanh", nn.Tanh), ("SiLU", nn.SiLU)):
+        torch.manual_seed(0)
+        de = models.DE_Func(xd + zd, (64, 64, 64), xd, activation=A).cuda()
+        s = nd.RK4()
+        s.fused = "off"
+        with torch.no_grad():
+            t0 = time.perf_counter()
+            s.integrate_ODE(x_func=de, t=t, x=x, z=z, all_initial=a0)
+            torch.cuda.synchronize()
+            walk_f = (time.perf_counter() - t0) * 1e3
         t0 = time.perf_counter()
-        s.integrate_ODE(x_func=de, t=t, x=x, z=z, all_initial=a0)
+        xs = s.integrate_ODE(x_func=de, t=t, x=x, z=z, all_initial=a0)
+        (xs * G).sum().backward()
         torch.cuda.synchronize()
-        walk_f = (time.perf_counter() - t0) * 1e3
-    t0 = time.perf_counter()
-    xs = s.integrate_ODE(x_func=de, t=t, x=x, z=z, all_initial=a0)
-    (xs * G).sum().backward()
-    torch.cuda.synchronize()
-    walk_s = (time.perf_counter() - t0) * 1e3
-    tanh_f = float(lines[2].split("forward K0")[1].split()[0])
-    tanh_s = float(lines[2].split("training step K0+K5")[1].split()[0])
-    lines.append(f"Tanh walk  forward    {walk_f:8.1f}  ({walk_f / tanh_f:.1f}x the fused Tanh forward)   "
-                 f"training step {walk_s:8.1f}  ({walk_s / tanh_s:.1f}x the fused Tanh step)")
+        walk_s = (time.perf_counter() - t0) * 1e3
+        f_ms, s_ms = fused_ms[name]
+        lines.append(f"{name + ' walk':10s} forward    {walk_f:8.1f}  ({walk_f / f_ms:.1f}x the fused {name} forward)   "
+                     f"training step {walk_s:8.1f}  ({walk_s / s_ms:.1f}x the fused {name} step)")
     text = "\n".join(lines)
     print(text)
     if args.out:

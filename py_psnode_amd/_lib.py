@@ -81,6 +81,8 @@ class ActF32(ctypes.Structure):
 
 
 ACT_ELU, ACT_TANH, ACT_SIGMOID, ACT_RELU, ACT_LEAKY_RELU, ACT_SOFTPLUS = 0, 1, 2, 3, 4, 5
+# the pre-activation family (bit 5): derivatives that need the pre-activation u, kept by K5's pre build
+ACT_SILU, ACT_GELU, ACT_GELU_TANH, ACT_MISH = 32, 33, 34, 35
 
 
 class ViewF32(ctypes.Structure):

@@ -126,6 +126,102 @@ __device__ __forceinline__ ActDev act_pick(bool first, const ActDev& x, const Ac
     return r;
 }
 
+// ---- the pre-activation family (kind >= PSNODE_ACT_PRE_FAMILY): SiLU, GELU (erf / tanh form), Mish.  Their derivatives are functions of the
+// PRE-activation u, not of h, so K5 keeps u for them (its pre build: psnode_generic_bwd_pre.hip).  New functions, kept out of act_quad /
+// act_grad_quad, so that the six-kind kernels keep their instruction stream.  Every form below is finite for every finite u (|u| up to the
+// fp32 range: each exponential that can overflow is taken of a non-positive argument or guarded) and keeps the ~1e-7 absolute budget:
+//   SiLU        u s,  s = 1 / (1 + e^-u)                          s (1 + u (1 - s)),  1 - s = e^-u s for u >= 0 (no cancellation)
+//   GELU        u Phi(u),  Phi(u) = erfc(-u / sqrt 2) / 2          Phi(u) + u phi(u)   (erfc: no cancellation of 1 + erf for u < 0)
+//   GELU(tanh)  u (1 + t) / 2,  t = tanh z,  z = c (u + k u^3)    (1 + t) / 2 + u (1 - t^2) c (1 + 3 k u^2) / 2
+//               with e = e^(-2|z|), r = 1 / (1 + e):  (1 + t) / 2 = r (z < 0 ? e : 1),  1 - t^2 = 4 e r^2   (both free of cancellation)
+//   Mish        u T,  T = tanh(softplus u) = n / (n + 2),  n = w (w + 2),  w = e^u     (T = 1 above u = 20, where n / (n + 2) rounds to 1)
+//               T + u (1 - T^2) sigma(u),  1 - T^2 = 4 (n + 1) / (n + 2)^2,  sigma(u) = w / (1 + w)
+//               (the closed form of tanh(log1p(e^u)): the log1p form loses 1 - e^(-2 sp) to cancellation where sp is small, ~1e-6 at u = -20)
+constexpr float kSqrtHalf = 0.707106781186547524f, kInvSqrt2Pi = 0.398942280401432678f;
+constexpr float kGeluC = 0.797884560802865355f, kGeluK = 0.044715f;     // sqrt(2 / pi), the cubic coefficient of GELU(tanh)
+
+template <int KIND>
+__device__ __forceinline__ float pre_act1_k(float u) {
+    if constexpr (KIND == PSNODE_ACT_SILU) {
+        return u * __builtin_amdgcn_rcpf(1.0f + act_exp(-u));           // e^-u = inf -> u * 0
+    } else if constexpr (KIND == PSNODE_ACT_GELU) {
+        return u * (0.5f * erfcf(-u * kSqrtHalf));
+    } else if constexpr (KIND == PSNODE_ACT_GELU_TANH) {
+        const float z = kGeluC * (u + kGeluK * u * u * u);
+        const float e = __builtin_amdgcn_exp2f(-2.0f * kLog2e * fabsf(z)), r = __builtin_amdgcn_rcpf(1.0f + e);
+        return u * (r * (z < 0.0f ? e : 1.0f));
+    } else {    // PSNODE_ACT_MISH
+        const float w = act_exp(fminf(u, 20.0f)), n = w * (w + 2.0f);
+        return u * (u > 20.0f ? 1.0f : n * __builtin_amdgcn_rcpf(n + 2.0f));
+    }
+}
+template <int KIND>
+__device__ __forceinline__ float pre_grad1_k(float u) {
+    if constexpr (KIND == PSNODE_ACT_SILU) {
+        const float e = act_exp(-u), s = __builtin_amdgcn_rcpf(1.0f + e);
+        const float oms = u >= 0.0f ? e * s : 1.0f - s;                 // 1 - s (e * s would be inf * 0 where e^-u overflows)
+        return s * (1.0f + u * oms);
+    } else if constexpr (KIND == PSNODE_ACT_GELU) {
+        return 0.5f * erfcf(-u * kSqrtHalf) + u * (kInvSqrt2Pi * act_exp(-0.5f * u * u));
+    } else if constexpr (KIND == PSNODE_ACT_GELU_TANH) {
+        const float u2 = u * u, z = kGeluC * (u + kGeluK * u2 * u);
+        const float e = __builtin_amdgcn_exp2f(-2.0f * kLog2e * fabsf(z)), r = __builtin_amdgcn_rcpf(1.0f + e);
+        return r * (z < 0.0f ? e : 1.0f) + (u * (2.0f * e * r * r)) * (kGeluC * (1.0f + 3.0f * kGeluK * u2));
+    } else {    // PSNODE_ACT_MISH
+        const float w = act_exp(fminf(u, 20.0f)), n = w * (w + 2.0f), q = __builtin_amdgcn_rcpf(n + 2.0f);
+        const float sech2 = 4.0f * (n + 1.0f) * q * q, sg = w * __builtin_amdgcn_rcpf(1.0f + w);
+        return u > 20.0f ? 1.0f : n * q + u * sech2 * sg;
+    }
+}
+template <int KIND>
+__device__ __forceinline__ act_f4 pre_act_quad_k(const act_f4 v) {
+    return act_f4{pre_act1_k<KIND>(v[0]), pre_act1_k<KIND>(v[1]), pre_act1_k<KIND>(v[2]), pre_act1_k<KIND>(v[3])};
+}
+template <int KIND>
+__device__ __forceinline__ act_f4 pre_grad_quad_k(const act_f4 u) {
+    return act_f4{pre_grad1_k<KIND>(u[0]), pre_grad1_k<KIND>(u[1]), pre_grad1_k<KIND>(u[2]), pre_grad1_k<KIND>(u[3])};
+}
+// the pre build's forms over all ten kinds (an ActPair may mix the families): kinds < 32 are act1 / act_quad and take their derivative
+// from h (act_grad1 / act_grad_quad, the numbers of the act build), the family >= 32 from u.  One branch per quad, as act_quad.
+__device__ __forceinline__ act_f4 pre_act_quad(const act_f4 v, const ActDev& a) {
+    if (a.kind < PSNODE_ACT_PRE_FAMILY) return act_quad(v, a);
+    switch (a.kind) {
+        case PSNODE_ACT_SILU: return pre_act_quad_k<PSNODE_ACT_SILU>(v);
+        case PSNODE_ACT_GELU: return pre_act_quad_k<PSNODE_ACT_GELU>(v);
+        case PSNODE_ACT_GELU_TANH: return pre_act_quad_k<PSNODE_ACT_GELU_TANH>(v);
+        default: return pre_act_quad_k<PSNODE_ACT_MISH>(v);
+    }
+}
+__device__ __forceinline__ act_f4 pre_grad_quad(const act_f4 h, const act_f4 u, const ActDev& a) {
+    if (a.kind < PSNODE_ACT_PRE_FAMILY) return act_grad_quad(h, a);
+    switch (a.kind) {
+        case PSNODE_ACT_SILU: return pre_grad_quad_k<PSNODE_ACT_SILU>(u);
+        case PSNODE_ACT_GELU: return pre_grad_quad_k<PSNODE_ACT_GELU>(u);
+        case PSNODE_ACT_GELU_TANH: return pre_grad_quad_k<PSNODE_ACT_GELU_TANH>(u);
+        default: return pre_grad_quad_k<PSNODE_ACT_MISH>(u);
+    }
+}
+__device__ __forceinline__ float pre_act1(float x, const ActDev& a) {
+    if (a.kind < PSNODE_ACT_PRE_FAMILY) return act1(x, a);
+    switch (a.kind) {
+        case PSNODE_ACT_SILU: return pre_act1_k<PSNODE_ACT_SILU>(x);
+        case PSNODE_ACT_GELU: return pre_act1_k<PSNODE_ACT_GELU>(x);
+        case PSNODE_ACT_GELU_TANH: return pre_act1_k<PSNODE_ACT_GELU_TANH>(x);
+        default: return pre_act1_k<PSNODE_ACT_MISH>(x);
+    }
+}
+__device__ __forceinline__ float pre_grad1(float h, float u, const ActDev& a) {
+    if (a.kind < PSNODE_ACT_PRE_FAMILY) return act_grad1(h, a);
+    switch (a.kind) {
+        case PSNODE_ACT_SILU: return pre_grad1_k<PSNODE_ACT_SILU>(u);
+        case PSNODE_ACT_GELU: return pre_grad1_k<PSNODE_ACT_GELU>(u);
+        case PSNODE_ACT_GELU_TANH: return pre_grad1_k<PSNODE_ACT_GELU_TANH>(u);
+        default: return pre_grad1_k<PSNODE_ACT_MISH>(u);
+    }
+}
+// a call with an activation of the pre-activation family on either MLP runs the pre build
+inline bool act_pair_pre(const ActPair& p) { return p.de.kind >= PSNODE_ACT_PRE_FAMILY || p.ae.kind >= PSNODE_ACT_PRE_FAMILY; }
+
 // psnode_capi.hip: validates a psnode_act_f32 and converts it (NULL = ELU(1)).  Returns PSNODE_OK / PSNODE_ERR_*; `is_elu1` = the
 // existing ELU(1) routes apply.
 int act_from_abi(const psnode_act_f32* in, ActDev& out, bool& is_elu1);
@@ -138,6 +234,15 @@ bool generic_wide_mode(const IntegrateDev& a, bool dae);
 hipError_t launch_generic_act(const IntegrateDev& a, bool dae, const ActPair& act, hipStream_t stream);
 // psnode_generic_bwd_act.hip: K5 with the activations of `act` (the ELU(1) call is generic_backward_launch)
 int generic_backward_launch_act(const ActPair& act, int method, int xd, int zd, int vd, int id, long long T, long long B,
+                                const psnode_mlp_f32* de, const psnode_mlp_f32* ae, ViewDev t, ViewDev z, ViewDev v, const float* a0,
+                                const int* ev, const float* zj, long long zjb, long long zje, const float* vj, long long vjb, long long vje,
+                                int n_events, const float* xs, const float* is_, const float* gxs, const float* gis, float* gx0, float* gz,
+                                float* gv, float* gzj, float* gvj, float* ga0, float* gparams_de, float* gparams_ae, float* workspace,
+                                hipStream_t stream);
+// psnode_generic_pre.hip / psnode_generic_bwd_pre.hip: the same for an ActPair with a kind of the pre-activation family (act_pair_pre)
+hipError_t launch_generic_pre(const IntegrateDev& a, bool dae, const ActPair& act, hipStream_t stream);
+int generic_bwd_fits_pre(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, int xd, int zd, int vd, int id);
+int generic_backward_launch_pre(const ActPair& act, int method, int xd, int zd, int vd, int id, long long T, long long B,
                                 const psnode_mlp_f32* de, const psnode_mlp_f32* ae, ViewDev t, ViewDev z, ViewDev v, const float* a0,
                                 const int* ev, const float* zj, long long zjb, long long zje, const float* vj, long long vjb, long long vje,
                                 int n_events, const float* xs, const float* is_, const float* gxs, const float* gis, float* gx0, float* gz,

@@ -21,11 +21,12 @@ int generic_np(const psnode_mlp_f32& m) {
     for (int l = 0; l < m.n_layers; ++l) { np += m.out_dim[l] * (k + 1); k = m.out_dim[l]; }
     return np;
 }
-bool ode_generic_ok(const psnode_ode_bwd_args_f32* a) {
+// pre: K5's pre-activation build (its own LDS fit: psnode_generic_bwd.hip, pre_floats)
+bool ode_generic_ok(const psnode_ode_bwd_args_f32* a, bool pre = false) {
     const psnode_mlp_f32& m = a->de;
     if (a->x_dim < 1 || a->z_dim < 0 || m.n_layers < 1 || m.n_layers > kMaxLayers) return false;
     if (m.in_dim != 3 * (a->x_dim + a->z_dim) || m.out_dim[m.n_layers - 1] != a->x_dim) return false;
-    return generic_bwd_fits(&a->de, nullptr, a->x_dim, a->z_dim, 0, 0) != 0;
+    return (pre ? generic_bwd_fits_pre(&a->de, nullptr, a->x_dim, a->z_dim, 0, 0) : generic_bwd_fits(&a->de, nullptr, a->x_dim, a->z_dim, 0, 0)) != 0;
 }
 // K4f: every width <= 128 (z_dim up to 8), saved-activation and recompute forms
 bool use_fused_bwd(const psnode_ode_bwd_args_f32* a) { return a->kernel != PSNODE_KERNEL_GENERIC && fused_bwd_shape_ok(a); }
@@ -177,7 +178,7 @@ extern "C" int32_t psnode_ode_backward_act_supported(const psnode_ode_bwd_args_f
     if (act_from_abi(de_act, d, elu1)) return 0;
     if (elu1) return psnode_ode_backward_supported(a);
     if (!a || a->method < PSNODE_EULER || a->method > PSNODE_RK4_38) return 0;
-    return act_bwd_ok(a->kernel, a->flags, a->saved_act) && ode_generic_ok(a);
+    return act_bwd_ok(a->kernel, a->flags, a->saved_act) && ode_generic_ok(a, d.kind >= PSNODE_ACT_PRE_FAMILY);
 }
 
 extern "C" int32_t psnode_ode_backward_act_f32(const psnode_ode_bwd_args_f32* a, const psnode_act_f32* de_act, void* workspace,
@@ -191,7 +192,8 @@ extern "C" int32_t psnode_ode_backward_act_f32(const psnode_ode_bwd_args_f32* a,
     if (!a) return PSNODE_ERR_NULL;
     if (a->method < PSNODE_EULER || a->method > PSNODE_RK4_38) return PSNODE_ERR_METHOD;
     if (a->T < 1 || a->B < 1) return PSNODE_ERR_DIMS;
-    if (!act_bwd_ok(a->kernel, a->flags, a->saved_act) || a->saved_xstage || !ode_generic_ok(a)) return PSNODE_ERR_UNSUPPORTED;
+    const bool pre = act_pair_pre(p);
+    if (!act_bwd_ok(a->kernel, a->flags, a->saved_act) || a->saved_xstage || !ode_generic_ok(a, pre)) return PSNODE_ERR_UNSUPPORTED;
     for (int l = 0; l < a->de.n_layers; ++l) if (!a->de.weight[l] || !a->de.bias[l]) return PSNODE_ERR_NULL;
     if (!a->t.ptr || !a->all_initial || !a->xs || !a->grad_xs || !a->grad_x0 || !a->grad_all_initial || !a->grad_params) return PSNODE_ERR_NULL;
     if (a->z_dim > 0 && !a->z.ptr) return PSNODE_ERR_NULL;
@@ -199,7 +201,7 @@ extern "C" int32_t psnode_ode_backward_act_f32(const psnode_ode_bwd_args_f32* a,
     if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 255u) ||
         workspace_bytes < generic_bwd_workspace_floats(&a->de, nullptr, a->B) * sizeof(float))
         return PSNODE_ERR_WORKSPACE;
-    return generic_backward_launch_act(p, a->method, a->x_dim, a->z_dim, 0, 0, a->T, a->B, &a->de, nullptr,
+    return (pre ? generic_backward_launch_pre : generic_backward_launch_act)(p, a->method, a->x_dim, a->z_dim, 0, 0, a->T, a->B, &a->de, nullptr,
                                        ViewDev{a->t.ptr, a->t.stride_t, a->t.stride_b}, ViewDev{a->z.ptr, a->z.stride_t, a->z.stride_b},
                                        ViewDev{nullptr, 0, 0}, a->all_initial, a->event_idx, a->z_jump, a->zj_stride_b, a->zj_stride_e, nullptr,
                                        0, 0, a->n_events, a->xs, nullptr, a->grad_xs, nullptr, a->grad_x0, a->grad_z, nullptr, a->grad_z_jump,
@@ -208,14 +210,15 @@ extern "C" int32_t psnode_ode_backward_act_f32(const psnode_ode_bwd_args_f32* a,
 }
 
 namespace {
-bool dae_generic_ok(const psnode_dae_bwd_args_f32* a) {
+bool dae_generic_ok(const psnode_dae_bwd_args_f32* a, bool pre = false) {
     if (a->x_dim < 1 || a->z_dim < 0 || a->v_dim < 0 || a->i_dim < 1) return false;
     const int n = a->x_dim + a->z_dim + a->v_dim + a->i_dim;
     const psnode_mlp_f32 &d = a->de, &g = a->ae;
     if (d.n_layers < 1 || d.n_layers > kMaxLayers || g.n_layers < 1 || g.n_layers > kMaxLayers) return false;
     if (d.in_dim != 3 * n || d.out_dim[d.n_layers - 1] != a->x_dim) return false;
     if (g.in_dim != n + a->x_dim + a->z_dim + a->v_dim || g.out_dim[g.n_layers - 1] != a->i_dim) return false;
-    return generic_bwd_fits(&a->de, &a->ae, a->x_dim, a->z_dim, a->v_dim, a->i_dim) != 0;
+    return (pre ? generic_bwd_fits_pre(&a->de, &a->ae, a->x_dim, a->z_dim, a->v_dim, a->i_dim)
+                : generic_bwd_fits(&a->de, &a->ae, a->x_dim, a->z_dim, a->v_dim, a->i_dim)) != 0;
 }
 }  // namespace
 
@@ -225,7 +228,7 @@ extern "C" int32_t psnode_dae_backward_act_supported(const psnode_dae_bwd_args_f
     if (act_from_abi(de_act, d, e_de) || act_from_abi(ae_act, g, e_ae)) return 0;
     if (e_de && e_ae) return psnode_dae_backward_supported(a);
     if (!a || a->method < PSNODE_EULER || a->method > PSNODE_RK4_38) return 0;
-    return act_bwd_ok(a->kernel, 0, a->saved_act) && dae_generic_ok(a);
+    return act_bwd_ok(a->kernel, 0, a->saved_act) && dae_generic_ok(a, d.kind >= PSNODE_ACT_PRE_FAMILY || g.kind >= PSNODE_ACT_PRE_FAMILY);
 }
 
 extern "C" int32_t psnode_dae_backward_act_f32(const psnode_dae_bwd_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
@@ -239,7 +242,8 @@ extern "C" int32_t psnode_dae_backward_act_f32(const psnode_dae_bwd_args_f32* a,
     if (!a) return PSNODE_ERR_NULL;
     if (a->method < PSNODE_EULER || a->method > PSNODE_RK4_38) return PSNODE_ERR_METHOD;
     if (a->T < 1 || a->B < 1) return PSNODE_ERR_DIMS;
-    if (!act_bwd_ok(a->kernel, 0, a->saved_act) || a->saved_xstage || a->saved_ae_act || !dae_generic_ok(a)) return PSNODE_ERR_UNSUPPORTED;
+    const bool pre = act_pair_pre(p);
+    if (!act_bwd_ok(a->kernel, 0, a->saved_act) || a->saved_xstage || a->saved_ae_act || !dae_generic_ok(a, pre)) return PSNODE_ERR_UNSUPPORTED;
     for (int l = 0; l < a->de.n_layers; ++l) if (!a->de.weight[l] || !a->de.bias[l]) return PSNODE_ERR_NULL;
     for (int l = 0; l < a->ae.n_layers; ++l) if (!a->ae.weight[l] || !a->ae.bias[l]) return PSNODE_ERR_NULL;
     if (!a->t.ptr || !a->all_initial || !a->xs || !a->is || !a->grad_xs || !a->grad_x_init || !a->grad_all_initial || !a->grad_params_de ||
@@ -250,7 +254,7 @@ extern "C" int32_t psnode_dae_backward_act_f32(const psnode_dae_bwd_args_f32* a,
     if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 255u) ||
         workspace_bytes < generic_bwd_workspace_floats(&a->de, &a->ae, a->B) * sizeof(float))
         return PSNODE_ERR_WORKSPACE;
-    return generic_backward_launch_act(p, a->method, a->x_dim, a->z_dim, a->v_dim, a->i_dim, a->T, a->B, &a->de, &a->ae,
+    return (pre ? generic_backward_launch_pre : generic_backward_launch_act)(p, a->method, a->x_dim, a->z_dim, a->v_dim, a->i_dim, a->T, a->B, &a->de, &a->ae,
                                        ViewDev{a->t.ptr, a->t.stride_t, a->t.stride_b}, ViewDev{a->z.ptr, a->z.stride_t, a->z.stride_b},
                                        ViewDev{a->v.ptr, a->v.stride_t, a->v.stride_b}, a->all_initial, a->event_idx, a->z_jump, a->zj_stride_b,
                                        a->zj_stride_e, a->v_jump, a->vj_stride_b, a->vj_stride_e, a->n_events, a->xs, a->is, a->grad_xs,

@@ -105,7 +105,8 @@ int dispatch(IntegrateDev& d, bool dae, int kernel, const psnode_mlp_f32* de, co
     } else {
         if (generic_lds_bytes(d, dae) > 160 * 1024) return PSNODE_ERR_UNSUPPORTED;
         e = launch_pack_image(d.de, dae ? &d.ae : nullptr, d.xd, d.xd + d.zd + (dae ? d.vd + d.id : 0), d.zd + (dae ? d.vd : 0), stream);
-        if (e == hipSuccess) e = act ? launch_generic_act(d, dae, *act, stream) : launch_generic(d, dae, stream);
+        if (e == hipSuccess)
+            e = !act ? launch_generic(d, dae, stream) : (act_pair_pre(*act) ? launch_generic_pre(d, dae, *act, stream) : launch_generic_act(d, dae, *act, stream));
     }
     return e == hipSuccess ? PSNODE_OK : PSNODE_ERR_HIP;
 }
@@ -219,7 +220,8 @@ int act_from_abi(const psnode_act_f32* in, ActDev& out, bool& is_elu1) {
     out = ActDev{PSNODE_ACT_ELU, 1.0f, 1.0f, 20.0f, 1.0f};
     is_elu1 = true;
     if (!in) return PSNODE_OK;
-    if (in->kind < PSNODE_ACT_ELU || in->kind > PSNODE_ACT_SOFTPLUS) return PSNODE_ERR_METHOD;
+    const bool pre = in->kind >= PSNODE_ACT_SILU && in->kind <= PSNODE_ACT_MISH;      // (no parameters: alpha / beta / threshold ignored)
+    if ((in->kind < PSNODE_ACT_ELU || in->kind > PSNODE_ACT_SOFTPLUS) && !pre) return PSNODE_ERR_METHOD;
     out.kind = in->kind;
     out.alpha = 0.0f;
     switch (in->kind) {

@@ -30,7 +30,17 @@
 // (generic_act_kernel) take the DE's and the AE's activation as a second kernel argument (psnode_act.h) and apply it wherever these
 // kernels apply ELU(1); its launcher is launch_generic_act.  Without the macro the tokens below expand to exactly the ELU(1) source, so
 // the ELU(1) kernels compile to the instruction stream they always had.
-#ifdef PSNODE_K0_ACT_BUILD
+// Pre-activation build: psnode_generic_pre.hip compiles it a third time with PSNODE_K0_PRE_BUILD defined as well.  Its kernels
+// (generic_pre_act_kernel) apply all ten kinds (pre_act_quad: the six above, and SiLU / GELU / GELU(tanh) / Mish); the forward needs no
+// pre-activation.  Its launcher is launch_generic_pre.
+#if defined(PSNODE_K0_PRE_BUILD)
+#include "psnode_act.h"
+#define K0_ACT(v) pre_act_quad(v, ac)
+#define K0_ACT_PARAM , const ActDev& ac
+#define K0_ACT_ARG(x) , x
+#define K0_KERNEL generic_pre_act_kernel
+#define K0_KERNEL_PARAMS const IntegrateDev a, const ActPair act
+#elif defined(PSNODE_K0_ACT_BUILD)
 #include "psnode_act.h"
 #define K0_ACT(v) act_quad(v, ac)
 #define K0_ACT_PARAM , const ActDev& ac
@@ -1027,7 +1037,9 @@ size_t generic_plan(const IntegrateDev& a, bool dae, unsigned& mask) {
 
 #endif  // PSNODE_K0_ACT_BUILD
 
-#ifdef PSNODE_K0_ACT_BUILD
+#if defined(PSNODE_K0_PRE_BUILD)
+hipError_t launch_generic_pre(const IntegrateDev& a_in, bool dae, const ActPair& act, hipStream_t stream_) {
+#elif defined(PSNODE_K0_ACT_BUILD)
 hipError_t launch_generic_act(const IntegrateDev& a_in, bool dae, const ActPair& act, hipStream_t stream_) {
 #else
 hipError_t launch_generic(const IntegrateDev& a_in, bool dae, hipStream_t stream_) {

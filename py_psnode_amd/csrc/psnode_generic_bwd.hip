@@ -20,25 +20,48 @@
 // (generic_backward_act_kernel) take the DE's and the AE's activation as a second kernel argument (psnode_act.h) and use it wherever these
 // kernels use ELU(1) and its derivative; its launcher is generic_backward_launch_act.  Without the macro the tokens below expand to exactly
 // the ELU(1) source, so the ELU(1) kernels compile to the instruction stream they always had.
-#ifdef PSNODE_K5_ACT_BUILD
+//
+// Pre-activation build: psnode_generic_bwd_pre.hip compiles it a third time with PSNODE_K5_PRE_BUILD defined as well
+// (generic_backward_pre_act_kernel, launcher generic_backward_launch_pre).  Its forward recomputation also writes each hidden layer's
+// pre-activation u into a region of its own at the end of the LDS layout (`upre`, GMlp::pre: [unit][TP] rows on the staged path,
+// quad-row images on the register / streamed paths), and its VJP passes u next to h to the derivative (pre_grad1 / pre_grad_quad: from u
+// for SiLU / GELU / Mish, from h for the other kinds).  K5_PRE(...) is code of that build only; the u arguments of K5_DACT1 / K5_DACTQ are
+// dropped unread by the other two.
+#if defined(PSNODE_K5_PRE_BUILD)
+#include "psnode_act.h"
+#define K5_ACT1(v) pre_act1(v, ac)
+#define K5_DACT1(h, u) pre_grad1(h, u, ac)
+#define K5_ACTQ(v) pre_act_quad(v, ac)
+#define K5_DACTQ(h, u) pre_grad_quad(h, u, ac)
+#define K5_ACT_PARAM , const ActDev& ac, float* upre
+#define K5_ACT_ARG(x) , x, upre
+#define K5_PRE(...) __VA_ARGS__
+#define K5_KERNEL generic_backward_pre_act_kernel
+#define K5_KERNEL_PARAMS const GBwd a, const ActPair act
+#define K5_LAUNCH_ARG(x) , x
+#elif defined(PSNODE_K5_ACT_BUILD)
 #include "psnode_act.h"
 #define K5_ACT1(v) act1(v, ac)
-#define K5_DACT1(h) act_grad1(h, ac)
+#define K5_DACT1(h, u) act_grad1(h, ac)
 #define K5_ACTQ(v) act_quad(v, ac)
-#define K5_DACTQ(h) act_grad_quad(h, ac)
+#define K5_DACTQ(h, u) act_grad_quad(h, ac)
 #define K5_ACT_PARAM , const ActDev& ac
 #define K5_ACT_ARG(x) , x
+#define K5_PRE(...)
 #define K5_KERNEL generic_backward_act_kernel
 #define K5_KERNEL_PARAMS const GBwd a, const ActPair act
+#define K5_LAUNCH_ARG(x) , x
 #else
 #define K5_ACT1(v) elu1(v)
-#define K5_DACT1(h) delu(h)
+#define K5_DACT1(h, u) delu(h)
 #define K5_ACTQ(v) elu_quad(v)
-#define K5_DACTQ(h) elu_grad_quad(h)
+#define K5_DACTQ(h, u) elu_grad_quad(h)
 #define K5_ACT_PARAM
 #define K5_ACT_ARG(x)
+#define K5_PRE(...)
 #define K5_KERNEL generic_backward_kernel
 #define K5_KERNEL_PARAMS const GBwd a
+#define K5_LAUNCH_ARG(x)
 #endif
 
 namespace psnode {
@@ -57,6 +80,9 @@ struct GMlp {
     int gw[kMaxLayers], gb[kMaxLayers];   // offsets of dW, db in the flat gradient vector (nn.Linear order)
     int act[kMaxLayers + 1];              // row offsets of the layer activations (act[0] = input) in the acts buffer
     int np;
+#ifdef PSNODE_K5_PRE_BUILD
+    int pre[kMaxLayers];                  // float offsets of the hidden layers' pre-activations in the u region (pre_layout)
+#endif
 };
 
 struct GBwd {
@@ -86,6 +112,9 @@ struct GBwd {
     float* tmpart;     // per-workgroup TILE-MAJOR global accumulators of the MLPs off the staged path (gacc_global != 0): tm_total(de) + tm_total(ae)
     const float* fimgA[kMaxLayers];
     const float* timgA[kMaxLayers];
+#ifdef PSNODE_K5_PRE_BUILD
+    int upre_off;      // float offset of the u region in LDS (behind everything else)
+#endif
 };
 
 __device__ __forceinline__ float delu(float h) { return elu_grad(h); }   // ELU'(pre) from h = ELU(pre)
@@ -139,6 +168,7 @@ __device__ __forceinline__ void g_forward(const GMlp& m, float* acts, float* wbu
                     const int uu = 16 * mt + 4 * g + r;
                     if (uu < N) {
                         float v = accA[r] + accB[r];
+                        K5_PRE(if (final && !last) upre[m.pre[l] + uu * TP + i] = v;)
                         if (final && !last) v = K5_ACT1(v);
                         out[uu * TP + i] = v;
                     }
@@ -220,7 +250,7 @@ __device__ __forceinline__ float* g_vjp(const GMlp& m, const float* acts, float*
                     const int kr = 16 * kt + 4 * g + r;
                     if (kr < K) {
                         float v = accA[r] + accB[r];
-                        if (final && l > 0) v *= K5_DACT1(a_in[kr * TP + i]);
+                        if (final && l > 0) v *= K5_DACT1(a_in[kr * TP + i], upre[m.pre[l - 1] + kr * TP + i]);
                         dout[kr * TP + i] = v;
                     }
                 }
@@ -367,6 +397,7 @@ __device__ __forceinline__ void g_forward_reg(const GBwd& a, float* acts, float*
                 if (uu < N) out[uu * TP + j] = e[r];
             }
             if (!last) reinterpret_cast<f4*>(qb + qo.act[l < 3 ? l : 0])[w * 64 + lane] = e;
+            K5_PRE(if (!last) reinterpret_cast<f4*>(upre + m.pre[l < 3 ? l : 0])[w * 64 + lane] = acc;)
         }
         __syncthreads();
     }
@@ -436,7 +467,7 @@ __device__ __forceinline__ float* g_vjp_reg(const GBwd& a, const float* acts, fl
                 asm volatile("s_nop 3" : "+v"(acc));
                 if (l > 0) {
                     const f4 h = reinterpret_cast<const f4*>(qb + qo.act[l - 1 >= 0 ? l - 1 : 0])[kt * 64 + lane];
-                    acc = acc * K5_DACTQ(h);
+                    acc = acc * K5_DACTQ(h, reinterpret_cast<const f4*>(upre + m.pre[l - 1 >= 0 ? l - 1 : 0])[kt * 64 + lane]);
                     reinterpret_cast<f4*>(qb + qn)[kt * 64 + lane] = acc;
                 }
 #pragma unroll
@@ -507,6 +538,7 @@ __device__ __forceinline__ void g_forward_str(const GMlp& m, const float* const*
                 if (uu < N) out[uu * TP + j] = e[r];
             }
             if (!last) reinterpret_cast<f4*>(qb + qo.act[l])[nt * 64 + lane] = e;
+            K5_PRE(if (!last) reinterpret_cast<f4*>(upre + m.pre[l])[nt * 64 + lane] = acc;)
         }
         __syncthreads();
     }
@@ -564,7 +596,7 @@ __device__ __forceinline__ float* g_vjp_str(const GMlp& m, const float* const* t
             asm volatile("s_nop 3" : "+v"(acc));       // (as on the register path: the store below may sit on a taken branch edge)
             if (l > 0) {
                 const f4 h = reinterpret_cast<const f4*>(qb + qo.act[l - 1])[kt * 64 + lane];
-                acc = acc * K5_DACTQ(h);
+                acc = acc * K5_DACTQ(h, reinterpret_cast<const f4*>(upre + m.pre[l - 1])[kt * 64 + lane]);
                 reinterpret_cast<f4*>(qb + qn)[kt * 64 + lane] = acc;
             }
 #pragma unroll
@@ -623,6 +655,7 @@ __global__ __launch_bounds__(NT) void K5_KERNEL(K5_KERNEL_PARAMS) {
     const int np_all = ae_at + ((a.dae && !ggA) ? ae_acc : 0);        // floats of LDS accumulators
     float* qb = gacc_l + ((np_all + 3) & ~3);
     const QOff qo = q_offsets(a.de), qoA = q_offsets(a.ae);           // (one region: the two MLPs' evaluations never overlap in time)
+    K5_PRE(float* upre = lds + a.upre_off;)                          // (likewise one region for both MLPs' pre-activations)
     RegFwd rfw;
     RegBwd rbw;
     if constexpr (REG) load_reg_images(a, rfw, rbw);
@@ -913,6 +946,24 @@ int fill_gmlp(const psnode_mlp_f32& m, GMlp& g, float*& ws) {
     return rows;
 }
 
+#ifdef PSNODE_K5_PRE_BUILD
+// the u region of one MLP: per hidden layer [unit][TP] rows on the staged path (`quad` false), a quad-row image (as its h in qb) on the
+// register / streamed paths.  Sets m.pre when `set`; returns the floats.
+inline int pre_layout(GMlp& m, bool quad, bool set) {
+    int o = 0;
+    for (int l = 0; l + 1 < m.L; ++l) {
+        if (set) m.pre[l] = o;
+        o += quad ? up16(m.out_dim[l]) * TB : m.out_dim[l] * TP;
+    }
+    return o;
+}
+size_t pre_floats(const GBwd& a) {      // both MLPs share the region (their evaluations never overlap in time)
+    GBwd c = a;
+    const int de = pre_layout(c.de, a.de_reg || a.str == 2, false), ae = a.dae ? pre_layout(c.ae, a.str >= 1, false) : 0;
+    return (size_t)(de > ae ? de : ae);
+}
+#endif
+
 size_t gbwd_lds_floats(const GBwd& a) {
     const int vd = a.dae ? a.vd : 0, id = a.dae ? a.id : 0, ne = a.zd + vd + id, n = a.xd + ne;
     const bool de_tm = a.de_reg || a.str == 2, ae_tm = a.str >= 1;
@@ -923,7 +974,7 @@ size_t gbwd_lds_floats(const GBwd& a) {
     if (de_tm) q = (size_t)q_offsets(a.de).total;
     if (a.dae && ae_tm && (size_t)q_offsets(a.ae).total > q) q = (size_t)q_offsets(a.ae).total;
     return (size_t)a.act_rows * TP + 2 * (size_t)a.maxw * TP + 2 * (size_t)n * TP + 2 * (size_t)ne * TP + (size_t)a.xd * TP * (1 + 12 + 2) +
-           (size_t)id * TP + TP + (stages ? kWBuf : 0) + ((np_all + 3) & ~(size_t)3) + q;
+           (size_t)id * TP + TP + (stages ? kWBuf : 0) + ((np_all + 3) & ~(size_t)3) + q K5_PRE(+ pre_floats(a));
 }
 // the DE's shape class of the register path
 bool de_reg_class(const psnode_mlp_f32& de) {
@@ -998,17 +1049,8 @@ bool mlp_ok(const psnode_mlp_f32& m, int in_dim, int out_dim) {
     return true;
 }
 
-}  // namespace
-
-#ifndef PSNODE_K5_ACT_BUILD
-// shared by the ODE and DAE entry points (psnode_backward.hip calls this for kernel = generic / unsupported MFMA shapes)
-size_t generic_bwd_workspace_floats(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, long long B) {
-    const size_t nwg = (size_t)((B + TB - 1) / TB);
-    return mlp_wt_floats(*de) + (ae ? mlp_wt_floats(*ae) : 0) + nwg * (size_t)(mlp_np(*de) + (ae ? mlp_np(*ae) : 0)) + 64 +
-           reg_image_floats(*de) + 64 + (ae ? reg_image_floats(*ae) + 64 : 0) + nwg * tm_floats(*de, ae) + 64;
-}
-
-int generic_bwd_fits(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, int xd, int zd, int vd, int id) {
+// K5's mode for these dims in this build (gbwd_mode), 0 if the shape does not fit
+int bwd_fits_here(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, int xd, int zd, int vd, int id) {
     GBwd a;
     memset(&a, 0, sizeof(a));
     a.dae = ae != nullptr; a.xd = xd; a.zd = zd; a.vd = vd; a.id = id;
@@ -1025,10 +1067,32 @@ int generic_bwd_fits(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, int xd,
     return gbwd_mode(a);
 }
 
+}  // namespace
+
+#ifdef PSNODE_K5_PRE_BUILD
+int generic_bwd_fits_pre(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, int xd, int zd, int vd, int id) {
+    return bwd_fits_here(de, ae, xd, zd, vd, id);
+}
+#endif
+
+#ifndef PSNODE_K5_ACT_BUILD
+// shared by the ODE and DAE entry points (psnode_backward.hip calls this for kernel = generic / unsupported MFMA shapes)
+size_t generic_bwd_workspace_floats(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, long long B) {
+    const size_t nwg = (size_t)((B + TB - 1) / TB);
+    return mlp_wt_floats(*de) + (ae ? mlp_wt_floats(*ae) : 0) + nwg * (size_t)(mlp_np(*de) + (ae ? mlp_np(*ae) : 0)) + 64 +
+           reg_image_floats(*de) + 64 + (ae ? reg_image_floats(*ae) + 64 : 0) + nwg * tm_floats(*de, ae) + 64;
+}
+
+int generic_bwd_fits(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, int xd, int zd, int vd, int id) {
+    return bwd_fits_here(de, ae, xd, zd, vd, id);
+}
+
 #endif  // PSNODE_K5_ACT_BUILD
 
 // launches pack (transpose), the backward kernel and the partial reduction
-#ifdef PSNODE_K5_ACT_BUILD
+#if defined(PSNODE_K5_PRE_BUILD)
+int generic_backward_launch_pre(const ActPair& act, int method,
+#elif defined(PSNODE_K5_ACT_BUILD)
 int generic_backward_launch_act(const ActPair& act, int method,
 #else
 int generic_backward_launch(int method,
@@ -1081,6 +1145,8 @@ int generic_backward_launch(int method,
     }
     if (!gbwd_mode(a)) return PSNODE_ERR_UNSUPPORTED;
     const size_t lds = gbwd_lds_floats(a) * sizeof(float);
+    K5_PRE(pre_layout(a.de, a.de_reg || a.str == 2, true); if (dae) pre_layout(a.ae, a.str >= 1, true);
+           a.upre_off = (int)(gbwd_lds_floats(a) - pre_floats(a));)
     // transposed weights for the forward recomputation
     MlpDev mde, mae;
     memset(&mde, 0, sizeof(mde));
@@ -1104,7 +1170,7 @@ int generic_backward_launch(int method,
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         return PSNODE_ERR_HIP;
     const unsigned nwg = (unsigned)((B + TB - 1) / TB);
-    hipLaunchKernelGGL(kern, dim3(nwg), dim3(NT), lds, stream, a K5_ACT_ARG(act));
+    hipLaunchKernelGGL(kern, dim3(nwg), dim3(NT), lds, stream, a K5_LAUNCH_ARG(act));
     if (hipGetLastError() != hipSuccess) return PSNODE_ERR_HIP;
     return launch_reduce_partials(a.wpart, gparams_de, gparams_ae, a.de.np, dae ? a.ae.np : 0, (int)nwg, stream) == hipSuccess ? PSNODE_OK : PSNODE_ERR_HIP;
 }

@@ -89,6 +89,14 @@ class Act:
             return F.relu(u)
         if self.kind == _lib.ACT_LEAKY_RELU:
             return F.leaky_relu(u, self.alpha)
+        if self.kind == _lib.ACT_SILU:
+            return F.silu(u)
+        if self.kind == _lib.ACT_GELU:
+            return F.gelu(u)
+        if self.kind == _lib.ACT_GELU_TANH:
+            return F.gelu(u, approximate="tanh")
+        if self.kind == _lib.ACT_MISH:
+            return F.mish(u)
         return F.softplus(u, self.beta, self.threshold)
 
     def _key(self):
@@ -142,10 +150,9 @@ def act_of_module(m) -> Optional[object]:
     return False
 
 
-def sequential_mlp(seq):
-    """(layers, act) if `seq` is nn.Sequential(Linear, A, Linear, ..., A, Linear) with ONE activation A throughout that the generic kernels
-    apply (ELU(alpha > 0), Tanh, Sigmoid, ReLU, LeakyReLU(slope >= 0), Softplus(beta > 0)); act None = ELU(1).  Else None (mixed activations
-    included)."""
+def _sequential_one_act(seq, recognise):
+    """(layers, act) if `seq` is nn.Sequential(Linear, A, Linear, ..., A, Linear) with ONE activation A throughout that `recognise` maps to
+    an Act (or None = ELU(1)), else None."""
     if not isinstance(seq, nn.Sequential) or len(seq) == 0 or len(seq) % 2 == 0:
         return None
     out, acts = [], []
@@ -155,7 +162,7 @@ def sequential_mlp(seq):
                 return None
             out.append((m.weight, m.bias))
         else:
-            a = act_of_module(m)
+            a = recognise(m)
             if a is False:
                 return None
             acts.append(a)
@@ -169,11 +176,45 @@ def sequential_mlp(seq):
     return out, (acts[0] if acts else None)
 
 
+def sequential_mlp(seq):
+    """(layers, act) if `seq` is nn.Sequential(Linear, A, Linear, ..., A, Linear) with ONE activation A throughout that the generic kernels
+    apply (ELU(alpha > 0), Tanh, Sigmoid, ReLU, LeakyReLU(slope >= 0), Softplus(beta > 0)); act None = ELU(1).  Else None (mixed activations
+    included)."""
+    return _sequential_one_act(seq, act_of_module)
+
+
+def pre_act_of_module(m) -> Optional[object]:
+    """`False` if `m` is no activation of the pre-activation family (derivative from the pre-activation u: SiLU, GELU (erf or tanh form),
+    Mish), else its Act."""
+    t = type(m)
+    if t is nn.SiLU:
+        return Act(_lib.ACT_SILU, name="SiLU")
+    if t is nn.GELU:
+        if m.approximate == "none":
+            return Act(_lib.ACT_GELU, name="GELU")
+        if m.approximate == "tanh":
+            return Act(_lib.ACT_GELU_TANH, name="GELU(approximate='tanh')")
+        return False
+    if t is nn.Mish:
+        return Act(_lib.ACT_MISH, name="Mish")
+    return False
+
+
+def sequential_mlp_any(seq):
+    """(layers, act) as `sequential_mlp`, with ONE activation throughout from either family: those of `act_of_module` (derivative from the
+    layer output) or those of `pre_act_of_module` (SiLU, GELU, Mish: derivative from the pre-activation).  Else None (mixed activations,
+    within a family or across the two, included)."""
+    def either(m):
+        a = act_of_module(m)
+        return pre_act_of_module(m) if a is False else a
+    return _sequential_one_act(seq, either)
+
+
 def de_mlp_of(x_func, n: int, x_dim: int):
-    """(layers, act) of a DE_Func whose MLP has any activation of `sequential_mlp` (act None = ELU(1)), else None."""
+    """(layers, act) of a DE_Func whose MLP has any activation of `sequential_mlp_any` (act None = ELU(1)), else None."""
     if not isinstance(x_func, nn.Module) or _overrides_forward_hooks(x_func):
         return None
-    r = sequential_mlp(getattr(x_func, "x_dot", None))
+    r = sequential_mlp_any(getattr(x_func, "x_dot", None))
     if r is None or r[0][0][0].shape[1] != 3 * n or r[0][-1][0].shape[0] != x_dim:
         return None
     if not _only_params_of(x_func, x_func.x_dot):
@@ -182,10 +223,10 @@ def de_mlp_of(x_func, n: int, x_dim: int):
 
 
 def ae_mlp_of(i_func, n: int, m: int, i_dim: int):
-    """(layers, act) of an AE_Func whose MLP has any activation of `sequential_mlp` (act None = ELU(1)), else None."""
+    """(layers, act) of an AE_Func whose MLP has any activation of `sequential_mlp_any` (act None = ELU(1)), else None."""
     if not isinstance(i_func, nn.Module) or _overrides_forward_hooks(i_func):
         return None
-    r = sequential_mlp(getattr(i_func, "i_calculator", None))
+    r = sequential_mlp_any(getattr(i_func, "i_calculator", None))
     if r is None or r[0][0][0].shape[1] != n + m or r[0][-1][0].shape[0] != i_dim:
         return None
     if not _only_params_of(i_func, i_func.i_calculator):

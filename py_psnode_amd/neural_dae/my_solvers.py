@@ -74,7 +74,7 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
         if self.fused == "auto" and tensor.device.type == "cuda" and not getattr(self, "_walk_warned", False):
             self._walk_warned = True
             warnings.warn(f"{what}: this call is not fusable (needs fp32 HIP tensors, DE_Func/AE_Func-style MLPs with one activation "
-                          "of ELU / Tanh / Sigmoid / ReLU / LeakyReLU / Softplus -- other than ELU(1) on kernel 'auto' / 'generic' only --, "
+                          "of ELU / Tanh / Sigmoid / ReLU / LeakyReLU / Softplus / SiLU / GELU / Mish -- other than ELU(1) on kernel 'auto' / 'generic' only --, "
                           "ODE_Event/DAE_Event callbacks; under autograd also a shape with a backward kernel and no teacher "
                           "forcing) -- stepping through the Python callables instead", RuntimeWarning, stacklevel=3)
 
@@ -137,7 +137,7 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
                                                check_events=self._check_events_now(event_t), input_true_x=True)
             if self.fused == "require":
                 raise NotFusableError("integrate_ODE: call is not fusable (needs fp32 HIP tensors, a DE_Func-style MLP `x_dot` with one "
-                                      "activation of ELU / Tanh / Sigmoid / ReLU / LeakyReLU / Softplus, ODE_Event callbacks; with autograd: "
+                                      "activation of ELU / Tanh / Sigmoid / ReLU / LeakyReLU / Softplus / SiLU / GELU / Mish, ODE_Event callbacks; with autograd: "
                                       "a shape with a backward kernel, no teacher forcing)")
             self._note_walk("integrate_ODE", x)
         return self._walk_ode(x_func, t, x, z, all_initial, event_fn, jump_change_fn, input_true_x, x_init)
@@ -190,7 +190,7 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
                                                input_true_i=input_true_i)
             if self.fused == "require":
                 raise NotFusableError("integrate_DAE: call is not fusable (needs fp32 HIP tensors, DE_Func/AE_Func-style "
-                                      "MLPs with one activation each of ELU / Tanh / Sigmoid / ReLU / LeakyReLU / Softplus, DAE_Event callbacks; with autograd: a shape with a backward kernel; teacher forcing: hidden <= 128, dataset rows without grad)")
+                                      "MLPs with one activation each of ELU / Tanh / Sigmoid / ReLU / LeakyReLU / Softplus / SiLU / GELU / Mish, DAE_Event callbacks; with autograd: a shape with a backward kernel; teacher forcing: hidden <= 128, dataset rows without grad)")
             self._note_walk("integrate_DAE", z if z.numel() else v)
         return self._walk_dae(x_init, x_func, i_func, t, x, z, v, i, all_initial, event_fn, jump_change_fn,
                               input_true_x, input_true_i)
