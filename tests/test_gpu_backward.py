@@ -384,7 +384,7 @@ def test_head_grads_kernel_against_torch(hidden, R, B, nzv, ev_layout):
                                         # round 6, the DE's register path (<= 4 layers of <= 64 units, 3 n <= 128 input columns) and its edges:
                                         (20, 2, 64, 3), (32, 4, 48, 2), (17, 0, 33, 3), (40, 2, 64, 1), (8, 2, (33, 17, 64), 3), (5, 3, (16, 64, 16), 3),
                                         (44, 0, 40, 2),            # 132 input columns: back on the staged path
-                                        (8, 2, 64, 4)])            # five Linear layers: staged path
+                                        (8, 2, 64, 4)])            # five Linear layers: out of the register class (streamed, LDS accumulators)
 def test_generic_backward_kernel_ode(method, xd, zd, H, nh):
     """K5 (kernel='generic') on the MFMA shape, the direct_encode latent shape, an odd shape, and the --hidden 128 / 32 shapes
     (at 128 the parameter-gradient accumulators no longer fit LDS and live in the workgroup's global partial slice), raw-tensor API."""
