@@ -28,7 +28,7 @@ def latent_wide_training_fits(method, de, ae, hidden, T, B, dev) -> bool:
         return False
     if SAVE_ACTIVATIONS == "1" or T < 2:         # (T = 1: no step, nothing to save)
         return True
-    S = {"euler": 1, "midpoint": 2, "rk4": 4}[method]
+    S = fused.STAGES[method]
     rows = (T - 1) * S * B * hidden * 4              # one [T-1,S,B,H] tensor
     grid = T * B * hidden * 4                        # one [T,B,H] tensor
     need = 4 * rows + (6 if ae is None else 12) * grid       # saved act + xst, gk + d1; d1s, the where / contiguous copies of the external blocks, (DAE) gi, da1, s_ae
@@ -66,7 +66,7 @@ def _want_saved(method, kernel, layers, x_dim, z_dim, T, B):
         return False
     if SAVE_ACTIVATIONS == "1":
         return True
-    S = {"euler": 1, "midpoint": 2, "rk4": 4}[method]
+    S = fused.STAGES[method]
     need = (T - 1) * S * B * ((len(layers) - 1) * Hp + x_dim) * 4
     free, _ = torch.cuda.mem_get_info(layers[0][0].device)
     return need <= free // 2
@@ -84,7 +84,7 @@ def _want_saved_dae(method, kernel, de, ae, x_dim, z_dim, v_dim, i_dim, T, B):
             return False
         if SAVE_ACTIVATIONS == "1":
             return True
-        S = {"euler": 1, "midpoint": 2, "rk4": 4}[method]
+        S = fused.STAGES[method]
         free, _ = torch.cuda.mem_get_info(de[0][0].device)
         return ((T - 1) * S * 2 + T) * 64 * B * 4 <= free // 2
     # hidden 64 also has the one-launch kernel K7 (recompute).  The saved form beats it at every method since round 4 (K7f requests its
@@ -95,7 +95,7 @@ def _want_saved_dae(method, kernel, de, ae, x_dim, z_dim, v_dim, i_dim, T, B):
         return False
     if SAVE_ACTIVATIONS == "1":
         return True
-    S = {"euler": 1, "midpoint": 2, "rk4": 4}[method]
+    S = fused.STAGES[method]
     need = ((T - 1) * S * (3 * Hp + x_dim) + 3 * T * Hp) * B * 4
     free, _ = torch.cuda.mem_get_info(de[0][0].device)
     return need <= free // 2

@@ -225,6 +225,14 @@ inline bool act_pair_pre(const ActPair& p) { return p.de.kind >= PSNODE_ACT_PRE_
 // psnode_capi.hip: validates a psnode_act_f32 and converts it (NULL = ELU(1)).  Returns PSNODE_OK / PSNODE_ERR_*; `is_elu1` = the
 // existing ELU(1) routes apply.
 int act_from_abi(const psnode_act_f32* in, ActDev& out, bool& is_elu1);
+// the two activations of an _act call (the ODE's has ae = NULL); `elu1`: both are ELU(1), the call takes the entry point without _act
+inline int act_pair(const psnode_act_f32* de, const psnode_act_f32* ae, ActPair& p, bool& elu1) {
+    bool e_de = true, e_ae = true;
+    int rc = act_from_abi(de, p.de, e_de);
+    if (rc == PSNODE_OK) rc = act_from_abi(ae, p.ae, e_ae);
+    elu1 = e_de && e_ae;
+    return rc;
+}
 
 // psnode_generic.hip: K0's launch planning, shared by both builds
 size_t generic_plan(const IntegrateDev& a, bool dae, unsigned& mask);
@@ -232,21 +240,8 @@ int generic_reg_mode(const IntegrateDev& a, bool dae);
 bool generic_wide_mode(const IntegrateDev& a, bool dae);
 // psnode_generic_act.hip: K0 with the activations of `act` (the ELU(1) call is launch_generic)
 hipError_t launch_generic_act(const IntegrateDev& a, bool dae, const ActPair& act, hipStream_t stream);
-// psnode_generic_bwd_act.hip: K5 with the activations of `act` (the ELU(1) call is generic_backward_launch)
-int generic_backward_launch_act(const ActPair& act, int method, int xd, int zd, int vd, int id, long long T, long long B,
-                                const psnode_mlp_f32* de, const psnode_mlp_f32* ae, ViewDev t, ViewDev z, ViewDev v, const float* a0,
-                                const int* ev, const float* zj, long long zjb, long long zje, const float* vj, long long vjb, long long vje,
-                                int n_events, const float* xs, const float* is_, const float* gxs, const float* gis, float* gx0, float* gz,
-                                float* gv, float* gzj, float* gvj, float* ga0, float* gparams_de, float* gparams_ae, float* workspace,
-                                hipStream_t stream);
-// psnode_generic_pre.hip / psnode_generic_bwd_pre.hip: the same for an ActPair with a kind of the pre-activation family (act_pair_pre)
+// psnode_generic_pre.hip: the same for an ActPair with a kind of the pre-activation family (act_pair_pre)
+// (K5's three launchers: psnode_common.h, generic_backward_launch*)
 hipError_t launch_generic_pre(const IntegrateDev& a, bool dae, const ActPair& act, hipStream_t stream);
-int generic_bwd_fits_pre(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, int xd, int zd, int vd, int id);
-int generic_backward_launch_pre(const ActPair& act, int method, int xd, int zd, int vd, int id, long long T, long long B,
-                                const psnode_mlp_f32* de, const psnode_mlp_f32* ae, ViewDev t, ViewDev z, ViewDev v, const float* a0,
-                                const int* ev, const float* zj, long long zjb, long long zje, const float* vj, long long vjb, long long vje,
-                                int n_events, const float* xs, const float* is_, const float* gxs, const float* gis, float* gx0, float* gz,
-                                float* gv, float* gzj, float* gvj, float* ga0, float* gparams_de, float* gparams_ae, float* workspace,
-                                hipStream_t stream);
 
 }  // namespace psnode

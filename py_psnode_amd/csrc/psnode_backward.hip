@@ -16,17 +16,85 @@
 using namespace psnode;
 
 namespace {
-int generic_np(const psnode_mlp_f32& m) {
-    int np = 0, k = m.in_dim;
-    for (int l = 0; l < m.n_layers; ++l) { np += m.out_dim[l] * (k + 1); k = m.out_dim[l]; }
-    return np;
+template <class Args>
+bool method_ok(const Args* a) { return a && a->method >= PSNODE_EULER && a->method <= PSNODE_RK4_38; }
+// the first three statuses of every backward entry point, in their order: NULL args, method, T / B
+template <class Args>
+int check_call(const Args* a) {
+    if (!a) return PSNODE_ERR_NULL;
+    if (!method_ok(a)) return PSNODE_ERR_METHOD;
+    return a->T < 1 || a->B < 1 ? PSNODE_ERR_DIMS : PSNODE_OK;
 }
+bool mlp_ptrs_ok(const psnode_mlp_f32& m) {
+    for (int l = 0; l < m.n_layers; ++l) if (!m.weight[l] || !m.bias[l]) return false;
+    return true;
+}
+// the pointers every ODE / DAE backward kernel needs (PSNODE_ERR_NULL otherwise)
+bool ptrs_ok(const psnode_ode_bwd_args_f32* a) {
+    if (!mlp_ptrs_ok(a->de)) return false;
+    if (!a->t.ptr || !a->all_initial || !a->xs || !a->grad_xs || !a->grad_x0 || !a->grad_all_initial || !a->grad_params) return false;
+    if (a->z_dim > 0 && !a->z.ptr) return false;
+    return !(a->event_idx && a->z_dim > 0 && !a->z_jump);
+}
+bool ptrs_ok(const psnode_dae_bwd_args_f32* a) {
+    if (!mlp_ptrs_ok(a->de) || !mlp_ptrs_ok(a->ae)) return false;
+    if (!a->t.ptr || !a->all_initial || !a->xs || !a->is || !a->grad_xs || !a->grad_x_init || !a->grad_all_initial || !a->grad_params_de ||
+        !a->grad_params_ae)
+        return false;
+    if ((a->z_dim > 0 && !a->z.ptr) || (a->v_dim > 0 && !a->v.ptr)) return false;
+    return !(a->event_idx && ((a->z_dim > 0 && !a->z_jump) || (a->v_dim > 0 && !a->v_jump)));
+}
+bool workspace_ok(const void* workspace, size_t workspace_bytes, size_t need) {
+    return workspace && !(reinterpret_cast<uintptr_t>(workspace) & 255u) && workspace_bytes >= need;
+}
+
+// ---- K5 (psnode_generic_bwd.hip): the recipe dims it takes, its call struct, the choice among its three builds
 // pre: K5's pre-activation build (its own LDS fit: psnode_generic_bwd.hip, pre_floats)
 bool ode_generic_ok(const psnode_ode_bwd_args_f32* a, bool pre = false) {
     const psnode_mlp_f32& m = a->de;
     if (a->x_dim < 1 || a->z_dim < 0 || m.n_layers < 1 || m.n_layers > kMaxLayers) return false;
     if (m.in_dim != 3 * (a->x_dim + a->z_dim) || m.out_dim[m.n_layers - 1] != a->x_dim) return false;
-    return (pre ? generic_bwd_fits_pre(&a->de, nullptr, a->x_dim, a->z_dim, 0, 0) : generic_bwd_fits(&a->de, nullptr, a->x_dim, a->z_dim, 0, 0)) != 0;
+    return generic_bwd_fits(&a->de, nullptr, a->x_dim, a->z_dim, 0, 0, pre) != 0;
+}
+// (K5's mode for the shape, 0 = not taken: what psnode_dae_backward_supported returns)
+int dae_generic_ok(const psnode_dae_bwd_args_f32* a, bool pre = false) {
+    if (a->x_dim < 1 || a->z_dim < 0 || a->v_dim < 0 || a->i_dim < 1) return 0;
+    const int n = a->x_dim + a->z_dim + a->v_dim + a->i_dim;
+    const psnode_mlp_f32 &d = a->de, &g = a->ae;
+    if (d.n_layers < 1 || d.n_layers > kMaxLayers || g.n_layers < 1 || g.n_layers > kMaxLayers) return 0;
+    if (d.in_dim != 3 * n || d.out_dim[d.n_layers - 1] != a->x_dim) return 0;
+    if (g.in_dim != n + a->x_dim + a->z_dim + a->v_dim || g.out_dim[g.n_layers - 1] != a->i_dim) return 0;
+    return generic_bwd_fits(&a->de, &a->ae, a->x_dim, a->z_dim, a->v_dim, a->i_dim, pre);
+}
+ViewDev view(const psnode_view_f32& v) { return ViewDev{v.ptr, v.stride_t, v.stride_b}; }
+GenericBwdCall generic_bwd_call(const psnode_ode_bwd_args_f32& a) {
+    GenericBwdCall c{};
+    c.method = a.method; c.xd = a.x_dim; c.zd = a.z_dim; c.T = a.T; c.B = a.B; c.de = &a.de;
+    c.t = view(a.t); c.z = view(a.z); c.a0 = a.all_initial;
+    c.ev = a.event_idx; c.zj = a.z_jump; c.zjb = a.zj_stride_b; c.zje = a.zj_stride_e; c.n_events = a.n_events;
+    c.xs = a.xs; c.gxs = a.grad_xs;
+    c.gx0 = a.grad_x0; c.gz = a.grad_z; c.gzj = a.grad_z_jump; c.ga0 = a.grad_all_initial; c.gparams_de = a.grad_params;
+    return c;
+}
+GenericBwdCall generic_bwd_call(const psnode_dae_bwd_args_f32& a) {
+    GenericBwdCall c{};
+    c.method = a.method; c.xd = a.x_dim; c.zd = a.z_dim; c.vd = a.v_dim; c.id = a.i_dim; c.T = a.T; c.B = a.B; c.de = &a.de; c.ae = &a.ae;
+    c.t = view(a.t); c.z = view(a.z); c.v = view(a.v); c.a0 = a.all_initial;
+    c.ev = a.event_idx; c.zj = a.z_jump; c.zjb = a.zj_stride_b; c.zje = a.zj_stride_e; c.vj = a.v_jump; c.vjb = a.vj_stride_b;
+    c.vje = a.vj_stride_e; c.n_events = a.n_events;
+    c.xs = a.xs; c.is_ = a.is; c.gxs = a.grad_xs; c.gis = a.grad_is;
+    c.gx0 = a.grad_x_init; c.gz = a.grad_z; c.gv = a.grad_v; c.gzj = a.grad_z_jump; c.gvj = a.grad_v_jump; c.ga0 = a.grad_all_initial;
+    c.gparams_de = a.grad_params_de; c.gparams_ae = a.grad_params_ae;
+    return c;
+}
+// act: the activations of a non-ELU(1) call, or nullptr
+int generic_backward(const GenericBwdCall& c, const ActPair* act, void* workspace, void* stream) {
+    const auto launch = !act ? generic_backward_launch : (act_pair_pre(*act) ? generic_backward_launch_pre : generic_backward_launch_act);
+    return launch(c, act, static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
+}
+// what a non-ELU(1) act asks of the call besides the dims: K5 (AUTO / GENERIC), no teacher forcing, no saved rows
+bool act_bwd_ok(int kernel, uint32_t flags, const void* saved_act) {
+    return (kernel == PSNODE_KERNEL_AUTO || kernel == PSNODE_KERNEL_GENERIC) && flags == 0 && !saved_act;
 }
 // K4f: every width <= 128 (z_dim up to 8), saved-activation and recompute forms
 bool use_fused_bwd(const psnode_ode_bwd_args_f32* a) { return a->kernel != PSNODE_KERNEL_GENERIC && fused_bwd_shape_ok(a); }
@@ -40,7 +108,7 @@ bool use_latent64_bwd(const psnode_ode_bwd_args_f32* a) {   // K9: the only fuse
 }  // namespace
 
 extern "C" int32_t psnode_ode_backward_supported(const psnode_ode_bwd_args_f32* a) {
-    if (!a || a->method < PSNODE_EULER || a->method > PSNODE_RK4_38) return 0;
+    if (!method_ok(a)) return 0;
     if (a->kernel == PSNODE_KERNEL_MFMA_WIDE || a->kernel == PSNODE_KERNEL_MFMA_TILE) return fused_bwd_shape_ok(a);
     if (a->kernel == PSNODE_KERNEL_MFMA_WAVE) return bwd_x_shape_ok(a);       // K4x (needs the saved rows at launch)
     if (a->kernel == PSNODE_KERNEL_MFMA) return fused_bwd_shape_ok(a) || use_latent_bwd(a) || use_latent64_bwd(a);
@@ -48,7 +116,7 @@ extern "C" int32_t psnode_ode_backward_supported(const psnode_ode_bwd_args_f32* 
 }
 
 extern "C" int64_t psnode_ode_backward_param_count(const psnode_ode_bwd_args_f32* a) {
-    return a && a->de.n_layers >= 1 && a->de.n_layers <= kMaxLayers ? generic_np(a->de) : 0;
+    return a && a->de.n_layers >= 1 && a->de.n_layers <= kMaxLayers ? mlp_np(a->de) : 0;
 }
 
 extern "C" size_t psnode_ode_backward_workspace_bytes(const psnode_ode_bwd_args_f32* a) {
@@ -62,16 +130,11 @@ extern "C" size_t psnode_ode_backward_workspace_bytes(const psnode_ode_bwd_args_
 }
 
 extern "C" int32_t psnode_ode_backward_f32(const psnode_ode_bwd_args_f32* a, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!a) return PSNODE_ERR_NULL;
-    if (a->method < PSNODE_EULER || a->method > PSNODE_RK4_38) return PSNODE_ERR_METHOD;
-    if (a->T < 1 || a->B < 1) return PSNODE_ERR_DIMS;
+    const int rc = check_call(a);
+    if (rc) return rc;
     if (!psnode_ode_backward_supported(a)) return PSNODE_ERR_UNSUPPORTED;
-    for (int l = 0; l < a->de.n_layers; ++l) if (!a->de.weight[l] || !a->de.bias[l]) return PSNODE_ERR_NULL;
-    if (!a->t.ptr || !a->all_initial || !a->xs || !a->grad_xs || !a->grad_x0 || !a->grad_all_initial || !a->grad_params) return PSNODE_ERR_NULL;
-    if (a->z_dim > 0 && !a->z.ptr) return PSNODE_ERR_NULL;
-    if (a->event_idx && a->z_dim > 0 && !a->z_jump) return PSNODE_ERR_NULL;
-    if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 255u) || workspace_bytes < psnode_ode_backward_workspace_bytes(a))
-        return PSNODE_ERR_WORKSPACE;
+    if (!ptrs_ok(a)) return PSNODE_ERR_NULL;
+    if (!workspace_ok(workspace, workspace_bytes, psnode_ode_backward_workspace_bytes(a))) return PSNODE_ERR_WORKSPACE;
     if ((a->saved_act != nullptr) != (a->saved_xstage != nullptr)) return PSNODE_ERR_NULL;
     if (a->kernel == PSNODE_KERNEL_MFMA_WAVE && !bwd_x_preferred(a)) return PSNODE_ERR_UNSUPPORTED;   // K4x: saved rows, no teacher forcing
     if (a->kernel == PSNODE_KERNEL_MFMA_TILE && !fused_bwd_shape_ok(a)) return PSNODE_ERR_UNSUPPORTED;
@@ -87,11 +150,7 @@ extern "C" int32_t psnode_ode_backward_f32(const psnode_ode_bwd_args_f32* a, voi
     if (use_latent64_bwd(a)) return latent64_ode_bwd_launch(a, static_cast<float*>(workspace), s);
     if (use_fused_bwd(a)) return fused_bwd_launch(a, static_cast<float*>(workspace), s);
     if (a->kernel == PSNODE_KERNEL_MFMA) return PSNODE_ERR_UNSUPPORTED;   // latent shape, unaligned views
-    return generic_backward_launch(a->method, a->x_dim, a->z_dim, 0, 0, a->T, a->B, &a->de, nullptr,
-                                   ViewDev{a->t.ptr, a->t.stride_t, a->t.stride_b}, ViewDev{a->z.ptr, a->z.stride_t, a->z.stride_b},
-                                   ViewDev{nullptr, 0, 0}, a->all_initial, a->event_idx, a->z_jump, a->zj_stride_b, a->zj_stride_e, nullptr,
-                                   0, 0, a->n_events, a->xs, nullptr, a->grad_xs, nullptr, a->grad_x0, a->grad_z, nullptr, a->grad_z_jump,
-                                   nullptr, a->grad_all_initial, a->grad_params, nullptr, static_cast<float*>(workspace), s);
+    return generic_backward(generic_bwd_call(*a), nullptr, workspace, stream);
 }
 
 namespace {
@@ -104,16 +163,11 @@ bool use_latent64_dae_bwd(const psnode_dae_bwd_args_f32* a) {
 }  // namespace
 
 extern "C" int32_t psnode_dae_backward_supported(const psnode_dae_bwd_args_f32* a) {
-    if (!a || a->method < PSNODE_EULER || a->method > PSNODE_RK4_38) return 0;
+    if (!method_ok(a)) return 0;
     if (a->x_dim < 1 || a->z_dim < 0 || a->v_dim < 0 || a->i_dim < 1) return 0;
     if (a->kernel == PSNODE_KERNEL_MFMA) return use_latent64_dae_bwd(a) || use_latent16_dae_bwd(a);
     if (use_latent64_dae_bwd(a) || use_latent16_dae_bwd(a)) return 1;
-    const int n = a->x_dim + a->z_dim + a->v_dim + a->i_dim;
-    const psnode_mlp_f32 &d = a->de, &g = a->ae;
-    if (d.n_layers < 1 || d.n_layers > kMaxLayers || g.n_layers < 1 || g.n_layers > kMaxLayers) return 0;
-    if (d.in_dim != 3 * n || d.out_dim[d.n_layers - 1] != a->x_dim) return 0;
-    if (g.in_dim != n + a->x_dim + a->z_dim + a->v_dim || g.out_dim[g.n_layers - 1] != a->i_dim) return 0;
-    return generic_bwd_fits(&a->de, &a->ae, a->x_dim, a->z_dim, a->v_dim, a->i_dim);
+    return dae_generic_ok(a);
 }
 
 extern "C" size_t psnode_dae_backward_workspace_bytes(const psnode_dae_bwd_args_f32* a) {
@@ -121,7 +175,7 @@ extern "C" size_t psnode_dae_backward_workspace_bytes(const psnode_dae_bwd_args_
     if (latent64_dae_bwd_shape_ok(a) && a->kernel != PSNODE_KERNEL_GENERIC) {
         // sized for every kernel this launch can end up on: K9, or K5 when the pointers turn out unaligned and K5 fits the shape
         size_t f = latent64_dae_bwd_workspace_floats(a);
-        if (generic_bwd_fits(&a->de, &a->ae, a->x_dim, a->z_dim, a->v_dim, a->i_dim)) {
+        if (generic_bwd_fits(&a->de, &a->ae, a->x_dim, a->z_dim, a->v_dim, a->i_dim, false)) {
             const size_t k5 = generic_bwd_workspace_floats(&a->de, &a->ae, a->B);
             f = k5 > f ? k5 : f;
         }
@@ -135,19 +189,11 @@ extern "C" size_t psnode_dae_backward_workspace_bytes(const psnode_dae_bwd_args_
 }
 
 extern "C" int32_t psnode_dae_backward_f32(const psnode_dae_bwd_args_f32* a, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!a) return PSNODE_ERR_NULL;
-    if (a->method < PSNODE_EULER || a->method > PSNODE_RK4_38) return PSNODE_ERR_METHOD;
-    if (a->T < 1 || a->B < 1) return PSNODE_ERR_DIMS;
+    const int rc = check_call(a);
+    if (rc) return rc;
     if (!psnode_dae_backward_supported(a)) return PSNODE_ERR_UNSUPPORTED;
-    for (int l = 0; l < a->de.n_layers; ++l) if (!a->de.weight[l] || !a->de.bias[l]) return PSNODE_ERR_NULL;
-    for (int l = 0; l < a->ae.n_layers; ++l) if (!a->ae.weight[l] || !a->ae.bias[l]) return PSNODE_ERR_NULL;
-    if (!a->t.ptr || !a->all_initial || !a->xs || !a->is || !a->grad_xs || !a->grad_x_init || !a->grad_all_initial || !a->grad_params_de ||
-        !a->grad_params_ae)
-        return PSNODE_ERR_NULL;
-    if ((a->z_dim > 0 && !a->z.ptr) || (a->v_dim > 0 && !a->v.ptr)) return PSNODE_ERR_NULL;
-    if (a->event_idx && ((a->z_dim > 0 && !a->z_jump) || (a->v_dim > 0 && !a->v_jump))) return PSNODE_ERR_NULL;
-    if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 255u) || workspace_bytes < psnode_dae_backward_workspace_bytes(a))
-        return PSNODE_ERR_WORKSPACE;
+    if (!ptrs_ok(a)) return PSNODE_ERR_NULL;
+    if (!workspace_ok(workspace, workspace_bytes, psnode_dae_backward_workspace_bytes(a))) return PSNODE_ERR_WORKSPACE;
     {
         const bool sv = a->saved_act != nullptr;
         if ((a->saved_xstage != nullptr) != sv || (a->saved_ae_act != nullptr) != sv) return PSNODE_ERR_NULL;
@@ -157,107 +203,54 @@ extern "C" int32_t psnode_dae_backward_f32(const psnode_dae_bwd_args_f32* a, voi
     if (use_latent64_dae_bwd(a)) return latent64_dae_bwd_launch(a, static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
     if (use_latent16_dae_bwd(a)) return latent16_dae_bwd_launch(a, static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
     if (a->kernel == PSNODE_KERNEL_MFMA) return PSNODE_ERR_UNSUPPORTED;
-    return generic_backward_launch(a->method, a->x_dim, a->z_dim, a->v_dim, a->i_dim, a->T, a->B, &a->de, &a->ae,
-                                   ViewDev{a->t.ptr, a->t.stride_t, a->t.stride_b}, ViewDev{a->z.ptr, a->z.stride_t, a->z.stride_b},
-                                   ViewDev{a->v.ptr, a->v.stride_t, a->v.stride_b}, a->all_initial, a->event_idx, a->z_jump, a->zj_stride_b,
-                                   a->zj_stride_e, a->v_jump, a->vj_stride_b, a->vj_stride_e, a->n_events, a->xs, a->is, a->grad_xs, a->grad_is,
-                                   a->grad_x_init, a->grad_z, a->grad_v, a->grad_z_jump, a->grad_v_jump, a->grad_all_initial,
-                                   a->grad_params_de, a->grad_params_ae, static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
+    return generic_backward(generic_bwd_call(*a), nullptr, workspace, stream);
 }
 
-// ---- hidden-layer activations other than ELU(1) (include/psnode_hip.h, psnode_act_f32): K5 only, no teacher forcing, no saved rows
-namespace {
-bool act_bwd_ok(int kernel, uint32_t flags, const void* saved_act) {
-    return (kernel == PSNODE_KERNEL_AUTO || kernel == PSNODE_KERNEL_GENERIC) && flags == 0 && !saved_act;
-}
-}  // namespace
-
+// ---- hidden-layer activations other than ELU(1) (include/psnode_hip.h, psnode_act_f32): K5 only, no teacher forcing, no saved rows.
+// The act is checked first and an ELU(1) pair forwarded to the entry point above; then NULL args -> method -> dims -> unsupported ->
+// pointers -> workspace, as there.
 extern "C" int32_t psnode_ode_backward_act_supported(const psnode_ode_bwd_args_f32* a, const psnode_act_f32* de_act) {
-    ActDev d;
+    ActPair p;
     bool elu1 = true;
-    if (act_from_abi(de_act, d, elu1)) return 0;
+    if (act_pair(de_act, nullptr, p, elu1)) return 0;
     if (elu1) return psnode_ode_backward_supported(a);
-    if (!a || a->method < PSNODE_EULER || a->method > PSNODE_RK4_38) return 0;
-    return act_bwd_ok(a->kernel, a->flags, a->saved_act) && ode_generic_ok(a, d.kind >= PSNODE_ACT_PRE_FAMILY);
+    return method_ok(a) && act_bwd_ok(a->kernel, a->flags, a->saved_act) && ode_generic_ok(a, act_pair_pre(p));
 }
 
 extern "C" int32_t psnode_ode_backward_act_f32(const psnode_ode_bwd_args_f32* a, const psnode_act_f32* de_act, void* workspace,
                                                size_t workspace_bytes, void* stream) {
     ActPair p;
-    bool elu1 = true, unused = true;
-    int rc = act_from_abi(de_act, p.de, elu1);
+    bool elu1 = true;
+    int rc = act_pair(de_act, nullptr, p, elu1);
     if (rc) return rc;
-    act_from_abi(nullptr, p.ae, unused);
     if (elu1) return psnode_ode_backward_f32(a, workspace, workspace_bytes, stream);
-    if (!a) return PSNODE_ERR_NULL;
-    if (a->method < PSNODE_EULER || a->method > PSNODE_RK4_38) return PSNODE_ERR_METHOD;
-    if (a->T < 1 || a->B < 1) return PSNODE_ERR_DIMS;
-    const bool pre = act_pair_pre(p);
-    if (!act_bwd_ok(a->kernel, a->flags, a->saved_act) || a->saved_xstage || !ode_generic_ok(a, pre)) return PSNODE_ERR_UNSUPPORTED;
-    for (int l = 0; l < a->de.n_layers; ++l) if (!a->de.weight[l] || !a->de.bias[l]) return PSNODE_ERR_NULL;
-    if (!a->t.ptr || !a->all_initial || !a->xs || !a->grad_xs || !a->grad_x0 || !a->grad_all_initial || !a->grad_params) return PSNODE_ERR_NULL;
-    if (a->z_dim > 0 && !a->z.ptr) return PSNODE_ERR_NULL;
-    if (a->event_idx && a->z_dim > 0 && !a->z_jump) return PSNODE_ERR_NULL;
-    if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 255u) ||
-        workspace_bytes < generic_bwd_workspace_floats(&a->de, nullptr, a->B) * sizeof(float))
-        return PSNODE_ERR_WORKSPACE;
-    return (pre ? generic_backward_launch_pre : generic_backward_launch_act)(p, a->method, a->x_dim, a->z_dim, 0, 0, a->T, a->B, &a->de, nullptr,
-                                       ViewDev{a->t.ptr, a->t.stride_t, a->t.stride_b}, ViewDev{a->z.ptr, a->z.stride_t, a->z.stride_b},
-                                       ViewDev{nullptr, 0, 0}, a->all_initial, a->event_idx, a->z_jump, a->zj_stride_b, a->zj_stride_e, nullptr,
-                                       0, 0, a->n_events, a->xs, nullptr, a->grad_xs, nullptr, a->grad_x0, a->grad_z, nullptr, a->grad_z_jump,
-                                       nullptr, a->grad_all_initial, a->grad_params, nullptr, static_cast<float*>(workspace),
-                                       static_cast<hipStream_t>(stream));
+    rc = check_call(a);
+    if (rc) return rc;
+    if (!act_bwd_ok(a->kernel, a->flags, a->saved_act) || a->saved_xstage || !ode_generic_ok(a, act_pair_pre(p))) return PSNODE_ERR_UNSUPPORTED;
+    if (!ptrs_ok(a)) return PSNODE_ERR_NULL;
+    if (!workspace_ok(workspace, workspace_bytes, generic_bwd_workspace_floats(&a->de, nullptr, a->B) * sizeof(float))) return PSNODE_ERR_WORKSPACE;
+    return generic_backward(generic_bwd_call(*a), &p, workspace, stream);
 }
-
-namespace {
-bool dae_generic_ok(const psnode_dae_bwd_args_f32* a, bool pre = false) {
-    if (a->x_dim < 1 || a->z_dim < 0 || a->v_dim < 0 || a->i_dim < 1) return false;
-    const int n = a->x_dim + a->z_dim + a->v_dim + a->i_dim;
-    const psnode_mlp_f32 &d = a->de, &g = a->ae;
-    if (d.n_layers < 1 || d.n_layers > kMaxLayers || g.n_layers < 1 || g.n_layers > kMaxLayers) return false;
-    if (d.in_dim != 3 * n || d.out_dim[d.n_layers - 1] != a->x_dim) return false;
-    if (g.in_dim != n + a->x_dim + a->z_dim + a->v_dim || g.out_dim[g.n_layers - 1] != a->i_dim) return false;
-    return (pre ? generic_bwd_fits_pre(&a->de, &a->ae, a->x_dim, a->z_dim, a->v_dim, a->i_dim)
-                : generic_bwd_fits(&a->de, &a->ae, a->x_dim, a->z_dim, a->v_dim, a->i_dim)) != 0;
-}
-}  // namespace
 
 extern "C" int32_t psnode_dae_backward_act_supported(const psnode_dae_bwd_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act) {
-    ActDev d, g;
-    bool e_de = true, e_ae = true;
-    if (act_from_abi(de_act, d, e_de) || act_from_abi(ae_act, g, e_ae)) return 0;
-    if (e_de && e_ae) return psnode_dae_backward_supported(a);
-    if (!a || a->method < PSNODE_EULER || a->method > PSNODE_RK4_38) return 0;
-    return act_bwd_ok(a->kernel, 0, a->saved_act) && dae_generic_ok(a, d.kind >= PSNODE_ACT_PRE_FAMILY || g.kind >= PSNODE_ACT_PRE_FAMILY);
+    ActPair p;
+    bool elu1 = true;
+    if (act_pair(de_act, ae_act, p, elu1)) return 0;
+    if (elu1) return psnode_dae_backward_supported(a);
+    return method_ok(a) && act_bwd_ok(a->kernel, 0, a->saved_act) && dae_generic_ok(a, act_pair_pre(p));
 }
 
 extern "C" int32_t psnode_dae_backward_act_f32(const psnode_dae_bwd_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
                                                void* workspace, size_t workspace_bytes, void* stream) {
     ActPair p;
-    bool e_de = true, e_ae = true;
-    int rc = act_from_abi(de_act, p.de, e_de);
-    if (rc == PSNODE_OK) rc = act_from_abi(ae_act, p.ae, e_ae);
+    bool elu1 = true;
+    int rc = act_pair(de_act, ae_act, p, elu1);
     if (rc) return rc;
-    if (e_de && e_ae) return psnode_dae_backward_f32(a, workspace, workspace_bytes, stream);
-    if (!a) return PSNODE_ERR_NULL;
-    if (a->method < PSNODE_EULER || a->method > PSNODE_RK4_38) return PSNODE_ERR_METHOD;
-    if (a->T < 1 || a->B < 1) return PSNODE_ERR_DIMS;
-    const bool pre = act_pair_pre(p);
-    if (!act_bwd_ok(a->kernel, 0, a->saved_act) || a->saved_xstage || a->saved_ae_act || !dae_generic_ok(a, pre)) return PSNODE_ERR_UNSUPPORTED;
-    for (int l = 0; l < a->de.n_layers; ++l) if (!a->de.weight[l] || !a->de.bias[l]) return PSNODE_ERR_NULL;
-    for (int l = 0; l < a->ae.n_layers; ++l) if (!a->ae.weight[l] || !a->ae.bias[l]) return PSNODE_ERR_NULL;
-    if (!a->t.ptr || !a->all_initial || !a->xs || !a->is || !a->grad_xs || !a->grad_x_init || !a->grad_all_initial || !a->grad_params_de ||
-        !a->grad_params_ae)
-        return PSNODE_ERR_NULL;
-    if ((a->z_dim > 0 && !a->z.ptr) || (a->v_dim > 0 && !a->v.ptr)) return PSNODE_ERR_NULL;
-    if (a->event_idx && ((a->z_dim > 0 && !a->z_jump) || (a->v_dim > 0 && !a->v_jump))) return PSNODE_ERR_NULL;
-    if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 255u) ||
-        workspace_bytes < generic_bwd_workspace_floats(&a->de, &a->ae, a->B) * sizeof(float))
-        return PSNODE_ERR_WORKSPACE;
-    return (pre ? generic_backward_launch_pre : generic_backward_launch_act)(p, a->method, a->x_dim, a->z_dim, a->v_dim, a->i_dim, a->T, a->B, &a->de, &a->ae,
-                                       ViewDev{a->t.ptr, a->t.stride_t, a->t.stride_b}, ViewDev{a->z.ptr, a->z.stride_t, a->z.stride_b},
-                                       ViewDev{a->v.ptr, a->v.stride_t, a->v.stride_b}, a->all_initial, a->event_idx, a->z_jump, a->zj_stride_b,
-                                       a->zj_stride_e, a->v_jump, a->vj_stride_b, a->vj_stride_e, a->n_events, a->xs, a->is, a->grad_xs,
-                                       a->grad_is, a->grad_x_init, a->grad_z, a->grad_v, a->grad_z_jump, a->grad_v_jump, a->grad_all_initial,
-                                       a->grad_params_de, a->grad_params_ae, static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
+    if (elu1) return psnode_dae_backward_f32(a, workspace, workspace_bytes, stream);
+    rc = check_call(a);
+    if (rc) return rc;
+    if (!act_bwd_ok(a->kernel, 0, a->saved_act) || a->saved_xstage || a->saved_ae_act || !dae_generic_ok(a, act_pair_pre(p))) return PSNODE_ERR_UNSUPPORTED;
+    if (!ptrs_ok(a)) return PSNODE_ERR_NULL;
+    if (!workspace_ok(workspace, workspace_bytes, generic_bwd_workspace_floats(&a->de, &a->ae, a->B) * sizeof(float))) return PSNODE_ERR_WORKSPACE;
+    return generic_backward(generic_bwd_call(*a), &p, workspace, stream);
 }

@@ -24,18 +24,20 @@ size_t generic_floats(const psnode_mlp_f32* m) {
     return tot;
 }
 
-int check_mlp(const psnode_mlp_f32& m, int want_in, int want_out) {
+// the widths alone (the dims-only queries); `ptrs`: also every layer's weight and bias, in check_mlp's order of statuses
+int check_mlp_dims(const psnode_mlp_f32& m, int want_in, int want_out, bool ptrs = false) {
     if (m.n_layers < 1 || m.n_layers > kMaxLayers) return PSNODE_ERR_DIMS;
     if (m.in_dim != want_in || m.in_dim < 1) return PSNODE_ERR_DIMS;
     if (m.in_dim > PSNODE_MAX_IN_WIDTH) return PSNODE_ERR_UNSUPPORTED;    // consistent, but wider than any kernel takes
     for (int l = 0; l < m.n_layers; ++l) {
         if (m.out_dim[l] < 1) return PSNODE_ERR_DIMS;
         if (m.out_dim[l] > PSNODE_MAX_WIDTH) return PSNODE_ERR_UNSUPPORTED;
-        if (!m.weight[l] || !m.bias[l]) return PSNODE_ERR_NULL;
+        if (ptrs && (!m.weight[l] || !m.bias[l])) return PSNODE_ERR_NULL;
     }
     if (m.out_dim[m.n_layers - 1] != want_out) return PSNODE_ERR_DIMS;
     return PSNODE_OK;
 }
+int check_mlp(const psnode_mlp_f32& m, int want_in, int want_out) { return check_mlp_dims(m, want_in, want_out, true); }
 
 // Fills `d` and assigns the transposed-weight segments; returns the next free float of the workspace.
 float* bind_mlp(const psnode_mlp_f32& m, MlpDev& d, float* ws) {
@@ -56,6 +58,13 @@ float* bind_mlp(const psnode_mlp_f32& m, MlpDev& d, float* ws) {
 int max_width(const psnode_mlp_f32& m) {
     int w = m.in_dim;
     for (int l = 0; l < m.n_layers; ++l) w = m.out_dim[l] > w ? m.out_dim[l] : w;
+    return w;
+}
+// widest layer OUTPUT of the call's MLPs (IntegrateDev::maxo)
+int max_out_width(const psnode_mlp_f32& de, const psnode_mlp_f32* ae) {
+    int w = 1;
+    for (int l = 0; l < de.n_layers; ++l) w = de.out_dim[l] > w ? de.out_dim[l] : w;
+    if (ae) for (int l = 0; l < ae->n_layers; ++l) w = ae->out_dim[l] > w ? ae->out_dim[l] : w;
     return w;
 }
 
@@ -87,9 +96,7 @@ int dispatch(IntegrateDev& d, bool dae, int kernel, const psnode_mlp_f32* de, co
     if (dae) ws = bind_mlp(*ae, d.ae, ws);
     d.maxw = max_width(*de);
     if (dae && max_width(*ae) > d.maxw) d.maxw = max_width(*ae);
-    d.maxo = 1;
-    for (int l = 0; l < de->n_layers; ++l) d.maxo = de->out_dim[l] > d.maxo ? de->out_dim[l] : d.maxo;
-    if (dae) for (int l = 0; l < ae->n_layers; ++l) d.maxo = ae->out_dim[l] > d.maxo ? ae->out_dim[l] : d.maxo;
+    d.maxo = max_out_width(*de, dae ? ae : nullptr);
 
     const bool has_mfma = !act && (dae ? mfma_dae_supported(d) : mfma_ode_supported(d));
     const bool want_mfma = kernel == PSNODE_KERNEL_MFMA || kernel == PSNODE_KERNEL_MFMA_TILE || kernel == PSNODE_KERNEL_MFMA_WAVE;
@@ -111,6 +118,31 @@ int dispatch(IntegrateDev& d, bool dae, int kernel, const psnode_mlp_f32* de, co
     return e == hipSuccess ? PSNODE_OK : PSNODE_ERR_HIP;
 }
 
+// dims-only view of the args: what the *_save_hidden / *_kernel_for / *_act_supported queries ask the kernel families with (no pointers),
+// and what fill_ode / fill_dae start from
+void bind_dims(const psnode_mlp_f32& m, MlpDev& d) {
+    d.n_layers = m.n_layers;
+    d.in_dim = m.in_dim;
+    for (int l = 0; l < m.n_layers && l < kMaxLayers; ++l) d.out_dim[l] = m.out_dim[l];
+}
+IntegrateDev dims_only(const psnode_ode_args_f32& a) {
+    IntegrateDev d;
+    memset(&d, 0, sizeof(d));
+    d.method = a.method; d.flags = a.flags; d.xd = a.x_dim; d.zd = a.z_dim; d.T = a.T; d.B = a.B;
+    bind_dims(a.de, d.de);
+    d.kern = a.kernel;      // a forced _TILE / _WAVE / GENERIC is what the call would run
+    return d;
+}
+IntegrateDev dims_only(const psnode_dae_args_f32& a) {
+    IntegrateDev d;
+    memset(&d, 0, sizeof(d));
+    d.method = a.method; d.flags = a.flags; d.xd = a.x_dim; d.zd = a.z_dim; d.vd = a.v_dim; d.id = a.i_dim; d.T = a.T; d.B = a.B;
+    bind_dims(a.de, d.de);
+    bind_dims(a.ae, d.ae);
+    d.kern = a.kernel;
+    return d;
+}
+
 int fill_ode(const psnode_ode_args_f32* a, IntegrateDev& d) {
     if (!a) return PSNODE_ERR_NULL;
     if (a->method < PSNODE_EULER || a->method > PSNODE_RK4_38) return PSNODE_ERR_METHOD;
@@ -121,13 +153,8 @@ int fill_ode(const psnode_ode_args_f32* a, IntegrateDev& d) {
     if (!a->t.ptr || !a->x.ptr || !a->all_initial || !a->x_out) return PSNODE_ERR_NULL;
     if (a->z_dim > 0 && !a->z.ptr) return PSNODE_ERR_NULL;
     if (a->event_idx && a->z_dim > 0 && !a->z_jump) return PSNODE_ERR_NULL;
-    memset(&d, 0, sizeof(d));
-    d.method = a->method;
-    d.flags = a->flags & PSNODE_FLAG_INPUT_TRUE_X;
-    d.xd = a->x_dim;
-    d.zd = a->z_dim;
-    d.T = a->T;
-    d.B = a->B;
+    d = dims_only(*a);
+    d.flags &= PSNODE_FLAG_INPUT_TRUE_X;
     d.t = view(a->t);
     d.x = view(a->x);
     d.z = view(a->z);
@@ -157,15 +184,8 @@ int fill_dae(const psnode_dae_args_f32* a, IntegrateDev& d) {
     if ((a->flags & PSNODE_FLAG_INPUT_TRUE_X) && !a->x.ptr) return PSNODE_ERR_NULL;
     if ((a->flags & PSNODE_FLAG_INPUT_TRUE_I) && !a->i.ptr) return PSNODE_ERR_NULL;
     if (a->event_idx && ((a->z_dim > 0 && !a->z_jump) || (a->v_dim > 0 && !a->v_jump))) return PSNODE_ERR_NULL;
-    memset(&d, 0, sizeof(d));
-    d.method = a->method;
-    d.flags = a->flags & (PSNODE_FLAG_INPUT_TRUE_X | PSNODE_FLAG_INPUT_TRUE_I);
-    d.xd = a->x_dim;
-    d.zd = a->z_dim;
-    d.vd = a->v_dim;
-    d.id = a->i_dim;
-    d.T = a->T;
-    d.B = a->B;
+    d = dims_only(*a);
+    d.flags &= PSNODE_FLAG_INPUT_TRUE_X | PSNODE_FLAG_INPUT_TRUE_I;
     d.t = view(a->t);
     d.x = view(a->x);
     d.z = view(a->z);
@@ -193,25 +213,9 @@ int fill_dae(const psnode_dae_args_f32* a, IntegrateDev& d) {
     return PSNODE_OK;
 }
 
-// the two activations of an _act call; `elu1`: both are ELU(1), the call takes the entry point without _act
-int act_pair(const psnode_act_f32* de, const psnode_act_f32* ae, ActPair& p, bool& elu1) {
-    bool e_de = true, e_ae = true;
-    int rc = act_from_abi(de, p.de, e_de);
-    if (rc == PSNODE_OK) rc = act_from_abi(ae, p.ae, e_ae);
-    elu1 = e_de && e_ae;
-    return rc;
-}
-
 // what a non-ELU(1) act asks of the call besides the dims: K0 (AUTO / GENERIC), no training side outputs
 bool act_call_ok(int kernel, const void* save_act) {
     return (kernel == PSNODE_KERNEL_AUTO || kernel == PSNODE_KERNEL_GENERIC) && !save_act;
-}
-
-// dims-only view of the args for the *_kernel_for queries (pointers unused)
-void bind_dims(const psnode_mlp_f32& m, MlpDev& d) {
-    d.n_layers = m.n_layers;
-    d.in_dim = m.in_dim;
-    for (int l = 0; l < m.n_layers && l < kMaxLayers; ++l) d.out_dim[l] = m.out_dim[l];
 }
 
 }  // namespace
@@ -288,46 +292,28 @@ int32_t psnode_event_table_f32(int64_t n_steps, const float* clock, int64_t stri
 }
 
 int32_t psnode_ode_save_hidden(const psnode_ode_args_f32* a) {
-    if (!a) return 0;
-    IntegrateDev d;
-    memset(&d, 0, sizeof(d));
-    d.method = a->method; d.flags = a->flags; d.xd = a->x_dim; d.zd = a->z_dim; d.T = a->T; d.B = a->B;
-    bind_dims(a->de, d.de);
-    return a->kernel == PSNODE_KERNEL_GENERIC ? 0 : mfma_ode_save_hidden(d);
+    return !a || a->kernel == PSNODE_KERNEL_GENERIC ? 0 : mfma_ode_save_hidden(dims_only(*a));
 }
 
 int32_t psnode_ode_integrate_f32(const psnode_ode_args_f32* args, void* workspace, size_t workspace_bytes, void* stream) {
     IntegrateDev d;
     const int rc = fill_ode(args, d);
     if (rc) return rc;
-    if (d.sact) {      // only K1 proper / K3c write the training side outputs (checked with the pointers in place: alignment counts)
-        IntegrateDev q = d;
-        bind_dims(args->de, q.de);
-        if (args->kernel == PSNODE_KERNEL_GENERIC || !mfma_ode_save_hidden(q)) return PSNODE_ERR_UNSUPPORTED;
-    }
+    // only K1 proper / K3c write the training side outputs (checked with the pointers in place: alignment counts)
+    if (d.sact && (args->kernel == PSNODE_KERNEL_GENERIC || !mfma_ode_save_hidden(d))) return PSNODE_ERR_UNSUPPORTED;
     return dispatch(d, false, args->kernel, &args->de, nullptr, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
 }
 
 int32_t psnode_dae_save_hidden(const psnode_dae_args_f32* a) {
-    if (!a) return 0;
-    IntegrateDev d;
-    memset(&d, 0, sizeof(d));
-    d.method = a->method; d.flags = a->flags; d.xd = a->x_dim; d.zd = a->z_dim; d.vd = a->v_dim; d.id = a->i_dim; d.T = a->T; d.B = a->B;
-    bind_dims(a->de, d.de);
-    bind_dims(a->ae, d.ae);
-    return a->kernel == PSNODE_KERNEL_GENERIC ? 0 : mfma_dae_save_hidden(d);
+    return !a || a->kernel == PSNODE_KERNEL_GENERIC ? 0 : mfma_dae_save_hidden(dims_only(*a));
 }
 
 int32_t psnode_dae_integrate_f32(const psnode_dae_args_f32* args, void* workspace, size_t workspace_bytes, void* stream) {
     IntegrateDev d;
     const int rc = fill_dae(args, d);
     if (rc) return rc;
-    if (d.sact) {      // only K2 proper writes the training side outputs
-        IntegrateDev q = d;
-        bind_dims(args->de, q.de);
-        bind_dims(args->ae, q.ae);
-        if (args->kernel == PSNODE_KERNEL_GENERIC || !mfma_dae_save_hidden(q)) return PSNODE_ERR_UNSUPPORTED;
-    }
+    // only K2 proper writes the training side outputs
+    if (d.sact && (args->kernel == PSNODE_KERNEL_GENERIC || !mfma_dae_save_hidden(d))) return PSNODE_ERR_UNSUPPORTED;
     return dispatch(d, true, args->kernel, &args->de, &args->ae, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
 }
 
@@ -336,18 +322,11 @@ int32_t psnode_ode_integrate_act_supported(const psnode_ode_args_f32* a, const p
     bool elu1 = true;
     if (!a || act_pair(de_act, nullptr, p, elu1)) return 0;
     if (a->method < PSNODE_EULER || a->method > PSNODE_RK4_38 || a->x_dim < 1 || a->z_dim < 0) return 0;
-    const psnode_mlp_f32& m = a->de;
-    if (m.n_layers < 1 || m.n_layers > kMaxLayers || m.in_dim != 3 * (a->x_dim + a->z_dim) || m.in_dim > PSNODE_MAX_IN_WIDTH) return 0;
-    for (int l = 0; l < m.n_layers; ++l) if (m.out_dim[l] < 1 || m.out_dim[l] > PSNODE_MAX_WIDTH) return 0;
-    if (m.out_dim[m.n_layers - 1] != a->x_dim) return 0;
+    if (check_mlp_dims(a->de, 3 * (a->x_dim + a->z_dim), a->x_dim)) return 0;
     if (elu1) return 1;
     if (!act_call_ok(a->kernel, a->save_act)) return 0;
-    IntegrateDev d;
-    memset(&d, 0, sizeof(d));
-    d.xd = a->x_dim; d.zd = a->z_dim;
-    bind_dims(m, d.de);
-    d.maxo = 1;
-    for (int l = 0; l < m.n_layers; ++l) d.maxo = m.out_dim[l] > d.maxo ? m.out_dim[l] : d.maxo;
+    IntegrateDev d = dims_only(*a);
+    d.maxo = max_out_width(a->de, nullptr);
     return generic_lds_bytes(d, false) <= 160 * 1024;
 }
 
@@ -371,23 +350,11 @@ int32_t psnode_dae_integrate_act_supported(const psnode_dae_args_f32* a, const p
     if (!a || act_pair(de_act, ae_act, p, elu1)) return 0;
     if (a->method < PSNODE_EULER || a->method > PSNODE_RK4_38 || a->x_dim < 1 || a->z_dim < 0 || a->v_dim < 0 || a->i_dim < 1) return 0;
     const int n = a->x_dim + a->z_dim + a->v_dim + a->i_dim;
-    IntegrateDev d;
-    memset(&d, 0, sizeof(d));
-    d.xd = a->x_dim; d.zd = a->z_dim; d.vd = a->v_dim; d.id = a->i_dim;
-    d.maxo = 1;
-    for (int k = 0; k < 2; ++k) {
-        const psnode_mlp_f32& m = k ? a->ae : a->de;
-        const int want_in = k ? n + a->x_dim + a->z_dim + a->v_dim : 3 * n, want_out = k ? a->i_dim : a->x_dim;
-        if (m.n_layers < 1 || m.n_layers > kMaxLayers || m.in_dim != want_in || m.in_dim > PSNODE_MAX_IN_WIDTH) return 0;
-        for (int l = 0; l < m.n_layers; ++l) {
-            if (m.out_dim[l] < 1 || m.out_dim[l] > PSNODE_MAX_WIDTH) return 0;
-            d.maxo = m.out_dim[l] > d.maxo ? m.out_dim[l] : d.maxo;
-        }
-        if (m.out_dim[m.n_layers - 1] != want_out) return 0;
-        bind_dims(m, k ? d.ae : d.de);
-    }
+    if (check_mlp_dims(a->de, 3 * n, a->x_dim) || check_mlp_dims(a->ae, n + a->x_dim + a->z_dim + a->v_dim, a->i_dim)) return 0;
     if (elu1) return 1;
     if (!act_call_ok(a->kernel, a->save_act)) return 0;
+    IntegrateDev d = dims_only(*a);
+    d.maxo = max_out_width(a->de, &a->ae);
     return generic_lds_bytes(d, true) <= 160 * 1024;
 }
 
@@ -407,11 +374,7 @@ int32_t psnode_dae_integrate_act_f32(const psnode_dae_args_f32* args, const psno
 
 int32_t psnode_ode_kernel_for(const psnode_ode_args_f32* a) {
     if (!a) return PSNODE_ERR_NULL;
-    IntegrateDev d;
-    memset(&d, 0, sizeof(d));
-    d.method = a->method; d.flags = a->flags; d.xd = a->x_dim; d.zd = a->z_dim; d.T = a->T; d.B = a->B;
-    bind_dims(a->de, d.de);
-    d.kern = a->kernel;                                              // a forced _TILE / _WAVE / GENERIC is what the call would run
+    IntegrateDev d = dims_only(*a);
     if (a->kernel == PSNODE_KERNEL_GENERIC || !mfma_ode_supported(d)) return PSNODE_KERNEL_GENERIC;
     d.sact = a->save_act;
     return mfma_x_ode_preferred(d) ? PSNODE_KERNEL_MFMA_WAVE : PSNODE_KERNEL_MFMA;      // (_WAVE: K1x -- the one-wave-per-4-trajectories integrator)
@@ -419,13 +382,7 @@ int32_t psnode_ode_kernel_for(const psnode_ode_args_f32* a) {
 
 int32_t psnode_dae_kernel_for(const psnode_dae_args_f32* a) {
     if (!a) return PSNODE_ERR_NULL;
-    IntegrateDev d;
-    memset(&d, 0, sizeof(d));
-    d.method = a->method; d.flags = a->flags; d.xd = a->x_dim; d.zd = a->z_dim; d.vd = a->v_dim; d.id = a->i_dim;
-    d.T = a->T; d.B = a->B;
-    bind_dims(a->de, d.de);
-    bind_dims(a->ae, d.ae);
-    d.kern = a->kernel;
+    IntegrateDev d = dims_only(*a);
     if (a->kernel == PSNODE_KERNEL_GENERIC || !mfma_dae_supported(d)) return PSNODE_KERNEL_GENERIC;
     d.sact = a->save_act;
     return mfma_x_dae_preferred(d) ? PSNODE_KERNEL_MFMA_WAVE : PSNODE_KERNEL_MFMA;      // (_WAVE: K2x)

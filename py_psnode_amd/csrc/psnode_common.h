@@ -290,13 +290,37 @@ hipError_t launch_mfma_h192(const IntegrateDev& a, bool dae, float* pack, hipStr
 hipError_t launch_mfma_h256(const IntegrateDev& a, bool dae, float* pack, hipStream_t stream);   // psnode_mfma_h256.hip (forward only)
 
 // psnode_generic_bwd.hip (K5: generic fused backward, ODE and DAE)
+// parameters of an MLP in the flat gradient vector (nn.Linear order: W, b per layer)
+inline int mlp_np(const psnode_mlp_f32& m) {
+    int np = 0, k = m.in_dim;
+    for (int l = 0; l < m.n_layers; ++l) { np += m.out_dim[l] * (k + 1); k = m.out_dim[l]; }
+    return np;
+}
+// One K5 call (host side only).  The ODE call is the DAE call with vd = id = 0, ae = nullptr and the v / i fields left zero
+// (psnode_backward.hip: generic_bwd_call).
+struct GenericBwdCall {
+    int method, xd, zd, vd, id;
+    long long T, B;
+    const psnode_mlp_f32 *de, *ae;
+    ViewDev t, z, v;
+    const float* a0;
+    const int* ev;
+    const float* zj; long long zjb, zje;
+    const float* vj; long long vjb, vje;
+    int n_events;
+    const float *xs, *is_, *gxs, *gis;
+    float *gx0, *gz, *gv, *gzj, *gvj, *ga0, *gparams_de, *gparams_ae;
+};
+struct ActPair;     // psnode_act.h: the DE's and the AE's activation of a non-ELU(1) call
 size_t generic_bwd_workspace_floats(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, long long B);
-int generic_bwd_fits(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, int xd, int zd, int vd, int id);
-int generic_backward_launch(int method, int xd, int zd, int vd, int id, long long T, long long B, const psnode_mlp_f32* de,
-                            const psnode_mlp_f32* ae, ViewDev t, ViewDev z, ViewDev v, const float* a0, const int* ev, const float* zj,
-                            long long zjb, long long zje, const float* vj, long long vjb, long long vje, int n_events, const float* xs,
-                            const float* is_, const float* gxs, const float* gis, float* gx0, float* gz, float* gv, float* gzj, float* gvj,
-                            float* ga0, float* gparams_de, float* gparams_ae, float* workspace, hipStream_t stream);
+// pre: the fit of K5's pre-activation build (it keeps u in LDS as well: generic_bwd_fits_pre, psnode_generic_bwd_pre.hip)
+int generic_bwd_fits(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, int xd, int zd, int vd, int id, bool pre);
+int generic_bwd_fits_pre(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, int xd, int zd, int vd, int id);
+// One launcher per build of psnode_generic_bwd.hip: ELU(1) (ignores `act`), the activations of psnode_act.h (psnode_generic_bwd_act.hip),
+// those and the pre-activation family (psnode_generic_bwd_pre.hip).  psnode_backward.hip: generic_backward picks among them.
+int generic_backward_launch(const GenericBwdCall& c, const ActPair* act, float* workspace, hipStream_t stream);
+int generic_backward_launch_act(const GenericBwdCall& c, const ActPair* act, float* workspace, hipStream_t stream);
+int generic_backward_launch_pre(const GenericBwdCall& c, const ActPair* act, float* workspace, hipStream_t stream);
 
 // psnode_latent.hip (direct_encode latent shapes, hidden_dim 16)
 bool latent_shape_ok(const IntegrateDev& a, bool dae);

@@ -1037,11 +1037,6 @@ size_t mlp_wt_floats(const psnode_mlp_f32& m) {
     for (int l = 0; l < m.n_layers; ++l) { tot += ((size_t)k * m.out_dim[l] + 63) / 64 * 64; k = m.out_dim[l]; }
     return tot;
 }
-int mlp_np(const psnode_mlp_f32& m) {
-    int np = 0, k = m.in_dim;
-    for (int l = 0; l < m.n_layers; ++l) { np += m.out_dim[l] * (k + 1); k = m.out_dim[l]; }
-    return np;
-}
 bool mlp_ok(const psnode_mlp_f32& m, int in_dim, int out_dim) {
     if (m.n_layers < 1 || m.n_layers > kMaxLayers || m.in_dim != in_dim || m.out_dim[m.n_layers - 1] != out_dim) return false;
     for (int l = 0; l < m.n_layers; ++l)
@@ -1083,32 +1078,30 @@ size_t generic_bwd_workspace_floats(const psnode_mlp_f32* de, const psnode_mlp_f
            reg_image_floats(*de) + 64 + (ae ? reg_image_floats(*ae) + 64 : 0) + nwg * tm_floats(*de, ae) + 64;
 }
 
-int generic_bwd_fits(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, int xd, int zd, int vd, int id) {
-    return bwd_fits_here(de, ae, xd, zd, vd, id);
+int generic_bwd_fits(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, int xd, int zd, int vd, int id, bool pre) {
+    return pre ? generic_bwd_fits_pre(de, ae, xd, zd, vd, id) : bwd_fits_here(de, ae, xd, zd, vd, id);
 }
 
 #endif  // PSNODE_K5_ACT_BUILD
 
-// launches pack (transpose), the backward kernel and the partial reduction
+// launches pack (transpose), the backward kernel and the partial reduction (`act`: read by the activation builds only)
 #if defined(PSNODE_K5_PRE_BUILD)
-int generic_backward_launch_pre(const ActPair& act, int method,
+int generic_backward_launch_pre(
 #elif defined(PSNODE_K5_ACT_BUILD)
-int generic_backward_launch_act(const ActPair& act, int method,
+int generic_backward_launch_act(
 #else
-int generic_backward_launch(int method,
+int generic_backward_launch(
 #endif
-                            int xd, int zd, int vd, int id, long long T, long long B, const psnode_mlp_f32* de,
-                            const psnode_mlp_f32* ae, ViewDev t, ViewDev z, ViewDev v, const float* a0, const int* ev, const float* zj,
-                            long long zjb, long long zje, const float* vj, long long vjb, long long vje, int n_events, const float* xs,
-                            const float* is_, const float* gxs, const float* gis, float* gx0, float* gz, float* gv, float* gzj, float* gvj,
-                            float* ga0, float* gparams_de, float* gparams_ae, float* workspace, hipStream_t stream) {
+    const GenericBwdCall& c, const ActPair* act, float* workspace, hipStream_t stream) {
+    const psnode_mlp_f32 *de = c.de, *ae = c.ae;
     const bool dae = ae != nullptr;
-    const int n = xd + zd + (dae ? vd + id : 0);
-    if (!mlp_ok(*de, 3 * n, xd)) return PSNODE_ERR_DIMS;
-    if (dae && !mlp_ok(*ae, n + xd + zd + vd, id)) return PSNODE_ERR_DIMS;
+    const long long B = c.B;
+    const int n = c.xd + c.zd + (dae ? c.vd + c.id : 0);
+    if (!mlp_ok(*de, 3 * n, c.xd)) return PSNODE_ERR_DIMS;
+    if (dae && !mlp_ok(*ae, n + c.xd + c.zd + c.vd, c.id)) return PSNODE_ERR_DIMS;
     GBwd a;
     memset(&a, 0, sizeof(a));
-    a.method = method; a.dae = dae; a.xd = xd; a.zd = zd; a.vd = vd; a.id = id; a.T = T; a.B = B;
+    a.method = c.method; a.dae = dae; a.xd = c.xd; a.zd = c.zd; a.vd = c.vd; a.id = c.id; a.T = c.T; a.B = B;
     float* ws = workspace;
     int rows = fill_gmlp(*de, a.de, ws);
     a.maxw = mlp_maxw(*de);
@@ -1118,9 +1111,9 @@ int generic_backward_launch(int method,
         a.maxw = mlp_maxw(*ae) > a.maxw ? mlp_maxw(*ae) : a.maxw;
     }
     a.act_rows = rows;
-    a.t = t; a.z = z; a.v = v; a.a0 = a0; a.ev = ev; a.zj = zj; a.zjb = zjb; a.zje = zje; a.vj = vj; a.vjb = vjb; a.vje = vje;
-    a.n_events = n_events; a.xs = xs; a.is_ = is_; a.gxs = gxs; a.gis = gis; a.gx0 = gx0; a.gz = gz; a.gv = gv; a.gzj = gzj; a.gvj = gvj;
-    a.ga0 = ga0;
+    a.t = c.t; a.z = c.z; a.v = c.v; a.a0 = c.a0; a.ev = c.ev; a.zj = c.zj; a.zjb = c.zjb; a.zje = c.zje; a.vj = c.vj; a.vjb = c.vjb;
+    a.vje = c.vje; a.n_events = c.n_events; a.xs = c.xs; a.is_ = c.is_; a.gxs = c.gxs; a.gis = c.gis; a.gx0 = c.gx0; a.gz = c.gz; a.gv = c.gv;
+    a.gzj = c.gzj; a.gvj = c.gvj; a.ga0 = c.ga0;
     a.de_reg = de_reg_class(*de) ? 1 : 0;
     float* img[kMaxLayers] = {}, *imgT[kMaxLayers] = {}, *imgA[kMaxLayers] = {}, *imgTA[kMaxLayers] = {};
     {                           // the plain / transposed images of both MLPs sit in front of the per-workgroup partials
@@ -1170,9 +1163,9 @@ int generic_backward_launch(int method,
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         return PSNODE_ERR_HIP;
     const unsigned nwg = (unsigned)((B + TB - 1) / TB);
-    hipLaunchKernelGGL(kern, dim3(nwg), dim3(NT), lds, stream, a K5_LAUNCH_ARG(act));
+    hipLaunchKernelGGL(kern, dim3(nwg), dim3(NT), lds, stream, a K5_LAUNCH_ARG(*act));
     if (hipGetLastError() != hipSuccess) return PSNODE_ERR_HIP;
-    return launch_reduce_partials(a.wpart, gparams_de, gparams_ae, a.de.np, dae ? a.ae.np : 0, (int)nwg, stream) == hipSuccess ? PSNODE_OK : PSNODE_ERR_HIP;
+    return launch_reduce_partials(a.wpart, c.gparams_de, c.gparams_ae, a.de.np, dae ? a.ae.np : 0, (int)nwg, stream) == hipSuccess ? PSNODE_OK : PSNODE_ERR_HIP;
 }
 
 }  // namespace psnode

@@ -16,6 +16,7 @@ Layers = Sequence[Tuple[torch.Tensor, torch.Tensor]]
 
 
 METHOD_ID = {"euler": _lib.EULER, "midpoint": _lib.MIDPOINT, "rk4": _lib.RK4_38}
+STAGES = {"euler": 1, "midpoint": 2, "rk4": 4}      # right-hand-side evaluations per step
 
 
 KERNEL_ID = {"auto": _lib.KERNEL_AUTO, "generic": _lib.KERNEL_GENERIC, "mfma": _lib.KERNEL_MFMA, "wide": _lib.KERNEL_MFMA_WIDE,
@@ -41,28 +42,6 @@ def _empty(*size, **kw) -> torch.Tensor:
 
 
 # ----------------------------------------------------------------------------- recognition
-def sequential_layers(seq) -> Optional[List[Tuple[torch.Tensor, torch.Tensor]]]:
-    """[(W,b), ...] if `seq` is nn.Sequential(Linear, ELU(alpha=1), Linear, ..., Linear), else None
-    (the only MLP shape the reference's live right-hand sides use, neural_00_ODE_01_no_encode.py:61-64)."""
-    if not isinstance(seq, nn.Sequential) or len(seq) == 0 or len(seq) % 2 == 0:
-        return None
-    out = []
-    for k, m in enumerate(seq):
-        if k % 2 == 0:
-            if type(m) is not nn.Linear or m.bias is None:
-                return None
-            out.append((m.weight, m.bias))
-        else:
-            if type(m) is not nn.ELU or m.alpha != 1.0:
-                return None
-    if len(out) > _lib.MAX_LAYERS:
-        return None
-    for (w, _), (w2, _) in zip(out[:-1], out[1:]):
-        if w2.shape[1] != w.shape[0]:
-            return None
-    return out
-
-
 class Act:
     """A hidden-layer activation other than ELU(alpha=1) that the generic kernels K0 / K5 apply (psnode_act_f32, include/psnode_hip.h).
     Everywhere in this package `act=None` means ELU(1), the activation of every specialised kernel.  Calling it applies the activation
@@ -78,26 +57,7 @@ class Act:
         return a
 
     def __call__(self, u: torch.Tensor) -> torch.Tensor:
-        F = nn.functional
-        if self.kind == _lib.ACT_ELU:
-            return F.elu(u, self.alpha)
-        if self.kind == _lib.ACT_TANH:
-            return torch.tanh(u)
-        if self.kind == _lib.ACT_SIGMOID:
-            return torch.sigmoid(u)
-        if self.kind == _lib.ACT_RELU:
-            return F.relu(u)
-        if self.kind == _lib.ACT_LEAKY_RELU:
-            return F.leaky_relu(u, self.alpha)
-        if self.kind == _lib.ACT_SILU:
-            return F.silu(u)
-        if self.kind == _lib.ACT_GELU:
-            return F.gelu(u)
-        if self.kind == _lib.ACT_GELU_TANH:
-            return F.gelu(u, approximate="tanh")
-        if self.kind == _lib.ACT_MISH:
-            return F.mish(u)
-        return F.softplus(u, self.beta, self.threshold)
+        return _ACT_TORCH[self.kind](self, u)
 
     def _key(self):
         return (self.kind, self.alpha, self.beta, self.threshold)
@@ -112,18 +72,48 @@ class Act:
         return f"Act({self.name})"
 
 
+_F = nn.functional
+_ACT_TORCH = {
+    _lib.ACT_ELU: lambda a, u: _F.elu(u, a.alpha),
+    _lib.ACT_TANH: lambda a, u: torch.tanh(u),
+    _lib.ACT_SIGMOID: lambda a, u: torch.sigmoid(u),
+    _lib.ACT_RELU: lambda a, u: _F.relu(u),
+    _lib.ACT_LEAKY_RELU: lambda a, u: _F.leaky_relu(u, a.alpha),
+    _lib.ACT_SOFTPLUS: lambda a, u: _F.softplus(u, a.beta, a.threshold),
+    _lib.ACT_SILU: lambda a, u: _F.silu(u),
+    _lib.ACT_GELU: lambda a, u: _F.gelu(u),
+    _lib.ACT_GELU_TANH: lambda a, u: _F.gelu(u, approximate="tanh"),
+    _lib.ACT_MISH: lambda a, u: _F.mish(u),
+}
+
+
 def _act_refs(*acts):
     """ctypes pointers of the psnode_act_f32 of `acts` (None = ELU(1): NULL), and whether any of them is not ELU(1)."""
     refs = [ctypes.byref(a.abi()) if a is not None else None for a in acts]
     return refs, any(a is not None for a in acts)
 
 
-def _dae_acts(act):
-    """act of a DAE call: None (both MLPs ELU(1)) or (de_act, ae_act)."""
-    if act is None:
-        return None, None
-    de_act, ae_act = act
-    return de_act, ae_act
+def dae_acts(act):
+    """The public `act=` of a DAE call -- None (both MLPs ELU(1)) or (de_act, ae_act) -- as the tuple of Act | None every call carries
+    inside this package (an ODE call's is `(act,)`)."""
+    return (None, None) if act is None else tuple(act)
+
+
+def call_entry(lib, stem: str, args, acts, wp, wn, stream) -> int:
+    """The one place that picks an entry point of the generic-kernel families: psnode_<stem>_f32 when every act is None (ELU(1)),
+    psnode_<stem>_act_f32 with the acts' psnode_act_f32 otherwise.  stem: "ode_integrate", "dae_integrate", "ode_backward", "dae_backward"."""
+    refs, non_elu = _act_refs(*acts)
+    if not non_elu:
+        return getattr(lib, f"psnode_{stem}_f32")(ctypes.byref(args), wp, wn, stream)
+    return getattr(lib, f"psnode_{stem}_act_f32")(ctypes.byref(args), *refs, wp, wn, stream)
+
+
+def entry_supported(lib, stem: str, args, acts) -> bool:
+    """psnode_<stem>_supported, or psnode_<stem>_act_supported when an act is not None (`call_entry`'s query)."""
+    refs, non_elu = _act_refs(*acts)
+    if not non_elu:
+        return bool(getattr(lib, f"psnode_{stem}_supported")(ctypes.byref(args)))
+    return bool(getattr(lib, f"psnode_{stem}_act_supported")(ctypes.byref(args), *refs))
 
 
 def act_of_module(m) -> Optional[object]:
@@ -183,6 +173,12 @@ def sequential_mlp(seq):
     return _sequential_one_act(seq, act_of_module)
 
 
+def sequential_layers(seq) -> Optional[List[Tuple[torch.Tensor, torch.Tensor]]]:
+    """[(W,b), ...] if `seq` is nn.Sequential(Linear, ELU(alpha=1), Linear, ..., Linear), else None
+    (the only MLP shape the reference's live right-hand sides use, neural_00_ODE_01_no_encode.py:61-64)."""
+    return _elu1_layers(sequential_mlp(seq))
+
+
 def pre_act_of_module(m) -> Optional[object]:
     """`False` if `m` is no activation of the pre-activation family (derivative from the pre-activation u: SiLU, GELU (erf or tanh form),
     Mish), else its Act."""
@@ -210,52 +206,41 @@ def sequential_mlp_any(seq):
     return _sequential_one_act(seq, either)
 
 
+def _rhs_mlp_of(mod, attr: str, in_dim: int, out_dim: int):
+    """(layers, act) of a right-hand-side module whose only parameters are those of its Sequential `attr`, an MLP of `sequential_mlp_any`
+    from in_dim to out_dim; else None."""
+    if not isinstance(mod, nn.Module) or _overrides_forward_hooks(mod):
+        return None
+    r = sequential_mlp_any(getattr(mod, attr, None))
+    if r is None or r[0][0][0].shape[1] != in_dim or r[0][-1][0].shape[0] != out_dim:
+        return None
+    return r if _only_params_of(mod, getattr(mod, attr)) else None
+
+
+def _elu1_layers(r):
+    return r[0] if r is not None and r[1] is None else None
+
+
 def de_mlp_of(x_func, n: int, x_dim: int):
-    """(layers, act) of a DE_Func whose MLP has any activation of `sequential_mlp_any` (act None = ELU(1)), else None."""
-    if not isinstance(x_func, nn.Module) or _overrides_forward_hooks(x_func):
-        return None
-    r = sequential_mlp_any(getattr(x_func, "x_dot", None))
-    if r is None or r[0][0][0].shape[1] != 3 * n or r[0][-1][0].shape[0] != x_dim:
-        return None
-    if not _only_params_of(x_func, x_func.x_dot):
-        return None
-    return r
+    """(layers, act) of a DE_Func (attribute `x_dot`, input recipe cat(a0, s-a0, s)) whose MLP has any activation of
+    `sequential_mlp_any` (act None = ELU(1)), else None."""
+    return _rhs_mlp_of(x_func, "x_dot", 3 * n, x_dim)
 
 
 def ae_mlp_of(i_func, n: int, m: int, i_dim: int):
-    """(layers, act) of an AE_Func whose MLP has any activation of `sequential_mlp_any` (act None = ELU(1)), else None."""
-    if not isinstance(i_func, nn.Module) or _overrides_forward_hooks(i_func):
-        return None
-    r = sequential_mlp_any(getattr(i_func, "i_calculator", None))
-    if r is None or r[0][0][0].shape[1] != n + m or r[0][-1][0].shape[0] != i_dim:
-        return None
-    if not _only_params_of(i_func, i_func.i_calculator):
-        return None
-    return r
+    """(layers, act) of an AE_Func (attribute `i_calculator`, input recipe cat(a0, x, z, v)) whose MLP has any activation of
+    `sequential_mlp_any` (act None = ELU(1)), else None."""
+    return _rhs_mlp_of(i_func, "i_calculator", n + m, i_dim)
 
 
 def de_layers_of(x_func, n: int, x_dim: int):
-    """Layers of a DE_Func (attribute `x_dot`, input recipe cat(a0, s-a0, s))."""
-    if not isinstance(x_func, nn.Module) or _overrides_forward_hooks(x_func):
-        return None
-    layers = sequential_layers(getattr(x_func, "x_dot", None))
-    if layers is None or layers[0][0].shape[1] != 3 * n or layers[-1][0].shape[0] != x_dim:
-        return None
-    if not _only_params_of(x_func, x_func.x_dot):
-        return None
-    return layers
+    """Layers of a DE_Func with ELU(1) hidden layers (`de_mlp_of` with act None), else None."""
+    return _elu1_layers(de_mlp_of(x_func, n, x_dim))
 
 
 def ae_layers_of(i_func, n: int, m: int, i_dim: int):
-    """Layers of an AE_Func (attribute `i_calculator`, input recipe cat(a0, x, z, v))."""
-    if not isinstance(i_func, nn.Module) or _overrides_forward_hooks(i_func):
-        return None
-    layers = sequential_layers(getattr(i_func, "i_calculator", None))
-    if layers is None or layers[0][0].shape[1] != n + m or layers[-1][0].shape[0] != i_dim:
-        return None
-    if not _only_params_of(i_func, i_func.i_calculator):
-        return None
-    return layers
+    """Layers of an AE_Func with ELU(1) hidden layers (`ae_mlp_of` with act None), else None."""
+    return _elu1_layers(ae_mlp_of(i_func, n, m, i_dim))
 
 
 def _mlp_eval(layers, u, act=None):
@@ -392,6 +377,35 @@ def _jump(j: Optional[torch.Tensor], dev, name: str, keep: list):
         j = j.contiguous()
     keep.append(j)
     return j.data_ptr(), j.stride(0), j.stride(1)
+
+
+def _bind_jumps(a, event_idx, jumps, dev, keep: list):
+    """Binds the event table and each jump of `jumps` = (("z_jump", tensor), ...) into the args struct `a` (fields <name>, <zj|vj>_stride_b,
+    <zj|vj>_stride_e); nothing when there is no table."""
+    if event_idx is None:
+        return
+    keep.append(event_idx)
+    a.event_idx = event_idx.data_ptr()
+    for name, j in jumps:
+        ptr, sb, se = _jump(j, dev, name, keep)
+        setattr(a, name, ptr)
+        setattr(a, f"{name[0]}j_stride_b", sb)
+        setattr(a, f"{name[0]}j_stride_e", se)
+
+
+def _bind_events(a, t, event_t, event_idx, check_events: bool, jumps, B: int, dev, keep: list):
+    """Event prologue of the forward entry points: the caller's `event_idx` (int32[T-1], validated) or the table of `event_t`
+    (`event_table`), the jumps' shapes (`jumps` = ((name, tensor, width), ...)) and `_bind_jumps`.  Returns the table, None = no events."""
+    T = t.shape[0]
+    if event_idx is None:
+        event_idx = event_table(t, event_t, check_events)
+    elif event_idx.numel() < T - 1 or event_idx.dtype != torch.int32:
+        raise ValueError(f"event_idx must be int32[T-1={T - 1}], got {event_idx.dtype}[{event_idx.numel()}]")
+    if event_idx is not None:
+        for name, j, width in jumps:
+            _check_jump(name, j, B, width, event_idx)
+        _bind_jumps(a, event_idx, [(name, j) for name, j, _ in jumps], dev, keep)
+    return event_idx
 
 
 def event_table(t: torch.Tensor, event_t: Optional[torch.Tensor], check_duplicates: bool = False) -> Optional[torch.Tensor]:

@@ -6,31 +6,26 @@ import ctypes
 import torch
 
 from .. import _lib
-from ._common import (KERNEL_ID, Layers, METHOD_ID, _act_refs, _dae_acts, _aligned16, _aligned_ptr, _check_saved, _empty, _f32_dev, _jump, _mlp, _pad_rows, _padded_hidden, _split_grads, _view)
+from ._common import (KERNEL_ID, Layers, METHOD_ID, STAGES, _aligned16, _aligned_ptr, _bind_jumps, _check_saved, _empty, _f32_dev, _mlp, _pad_rows, _padded_hidden, _split_grads, _view, call_entry, dae_acts, entry_supported)
 from .latent import latent_backward_wide, latent_wide_shape
 
 def dae_backward_supported(method: str, de_layers: Layers, ae_layers: Layers, x_dim, z_dim, v_dim, i_dim, act=None) -> bool:
     """act: None (both MLPs ELU(1)) or (de_act, ae_act); an activation other than ELU(1) is K5's alone."""
     if de_layers[0][0].device.type != "cuda" or max(len(de_layers), len(ae_layers)) > _lib.MAX_LAYERS:
         return False
-    refs, non_elu = _act_refs(*_dae_acts(act))
-    if non_elu:
-        a = _lib.DaeBwdArgsF32()
-        a.method = METHOD_ID[method]
-        a.x_dim, a.z_dim, a.v_dim, a.i_dim, a.T, a.B = x_dim, z_dim, v_dim, i_dim, 2, 1
-        dev = de_layers[0][0].device
-        a.de, a.ae = _mlp(de_layers, dev, "de", []), _mlp(ae_layers, dev, "ae", [])
-        return bool(_lib.load().psnode_dae_backward_act_supported(ctypes.byref(a), *refs))
-    if latent_wide_shape(de_layers, ae_layers, x_dim, z_dim, v_dim, i_dim):
+    acts = dae_acts(act)
+    non_elu = any(q is not None for q in acts)
+    if not non_elu and latent_wide_shape(de_layers, ae_layers, x_dim, z_dim, v_dim, i_dim):
         return True                          # K3w (saving) + K9w + library GEMMs
-    lib = _lib.load()
     a = _lib.DaeBwdArgsF32()
     a.method = METHOD_ID[method]
     a.x_dim, a.z_dim, a.v_dim, a.i_dim, a.T, a.B = x_dim, z_dim, v_dim, i_dim, 2, 1
     dev = de_layers[0][0].device
     a.de, a.ae = _mlp(de_layers, dev, "de", []), _mlp(ae_layers, dev, "ae", [])
-    if bool(lib.psnode_dae_backward_supported(ctypes.byref(a))):      # K9 / K8 (latent shapes) or K5
+    if entry_supported(_lib.load(), "dae_backward", a, acts):      # K9 / K8 (latent shapes) or K5
         return True
+    if non_elu:
+        return False
     return dae_backward_wide_supported(method, de_layers, ae_layers, x_dim, z_dim, v_dim, i_dim)      # K7f: the DAE_01 class at hidden <= 128
 
 
@@ -66,7 +61,7 @@ def dae_backward_wide(method: str, de_layers: Layers, ae_layers: Layers, t, z, v
     n = xd + ne
     Hr = de_layers[0][0].shape[0]                       # the MLPs' width; H = the width the kernel runs them at (zero-padded rows)
     H = _padded_hidden(Hr)
-    S = {"euler": 1, "midpoint": 2, "rk4": 4}[method]
+    S = STAGES[method]
     if saved is None and B > 16:
         # the recompute form stores the AE head's rows of EVERY grid point (6 x [T,B,H] + [T,B,16] + the u rows of K7h): a very long grid on
         # a full card goes through in batch slices (a saved-activation call is not sliced: its forward already held ~S times as much)
@@ -91,11 +86,8 @@ def dae_backward_wide(method: str, de_layers: Layers, ae_layers: Layers, t, z, v
     a.grad_is = gi_c.data_ptr() if gi_c is not None else None
     f32 = dict(dtype=torch.float32, device=dev)
     n_ev = 0
+    _bind_jumps(a, event_idx, (("z_jump", z_jump), ("v_jump", v_jump)), dev, keep)
     if event_idx is not None:
-        keep.append(event_idx)
-        a.event_idx = event_idx.data_ptr()
-        a.z_jump, a.zj_stride_b, a.zj_stride_e = _jump(z_jump, dev, "z_jump", keep)
-        a.v_jump, a.vj_stride_b, a.vj_stride_e = _jump(v_jump, dev, "v_jump", keep)
         n_ev = (z_jump if z_jump is not None else v_jump).shape[1]
         a.n_events = n_ev
         # rows of the event-time heads: zero-initialised, so that events no step takes contribute nothing
@@ -311,8 +303,8 @@ def dae_backward(method: str, de_layers: Layers, ae_layers: Layers, t, z, v, all
     dev = xs.device
     T, B, xd = xs.shape
     zd, vd, idim = z.shape[-1], v.shape[-1], is_.shape[-1]
-    refs, non_elu = _act_refs(*_dae_acts(act))
-    if non_elu:
+    acts = dae_acts(act)
+    if any(q is not None for q in acts):
         if kernel not in ("auto", "generic") or saved is not None:
             raise _lib.UnsupportedShapeError("dae_backward: an activation other than ELU(alpha=1) runs on the generic backward K5 only "
                                              "(kernel 'auto' / 'generic', no saved rows)")
@@ -342,11 +334,8 @@ def dae_backward(method: str, de_layers: Layers, ae_layers: Layers, t, z, v, all
     a.all_initial, a.xs, a.is_, a.grad_xs = a0.data_ptr(), xs_c.data_ptr(), is_c.data_ptr(), gx_c.data_ptr()
     a.grad_is = gi_c.data_ptr() if gi_c is not None else None
     g = {"z_jump": None, "v_jump": None}
+    _bind_jumps(a, event_idx, (("z_jump", z_jump), ("v_jump", v_jump)), dev, keep)
     if event_idx is not None:
-        keep.append(event_idx)
-        a.event_idx = event_idx.data_ptr()
-        a.z_jump, a.zj_stride_b, a.zj_stride_e = _jump(z_jump, dev, "z_jump", keep)
-        a.v_jump, a.vj_stride_b, a.vj_stride_e = _jump(v_jump, dev, "v_jump", keep)
         n_ev = (z_jump if z_jump is not None else v_jump).shape[1]
         a.n_events = n_ev
         if zd > 0:
@@ -371,7 +360,7 @@ def dae_backward(method: str, de_layers: Layers, ae_layers: Layers, t, z, v, all
         if saved is not None and T >= 2:        # (K9 reads them; the C side refuses them for the kernels that recompute)
             s_act, s_xst, s_ae, s_ev, s_evi = saved
             L = len(de_layers) - 1
-            _check_saved(s_act, s_xst, T, B, xd, {"euler": 1, "midpoint": 2, "rk4": 4}[method], L, dev)
+            _check_saved(s_act, s_xst, T, B, xd, STAGES[method], L, dev)
             if tuple(s_ae.shape[:3]) != (L, T, B) or s_ae.shape[-1] != s_act.shape[-1] or not s_ae.is_contiguous() or s_ae.device != dev:
                 raise ValueError("saved AE activations do not belong to this call (shape / device)")
             keep += [s_act, s_xst, s_ae, s_ev, s_evi]
@@ -384,10 +373,7 @@ def dae_backward(method: str, de_layers: Layers, ae_layers: Layers, t, z, v, all
         nbytes = lib.psnode_dae_backward_workspace_bytes(ctypes.byref(a))
         ws = _empty(nbytes + 256, dtype=torch.uint8, device=dev)
         wp, wn = _aligned_ptr(ws)
-        if not non_elu:
-            rc = lib.psnode_dae_backward_f32(ctypes.byref(a), wp, wn, torch.cuda.current_stream(dev).cuda_stream)
-        else:
-            rc = lib.psnode_dae_backward_act_f32(ctypes.byref(a), *refs, wp, wn, torch.cuda.current_stream(dev).cuda_stream)
+        rc = call_entry(lib, "dae_backward", a, acts, wp, wn, torch.cuda.current_stream(dev).cuda_stream)
     _lib.check(rc, "psnode_dae_backward_f32")
     g["de"], g["ae"] = _split_grads(gde, de_layers), _split_grads(gae, ae_layers)
     return g

@@ -5,7 +5,7 @@ import ctypes
 import torch
 
 from .. import _lib
-from ._common import (KERNEL_ID, Layers, METHOD_ID, _act_refs, _aligned16, _aligned_ptr, _check_saved, _empty, _f32_dev, _jump, _mlp, _split_grads, _view)
+from ._common import (KERNEL_ID, Layers, METHOD_ID, STAGES, _aligned16, _aligned_ptr, _bind_jumps, _check_saved, _empty, _f32_dev, _mlp, _split_grads, _view, call_entry, entry_supported)
 from .latent import latent_backward_wide, latent_wide_shape
 
 def _bwd_args(method, de_layers, x_dim, z_dim, T, B, dev, keep, kernel="auto"):
@@ -22,15 +22,10 @@ def ode_backward_supported(method: str, de_layers: Layers, x_dim: int, z_dim: in
     activations and parameter gradients fit the LDS (generic backward).  act (fused.Act) other than None = ELU(1): K5 only."""
     if de_layers[0][0].device.type != "cuda" or len(de_layers) > _lib.MAX_LAYERS:
         return False
-    if act is not None:
-        a = _bwd_args(method, de_layers, x_dim, z_dim, 2, 1, de_layers[0][0].device, [], kernel)
-        refs, _ = _act_refs(act)
-        return bool(_lib.load().psnode_ode_backward_act_supported(ctypes.byref(a), *refs))
-    if kernel in ("auto", "mfma") and latent_wide_shape(de_layers, None, x_dim, z_dim):
+    if act is None and kernel in ("auto", "mfma") and latent_wide_shape(de_layers, None, x_dim, z_dim):
         return True                          # K3w (saving) + K9w + library GEMMs
-    lib = _lib.load()
     a = _bwd_args(method, de_layers, x_dim, z_dim, 2, 1, de_layers[0][0].device, [], kernel)
-    return bool(lib.psnode_ode_backward_supported(ctypes.byref(a)))
+    return entry_supported(_lib.load(), "ode_backward", a, (act,))
 
 
 def ode_backward(method: str, de_layers: Layers, t, z, all_initial, xs, grad_xs, event_idx=None, z_jump=None, need_grad_z: bool = True,
@@ -72,10 +67,8 @@ def ode_backward(method: str, de_layers: Layers, t, z, all_initial, xs, grad_xs,
     keep += [a0, xs_c, g_c]
     a.all_initial, a.xs, a.grad_xs = a0.data_ptr(), xs_c.data_ptr(), g_c.data_ptr()
     gzj = None
+    _bind_jumps(a, event_idx, (("z_jump", z_jump),), dev, keep)
     if event_idx is not None:
-        keep.append(event_idx)
-        a.event_idx = event_idx.data_ptr()
-        a.z_jump, a.zj_stride_b, a.zj_stride_e = _jump(z_jump, dev, "z_jump", keep)
         if z_jump is not None and zd > 0:
             a.n_events = z_jump.shape[1]
         if z_jump is not None and zd > 0 and need_grad_zj:
@@ -90,16 +83,12 @@ def ode_backward(method: str, de_layers: Layers, t, z, all_initial, xs, grad_xs,
         a.grad_x0, a.grad_all_initial, a.grad_params = gx0.data_ptr(), ga0.data_ptr(), gpar.data_ptr()
         a.grad_z = gz.data_ptr() if gz is not None else None
         if saved is not None and T >= 2:
-            _check_saved(saved[0], saved[1], T, B, xd, {"euler": 1, "midpoint": 2, "rk4": 4}[method], len(de_layers) - 1, dev)
+            _check_saved(saved[0], saved[1], T, B, xd, STAGES[method], len(de_layers) - 1, dev)
             keep += [saved[0], saved[1]]
             a.saved_act, a.saved_xstage = saved[0].data_ptr(), saved[1].data_ptr()
         nbytes = lib.psnode_ode_backward_workspace_bytes(ctypes.byref(a))
         ws = _empty(nbytes + 256, dtype=torch.uint8, device=dev)
         wp, wn = _aligned_ptr(ws)
-        if act is None:
-            rc = lib.psnode_ode_backward_f32(ctypes.byref(a), wp, wn, torch.cuda.current_stream(dev).cuda_stream)
-        else:
-            refs, _ = _act_refs(act)
-            rc = lib.psnode_ode_backward_act_f32(ctypes.byref(a), *refs, wp, wn, torch.cuda.current_stream(dev).cuda_stream)
+        rc = call_entry(lib, "ode_backward", a, (act,), wp, wn, torch.cuda.current_stream(dev).cuda_stream)
     _lib.check(rc, "psnode_ode_backward_f32")
     return gx0, gz, gzj, ga0, _split_grads(gpar, de_layers)

@@ -6,7 +6,7 @@ from typing import Optional
 import torch
 
 from .. import _lib
-from ._common import (KERNEL_ID, Layers, METHOD_ID, _act_refs, _dae_acts, _aligned16, _aligned_ptr, _check_jump, _check_tb, _empty, _f32_dev, _jump, _mlp, _view, _workspace, event_table)
+from ._common import (KERNEL_ID, Layers, METHOD_ID, STAGES, _aligned16, _aligned_ptr, _bind_events, _check_tb, _empty, _f32_dev, _mlp, _view, _workspace, call_entry, dae_acts)
 
 _MFMA_CLASSES = ("MFMA integrators K1 / K2 cover `in -> H -> H -> H -> out` ELU-MLPs with H <= 128 (any x_dim <= 16 for the ODE, "
                  "x_dim <= 8 and z+v+i <= 8 for the DAE), and -- weights streamed from L2 -- the ODE up to H = 192 at any x_dim <= 16 and "
@@ -76,8 +76,6 @@ def ode_integrate(method: str, de_layers: Layers, t, x, z, all_initial, event_t=
     zd = z.shape[-1]
     _check_tb("t", t, T, B)
     _check_tb("z", z, T, B)
-    if event_idx is not None and (event_idx.numel() < T - 1 or event_idx.dtype != torch.int32):
-        raise ValueError(f"event_idx must be int32[T-1={T - 1}], got {event_idx.dtype}[{event_idx.numel()}]")
     keep: list = []
     a = _lib.OdeArgsF32()
     a.method = METHOD_ID[method]
@@ -96,13 +94,7 @@ def ode_integrate(method: str, de_layers: Layers, t, x, z, all_initial, event_t=
     keep.append(a0)
     a.all_initial = a0.data_ptr()
     with torch.cuda.device(dev):
-        if event_idx is None:
-            event_idx = event_table(t, event_t, check_events)
-        if event_idx is not None:
-            _check_jump("z_jump", z_jump, B, zd, event_idx)
-            keep.append(event_idx)
-            a.event_idx = event_idx.data_ptr()
-            a.z_jump, a.zj_stride_b, a.zj_stride_e = _jump(z_jump, dev, "z_jump", keep)
+        _bind_events(a, t, event_t, event_idx, check_events, (("z_jump", z_jump, zd),), B, dev, keep)
         if out is None:
             out = _empty((T, B, xd), dtype=torch.float32, device=dev)
         elif out.shape != (T, B, xd) or not out.is_contiguous() or out.dtype != torch.float32 or out.device != dev:
@@ -113,7 +105,7 @@ def ode_integrate(method: str, de_layers: Layers, t, x, z, all_initial, event_t=
             Hp = lib.psnode_ode_save_hidden(ctypes.byref(a))
             if Hp <= 0:
                 raise _lib.UnsupportedShapeError("ode_integrate(save=True): the MFMA integrator K1 does not take this shape")
-            S = {"euler": 1, "midpoint": 2, "rk4": 4}[method]
+            S = STAGES[method]
             L = len(de_layers) - 1       # hidden layers: 3 for the no_encode MLPs (K1), 1 for the latent ones at hidden 64 (K3c)
             saved = (_empty((max(T - 1, 0), S, L, B, Hp), dtype=torch.float32, device=dev),
                      _empty((max(T - 1, 0), S, B, xd), dtype=torch.float32, device=dev))
@@ -121,11 +113,7 @@ def ode_integrate(method: str, de_layers: Layers, t, x, z, all_initial, event_t=
                 a.save_act, a.save_xstage = saved[0].data_ptr(), saved[1].data_ptr()
         ws = _workspace(lib, a.de, None, dev)
         wp, wn = _aligned_ptr(ws)
-        if act is None:
-            rc = lib.psnode_ode_integrate_f32(ctypes.byref(a), wp, wn, torch.cuda.current_stream(dev).cuda_stream)
-        else:
-            refs, _ = _act_refs(act)
-            rc = lib.psnode_ode_integrate_act_f32(ctypes.byref(a), *refs, wp, wn, torch.cuda.current_stream(dev).cuda_stream)
+        rc = call_entry(lib, "ode_integrate", a, (act,), wp, wn, torch.cuda.current_stream(dev).cuda_stream)
     _mfma_miss(rc, kernel, "psnode_ode_integrate_f32", de_layers)
     _lib.check(rc, "psnode_ode_integrate_f32")
     if kernel == "auto" and act is None:
@@ -160,7 +148,8 @@ def dae_integrate(method: str, de_layers: Layers, ae_layers: Layers, x_init, t, 
     dev = x_init.device
     if dev.type != "cuda":
         raise ValueError("fused integrator needs tensors on a HIP device")
-    refs, non_elu = _act_refs(*_dae_acts(act))
+    acts = dae_acts(act)
+    non_elu = any(q is not None for q in acts)
     _act_route_ok("dae_integrate", non_elu, kernel, save)
     T, B = t.shape[0], t.shape[1]
     xd, zd, vd, idim = x_init.shape[-1], z.shape[-1], v.shape[-1], i.shape[-1]
@@ -173,8 +162,6 @@ def dae_integrate(method: str, de_layers: Layers, ae_layers: Layers, x_init, t, 
         _check_tb("x", x, T, B)
     if input_true_i:
         _check_tb("i", i, T, B)
-    if event_idx is not None and (event_idx.numel() < T - 1 or event_idx.dtype != torch.int32):
-        raise ValueError(f"event_idx must be int32[T-1={T - 1}], got {event_idx.dtype}[{event_idx.numel()}]")
     keep: list = []
     a = _lib.DaeArgsF32()
     a.method = METHOD_ID[method]
@@ -199,15 +186,7 @@ def dae_integrate(method: str, de_layers: Layers, ae_layers: Layers, x_init, t, 
     keep += [xi, a0]
     a.x_init, a.all_initial = xi.data_ptr(), a0.data_ptr()
     with torch.cuda.device(dev):
-        if event_idx is None:
-            event_idx = event_table(t, event_t, check_events)
-        if event_idx is not None:
-            _check_jump("z_jump", z_jump, B, zd, event_idx)
-            _check_jump("v_jump", v_jump, B, vd, event_idx)
-            keep.append(event_idx)
-            a.event_idx = event_idx.data_ptr()
-            a.z_jump, a.zj_stride_b, a.zj_stride_e = _jump(z_jump, dev, "z_jump", keep)
-            a.v_jump, a.vj_stride_b, a.vj_stride_e = _jump(v_jump, dev, "v_jump", keep)
+        event_idx = _bind_events(a, t, event_t, event_idx, check_events, (("z_jump", z_jump, zd), ("v_jump", v_jump, vd)), B, dev, keep)
         if out is None:
             xs = _empty((T, B, xd), dtype=torch.float32, device=dev)
             is_ = _empty((T, B, idim), dtype=torch.float32, device=dev)
@@ -221,7 +200,7 @@ def dae_integrate(method: str, de_layers: Layers, ae_layers: Layers, x_init, t, 
             Hp = lib.psnode_dae_save_hidden(ctypes.byref(a))
             if Hp <= 0:
                 raise _lib.UnsupportedShapeError("dae_integrate(save=True): the MFMA integrator K2 does not take this shape")
-            S = {"euler": 1, "midpoint": 2, "rk4": 4}[method]
+            S = STAGES[method]
             f32 = dict(dtype=torch.float32, device=dev)
             n_ev = (z_jump if z_jump is not None else v_jump).shape[1] if event_idx is not None else 0
             L = len(de_layers) - 1       # hidden layers: 3 (K2), 1 for the latent shapes at hidden 64 (K3c; i0 rows are then i_dim wide)
@@ -238,10 +217,7 @@ def dae_integrate(method: str, de_layers: Layers, ae_layers: Layers, x_init, t, 
                 a.save_ev_act, a.save_ev_i = saved[3].data_ptr(), saved[4].data_ptr()
         ws = _workspace(lib, a.de, a.ae, dev)
         wp, wn = _aligned_ptr(ws)
-        if not non_elu:
-            rc = lib.psnode_dae_integrate_f32(ctypes.byref(a), wp, wn, torch.cuda.current_stream(dev).cuda_stream)
-        else:
-            rc = lib.psnode_dae_integrate_act_f32(ctypes.byref(a), *refs, wp, wn, torch.cuda.current_stream(dev).cuda_stream)
+        rc = call_entry(lib, "dae_integrate", a, acts, wp, wn, torch.cuda.current_stream(dev).cuda_stream)
     _mfma_miss(rc, kernel, "psnode_dae_integrate_f32", de_layers)
     _lib.check(rc, "psnode_dae_integrate_f32")
     if kernel == "auto" and not non_elu:

@@ -3,7 +3,7 @@ layers / event tensors."""
 
 import torch
 
-from ._common import _recipe_ok, ae_layers_of, ae_mlp_of, de_layers_of, de_mlp_of
+from ._common import _recipe_ok, ae_mlp_of, de_mlp_of
 
 # ----------------------------------------------------------------------------- planning for the solver classes
 def _event_tensors(event_fn, jump_change_fn, want_v: bool):
@@ -43,9 +43,7 @@ def plan_ode(x_func, x, z, all_initial, event_fn, jump_change_fn, t=None, x_init
     xd, zd = x.shape[-1], z.shape[-1]
     if all_initial.dim() != 2 or all_initial.shape[-1] != xd + zd:
         return None
-    layers, act = de_layers_of(x_func, xd + zd, xd), None
-    if layers is None:
-        layers, act = de_mlp_of(x_func, xd + zd, xd) or (None, None)
+    layers, act = de_mlp_of(x_func, xd + zd, xd) or (None, None)
     if layers is None or not _recipe_ok(x_func, layers, "de_ode", (xd, zd), act):
         return None
     ok, event_t, z_jump, _ = _event_tensors(event_fn, jump_change_fn, False)
@@ -64,11 +62,8 @@ def plan_dae(x_init, x_func, i_func, z, v, i, all_initial, event_fn, jump_change
     n = xd + zd + vd + idim
     if all_initial.dim() != 2 or all_initial.shape[-1] != n:
         return None
-    de, ae, de_act, ae_act = de_layers_of(x_func, n, xd), ae_layers_of(i_func, n, xd + zd + vd, idim), None, None
-    if de is None:
-        de, de_act = de_mlp_of(x_func, n, xd) or (None, None)
-    if ae is None:
-        ae, ae_act = ae_mlp_of(i_func, n, xd + zd + vd, idim) or (None, None)
+    de, de_act = de_mlp_of(x_func, n, xd) or (None, None)
+    ae, ae_act = ae_mlp_of(i_func, n, xd + zd + vd, idim) or (None, None)
     if de is None or ae is None:
         return None
     if not _recipe_ok(x_func, de, "de_dae", (xd, zd, vd, idim), de_act) or not _recipe_ok(i_func, ae, "ae", (xd, zd, vd, n), ae_act):

@@ -282,14 +282,14 @@ def test_teacher_forced_training_with_non_elu_walks():
 
 def test_null_act_is_the_elu1_entry_point(monkeypatch):
     """psnode_ode_integrate_act_f32 with a NULL act: bitwise the output of psnode_ode_integrate_f32 at kernel = GENERIC."""
-    from py_psnode_amd.fused import forward
+    from py_psnode_amd.fused import _common
     de, t, x, z, ev, zj = _ode_case("tanh", 8, 2, (64, 64, 64), 40, 20, seed=8, events=True)
     de = models.DE_Func(10, (64, 64, 64), 8).cuda()
     layers = [(m.weight.detach(), m.bias.detach()) for m in de.x_dot if isinstance(m, nn.Linear)]
     c = lambda a: a.cuda()
     a0 = torch.cat((x[0], z[0]), -1).cuda()
     ref = fused.ode_integrate("rk4", layers, c(t), c(x), c(z), a0, event_t=c(ev), z_jump=c(zj), kernel="generic")
-    monkeypatch.setattr(forward, "_act_refs", lambda *a: ([None], True))
+    monkeypatch.setattr(_common, "_act_refs", lambda *a: ([None], True))
     got = fused.ode_integrate("rk4", layers, c(t), c(x), c(z), a0, event_t=c(ev), z_jump=c(zj), kernel="generic", act=object())
     elu1 = fused.Act(fused._lib.ACT_ELU, alpha=1.0)
     monkeypatch.undo()
