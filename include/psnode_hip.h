@@ -286,7 +286,7 @@ int32_t psnode_recon_rows_backward_f32(const psnode_mlp_f32* encoder, const psno
  * [W1 (64 x 3n), b1, W2, b2, W3, b3, W4 (x_dim x 64), b4] (psnode_ode_backward_param_count floats).
  * Kernels: MFMA backwards for the shape classes 3n -> h -> h -> h -> x_dim (h <= 128, x_dim <= 8, z_dim <= 8; K4x / K4f) and the latent
  * 6H -> H -> H with x_dim = z_dim = H in {16, 64} (16-byte aligned rows); the generic backward for any MLP whose activations
- * fit the 160 KB LDS (its parameter-gradient accumulators move to the workspace when they do not).  No teacher forcing;
+ * fit the 160 KB LDS (its parameter-gradient accumulators move to the workspace when they do not).  Teacher forcing: `flags`;
  * t carries no gradient.  Deterministic (per-workgroup partials summed in a fixed order). */
 typedef struct {
     int32_t method;
@@ -313,7 +313,8 @@ typedef struct {
     uint32_t flags;                  /* ABI 5: PSNODE_FLAG_INPUT_TRUE_X = backward of a teacher-forced call (my_solvers.py:72-74: every step starts
                                         from the dataset row x[k]): `xs` then holds the DATASET x [T,B,x_dim] contiguous (the forward result is not
                                         needed), no adjoint is carried from step to step, grad_x0 = dL/dxs[0] + the start adjoint of step 0.
-                                        K4f only (hidden <= 128, x_dim <= 8, recompute form: saved_* must be NULL) */
+                                        Recompute form only (saved_* must be NULL): K4f where kernel != GENERIC and the shape is its (hidden
+                                        <= 128, x_dim <= 8), else the generic backward K5 (kernel AUTO / GENERIC; _MFMA_WAVE is refused) */
 } psnode_ode_bwd_args_f32;
 
 int32_t psnode_ode_backward_supported(const psnode_ode_bwd_args_f32* args);
@@ -321,7 +322,7 @@ int64_t psnode_ode_backward_param_count(const psnode_ode_bwd_args_f32* args);
 size_t psnode_ode_backward_workspace_bytes(const psnode_ode_bwd_args_f32* args);
 int32_t psnode_ode_backward_f32(const psnode_ode_bwd_args_f32* args, void* workspace, size_t workspace_bytes, void* stream);
 
-/* Backward pass through psnode_dae_integrate_f32 (no teacher forcing): loss.backward() through integrate_DAE
+/* Backward pass through psnode_dae_integrate_f32 (no teacher forcing; psnode_dae_backward_tf_f32 below has it): loss.backward() through integrate_DAE
  * (neural_01_DAE_01_no_encode.py:422-424 over my_solvers.py:94-129), including the AE head, the feedback of the
  * algebraic variable into the DE input and the event-time recomputation i0 = g(x0; jumps).
  * grad_params_de / grad_params_ae: flat nn.Linear-order vectors (psnode_dae_backward_param_counts). */
@@ -363,6 +364,27 @@ typedef struct {
 int32_t psnode_dae_backward_supported(const psnode_dae_bwd_args_f32* args);
 size_t psnode_dae_backward_workspace_bytes(const psnode_dae_bwd_args_f32* args);
 int32_t psnode_dae_backward_f32(const psnode_dae_bwd_args_f32* args, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Backward of a teacher-forced integrate_DAE (my_solvers.py:111-121) on the generic backward K5 -- every shape K5 takes untied, it takes
+ * teacher-forced (additive in ABI 10: psnode_dae_bwd_args_f32 is unchanged).  flags / x_true / i_true mean what they mean in
+ * psnode_dae_bwd_wide_args_f32 below (K7f):
+ *   PSNODE_FLAG_INPUT_TRUE_X: the DE of step k starts from x_true[k]; the head at grid point j (i_0 included) reads x_true[j] and its
+ *     x-adjoint is dropped; the recomputed head of an event step still reads the running state base.xs[k] -- the only route by which an
+ *     adjoint still travels from step to step through x.
+ *   PSNODE_FLAG_INPUT_TRUE_I: the DE reads i_true[k], also on event steps; its algebraic adjoint is dropped (the adjoint of is[k] is
+ *     grad_is[k] alone) and the event-time head, which then feeds nothing, is neither recomputed nor differentiated.
+ * x_true [T,B,x_dim] / i_true [T,B,i_dim]: contiguous dataset rows, required for the flag set; no gradient is formed for them.
+ * flags == 0 forwards to psnode_dae_backward_f32.  With flags: base.kernel AUTO or GENERIC, base.saved_* NULL, T >= 2. */
+typedef struct {
+    psnode_dae_bwd_args_f32 base;
+    uint32_t flags;                  /* PSNODE_FLAG_INPUT_TRUE_X | PSNODE_FLAG_INPUT_TRUE_I */
+    const float* x_true;
+    const float* i_true;
+} psnode_dae_bwd_tf_args_f32;
+
+int32_t psnode_dae_backward_tf_supported(const psnode_dae_bwd_tf_args_f32* args);   /* dims only */
+size_t psnode_dae_backward_tf_workspace_bytes(const psnode_dae_bwd_tf_args_f32* args);
+int32_t psnode_dae_backward_tf_f32(const psnode_dae_bwd_tf_args_f32* args, void* workspace, size_t workspace_bytes, void* stream);
 
 /* The DAE backward at hidden <= 128 (K7f, csrc/psnode_dae_backward_fused.hip): loss.backward() through integrate_DAE
  * (my_solvers.py:94-129) in ONE launch over the whole grid -- per grid point the AE head's adjoint (its output adjoint = dL/dis of that

@@ -29,7 +29,8 @@ ABI_VERSION = 10         # == PSNODE_ABI_VERSION of include/psnode_hip.h (2: rou
                          # 10: psnode_gemm_tn_* / psnode_linear_rows_*: the contraction over rows (K10) and the row-linear layer (K11) that replace library GEMMs; the `kernel` field of
                          #     psnode_ode_bwd_args_f32 selects K4x (_MFMA_WAVE) / K4f (_MFMA_TILE, _MFMA_WIDE);
                          #     additive, same version: psnode_act_f32 and the psnode_{ode,dae}_{integrate,backward}_act_* entry points --
-                         #     hidden-layer activations other than ELU(1) on the generic kernels K0 / K5)
+                         #     hidden-layer activations other than ELU(1) on the generic kernels K0 / K5;
+                         #     additive, same version: psnode_dae_bwd_tf_args_f32 and psnode_dae_backward_tf_* -- the teacher-forced DAE backward on K5)
 LIB_NAME = "libpsnode_hip.so"
 # PSNODE_LIB_PATH lets kernel experiments (profiles/scripts/*) load an alternative build of the same ABI
 LIB_PATH = os.environ.get("PSNODE_LIB_PATH") or os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
@@ -55,6 +56,7 @@ EXPORTS = (
     "psnode_linear_rows_supported", "psnode_linear_rows_f32",
     "psnode_ode_integrate_act_supported", "psnode_ode_integrate_act_f32", "psnode_dae_integrate_act_supported", "psnode_dae_integrate_act_f32",
     "psnode_ode_backward_act_supported", "psnode_ode_backward_act_f32", "psnode_dae_backward_act_supported", "psnode_dae_backward_act_f32",
+    "psnode_dae_backward_tf_supported", "psnode_dae_backward_tf_workspace_bytes", "psnode_dae_backward_tf_f32",
 )
 
 
@@ -129,6 +131,11 @@ class DaeBwdArgsF32(ctypes.Structure):
                 ("grad_v_jump", c_void_p), ("grad_all_initial", c_void_p), ("grad_params_de", c_void_p), ("grad_params_ae", c_void_p),
                 ("saved_act", c_void_p), ("saved_xstage", c_void_p), ("saved_ae_act", c_void_p), ("saved_ev_act", c_void_p),
                 ("saved_ev_i", c_void_p)]
+
+
+class DaeBwdTfArgsF32(ctypes.Structure):
+    """psnode_dae_bwd_tf_args_f32: a DAE backward call + the teacher-forcing flags and dataset rows (K5)."""
+    _fields_ = [("base", DaeBwdArgsF32), ("flags", c_uint32), ("x_true", c_void_p), ("i_true", c_void_p)]
 
 
 class OdeEncodedArgsF32(ctypes.Structure):
@@ -272,6 +279,13 @@ def load():
     lib.psnode_dae_backward_workspace_bytes.argtypes = [ctypes.POINTER(DaeBwdArgsF32)]
     lib.psnode_dae_backward_f32.restype = c_int32
     lib.psnode_dae_backward_f32.argtypes = [ctypes.POINTER(DaeBwdArgsF32), c_void_p, c_size_t, c_void_p]
+    if hasattr(lib, "psnode_dae_backward_tf_f32"):
+        lib.psnode_dae_backward_tf_supported.restype = c_int32
+        lib.psnode_dae_backward_tf_supported.argtypes = [ctypes.POINTER(DaeBwdTfArgsF32)]
+        lib.psnode_dae_backward_tf_workspace_bytes.restype = c_size_t
+        lib.psnode_dae_backward_tf_workspace_bytes.argtypes = [ctypes.POINTER(DaeBwdTfArgsF32)]
+        lib.psnode_dae_backward_tf_f32.restype = c_int32
+        lib.psnode_dae_backward_tf_f32.argtypes = [ctypes.POINTER(DaeBwdTfArgsF32), c_void_p, c_size_t, c_void_p]
     act_p = ctypes.POINTER(ActF32)
     for name, args_t, n_act in (("ode_integrate", OdeArgsF32, 1), ("dae_integrate", DaeArgsF32, 2), ("ode_backward", OdeBwdArgsF32, 1),
                                 ("dae_backward", DaeBwdArgsF32, 2)):

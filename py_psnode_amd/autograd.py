@@ -36,9 +36,16 @@ def latent_wide_training_fits(method, de, ae, hidden, T, B, dev) -> bool:
     return need <= free // 2
 
 
-def ode_training_supported(method, layers, x_dim, z_dim, T, B, kernel="auto", act=None) -> bool:
+def ode_training_supported(method, layers, x_dim, z_dim, T, B, kernel="auto", act=None, input_true_x=False) -> bool:
     """What the solver asks before it routes a call that needs autograd to the fused forward + backward pair.  act (fused.Act; None =
-    ELU(1)): an activation other than ELU(1) trains on K0 + K5 alone, so K5 answers."""
+    ELU(1)): an activation other than ELU(1) trains on K0 + K5 alone, so K5 answers.  input_true_x: teacher-forced training -- K4f's
+    recompute form on kernel "auto" / "mfma" where the shape is its, else K5 on "auto" / "generic"; ELU(1) only."""
+    if input_true_x:
+        if act is not None:
+            return False
+        if kernel in ("auto", "mfma") and fused.ode_backward_supported(method, layers, x_dim, z_dim, "wide"):
+            return True
+        return kernel in ("auto", "generic") and fused.ode_backward_supported(method, layers, x_dim, z_dim, "generic")
     if act is not None:
         return fused.ode_backward_supported(method, layers, x_dim, z_dim, kernel, act=act)
     if kernel in ("auto", "mfma") and fused.latent_wide_shape(layers, None, x_dim, z_dim):
@@ -46,8 +53,21 @@ def ode_training_supported(method, layers, x_dim, z_dim, T, B, kernel="auto", ac
     return fused.ode_backward_supported(method, layers, x_dim, z_dim, kernel)
 
 
-def dae_training_supported(method, de, ae, x_dim, z_dim, v_dim, i_dim, T, B, act=None) -> bool:
-    """act: None (both MLPs ELU(1)) or (de_act, ae_act); an activation other than ELU(1) trains on K0 + K5 alone, so K5 answers."""
+def _dae_tf_on_k7f(method, kernel, de, ae, x_dim, z_dim, v_dim, i_dim) -> bool:
+    return kernel in ("auto", "mfma") and fused.dae_backward_wide_supported(method, de, ae, x_dim, z_dim, v_dim, i_dim)
+
+
+def dae_training_supported(method, de, ae, x_dim, z_dim, v_dim, i_dim, T, B, act=None, kernel="auto", input_true_x=False,
+                           input_true_i=False) -> bool:
+    """act: None (both MLPs ELU(1)) or (de_act, ae_act); an activation other than ELU(1) trains on K0 + K5 alone, so K5 answers.
+    input_true_x / input_true_i: teacher-forced training (T >= 2, ELU(1) only) -- K7f's recompute form on kernel "auto" / "mfma" where the
+    shape is its, else K5 on "auto" / "generic"."""
+    if input_true_x or input_true_i:
+        if T < 2 or (act is not None and any(a is not None for a in act)):
+            return False
+        if _dae_tf_on_k7f(method, kernel, de, ae, x_dim, z_dim, v_dim, i_dim):
+            return True
+        return kernel in ("auto", "generic") and fused.dae_backward_supported(method, de, ae, x_dim, z_dim, v_dim, i_dim, kernel="generic")
     if act is not None and any(a is not None for a in act):
         return fused.dae_backward_supported(method, de, ae, x_dim, z_dim, v_dim, i_dim, act=act)
     if fused.latent_wide_shape(de, ae, x_dim, z_dim, v_dim, i_dim):
@@ -118,13 +138,14 @@ class _FusedOde(torch.autograd.Function):
             ctx.method, ctx.bwd_kernel, ctx.has_jump, ctx.has_saved, ctx.event_idx = method, "auto", z_jump is not None, False, event_idx
             ctx.save_for_backward(t, z, all_initial, xs, *((z_jump,) if z_jump is not None else ()), *params)
             return xs
-        if x0.dim() == 3:        # teacher forcing (my_solvers.py:72-74): x0 is the whole dataset x [T,B,xd]; nothing is saved, K4f recomputes
+        if x0.dim() == 3:        # teacher forcing (my_solvers.py:72-74): x0 is the whole dataset x [T,B,xd]; nothing is saved, K4f / K5 recompute
             x_true = x0.detach().contiguous()
             xs = fused.ode_integrate(method, layers, t, x_true, z, all_initial, z_jump=z_jump, event_idx=event_idx, kernel=kernel,
                                      input_true_x=True)
             last_saved_bytes = 0
             ctx.x_true = True
             ctx.method, ctx.has_jump, ctx.has_saved, ctx.event_idx = method, z_jump is not None, False, event_idx
+            ctx.bwd_kernel = kernel      # "auto" / "mfma": K4f where the shape is its, "auto" else and "generic": K5
             # (the dataset rows go through save_for_backward like everything else the backward reads: autograd's version counter then
             #  catches an in-place edit of x between forward and backward)
             ctx.save_for_backward(t, z, all_initial, xs, *((z_jump,) if z_jump is not None else ()), x_true, *params)
@@ -166,9 +187,9 @@ class _FusedOde(torch.autograd.Function):
         params = saved[pos:]
         layers = [(params[k], params[k + 1]) for k in range(0, len(params), 2)]
         need_z = ctx.needs_input_grad[6]
-        if x_true is not None:   # teacher forcing: every step started from a dataset row -- K4f with the dataset as `xs`, no carried adjoint
+        if x_true is not None:   # teacher forcing: every step started from a dataset row -- K4f / K5 with the dataset as `xs`, no carried adjoint
             gx0, gz, gzj, ga0, gpar = fused.ode_backward(ctx.method, layers, t, z, a0, x_true, grad_xs, event_idx=ctx.event_idx,
-                                                         z_jump=z_jump, need_grad_z=need_z, kernel="wide", input_true_x=True)
+                                                         z_jump=z_jump, need_grad_z=need_z, kernel=ctx.bwd_kernel, input_true_x=True)
             if gz is None and need_z:
                 gz = torch.zeros_like(z)
             return (None, None, None, None, None, None, gz, ga0, gzj if ctx.needs_input_grad[8] else None, *gpar)   # (no gradient for the dataset x)
@@ -246,8 +267,9 @@ class _FusedDae(torch.autograd.Function):
 
 
 class _FusedDaeTeacherForced(torch.autograd.Function):
-    """integrate_DAE with input_true_x and / or input_true_i (my_solvers.py:111-121): forward K2 with the flags (nothing saved), backward
-    K7f in its recompute form with the dataset rows (psnode_dae_bwd_wide_args_f32::x_true / i_true).  The dataset rows get no gradient."""
+    """integrate_DAE with input_true_x and / or input_true_i (my_solvers.py:111-121): forward K2 / K0 with the flags (nothing saved),
+    backward with the dataset rows on K7f in its recompute form (psnode_dae_bwd_wide_args_f32::x_true / i_true) where the shape is its and
+    the kernel "auto" / "mfma", else on K5 (psnode_dae_bwd_tf_args_f32).  The dataset rows get no gradient."""
 
     @staticmethod
     def forward(ctx, method, kernel, event_idx, n_de, tx, ti, t, x_init, x, z, v, i, all_initial, z_jump, v_jump, *params):
@@ -256,6 +278,8 @@ class _FusedDaeTeacherForced(torch.autograd.Function):
         xs, is_ = fused.dae_integrate(method, de, ae, x_init, t, x, z, v, i, all_initial, z_jump=z_jump, v_jump=v_jump, event_idx=event_idx,
                                       kernel=kernel, input_true_x=tx, input_true_i=ti)[:2]
         ctx.method, ctx.n_de, ctx.event_idx, ctx.tx, ctx.ti = method, n_de, event_idx, tx, ti
+        ctx.k7f = _dae_tf_on_k7f(method, kernel, de, ae, x_init.shape[-1], z.shape[-1], v.shape[-1], i.shape[-1])
+        ctx.kernel = kernel
         ctx.has_zj, ctx.has_vj = z_jump is not None, v_jump is not None
         ctx.save_for_backward(t, z, v, all_initial, xs, is_, x, i, *((z_jump,) if z_jump is not None else ()),
                               *((v_jump,) if v_jump is not None else ()), *params)
@@ -273,8 +297,13 @@ class _FusedDaeTeacherForced(torch.autograd.Function):
         params = sv[k:]
         de = [(params[q], params[q + 1]) for q in range(0, 2 * ctx.n_de, 2)]
         ae = [(params[q], params[q + 1]) for q in range(2 * ctx.n_de, len(params), 2)]
-        g = fused.dae_backward_wide(ctx.method, de, ae, t, z, v, a0, xs, is_, grad_xs, grad_is, event_idx=ctx.event_idx, z_jump=z_jump,
-                                    v_jump=v_jump, x_true=x if ctx.tx else None, i_true=i if ctx.ti else None)
+        rows = dict(x_true=x if ctx.tx else None, i_true=i if ctx.ti else None)
+        if ctx.k7f:
+            g = fused.dae_backward_wide(ctx.method, de, ae, t, z, v, a0, xs, is_, grad_xs, grad_is, event_idx=ctx.event_idx, z_jump=z_jump,
+                                        v_jump=v_jump, **rows)
+        else:
+            g = fused.dae_backward_tf(ctx.method, de, ae, t, z, v, a0, xs, is_, grad_xs, grad_is, event_idx=ctx.event_idx, z_jump=z_jump,
+                                      v_jump=v_jump, kernel=ctx.kernel, **rows)
         gz = g["z"] if g["z"] is not None else (torch.zeros_like(z) if ctx.needs_input_grad[9] else None)
         gv = g["v"] if g["v"] is not None else (torch.zeros_like(v) if ctx.needs_input_grad[10] else None)
         return (None, None, None, None, None, None, None, g["x_init"], None, gz, gv, None, g["all_initial"],

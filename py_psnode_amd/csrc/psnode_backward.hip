@@ -4,7 +4,7 @@
 //   K4f (psnode_backward_fused.hip)      ODE, in -> H -> H -> H -> x at hidden <= 128: one launch, saved-activation and recompute forms
 //   K8f / K9 (psnode_latent_dpp.hip / psnode_latent64_bwd*.hip)   the latent integrators of the direct_encode models at hidden 16 / 64
 //   K8 (psnode_latent_bwd.hip)           the latent DAE at hidden 16
-//   K5 (psnode_generic_bwd.hip)          anything else that fits the LDS
+//   K5 (psnode_generic_bwd.hip)          anything else that fits the LDS, with or without teacher forcing
 // (the DAE's no_encode shapes go through psnode_dae_backward_wide_f32 -> K7f, psnode_dae_backward_fused.hip).
 // Rounds 1-4 also carried K4 / K7, hidden-64 specialisations of the recompute form; K4f / K7f cover their shapes (round 5:
 // profiles/scripts/variants/ keeps the sources).
@@ -72,7 +72,7 @@ GenericBwdCall generic_bwd_call(const psnode_ode_bwd_args_f32& a) {
     c.method = a.method; c.xd = a.x_dim; c.zd = a.z_dim; c.T = a.T; c.B = a.B; c.de = &a.de;
     c.t = view(a.t); c.z = view(a.z); c.a0 = a.all_initial;
     c.ev = a.event_idx; c.zj = a.z_jump; c.zjb = a.zj_stride_b; c.zje = a.zj_stride_e; c.n_events = a.n_events;
-    c.xs = a.xs; c.gxs = a.grad_xs;
+    c.xs = a.xs; c.gxs = a.grad_xs; c.flags = a.flags;
     c.gx0 = a.grad_x0; c.gz = a.grad_z; c.gzj = a.grad_z_jump; c.ga0 = a.grad_all_initial; c.gparams_de = a.grad_params;
     return c;
 }
@@ -141,9 +141,11 @@ extern "C" int32_t psnode_ode_backward_f32(const psnode_ode_bwd_args_f32* a, voi
     if (a->saved_act && !use_fused_bwd(a) && !use_latent64_bwd(a)) return PSNODE_ERR_UNSUPPORTED;      // only K4x, K4f and K9 read them
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (a->flags & ~PSNODE_FLAG_INPUT_TRUE_X) return PSNODE_ERR_UNSUPPORTED;
-    if (a->flags & PSNODE_FLAG_INPUT_TRUE_X) {      // teacher-forced backward: K4f (recompute form) is the kernel that has it
-        if (a->kernel == PSNODE_KERNEL_GENERIC || a->saved_act || !fused_bwd_shape_ok(a)) return PSNODE_ERR_UNSUPPORTED;
-        return fused_bwd_launch(a, static_cast<float*>(workspace), s);
+    if (a->flags & PSNODE_FLAG_INPUT_TRUE_X) {      // teacher-forced backward: K4f (recompute form) where the shape is its, else K5
+        if (a->saved_act || a->kernel == PSNODE_KERNEL_MFMA_WAVE) return PSNODE_ERR_UNSUPPORTED;
+        if (use_fused_bwd(a)) return fused_bwd_launch(a, static_cast<float*>(workspace), s);
+        if ((a->kernel != PSNODE_KERNEL_AUTO && a->kernel != PSNODE_KERNEL_GENERIC) || !ode_generic_ok(a)) return PSNODE_ERR_UNSUPPORTED;
+        return generic_backward(generic_bwd_call(*a), nullptr, workspace, stream);
     }
     if (bwd_x_preferred(a)) return bwd_x_launch(a, static_cast<float*>(workspace), s);      // K4x: up to one wave per SIMD at hidden 33..64
     if (use_latent_bwd(a)) return latent_bwd_launch(a, static_cast<float*>(workspace), s);
@@ -204,6 +206,46 @@ extern "C" int32_t psnode_dae_backward_f32(const psnode_dae_bwd_args_f32* a, voi
     if (use_latent16_dae_bwd(a)) return latent16_dae_bwd_launch(a, static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
     if (a->kernel == PSNODE_KERNEL_MFMA) return PSNODE_ERR_UNSUPPORTED;
     return generic_backward(generic_bwd_call(*a), nullptr, workspace, stream);
+}
+
+// ---- teacher-forced DAE backward (include/psnode_hip.h, psnode_dae_bwd_tf_args_f32): K5 alone answers a call with flags; flags == 0 is
+// the entry point above.  NULL args -> method -> dims -> unsupported -> pointers -> workspace, as there.
+namespace {
+constexpr uint32_t kTfFlags = PSNODE_FLAG_INPUT_TRUE_X | PSNODE_FLAG_INPUT_TRUE_I;
+bool dae_tf_ok(const psnode_dae_bwd_tf_args_f32* a) {
+    const psnode_dae_bwd_args_f32& b = a->base;
+    if ((a->flags & ~kTfFlags) || (b.kernel != PSNODE_KERNEL_AUTO && b.kernel != PSNODE_KERNEL_GENERIC)) return false;
+    return !b.saved_act && !b.saved_xstage && !b.saved_ae_act && !b.saved_ev_act && !b.saved_ev_i && dae_generic_ok(&b) != 0;
+}
+}  // namespace
+
+extern "C" int32_t psnode_dae_backward_tf_supported(const psnode_dae_bwd_tf_args_f32* a) {
+    if (!a) return 0;
+    if (a->flags == 0) return psnode_dae_backward_supported(&a->base);
+    return method_ok(&a->base) && dae_tf_ok(a);
+}
+
+extern "C" size_t psnode_dae_backward_tf_workspace_bytes(const psnode_dae_bwd_tf_args_f32* a) {
+    if (!a) return 0;
+    if (a->flags == 0) return psnode_dae_backward_workspace_bytes(&a->base);
+    if (!psnode_dae_backward_tf_supported(a)) return 0;
+    return generic_bwd_workspace_floats(&a->base.de, &a->base.ae, a->base.B) * sizeof(float);
+}
+
+extern "C" int32_t psnode_dae_backward_tf_f32(const psnode_dae_bwd_tf_args_f32* a, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!a) return PSNODE_ERR_NULL;
+    if (a->flags == 0) return psnode_dae_backward_f32(&a->base, workspace, workspace_bytes, stream);
+    const psnode_dae_bwd_args_f32* b = &a->base;
+    const int rc = check_call(b);
+    if (rc) return rc;
+    if (b->T < 2) return PSNODE_ERR_DIMS;
+    if (!dae_tf_ok(a)) return PSNODE_ERR_UNSUPPORTED;
+    if (!ptrs_ok(b)) return PSNODE_ERR_NULL;
+    if (((a->flags & PSNODE_FLAG_INPUT_TRUE_X) && !a->x_true) || ((a->flags & PSNODE_FLAG_INPUT_TRUE_I) && !a->i_true)) return PSNODE_ERR_NULL;
+    if (!workspace_ok(workspace, workspace_bytes, psnode_dae_backward_tf_workspace_bytes(a))) return PSNODE_ERR_WORKSPACE;
+    GenericBwdCall c = generic_bwd_call(*b);
+    c.flags = a->flags; c.xt = a->x_true; c.it = a->i_true;
+    return generic_backward(c, nullptr, workspace, stream);
 }
 
 // ---- hidden-layer activations other than ELU(1) (include/psnode_hip.h, psnode_act_f32): K5 only, no teacher forcing, no saved rows.

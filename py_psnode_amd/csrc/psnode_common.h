@@ -310,6 +310,8 @@ struct GenericBwdCall {
     int n_events;
     const float *xs, *is_, *gxs, *gis;
     float *gx0, *gz, *gv, *gzj, *gvj, *ga0, *gparams_de, *gparams_ae;
+    unsigned flags;            // PSNODE_FLAG_INPUT_TRUE_X / _I: the teacher-forced sweep (ELU(1) build only for now)
+    const float *xt, *it;      // DAE: x_true / i_true [T,B,.] for the flags set (the ODE's dataset comes in as xs)
 };
 struct ActPair;     // psnode_act.h: the DE's and the AE's activation of a non-ELU(1) call
 size_t generic_bwd_workspace_floats(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, long long B);

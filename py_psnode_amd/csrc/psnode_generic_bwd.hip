@@ -12,6 +12,7 @@
 // activations followed by the VJP:  delta_in = W^T delta_out * ELU'(.) (weights read row-major, coalesced over the input
 // index) and dW += delta (x) act in 4x4 register blocks.  DAE: the AE head's VJP is chained in through the algebraic
 // variable (i_{k+1} = g(x_{k+1}; z,v) feeds the DE of step k+1; at event steps i0 = g(x_k; jumps) instead).
+// Teacher forcing (GBwd::flags) changes the outer sweep only: which rows a step starts from and which adjoints travel to the step before.
 #include <string.h>
 
 #include "psnode_common.h"
@@ -63,6 +64,13 @@
 #define K5_KERNEL_PARAMS const GBwd a
 #define K5_LAUNCH_ARG(x)
 #endif
+#if defined(PSNODE_K5_PRE_BUILD)
+#define K5_TWO_WAVES(gg, STR) 1
+#elif defined(PSNODE_K5_ACT_BUILD)
+#define K5_TWO_WAVES(gg, STR) ((STR) == 2 ? 2 : 1)
+#else
+#define K5_TWO_WAVES(gg, STR) (((STR) == 2 && !(gg)) ? 2 : 1)
+#endif
 
 namespace psnode {
 namespace {
@@ -97,6 +105,10 @@ struct GBwd {
     const float* vj; long long vjb, vje;
     int n_events;
     const float *xs, *is_, *gxs, *gis;
+    // teacher forcing (include/psnode_hip.h, PSNODE_FLAG_INPUT_TRUE_X / _I): launch-uniform, tested at sweep level only.  xt / it: the dataset
+    // rows x_true / i_true [T,B,.] (an ODE call hands the dataset in as xs: its launcher sets xt = xs)
+    unsigned flags;
+    const float *xt, *it;
     float *gx0, *gz, *gv, *gzj, *gvj, *ga0, *wpart;
     int maxw, act_rows;
     int gacc_global;   // parameter-gradient accumulators in this workgroup's slice of wpart (global, L2) instead of LDS: 0 = none,
@@ -614,8 +626,10 @@ __device__ __forceinline__ float* g_vjp_str(const GMlp& m, const float* const* t
 
 // gg / ggA: the DE's / the AE's accumulators live in the workgroup's global slice.  REG: the DE on the register path.  STR: 1 = the AE
 // head streamed, 2 = both MLPs streamed (0: whatever is not on the register path stages its weights through LDS).
+// (waves per SIMD, K5_TWO_WAVES: the fully streamed instances that fitted 256 registers -- two workgroups per CU where their LDS allows
+//  it -- keep that budget: the sweep-level flag values must not cost them the second workgroup)
 template <bool gg, bool REG, bool ggA = gg, int STR = 0>
-__global__ __launch_bounds__(NT) void K5_KERNEL(K5_KERNEL_PARAMS) {
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(K5_TWO_WAVES(gg, STR), 8))) void K5_KERNEL(K5_KERNEL_PARAMS) {
     constexpr bool DE_TM = REG || STR == 2;      // the DE's LDS accumulators are tile-major
     constexpr bool AE_TM = STR >= 1;
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -626,6 +640,10 @@ __global__ __launch_bounds__(NT) void K5_KERNEL(K5_KERNEL_PARAMS) {
     const int nzv = zd + vd, ne = nzv + id, n = xd + ne;
     const int S = rk_stages(a.method);
     const int nx = xd * TP;
+    // teacher forcing: tx -- every DE step and every grid-point head reads the dataset row (xsrc), the adjoint of a step's start state is
+    // dropped; ti -- the DE reads i_true[k], its algebraic adjoint is dropped and the event-time head feeds nothing
+    const bool tx = (a.flags & PSNODE_FLAG_INPUT_TRUE_X) != 0, ti = dae && (a.flags & PSNODE_FLAG_INPUT_TRUE_I) != 0;
+    const float* __restrict__ xsrc = tx ? a.xt : a.xs;
 
     float* acts = lds;                            // [act_rows][TP]
     float* dA = acts + a.act_rows * TP;           // [maxw][TP]
@@ -743,7 +761,8 @@ __global__ __launch_bounds__(NT) void K5_KERNEL(K5_KERNEL_PARAMS) {
         __syncthreads();
     };
 
-    // Look-ahead (round 6): the rows a step reads from HBM -- the clocks, the dataset z | v, xs[k], the incoming gradient of grid point k --
+    // Look-ahead (round 6): the rows a step reads from HBM -- the clocks, the dataset z | v, xs[k] (x_true[k] under INPUT_TRUE_X), the incoming
+    // gradient of grid point k --
     // are requested one step early into registers (items tid + 256 j, j < LA: up to 32 rows each; rows beyond that are loaded where they are
     // used), so that their latency hides behind the previous step instead of standing at the top and the bottom of every step.
     constexpr int LA = 2;
@@ -753,7 +772,7 @@ __global__ __launch_bounds__(NT) void K5_KERNEL(K5_KERNEL_PARAMS) {
         for (int j = 0; j < LA; ++j) {
             const int idx = tid + NT * j;
             const int ix = idx < xd * TB ? idx : 0, rx = ix / TB, cx = ix % TB;
-            la_x[j] = a.xs[(kk * a.B + gb(cx)) * xd + rx];
+            la_x[j] = xsrc[(kk * a.B + gb(cx)) * xd + rx];
             la_g[j] = a.gxs[(kk * a.B + gb(cx)) * xd + rx];
             const int iz = idx < nzv * TB ? idx : 0, rz = iz / TB;
             const long long b = gb(iz % TB);
@@ -776,7 +795,7 @@ __global__ __launch_bounds__(NT) void K5_KERNEL(K5_KERNEL_PARAMS) {
             if (idx < xd * TB) x0[(idx / TB) * TP + idx % TB] = la_x[j];
             if (idx < nzv * TB && ev < 0) ext[(idx / TB) * TP + idx % TB] = la_zv[j];
         }
-        for (int idx = tid + NT * LA; idx < xd * TB; idx += NT) x0[(idx / TB) * TP + idx % TB] = a.xs[(k * a.B + gb(idx % TB)) * xd + idx / TB];
+        for (int idx = tid + NT * LA; idx < xd * TB; idx += NT) x0[(idx / TB) * TP + idx % TB] = xsrc[(k * a.B + gb(idx % TB)) * xd + idx / TB];
         TILE_LOOP(nzv) {
             if (ev < 0 && idx < NT * LA) continue;                                      // (came through the look-ahead registers)
             const long long b = gb(c);
@@ -790,12 +809,21 @@ __global__ __launch_bounds__(NT) void K5_KERNEL(K5_KERNEL_PARAMS) {
         __syncthreads();
         if (dae) {
             // (1) AE head at the end of step k: i_{k+1} = g(x_{k+1}; z[k+1], v[k+1]) carries gic
-            TILE_LOOP(xd) xst[r * TP + c] = a.xs[((k + 1) * a.B + gb(c)) * xd + r];
+            //     (tx: the head read x_true[k+1] and its x-adjoint is dropped -- gx0 is rewritten in (3b))
+            TILE_LOOP(xd) xst[r * TP + c] = xsrc[((k + 1) * a.B + gb(c)) * xd + r];
             __syncthreads();
-            ae_vjp(xst, k + 1, -1, gic, gxc);
-            // (2) algebraic input of this step's DE
-            if (ev >= 0) {
-                ae_input(x0, -1);
+            ae_vjp(xst, k + 1, -1, gic, tx ? gx0 : gxc);
+            // (2) algebraic input of this step's DE (ti: the dataset row, also on event steps)
+            if (ti) {
+                TILE_LOOP(id) ext[(nzv + r) * TP + c] = a.it[(k * a.B + gb(c)) * id + r];
+            } else if (ev >= 0) {
+                const float* xr = x0;
+                if (tx) {       // the event-time head reads the RUNNING state xs[k], not the row the DE starts from (xst is free until (3a))
+                    TILE_LOOP(xd) xst[r * TP + c] = a.xs[(k * a.B + gb(c)) * xd + r];
+                    __syncthreads();
+                    xr = xst;
+                }
+                ae_input(xr, -1);
                 if constexpr (STR >= 1) g_forward_str(a.ae, a.fimgA, acts, qb, qoA K5_ACT_ARG(act.ae)); else g_forward(a.ae, acts, wbuf K5_ACT_ARG(act.ae));
                 const float* out = acts + a.ae.act[a.ae.L] * TP;
                 TILE_LOOP(id) ext[(nzv + r) * TP + c] = out[r * TP + c];
@@ -852,6 +880,9 @@ __global__ __launch_bounds__(NT) void K5_KERNEL(K5_KERNEL_PARAMS) {
             }
             __syncthreads();
         }
+        // tx: the step started from a dataset row -- its start adjoint goes nowhere (an ODE keeps step 0's: grad_x0 = grad_xs[0] + it), and
+        // gx0 from here on collects what still reaches the running state xs[k]: the event-time head's x-adjoint
+        if (tx && (dae || k > 0)) { TILE_LOOP(xd) gx0[r * TP + c] = 0.0f; }
         // (4) gradients of this step's external inputs
         TILE_LOOP(nzv) {
             if (!on(c)) continue;
@@ -869,8 +900,16 @@ __global__ __launch_bounds__(NT) void K5_KERNEL(K5_KERNEL_PARAMS) {
         }
         if (dae) {
             __syncthreads();
-            if (ev >= 0) {   // i_in = g(x_k; jumps): its gradient flows into x_k and the jump inputs; i_k itself was unused
-                ae_vjp(x0, -1, ev, gext + nzv * TP, gx0);
+            if (ti) {        // the DE read i_true[k]: nothing flows back through the algebraic variable
+                TILE_LOOP(id) gic[r * TP + c] = (on(c) && a.gis) ? a.gis[(k * a.B + gb(c)) * id + r] : 0.0f;
+            } else if (ev >= 0) {   // i_in = g(x_k; jumps): its gradient flows into x_k and the jump inputs; i_k itself was unused
+                const float* xr = x0;
+                if (tx) {    // (the stages are done with xst)
+                    TILE_LOOP(xd) xst[r * TP + c] = a.xs[(k * a.B + gb(c)) * xd + r];
+                    __syncthreads();
+                    xr = xst;
+                }
+                ae_vjp(xr, -1, ev, gext + nzv * TP, gx0);
                 TILE_LOOP(id) gic[r * TP + c] = (on(c) && a.gis) ? a.gis[(k * a.B + gb(c)) * id + r] : 0.0f;
             } else {
                 TILE_LOOP(id) gic[r * TP + c] = gext[(nzv + r) * TP + c] + ((on(c) && a.gis) ? a.gis[(k * a.B + gb(c)) * id + r] : 0.0f);
@@ -889,9 +928,9 @@ __global__ __launch_bounds__(NT) void K5_KERNEL(K5_KERNEL_PARAMS) {
         __syncthreads();
     }
     if (dae) {   // i_0 = g(x_0; z[0], v[0])   (my_solvers.py:95)
-        TILE_LOOP(xd) x0[r * TP + c] = a.xs[gb(c) * xd + r];
+        TILE_LOOP(xd) x0[r * TP + c] = xsrc[gb(c) * xd + r];
         __syncthreads();
-        ae_vjp(x0, 0, -1, gic, gxc);
+        ae_vjp(x0, 0, -1, gic, tx ? gx0 : gxc);
     }
     TILE_LOOP(xd) if (on(c)) a.gx0[(b0 + c) * xd + r] = gxc[r * TP + c];
     TILE_LOOP(n) if (on(c)) a.ga0[(b0 + c) * n + r] = ga0s[r * TP + c];
@@ -1114,6 +1153,7 @@ int generic_backward_launch(
     a.t = c.t; a.z = c.z; a.v = c.v; a.a0 = c.a0; a.ev = c.ev; a.zj = c.zj; a.zjb = c.zjb; a.zje = c.zje; a.vj = c.vj; a.vjb = c.vjb;
     a.vje = c.vje; a.n_events = c.n_events; a.xs = c.xs; a.is_ = c.is_; a.gxs = c.gxs; a.gis = c.gis; a.gx0 = c.gx0; a.gz = c.gz; a.gv = c.gv;
     a.gzj = c.gzj; a.gvj = c.gvj; a.ga0 = c.ga0;
+    a.flags = c.flags; a.xt = dae ? c.xt : c.xs; a.it = c.it;
     a.de_reg = de_reg_class(*de) ? 1 : 0;
     float* img[kMaxLayers] = {}, *imgT[kMaxLayers] = {}, *imgA[kMaxLayers] = {}, *imgTA[kMaxLayers] = {};
     {                           // the plain / transposed images of both MLPs sit in front of the per-workgroup partials

@@ -1,6 +1,6 @@
 """Backward of `dae_integrate`: K7f in one launch for the DAE_01 shape class at hidden <= 128 (psnode_dae_backward_wide_f32, + K7h for
 the AE head's rows where the kernel does not form the head's gradients itself), K9 / K8 / K9w for the latent shapes, the generic K5
-otherwise (psnode_dae_backward_f32)."""
+otherwise (psnode_dae_backward_f32); teacher-forced calls outside K7f's class go to K5 through psnode_dae_backward_tf_f32."""
 import ctypes
 
 import torch
@@ -9,22 +9,24 @@ from .. import _lib
 from ._common import (KERNEL_ID, Layers, METHOD_ID, STAGES, _aligned16, _aligned_ptr, _bind_jumps, _check_saved, _empty, _f32_dev, _mlp, _pad_rows, _padded_hidden, _split_grads, _view, call_entry, dae_acts, entry_supported)
 from .latent import latent_backward_wide, latent_wide_shape
 
-def dae_backward_supported(method: str, de_layers: Layers, ae_layers: Layers, x_dim, z_dim, v_dim, i_dim, act=None) -> bool:
-    """act: None (both MLPs ELU(1)) or (de_act, ae_act); an activation other than ELU(1) is K5's alone."""
+def dae_backward_supported(method: str, de_layers: Layers, ae_layers: Layers, x_dim, z_dim, v_dim, i_dim, act=None, kernel: str = "auto") -> bool:
+    """act: None (both MLPs ELU(1)) or (de_act, ae_act); an activation other than ELU(1) is K5's alone.  kernel="generic": does K5 take
+    the shape (the question a teacher-forced call outside K7f's class asks)."""
     if de_layers[0][0].device.type != "cuda" or max(len(de_layers), len(ae_layers)) > _lib.MAX_LAYERS:
         return False
     acts = dae_acts(act)
     non_elu = any(q is not None for q in acts)
-    if not non_elu and latent_wide_shape(de_layers, ae_layers, x_dim, z_dim, v_dim, i_dim):
+    if not non_elu and kernel != "generic" and latent_wide_shape(de_layers, ae_layers, x_dim, z_dim, v_dim, i_dim):
         return True                          # K3w (saving) + K9w + library GEMMs
     a = _lib.DaeBwdArgsF32()
     a.method = METHOD_ID[method]
     a.x_dim, a.z_dim, a.v_dim, a.i_dim, a.T, a.B = x_dim, z_dim, v_dim, i_dim, 2, 1
     dev = de_layers[0][0].device
     a.de, a.ae = _mlp(de_layers, dev, "de", []), _mlp(ae_layers, dev, "ae", [])
+    a.kernel = KERNEL_ID[kernel]
     if entry_supported(_lib.load(), "dae_backward", a, acts):      # K9 / K8 (latent shapes) or K5
         return True
-    if non_elu:
+    if non_elu or kernel == "generic":
         return False
     return dae_backward_wide_supported(method, de_layers, ae_layers, x_dim, z_dim, v_dim, i_dim)      # K7f: the DAE_01 class at hidden <= 128
 
@@ -299,8 +301,6 @@ def dae_backward(method: str, de_layers: Layers, ae_layers: Layers, t, z, v, all
     saved = what `dae_integrate(save=True)` returned (read by K7f, K9 and K9w; K8 / K5 recompute and refuse them).
     act: None (both MLPs ELU(1)) or (de_act, ae_act); an activation other than ELU(1) runs on K5 only (kernel "auto" / "generic").
     Returns dict(x_init, z, v, z_jump, v_jump, all_initial, de=[...], ae=[...]) of gradients."""
-    lib = _lib.load()
-    dev = xs.device
     T, B, xd = xs.shape
     zd, vd, idim = z.shape[-1], v.shape[-1], is_.shape[-1]
     acts = dae_acts(act)
@@ -318,8 +318,46 @@ def dae_backward(method: str, de_layers: Layers, ae_layers: Layers, t, z, v, all
                             and dae_backward_wide_supported(method, de_layers, ae_layers, xd, zd, vd, idim)):
         return dae_backward_wide(method, de_layers, ae_layers, t, z, v, all_initial, xs, is_, grad_xs, grad_is, event_idx=event_idx,
                                  z_jump=z_jump, v_jump=v_jump, saved=saved)
+    return _dae_backward_entry(method, de_layers, ae_layers, t, z, v, all_initial, xs, is_, grad_xs, grad_is, event_idx, z_jump, v_jump,
+                               kernel, saved, acts)
+
+
+def dae_backward_tf(method: str, de_layers: Layers, ae_layers: Layers, t, z, v, all_initial, xs, is_, grad_xs, grad_is, event_idx=None,
+                    z_jump=None, v_jump=None, kernel: str = "auto", x_true=None, i_true=None):
+    """Backward of a teacher-forced `dae_integrate` (input_true_x / input_true_i, my_solvers.py:111-121) on the generic backward K5
+    (psnode_dae_backward_tf_f32): every shape K5 takes untied.  x_true [T,B,x_dim] / i_true [T,B,i_dim]: the dataset rows the forward call
+    fed the DE / the heads (None = that flag was not set; both None = `dae_backward` on K5's entry point); they get no gradient.  xs / is_:
+    the forward results (an event step's recomputed head reads the running state xs[k]).  kernel: "auto" | "generic".
+    Same return value as `dae_backward`."""
+    if kernel not in ("auto", "generic"):
+        raise _lib.UnsupportedShapeError("dae_backward_tf: the teacher-forced backward behind this entry point is K5's (kernel 'auto' / 'generic'); "
+                                         "K7f's is dae_backward_wide")
+    T, B, xd = xs.shape
+    for name, q, w in (("x_true", x_true, xd), ("i_true", i_true, is_.shape[-1])):
+        if q is not None and tuple(q.shape) != (T, B, w):
+            raise ValueError(f"{name} must be [T,B,{w}], got {tuple(q.shape)}")
+    return _dae_backward_entry(method, de_layers, ae_layers, t, z, v, all_initial, xs, is_, grad_xs, grad_is, event_idx, z_jump, v_jump,
+                               kernel, None, (None, None), x_true=x_true, i_true=i_true)
+
+
+def _dae_backward_entry(method, de_layers, ae_layers, t, z, v, all_initial, xs, is_, grad_xs, grad_is, event_idx, z_jump, v_jump, kernel, saved,
+                        acts, x_true=None, i_true=None):
+    """psnode_dae_backward_f32 / _act_f32, or psnode_dae_backward_tf_f32 when dataset rows come along: one marshalling for the three."""
+    lib = _lib.load()
+    dev = xs.device
+    T, B, xd = xs.shape
+    zd, vd, idim = z.shape[-1], v.shape[-1], is_.shape[-1]
     keep: list = []
-    a = _lib.DaeBwdArgsF32()
+    tf = None
+    if x_true is not None or i_true is not None:
+        tf = _lib.DaeBwdTfArgsF32()
+        xt_c = _f32_dev(x_true, dev, "x_true").contiguous() if x_true is not None else None
+        it_c = _f32_dev(i_true, dev, "i_true").contiguous() if i_true is not None else None
+        keep += [xt_c, it_c]
+        tf.flags = (_lib.FLAG_INPUT_TRUE_X if xt_c is not None else 0) | (_lib.FLAG_INPUT_TRUE_I if it_c is not None else 0)
+        tf.x_true = xt_c.data_ptr() if xt_c is not None else None
+        tf.i_true = it_c.data_ptr() if it_c is not None else None
+    a = tf.base if tf is not None else _lib.DaeBwdArgsF32()      # (tf.base: a view of the struct's own memory)
     a.method = METHOD_ID[method]
     a.kernel = KERNEL_ID[kernel]
     a.x_dim, a.z_dim, a.v_dim, a.i_dim, a.T, a.B = xd, zd, vd, idim, T, B
@@ -370,10 +408,14 @@ def dae_backward(method: str, de_layers: Layers, ae_layers: Layers, t, z, v, all
                 if s_ev is None or s_evi is None or s_ev.shape[0] != n_ev_ or s_ev.shape[2] != B or s_evi.shape[:2] != (n_ev_, B):
                     raise ValueError("saved event activations do not belong to this call (shape)")
                 a.saved_ev_act, a.saved_ev_i = s_ev.data_ptr(), s_evi.data_ptr()
-        nbytes = lib.psnode_dae_backward_workspace_bytes(ctypes.byref(a))
+        if tf is not None:
+            nbytes = lib.psnode_dae_backward_tf_workspace_bytes(ctypes.byref(tf))
+        else:
+            nbytes = lib.psnode_dae_backward_workspace_bytes(ctypes.byref(a))
         ws = _empty(nbytes + 256, dtype=torch.uint8, device=dev)
         wp, wn = _aligned_ptr(ws)
-        rc = call_entry(lib, "dae_backward", a, acts, wp, wn, torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(rc, "psnode_dae_backward_f32")
+        st = torch.cuda.current_stream(dev).cuda_stream
+        rc = lib.psnode_dae_backward_tf_f32(ctypes.byref(tf), wp, wn, st) if tf is not None else call_entry(lib, "dae_backward", a, acts, wp, wn, st)
+    _lib.check(rc, "psnode_dae_backward_tf_f32" if tf is not None else "psnode_dae_backward_f32")
     g["de"], g["ae"] = _split_grads(gde, de_layers), _split_grads(gae, ae_layers)
     return g

@@ -32,7 +32,8 @@ def ode_backward(method: str, de_layers: Layers, t, z, all_initial, xs, grad_xs,
                  kernel: str = "auto", saved=None, input_true_x: bool = False, need_grad_zj: bool = True, act=None):
     """Backward pass of `ode_integrate` in one launch.  `saved` = what `ode_integrate(save=True)` returned next to
     xs: K4f then skips the recompute of the stage evaluations.  input_true_x: backward of a teacher-forced call (my_solvers.py:72-74) --
-    `xs` must then be the DATASET x the forward call started every step from; K4f (hidden <= 128, x_dim <= 8) only.
+    `xs` must then be the DATASET x the forward call started every step from; K4f where the shape is its (hidden <= 128, x_dim <= 8) and
+    kernel is not "generic", else the generic K5 (kernel "auto" / "generic").
     need_grad_z / need_grad_zj = False: dL/dz / dL/dz_jump are not formed (the scripts' z and z_jump are dataset tensors: K4x then runs
     without its per-step dL/dz layer, and the [B,nE,zd] zero fill is not made).
     kernel: "wave" = K4x (one wave per 4 trajectories; hidden 33..64, saved rows), "wide" / "tile" = K4f; "auto" picks between them.

@@ -5,7 +5,7 @@ fresh contiguous [T,B,D] out) and error behaviour (my_solvers.py:11-29, 52-131).
 sides are the reference's ELU-MLPs on a HIP device the whole time loop runs in ONE fused HIP launch
 (py_psnode_amd.fused -> libpsnode_hip.so); with autograd in play the call becomes a torch.autograd.Function
 (fused forward kernel + one fused backward kernel, py_psnode_amd/autograd.py).  Arbitrary Python callbacks --
-which no kernel can execute -- teacher-forced training and shapes no backward kernel covers are stepped through
+which no kernel can execute -- and shapes no backward kernel covers are stepped through
 the user's own callables by `_walk_*` below.
 
 `solver.fused` selects the route: "auto" (default; fused whenever the call is fusable, and it then FAILS
@@ -75,8 +75,8 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
             self._walk_warned = True
             warnings.warn(f"{what}: this call is not fusable (needs fp32 HIP tensors, DE_Func/AE_Func-style MLPs with one activation "
                           "of ELU / Tanh / Sigmoid / ReLU / LeakyReLU / Softplus / SiLU / GELU / Mish -- other than ELU(1) on kernel 'auto' / 'generic' only --, "
-                          "ODE_Event/DAE_Event callbacks; under autograd also a shape with a backward kernel and no teacher "
-                          "forcing) -- stepping through the Python callables instead", RuntimeWarning, stacklevel=3)
+                          "ODE_Event/DAE_Event callbacks; under autograd also a shape with a backward kernel; teacher-forced "
+                          "training: ELU(1), dataset rows without grad) -- stepping through the Python callables instead", RuntimeWarning, stacklevel=3)
 
     def _act_kernel_ok(self, what, acts) -> bool:
         """An activation other than ELU(1) runs on the generic kernels K0 / K5 only: kernel 'wave' / 'tile' / 'mfma' / 'wide' with one walks
@@ -129,16 +129,17 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
                     from ..autograd import fused_ode_integrate
                     return fused_ode_integrate(self.method, self.kernel, layers, t, x, z, all_initial, event_t, z_jump,
                                                check_events=self._check_events_now(event_t), x_init=x_init, act=act)
-                # teacher-forced training (my_solvers.py:72-74): K4f in its recompute form (ELU(1) only); the dataset x gets no gradient
-                elif input_true_x and act is None and not x.requires_grad and self.kernel in ("auto", "mfma") and \
-                        _fused.ode_backward_supported(self.method, layers, x.shape[-1], z.shape[-1], "wide"):
+                # teacher-forced training (my_solvers.py:72-74): K4f in its recompute form where the shape is its, else K5 (ELU(1) only);
+                # the dataset x gets no gradient
+                elif input_true_x and act is None and not x.requires_grad and _autograd().ode_training_supported(
+                        self.method, layers, x.shape[-1], z.shape[-1], t.shape[0], t.shape[1], kernel=self.kernel, input_true_x=True):
                     from ..autograd import fused_ode_integrate
                     return fused_ode_integrate(self.method, self.kernel, layers, t, x, z, all_initial, event_t, z_jump,
                                                check_events=self._check_events_now(event_t), input_true_x=True)
             if self.fused == "require":
                 raise NotFusableError("integrate_ODE: call is not fusable (needs fp32 HIP tensors, a DE_Func-style MLP `x_dot` with one "
                                       "activation of ELU / Tanh / Sigmoid / ReLU / LeakyReLU / Softplus / SiLU / GELU / Mish, ODE_Event callbacks; with autograd: "
-                                      "a shape with a backward kernel, no teacher forcing)")
+                                      "a shape with a backward kernel; teacher-forced training: ELU(1), kernel 'auto' / 'mfma' / 'generic', x without grad)")
             self._note_walk("integrate_ODE", x)
         return self._walk_ode(x_func, t, x, z, all_initial, event_fn, jump_change_fn, input_true_x, x_init)
 
@@ -180,17 +181,19 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
                     from ..autograd import fused_dae_integrate
                     return fused_dae_integrate(self.method, self.kernel, de, ae, x_init, t, z, v, i, all_initial, event_t, z_jump, v_jump,
                                                check_events=self._check_events_now(event_t), act=act)
-                # teacher-forced training (my_solvers.py:111-121): K7f in its recompute form (ELU(1) only); the dataset rows get no gradient
+                # teacher-forced training (my_solvers.py:111-121): K7f in its recompute form where the shape is its, else K5 (ELU(1) only);
+                # the dataset rows get no gradient
                 elif act is None and (input_true_x or input_true_i) and not (input_true_x and x.requires_grad) and not (input_true_i and i.requires_grad) \
-                        and x.shape[-1] == x_init.shape[-1] and self.kernel in ("auto", "mfma") and t.shape[0] >= 2 and \
-                        _fused.dae_backward_wide_supported(self.method, de, ae, x_init.shape[-1], z.shape[-1], v.shape[-1], i.shape[-1]):
+                        and x.shape[-1] == x_init.shape[-1] and _autograd().dae_training_supported(
+                            self.method, de, ae, x_init.shape[-1], z.shape[-1], v.shape[-1], i.shape[-1], t.shape[0], t.shape[1],
+                            kernel=self.kernel, input_true_x=input_true_x, input_true_i=input_true_i):
                     from ..autograd import fused_dae_integrate
                     return fused_dae_integrate(self.method, self.kernel, de, ae, x_init, t, z, v, i, all_initial, event_t, z_jump, v_jump,
                                                check_events=self._check_events_now(event_t), x=x, input_true_x=input_true_x,
                                                input_true_i=input_true_i)
             if self.fused == "require":
                 raise NotFusableError("integrate_DAE: call is not fusable (needs fp32 HIP tensors, DE_Func/AE_Func-style "
-                                      "MLPs with one activation each of ELU / Tanh / Sigmoid / ReLU / LeakyReLU / Softplus / SiLU / GELU / Mish, DAE_Event callbacks; with autograd: a shape with a backward kernel; teacher forcing: hidden <= 128, dataset rows without grad)")
+                                      "MLPs with one activation each of ELU / Tanh / Sigmoid / ReLU / LeakyReLU / Softplus / SiLU / GELU / Mish, DAE_Event callbacks; with autograd: a shape with a backward kernel; teacher-forced training: ELU(1), kernel 'auto' / 'mfma' / 'generic', T >= 2, dataset rows without grad)")
             self._note_walk("integrate_DAE", z if z.numel() else v)
         return self._walk_dae(x_init, x_func, i_func, t, x, z, v, i, all_initial, event_fn, jump_change_fn,
                               input_true_x, input_true_i)
