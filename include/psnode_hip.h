@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define PSNODE_ABI_VERSION 10    /* 10 also carries the additive psnode_act_f32 / *_act_* entry points (end of this file) */
+#define PSNODE_ABI_VERSION 10    /* 10 also carries the additive psnode_act_f32 / *_act_* and psnode_rk_tableau_f32 / *_rk_* entry points (end of this file) */
 #define PSNODE_MAX_LAYERS 8      /* Linear layers per MLP */
 #define PSNODE_MAX_WIDTH 1024    /* widest layer OUTPUT the kernels accept */
 #define PSNODE_MAX_IN_WIDTH 2048 /* widest first-layer INPUT (the latent DE of DAE_02 at --hidden 128 is 12 x 128 = 1536 wide) */
@@ -682,6 +682,48 @@ int32_t psnode_ode_backward_act_f32(const psnode_ode_bwd_args_f32* args, const p
 int32_t psnode_dae_backward_act_supported(const psnode_dae_bwd_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act);
 int32_t psnode_dae_backward_act_f32(const psnode_dae_bwd_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
                                     void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- Explicit Runge-Kutta tableaus on the generic kernels (additive to ABI 10; DESIGN.md "Runge-Kutta tableaus").
+ * Any explicit method of 1..4 stages: a[s][j] (j < s) is the coefficient of slope k_j in the argument of stage s, b[s] the weight of k_s
+ * in the update.  One step, in fp32, sums in increasing index, a coefficient that is exactly 0 skipped (its slope is not read):
+ *     argument of stage s = x0 + h * sum_{j<s} a[s][j] k_j          new state = x0 + h * sum_s b[s] k_s
+ * Everything else of the integrators -- zero-order hold of z | v | i, events, the AE head's slots, both teacher-forcing flags -- is that
+ * of the entry points without _rk.  The 3/8 rule, for instance, is stages 4, a21 = 1/3, a31 = -1/3, a32 = 1, a41 = 1, a42 = -1, a43 = 1,
+ * b = 1/8, 3/8, 3/8, 1/8; it then agrees with PSNODE_RK4_38 up to the rounding of the two ways to write the sums.
+ * Rules of every _rk entry point:
+ *   - the `method` field of the args is NOT read; the existing entry points keep rejecting every method outside 0..2;
+ *   - they run K0 (forward) and K5 (backward) only, in a build of their own that carries every activation kind (ELU(1), a NULL act, runs
+ *     as ELU with alpha = 1): `kernel` must be PSNODE_KERNEL_AUTO or _GENERIC and the save_* / saved_* pointers NULL, else
+ *     PSNODE_ERR_UNSUPPORTED; so is a backward call with teacher-forcing flags and an activation other than ELU(1);
+ *   - K5's tableau build keeps the pre-activations in LDS like its pre-activation build, for every kind: the backward fits the shapes that
+ *     build fits (psnode_*_backward_rk_supported answers for it), a class somewhat smaller than that of the ELU(1) backward;
+ *   - a NULL tableau gives PSNODE_ERR_NULL; stages outside 1..4, a coefficient that is not finite, or a non-zero a[s][j] with j >= s
+ *     (entries of rows / columns >= stages included) PSNODE_ERR_METHOD; an invalid act its status of the _act entry points.
+ * The _supported queries answer 1 / 0 for the same rules (dims only).  Workspaces: psnode_workspace_bytes (forward),
+ * psnode_ode_backward_workspace_bytes with any valid method (ODE backward), psnode_dae_backward_rk_workspace_bytes (DAE backward).
+ * The DAE backward takes psnode_dae_bwd_tf_args_f32, whose flags may be 0: one entry point for plain and teacher-forced calls. */
+typedef struct {
+    int32_t stages;        /* 1..4 */
+    float a[4][4];         /* strictly lower triangular */
+    float b[4];
+} psnode_rk_tableau_f32;
+
+int32_t psnode_ode_integrate_rk_supported(const psnode_ode_args_f32* args, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab);
+int32_t psnode_ode_integrate_rk_f32(const psnode_ode_args_f32* args, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
+                                    void* workspace, size_t workspace_bytes, void* stream);
+int32_t psnode_dae_integrate_rk_supported(const psnode_dae_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                          const psnode_rk_tableau_f32* tab);
+int32_t psnode_dae_integrate_rk_f32(const psnode_dae_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                    const psnode_rk_tableau_f32* tab, void* workspace, size_t workspace_bytes, void* stream);
+int32_t psnode_ode_backward_rk_supported(const psnode_ode_bwd_args_f32* args, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab);
+int32_t psnode_ode_backward_rk_f32(const psnode_ode_bwd_args_f32* args, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
+                                   void* workspace, size_t workspace_bytes, void* stream);
+int32_t psnode_dae_backward_rk_supported(const psnode_dae_bwd_tf_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                         const psnode_rk_tableau_f32* tab);
+size_t psnode_dae_backward_rk_workspace_bytes(const psnode_dae_bwd_tf_args_f32* args, const psnode_act_f32* de_act,
+                                              const psnode_act_f32* ae_act, const psnode_rk_tableau_f32* tab);
+int32_t psnode_dae_backward_rk_f32(const psnode_dae_bwd_tf_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                   const psnode_rk_tableau_f32* tab, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -30,7 +30,9 @@ ABI_VERSION = 10         # == PSNODE_ABI_VERSION of include/psnode_hip.h (2: rou
                          #     psnode_ode_bwd_args_f32 selects K4x (_MFMA_WAVE) / K4f (_MFMA_TILE, _MFMA_WIDE);
                          #     additive, same version: psnode_act_f32 and the psnode_{ode,dae}_{integrate,backward}_act_* entry points --
                          #     hidden-layer activations other than ELU(1) on the generic kernels K0 / K5;
-                         #     additive, same version: psnode_dae_bwd_tf_args_f32 and psnode_dae_backward_tf_* -- the teacher-forced DAE backward on K5)
+                         #     additive, same version: psnode_dae_bwd_tf_args_f32 and psnode_dae_backward_tf_* -- the teacher-forced DAE backward on K5;
+                         #     additive, same version: psnode_rk_tableau_f32 and the psnode_{ode,dae}_{integrate,backward}_rk_* entry points --
+                         #     explicit Runge-Kutta tableaus of up to four stages on K0 / K5)
 LIB_NAME = "libpsnode_hip.so"
 # PSNODE_LIB_PATH lets kernel experiments (profiles/scripts/*) load an alternative build of the same ABI
 LIB_PATH = os.environ.get("PSNODE_LIB_PATH") or os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
@@ -57,6 +59,9 @@ EXPORTS = (
     "psnode_ode_integrate_act_supported", "psnode_ode_integrate_act_f32", "psnode_dae_integrate_act_supported", "psnode_dae_integrate_act_f32",
     "psnode_ode_backward_act_supported", "psnode_ode_backward_act_f32", "psnode_dae_backward_act_supported", "psnode_dae_backward_act_f32",
     "psnode_dae_backward_tf_supported", "psnode_dae_backward_tf_workspace_bytes", "psnode_dae_backward_tf_f32",
+    "psnode_ode_integrate_rk_supported", "psnode_ode_integrate_rk_f32", "psnode_dae_integrate_rk_supported", "psnode_dae_integrate_rk_f32",
+    "psnode_ode_backward_rk_supported", "psnode_ode_backward_rk_f32",
+    "psnode_dae_backward_rk_supported", "psnode_dae_backward_rk_workspace_bytes", "psnode_dae_backward_rk_f32",
 )
 
 
@@ -80,6 +85,11 @@ class MlpF32(ctypes.Structure):
 class ActF32(ctypes.Structure):
     """psnode_act_f32: a hidden-layer activation other than ELU(1) (kind = ACT_*)."""
     _fields_ = [("kind", c_int32), ("alpha", ctypes.c_float), ("beta", ctypes.c_float), ("threshold", ctypes.c_float)]
+
+
+class RkTableauF32(ctypes.Structure):
+    """psnode_rk_tableau_f32: an explicit Runge-Kutta method of 1..4 stages (a strictly lower triangular)."""
+    _fields_ = [("stages", c_int32), ("a", (ctypes.c_float * 4) * 4), ("b", ctypes.c_float * 4)]
 
 
 ACT_ELU, ACT_TANH, ACT_SIGMOID, ACT_RELU, ACT_LEAKY_RELU, ACT_SOFTPLUS = 0, 1, 2, 3, 4, 5
@@ -293,6 +303,15 @@ def load():
         q.restype, q.argtypes = c_int32, [ctypes.POINTER(args_t)] + [act_p] * n_act
         f = getattr(lib, f"psnode_{name}_act_f32")
         f.restype, f.argtypes = c_int32, [ctypes.POINTER(args_t)] + [act_p] * n_act + [c_void_p, c_size_t, c_void_p]
+    rk_p = ctypes.POINTER(RkTableauF32)
+    for name, args_t, n_act in (("ode_integrate", OdeArgsF32, 1), ("dae_integrate", DaeArgsF32, 2), ("ode_backward", OdeBwdArgsF32, 1),
+                                ("dae_backward", DaeBwdTfArgsF32, 2)):
+        q = getattr(lib, f"psnode_{name}_rk_supported")
+        q.restype, q.argtypes = c_int32, [ctypes.POINTER(args_t)] + [act_p] * n_act + [rk_p]
+        f = getattr(lib, f"psnode_{name}_rk_f32")
+        f.restype, f.argtypes = c_int32, [ctypes.POINTER(args_t)] + [act_p] * n_act + [rk_p, c_void_p, c_size_t, c_void_p]
+    lib.psnode_dae_backward_rk_workspace_bytes.restype = c_size_t
+    lib.psnode_dae_backward_rk_workspace_bytes.argtypes = [ctypes.POINTER(DaeBwdTfArgsF32), act_p, act_p, rk_p]
     lib.psnode_mlp_rows_backward_workspace_bytes.restype = c_size_t
     lib.psnode_mlp_rows_backward_workspace_bytes.argtypes = [ctypes.POINTER(MlpF32), c_int64]
     lib.psnode_mlp_rows_backward_f32.restype = c_int32

@@ -20,6 +20,11 @@ last_saved_bytes = 0
 _warned_generic_override = False
 
 
+def _is_tableau(method) -> bool:
+    """A fused.Tableau method trains on K0 + K5 alone: nothing is saved, no specialised or latent kernel is asked."""
+    return isinstance(method, fused.Tableau)
+
+
 def latent_wide_training_fits(method, de, ae, hidden, T, B, dev) -> bool:
     """Training at the latent-wide hidden widths exists in ONE form: K3w saves its rows, K9w writes as many adjoint rows again and the
     host contracts them (fused.latent_backward_wide) -- there is no recompute form to fall back to.  True if all of that fits half of the
@@ -28,7 +33,7 @@ def latent_wide_training_fits(method, de, ae, hidden, T, B, dev) -> bool:
         return False
     if SAVE_ACTIVATIONS == "1" or T < 2:         # (T = 1: no step, nothing to save)
         return True
-    S = fused.STAGES[method]
+    S = fused.method_info(method)[1]
     rows = (T - 1) * S * B * hidden * 4              # one [T-1,S,B,H] tensor
     grid = T * B * hidden * 4                        # one [T,B,H] tensor
     need = 4 * rows + (6 if ae is None else 12) * grid       # saved act + xst, gk + d1; d1s, the where / contiguous copies of the external blocks, (DAE) gi, da1, s_ae
@@ -39,7 +44,10 @@ def latent_wide_training_fits(method, de, ae, hidden, T, B, dev) -> bool:
 def ode_training_supported(method, layers, x_dim, z_dim, T, B, kernel="auto", act=None, input_true_x=False) -> bool:
     """What the solver asks before it routes a call that needs autograd to the fused forward + backward pair.  act (fused.Act; None =
     ELU(1)): an activation other than ELU(1) trains on K0 + K5 alone, so K5 answers.  input_true_x: teacher-forced training -- K4f's
-    recompute form on kernel "auto" / "mfma" where the shape is its, else K5 on "auto" / "generic"; ELU(1) only."""
+    recompute form on kernel "auto" / "mfma" where the shape is its, else K5 on "auto" / "generic"; ELU(1) only.
+    method a fused.Tableau: K0 + K5 on kernel "auto" / "generic" (K5's tableau build answers for its fit), the same teacher-forcing rule."""
+    if _is_tableau(method) and kernel not in ("auto", "generic"):
+        return False
     if input_true_x:
         if act is not None:
             return False
@@ -48,20 +56,22 @@ def ode_training_supported(method, layers, x_dim, z_dim, T, B, kernel="auto", ac
         return kernel in ("auto", "generic") and fused.ode_backward_supported(method, layers, x_dim, z_dim, "generic")
     if act is not None:
         return fused.ode_backward_supported(method, layers, x_dim, z_dim, kernel, act=act)
-    if kernel in ("auto", "mfma") and fused.latent_wide_shape(layers, None, x_dim, z_dim):
+    if not _is_tableau(method) and kernel in ("auto", "mfma") and fused.latent_wide_shape(layers, None, x_dim, z_dim):
         return latent_wide_training_fits(method, layers, None, x_dim, T, B, layers[0][0].device)
     return fused.ode_backward_supported(method, layers, x_dim, z_dim, kernel)
 
 
 def _dae_tf_on_k7f(method, kernel, de, ae, x_dim, z_dim, v_dim, i_dim) -> bool:
-    return kernel in ("auto", "mfma") and fused.dae_backward_wide_supported(method, de, ae, x_dim, z_dim, v_dim, i_dim)
+    return not _is_tableau(method) and kernel in ("auto", "mfma") and fused.dae_backward_wide_supported(method, de, ae, x_dim, z_dim, v_dim, i_dim)
 
 
 def dae_training_supported(method, de, ae, x_dim, z_dim, v_dim, i_dim, T, B, act=None, kernel="auto", input_true_x=False,
                            input_true_i=False) -> bool:
     """act: None (both MLPs ELU(1)) or (de_act, ae_act); an activation other than ELU(1) trains on K0 + K5 alone, so K5 answers.
     input_true_x / input_true_i: teacher-forced training (T >= 2, ELU(1) only) -- K7f's recompute form on kernel "auto" / "mfma" where the
-    shape is its, else K5 on "auto" / "generic"."""
+    shape is its, else K5 on "auto" / "generic".  method a fused.Tableau: K0 + K5 on kernel "auto" / "generic", the same rules."""
+    if _is_tableau(method) and kernel not in ("auto", "generic"):
+        return False
     if input_true_x or input_true_i:
         if T < 2 or (act is not None and any(a is not None for a in act)):
             return False
@@ -70,12 +80,14 @@ def dae_training_supported(method, de, ae, x_dim, z_dim, v_dim, i_dim, T, B, act
         return kernel in ("auto", "generic") and fused.dae_backward_supported(method, de, ae, x_dim, z_dim, v_dim, i_dim, kernel="generic")
     if act is not None and any(a is not None for a in act):
         return fused.dae_backward_supported(method, de, ae, x_dim, z_dim, v_dim, i_dim, act=act)
-    if fused.latent_wide_shape(de, ae, x_dim, z_dim, v_dim, i_dim):
+    if not _is_tableau(method) and fused.latent_wide_shape(de, ae, x_dim, z_dim, v_dim, i_dim):
         return latent_wide_training_fits(method, de, ae, x_dim, T, B, de[0][0].device)
     return fused.dae_backward_supported(method, de, ae, x_dim, z_dim, v_dim, i_dim)
 
 
 def _want_saved(method, kernel, layers, x_dim, z_dim, T, B):
+    if _is_tableau(method):
+        return False
     if fused.latent_wide_shape(layers, None, x_dim, z_dim):      # K3w saves, K9w reads: the only fused backward at these widths (the solver
         return True                                              # asked latent_wide_training_fits before it came here)
     if SAVE_ACTIVATIONS == "0" or T < 2 or kernel not in ("auto", "mfma", "wave", "tile"):
@@ -86,7 +98,7 @@ def _want_saved(method, kernel, layers, x_dim, z_dim, T, B):
         return False
     if SAVE_ACTIVATIONS == "1":
         return True
-    S = fused.STAGES[method]
+    S = fused.method_info(method)[1]
     need = (T - 1) * S * B * ((len(layers) - 1) * Hp + x_dim) * 4
     free, _ = torch.cuda.mem_get_info(layers[0][0].device)
     return need <= free // 2
@@ -95,6 +107,8 @@ def _want_saved(method, kernel, layers, x_dim, z_dim, T, B):
 def _want_saved_dae(method, kernel, de, ae, x_dim, z_dim, v_dim, i_dim, T, B):
     """The same policy for the DAE: saved rows are read by the fused-DE backward K7f, i.e. at hidden widths other than 64 (K7, the
     one-launch kernel there, recomputes)."""
+    if _is_tableau(method):
+        return False
     if fused.latent_wide_shape(de, ae, x_dim, z_dim, v_dim, i_dim):
         return True
     if SAVE_ACTIVATIONS == "0" or T < 2 or kernel not in ("auto", "mfma") or len(de) not in (2, 4):
@@ -104,7 +118,7 @@ def _want_saved_dae(method, kernel, de, ae, x_dim, z_dim, v_dim, i_dim, T, B):
             return False
         if SAVE_ACTIVATIONS == "1":
             return True
-        S = fused.STAGES[method]
+        S = fused.method_info(method)[1]
         free, _ = torch.cuda.mem_get_info(de[0][0].device)
         return ((T - 1) * S * 2 + T) * 64 * B * 4 <= free // 2
     # hidden 64 also has the one-launch kernel K7 (recompute).  The saved form beats it at every method since round 4 (K7f requests its
@@ -115,7 +129,7 @@ def _want_saved_dae(method, kernel, de, ae, x_dim, z_dim, v_dim, i_dim, T, B):
         return False
     if SAVE_ACTIVATIONS == "1":
         return True
-    S = fused.STAGES[method]
+    S = fused.method_info(method)[1]
     need = ((T - 1) * S * (3 * Hp + x_dim) + 3 * T * Hp) * B * 4
     free, _ = torch.cuda.mem_get_info(de[0][0].device)
     return need <= free // 2
@@ -150,7 +164,7 @@ class _FusedOde(torch.autograd.Function):
             #  catches an in-place edit of x between forward and backward)
             ctx.save_for_backward(t, z, all_initial, xs, *((z_jump,) if z_jump is not None else ()), x_true, *params)
             return xs
-        if kernel == "generic" and fused.latent_wide_shape(layers, None, x0.shape[-1], z.shape[-1]):
+        if kernel == "generic" and not _is_tableau(method) and fused.latent_wide_shape(layers, None, x0.shape[-1], z.shape[-1]):
             global _warned_generic_override
             if not _warned_generic_override:
                 _warned_generic_override = True
@@ -224,7 +238,8 @@ class _FusedDae(torch.autograd.Function):
         ae = [(params[k], params[k + 1]) for k in range(2 * n_de, len(params), 2)]
         T, B = t.shape[0], t.shape[1]
         x_dummy = x_init.new_zeros((1, B, 0))
-        if kernel == "generic" and fused.latent_wide_shape(de, ae, x_init.shape[-1], z.shape[-1], v.shape[-1], i_shape_like.shape[-1]):
+        if kernel == "generic" and not _is_tableau(method) and fused.latent_wide_shape(de, ae, x_init.shape[-1], z.shape[-1], v.shape[-1],
+                                                                                        i_shape_like.shape[-1]):
             kernel = "auto"
         non_elu = act is not None and any(a is not None for a in act)
         ctx.act = act if non_elu else None

@@ -243,5 +243,7 @@ hipError_t launch_generic_act(const IntegrateDev& a, bool dae, const ActPair& ac
 // psnode_generic_pre.hip: the same for an ActPair with a kind of the pre-activation family (act_pair_pre)
 // (K5's three launchers: psnode_common.h, generic_backward_launch*)
 hipError_t launch_generic_pre(const IntegrateDev& a, bool dae, const ActPair& act, hipStream_t stream);
+// psnode_generic_rk.hip: K0 with the Butcher tableau `rk` in place of a.method, every activation kind (ELU(1) as ELU with alpha = 1)
+hipError_t launch_generic_rk(const IntegrateDev& a, bool dae, const ActPair& act, const psnode_rk_tableau_f32& rk, hipStream_t stream);
 
 }  // namespace psnode

@@ -89,6 +89,7 @@ GenericBwdCall generic_bwd_call(const psnode_dae_bwd_args_f32& a) {
 }
 // act: the activations of a non-ELU(1) call, or nullptr
 int generic_backward(const GenericBwdCall& c, const ActPair* act, void* workspace, void* stream) {
+    if (c.rk) return generic_backward_launch_rk(c, act, static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
     const auto launch = !act ? generic_backward_launch : (act_pair_pre(*act) ? generic_backward_launch_pre : generic_backward_launch_act);
     return launch(c, act, static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
 }
@@ -295,4 +296,90 @@ extern "C" int32_t psnode_dae_backward_act_f32(const psnode_dae_bwd_args_f32* a,
     if (!ptrs_ok(a)) return PSNODE_ERR_NULL;
     if (!workspace_ok(workspace, workspace_bytes, generic_bwd_workspace_floats(&a->de, &a->ae, a->B) * sizeof(float))) return PSNODE_ERR_WORKSPACE;
     return generic_backward(generic_bwd_call(*a), &p, workspace, stream);
+}
+
+// ---- explicit Runge-Kutta tableaus (include/psnode_hip.h, psnode_rk_tableau_f32): K5's tableau build alone (every activation kind; it
+// keeps the pre-activations, so generic_bwd_fits_rk answers for the shape).  The act is checked first, then the tableau; `method` is not
+// read; then NULL args -> dims -> unsupported -> pointers -> workspace, as above.
+namespace {
+bool rk_ode_ok(const psnode_ode_bwd_args_f32* a, bool elu1) {
+    if ((a->kernel != PSNODE_KERNEL_AUTO && a->kernel != PSNODE_KERNEL_GENERIC) || a->saved_act || a->saved_xstage) return false;
+    if ((a->flags & ~PSNODE_FLAG_INPUT_TRUE_X) || (a->flags && !elu1)) return false;
+    const psnode_mlp_f32& m = a->de;
+    if (a->x_dim < 1 || a->z_dim < 0 || m.n_layers < 1 || m.n_layers > kMaxLayers) return false;
+    if (m.in_dim != 3 * (a->x_dim + a->z_dim) || m.out_dim[m.n_layers - 1] != a->x_dim) return false;
+    return generic_bwd_fits_rk(&a->de, nullptr, a->x_dim, a->z_dim, 0, 0) != 0;
+}
+bool rk_dae_ok(const psnode_dae_bwd_tf_args_f32* a, bool elu1) {
+    const psnode_dae_bwd_args_f32& b = a->base;
+    if ((a->flags & ~kTfFlags) || (a->flags && !elu1) || (b.kernel != PSNODE_KERNEL_AUTO && b.kernel != PSNODE_KERNEL_GENERIC)) return false;
+    if (b.saved_act || b.saved_xstage || b.saved_ae_act || b.saved_ev_act || b.saved_ev_i) return false;
+    if (b.x_dim < 1 || b.z_dim < 0 || b.v_dim < 0 || b.i_dim < 1) return false;
+    const int n = b.x_dim + b.z_dim + b.v_dim + b.i_dim;
+    const psnode_mlp_f32 &d = b.de, &g = b.ae;
+    if (d.n_layers < 1 || d.n_layers > kMaxLayers || g.n_layers < 1 || g.n_layers > kMaxLayers) return false;
+    if (d.in_dim != 3 * n || d.out_dim[d.n_layers - 1] != b.x_dim) return false;
+    if (g.in_dim != n + b.x_dim + b.z_dim + b.v_dim || g.out_dim[g.n_layers - 1] != b.i_dim) return false;
+    return generic_bwd_fits_rk(&b.de, &b.ae, b.x_dim, b.z_dim, b.v_dim, b.i_dim) != 0;
+}
+}  // namespace
+
+extern "C" int32_t psnode_ode_backward_rk_supported(const psnode_ode_bwd_args_f32* a, const psnode_act_f32* de_act,
+                                                    const psnode_rk_tableau_f32* tab) {
+    ActPair p;
+    bool elu1 = true;
+    if (!a || act_pair(de_act, nullptr, p, elu1) || rk_tableau_check(tab)) return 0;
+    return rk_ode_ok(a, elu1);
+}
+
+extern "C" int32_t psnode_ode_backward_rk_f32(const psnode_ode_bwd_args_f32* a, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
+                                              void* workspace, size_t workspace_bytes, void* stream) {
+    ActPair p;
+    bool elu1 = true;
+    int rc = act_pair(de_act, nullptr, p, elu1);
+    if (rc) return rc;
+    rc = rk_tableau_check(tab);
+    if (rc) return rc;
+    if (!a) return PSNODE_ERR_NULL;
+    if (a->T < 1 || a->B < 1) return PSNODE_ERR_DIMS;
+    if (!rk_ode_ok(a, elu1)) return PSNODE_ERR_UNSUPPORTED;
+    if (!ptrs_ok(a)) return PSNODE_ERR_NULL;
+    if (!workspace_ok(workspace, workspace_bytes, generic_bwd_workspace_floats(&a->de, nullptr, a->B) * sizeof(float))) return PSNODE_ERR_WORKSPACE;
+    GenericBwdCall c = generic_bwd_call(*a);
+    c.rk = tab;
+    return generic_backward(c, &p, workspace, stream);
+}
+
+extern "C" int32_t psnode_dae_backward_rk_supported(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act,
+                                                    const psnode_act_f32* ae_act, const psnode_rk_tableau_f32* tab) {
+    ActPair p;
+    bool elu1 = true;
+    if (!a || act_pair(de_act, ae_act, p, elu1) || rk_tableau_check(tab)) return 0;
+    return rk_dae_ok(a, elu1);
+}
+
+extern "C" size_t psnode_dae_backward_rk_workspace_bytes(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act,
+                                                         const psnode_act_f32* ae_act, const psnode_rk_tableau_f32* tab) {
+    if (!psnode_dae_backward_rk_supported(a, de_act, ae_act, tab)) return 0;
+    return generic_bwd_workspace_floats(&a->base.de, &a->base.ae, a->base.B) * sizeof(float);
+}
+
+extern "C" int32_t psnode_dae_backward_rk_f32(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                              const psnode_rk_tableau_f32* tab, void* workspace, size_t workspace_bytes, void* stream) {
+    ActPair p;
+    bool elu1 = true;
+    int rc = act_pair(de_act, ae_act, p, elu1);
+    if (rc) return rc;
+    rc = rk_tableau_check(tab);
+    if (rc) return rc;
+    if (!a) return PSNODE_ERR_NULL;
+    const psnode_dae_bwd_args_f32* b = &a->base;
+    if (b->T < 1 || b->B < 1 || (a->flags && b->T < 2)) return PSNODE_ERR_DIMS;
+    if (!rk_dae_ok(a, elu1)) return PSNODE_ERR_UNSUPPORTED;
+    if (!ptrs_ok(b)) return PSNODE_ERR_NULL;
+    if (((a->flags & PSNODE_FLAG_INPUT_TRUE_X) && !a->x_true) || ((a->flags & PSNODE_FLAG_INPUT_TRUE_I) && !a->i_true)) return PSNODE_ERR_NULL;
+    if (!workspace_ok(workspace, workspace_bytes, psnode_dae_backward_rk_workspace_bytes(a, de_act, ae_act, tab))) return PSNODE_ERR_WORKSPACE;
+    GenericBwdCall c = generic_bwd_call(*b);
+    c.flags = a->flags; c.xt = a->x_true; c.it = a->i_true; c.rk = tab;
+    return generic_backward(c, &p, workspace, stream);
 }

@@ -86,9 +86,10 @@ __global__ void event_table_kernel(long long n_steps, const float* clock, long l
 
 ViewDev view(const psnode_view_f32& v) { return ViewDev{v.ptr, v.stride_t, v.stride_b}; }
 
-// act: the hidden layers' activations of a non-ELU(1) call (K0 only), or nullptr
+// act: the hidden layers' activations of a non-ELU(1) call (K0 only), or nullptr; rk: the tableau of an _rk call (K0's tableau build, with
+// `act` always given), or nullptr
 int dispatch(IntegrateDev& d, bool dae, int kernel, const psnode_mlp_f32* de, const psnode_mlp_f32* ae, void* workspace,
-             size_t workspace_bytes, hipStream_t stream, const ActPair* act = nullptr) {
+             size_t workspace_bytes, hipStream_t stream, const ActPair* act = nullptr, const psnode_rk_tableau_f32* rk = nullptr) {
     if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 255u)) return PSNODE_ERR_WORKSPACE;
     if (workspace_bytes < psnode_workspace_bytes(de, ae)) return PSNODE_ERR_WORKSPACE;
     float* ws = static_cast<float*>(workspace);
@@ -112,7 +113,9 @@ int dispatch(IntegrateDev& d, bool dae, int kernel, const psnode_mlp_f32* de, co
     } else {
         if (generic_lds_bytes(d, dae) > 160 * 1024) return PSNODE_ERR_UNSUPPORTED;
         e = launch_pack_image(d.de, dae ? &d.ae : nullptr, d.xd, d.xd + d.zd + (dae ? d.vd + d.id : 0), d.zd + (dae ? d.vd : 0), stream);
-        if (e == hipSuccess)
+        if (e == hipSuccess && rk)
+            e = launch_generic_rk(d, dae, *act, *rk, stream);
+        else if (e == hipSuccess)
             e = !act ? launch_generic(d, dae, stream) : (act_pair_pre(*act) ? launch_generic_pre(d, dae, *act, stream) : launch_generic_act(d, dae, *act, stream));
     }
     return e == hipSuccess ? PSNODE_OK : PSNODE_ERR_HIP;
@@ -219,6 +222,19 @@ bool act_call_ok(int kernel, const void* save_act) {
 }
 
 }  // namespace
+
+int rk_tableau_check(const psnode_rk_tableau_f32* tab) {
+    if (!tab) return PSNODE_ERR_NULL;
+    if (tab->stages < 1 || tab->stages > 4) return PSNODE_ERR_METHOD;
+    for (int s = 0; s < 4; ++s) {
+        if (!isfinite(tab->b[s]) || (s >= tab->stages && tab->b[s] != 0.0f)) return PSNODE_ERR_METHOD;
+        for (int j = 0; j < 4; ++j) {
+            if (!isfinite(tab->a[s][j])) return PSNODE_ERR_METHOD;
+            if ((j >= s || s >= tab->stages) && tab->a[s][j] != 0.0f) return PSNODE_ERR_METHOD;
+        }
+    }
+    return PSNODE_OK;
+}
 
 int act_from_abi(const psnode_act_f32* in, ActDev& out, bool& is_elu1) {
     out = ActDev{PSNODE_ACT_ELU, 1.0f, 1.0f, 20.0f, 1.0f};
@@ -370,6 +386,72 @@ int32_t psnode_dae_integrate_act_f32(const psnode_dae_args_f32* args, const psno
     rc = fill_dae(args, d);
     if (rc) return rc;
     return dispatch(d, true, args->kernel, &args->de, &args->ae, workspace, workspace_bytes, static_cast<hipStream_t>(stream), &p);
+}
+
+// ---- explicit Runge-Kutta tableaus (include/psnode_hip.h, psnode_rk_tableau_f32): K0's tableau build alone.  The act is checked first, then
+// the tableau, then the route (kernel, save_*); `method` is not read (the copy of the args carries a valid one through fill_ode / fill_dae).
+int32_t psnode_ode_integrate_rk_supported(const psnode_ode_args_f32* a, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab) {
+    if (!a || rk_tableau_check(tab)) return 0;
+    psnode_ode_args_f32 c = *a;
+    c.method = PSNODE_EULER;
+    if (!act_call_ok(c.kernel, c.save_act) || c.save_xstage) return 0;
+    c.kernel = PSNODE_KERNEL_GENERIC;
+    const psnode_act_f32 tanh_act = {PSNODE_ACT_TANH, 0.0f, 0.0f, 0.0f};      // (any non-ELU(1) kind: the query of K0's LDS fit)
+    ActPair p;
+    bool elu1 = true;
+    if (act_pair(de_act, nullptr, p, elu1)) return 0;
+    return psnode_ode_integrate_act_supported(&c, &tanh_act);
+}
+
+int32_t psnode_ode_integrate_rk_f32(const psnode_ode_args_f32* args, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
+                                    void* workspace, size_t workspace_bytes, void* stream) {
+    ActPair p;
+    bool elu1 = true;
+    int rc = act_pair(de_act, nullptr, p, elu1);
+    if (rc) return rc;
+    rc = rk_tableau_check(tab);
+    if (rc) return rc;
+    if (!args) return PSNODE_ERR_NULL;
+    if (!act_call_ok(args->kernel, args->save_act) || args->save_xstage) return PSNODE_ERR_UNSUPPORTED;      // K0 only
+    psnode_ode_args_f32 c = *args;
+    c.method = PSNODE_EULER;
+    IntegrateDev d;
+    rc = fill_ode(&c, d);
+    if (rc) return rc;
+    return dispatch(d, false, c.kernel, &c.de, nullptr, workspace, workspace_bytes, static_cast<hipStream_t>(stream), &p, tab);
+}
+
+int32_t psnode_dae_integrate_rk_supported(const psnode_dae_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                          const psnode_rk_tableau_f32* tab) {
+    if (!a || rk_tableau_check(tab)) return 0;
+    psnode_dae_args_f32 c = *a;
+    c.method = PSNODE_EULER;
+    if (!act_call_ok(c.kernel, c.save_act) || c.save_xstage || c.save_ae_act || c.save_ev_act || c.save_ev_i) return 0;
+    c.kernel = PSNODE_KERNEL_GENERIC;
+    const psnode_act_f32 tanh_act = {PSNODE_ACT_TANH, 0.0f, 0.0f, 0.0f};
+    ActPair p;
+    bool elu1 = true;
+    if (act_pair(de_act, ae_act, p, elu1)) return 0;
+    return psnode_dae_integrate_act_supported(&c, &tanh_act, &tanh_act);
+}
+
+int32_t psnode_dae_integrate_rk_f32(const psnode_dae_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                    const psnode_rk_tableau_f32* tab, void* workspace, size_t workspace_bytes, void* stream) {
+    ActPair p;
+    bool elu1 = true;
+    int rc = act_pair(de_act, ae_act, p, elu1);
+    if (rc) return rc;
+    rc = rk_tableau_check(tab);
+    if (rc) return rc;
+    if (!args) return PSNODE_ERR_NULL;
+    if (!act_call_ok(args->kernel, args->save_act) || args->save_xstage || args->save_ae_act || args->save_ev_act || args->save_ev_i)
+        return PSNODE_ERR_UNSUPPORTED;
+    psnode_dae_args_f32 c = *args;
+    c.method = PSNODE_EULER;
+    IntegrateDev d;
+    rc = fill_dae(&c, d);
+    if (rc) return rc;
+    return dispatch(d, true, c.kernel, &c.de, &c.ae, workspace, workspace_bytes, static_cast<hipStream_t>(stream), &p, tab);
 }
 
 int32_t psnode_ode_kernel_for(const psnode_ode_args_f32* a) {

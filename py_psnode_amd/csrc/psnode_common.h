@@ -312,6 +312,7 @@ struct GenericBwdCall {
     float *gx0, *gz, *gv, *gzj, *gvj, *ga0, *gparams_de, *gparams_ae;
     unsigned flags;            // PSNODE_FLAG_INPUT_TRUE_X / _I: the teacher-forced sweep (ELU(1) build only for now)
     const float *xt, *it;      // DAE: x_true / i_true [T,B,.] for the flags set (the ODE's dataset comes in as xs)
+    const psnode_rk_tableau_f32* rk;      // generic_backward_launch_rk: the tableau (checked: rk_tableau_check); `method` is then not read
 };
 struct ActPair;     // psnode_act.h: the DE's and the AE's activation of a non-ELU(1) call
 size_t generic_bwd_workspace_floats(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, long long B);
@@ -323,6 +324,13 @@ int generic_bwd_fits_pre(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, int
 int generic_backward_launch(const GenericBwdCall& c, const ActPair* act, float* workspace, hipStream_t stream);
 int generic_backward_launch_act(const GenericBwdCall& c, const ActPair* act, float* workspace, hipStream_t stream);
 int generic_backward_launch_pre(const GenericBwdCall& c, const ActPair* act, float* workspace, hipStream_t stream);
+// psnode_generic_bwd_rk.hip: the tableau build -- every activation kind (`act` is required: ELU(1) runs as ELU with alpha = 1) and c.rk
+// in place of c.method; it keeps the pre-activations like the pre build, so its own fit answers for it
+int generic_backward_launch_rk(const GenericBwdCall& c, const ActPair* act, float* workspace, hipStream_t stream);
+int generic_bwd_fits_rk(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, int xd, int zd, int vd, int id);
+// psnode_capi.hip: PSNODE_OK, PSNODE_ERR_NULL (no tableau) or PSNODE_ERR_METHOD (stages outside 1..4, a coefficient that is not finite, a
+// non-zero a[s][j] with j >= s or in a row / column >= stages, a non-zero b[s] with s >= stages)
+int rk_tableau_check(const psnode_rk_tableau_f32* tab);
 
 // psnode_latent.hip (direct_encode latent shapes, hidden_dim 16)
 bool latent_shape_ok(const IntegrateDev& a, bool dae);

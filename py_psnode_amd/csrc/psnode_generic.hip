@@ -33,13 +33,25 @@
 // Pre-activation build: psnode_generic_pre.hip compiles it a third time with PSNODE_K0_PRE_BUILD defined as well.  Its kernels
 // (generic_pre_act_kernel) apply all ten kinds (pre_act_quad: the six above, and SiLU / GELU / GELU(tanh) / Mish); the forward needs no
 // pre-activation.  Its launcher is launch_generic_pre.
-#if defined(PSNODE_K0_PRE_BUILD)
+// Tableau build: psnode_generic_rk.hip compiles it a fourth time, on top of the pre-activation macros, with PSNODE_K0_RK_BUILD.  Its kernels
+// (generic_rk_kernel) take a launch-uniform Butcher tableau of up to four stages (psnode_rk_tableau_f32) as a third kernel argument and
+// apply it in the stage pass instead of the three built-in formulas; a.method is not read.  Its launcher is launch_generic_rk.
+#if defined(PSNODE_K0_RK_BUILD)
+#include "psnode_act.h"
+#define K0_ACT(v) pre_act_quad(v, ac)
+#define K0_ACT_PARAM , const ActDev& ac
+#define K0_ACT_ARG(x) , x
+#define K0_KERNEL generic_rk_kernel
+#define K0_KERNEL_PARAMS const IntegrateDev a, const ActPair act, const psnode_rk_tableau_f32 rk
+#define K0_RK_ARG , rk
+#elif defined(PSNODE_K0_PRE_BUILD)
 #include "psnode_act.h"
 #define K0_ACT(v) pre_act_quad(v, ac)
 #define K0_ACT_PARAM , const ActDev& ac
 #define K0_ACT_ARG(x) , x
 #define K0_KERNEL generic_pre_act_kernel
 #define K0_KERNEL_PARAMS const IntegrateDev a, const ActPair act
+#define K0_RK_ARG
 #elif defined(PSNODE_K0_ACT_BUILD)
 #include "psnode_act.h"
 #define K0_ACT(v) act_quad(v, ac)
@@ -47,12 +59,14 @@
 #define K0_ACT_ARG(x) , x
 #define K0_KERNEL generic_act_kernel
 #define K0_KERNEL_PARAMS const IntegrateDev a, const ActPair act
+#define K0_RK_ARG
 #else
 #define K0_ACT(v) elu_quad(v)
 #define K0_ACT_PARAM
 #define K0_ACT_ARG(x)
 #define K0_KERNEL generic_kernel
 #define K0_KERNEL_PARAMS const IntegrateDev a
+#define K0_RK_ARG
 #endif
 
 namespace psnode {
@@ -690,7 +704,17 @@ __global__ __launch_bounds__(NT) void K0_KERNEL(K0_KERNEL_PARAMS) {
     if constexpr (MODE == 0 && DAE) {       // the AE's a0 block: constant over the trajectory
         if (wv < tab_tiles(tae.dims[0])) cae = fold0<ML>(tae, lds, inAE, wv);
     }
+#ifdef PSNODE_K0_RK_BUILD
+    const int nstage = __builtin_amdgcn_readfirstlane(rk.stages);
+    // The coefficients go to LDS once: rows a[1][0], a[2][0..1], a[3][0..2], b[0..3] packed into ten floats of kbuf's fourth slot, which no
+    // stage pass writes (kbuf keeps k_0 .. k_{S - 2}, at most three slopes; nx >= 16).  Read back per stage pass as broadcasts: kept as kernel
+    // arguments they cost the time loop scalar registers it does not have.  (Every step's input barrier lies between this and the first read.)
+    static_assert(TB >= 10, "the tableau needs ten floats of the fourth kbuf slot (nx = x_dim * TB)");
+    float* rkt = kbuf + 3 * xd * TB;
+    if (tid < 10) rkt[tid] = tid < 6 ? (&rk.a[0][0])[tid == 0 ? 4 : (tid == 1 ? 8 : (tid == 2 ? 9 : 9 + tid))] : rk.b[tid - 6];
+#else
     const int nstage = a.method == PSNODE_EULER ? 1 : (a.method == PSNODE_MIDPOINT ? 2 : 4);
+#endif
     // look-ahead registers: clocks (threads < TB), the next step's event index, the next grid point's z | v
     float tc = 0.0f, tn = 0.0f;
     if (tid < TB) {
@@ -789,12 +813,32 @@ __global__ __launch_bounds__(NT) void K0_KERNEL(K0_KERNEL_PARAMS) {
             //      or, behind the last stage, the new state, its output row, the AE input and the look-ahead rows
             const int s_ = e - 1;
             const bool final_stage = s_ + 1 == nstage;
+#ifdef PSNODE_K0_RK_BUILD
+            // the tableau row this pass applies to k_0 .. k_s (uniform): a[s + 1][.] -- the next stage's argument -- or, behind the last
+            // stage, b.  kbuf keeps k_0 .. k_{S - 2}: at most three slopes.
+            auto rku = [](float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); };
+            const float* rrow = rkt + (final_stage ? 6 : (s_ == 0 ? 0 : (s_ == 1 ? 1 : 3)));
+            const float c0 = rku(rrow[0]);
+            const float c1 = s_ >= 1 ? rku(rrow[1]) : 0.0f;
+            const float c2 = s_ >= 2 ? rku(rrow[2]) : 0.0f;
+            const float c3 = s_ >= 3 ? rku(rrow[3]) : 0.0f;
+#endif
             for (int idx = tid; idx < nx; idx += NT) {
                 const int r = idx / TB, c = idx % TB;
                 const float h = dts[c];
                 const float x0 = xsrc[idx];
                 const float ks = lds[f + qi(r, c)];
                 float v;
+#ifdef PSNODE_K0_RK_BUILD
+                // v = x0 + h * sum_j c_j k_j in increasing j, zero coefficients skipped (psnode_rk_tableau_f32); k_s is this stage's slope
+                if (s_ < 3 && !final_stage) kbuf[s_ * nx + idx] = ks;
+                float acc = 0.0f;
+                if (c0 != 0.0f) acc += c0 * (s_ == 0 ? ks : kbuf[idx]);
+                if (c1 != 0.0f) acc += c1 * (s_ == 1 ? ks : kbuf[nx + idx]);
+                if (c2 != 0.0f) acc += c2 * (s_ == 2 ? ks : kbuf[2 * nx + idx]);
+                if (c3 != 0.0f) acc += c3 * ks;
+                v = x0 + h * acc;
+#else
                 if (a.method == PSNODE_EULER) {
                     v = x0 + h * ks;
                 } else if (a.method == PSNODE_MIDPOINT) {
@@ -807,6 +851,7 @@ __global__ __launch_bounds__(NT) void K0_KERNEL(K0_KERNEL_PARAMS) {
                     else if (s_ == 2) v = x0 + h * (k1 - kbuf[nx + idx] + ks);
                     else v = x0 + (k1 + 3.0f * (kbuf[nx + idx] + kbuf[2 * nx + idx]) + ks) * h * 0.125f;
                 }
+#endif
                 if (!final_stage) {
                     put_x(r, c, v);
                 } else {
@@ -1037,7 +1082,9 @@ size_t generic_plan(const IntegrateDev& a, bool dae, unsigned& mask) {
 
 #endif  // PSNODE_K0_ACT_BUILD
 
-#if defined(PSNODE_K0_PRE_BUILD)
+#if defined(PSNODE_K0_RK_BUILD)
+hipError_t launch_generic_rk(const IntegrateDev& a_in, bool dae, const ActPair& act, const psnode_rk_tableau_f32& rk, hipStream_t stream_) {
+#elif defined(PSNODE_K0_PRE_BUILD)
 hipError_t launch_generic_pre(const IntegrateDev& a_in, bool dae, const ActPair& act, hipStream_t stream_) {
 #elif defined(PSNODE_K0_ACT_BUILD)
 hipError_t launch_generic_act(const IntegrateDev& a_in, bool dae, const ActPair& act, hipStream_t stream_) {
@@ -1058,7 +1105,7 @@ hipError_t launch_generic(const IntegrateDev& a_in, bool dae, hipStream_t stream
     auto go = [&](auto kern) -> hipError_t {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_launch);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), lds_launch, stream_, a K0_ACT_ARG(act));
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), lds_launch, stream_, a K0_ACT_ARG(act) K0_RK_ARG);
         return hipGetLastError();
     };
     const int qm = generic_reg_mode(a, dae);

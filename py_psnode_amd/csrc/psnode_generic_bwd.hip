@@ -28,6 +28,30 @@
 // quad-row images on the register / streamed paths), and its VJP passes u next to h to the derivative (pre_grad1 / pre_grad_quad: from u
 // for SiLU / GELU / Mish, from h for the other kinds).  K5_PRE(...) is code of that build only; the u arguments of K5_DACT1 / K5_DACTQ are
 // dropped unread by the other two.
+//
+// Tableau build: psnode_generic_bwd_rk.hip compiles it a fourth time, on top of the pre-activation build's macros, with PSNODE_K5_RK_BUILD
+// (generic_backward_rk_kernel, launcher generic_backward_launch_rk).  Its stage loops (3a) / (3b) read the stage count and the coefficients
+// from a launch-uniform psnode_rk_tableau_f32, a third kernel argument, instead of rk_stages / rk_a / rk_b of a.method, which it does not
+// read.  K5_RK_* are the only tokens that differ; in the other three builds they expand to the source those loops always had.
+#if defined(PSNODE_K5_RK_BUILD)
+#define K5_RK_STAGES __builtin_amdgcn_readfirstlane(rk.stages)
+// the coefficients go to LDS once -- a[4][4] | b[4] in the fourth slot of `ks`, which holds k_0 .. k_{S - 2} only (nx >= 20 floats) -- and come
+// back as broadcast reads: indexed as kernel arguments they are scalar loads (and their waits) inside the stage loops
+#define K5_RK_INIT { static_assert(TP >= 20, "the tableau needs 20 floats of the fourth ks slot (nx = x_dim * TP)"); if (tid < 20) ks[3 * nx + tid] = tid < 16 ? rk.a[tid >> 2][tid & 3] : rk.b[tid - 16]; }
+#define K5_RK_U(v) __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)))
+#define K5_RK_A(s, j) K5_RK_U(ks[3 * nx + 4 * (s) + (j)])
+#define K5_RK_B(s) K5_RK_U(ks[3 * nx + 16 + (s)])
+// a coefficient that is exactly 0 is skipped (psnode_rk_tableau_f32)
+#define K5_RK_ADD(dst, coef, val) { const float c_ = coef; if (c_ != 0.0f) dst += c_ * val; }
+#define K5_RK_ADD_H(dst, h, coef, val) { const float c_ = coef; if (c_ != 0.0f) dst += h * c_ * val; }
+#else
+#define K5_RK_INIT
+#define K5_RK_STAGES rk_stages(a.method)
+#define K5_RK_A(s, j) rk_a(a.method, s, j)
+#define K5_RK_B(s) rk_b(a.method, s)
+#define K5_RK_ADD(dst, coef, val) dst += coef * val;
+#define K5_RK_ADD_H(dst, h, coef, val) dst += h * coef * val;
+#endif
 #if defined(PSNODE_K5_PRE_BUILD)
 #include "psnode_act.h"
 #define K5_ACT1(v) pre_act1(v, ac)
@@ -37,9 +61,15 @@
 #define K5_ACT_PARAM , const ActDev& ac, float* upre
 #define K5_ACT_ARG(x) , x, upre
 #define K5_PRE(...) __VA_ARGS__
+#if defined(PSNODE_K5_RK_BUILD)
+#define K5_KERNEL generic_backward_rk_kernel
+#define K5_KERNEL_PARAMS const GBwd a, const ActPair act, const psnode_rk_tableau_f32 rk
+#define K5_LAUNCH_ARG(x) , x, *c.rk
+#else
 #define K5_KERNEL generic_backward_pre_act_kernel
 #define K5_KERNEL_PARAMS const GBwd a, const ActPair act
 #define K5_LAUNCH_ARG(x) , x
+#endif
 #elif defined(PSNODE_K5_ACT_BUILD)
 #include "psnode_act.h"
 #define K5_ACT1(v) act1(v, ac)
@@ -638,7 +668,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(K5_TWO_WAVES
     const bool dae = a.dae != 0;
     const int xd = a.xd, zd = a.zd, vd = dae ? a.vd : 0, id = dae ? a.id : 0;
     const int nzv = zd + vd, ne = nzv + id, n = xd + ne;
-    const int S = rk_stages(a.method);
+    const int S = K5_RK_STAGES;
     const int nx = xd * TP;
     // teacher forcing: tx -- every DE step and every grid-point head reads the dataset row (xsrc), the adjoint of a step's start state is
     // dropped; ti -- the DE reads i_true[k], its algebraic adjoint is dropped and the event-time head feeds nothing
@@ -683,6 +713,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(K5_TWO_WAVES
     // loops over [rows][TB] tiles: idx -> (r, c)
 #define TILE_LOOP(rows) for (int idx = tid, r = tid / TB, c = tid % TB; idx < (rows) * TB; idx += NT, r = idx / TB, c = idx % TB)
 
+    K5_RK_INIT
     for (int e = tid; e < np_all; e += NT) gacc_l[e] = 0.0f;
     // global accumulators: tile-major slices (tmpart) for the MLPs off the staged path, the natural partial slice itself for a staged one
     float* tmg = a.tmpart + (size_t)blockIdx.x * (tm_total(a.de) + (a.dae ? tm_total(a.ae) : 0));
@@ -836,7 +867,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(K5_TWO_WAVES
         for (int s = 0; s < S; ++s) {
             TILE_LOOP(xd) {
                 float acc = 0.0f;
-                for (int j = 0; j < s; ++j) acc += rk_a(a.method, s, j) * ks[j * nx + r * TP + c];
+                for (int j = 0; j < s; ++j) K5_RK_ADD(acc, K5_RK_A(s, j), ks[j * nx + r * TP + c])
                 xst[s * nx + r * TP + c] = s == 0 ? x0[r * TP + c] : x0[r * TP + c] + dts[c] * acc;
             }
             __syncthreads();
@@ -854,7 +885,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(K5_TWO_WAVES
         TILE_LOOP(xd) {
             const float g1 = gxc[r * TP + c];
             gx0[r * TP + c] = g1;
-            for (int s = 0; s < S; ++s) gks[s * nx + r * TP + c] = dts[c] * rk_b(a.method, s) * g1;
+            for (int s = 0; s < S; ++s) gks[s * nx + r * TP + c] = dts[c] * K5_RK_B(s) * g1;
         }
         TILE_LOOP(ne) gext[r * TP + c] = 0.0f;
         __syncthreads();
@@ -873,7 +904,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(K5_TWO_WAVES
                 ga0s[r * TP + c] += gu[r * TP + c] - gu[(n + r) * TP + c];
                 if (r < xd) {
                     gx0[r * TP + c] += gs;
-                    for (int j = 0; j < s; ++j) gks[j * nx + r * TP + c] += dts[c] * rk_a(a.method, s, j) * gs;
+                    for (int j = 0; j < s; ++j) K5_RK_ADD_H(gks[j * nx + r * TP + c], dts[c], K5_RK_A(s, j), gs)
                 } else {
                     gext[(r - xd) * TP + c] += gs;
                 }
@@ -1103,7 +1134,11 @@ int bwd_fits_here(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, int xd, in
 
 }  // namespace
 
-#ifdef PSNODE_K5_PRE_BUILD
+#if defined(PSNODE_K5_RK_BUILD)
+int generic_bwd_fits_rk(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, int xd, int zd, int vd, int id) {
+    return bwd_fits_here(de, ae, xd, zd, vd, id);
+}
+#elif defined(PSNODE_K5_PRE_BUILD)
 int generic_bwd_fits_pre(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, int xd, int zd, int vd, int id) {
     return bwd_fits_here(de, ae, xd, zd, vd, id);
 }
@@ -1124,7 +1159,9 @@ int generic_bwd_fits(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, int xd,
 #endif  // PSNODE_K5_ACT_BUILD
 
 // launches pack (transpose), the backward kernel and the partial reduction (`act`: read by the activation builds only)
-#if defined(PSNODE_K5_PRE_BUILD)
+#if defined(PSNODE_K5_RK_BUILD)
+int generic_backward_launch_rk(
+#elif defined(PSNODE_K5_PRE_BUILD)
 int generic_backward_launch_pre(
 #elif defined(PSNODE_K5_ACT_BUILD)
 int generic_backward_launch_act(

@@ -2,6 +2,7 @@
 C ABI structs (include/psnode_hip.h), the device-side event table, workspaces.  Nothing here computes on the CPU and nothing here
 imports oracle/."""
 import ctypes
+import dataclasses
 import math
 import os
 import weakref
@@ -17,6 +18,81 @@ Layers = Sequence[Tuple[torch.Tensor, torch.Tensor]]
 
 METHOD_ID = {"euler": _lib.EULER, "midpoint": _lib.MIDPOINT, "rk4": _lib.RK4_38}
 STAGES = {"euler": 1, "midpoint": 2, "rk4": 4}      # right-hand-side evaluations per step
+
+
+@dataclasses.dataclass(frozen=True)
+class Tableau:
+    """An explicit Runge-Kutta method of 1..4 stages as a `method` of the generic route (K0 forward, K5 backward; psnode_rk_tableau_f32,
+    include/psnode_hip.h): a[s][j], j < s, is the coefficient of slope k_j in the argument of stage s, b[s] the weight of k_s in the update.
+    One step:  argument of stage s = x0 + h * sum_{j<s} a[s][j] k_j,  new state = x0 + h * sum_s b[s] k_s  (sums in increasing index, a
+    coefficient that is exactly 0 skipped).  `a` may be given as S rows of any length up to S (missing entries are zeros) and must be
+    strictly lower triangular.  Frozen and hashable; `order` is informative."""
+    name: str
+    a: tuple
+    b: tuple
+    order: int
+
+    def __post_init__(self):
+        try:
+            b = tuple(float(q) for q in self.b)
+            S = len(b)
+            rows = [tuple(float(q) for q in r) for r in self.a]
+        except TypeError as e:
+            raise ValueError(f"Tableau: a must be a sequence of rows and b a sequence of numbers ({e})") from e
+        if not 1 <= S <= 4:
+            raise ValueError(f"Tableau: {S} stages, supported 1..4")
+        if len(rows) != S or any(len(r) > S for r in rows):
+            raise ValueError(f"Tableau: a must have {S} rows of at most {S} entries, as b has {S}")
+        rows = [r + (0.0,) * (S - len(r)) for r in rows]
+        if not all(math.isfinite(q) for r in rows for q in r) or not all(math.isfinite(q) for q in b):
+            raise ValueError("Tableau: coefficients must be finite")
+        if any(rows[s][j] != 0.0 for s in range(S) for j in range(s, S)):
+            raise ValueError("Tableau: a must be strictly lower triangular (an explicit method)")
+        if abs(sum(b) - 1.0) > 1e-6:
+            raise ValueError(f"Tableau: sum(b) = {sum(b)!r}, must be 1 within 1e-6")
+        object.__setattr__(self, "a", tuple(rows))
+        object.__setattr__(self, "b", b)
+        object.__setattr__(self, "name", str(self.name))
+        object.__setattr__(self, "order", int(self.order))
+        object.__setattr__(self, "_c", tuple(sum(r) for r in rows))
+
+    @property
+    def stages(self) -> int:
+        return len(self.b)
+
+    @property
+    def c(self) -> tuple:
+        """The nodes c_s = sum_j a[s][j] (the callback walk evaluates stage s at t0 + c_s dt)."""
+        return self._c
+
+    def abi(self) -> "_lib.RkTableauF32":
+        t = _lib.RkTableauF32()
+        t.stages = self.stages
+        for s, r in enumerate(self.a):
+            for j, q in enumerate(r):
+                t.a[s][j] = q
+        for s, q in enumerate(self.b):
+            t.b[s] = q
+        return t
+
+    def __str__(self):
+        return self.name
+
+
+def method_info(method):
+    """(method id for the args struct, right-hand-side evaluations per step, Tableau | None) of a `method` of the generic route: one of the
+    built-in names, or a Tableau (whose calls go to the _rk entry points, which do not read the id)."""
+    if isinstance(method, Tableau):
+        return _lib.EULER, method.stages, method
+    return METHOD_ID[method], STAGES[method], None
+
+
+def builtin_method(method, what: str):
+    """(method id, stages) for the specialised kernels, which carry the three built-in formulas only: a Tableau is refused."""
+    if isinstance(method, Tableau):
+        raise _lib.UnsupportedShapeError(f"{what}: a Runge-Kutta tableau ({method.name}) runs on the generic kernels K0 / K5 only "
+                                         "(kernel 'auto' / 'generic', no saved rows); this entry point carries euler / midpoint / rk4")
+    return METHOD_ID[method], STAGES[method]
 
 
 KERNEL_ID = {"auto": _lib.KERNEL_AUTO, "generic": _lib.KERNEL_GENERIC, "mfma": _lib.KERNEL_MFMA, "wide": _lib.KERNEL_MFMA_WIDE,
@@ -99,18 +175,24 @@ def dae_acts(act):
     return (None, None) if act is None else tuple(act)
 
 
-def call_entry(lib, stem: str, args, acts, wp, wn, stream) -> int:
+def call_entry(lib, stem: str, args, acts, wp, wn, stream, tab=None) -> int:
     """The one place that picks an entry point of the generic-kernel families: psnode_<stem>_f32 when every act is None (ELU(1)),
-    psnode_<stem>_act_f32 with the acts' psnode_act_f32 otherwise.  stem: "ode_integrate", "dae_integrate", "ode_backward", "dae_backward"."""
+    psnode_<stem>_act_f32 with the acts' psnode_act_f32 otherwise.  stem: "ode_integrate", "dae_integrate", "ode_backward", "dae_backward".
+    tab (a Tableau): psnode_<stem>_rk_f32 with the acts and the tableau ("dae_backward": args is then a DaeBwdTfArgsF32)."""
     refs, non_elu = _act_refs(*acts)
+    if tab is not None:
+        return getattr(lib, f"psnode_{stem}_rk_f32")(ctypes.byref(args), *refs, ctypes.byref(tab.abi()), wp, wn, stream)
     if not non_elu:
         return getattr(lib, f"psnode_{stem}_f32")(ctypes.byref(args), wp, wn, stream)
     return getattr(lib, f"psnode_{stem}_act_f32")(ctypes.byref(args), *refs, wp, wn, stream)
 
 
-def entry_supported(lib, stem: str, args, acts) -> bool:
-    """psnode_<stem>_supported, or psnode_<stem>_act_supported when an act is not None (`call_entry`'s query)."""
+def entry_supported(lib, stem: str, args, acts, tab=None) -> bool:
+    """psnode_<stem>_supported, or psnode_<stem>_act_supported when an act is not None, or psnode_<stem>_rk_supported for a Tableau
+    (`call_entry`'s query)."""
     refs, non_elu = _act_refs(*acts)
+    if tab is not None:
+        return bool(getattr(lib, f"psnode_{stem}_rk_supported")(ctypes.byref(args), *refs, ctypes.byref(tab.abi())))
     if not non_elu:
         return bool(getattr(lib, f"psnode_{stem}_supported")(ctypes.byref(args)))
     return bool(getattr(lib, f"psnode_{stem}_act_supported")(ctypes.byref(args), *refs))

@@ -6,20 +6,30 @@ import ctypes
 import torch
 
 from .. import _lib
-from ._common import (KERNEL_ID, Layers, METHOD_ID, STAGES, _aligned16, _aligned_ptr, _bind_jumps, _check_saved, _empty, _f32_dev, _mlp, _pad_rows, _padded_hidden, _split_grads, _view, call_entry, dae_acts, entry_supported)
+from ._common import (KERNEL_ID, Layers, builtin_method, method_info, _aligned16, _aligned_ptr, _bind_jumps, _check_saved, _empty, _f32_dev, _mlp, _pad_rows, _padded_hidden, _split_grads, _view, call_entry, dae_acts, entry_supported)
 from .latent import latent_backward_wide, latent_wide_shape
 
-def dae_backward_supported(method: str, de_layers: Layers, ae_layers: Layers, x_dim, z_dim, v_dim, i_dim, act=None, kernel: str = "auto") -> bool:
+def dae_backward_supported(method, de_layers: Layers, ae_layers: Layers, x_dim, z_dim, v_dim, i_dim, act=None, kernel: str = "auto") -> bool:
     """act: None (both MLPs ELU(1)) or (de_act, ae_act); an activation other than ELU(1) is K5's alone.  kernel="generic": does K5 take
-    the shape (the question a teacher-forced call outside K7f's class asks)."""
+    the shape (the question a teacher-forced call outside K7f's class asks).  method a fused.Tableau: K5's tableau build only (kernel
+    "auto" / "generic"; it answers for its own LDS fit)."""
     if de_layers[0][0].device.type != "cuda" or max(len(de_layers), len(ae_layers)) > _lib.MAX_LAYERS:
         return False
     acts = dae_acts(act)
+    tab = method_info(method)[2]
+    if tab is not None:
+        tf = _lib.DaeBwdTfArgsF32()
+        b = tf.base
+        b.method, b.kernel = _lib.EULER, KERNEL_ID[kernel]
+        b.x_dim, b.z_dim, b.v_dim, b.i_dim, b.T, b.B = x_dim, z_dim, v_dim, i_dim, 2, 1
+        dev = de_layers[0][0].device
+        b.de, b.ae = _mlp(de_layers, dev, "de", []), _mlp(ae_layers, dev, "ae", [])
+        return entry_supported(_lib.load(), "dae_backward", tf, acts, tab)
     non_elu = any(q is not None for q in acts)
     if not non_elu and kernel != "generic" and latent_wide_shape(de_layers, ae_layers, x_dim, z_dim, v_dim, i_dim):
         return True                          # K3w (saving) + K9w + library GEMMs
     a = _lib.DaeBwdArgsF32()
-    a.method = METHOD_ID[method]
+    a.method = method_info(method)[0]
     a.x_dim, a.z_dim, a.v_dim, a.i_dim, a.T, a.B = x_dim, z_dim, v_dim, i_dim, 2, 1
     dev = de_layers[0][0].device
     a.de, a.ae = _mlp(de_layers, dev, "de", []), _mlp(ae_layers, dev, "ae", [])
@@ -38,7 +48,7 @@ def dae_backward_wide_supported(method: str, de_layers: Layers, ae_layers: Layer
         return False
     lib = _lib.load()
     a = _lib.DaeBwdWideArgsF32()
-    a.method, a.x_dim, a.z_dim, a.v_dim, a.i_dim, a.T, a.B = METHOD_ID[method], x_dim, z_dim, v_dim, i_dim, 2, 1
+    a.method, a.x_dim, a.z_dim, a.v_dim, a.i_dim, a.T, a.B = builtin_method(method, "dae_backward_wide_supported")[0], x_dim, z_dim, v_dim, i_dim, 2, 1
     dev = de_layers[0][0].device
     a.de, a.ae = _mlp(de_layers, dev, "de", []), _mlp(ae_layers, dev, "ae", [])
     return bool(lib.psnode_dae_backward_wide_supported(ctypes.byref(a)))
@@ -63,7 +73,7 @@ def dae_backward_wide(method: str, de_layers: Layers, ae_layers: Layers, t, z, v
     n = xd + ne
     Hr = de_layers[0][0].shape[0]                       # the MLPs' width; H = the width the kernel runs them at (zero-padded rows)
     H = _padded_hidden(Hr)
-    S = STAGES[method]
+    method_id, S = builtin_method(method, "dae_backward_wide")
     if saved is None and B > 16:
         # the recompute form stores the AE head's rows of EVERY grid point (6 x [T,B,H] + [T,B,16] + the u rows of K7h): a very long grid on
         # a full card goes through in batch slices (a saved-activation call is not sliced: its forward already held ~S times as much)
@@ -76,7 +86,7 @@ def dae_backward_wide(method: str, de_layers: Layers, ae_layers: Layers, t, z, v
                                              event_idx, z_jump, v_jump, x_true, i_true)
     keep: list = []
     a = _lib.DaeBwdWideArgsF32()
-    a.method, a.x_dim, a.z_dim, a.v_dim, a.i_dim, a.T, a.B = METHOD_ID[method], xd, zd, vd, idim, T, B
+    a.method, a.x_dim, a.z_dim, a.v_dim, a.i_dim, a.T, a.B = method_id, xd, zd, vd, idim, T, B
     a.de, a.ae = _mlp(de_layers, dev, "de", keep), _mlp(ae_layers, dev, "ae", keep)
     a.t, a.z, a.v = _view(t, dev, "t", keep), _view(z, dev, "z", keep), _view(v, dev, "v", keep)
     a0 = _f32_dev(all_initial, dev, "all_initial").contiguous()
@@ -293,13 +303,14 @@ def _dae_backward_wide_sliced(step, method, de_layers, ae_layers, t, z, v, all_i
     return {k: (val if k in ("de", "ae") else (torch.cat(val, cat_dim[k]) if val is not None else None)) for k, val in out.items()}
 
 
-def dae_backward(method: str, de_layers: Layers, ae_layers: Layers, t, z, v, all_initial, xs, is_, grad_xs, grad_is, event_idx=None,
+def dae_backward(method, de_layers: Layers, ae_layers: Layers, t, z, v, all_initial, xs, is_, grad_xs, grad_is, event_idx=None,
                  z_jump=None, v_jump=None, kernel: str = "auto", saved=None, act=None):
     """Backward pass of `dae_integrate` (no teacher forcing): the one-launch K7f (`dae_backward_wide`) for the DAE_01 shape class at
     hidden <= 128, K9 / K8 / K9w for the latent shapes of the direct_encode models, else the generic backward kernel (K5);
     `kernel` = "auto" | "mfma" | "generic" | "wide" (K7f or an error).
     saved = what `dae_integrate(save=True)` returned (read by K7f, K9 and K9w; K8 / K5 recompute and refuse them).
     act: None (both MLPs ELU(1)) or (de_act, ae_act); an activation other than ELU(1) runs on K5 only (kernel "auto" / "generic").
+    method: "euler" | "midpoint" | "rk4", or a fused.Tableau -- K5 only (kernel "auto" / "generic", no saved rows).
     Returns dict(x_init, z, v, z_jump, v_jump, all_initial, de=[...], ae=[...]) of gradients."""
     T, B, xd = xs.shape
     zd, vd, idim = z.shape[-1], v.shape[-1], is_.shape[-1]
@@ -309,6 +320,13 @@ def dae_backward(method: str, de_layers: Layers, ae_layers: Layers, t, z, v, all
             raise _lib.UnsupportedShapeError("dae_backward: an activation other than ELU(alpha=1) runs on the generic backward K5 only "
                                              "(kernel 'auto' / 'generic', no saved rows)")
         kernel = "generic"
+    tab = method_info(method)[2]
+    if tab is not None:
+        if kernel not in ("auto", "generic") or saved is not None:
+            raise _lib.UnsupportedShapeError(f"dae_backward: a Runge-Kutta tableau ({tab.name}) runs on the generic backward K5 only "
+                                             "(kernel 'auto' / 'generic', no saved rows)")
+        return _dae_backward_entry(method, de_layers, ae_layers, t, z, v, all_initial, xs, is_, grad_xs, grad_is, event_idx, z_jump, v_jump,
+                                   kernel, None, acts)
     if kernel in ("wide", "mfma") and T < 2 and len(de_layers) == 4:
         kernel = "generic"       # no step to sweep: K7f has no head-only form, K5 handles the single grid point
     if saved is not None and latent_wide_shape(de_layers, ae_layers, xd, zd, vd, idim):
@@ -322,7 +340,7 @@ def dae_backward(method: str, de_layers: Layers, ae_layers: Layers, t, z, v, all
                                kernel, saved, acts)
 
 
-def dae_backward_tf(method: str, de_layers: Layers, ae_layers: Layers, t, z, v, all_initial, xs, is_, grad_xs, grad_is, event_idx=None,
+def dae_backward_tf(method, de_layers: Layers, ae_layers: Layers, t, z, v, all_initial, xs, is_, grad_xs, grad_is, event_idx=None,
                     z_jump=None, v_jump=None, kernel: str = "auto", x_true=None, i_true=None):
     """Backward of a teacher-forced `dae_integrate` (input_true_x / input_true_i, my_solvers.py:111-121) on the generic backward K5
     (psnode_dae_backward_tf_f32): every shape K5 takes untied.  x_true [T,B,x_dim] / i_true [T,B,i_dim]: the dataset rows the forward call
@@ -349,7 +367,8 @@ def _dae_backward_entry(method, de_layers, ae_layers, t, z, v, all_initial, xs, 
     zd, vd, idim = z.shape[-1], v.shape[-1], is_.shape[-1]
     keep: list = []
     tf = None
-    if x_true is not None or i_true is not None:
+    method_id, S, tab = method_info(method)
+    if x_true is not None or i_true is not None or tab is not None:      # (the _rk entry point takes the tf struct, flags 0 included)
         tf = _lib.DaeBwdTfArgsF32()
         xt_c = _f32_dev(x_true, dev, "x_true").contiguous() if x_true is not None else None
         it_c = _f32_dev(i_true, dev, "i_true").contiguous() if i_true is not None else None
@@ -358,7 +377,7 @@ def _dae_backward_entry(method, de_layers, ae_layers, t, z, v, all_initial, xs, 
         tf.x_true = xt_c.data_ptr() if xt_c is not None else None
         tf.i_true = it_c.data_ptr() if it_c is not None else None
     a = tf.base if tf is not None else _lib.DaeBwdArgsF32()      # (tf.base: a view of the struct's own memory)
-    a.method = METHOD_ID[method]
+    a.method = method_id
     a.kernel = KERNEL_ID[kernel]
     a.x_dim, a.z_dim, a.v_dim, a.i_dim, a.T, a.B = xd, zd, vd, idim, T, B
     a.de, a.ae = _mlp(de_layers, dev, "de", keep), _mlp(ae_layers, dev, "ae", keep)
@@ -398,7 +417,7 @@ def _dae_backward_entry(method, de_layers, ae_layers, t, z, v, all_initial, xs, 
         if saved is not None and T >= 2:        # (K9 reads them; the C side refuses them for the kernels that recompute)
             s_act, s_xst, s_ae, s_ev, s_evi = saved
             L = len(de_layers) - 1
-            _check_saved(s_act, s_xst, T, B, xd, STAGES[method], L, dev)
+            _check_saved(s_act, s_xst, T, B, xd, S, L, dev)
             if tuple(s_ae.shape[:3]) != (L, T, B) or s_ae.shape[-1] != s_act.shape[-1] or not s_ae.is_contiguous() or s_ae.device != dev:
                 raise ValueError("saved AE activations do not belong to this call (shape / device)")
             keep += [s_act, s_xst, s_ae, s_ev, s_evi]
@@ -408,14 +427,20 @@ def _dae_backward_entry(method, de_layers, ae_layers, t, z, v, all_initial, xs, 
                 if s_ev is None or s_evi is None or s_ev.shape[0] != n_ev_ or s_ev.shape[2] != B or s_evi.shape[:2] != (n_ev_, B):
                     raise ValueError("saved event activations do not belong to this call (shape)")
                 a.saved_ev_act, a.saved_ev_i = s_ev.data_ptr(), s_evi.data_ptr()
-        if tf is not None:
+        if tab is not None:
+            arefs = [ctypes.byref(q.abi()) if q is not None else None for q in acts]
+            nbytes = lib.psnode_dae_backward_rk_workspace_bytes(ctypes.byref(tf), *arefs, ctypes.byref(tab.abi()))
+        elif tf is not None:
             nbytes = lib.psnode_dae_backward_tf_workspace_bytes(ctypes.byref(tf))
         else:
             nbytes = lib.psnode_dae_backward_workspace_bytes(ctypes.byref(a))
         ws = _empty(nbytes + 256, dtype=torch.uint8, device=dev)
         wp, wn = _aligned_ptr(ws)
         st = torch.cuda.current_stream(dev).cuda_stream
-        rc = lib.psnode_dae_backward_tf_f32(ctypes.byref(tf), wp, wn, st) if tf is not None else call_entry(lib, "dae_backward", a, acts, wp, wn, st)
-    _lib.check(rc, "psnode_dae_backward_tf_f32" if tf is not None else "psnode_dae_backward_f32")
+        if tab is not None:
+            rc = call_entry(lib, "dae_backward", tf, acts, wp, wn, st, tab)
+        else:
+            rc = lib.psnode_dae_backward_tf_f32(ctypes.byref(tf), wp, wn, st) if tf is not None else call_entry(lib, "dae_backward", a, acts, wp, wn, st)
+    _lib.check(rc, "psnode_dae_backward_rk_f32" if tab is not None else ("psnode_dae_backward_tf_f32" if tf is not None else "psnode_dae_backward_f32"))
     g["de"], g["ae"] = _split_grads(gde, de_layers), _split_grads(gae, ae_layers)
     return g

@@ -5,30 +5,35 @@ import ctypes
 import torch
 
 from .. import _lib
-from ._common import (KERNEL_ID, Layers, METHOD_ID, STAGES, _aligned16, _aligned_ptr, _bind_jumps, _check_saved, _empty, _f32_dev, _mlp, _split_grads, _view, call_entry, entry_supported)
+from ._common import (KERNEL_ID, Layers, method_info, _aligned16, _aligned_ptr, _bind_jumps, _check_saved, _empty, _f32_dev, _mlp, _split_grads, _view, call_entry, entry_supported)
 from .latent import latent_backward_wide, latent_wide_shape
 
 def _bwd_args(method, de_layers, x_dim, z_dim, T, B, dev, keep, kernel="auto"):
     a = _lib.OdeBwdArgsF32()
-    a.method = METHOD_ID[method]
+    a.method = method_info(method)[0]
     a.kernel = KERNEL_ID[kernel]
     a.x_dim, a.z_dim, a.T, a.B = x_dim, z_dim, T, B
     a.de = _mlp(de_layers, dev, "de", keep)
     return a
 
 
-def ode_backward_supported(method: str, de_layers: Layers, x_dim: int, z_dim: int, kernel: str = "auto", act=None) -> bool:
+def ode_backward_supported(method, de_layers: Layers, x_dim: int, z_dim: int, kernel: str = "auto", act=None) -> bool:
     """True if a fused backward kernel covers this shape: the MFMA class (3n->64->64->64->x, x<=8, z<=4) or any MLP whose
-    activations and parameter gradients fit the LDS (generic backward).  act (fused.Act) other than None = ELU(1): K5 only."""
+    activations and parameter gradients fit the LDS (generic backward).  act (fused.Act) other than None = ELU(1): K5 only.
+    method a fused.Tableau: K5's tableau build only (kernel "auto" / "generic"; it answers for its own LDS fit)."""
     if de_layers[0][0].device.type != "cuda" or len(de_layers) > _lib.MAX_LAYERS:
         return False
+    tab = method_info(method)[2]
+    if tab is not None:
+        a = _bwd_args(method, de_layers, x_dim, z_dim, 2, 1, de_layers[0][0].device, [], kernel)
+        return entry_supported(_lib.load(), "ode_backward", a, (act,), tab)
     if act is None and kernel in ("auto", "mfma") and latent_wide_shape(de_layers, None, x_dim, z_dim):
         return True                          # K3w (saving) + K9w + library GEMMs
     a = _bwd_args(method, de_layers, x_dim, z_dim, 2, 1, de_layers[0][0].device, [], kernel)
     return entry_supported(_lib.load(), "ode_backward", a, (act,))
 
 
-def ode_backward(method: str, de_layers: Layers, t, z, all_initial, xs, grad_xs, event_idx=None, z_jump=None, need_grad_z: bool = True,
+def ode_backward(method, de_layers: Layers, t, z, all_initial, xs, grad_xs, event_idx=None, z_jump=None, need_grad_z: bool = True,
                  kernel: str = "auto", saved=None, input_true_x: bool = False, need_grad_zj: bool = True, act=None):
     """Backward pass of `ode_integrate` in one launch.  `saved` = what `ode_integrate(save=True)` returned next to
     xs: K4f then skips the recompute of the stage evaluations.  input_true_x: backward of a teacher-forced call (my_solvers.py:72-74) --
@@ -39,6 +44,7 @@ def ode_backward(method: str, de_layers: Layers, t, z, all_initial, xs, grad_xs,
     kernel: "wave" = K4x (one wave per 4 trajectories; hidden 33..64, saved rows), "wide" / "tile" = K4f; "auto" picks between them.
     act: the hidden layers' activation (fused.Act); None = ELU(1).  Any other runs on the generic backward K5 only (kernel "auto" /
     "generic", no saved rows, no teacher forcing).
+    method: "euler" | "midpoint" | "rk4", or a fused.Tableau -- K5 only (kernel "auto" / "generic", no saved rows).
     Returns (grad_x0 [B,xd], grad_z [T,B,zd] | None, grad_z_jump | None, grad_all_initial [B,n], [grad W1, b1, ..., W4, b4])."""
     lib = _lib.load()
     dev = xs.device
@@ -49,6 +55,10 @@ def ode_backward(method: str, de_layers: Layers, t, z, all_initial, xs, grad_xs,
     if act is not None and (kernel not in ("auto", "generic") or saved is not None or input_true_x):
         raise _lib.UnsupportedShapeError("ode_backward: an activation other than ELU(alpha=1) runs on the generic backward K5 only "
                                          "(kernel 'auto' / 'generic', no saved rows, no teacher forcing)")
+    method_id, S, tab = method_info(method)
+    if tab is not None and (kernel not in ("auto", "generic") or saved is not None):
+        raise _lib.UnsupportedShapeError(f"ode_backward: a Runge-Kutta tableau ({tab.name}) runs on the generic backward K5 only "
+                                         "(kernel 'auto' / 'generic', no saved rows)")
     if saved is not None and not input_true_x and latent_wide_shape(de_layers, None, xd, zd):
         g = latent_backward_wide(method, de_layers, None, t, z, None, all_initial, xs, None, grad_xs, None, event_idx=event_idx,
                                  z_jump=z_jump, saved=saved, need_grad_z=need_grad_z)
@@ -84,12 +94,12 @@ def ode_backward(method: str, de_layers: Layers, t, z, all_initial, xs, grad_xs,
         a.grad_x0, a.grad_all_initial, a.grad_params = gx0.data_ptr(), ga0.data_ptr(), gpar.data_ptr()
         a.grad_z = gz.data_ptr() if gz is not None else None
         if saved is not None and T >= 2:
-            _check_saved(saved[0], saved[1], T, B, xd, STAGES[method], len(de_layers) - 1, dev)
+            _check_saved(saved[0], saved[1], T, B, xd, S, len(de_layers) - 1, dev)
             keep += [saved[0], saved[1]]
             a.saved_act, a.saved_xstage = saved[0].data_ptr(), saved[1].data_ptr()
         nbytes = lib.psnode_ode_backward_workspace_bytes(ctypes.byref(a))
         ws = _empty(nbytes + 256, dtype=torch.uint8, device=dev)
         wp, wn = _aligned_ptr(ws)
-        rc = call_entry(lib, "ode_backward", a, (act,), wp, wn, torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(rc, "psnode_ode_backward_f32")
+        rc = call_entry(lib, "ode_backward", a, (act,), wp, wn, torch.cuda.current_stream(dev).cuda_stream, tab)
+    _lib.check(rc, "psnode_ode_backward_rk_f32" if tab is not None else "psnode_ode_backward_f32")
     return gx0, gz, gzj, ga0, _split_grads(gpar, de_layers)

@@ -5,7 +5,7 @@ import ctypes
 import torch
 
 from .. import _lib
-from ._common import Layers, METHOD_ID, _aligned_ptr, _check_jump, _empty, _f32_dev, _jump, _mlp, _view, event_table
+from ._common import Layers, builtin_method, _aligned_ptr, _check_jump, _empty, _f32_dev, _jump, _mlp, _view, event_table
 
 def ode_encoded_supported(x_encoder: Layers, z_encoder: Layers, x_decoder: Layers, de_layers: Layers) -> bool:
     """Shapes of the fused direct_encode ODE forward (psnode_ode_encoded_integrate_f32): every MLP 2 layers with hidden 16."""
@@ -32,7 +32,7 @@ def ode_encoded_integrate(method: str, x_encoder: Layers, z_encoder: Layers, x_d
     dev = x.device
     keep: list = []
     a = _lib.OdeEncodedArgsF32()
-    a.method = METHOD_ID[method]
+    a.method = builtin_method(method, "ode_encoded_integrate")[0]
     B, T, xd = x.shape
     zd = z.shape[-1]
     if t.shape[:2] != (B, T) or z.shape[:2] != (B, T):
@@ -116,7 +116,7 @@ def dae_encoded_integrate(method: str, x_encoder, z_encoder, v_encoder, i_encode
         zd = 0
     mlps = (x_encoder, z_encoder, v_encoder, i_encoder, x_decoder, i_decoder, de_layers, ae_layers)
     a = _dae_encoded_args(mlps, dev, keep, xd, zd, vd, idim)
-    a.method, a.T, a.B = METHOD_ID[method], T, B
+    a.method, a.T, a.B = builtin_method(method, "dae_encoded_integrate")[0], T, B
     if not lib.psnode_dae_encoded_supported(ctypes.byref(a)):
         raise _lib.UnsupportedShapeError("dae_encoded_integrate: needs encoders in->64->64 (x <= 16, z | v | i <= 8 wide), decoders "
                                          "64->64->out, de 12H|9H->64->64, ae 7H|5H->64->64")

@@ -6,7 +6,7 @@ from typing import Optional
 import torch
 
 from .. import _lib
-from ._common import (KERNEL_ID, Layers, METHOD_ID, STAGES, _aligned16, _aligned_ptr, _bind_events, _check_tb, _empty, _f32_dev, _mlp, _view, _workspace, call_entry, dae_acts)
+from ._common import (KERNEL_ID, Layers, Tableau, builtin_method, method_info, _aligned16, _aligned_ptr, _bind_events, _check_tb, _empty, _f32_dev, _mlp, _view, _workspace, call_entry, dae_acts)
 
 _MFMA_CLASSES = ("MFMA integrators K1 / K2 cover `in -> H -> H -> H -> out` ELU-MLPs with H <= 128 (any x_dim <= 16 for the ODE, "
                  "x_dim <= 8 and z+v+i <= 8 for the DAE), and -- weights streamed from L2 -- the ODE up to H = 192 at any x_dim <= 16 and "
@@ -49,11 +49,20 @@ def _act_route_ok(what: str, non_elu: bool, kernel: str, save: bool):
                                          f"(kernel 'auto' / 'generic', no save=True); got kernel={kernel!r}, save={save}")
 
 
-def ode_integrate(method: str, de_layers: Layers, t, x, z, all_initial, event_t=None, z_jump=None,
+def _rk_route_ok(what: str, tab, kernel: str, save: bool):
+    """A Runge-Kutta tableau runs on the generic kernels only."""
+    if tab is not None and (kernel not in ("auto", "generic") or save):
+        raise _lib.UnsupportedShapeError(f"{what}: a Runge-Kutta tableau ({tab.name}) runs on the generic kernel K0 only "
+                                         f"(kernel 'auto' / 'generic', no save=True); got kernel={kernel!r}, save={save}")
+
+
+def ode_integrate(method, de_layers: Layers, t, x, z, all_initial, event_t=None, z_jump=None,
                   input_true_x: bool = False, kernel: str = "auto", event_idx: Optional[torch.Tensor] = None,
                   check_events: bool = False, out: Optional[torch.Tensor] = None, save: bool = False, act=None):
     """Fused integrate_ODE (replaces my_solvers.py:52-80 + my_fixed_grid.py + DE_Func.forward).
 
+    method: "euler" | "midpoint" | "rk4" (the 3/8 rule), or a fused.Tableau -- any explicit Runge-Kutta method of up to four stages, on
+    the generic kernel K0 only (kernel "auto" / "generic"; save=True is refused).
     act: the hidden layers' activation (fused.Act, from `sequential_mlp`); None = ELU(1).  Any other runs on the generic kernel K0 only
     (kernel "auto" / "generic"; save=True is refused).
 
@@ -70,6 +79,8 @@ def ode_integrate(method: str, de_layers: Layers, t, x, z, all_initial, event_t=
     if dev.type != "cuda":
         raise ValueError("fused integrator needs tensors on a HIP device")
     _act_route_ok("ode_integrate", act is not None, kernel, save)
+    method_id, S, tab = method_info(method)
+    _rk_route_ok("ode_integrate", tab, kernel, save)
     T, B, xd = t.shape[0], x.shape[1], x.shape[2]
     if x.shape[0] < (T if input_true_x else 1):
         raise ValueError("x has fewer grid points than t")
@@ -78,7 +89,7 @@ def ode_integrate(method: str, de_layers: Layers, t, x, z, all_initial, event_t=
     _check_tb("z", z, T, B)
     keep: list = []
     a = _lib.OdeArgsF32()
-    a.method = METHOD_ID[method]
+    a.method = method_id
     a.kernel = KERNEL_ID[kernel]
     a.flags = _lib.FLAG_INPUT_TRUE_X if input_true_x else 0
     a.x_dim, a.z_dim, a.T, a.B = xd, zd, T, B
@@ -105,7 +116,6 @@ def ode_integrate(method: str, de_layers: Layers, t, x, z, all_initial, event_t=
             Hp = lib.psnode_ode_save_hidden(ctypes.byref(a))
             if Hp <= 0:
                 raise _lib.UnsupportedShapeError("ode_integrate(save=True): the MFMA integrator K1 does not take this shape")
-            S = STAGES[method]
             L = len(de_layers) - 1       # hidden layers: 3 for the no_encode MLPs (K1), 1 for the latent ones at hidden 64 (K3c)
             saved = (_empty((max(T - 1, 0), S, L, B, Hp), dtype=torch.float32, device=dev),
                      _empty((max(T - 1, 0), S, B, xd), dtype=torch.float32, device=dev))
@@ -113,31 +123,33 @@ def ode_integrate(method: str, de_layers: Layers, t, x, z, all_initial, event_t=
                 a.save_act, a.save_xstage = saved[0].data_ptr(), saved[1].data_ptr()
         ws = _workspace(lib, a.de, None, dev)
         wp, wn = _aligned_ptr(ws)
-        rc = call_entry(lib, "ode_integrate", a, (act,), wp, wn, torch.cuda.current_stream(dev).cuda_stream)
-    _mfma_miss(rc, kernel, "psnode_ode_integrate_f32", de_layers)
-    _lib.check(rc, "psnode_ode_integrate_f32")
-    if kernel == "auto" and act is None:
+        rc = call_entry(lib, "ode_integrate", a, (act,), wp, wn, torch.cuda.current_stream(dev).cuda_stream, tab)
+    entry = "psnode_ode_integrate_rk_f32" if tab is not None else "psnode_ode_integrate_f32"
+    _mfma_miss(rc, kernel, entry, de_layers)
+    _lib.check(rc, entry)
+    if kernel == "auto" and act is None and tab is None:
         _note_k0(lib, a, False, de_layers)
     # the stream-ordered caching allocator keeps `keep`/`ws` storage valid until the kernel has run
     return (out, saved) if save else out
 
 
-def ode_save_hidden(method: str, de_layers: Layers, x_dim: int, z_dim: int, kernel: str = "auto") -> int:
-    """Row width of the saved activations if the forward for these dims can save them (K1 proper), else 0."""
-    if de_layers[0][0].device.type != "cuda" or len(de_layers) > _lib.MAX_LAYERS:
+def ode_save_hidden(method, de_layers: Layers, x_dim: int, z_dim: int, kernel: str = "auto") -> int:
+    """Row width of the saved activations if the forward for these dims can save them (K1 proper), else 0 (always for a Tableau)."""
+    if isinstance(method, Tableau) or de_layers[0][0].device.type != "cuda" or len(de_layers) > _lib.MAX_LAYERS:
         return 0
     lib = _lib.load()
     a = _lib.OdeArgsF32()
-    a.method, a.kernel, a.x_dim, a.z_dim, a.T, a.B = METHOD_ID[method], KERNEL_ID[kernel], x_dim, z_dim, 2, 1
+    a.method, a.kernel, a.x_dim, a.z_dim, a.T, a.B = builtin_method(method, "ode_save_hidden")[0], KERNEL_ID[kernel], x_dim, z_dim, 2, 1
     a.de = _mlp(de_layers, de_layers[0][0].device, "de", [])
     return int(lib.psnode_ode_save_hidden(ctypes.byref(a)))
 
 
-def dae_integrate(method: str, de_layers: Layers, ae_layers: Layers, x_init, t, x, z, v, i, all_initial,
+def dae_integrate(method, de_layers: Layers, ae_layers: Layers, x_init, t, x, z, v, i, all_initial,
                   event_t=None, z_jump=None, v_jump=None, input_true_x: bool = False, input_true_i: bool = False,
                   kernel: str = "auto", event_idx: Optional[torch.Tensor] = None, check_events: bool = False, out=None,
                   save: bool = False, act=None):
     """Fused integrate_DAE (replaces my_solvers.py:82-131 + step functions + DE_Func/AE_Func forwards).
+    method: "euler" | "midpoint" | "rk4", or a fused.Tableau (generic kernel K0 only: kernel "auto" / "generic"; save=True is refused).
     act: None (both MLPs ELU(1)) or (de_act, ae_act), each a fused.Act or None = ELU(1); an activation other than ELU(1) runs on the
     generic kernel K0 only (kernel "auto" / "generic"; save=True is refused).
     `out` = (xs, is) contiguous [T,B,xd] / [T,B,id] tensors to write into (time-chunked launches).
@@ -151,6 +163,8 @@ def dae_integrate(method: str, de_layers: Layers, ae_layers: Layers, x_init, t, 
     acts = dae_acts(act)
     non_elu = any(q is not None for q in acts)
     _act_route_ok("dae_integrate", non_elu, kernel, save)
+    method_id, S, tab = method_info(method)
+    _rk_route_ok("dae_integrate", tab, kernel, save)
     T, B = t.shape[0], t.shape[1]
     xd, zd, vd, idim = x_init.shape[-1], z.shape[-1], v.shape[-1], i.shape[-1]
     if x_init.dim() != 2 or x_init.shape[0] != B:
@@ -164,7 +178,7 @@ def dae_integrate(method: str, de_layers: Layers, ae_layers: Layers, x_init, t, 
         _check_tb("i", i, T, B)
     keep: list = []
     a = _lib.DaeArgsF32()
-    a.method = METHOD_ID[method]
+    a.method = method_id
     a.kernel = KERNEL_ID[kernel]
     a.flags = (_lib.FLAG_INPUT_TRUE_X if input_true_x else 0) | (_lib.FLAG_INPUT_TRUE_I if input_true_i else 0)
     a.x_dim, a.z_dim, a.v_dim, a.i_dim, a.T, a.B = xd, zd, vd, idim, T, B
@@ -200,7 +214,6 @@ def dae_integrate(method: str, de_layers: Layers, ae_layers: Layers, x_init, t, 
             Hp = lib.psnode_dae_save_hidden(ctypes.byref(a))
             if Hp <= 0:
                 raise _lib.UnsupportedShapeError("dae_integrate(save=True): the MFMA integrator K2 does not take this shape")
-            S = STAGES[method]
             f32 = dict(dtype=torch.float32, device=dev)
             n_ev = (z_jump if z_jump is not None else v_jump).shape[1] if event_idx is not None else 0
             L = len(de_layers) - 1       # hidden layers: 3 (K2), 1 for the latent shapes at hidden 64 (K3c; i0 rows are then i_dim wide)
@@ -217,22 +230,23 @@ def dae_integrate(method: str, de_layers: Layers, ae_layers: Layers, x_init, t, 
                 a.save_ev_act, a.save_ev_i = saved[3].data_ptr(), saved[4].data_ptr()
         ws = _workspace(lib, a.de, a.ae, dev)
         wp, wn = _aligned_ptr(ws)
-        rc = call_entry(lib, "dae_integrate", a, acts, wp, wn, torch.cuda.current_stream(dev).cuda_stream)
-    _mfma_miss(rc, kernel, "psnode_dae_integrate_f32", de_layers)
-    _lib.check(rc, "psnode_dae_integrate_f32")
-    if kernel == "auto" and not non_elu:
+        rc = call_entry(lib, "dae_integrate", a, acts, wp, wn, torch.cuda.current_stream(dev).cuda_stream, tab)
+    entry = "psnode_dae_integrate_rk_f32" if tab is not None else "psnode_dae_integrate_f32"
+    _mfma_miss(rc, kernel, entry, de_layers)
+    _lib.check(rc, entry)
+    if kernel == "auto" and not non_elu and tab is None:
         _note_k0(lib, a, True, de_layers)
     return (xs, is_, saved) if save else (xs, is_)
 
 
-def dae_save_hidden(method: str, de_layers: Layers, ae_layers: Layers, x_dim: int, z_dim: int, v_dim: int, i_dim: int,
+def dae_save_hidden(method, de_layers: Layers, ae_layers: Layers, x_dim: int, z_dim: int, v_dim: int, i_dim: int,
                     kernel: str = "auto") -> int:
-    """Row width of the saved activations if the forward for these dims can save them (K2 proper), else 0."""
-    if de_layers[0][0].device.type != "cuda" or max(len(de_layers), len(ae_layers)) > _lib.MAX_LAYERS:
+    """Row width of the saved activations if the forward for these dims can save them (K2 proper), else 0 (always for a Tableau)."""
+    if isinstance(method, Tableau) or de_layers[0][0].device.type != "cuda" or max(len(de_layers), len(ae_layers)) > _lib.MAX_LAYERS:
         return 0
     lib = _lib.load()
     a = _lib.DaeArgsF32()
-    a.method, a.kernel, a.x_dim, a.z_dim, a.v_dim, a.i_dim, a.T, a.B = METHOD_ID[method], KERNEL_ID[kernel], x_dim, z_dim, v_dim, i_dim, 2, 1
+    a.method, a.kernel, a.x_dim, a.z_dim, a.v_dim, a.i_dim, a.T, a.B = builtin_method(method, "dae_save_hidden")[0], KERNEL_ID[kernel], x_dim, z_dim, v_dim, i_dim, 2, 1
     dev = de_layers[0][0].device
     a.de, a.ae = _mlp(de_layers, dev, "de", []), _mlp(ae_layers, dev, "ae", [])
     return int(lib.psnode_dae_save_hidden(ctypes.byref(a)))

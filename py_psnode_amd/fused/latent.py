@@ -7,7 +7,7 @@ from typing import Optional
 import torch
 
 from .. import _lib
-from ._common import Layers, METHOD_ID, STAGES, _aligned_ptr, _empty, _f32_dev, _gemm_tn, _mlp, _view, gemm_tn
+from ._common import Layers, builtin_method, _aligned_ptr, _empty, _f32_dev, _gemm_tn, _mlp, _view, gemm_tn
 
 def latent_wide_shape(de_layers: Layers, ae_layers: Optional[Layers], x_dim: int, z_dim: int, v_dim: int = 0, i_dim: int = 0) -> bool:
     """The latent shapes of the direct_encode models at a hidden width the dedicated latent kernels do not take (every H <= 128 with
@@ -36,13 +36,13 @@ def latent_backward_wide(method: str, de_layers: Layers, ae_layers: Optional[Lay
     dae = ae_layers is not None
     T, B, H = xs.shape
     zd = z.shape[-1] if z is not None else 0
-    S = STAGES[method]
+    method_id, S = builtin_method(method, "latent_backward_wide")
     nblk = (4 if zd else 3) if dae else 2
     n = nblk * H
     f32 = dict(dtype=torch.float32, device=dev)
     keep: list = []
     a = _lib.LatentBwdWideArgsF32()
-    a.method, a.hidden, a.z_dim, a.dae, a.T, a.B = METHOD_ID[method], H, zd, int(dae), T, B
+    a.method, a.hidden, a.z_dim, a.dae, a.T, a.B = method_id, H, zd, int(dae), T, B
     a.de = _mlp(de_layers, dev, "de", keep)
     if dae:
         a.ae = _mlp(ae_layers, dev, "ae", keep)

@@ -34,7 +34,7 @@ def _autograd():
 
 class FixedGridODESolver(metaclass=abc.ABCMeta):
     order: int
-    method: str = ""
+    method = ""        # "euler" | "midpoint" | "rk4", or a fused.Tableau (my_fixed_grid.ExplicitRK): the formula the fused kernels run
 
     def __init__(self, step_size=None, grid_constructor=None, interp="linear"):
         # public attributes of the reference (my_solvers.py:13-18)
@@ -75,7 +75,7 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
             self._walk_warned = True
             warnings.warn(f"{what}: this call is not fusable (needs fp32 HIP tensors, DE_Func/AE_Func-style MLPs with one activation "
                           "of ELU / Tanh / Sigmoid / ReLU / LeakyReLU / Softplus / SiLU / GELU / Mish -- other than ELU(1) on kernel 'auto' / 'generic' only --, "
-                          "ODE_Event/DAE_Event callbacks; under autograd also a shape with a backward kernel; teacher-forced "
+                          "ODE_Event/DAE_Event callbacks; an ExplicitRK tableau on kernel 'auto' / 'generic' only; under autograd also a shape with a backward kernel; teacher-forced "
                           "training: ELU(1), dataset rows without grad) -- stepping through the Python callables instead", RuntimeWarning, stacklevel=3)
 
     def _act_kernel_ok(self, what, acts) -> bool:
@@ -87,6 +87,16 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
             names = ", ".join(repr(a) for a in acts if a is not None)
             raise UnsupportedShapeError(f"{what}: kernel={self.kernel!r} has no form for the activation {names}: activations other than "
                                         "ELU(alpha=1) run on the generic kernels (kernel 'auto' / 'generic')")
+        return False
+
+    def _rk_kernel_ok(self, what) -> bool:
+        """A Runge-Kutta tableau (ExplicitRK: `method` is a fused.Tableau) runs on the generic kernels K0 / K5 only: kernel 'wave' / 'tile'
+        / 'mfma' / 'wide' with one walks under fused='auto' and raises under 'require'."""
+        if not isinstance(self.method, _fused.Tableau) or self.kernel in ("auto", "generic"):
+            return True
+        if self.fused == "require":
+            raise UnsupportedShapeError(f"{what}: kernel={self.kernel!r} has no form for the Runge-Kutta tableau {self.method.name}: "
+                                        "tableaus run on the generic kernels (kernel 'auto' / 'generic')")
         return False
 
     def _check_events_now(self, event_t):
@@ -110,7 +120,7 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
             raise ValueError("integrate_ODE: x_init and input_true_x exclude each other (teacher forcing starts every step from x[k])")
         if self.fused != "off":
             plan = _fused.plan_ode(x_func, x, z, all_initial, event_fn, jump_change_fn, t=t, x_init=x_init)
-            if plan is not None and not self._act_kernel_ok("integrate_ODE", plan[4:]):
+            if plan is not None and not (self._act_kernel_ok("integrate_ODE", plan[4:]) and self._rk_kernel_ok("integrate_ODE")):
                 plan = None
             if plan is not None:
                 layers, event_t, z_jump, needs_grad, act = plan
@@ -162,7 +172,7 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
                       input_true_x=False, input_true_i=False):
         if self.fused != "off":
             plan = _fused.plan_dae(x_init, x_func, i_func, z, v, i, all_initial, event_fn, jump_change_fn, t=t)
-            if plan is not None and not self._act_kernel_ok("integrate_DAE", plan[6:]):
+            if plan is not None and not (self._act_kernel_ok("integrate_DAE", plan[6:]) and self._rk_kernel_ok("integrate_DAE")):
                 plan = None
             if plan is not None:
                 de, ae, event_t, z_jump, v_jump, needs_grad, de_act, ae_act = plan
