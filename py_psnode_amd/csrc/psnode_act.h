@@ -1,4 +1,4 @@
-// Hidden-layer activations other than ELU(1) for the generic kernels K0 (psnode_generic.hip) and K5 (psnode_generic_bwd.hip).
+// Hidden-layer activations other than ELU(1) for the generic kernels K0 (psnode_generic_impl.h) and K5 (psnode_generic_bwd_impl.h).
 //
 // The ELU(1) kernels of both files do not see any of this: they keep elu_quad / elu_grad_quad (psnode_common.h).  The activation kernels
 // (generic_act_kernel / generic_backward_act_kernel: the same sources compiled a second time, psnode_generic_act.hip /
@@ -241,7 +241,7 @@ bool generic_wide_mode(const IntegrateDev& a, bool dae);
 // psnode_generic_act.hip: K0 with the activations of `act` (the ELU(1) call is launch_generic)
 hipError_t launch_generic_act(const IntegrateDev& a, bool dae, const ActPair& act, hipStream_t stream);
 // psnode_generic_pre.hip: the same for an ActPair with a kind of the pre-activation family (act_pair_pre)
-// (K5's three launchers: psnode_common.h, generic_backward_launch*)
+// (K5's launchers: psnode_common.h, generic_backward_launch<Bd>)
 hipError_t launch_generic_pre(const IntegrateDev& a, bool dae, const ActPair& act, hipStream_t stream);
 // psnode_generic_rk.hip: K0 with the Butcher tableau `rk` in place of a.method, every activation kind (ELU(1) as ELU with alpha = 1)
 hipError_t launch_generic_rk(const IntegrateDev& a, bool dae, const ActPair& act, const psnode_rk_tableau_f32& rk, hipStream_t stream);

@@ -4,7 +4,7 @@
 //   K4f (psnode_backward_fused.hip)      ODE, in -> H -> H -> H -> x at hidden <= 128: one launch, saved-activation and recompute forms
 //   K8f / K9 (psnode_latent_dpp.hip / psnode_latent64_bwd*.hip)   the latent integrators of the direct_encode models at hidden 16 / 64
 //   K8 (psnode_latent_bwd.hip)           the latent DAE at hidden 16
-//   K5 (psnode_generic_bwd.hip)          anything else that fits the LDS, with or without teacher forcing
+//   K5 (psnode_generic_bwd_impl.h)       anything else that fits the LDS, with or without teacher forcing
 // (the DAE's no_encode shapes go through psnode_dae_backward_wide_f32 -> K7f, psnode_dae_backward_fused.hip).
 // Rounds 1-4 also carried K4 / K7, hidden-64 specialisations of the recompute form; K4f / K7f cover their shapes (round 5:
 // profiles/scripts/variants/ keeps the sources).
@@ -48,8 +48,8 @@ bool workspace_ok(const void* workspace, size_t workspace_bytes, size_t need) {
     return workspace && !(reinterpret_cast<uintptr_t>(workspace) & 255u) && workspace_bytes >= need;
 }
 
-// ---- K5 (psnode_generic_bwd.hip): the recipe dims it takes, its call struct, the choice among its three builds
-// pre: K5's pre-activation build (its own LDS fit: psnode_generic_bwd.hip, pre_floats)
+// ---- K5 (psnode_generic_bwd_impl.h): the recipe dims it takes, its call struct, the choice among its three builds
+// pre: K5's pre-activation build (its own LDS fit: psnode_generic_bwd_impl.h, pre_floats)
 bool ode_generic_ok(const psnode_ode_bwd_args_f32* a, bool pre = false) {
     const psnode_mlp_f32& m = a->de;
     if (a->x_dim < 1 || a->z_dim < 0 || m.n_layers < 1 || m.n_layers > kMaxLayers) return false;
@@ -89,8 +89,8 @@ GenericBwdCall generic_bwd_call(const psnode_dae_bwd_args_f32& a) {
 }
 // act: the activations of a non-ELU(1) call, or nullptr
 int generic_backward(const GenericBwdCall& c, const ActPair* act, void* workspace, void* stream) {
-    if (c.rk) return generic_backward_launch_rk(c, act, static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
-    const auto launch = !act ? generic_backward_launch : (act_pair_pre(*act) ? generic_backward_launch_pre : generic_backward_launch_act);
+    if (c.rk) return generic_backward_launch<BuildRk>(c, act, static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
+    const auto launch = !act ? generic_backward_launch<BuildElu1> : (act_pair_pre(*act) ? generic_backward_launch<BuildPre> : generic_backward_launch<BuildAct>);
     return launch(c, act, static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
 }
 // what a non-ELU(1) act asks of the call besides the dims: K5 (AUTO / GENERIC), no teacher forcing, no saved rows
@@ -299,7 +299,7 @@ extern "C" int32_t psnode_dae_backward_act_f32(const psnode_dae_bwd_args_f32* a,
 }
 
 // ---- explicit Runge-Kutta tableaus (include/psnode_hip.h, psnode_rk_tableau_f32): K5's tableau build alone (every activation kind; it
-// keeps the pre-activations, so generic_bwd_fits_rk answers for the shape).  The act is checked first, then the tableau; `method` is not
+// keeps the pre-activations, so the pre fit of generic_bwd_fits answers for the shape).  The act is checked first, then the tableau; `method` is not
 // read; then NULL args -> dims -> unsupported -> pointers -> workspace, as above.
 namespace {
 bool rk_ode_ok(const psnode_ode_bwd_args_f32* a, bool elu1) {
@@ -308,7 +308,7 @@ bool rk_ode_ok(const psnode_ode_bwd_args_f32* a, bool elu1) {
     const psnode_mlp_f32& m = a->de;
     if (a->x_dim < 1 || a->z_dim < 0 || m.n_layers < 1 || m.n_layers > kMaxLayers) return false;
     if (m.in_dim != 3 * (a->x_dim + a->z_dim) || m.out_dim[m.n_layers - 1] != a->x_dim) return false;
-    return generic_bwd_fits_rk(&a->de, nullptr, a->x_dim, a->z_dim, 0, 0) != 0;
+    return generic_bwd_fits(&a->de, nullptr, a->x_dim, a->z_dim, 0, 0, true) != 0;
 }
 bool rk_dae_ok(const psnode_dae_bwd_tf_args_f32* a, bool elu1) {
     const psnode_dae_bwd_args_f32& b = a->base;
@@ -320,7 +320,7 @@ bool rk_dae_ok(const psnode_dae_bwd_tf_args_f32* a, bool elu1) {
     if (d.n_layers < 1 || d.n_layers > kMaxLayers || g.n_layers < 1 || g.n_layers > kMaxLayers) return false;
     if (d.in_dim != 3 * n || d.out_dim[d.n_layers - 1] != b.x_dim) return false;
     if (g.in_dim != n + b.x_dim + b.z_dim + b.v_dim || g.out_dim[g.n_layers - 1] != b.i_dim) return false;
-    return generic_bwd_fits_rk(&b.de, &b.ae, b.x_dim, b.z_dim, b.v_dim, b.i_dim) != 0;
+    return generic_bwd_fits(&b.de, &b.ae, b.x_dim, b.z_dim, b.v_dim, b.i_dim, true) != 0;
 }
 }  // namespace
 

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "psnode_generic_build.h"
 #include "psnode_hip.h"
 
 namespace psnode {
@@ -289,7 +290,7 @@ hipError_t launch_mfma_h128(const IntegrateDev& a, bool dae, float* pack, hipStr
 hipError_t launch_mfma_h192(const IntegrateDev& a, bool dae, float* pack, hipStream_t stream);   // psnode_mfma_h192.hip (forward only)
 hipError_t launch_mfma_h256(const IntegrateDev& a, bool dae, float* pack, hipStream_t stream);   // psnode_mfma_h256.hip (forward only)
 
-// psnode_generic_bwd.hip (K5: generic fused backward, ODE and DAE)
+// psnode_generic_bwd_impl.h (K5: generic fused backward, ODE and DAE)
 // parameters of an MLP in the flat gradient vector (nn.Linear order: W, b per layer)
 inline int mlp_np(const psnode_mlp_f32& m) {
     int np = 0, k = m.in_dim;
@@ -312,22 +313,19 @@ struct GenericBwdCall {
     float *gx0, *gz, *gv, *gzj, *gvj, *ga0, *gparams_de, *gparams_ae;
     unsigned flags;            // PSNODE_FLAG_INPUT_TRUE_X / _I: the teacher-forced sweep (ELU(1) build only for now)
     const float *xt, *it;      // DAE: x_true / i_true [T,B,.] for the flags set (the ODE's dataset comes in as xs)
-    const psnode_rk_tableau_f32* rk;      // generic_backward_launch_rk: the tableau (checked: rk_tableau_check); `method` is then not read
+    const psnode_rk_tableau_f32* rk;      // generic_backward_launch<BuildRk>: the tableau (checked: rk_tableau_check); `method` is then not read
 };
 struct ActPair;     // psnode_act.h: the DE's and the AE's activation of a non-ELU(1) call
 size_t generic_bwd_workspace_floats(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, long long B);
-// pre: the fit of K5's pre-activation build (it keeps u in LDS as well: generic_bwd_fits_pre, psnode_generic_bwd_pre.hip)
+// K5's mode for these dims, 0 if the shape does not fit: the one fit query of all four builds.  pre: the fit of the builds that keep u in LDS
+// as well -- the pre-activation build and the tableau build, whose LDS layouts are the same
 int generic_bwd_fits(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, int xd, int zd, int vd, int id, bool pre);
-int generic_bwd_fits_pre(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, int xd, int zd, int vd, int id);
-// One launcher per build of psnode_generic_bwd.hip: ELU(1) (ignores `act`), the activations of psnode_act.h (psnode_generic_bwd_act.hip),
-// those and the pre-activation family (psnode_generic_bwd_pre.hip).  psnode_backward.hip: generic_backward picks among them.
+// K5's launcher (psnode_generic_bwd_impl.h), instantiated once per build policy (psnode_generic_build.h) in that policy's object: BuildElu1
+// (ignores `act`), BuildAct (the activations of psnode_act.h), BuildPre (those and the pre-activation family), BuildRk (the tableau build:
+// every activation kind -- `act` is required, ELU(1) runs as ELU with alpha = 1 -- and c.rk in place of c.method; it keeps the
+// pre-activations like the pre build).  psnode_backward.hip: generic_backward picks among them.
+template <class B>
 int generic_backward_launch(const GenericBwdCall& c, const ActPair* act, float* workspace, hipStream_t stream);
-int generic_backward_launch_act(const GenericBwdCall& c, const ActPair* act, float* workspace, hipStream_t stream);
-int generic_backward_launch_pre(const GenericBwdCall& c, const ActPair* act, float* workspace, hipStream_t stream);
-// psnode_generic_bwd_rk.hip: the tableau build -- every activation kind (`act` is required: ELU(1) runs as ELU with alpha = 1) and c.rk
-// in place of c.method; it keeps the pre-activations like the pre build, so its own fit answers for it
-int generic_backward_launch_rk(const GenericBwdCall& c, const ActPair* act, float* workspace, hipStream_t stream);
-int generic_bwd_fits_rk(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, int xd, int zd, int vd, int id);
 // psnode_capi.hip: PSNODE_OK, PSNODE_ERR_NULL (no tableau) or PSNODE_ERR_METHOD (stages outside 1..4, a coefficient that is not finite, a
 // non-zero a[s][j] with j >= s or in a row / column >= stages, a non-zero b[s] with s >= stages)
 int rk_tableau_check(const psnode_rk_tableau_f32* tab);

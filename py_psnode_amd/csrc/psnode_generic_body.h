@@ -1,0 +1,287 @@
+// The body of K0's kernel (psnode_generic_impl.h), as text: each of the four objects writes its own __global__ -- generic_kernel(a),
+// generic_act_kernel(a, act), generic_pre_act_kernel(a, act), generic_rk_kernel(a, act, rk) -- and includes this file between its braces.
+// Template parameters in scope: DAE, MODE, ML, QM.  Names in scope: a, act (ActPair; NoActPair in the ELU(1) object) and rk (read under
+// Bd::rk only; the other objects declare an unread one).  The build policy Bd decides the rest with `if constexpr`.
+    constexpr bool STREAM = MODE == 2;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int tid = threadIdx.x;
+    const long long b0 = (long long)blockIdx.x * TB;
+    const int xd = a.xd, zd = a.zd;
+    const int vd = DAE ? a.vd : 0, id = DAE ? a.id : 0;
+    const int n = xd + zd + vd + id;   // width of all_initial
+    const int ne = n - xd;             // external rows: z | v | i
+    const int nzv = zd + vd;
+
+    // quad-row buffers (float offsets): the two MLP inputs keep their constant columns (a0; the externals of a step) between evaluations,
+    // only the columns that change are rewritten -- per stage that is the state x alone
+    constexpr int inDE = 0;
+    const int SX = de_sx(xd), SA = ae_sa(xd, nzv);      // first column of the second block of the DE / AE input
+    const int inAE = de_k16(xd, n) * TB;
+    const int ping = inAE + (DAE ? ae_k16(xd, nzv, n) * TB : 0);
+    const int pong = ping + up16(a.maxo) * TB;
+    float* a0 = lds + pong + up16(a.maxo) * TB;   // [n][TB]
+    float* ext = a0 + n * TB;          // [ne][TB] z | v | i fed to the DE stages of this step
+    float* xcur = ext + ne * TB;       // [xd][TB] running state
+    float* xsrc = xcur + xd * TB;      // [xd][TB] start of this step (xcur, or dataset x under teacher forcing)
+    float* kbuf = xsrc + xd * TB;      // [4][xd][TB]
+    float* icur = kbuf + 4 * xd * TB;  // [id][TB]
+    float* zvn = icur + id * TB;       // [nzv][TB] dataset z | v of the NEXT grid point
+    float* dts = zvn + nzv * TB;       // [TB]
+
+#ifdef PSNODE_K0_PROF      // discriminator builds only: cycles per phase of workgroup 0, printed by its first thread
+    long long prof[6] = {0, 0, 0, 0, 0, 0};
+    long long pt = clock64();
+#define K0_PROF(i) { const long long now_ = clock64(); prof[i] += now_ - pt; pt = now_; }
+#else
+#define K0_PROF(i)
+#endif
+    Pref pf;
+    pf.tag = nullptr;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    unsigned bias_at = (unsigned)(dts + TB - lds), img_at = bias_at + (unsigned)generic_bias_floats(a, DAE);
+    const Tab<ML> tde = make_tab<ML>(a.de, wv, a.k0_res & 0xffu, bias_at, img_at, de_k16(xd, n), SX >> 4);
+    const Tab<ML> tae = DAE ? make_tab<ML>(a.ae, wv, (a.k0_res >> 8) & 0xffu, bias_at, img_at, ae_k16(xd, nzv, n), SA >> 4) : tde;
+    load_resident(a.de, tde, lds);
+    if constexpr (DAE) load_resident(a.ae, tae, lds);
+    WReg<MODE == 0 ? ML : 2, MODE == 0 ? QM : 1> wde;
+    WRegW<MODE == 3 ? ML : 3> wdw;
+    if constexpr (MODE == 3) load_regs_wide<ML>(a.de, tde, wdw);
+    const f4 fzero = f4{0.f, 0.f, 0.f, 0.f};
+    f4 cde = fzero, cde2 = fzero, cae = fzero;       // fold0 of the wave's tile(s) of the DE's / AE's first layer (register forms)
+    WReg<(MODE == 0 && DAE) ? ML : 2, (MODE == 0 && DAE) ? QM : 1> wae;
+    if constexpr (MODE == 0) {
+        load_regs<ML, QM>(a.de, tde, wde);
+        if constexpr (DAE) load_regs<ML, QM>(a.ae, tae, wae);
+    }
+
+    auto gb = [&](int c) -> long long { const long long b = b0 + c; return b < a.B ? b : a.B - 1; };
+    const bool true_x = (a.flags & PSNODE_FLAG_INPUT_TRUE_X) != 0;
+    const bool true_i = DAE && (a.flags & PSNODE_FLAG_INPUT_TRUE_I) != 0;
+    const int nx = xd * TB;
+    // dataset z | v row r of trajectory column c at grid point j
+    auto zv_at = [&](long long j, int r, int c) -> float {
+        const long long b = gb(c);
+        return r < zd ? a.z.p[j * a.z.st + b * a.z.sb + r] : a.v.p[j * a.v.st + b * a.v.sb + (r - zd)];
+    };
+    // external row r (z | v | i order) of the DE input: columns n + xd + r (s - a0) and 2 n + xd + r (s)
+    auto put_ext = [&](int r, int c, float v) {
+        ext[r * TB + c] = v;
+        lds[inDE + qi(SX + n + r, c)] = v - a0[(xd + r) * TB + c];
+        lds[inDE + qi(SX + n + ne + r, c)] = v;
+    };
+    auto put_x = [&](int r, int c, float v) {
+        lds[inDE + qi(r, c)] = v - a0[r * TB + c];
+        lds[inDE + qi(xd + r, c)] = v;
+    };
+
+    // ---- per-trajectory constants, the constant and pad columns of both inputs, the initial state, z | v of grid point 0
+    for (int idx = tid; idx < n * TB; idx += NT) {
+        const int r = idx / TB, c = idx % TB;
+        const float v = a.a0[gb(c) * n + r];
+        a0[idx] = v;
+        lds[inDE + qi(SX + r, c)] = v;
+        if constexpr (DAE) lds[inAE + qi(SA + r, c)] = v;
+    }
+    for (int idx = tid; idx < de_k16(xd, n) * TB; idx += NT)       // pad columns (the others are overwritten below / at the top of every step)
+        if (de_orig_col(idx / TB, xd, n) < 0) lds[inDE + qi(idx / TB, idx % TB)] = 0.0f;
+    if constexpr (DAE)
+        for (int idx = tid; idx < ae_k16(xd, nzv, n) * TB; idx += NT)
+            if (ae_orig_col(idx / TB, xd, nzv, n) < 0) lds[inAE + qi(idx / TB, idx % TB)] = 0.0f;
+    for (int idx = tid; idx < nx; idx += NT) {
+        const int r = idx / TB, c = idx % TB;
+        const long long b = gb(c);
+        const float v = DAE ? a.x_init[b * xd + r] : a.x.p[b * a.x.sb + r];
+        xcur[idx] = v;
+        if (b0 + c < a.B) a.xo[b * xd + r] = v;
+        if constexpr (DAE) lds[inAE + qi(r, c)] = true_x ? a.x.p[b * a.x.sb + r] : v;      // my_solvers.py:95
+    }
+    for (int idx = tid; idx < nzv * TB; idx += NT) {
+        const float v = zv_at(0, idx / TB, idx % TB);
+        zvn[idx] = v;
+        if constexpr (DAE) lds[inAE + qi(xd + idx / TB, idx % TB)] = v;
+    }
+    lds_barrier();
+
+    if constexpr (MODE == 0 && DAE) {       // the AE's a0 block: constant over the trajectory
+        if (wv < tab_tiles(tae.dims[0])) cae = fold0<ML>(tae, lds, inAE, wv);
+    }
+    const int nstage = Bd::rk ? __builtin_amdgcn_readfirstlane(rk.stages) : (a.method == PSNODE_EULER ? 1 : (a.method == PSNODE_MIDPOINT ? 2 : 4));
+    // The coefficients go to LDS once: rows a[1][0], a[2][0..1], a[3][0..2], b[0..3] packed into ten floats of kbuf's fourth slot, which no
+    // stage pass writes (kbuf keeps k_0 .. k_{S - 2}, at most three slopes; nx >= 16).  Read back per stage pass as broadcasts: kept as kernel
+    // arguments they cost the time loop scalar registers it does not have.  (Every step's input barrier lies between this and the first read.)
+    static_assert(TB >= 10, "the tableau needs ten floats of the fourth kbuf slot (nx = x_dim * TB)");
+    float* rkt = kbuf + 3 * xd * TB;
+    if constexpr (Bd::rk) {
+        if (tid < 10) rkt[tid] = tid < 6 ? (&rk.a[0][0])[tid == 0 ? 4 : (tid == 1 ? 8 : (tid == 2 ? 9 : 9 + tid))] : rk.b[tid - 6];
+    }
+    // look-ahead registers: clocks (threads < TB), the next step's event index, the next grid point's z | v
+    float tc = 0.0f, tn = 0.0f;
+    if (tid < TB) {
+        tc = a.t.p[gb(tid) * a.t.sb];
+        tn = a.T > 1 ? a.t.p[a.t.st + gb(tid) * a.t.sb] : tc;
+    }
+    // the next step's event index travels through a VECTOR load (every lane the same address): a scalar load would be waited for by the
+    // very next LDS wait (SMEM returns out of order, so any lgkmcnt wait is lgkmcnt(0)) -- an L2 round trip at the top of every step
+    const int* evp = a.ev ? a.ev : reinterpret_cast<const int*>(a.t.p);      // (a valid address when there are no events)
+    int evn_v = (a.ev && a.T > 1) ? __builtin_nontemporal_load(evp) : -1;
+
+    float pz[PF];
+
+    // One MLP call site for every evaluation (the unrolled layer code exists once: it has to stay inside the instruction cache).  Slots of
+    // step k: 0 = the AE head at an event (my_solvers.py:110), 1 .. S = the DE stages, S + 1 = the AE head at grid point k + 1
+    // (my_solvers.py:95, 121); the pseudo-step k = -1 of the DAE is that last slot alone, for grid point 0.
+    for (long long k = DAE ? -1 : 0; k + 1 < a.T; ++k) {
+        K0_PROF(5)
+        const int ev = k >= 0 ? __builtin_amdgcn_readfirstlane(evn_v) : -1;
+        if (k >= 0) {
+            // ---- this step's inputs (zero-order hold: the left grid point feeds every stage)
+            if (tid < TB) dts[tid] = tn - tc;
+            for (int idx = tid; idx < nzv * TB; idx += NT) {
+                const int r = idx / TB, c = idx % TB;
+                float v;
+                if (ev >= 0) { const long long b = gb(c); v = r < zd ? a.zj[b * a.zjb + ev * a.zje + r] : a.vj[b * a.vjb + ev * a.vje + (r - zd)]; }
+                else v = zvn[idx];
+                put_ext(r, c, v);
+                if constexpr (DAE) if (ev >= 0) lds[inAE + qi(xd + r, c)] = v;      // the event's AE evaluation sees the jumped rows
+            }
+            for (int idx = tid; idx < nx; idx += NT) {
+                const int r = idx / TB, c = idx % TB;
+                const float v = true_x ? a.x.p[k * a.x.st + gb(c) * a.x.sb + r] : xcur[idx];
+                xsrc[idx] = v;
+                put_x(r, c, v);
+                if constexpr (DAE) if (ev >= 0) lds[inAE + qi(r, c)] = xcur[idx];   // ... and the computed state
+            }
+            if constexpr (DAE) {
+                if (ev < 0)
+                    for (int idx = tid; idx < id * TB; idx += NT) {
+                        const int r = idx / TB, c = idx % TB;
+                        put_ext(nzv + r, c, true_i ? a.i.p[k * a.i.st + gb(c) * a.i.sb + r] : icur[idx]);
+                    }
+            }
+            // ---- look-ahead for grid point k + 1
+            const long long k1 = k + 1, k2 = k + 2 < a.T ? k + 2 : a.T - 1;
+            if (tid < TB) { tc = tn; tn = a.t.p[k2 * a.t.st + gb(tid) * a.t.sb]; }
+            evn_v = (a.ev && k1 + 1 < a.T) ? evp[k1] : -1;
+#pragma unroll
+            for (int j = 0; j < PF; ++j) {
+                const int idx = tid + NT * j;
+                const int ii = idx < nzv * TB ? idx : 0;
+                pz[j] = nzv > 0 ? zv_at(k1, ii / TB, ii % TB) : 0.0f;
+            }
+            lds_barrier();
+        }
+        K0_PROF(0)
+        const int e_end = DAE ? nstage + 1 : nstage;
+        for (int e = k < 0 ? nstage + 1 : ((DAE && ev >= 0) ? 0 : 1); e <= e_end; ++e) {
+            const bool is_ae = DAE && (e == 0 || e == nstage + 1);
+            const bool ae_next = DAE && e == nstage;
+            int f;
+            if constexpr (MODE == 0 || MODE == 3) {
+                if (e == 1) {       // the step's externals are in place (behind an event's AE evaluation too): the DE's per-step constant
+                    const int nt0 = tab_tiles(tde.dims[0]);
+                    if (wv < nt0) cde = fold0<ML>(tde, lds, inDE, wv);
+                    if (MODE == 3 && wv + 4 < nt0) cde2 = fold0<ML>(tde, lds, inDE, wv + 4);
+                }
+            }
+            if constexpr (MODE == 3) {
+                f = mlp_regw<ML>(tde, lds, inDE, ping, pong, wdw, cde, cde2, ActCtx{act.de});
+            } else if constexpr (MODE == 0) {      // two call sites: the operands are two different register sets
+                if (is_ae) { if constexpr (DAE) f = mlp_reg<ML, QM>(tae, lds, inAE, ping, pong, wae, cae, ActCtx{act.ae}); else f = ping; }
+                else f = mlp_reg<ML, QM>(tde, lds, inDE, ping, pong, wde, cde, ActCtx{act.de});
+            } else {
+                f = DAE ? mlp_eval<STREAM, ML>(pick_tab(is_ae, tae, tde), lds, is_ae ? inAE : inDE, ping, pong, pf, pick_tab(ae_next, tae, tde),
+                                               ActCtx{act_pick(is_ae, act.ae, act.de)})
+                        : mlp_eval<STREAM, ML>(tde, lds, inDE, ping, pong, pf, tde, ActCtx{act.de});
+            }
+            K0_PROF(2)
+            if (is_ae) {
+                if constexpr (DAE) {
+                    for (int idx = tid; idx < id * TB; idx += NT) {
+                        const int r = idx / TB, c = idx % TB;
+                        const float v = lds[f + qi(r, c)];
+                        icur[idx] = v;       // read back by the same thread (below, or at the top of the next step)
+                        if (e == 0) put_ext(nzv + r, c, true_i ? a.i.p[k * a.i.st + gb(c) * a.i.sb + r] : v);
+                        else if (b0 + c < a.B) a.io[((k + 1) * a.B + b0 + c) * id + r] = v;
+                    }
+                    if (e == 0) lds_barrier();
+                }
+                K0_PROF(4)
+                continue;
+            }
+            // ---- stage s: ONE pass that forms the next stage's argument straight into the DE input (my_fixed_grid.py:15-18, 23-32, 38-51)
+            //      or, behind the last stage, the new state, its output row, the AE input and the look-ahead rows
+            const int s_ = e - 1;
+            const bool final_stage = s_ + 1 == nstage;
+            float c0 = 0.0f, c1 = 0.0f, c2 = 0.0f, c3 = 0.0f;
+            if constexpr (Bd::rk) {
+            // the tableau row this pass applies to k_0 .. k_s (uniform): a[s + 1][.] -- the next stage's argument -- or, behind the last
+            // stage, b.  kbuf keeps k_0 .. k_{S - 2}: at most three slopes.
+            auto rku = [](float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); };
+            const float* rrow = rkt + (final_stage ? 6 : (s_ == 0 ? 0 : (s_ == 1 ? 1 : 3)));
+            c0 = rku(rrow[0]);
+            c1 = s_ >= 1 ? rku(rrow[1]) : 0.0f;
+            c2 = s_ >= 2 ? rku(rrow[2]) : 0.0f;
+            c3 = s_ >= 3 ? rku(rrow[3]) : 0.0f;
+            }
+            for (int idx = tid; idx < nx; idx += NT) {
+                const int r = idx / TB, c = idx % TB;
+                const float h = dts[c];
+                const float x0 = xsrc[idx];
+                const float ks = lds[f + qi(r, c)];
+                float v;
+                if constexpr (Bd::rk) {
+                // v = x0 + h * sum_j c_j k_j in increasing j, zero coefficients skipped (psnode_rk_tableau_f32); k_s is this stage's slope
+                if (s_ < 3 && !final_stage) kbuf[s_ * nx + idx] = ks;
+                float acc = 0.0f;
+                if (c0 != 0.0f) acc += c0 * (s_ == 0 ? ks : kbuf[idx]);
+                if (c1 != 0.0f) acc += c1 * (s_ == 1 ? ks : kbuf[nx + idx]);
+                if (c2 != 0.0f) acc += c2 * (s_ == 2 ? ks : kbuf[2 * nx + idx]);
+                if (c3 != 0.0f) acc += c3 * ks;
+                v = x0 + h * acc;
+                } else {
+                if (a.method == PSNODE_EULER) {
+                    v = x0 + h * ks;
+                } else if (a.method == PSNODE_MIDPOINT) {
+                    v = s_ == 0 ? x0 + ks * (0.5f * h) : x0 + h * ks;
+                } else {
+                    if (s_ < 3) kbuf[s_ * nx + idx] = ks;
+                    const float k1 = kbuf[idx];
+                    if (s_ == 0) v = x0 + h * k1 * kOneThird;
+                    else if (s_ == 1) v = x0 + h * (ks - k1 * kOneThird);
+                    else if (s_ == 2) v = x0 + h * (k1 - kbuf[nx + idx] + ks);
+                    else v = x0 + (k1 + 3.0f * (kbuf[nx + idx] + kbuf[2 * nx + idx]) + ks) * h * 0.125f;
+                }
+                }
+                if (!final_stage) {
+                    put_x(r, c, v);
+                } else {
+                    xcur[idx] = v;
+                    if (b0 + c < a.B) a.xo[((k + 1) * a.B + b0 + c) * xd + r] = v;
+                    if constexpr (DAE) lds[inAE + qi(r, c)] = true_x ? a.x.p[(k + 1) * a.x.st + gb(c) * a.x.sb + r] : v;   // my_solvers.py:121
+                }
+            }
+            if (final_stage) {
+#pragma unroll
+                for (int j = 0; j < PF; ++j) {
+                    const int idx = tid + NT * j;
+                    if (idx < nzv * TB) {
+                        zvn[idx] = pz[j];
+                        if constexpr (DAE) lds[inAE + qi(xd + idx / TB, idx % TB)] = pz[j];
+                    }
+                }
+                for (int idx = tid + NT * PF; idx < nzv * TB; idx += NT) {
+                    const float v = zv_at(k + 1, idx / TB, idx % TB);
+                    zvn[idx] = v;
+                    if constexpr (DAE) lds[inAE + qi(xd + idx / TB, idx % TB)] = v;
+                }
+            }
+            lds_barrier();
+            K0_PROF(3)
+        }
+    }
+#ifdef PSNODE_K0_PROF
+    if (blockIdx.x == 0 && tid == 0)
+        printf("K0 phases (cycles of clock64, workgroup 0): step inputs %lld | mlp %lld | update %lld | AE head + output %lld | loop %lld\n", prof[0], prof[2],
+               prof[3], prof[4], prof[5]);
+#endif
+#undef K0_PROF

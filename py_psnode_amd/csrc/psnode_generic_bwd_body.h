@@ -1,0 +1,345 @@
+// The body of K5's kernel (psnode_generic_bwd_impl.h), as text: each of the four objects writes its own __global__ --
+// generic_backward_kernel(a), generic_backward_act_kernel(a, act), generic_backward_pre_act_kernel(a, act),
+// generic_backward_rk_kernel(a, act, rk) -- and includes this file between its braces.  Template parameters in scope: gg, REG, ggA, STR.
+// Names in scope: a, act (ActPair; NoActPair in the ELU(1) object) and rk (read under Bd::rk only; the other objects declare an unread one).
+    constexpr bool DE_TM = REG || STR == 2;      // the DE's LDS accumulators are tile-major
+    constexpr bool AE_TM = STR >= 1;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int tid = threadIdx.x;
+    const long long b0 = (long long)blockIdx.x * TB;
+    const bool dae = a.dae != 0;
+    const int xd = a.xd, zd = a.zd, vd = dae ? a.vd : 0, id = dae ? a.id : 0;
+    const int nzv = zd + vd, ne = nzv + id, n = xd + ne;
+    const int S = Bd::rk ? __builtin_amdgcn_readfirstlane(rk.stages) : rk_stages(a.method);
+    const int nx = xd * TP;
+    // teacher forcing: tx -- every DE step and every grid-point head reads the dataset row (xsrc), the adjoint of a step's start state is
+    // dropped; ti -- the DE reads i_true[k], its algebraic adjoint is dropped and the event-time head feeds nothing
+    const bool tx = (a.flags & PSNODE_FLAG_INPUT_TRUE_X) != 0, ti = dae && (a.flags & PSNODE_FLAG_INPUT_TRUE_I) != 0;
+    const float* __restrict__ xsrc = tx ? a.xt : a.xs;
+
+    float* acts = lds;                            // [act_rows][TP]
+    float* dA = acts + a.act_rows * TP;           // [maxw][TP]
+    float* dB = dA + a.maxw * TP;
+    float* a0s = dB + a.maxw * TP;                // [n][TP]
+    float* ga0s = a0s + n * TP;                   // [n][TP]
+    float* ext = ga0s + n * TP;                   // [ne][TP]  z | v | i fed to the DE of this step
+    float* gext = ext + ne * TP;                  // [ne][TP]
+    float* x0 = gext + ne * TP;                   // [xd][TP]
+    float* xst = x0 + nx;                         // [4][xd][TP]
+    float* ks = xst + 4 * nx;                     // [4][xd][TP]
+    float* gks = ks + 4 * nx;                     // [4][xd][TP]
+    float* gx0 = gks + 4 * nx;                    // [xd][TP]
+    float* gxc = gx0 + nx;                        // [xd][TP]  carried dL/dx_{k+1}
+    float* gic = gxc + nx;                        // [id][TP]  carried dL/di_{k+1}
+    float* dts = gic + id * TP;                   // [TP]
+    float* wbuf = dts + TP;                       // [kWBuf] staged weights
+    // [np_de + np_ae]: in LDS when it fits, else this workgroup's partial slice in global memory (each element is owned by
+    // one thread either way, so the read-modify-write needs no atomics)
+    float* gacc_g = a.wpart + (size_t)blockIdx.x * (a.de.np + (a.dae ? a.ae.np : 0));      // (used when gg)
+    const bool stages = (!REG && STR != 2) || (a.dae && STR == 0);      // some MLP still stages its weights through LDS
+    float* gacc_l = wbuf + (stages ? kWBuf : 0);
+    // register path of the DE: quad-row buffers behind the accumulators, the wave's MFMA operands of both passes in VGPRs
+    const int de_acc = (DE_TM && !gg) ? tm_total(a.de) : a.de.np;      // floats of the DE's accumulators in LDS (tile-major off the staged path)
+    const int ae_at = gg ? 0 : de_acc;                                 // the AE's accumulators in LDS (when !ggA) sit behind the DE's
+    const int ae_acc = (AE_TM && !ggA) ? tm_total(a.ae) : a.ae.np;
+    const int np_all = ae_at + ((a.dae && !ggA) ? ae_acc : 0);        // floats of LDS accumulators
+    float* qb = gacc_l + ((np_all + 3) & ~3);
+    const QOff qo = q_offsets(a.de), qoA = q_offsets(a.ae);           // (one region: the two MLPs' evaluations never overlap in time)
+    float* upre = u_region(lds, a);                                  // (likewise one region for both MLPs' pre-activations)
+    RegFwd rfw;
+    RegBwd rbw;
+    if constexpr (REG) load_reg_images(a, rfw, rbw);
+
+    auto gb = [&](int c) -> long long { const long long b = b0 + c; return b < a.B ? b : a.B - 1; };
+    auto on = [&](int c) -> bool { return b0 + c < a.B; };
+    // loops over [rows][TB] tiles: idx -> (r, c)
+#define TILE_LOOP(rows) for (int idx = tid, r = tid / TB, c = tid % TB; idx < (rows) * TB; idx += NT, r = idx / TB, c = idx % TB)
+
+    if constexpr (Bd::rk) {      // the tableau -> LDS (coef_a, coef_b)
+        static_assert(TP >= 20, "the tableau needs 20 floats of the fourth ks slot (nx = x_dim * TP)");
+        if (tid < 20) ks[3 * nx + tid] = tid < 16 ? rk.a[tid >> 2][tid & 3] : rk.b[tid - 16];
+    }
+    for (int e = tid; e < np_all; e += NT) gacc_l[e] = 0.0f;
+    // global accumulators: tile-major slices (tmpart) for the MLPs off the staged path, the natural partial slice itself for a staged one
+    float* tmg = a.tmpart + (size_t)blockIdx.x * (tm_total(a.de) + (a.dae ? tm_total(a.ae) : 0));
+    float* tmgA = tmg + tm_total(a.de);
+    if constexpr (gg) {
+        if constexpr (DE_TM) { for (int e = tid; e < tm_total(a.de); e += NT) tmg[e] = 0.0f; }
+        else { for (int e = tid; e < a.de.np; e += NT) gacc_g[e] = 0.0f; }
+    }
+    if constexpr (ggA) {
+        if (dae) {
+            if constexpr (AE_TM) { for (int e = tid; e < tm_total(a.ae); e += NT) tmgA[e] = 0.0f; }
+            else { for (int e = tid; e < a.ae.np; e += NT) gacc_g[a.de.np + e] = 0.0f; }
+        }
+    }
+    TILE_LOOP(n) { a0s[r * TP + c] = a.a0[gb(c) * n + r]; ga0s[r * TP + c] = 0.0f; }
+    TILE_LOOP(xd) gxc[r * TP + c] = on(c) ? a.gxs[((a.T - 1) * a.B + gb(c)) * xd + r] : 0.0f;
+    TILE_LOOP(id) gic[r * TP + c] = (on(c) && a.gis) ? a.gis[((a.T - 1) * a.B + gb(c)) * id + r] : 0.0f;
+    TILE_LOOP(nzv) {   // the last grid point's z|v only receive the AE part (DAE) or nothing (ODE)
+        if (!on(c)) continue;
+        const bool isz = r < zd;
+        float* dst = isz ? a.gz : a.gv;
+        if (dst) dst[((a.T - 1) * a.B + b0 + c) * (isz ? zd : vd) + (isz ? r : r - zd)] = 0.0f;
+    }
+    __syncthreads();
+
+    // DE input rows of acts: a0 | s - a0 | s  with s = x | ext
+    auto de_input = [&](const float* xs_rows) {
+        float* u = acts + a.de.act[0] * TP;
+        TILE_LOOP(n) {
+            const float s = r < xd ? xs_rows[r * TP + c] : ext[(r - xd) * TP + c];
+            const float i0 = a0s[r * TP + c];
+            u[r * TP + c] = i0;
+            u[(n + r) * TP + c] = s - i0;
+            u[(2 * n + r) * TP + c] = s;
+        }
+        __syncthreads();
+    };
+    // AE input rows: a0 | x | z | v ; x from xrows (LDS) ; z|v from grid point jzv (>= 0) or from ext
+    auto ae_input = [&](const float* xrows, long long jzv) {
+        float* u = acts + a.ae.act[0] * TP;
+        TILE_LOOP(n + xd + nzv) {
+            float v;
+            if (r < n) v = a0s[r * TP + c];
+            else if (r < n + xd) v = xrows[(r - n) * TP + c];
+            else if (jzv < 0) v = ext[(r - n - xd) * TP + c];
+            else if (r < n + xd + zd) v = a.z.p[jzv * a.z.st + gb(c) * a.z.sb + (r - n - xd)];
+            else v = a.v.p[jzv * a.v.st + gb(c) * a.v.sb + (r - n - xd - zd)];
+            u[r * TP + c] = v;
+        }
+        __syncthreads();
+    };
+    // VJP of the AE head at (xrows; z|v of grid point jzv or the jumped ext rows) with output gradient `gi`:
+    // adds to gx_dst, ga0s, and to the z|v gradients (global gz/gv at jzv, or the jump gradients of event ev)
+    auto ae_vjp = [&](const float* xrows, long long jzv, int ev, const float* gi, float* gx_dst) {
+        ae_input(xrows, jzv);
+        if constexpr (STR >= 1) g_forward_str(a.ae, a.fimgA, acts, qb, qoA, ActCtx{act.ae, upre}); else g_forward(a.ae, acts, wbuf, ActCtx{act.ae, upre});
+        TILE_LOOP(id) dA[r * TP + c] = gi[r * TP + c];
+        __syncthreads();
+        const float* gu = STR >= 1 ? g_vjp_str<ggA>(a.ae, a.timgA, acts, dA, dB, gacc_l + ae_at, tmgA, qb, qoA, ActCtx{act.ae, upre})
+                                   : g_vjp<ggA>(a.ae, acts, dA, dB, gacc_l + ae_at, gacc_g + a.de.np, wbuf, ActCtx{act.ae, upre});
+        TILE_LOOP(n) ga0s[r * TP + c] += gu[r * TP + c];
+        TILE_LOOP(xd) gx_dst[r * TP + c] += gu[(n + r) * TP + c];
+        TILE_LOOP(nzv) {
+            if (!on(c)) continue;
+            const float g = gu[(n + xd + r) * TP + c];
+            const bool isz = r < zd;
+            const int d_ = isz ? r : r - zd, w_ = isz ? zd : vd;
+            if (jzv >= 0) {
+                float* dst = isz ? a.gz : a.gv;
+                if (dst) dst[(jzv * a.B + b0 + c) * w_ + d_] += g;
+            } else {
+                float* dst = isz ? a.gzj : a.gvj;
+                if (dst) dst[((b0 + c) * a.n_events + ev) * w_ + d_] += g;
+            }
+        }
+        __syncthreads();
+    };
+
+    // Look-ahead (round 6): the rows a step reads from HBM -- the clocks, the dataset z | v, xs[k] (x_true[k] under INPUT_TRUE_X), the incoming
+    // gradient of grid point k --
+    // are requested one step early into registers (items tid + 256 j, j < LA: up to 32 rows each; rows beyond that are loaded where they are
+    // used), so that their latency hides behind the previous step instead of standing at the top and the bottom of every step.
+    constexpr int LA = 2;
+    float la_x[LA], la_g[LA], la_zv[LA], la_t = 0.0f, la_tn = 0.0f;
+    auto look_ahead = [&](long long kk) {       // grid point kk >= 0
+#pragma unroll
+        for (int j = 0; j < LA; ++j) {
+            const int idx = tid + NT * j;
+            const int ix = idx < xd * TB ? idx : 0, rx = ix / TB, cx = ix % TB;
+            la_x[j] = xsrc[(kk * a.B + gb(cx)) * xd + rx];
+            la_g[j] = a.gxs[(kk * a.B + gb(cx)) * xd + rx];
+            const int iz = idx < nzv * TB ? idx : 0, rz = iz / TB;
+            const long long b = gb(iz % TB);
+            la_zv[j] = nzv == 0 ? 0.0f : (rz < zd ? a.z.p[kk * a.z.st + b * a.z.sb + rz] : a.v.p[kk * a.v.st + b * a.v.sb + (rz - zd)]);
+        }
+        if (tid < TB) la_t = a.t.p[kk * a.t.st + gb(tid) * a.t.sb];
+    };
+    if (a.T >= 2) {
+        if (tid < TB) la_tn = a.t.p[(a.T - 1) * a.t.st + gb(tid) * a.t.sb];
+        look_ahead(a.T - 2);
+    }
+    for (long long k = a.T - 2; k >= 0; --k) {
+        const int ev = a.ev ? a.ev[k] : -1;
+        if (tid < TB) dts[tid] = la_tn - la_t;
+        float gx_in[LA];                             // the incoming gradient of grid point k, consumed at the bottom of the step
+#pragma unroll
+        for (int j = 0; j < LA; ++j) {
+            const int idx = tid + NT * j;
+            gx_in[j] = la_g[j];
+            if (idx < xd * TB) x0[(idx / TB) * TP + idx % TB] = la_x[j];
+            if (idx < nzv * TB && ev < 0) ext[(idx / TB) * TP + idx % TB] = la_zv[j];
+        }
+        for (int idx = tid + NT * LA; idx < xd * TB; idx += NT) x0[(idx / TB) * TP + idx % TB] = xsrc[(k * a.B + gb(idx % TB)) * xd + idx / TB];
+        TILE_LOOP(nzv) {
+            if (ev < 0 && idx < NT * LA) continue;                                      // (came through the look-ahead registers)
+            const long long b = gb(c);
+            float v;
+            if (r < zd) v = ev >= 0 ? a.zj[b * a.zjb + ev * a.zje + r] : a.z.p[k * a.z.st + b * a.z.sb + r];
+            else v = ev >= 0 ? a.vj[b * a.vjb + ev * a.vje + (r - zd)] : a.v.p[k * a.v.st + b * a.v.sb + (r - zd)];
+            ext[r * TP + c] = v;
+        }
+        if (tid < TB) la_tn = la_t;
+        if (k > 0) look_ahead(k - 1);
+        __syncthreads();
+        if (dae) {
+            // (1) AE head at the end of step k: i_{k+1} = g(x_{k+1}; z[k+1], v[k+1]) carries gic
+            //     (tx: the head read x_true[k+1] and its x-adjoint is dropped -- gx0 is rewritten in (3b))
+            TILE_LOOP(xd) xst[r * TP + c] = xsrc[((k + 1) * a.B + gb(c)) * xd + r];
+            __syncthreads();
+            ae_vjp(xst, k + 1, -1, gic, tx ? gx0 : gxc);
+            // (2) algebraic input of this step's DE (ti: the dataset row, also on event steps)
+            if (ti) {
+                TILE_LOOP(id) ext[(nzv + r) * TP + c] = a.it[(k * a.B + gb(c)) * id + r];
+            } else if (ev >= 0) {
+                const float* xr = x0;
+                if (tx) {       // the event-time head reads the RUNNING state xs[k], not the row the DE starts from (xst is free until (3a))
+                    TILE_LOOP(xd) xst[r * TP + c] = a.xs[(k * a.B + gb(c)) * xd + r];
+                    __syncthreads();
+                    xr = xst;
+                }
+                ae_input(xr, -1);
+                if constexpr (STR >= 1) g_forward_str(a.ae, a.fimgA, acts, qb, qoA, ActCtx{act.ae, upre}); else g_forward(a.ae, acts, wbuf, ActCtx{act.ae, upre});
+                const float* out = acts + a.ae.act[a.ae.L] * TP;
+                TILE_LOOP(id) ext[(nzv + r) * TP + c] = out[r * TP + c];
+            } else {
+                TILE_LOOP(id) ext[(nzv + r) * TP + c] = a.is_[(k * a.B + gb(c)) * id + r];
+            }
+            __syncthreads();
+        }
+        // (3a) stage inputs and slopes
+        for (int s = 0; s < S; ++s) {
+            TILE_LOOP(xd) {
+                float acc = 0.0f;
+                for (int j = 0; j < s; ++j) {      // (the tableau build skips a coefficient that is exactly 0)
+                    const float cf = coef_a(a.method, ks, nx, s, j);
+                    if constexpr (Bd::rk) { if (cf != 0.0f) acc += cf * ks[j * nx + r * TP + c]; } else acc += cf * ks[j * nx + r * TP + c];
+                }
+                xst[s * nx + r * TP + c] = s == 0 ? x0[r * TP + c] : x0[r * TP + c] + dts[c] * acc;
+            }
+            __syncthreads();
+            if (s + 1 < S) {               // (the last stage's slope feeds no stage input: its evaluation is (3b)'s first, not done here)
+                de_input(xst + s * nx);
+                if constexpr (REG) g_forward_reg(a, acts, qb, qo, rfw, ActCtx{act.de, upre});
+                else if constexpr (STR == 2) g_forward_str(a.de, a.fimg, acts, qb, qo, ActCtx{act.de, upre});
+                else g_forward(a.de, acts, wbuf, ActCtx{act.de, upre});
+                const float* out = acts + a.de.act[a.de.L] * TP;
+                TILE_LOOP(xd) ks[s * nx + r * TP + c] = out[r * TP + c];
+                __syncthreads();
+            }
+        }
+        // (3b) stages backwards
+        TILE_LOOP(xd) {
+            const float g1 = gxc[r * TP + c];
+            gx0[r * TP + c] = g1;
+            for (int s = 0; s < S; ++s) gks[s * nx + r * TP + c] = dts[c] * coef_b(a.method, ks, nx, s) * g1;
+        }
+        TILE_LOOP(ne) gext[r * TP + c] = 0.0f;
+        __syncthreads();
+        for (int s = S - 1; s >= 0; --s) {
+            de_input(xst + s * nx);
+            if constexpr (REG) { if (PSNODE_K5_ABL != 3) g_forward_reg(a, acts, qb, qo, rfw, ActCtx{act.de, upre}); }
+            else if constexpr (STR == 2) g_forward_str(a.de, a.fimg, acts, qb, qo, ActCtx{act.de, upre});
+            else g_forward(a.de, acts, wbuf, ActCtx{act.de, upre});
+            TILE_LOOP(xd) dA[r * TP + c] = gks[s * nx + r * TP + c];
+            __syncthreads();
+            const float* gu = REG ? g_vjp_reg<gg>(a, acts, dA, dB, gacc_l, tmg, qb, qo, rbw, ActCtx{act.de, upre})
+                                  : (STR == 2 ? g_vjp_str<gg>(a.de, a.timg, acts, dA, dB, gacc_l, tmg, qb, qo, ActCtx{act.de, upre})
+                                              : g_vjp<gg>(a.de, acts, dA, dB, gacc_l, gacc_g, wbuf, ActCtx{act.de, upre}));
+            TILE_LOOP(n) {
+                const float gs = gu[(n + r) * TP + c] + gu[(2 * n + r) * TP + c];
+                ga0s[r * TP + c] += gu[r * TP + c] - gu[(n + r) * TP + c];
+                if (r < xd) {
+                    gx0[r * TP + c] += gs;
+                    for (int j = 0; j < s; ++j) {
+                        if constexpr (Bd::rk) { const float cf = coef_a(a.method, ks, nx, s, j); if (cf != 0.0f) gks[j * nx + r * TP + c] += dts[c] * cf * gs; }
+                        else gks[j * nx + r * TP + c] += dts[c] * coef_a(a.method, ks, nx, s, j) * gs;
+                    }
+                } else {
+                    gext[(r - xd) * TP + c] += gs;
+                }
+            }
+            __syncthreads();
+        }
+        // tx: the step started from a dataset row -- its start adjoint goes nowhere (an ODE keeps step 0's: grad_x0 = grad_xs[0] + it), and
+        // gx0 from here on collects what still reaches the running state xs[k]: the event-time head's x-adjoint
+        if (tx && (dae || k > 0)) { TILE_LOOP(xd) gx0[r * TP + c] = 0.0f; }
+        // (4) gradients of this step's external inputs
+        TILE_LOOP(nzv) {
+            if (!on(c)) continue;
+            const float g = gext[r * TP + c];
+            const bool isz = r < zd;
+            const int d_ = isz ? r : r - zd, w_ = isz ? zd : vd;
+            float* dst = isz ? a.gz : a.gv;
+            float* dj = isz ? a.gzj : a.gvj;
+            if (ev >= 0) {
+                if (dj) dj[((b0 + c) * a.n_events + ev) * w_ + d_] = g;
+                if (dst) dst[(k * a.B + b0 + c) * w_ + d_] = 0.0f;
+            } else if (dst) {
+                dst[(k * a.B + b0 + c) * w_ + d_] = g;
+            }
+        }
+        if (dae) {
+            __syncthreads();
+            if (ti) {        // the DE read i_true[k]: nothing flows back through the algebraic variable
+                TILE_LOOP(id) gic[r * TP + c] = (on(c) && a.gis) ? a.gis[(k * a.B + gb(c)) * id + r] : 0.0f;
+            } else if (ev >= 0) {   // i_in = g(x_k; jumps): its gradient flows into x_k and the jump inputs; i_k itself was unused
+                const float* xr = x0;
+                if (tx) {    // (the stages are done with xst)
+                    TILE_LOOP(xd) xst[r * TP + c] = a.xs[(k * a.B + gb(c)) * xd + r];
+                    __syncthreads();
+                    xr = xst;
+                }
+                ae_vjp(xr, -1, ev, gext + nzv * TP, gx0);
+                TILE_LOOP(id) gic[r * TP + c] = (on(c) && a.gis) ? a.gis[(k * a.B + gb(c)) * id + r] : 0.0f;
+            } else {
+                TILE_LOOP(id) gic[r * TP + c] = gext[(nzv + r) * TP + c] + ((on(c) && a.gis) ? a.gis[(k * a.B + gb(c)) * id + r] : 0.0f);
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < LA; ++j) {
+            const int idx = tid + NT * j;
+            if (idx < xd * TB) gxc[(idx / TB) * TP + idx % TB] = gx0[(idx / TB) * TP + idx % TB] + (on(idx % TB) ? gx_in[j] : 0.0f);
+        }
+        for (int idx = tid + NT * LA; idx < xd * TB; idx += NT) {
+            const int r = idx / TB, c = idx % TB;
+            gxc[r * TP + c] = gx0[r * TP + c] + (on(c) ? a.gxs[(k * a.B + gb(c)) * xd + r] : 0.0f);
+        }
+        __syncthreads();
+    }
+    if (dae) {   // i_0 = g(x_0; z[0], v[0])   (my_solvers.py:95)
+        TILE_LOOP(xd) x0[r * TP + c] = xsrc[gb(c) * xd + r];
+        __syncthreads();
+        ae_vjp(x0, 0, -1, gic, tx ? gx0 : gxc);
+    }
+    TILE_LOOP(xd) if (on(c)) a.gx0[(b0 + c) * xd + r] = gxc[r * TP + c];
+    TILE_LOOP(n) if (on(c)) a.ga0[(b0 + c) * n + r] = ga0s[r * TP + c];
+    float* wp = a.wpart + (size_t)blockIdx.x * (a.de.np + (dae ? a.ae.np : 0));
+    // the LDS accumulators -> this workgroup's partial in nn.Linear order (tile-major ones un-permuted)
+    // (volatile: the global tile-major slices were written by other lanes of this workgroup; read them past the vector L1)
+    auto unpermute = [&](const GMlp& m, const volatile float* base, float* dst) {
+        for (int l = 0; l < m.L; ++l) {
+            const int N = m.out_dim[l], K = l ? m.out_dim[l - 1] : m.in_dim, ntk = (K + 15) / 16;
+            const volatile float* tw = base + tm_dw_off(m, l);
+            for (int e = tid; e < N * K; e += NT) {
+                const int j = e / K, k = e % K;
+                dst[m.gw[l] + e] = tw[(((j >> 4) * ntk + (k >> 4)) * 64 + ((j & 15) >> 2) * 16 + (k & 15)) * 4 + (j & 3)];
+            }
+            for (int e = tid; e < N; e += NT) dst[m.gb[l] + e] = base[tm_db_off(m, l) + e];
+        }
+    };
+    if constexpr (!ggA) {
+        if (dae) {
+            if constexpr (AE_TM) unpermute(a.ae, gacc_l + ae_at, wp + a.de.np);
+            else for (int e = tid; e < a.ae.np; e += NT) wp[a.de.np + e] = gacc_l[ae_at + e];
+        }
+    }
+    if constexpr (!gg) {
+        if constexpr (DE_TM) unpermute(a.de, gacc_l, wp);
+        else for (int e = tid; e < a.de.np; e += NT) wp[e] = gacc_l[e];
+    }
+    if constexpr (gg && DE_TM) { __threadfence(); __syncthreads(); unpermute(a.de, tmg, wp); }
+    if constexpr (ggA && AE_TM) { if (dae) { __threadfence(); __syncthreads(); unpermute(a.ae, tmgA, wp + a.de.np); } }
+#undef TILE_LOOP

@@ -1,7 +1,23 @@
-// K5 with a launch-time Butcher tableau (psnode_rk_tableau_f32) and every activation kind: psnode_generic_bwd.hip compiled a fourth time, on
-// top of the pre-activation build's macros (PSNODE_K5_ACT_BUILD, PSNODE_K5_PRE_BUILD), with PSNODE_K5_RK_BUILD.  A translation unit of its
-// own, so that the kernels of psnode_generic_bwd.o, psnode_generic_bwd_act.o and psnode_generic_bwd_pre.o stay exactly what they are.
-#define PSNODE_K5_ACT_BUILD 1
-#define PSNODE_K5_PRE_BUILD 1
-#define PSNODE_K5_RK_BUILD 1
-#include "psnode_generic_bwd.hip"
+// K5 with a launch-time Butcher tableau (psnode_rk_tableau_f32) and every activation kind: the BuildRk object of psnode_generic_bwd_impl.h.
+// A translation unit of its own, so that the kernels of psnode_generic_bwd.o, psnode_generic_bwd_act.o and psnode_generic_bwd_pre.o stay
+// exactly what they are.
+#include "psnode_generic_build.h"
+namespace psnode { namespace { using Bd = BuildRk; } }
+#include "psnode_generic_bwd_impl.h"
+
+namespace psnode {
+namespace {
+
+template <bool gg, bool REG, bool ggA = gg, int STR = 0>
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(Bd::two_waves(gg, STR), 8))) void generic_backward_rk_kernel(const GBwd a, const ActPair act, const psnode_rk_tableau_f32 rk) {
+#include "psnode_generic_bwd_body.h"
+}
+template <> struct GenericBwdKernels<Bd> {
+    template <bool gg, bool REG, bool ggA, int STR> static constexpr auto get() { return &generic_backward_rk_kernel<gg, REG, ggA, STR>; }
+};
+
+}  // namespace
+
+template int generic_backward_launch<Bd>(const GenericBwdCall&, const ActPair*, float*, hipStream_t);
+
+}  // namespace psnode

@@ -207,7 +207,7 @@ def test_ode_training(method, act):
         _close(got[k], r, f"grad {k}")
 
 
-# which K5 path each shape takes (psnode_generic_bwd.hip, gbwd_mode, with the pre build's u rows counted):
+# which K5 path each shape takes (psnode_generic_bwd_impl.h, gbwd_mode, with the pre build's u rows counted):
 K5_PATHS = {
     "register, LDS accumulators": (8, 2, (64, 64, 64)),
     "streamed, global accumulators": (20, 3, (96, 96)),

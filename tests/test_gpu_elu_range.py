@@ -12,7 +12,7 @@ Which form of ELU each kernel carries (read from csrc/):
   elu_quad / elu_pair (plain domain)
         every save=True instance of those, K0 (`generic`) in its register / wide-register / LDS / streamed forms, K3a / K3c / K3w;
   the DPP form of psnode_latent_dpp.hip     K3f (hidden 16);
-  elu1 (expm1f; psnode_generic_bwd.hip: K5_ACT1)     the recompute of K5's STAGED path only (its register and streamed paths
+  elu1 (expm1f; psnode_generic_bwd_impl.h: ActCtx::act1) the recompute of K5's STAGED path only (its register and streamed paths
         recompute with elu_quad): reached at hidden (256, 256), the shape test_gpu_activations_pre.py's K5_PATHS files under "staged";
   ELU' = med3(h, -2, 0) + 1 of the stored or recomputed h       K4x, K4f, K5, K7f.
 The probes below do not trust this table: an instance gets the plain-domain contract unless it is an inference instance of K1 / K1x /

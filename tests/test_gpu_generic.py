@@ -1,4 +1,4 @@
-"""The generic integrator K0 (csrc/psnode_generic.hip) in each of its three forms, against the CPU oracle: the shapes outside the
+"""The generic integrator K0 (csrc/psnode_generic_impl.h) in each of its three forms, against the CPU oracle: the shapes outside the
 specialised integrators' classes -- x_dim > 16, z + v + i > 8, depth != 3 hidden layers, mixed and very wide layers; all of them data- or
 user-defined upstream (neural_00_ODE_01_no_encode.py:293).
   register form : layers of <= 64 units, first contraction <= 128 columns (the wave's MFMA A operands stay in VGPRs);
