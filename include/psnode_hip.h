@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define PSNODE_ABI_VERSION 10    /* 10 also carries the additive psnode_act_f32 / *_act_* and psnode_rk_tableau_f32 / *_rk_* entry points (end of this file) */
+#define PSNODE_ABI_VERSION 10    /* 10 also carries the additive psnode_act_f32 / *_act_*, psnode_rk_tableau_f32 / *_rk_* and psnode_substeps_f32 / *_sub_* entry points (end of this file) */
 #define PSNODE_MAX_LAYERS 8      /* Linear layers per MLP */
 #define PSNODE_MAX_WIDTH 1024    /* widest layer OUTPUT the kernels accept */
 #define PSNODE_MAX_IN_WIDTH 2048 /* widest first-layer INPUT (the latent DE of DAE_02 at --hidden 128 is 12 x 128 = 1536 wide) */
@@ -724,6 +724,51 @@ size_t psnode_dae_backward_rk_workspace_bytes(const psnode_dae_bwd_tf_args_f32* 
                                               const psnode_act_f32* ae_act, const psnode_rk_tableau_f32* tab);
 int32_t psnode_dae_backward_rk_f32(const psnode_dae_bwd_tf_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
                                    const psnode_rk_tableau_f32* tab, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- Sub-steps per grid interval on the generic kernels (additive to ABI 10; DESIGN.md "Sub-steps per grid interval").
+ * With substeps = n every grid interval [t[k], t[k+1]] is integrated in n equal sub-steps of h = (t[k+1] - t[k]) / n (one correctly rounded
+ * fp32 division per interval and trajectory).  The interval's external inputs -- z | v of grid point k, or the jumped values on an interval
+ * that starts with an event -- are held over all n sub-steps; under PSNODE_FLAG_INPUT_TRUE_X only sub-step 0 starts from the dataset row;
+ * under PSNODE_FLAG_INPUT_TRUE_I every sub-step reads i[k].  A DAE that integrates its own algebraic variable re-evaluates the head at the
+ * start of every sub-step j >= 1, i = g(state; z | v of the interval): the algebraic variable follows the state inside the interval.
+ * Outputs stay on the caller's grid: x_out [T,B,x_dim], i_out [T,B,i_dim].
+ * x_sub [T-1, n-1, B, x_dim], contiguous and caller-owned like save_xstage: row (k, j-1) is the start state of sub-step j of interval k,
+ * 1 <= j < n.  A forward call writes it when the pointer is not NULL (a training forward); a backward call reads it and never writes it.
+ * Rules of every _sub entry point (they take what the _rk entry points take, plus this struct):
+ *   - a NULL struct gives PSNODE_ERR_NULL, substeps outside 1..1024 PSNODE_ERR_DIMS;
+ *   - substeps == 1 forwards to the _rk entry point (tableau given) or the _act entry point (tableau NULL), x_sub is not touched;
+ *   - otherwise: a NULL act is ELU(1); a NULL tableau is the built-in `method` of the args written as its tableau (the 3/8 rule then
+ *     differs from PSNODE_RK4_38 by rounding only); the call runs K0 / K5 in a build of their own, so `kernel` must be PSNODE_KERNEL_AUTO
+ *     or _GENERIC and the save_* / saved_* pointers NULL (PSNODE_ERR_UNSUPPORTED), a teacher-forced backward needs ELU(1), and the backward
+ *     fits the shapes the tableau build fits;
+ *   - a backward call with substeps > 1, T >= 2 and a NULL x_sub gives PSNODE_ERR_NULL.
+ * Every check returns its status before anything is launched.  The _supported queries answer 1 / 0 for the same rules (dims only; x_sub is
+ * not looked at).  Workspaces: those of the _rk entry points (psnode_dae_backward_sub_workspace_bytes for the DAE backward). */
+typedef struct {
+    int32_t substeps;      /* 1..1024 */
+    float* x_sub;          /* [T-1, substeps-1, B, x_dim] or NULL (forward); required by a backward call with substeps > 1 */
+} psnode_substeps_f32;
+
+int32_t psnode_ode_integrate_sub_supported(const psnode_ode_args_f32* args, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
+                                           const psnode_substeps_f32* sub);
+int32_t psnode_ode_integrate_sub_f32(const psnode_ode_args_f32* args, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
+                                     const psnode_substeps_f32* sub, void* workspace, size_t workspace_bytes, void* stream);
+int32_t psnode_dae_integrate_sub_supported(const psnode_dae_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                           const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub);
+int32_t psnode_dae_integrate_sub_f32(const psnode_dae_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                     const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, void* workspace, size_t workspace_bytes,
+                                     void* stream);
+int32_t psnode_ode_backward_sub_supported(const psnode_ode_bwd_args_f32* args, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
+                                          const psnode_substeps_f32* sub);
+int32_t psnode_ode_backward_sub_f32(const psnode_ode_bwd_args_f32* args, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
+                                    const psnode_substeps_f32* sub, void* workspace, size_t workspace_bytes, void* stream);
+int32_t psnode_dae_backward_sub_supported(const psnode_dae_bwd_tf_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                          const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub);
+size_t psnode_dae_backward_sub_workspace_bytes(const psnode_dae_bwd_tf_args_f32* args, const psnode_act_f32* de_act,
+                                               const psnode_act_f32* ae_act, const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub);
+int32_t psnode_dae_backward_sub_f32(const psnode_dae_bwd_tf_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                    const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, void* workspace, size_t workspace_bytes,
+                                    void* stream);
 
 #ifdef __cplusplus
 }

@@ -32,7 +32,9 @@ ABI_VERSION = 10         # == PSNODE_ABI_VERSION of include/psnode_hip.h (2: rou
                          #     hidden-layer activations other than ELU(1) on the generic kernels K0 / K5;
                          #     additive, same version: psnode_dae_bwd_tf_args_f32 and psnode_dae_backward_tf_* -- the teacher-forced DAE backward on K5;
                          #     additive, same version: psnode_rk_tableau_f32 and the psnode_{ode,dae}_{integrate,backward}_rk_* entry points --
-                         #     explicit Runge-Kutta tableaus of up to four stages on K0 / K5)
+                         #     explicit Runge-Kutta tableaus of up to four stages on K0 / K5;
+                         #     additive, same version: psnode_substeps_f32 and the psnode_{ode,dae}_{integrate,backward}_sub_* entry points --
+                         #     sub-steps per grid interval on K0 / K5)
 LIB_NAME = "libpsnode_hip.so"
 # PSNODE_LIB_PATH lets kernel experiments (profiles/scripts/*) load an alternative build of the same ABI
 LIB_PATH = os.environ.get("PSNODE_LIB_PATH") or os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
@@ -62,6 +64,9 @@ EXPORTS = (
     "psnode_ode_integrate_rk_supported", "psnode_ode_integrate_rk_f32", "psnode_dae_integrate_rk_supported", "psnode_dae_integrate_rk_f32",
     "psnode_ode_backward_rk_supported", "psnode_ode_backward_rk_f32",
     "psnode_dae_backward_rk_supported", "psnode_dae_backward_rk_workspace_bytes", "psnode_dae_backward_rk_f32",
+    "psnode_ode_integrate_sub_supported", "psnode_ode_integrate_sub_f32", "psnode_dae_integrate_sub_supported", "psnode_dae_integrate_sub_f32",
+    "psnode_ode_backward_sub_supported", "psnode_ode_backward_sub_f32",
+    "psnode_dae_backward_sub_supported", "psnode_dae_backward_sub_workspace_bytes", "psnode_dae_backward_sub_f32",
 )
 
 
@@ -92,6 +97,12 @@ class RkTableauF32(ctypes.Structure):
     _fields_ = [("stages", c_int32), ("a", (ctypes.c_float * 4) * 4), ("b", ctypes.c_float * 4)]
 
 
+class SubstepsF32(ctypes.Structure):
+    """psnode_substeps_f32: sub-steps per grid interval and the sub-state rows [T-1, substeps-1, B, x_dim] (NULL: a forward call keeps none)."""
+    _fields_ = [("substeps", c_int32), ("x_sub", c_void_p)]
+
+
+MAX_SUBSTEPS = 1024
 ACT_ELU, ACT_TANH, ACT_SIGMOID, ACT_RELU, ACT_LEAKY_RELU, ACT_SOFTPLUS = 0, 1, 2, 3, 4, 5
 # the pre-activation family (bit 5): derivatives that need the pre-activation u, kept by K5's pre build
 ACT_SILU, ACT_GELU, ACT_GELU_TANH, ACT_MISH = 32, 33, 34, 35
@@ -312,6 +323,15 @@ def load():
         f.restype, f.argtypes = c_int32, [ctypes.POINTER(args_t)] + [act_p] * n_act + [rk_p, c_void_p, c_size_t, c_void_p]
     lib.psnode_dae_backward_rk_workspace_bytes.restype = c_size_t
     lib.psnode_dae_backward_rk_workspace_bytes.argtypes = [ctypes.POINTER(DaeBwdTfArgsF32), act_p, act_p, rk_p]
+    sub_p = ctypes.POINTER(SubstepsF32)
+    for name, args_t, n_act in (("ode_integrate", OdeArgsF32, 1), ("dae_integrate", DaeArgsF32, 2), ("ode_backward", OdeBwdArgsF32, 1),
+                                ("dae_backward", DaeBwdTfArgsF32, 2)):
+        q = getattr(lib, f"psnode_{name}_sub_supported")
+        q.restype, q.argtypes = c_int32, [ctypes.POINTER(args_t)] + [act_p] * n_act + [rk_p, sub_p]
+        f = getattr(lib, f"psnode_{name}_sub_f32")
+        f.restype, f.argtypes = c_int32, [ctypes.POINTER(args_t)] + [act_p] * n_act + [rk_p, sub_p, c_void_p, c_size_t, c_void_p]
+    lib.psnode_dae_backward_sub_workspace_bytes.restype = c_size_t
+    lib.psnode_dae_backward_sub_workspace_bytes.argtypes = [ctypes.POINTER(DaeBwdTfArgsF32), act_p, act_p, rk_p, sub_p]
     lib.psnode_mlp_rows_backward_workspace_bytes.restype = c_size_t
     lib.psnode_mlp_rows_backward_workspace_bytes.argtypes = [ctypes.POINTER(MlpF32), c_int64]
     lib.psnode_mlp_rows_backward_f32.restype = c_int32

@@ -41,13 +41,18 @@ def latent_wide_training_fits(method, de, ae, hidden, T, B, dev) -> bool:
     return need <= free // 2
 
 
-def ode_training_supported(method, layers, x_dim, z_dim, T, B, kernel="auto", act=None, input_true_x=False) -> bool:
+def ode_training_supported(method, layers, x_dim, z_dim, T, B, kernel="auto", act=None, input_true_x=False, substeps=1) -> bool:
     """What the solver asks before it routes a call that needs autograd to the fused forward + backward pair.  act (fused.Act; None =
     ELU(1)): an activation other than ELU(1) trains on K0 + K5 alone, so K5 answers.  input_true_x: teacher-forced training -- K4f's
     recompute form on kernel "auto" / "mfma" where the shape is its, else K5 on "auto" / "generic"; ELU(1) only.
-    method a fused.Tableau: K0 + K5 on kernel "auto" / "generic" (K5's tableau build answers for its fit), the same teacher-forcing rule."""
+    method a fused.Tableau: K0 + K5 on kernel "auto" / "generic" (K5's tableau build answers for its fit), the same teacher-forcing rule.
+    substeps > 1: K0 + K5 in their sub-step builds on kernel "auto" / "generic" (K5's answers for its fit), the same teacher-forcing rule."""
     if _is_tableau(method) and kernel not in ("auto", "generic"):
         return False
+    if substeps != 1:
+        if kernel not in ("auto", "generic") or (input_true_x and act is not None):
+            return False
+        return fused.ode_backward_supported(method, layers, x_dim, z_dim, kernel, act=act, substeps=substeps)
     if input_true_x:
         if act is not None:
             return False
@@ -66,12 +71,18 @@ def _dae_tf_on_k7f(method, kernel, de, ae, x_dim, z_dim, v_dim, i_dim) -> bool:
 
 
 def dae_training_supported(method, de, ae, x_dim, z_dim, v_dim, i_dim, T, B, act=None, kernel="auto", input_true_x=False,
-                           input_true_i=False) -> bool:
+                           input_true_i=False, substeps=1) -> bool:
     """act: None (both MLPs ELU(1)) or (de_act, ae_act); an activation other than ELU(1) trains on K0 + K5 alone, so K5 answers.
     input_true_x / input_true_i: teacher-forced training (T >= 2, ELU(1) only) -- K7f's recompute form on kernel "auto" / "mfma" where the
-    shape is its, else K5 on "auto" / "generic".  method a fused.Tableau: K0 + K5 on kernel "auto" / "generic", the same rules."""
+    shape is its, else K5 on "auto" / "generic".  method a fused.Tableau: K0 + K5 on kernel "auto" / "generic", the same rules.
+    substeps > 1: K0 + K5 in their sub-step builds on kernel "auto" / "generic", the same rules."""
     if _is_tableau(method) and kernel not in ("auto", "generic"):
         return False
+    if substeps != 1:
+        non_elu = act is not None and any(a is not None for a in act)
+        if kernel not in ("auto", "generic") or ((input_true_x or input_true_i) and (T < 2 or non_elu)):
+            return False
+        return fused.dae_backward_supported(method, de, ae, x_dim, z_dim, v_dim, i_dim, act=act, kernel=kernel, substeps=substeps)
     if input_true_x or input_true_i:
         if T < 2 or (act is not None and any(a is not None for a in act)):
             return False
@@ -215,8 +226,41 @@ class _FusedOde(torch.autograd.Function):
         return (None, None, None, None, None, gx0, gz, ga0, gzj if ctx.needs_input_grad[8] else None, *gpar)
 
 
+class _FusedOdeSub(torch.autograd.Function):
+    """integrate_ODE with substeps > 1, plain or teacher-forced: K0 forward in its sub-step build, which also writes the start state of every
+    sub-step behind an interval's first (x_sub, saved next to xs), K5 backward in its sub-step build."""
+
+    @staticmethod
+    def forward(ctx, method, kernel, act, substeps, tx, event_idx, t, x0, z, all_initial, z_jump, *params):
+        layers = [(params[k], params[k + 1]) for k in range(0, len(params), 2)]
+        global last_saved_bytes
+        x_in = x0.detach().contiguous() if tx else x0.unsqueeze(0)      # tx: the whole dataset x [T,B,xd]
+        xs, x_sub = fused.ode_integrate(method, layers, t, x_in, z, all_initial, z_jump=z_jump, event_idx=event_idx, kernel=kernel,
+                                        input_true_x=tx, act=act, substeps=substeps, save_sub=True)
+        last_saved_bytes = x_sub.numel() * x_sub.element_size()
+        ctx.method, ctx.kernel, ctx.act, ctx.substeps, ctx.tx, ctx.event_idx, ctx.has_jump = method, kernel, act, substeps, tx, event_idx, z_jump is not None
+        # (tx: the backward starts every interval from the dataset row and reads no xs)
+        ctx.save_for_backward(t, z, all_initial, x_in if tx else xs, x_sub, *((z_jump,) if z_jump is not None else ()), *params)
+        return xs
+
+    @staticmethod
+    def backward(ctx, grad_xs):
+        saved = ctx.saved_tensors
+        t, z, a0, xs, x_sub = saved[:5]
+        z_jump = saved[5] if ctx.has_jump else None
+        params = saved[6 if ctx.has_jump else 5:]
+        layers = [(params[k], params[k + 1]) for k in range(0, len(params), 2)]
+        need_z = ctx.needs_input_grad[8]
+        gx0, gz, gzj, ga0, gpar = fused.ode_backward(ctx.method, layers, t, z, a0, xs, grad_xs, event_idx=ctx.event_idx, z_jump=z_jump,
+                                                     need_grad_z=need_z, need_grad_zj=bool(ctx.needs_input_grad[10]), kernel=ctx.kernel,
+                                                     input_true_x=ctx.tx, act=ctx.act, substeps=ctx.substeps, x_sub=x_sub)
+        if gz is None and need_z:
+            gz = torch.zeros_like(z)
+        return (None, None, None, None, None, None, None, None if ctx.tx else gx0, gz, ga0, gzj if ctx.needs_input_grad[10] else None, *gpar)
+
+
 def fused_ode_integrate(method, kernel, layers, t, x, z, all_initial, event_t=None, z_jump=None, check_events=False, input_true_x=False,
-                        x_init=None, act=None):
+                        x_init=None, act=None, substeps=1):
     """Differentiable fused integrate_ODE: gradients flow to x[0], z, all_initial, z_jump and the MLP.  input_true_x (teacher forcing,
     my_solvers.py:72-74): every step starts from the dataset row x[k]; gradients flow to z, all_initial, z_jump and the MLP (the dataset
     x gets none: callers whose x requires grad take the callback walk).  act: the MLP's activation (fused.Act), None = ELU(1); any other
@@ -227,6 +271,8 @@ def fused_ode_integrate(method, kernel, layers, t, x, z, all_initial, event_t=No
         z_jump = None
     params = [p for wb in layers for p in wb]
     x0 = x.detach() if input_true_x else (x[0] if x_init is None else x_init)     # (x_init: integrate_ODE's extension -- no SelectBackward)
+    if substeps != 1:
+        return _FusedOdeSub.apply(method, kernel, act, substeps, bool(input_true_x), event_idx, t, x0, z, all_initial, z_jump, *params)
     return _FusedOde.apply(method, kernel, act, event_idx, t, x0, z, all_initial, z_jump, *params)
 
 
@@ -325,8 +371,52 @@ class _FusedDaeTeacherForced(torch.autograd.Function):
                 g["z_jump"] if ctx.needs_input_grad[13] else None, g["v_jump"] if ctx.needs_input_grad[14] else None, *g["de"], *g["ae"])
 
 
+class _FusedDaeSub(torch.autograd.Function):
+    """integrate_DAE with substeps > 1, plain or teacher-forced: K0 forward and K5 backward in their sub-step builds, x_sub saved next to
+    xs / is.  The dataset rows of a teacher-forced call get no gradient."""
+
+    @staticmethod
+    def forward(ctx, method, kernel, act, substeps, tx, ti, event_idx, n_de, t, x_init, x, z, v, i, all_initial, z_jump, v_jump, *params):
+        de = [(params[k], params[k + 1]) for k in range(0, 2 * n_de, 2)]
+        ae = [(params[k], params[k + 1]) for k in range(2 * n_de, len(params), 2)]
+        non_elu = act is not None and any(a is not None for a in act)
+        xs, is_, x_sub = fused.dae_integrate(method, de, ae, x_init, t, x, z, v, i, all_initial, z_jump=z_jump, v_jump=v_jump, event_idx=event_idx,
+                                             kernel=kernel, input_true_x=tx, input_true_i=ti, act=act if non_elu else None, substeps=substeps,
+                                             save_sub=True)
+        global last_saved_bytes
+        last_saved_bytes = x_sub.numel() * x_sub.element_size()
+        ctx.method, ctx.kernel, ctx.act, ctx.substeps, ctx.tx, ctx.ti = method, kernel, act if non_elu else None, substeps, tx, ti
+        ctx.n_de, ctx.event_idx, ctx.has_zj, ctx.has_vj = n_de, event_idx, z_jump is not None, v_jump is not None
+        ctx.save_for_backward(t, z, v, all_initial, xs, is_, x_sub, x, i, *((z_jump,) if z_jump is not None else ()),
+                              *((v_jump,) if v_jump is not None else ()), *params)
+        return xs, is_
+
+    @staticmethod
+    def backward(ctx, grad_xs, grad_is):
+        sv = list(ctx.saved_tensors)
+        t, z, v, a0, xs, is_, x_sub, x, i = sv[:9]
+        k = 9
+        z_jump = sv[k] if ctx.has_zj else None
+        k += int(ctx.has_zj)
+        v_jump = sv[k] if ctx.has_vj else None
+        k += int(ctx.has_vj)
+        params = sv[k:]
+        de = [(params[q], params[q + 1]) for q in range(0, 2 * ctx.n_de, 2)]
+        ae = [(params[q], params[q + 1]) for q in range(2 * ctx.n_de, len(params), 2)]
+        common = dict(event_idx=ctx.event_idx, z_jump=z_jump, v_jump=v_jump, kernel=ctx.kernel, substeps=ctx.substeps, x_sub=x_sub)
+        if ctx.tx or ctx.ti:
+            g = fused.dae_backward_tf(ctx.method, de, ae, t, z, v, a0, xs, is_, grad_xs, grad_is, x_true=x if ctx.tx else None,
+                                      i_true=i if ctx.ti else None, **common)
+        else:
+            g = fused.dae_backward(ctx.method, de, ae, t, z, v, a0, xs, is_, grad_xs, grad_is, act=ctx.act, **common)
+        gz = g["z"] if g["z"] is not None else (torch.zeros_like(z) if ctx.needs_input_grad[11] else None)
+        gv = g["v"] if g["v"] is not None else (torch.zeros_like(v) if ctx.needs_input_grad[12] else None)
+        return (None, None, None, None, None, None, None, None, None, g["x_init"], None, gz, gv, None, g["all_initial"],
+                g["z_jump"] if ctx.needs_input_grad[15] else None, g["v_jump"] if ctx.needs_input_grad[16] else None, *g["de"], *g["ae"])
+
+
 def fused_dae_integrate(method, kernel, de_layers, ae_layers, x_init, t, z, v, i, all_initial, event_t=None, z_jump=None, v_jump=None,
-                        check_events=False, x=None, input_true_x=False, input_true_i=False, act=None):
+                        check_events=False, x=None, input_true_x=False, input_true_i=False, act=None, substeps=1):
     """Differentiable fused integrate_DAE: gradients flow to x_init, z, v, all_initial, the jump inputs and both MLPs.  Without teacher
     forcing `i` only provides the width of the algebraic variable.  input_true_x / input_true_i: `x` / `i` are the dataset rows the DE
     and the heads are fed (my_solvers.py:111-121); they get no gradient.  act: None or (de_act, ae_act) (fused.Act, None = ELU(1)); an
@@ -339,6 +429,10 @@ def fused_dae_integrate(method, kernel, de_layers, ae_layers, x_init, t, z, v, i
         z_jump = z_jump if (z_jump is not None and z_jump.shape[-1] > 0) else None
         v_jump = v_jump if (v_jump is not None and v_jump.shape[-1] > 0) else None
     params = [p for wb in list(de_layers) + list(ae_layers) for p in wb]
+    if substeps != 1:
+        xd_ = x.detach() if input_true_x else x_init.new_zeros((1, t.shape[1], 0))
+        return _FusedDaeSub.apply(method, kernel, act, substeps, bool(input_true_x), bool(input_true_i), event_idx, len(de_layers), t, x_init, xd_,
+                                  z, v, i.detach(), all_initial, z_jump, v_jump, *params)
     if input_true_x or input_true_i:
         xd_ = x.detach() if input_true_x else x_init.new_zeros((1, t.shape[1], 0))
         return _FusedDaeTeacherForced.apply(method, kernel, event_idx, len(de_layers), bool(input_true_x), bool(input_true_i), t, x_init, xd_,

@@ -245,5 +245,8 @@ hipError_t launch_generic_act(const IntegrateDev& a, bool dae, const ActPair& ac
 hipError_t launch_generic_pre(const IntegrateDev& a, bool dae, const ActPair& act, hipStream_t stream);
 // psnode_generic_rk.hip: K0 with the Butcher tableau `rk` in place of a.method, every activation kind (ELU(1) as ELU with alpha = 1)
 hipError_t launch_generic_rk(const IntegrateDev& a, bool dae, const ActPair& act, const psnode_rk_tableau_f32& rk, hipStream_t stream);
+// psnode_generic_sub.hip: the tableau build with sub.n sub-steps per grid interval (sub.x_sub: the sub-states for K5, or null)
+hipError_t launch_generic_sub(const IntegrateDev& a, bool dae, const ActPair& act, const psnode_rk_tableau_f32& rk, const SubDev& sub,
+                              hipStream_t stream);
 
 }  // namespace psnode

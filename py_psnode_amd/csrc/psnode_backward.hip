@@ -89,6 +89,7 @@ GenericBwdCall generic_bwd_call(const psnode_dae_bwd_args_f32& a) {
 }
 // act: the activations of a non-ELU(1) call, or nullptr
 int generic_backward(const GenericBwdCall& c, const ActPair* act, void* workspace, void* stream) {
+    if (c.rk && c.substeps > 1) return generic_backward_launch<BuildSub>(c, act, static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
     if (c.rk) return generic_backward_launch<BuildRk>(c, act, static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
     const auto launch = !act ? generic_backward_launch<BuildElu1> : (act_pair_pre(*act) ? generic_backward_launch<BuildPre> : generic_backward_launch<BuildAct>);
     return launch(c, act, static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
@@ -381,5 +382,104 @@ extern "C" int32_t psnode_dae_backward_rk_f32(const psnode_dae_bwd_tf_args_f32* 
     if (!workspace_ok(workspace, workspace_bytes, psnode_dae_backward_rk_workspace_bytes(a, de_act, ae_act, tab))) return PSNODE_ERR_WORKSPACE;
     GenericBwdCall c = generic_bwd_call(*b);
     c.flags = a->flags; c.xt = a->x_true; c.it = a->i_true; c.rk = tab;
+    return generic_backward(c, &p, workspace, stream);
+}
+
+// ---- sub-steps per grid interval (include/psnode_hip.h, psnode_substeps_f32): K5's sub-step build alone, under the rules of the tableau
+// build.  The struct is checked first (substeps == 1 leaves for the _rk / _act / _tf entry point there), then the act, the tableau (NULL:
+// the args' method as one); then NULL args -> dims -> unsupported -> pointers (x_sub among them) -> workspace, as above.
+extern "C" int32_t psnode_ode_backward_sub_supported(const psnode_ode_bwd_args_f32* a, const psnode_act_f32* de_act,
+                                                     const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub) {
+    if (!a || substeps_check(sub)) return 0;
+    if (sub->substeps == 1) return tab ? psnode_ode_backward_rk_supported(a, de_act, tab) : psnode_ode_backward_act_supported(a, de_act);
+    psnode_rk_tableau_f32 t;
+    if (sub_tableau(tab, a->method, t)) return 0;
+    return psnode_ode_backward_rk_supported(a, de_act, &t);
+}
+
+extern "C" int32_t psnode_ode_backward_sub_f32(const psnode_ode_bwd_args_f32* a, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
+                                               const psnode_substeps_f32* sub, void* workspace, size_t workspace_bytes, void* stream) {
+    int rc = substeps_check(sub);
+    if (rc) return rc;
+    if (sub->substeps == 1)
+        return tab ? psnode_ode_backward_rk_f32(a, de_act, tab, workspace, workspace_bytes, stream)
+                   : psnode_ode_backward_act_f32(a, de_act, workspace, workspace_bytes, stream);
+    ActPair p;
+    bool elu1 = true;
+    rc = act_pair(de_act, nullptr, p, elu1);
+    if (rc) return rc;
+    if (!a) return PSNODE_ERR_NULL;
+    psnode_rk_tableau_f32 t;
+    rc = sub_tableau(tab, a->method, t);
+    if (rc) return rc;
+    if (a->T < 1 || a->B < 1) return PSNODE_ERR_DIMS;
+    if (!rk_ode_ok(a, elu1)) return PSNODE_ERR_UNSUPPORTED;
+    if (!ptrs_ok(a) || (a->T >= 2 && !sub->x_sub)) return PSNODE_ERR_NULL;
+    if (!workspace_ok(workspace, workspace_bytes, generic_bwd_workspace_floats(&a->de, nullptr, a->B) * sizeof(float))) return PSNODE_ERR_WORKSPACE;
+    GenericBwdCall c = generic_bwd_call(*a);
+    c.rk = &t; c.substeps = sub->substeps; c.x_sub = sub->x_sub;
+    return generic_backward(c, &p, workspace, stream);
+}
+
+extern "C" int32_t psnode_dae_backward_sub_supported(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act,
+                                                     const psnode_act_f32* ae_act, const psnode_rk_tableau_f32* tab,
+                                                     const psnode_substeps_f32* sub) {
+    if (!a || substeps_check(sub)) return 0;
+    if (sub->substeps == 1 && tab) return psnode_dae_backward_rk_supported(a, de_act, ae_act, tab);
+    if (sub->substeps == 1) {
+        ActPair p;
+        bool elu1 = true;
+        if (act_pair(de_act, ae_act, p, elu1)) return 0;
+        if (elu1) return psnode_dae_backward_tf_supported(a);
+        return a->flags == 0 && psnode_dae_backward_act_supported(&a->base, de_act, ae_act);
+    }
+    psnode_rk_tableau_f32 t;
+    if (sub_tableau(tab, a->base.method, t)) return 0;
+    return psnode_dae_backward_rk_supported(a, de_act, ae_act, &t);
+}
+
+extern "C" size_t psnode_dae_backward_sub_workspace_bytes(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act,
+                                                          const psnode_act_f32* ae_act, const psnode_rk_tableau_f32* tab,
+                                                          const psnode_substeps_f32* sub) {
+    if (!psnode_dae_backward_sub_supported(a, de_act, ae_act, tab, sub)) return 0;
+    if (sub->substeps == 1 && !tab) {
+        ActPair p;
+        bool elu1 = true;
+        act_pair(de_act, ae_act, p, elu1);
+        return elu1 ? psnode_dae_backward_tf_workspace_bytes(a) : psnode_dae_backward_workspace_bytes(&a->base);
+    }
+    return generic_bwd_workspace_floats(&a->base.de, &a->base.ae, a->base.B) * sizeof(float);
+}
+
+extern "C" int32_t psnode_dae_backward_sub_f32(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                               const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, void* workspace,
+                                               size_t workspace_bytes, void* stream) {
+    int rc = substeps_check(sub);
+    if (rc) return rc;
+    ActPair p;
+    bool elu1 = true;
+    if (sub->substeps == 1) {
+        if (tab) return psnode_dae_backward_rk_f32(a, de_act, ae_act, tab, workspace, workspace_bytes, stream);
+        rc = act_pair(de_act, ae_act, p, elu1);
+        if (rc) return rc;
+        if (elu1) return psnode_dae_backward_tf_f32(a, workspace, workspace_bytes, stream);
+        if (!a) return PSNODE_ERR_NULL;
+        if (a->flags) return PSNODE_ERR_UNSUPPORTED;      // (teacher forcing: ELU(1) only)
+        return psnode_dae_backward_act_f32(&a->base, de_act, ae_act, workspace, workspace_bytes, stream);
+    }
+    rc = act_pair(de_act, ae_act, p, elu1);
+    if (rc) return rc;
+    if (!a) return PSNODE_ERR_NULL;
+    const psnode_dae_bwd_args_f32* b = &a->base;
+    psnode_rk_tableau_f32 t;
+    rc = sub_tableau(tab, b->method, t);
+    if (rc) return rc;
+    if (b->T < 1 || b->B < 1 || (a->flags && b->T < 2)) return PSNODE_ERR_DIMS;
+    if (!rk_dae_ok(a, elu1)) return PSNODE_ERR_UNSUPPORTED;
+    if (!ptrs_ok(b) || (b->T >= 2 && !sub->x_sub)) return PSNODE_ERR_NULL;
+    if (((a->flags & PSNODE_FLAG_INPUT_TRUE_X) && !a->x_true) || ((a->flags & PSNODE_FLAG_INPUT_TRUE_I) && !a->i_true)) return PSNODE_ERR_NULL;
+    if (!workspace_ok(workspace, workspace_bytes, generic_bwd_workspace_floats(&b->de, &b->ae, b->B) * sizeof(float))) return PSNODE_ERR_WORKSPACE;
+    GenericBwdCall c = generic_bwd_call(*b);
+    c.flags = a->flags; c.xt = a->x_true; c.it = a->i_true; c.rk = &t; c.substeps = sub->substeps; c.x_sub = sub->x_sub;
     return generic_backward(c, &p, workspace, stream);
 }

@@ -87,9 +87,10 @@ __global__ void event_table_kernel(long long n_steps, const float* clock, long l
 ViewDev view(const psnode_view_f32& v) { return ViewDev{v.ptr, v.stride_t, v.stride_b}; }
 
 // act: the hidden layers' activations of a non-ELU(1) call (K0 only), or nullptr; rk: the tableau of an _rk call (K0's tableau build, with
-// `act` always given), or nullptr
+// `act` always given), or nullptr; sub: the sub-steps of a _sub call (K0's sub-step build, with `act` and `rk` always given), or nullptr
 int dispatch(IntegrateDev& d, bool dae, int kernel, const psnode_mlp_f32* de, const psnode_mlp_f32* ae, void* workspace,
-             size_t workspace_bytes, hipStream_t stream, const ActPair* act = nullptr, const psnode_rk_tableau_f32* rk = nullptr) {
+             size_t workspace_bytes, hipStream_t stream, const ActPair* act = nullptr, const psnode_rk_tableau_f32* rk = nullptr,
+             const SubDev* sub = nullptr) {
     if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 255u)) return PSNODE_ERR_WORKSPACE;
     if (workspace_bytes < psnode_workspace_bytes(de, ae)) return PSNODE_ERR_WORKSPACE;
     float* ws = static_cast<float*>(workspace);
@@ -113,7 +114,9 @@ int dispatch(IntegrateDev& d, bool dae, int kernel, const psnode_mlp_f32* de, co
     } else {
         if (generic_lds_bytes(d, dae) > 160 * 1024) return PSNODE_ERR_UNSUPPORTED;
         e = launch_pack_image(d.de, dae ? &d.ae : nullptr, d.xd, d.xd + d.zd + (dae ? d.vd + d.id : 0), d.zd + (dae ? d.vd : 0), stream);
-        if (e == hipSuccess && rk)
+        if (e == hipSuccess && sub)
+            e = launch_generic_sub(d, dae, *act, *rk, *sub, stream);
+        else if (e == hipSuccess && rk)
             e = launch_generic_rk(d, dae, *act, *rk, stream);
         else if (e == hipSuccess)
             e = !act ? launch_generic(d, dae, stream) : (act_pair_pre(*act) ? launch_generic_pre(d, dae, *act, stream) : launch_generic_act(d, dae, *act, stream));
@@ -234,6 +237,26 @@ int rk_tableau_check(const psnode_rk_tableau_f32* tab) {
         }
     }
     return PSNODE_OK;
+}
+
+int sub_tableau(const psnode_rk_tableau_f32* tab, int method, psnode_rk_tableau_f32& out) {
+    if (tab) {
+        out = *tab;
+        return rk_tableau_check(tab);
+    }
+    if (method < PSNODE_EULER || method > PSNODE_RK4_38) return PSNODE_ERR_METHOD;
+    memset(&out, 0, sizeof(out));
+    out.stages = rk_stages(method);
+    for (int s = 0; s < out.stages; ++s) {
+        out.b[s] = rk_b(method, s);
+        for (int j = 0; j < s; ++j) out.a[s][j] = rk_a(method, s, j);
+    }
+    return PSNODE_OK;
+}
+
+int substeps_check(const psnode_substeps_f32* sub) {
+    if (!sub) return PSNODE_ERR_NULL;
+    return sub->substeps < 1 || sub->substeps > 1024 ? PSNODE_ERR_DIMS : PSNODE_OK;
 }
 
 int act_from_abi(const psnode_act_f32* in, ActDev& out, bool& is_elu1) {
@@ -452,6 +475,79 @@ int32_t psnode_dae_integrate_rk_f32(const psnode_dae_args_f32* args, const psnod
     rc = fill_dae(&c, d);
     if (rc) return rc;
     return dispatch(d, true, c.kernel, &c.de, &c.ae, workspace, workspace_bytes, static_cast<hipStream_t>(stream), &p, tab);
+}
+
+// ---- sub-steps per grid interval (include/psnode_hip.h, psnode_substeps_f32): K0's sub-step build alone.  The struct is checked first
+// (substeps == 1 leaves for the _rk / _act entry point there), then the act, the tableau (NULL: the args' method as one), the route.
+int32_t psnode_ode_integrate_sub_supported(const psnode_ode_args_f32* a, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
+                                           const psnode_substeps_f32* sub) {
+    if (!a || substeps_check(sub)) return 0;
+    if (sub->substeps == 1) return tab ? psnode_ode_integrate_rk_supported(a, de_act, tab) : psnode_ode_integrate_act_supported(a, de_act);
+    psnode_rk_tableau_f32 t;
+    if (sub_tableau(tab, a->method, t)) return 0;
+    return psnode_ode_integrate_rk_supported(a, de_act, &t);
+}
+
+int32_t psnode_ode_integrate_sub_f32(const psnode_ode_args_f32* args, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
+                                     const psnode_substeps_f32* sub, void* workspace, size_t workspace_bytes, void* stream) {
+    int rc = substeps_check(sub);
+    if (rc) return rc;
+    if (sub->substeps == 1)
+        return tab ? psnode_ode_integrate_rk_f32(args, de_act, tab, workspace, workspace_bytes, stream)
+                   : psnode_ode_integrate_act_f32(args, de_act, workspace, workspace_bytes, stream);
+    ActPair p;
+    bool elu1 = true;
+    rc = act_pair(de_act, nullptr, p, elu1);
+    if (rc) return rc;
+    if (!args) return PSNODE_ERR_NULL;
+    psnode_rk_tableau_f32 t;
+    rc = sub_tableau(tab, args->method, t);
+    if (rc) return rc;
+    if (!act_call_ok(args->kernel, args->save_act) || args->save_xstage) return PSNODE_ERR_UNSUPPORTED;      // K0 only
+    psnode_ode_args_f32 c = *args;
+    c.method = PSNODE_EULER;
+    IntegrateDev d;
+    rc = fill_ode(&c, d);
+    if (rc) return rc;
+    const SubDev sd{sub->substeps, sub->x_sub};
+    return dispatch(d, false, c.kernel, &c.de, nullptr, workspace, workspace_bytes, static_cast<hipStream_t>(stream), &p, &t, &sd);
+}
+
+int32_t psnode_dae_integrate_sub_supported(const psnode_dae_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                           const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub) {
+    if (!a || substeps_check(sub)) return 0;
+    if (sub->substeps == 1)
+        return tab ? psnode_dae_integrate_rk_supported(a, de_act, ae_act, tab) : psnode_dae_integrate_act_supported(a, de_act, ae_act);
+    psnode_rk_tableau_f32 t;
+    if (sub_tableau(tab, a->method, t)) return 0;
+    return psnode_dae_integrate_rk_supported(a, de_act, ae_act, &t);
+}
+
+int32_t psnode_dae_integrate_sub_f32(const psnode_dae_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                     const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, void* workspace, size_t workspace_bytes,
+                                     void* stream) {
+    int rc = substeps_check(sub);
+    if (rc) return rc;
+    if (sub->substeps == 1)
+        return tab ? psnode_dae_integrate_rk_f32(args, de_act, ae_act, tab, workspace, workspace_bytes, stream)
+                   : psnode_dae_integrate_act_f32(args, de_act, ae_act, workspace, workspace_bytes, stream);
+    ActPair p;
+    bool elu1 = true;
+    rc = act_pair(de_act, ae_act, p, elu1);
+    if (rc) return rc;
+    if (!args) return PSNODE_ERR_NULL;
+    psnode_rk_tableau_f32 t;
+    rc = sub_tableau(tab, args->method, t);
+    if (rc) return rc;
+    if (!act_call_ok(args->kernel, args->save_act) || args->save_xstage || args->save_ae_act || args->save_ev_act || args->save_ev_i)
+        return PSNODE_ERR_UNSUPPORTED;
+    psnode_dae_args_f32 c = *args;
+    c.method = PSNODE_EULER;
+    IntegrateDev d;
+    rc = fill_dae(&c, d);
+    if (rc) return rc;
+    const SubDev sd{sub->substeps, sub->x_sub};
+    return dispatch(d, true, c.kernel, &c.de, &c.ae, workspace, workspace_bytes, static_cast<hipStream_t>(stream), &p, &t, &sd);
 }
 
 int32_t psnode_ode_kernel_for(const psnode_ode_args_f32* a) {

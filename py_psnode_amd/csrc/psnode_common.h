@@ -54,6 +54,14 @@ struct IntegrateDev {
     unsigned k0_res;       // generic kernel: which layers' weight images are resident in LDS (bit l: DE layer l, bit 8 + l: AE layer l)
 };
 
+// Sub-steps per grid interval (psnode_substeps_f32, include/psnode_hip.h), as the sub-step builds of K0 / K5 take them: one further kernel
+// argument behind the tableau.  Every grid interval [t[k], t[k + 1]] runs n equal sub-steps; x_sub [T-1, n-1, B, xd] keeps the start state
+// of sub-steps 1 .. n-1 of every interval (row (k, j - 1): sub-step j) -- written by K0 when the pointer is not null, read by K5.
+struct SubDev {
+    int n;
+    float* x_sub;
+};
+
 // ELU(alpha=1) with the negative branch at expm1 quality: ATen's CPU kernel (what the reference runs) returns
 // expm1(x) for x <= 0 -- checked bitwise in the build container ("ELU").
 // libm flavour, used by the generic kernel:
@@ -314,6 +322,8 @@ struct GenericBwdCall {
     unsigned flags;            // PSNODE_FLAG_INPUT_TRUE_X / _I: the teacher-forced sweep (ELU(1) build only for now)
     const float *xt, *it;      // DAE: x_true / i_true [T,B,.] for the flags set (the ODE's dataset comes in as xs)
     const psnode_rk_tableau_f32* rk;      // generic_backward_launch<BuildRk>: the tableau (checked: rk_tableau_check); `method` is then not read
+    int substeps;              // generic_backward_launch<BuildSub> (with rk): sub-steps per grid interval, > 1, and the sub-states K0 wrote
+    const float* x_sub;        // [T-1, substeps-1, B, xd]
 };
 struct ActPair;     // psnode_act.h: the DE's and the AE's activation of a non-ELU(1) call
 size_t generic_bwd_workspace_floats(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, long long B);
@@ -323,12 +333,17 @@ int generic_bwd_fits(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, int xd,
 // K5's launcher (psnode_generic_bwd_impl.h), instantiated once per build policy (psnode_generic_build.h) in that policy's object: BuildElu1
 // (ignores `act`), BuildAct (the activations of psnode_act.h), BuildPre (those and the pre-activation family), BuildRk (the tableau build:
 // every activation kind -- `act` is required, ELU(1) runs as ELU with alpha = 1 -- and c.rk in place of c.method; it keeps the
-// pre-activations like the pre build).  psnode_backward.hip: generic_backward picks among them.
+// pre-activations like the pre build), BuildSub (the tableau build with c.substeps sub-steps per grid interval, read from c.x_sub).
+// psnode_backward.hip: generic_backward picks among them.
 template <class B>
 int generic_backward_launch(const GenericBwdCall& c, const ActPair* act, float* workspace, hipStream_t stream);
 // psnode_capi.hip: PSNODE_OK, PSNODE_ERR_NULL (no tableau) or PSNODE_ERR_METHOD (stages outside 1..4, a coefficient that is not finite, a
 // non-zero a[s][j] with j >= s or in a row / column >= stages, a non-zero b[s] with s >= stages)
 int rk_tableau_check(const psnode_rk_tableau_f32* tab);
+// the tableau of a sub-step call: *tab (checked), or -- tab NULL -- the built-in `method` written as one (PSNODE_ERR_METHOD outside 0..2)
+int sub_tableau(const psnode_rk_tableau_f32* tab, int method, psnode_rk_tableau_f32& out);
+// PSNODE_OK, PSNODE_ERR_NULL (no struct) or PSNODE_ERR_DIMS (substeps outside 1..1024)
+int substeps_check(const psnode_substeps_f32* sub);
 
 // psnode_latent.hip (direct_encode latent shapes, hidden_dim 16)
 bool latent_shape_ok(const IntegrateDev& a, bool dae);

@@ -11,6 +11,7 @@ template <bool DAE, int MODE, int ML, int QM = 4>
 __global__ __launch_bounds__(NT) void generic_kernel(const IntegrateDev a) {
     const NoActPair act;                   // no activation argument: ActCtx is empty
     const psnode_rk_tableau_f32 rk{};      // never read: the tableau code is under `if constexpr (Bd::rk)`
+    const SubDev sub{};                    // never read: the sub-step code is under `if constexpr (Bd::sub)`
 #include "psnode_generic_body.h"
 }
 template <> struct GenericKernels<Bd> {

@@ -1,7 +1,9 @@
-// The body of K0's kernel (psnode_generic_impl.h), as text: each of the four objects writes its own __global__ -- generic_kernel(a),
-// generic_act_kernel(a, act), generic_pre_act_kernel(a, act), generic_rk_kernel(a, act, rk) -- and includes this file between its braces.
-// Template parameters in scope: DAE, MODE, ML, QM.  Names in scope: a, act (ActPair; NoActPair in the ELU(1) object) and rk (read under
-// Bd::rk only; the other objects declare an unread one).  The build policy Bd decides the rest with `if constexpr`.
+// The body of K0's kernel (psnode_generic_impl.h), as text: each of the five objects writes its own __global__ -- generic_kernel(a),
+// generic_act_kernel(a, act), generic_pre_act_kernel(a, act), generic_rk_kernel(a, act, rk), generic_sub_kernel(a, act, rk, sub) -- and
+// includes this file between its braces.
+// Template parameters in scope: DAE, MODE, ML, QM.  Names in scope: a, act (ActPair; NoActPair in the ELU(1) object), rk (read under
+// Bd::rk only) and sub (SubDev, read under Bd::sub only); the objects without one declare an unread one.  The build policy Bd decides the
+// rest with `if constexpr`.
     constexpr bool STREAM = MODE == 2;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x;
@@ -114,6 +116,17 @@
     if constexpr (Bd::rk) {
         if (tid < 10) rkt[tid] = tid < 6 ? (&rk.a[0][0])[tid == 0 ? 4 : (tid == 1 ? 8 : (tid == 2 ? 9 : 9 + tid))] : rk.b[tid - 6];
     }
+    // Sub-steps (Bd::sub): every grid interval runs nsub passes of the evaluation loop on h = (t[k + 1] - t[k]) / nsub with the interval's
+    // z | v held; behind a sub-step that is not the interval's last the new state goes where a step's start state lives and nothing else
+    // advances.  1 in every other build.
+    int nsub = 1;
+    // (the sub-step build pins the loop bound in scalar registers: left to the compiler it is reloaded inside the divergent arms below, merges
+    //  into a vector register, and the whole time loop then sits under a vector-compare guard)
+    long long Tn = 0;
+    if constexpr (Bd::sub) {
+        nsub = __builtin_amdgcn_readfirstlane(sub.n);
+        Tn = uniform64(a.T);
+    }
     // look-ahead registers: clocks (threads < TB), the next step's event index, the next grid point's z | v
     float tc = 0.0f, tn = 0.0f;
     if (tid < TB) {
@@ -130,12 +143,13 @@
     // One MLP call site for every evaluation (the unrolled layer code exists once: it has to stay inside the instruction cache).  Slots of
     // step k: 0 = the AE head at an event (my_solvers.py:110), 1 .. S = the DE stages, S + 1 = the AE head at grid point k + 1
     // (my_solvers.py:95, 121); the pseudo-step k = -1 of the DAE is that last slot alone, for grid point 0.
-    for (long long k = DAE ? -1 : 0; k + 1 < a.T; ++k) {
+    for (long long k = DAE ? -1 : 0; k + 1 < (Bd::sub ? Tn : a.T); ++k) {
         K0_PROF(5)
         const int ev = k >= 0 ? __builtin_amdgcn_readfirstlane(evn_v) : -1;
         if (k >= 0) {
             // ---- this step's inputs (zero-order hold: the left grid point feeds every stage)
-            if (tid < TB) dts[tid] = tn - tc;
+            if constexpr (Bd::sub) { if (tid < TB) dts[tid] = (tn - tc) / (float)nsub; }
+            else { if (tid < TB) dts[tid] = tn - tc; }
             for (int idx = tid; idx < nzv * TB; idx += NT) {
                 const int r = idx / TB, c = idx % TB;
                 float v;
@@ -171,13 +185,19 @@
             lds_barrier();
         }
         K0_PROF(0)
-        const int e_end = DAE ? nstage + 1 : nstage;
-        for (int e = k < 0 ? nstage + 1 : ((DAE && ev >= 0) ? 0 : 1); e <= e_end; ++e) {
+        // sub-step si.i of the interval (one pass in the builds without sub-steps, and for the DAE's pseudo-step): only the first has the
+        // event slot, only the last the head at grid point k + 1; the others of a DAE that integrates its own i start with an AE evaluation
+        // in the event slot's form -- the algebraic variable follows the state inside the interval
+        SubIter<Bd::sub> si(k >= 0 ? nsub : 1);
+        do {
+        const int e_end = (DAE && si.last()) ? nstage + 1 : nstage;
+        for (int e = k < 0 ? nstage + 1 : ((DAE && (si.first() ? ev >= 0 : !true_i)) ? 0 : 1); e <= e_end; ++e) {
             const bool is_ae = DAE && (e == 0 || e == nstage + 1);
-            const bool ae_next = DAE && e == nstage;
+            const bool ae_next = DAE && e == nstage && (si.last() || !true_i);
             int f;
             if constexpr (MODE == 0 || MODE == 3) {
-                if (e == 1) {       // the step's externals are in place (behind an event's AE evaluation too): the DE's per-step constant
+                // (sub-steps: the externals change inside an interval only where the DAE's own i does)
+                if (e == 1 && (si.first() || (DAE && !true_i))) {       // the step's externals are in place (behind an event's AE evaluation too): the DE's per-step constant
                     const int nt0 = tab_tiles(tde.dims[0]);
                     if (wv < nt0) cde = fold0<ML>(tde, lds, inDE, wv);
                     if (MODE == 3 && wv + 4 < nt0) cde2 = fold0<ML>(tde, lds, inDE, wv + 4);
@@ -255,12 +275,22 @@
                 if (!final_stage) {
                     put_x(r, c, v);
                 } else {
+                    if constexpr (Bd::sub) {
+                        if (!si.last()) {      // the start state of sub-step si.i + 1: nothing of grid point k + 1 is touched
+                            xsrc[idx] = v;
+                            xcur[idx] = v;
+                            put_x(r, c, v);
+                            if constexpr (DAE) lds[inAE + qi(r, c)] = v;
+                            if (sub.x_sub && b0 + c < a.B) sub.x_sub[((k * (nsub - 1) + si.i) * a.B + b0 + c) * xd + r] = v;
+                            continue;
+                        }
+                    }
                     xcur[idx] = v;
                     if (b0 + c < a.B) a.xo[((k + 1) * a.B + b0 + c) * xd + r] = v;
                     if constexpr (DAE) lds[inAE + qi(r, c)] = true_x ? a.x.p[(k + 1) * a.x.st + gb(c) * a.x.sb + r] : v;   // my_solvers.py:121
                 }
             }
-            if (final_stage) {
+            if (final_stage && si.last()) {
 #pragma unroll
                 for (int j = 0; j < PF; ++j) {
                     const int idx = tid + NT * j;
@@ -278,6 +308,7 @@
             lds_barrier();
             K0_PROF(3)
         }
+        } while (si.more());
     }
 #ifdef PSNODE_K0_PROF
     if (blockIdx.x == 0 && tid == 0)

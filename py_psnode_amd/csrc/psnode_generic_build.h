@@ -1,21 +1,40 @@
-// The build policy of the generic kernels K0 (psnode_generic_impl.h) and K5 (psnode_generic_bwd_impl.h): what separates the four objects each
+// The build policy of the generic kernels K0 (psnode_generic_impl.h) and K5 (psnode_generic_bwd_impl.h): what separates the five objects each
 // is compiled into, as constants the language can see.
 #pragma once
 
 namespace psnode {
 
-template <bool ACT, bool PRE, bool RK>
+template <bool ACT, bool PRE, bool RK, bool SUB = false>
 struct GenericBuild {
     static constexpr bool act = ACT;      // the hidden-layer activation is a kernel argument (ActPair, psnode_act.h), not ELU(1)
     static constexpr bool pre = PRE;      // the hidden layers' pre-activations u are kept next to h (SiLU / GELU / Mish differentiate from u)
     static constexpr bool rk = RK;        // the stage loops read a psnode_rk_tableau_f32 kernel argument instead of a.method
+    static constexpr bool sub = SUB;      // every grid interval runs SubDev::n equal sub-steps (a further kernel argument, psnode_common.h)
     // K5's waves per SIMD: the fully streamed instances (STR 2) that fitted 256 registers keep two workgroups per CU -- every one of the
     // act build, the ELU(1) build's with the accumulators in LDS, none of the builds that keep u
     static constexpr int two_waves(bool gg, int str) { return PRE ? 1 : (str == 2 && (ACT || !gg) ? 2 : 1); }
 };
+// The sub-step loop of both kernel bodies: `do { ... } while (si.more())` around what a step does per sub-step.  Without sub-steps it is one
+// pass whose every question is a constant, so that the builds without them compile to the code they had before the loop existed.
+template <bool SUB> struct SubIter {
+    int n, i;
+    __host__ __device__ explicit SubIter(int n_) : n(n_), i(0) {}
+    __host__ __device__ bool first() const { return i == 0; }
+    __host__ __device__ bool last() const { return i + 1 == n; }
+    __host__ __device__ bool more() { return ++i < n; }
+};
+template <> struct SubIter<false> {
+    static constexpr int i = 0;
+    __host__ __device__ explicit constexpr SubIter(int) {}
+    static constexpr bool first() { return true; }
+    static constexpr bool last() { return true; }
+    static constexpr bool more() { return false; }
+};
+
 using BuildElu1 = GenericBuild<false, false, false>;
 using BuildAct = GenericBuild<true, false, false>;
 using BuildPre = GenericBuild<true, true, false>;
 using BuildRk = GenericBuild<true, true, true>;
+using BuildSub = GenericBuild<true, true, true, true>;      // BuildRk's policy with sub-steps: all ten activation kinds, the tableau
 
 }  // namespace psnode

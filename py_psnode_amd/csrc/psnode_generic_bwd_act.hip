@@ -10,6 +10,7 @@ namespace {
 template <bool gg, bool REG, bool ggA = gg, int STR = 0>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(Bd::two_waves(gg, STR), 8))) void generic_backward_act_kernel(const GBwd a, const ActPair act) {
     const psnode_rk_tableau_f32 rk{};      // never read: the tableau code is under `if constexpr (Bd::rk)`
+    const SubDev sub{};                    // never read: the sub-step code is under `if constexpr (Bd::sub)`
 #include "psnode_generic_bwd_body.h"
 }
 template <> struct GenericBwdKernels<Bd> {

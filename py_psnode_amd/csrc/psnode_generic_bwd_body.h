@@ -1,7 +1,8 @@
-// The body of K5's kernel (psnode_generic_bwd_impl.h), as text: each of the four objects writes its own __global__ --
+// The body of K5's kernel (psnode_generic_bwd_impl.h), as text: each of the five objects writes its own __global__ --
 // generic_backward_kernel(a), generic_backward_act_kernel(a, act), generic_backward_pre_act_kernel(a, act),
-// generic_backward_rk_kernel(a, act, rk) -- and includes this file between its braces.  Template parameters in scope: gg, REG, ggA, STR.
-// Names in scope: a, act (ActPair; NoActPair in the ELU(1) object) and rk (read under Bd::rk only; the other objects declare an unread one).
+// generic_backward_rk_kernel(a, act, rk), generic_backward_sub_kernel(a, act, rk, sub) -- and includes this file between its braces.
+// Template parameters in scope: gg, REG, ggA, STR.  Names in scope: a, act (ActPair; NoActPair in the ELU(1) object), rk (read under
+// Bd::rk only) and sub (SubDev, read under Bd::sub only); the objects without one declare an unread one.
     constexpr bool DE_TM = REG || STR == 2;      // the DE's LDS accumulators are tile-major
     constexpr bool AE_TM = STR >= 1;
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -12,6 +13,10 @@
     const int nzv = zd + vd, ne = nzv + id, n = xd + ne;
     const int S = Bd::rk ? __builtin_amdgcn_readfirstlane(rk.stages) : rk_stages(a.method);
     const int nx = xd * TP;
+    // sub-steps per grid interval (Bd::sub; 1 in every other build): the sweep walks them backwards inside each interval, from the start
+    // states K0 left in sub.x_sub
+    int nsub = 1;
+    if constexpr (Bd::sub) nsub = __builtin_amdgcn_readfirstlane(sub.n);
     // teacher forcing: tx -- every DE step and every grid-point head reads the dataset row (xsrc), the adjoint of a step's start state is
     // dropped; ti -- the DE reads i_true[k], its algebraic adjoint is dropped and the event-time head feeds nothing
     const bool tx = (a.flags & PSNODE_FLAG_INPUT_TRUE_X) != 0, ti = dae && (a.flags & PSNODE_FLAG_INPUT_TRUE_I) != 0;
@@ -111,7 +116,8 @@
         __syncthreads();
     };
     // VJP of the AE head at (xrows; z|v of grid point jzv or the jumped ext rows) with output gradient `gi`:
-    // adds to gx_dst, ga0s, and to the z|v gradients (global gz/gv at jzv, or the jump gradients of event ev)
+    // adds to gx_dst, ga0s, and to the z|v gradients (global gz/gv at jzv, or the jump gradients of event ev; sub-step build, ev == -2: the
+    // z | v rows of gext, which collect an interval's sub-steps)
     auto ae_vjp = [&](const float* xrows, long long jzv, int ev, const float* gi, float* gx_dst) {
         ae_input(xrows, jzv);
         if constexpr (STR >= 1) g_forward_str(a.ae, a.fimgA, acts, qb, qoA, ActCtx{act.ae, upre}); else g_forward(a.ae, acts, wbuf, ActCtx{act.ae, upre});
@@ -126,6 +132,9 @@
             const float g = gu[(n + xd + r) * TP + c];
             const bool isz = r < zd;
             const int d_ = isz ? r : r - zd, w_ = isz ? zd : vd;
+            if constexpr (Bd::sub) {
+                if (ev == -2) { gext[r * TP + c] += g; continue; }
+            }
             if (jzv >= 0) {
                 float* dst = isz ? a.gz : a.gv;
                 if (dst) dst[(jzv * a.B + b0 + c) * w_ + d_] += g;
@@ -162,12 +171,15 @@
     }
     for (long long k = a.T - 2; k >= 0; --k) {
         const int ev = a.ev ? a.ev[k] : -1;
-        if (tid < TB) dts[tid] = la_tn - la_t;
+        if constexpr (Bd::sub) { if (tid < TB) dts[tid] = (la_tn - la_t) / (float)nsub; }
+        else { if (tid < TB) dts[tid] = la_tn - la_t; }
         float gx_in[LA];                             // the incoming gradient of grid point k, consumed at the bottom of the step
+        [[maybe_unused]] float x_keep[LA];           // sub-step build: xs[k] of the look-ahead, for sub-step 0 (x0 holds the later ones' starts first)
 #pragma unroll
         for (int j = 0; j < LA; ++j) {
             const int idx = tid + NT * j;
             gx_in[j] = la_g[j];
+            if constexpr (Bd::sub) x_keep[j] = la_x[j];
             if (idx < xd * TB) x0[(idx / TB) * TP + idx % TB] = la_x[j];
             if (idx < nzv * TB && ev < 0) ext[(idx / TB) * TP + idx % TB] = la_zv[j];
         }
@@ -183,18 +195,42 @@
         if (tid < TB) la_tn = la_t;
         if (k > 0) look_ahead(k - 1);
         __syncthreads();
+        // Sub-step nsub - 1 - si.i of the interval, last to first (one pass in the builds without sub-steps).  gxc carries between them; the
+        // z | v rows of gext collect all of them before (4); a sub-step behind the first (`inner`) starts from x_sub[k][that - 1], and where
+        // the DAE integrates its own i its algebraic input is the head at that state and the interval's z | v.
+        SubIter<Bd::sub> si(nsub);
+        do {
+        const bool inner = !si.last();
+        if constexpr (Bd::sub) {
+            if (nsub > 1) {      // (defensive: the host never launches this build with one sub-step -- substeps == 1 takes the other entry points)
+                const int js = nsub - 1 - si.i;
+                if (js > 0) {
+                    TILE_LOOP(xd) x0[r * TP + c] = sub.x_sub[((k * (nsub - 1) + js - 1) * a.B + gb(c)) * xd + r];
+                } else {      // back to xs[k]: from the look-ahead registers, rows beyond them from memory as at the top of the step
+#pragma unroll
+                    for (int j = 0; j < LA; ++j) {
+                        const int idx = tid + NT * j;
+                        if (idx < xd * TB) x0[(idx / TB) * TP + idx % TB] = x_keep[j];
+                    }
+                    for (int idx = tid + NT * LA; idx < xd * TB; idx += NT) x0[(idx / TB) * TP + idx % TB] = xsrc[(k * a.B + gb(idx % TB)) * xd + idx / TB];
+                }
+                __syncthreads();
+            }
+        }
         if (dae) {
             // (1) AE head at the end of step k: i_{k+1} = g(x_{k+1}; z[k+1], v[k+1]) carries gic
             //     (tx: the head read x_true[k+1] and its x-adjoint is dropped -- gx0 is rewritten in (3b))
+            if (si.first()) {
             TILE_LOOP(xd) xst[r * TP + c] = xsrc[((k + 1) * a.B + gb(c)) * xd + r];
             __syncthreads();
             ae_vjp(xst, k + 1, -1, gic, tx ? gx0 : gxc);
+            }
             // (2) algebraic input of this step's DE (ti: the dataset row, also on event steps)
             if (ti) {
                 TILE_LOOP(id) ext[(nzv + r) * TP + c] = a.it[(k * a.B + gb(c)) * id + r];
-            } else if (ev >= 0) {
+            } else if (ev >= 0 || inner) {
                 const float* xr = x0;
-                if (tx) {       // the event-time head reads the RUNNING state xs[k], not the row the DE starts from (xst is free until (3a))
+                if (tx && !inner) {       // the event-time head reads the RUNNING state xs[k], not the row the DE starts from (xst is free until (3a))
                     TILE_LOOP(xd) xst[r * TP + c] = a.xs[(k * a.B + gb(c)) * xd + r];
                     __syncthreads();
                     xr = xst;
@@ -235,7 +271,8 @@
             gx0[r * TP + c] = g1;
             for (int s = 0; s < S; ++s) gks[s * nx + r * TP + c] = dts[c] * coef_b(a.method, ks, nx, s) * g1;
         }
-        TILE_LOOP(ne) gext[r * TP + c] = 0.0f;
+        if constexpr (Bd::sub) { TILE_LOOP(ne) if (r >= nzv || si.first()) gext[r * TP + c] = 0.0f; }
+        else { TILE_LOOP(ne) gext[r * TP + c] = 0.0f; }
         __syncthreads();
         for (int s = S - 1; s >= 0; --s) {
             de_input(xst + s * nx);
@@ -261,6 +298,14 @@
                 }
             }
             __syncthreads();
+        }
+        if constexpr (Bd::sub) {
+            if (inner) {      // the head that fed this sub-step's DE: into its start state's adjoint, ga0s and the interval's z | v
+                if (dae && !ti) ae_vjp(x0, -1, -2, gext + nzv * TP, gx0);
+                TILE_LOOP(xd) gxc[r * TP + c] = gx0[r * TP + c];
+                __syncthreads();
+                continue;
+            }
         }
         // tx: the step started from a dataset row -- its start adjoint goes nowhere (an ODE keeps step 0's: grad_x0 = grad_xs[0] + it), and
         // gx0 from here on collects what still reaches the running state xs[k]: the event-time head's x-adjoint
@@ -308,6 +353,7 @@
             gxc[r * TP + c] = gx0[r * TP + c] + (on(c) ? a.gxs[(k * a.B + gb(c)) * xd + r] : 0.0f);
         }
         __syncthreads();
+        } while (si.more());
     }
     if (dae) {   // i_0 = g(x_0; z[0], v[0])   (my_solvers.py:95)
         TILE_LOOP(xd) x0[r * TP + c] = xsrc[gb(c) * xd + r];

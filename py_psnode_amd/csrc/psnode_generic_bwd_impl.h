@@ -15,7 +15,7 @@
 // Teacher forcing (GBwd::flags) changes the outer sweep only: which rows a step starts from and which adjoints travel to the step before.
 #include <string.h>
 
-// Four objects are compiled from this header, one per build policy (psnode_generic_build.h).  Each of psnode_generic_bwd{,_act,_pre,_rk}.hip
+// Five objects are compiled from this header, one per build policy (psnode_generic_build.h).  Each of psnode_generic_bwd{,_act,_pre,_rk,_sub}.hip
 // names its policy `Bd` in front of the include, writes its kernel around psnode_generic_bwd_body.h and instantiates the launcher:
 //   BuildElu1  generic_backward_kernel(a)                    ELU(1) and its derivative
 //   BuildAct   generic_backward_act_kernel(a, act)           the DE's and the AE's activation as a second kernel argument (ActPair)
@@ -24,6 +24,8 @@
 //              paths); the derivative reads u next to h (from u for SiLU / GELU / Mish, from h for the other kinds)
 //   BuildRk    generic_backward_rk_kernel(a, act, rk)        the pre build whose stage loops (3a) / (3b) read the stage count and the coefficients
 //              from a launch-uniform psnode_rk_tableau_f32 instead of rk_stages / rk_a / rk_b of a.method, which it does not read
+//   BuildSub   generic_backward_sub_kernel(a, act, rk, sub)  the tableau build with SubDev::n sub-steps per grid interval: an inner reverse loop
+//              around (2) .. (3b) of the kernel body that starts each sub-step from the state K0 stored in SubDev::x_sub; no LDS of its own
 // The policy decides in the language: the kernel-argument structs (GMlpT / GBwdT: the pre fields are a base that is empty elsewhere), the
 // activation context ActCtx every device function takes, the stage coefficients (coef_a, coef_b) and
 // `if constexpr` in the kernel body and the launcher.  The host's fit and layout functions take `pre` at run time.
@@ -652,7 +654,7 @@ __device__ __forceinline__ float* g_vjp_str(const GMlp& m, const float* const* t
 // head streamed, 2 = both MLPs streamed (0: whatever is not on the register path stages its weights through LDS).
 // (waves per SIMD, Bd::two_waves: the fully streamed instances that fitted 256 registers -- two workgroups per CU where their LDS allows
 //  it -- keep that budget: the sweep-level flag values must not cost them the second workgroup)
-// (the four kernels: psnode_generic_bwd{,_act,_pre,_rk}.hip around psnode_generic_bwd_body.h)
+// (the five kernels: psnode_generic_bwd{,_act,_pre,_rk,_sub}.hip around psnode_generic_bwd_body.h)
 template <class B> struct GenericBwdKernels;      // the kernels of policy B, by their template arguments: specialised by the object that defines them
 
 int fill_gmlp(const psnode_mlp_f32& m, GMlp& g, float*& ws) {
@@ -859,7 +861,8 @@ int generic_backward_launch(const GenericBwdCall& c, const ActPair* act, float* 
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         return PSNODE_ERR_HIP;
     const unsigned nwg = (unsigned)((B + TB - 1) / TB);
-    if constexpr (Pol::rk) hipLaunchKernelGGL(kern, dim3(nwg), dim3(NT), lds, stream, a, *act, *c.rk);
+    if constexpr (Pol::sub) hipLaunchKernelGGL(kern, dim3(nwg), dim3(NT), lds, stream, a, *act, *c.rk, SubDev{c.substeps, const_cast<float*>(c.x_sub)});
+    else if constexpr (Pol::rk) hipLaunchKernelGGL(kern, dim3(nwg), dim3(NT), lds, stream, a, *act, *c.rk);
     else if constexpr (Pol::act) hipLaunchKernelGGL(kern, dim3(nwg), dim3(NT), lds, stream, a, *act);
     else hipLaunchKernelGGL(kern, dim3(nwg), dim3(NT), lds, stream, a);
     if (hipGetLastError() != hipSuccess) return PSNODE_ERR_HIP;

@@ -25,7 +25,7 @@
 // Padded columns: the image holds zeros there and the input builders write zeros into the pad columns of the first layer's input; a
 // hidden layer's pad units come out of the MFMA as ELU(0 + 0) = 0.
 //
-// Four objects are compiled from this header, one per build policy (psnode_generic_build.h).  Each of psnode_generic{,_act,_pre,_rk}.hip
+// Five objects are compiled from this header, one per build policy (psnode_generic_build.h).  Each of psnode_generic{,_act,_pre,_rk,_sub}.hip
 // names its policy `Bd` in front of the include, writes its kernel around psnode_generic_body.h and its exported launcher over
 // launch_generic_build:
 //   BuildElu1  generic_kernel(a), launch_generic                    ELU(1)
@@ -33,8 +33,11 @@
 //   BuildPre   generic_pre_act_kernel(a, act), launch_generic_pre   all ten kinds (SiLU / GELU / GELU(tanh) / Mish too; the forward keeps no u)
 //   BuildRk    generic_rk_kernel(a, act, rk), launch_generic_rk     the pre build with a launch-uniform Butcher tableau of up to four stages
 //              (psnode_rk_tableau_f32) applied in the stage pass instead of the three built-in formulas; a.method is not read
+//   BuildSub   generic_sub_kernel(a, act, rk, sub), launch_generic_sub   the tableau build with SubDev::n sub-steps per grid interval: the
+//              evaluation loop of a step runs n times on h / n, outputs and look-ahead rows advance behind the last one; no LDS of its own
 // The device functions take the activation as one ordinary parameter, ActCtx; the kernel body chooses the tableau code with
-// `if constexpr (Bd::rk)`.  The host's plan / fit / pack code is compiled once, in psnode_generic.hip.
+// `if constexpr (Bd::rk)`, the sub-step code with `if constexpr (Bd::sub)`.  The host's plan / fit / pack code is compiled once, in
+// psnode_generic.hip.
 #pragma once
 #include "psnode_act.h"
 #include "psnode_common.h"
@@ -582,6 +585,12 @@ __device__ __forceinline__ int mlp_regw(const Tab<ML>& T, float* lds, int in, co
         in = out;
     }
     return out;
+}
+
+// a launch-uniform 64-bit value, pinned in scalar registers (two readfirstlane halves)
+__device__ __forceinline__ long long uniform64(long long v) {
+    const unsigned long long u = (unsigned long long)v;
+    return (long long)(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(u >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)u));
 }
 
 // PF: z | v values a thread keeps in flight for the next grid point (items tid + 256 j); rows beyond 16 PF are loaded where they are used

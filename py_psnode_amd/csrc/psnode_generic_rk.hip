@@ -10,6 +10,7 @@ namespace {
 
 template <bool DAE, int MODE, int ML, int QM = 4>
 __global__ __launch_bounds__(NT) void generic_rk_kernel(const IntegrateDev a, const ActPair act, const psnode_rk_tableau_f32 rk) {
+    const SubDev sub{};      // never read: the sub-step code is under `if constexpr (Bd::sub)`
 #include "psnode_generic_body.h"
 }
 template <> struct GenericKernels<Bd> {

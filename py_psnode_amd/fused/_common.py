@@ -95,6 +95,33 @@ def builtin_method(method, what: str):
     return METHOD_ID[method], STAGES[method]
 
 
+def no_substeps(substeps: int, what: str):
+    """The specialised, latent, encoded and saved-row entries take one step per grid interval: sub-steps are refused like a Tableau."""
+    if substeps != 1:
+        raise _lib.UnsupportedShapeError(f"{what}: sub-steps per grid interval (substeps={substeps}) run on the generic kernels K0 / K5 only "
+                                         "(kernel 'auto' / 'generic', no saved rows); this entry point takes one step per interval")
+
+
+def substeps_abi(substeps: int, x_sub=None):
+    """The psnode_substeps_f32 of a call of the generic route with substeps > 1 (x_sub: the sub-state rows, or None), None for substeps == 1
+    -- the call then takes the entry point it takes without sub-steps.  ValueError unless an int in 1..1024."""
+    if isinstance(substeps, bool) or not isinstance(substeps, int) or not 1 <= substeps <= _lib.MAX_SUBSTEPS:
+        raise ValueError(f"substeps must be an int in 1..{_lib.MAX_SUBSTEPS}, got {substeps!r}")
+    if substeps == 1:
+        return None
+    s = _lib.SubstepsF32()
+    s.substeps = substeps
+    s.x_sub = x_sub.data_ptr() if x_sub is not None and x_sub.numel() else None
+    return s
+
+
+def sub_route_ok(what: str, substeps: int, kernel: str, save: bool):
+    """Sub-steps run on the generic kernels only."""
+    if substeps != 1 and (kernel not in ("auto", "generic") or save):
+        raise _lib.UnsupportedShapeError(f"{what}: sub-steps per grid interval (substeps={substeps}) run on the generic kernels K0 / K5 only "
+                                         f"(kernel 'auto' / 'generic', no saved rows); got kernel={kernel!r}, saved rows={save}")
+
+
 KERNEL_ID = {"auto": _lib.KERNEL_AUTO, "generic": _lib.KERNEL_GENERIC, "mfma": _lib.KERNEL_MFMA, "wide": _lib.KERNEL_MFMA_WIDE,
              "tile": _lib.KERNEL_MFMA_TILE, "wave": _lib.KERNEL_MFMA_WAVE}      # forward ODE calls: K1 (4-wave tile) / K1x (one wave per 4 trajectories)
 
@@ -175,11 +202,16 @@ def dae_acts(act):
     return (None, None) if act is None else tuple(act)
 
 
-def call_entry(lib, stem: str, args, acts, wp, wn, stream, tab=None) -> int:
+def call_entry(lib, stem: str, args, acts, wp, wn, stream, tab=None, sub=None) -> int:
     """The one place that picks an entry point of the generic-kernel families: psnode_<stem>_f32 when every act is None (ELU(1)),
     psnode_<stem>_act_f32 with the acts' psnode_act_f32 otherwise.  stem: "ode_integrate", "dae_integrate", "ode_backward", "dae_backward".
-    tab (a Tableau): psnode_<stem>_rk_f32 with the acts and the tableau ("dae_backward": args is then a DaeBwdTfArgsF32)."""
+    tab (a Tableau): psnode_<stem>_rk_f32 with the acts and the tableau ("dae_backward": args is then a DaeBwdTfArgsF32).
+    sub (`substeps_abi`, not None: substeps > 1): psnode_<stem>_sub_f32 with the acts, the tableau or NULL (= the args' method) and the
+    struct ("dae_backward": a DaeBwdTfArgsF32)."""
     refs, non_elu = _act_refs(*acts)
+    if sub is not None:
+        return getattr(lib, f"psnode_{stem}_sub_f32")(ctypes.byref(args), *refs, ctypes.byref(tab.abi()) if tab is not None else None,
+                                                      ctypes.byref(sub), wp, wn, stream)
     if tab is not None:
         return getattr(lib, f"psnode_{stem}_rk_f32")(ctypes.byref(args), *refs, ctypes.byref(tab.abi()), wp, wn, stream)
     if not non_elu:
@@ -187,10 +219,13 @@ def call_entry(lib, stem: str, args, acts, wp, wn, stream, tab=None) -> int:
     return getattr(lib, f"psnode_{stem}_act_f32")(ctypes.byref(args), *refs, wp, wn, stream)
 
 
-def entry_supported(lib, stem: str, args, acts, tab=None) -> bool:
-    """psnode_<stem>_supported, or psnode_<stem>_act_supported when an act is not None, or psnode_<stem>_rk_supported for a Tableau
-    (`call_entry`'s query)."""
+def entry_supported(lib, stem: str, args, acts, tab=None, sub=None) -> bool:
+    """psnode_<stem>_supported, or psnode_<stem>_act_supported when an act is not None, or psnode_<stem>_rk_supported for a Tableau, or
+    psnode_<stem>_sub_supported for sub-steps (`call_entry`'s query)."""
     refs, non_elu = _act_refs(*acts)
+    if sub is not None:
+        return bool(getattr(lib, f"psnode_{stem}_sub_supported")(ctypes.byref(args), *refs, ctypes.byref(tab.abi()) if tab is not None else None,
+                                                                 ctypes.byref(sub)))
     if tab is not None:
         return bool(getattr(lib, f"psnode_{stem}_rk_supported")(ctypes.byref(args), *refs, ctypes.byref(tab.abi())))
     if not non_elu:

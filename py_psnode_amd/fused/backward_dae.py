@@ -6,25 +6,27 @@ import ctypes
 import torch
 
 from .. import _lib
-from ._common import (KERNEL_ID, Layers, builtin_method, method_info, _aligned16, _aligned_ptr, _bind_jumps, _check_saved, _empty, _f32_dev, _mlp, _pad_rows, _padded_hidden, _split_grads, _view, call_entry, dae_acts, entry_supported)
+from ._common import (KERNEL_ID, Layers, builtin_method, method_info, _aligned16, _aligned_ptr, _bind_jumps, _check_saved, _empty, _f32_dev, _mlp, _pad_rows, _padded_hidden, _split_grads, _view, call_entry, dae_acts, entry_supported, no_substeps, sub_route_ok, substeps_abi)
 from .latent import latent_backward_wide, latent_wide_shape
 
-def dae_backward_supported(method, de_layers: Layers, ae_layers: Layers, x_dim, z_dim, v_dim, i_dim, act=None, kernel: str = "auto") -> bool:
+def dae_backward_supported(method, de_layers: Layers, ae_layers: Layers, x_dim, z_dim, v_dim, i_dim, act=None, kernel: str = "auto",
+                           substeps: int = 1) -> bool:
     """act: None (both MLPs ELU(1)) or (de_act, ae_act); an activation other than ELU(1) is K5's alone.  kernel="generic": does K5 take
     the shape (the question a teacher-forced call outside K7f's class asks).  method a fused.Tableau: K5's tableau build only (kernel
-    "auto" / "generic"; it answers for its own LDS fit)."""
+    "auto" / "generic"; it answers for its own LDS fit).  substeps > 1: K5's sub-step build only, under the same rules."""
     if de_layers[0][0].device.type != "cuda" or max(len(de_layers), len(ae_layers)) > _lib.MAX_LAYERS:
         return False
     acts = dae_acts(act)
     tab = method_info(method)[2]
-    if tab is not None:
+    sub = substeps_abi(substeps)
+    if tab is not None or sub is not None:
         tf = _lib.DaeBwdTfArgsF32()
         b = tf.base
-        b.method, b.kernel = _lib.EULER, KERNEL_ID[kernel]
+        b.method, b.kernel = method_info(method)[0], KERNEL_ID[kernel]
         b.x_dim, b.z_dim, b.v_dim, b.i_dim, b.T, b.B = x_dim, z_dim, v_dim, i_dim, 2, 1
         dev = de_layers[0][0].device
         b.de, b.ae = _mlp(de_layers, dev, "de", []), _mlp(ae_layers, dev, "ae", [])
-        return entry_supported(_lib.load(), "dae_backward", tf, acts, tab)
+        return entry_supported(_lib.load(), "dae_backward", tf, acts, tab, sub)
     non_elu = any(q is not None for q in acts)
     if not non_elu and kernel != "generic" and latent_wide_shape(de_layers, ae_layers, x_dim, z_dim, v_dim, i_dim):
         return True                          # K3w (saving) + K9w + library GEMMs
@@ -41,9 +43,10 @@ def dae_backward_supported(method, de_layers: Layers, ae_layers: Layers, x_dim, 
     return dae_backward_wide_supported(method, de_layers, ae_layers, x_dim, z_dim, v_dim, i_dim)      # K7f: the DAE_01 class at hidden <= 128
 
 
-def dae_backward_wide_supported(method: str, de_layers: Layers, ae_layers: Layers, x_dim, z_dim, v_dim, i_dim) -> bool:
+def dae_backward_wide_supported(method: str, de_layers: Layers, ae_layers: Layers, x_dim, z_dim, v_dim, i_dim, substeps: int = 1) -> bool:
     """Shapes of K7f (psnode_dae_backward_wide_f32): DE 3n -> h -> h -> h -> x and AE n+x+z+v -> h -> h -> h -> i with h <= 128,
     x <= 8, z+v+i <= 8."""
+    no_substeps(substeps, "dae_backward_wide_supported")
     if de_layers[0][0].device.type != "cuda" or len(de_layers) != 4 or len(ae_layers) != 4:
         return False
     lib = _lib.load()
@@ -55,7 +58,7 @@ def dae_backward_wide_supported(method: str, de_layers: Layers, ae_layers: Layer
 
 
 def dae_backward_wide(method: str, de_layers: Layers, ae_layers: Layers, t, z, v, all_initial, xs, is_, grad_xs, grad_is, event_idx=None,
-                      z_jump=None, v_jump=None, saved=None, x_true=None, i_true=None):
+                      z_jump=None, v_jump=None, saved=None, x_true=None, i_true=None, substeps: int = 1):
     """Backward of `dae_integrate` at hidden <= 128 (the DAE_01 shape class): K7f (psnode_dae_backward_wide_f32) -- ONE launch over the
     whole grid that sweeps the adjoint through the DE stages, the AE head per grid point and the event-time recomputes and forms the DE's
     parameter gradients and the DE's share of the input gradients in the kernel.  With saved activations at hidden <= 64 the head's
@@ -65,6 +68,7 @@ def dae_backward_wide(method: str, de_layers: Layers, ae_layers: Layers, t, z, v
     DE / the heads; recompute form only.  A call whose head rows (6 x [T,B,H] + [T,B,40]) would not fit half of the free HBM is run over
     BATCH slices (trajectories are independent: parameter gradients add, per-trajectory gradients concatenate).
     Same return value as `dae_backward`."""
+    no_substeps(substeps, "dae_backward_wide")
     lib = _lib.load()
     dev = xs.device
     T, B, xd = xs.shape
@@ -304,13 +308,14 @@ def _dae_backward_wide_sliced(step, method, de_layers, ae_layers, t, z, v, all_i
 
 
 def dae_backward(method, de_layers: Layers, ae_layers: Layers, t, z, v, all_initial, xs, is_, grad_xs, grad_is, event_idx=None,
-                 z_jump=None, v_jump=None, kernel: str = "auto", saved=None, act=None):
+                 z_jump=None, v_jump=None, kernel: str = "auto", saved=None, act=None, substeps: int = 1, x_sub=None):
     """Backward pass of `dae_integrate` (no teacher forcing): the one-launch K7f (`dae_backward_wide`) for the DAE_01 shape class at
     hidden <= 128, K9 / K8 / K9w for the latent shapes of the direct_encode models, else the generic backward kernel (K5);
     `kernel` = "auto" | "mfma" | "generic" | "wide" (K7f or an error).
     saved = what `dae_integrate(save=True)` returned (read by K7f, K9 and K9w; K8 / K5 recompute and refuse them).
     act: None (both MLPs ELU(1)) or (de_act, ae_act); an activation other than ELU(1) runs on K5 only (kernel "auto" / "generic").
     method: "euler" | "midpoint" | "rk4", or a fused.Tableau -- K5 only (kernel "auto" / "generic", no saved rows).
+    substeps > 1: backward of `dae_integrate(..., substeps=, save_sub=True)` with the x_sub it returned -- K5 only, the same rules.
     Returns dict(x_init, z, v, z_jump, v_jump, all_initial, de=[...], ae=[...]) of gradients."""
     T, B, xd = xs.shape
     zd, vd, idim = z.shape[-1], v.shape[-1], is_.shape[-1]
@@ -321,12 +326,13 @@ def dae_backward(method, de_layers: Layers, ae_layers: Layers, t, z, v, all_init
                                              "(kernel 'auto' / 'generic', no saved rows)")
         kernel = "generic"
     tab = method_info(method)[2]
-    if tab is not None:
-        if kernel not in ("auto", "generic") or saved is not None:
+    sub_route_ok("dae_backward", substeps, kernel, saved is not None)
+    if tab is not None or substeps > 1:
+        if tab is not None and (kernel not in ("auto", "generic") or saved is not None):
             raise _lib.UnsupportedShapeError(f"dae_backward: a Runge-Kutta tableau ({tab.name}) runs on the generic backward K5 only "
                                              "(kernel 'auto' / 'generic', no saved rows)")
         return _dae_backward_entry(method, de_layers, ae_layers, t, z, v, all_initial, xs, is_, grad_xs, grad_is, event_idx, z_jump, v_jump,
-                                   kernel, None, acts)
+                                   kernel, None, acts, substeps=substeps, x_sub=x_sub)
     if kernel in ("wide", "mfma") and T < 2 and len(de_layers) == 4:
         kernel = "generic"       # no step to sweep: K7f has no head-only form, K5 handles the single grid point
     if saved is not None and latent_wide_shape(de_layers, ae_layers, xd, zd, vd, idim):
@@ -341,11 +347,12 @@ def dae_backward(method, de_layers: Layers, ae_layers: Layers, t, z, v, all_init
 
 
 def dae_backward_tf(method, de_layers: Layers, ae_layers: Layers, t, z, v, all_initial, xs, is_, grad_xs, grad_is, event_idx=None,
-                    z_jump=None, v_jump=None, kernel: str = "auto", x_true=None, i_true=None):
+                    z_jump=None, v_jump=None, kernel: str = "auto", x_true=None, i_true=None, substeps: int = 1, x_sub=None):
     """Backward of a teacher-forced `dae_integrate` (input_true_x / input_true_i, my_solvers.py:111-121) on the generic backward K5
     (psnode_dae_backward_tf_f32): every shape K5 takes untied.  x_true [T,B,x_dim] / i_true [T,B,i_dim]: the dataset rows the forward call
     fed the DE / the heads (None = that flag was not set; both None = `dae_backward` on K5's entry point); they get no gradient.  xs / is_:
-    the forward results (an event step's recomputed head reads the running state xs[k]).  kernel: "auto" | "generic".
+    the forward results (an event step's recomputed head reads the running state xs[k]).  kernel: "auto" | "generic".  substeps > 1: with the
+    x_sub of the forward call (`dae_integrate(..., substeps=, save_sub=True)`).
     Same return value as `dae_backward`."""
     if kernel not in ("auto", "generic"):
         raise _lib.UnsupportedShapeError("dae_backward_tf: the teacher-forced backward behind this entry point is K5's (kernel 'auto' / 'generic'); "
@@ -355,20 +362,26 @@ def dae_backward_tf(method, de_layers: Layers, ae_layers: Layers, t, z, v, all_i
         if q is not None and tuple(q.shape) != (T, B, w):
             raise ValueError(f"{name} must be [T,B,{w}], got {tuple(q.shape)}")
     return _dae_backward_entry(method, de_layers, ae_layers, t, z, v, all_initial, xs, is_, grad_xs, grad_is, event_idx, z_jump, v_jump,
-                               kernel, None, (None, None), x_true=x_true, i_true=i_true)
+                               kernel, None, (None, None), x_true=x_true, i_true=i_true, substeps=substeps, x_sub=x_sub)
 
 
 def _dae_backward_entry(method, de_layers, ae_layers, t, z, v, all_initial, xs, is_, grad_xs, grad_is, event_idx, z_jump, v_jump, kernel, saved,
-                        acts, x_true=None, i_true=None):
-    """psnode_dae_backward_f32 / _act_f32, or psnode_dae_backward_tf_f32 when dataset rows come along: one marshalling for the three."""
+                        acts, x_true=None, i_true=None, substeps: int = 1, x_sub=None):
+    """psnode_dae_backward_f32 / _act_f32, or psnode_dae_backward_tf_f32 when dataset rows come along, or the _rk / _sub entry points: one
+    marshalling for all of them."""
     lib = _lib.load()
     dev = xs.device
     T, B, xd = xs.shape
     zd, vd, idim = z.shape[-1], v.shape[-1], is_.shape[-1]
-    keep: list = []
+    if substeps > 1 and T >= 2 and (x_sub is None or tuple(x_sub.shape) != (T - 1, substeps - 1, B, xd) or not x_sub.is_contiguous()
+                                    or x_sub.dtype != torch.float32 or x_sub.device != dev):
+        raise ValueError(f"dae_backward: substeps={substeps} needs x_sub, the contiguous fp32 [{T - 1},{substeps - 1},{B},{xd}] tensor the "
+                         "forward call returned with save_sub=True")
+    keep: list = [x_sub]
+    sub = substeps_abi(substeps, x_sub)
     tf = None
     method_id, S, tab = method_info(method)
-    if x_true is not None or i_true is not None or tab is not None:      # (the _rk entry point takes the tf struct, flags 0 included)
+    if x_true is not None or i_true is not None or tab is not None or sub is not None:      # (the _rk / _sub entry points take the tf struct, flags 0 included)
         tf = _lib.DaeBwdTfArgsF32()
         xt_c = _f32_dev(x_true, dev, "x_true").contiguous() if x_true is not None else None
         it_c = _f32_dev(i_true, dev, "i_true").contiguous() if i_true is not None else None
@@ -427,7 +440,11 @@ def _dae_backward_entry(method, de_layers, ae_layers, t, z, v, all_initial, xs, 
                 if s_ev is None or s_evi is None or s_ev.shape[0] != n_ev_ or s_ev.shape[2] != B or s_evi.shape[:2] != (n_ev_, B):
                     raise ValueError("saved event activations do not belong to this call (shape)")
                 a.saved_ev_act, a.saved_ev_i = s_ev.data_ptr(), s_evi.data_ptr()
-        if tab is not None:
+        if sub is not None:
+            arefs = [ctypes.byref(q.abi()) if q is not None else None for q in acts]
+            nbytes = lib.psnode_dae_backward_sub_workspace_bytes(ctypes.byref(tf), *arefs, ctypes.byref(tab.abi()) if tab is not None else None,
+                                                                 ctypes.byref(sub))
+        elif tab is not None:
             arefs = [ctypes.byref(q.abi()) if q is not None else None for q in acts]
             nbytes = lib.psnode_dae_backward_rk_workspace_bytes(ctypes.byref(tf), *arefs, ctypes.byref(tab.abi()))
         elif tf is not None:
@@ -437,10 +454,10 @@ def _dae_backward_entry(method, de_layers, ae_layers, t, z, v, all_initial, xs, 
         ws = _empty(nbytes + 256, dtype=torch.uint8, device=dev)
         wp, wn = _aligned_ptr(ws)
         st = torch.cuda.current_stream(dev).cuda_stream
-        if tab is not None:
-            rc = call_entry(lib, "dae_backward", tf, acts, wp, wn, st, tab)
+        if tab is not None or sub is not None:
+            rc = call_entry(lib, "dae_backward", tf, acts, wp, wn, st, tab, sub)
         else:
             rc = lib.psnode_dae_backward_tf_f32(ctypes.byref(tf), wp, wn, st) if tf is not None else call_entry(lib, "dae_backward", a, acts, wp, wn, st)
-    _lib.check(rc, "psnode_dae_backward_rk_f32" if tab is not None else ("psnode_dae_backward_tf_f32" if tf is not None else "psnode_dae_backward_f32"))
+    _lib.check(rc, "psnode_dae_backward_sub_f32" if sub is not None else "psnode_dae_backward_rk_f32" if tab is not None else ("psnode_dae_backward_tf_f32" if tf is not None else "psnode_dae_backward_f32"))
     g["de"], g["ae"] = _split_grads(gde, de_layers), _split_grads(gae, ae_layers)
     return g

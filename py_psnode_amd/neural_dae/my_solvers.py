@@ -36,7 +36,15 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
     order: int
     method = ""        # "euler" | "midpoint" | "rk4", or a fused.Tableau (my_fixed_grid.ExplicitRK): the formula the fused kernels run
 
-    def __init__(self, step_size=None, grid_constructor=None, interp="linear"):
+    def __init__(self, step_size=None, grid_constructor=None, interp="linear", substeps=1):
+        """substeps (an int >= 1, default 1): every grid interval [t[k], t[k+1]] is integrated in that many equal sub-steps of
+        h = (t[k+1] - t[k]) / substeps, with the interval's external inputs held over all of them and the outputs staying on the grid of t
+        (`_walk_ode` / `_walk_dae` are the definition; more than 1 runs fused on the generic kernels K0 / K5, kernel 'auto' / 'generic').
+        It is the supported way to integrate with a finer step than the data's sampling interval: `step_size`, `grid_constructor` and
+        `interp` are kept for the reference's call surface and are read by neither integrate_ODE nor integrate_DAE, as upstream."""
+        if isinstance(substeps, bool) or not isinstance(substeps, int) or substeps < 1:
+            raise ValueError(f"substeps must be an int >= 1, got {substeps!r}")
+        self.substeps = substeps
         # public attributes of the reference (my_solvers.py:13-18)
         self.step_size = step_size
         self.interp = interp
@@ -75,7 +83,7 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
             self._walk_warned = True
             warnings.warn(f"{what}: this call is not fusable (needs fp32 HIP tensors, DE_Func/AE_Func-style MLPs with one activation "
                           "of ELU / Tanh / Sigmoid / ReLU / LeakyReLU / Softplus / SiLU / GELU / Mish -- other than ELU(1) on kernel 'auto' / 'generic' only --, "
-                          "ODE_Event/DAE_Event callbacks; an ExplicitRK tableau on kernel 'auto' / 'generic' only; under autograd also a shape with a backward kernel; teacher-forced "
+                          "ODE_Event/DAE_Event callbacks; an ExplicitRK tableau or substeps > 1 on kernel 'auto' / 'generic' only (substeps <= 1024); under autograd also a shape with a backward kernel; teacher-forced "
                           "training: ELU(1), dataset rows without grad) -- stepping through the Python callables instead", RuntimeWarning, stacklevel=3)
 
     def _act_kernel_ok(self, what, acts) -> bool:
@@ -99,6 +107,16 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
                                         "tableaus run on the generic kernels (kernel 'auto' / 'generic')")
         return False
 
+    def _sub_kernel_ok(self, what) -> bool:
+        """Sub-steps per grid interval (substeps > 1) run on the generic kernels K0 / K5 only, up to 1024 of them: kernel 'wave' / 'tile' /
+        'mfma' / 'wide' with them walks under fused='auto' and raises under 'require'."""
+        if self.substeps == 1 or (self.kernel in ("auto", "generic") and self.substeps <= _fused._lib.MAX_SUBSTEPS):
+            return True
+        if self.fused == "require":
+            raise UnsupportedShapeError(f"{what}: kernel={self.kernel!r} with substeps={self.substeps} has no fused form: sub-steps per grid "
+                                        f"interval run on the generic kernels (kernel 'auto' / 'generic', substeps <= {_fused._lib.MAX_SUBSTEPS})")
+        return False
+
     def _check_events_now(self, event_t):
         return (self.check_events and event_t is not None and event_t.dim() == 3 and event_t.shape[1] > 1
                 and not torch.cuda.is_current_stream_capturing())
@@ -120,8 +138,10 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
             raise ValueError("integrate_ODE: x_init and input_true_x exclude each other (teacher forcing starts every step from x[k])")
         if self.fused != "off":
             plan = _fused.plan_ode(x_func, x, z, all_initial, event_fn, jump_change_fn, t=t, x_init=x_init)
-            if plan is not None and not (self._act_kernel_ok("integrate_ODE", plan[4:]) and self._rk_kernel_ok("integrate_ODE")):
+            if plan is not None and not (self._act_kernel_ok("integrate_ODE", plan[4:]) and self._rk_kernel_ok("integrate_ODE")
+                                         and self._sub_kernel_ok("integrate_ODE")):
                 plan = None
+            sub = dict(substeps=self.substeps) if self.substeps != 1 else {}      # (substeps == 1: the calls as they always were)
             if plan is not None:
                 layers, event_t, z_jump, needs_grad, act = plan
                 if not needs_grad:
@@ -129,23 +149,23 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
                         return _fused.ode_integrate(self.method, layers, t, x if x_init is None else x_init.unsqueeze(0), z, all_initial,
                                                     event_t=event_t, z_jump=z_jump,
                                                     input_true_x=input_true_x, kernel=self.kernel,
-                                                    check_events=self._check_events_now(event_t), act=act)
+                                                    check_events=self._check_events_now(event_t), act=act, **sub)
                     except UnsupportedShapeError:      # no kernel covers the shape (too wide for LDS): user callables it is
                         if self.fused == "require":
                             raise
                 # training: fused forward + fused backward when the backward kernel covers the shape
                 elif not input_true_x and _autograd().ode_training_supported(self.method, layers, x.shape[-1], z.shape[-1], t.shape[0],
-                                                                             t.shape[1], kernel=self.kernel, act=act):
+                                                                             t.shape[1], kernel=self.kernel, act=act, **sub):
                     from ..autograd import fused_ode_integrate
                     return fused_ode_integrate(self.method, self.kernel, layers, t, x, z, all_initial, event_t, z_jump,
-                                               check_events=self._check_events_now(event_t), x_init=x_init, act=act)
+                                               check_events=self._check_events_now(event_t), x_init=x_init, act=act, **sub)
                 # teacher-forced training (my_solvers.py:72-74): K4f in its recompute form where the shape is its, else K5 (ELU(1) only);
                 # the dataset x gets no gradient
                 elif input_true_x and act is None and not x.requires_grad and _autograd().ode_training_supported(
-                        self.method, layers, x.shape[-1], z.shape[-1], t.shape[0], t.shape[1], kernel=self.kernel, input_true_x=True):
+                        self.method, layers, x.shape[-1], z.shape[-1], t.shape[0], t.shape[1], kernel=self.kernel, input_true_x=True, **sub):
                     from ..autograd import fused_ode_integrate
                     return fused_ode_integrate(self.method, self.kernel, layers, t, x, z, all_initial, event_t, z_jump,
-                                               check_events=self._check_events_now(event_t), input_true_x=True)
+                                               check_events=self._check_events_now(event_t), input_true_x=True, **sub)
             if self.fused == "require":
                 raise NotFusableError("integrate_ODE: call is not fusable (needs fp32 HIP tensors, a DE_Func-style MLP `x_dot` with one "
                                       "activation of ELU / Tanh / Sigmoid / ReLU / LeakyReLU / Softplus / SiLU / GELU / Mish, ODE_Event callbacks; with autograd: "
@@ -163,7 +183,13 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
             if event_fn is not None and event_fn(t0) == True:  # noqa: E712 (callbacks may return tensors)
                 zk = jump_change_fn(t0, zk)
             start = x[k] if input_true_x else cur
-            cur, _ = self.step_integrate(func=x_func, t0=t0, dt=t1 - t0, t1=t1, x0=start, z0=zk, all_initial=all_initial)
+            if self.substeps == 1:
+                cur, _ = self.step_integrate(func=x_func, t0=t0, dt=t1 - t0, t1=t1, x0=start, z0=zk, all_initial=all_initial)
+            else:       # n equal sub-steps of h = (t1 - t0) / n with the interval's z held; only sub-step 0 starts from the dataset row
+                h = (t1 - t0) / self.substeps
+                cur = start
+                for j in range(self.substeps):
+                    cur, _ = self.step_integrate(func=x_func, t0=t0 + j * h, dt=h, t1=t0 + (j + 1) * h, x0=cur, z0=zk, all_initial=all_initial)
             xs[k + 1] = cur
         return xs
 
@@ -172,8 +198,10 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
                       input_true_x=False, input_true_i=False):
         if self.fused != "off":
             plan = _fused.plan_dae(x_init, x_func, i_func, z, v, i, all_initial, event_fn, jump_change_fn, t=t)
-            if plan is not None and not (self._act_kernel_ok("integrate_DAE", plan[6:]) and self._rk_kernel_ok("integrate_DAE")):
+            if plan is not None and not (self._act_kernel_ok("integrate_DAE", plan[6:]) and self._rk_kernel_ok("integrate_DAE")
+                                         and self._sub_kernel_ok("integrate_DAE")):
                 plan = None
+            sub = dict(substeps=self.substeps) if self.substeps != 1 else {}
             if plan is not None:
                 de, ae, event_t, z_jump, v_jump, needs_grad, de_act, ae_act = plan
                 act = None if de_act is None and ae_act is None else (de_act, ae_act)
@@ -182,25 +210,25 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
                         return _fused.dae_integrate(self.method, de, ae, x_init, t, x, z, v, i, all_initial, event_t=event_t,
                                                     z_jump=z_jump, v_jump=v_jump, input_true_x=input_true_x,
                                                     input_true_i=input_true_i, kernel=self.kernel,
-                                                    check_events=self._check_events_now(event_t), act=act)
+                                                    check_events=self._check_events_now(event_t), act=act, **sub)
                     except UnsupportedShapeError:
                         if self.fused == "require":
                             raise
                 elif not (input_true_x or input_true_i) and _autograd().dae_training_supported(
-                        self.method, de, ae, x_init.shape[-1], z.shape[-1], v.shape[-1], i.shape[-1], t.shape[0], t.shape[1], act=act):
+                        self.method, de, ae, x_init.shape[-1], z.shape[-1], v.shape[-1], i.shape[-1], t.shape[0], t.shape[1], act=act, **sub):
                     from ..autograd import fused_dae_integrate
                     return fused_dae_integrate(self.method, self.kernel, de, ae, x_init, t, z, v, i, all_initial, event_t, z_jump, v_jump,
-                                               check_events=self._check_events_now(event_t), act=act)
+                                               check_events=self._check_events_now(event_t), act=act, **sub)
                 # teacher-forced training (my_solvers.py:111-121): K7f in its recompute form where the shape is its, else K5 (ELU(1) only);
                 # the dataset rows get no gradient
                 elif act is None and (input_true_x or input_true_i) and not (input_true_x and x.requires_grad) and not (input_true_i and i.requires_grad) \
                         and x.shape[-1] == x_init.shape[-1] and _autograd().dae_training_supported(
                             self.method, de, ae, x_init.shape[-1], z.shape[-1], v.shape[-1], i.shape[-1], t.shape[0], t.shape[1],
-                            kernel=self.kernel, input_true_x=input_true_x, input_true_i=input_true_i):
+                            kernel=self.kernel, input_true_x=input_true_x, input_true_i=input_true_i, **sub):
                     from ..autograd import fused_dae_integrate
                     return fused_dae_integrate(self.method, self.kernel, de, ae, x_init, t, z, v, i, all_initial, event_t, z_jump, v_jump,
                                                check_events=self._check_events_now(event_t), x=x, input_true_x=input_true_x,
-                                               input_true_i=input_true_i)
+                                               input_true_i=input_true_i, **sub)
             if self.fused == "require":
                 raise NotFusableError("integrate_DAE: call is not fusable (needs fp32 HIP tensors, DE_Func/AE_Func-style "
                                       "MLPs with one activation each of ELU / Tanh / Sigmoid / ReLU / LeakyReLU / Softplus / SiLU / GELU / Mish, DAE_Event callbacks; with autograd: a shape with a backward kernel; teacher-forced training: ELU(1), kernel 'auto' / 'mfma' / 'generic', T >= 2, dataset rows without grad)")
@@ -223,8 +251,17 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
                 cur_i = i_func(xt=cur_x, zt=zk, vt=vk, all_initial=all_initial)
             start = x[k] if input_true_x else cur_x
             i_in = i[k] if input_true_i else cur_i
-            cur_x, _ = self.step_integrate(func=x_func, t0=t0, dt=t1 - t0, t1=t1, x0=start, z0=zk, v0=vk, i0=i_in,
-                                           all_initial=all_initial)
+            if self.substeps == 1:
+                cur_x, _ = self.step_integrate(func=x_func, t0=t0, dt=t1 - t0, t1=t1, x0=start, z0=zk, v0=vk, i0=i_in,
+                                               all_initial=all_initial)
+            else:       # n equal sub-steps with the interval's z | v held; the algebraic variable follows the state inside the interval
+                h = (t1 - t0) / self.substeps
+                cur_x = start
+                for j in range(self.substeps):
+                    if j > 0 and not input_true_i:
+                        i_in = i_func(xt=cur_x, zt=zk, vt=vk, all_initial=all_initial)
+                    cur_x, _ = self.step_integrate(func=x_func, t0=t0 + j * h, dt=h, t1=t0 + (j + 1) * h, x0=cur_x, z0=zk, v0=vk, i0=i_in,
+                                                   all_initial=all_initial)
             cur_i = i_func(xt=x[k + 1] if input_true_x else cur_x, zt=z[k + 1], vt=v[k + 1], all_initial=all_initial)
             xs[k + 1], is_[k + 1] = cur_x, cur_i
         return xs, is_
