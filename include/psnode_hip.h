@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define PSNODE_ABI_VERSION 10    /* 10 also carries the additive psnode_act_f32 / *_act_*, psnode_rk_tableau_f32 / *_rk_* and psnode_substeps_f32 / *_sub_* entry points (end of this file) */
+#define PSNODE_ABI_VERSION 10    /* 10 also carries the additive psnode_act_f32 / *_act_*, psnode_rk_tableau_f32 / *_rk_*, psnode_substeps_f32 / *_sub_* and *_lin_* entry points (end of this file) */
 #define PSNODE_MAX_LAYERS 8      /* Linear layers per MLP */
 #define PSNODE_MAX_WIDTH 1024    /* widest layer OUTPUT the kernels accept */
 #define PSNODE_MAX_IN_WIDTH 2048 /* widest first-layer INPUT (the latent DE of DAE_02 at --hidden 128 is 12 x 128 = 1536 wide) */
@@ -767,6 +767,44 @@ int32_t psnode_dae_backward_sub_supported(const psnode_dae_bwd_tf_args_f32* args
 size_t psnode_dae_backward_sub_workspace_bytes(const psnode_dae_bwd_tf_args_f32* args, const psnode_act_f32* de_act,
                                                const psnode_act_f32* ae_act, const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub);
 int32_t psnode_dae_backward_sub_f32(const psnode_dae_bwd_tf_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                    const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, void* workspace, size_t workspace_bytes,
+                                    void* stream);
+
+/* ---- Linear interpolation of externals on the generic kernels (additive to ABI 10; DESIGN.md "Linear interpolation of externals on K0 / K5").
+ * The entry point itself means "linear": stage s (abscissa c_s = sum_{j<s} a[s][j], summed in increasing index) of sub-step j of interval k
+ * reads, for every column of z | v,
+ *     theta = (j + c_s) / n,   w = w_L + theta * (w_R - w_L)          (fp32, as written, not contracted)
+ * with w_L row k of the dataset (the jumped values on an interval that starts with an event) and w_R row k + 1 of the dataset, never
+ * jumped; rows beyond T - 1 are not read.  theta does not depend on the clock.  h, the event table, the event-time head (theta = 0), the
+ * head at grid point k + 1 (rows k + 1), the outputs and both teacher-forcing flags are what the _sub entry points define; the algebraic
+ * variable is never interpolated; a DAE that integrates its own i evaluates the head in front of sub-step j >= 1 at the state and the
+ * z | v of theta = j / n.  A backward call adds (1 - theta) g to the gradient of w_L (row k of grad_z / grad_v, or the event's jump
+ * gradient) and theta g to row k + 1; no atomics, bitwise repeatable.
+ * Rules (the entry points take exactly what their _sub siblings take):
+ *   - a NULL psnode_substeps_f32 means one sub-step; otherwise substeps outside 1..1024 gives PSNODE_ERR_DIMS; every substeps >= 1 runs here;
+ *   - a NULL act is ELU(1); a NULL tableau is the built-in `method` of the args written as its tableau;
+ *   - `kernel` must be PSNODE_KERNEL_AUTO or _GENERIC and the save_* / saved_* pointers NULL (PSNODE_ERR_UNSUPPORTED); a teacher-forced
+ *     backward needs ELU(1); the _supported queries answer for this build's own LDS fit (K0: z_dim + v_dim more rows; K5: three times that);
+ *   - a backward call with substeps > 1, T >= 2 and a NULL x_sub gives PSNODE_ERR_NULL.
+ * Every check returns its status before anything is launched.  Workspaces: those of the _rk entry points. */
+int32_t psnode_ode_integrate_lin_supported(const psnode_ode_args_f32* args, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
+                                           const psnode_substeps_f32* sub);
+int32_t psnode_ode_integrate_lin_f32(const psnode_ode_args_f32* args, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
+                                     const psnode_substeps_f32* sub, void* workspace, size_t workspace_bytes, void* stream);
+int32_t psnode_dae_integrate_lin_supported(const psnode_dae_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                           const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub);
+int32_t psnode_dae_integrate_lin_f32(const psnode_dae_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                     const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, void* workspace, size_t workspace_bytes,
+                                     void* stream);
+int32_t psnode_ode_backward_lin_supported(const psnode_ode_bwd_args_f32* args, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
+                                          const psnode_substeps_f32* sub);
+int32_t psnode_ode_backward_lin_f32(const psnode_ode_bwd_args_f32* args, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
+                                    const psnode_substeps_f32* sub, void* workspace, size_t workspace_bytes, void* stream);
+int32_t psnode_dae_backward_lin_supported(const psnode_dae_bwd_tf_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                          const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub);
+size_t psnode_dae_backward_lin_workspace_bytes(const psnode_dae_bwd_tf_args_f32* args, const psnode_act_f32* de_act,
+                                               const psnode_act_f32* ae_act, const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub);
+int32_t psnode_dae_backward_lin_f32(const psnode_dae_bwd_tf_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
                                     const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, void* workspace, size_t workspace_bytes,
                                     void* stream);
 

@@ -34,7 +34,9 @@ ABI_VERSION = 10         # == PSNODE_ABI_VERSION of include/psnode_hip.h (2: rou
                          #     additive, same version: psnode_rk_tableau_f32 and the psnode_{ode,dae}_{integrate,backward}_rk_* entry points --
                          #     explicit Runge-Kutta tableaus of up to four stages on K0 / K5;
                          #     additive, same version: psnode_substeps_f32 and the psnode_{ode,dae}_{integrate,backward}_sub_* entry points --
-                         #     sub-steps per grid interval on K0 / K5)
+                         #     sub-steps per grid interval on K0 / K5;
+                         #     additive, same version: the psnode_{ode,dae}_{integrate,backward}_lin_* entry points -- z | v interpolated
+                         #     linearly inside every grid interval on K0 / K5)
 LIB_NAME = "libpsnode_hip.so"
 # PSNODE_LIB_PATH lets kernel experiments (profiles/scripts/*) load an alternative build of the same ABI
 LIB_PATH = os.environ.get("PSNODE_LIB_PATH") or os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
@@ -67,6 +69,9 @@ EXPORTS = (
     "psnode_ode_integrate_sub_supported", "psnode_ode_integrate_sub_f32", "psnode_dae_integrate_sub_supported", "psnode_dae_integrate_sub_f32",
     "psnode_ode_backward_sub_supported", "psnode_ode_backward_sub_f32",
     "psnode_dae_backward_sub_supported", "psnode_dae_backward_sub_workspace_bytes", "psnode_dae_backward_sub_f32",
+    "psnode_ode_integrate_lin_supported", "psnode_ode_integrate_lin_f32", "psnode_dae_integrate_lin_supported", "psnode_dae_integrate_lin_f32",
+    "psnode_ode_backward_lin_supported", "psnode_ode_backward_lin_f32",
+    "psnode_dae_backward_lin_supported", "psnode_dae_backward_lin_workspace_bytes", "psnode_dae_backward_lin_f32",
 )
 
 
@@ -326,12 +331,14 @@ def load():
     sub_p = ctypes.POINTER(SubstepsF32)
     for name, args_t, n_act in (("ode_integrate", OdeArgsF32, 1), ("dae_integrate", DaeArgsF32, 2), ("ode_backward", OdeBwdArgsF32, 1),
                                 ("dae_backward", DaeBwdTfArgsF32, 2)):
-        q = getattr(lib, f"psnode_{name}_sub_supported")
-        q.restype, q.argtypes = c_int32, [ctypes.POINTER(args_t)] + [act_p] * n_act + [rk_p, sub_p]
-        f = getattr(lib, f"psnode_{name}_sub_f32")
-        f.restype, f.argtypes = c_int32, [ctypes.POINTER(args_t)] + [act_p] * n_act + [rk_p, sub_p, c_void_p, c_size_t, c_void_p]
-    lib.psnode_dae_backward_sub_workspace_bytes.restype = c_size_t
-    lib.psnode_dae_backward_sub_workspace_bytes.argtypes = [ctypes.POINTER(DaeBwdTfArgsF32), act_p, act_p, rk_p, sub_p]
+        for fam in ("sub", "lin"):      # (the _lin entry points take exactly what their _sub siblings take)
+            q = getattr(lib, f"psnode_{name}_{fam}_supported")
+            q.restype, q.argtypes = c_int32, [ctypes.POINTER(args_t)] + [act_p] * n_act + [rk_p, sub_p]
+            f = getattr(lib, f"psnode_{name}_{fam}_f32")
+            f.restype, f.argtypes = c_int32, [ctypes.POINTER(args_t)] + [act_p] * n_act + [rk_p, sub_p, c_void_p, c_size_t, c_void_p]
+    for fam in ("sub", "lin"):
+        w = getattr(lib, f"psnode_dae_backward_{fam}_workspace_bytes")
+        w.restype, w.argtypes = c_size_t, [ctypes.POINTER(DaeBwdTfArgsF32), act_p, act_p, rk_p, sub_p]
     lib.psnode_mlp_rows_backward_workspace_bytes.restype = c_size_t
     lib.psnode_mlp_rows_backward_workspace_bytes.argtypes = [ctypes.POINTER(MlpF32), c_int64]
     lib.psnode_mlp_rows_backward_f32.restype = c_int32

@@ -41,18 +41,20 @@ def latent_wide_training_fits(method, de, ae, hidden, T, B, dev) -> bool:
     return need <= free // 2
 
 
-def ode_training_supported(method, layers, x_dim, z_dim, T, B, kernel="auto", act=None, input_true_x=False, substeps=1) -> bool:
+def ode_training_supported(method, layers, x_dim, z_dim, T, B, kernel="auto", act=None, input_true_x=False, substeps=1,
+                           externals="hold") -> bool:
     """What the solver asks before it routes a call that needs autograd to the fused forward + backward pair.  act (fused.Act; None =
     ELU(1)): an activation other than ELU(1) trains on K0 + K5 alone, so K5 answers.  input_true_x: teacher-forced training -- K4f's
     recompute form on kernel "auto" / "mfma" where the shape is its, else K5 on "auto" / "generic"; ELU(1) only.
     method a fused.Tableau: K0 + K5 on kernel "auto" / "generic" (K5's tableau build answers for its fit), the same teacher-forcing rule.
-    substeps > 1: K0 + K5 in their sub-step builds on kernel "auto" / "generic" (K5's answers for its fit), the same teacher-forcing rule."""
+    substeps > 1: K0 + K5 in their sub-step builds on kernel "auto" / "generic" (K5's answers for its fit), the same teacher-forcing rule.
+    externals="linear": K0 + K5 in their linear-externals builds for every substeps >= 1, the same rules."""
     if _is_tableau(method) and kernel not in ("auto", "generic"):
         return False
-    if substeps != 1:
+    if substeps != 1 or fused.is_linear(externals):
         if kernel not in ("auto", "generic") or (input_true_x and act is not None):
             return False
-        return fused.ode_backward_supported(method, layers, x_dim, z_dim, kernel, act=act, substeps=substeps)
+        return fused.ode_backward_supported(method, layers, x_dim, z_dim, kernel, act=act, substeps=substeps, externals=externals)
     if input_true_x:
         if act is not None:
             return False
@@ -71,18 +73,20 @@ def _dae_tf_on_k7f(method, kernel, de, ae, x_dim, z_dim, v_dim, i_dim) -> bool:
 
 
 def dae_training_supported(method, de, ae, x_dim, z_dim, v_dim, i_dim, T, B, act=None, kernel="auto", input_true_x=False,
-                           input_true_i=False, substeps=1) -> bool:
+                           input_true_i=False, substeps=1, externals="hold") -> bool:
     """act: None (both MLPs ELU(1)) or (de_act, ae_act); an activation other than ELU(1) trains on K0 + K5 alone, so K5 answers.
     input_true_x / input_true_i: teacher-forced training (T >= 2, ELU(1) only) -- K7f's recompute form on kernel "auto" / "mfma" where the
     shape is its, else K5 on "auto" / "generic".  method a fused.Tableau: K0 + K5 on kernel "auto" / "generic", the same rules.
-    substeps > 1: K0 + K5 in their sub-step builds on kernel "auto" / "generic", the same rules."""
+    substeps > 1: K0 + K5 in their sub-step builds on kernel "auto" / "generic", the same rules.
+    externals="linear": K0 + K5 in their linear-externals builds for every substeps >= 1, the same rules."""
     if _is_tableau(method) and kernel not in ("auto", "generic"):
         return False
-    if substeps != 1:
+    if substeps != 1 or fused.is_linear(externals):
         non_elu = act is not None and any(a is not None for a in act)
         if kernel not in ("auto", "generic") or ((input_true_x or input_true_i) and (T < 2 or non_elu)):
             return False
-        return fused.dae_backward_supported(method, de, ae, x_dim, z_dim, v_dim, i_dim, act=act, kernel=kernel, substeps=substeps)
+        return fused.dae_backward_supported(method, de, ae, x_dim, z_dim, v_dim, i_dim, act=act, kernel=kernel, substeps=substeps,
+                                            externals=externals)
     if input_true_x or input_true_i:
         if T < 2 or (act is not None and any(a is not None for a in act)):
             return False
@@ -228,15 +232,17 @@ class _FusedOde(torch.autograd.Function):
 
 class _FusedOdeSub(torch.autograd.Function):
     """integrate_ODE with substeps > 1, plain or teacher-forced: K0 forward in its sub-step build, which also writes the start state of every
-    sub-step behind an interval's first (x_sub, saved next to xs), K5 backward in its sub-step build."""
+    sub-step behind an interval's first (x_sub, saved next to xs), K5 backward in its sub-step build.  ctx.externals ("hold" unless the
+    sibling _FusedOdeLin set it) travels to both calls."""
 
     @staticmethod
     def forward(ctx, method, kernel, act, substeps, tx, event_idx, t, x0, z, all_initial, z_jump, *params):
+        ctx.externals = getattr(ctx, "externals", "hold")
         layers = [(params[k], params[k + 1]) for k in range(0, len(params), 2)]
         global last_saved_bytes
         x_in = x0.detach().contiguous() if tx else x0.unsqueeze(0)      # tx: the whole dataset x [T,B,xd]
         xs, x_sub = fused.ode_integrate(method, layers, t, x_in, z, all_initial, z_jump=z_jump, event_idx=event_idx, kernel=kernel,
-                                        input_true_x=tx, act=act, substeps=substeps, save_sub=True)
+                                        input_true_x=tx, act=act, substeps=substeps, save_sub=True, externals=ctx.externals)
         last_saved_bytes = x_sub.numel() * x_sub.element_size()
         ctx.method, ctx.kernel, ctx.act, ctx.substeps, ctx.tx, ctx.event_idx, ctx.has_jump = method, kernel, act, substeps, tx, event_idx, z_jump is not None
         # (tx: the backward starts every interval from the dataset row and reads no xs)
@@ -253,14 +259,25 @@ class _FusedOdeSub(torch.autograd.Function):
         need_z = ctx.needs_input_grad[8]
         gx0, gz, gzj, ga0, gpar = fused.ode_backward(ctx.method, layers, t, z, a0, xs, grad_xs, event_idx=ctx.event_idx, z_jump=z_jump,
                                                      need_grad_z=need_z, need_grad_zj=bool(ctx.needs_input_grad[10]), kernel=ctx.kernel,
-                                                     input_true_x=ctx.tx, act=ctx.act, substeps=ctx.substeps, x_sub=x_sub)
+                                                     input_true_x=ctx.tx, act=ctx.act, substeps=ctx.substeps, x_sub=x_sub,
+                                                     externals=ctx.externals)
         if gz is None and need_z:
             gz = torch.zeros_like(z)
         return (None, None, None, None, None, None, None, None if ctx.tx else gx0, gz, ga0, gzj if ctx.needs_input_grad[10] else None, *gpar)
 
 
+class _FusedOdeLin(_FusedOdeSub):
+    """integrate_ODE with externals="linear", every substeps >= 1: _FusedOdeSub on the linear-externals builds of K0 / K5 (grad z[k + 1]
+    also takes the right-hand share of interval k)."""
+
+    @staticmethod
+    def forward(ctx, *args):
+        ctx.externals = "linear"
+        return _FusedOdeSub.forward(ctx, *args)
+
+
 def fused_ode_integrate(method, kernel, layers, t, x, z, all_initial, event_t=None, z_jump=None, check_events=False, input_true_x=False,
-                        x_init=None, act=None, substeps=1):
+                        x_init=None, act=None, substeps=1, externals="hold"):
     """Differentiable fused integrate_ODE: gradients flow to x[0], z, all_initial, z_jump and the MLP.  input_true_x (teacher forcing,
     my_solvers.py:72-74): every step starts from the dataset row x[k]; gradients flow to z, all_initial, z_jump and the MLP (the dataset
     x gets none: callers whose x requires grad take the callback walk).  act: the MLP's activation (fused.Act), None = ELU(1); any other
@@ -271,6 +288,8 @@ def fused_ode_integrate(method, kernel, layers, t, x, z, all_initial, event_t=No
         z_jump = None
     params = [p for wb in layers for p in wb]
     x0 = x.detach() if input_true_x else (x[0] if x_init is None else x_init)     # (x_init: integrate_ODE's extension -- no SelectBackward)
+    if fused.is_linear(externals):
+        return _FusedOdeLin.apply(method, kernel, act, substeps, bool(input_true_x), event_idx, t, x0, z, all_initial, z_jump, *params)
     if substeps != 1:
         return _FusedOdeSub.apply(method, kernel, act, substeps, bool(input_true_x), event_idx, t, x0, z, all_initial, z_jump, *params)
     return _FusedOde.apply(method, kernel, act, event_idx, t, x0, z, all_initial, z_jump, *params)
@@ -377,12 +396,13 @@ class _FusedDaeSub(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, method, kernel, act, substeps, tx, ti, event_idx, n_de, t, x_init, x, z, v, i, all_initial, z_jump, v_jump, *params):
+        ctx.externals = getattr(ctx, "externals", "hold")      # ("linear": the sibling _FusedDaeLin set it)
         de = [(params[k], params[k + 1]) for k in range(0, 2 * n_de, 2)]
         ae = [(params[k], params[k + 1]) for k in range(2 * n_de, len(params), 2)]
         non_elu = act is not None and any(a is not None for a in act)
         xs, is_, x_sub = fused.dae_integrate(method, de, ae, x_init, t, x, z, v, i, all_initial, z_jump=z_jump, v_jump=v_jump, event_idx=event_idx,
                                              kernel=kernel, input_true_x=tx, input_true_i=ti, act=act if non_elu else None, substeps=substeps,
-                                             save_sub=True)
+                                             save_sub=True, externals=ctx.externals)
         global last_saved_bytes
         last_saved_bytes = x_sub.numel() * x_sub.element_size()
         ctx.method, ctx.kernel, ctx.act, ctx.substeps, ctx.tx, ctx.ti = method, kernel, act if non_elu else None, substeps, tx, ti
@@ -403,7 +423,8 @@ class _FusedDaeSub(torch.autograd.Function):
         params = sv[k:]
         de = [(params[q], params[q + 1]) for q in range(0, 2 * ctx.n_de, 2)]
         ae = [(params[q], params[q + 1]) for q in range(2 * ctx.n_de, len(params), 2)]
-        common = dict(event_idx=ctx.event_idx, z_jump=z_jump, v_jump=v_jump, kernel=ctx.kernel, substeps=ctx.substeps, x_sub=x_sub)
+        common = dict(event_idx=ctx.event_idx, z_jump=z_jump, v_jump=v_jump, kernel=ctx.kernel, substeps=ctx.substeps, x_sub=x_sub,
+                      externals=ctx.externals)
         if ctx.tx or ctx.ti:
             g = fused.dae_backward_tf(ctx.method, de, ae, t, z, v, a0, xs, is_, grad_xs, grad_is, x_true=x if ctx.tx else None,
                                       i_true=i if ctx.ti else None, **common)
@@ -415,8 +436,17 @@ class _FusedDaeSub(torch.autograd.Function):
                 g["z_jump"] if ctx.needs_input_grad[15] else None, g["v_jump"] if ctx.needs_input_grad[16] else None, *g["de"], *g["ae"])
 
 
+class _FusedDaeLin(_FusedDaeSub):
+    """integrate_DAE with externals="linear", every substeps >= 1: _FusedDaeSub on the linear-externals builds of K0 / K5."""
+
+    @staticmethod
+    def forward(ctx, *args):
+        ctx.externals = "linear"
+        return _FusedDaeSub.forward(ctx, *args)
+
+
 def fused_dae_integrate(method, kernel, de_layers, ae_layers, x_init, t, z, v, i, all_initial, event_t=None, z_jump=None, v_jump=None,
-                        check_events=False, x=None, input_true_x=False, input_true_i=False, act=None, substeps=1):
+                        check_events=False, x=None, input_true_x=False, input_true_i=False, act=None, substeps=1, externals="hold"):
     """Differentiable fused integrate_DAE: gradients flow to x_init, z, v, all_initial, the jump inputs and both MLPs.  Without teacher
     forcing `i` only provides the width of the algebraic variable.  input_true_x / input_true_i: `x` / `i` are the dataset rows the DE
     and the heads are fed (my_solvers.py:111-121); they get no gradient.  act: None or (de_act, ae_act) (fused.Act, None = ELU(1)); an
@@ -429,9 +459,9 @@ def fused_dae_integrate(method, kernel, de_layers, ae_layers, x_init, t, z, v, i
         z_jump = z_jump if (z_jump is not None and z_jump.shape[-1] > 0) else None
         v_jump = v_jump if (v_jump is not None and v_jump.shape[-1] > 0) else None
     params = [p for wb in list(de_layers) + list(ae_layers) for p in wb]
-    if substeps != 1:
+    if substeps != 1 or fused.is_linear(externals):
         xd_ = x.detach() if input_true_x else x_init.new_zeros((1, t.shape[1], 0))
-        return _FusedDaeSub.apply(method, kernel, act, substeps, bool(input_true_x), bool(input_true_i), event_idx, len(de_layers), t, x_init, xd_,
+        return (_FusedDaeLin if fused.is_linear(externals) else _FusedDaeSub).apply(method, kernel, act, substeps, bool(input_true_x), bool(input_true_i), event_idx, len(de_layers), t, x_init, xd_,
                                   z, v, i.detach(), all_initial, z_jump, v_jump, *params)
     if input_true_x or input_true_i:
         xd_ = x.detach() if input_true_x else x_init.new_zeros((1, t.shape[1], 0))

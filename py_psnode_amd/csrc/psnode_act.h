@@ -235,7 +235,7 @@ inline int act_pair(const psnode_act_f32* de, const psnode_act_f32* ae, ActPair&
 }
 
 // psnode_generic.hip: K0's launch planning, shared by both builds
-size_t generic_plan(const IntegrateDev& a, bool dae, unsigned& mask);
+size_t generic_plan(const IntegrateDev& a, bool dae, unsigned& mask, bool lin = false);      // lin: the linear-externals build's layout
 int generic_reg_mode(const IntegrateDev& a, bool dae);
 bool generic_wide_mode(const IntegrateDev& a, bool dae);
 // psnode_generic_act.hip: K0 with the activations of `act` (the ELU(1) call is launch_generic)
@@ -247,6 +247,9 @@ hipError_t launch_generic_pre(const IntegrateDev& a, bool dae, const ActPair& ac
 hipError_t launch_generic_rk(const IntegrateDev& a, bool dae, const ActPair& act, const psnode_rk_tableau_f32& rk, hipStream_t stream);
 // psnode_generic_sub.hip: the tableau build with sub.n sub-steps per grid interval (sub.x_sub: the sub-states for K5, or null)
 hipError_t launch_generic_sub(const IntegrateDev& a, bool dae, const ActPair& act, const psnode_rk_tableau_f32& rk, const SubDev& sub,
+                              hipStream_t stream);
+// psnode_generic_lin.hip: the sub-step build (sub.n >= 1) with z | v interpolated linearly inside every grid interval
+hipError_t launch_generic_lin(const IntegrateDev& a, bool dae, const ActPair& act, const psnode_rk_tableau_f32& rk, const SubDev& sub,
                               hipStream_t stream);
 
 }  // namespace psnode

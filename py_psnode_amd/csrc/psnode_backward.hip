@@ -89,6 +89,7 @@ GenericBwdCall generic_bwd_call(const psnode_dae_bwd_args_f32& a) {
 }
 // act: the activations of a non-ELU(1) call, or nullptr
 int generic_backward(const GenericBwdCall& c, const ActPair* act, void* workspace, void* stream) {
+    if (c.rk && c.lin) return generic_backward_launch<BuildLin>(c, act, static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
     if (c.rk && c.substeps > 1) return generic_backward_launch<BuildSub>(c, act, static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
     if (c.rk) return generic_backward_launch<BuildRk>(c, act, static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
     const auto launch = !act ? generic_backward_launch<BuildElu1> : (act_pair_pre(*act) ? generic_backward_launch<BuildPre> : generic_backward_launch<BuildAct>);
@@ -303,15 +304,15 @@ extern "C" int32_t psnode_dae_backward_act_f32(const psnode_dae_bwd_args_f32* a,
 // keeps the pre-activations, so the pre fit of generic_bwd_fits answers for the shape).  The act is checked first, then the tableau; `method` is not
 // read; then NULL args -> dims -> unsupported -> pointers -> workspace, as above.
 namespace {
-bool rk_ode_ok(const psnode_ode_bwd_args_f32* a, bool elu1) {
+bool rk_ode_ok(const psnode_ode_bwd_args_f32* a, bool elu1, bool lin = false) {      // lin: the linear-externals build's own LDS fit
     if ((a->kernel != PSNODE_KERNEL_AUTO && a->kernel != PSNODE_KERNEL_GENERIC) || a->saved_act || a->saved_xstage) return false;
     if ((a->flags & ~PSNODE_FLAG_INPUT_TRUE_X) || (a->flags && !elu1)) return false;
     const psnode_mlp_f32& m = a->de;
     if (a->x_dim < 1 || a->z_dim < 0 || m.n_layers < 1 || m.n_layers > kMaxLayers) return false;
     if (m.in_dim != 3 * (a->x_dim + a->z_dim) || m.out_dim[m.n_layers - 1] != a->x_dim) return false;
-    return generic_bwd_fits(&a->de, nullptr, a->x_dim, a->z_dim, 0, 0, true) != 0;
+    return generic_bwd_fits(&a->de, nullptr, a->x_dim, a->z_dim, 0, 0, true, lin) != 0;
 }
-bool rk_dae_ok(const psnode_dae_bwd_tf_args_f32* a, bool elu1) {
+bool rk_dae_ok(const psnode_dae_bwd_tf_args_f32* a, bool elu1, bool lin = false) {
     const psnode_dae_bwd_args_f32& b = a->base;
     if ((a->flags & ~kTfFlags) || (a->flags && !elu1) || (b.kernel != PSNODE_KERNEL_AUTO && b.kernel != PSNODE_KERNEL_GENERIC)) return false;
     if (b.saved_act || b.saved_xstage || b.saved_ae_act || b.saved_ev_act || b.saved_ev_i) return false;
@@ -321,7 +322,7 @@ bool rk_dae_ok(const psnode_dae_bwd_tf_args_f32* a, bool elu1) {
     if (d.n_layers < 1 || d.n_layers > kMaxLayers || g.n_layers < 1 || g.n_layers > kMaxLayers) return false;
     if (d.in_dim != 3 * n || d.out_dim[d.n_layers - 1] != b.x_dim) return false;
     if (g.in_dim != n + b.x_dim + b.z_dim + b.v_dim || g.out_dim[g.n_layers - 1] != b.i_dim) return false;
-    return generic_bwd_fits(&b.de, &b.ae, b.x_dim, b.z_dim, b.v_dim, b.i_dim, true) != 0;
+    return generic_bwd_fits(&b.de, &b.ae, b.x_dim, b.z_dim, b.v_dim, b.i_dim, true, lin) != 0;
 }
 }  // namespace
 
@@ -481,5 +482,81 @@ extern "C" int32_t psnode_dae_backward_sub_f32(const psnode_dae_bwd_tf_args_f32*
     if (!workspace_ok(workspace, workspace_bytes, generic_bwd_workspace_floats(&b->de, &b->ae, b->B) * sizeof(float))) return PSNODE_ERR_WORKSPACE;
     GenericBwdCall c = generic_bwd_call(*b);
     c.flags = a->flags; c.xt = a->x_true; c.it = a->i_true; c.rk = &t; c.substeps = sub->substeps; c.x_sub = sub->x_sub;
+    return generic_backward(c, &p, workspace, stream);
+}
+
+// ---- linearly interpolated externals (include/psnode_hip.h, "Linear interpolation of externals"): K5's linear-externals build alone, for
+// every substeps >= 1 (a NULL struct is one sub-step).  The struct is checked first, then the act, the tableau (NULL: the args' method as
+// one); then NULL args -> dims -> unsupported -> pointers (x_sub among them) -> workspace, as above.
+extern "C" int32_t psnode_ode_backward_lin_supported(const psnode_ode_bwd_args_f32* a, const psnode_act_f32* de_act,
+                                                     const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub) {
+    ActPair p;
+    bool elu1 = true;
+    psnode_rk_tableau_f32 t;
+    if (!a || (sub && substeps_check(sub)) || act_pair(de_act, nullptr, p, elu1) || sub_tableau(tab, a->method, t)) return 0;
+    return rk_ode_ok(a, elu1, true);
+}
+
+extern "C" int32_t psnode_ode_backward_lin_f32(const psnode_ode_bwd_args_f32* a, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
+                                               const psnode_substeps_f32* sub, void* workspace, size_t workspace_bytes, void* stream) {
+    int rc = sub ? substeps_check(sub) : PSNODE_OK;
+    if (rc) return rc;
+    const int nsub = sub ? sub->substeps : 1;
+    ActPair p;
+    bool elu1 = true;
+    rc = act_pair(de_act, nullptr, p, elu1);
+    if (rc) return rc;
+    if (!a) return PSNODE_ERR_NULL;
+    psnode_rk_tableau_f32 t;
+    rc = sub_tableau(tab, a->method, t);
+    if (rc) return rc;
+    if (a->T < 1 || a->B < 1) return PSNODE_ERR_DIMS;
+    if (!rk_ode_ok(a, elu1, true)) return PSNODE_ERR_UNSUPPORTED;
+    if (!ptrs_ok(a) || (nsub > 1 && a->T >= 2 && !sub->x_sub)) return PSNODE_ERR_NULL;
+    if (!workspace_ok(workspace, workspace_bytes, generic_bwd_workspace_floats(&a->de, nullptr, a->B) * sizeof(float))) return PSNODE_ERR_WORKSPACE;
+    GenericBwdCall c = generic_bwd_call(*a);
+    c.rk = &t; c.substeps = nsub; c.x_sub = sub ? sub->x_sub : nullptr; c.lin = true;
+    return generic_backward(c, &p, workspace, stream);
+}
+
+extern "C" int32_t psnode_dae_backward_lin_supported(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act,
+                                                     const psnode_act_f32* ae_act, const psnode_rk_tableau_f32* tab,
+                                                     const psnode_substeps_f32* sub) {
+    ActPair p;
+    bool elu1 = true;
+    psnode_rk_tableau_f32 t;
+    if (!a || (sub && substeps_check(sub)) || act_pair(de_act, ae_act, p, elu1) || sub_tableau(tab, a->base.method, t)) return 0;
+    return rk_dae_ok(a, elu1, true);
+}
+
+extern "C" size_t psnode_dae_backward_lin_workspace_bytes(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act,
+                                                          const psnode_act_f32* ae_act, const psnode_rk_tableau_f32* tab,
+                                                          const psnode_substeps_f32* sub) {
+    if (!psnode_dae_backward_lin_supported(a, de_act, ae_act, tab, sub)) return 0;
+    return generic_bwd_workspace_floats(&a->base.de, &a->base.ae, a->base.B) * sizeof(float);
+}
+
+extern "C" int32_t psnode_dae_backward_lin_f32(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                               const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, void* workspace,
+                                               size_t workspace_bytes, void* stream) {
+    int rc = sub ? substeps_check(sub) : PSNODE_OK;
+    if (rc) return rc;
+    const int nsub = sub ? sub->substeps : 1;
+    ActPair p;
+    bool elu1 = true;
+    rc = act_pair(de_act, ae_act, p, elu1);
+    if (rc) return rc;
+    if (!a) return PSNODE_ERR_NULL;
+    const psnode_dae_bwd_args_f32* b = &a->base;
+    psnode_rk_tableau_f32 t;
+    rc = sub_tableau(tab, b->method, t);
+    if (rc) return rc;
+    if (b->T < 1 || b->B < 1 || (a->flags && b->T < 2)) return PSNODE_ERR_DIMS;
+    if (!rk_dae_ok(a, elu1, true)) return PSNODE_ERR_UNSUPPORTED;
+    if (!ptrs_ok(b) || (nsub > 1 && b->T >= 2 && !sub->x_sub)) return PSNODE_ERR_NULL;
+    if (((a->flags & PSNODE_FLAG_INPUT_TRUE_X) && !a->x_true) || ((a->flags & PSNODE_FLAG_INPUT_TRUE_I) && !a->i_true)) return PSNODE_ERR_NULL;
+    if (!workspace_ok(workspace, workspace_bytes, generic_bwd_workspace_floats(&b->de, &b->ae, b->B) * sizeof(float))) return PSNODE_ERR_WORKSPACE;
+    GenericBwdCall c = generic_bwd_call(*b);
+    c.flags = a->flags; c.xt = a->x_true; c.it = a->i_true; c.rk = &t; c.substeps = nsub; c.x_sub = sub ? sub->x_sub : nullptr; c.lin = true;
     return generic_backward(c, &p, workspace, stream);
 }

@@ -87,10 +87,11 @@ __global__ void event_table_kernel(long long n_steps, const float* clock, long l
 ViewDev view(const psnode_view_f32& v) { return ViewDev{v.ptr, v.stride_t, v.stride_b}; }
 
 // act: the hidden layers' activations of a non-ELU(1) call (K0 only), or nullptr; rk: the tableau of an _rk call (K0's tableau build, with
-// `act` always given), or nullptr; sub: the sub-steps of a _sub call (K0's sub-step build, with `act` and `rk` always given), or nullptr
+// `act` always given), or nullptr; sub: the sub-steps of a _sub call (K0's sub-step build, with `act` and `rk` always given), or nullptr;
+// lin: a _lin call (K0's linear-externals build, with all three given)
 int dispatch(IntegrateDev& d, bool dae, int kernel, const psnode_mlp_f32* de, const psnode_mlp_f32* ae, void* workspace,
              size_t workspace_bytes, hipStream_t stream, const ActPair* act = nullptr, const psnode_rk_tableau_f32* rk = nullptr,
-             const SubDev* sub = nullptr) {
+             const SubDev* sub = nullptr, bool lin = false) {
     if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 255u)) return PSNODE_ERR_WORKSPACE;
     if (workspace_bytes < psnode_workspace_bytes(de, ae)) return PSNODE_ERR_WORKSPACE;
     float* ws = static_cast<float*>(workspace);
@@ -112,9 +113,11 @@ int dispatch(IntegrateDev& d, bool dae, int kernel, const psnode_mlp_f32* de, co
     if (use_mfma) {
         e = launch_mfma(d, dae, ws, stream);
     } else {
-        if (generic_lds_bytes(d, dae) > 160 * 1024) return PSNODE_ERR_UNSUPPORTED;
+        if (generic_lds_bytes(d, dae, lin) > 160 * 1024) return PSNODE_ERR_UNSUPPORTED;
         e = launch_pack_image(d.de, dae ? &d.ae : nullptr, d.xd, d.xd + d.zd + (dae ? d.vd + d.id : 0), d.zd + (dae ? d.vd : 0), stream);
-        if (e == hipSuccess && sub)
+        if (e == hipSuccess && sub && lin)
+            e = launch_generic_lin(d, dae, *act, *rk, *sub, stream);
+        else if (e == hipSuccess && sub)
             e = launch_generic_sub(d, dae, *act, *rk, *sub, stream);
         else if (e == hipSuccess && rk)
             e = launch_generic_rk(d, dae, *act, *rk, stream);
@@ -548,6 +551,83 @@ int32_t psnode_dae_integrate_sub_f32(const psnode_dae_args_f32* args, const psno
     if (rc) return rc;
     const SubDev sd{sub->substeps, sub->x_sub};
     return dispatch(d, true, c.kernel, &c.de, &c.ae, workspace, workspace_bytes, static_cast<hipStream_t>(stream), &p, &t, &sd);
+}
+
+// ---- linearly interpolated externals (include/psnode_hip.h, "Linear interpolation of externals"): K0's linear-externals build alone, for
+// every substeps >= 1 (a NULL struct is one sub-step).  The struct is checked first, then the act, the tableau (NULL: the args' method as
+// one), the route; the _supported queries answer for this build's own LDS fit.
+int32_t psnode_ode_integrate_lin_supported(const psnode_ode_args_f32* a, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
+                                           const psnode_substeps_f32* sub) {
+    ActPair p;
+    bool elu1 = true;
+    psnode_rk_tableau_f32 t;
+    if (!a || (sub && substeps_check(sub)) || act_pair(de_act, nullptr, p, elu1) || sub_tableau(tab, a->method, t)) return 0;
+    if (!act_call_ok(a->kernel, a->save_act) || a->save_xstage || a->x_dim < 1 || a->z_dim < 0) return 0;
+    if (check_mlp_dims(a->de, 3 * (a->x_dim + a->z_dim), a->x_dim)) return 0;
+    IntegrateDev d = dims_only(*a);
+    d.maxo = max_out_width(a->de, nullptr);
+    return generic_lds_bytes(d, false, true) <= 160 * 1024;
+}
+
+int32_t psnode_ode_integrate_lin_f32(const psnode_ode_args_f32* args, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
+                                     const psnode_substeps_f32* sub, void* workspace, size_t workspace_bytes, void* stream) {
+    int rc = sub ? substeps_check(sub) : PSNODE_OK;
+    if (rc) return rc;
+    ActPair p;
+    bool elu1 = true;
+    rc = act_pair(de_act, nullptr, p, elu1);
+    if (rc) return rc;
+    if (!args) return PSNODE_ERR_NULL;
+    psnode_rk_tableau_f32 t;
+    rc = sub_tableau(tab, args->method, t);
+    if (rc) return rc;
+    if (!act_call_ok(args->kernel, args->save_act) || args->save_xstage) return PSNODE_ERR_UNSUPPORTED;      // K0 only
+    psnode_ode_args_f32 c = *args;
+    c.method = PSNODE_EULER;
+    IntegrateDev d;
+    rc = fill_ode(&c, d);
+    if (rc) return rc;
+    const SubDev sd{sub ? sub->substeps : 1, sub ? sub->x_sub : nullptr};
+    return dispatch(d, false, c.kernel, &c.de, nullptr, workspace, workspace_bytes, static_cast<hipStream_t>(stream), &p, &t, &sd, true);
+}
+
+int32_t psnode_dae_integrate_lin_supported(const psnode_dae_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                           const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub) {
+    ActPair p;
+    bool elu1 = true;
+    psnode_rk_tableau_f32 t;
+    if (!a || (sub && substeps_check(sub)) || act_pair(de_act, ae_act, p, elu1) || sub_tableau(tab, a->method, t)) return 0;
+    if (!act_call_ok(a->kernel, a->save_act) || a->save_xstage || a->save_ae_act || a->save_ev_act || a->save_ev_i) return 0;
+    if (a->x_dim < 1 || a->z_dim < 0 || a->v_dim < 0 || a->i_dim < 1) return 0;
+    const int n = a->x_dim + a->z_dim + a->v_dim + a->i_dim;
+    if (check_mlp_dims(a->de, 3 * n, a->x_dim) || check_mlp_dims(a->ae, n + a->x_dim + a->z_dim + a->v_dim, a->i_dim)) return 0;
+    IntegrateDev d = dims_only(*a);
+    d.maxo = max_out_width(a->de, &a->ae);
+    return generic_lds_bytes(d, true, true) <= 160 * 1024;
+}
+
+int32_t psnode_dae_integrate_lin_f32(const psnode_dae_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                     const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, void* workspace, size_t workspace_bytes,
+                                     void* stream) {
+    int rc = sub ? substeps_check(sub) : PSNODE_OK;
+    if (rc) return rc;
+    ActPair p;
+    bool elu1 = true;
+    rc = act_pair(de_act, ae_act, p, elu1);
+    if (rc) return rc;
+    if (!args) return PSNODE_ERR_NULL;
+    psnode_rk_tableau_f32 t;
+    rc = sub_tableau(tab, args->method, t);
+    if (rc) return rc;
+    if (!act_call_ok(args->kernel, args->save_act) || args->save_xstage || args->save_ae_act || args->save_ev_act || args->save_ev_i)
+        return PSNODE_ERR_UNSUPPORTED;
+    psnode_dae_args_f32 c = *args;
+    c.method = PSNODE_EULER;
+    IntegrateDev d;
+    rc = fill_dae(&c, d);
+    if (rc) return rc;
+    const SubDev sd{sub ? sub->substeps : 1, sub ? sub->x_sub : nullptr};
+    return dispatch(d, true, c.kernel, &c.de, &c.ae, workspace, workspace_bytes, static_cast<hipStream_t>(stream), &p, &t, &sd, true);
 }
 
 int32_t psnode_ode_kernel_for(const psnode_ode_args_f32* a) {

@@ -235,7 +235,7 @@ __host__ __device__ __forceinline__ constexpr float rk_b(int method, int s) {
 
 // psnode_generic.hip
 hipError_t launch_generic(const IntegrateDev& a, bool dae, hipStream_t stream);
-size_t generic_lds_bytes(const IntegrateDev& a, bool dae);
+size_t generic_lds_bytes(const IntegrateDev& a, bool dae, bool lin = false);      // lin: K0's linear-externals build (nzv more rows)
 hipError_t launch_pack_transpose(const MlpDev& de, const MlpDev* ae, hipStream_t stream);   // generic backward: transposed weights
 hipError_t launch_pack_image(const MlpDev& de, const MlpDev* ae, int xd, int n, int nzv, hipStream_t stream);   // generic forward: MFMA images
 size_t generic_image_floats(int K, int N);
@@ -324,16 +324,18 @@ struct GenericBwdCall {
     const psnode_rk_tableau_f32* rk;      // generic_backward_launch<BuildRk>: the tableau (checked: rk_tableau_check); `method` is then not read
     int substeps;              // generic_backward_launch<BuildSub> (with rk): sub-steps per grid interval, > 1, and the sub-states K0 wrote
     const float* x_sub;        // [T-1, substeps-1, B, xd]
+    bool lin;                  // generic_backward_launch<BuildLin> (with rk; substeps >= 1): z | v interpolated linearly inside every grid interval
 };
 struct ActPair;     // psnode_act.h: the DE's and the AE's activation of a non-ELU(1) call
 size_t generic_bwd_workspace_floats(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, long long B);
 // K5's mode for these dims, 0 if the shape does not fit: the one fit query of all four builds.  pre: the fit of the builds that keep u in LDS
 // as well -- the pre-activation build and the tableau build, whose LDS layouts are the same
-int generic_bwd_fits(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, int xd, int zd, int vd, int id, bool pre);
+int generic_bwd_fits(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, int xd, int zd, int vd, int id, bool pre, bool lin = false);      // lin: the linear-externals build's layout
 // K5's launcher (psnode_generic_bwd_impl.h), instantiated once per build policy (psnode_generic_build.h) in that policy's object: BuildElu1
 // (ignores `act`), BuildAct (the activations of psnode_act.h), BuildPre (those and the pre-activation family), BuildRk (the tableau build:
 // every activation kind -- `act` is required, ELU(1) runs as ELU with alpha = 1 -- and c.rk in place of c.method; it keeps the
-// pre-activations like the pre build), BuildSub (the tableau build with c.substeps sub-steps per grid interval, read from c.x_sub).
+// pre-activations like the pre build), BuildSub (the tableau build with c.substeps sub-steps per grid interval, read from c.x_sub), BuildLin
+// (the sub-step build, any c.substeps >= 1, with linearly interpolated externals: c.lin).
 // psnode_backward.hip: generic_backward picks among them.
 template <class B>
 int generic_backward_launch(const GenericBwdCall& c, const ActPair* act, float* workspace, hipStream_t stream);

@@ -1,6 +1,6 @@
-// The body of K0's kernel (psnode_generic_impl.h), as text: each of the five objects writes its own __global__ -- generic_kernel(a),
-// generic_act_kernel(a, act), generic_pre_act_kernel(a, act), generic_rk_kernel(a, act, rk), generic_sub_kernel(a, act, rk, sub) -- and
-// includes this file between its braces.
+// The body of K0's kernel (psnode_generic_impl.h), as text: each of the six objects writes its own __global__ -- generic_kernel(a),
+// generic_act_kernel(a, act), generic_pre_act_kernel(a, act), generic_rk_kernel(a, act, rk), generic_sub_kernel(a, act, rk, sub),
+// generic_lin_kernel(a, act, rk, sub) -- and includes this file between its braces.
 // Template parameters in scope: DAE, MODE, ML, QM.  Names in scope: a, act (ActPair; NoActPair in the ELU(1) object), rk (read under
 // Bd::rk only) and sub (SubDev, read under Bd::sub only); the objects without one declare an unread one.  The build policy Bd decides the
 // rest with `if constexpr`.
@@ -29,6 +29,7 @@
     float* icur = kbuf + 4 * xd * TB;  // [id][TB]
     float* zvn = icur + id * TB;       // [nzv][TB] dataset z | v of the NEXT grid point
     float* dts = zvn + nzv * TB;       // [TB]
+    [[maybe_unused]] float* wl = dts + TB;      // Bd::lin only: [nzv][TB] z | v at the interval's left end (the jumped values behind an event)
 
 #ifdef PSNODE_K0_PROF      // discriminator builds only: cycles per phase of workgroup 0, printed by its first thread
     long long prof[6] = {0, 0, 0, 0, 0, 0};
@@ -40,7 +41,7 @@
     Pref pf;
     pf.tag = nullptr;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    unsigned bias_at = (unsigned)(dts + TB - lds), img_at = bias_at + (unsigned)generic_bias_floats(a, DAE);
+    unsigned bias_at = (unsigned)(dts + TB - lds) + (Bd::lin ? (unsigned)(nzv * TB) : 0u), img_at = bias_at + (unsigned)generic_bias_floats(a, DAE);
     const Tab<ML> tde = make_tab<ML>(a.de, wv, a.k0_res & 0xffu, bias_at, img_at, de_k16(xd, n), SX >> 4);
     const Tab<ML> tae = DAE ? make_tab<ML>(a.ae, wv, (a.k0_res >> 8) & 0xffu, bias_at, img_at, ae_k16(xd, nzv, n), SA >> 4) : tde;
     load_resident(a.de, tde, lds);
@@ -139,6 +140,10 @@
     int evn_v = (a.ev && a.T > 1) ? __builtin_nontemporal_load(evp) : -1;
 
     float pz[PF];
+    // Linear externals (Bd::lin): stage s of sub-step j reads z | v at theta = (j + c_s) / nsub between the interval's left rows (wl) and the
+    // dataset's rows of grid point k + 1 (zvn, which the first stage pass of the interval fills from the look-ahead registers).  th_in: the
+    // theta of the rows the DE input holds; th_fd: the one the register forms' fold0 was taken at.  Both are wave-uniform.
+    [[maybe_unused]] float th_in = 0.0f, th_fd = 0.0f;
 
     // One MLP call site for every evaluation (the unrolled layer code exists once: it has to stay inside the instruction cache).  Slots of
     // step k: 0 = the AE head at an event (my_solvers.py:110), 1 .. S = the DE stages, S + 1 = the AE head at grid point k + 1
@@ -156,8 +161,10 @@
                 if (ev >= 0) { const long long b = gb(c); v = r < zd ? a.zj[b * a.zjb + ev * a.zje + r] : a.vj[b * a.vjb + ev * a.vje + (r - zd)]; }
                 else v = zvn[idx];
                 put_ext(r, c, v);
+                if constexpr (Bd::lin) wl[idx] = v;
                 if constexpr (DAE) if (ev >= 0) lds[inAE + qi(xd + r, c)] = v;      // the event's AE evaluation sees the jumped rows
             }
+            if constexpr (Bd::lin) th_in = 0.0f;
             for (int idx = tid; idx < nx; idx += NT) {
                 const int r = idx / TB, c = idx % TB;
                 const float v = true_x ? a.x.p[k * a.x.st + gb(c) * a.x.sb + r] : xcur[idx];
@@ -197,10 +204,12 @@
             int f;
             if constexpr (MODE == 0 || MODE == 3) {
                 // (sub-steps: the externals change inside an interval only where the DAE's own i does)
-                if (e == 1 && (si.first() || (DAE && !true_i))) {       // the step's externals are in place (behind an event's AE evaluation too): the DE's per-step constant
+                // (linear externals: and in front of every stage whose theta is not the one folded)
+                if ((e == 1 && (si.first() || (DAE && !true_i))) || (Bd::lin && !is_ae && th_in != th_fd)) {       // the step's externals are in place (behind an event's AE evaluation too): the DE's per-step constant
                     const int nt0 = tab_tiles(tde.dims[0]);
                     if (wv < nt0) cde = fold0<ML>(tde, lds, inDE, wv);
                     if (MODE == 3 && wv + 4 < nt0) cde2 = fold0<ML>(tde, lds, inDE, wv + 4);
+                    if constexpr (Bd::lin) th_fd = th_in;
                 }
             }
             if constexpr (MODE == 3) {
@@ -242,6 +251,29 @@
             c1 = s_ >= 1 ? rku(rrow[1]) : 0.0f;
             c2 = s_ >= 2 ? rku(rrow[2]) : 0.0f;
             c3 = s_ >= 3 ? rku(rrow[3]) : 0.0f;
+            }
+            if constexpr (Bd::lin) {
+                if (s_ == 0 && si.first()) {      // the right rows, behind the interval's first evaluation (the final pass rewrites the same values)
+#pragma unroll
+                    for (int j = 0; j < PF; ++j) {
+                        const int idx = tid + NT * j;
+                        if (idx < nzv * TB) zvn[idx] = pz[j];
+                    }
+                    for (int idx = tid + NT * PF; idx < nzv * TB; idx += NT) zvn[idx] = zv_at(k + 1, idx / TB, idx % TB);
+                }
+                if (!(final_stage && si.last())) {
+                    // the externals of the next stage, or of the next sub-step's first one (and of the head in front of it): c_{s + 1} is the
+                    // row sum just read, in increasing index
+                    const float th = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(((float)si.i + (final_stage ? 1.0f : (c0 + c1) + c2)) / (float)nsub)));
+                    for (int idx = tid; idx < nzv * TB; idx += NT) {      // (each thread reads back what it wrote itself)
+                        const int r = idx / TB, c = idx % TB;
+                        const float l_ = wl[idx];
+                        const float v = l_ + th * (zvn[idx] - l_);
+                        put_ext(r, c, v);
+                        if constexpr (DAE) if (final_stage) lds[inAE + qi(xd + r, c)] = v;
+                    }
+                    th_in = th;
+                }
             }
             for (int idx = tid; idx < nx; idx += NT) {
                 const int r = idx / TB, c = idx % TB;

@@ -29,7 +29,7 @@ size_t generic_bwd_workspace_floats(const psnode_mlp_f32* de, const psnode_mlp_f
 }
 
 // (the pre fields, which this object's GBwd does not have, are written by a launch only: the fit reads none of them)
-int generic_bwd_fits(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, int xd, int zd, int vd, int id, bool pre) {
+int generic_bwd_fits(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, int xd, int zd, int vd, int id, bool pre, bool lin) {
     GBwd a;
     memset(&a, 0, sizeof(a));
     a.dae = ae != nullptr; a.xd = xd; a.zd = zd; a.vd = vd; a.id = id;
@@ -43,7 +43,7 @@ int generic_bwd_fits(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, int xd,
     }
     a.act_rows = rows;
     a.de_reg = de_reg_class(*de) ? 1 : 0;
-    return gbwd_mode(a, pre);
+    return gbwd_mode(a, pre, lin);
 }
 
 }  // namespace psnode

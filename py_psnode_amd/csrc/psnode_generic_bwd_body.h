@@ -1,6 +1,7 @@
-// The body of K5's kernel (psnode_generic_bwd_impl.h), as text: each of the five objects writes its own __global__ --
+// The body of K5's kernel (psnode_generic_bwd_impl.h), as text: each of the six objects writes its own __global__ --
 // generic_backward_kernel(a), generic_backward_act_kernel(a, act), generic_backward_pre_act_kernel(a, act),
-// generic_backward_rk_kernel(a, act, rk), generic_backward_sub_kernel(a, act, rk, sub) -- and includes this file between its braces.
+// generic_backward_rk_kernel(a, act, rk), generic_backward_sub_kernel(a, act, rk, sub), generic_backward_lin_kernel(a, act, rk, sub) -- and
+// includes this file between its braces.
 // Template parameters in scope: gg, REG, ggA, STR.  Names in scope: a, act (ActPair; NoActPair in the ELU(1) object), rk (read under
 // Bd::rk only) and sub (SubDev, read under Bd::sub only); the objects without one declare an unread one.
     constexpr bool DE_TM = REG || STR == 2;      // the DE's LDS accumulators are tile-major
@@ -37,7 +38,12 @@
     float* gxc = gx0 + nx;                        // [xd][TP]  carried dL/dx_{k+1}
     float* gic = gxc + nx;                        // [id][TP]  carried dL/di_{k+1}
     float* dts = gic + id * TP;                   // [TP]
-    float* wbuf = dts + TP;                       // [kWBuf] staged weights
+    // Linear externals (Bd::lin): the interval's left z | v rows (the jumped values behind an event), the dataset's rows of grid point k + 1,
+    // and the adjoint of those right rows -- gext's z | v rows are the left one.  ext's z | v rows are rewritten per stage from the first two.
+    [[maybe_unused]] float* wl = dts + TP;                        // [nzv][TP]
+    [[maybe_unused]] float* wr = wl + nzv * TP;                   // [nzv][TP]
+    [[maybe_unused]] float* gexr = wr + nzv * TP;                 // [nzv][TP]
+    float* wbuf = dts + TP + (Bd::lin ? 3 * nzv * TP : 0);        // [kWBuf] staged weights
     // [np_de + np_ae]: in LDS when it fits, else this workgroup's partial slice in global memory (each element is owned by
     // one thread either way, so the read-modify-write needs no atomics)
     float* gacc_g = a.wpart + (size_t)blockIdx.x * (a.de.np + (a.dae ? a.ae.np : 0));      // (used when gg)
@@ -118,6 +124,7 @@
     // VJP of the AE head at (xrows; z|v of grid point jzv or the jumped ext rows) with output gradient `gi`:
     // adds to gx_dst, ga0s, and to the z|v gradients (global gz/gv at jzv, or the jump gradients of event ev; sub-step build, ev == -2: the
     // z | v rows of gext, which collect an interval's sub-steps)
+    [[maybe_unused]] float th_head = 0.0f;      // Bd::lin: theta of the in-interval head whose VJP runs (ev == -2)
     auto ae_vjp = [&](const float* xrows, long long jzv, int ev, const float* gi, float* gx_dst) {
         ae_input(xrows, jzv);
         if constexpr (STR >= 1) g_forward_str(a.ae, a.fimgA, acts, qb, qoA, ActCtx{act.ae, upre}); else g_forward(a.ae, acts, wbuf, ActCtx{act.ae, upre});
@@ -133,7 +140,11 @@
             const bool isz = r < zd;
             const int d_ = isz ? r : r - zd, w_ = isz ? zd : vd;
             if constexpr (Bd::sub) {
-                if (ev == -2) { gext[r * TP + c] += g; continue; }
+                if (ev == -2) {
+                    if constexpr (Bd::lin) { gext[r * TP + c] += (1.0f - th_head) * g; gexr[r * TP + c] += th_head * g; }
+                    else gext[r * TP + c] += g;
+                    continue;
+                }
             }
             if (jzv >= 0) {
                 float* dst = isz ? a.gz : a.gv;
@@ -192,6 +203,13 @@
             else v = ev >= 0 ? a.vj[b * a.vjb + ev * a.vje + (r - zd)] : a.v.p[k * a.v.st + b * a.v.sb + (r - zd)];
             ext[r * TP + c] = v;
         }
+        if constexpr (Bd::lin) {      // (each thread copies the ext values it wrote itself; the right rows are the dataset's, never jumped)
+            TILE_LOOP(nzv) {
+                const long long b = gb(c);
+                wl[r * TP + c] = ext[r * TP + c];
+                wr[r * TP + c] = r < zd ? a.z.p[(k + 1) * a.z.st + b * a.z.sb + r] : a.v.p[(k + 1) * a.v.st + b * a.v.sb + (r - zd)];
+            }
+        }
         if (tid < TB) la_tn = la_t;
         if (k > 0) look_ahead(k - 1);
         __syncthreads();
@@ -201,6 +219,16 @@
         SubIter<Bd::sub> si(nsub);
         do {
         const bool inner = !si.last();
+        // Bd::lin: theta of stage s of this sub-step, (js + c_s) / nsub with c_s the tableau's row sum in increasing index (wave-uniform), and
+        // the z | v rows of ext at it -- the expression K0's stage pass evaluates
+        [[maybe_unused]] auto theta = [&](int s) -> float {
+            float cs = 0.0f;
+            for (int j = 0; j < s; ++j) cs += coef_a(a.method, ks, nx, s, j);
+            return rk_u(((float)(nsub - 1 - si.i) + cs) / (float)nsub);
+        };
+        [[maybe_unused]] auto lin_ext = [&](float th) {      // (no barrier of its own)
+            TILE_LOOP(nzv) { const float l_ = wl[r * TP + c]; ext[r * TP + c] = l_ + th * (wr[r * TP + c] - l_); }
+        };
         if constexpr (Bd::sub) {
             if (nsub > 1) {      // (defensive: the host never launches this build with one sub-step -- substeps == 1 takes the other entry points)
                 const int js = nsub - 1 - si.i;
@@ -214,6 +242,7 @@
                     }
                     for (int idx = tid + NT * LA; idx < xd * TB; idx += NT) x0[(idx / TB) * TP + idx % TB] = xsrc[(k * a.B + gb(idx % TB)) * xd + idx / TB];
                 }
+                if constexpr (Bd::lin) lin_ext(theta(0));      // what the head in front of this sub-step (or the event's) saw
                 __syncthreads();
             }
         }
@@ -254,6 +283,7 @@
                 }
                 xst[s * nx + r * TP + c] = s == 0 ? x0[r * TP + c] : x0[r * TP + c] + dts[c] * acc;
             }
+            if constexpr (Bd::lin) lin_ext(theta(s));      // (behind the loop ext holds the last stage's rows, (3b)'s first)
             __syncthreads();
             if (s + 1 < S) {               // (the last stage's slope feeds no stage input: its evaluation is (3b)'s first, not done here)
                 de_input(xst + s * nx);
@@ -271,6 +301,7 @@
             gx0[r * TP + c] = g1;
             for (int s = 0; s < S; ++s) gks[s * nx + r * TP + c] = dts[c] * coef_b(a.method, ks, nx, s) * g1;
         }
+        if constexpr (Bd::lin) { if (si.first()) { TILE_LOOP(nzv) gexr[r * TP + c] = 0.0f; } }
         if constexpr (Bd::sub) { TILE_LOOP(ne) if (r >= nzv || si.first()) gext[r * TP + c] = 0.0f; }
         else { TILE_LOOP(ne) gext[r * TP + c] = 0.0f; }
         __syncthreads();
@@ -284,6 +315,8 @@
             const float* gu = REG ? g_vjp_reg<gg>(a, acts, dA, dB, gacc_l, tmg, qb, qo, rbw, ActCtx{act.de, upre})
                                   : (STR == 2 ? g_vjp_str<gg>(a.de, a.timg, acts, dA, dB, gacc_l, tmg, qb, qo, ActCtx{act.de, upre})
                                               : g_vjp<gg>(a.de, acts, dA, dB, gacc_l, gacc_g, wbuf, ActCtx{act.de, upre}));
+            [[maybe_unused]] float th_s = 0.0f;
+            if constexpr (Bd::lin) th_s = theta(s);
             TILE_LOOP(n) {
                 const float gs = gu[(n + r) * TP + c] + gu[(2 * n + r) * TP + c];
                 ga0s[r * TP + c] += gu[r * TP + c] - gu[(n + r) * TP + c];
@@ -294,13 +327,24 @@
                         else gks[j * nx + r * TP + c] += dts[c] * coef_a(a.method, ks, nx, s, j) * gs;
                     }
                 } else {
-                    gext[(r - xd) * TP + c] += gs;
+                    if constexpr (Bd::lin) {
+                        if (r - xd < nzv) {      // w = w_L + theta (w_R - w_L): the stage's external adjoint goes to both ends
+                            gext[(r - xd) * TP + c] += (1.0f - th_s) * gs;
+                            gexr[(r - xd) * TP + c] += th_s * gs;
+                        } else {
+                            gext[(r - xd) * TP + c] += gs;
+                        }
+                    } else {
+                        gext[(r - xd) * TP + c] += gs;
+                    }
                 }
             }
+            if constexpr (Bd::lin) { if (s > 0) lin_ext(theta(s - 1)); }      // (ext was copied into the DE input before the VJP)
             __syncthreads();
         }
         if constexpr (Bd::sub) {
             if (inner) {      // the head that fed this sub-step's DE: into its start state's adjoint, ga0s and the interval's z | v
+                if constexpr (Bd::lin) th_head = theta(0);
                 if (dae && !ti) ae_vjp(x0, -1, -2, gext + nzv * TP, gx0);
                 TILE_LOOP(xd) gxc[r * TP + c] = gx0[r * TP + c];
                 __syncthreads();
@@ -324,6 +368,9 @@
             } else if (dst) {
                 dst[(k * a.B + b0 + c) * w_ + d_] = g;
             }
+            // the right sums: into row k + 1, which this thread wrote one interval earlier (the last row: zeroed up front) and to which it
+            // alone has added since (the head VJP at grid point k + 1)
+            if constexpr (Bd::lin) { if (dst) dst[((k + 1) * a.B + b0 + c) * w_ + d_] += gexr[r * TP + c]; }
         }
         if (dae) {
             __syncthreads();

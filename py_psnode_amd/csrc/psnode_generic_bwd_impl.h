@@ -15,7 +15,7 @@
 // Teacher forcing (GBwd::flags) changes the outer sweep only: which rows a step starts from and which adjoints travel to the step before.
 #include <string.h>
 
-// Five objects are compiled from this header, one per build policy (psnode_generic_build.h).  Each of psnode_generic_bwd{,_act,_pre,_rk,_sub}.hip
+// Six objects are compiled from this header, one per build policy (psnode_generic_build.h).  Each of psnode_generic_bwd{,_act,_pre,_rk,_sub,_lin}.hip
 // names its policy `Bd` in front of the include, writes its kernel around psnode_generic_bwd_body.h and instantiates the launcher:
 //   BuildElu1  generic_backward_kernel(a)                    ELU(1) and its derivative
 //   BuildAct   generic_backward_act_kernel(a, act)           the DE's and the AE's activation as a second kernel argument (ActPair)
@@ -26,6 +26,8 @@
 //              from a launch-uniform psnode_rk_tableau_f32 instead of rk_stages / rk_a / rk_b of a.method, which it does not read
 //   BuildSub   generic_backward_sub_kernel(a, act, rk, sub)  the tableau build with SubDev::n sub-steps per grid interval: an inner reverse loop
 //              around (2) .. (3b) of the kernel body that starts each sub-step from the state K0 stored in SubDev::x_sub; no LDS of its own
+//   BuildLin   generic_backward_lin_kernel(a, act, rk, sub)  the sub-step build (every n >= 1) with z | v interpolated linearly per stage: ext's
+//              z | v rows are refilled per stage from the interval's two ends, a second accumulator takes the right end's adjoint; 3 nzv rows of LDS
 // The policy decides in the language: the kernel-argument structs (GMlpT / GBwdT: the pre fields are a base that is empty elsewhere), the
 // activation context ActCtx every device function takes, the stage coefficients (coef_a, coef_b) and
 // `if constexpr` in the kernel body and the launcher.  The host's fit and layout functions take `pre` at run time.
@@ -654,7 +656,7 @@ __device__ __forceinline__ float* g_vjp_str(const GMlp& m, const float* const* t
 // head streamed, 2 = both MLPs streamed (0: whatever is not on the register path stages its weights through LDS).
 // (waves per SIMD, Bd::two_waves: the fully streamed instances that fitted 256 registers -- two workgroups per CU where their LDS allows
 //  it -- keep that budget: the sweep-level flag values must not cost them the second workgroup)
-// (the five kernels: psnode_generic_bwd{,_act,_pre,_rk,_sub}.hip around psnode_generic_bwd_body.h)
+// (the six kernels: psnode_generic_bwd{,_act,_pre,_rk,_sub,_lin}.hip around psnode_generic_bwd_body.h)
 template <class B> struct GenericBwdKernels;      // the kernels of policy B, by their template arguments: specialised by the object that defines them
 
 int fill_gmlp(const psnode_mlp_f32& m, GMlp& g, float*& ws) {
@@ -703,8 +705,9 @@ template <bool PRE> void place_u_region(GBwdT<PRE>& a, size_t lds_floats, size_t
     }
 }
 
-// pre (here and below): count the u region, as the builds that keep the pre-activations lay LDS out (Bd::pre at a launch)
-size_t gbwd_lds_floats(const GBwd& a, bool pre) {
+// pre (here and below): count the u region, as the builds that keep the pre-activations lay LDS out (Bd::pre at a launch); lin: count the
+// linear-externals build's three z | v regions (both ends of the interval, the right end's adjoint)
+size_t gbwd_lds_floats(const GBwd& a, bool pre, bool lin = false) {
     const int vd = a.dae ? a.vd : 0, id = a.dae ? a.id : 0, ne = a.zd + vd + id, n = a.xd + ne;
     const bool de_tm = a.de_reg || a.str == 2, ae_tm = a.str >= 1;
     const size_t de_acc = a.gacc_global == 1 ? 0 : (size_t)(de_tm ? tm_total(a.de) : a.de.np);
@@ -714,7 +717,7 @@ size_t gbwd_lds_floats(const GBwd& a, bool pre) {
     if (de_tm) q = (size_t)q_offsets(a.de).total;
     if (a.dae && ae_tm && (size_t)q_offsets(a.ae).total > q) q = (size_t)q_offsets(a.ae).total;
     return (size_t)a.act_rows * TP + 2 * (size_t)a.maxw * TP + 2 * (size_t)n * TP + 2 * (size_t)ne * TP + (size_t)a.xd * TP * (1 + 12 + 2) +
-           (size_t)id * TP + TP + (stages ? kWBuf : 0) + ((np_all + 3) & ~(size_t)3) + q + (pre ? pre_floats(a) : 0);
+           (size_t)id * TP + TP + (lin ? 3 * (size_t)(a.zd + vd) * TP : 0) + (stages ? kWBuf : 0) + ((np_all + 3) & ~(size_t)3) + q + (pre ? pre_floats(a) : 0);
 }
 // the DE's shape class of the register path
 bool de_reg_class(const psnode_mlp_f32& de) {
@@ -745,7 +748,7 @@ size_t reg_image_floats(const psnode_mlp_f32& de) {       // plain + transposed 
 }
 // 1: everything in LDS; 2: only with the parameter-gradient accumulators in global memory; 0: does not fit.  a.de_reg (the DE's class
 // allows the register path) is kept when its quad-row buffers fit next to the LDS accumulators, else dropped.
-int gbwd_mode(GBwd& a, bool pre) {
+int gbwd_mode(GBwd& a, bool pre, bool lin = false) {
     const int want_reg = a.de_reg;
     // paths in order of preference: register DE (+ streamed AE head), everything streamed, then the staged paths; for each, the accumulators
     // in LDS, the AE's in the global slice, both there
@@ -755,13 +758,13 @@ int gbwd_mode(GBwd& a, bool pre) {
         if (c == 2 && (!want_reg || !a.dae)) continue;
         a.de_reg = cand[c][0]; a.str = cand[c][1];
         a.gacc_global = 0;
-        if (gbwd_lds_floats(a, pre) * sizeof(float) <= 160 * 1024) return 1;
+        if (gbwd_lds_floats(a, pre, lin) * sizeof(float) <= 160 * 1024) return 1;
         if (a.dae && (a.de_reg || a.str == 2)) {
             a.gacc_global = 2;
-            if (gbwd_lds_floats(a, pre) * sizeof(float) <= 160 * 1024) return 2;
+            if (gbwd_lds_floats(a, pre, lin) * sizeof(float) <= 160 * 1024) return 2;
         }
         a.gacc_global = 1;
-        if (gbwd_lds_floats(a, pre) * sizeof(float) <= 160 * 1024) return 2;
+        if (gbwd_lds_floats(a, pre, lin) * sizeof(float) <= 160 * 1024) return 2;
     }
     return 0;
 }
@@ -834,9 +837,9 @@ int generic_backward_launch(const GenericBwdCall& c, const ActPair* act, float* 
         float* tm = ws + nwg_ * (size_t)(a.de.np + (dae ? a.ae.np : 0));
         a.tmpart = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(tm) + 255) & ~(uintptr_t)255);
     }
-    if (!gbwd_mode(a, Pol::pre)) return PSNODE_ERR_UNSUPPORTED;
-    const size_t lds = gbwd_lds_floats(a, Pol::pre) * sizeof(float);
-    place_u_region<Pol::pre>(a, gbwd_lds_floats(a, Pol::pre), pre_floats(a));
+    if (!gbwd_mode(a, Pol::pre, Pol::lin)) return PSNODE_ERR_UNSUPPORTED;
+    const size_t lds = gbwd_lds_floats(a, Pol::pre, Pol::lin) * sizeof(float);
+    place_u_region<Pol::pre>(a, gbwd_lds_floats(a, Pol::pre, Pol::lin), pre_floats(a));
     // transposed weights for the forward recomputation
     MlpDev mde, mae;
     memset(&mde, 0, sizeof(mde));

@@ -25,7 +25,7 @@
 // Padded columns: the image holds zeros there and the input builders write zeros into the pad columns of the first layer's input; a
 // hidden layer's pad units come out of the MFMA as ELU(0 + 0) = 0.
 //
-// Five objects are compiled from this header, one per build policy (psnode_generic_build.h).  Each of psnode_generic{,_act,_pre,_rk,_sub}.hip
+// Six objects are compiled from this header, one per build policy (psnode_generic_build.h).  Each of psnode_generic{,_act,_pre,_rk,_sub,_lin}.hip
 // names its policy `Bd` in front of the include, writes its kernel around psnode_generic_body.h and its exported launcher over
 // launch_generic_build:
 //   BuildElu1  generic_kernel(a), launch_generic                    ELU(1)
@@ -35,6 +35,8 @@
 //              (psnode_rk_tableau_f32) applied in the stage pass instead of the three built-in formulas; a.method is not read
 //   BuildSub   generic_sub_kernel(a, act, rk, sub), launch_generic_sub   the tableau build with SubDev::n sub-steps per grid interval: the
 //              evaluation loop of a step runs n times on h / n, outputs and look-ahead rows advance behind the last one; no LDS of its own
+//   BuildLin   generic_lin_kernel(a, act, rk, sub), launch_generic_lin   the sub-step build (every n >= 1) with z | v interpolated linearly per
+//              stage between the interval's left rows and the next grid point's; nzv * TB floats of LDS of its own (generic_lds_bytes(.., lin))
 // The device functions take the activation as one ordinary parameter, ActCtx; the kernel body chooses the tableau code with
 // `if constexpr (Bd::rk)`, the sub-step code with `if constexpr (Bd::sub)`.  The host's plan / fit / pack code is compiled once, in
 // psnode_generic.hip.
@@ -607,7 +609,7 @@ template <class B> struct GenericKernels;
 template <class B, class... Extra>
 hipError_t launch_generic_build(const IntegrateDev& a_in, bool dae, hipStream_t stream_, const Extra&... extra) {
     IntegrateDev a = a_in;
-    const size_t lds = generic_plan(a, dae, a.k0_res);
+    const size_t lds = generic_plan(a, dae, a.k0_res, B::lin);
     const unsigned grid = (unsigned)((a.B + TB - 1) / TB);
     unsigned all = (1u << a.de.n_layers) - 1u;
     if (dae) all |= ((1u << a.ae.n_layers) - 1u) << 8;

@@ -102,24 +102,53 @@ def no_substeps(substeps: int, what: str):
                                          "(kernel 'auto' / 'generic', no saved rows); this entry point takes one step per interval")
 
 
-def substeps_abi(substeps: int, x_sub=None):
+EXTERNALS = ("hold", "linear")      # z | v inside a grid interval: the left grid point's rows held (the reference), or interpolated to the right one's
+
+
+def is_linear(externals: str) -> bool:
+    """True for externals="linear", False for "hold"; ValueError for anything else."""
+    if externals not in EXTERNALS:
+        raise ValueError(f"externals must be one of {EXTERNALS}, got {externals!r}")
+    return externals == "linear"
+
+
+def no_linear(externals: str, what: str):
+    """The specialised, latent, encoded and saved-row entries hold the external inputs over a step: interpolated ones are refused like
+    sub-steps."""
+    if is_linear(externals):
+        raise _lib.UnsupportedShapeError(f"{what}: linearly interpolated external inputs (externals='linear') run on the generic kernels "
+                                         "K0 / K5 only (kernel 'auto' / 'generic', no saved rows); this entry point holds them over a step")
+
+
+def substeps_abi(substeps: int, x_sub=None, externals: str = "hold"):
     """The psnode_substeps_f32 of a call of the generic route with substeps > 1 (x_sub: the sub-state rows, or None), None for substeps == 1
-    -- the call then takes the entry point it takes without sub-steps.  ValueError unless an int in 1..1024."""
+    -- the call then takes the entry point it takes without sub-steps.  ValueError unless an int in 1..1024.
+    externals="linear": a struct for every substeps >= 1, marked `.lin` -- `call_entry` / `entry_supported` then take the _lin entry points."""
     if isinstance(substeps, bool) or not isinstance(substeps, int) or not 1 <= substeps <= _lib.MAX_SUBSTEPS:
         raise ValueError(f"substeps must be an int in 1..{_lib.MAX_SUBSTEPS}, got {substeps!r}")
-    if substeps == 1:
+    lin = is_linear(externals)
+    if substeps == 1 and not lin:
         return None
     s = _lib.SubstepsF32()
+    s.lin = lin
     s.substeps = substeps
     s.x_sub = x_sub.data_ptr() if x_sub is not None and x_sub.numel() else None
     return s
 
 
-def sub_route_ok(what: str, substeps: int, kernel: str, save: bool):
-    """Sub-steps run on the generic kernels only."""
+def sub_route_ok(what: str, substeps: int, kernel: str, save: bool, externals: str = "hold"):
+    """Sub-steps and linearly interpolated externals run on the generic kernels only."""
     if substeps != 1 and (kernel not in ("auto", "generic") or save):
         raise _lib.UnsupportedShapeError(f"{what}: sub-steps per grid interval (substeps={substeps}) run on the generic kernels K0 / K5 only "
                                          f"(kernel 'auto' / 'generic', no saved rows); got kernel={kernel!r}, saved rows={save}")
+    if is_linear(externals) and (kernel not in ("auto", "generic") or save):
+        raise _lib.UnsupportedShapeError(f"{what}: linearly interpolated external inputs (externals='linear') run on the generic kernels K0 / K5 "
+                                         f"only (kernel 'auto' / 'generic', no saved rows); got kernel={kernel!r}, saved rows={save}")
+
+
+def sub_family(sub) -> str:
+    """"lin" or "sub": the entry-point family of a `substeps_abi` struct."""
+    return "lin" if getattr(sub, "lin", False) else "sub"
 
 
 KERNEL_ID = {"auto": _lib.KERNEL_AUTO, "generic": _lib.KERNEL_GENERIC, "mfma": _lib.KERNEL_MFMA, "wide": _lib.KERNEL_MFMA_WIDE,
@@ -207,10 +236,10 @@ def call_entry(lib, stem: str, args, acts, wp, wn, stream, tab=None, sub=None) -
     psnode_<stem>_act_f32 with the acts' psnode_act_f32 otherwise.  stem: "ode_integrate", "dae_integrate", "ode_backward", "dae_backward".
     tab (a Tableau): psnode_<stem>_rk_f32 with the acts and the tableau ("dae_backward": args is then a DaeBwdTfArgsF32).
     sub (`substeps_abi`, not None: substeps > 1): psnode_<stem>_sub_f32 with the acts, the tableau or NULL (= the args' method) and the
-    struct ("dae_backward": a DaeBwdTfArgsF32)."""
+    struct ("dae_backward": a DaeBwdTfArgsF32); a struct marked `.lin` (externals="linear"): psnode_<stem>_lin_f32 with the same arguments."""
     refs, non_elu = _act_refs(*acts)
     if sub is not None:
-        return getattr(lib, f"psnode_{stem}_sub_f32")(ctypes.byref(args), *refs, ctypes.byref(tab.abi()) if tab is not None else None,
+        return getattr(lib, f"psnode_{stem}_{sub_family(sub)}_f32")(ctypes.byref(args), *refs, ctypes.byref(tab.abi()) if tab is not None else None,
                                                       ctypes.byref(sub), wp, wn, stream)
     if tab is not None:
         return getattr(lib, f"psnode_{stem}_rk_f32")(ctypes.byref(args), *refs, ctypes.byref(tab.abi()), wp, wn, stream)
@@ -224,7 +253,7 @@ def entry_supported(lib, stem: str, args, acts, tab=None, sub=None) -> bool:
     psnode_<stem>_sub_supported for sub-steps (`call_entry`'s query)."""
     refs, non_elu = _act_refs(*acts)
     if sub is not None:
-        return bool(getattr(lib, f"psnode_{stem}_sub_supported")(ctypes.byref(args), *refs, ctypes.byref(tab.abi()) if tab is not None else None,
+        return bool(getattr(lib, f"psnode_{stem}_{sub_family(sub)}_supported")(ctypes.byref(args), *refs, ctypes.byref(tab.abi()) if tab is not None else None,
                                                                  ctypes.byref(sub)))
     if tab is not None:
         return bool(getattr(lib, f"psnode_{stem}_rk_supported")(ctypes.byref(args), *refs, ctypes.byref(tab.abi())))

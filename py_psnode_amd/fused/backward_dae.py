@@ -6,19 +6,20 @@ import ctypes
 import torch
 
 from .. import _lib
-from ._common import (KERNEL_ID, Layers, builtin_method, method_info, _aligned16, _aligned_ptr, _bind_jumps, _check_saved, _empty, _f32_dev, _mlp, _pad_rows, _padded_hidden, _split_grads, _view, call_entry, dae_acts, entry_supported, no_substeps, sub_route_ok, substeps_abi)
+from ._common import (KERNEL_ID, Layers, builtin_method, method_info, _aligned16, _aligned_ptr, _bind_jumps, _check_saved, _empty, _f32_dev, _mlp, _pad_rows, _padded_hidden, _split_grads, _view, call_entry, dae_acts, entry_supported, is_linear, no_linear, no_substeps, sub_family, sub_route_ok, substeps_abi)
 from .latent import latent_backward_wide, latent_wide_shape
 
 def dae_backward_supported(method, de_layers: Layers, ae_layers: Layers, x_dim, z_dim, v_dim, i_dim, act=None, kernel: str = "auto",
-                           substeps: int = 1) -> bool:
+                           substeps: int = 1, externals: str = "hold") -> bool:
     """act: None (both MLPs ELU(1)) or (de_act, ae_act); an activation other than ELU(1) is K5's alone.  kernel="generic": does K5 take
     the shape (the question a teacher-forced call outside K7f's class asks).  method a fused.Tableau: K5's tableau build only (kernel
-    "auto" / "generic"; it answers for its own LDS fit).  substeps > 1: K5's sub-step build only, under the same rules."""
+    "auto" / "generic"; it answers for its own LDS fit).  substeps > 1: K5's sub-step build only, under the same rules.
+    externals="linear": K5's linear-externals build only (every substeps >= 1; it answers for its own LDS fit)."""
     if de_layers[0][0].device.type != "cuda" or max(len(de_layers), len(ae_layers)) > _lib.MAX_LAYERS:
         return False
     acts = dae_acts(act)
     tab = method_info(method)[2]
-    sub = substeps_abi(substeps)
+    sub = substeps_abi(substeps, None, externals)
     if tab is not None or sub is not None:
         tf = _lib.DaeBwdTfArgsF32()
         b = tf.base
@@ -43,10 +44,12 @@ def dae_backward_supported(method, de_layers: Layers, ae_layers: Layers, x_dim, 
     return dae_backward_wide_supported(method, de_layers, ae_layers, x_dim, z_dim, v_dim, i_dim)      # K7f: the DAE_01 class at hidden <= 128
 
 
-def dae_backward_wide_supported(method: str, de_layers: Layers, ae_layers: Layers, x_dim, z_dim, v_dim, i_dim, substeps: int = 1) -> bool:
+def dae_backward_wide_supported(method: str, de_layers: Layers, ae_layers: Layers, x_dim, z_dim, v_dim, i_dim, substeps: int = 1,
+                                externals: str = "hold") -> bool:
     """Shapes of K7f (psnode_dae_backward_wide_f32): DE 3n -> h -> h -> h -> x and AE n+x+z+v -> h -> h -> h -> i with h <= 128,
     x <= 8, z+v+i <= 8."""
     no_substeps(substeps, "dae_backward_wide_supported")
+    no_linear(externals, "dae_backward_wide_supported")
     if de_layers[0][0].device.type != "cuda" or len(de_layers) != 4 or len(ae_layers) != 4:
         return False
     lib = _lib.load()
@@ -58,7 +61,7 @@ def dae_backward_wide_supported(method: str, de_layers: Layers, ae_layers: Layer
 
 
 def dae_backward_wide(method: str, de_layers: Layers, ae_layers: Layers, t, z, v, all_initial, xs, is_, grad_xs, grad_is, event_idx=None,
-                      z_jump=None, v_jump=None, saved=None, x_true=None, i_true=None, substeps: int = 1):
+                      z_jump=None, v_jump=None, saved=None, x_true=None, i_true=None, substeps: int = 1, externals: str = "hold"):
     """Backward of `dae_integrate` at hidden <= 128 (the DAE_01 shape class): K7f (psnode_dae_backward_wide_f32) -- ONE launch over the
     whole grid that sweeps the adjoint through the DE stages, the AE head per grid point and the event-time recomputes and forms the DE's
     parameter gradients and the DE's share of the input gradients in the kernel.  With saved activations at hidden <= 64 the head's
@@ -69,6 +72,7 @@ def dae_backward_wide(method: str, de_layers: Layers, ae_layers: Layers, t, z, v
     BATCH slices (trajectories are independent: parameter gradients add, per-trajectory gradients concatenate).
     Same return value as `dae_backward`."""
     no_substeps(substeps, "dae_backward_wide")
+    no_linear(externals, "dae_backward_wide")
     lib = _lib.load()
     dev = xs.device
     T, B, xd = xs.shape
@@ -308,7 +312,7 @@ def _dae_backward_wide_sliced(step, method, de_layers, ae_layers, t, z, v, all_i
 
 
 def dae_backward(method, de_layers: Layers, ae_layers: Layers, t, z, v, all_initial, xs, is_, grad_xs, grad_is, event_idx=None,
-                 z_jump=None, v_jump=None, kernel: str = "auto", saved=None, act=None, substeps: int = 1, x_sub=None):
+                 z_jump=None, v_jump=None, kernel: str = "auto", saved=None, act=None, substeps: int = 1, x_sub=None, externals: str = "hold"):
     """Backward pass of `dae_integrate` (no teacher forcing): the one-launch K7f (`dae_backward_wide`) for the DAE_01 shape class at
     hidden <= 128, K9 / K8 / K9w for the latent shapes of the direct_encode models, else the generic backward kernel (K5);
     `kernel` = "auto" | "mfma" | "generic" | "wide" (K7f or an error).
@@ -316,6 +320,7 @@ def dae_backward(method, de_layers: Layers, ae_layers: Layers, t, z, v, all_init
     act: None (both MLPs ELU(1)) or (de_act, ae_act); an activation other than ELU(1) runs on K5 only (kernel "auto" / "generic").
     method: "euler" | "midpoint" | "rk4", or a fused.Tableau -- K5 only (kernel "auto" / "generic", no saved rows).
     substeps > 1: backward of `dae_integrate(..., substeps=, save_sub=True)` with the x_sub it returned -- K5 only, the same rules.
+    externals="linear": backward of `dae_integrate(..., externals="linear")` -- K5's linear-externals build only, the same rules.
     Returns dict(x_init, z, v, z_jump, v_jump, all_initial, de=[...], ae=[...]) of gradients."""
     T, B, xd = xs.shape
     zd, vd, idim = z.shape[-1], v.shape[-1], is_.shape[-1]
@@ -326,13 +331,13 @@ def dae_backward(method, de_layers: Layers, ae_layers: Layers, t, z, v, all_init
                                              "(kernel 'auto' / 'generic', no saved rows)")
         kernel = "generic"
     tab = method_info(method)[2]
-    sub_route_ok("dae_backward", substeps, kernel, saved is not None)
-    if tab is not None or substeps > 1:
+    sub_route_ok("dae_backward", substeps, kernel, saved is not None, externals)
+    if tab is not None or substeps > 1 or is_linear(externals):
         if tab is not None and (kernel not in ("auto", "generic") or saved is not None):
             raise _lib.UnsupportedShapeError(f"dae_backward: a Runge-Kutta tableau ({tab.name}) runs on the generic backward K5 only "
                                              "(kernel 'auto' / 'generic', no saved rows)")
         return _dae_backward_entry(method, de_layers, ae_layers, t, z, v, all_initial, xs, is_, grad_xs, grad_is, event_idx, z_jump, v_jump,
-                                   kernel, None, acts, substeps=substeps, x_sub=x_sub)
+                                   kernel, None, acts, substeps=substeps, x_sub=x_sub, externals=externals)
     if kernel in ("wide", "mfma") and T < 2 and len(de_layers) == 4:
         kernel = "generic"       # no step to sweep: K7f has no head-only form, K5 handles the single grid point
     if saved is not None and latent_wide_shape(de_layers, ae_layers, xd, zd, vd, idim):
@@ -347,7 +352,8 @@ def dae_backward(method, de_layers: Layers, ae_layers: Layers, t, z, v, all_init
 
 
 def dae_backward_tf(method, de_layers: Layers, ae_layers: Layers, t, z, v, all_initial, xs, is_, grad_xs, grad_is, event_idx=None,
-                    z_jump=None, v_jump=None, kernel: str = "auto", x_true=None, i_true=None, substeps: int = 1, x_sub=None):
+                    z_jump=None, v_jump=None, kernel: str = "auto", x_true=None, i_true=None, substeps: int = 1, x_sub=None,
+                    externals: str = "hold"):
     """Backward of a teacher-forced `dae_integrate` (input_true_x / input_true_i, my_solvers.py:111-121) on the generic backward K5
     (psnode_dae_backward_tf_f32): every shape K5 takes untied.  x_true [T,B,x_dim] / i_true [T,B,i_dim]: the dataset rows the forward call
     fed the DE / the heads (None = that flag was not set; both None = `dae_backward` on K5's entry point); they get no gradient.  xs / is_:
@@ -362,11 +368,11 @@ def dae_backward_tf(method, de_layers: Layers, ae_layers: Layers, t, z, v, all_i
         if q is not None and tuple(q.shape) != (T, B, w):
             raise ValueError(f"{name} must be [T,B,{w}], got {tuple(q.shape)}")
     return _dae_backward_entry(method, de_layers, ae_layers, t, z, v, all_initial, xs, is_, grad_xs, grad_is, event_idx, z_jump, v_jump,
-                               kernel, None, (None, None), x_true=x_true, i_true=i_true, substeps=substeps, x_sub=x_sub)
+                               kernel, None, (None, None), x_true=x_true, i_true=i_true, substeps=substeps, x_sub=x_sub, externals=externals)
 
 
 def _dae_backward_entry(method, de_layers, ae_layers, t, z, v, all_initial, xs, is_, grad_xs, grad_is, event_idx, z_jump, v_jump, kernel, saved,
-                        acts, x_true=None, i_true=None, substeps: int = 1, x_sub=None):
+                        acts, x_true=None, i_true=None, substeps: int = 1, x_sub=None, externals: str = "hold"):
     """psnode_dae_backward_f32 / _act_f32, or psnode_dae_backward_tf_f32 when dataset rows come along, or the _rk / _sub entry points: one
     marshalling for all of them."""
     lib = _lib.load()
@@ -378,7 +384,7 @@ def _dae_backward_entry(method, de_layers, ae_layers, t, z, v, all_initial, xs, 
         raise ValueError(f"dae_backward: substeps={substeps} needs x_sub, the contiguous fp32 [{T - 1},{substeps - 1},{B},{xd}] tensor the "
                          "forward call returned with save_sub=True")
     keep: list = [x_sub]
-    sub = substeps_abi(substeps, x_sub)
+    sub = substeps_abi(substeps, x_sub, externals)
     tf = None
     method_id, S, tab = method_info(method)
     if x_true is not None or i_true is not None or tab is not None or sub is not None:      # (the _rk / _sub entry points take the tf struct, flags 0 included)
@@ -442,7 +448,7 @@ def _dae_backward_entry(method, de_layers, ae_layers, t, z, v, all_initial, xs, 
                 a.saved_ev_act, a.saved_ev_i = s_ev.data_ptr(), s_evi.data_ptr()
         if sub is not None:
             arefs = [ctypes.byref(q.abi()) if q is not None else None for q in acts]
-            nbytes = lib.psnode_dae_backward_sub_workspace_bytes(ctypes.byref(tf), *arefs, ctypes.byref(tab.abi()) if tab is not None else None,
+            nbytes = getattr(lib, f"psnode_dae_backward_{sub_family(sub)}_workspace_bytes")(ctypes.byref(tf), *arefs, ctypes.byref(tab.abi()) if tab is not None else None,
                                                                  ctypes.byref(sub))
         elif tab is not None:
             arefs = [ctypes.byref(q.abi()) if q is not None else None for q in acts]
@@ -458,6 +464,6 @@ def _dae_backward_entry(method, de_layers, ae_layers, t, z, v, all_initial, xs, 
             rc = call_entry(lib, "dae_backward", tf, acts, wp, wn, st, tab, sub)
         else:
             rc = lib.psnode_dae_backward_tf_f32(ctypes.byref(tf), wp, wn, st) if tf is not None else call_entry(lib, "dae_backward", a, acts, wp, wn, st)
-    _lib.check(rc, "psnode_dae_backward_sub_f32" if sub is not None else "psnode_dae_backward_rk_f32" if tab is not None else ("psnode_dae_backward_tf_f32" if tf is not None else "psnode_dae_backward_f32"))
+    _lib.check(rc, f"psnode_dae_backward_{sub_family(sub)}_f32" if sub is not None else "psnode_dae_backward_rk_f32" if tab is not None else ("psnode_dae_backward_tf_f32" if tf is not None else "psnode_dae_backward_f32"))
     g["de"], g["ae"] = _split_grads(gde, de_layers), _split_grads(gae, ae_layers)
     return g

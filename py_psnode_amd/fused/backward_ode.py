@@ -5,7 +5,7 @@ import ctypes
 import torch
 
 from .. import _lib
-from ._common import (KERNEL_ID, Layers, method_info, _aligned16, _aligned_ptr, _bind_jumps, _check_saved, _empty, _f32_dev, _mlp, _split_grads, _view, call_entry, entry_supported, sub_route_ok, substeps_abi)
+from ._common import (KERNEL_ID, Layers, method_info, _aligned16, _aligned_ptr, _bind_jumps, _check_saved, _empty, _f32_dev, _mlp, _split_grads, _view, call_entry, entry_supported, sub_family, sub_route_ok, substeps_abi)
 from .latent import latent_backward_wide, latent_wide_shape
 
 def _bwd_args(method, de_layers, x_dim, z_dim, T, B, dev, keep, kernel="auto"):
@@ -17,15 +17,16 @@ def _bwd_args(method, de_layers, x_dim, z_dim, T, B, dev, keep, kernel="auto"):
     return a
 
 
-def ode_backward_supported(method, de_layers: Layers, x_dim: int, z_dim: int, kernel: str = "auto", act=None, substeps: int = 1) -> bool:
+def ode_backward_supported(method, de_layers: Layers, x_dim: int, z_dim: int, kernel: str = "auto", act=None, substeps: int = 1,
+                           externals: str = "hold") -> bool:
     """True if a fused backward kernel covers this shape: the MFMA class (3n->64->64->64->x, x<=8, z<=4) or any MLP whose
     activations and parameter gradients fit the LDS (generic backward).  act (fused.Act) other than None = ELU(1): K5 only.
     method a fused.Tableau: K5's tableau build only (kernel "auto" / "generic"; it answers for its own LDS fit).  substeps > 1: K5's
-    sub-step build only, under the same rules."""
+    sub-step build only, under the same rules.  externals="linear": K5's linear-externals build only (every substeps >= 1; its own LDS fit)."""
     if de_layers[0][0].device.type != "cuda" or len(de_layers) > _lib.MAX_LAYERS:
         return False
     tab = method_info(method)[2]
-    sub = substeps_abi(substeps)
+    sub = substeps_abi(substeps, None, externals)
     if sub is not None:
         a = _bwd_args(method, de_layers, x_dim, z_dim, 2, 1, de_layers[0][0].device, [], kernel)
         return entry_supported(_lib.load(), "ode_backward", a, (act,), tab, sub)
@@ -40,7 +41,7 @@ def ode_backward_supported(method, de_layers: Layers, x_dim: int, z_dim: int, ke
 
 def ode_backward(method, de_layers: Layers, t, z, all_initial, xs, grad_xs, event_idx=None, z_jump=None, need_grad_z: bool = True,
                  kernel: str = "auto", saved=None, input_true_x: bool = False, need_grad_zj: bool = True, act=None, substeps: int = 1,
-                 x_sub=None):
+                 x_sub=None, externals: str = "hold"):
     """Backward pass of `ode_integrate` in one launch.  `saved` = what `ode_integrate(save=True)` returned next to
     xs: K4f then skips the recompute of the stage evaluations.  input_true_x: backward of a teacher-forced call (my_solvers.py:72-74) --
     `xs` must then be the DATASET x the forward call started every step from; K4f where the shape is its (hidden <= 128, x_dim <= 8) and
@@ -53,6 +54,8 @@ def ode_backward(method, de_layers: Layers, t, z, all_initial, xs, grad_xs, even
     method: "euler" | "midpoint" | "rk4", or a fused.Tableau -- K5 only (kernel "auto" / "generic", no saved rows).
     substeps > 1: backward of `ode_integrate(..., substeps=, save_sub=True)`, with the x_sub [T-1, substeps-1, B, xd] it returned -- K5 only
     (kernel "auto" / "generic", no saved rows; teacher forcing with ELU(1) only).
+    externals="linear": backward of `ode_integrate(..., externals="linear")` -- K5's linear-externals build, the same rules; grad_z row k + 1
+    also receives the right-hand share theta g of interval k's stages.
     Returns (grad_x0 [B,xd], grad_z [T,B,zd] | None, grad_z_jump | None, grad_all_initial [B,n], [grad W1, b1, ..., W4, b4])."""
     lib = _lib.load()
     dev = xs.device
@@ -60,7 +63,7 @@ def ode_backward(method, de_layers: Layers, t, z, all_initial, xs, grad_xs, even
     zd = z.shape[-1]
     # kernel: "auto" / "mfma" = the one-launch K4f at every hidden width <= 128 (z_dim <= 8), K8f / K9 / K9w for the latent shapes, else the
     # generic K5 ("auto" only); "wide" forces K4f
-    sub_route_ok("ode_backward", substeps, kernel, saved is not None)
+    sub_route_ok("ode_backward", substeps, kernel, saved is not None, externals)
     if substeps > 1 and T >= 2 and (x_sub is None or tuple(x_sub.shape) != (T - 1, substeps - 1, B, xd) or not x_sub.is_contiguous()
                                     or x_sub.dtype != torch.float32 or x_sub.device != dev):
         raise ValueError(f"ode_backward: substeps={substeps} needs x_sub, the contiguous fp32 [{T - 1},{substeps - 1},{B},{xd}] tensor the "
@@ -77,7 +80,7 @@ def ode_backward(method, de_layers: Layers, t, z, all_initial, xs, grad_xs, even
                                  z_jump=z_jump, saved=saved, need_grad_z=need_grad_z)
         return g["x_init"], g["z"], g["z_jump"], g["all_initial"], g["de"]
     keep: list = [x_sub]
-    sub = substeps_abi(substeps, x_sub)
+    sub = substeps_abi(substeps, x_sub, externals)
     a = _bwd_args(method, de_layers, xd, zd, T, B, dev, keep, kernel)
     if input_true_x:
         if saved is not None:
@@ -115,5 +118,5 @@ def ode_backward(method, de_layers: Layers, t, z, all_initial, xs, grad_xs, even
         ws = _empty(nbytes + 256, dtype=torch.uint8, device=dev)
         wp, wn = _aligned_ptr(ws)
         rc = call_entry(lib, "ode_backward", a, (act,), wp, wn, torch.cuda.current_stream(dev).cuda_stream, tab, sub)
-    _lib.check(rc, "psnode_ode_backward_sub_f32" if sub is not None else ("psnode_ode_backward_rk_f32" if tab is not None else "psnode_ode_backward_f32"))
+    _lib.check(rc, f"psnode_ode_backward_{sub_family(sub)}_f32" if sub is not None else ("psnode_ode_backward_rk_f32" if tab is not None else "psnode_ode_backward_f32"))
     return gx0, gz, gzj, ga0, _split_grads(gpar, de_layers)

@@ -5,7 +5,7 @@ import ctypes
 import torch
 
 from .. import _lib
-from ._common import Layers, builtin_method, no_substeps, _aligned_ptr, _check_jump, _empty, _f32_dev, _jump, _mlp, _view, event_table
+from ._common import Layers, builtin_method, no_linear, no_substeps, _aligned_ptr, _check_jump, _empty, _f32_dev, _jump, _mlp, _view, event_table
 
 def ode_encoded_supported(x_encoder: Layers, z_encoder: Layers, x_decoder: Layers, de_layers: Layers) -> bool:
     """Shapes of the fused direct_encode ODE forward (psnode_ode_encoded_integrate_f32): every MLP 2 layers with hidden 16."""
@@ -23,7 +23,7 @@ def ode_encoded_supported(x_encoder: Layers, z_encoder: Layers, x_decoder: Layer
 
 def ode_encoded_integrate(method: str, x_encoder: Layers, z_encoder: Layers, x_decoder: Layers, de_layers: Layers, t, x, z,
                           event_t=None, z_jump=None, event_idx=None, want_recon: bool = True, want_latent: bool = False,
-                          check_events: bool = False, substeps: int = 1):
+                          check_events: bool = False, substeps: int = 1, externals: str = "hold"):
     """The whole ODE_Model.forward of neural_00_ODE_02_direct_encode.py:74-89 in ONE launch (hidden_dim 16): encoders, latent
     integrate_ODE, decoder of the solution and the reconstruction x_decoder(x_encoder(x)).  t, x, z are the scripts' B-major
     tensors [B,T,*] (any strides with a contiguous last dim); z_jump is the RAW [B,nE,z_dim] tensor.  Returns
@@ -33,6 +33,7 @@ def ode_encoded_integrate(method: str, x_encoder: Layers, z_encoder: Layers, x_d
     keep: list = []
     a = _lib.OdeEncodedArgsF32()
     no_substeps(substeps, "ode_encoded_integrate")
+    no_linear(externals, "ode_encoded_integrate")
     a.method = builtin_method(method, "ode_encoded_integrate")[0]
     B, T, xd = x.shape
     zd = z.shape[-1]
@@ -102,7 +103,7 @@ def dae_encoded_supported(x_encoder, z_encoder, v_encoder, i_encoder, x_decoder,
 
 def dae_encoded_integrate(method: str, x_encoder, z_encoder, v_encoder, i_encoder, x_decoder, i_decoder, de_layers, ae_layers,
                           x0, t, x, z, v, i, event_t=None, z_jump=None, v_jump=None, event_idx=None, want_recon: bool = True,
-                          check_events: bool = False, substeps: int = 1):
+                          check_events: bool = False, substeps: int = 1, externals: str = "hold"):
     """The whole DAE_Model.forward of neural_01_DAE_02_direct_encode.py:125-153 in ONE launch (hidden_dim 64): the four encoders,
     all_initial, the latent integrate_DAE, both decoders of the solution and the two reconstructions.  x0 [B,xd] is Init_Func's output;
     t, x, z, v, i are the scripts' B-major tensors [B,T,*] (z of width 0 when the model has no z_encoder); z_jump / v_jump the RAW
@@ -118,6 +119,7 @@ def dae_encoded_integrate(method: str, x_encoder, z_encoder, v_encoder, i_encode
     mlps = (x_encoder, z_encoder, v_encoder, i_encoder, x_decoder, i_decoder, de_layers, ae_layers)
     a = _dae_encoded_args(mlps, dev, keep, xd, zd, vd, idim)
     no_substeps(substeps, "dae_encoded_integrate")
+    no_linear(externals, "dae_encoded_integrate")
     a.method, a.T, a.B = builtin_method(method, "dae_encoded_integrate")[0], T, B
     if not lib.psnode_dae_encoded_supported(ctypes.byref(a)):
         raise _lib.UnsupportedShapeError("dae_encoded_integrate: needs encoders in->64->64 (x <= 16, z | v | i <= 8 wide), decoders "

@@ -6,7 +6,7 @@ from typing import Optional
 import torch
 
 from .. import _lib
-from ._common import (KERNEL_ID, Layers, Tableau, builtin_method, method_info, _aligned16, _aligned_ptr, _bind_events, _check_tb, _empty, _f32_dev, _mlp, _view, _workspace, call_entry, dae_acts, sub_route_ok, substeps_abi)
+from ._common import (KERNEL_ID, Layers, Tableau, builtin_method, method_info, _aligned16, _aligned_ptr, _bind_events, _check_tb, _empty, _f32_dev, _mlp, _view, _workspace, call_entry, dae_acts, is_linear, sub_family, sub_route_ok, substeps_abi)
 
 _MFMA_CLASSES = ("MFMA integrators K1 / K2 cover `in -> H -> H -> H -> out` ELU-MLPs with H <= 128 (any x_dim <= 16 for the ODE, "
                  "x_dim <= 8 and z+v+i <= 8 for the DAE), and -- weights streamed from L2 -- the ODE up to H = 192 at any x_dim <= 16 and "
@@ -59,7 +59,7 @@ def _rk_route_ok(what: str, tab, kernel: str, save: bool):
 def ode_integrate(method, de_layers: Layers, t, x, z, all_initial, event_t=None, z_jump=None,
                   input_true_x: bool = False, kernel: str = "auto", event_idx: Optional[torch.Tensor] = None,
                   check_events: bool = False, out: Optional[torch.Tensor] = None, save: bool = False, act=None, substeps: int = 1,
-                  save_sub: bool = False):
+                  save_sub: bool = False, externals: str = "hold"):
     """Fused integrate_ODE (replaces my_solvers.py:52-80 + my_fixed_grid.py + DE_Func.forward).
 
     method: "euler" | "midpoint" | "rk4" (the 3/8 rule), or a fused.Tableau -- any explicit Runge-Kutta method of up to four stages, on
@@ -71,6 +71,10 @@ def ode_integrate(method, de_layers: Layers, t, x, z, all_initial, event_t=None,
     grid of t.  More than 1 runs on the generic kernel K0 only (kernel "auto" / "generic"; save=True is refused).  save_sub=True (training
     forward): returns (xs, x_sub) with x_sub [T-1, substeps-1, B, xd] the start states of sub-steps 1.. of every interval, for
     `ode_backward(..., substeps=, x_sub=)` (None for substeps == 1).
+
+    externals: "hold" (the left grid point's z feeds every stage of an interval) or "linear": stage s of sub-step j reads
+    z[k] + theta (z[k+1] - z[k]) at theta = (j + c_s) / substeps, z[k] being the jumped row behind an event; the generic kernel K0 in its
+    linear-externals build for every substeps >= 1 (kernel "auto" / "generic"; save=True is refused; save_sub then always returns a tensor).
 
     save=True (training forward, K1 shapes only -- `ode_save_hidden`): the kernel also writes what autograd would save, the hidden
     activations [T-1,S,3,B,Hp] and the stage inputs [T-1,S,B,xd]; returns (xs, (act, xstage)) for `ode_backward(..., saved=)`.
@@ -87,7 +91,7 @@ def ode_integrate(method, de_layers: Layers, t, x, z, all_initial, event_t=None,
     _act_route_ok("ode_integrate", act is not None, kernel, save)
     method_id, S, tab = method_info(method)
     _rk_route_ok("ode_integrate", tab, kernel, save)
-    sub_route_ok("ode_integrate", substeps, kernel, save)
+    sub_route_ok("ode_integrate", substeps, kernel, save, externals)
     T, B, xd = t.shape[0], x.shape[1], x.shape[2]
     if x.shape[0] < (T if input_true_x else 1):
         raise ValueError("x has fewer grid points than t")
@@ -128,12 +132,12 @@ def ode_integrate(method, de_layers: Layers, t, x, z, all_initial, event_t=None,
                      _empty((max(T - 1, 0), S, B, xd), dtype=torch.float32, device=dev))
             if T >= 2:
                 a.save_act, a.save_xstage = saved[0].data_ptr(), saved[1].data_ptr()
-        x_sub = _empty((max(T - 1, 0), substeps - 1, B, xd), dtype=torch.float32, device=dev) if save_sub and substeps > 1 else None
-        sub = substeps_abi(substeps, x_sub)
+        x_sub = _empty((max(T - 1, 0), substeps - 1, B, xd), dtype=torch.float32, device=dev) if save_sub and (substeps > 1 or is_linear(externals)) else None
+        sub = substeps_abi(substeps, x_sub, externals)
         ws = _workspace(lib, a.de, None, dev)
         wp, wn = _aligned_ptr(ws)
         rc = call_entry(lib, "ode_integrate", a, (act,), wp, wn, torch.cuda.current_stream(dev).cuda_stream, tab, sub)
-    entry = "psnode_ode_integrate_sub_f32" if sub is not None else ("psnode_ode_integrate_rk_f32" if tab is not None else "psnode_ode_integrate_f32")
+    entry = f"psnode_ode_integrate_{sub_family(sub)}_f32" if sub is not None else ("psnode_ode_integrate_rk_f32" if tab is not None else "psnode_ode_integrate_f32")
     _mfma_miss(rc, kernel, entry, de_layers)
     _lib.check(rc, entry)
     if kernel == "auto" and act is None and tab is None and sub is None:
@@ -144,10 +148,10 @@ def ode_integrate(method, de_layers: Layers, t, x, z, all_initial, event_t=None,
     return (out, saved) if save else out
 
 
-def ode_save_hidden(method, de_layers: Layers, x_dim: int, z_dim: int, kernel: str = "auto", substeps: int = 1) -> int:
-    """Row width of the saved activations if the forward for these dims can save them (K1 proper), else 0 (always for a Tableau and for
-    substeps > 1)."""
-    if substeps != 1 or isinstance(method, Tableau) or de_layers[0][0].device.type != "cuda" or len(de_layers) > _lib.MAX_LAYERS:
+def ode_save_hidden(method, de_layers: Layers, x_dim: int, z_dim: int, kernel: str = "auto", substeps: int = 1, externals: str = "hold") -> int:
+    """Row width of the saved activations if the forward for these dims can save them (K1 proper), else 0 (always for a Tableau, for
+    substeps > 1 and for externals="linear")."""
+    if is_linear(externals) or substeps != 1 or isinstance(method, Tableau) or de_layers[0][0].device.type != "cuda" or len(de_layers) > _lib.MAX_LAYERS:
         return 0
     lib = _lib.load()
     a = _lib.OdeArgsF32()
@@ -159,7 +163,7 @@ def ode_save_hidden(method, de_layers: Layers, x_dim: int, z_dim: int, kernel: s
 def dae_integrate(method, de_layers: Layers, ae_layers: Layers, x_init, t, x, z, v, i, all_initial,
                   event_t=None, z_jump=None, v_jump=None, input_true_x: bool = False, input_true_i: bool = False,
                   kernel: str = "auto", event_idx: Optional[torch.Tensor] = None, check_events: bool = False, out=None,
-                  save: bool = False, act=None, substeps: int = 1, save_sub: bool = False):
+                  save: bool = False, act=None, substeps: int = 1, save_sub: bool = False, externals: str = "hold"):
     """Fused integrate_DAE (replaces my_solvers.py:82-131 + step functions + DE_Func/AE_Func forwards).
     method: "euler" | "midpoint" | "rk4", or a fused.Tableau (generic kernel K0 only: kernel "auto" / "generic"; save=True is refused).
     act: None (both MLPs ELU(1)) or (de_act, ae_act), each a fused.Act or None = ELU(1); an activation other than ELU(1) runs on the
@@ -167,6 +171,9 @@ def dae_integrate(method, de_layers: Layers, ae_layers: Layers, x_init, t, x, z,
     substeps (1..1024): sub-steps per grid interval with z | v held; without input_true_i the algebraic variable is re-evaluated from the
     state at the start of every sub-step behind the first.  More than 1: the generic kernel K0 only (kernel "auto" / "generic", no save).
     save_sub=True (training forward): returns (xs, is, x_sub), x_sub [T-1, substeps-1, B, xd] for the backward (None for substeps == 1).
+    externals: "hold", or "linear" -- every stage reads z | v interpolated between grid points k (the jumped rows behind an event) and k + 1
+    at theta = (j + c_s) / substeps, as does the head in front of sub-step j >= 1 (theta = j / substeps); i is never interpolated.  K0's
+    linear-externals build for every substeps >= 1 (kernel "auto" / "generic", no save).
     `out` = (xs, is) contiguous [T,B,xd] / [T,B,id] tensors to write into (time-chunked launches).
     save=True (training forward, K2 shapes without teacher forcing -- `dae_save_hidden`): the kernel also writes what autograd would
     save (psnode_dae_args_f32::save_*); returns (xs, is, saved) with saved = (act [T-1,S,3,B,Hp], xstage [T-1,S,B,xd],
@@ -180,7 +187,7 @@ def dae_integrate(method, de_layers: Layers, ae_layers: Layers, x_init, t, x, z,
     _act_route_ok("dae_integrate", non_elu, kernel, save)
     method_id, S, tab = method_info(method)
     _rk_route_ok("dae_integrate", tab, kernel, save)
-    sub_route_ok("dae_integrate", substeps, kernel, save)
+    sub_route_ok("dae_integrate", substeps, kernel, save, externals)
     T, B = t.shape[0], t.shape[1]
     xd, zd, vd, idim = x_init.shape[-1], z.shape[-1], v.shape[-1], i.shape[-1]
     if x_init.dim() != 2 or x_init.shape[0] != B:
@@ -244,12 +251,12 @@ def dae_integrate(method, de_layers: Layers, ae_layers: Layers, x_init, t, x, z,
                 a.save_act = a.save_xstage = dummy.data_ptr()
             if n_ev:
                 a.save_ev_act, a.save_ev_i = saved[3].data_ptr(), saved[4].data_ptr()
-        x_sub = _empty((max(T - 1, 0), substeps - 1, B, xd), dtype=torch.float32, device=dev) if save_sub and substeps > 1 else None
-        sub = substeps_abi(substeps, x_sub)
+        x_sub = _empty((max(T - 1, 0), substeps - 1, B, xd), dtype=torch.float32, device=dev) if save_sub and (substeps > 1 or is_linear(externals)) else None
+        sub = substeps_abi(substeps, x_sub, externals)
         ws = _workspace(lib, a.de, a.ae, dev)
         wp, wn = _aligned_ptr(ws)
         rc = call_entry(lib, "dae_integrate", a, acts, wp, wn, torch.cuda.current_stream(dev).cuda_stream, tab, sub)
-    entry = "psnode_dae_integrate_sub_f32" if sub is not None else ("psnode_dae_integrate_rk_f32" if tab is not None else "psnode_dae_integrate_f32")
+    entry = f"psnode_dae_integrate_{sub_family(sub)}_f32" if sub is not None else ("psnode_dae_integrate_rk_f32" if tab is not None else "psnode_dae_integrate_f32")
     _mfma_miss(rc, kernel, entry, de_layers)
     _lib.check(rc, entry)
     if kernel == "auto" and not non_elu and tab is None and sub is None:
@@ -260,10 +267,10 @@ def dae_integrate(method, de_layers: Layers, ae_layers: Layers, x_init, t, x, z,
 
 
 def dae_save_hidden(method, de_layers: Layers, ae_layers: Layers, x_dim: int, z_dim: int, v_dim: int, i_dim: int,
-                    kernel: str = "auto", substeps: int = 1) -> int:
-    """Row width of the saved activations if the forward for these dims can save them (K2 proper), else 0 (always for a Tableau and for
-    substeps > 1)."""
-    if substeps != 1 or isinstance(method, Tableau) or de_layers[0][0].device.type != "cuda" or max(len(de_layers), len(ae_layers)) > _lib.MAX_LAYERS:
+                    kernel: str = "auto", substeps: int = 1, externals: str = "hold") -> int:
+    """Row width of the saved activations if the forward for these dims can save them (K2 proper), else 0 (always for a Tableau, for
+    substeps > 1 and for externals="linear")."""
+    if is_linear(externals) or substeps != 1 or isinstance(method, Tableau) or de_layers[0][0].device.type != "cuda" or max(len(de_layers), len(ae_layers)) > _lib.MAX_LAYERS:
         return 0
     lib = _lib.load()
     a = _lib.DaeArgsF32()

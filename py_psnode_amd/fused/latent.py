@@ -7,7 +7,7 @@ from typing import Optional
 import torch
 
 from .. import _lib
-from ._common import Layers, builtin_method, no_substeps, _aligned_ptr, _empty, _f32_dev, _gemm_tn, _mlp, _view, gemm_tn
+from ._common import Layers, builtin_method, no_linear, no_substeps, _aligned_ptr, _empty, _f32_dev, _gemm_tn, _mlp, _view, gemm_tn
 
 def latent_wide_shape(de_layers: Layers, ae_layers: Optional[Layers], x_dim: int, z_dim: int, v_dim: int = 0, i_dim: int = 0) -> bool:
     """The latent shapes of the direct_encode models at a hidden width the dedicated latent kernels do not take (every H <= 128 with
@@ -24,7 +24,8 @@ def latent_wide_shape(de_layers: Layers, ae_layers: Optional[Layers], x_dim: int
 
 
 def latent_backward_wide(method: str, de_layers: Layers, ae_layers: Optional[Layers], t, z, v, all_initial, xs, is_, grad_xs, grad_is,
-                         event_idx=None, z_jump=None, v_jump=None, saved=None, need_grad_z: bool = True, substeps: int = 1):
+                         event_idx=None, z_jump=None, v_jump=None, saved=None, need_grad_z: bool = True, substeps: int = 1,
+                         externals: str = "hold"):
     """Backward of the latent integrate_ODE / integrate_DAE at the hidden widths of `latent_wide_shape` (split form): the sequential
     adjoint sweep K9w (psnode_latent_backward_wide_f32) reads the activations the K3w training forward saved and stores the adjoint rows;
     every parameter / input gradient is then a contraction over those rows as library GEMMs.  Returns the dict of `dae_backward` (for the
@@ -37,6 +38,7 @@ def latent_backward_wide(method: str, de_layers: Layers, ae_layers: Optional[Lay
     T, B, H = xs.shape
     zd = z.shape[-1] if z is not None else 0
     no_substeps(substeps, "latent_backward_wide")
+    no_linear(externals, "latent_backward_wide")
     method_id, S = builtin_method(method, "latent_backward_wide")
     nblk = (4 if zd else 3) if dae else 2
     n = nblk * H

@@ -4,12 +4,25 @@ Runge-Kutta tableau of up to four stages (Heun2, Ralston2, Kutta3, SSPRK3, RK4Cl
 `method` names the formula the fused HIP kernel runs for the class; `_step_func` is the same formula for
 the callback walk (user callables / autograd).  Callback convention (my_fixed_grid.py:16-17): ODE branch
 `func(t0=, xt=, zt=, all_initial=)` when v0 is None, else `func(t0=, xt=, zt=, vt=, it=, all_initial=)`.
+
+`_step_func_lin` is each class's formula once more for `externals="linear"` (my_solvers.py): the stage at abscissa c reads the externals
+`ext_at(c)` instead of the step's frozen ones.  `_step_func`, its signature and the "hold" path are untouched by it.
 """
 from .. import fused as _fused
 from .my_solvers import FixedGridODESolver
 
 _one_third = 1 / 3
 _two_thirds = 2 / 3
+
+
+def _rhs_at(func, ext_at, i0, all_initial):
+    """f(c, t, x): the right-hand side whose externals are those of abscissa c, ext_at(c) = (z, v | None) (externals='linear')."""
+    def f(c, tt, xx):
+        z0, v0 = ext_at(c)
+        if v0 is None:
+            return func(t0=tt, xt=xx, zt=z0, all_initial=all_initial)
+        return func(t0=tt, xt=xx, zt=z0, vt=v0, it=i0, all_initial=all_initial)
+    return f
 
 
 def _rhs(func, z0, v0, i0, all_initial):
@@ -27,6 +40,9 @@ class Euler(FixedGridODESolver):
         f0 = _rhs(func, z0, v0, i0, all_initial)(t0, x0)
         return dt * f0, f0
 
+    def _step_func_lin(self, func, t0, dt, x0, ext_at, i0=None, all_initial=None):
+        return dt * _rhs_at(func, ext_at, i0, all_initial)(0.0, t0, x0)
+
 
 class Midpoint(FixedGridODESolver):
     order = 2
@@ -37,6 +53,11 @@ class Midpoint(FixedGridODESolver):
         half_dt = 0.5 * dt
         f0 = f(t0, x0)
         return dt * f(t0 + half_dt, x0 + f0 * half_dt), f0
+
+    def _step_func_lin(self, func, t0, dt, x0, ext_at, i0=None, all_initial=None):
+        f = _rhs_at(func, ext_at, i0, all_initial)
+        half_dt = 0.5 * dt
+        return dt * f(0.5, t0 + half_dt, x0 + f(0.0, t0, x0) * half_dt)
 
 
 class RK4(FixedGridODESolver):
@@ -56,6 +77,15 @@ class RK4(FixedGridODESolver):
         f0 = _rhs(func, z0, v0, i0, all_initial)(t0, x0)
         return self.rk4_alt_step_func(func=func, t0=t0, dt=dt, t1=t1, x0=x0, z0=z0, v0=v0, i0=i0,
                                       all_initial=all_initial, f0=f0), f0
+
+    def _step_func_lin(self, func, t0, dt, x0, ext_at, i0=None, all_initial=None):
+        """The 3/8 rule with the externals of c = 0, 1/3, 2/3, 1."""
+        f = _rhs_at(func, ext_at, i0, all_initial)
+        k1 = f(0.0, t0, x0)
+        k2 = f(_one_third, t0 + dt * _one_third, x0 + dt * k1 * _one_third)
+        k3 = f(_two_thirds, t0 + dt * _two_thirds, x0 + dt * (k2 - k1 * _one_third))
+        k4 = f(1.0, t0 + dt, x0 + dt * (k1 - k2 + k3))
+        return (k1 + 3 * (k2 + k3) + k4) * dt * 0.125
 
 
 class ExplicitRK(FixedGridODESolver):
@@ -86,6 +116,15 @@ class ExplicitRK(FixedGridODESolver):
             inc = self._combine(tab.a[s][:s], ks)
             ks.append(f(t0 + tab.c[s] * dt if s else t0, x0 if inc is None else x0 + dt * inc))
         return dt * self._combine(tab.b, ks), ks[0]
+
+    def _step_func_lin(self, func, t0, dt, x0, ext_at, i0=None, all_initial=None):
+        f = _rhs_at(func, ext_at, i0, all_initial)
+        tab = self.method
+        ks = []
+        for s in range(tab.stages):
+            inc = self._combine(tab.a[s][:s], ks)
+            ks.append(f(tab.c[s], t0 + tab.c[s] * dt if s else t0, x0 if inc is None else x0 + dt * inc))
+        return dt * self._combine(tab.b, ks)
 
 
 class _NamedRK(ExplicitRK):

@@ -36,8 +36,14 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
     order: int
     method = ""        # "euler" | "midpoint" | "rk4", or a fused.Tableau (my_fixed_grid.ExplicitRK): the formula the fused kernels run
 
-    def __init__(self, step_size=None, grid_constructor=None, interp="linear", substeps=1):
-        """substeps (an int >= 1, default 1): every grid interval [t[k], t[k+1]] is integrated in that many equal sub-steps of
+    def __init__(self, step_size=None, grid_constructor=None, interp="linear", substeps=1, externals="hold"):
+        """externals ("hold", the default and the reference's behaviour, or "linear"): what the stages of a grid interval read of the
+        external inputs z | v.  "hold": the left grid point's rows (the jumped ones behind an event) for every stage and sub-step -- which
+        leaves an O(interval) error that no method order and no number of sub-steps removes.  "linear": stage s (abscissa c_s) of sub-step j
+        reads w_L + theta (w_R - w_L) at theta = (j + c_s) / substeps, w_L the left rows (jumped behind an event), w_R the dataset's rows of
+        the next grid point (`_walk_ode` / `_walk_dae` are the definition; fused on the generic kernels K0 / K5, kernel 'auto' / 'generic').
+        `interp` cannot carry this: the reference passes interp="linear" by default and holds.
+        substeps (an int >= 1, default 1): every grid interval [t[k], t[k+1]] is integrated in that many equal sub-steps of
         h = (t[k+1] - t[k]) / substeps, with the interval's external inputs held over all of them and the outputs staying on the grid of t
         (`_walk_ode` / `_walk_dae` are the definition; more than 1 runs fused on the generic kernels K0 / K5, kernel 'auto' / 'generic').
         It is the supported way to integrate with a finer step than the data's sampling interval: `step_size`, `grid_constructor` and
@@ -45,6 +51,9 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
         if isinstance(substeps, bool) or not isinstance(substeps, int) or substeps < 1:
             raise ValueError(f"substeps must be an int >= 1, got {substeps!r}")
         self.substeps = substeps
+        if externals not in _fused.EXTERNALS:
+            raise ValueError(f"externals must be one of {_fused.EXTERNALS}, got {externals!r}")
+        self.externals = externals
         # public attributes of the reference (my_solvers.py:13-18)
         self.step_size = step_size
         self.interp = interp
@@ -83,7 +92,7 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
             self._walk_warned = True
             warnings.warn(f"{what}: this call is not fusable (needs fp32 HIP tensors, DE_Func/AE_Func-style MLPs with one activation "
                           "of ELU / Tanh / Sigmoid / ReLU / LeakyReLU / Softplus / SiLU / GELU / Mish -- other than ELU(1) on kernel 'auto' / 'generic' only --, "
-                          "ODE_Event/DAE_Event callbacks; an ExplicitRK tableau or substeps > 1 on kernel 'auto' / 'generic' only (substeps <= 1024); under autograd also a shape with a backward kernel; teacher-forced "
+                          "ODE_Event/DAE_Event callbacks; an ExplicitRK tableau, substeps > 1 or externals='linear' on kernel 'auto' / 'generic' only (substeps <= 1024); under autograd also a shape with a backward kernel; teacher-forced "
                           "training: ELU(1), dataset rows without grad) -- stepping through the Python callables instead", RuntimeWarning, stacklevel=3)
 
     def _act_kernel_ok(self, what, acts) -> bool:
@@ -117,6 +126,31 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
                                         f"interval run on the generic kernels (kernel 'auto' / 'generic', substeps <= {_fused._lib.MAX_SUBSTEPS})")
         return False
 
+    def _lin_kernel_ok(self, what) -> bool:
+        """Linearly interpolated externals (externals='linear') run on the generic kernels K0 / K5 only: kernel 'wave' / 'tile' / 'mfma' /
+        'wide' with them walks under fused='auto' and raises under 'require'."""
+        if self.externals == "hold" or (self.kernel in ("auto", "generic") and self.substeps <= _fused._lib.MAX_SUBSTEPS):
+            return True
+        if self.fused == "require":
+            raise UnsupportedShapeError(f"{what}: kernel={self.kernel!r} with externals='linear' has no fused form: interpolated external "
+                                        f"inputs run on the generic kernels (kernel 'auto' / 'generic', substeps <= {_fused._lib.MAX_SUBSTEPS})")
+        return False
+
+    def _step_func_lin(self, func, t0, dt, x0, ext_at, i0=None, all_initial=None):
+        """-> dx of one (sub-)step whose stage at abscissa c reads the externals ext_at(c) = (z, v | None): the class's own formula with a
+        per-stage external (the private path of externals='linear'; my_fixed_grid.py implements it for every solver of the package)."""
+        raise NotImplementedError(f"{type(self).__name__} has no _step_func_lin: externals='linear' needs the step formula with per-stage "
+                                  "external inputs")
+
+    @staticmethod
+    def _lin_ext(j, n, left, right):
+        """c -> the externals at theta = (j + c) / n between the rows `left` and `right` (tuples of z[, v]): w_L + theta (w_R - w_L) in the
+        tensors' dtype, as written."""
+        def ext_at(c):
+            theta = (j + c) / n
+            return tuple(wl + theta * (wr - wl) for wl, wr in zip(left, right))
+        return ext_at
+
     def _check_events_now(self, event_t):
         return (self.check_events and event_t is not None and event_t.dim() == 3 and event_t.shape[1] > 1
                 and not torch.cuda.is_current_stream_capturing())
@@ -139,9 +173,11 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
         if self.fused != "off":
             plan = _fused.plan_ode(x_func, x, z, all_initial, event_fn, jump_change_fn, t=t, x_init=x_init)
             if plan is not None and not (self._act_kernel_ok("integrate_ODE", plan[4:]) and self._rk_kernel_ok("integrate_ODE")
-                                         and self._sub_kernel_ok("integrate_ODE")):
+                                         and self._sub_kernel_ok("integrate_ODE") and self._lin_kernel_ok("integrate_ODE")):
                 plan = None
             sub = dict(substeps=self.substeps) if self.substeps != 1 else {}      # (substeps == 1: the calls as they always were)
+            if self.externals != "hold":                                          # ("hold" likewise)
+                sub["externals"] = self.externals
             if plan is not None:
                 layers, event_t, z_jump, needs_grad, act = plan
                 if not needs_grad:
@@ -183,7 +219,14 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
             if event_fn is not None and event_fn(t0) == True:  # noqa: E712 (callbacks may return tensors)
                 zk = jump_change_fn(t0, zk)
             start = x[k] if input_true_x else cur
-            if self.substeps == 1:
+            if self.externals == "linear":      # stage s of sub-step j reads zk + theta (z[k + 1] - zk), theta = (j + c_s) / n; zk jumped behind an event
+                h = (t1 - t0) / self.substeps
+                cur = start
+                for j in range(self.substeps):
+                    ext_at = self._lin_ext(j, self.substeps, (zk,), (z[k + 1],))
+                    cur = cur + self._step_func_lin(func=x_func, t0=t0 + j * h if j else t0, dt=h, x0=cur, ext_at=lambda c: ext_at(c) + (None,),
+                                                    all_initial=all_initial)
+            elif self.substeps == 1:
                 cur, _ = self.step_integrate(func=x_func, t0=t0, dt=t1 - t0, t1=t1, x0=start, z0=zk, all_initial=all_initial)
             else:       # n equal sub-steps of h = (t1 - t0) / n with the interval's z held; only sub-step 0 starts from the dataset row
                 h = (t1 - t0) / self.substeps
@@ -199,9 +242,11 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
         if self.fused != "off":
             plan = _fused.plan_dae(x_init, x_func, i_func, z, v, i, all_initial, event_fn, jump_change_fn, t=t)
             if plan is not None and not (self._act_kernel_ok("integrate_DAE", plan[6:]) and self._rk_kernel_ok("integrate_DAE")
-                                         and self._sub_kernel_ok("integrate_DAE")):
+                                         and self._sub_kernel_ok("integrate_DAE") and self._lin_kernel_ok("integrate_DAE")):
                 plan = None
             sub = dict(substeps=self.substeps) if self.substeps != 1 else {}
+            if self.externals != "hold":
+                sub["externals"] = self.externals
             if plan is not None:
                 de, ae, event_t, z_jump, v_jump, needs_grad, de_act, ae_act = plan
                 act = None if de_act is None and ae_act is None else (de_act, ae_act)
@@ -251,7 +296,17 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
                 cur_i = i_func(xt=cur_x, zt=zk, vt=vk, all_initial=all_initial)
             start = x[k] if input_true_x else cur_x
             i_in = i[k] if input_true_i else cur_i
-            if self.substeps == 1:
+            if self.externals == "linear":      # as the ODE, for z | v; i is frozen over a sub-step's stages and never interpolated; the head in
+                h = (t1 - t0) / self.substeps   # front of sub-step j >= 1 sees the state and the z | v of theta = j / n
+                cur_x = start
+                for j in range(self.substeps):
+                    ext_at = self._lin_ext(j, self.substeps, (zk, vk), (z[k + 1], v[k + 1]))
+                    if j > 0 and not input_true_i:
+                        zj_, vj_ = ext_at(0.0)
+                        i_in = i_func(xt=cur_x, zt=zj_, vt=vj_, all_initial=all_initial)
+                    cur_x = cur_x + self._step_func_lin(func=x_func, t0=t0 + j * h if j else t0, dt=h, x0=cur_x, ext_at=ext_at, i0=i_in,
+                                                        all_initial=all_initial)
+            elif self.substeps == 1:
                 cur_x, _ = self.step_integrate(func=x_func, t0=t0, dt=t1 - t0, t1=t1, x0=start, z0=zk, v0=vk, i0=i_in,
                                                all_initial=all_initial)
             else:       # n equal sub-steps with the interval's z | v held; the algebraic variable follows the state inside the interval
@@ -267,7 +322,8 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
         return xs, is_
 
     # dead helpers of the reference kept for API completeness (my_solvers.py:177-192); nothing calls them:
-    # the integrators hold external inputs constant over a step (zero-order hold).
+    # the integrators hold external inputs constant over a step (zero-order hold) unless externals="linear", whose walk interpolates
+    # with `_lin_ext` (theta from the sub-step and stage indices, not from the clock).
     def _cubic_hermite_interp(self, t0, x0, f0, t1, x1, f1, t):
         h = (t - t0) / (t1 - t0)
         dt = t1 - t0
