@@ -10,6 +10,8 @@
 // profiles/scripts/variants/ keeps the sources).
 #include <string.h>
 
+#include <type_traits>
+
 #include "psnode_act.h"
 #include "psnode_pack.h"
 
@@ -49,22 +51,22 @@ bool workspace_ok(const void* workspace, size_t workspace_bytes, size_t need) {
 }
 
 // ---- K5 (psnode_generic_bwd_impl.h): the recipe dims it takes, its call struct, the choice among its three builds
-// pre: K5's pre-activation build (its own LDS fit: psnode_generic_bwd_impl.h, pre_floats)
-bool ode_generic_ok(const psnode_ode_bwd_args_f32* a, bool pre = false) {
+// pre: K5's builds that keep the pre-activations (their own LDS fit: psnode_generic_bwd_impl.h, pre_floats); lin: the linear-externals build's
+bool ode_generic_ok(const psnode_ode_bwd_args_f32* a, bool pre = false, bool lin = false) {
     const psnode_mlp_f32& m = a->de;
     if (a->x_dim < 1 || a->z_dim < 0 || m.n_layers < 1 || m.n_layers > kMaxLayers) return false;
     if (m.in_dim != 3 * (a->x_dim + a->z_dim) || m.out_dim[m.n_layers - 1] != a->x_dim) return false;
-    return generic_bwd_fits(&a->de, nullptr, a->x_dim, a->z_dim, 0, 0, pre) != 0;
+    return generic_bwd_fits(&a->de, nullptr, a->x_dim, a->z_dim, 0, 0, pre, lin) != 0;
 }
 // (K5's mode for the shape, 0 = not taken: what psnode_dae_backward_supported returns)
-int dae_generic_ok(const psnode_dae_bwd_args_f32* a, bool pre = false) {
+int dae_generic_ok(const psnode_dae_bwd_args_f32* a, bool pre = false, bool lin = false) {
     if (a->x_dim < 1 || a->z_dim < 0 || a->v_dim < 0 || a->i_dim < 1) return 0;
     const int n = a->x_dim + a->z_dim + a->v_dim + a->i_dim;
     const psnode_mlp_f32 &d = a->de, &g = a->ae;
     if (d.n_layers < 1 || d.n_layers > kMaxLayers || g.n_layers < 1 || g.n_layers > kMaxLayers) return 0;
     if (d.in_dim != 3 * n || d.out_dim[d.n_layers - 1] != a->x_dim) return 0;
     if (g.in_dim != n + a->x_dim + a->z_dim + a->v_dim || g.out_dim[g.n_layers - 1] != a->i_dim) return 0;
-    return generic_bwd_fits(&a->de, &a->ae, a->x_dim, a->z_dim, a->v_dim, a->i_dim, pre);
+    return generic_bwd_fits(&a->de, &a->ae, a->x_dim, a->z_dim, a->v_dim, a->i_dim, pre, lin);
 }
 ViewDev view(const psnode_view_f32& v) { return ViewDev{v.ptr, v.stride_t, v.stride_b}; }
 GenericBwdCall generic_bwd_call(const psnode_ode_bwd_args_f32& a) {
@@ -94,10 +96,6 @@ int generic_backward(const GenericBwdCall& c, const ActPair* act, void* workspac
     if (c.rk) return generic_backward_launch<BuildRk>(c, act, static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
     const auto launch = !act ? generic_backward_launch<BuildElu1> : (act_pair_pre(*act) ? generic_backward_launch<BuildPre> : generic_backward_launch<BuildAct>);
     return launch(c, act, static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
-}
-// what a non-ELU(1) act asks of the call besides the dims: K5 (AUTO / GENERIC), no teacher forcing, no saved rows
-bool act_bwd_ok(int kernel, uint32_t flags, const void* saved_act) {
-    return (kernel == PSNODE_KERNEL_AUTO || kernel == PSNODE_KERNEL_GENERIC) && flags == 0 && !saved_act;
 }
 // K4f: every width <= 128 (z_dim up to 8), saved-activation and recompute forms
 bool use_fused_bwd(const psnode_ode_bwd_args_f32* a) { return a->kernel != PSNODE_KERNEL_GENERIC && fused_bwd_shape_ok(a); }
@@ -211,239 +209,137 @@ extern "C" int32_t psnode_dae_backward_f32(const psnode_dae_bwd_args_f32* a, voi
     return generic_backward(generic_bwd_call(*a), nullptr, workspace, stream);
 }
 
-// ---- teacher-forced DAE backward (include/psnode_hip.h, psnode_dae_bwd_tf_args_f32): K5 alone answers a call with flags; flags == 0 is
-// the entry point above.  NULL args -> method -> dims -> unsupported -> pointers -> workspace, as there.
+// ---- The K5 entry-point families psnode_dae_backward_tf_* and psnode_{ode,dae}_backward_{act,rk,sub,lin}_*: one checked call path
+// (k5_backward), one query (k5_supported).  Order of checks per family, which is the order of the statuses of a call that is wrong in
+// several ways:
+//
+//   _tf    NULL args | flags == 0 -> the plain entry point | method | T, B (T >= 2) | route | pointers | workspace
+//   _act   act pair | ELU(1) pair -> the plain entry point | NULL args | method | T, B | route | pointers | workspace
+//   _rk    act pair | tableau | NULL args | T, B | route | pointers | workspace            (`method` is not read)
+//   _sub   struct (NULL: PSNODE_ERR_NULL) | substeps == 1 -> the _rk family (tableau given) or the _act family | act pair | NULL args |
+//          tableau (NULL: the args' method as one) | T, B | route | pointers, x_sub where T >= 2 | workspace
+//   _lin   struct (NULL: one sub-step) | act pair | NULL args | tableau (as _sub) | T, B | route | pointers, x_sub where substeps > 1 and
+//          T >= 2 | workspace
+//   T, B: a DAE call with flags needs T >= 2.  Route (k5_route_ok): kernel AUTO / GENERIC, no saved_* rows, flags within the struct's and
+//   only next to an ELU(1) pair, the recipe dims and the LDS fit of the family's build.  Pointers: the teacher-forcing rows among them.
+//   The DAE's _act family takes psnode_dae_bwd_args_f32, the others the _tf struct: its _sub with substeps == 1 and no tableau goes to _tf
+//   (ELU(1) pair) or refuses flags (PSNODE_ERR_UNSUPPORTED, before the method is looked at) and goes to _act with the base args.
 namespace {
+enum K5Family { kFamTf, kFamAct, kFamRk, kFamSub, kFamLin };
 constexpr uint32_t kTfFlags = PSNODE_FLAG_INPUT_TRUE_X | PSNODE_FLAG_INPUT_TRUE_I;
-bool dae_tf_ok(const psnode_dae_bwd_tf_args_f32* a) {
-    const psnode_dae_bwd_args_f32& b = a->base;
-    if ((a->flags & ~kTfFlags) || (b.kernel != PSNODE_KERNEL_AUTO && b.kernel != PSNODE_KERNEL_GENERIC)) return false;
-    return !b.saved_act && !b.saved_xstage && !b.saved_ae_act && !b.saved_ev_act && !b.saved_ev_i && dae_generic_ok(&b) != 0;
-}
-}  // namespace
 
-extern "C" int32_t psnode_dae_backward_tf_supported(const psnode_dae_bwd_tf_args_f32* a) {
-    if (!a) return 0;
-    if (a->flags == 0) return psnode_dae_backward_supported(&a->base);
-    return method_ok(&a->base) && dae_tf_ok(a);
+// the difference between the three args structs: the base call, the flags and the ones the struct knows, the AE, the plain entry points
+const psnode_ode_bwd_args_f32& base(const psnode_ode_bwd_args_f32& a) { return a; }
+const psnode_dae_bwd_args_f32& base(const psnode_dae_bwd_args_f32& a) { return a; }
+const psnode_dae_bwd_args_f32& base(const psnode_dae_bwd_tf_args_f32& a) { return a.base; }
+uint32_t tf_flags(const psnode_ode_bwd_args_f32& a) { return a.flags; }
+uint32_t tf_flags(const psnode_dae_bwd_args_f32&) { return 0; }
+uint32_t tf_flags(const psnode_dae_bwd_tf_args_f32& a) { return a.flags; }
+uint32_t tf_mask(const psnode_ode_bwd_args_f32&) { return PSNODE_FLAG_INPUT_TRUE_X; }
+uint32_t tf_mask(const psnode_dae_bwd_args_f32&) { return 0; }
+uint32_t tf_mask(const psnode_dae_bwd_tf_args_f32&) { return kTfFlags; }
+const psnode_mlp_f32* ae_of(const psnode_ode_bwd_args_f32&) { return nullptr; }
+const psnode_mlp_f32* ae_of(const psnode_dae_bwd_args_f32& a) { return &a.ae; }
+int generic_ok(const psnode_ode_bwd_args_f32* a, bool pre, bool lin) { return ode_generic_ok(a, pre, lin); }
+int generic_ok(const psnode_dae_bwd_args_f32* a, bool pre, bool lin) { return dae_generic_ok(a, pre, lin); }
+int backward_elu1(const psnode_ode_bwd_args_f32* a, void* ws, size_t bytes, void* stream) { return psnode_ode_backward_f32(a, ws, bytes, stream); }
+int backward_elu1(const psnode_dae_bwd_args_f32* a, void* ws, size_t bytes, void* stream) { return psnode_dae_backward_f32(a, ws, bytes, stream); }
+int backward_elu1(const psnode_dae_bwd_tf_args_f32* a, void* ws, size_t bytes, void* stream) { return psnode_dae_backward_tf_f32(a, ws, bytes, stream); }
+int supported_elu1(const psnode_ode_bwd_args_f32* a) { return psnode_ode_backward_supported(a); }
+int supported_elu1(const psnode_dae_bwd_args_f32* a) { return psnode_dae_backward_supported(a); }
+int supported_elu1(const psnode_dae_bwd_tf_args_f32* a) { return psnode_dae_backward_tf_supported(a); }
+// the saved_* rows a family refuses: every one, but the _act family's call only the ones below kSavedAll and its query saved_act alone
+enum Saved { kSavedAct, kSavedActCall, kSavedAll };
+bool saved_rows(const psnode_ode_bwd_args_f32& a, Saved s) { return a.saved_act || (s != kSavedAct && a.saved_xstage); }
+bool saved_rows(const psnode_dae_bwd_args_f32& a, Saved s) {
+    return a.saved_act || (s != kSavedAct && (a.saved_xstage || a.saved_ae_act)) || (s == kSavedAll && (a.saved_ev_act || a.saved_ev_i));
+}
+// the dataset rows of the flags set, next to the pointers of the base call; the call struct with them
+bool ptrs_ok(const psnode_dae_bwd_tf_args_f32* a) {
+    if (((a->flags & PSNODE_FLAG_INPUT_TRUE_X) && !a->x_true) || ((a->flags & PSNODE_FLAG_INPUT_TRUE_I) && !a->i_true)) return false;
+    return ptrs_ok(&a->base);
+}
+GenericBwdCall generic_bwd_call(const psnode_dae_bwd_tf_args_f32& a) {
+    GenericBwdCall c = generic_bwd_call(a.base);
+    c.flags = a.flags; c.xt = a.x_true; c.it = a.i_true;
+    return c;
 }
 
-extern "C" size_t psnode_dae_backward_tf_workspace_bytes(const psnode_dae_bwd_tf_args_f32* a) {
-    if (!a) return 0;
-    if (a->flags == 0) return psnode_dae_backward_workspace_bytes(&a->base);
-    if (!psnode_dae_backward_tf_supported(a)) return 0;
-    return generic_bwd_workspace_floats(&a->base.de, &a->base.ae, a->base.B) * sizeof(float);
+template <class Args>
+bool k5_route_ok(K5Family fam, const Args& a, const ActPair& p, bool elu1, bool query) {
+    const auto& b = base(a);
+    const uint32_t flags = tf_flags(a);
+    if (b.kernel != PSNODE_KERNEL_AUTO && b.kernel != PSNODE_KERNEL_GENERIC) return false;
+    if ((flags & ~tf_mask(a)) || (flags && !elu1)) return false;      // (teacher forcing: ELU(1) only)
+    if (saved_rows(b, fam != kFamAct ? kSavedAll : query ? kSavedAct : kSavedActCall)) return false;
+    // the fit of the build: _tf runs the ELU(1) build, _act the act or the pre build, the others keep the pre-activations for every kind
+    const bool pre = fam == kFamAct ? act_pair_pre(p) : fam != kFamTf;
+    return generic_ok(&b, pre, fam == kFamLin) != 0;
+}
+// the struct of a _sub / _lin call; substeps == 1 on _sub is the family without sub-steps
+int k5_substeps(K5Family& fam, const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub) {
+    if (fam != kFamSub && !(fam == kFamLin && sub)) return PSNODE_OK;
+    const int rc = substeps_check(sub);
+    if (rc == PSNODE_OK && fam == kFamSub && sub->substeps == 1) fam = tab ? kFamRk : kFamAct;
+    return rc;
 }
 
-extern "C" int32_t psnode_dae_backward_tf_f32(const psnode_dae_bwd_tf_args_f32* a, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!a) return PSNODE_ERR_NULL;
-    if (a->flags == 0) return psnode_dae_backward_f32(&a->base, workspace, workspace_bytes, stream);
-    const psnode_dae_bwd_args_f32* b = &a->base;
-    const int rc = check_call(b);
-    if (rc) return rc;
-    if (b->T < 2) return PSNODE_ERR_DIMS;
-    if (!dae_tf_ok(a)) return PSNODE_ERR_UNSUPPORTED;
-    if (!ptrs_ok(b)) return PSNODE_ERR_NULL;
-    if (((a->flags & PSNODE_FLAG_INPUT_TRUE_X) && !a->x_true) || ((a->flags & PSNODE_FLAG_INPUT_TRUE_I) && !a->i_true)) return PSNODE_ERR_NULL;
-    if (!workspace_ok(workspace, workspace_bytes, psnode_dae_backward_tf_workspace_bytes(a))) return PSNODE_ERR_WORKSPACE;
-    GenericBwdCall c = generic_bwd_call(*b);
-    c.flags = a->flags; c.xt = a->x_true; c.it = a->i_true;
-    return generic_backward(c, nullptr, workspace, stream);
-}
-
-// ---- hidden-layer activations other than ELU(1) (include/psnode_hip.h, psnode_act_f32): K5 only, no teacher forcing, no saved rows.
-// The act is checked first and an ELU(1) pair forwarded to the entry point above; then NULL args -> method -> dims -> unsupported ->
-// pointers -> workspace, as there.
-extern "C" int32_t psnode_ode_backward_act_supported(const psnode_ode_bwd_args_f32* a, const psnode_act_f32* de_act) {
+template <class Args>
+int k5_backward(K5Family fam, const Args* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act, const psnode_rk_tableau_f32* tab,
+                const psnode_substeps_f32* sub, void* workspace, size_t workspace_bytes, void* stream) {
+    constexpr bool tf_struct = std::is_same<Args, psnode_dae_bwd_tf_args_f32>::value;
     ActPair p;
-    bool elu1 = true;
-    if (act_pair(de_act, nullptr, p, elu1)) return 0;
-    if (elu1) return psnode_ode_backward_supported(a);
-    return method_ok(a) && act_bwd_ok(a->kernel, a->flags, a->saved_act) && ode_generic_ok(a, act_pair_pre(p));
-}
-
-extern "C" int32_t psnode_ode_backward_act_f32(const psnode_ode_bwd_args_f32* a, const psnode_act_f32* de_act, void* workspace,
-                                               size_t workspace_bytes, void* stream) {
-    ActPair p;
-    bool elu1 = true;
-    int rc = act_pair(de_act, nullptr, p, elu1);
-    if (rc) return rc;
-    if (elu1) return psnode_ode_backward_f32(a, workspace, workspace_bytes, stream);
-    rc = check_call(a);
-    if (rc) return rc;
-    if (!act_bwd_ok(a->kernel, a->flags, a->saved_act) || a->saved_xstage || !ode_generic_ok(a, act_pair_pre(p))) return PSNODE_ERR_UNSUPPORTED;
-    if (!ptrs_ok(a)) return PSNODE_ERR_NULL;
-    if (!workspace_ok(workspace, workspace_bytes, generic_bwd_workspace_floats(&a->de, nullptr, a->B) * sizeof(float))) return PSNODE_ERR_WORKSPACE;
-    return generic_backward(generic_bwd_call(*a), &p, workspace, stream);
-}
-
-extern "C" int32_t psnode_dae_backward_act_supported(const psnode_dae_bwd_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act) {
-    ActPair p;
-    bool elu1 = true;
-    if (act_pair(de_act, ae_act, p, elu1)) return 0;
-    if (elu1) return psnode_dae_backward_supported(a);
-    return method_ok(a) && act_bwd_ok(a->kernel, 0, a->saved_act) && dae_generic_ok(a, act_pair_pre(p));
-}
-
-extern "C" int32_t psnode_dae_backward_act_f32(const psnode_dae_bwd_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
-                                               void* workspace, size_t workspace_bytes, void* stream) {
-    ActPair p;
-    bool elu1 = true;
-    int rc = act_pair(de_act, ae_act, p, elu1);
-    if (rc) return rc;
-    if (elu1) return psnode_dae_backward_f32(a, workspace, workspace_bytes, stream);
-    rc = check_call(a);
-    if (rc) return rc;
-    if (!act_bwd_ok(a->kernel, 0, a->saved_act) || a->saved_xstage || a->saved_ae_act || !dae_generic_ok(a, act_pair_pre(p))) return PSNODE_ERR_UNSUPPORTED;
-    if (!ptrs_ok(a)) return PSNODE_ERR_NULL;
-    if (!workspace_ok(workspace, workspace_bytes, generic_bwd_workspace_floats(&a->de, &a->ae, a->B) * sizeof(float))) return PSNODE_ERR_WORKSPACE;
-    return generic_backward(generic_bwd_call(*a), &p, workspace, stream);
-}
-
-// ---- explicit Runge-Kutta tableaus (include/psnode_hip.h, psnode_rk_tableau_f32): K5's tableau build alone (every activation kind; it
-// keeps the pre-activations, so the pre fit of generic_bwd_fits answers for the shape).  The act is checked first, then the tableau; `method` is not
-// read; then NULL args -> dims -> unsupported -> pointers -> workspace, as above.
-namespace {
-bool rk_ode_ok(const psnode_ode_bwd_args_f32* a, bool elu1, bool lin = false) {      // lin: the linear-externals build's own LDS fit
-    if ((a->kernel != PSNODE_KERNEL_AUTO && a->kernel != PSNODE_KERNEL_GENERIC) || a->saved_act || a->saved_xstage) return false;
-    if ((a->flags & ~PSNODE_FLAG_INPUT_TRUE_X) || (a->flags && !elu1)) return false;
-    const psnode_mlp_f32& m = a->de;
-    if (a->x_dim < 1 || a->z_dim < 0 || m.n_layers < 1 || m.n_layers > kMaxLayers) return false;
-    if (m.in_dim != 3 * (a->x_dim + a->z_dim) || m.out_dim[m.n_layers - 1] != a->x_dim) return false;
-    return generic_bwd_fits(&a->de, nullptr, a->x_dim, a->z_dim, 0, 0, true, lin) != 0;
-}
-bool rk_dae_ok(const psnode_dae_bwd_tf_args_f32* a, bool elu1, bool lin = false) {
-    const psnode_dae_bwd_args_f32& b = a->base;
-    if ((a->flags & ~kTfFlags) || (a->flags && !elu1) || (b.kernel != PSNODE_KERNEL_AUTO && b.kernel != PSNODE_KERNEL_GENERIC)) return false;
-    if (b.saved_act || b.saved_xstage || b.saved_ae_act || b.saved_ev_act || b.saved_ev_i) return false;
-    if (b.x_dim < 1 || b.z_dim < 0 || b.v_dim < 0 || b.i_dim < 1) return false;
-    const int n = b.x_dim + b.z_dim + b.v_dim + b.i_dim;
-    const psnode_mlp_f32 &d = b.de, &g = b.ae;
-    if (d.n_layers < 1 || d.n_layers > kMaxLayers || g.n_layers < 1 || g.n_layers > kMaxLayers) return false;
-    if (d.in_dim != 3 * n || d.out_dim[d.n_layers - 1] != b.x_dim) return false;
-    if (g.in_dim != n + b.x_dim + b.z_dim + b.v_dim || g.out_dim[g.n_layers - 1] != b.i_dim) return false;
-    return generic_bwd_fits(&b.de, &b.ae, b.x_dim, b.z_dim, b.v_dim, b.i_dim, true, lin) != 0;
-}
-}  // namespace
-
-extern "C" int32_t psnode_ode_backward_rk_supported(const psnode_ode_bwd_args_f32* a, const psnode_act_f32* de_act,
-                                                    const psnode_rk_tableau_f32* tab) {
-    ActPair p;
-    bool elu1 = true;
-    if (!a || act_pair(de_act, nullptr, p, elu1) || rk_tableau_check(tab)) return 0;
-    return rk_ode_ok(a, elu1);
-}
-
-extern "C" int32_t psnode_ode_backward_rk_f32(const psnode_ode_bwd_args_f32* a, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
-                                              void* workspace, size_t workspace_bytes, void* stream) {
-    ActPair p;
-    bool elu1 = true;
-    int rc = act_pair(de_act, nullptr, p, elu1);
-    if (rc) return rc;
-    rc = rk_tableau_check(tab);
-    if (rc) return rc;
-    if (!a) return PSNODE_ERR_NULL;
-    if (a->T < 1 || a->B < 1) return PSNODE_ERR_DIMS;
-    if (!rk_ode_ok(a, elu1)) return PSNODE_ERR_UNSUPPORTED;
-    if (!ptrs_ok(a)) return PSNODE_ERR_NULL;
-    if (!workspace_ok(workspace, workspace_bytes, generic_bwd_workspace_floats(&a->de, nullptr, a->B) * sizeof(float))) return PSNODE_ERR_WORKSPACE;
-    GenericBwdCall c = generic_bwd_call(*a);
-    c.rk = tab;
-    return generic_backward(c, &p, workspace, stream);
-}
-
-extern "C" int32_t psnode_dae_backward_rk_supported(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act,
-                                                    const psnode_act_f32* ae_act, const psnode_rk_tableau_f32* tab) {
-    ActPair p;
-    bool elu1 = true;
-    if (!a || act_pair(de_act, ae_act, p, elu1) || rk_tableau_check(tab)) return 0;
-    return rk_dae_ok(a, elu1);
-}
-
-extern "C" size_t psnode_dae_backward_rk_workspace_bytes(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act,
-                                                         const psnode_act_f32* ae_act, const psnode_rk_tableau_f32* tab) {
-    if (!psnode_dae_backward_rk_supported(a, de_act, ae_act, tab)) return 0;
-    return generic_bwd_workspace_floats(&a->base.de, &a->base.ae, a->base.B) * sizeof(float);
-}
-
-extern "C" int32_t psnode_dae_backward_rk_f32(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
-                                              const psnode_rk_tableau_f32* tab, void* workspace, size_t workspace_bytes, void* stream) {
-    ActPair p;
-    bool elu1 = true;
-    int rc = act_pair(de_act, ae_act, p, elu1);
-    if (rc) return rc;
-    rc = rk_tableau_check(tab);
-    if (rc) return rc;
-    if (!a) return PSNODE_ERR_NULL;
-    const psnode_dae_bwd_args_f32* b = &a->base;
-    if (b->T < 1 || b->B < 1 || (a->flags && b->T < 2)) return PSNODE_ERR_DIMS;
-    if (!rk_dae_ok(a, elu1)) return PSNODE_ERR_UNSUPPORTED;
-    if (!ptrs_ok(b)) return PSNODE_ERR_NULL;
-    if (((a->flags & PSNODE_FLAG_INPUT_TRUE_X) && !a->x_true) || ((a->flags & PSNODE_FLAG_INPUT_TRUE_I) && !a->i_true)) return PSNODE_ERR_NULL;
-    if (!workspace_ok(workspace, workspace_bytes, psnode_dae_backward_rk_workspace_bytes(a, de_act, ae_act, tab))) return PSNODE_ERR_WORKSPACE;
-    GenericBwdCall c = generic_bwd_call(*b);
-    c.flags = a->flags; c.xt = a->x_true; c.it = a->i_true; c.rk = tab;
-    return generic_backward(c, &p, workspace, stream);
-}
-
-// ---- sub-steps per grid interval (include/psnode_hip.h, psnode_substeps_f32): K5's sub-step build alone, under the rules of the tableau
-// build.  The struct is checked first (substeps == 1 leaves for the _rk / _act / _tf entry point there), then the act, the tableau (NULL:
-// the args' method as one); then NULL args -> dims -> unsupported -> pointers (x_sub among them) -> workspace, as above.
-extern "C" int32_t psnode_ode_backward_sub_supported(const psnode_ode_bwd_args_f32* a, const psnode_act_f32* de_act,
-                                                     const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub) {
-    if (!a || substeps_check(sub)) return 0;
-    if (sub->substeps == 1) return tab ? psnode_ode_backward_rk_supported(a, de_act, tab) : psnode_ode_backward_act_supported(a, de_act);
     psnode_rk_tableau_f32 t;
-    if (sub_tableau(tab, a->method, t)) return 0;
-    return psnode_ode_backward_rk_supported(a, de_act, &t);
-}
-
-extern "C" int32_t psnode_ode_backward_sub_f32(const psnode_ode_bwd_args_f32* a, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
-                                               const psnode_substeps_f32* sub, void* workspace, size_t workspace_bytes, void* stream) {
-    int rc = substeps_check(sub);
-    if (rc) return rc;
-    if (sub->substeps == 1)
-        return tab ? psnode_ode_backward_rk_f32(a, de_act, tab, workspace, workspace_bytes, stream)
-                   : psnode_ode_backward_act_f32(a, de_act, workspace, workspace_bytes, stream);
-    ActPair p;
     bool elu1 = true;
-    rc = act_pair(de_act, nullptr, p, elu1);
+    int rc = k5_substeps(fam, tab, sub);
+    if (rc == PSNODE_OK) rc = act_pair(de_act, ae_act, p, elu1);
     if (rc) return rc;
-    if (!a) return PSNODE_ERR_NULL;
-    psnode_rk_tableau_f32 t;
-    rc = sub_tableau(tab, a->method, t);
-    if (rc) return rc;
-    if (a->T < 1 || a->B < 1) return PSNODE_ERR_DIMS;
-    if (!rk_ode_ok(a, elu1)) return PSNODE_ERR_UNSUPPORTED;
-    if (!ptrs_ok(a) || (a->T >= 2 && !sub->x_sub)) return PSNODE_ERR_NULL;
-    if (!workspace_ok(workspace, workspace_bytes, generic_bwd_workspace_floats(&a->de, nullptr, a->B) * sizeof(float))) return PSNODE_ERR_WORKSPACE;
-    GenericBwdCall c = generic_bwd_call(*a);
-    c.rk = &t; c.substeps = sub->substeps; c.x_sub = sub->x_sub;
-    return generic_backward(c, &p, workspace, stream);
-}
-
-extern "C" int32_t psnode_dae_backward_sub_supported(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act,
-                                                     const psnode_act_f32* ae_act, const psnode_rk_tableau_f32* tab,
-                                                     const psnode_substeps_f32* sub) {
-    if (!a || substeps_check(sub)) return 0;
-    if (sub->substeps == 1 && tab) return psnode_dae_backward_rk_supported(a, de_act, ae_act, tab);
-    if (sub->substeps == 1) {
-        ActPair p;
-        bool elu1 = true;
-        if (act_pair(de_act, ae_act, p, elu1)) return 0;
-        if (elu1) return psnode_dae_backward_tf_supported(a);
-        return a->flags == 0 && psnode_dae_backward_act_supported(&a->base, de_act, ae_act);
+    if (fam == kFamAct && elu1) return backward_elu1(a, workspace, workspace_bytes, stream);
+    if constexpr (tf_struct) {
+        if (fam == kFamAct) {      // (_sub, substeps == 1, no tableau)
+            if (!a) return PSNODE_ERR_NULL;
+            if (a->flags) return PSNODE_ERR_UNSUPPORTED;
+            return k5_backward(kFamAct, &a->base, de_act, ae_act, nullptr, nullptr, workspace, workspace_bytes, stream);
+        }
     }
-    psnode_rk_tableau_f32 t;
-    if (sub_tableau(tab, a->base.method, t)) return 0;
-    return psnode_dae_backward_rk_supported(a, de_act, ae_act, &t);
+    if (fam == kFamRk) rc = rk_tableau_check(tab);
+    if (rc) return rc;
+    if (!a) return PSNODE_ERR_NULL;
+    const auto& b = base(*a);
+    rc = fam <= kFamAct ? (method_ok(&b) ? PSNODE_OK : PSNODE_ERR_METHOD) : sub_tableau(tab, b.method, t);
+    if (rc) return rc;
+    if (b.T < 1 || b.B < 1 || (tf_struct && tf_flags(*a) && b.T < 2)) return PSNODE_ERR_DIMS;
+    if (!k5_route_ok(fam, *a, p, elu1, false)) return PSNODE_ERR_UNSUPPORTED;
+    const int nsub = fam >= kFamSub && sub ? sub->substeps : 1;
+    if (!ptrs_ok(a) || (nsub > 1 && b.T >= 2 && !sub->x_sub)) return PSNODE_ERR_NULL;
+    if (!workspace_ok(workspace, workspace_bytes, generic_bwd_workspace_floats(&b.de, ae_of(b), b.B) * sizeof(float))) return PSNODE_ERR_WORKSPACE;
+    GenericBwdCall c = generic_bwd_call(*a);
+    if (fam >= kFamRk) c.rk = &t;
+    if (fam >= kFamSub) { c.substeps = nsub; c.x_sub = sub ? sub->x_sub : nullptr; c.lin = fam == kFamLin; }
+    return generic_backward(c, fam == kFamTf ? nullptr : &p, workspace, stream);
 }
 
-extern "C" size_t psnode_dae_backward_sub_workspace_bytes(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act,
-                                                          const psnode_act_f32* ae_act, const psnode_rk_tableau_f32* tab,
-                                                          const psnode_substeps_f32* sub) {
-    if (!psnode_dae_backward_sub_supported(a, de_act, ae_act, tab, sub)) return 0;
-    if (sub->substeps == 1 && !tab) {
+template <class Args>
+int k5_supported(K5Family fam, const Args* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act, const psnode_rk_tableau_f32* tab,
+                 const psnode_substeps_f32* sub) {
+    ActPair p;
+    psnode_rk_tableau_f32 t;
+    bool elu1 = true;
+    if (!a || k5_substeps(fam, tab, sub) || act_pair(de_act, ae_act, p, elu1)) return 0;
+    if (fam == kFamAct && elu1) return supported_elu1(a);
+    if constexpr (std::is_same<Args, psnode_dae_bwd_tf_args_f32>::value) {
+        if (fam == kFamAct) return a->flags == 0 && k5_supported(kFamAct, &a->base, de_act, ae_act, nullptr, nullptr);
+    }
+    const auto& b = base(*a);
+    if (fam <= kFamAct ? !method_ok(&b) : (fam == kFamRk && !tab) || sub_tableau(tab, b.method, t)) return 0;
+    return k5_route_ok(fam, *a, p, elu1, true);
+}
+
+// (DAE: the ODE's sizes come from psnode_ode_backward_workspace_bytes)
+size_t k5_workspace_bytes(K5Family fam, const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                          const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub) {
+    if (!k5_supported(fam, a, de_act, ae_act, tab, sub)) return 0;
+    if (fam == kFamSub && sub->substeps == 1 && !tab) {      // the entry point that call goes to
         ActPair p;
         bool elu1 = true;
         act_pair(de_act, ae_act, p, elu1);
@@ -451,112 +347,102 @@ extern "C" size_t psnode_dae_backward_sub_workspace_bytes(const psnode_dae_bwd_t
     }
     return generic_bwd_workspace_floats(&a->base.de, &a->base.ae, a->base.B) * sizeof(float);
 }
+}  // namespace
 
+// ---- the K5 families (the table of their checks: above).  Each wrapper names its family and forwards; flags == 0 on _tf is the plain call.
+extern "C" int32_t psnode_dae_backward_tf_supported(const psnode_dae_bwd_tf_args_f32* a) {
+    if (a && a->flags == 0) return psnode_dae_backward_supported(&a->base);
+    return k5_supported(kFamTf, a, nullptr, nullptr, nullptr, nullptr);
+}
+extern "C" size_t psnode_dae_backward_tf_workspace_bytes(const psnode_dae_bwd_tf_args_f32* a) {
+    if (a && a->flags == 0) return psnode_dae_backward_workspace_bytes(&a->base);
+    return k5_workspace_bytes(kFamTf, a, nullptr, nullptr, nullptr, nullptr);
+}
+extern "C" int32_t psnode_dae_backward_tf_f32(const psnode_dae_bwd_tf_args_f32* a, void* workspace, size_t workspace_bytes, void* stream) {
+    if (a && a->flags == 0) return psnode_dae_backward_f32(&a->base, workspace, workspace_bytes, stream);
+    return k5_backward(kFamTf, a, nullptr, nullptr, nullptr, nullptr, workspace, workspace_bytes, stream);
+}
+
+extern "C" int32_t psnode_ode_backward_act_supported(const psnode_ode_bwd_args_f32* a, const psnode_act_f32* de_act) {
+    return k5_supported(kFamAct, a, de_act, nullptr, nullptr, nullptr);
+}
+extern "C" int32_t psnode_ode_backward_act_f32(const psnode_ode_bwd_args_f32* a, const psnode_act_f32* de_act, void* workspace,
+                                               size_t workspace_bytes, void* stream) {
+    return k5_backward(kFamAct, a, de_act, nullptr, nullptr, nullptr, workspace, workspace_bytes, stream);
+}
+extern "C" int32_t psnode_dae_backward_act_supported(const psnode_dae_bwd_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act) {
+    return k5_supported(kFamAct, a, de_act, ae_act, nullptr, nullptr);
+}
+extern "C" int32_t psnode_dae_backward_act_f32(const psnode_dae_bwd_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                               void* workspace, size_t workspace_bytes, void* stream) {
+    return k5_backward(kFamAct, a, de_act, ae_act, nullptr, nullptr, workspace, workspace_bytes, stream);
+}
+
+extern "C" int32_t psnode_ode_backward_rk_supported(const psnode_ode_bwd_args_f32* a, const psnode_act_f32* de_act,
+                                                    const psnode_rk_tableau_f32* tab) {
+    return k5_supported(kFamRk, a, de_act, nullptr, tab, nullptr);
+}
+extern "C" int32_t psnode_ode_backward_rk_f32(const psnode_ode_bwd_args_f32* a, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
+                                              void* workspace, size_t workspace_bytes, void* stream) {
+    return k5_backward(kFamRk, a, de_act, nullptr, tab, nullptr, workspace, workspace_bytes, stream);
+}
+extern "C" int32_t psnode_dae_backward_rk_supported(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act,
+                                                    const psnode_act_f32* ae_act, const psnode_rk_tableau_f32* tab) {
+    return k5_supported(kFamRk, a, de_act, ae_act, tab, nullptr);
+}
+extern "C" size_t psnode_dae_backward_rk_workspace_bytes(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act,
+                                                         const psnode_act_f32* ae_act, const psnode_rk_tableau_f32* tab) {
+    return k5_workspace_bytes(kFamRk, a, de_act, ae_act, tab, nullptr);
+}
+extern "C" int32_t psnode_dae_backward_rk_f32(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                              const psnode_rk_tableau_f32* tab, void* workspace, size_t workspace_bytes, void* stream) {
+    return k5_backward(kFamRk, a, de_act, ae_act, tab, nullptr, workspace, workspace_bytes, stream);
+}
+
+extern "C" int32_t psnode_ode_backward_sub_supported(const psnode_ode_bwd_args_f32* a, const psnode_act_f32* de_act,
+                                                     const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub) {
+    return k5_supported(kFamSub, a, de_act, nullptr, tab, sub);
+}
+extern "C" int32_t psnode_ode_backward_sub_f32(const psnode_ode_bwd_args_f32* a, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
+                                               const psnode_substeps_f32* sub, void* workspace, size_t workspace_bytes, void* stream) {
+    return k5_backward(kFamSub, a, de_act, nullptr, tab, sub, workspace, workspace_bytes, stream);
+}
+extern "C" int32_t psnode_dae_backward_sub_supported(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act,
+                                                     const psnode_act_f32* ae_act, const psnode_rk_tableau_f32* tab,
+                                                     const psnode_substeps_f32* sub) {
+    return k5_supported(kFamSub, a, de_act, ae_act, tab, sub);
+}
+extern "C" size_t psnode_dae_backward_sub_workspace_bytes(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act,
+                                                          const psnode_act_f32* ae_act, const psnode_rk_tableau_f32* tab,
+                                                          const psnode_substeps_f32* sub) {
+    return k5_workspace_bytes(kFamSub, a, de_act, ae_act, tab, sub);
+}
 extern "C" int32_t psnode_dae_backward_sub_f32(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
                                                const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, void* workspace,
                                                size_t workspace_bytes, void* stream) {
-    int rc = substeps_check(sub);
-    if (rc) return rc;
-    ActPair p;
-    bool elu1 = true;
-    if (sub->substeps == 1) {
-        if (tab) return psnode_dae_backward_rk_f32(a, de_act, ae_act, tab, workspace, workspace_bytes, stream);
-        rc = act_pair(de_act, ae_act, p, elu1);
-        if (rc) return rc;
-        if (elu1) return psnode_dae_backward_tf_f32(a, workspace, workspace_bytes, stream);
-        if (!a) return PSNODE_ERR_NULL;
-        if (a->flags) return PSNODE_ERR_UNSUPPORTED;      // (teacher forcing: ELU(1) only)
-        return psnode_dae_backward_act_f32(&a->base, de_act, ae_act, workspace, workspace_bytes, stream);
-    }
-    rc = act_pair(de_act, ae_act, p, elu1);
-    if (rc) return rc;
-    if (!a) return PSNODE_ERR_NULL;
-    const psnode_dae_bwd_args_f32* b = &a->base;
-    psnode_rk_tableau_f32 t;
-    rc = sub_tableau(tab, b->method, t);
-    if (rc) return rc;
-    if (b->T < 1 || b->B < 1 || (a->flags && b->T < 2)) return PSNODE_ERR_DIMS;
-    if (!rk_dae_ok(a, elu1)) return PSNODE_ERR_UNSUPPORTED;
-    if (!ptrs_ok(b) || (b->T >= 2 && !sub->x_sub)) return PSNODE_ERR_NULL;
-    if (((a->flags & PSNODE_FLAG_INPUT_TRUE_X) && !a->x_true) || ((a->flags & PSNODE_FLAG_INPUT_TRUE_I) && !a->i_true)) return PSNODE_ERR_NULL;
-    if (!workspace_ok(workspace, workspace_bytes, generic_bwd_workspace_floats(&b->de, &b->ae, b->B) * sizeof(float))) return PSNODE_ERR_WORKSPACE;
-    GenericBwdCall c = generic_bwd_call(*b);
-    c.flags = a->flags; c.xt = a->x_true; c.it = a->i_true; c.rk = &t; c.substeps = sub->substeps; c.x_sub = sub->x_sub;
-    return generic_backward(c, &p, workspace, stream);
+    return k5_backward(kFamSub, a, de_act, ae_act, tab, sub, workspace, workspace_bytes, stream);
 }
 
-// ---- linearly interpolated externals (include/psnode_hip.h, "Linear interpolation of externals"): K5's linear-externals build alone, for
-// every substeps >= 1 (a NULL struct is one sub-step).  The struct is checked first, then the act, the tableau (NULL: the args' method as
-// one); then NULL args -> dims -> unsupported -> pointers (x_sub among them) -> workspace, as above.
 extern "C" int32_t psnode_ode_backward_lin_supported(const psnode_ode_bwd_args_f32* a, const psnode_act_f32* de_act,
                                                      const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub) {
-    ActPair p;
-    bool elu1 = true;
-    psnode_rk_tableau_f32 t;
-    if (!a || (sub && substeps_check(sub)) || act_pair(de_act, nullptr, p, elu1) || sub_tableau(tab, a->method, t)) return 0;
-    return rk_ode_ok(a, elu1, true);
+    return k5_supported(kFamLin, a, de_act, nullptr, tab, sub);
 }
-
 extern "C" int32_t psnode_ode_backward_lin_f32(const psnode_ode_bwd_args_f32* a, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
                                                const psnode_substeps_f32* sub, void* workspace, size_t workspace_bytes, void* stream) {
-    int rc = sub ? substeps_check(sub) : PSNODE_OK;
-    if (rc) return rc;
-    const int nsub = sub ? sub->substeps : 1;
-    ActPair p;
-    bool elu1 = true;
-    rc = act_pair(de_act, nullptr, p, elu1);
-    if (rc) return rc;
-    if (!a) return PSNODE_ERR_NULL;
-    psnode_rk_tableau_f32 t;
-    rc = sub_tableau(tab, a->method, t);
-    if (rc) return rc;
-    if (a->T < 1 || a->B < 1) return PSNODE_ERR_DIMS;
-    if (!rk_ode_ok(a, elu1, true)) return PSNODE_ERR_UNSUPPORTED;
-    if (!ptrs_ok(a) || (nsub > 1 && a->T >= 2 && !sub->x_sub)) return PSNODE_ERR_NULL;
-    if (!workspace_ok(workspace, workspace_bytes, generic_bwd_workspace_floats(&a->de, nullptr, a->B) * sizeof(float))) return PSNODE_ERR_WORKSPACE;
-    GenericBwdCall c = generic_bwd_call(*a);
-    c.rk = &t; c.substeps = nsub; c.x_sub = sub ? sub->x_sub : nullptr; c.lin = true;
-    return generic_backward(c, &p, workspace, stream);
+    return k5_backward(kFamLin, a, de_act, nullptr, tab, sub, workspace, workspace_bytes, stream);
 }
-
 extern "C" int32_t psnode_dae_backward_lin_supported(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act,
                                                      const psnode_act_f32* ae_act, const psnode_rk_tableau_f32* tab,
                                                      const psnode_substeps_f32* sub) {
-    ActPair p;
-    bool elu1 = true;
-    psnode_rk_tableau_f32 t;
-    if (!a || (sub && substeps_check(sub)) || act_pair(de_act, ae_act, p, elu1) || sub_tableau(tab, a->base.method, t)) return 0;
-    return rk_dae_ok(a, elu1, true);
+    return k5_supported(kFamLin, a, de_act, ae_act, tab, sub);
 }
-
 extern "C" size_t psnode_dae_backward_lin_workspace_bytes(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act,
                                                           const psnode_act_f32* ae_act, const psnode_rk_tableau_f32* tab,
                                                           const psnode_substeps_f32* sub) {
-    if (!psnode_dae_backward_lin_supported(a, de_act, ae_act, tab, sub)) return 0;
-    return generic_bwd_workspace_floats(&a->base.de, &a->base.ae, a->base.B) * sizeof(float);
+    return k5_workspace_bytes(kFamLin, a, de_act, ae_act, tab, sub);
 }
-
 extern "C" int32_t psnode_dae_backward_lin_f32(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
                                                const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, void* workspace,
                                                size_t workspace_bytes, void* stream) {
-    int rc = sub ? substeps_check(sub) : PSNODE_OK;
-    if (rc) return rc;
-    const int nsub = sub ? sub->substeps : 1;
-    ActPair p;
-    bool elu1 = true;
-    rc = act_pair(de_act, ae_act, p, elu1);
-    if (rc) return rc;
-    if (!a) return PSNODE_ERR_NULL;
-    const psnode_dae_bwd_args_f32* b = &a->base;
-    psnode_rk_tableau_f32 t;
-    rc = sub_tableau(tab, b->method, t);
-    if (rc) return rc;
-    if (b->T < 1 || b->B < 1 || (a->flags && b->T < 2)) return PSNODE_ERR_DIMS;
-    if (!rk_dae_ok(a, elu1, true)) return PSNODE_ERR_UNSUPPORTED;
-    if (!ptrs_ok(b) || (nsub > 1 && b->T >= 2 && !sub->x_sub)) return PSNODE_ERR_NULL;
-    if (((a->flags & PSNODE_FLAG_INPUT_TRUE_X) && !a->x_true) || ((a->flags & PSNODE_FLAG_INPUT_TRUE_I) && !a->i_true)) return PSNODE_ERR_NULL;
-    if (!workspace_ok(workspace, workspace_bytes, generic_bwd_workspace_floats(&b->de, &b->ae, b->B) * sizeof(float))) return PSNODE_ERR_WORKSPACE;
-    GenericBwdCall c = generic_bwd_call(*b);
-    c.flags = a->flags; c.xt = a->x_true; c.it = a->i_true; c.rk = &t; c.substeps = nsub; c.x_sub = sub ? sub->x_sub : nullptr; c.lin = true;
-    return generic_backward(c, &p, workspace, stream);
+    return k5_backward(kFamLin, a, de_act, ae_act, tab, sub, workspace, workspace_bytes, stream);
 }

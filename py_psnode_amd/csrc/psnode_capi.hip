@@ -86,12 +86,17 @@ __global__ void event_table_kernel(long long n_steps, const float* clock, long l
 
 ViewDev view(const psnode_view_f32& v) { return ViewDev{v.ptr, v.stride_t, v.stride_b}; }
 
-// act: the hidden layers' activations of a non-ELU(1) call (K0 only), or nullptr; rk: the tableau of an _rk call (K0's tableau build, with
-// `act` always given), or nullptr; sub: the sub-steps of a _sub call (K0's sub-step build, with `act` and `rk` always given), or nullptr;
-// lin: a _lin call (K0's linear-externals build, with all three given)
+// What a K0 call carries beyond its args: the build of the generic kernel that runs it (psnode_generic_build.h) and that build's kernel
+// arguments.  The plain entry points pass K0Call{}: ELU(1), the args' method, one step per interval -- the only call the MFMA kernels take.
+struct K0Call {
+    enum Build { kElu1, kAct, kRk, kSub, kLin } build;      // kAct: the act or the pre build, by the pair's kinds
+    ActPair act;                   // every build but kElu1
+    psnode_rk_tableau_f32 rk;      // kRk, kSub, kLin: given, or the args' method written as one (sub_tableau)
+    SubDev sub;                    // kSub, kLin: sub-steps per grid interval and x_sub
+};
+
 int dispatch(IntegrateDev& d, bool dae, int kernel, const psnode_mlp_f32* de, const psnode_mlp_f32* ae, void* workspace,
-             size_t workspace_bytes, hipStream_t stream, const ActPair* act = nullptr, const psnode_rk_tableau_f32* rk = nullptr,
-             const SubDev* sub = nullptr, bool lin = false) {
+             size_t workspace_bytes, hipStream_t stream, const K0Call& call) {
     if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 255u)) return PSNODE_ERR_WORKSPACE;
     if (workspace_bytes < psnode_workspace_bytes(de, ae)) return PSNODE_ERR_WORKSPACE;
     float* ws = static_cast<float*>(workspace);
@@ -101,28 +106,24 @@ int dispatch(IntegrateDev& d, bool dae, int kernel, const psnode_mlp_f32* de, co
     if (dae && max_width(*ae) > d.maxw) d.maxw = max_width(*ae);
     d.maxo = max_out_width(*de, dae ? ae : nullptr);
 
-    const bool has_mfma = !act && (dae ? mfma_dae_supported(d) : mfma_ode_supported(d));
+    const bool has_mfma = call.build == K0Call::kElu1 && (dae ? mfma_dae_supported(d) : mfma_ode_supported(d));
     const bool want_mfma = kernel == PSNODE_KERNEL_MFMA || kernel == PSNODE_KERNEL_MFMA_TILE || kernel == PSNODE_KERNEL_MFMA_WAVE;
     if (want_mfma && !has_mfma) return PSNODE_ERR_UNSUPPORTED;
     if (kernel == PSNODE_KERNEL_MFMA_WAVE && !(dae ? mfma_x_dae_supported(d) : mfma_x_ode_supported(d))) return PSNODE_ERR_UNSUPPORTED;
     d.kern = kernel;
     const bool use_mfma = has_mfma && kernel != PSNODE_KERNEL_GENERIC;
     if (d.T < 1 || d.B < 1) return PSNODE_ERR_DIMS;
+    if (use_mfma) return launch_mfma(d, dae, ws, stream) == hipSuccess ? PSNODE_OK : PSNODE_ERR_HIP;
 
-    hipError_t e;
-    if (use_mfma) {
-        e = launch_mfma(d, dae, ws, stream);
-    } else {
-        if (generic_lds_bytes(d, dae, lin) > 160 * 1024) return PSNODE_ERR_UNSUPPORTED;
-        e = launch_pack_image(d.de, dae ? &d.ae : nullptr, d.xd, d.xd + d.zd + (dae ? d.vd + d.id : 0), d.zd + (dae ? d.vd : 0), stream);
-        if (e == hipSuccess && sub && lin)
-            e = launch_generic_lin(d, dae, *act, *rk, *sub, stream);
-        else if (e == hipSuccess && sub)
-            e = launch_generic_sub(d, dae, *act, *rk, *sub, stream);
-        else if (e == hipSuccess && rk)
-            e = launch_generic_rk(d, dae, *act, *rk, stream);
-        else if (e == hipSuccess)
-            e = !act ? launch_generic(d, dae, stream) : (act_pair_pre(*act) ? launch_generic_pre(d, dae, *act, stream) : launch_generic_act(d, dae, *act, stream));
+    if (generic_lds_bytes(d, dae, call.build == K0Call::kLin) > 160 * 1024) return PSNODE_ERR_UNSUPPORTED;
+    hipError_t e = launch_pack_image(d.de, dae ? &d.ae : nullptr, d.xd, d.xd + d.zd + (dae ? d.vd + d.id : 0), d.zd + (dae ? d.vd : 0), stream);
+    if (e != hipSuccess) return PSNODE_ERR_HIP;
+    switch (call.build) {
+        case K0Call::kElu1: e = launch_generic(d, dae, stream); break;
+        case K0Call::kAct: e = act_pair_pre(call.act) ? launch_generic_pre(d, dae, call.act, stream) : launch_generic_act(d, dae, call.act, stream); break;
+        case K0Call::kRk: e = launch_generic_rk(d, dae, call.act, call.rk, stream); break;
+        case K0Call::kSub: e = launch_generic_sub(d, dae, call.act, call.rk, call.sub, stream); break;
+        case K0Call::kLin: e = launch_generic_lin(d, dae, call.act, call.rk, call.sub, stream); break;
     }
     return e == hipSuccess ? PSNODE_OK : PSNODE_ERR_HIP;
 }
@@ -222,9 +223,92 @@ int fill_dae(const psnode_dae_args_f32* a, IntegrateDev& d) {
     return PSNODE_OK;
 }
 
-// what a non-ELU(1) act asks of the call besides the dims: K0 (AUTO / GENERIC), no training side outputs
-bool act_call_ok(int kernel, const void* save_act) {
-    return (kernel == PSNODE_KERNEL_AUTO || kernel == PSNODE_KERNEL_GENERIC) && !save_act;
+// ---- The K0 entry-point families psnode_{ode,dae}_integrate_{act,rk,sub,lin}_*: one checked call path (k0_integrate) and one query
+// (k0_supported).  Order of checks per family, which is the order of the statuses of a call that is wrong in several ways:
+//
+//   _act   act pair | ELU(1) pair -> the plain entry point | NULL args | route (kernel, save_act alone) | fill_* (method, dims, pointers)
+//   _rk    act pair | tableau | NULL args | route (kernel, every save_*) | fill_* (`method` is not read: the copy carries EULER)
+//   _sub   struct (NULL: PSNODE_ERR_NULL) | substeps == 1 -> the _rk (tableau given) or the _act family | act pair | NULL args |
+//          tableau (NULL: the args' method as one) | route | fill_*
+//   _lin   struct (NULL: one sub-step) | act pair | NULL args | tableau (as _sub) | route | fill_*
+//   then dispatch: workspace | T, B | LDS fit of the build.
+// _act_supported with an ELU(1) pair answers from method and dims alone (the plain entry point picks its own kernel).
+enum K0Family { kFamAct, kFamRk, kFamSub, kFamLin };
+
+// the ODE / DAE difference: the side outputs, the recipe widths, fill_*, the AE, the plain entry point
+bool side_outputs(const psnode_ode_args_f32& a) { return a.save_act || a.save_xstage; }
+bool side_outputs(const psnode_dae_args_f32& a) { return a.save_act || a.save_xstage || a.save_ae_act || a.save_ev_act || a.save_ev_i; }
+bool recipe_ok(const psnode_ode_args_f32& a) {
+    return a.x_dim >= 1 && a.z_dim >= 0 && !check_mlp_dims(a.de, 3 * (a.x_dim + a.z_dim), a.x_dim);
+}
+bool recipe_ok(const psnode_dae_args_f32& a) {
+    if (a.x_dim < 1 || a.z_dim < 0 || a.v_dim < 0 || a.i_dim < 1) return false;
+    const int n = a.x_dim + a.z_dim + a.v_dim + a.i_dim;
+    return !check_mlp_dims(a.de, 3 * n, a.x_dim) && !check_mlp_dims(a.ae, n + a.x_dim + a.z_dim + a.v_dim, a.i_dim);
+}
+int fill(const psnode_ode_args_f32* a, IntegrateDev& d) { return fill_ode(a, d); }
+int fill(const psnode_dae_args_f32* a, IntegrateDev& d) { return fill_dae(a, d); }
+const psnode_mlp_f32* ae_of(const psnode_ode_args_f32&) { return nullptr; }
+const psnode_mlp_f32* ae_of(const psnode_dae_args_f32& a) { return &a.ae; }
+int integrate_elu1(const psnode_ode_args_f32* a, void* ws, size_t bytes, void* stream) { return psnode_ode_integrate_f32(a, ws, bytes, stream); }
+int integrate_elu1(const psnode_dae_args_f32* a, void* ws, size_t bytes, void* stream) { return psnode_dae_integrate_f32(a, ws, bytes, stream); }
+
+// K0 only (AUTO / GENERIC) and no training side outputs; the _act family looks at save_act alone (a lone save_xstage is fill_*'s status)
+template <class Args>
+bool k0_route_ok(K0Family fam, const Args& a) {
+    if (a.kernel != PSNODE_KERNEL_AUTO && a.kernel != PSNODE_KERNEL_GENERIC) return false;
+    return fam == kFamAct ? !a.save_act : !side_outputs(a);
+}
+// the struct of a _sub / _lin call; substeps == 1 on _sub is the family without sub-steps
+int k0_substeps(K0Family& fam, const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub) {
+    if (fam != kFamSub && !(fam == kFamLin && sub)) return PSNODE_OK;
+    const int rc = substeps_check(sub);
+    if (rc == PSNODE_OK && fam == kFamSub && sub->substeps == 1) fam = tab ? kFamRk : kFamAct;
+    return rc;
+}
+
+template <class Args>
+int k0_integrate(K0Family fam, const Args* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act, const psnode_rk_tableau_f32* tab,
+                 const psnode_substeps_f32* sub, void* workspace, size_t workspace_bytes, void* stream) {
+    K0Call call{};
+    bool elu1 = true;
+    int rc = k0_substeps(fam, tab, sub);
+    if (rc == PSNODE_OK) rc = act_pair(de_act, ae_act, call.act, elu1);
+    if (rc) return rc;
+    if (fam == kFamAct && elu1) return integrate_elu1(args, workspace, workspace_bytes, stream);
+    if (fam == kFamRk) rc = rk_tableau_check(tab);
+    if (rc) return rc;
+    if (!args) return PSNODE_ERR_NULL;
+    Args c = *args;
+    if (fam != kFamAct) {
+        rc = sub_tableau(tab, c.method, call.rk);
+        if (rc) return rc;
+        c.method = PSNODE_EULER;
+    }
+    if (!k0_route_ok(fam, c)) return PSNODE_ERR_UNSUPPORTED;
+    IntegrateDev d;
+    rc = fill(&c, d);
+    if (rc) return rc;
+    call.build = fam == kFamAct ? K0Call::kAct : fam == kFamRk ? K0Call::kRk : fam == kFamSub ? K0Call::kSub : K0Call::kLin;
+    call.sub = SubDev{sub ? sub->substeps : 1, sub ? sub->x_sub : nullptr};
+    return dispatch(d, ae_of(c) != nullptr, c.kernel, &c.de, ae_of(c), workspace, workspace_bytes, static_cast<hipStream_t>(stream), call);
+}
+
+// the same checks from the dims alone, and the LDS fit of the family's build
+template <class Args>
+int k0_supported(K0Family fam, const Args* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act, const psnode_rk_tableau_f32* tab,
+                 const psnode_substeps_f32* sub) {
+    ActPair p;
+    psnode_rk_tableau_f32 t;
+    bool elu1 = true;
+    if (!a || k0_substeps(fam, tab, sub) || act_pair(de_act, ae_act, p, elu1)) return 0;
+    if (fam == kFamAct ? (a->method < PSNODE_EULER || a->method > PSNODE_RK4_38) : (fam == kFamRk && !tab) || sub_tableau(tab, a->method, t)) return 0;
+    if (!recipe_ok(*a)) return 0;
+    if (fam == kFamAct && elu1) return 1;
+    if (!k0_route_ok(fam, *a)) return 0;
+    IntegrateDev d = dims_only(*a);
+    d.maxo = max_out_width(a->de, ae_of(*a));
+    return generic_lds_bytes(d, ae_of(*a) != nullptr, fam == kFamLin) <= 160 * 1024;
 }
 
 }  // namespace
@@ -343,7 +427,7 @@ int32_t psnode_ode_integrate_f32(const psnode_ode_args_f32* args, void* workspac
     if (rc) return rc;
     // only K1 proper / K3c write the training side outputs (checked with the pointers in place: alignment counts)
     if (d.sact && (args->kernel == PSNODE_KERNEL_GENERIC || !mfma_ode_save_hidden(d))) return PSNODE_ERR_UNSUPPORTED;
-    return dispatch(d, false, args->kernel, &args->de, nullptr, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+    return dispatch(d, false, args->kernel, &args->de, nullptr, workspace, workspace_bytes, static_cast<hipStream_t>(stream), K0Call{});
 }
 
 int32_t psnode_dae_save_hidden(const psnode_dae_args_f32* a) {
@@ -356,278 +440,75 @@ int32_t psnode_dae_integrate_f32(const psnode_dae_args_f32* args, void* workspac
     if (rc) return rc;
     // only K2 proper writes the training side outputs
     if (d.sact && (args->kernel == PSNODE_KERNEL_GENERIC || !mfma_dae_save_hidden(d))) return PSNODE_ERR_UNSUPPORTED;
-    return dispatch(d, true, args->kernel, &args->de, &args->ae, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+    return dispatch(d, true, args->kernel, &args->de, &args->ae, workspace, workspace_bytes, static_cast<hipStream_t>(stream), K0Call{});
 }
 
+// ---- the K0 families (the table of their checks: k0_integrate above).  Each wrapper names its family and forwards.
 int32_t psnode_ode_integrate_act_supported(const psnode_ode_args_f32* a, const psnode_act_f32* de_act) {
-    ActPair p;
-    bool elu1 = true;
-    if (!a || act_pair(de_act, nullptr, p, elu1)) return 0;
-    if (a->method < PSNODE_EULER || a->method > PSNODE_RK4_38 || a->x_dim < 1 || a->z_dim < 0) return 0;
-    if (check_mlp_dims(a->de, 3 * (a->x_dim + a->z_dim), a->x_dim)) return 0;
-    if (elu1) return 1;
-    if (!act_call_ok(a->kernel, a->save_act)) return 0;
-    IntegrateDev d = dims_only(*a);
-    d.maxo = max_out_width(a->de, nullptr);
-    return generic_lds_bytes(d, false) <= 160 * 1024;
+    return k0_supported(kFamAct, a, de_act, nullptr, nullptr, nullptr);
 }
-
 int32_t psnode_ode_integrate_act_f32(const psnode_ode_args_f32* args, const psnode_act_f32* de_act, void* workspace, size_t workspace_bytes,
                                      void* stream) {
-    ActPair p;
-    bool elu1 = true;
-    int rc = act_pair(de_act, nullptr, p, elu1);
-    if (rc) return rc;
-    if (elu1) return psnode_ode_integrate_f32(args, workspace, workspace_bytes, stream);
-    if (args && !act_call_ok(args->kernel, args->save_act)) return PSNODE_ERR_UNSUPPORTED;      // K0 only
-    IntegrateDev d;
-    rc = fill_ode(args, d);
-    if (rc) return rc;
-    return dispatch(d, false, args->kernel, &args->de, nullptr, workspace, workspace_bytes, static_cast<hipStream_t>(stream), &p);
+    return k0_integrate(kFamAct, args, de_act, nullptr, nullptr, nullptr, workspace, workspace_bytes, stream);
 }
-
 int32_t psnode_dae_integrate_act_supported(const psnode_dae_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act) {
-    ActPair p;
-    bool elu1 = true;
-    if (!a || act_pair(de_act, ae_act, p, elu1)) return 0;
-    if (a->method < PSNODE_EULER || a->method > PSNODE_RK4_38 || a->x_dim < 1 || a->z_dim < 0 || a->v_dim < 0 || a->i_dim < 1) return 0;
-    const int n = a->x_dim + a->z_dim + a->v_dim + a->i_dim;
-    if (check_mlp_dims(a->de, 3 * n, a->x_dim) || check_mlp_dims(a->ae, n + a->x_dim + a->z_dim + a->v_dim, a->i_dim)) return 0;
-    if (elu1) return 1;
-    if (!act_call_ok(a->kernel, a->save_act)) return 0;
-    IntegrateDev d = dims_only(*a);
-    d.maxo = max_out_width(a->de, &a->ae);
-    return generic_lds_bytes(d, true) <= 160 * 1024;
+    return k0_supported(kFamAct, a, de_act, ae_act, nullptr, nullptr);
 }
-
 int32_t psnode_dae_integrate_act_f32(const psnode_dae_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
                                      void* workspace, size_t workspace_bytes, void* stream) {
-    ActPair p;
-    bool elu1 = true;
-    int rc = act_pair(de_act, ae_act, p, elu1);
-    if (rc) return rc;
-    if (elu1) return psnode_dae_integrate_f32(args, workspace, workspace_bytes, stream);
-    if (args && !act_call_ok(args->kernel, args->save_act)) return PSNODE_ERR_UNSUPPORTED;      // K0 only
-    IntegrateDev d;
-    rc = fill_dae(args, d);
-    if (rc) return rc;
-    return dispatch(d, true, args->kernel, &args->de, &args->ae, workspace, workspace_bytes, static_cast<hipStream_t>(stream), &p);
+    return k0_integrate(kFamAct, args, de_act, ae_act, nullptr, nullptr, workspace, workspace_bytes, stream);
 }
 
-// ---- explicit Runge-Kutta tableaus (include/psnode_hip.h, psnode_rk_tableau_f32): K0's tableau build alone.  The act is checked first, then
-// the tableau, then the route (kernel, save_*); `method` is not read (the copy of the args carries a valid one through fill_ode / fill_dae).
 int32_t psnode_ode_integrate_rk_supported(const psnode_ode_args_f32* a, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab) {
-    if (!a || rk_tableau_check(tab)) return 0;
-    psnode_ode_args_f32 c = *a;
-    c.method = PSNODE_EULER;
-    if (!act_call_ok(c.kernel, c.save_act) || c.save_xstage) return 0;
-    c.kernel = PSNODE_KERNEL_GENERIC;
-    const psnode_act_f32 tanh_act = {PSNODE_ACT_TANH, 0.0f, 0.0f, 0.0f};      // (any non-ELU(1) kind: the query of K0's LDS fit)
-    ActPair p;
-    bool elu1 = true;
-    if (act_pair(de_act, nullptr, p, elu1)) return 0;
-    return psnode_ode_integrate_act_supported(&c, &tanh_act);
+    return k0_supported(kFamRk, a, de_act, nullptr, tab, nullptr);
 }
-
 int32_t psnode_ode_integrate_rk_f32(const psnode_ode_args_f32* args, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
                                     void* workspace, size_t workspace_bytes, void* stream) {
-    ActPair p;
-    bool elu1 = true;
-    int rc = act_pair(de_act, nullptr, p, elu1);
-    if (rc) return rc;
-    rc = rk_tableau_check(tab);
-    if (rc) return rc;
-    if (!args) return PSNODE_ERR_NULL;
-    if (!act_call_ok(args->kernel, args->save_act) || args->save_xstage) return PSNODE_ERR_UNSUPPORTED;      // K0 only
-    psnode_ode_args_f32 c = *args;
-    c.method = PSNODE_EULER;
-    IntegrateDev d;
-    rc = fill_ode(&c, d);
-    if (rc) return rc;
-    return dispatch(d, false, c.kernel, &c.de, nullptr, workspace, workspace_bytes, static_cast<hipStream_t>(stream), &p, tab);
+    return k0_integrate(kFamRk, args, de_act, nullptr, tab, nullptr, workspace, workspace_bytes, stream);
 }
-
 int32_t psnode_dae_integrate_rk_supported(const psnode_dae_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
                                           const psnode_rk_tableau_f32* tab) {
-    if (!a || rk_tableau_check(tab)) return 0;
-    psnode_dae_args_f32 c = *a;
-    c.method = PSNODE_EULER;
-    if (!act_call_ok(c.kernel, c.save_act) || c.save_xstage || c.save_ae_act || c.save_ev_act || c.save_ev_i) return 0;
-    c.kernel = PSNODE_KERNEL_GENERIC;
-    const psnode_act_f32 tanh_act = {PSNODE_ACT_TANH, 0.0f, 0.0f, 0.0f};
-    ActPair p;
-    bool elu1 = true;
-    if (act_pair(de_act, ae_act, p, elu1)) return 0;
-    return psnode_dae_integrate_act_supported(&c, &tanh_act, &tanh_act);
+    return k0_supported(kFamRk, a, de_act, ae_act, tab, nullptr);
 }
-
 int32_t psnode_dae_integrate_rk_f32(const psnode_dae_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
                                     const psnode_rk_tableau_f32* tab, void* workspace, size_t workspace_bytes, void* stream) {
-    ActPair p;
-    bool elu1 = true;
-    int rc = act_pair(de_act, ae_act, p, elu1);
-    if (rc) return rc;
-    rc = rk_tableau_check(tab);
-    if (rc) return rc;
-    if (!args) return PSNODE_ERR_NULL;
-    if (!act_call_ok(args->kernel, args->save_act) || args->save_xstage || args->save_ae_act || args->save_ev_act || args->save_ev_i)
-        return PSNODE_ERR_UNSUPPORTED;
-    psnode_dae_args_f32 c = *args;
-    c.method = PSNODE_EULER;
-    IntegrateDev d;
-    rc = fill_dae(&c, d);
-    if (rc) return rc;
-    return dispatch(d, true, c.kernel, &c.de, &c.ae, workspace, workspace_bytes, static_cast<hipStream_t>(stream), &p, tab);
+    return k0_integrate(kFamRk, args, de_act, ae_act, tab, nullptr, workspace, workspace_bytes, stream);
 }
 
-// ---- sub-steps per grid interval (include/psnode_hip.h, psnode_substeps_f32): K0's sub-step build alone.  The struct is checked first
-// (substeps == 1 leaves for the _rk / _act entry point there), then the act, the tableau (NULL: the args' method as one), the route.
 int32_t psnode_ode_integrate_sub_supported(const psnode_ode_args_f32* a, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
                                            const psnode_substeps_f32* sub) {
-    if (!a || substeps_check(sub)) return 0;
-    if (sub->substeps == 1) return tab ? psnode_ode_integrate_rk_supported(a, de_act, tab) : psnode_ode_integrate_act_supported(a, de_act);
-    psnode_rk_tableau_f32 t;
-    if (sub_tableau(tab, a->method, t)) return 0;
-    return psnode_ode_integrate_rk_supported(a, de_act, &t);
+    return k0_supported(kFamSub, a, de_act, nullptr, tab, sub);
 }
-
 int32_t psnode_ode_integrate_sub_f32(const psnode_ode_args_f32* args, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
                                      const psnode_substeps_f32* sub, void* workspace, size_t workspace_bytes, void* stream) {
-    int rc = substeps_check(sub);
-    if (rc) return rc;
-    if (sub->substeps == 1)
-        return tab ? psnode_ode_integrate_rk_f32(args, de_act, tab, workspace, workspace_bytes, stream)
-                   : psnode_ode_integrate_act_f32(args, de_act, workspace, workspace_bytes, stream);
-    ActPair p;
-    bool elu1 = true;
-    rc = act_pair(de_act, nullptr, p, elu1);
-    if (rc) return rc;
-    if (!args) return PSNODE_ERR_NULL;
-    psnode_rk_tableau_f32 t;
-    rc = sub_tableau(tab, args->method, t);
-    if (rc) return rc;
-    if (!act_call_ok(args->kernel, args->save_act) || args->save_xstage) return PSNODE_ERR_UNSUPPORTED;      // K0 only
-    psnode_ode_args_f32 c = *args;
-    c.method = PSNODE_EULER;
-    IntegrateDev d;
-    rc = fill_ode(&c, d);
-    if (rc) return rc;
-    const SubDev sd{sub->substeps, sub->x_sub};
-    return dispatch(d, false, c.kernel, &c.de, nullptr, workspace, workspace_bytes, static_cast<hipStream_t>(stream), &p, &t, &sd);
+    return k0_integrate(kFamSub, args, de_act, nullptr, tab, sub, workspace, workspace_bytes, stream);
 }
-
 int32_t psnode_dae_integrate_sub_supported(const psnode_dae_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
                                            const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub) {
-    if (!a || substeps_check(sub)) return 0;
-    if (sub->substeps == 1)
-        return tab ? psnode_dae_integrate_rk_supported(a, de_act, ae_act, tab) : psnode_dae_integrate_act_supported(a, de_act, ae_act);
-    psnode_rk_tableau_f32 t;
-    if (sub_tableau(tab, a->method, t)) return 0;
-    return psnode_dae_integrate_rk_supported(a, de_act, ae_act, &t);
+    return k0_supported(kFamSub, a, de_act, ae_act, tab, sub);
 }
-
 int32_t psnode_dae_integrate_sub_f32(const psnode_dae_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
                                      const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, void* workspace, size_t workspace_bytes,
                                      void* stream) {
-    int rc = substeps_check(sub);
-    if (rc) return rc;
-    if (sub->substeps == 1)
-        return tab ? psnode_dae_integrate_rk_f32(args, de_act, ae_act, tab, workspace, workspace_bytes, stream)
-                   : psnode_dae_integrate_act_f32(args, de_act, ae_act, workspace, workspace_bytes, stream);
-    ActPair p;
-    bool elu1 = true;
-    rc = act_pair(de_act, ae_act, p, elu1);
-    if (rc) return rc;
-    if (!args) return PSNODE_ERR_NULL;
-    psnode_rk_tableau_f32 t;
-    rc = sub_tableau(tab, args->method, t);
-    if (rc) return rc;
-    if (!act_call_ok(args->kernel, args->save_act) || args->save_xstage || args->save_ae_act || args->save_ev_act || args->save_ev_i)
-        return PSNODE_ERR_UNSUPPORTED;
-    psnode_dae_args_f32 c = *args;
-    c.method = PSNODE_EULER;
-    IntegrateDev d;
-    rc = fill_dae(&c, d);
-    if (rc) return rc;
-    const SubDev sd{sub->substeps, sub->x_sub};
-    return dispatch(d, true, c.kernel, &c.de, &c.ae, workspace, workspace_bytes, static_cast<hipStream_t>(stream), &p, &t, &sd);
+    return k0_integrate(kFamSub, args, de_act, ae_act, tab, sub, workspace, workspace_bytes, stream);
 }
 
-// ---- linearly interpolated externals (include/psnode_hip.h, "Linear interpolation of externals"): K0's linear-externals build alone, for
-// every substeps >= 1 (a NULL struct is one sub-step).  The struct is checked first, then the act, the tableau (NULL: the args' method as
-// one), the route; the _supported queries answer for this build's own LDS fit.
 int32_t psnode_ode_integrate_lin_supported(const psnode_ode_args_f32* a, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
                                            const psnode_substeps_f32* sub) {
-    ActPair p;
-    bool elu1 = true;
-    psnode_rk_tableau_f32 t;
-    if (!a || (sub && substeps_check(sub)) || act_pair(de_act, nullptr, p, elu1) || sub_tableau(tab, a->method, t)) return 0;
-    if (!act_call_ok(a->kernel, a->save_act) || a->save_xstage || a->x_dim < 1 || a->z_dim < 0) return 0;
-    if (check_mlp_dims(a->de, 3 * (a->x_dim + a->z_dim), a->x_dim)) return 0;
-    IntegrateDev d = dims_only(*a);
-    d.maxo = max_out_width(a->de, nullptr);
-    return generic_lds_bytes(d, false, true) <= 160 * 1024;
+    return k0_supported(kFamLin, a, de_act, nullptr, tab, sub);
 }
-
 int32_t psnode_ode_integrate_lin_f32(const psnode_ode_args_f32* args, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
                                      const psnode_substeps_f32* sub, void* workspace, size_t workspace_bytes, void* stream) {
-    int rc = sub ? substeps_check(sub) : PSNODE_OK;
-    if (rc) return rc;
-    ActPair p;
-    bool elu1 = true;
-    rc = act_pair(de_act, nullptr, p, elu1);
-    if (rc) return rc;
-    if (!args) return PSNODE_ERR_NULL;
-    psnode_rk_tableau_f32 t;
-    rc = sub_tableau(tab, args->method, t);
-    if (rc) return rc;
-    if (!act_call_ok(args->kernel, args->save_act) || args->save_xstage) return PSNODE_ERR_UNSUPPORTED;      // K0 only
-    psnode_ode_args_f32 c = *args;
-    c.method = PSNODE_EULER;
-    IntegrateDev d;
-    rc = fill_ode(&c, d);
-    if (rc) return rc;
-    const SubDev sd{sub ? sub->substeps : 1, sub ? sub->x_sub : nullptr};
-    return dispatch(d, false, c.kernel, &c.de, nullptr, workspace, workspace_bytes, static_cast<hipStream_t>(stream), &p, &t, &sd, true);
+    return k0_integrate(kFamLin, args, de_act, nullptr, tab, sub, workspace, workspace_bytes, stream);
 }
-
 int32_t psnode_dae_integrate_lin_supported(const psnode_dae_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
                                            const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub) {
-    ActPair p;
-    bool elu1 = true;
-    psnode_rk_tableau_f32 t;
-    if (!a || (sub && substeps_check(sub)) || act_pair(de_act, ae_act, p, elu1) || sub_tableau(tab, a->method, t)) return 0;
-    if (!act_call_ok(a->kernel, a->save_act) || a->save_xstage || a->save_ae_act || a->save_ev_act || a->save_ev_i) return 0;
-    if (a->x_dim < 1 || a->z_dim < 0 || a->v_dim < 0 || a->i_dim < 1) return 0;
-    const int n = a->x_dim + a->z_dim + a->v_dim + a->i_dim;
-    if (check_mlp_dims(a->de, 3 * n, a->x_dim) || check_mlp_dims(a->ae, n + a->x_dim + a->z_dim + a->v_dim, a->i_dim)) return 0;
-    IntegrateDev d = dims_only(*a);
-    d.maxo = max_out_width(a->de, &a->ae);
-    return generic_lds_bytes(d, true, true) <= 160 * 1024;
+    return k0_supported(kFamLin, a, de_act, ae_act, tab, sub);
 }
-
 int32_t psnode_dae_integrate_lin_f32(const psnode_dae_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
                                      const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, void* workspace, size_t workspace_bytes,
                                      void* stream) {
-    int rc = sub ? substeps_check(sub) : PSNODE_OK;
-    if (rc) return rc;
-    ActPair p;
-    bool elu1 = true;
-    rc = act_pair(de_act, ae_act, p, elu1);
-    if (rc) return rc;
-    if (!args) return PSNODE_ERR_NULL;
-    psnode_rk_tableau_f32 t;
-    rc = sub_tableau(tab, args->method, t);
-    if (rc) return rc;
-    if (!act_call_ok(args->kernel, args->save_act) || args->save_xstage || args->save_ae_act || args->save_ev_act || args->save_ev_i)
-        return PSNODE_ERR_UNSUPPORTED;
-    psnode_dae_args_f32 c = *args;
-    c.method = PSNODE_EULER;
-    IntegrateDev d;
-    rc = fill_dae(&c, d);
-    if (rc) return rc;
-    const SubDev sd{sub ? sub->substeps : 1, sub ? sub->x_sub : nullptr};
-    return dispatch(d, true, c.kernel, &c.de, &c.ae, workspace, workspace_bytes, static_cast<hipStream_t>(stream), &p, &t, &sd, true);
+    return k0_integrate(kFamLin, args, de_act, ae_act, tab, sub, workspace, workspace_bytes, stream);
 }
 
 int32_t psnode_ode_kernel_for(const psnode_ode_args_f32* a) {
