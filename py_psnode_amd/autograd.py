@@ -3,6 +3,8 @@
 This is what lets the reference's training loops (`loss.backward()` through the integrator,
 neural_00_ODE_01_no_encode.py:358-360) run on the fused HIP path instead of an unrolled T-step autograd graph.
 """
+import functools
+import inspect
 import os
 import warnings
 
@@ -41,6 +43,12 @@ def latent_wide_training_fits(method, de, ae, hidden, T, B, dev) -> bool:
     return need <= free // 2
 
 
+def _generic_only_training(opts, kernel, teacher_forced, T=2) -> bool:
+    """The gate of a training call that carries an option of the generic kernels (fused.GenericOpts.family other than "plain"): K0 + K5
+    alone, so kernel "auto" / "generic"; teacher forcing with ELU(1) only and, for the DAE, on a grid of T >= 2.  K5 then answers for its fit."""
+    return kernel in ("auto", "generic") and not (teacher_forced and (T < 2 or any(a is not None for a in opts.acts)))
+
+
 def ode_training_supported(method, layers, x_dim, z_dim, T, B, kernel="auto", act=None, input_true_x=False, substeps=1,
                            externals="hold") -> bool:
     """What the solver asks before it routes a call that needs autograd to the fused forward + backward pair.  act (fused.Act; None =
@@ -49,21 +57,15 @@ def ode_training_supported(method, layers, x_dim, z_dim, T, B, kernel="auto", ac
     method a fused.Tableau: K0 + K5 on kernel "auto" / "generic" (K5's tableau build answers for its fit), the same teacher-forcing rule.
     substeps > 1: K0 + K5 in their sub-step builds on kernel "auto" / "generic" (K5's answers for its fit), the same teacher-forcing rule.
     externals="linear": K0 + K5 in their linear-externals builds for every substeps >= 1, the same rules."""
-    if _is_tableau(method) and kernel not in ("auto", "generic"):
-        return False
-    if substeps != 1 or fused.is_linear(externals):
-        if kernel not in ("auto", "generic") or (input_true_x and act is not None):
-            return False
-        return fused.ode_backward_supported(method, layers, x_dim, z_dim, kernel, act=act, substeps=substeps, externals=externals)
+    opts = fused.GenericOpts.of(method, (act,), substeps, externals)
+    if opts.family != "plain":
+        return _generic_only_training(opts, kernel, input_true_x) and fused.ode_backward_supported(
+            method, layers, x_dim, z_dim, kernel, act=act, substeps=substeps, externals=externals)
     if input_true_x:
-        if act is not None:
-            return False
         if kernel in ("auto", "mfma") and fused.ode_backward_supported(method, layers, x_dim, z_dim, "wide"):
             return True
         return kernel in ("auto", "generic") and fused.ode_backward_supported(method, layers, x_dim, z_dim, "generic")
-    if act is not None:
-        return fused.ode_backward_supported(method, layers, x_dim, z_dim, kernel, act=act)
-    if not _is_tableau(method) and kernel in ("auto", "mfma") and fused.latent_wide_shape(layers, None, x_dim, z_dim):
+    if kernel in ("auto", "mfma") and fused.latent_wide_shape(layers, None, x_dim, z_dim):
         return latent_wide_training_fits(method, layers, None, x_dim, T, B, layers[0][0].device)
     return fused.ode_backward_supported(method, layers, x_dim, z_dim, kernel)
 
@@ -79,23 +81,20 @@ def dae_training_supported(method, de, ae, x_dim, z_dim, v_dim, i_dim, T, B, act
     shape is its, else K5 on "auto" / "generic".  method a fused.Tableau: K0 + K5 on kernel "auto" / "generic", the same rules.
     substeps > 1: K0 + K5 in their sub-step builds on kernel "auto" / "generic", the same rules.
     externals="linear": K0 + K5 in their linear-externals builds for every substeps >= 1, the same rules."""
-    if _is_tableau(method) and kernel not in ("auto", "generic"):
-        return False
-    if substeps != 1 or fused.is_linear(externals):
-        non_elu = act is not None and any(a is not None for a in act)
-        if kernel not in ("auto", "generic") or ((input_true_x or input_true_i) and (T < 2 or non_elu)):
-            return False
-        return fused.dae_backward_supported(method, de, ae, x_dim, z_dim, v_dim, i_dim, act=act, kernel=kernel, substeps=substeps,
-                                            externals=externals)
-    if input_true_x or input_true_i:
-        if T < 2 or (act is not None and any(a is not None for a in act)):
+    opts = fused.GenericOpts.of(method, fused.dae_acts(act), substeps, externals)
+    teacher_forced = input_true_x or input_true_i
+    if opts.family != "plain":
+        if opts.family == "act":      # (an activation alone: asked without the caller's kernel, as the ELU(1) call at the bottom is)
+            kernel = "auto"
+        return _generic_only_training(opts, kernel, teacher_forced, T) and fused.dae_backward_supported(
+            method, de, ae, x_dim, z_dim, v_dim, i_dim, act=act, kernel=kernel, substeps=substeps, externals=externals)
+    if teacher_forced:
+        if T < 2:
             return False
         if _dae_tf_on_k7f(method, kernel, de, ae, x_dim, z_dim, v_dim, i_dim):
             return True
         return kernel in ("auto", "generic") and fused.dae_backward_supported(method, de, ae, x_dim, z_dim, v_dim, i_dim, kernel="generic")
-    if act is not None and any(a is not None for a in act):
-        return fused.dae_backward_supported(method, de, ae, x_dim, z_dim, v_dim, i_dim, act=act)
-    if not _is_tableau(method) and fused.latent_wide_shape(de, ae, x_dim, z_dim, v_dim, i_dim):
+    if fused.latent_wide_shape(de, ae, x_dim, z_dim, v_dim, i_dim):
         return latent_wide_training_fits(method, de, ae, x_dim, T, B, de[0][0].device)
     return fused.dae_backward_supported(method, de, ae, x_dim, z_dim, v_dim, i_dim)
 
@@ -150,130 +149,164 @@ def _want_saved_dae(method, kernel, de, ae, x_dim, z_dim, v_dim, i_dim, T, B):
     return need <= free // 2
 
 
+def _layers(params, n_de=None):
+    """[(W, b), ...] of the flat *params of a Function; with n_de, the DE's and the AE's."""
+    pairs = [(params[k], params[k + 1]) for k in range(0, len(params), 2)]
+    return pairs if n_de is None else (pairs[:n_de], pairs[n_de:])
+
+
+def _pack(ctx, fixed, optional, params):
+    """The tensors for ctx.save_for_backward: `fixed`, those of `optional` = {name: tensor | tuple of tensors | None} that are there (None
+    entries of a tuple are not), `params`.  ctx remembers which are there; `_unpack` hands them back by name."""
+    layout, there = {}, []
+    for name, v in optional.items():
+        if v is None:
+            layout[name] = None
+        elif isinstance(v, tuple):
+            layout[name] = [q is not None for q in v]
+            there += [q for q in v if q is not None]
+        else:
+            layout[name] = True
+            there.append(v)
+    ctx.saved_layout = layout
+    return (*fixed, *there, *params)
+
+
+def _unpack(ctx, n_fixed):
+    """(the n_fixed leading tensors, {name: what `_pack` was given under it}, params) of ctx.saved_tensors."""
+    sv = ctx.saved_tensors
+    rest = iter(sv[n_fixed:])
+    optional = {}
+    for name, lay in ctx.saved_layout.items():
+        if lay is None:
+            optional[name] = None
+        elif lay is True:
+            optional[name] = next(rest)
+        else:
+            optional[name] = tuple(next(rest) if there else None for there in lay)
+    return sv[:n_fixed], optional, tuple(rest)
+
+
+@functools.lru_cache(maxsize=None)
+def _arg_index(cls) -> dict:
+    """name -> position of the arguments of cls.forward between ctx and *params: the signature is the one declaration of the order."""
+    return {name: k for k, name in enumerate(list(inspect.signature(cls.forward).parameters)[1:-1])}
+
+
+def _arg_names(cls) -> tuple:
+    return tuple(_arg_index(cls))
+
+
+def _needs(ctx, cls, name) -> bool:
+    return bool(ctx.needs_input_grad[_arg_index(cls)[name]])
+
+
+def _grad_tuple(ctx, cls, grads, param_grads) -> tuple:
+    """What cls.backward returns: grads = {forward argument: gradient} at the arguments' positions (where the input needs one), None for
+    every other argument, then the parameters' gradients."""
+    index = _arg_index(cls)
+    out = [None] * len(index)
+    for name, g in grads.items():
+        k = index[name]
+        out[k] = g if ctx.needs_input_grad[k] else None
+    return (*out, *param_grads)
+
+
 class _FusedOde(torch.autograd.Function):
     @staticmethod
     def forward(ctx, method, kernel, act, event_idx, t, x0, z, all_initial, z_jump, *params):
-        # act: the MLP's activation (fused.Act), None = ELU(1).  A non-tensor argument: `layers` is rebuilt from *params here and in backward
-        layers = [(params[k], params[k + 1]) for k in range(0, len(params), 2)]
+        # act: the MLP's activation (fused.Act), None = ELU(1)
+        layers = _layers(params)
         global last_saved_bytes
-        ctx.x_true = False
-        ctx.act = act
+        last_saved_bytes = 0
+        ctx.method, ctx.act, ctx.event_idx, ctx.bwd_kernel = method, act, event_idx, "auto"
+        saved = x_true = None
         if act is not None:      # K0 forward (it saves nothing) + K5 backward; no teacher forcing (the solver walks those calls)
             if x0.dim() == 3:
                 raise ValueError("teacher-forced training with an activation other than ELU(1) has no fused backward")
             xs = fused.ode_integrate(method, layers, t, x0.unsqueeze(0), z, all_initial, z_jump=z_jump, event_idx=event_idx, kernel=kernel,
                                      act=act)
-            last_saved_bytes = 0
-            ctx.method, ctx.bwd_kernel, ctx.has_jump, ctx.has_saved, ctx.event_idx = method, "auto", z_jump is not None, False, event_idx
-            ctx.save_for_backward(t, z, all_initial, xs, *((z_jump,) if z_jump is not None else ()), *params)
-            return xs
-        if x0.dim() == 3:        # teacher forcing (my_solvers.py:72-74): x0 is the whole dataset x [T,B,xd]; nothing is saved, K4f / K5 recompute
+        elif x0.dim() == 3:      # teacher forcing (my_solvers.py:72-74): x0 is the whole dataset x [T,B,xd]; nothing is saved, K4f / K5 recompute
             x_true = x0.detach().contiguous()
             xs = fused.ode_integrate(method, layers, t, x_true, z, all_initial, z_jump=z_jump, event_idx=event_idx, kernel=kernel,
                                      input_true_x=True)
-            last_saved_bytes = 0
-            ctx.x_true = True
-            ctx.method, ctx.has_jump, ctx.has_saved, ctx.event_idx = method, z_jump is not None, False, event_idx
             ctx.bwd_kernel = kernel      # "auto" / "mfma": K4f where the shape is its, "auto" else and "generic": K5
             # (the dataset rows go through save_for_backward like everything else the backward reads: autograd's version counter then
             #  catches an in-place edit of x between forward and backward)
-            ctx.save_for_backward(t, z, all_initial, xs, *((z_jump,) if z_jump is not None else ()), x_true, *params)
-            return xs
-        if kernel == "generic" and not _is_tableau(method) and fused.latent_wide_shape(layers, None, x0.shape[-1], z.shape[-1]):
-            global _warned_generic_override
-            if not _warned_generic_override:
-                _warned_generic_override = True
-                warnings.warn("kernel='generic' is ignored for training at the latent hidden widths other than 16 / 64: the only backward "
-                              "there reads the rows K3w saves (K0 saves nothing)", RuntimeWarning, stacklevel=3)
-            kernel = "auto"      # training at these widths exists on K3w + K9w only (K0 saves nothing)
-        save = _want_saved(method, kernel, layers, x0.shape[-1], z.shape[-1], t.shape[0], t.shape[1])
-        res = fused.ode_integrate(method, layers, t, x0.unsqueeze(0), z, all_initial, z_jump=z_jump, event_idx=event_idx, kernel=kernel,
-                                  save=save)
-        xs, saved = res if save else (res, None)
-        last_saved_bytes = sum(q.numel() * q.element_size() for q in saved) if saved is not None else 0
-        ctx.method = method
-        ctx.bwd_kernel = {"wave": "wave", "tile": "tile"}.get(kernel, "auto")      # a forced forward form forces its backward counterpart (K4x / K4f)
-        if ctx.bwd_kernel != "auto" and not fused.ode_backward_supported(method, layers, x0.shape[-1], z.shape[-1], ctx.bwd_kernel):
-            ctx.bwd_kernel = "auto"                                                    # ... where that counterpart exists for the shape
-        ctx.has_jump = z_jump is not None
-        ctx.has_saved = saved is not None
-        ctx.event_idx = event_idx
-        ctx.save_for_backward(t, z, all_initial, xs, *((z_jump,) if z_jump is not None else ()), *(saved if saved is not None else ()),
-                              *params)
+        else:
+            if kernel == "generic" and not _is_tableau(method) and fused.latent_wide_shape(layers, None, x0.shape[-1], z.shape[-1]):
+                global _warned_generic_override
+                if not _warned_generic_override:
+                    _warned_generic_override = True
+                    warnings.warn("kernel='generic' is ignored for training at the latent hidden widths other than 16 / 64: the only backward "
+                                  "there reads the rows K3w saves (K0 saves nothing)", RuntimeWarning, stacklevel=3)
+                kernel = "auto"      # training at these widths exists on K3w + K9w only (K0 saves nothing)
+            save = _want_saved(method, kernel, layers, x0.shape[-1], z.shape[-1], t.shape[0], t.shape[1])
+            res = fused.ode_integrate(method, layers, t, x0.unsqueeze(0), z, all_initial, z_jump=z_jump, event_idx=event_idx, kernel=kernel,
+                                      save=save)
+            xs, saved = res if save else (res, None)
+            last_saved_bytes = sum(q.numel() * q.element_size() for q in saved) if saved is not None else 0
+            ctx.bwd_kernel = {"wave": "wave", "tile": "tile"}.get(kernel, "auto")      # a forced forward form forces its backward counterpart (K4x / K4f)
+            if ctx.bwd_kernel != "auto" and not fused.ode_backward_supported(method, layers, x0.shape[-1], z.shape[-1], ctx.bwd_kernel):
+                ctx.bwd_kernel = "auto"                                                    # ... where that counterpart exists for the shape
+        ctx.save_for_backward(*_pack(ctx, (t, z, all_initial, xs), dict(z_jump=z_jump, saved=saved, x_true=x_true), params))
         return xs
 
     @staticmethod
     def backward(ctx, grad_xs):
-        saved = ctx.saved_tensors
-        t, z, a0, xs = saved[:4]
-        pos = 4
-        z_jump = saved[pos] if ctx.has_jump else None
-        pos += 1 if ctx.has_jump else 0
-        acts = (saved[pos], saved[pos + 1]) if ctx.has_saved else None
-        pos += 2 if ctx.has_saved else 0
-        x_true = saved[pos] if ctx.x_true else None
-        pos += 1 if ctx.x_true else 0
-        params = saved[pos:]
-        layers = [(params[k], params[k + 1]) for k in range(0, len(params), 2)]
-        need_z = ctx.needs_input_grad[6]
+        (t, z, a0, xs), opt, params = _unpack(ctx, 4)
+        z_jump, saved, x_true = opt["z_jump"], opt["saved"], opt["x_true"]
+        need_z = _needs(ctx, _FusedOde, "z")
         if x_true is not None:   # teacher forcing: every step started from a dataset row -- K4f / K5 with the dataset as `xs`, no carried adjoint
-            gx0, gz, gzj, ga0, gpar = fused.ode_backward(ctx.method, layers, t, z, a0, x_true, grad_xs, event_idx=ctx.event_idx,
+            gx0, gz, gzj, ga0, gpar = fused.ode_backward(ctx.method, _layers(params), t, z, a0, x_true, grad_xs, event_idx=ctx.event_idx,
                                                          z_jump=z_jump, need_grad_z=need_z, kernel=ctx.bwd_kernel, input_true_x=True)
-            if gz is None and need_z:
-                gz = torch.zeros_like(z)
-            return (None, None, None, None, None, None, gz, ga0, gzj if ctx.needs_input_grad[8] else None, *gpar)   # (no gradient for the dataset x)
-        gx0, gz, gzj, ga0, gpar = fused.ode_backward(ctx.method, layers, t, z, a0, xs, grad_xs, event_idx=ctx.event_idx, z_jump=z_jump,
-                                                     need_grad_z=need_z, saved=acts, need_grad_zj=bool(ctx.needs_input_grad[8]),
-                                                     kernel=ctx.bwd_kernel if acts is not None else "auto", act=ctx.act)
+            gx0 = None           # (no gradient for the dataset x)
+        else:
+            gx0, gz, gzj, ga0, gpar = fused.ode_backward(ctx.method, _layers(params), t, z, a0, xs, grad_xs, event_idx=ctx.event_idx, z_jump=z_jump,
+                                                         need_grad_z=need_z, saved=saved, need_grad_zj=_needs(ctx, _FusedOde, "z_jump"),
+                                                         kernel=ctx.bwd_kernel if saved is not None else "auto", act=ctx.act)
         if gz is None and need_z:
             gz = torch.zeros_like(z)
-        return (None, None, None, None, None, gx0, gz, ga0, gzj if ctx.needs_input_grad[8] else None, *gpar)
+        return _grad_tuple(ctx, _FusedOde, dict(x0=gx0, z=gz, all_initial=ga0, z_jump=gzj), gpar)
+
+
+def _ode_sub_forward(externals):
+    """The forward of _FusedOdeSub ("hold") / _FusedOdeLin ("linear"): one body, `externals` travels to both calls."""
+    def forward(ctx, method, kernel, act, substeps, tx, event_idx, t, x0, z, all_initial, z_jump, *params):
+        global last_saved_bytes
+        x_in = x0.detach().contiguous() if tx else x0.unsqueeze(0)      # tx: the whole dataset x [T,B,xd]
+        xs, x_sub = fused.ode_integrate(method, _layers(params), t, x_in, z, all_initial, z_jump=z_jump, event_idx=event_idx, kernel=kernel,
+                                        input_true_x=tx, act=act, substeps=substeps, save_sub=True, externals=externals)
+        last_saved_bytes = x_sub.numel() * x_sub.element_size()
+        ctx.method, ctx.kernel, ctx.act, ctx.substeps, ctx.tx, ctx.event_idx, ctx.externals = method, kernel, act, substeps, tx, event_idx, externals
+        # (tx: the backward starts every interval from the dataset row and reads no xs)
+        ctx.save_for_backward(*_pack(ctx, (t, z, all_initial, x_in if tx else xs, x_sub), dict(z_jump=z_jump), params))
+        return xs
+    return staticmethod(forward)
 
 
 class _FusedOdeSub(torch.autograd.Function):
     """integrate_ODE with substeps > 1, plain or teacher-forced: K0 forward in its sub-step build, which also writes the start state of every
-    sub-step behind an interval's first (x_sub, saved next to xs), K5 backward in its sub-step build.  ctx.externals ("hold" unless the
-    sibling _FusedOdeLin set it) travels to both calls."""
-
-    @staticmethod
-    def forward(ctx, method, kernel, act, substeps, tx, event_idx, t, x0, z, all_initial, z_jump, *params):
-        ctx.externals = getattr(ctx, "externals", "hold")
-        layers = [(params[k], params[k + 1]) for k in range(0, len(params), 2)]
-        global last_saved_bytes
-        x_in = x0.detach().contiguous() if tx else x0.unsqueeze(0)      # tx: the whole dataset x [T,B,xd]
-        xs, x_sub = fused.ode_integrate(method, layers, t, x_in, z, all_initial, z_jump=z_jump, event_idx=event_idx, kernel=kernel,
-                                        input_true_x=tx, act=act, substeps=substeps, save_sub=True, externals=ctx.externals)
-        last_saved_bytes = x_sub.numel() * x_sub.element_size()
-        ctx.method, ctx.kernel, ctx.act, ctx.substeps, ctx.tx, ctx.event_idx, ctx.has_jump = method, kernel, act, substeps, tx, event_idx, z_jump is not None
-        # (tx: the backward starts every interval from the dataset row and reads no xs)
-        ctx.save_for_backward(t, z, all_initial, x_in if tx else xs, x_sub, *((z_jump,) if z_jump is not None else ()), *params)
-        return xs
+    sub-step behind an interval's first (x_sub, saved next to xs), K5 backward in its sub-step build."""
+    forward = _ode_sub_forward("hold")
 
     @staticmethod
     def backward(ctx, grad_xs):
-        saved = ctx.saved_tensors
-        t, z, a0, xs, x_sub = saved[:5]
-        z_jump = saved[5] if ctx.has_jump else None
-        params = saved[6 if ctx.has_jump else 5:]
-        layers = [(params[k], params[k + 1]) for k in range(0, len(params), 2)]
-        need_z = ctx.needs_input_grad[8]
-        gx0, gz, gzj, ga0, gpar = fused.ode_backward(ctx.method, layers, t, z, a0, xs, grad_xs, event_idx=ctx.event_idx, z_jump=z_jump,
-                                                     need_grad_z=need_z, need_grad_zj=bool(ctx.needs_input_grad[10]), kernel=ctx.kernel,
+        (t, z, a0, xs, x_sub), opt, params = _unpack(ctx, 5)
+        need_z = _needs(ctx, _FusedOdeSub, "z")
+        gx0, gz, gzj, ga0, gpar = fused.ode_backward(ctx.method, _layers(params), t, z, a0, xs, grad_xs, event_idx=ctx.event_idx, z_jump=opt["z_jump"],
+                                                     need_grad_z=need_z, need_grad_zj=_needs(ctx, _FusedOdeSub, "z_jump"), kernel=ctx.kernel,
                                                      input_true_x=ctx.tx, act=ctx.act, substeps=ctx.substeps, x_sub=x_sub,
                                                      externals=ctx.externals)
         if gz is None and need_z:
             gz = torch.zeros_like(z)
-        return (None, None, None, None, None, None, None, None if ctx.tx else gx0, gz, ga0, gzj if ctx.needs_input_grad[10] else None, *gpar)
+        return _grad_tuple(ctx, _FusedOdeSub, dict(x0=None if ctx.tx else gx0, z=gz, all_initial=ga0, z_jump=gzj), gpar)
 
 
 class _FusedOdeLin(_FusedOdeSub):
     """integrate_ODE with externals="linear", every substeps >= 1: _FusedOdeSub on the linear-externals builds of K0 / K5 (grad z[k + 1]
     also takes the right-hand share of interval k)."""
-
-    @staticmethod
-    def forward(ctx, *args):
-        ctx.externals = "linear"
-        return _FusedOdeSub.forward(ctx, *args)
+    forward = _ode_sub_forward("linear")
 
 
 def fused_ode_integrate(method, kernel, layers, t, x, z, all_initial, event_t=None, z_jump=None, check_events=False, input_true_x=False,
@@ -295,12 +328,19 @@ def fused_ode_integrate(method, kernel, layers, t, x, z, all_initial, event_t=No
     return _FusedOde.apply(method, kernel, act, event_idx, t, x0, z, all_initial, z_jump, *params)
 
 
+def _dae_grads(ctx, cls, g, z, v) -> tuple:
+    """The return value of a DAE Function's backward from the dict of fused.dae_backward (the dataset rows of a teacher-forced call get none)."""
+    gz = g["z"] if g["z"] is not None else (torch.zeros_like(z) if _needs(ctx, cls, "z") else None)
+    gv = g["v"] if g["v"] is not None else (torch.zeros_like(v) if _needs(ctx, cls, "v") else None)
+    return _grad_tuple(ctx, cls, dict(x_init=g["x_init"], z=gz, v=gv, all_initial=g["all_initial"], z_jump=g["z_jump"], v_jump=g["v_jump"]),
+                       (*g["de"], *g["ae"]))
+
+
 class _FusedDae(torch.autograd.Function):
     @staticmethod
     def forward(ctx, method, kernel, act, event_idx, n_de, t, x_init, z, v, i_shape_like, all_initial, z_jump, v_jump, *params):
-        # act: None or (de_act, ae_act), a non-tensor argument (see _FusedOde); with an activation other than ELU(1): K0 + K5, nothing saved
-        de = [(params[k], params[k + 1]) for k in range(0, 2 * n_de, 2)]
-        ae = [(params[k], params[k + 1]) for k in range(2 * n_de, len(params), 2)]
+        # act: None or (de_act, ae_act); with an activation other than ELU(1): K0 + K5, nothing saved
+        de, ae = _layers(params, n_de)
         T, B = t.shape[0], t.shape[1]
         x_dummy = x_init.new_zeros((1, B, 0))
         if kernel == "generic" and not _is_tableau(method) and fused.latent_wide_shape(de, ae, x_init.shape[-1], z.shape[-1], v.shape[-1],
@@ -312,38 +352,19 @@ class _FusedDae(torch.autograd.Function):
         res = fused.dae_integrate(method, de, ae, x_init, t, x_dummy, z, v, i_shape_like, all_initial, z_jump=z_jump, v_jump=v_jump,
                                   event_idx=event_idx, kernel=kernel, save=save, act=ctx.act)
         xs, is_ = res[0], res[1]
-        acts = [q for q in res[2] if q is not None] if save else []
+        saved = res[2] if save else None
         global last_saved_bytes
-        last_saved_bytes = sum(q.numel() * q.element_size() for q in acts)
+        last_saved_bytes = sum(q.numel() * q.element_size() for q in saved if q is not None) if save else 0
         ctx.method, ctx.n_de, ctx.event_idx = method, n_de, event_idx
-        ctx.has_zj, ctx.has_vj = z_jump is not None, v_jump is not None
-        ctx.n_saved = len(acts)
-        ctx.save_for_backward(t, z, v, all_initial, xs, is_, *((z_jump,) if z_jump is not None else ()),
-                              *((v_jump,) if v_jump is not None else ()), *acts, *params)
+        ctx.save_for_backward(*_pack(ctx, (t, z, v, all_initial, xs, is_), dict(z_jump=z_jump, v_jump=v_jump, saved=saved), params))
         return xs, is_
 
     @staticmethod
     def backward(ctx, grad_xs, grad_is):
-        sv = list(ctx.saved_tensors)
-        t, z, v, a0, xs, is_ = sv[:6]
-        k = 6
-        z_jump = sv[k] if ctx.has_zj else None
-        k += int(ctx.has_zj)
-        v_jump = sv[k] if ctx.has_vj else None
-        k += int(ctx.has_vj)
-        acts = None
-        if ctx.n_saved:
-            acts = tuple(sv[k:k + ctx.n_saved]) + (None,) * (5 - ctx.n_saved)
-            k += ctx.n_saved
-        params = sv[k:]
-        de = [(params[q], params[q + 1]) for q in range(0, 2 * ctx.n_de, 2)]
-        ae = [(params[q], params[q + 1]) for q in range(2 * ctx.n_de, len(params), 2)]
-        g = fused.dae_backward(ctx.method, de, ae, t, z, v, a0, xs, is_, grad_xs, grad_is, event_idx=ctx.event_idx, z_jump=z_jump, v_jump=v_jump,
-                               saved=acts, act=ctx.act)
-        gz = g["z"] if g["z"] is not None else (torch.zeros_like(z) if ctx.needs_input_grad[7] else None)
-        gv = g["v"] if g["v"] is not None else (torch.zeros_like(v) if ctx.needs_input_grad[8] else None)
-        return (None, None, None, None, None, None, g["x_init"], gz, gv, None, g["all_initial"],
-                g["z_jump"] if ctx.needs_input_grad[11] else None, g["v_jump"] if ctx.needs_input_grad[12] else None, *g["de"], *g["ae"])
+        (t, z, v, a0, xs, is_), opt, params = _unpack(ctx, 6)
+        de, ae = _layers(params, ctx.n_de)
+        g = fused.dae_backward(ctx.method, de, ae, t, z, v, a0, xs, is_, grad_xs, grad_is, event_idx=ctx.event_idx, act=ctx.act, **opt)
+        return _dae_grads(ctx, _FusedDae, g, z, v)
 
 
 class _FusedDaeTeacherForced(torch.autograd.Function):
@@ -353,96 +374,66 @@ class _FusedDaeTeacherForced(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, method, kernel, event_idx, n_de, tx, ti, t, x_init, x, z, v, i, all_initial, z_jump, v_jump, *params):
-        de = [(params[k], params[k + 1]) for k in range(0, 2 * n_de, 2)]
-        ae = [(params[k], params[k + 1]) for k in range(2 * n_de, len(params), 2)]
+        de, ae = _layers(params, n_de)
         xs, is_ = fused.dae_integrate(method, de, ae, x_init, t, x, z, v, i, all_initial, z_jump=z_jump, v_jump=v_jump, event_idx=event_idx,
                                       kernel=kernel, input_true_x=tx, input_true_i=ti)[:2]
         ctx.method, ctx.n_de, ctx.event_idx, ctx.tx, ctx.ti = method, n_de, event_idx, tx, ti
         ctx.k7f = _dae_tf_on_k7f(method, kernel, de, ae, x_init.shape[-1], z.shape[-1], v.shape[-1], i.shape[-1])
         ctx.kernel = kernel
-        ctx.has_zj, ctx.has_vj = z_jump is not None, v_jump is not None
-        ctx.save_for_backward(t, z, v, all_initial, xs, is_, x, i, *((z_jump,) if z_jump is not None else ()),
-                              *((v_jump,) if v_jump is not None else ()), *params)
+        ctx.save_for_backward(*_pack(ctx, (t, z, v, all_initial, xs, is_, x, i), dict(z_jump=z_jump, v_jump=v_jump), params))
         return xs, is_
 
     @staticmethod
     def backward(ctx, grad_xs, grad_is):
-        sv = list(ctx.saved_tensors)
-        t, z, v, a0, xs, is_, x, i = sv[:8]
-        k = 8
-        z_jump = sv[k] if ctx.has_zj else None
-        k += int(ctx.has_zj)
-        v_jump = sv[k] if ctx.has_vj else None
-        k += int(ctx.has_vj)
-        params = sv[k:]
-        de = [(params[q], params[q + 1]) for q in range(0, 2 * ctx.n_de, 2)]
-        ae = [(params[q], params[q + 1]) for q in range(2 * ctx.n_de, len(params), 2)]
+        (t, z, v, a0, xs, is_, x, i), opt, params = _unpack(ctx, 8)
+        de, ae = _layers(params, ctx.n_de)
         rows = dict(x_true=x if ctx.tx else None, i_true=i if ctx.ti else None)
         if ctx.k7f:
-            g = fused.dae_backward_wide(ctx.method, de, ae, t, z, v, a0, xs, is_, grad_xs, grad_is, event_idx=ctx.event_idx, z_jump=z_jump,
-                                        v_jump=v_jump, **rows)
+            g = fused.dae_backward_wide(ctx.method, de, ae, t, z, v, a0, xs, is_, grad_xs, grad_is, event_idx=ctx.event_idx, **opt, **rows)
         else:
-            g = fused.dae_backward_tf(ctx.method, de, ae, t, z, v, a0, xs, is_, grad_xs, grad_is, event_idx=ctx.event_idx, z_jump=z_jump,
-                                      v_jump=v_jump, kernel=ctx.kernel, **rows)
-        gz = g["z"] if g["z"] is not None else (torch.zeros_like(z) if ctx.needs_input_grad[9] else None)
-        gv = g["v"] if g["v"] is not None else (torch.zeros_like(v) if ctx.needs_input_grad[10] else None)
-        return (None, None, None, None, None, None, None, g["x_init"], None, gz, gv, None, g["all_initial"],
-                g["z_jump"] if ctx.needs_input_grad[13] else None, g["v_jump"] if ctx.needs_input_grad[14] else None, *g["de"], *g["ae"])
+            g = fused.dae_backward_tf(ctx.method, de, ae, t, z, v, a0, xs, is_, grad_xs, grad_is, event_idx=ctx.event_idx, kernel=ctx.kernel,
+                                      **opt, **rows)
+        return _dae_grads(ctx, _FusedDaeTeacherForced, g, z, v)
+
+
+def _dae_sub_forward(externals):
+    """The forward of _FusedDaeSub ("hold") / _FusedDaeLin ("linear"): one body, `externals` travels to both calls."""
+    def forward(ctx, method, kernel, act, substeps, tx, ti, event_idx, n_de, t, x_init, x, z, v, i, all_initial, z_jump, v_jump, *params):
+        de, ae = _layers(params, n_de)
+        non_elu = act is not None and any(a is not None for a in act)
+        xs, is_, x_sub = fused.dae_integrate(method, de, ae, x_init, t, x, z, v, i, all_initial, z_jump=z_jump, v_jump=v_jump, event_idx=event_idx,
+                                             kernel=kernel, input_true_x=tx, input_true_i=ti, act=act if non_elu else None, substeps=substeps,
+                                             save_sub=True, externals=externals)
+        global last_saved_bytes
+        last_saved_bytes = x_sub.numel() * x_sub.element_size()
+        ctx.method, ctx.kernel, ctx.act, ctx.substeps, ctx.tx, ctx.ti = method, kernel, act if non_elu else None, substeps, tx, ti
+        ctx.n_de, ctx.event_idx, ctx.externals = n_de, event_idx, externals
+        ctx.save_for_backward(*_pack(ctx, (t, z, v, all_initial, xs, is_, x_sub, x, i), dict(z_jump=z_jump, v_jump=v_jump), params))
+        return xs, is_
+    return staticmethod(forward)
 
 
 class _FusedDaeSub(torch.autograd.Function):
     """integrate_DAE with substeps > 1, plain or teacher-forced: K0 forward and K5 backward in their sub-step builds, x_sub saved next to
     xs / is.  The dataset rows of a teacher-forced call get no gradient."""
-
-    @staticmethod
-    def forward(ctx, method, kernel, act, substeps, tx, ti, event_idx, n_de, t, x_init, x, z, v, i, all_initial, z_jump, v_jump, *params):
-        ctx.externals = getattr(ctx, "externals", "hold")      # ("linear": the sibling _FusedDaeLin set it)
-        de = [(params[k], params[k + 1]) for k in range(0, 2 * n_de, 2)]
-        ae = [(params[k], params[k + 1]) for k in range(2 * n_de, len(params), 2)]
-        non_elu = act is not None and any(a is not None for a in act)
-        xs, is_, x_sub = fused.dae_integrate(method, de, ae, x_init, t, x, z, v, i, all_initial, z_jump=z_jump, v_jump=v_jump, event_idx=event_idx,
-                                             kernel=kernel, input_true_x=tx, input_true_i=ti, act=act if non_elu else None, substeps=substeps,
-                                             save_sub=True, externals=ctx.externals)
-        global last_saved_bytes
-        last_saved_bytes = x_sub.numel() * x_sub.element_size()
-        ctx.method, ctx.kernel, ctx.act, ctx.substeps, ctx.tx, ctx.ti = method, kernel, act if non_elu else None, substeps, tx, ti
-        ctx.n_de, ctx.event_idx, ctx.has_zj, ctx.has_vj = n_de, event_idx, z_jump is not None, v_jump is not None
-        ctx.save_for_backward(t, z, v, all_initial, xs, is_, x_sub, x, i, *((z_jump,) if z_jump is not None else ()),
-                              *((v_jump,) if v_jump is not None else ()), *params)
-        return xs, is_
+    forward = _dae_sub_forward("hold")
 
     @staticmethod
     def backward(ctx, grad_xs, grad_is):
-        sv = list(ctx.saved_tensors)
-        t, z, v, a0, xs, is_, x_sub, x, i = sv[:9]
-        k = 9
-        z_jump = sv[k] if ctx.has_zj else None
-        k += int(ctx.has_zj)
-        v_jump = sv[k] if ctx.has_vj else None
-        k += int(ctx.has_vj)
-        params = sv[k:]
-        de = [(params[q], params[q + 1]) for q in range(0, 2 * ctx.n_de, 2)]
-        ae = [(params[q], params[q + 1]) for q in range(2 * ctx.n_de, len(params), 2)]
-        common = dict(event_idx=ctx.event_idx, z_jump=z_jump, v_jump=v_jump, kernel=ctx.kernel, substeps=ctx.substeps, x_sub=x_sub,
-                      externals=ctx.externals)
+        (t, z, v, a0, xs, is_, x_sub, x, i), opt, params = _unpack(ctx, 9)
+        de, ae = _layers(params, ctx.n_de)
+        common = dict(event_idx=ctx.event_idx, kernel=ctx.kernel, substeps=ctx.substeps, x_sub=x_sub, externals=ctx.externals, **opt)
         if ctx.tx or ctx.ti:
             g = fused.dae_backward_tf(ctx.method, de, ae, t, z, v, a0, xs, is_, grad_xs, grad_is, x_true=x if ctx.tx else None,
                                       i_true=i if ctx.ti else None, **common)
         else:
             g = fused.dae_backward(ctx.method, de, ae, t, z, v, a0, xs, is_, grad_xs, grad_is, act=ctx.act, **common)
-        gz = g["z"] if g["z"] is not None else (torch.zeros_like(z) if ctx.needs_input_grad[11] else None)
-        gv = g["v"] if g["v"] is not None else (torch.zeros_like(v) if ctx.needs_input_grad[12] else None)
-        return (None, None, None, None, None, None, None, None, None, g["x_init"], None, gz, gv, None, g["all_initial"],
-                g["z_jump"] if ctx.needs_input_grad[15] else None, g["v_jump"] if ctx.needs_input_grad[16] else None, *g["de"], *g["ae"])
+        return _dae_grads(ctx, _FusedDaeSub, g, z, v)
 
 
 class _FusedDaeLin(_FusedDaeSub):
     """integrate_DAE with externals="linear", every substeps >= 1: _FusedDaeSub on the linear-externals builds of K0 / K5."""
-
-    @staticmethod
-    def forward(ctx, *args):
-        ctx.externals = "linear"
-        return _FusedDaeSub.forward(ctx, *args)
+    forward = _dae_sub_forward("linear")
 
 
 def fused_dae_integrate(method, kernel, de_layers, ae_layers, x_init, t, z, v, i, all_initial, event_t=None, z_jump=None, v_jump=None,

@@ -3,6 +3,7 @@ C ABI structs (include/psnode_hip.h), the device-side event table, workspaces.  
 imports oracle/."""
 import ctypes
 import dataclasses
+import functools
 import math
 import os
 import weakref
@@ -95,13 +96,6 @@ def builtin_method(method, what: str):
     return METHOD_ID[method], STAGES[method]
 
 
-def no_substeps(substeps: int, what: str):
-    """The specialised, latent, encoded and saved-row entries take one step per grid interval: sub-steps are refused like a Tableau."""
-    if substeps != 1:
-        raise _lib.UnsupportedShapeError(f"{what}: sub-steps per grid interval (substeps={substeps}) run on the generic kernels K0 / K5 only "
-                                         "(kernel 'auto' / 'generic', no saved rows); this entry point takes one step per interval")
-
-
 EXTERNALS = ("hold", "linear")      # z | v inside a grid interval: the left grid point's rows held (the reference), or interpolated to the right one's
 
 
@@ -110,45 +104,6 @@ def is_linear(externals: str) -> bool:
     if externals not in EXTERNALS:
         raise ValueError(f"externals must be one of {EXTERNALS}, got {externals!r}")
     return externals == "linear"
-
-
-def no_linear(externals: str, what: str):
-    """The specialised, latent, encoded and saved-row entries hold the external inputs over a step: interpolated ones are refused like
-    sub-steps."""
-    if is_linear(externals):
-        raise _lib.UnsupportedShapeError(f"{what}: linearly interpolated external inputs (externals='linear') run on the generic kernels "
-                                         "K0 / K5 only (kernel 'auto' / 'generic', no saved rows); this entry point holds them over a step")
-
-
-def substeps_abi(substeps: int, x_sub=None, externals: str = "hold"):
-    """The psnode_substeps_f32 of a call of the generic route with substeps > 1 (x_sub: the sub-state rows, or None), None for substeps == 1
-    -- the call then takes the entry point it takes without sub-steps.  ValueError unless an int in 1..1024.
-    externals="linear": a struct for every substeps >= 1, marked `.lin` -- `call_entry` / `entry_supported` then take the _lin entry points."""
-    if isinstance(substeps, bool) or not isinstance(substeps, int) or not 1 <= substeps <= _lib.MAX_SUBSTEPS:
-        raise ValueError(f"substeps must be an int in 1..{_lib.MAX_SUBSTEPS}, got {substeps!r}")
-    lin = is_linear(externals)
-    if substeps == 1 and not lin:
-        return None
-    s = _lib.SubstepsF32()
-    s.lin = lin
-    s.substeps = substeps
-    s.x_sub = x_sub.data_ptr() if x_sub is not None and x_sub.numel() else None
-    return s
-
-
-def sub_route_ok(what: str, substeps: int, kernel: str, save: bool, externals: str = "hold"):
-    """Sub-steps and linearly interpolated externals run on the generic kernels only."""
-    if substeps != 1 and (kernel not in ("auto", "generic") or save):
-        raise _lib.UnsupportedShapeError(f"{what}: sub-steps per grid interval (substeps={substeps}) run on the generic kernels K0 / K5 only "
-                                         f"(kernel 'auto' / 'generic', no saved rows); got kernel={kernel!r}, saved rows={save}")
-    if is_linear(externals) and (kernel not in ("auto", "generic") or save):
-        raise _lib.UnsupportedShapeError(f"{what}: linearly interpolated external inputs (externals='linear') run on the generic kernels K0 / K5 "
-                                         f"only (kernel 'auto' / 'generic', no saved rows); got kernel={kernel!r}, saved rows={save}")
-
-
-def sub_family(sub) -> str:
-    """"lin" or "sub": the entry-point family of a `substeps_abi` struct."""
-    return "lin" if getattr(sub, "lin", False) else "sub"
 
 
 KERNEL_ID = {"auto": _lib.KERNEL_AUTO, "generic": _lib.KERNEL_GENERIC, "mfma": _lib.KERNEL_MFMA, "wide": _lib.KERNEL_MFMA_WIDE,
@@ -219,47 +174,133 @@ _ACT_TORCH = {
 }
 
 
-def _act_refs(*acts):
-    """ctypes pointers of the psnode_act_f32 of `acts` (None = ELU(1): NULL), and whether any of them is not ELU(1)."""
-    refs = [ctypes.byref(a.abi()) if a is not None else None for a in acts]
-    return refs, any(a is not None for a in acts)
-
-
 def dae_acts(act):
     """The public `act=` of a DAE call -- None (both MLPs ELU(1)) or (de_act, ae_act) -- as the tuple of Act | None every call carries
     inside this package (an ODE call's is `(act,)`)."""
     return (None, None) if act is None else tuple(act)
 
 
-def call_entry(lib, stem: str, args, acts, wp, wn, stream, tab=None, sub=None) -> int:
-    """The one place that picks an entry point of the generic-kernel families: psnode_<stem>_f32 when every act is None (ELU(1)),
-    psnode_<stem>_act_f32 with the acts' psnode_act_f32 otherwise.  stem: "ode_integrate", "dae_integrate", "ode_backward", "dae_backward".
-    tab (a Tableau): psnode_<stem>_rk_f32 with the acts and the tableau ("dae_backward": args is then a DaeBwdTfArgsF32).
-    sub (`substeps_abi`, not None: substeps > 1): psnode_<stem>_sub_f32 with the acts, the tableau or NULL (= the args' method) and the
-    struct ("dae_backward": a DaeBwdTfArgsF32); a struct marked `.lin` (externals="linear"): psnode_<stem>_lin_f32 with the same arguments."""
-    refs, non_elu = _act_refs(*acts)
-    if sub is not None:
-        return getattr(lib, f"psnode_{stem}_{sub_family(sub)}_f32")(ctypes.byref(args), *refs, ctypes.byref(tab.abi()) if tab is not None else None,
-                                                      ctypes.byref(sub), wp, wn, stream)
-    if tab is not None:
-        return getattr(lib, f"psnode_{stem}_rk_f32")(ctypes.byref(args), *refs, ctypes.byref(tab.abi()), wp, wn, stream)
-    if not non_elu:
-        return getattr(lib, f"psnode_{stem}_f32")(ctypes.byref(args), wp, wn, stream)
-    return getattr(lib, f"psnode_{stem}_act_f32")(ctypes.byref(args), *refs, wp, wn, stream)
+def _act_ptrs(acts):
+    """One ctypes pointer to a psnode_act_f32 per act, NULL for None = ELU(1).  (A pointer made by ctypes.byref holds on to its struct.)"""
+    return [ctypes.byref(a.abi()) if a is not None else None for a in acts]
 
 
-def entry_supported(lib, stem: str, args, acts, tab=None, sub=None) -> bool:
-    """psnode_<stem>_supported, or psnode_<stem>_act_supported when an act is not None, or psnode_<stem>_rk_supported for a Tableau, or
-    psnode_<stem>_sub_supported for sub-steps (`call_entry`'s query)."""
-    refs, non_elu = _act_refs(*acts)
-    if sub is not None:
-        return bool(getattr(lib, f"psnode_{stem}_{sub_family(sub)}_supported")(ctypes.byref(args), *refs, ctypes.byref(tab.abi()) if tab is not None else None,
-                                                                 ctypes.byref(sub)))
-    if tab is not None:
-        return bool(getattr(lib, f"psnode_{stem}_rk_supported")(ctypes.byref(args), *refs, ctypes.byref(tab.abi())))
-    if not non_elu:
-        return bool(getattr(lib, f"psnode_{stem}_supported")(ctypes.byref(args)))
-    return bool(getattr(lib, f"psnode_{stem}_act_supported")(ctypes.byref(args), *refs))
+@dataclasses.dataclass(frozen=True)
+class GenericOpts:
+    """What a call asks of the generic kernels K0 / K5 beyond the three built-in formulas with ELU(1), one step per grid interval and held
+    externals -- the Python counterpart of the library's K0Call: every public function builds one from its `method`, `act`, `substeps`
+    and `externals` (`of`), and the value says which entry-point family the call takes (`family`, `call_generic`) and which calls are
+    refused (`require_generic`, `require_plain`).  acts: one Act | None per MLP (ODE 1, DAE 2); tab: the Tableau of `method`, if it is one;
+    method_id / stages: what the args struct and the saved rows need of `method` (`method_info`)."""
+    acts: tuple
+    tab: Optional[Tableau]
+    substeps: int = 1
+    externals: str = "hold"
+    method_id: int = _lib.EULER
+    stages: int = 1
+    family: str = dataclasses.field(init=False)
+
+    def __post_init__(self):
+        """Validates substeps and externals, and names the entry-point family: "lin" (interpolated externals, every substeps >= 1), else
+        "sub" (substeps > 1), else "rk" (a Tableau), else "act" (an activation other than ELU(1)), else "plain"."""
+        if isinstance(self.substeps, bool) or not isinstance(self.substeps, int) or not 1 <= self.substeps <= _lib.MAX_SUBSTEPS:
+            raise ValueError(f"substeps must be an int in 1..{_lib.MAX_SUBSTEPS}, got {self.substeps!r}")
+        if is_linear(self.externals):
+            fam = "lin"
+        elif self.substeps > 1:
+            fam = "sub"
+        elif self.tab is not None:
+            fam = "rk"
+        else:
+            fam = "act" if any(a is not None for a in self.acts) else "plain"
+        object.__setattr__(self, "family", fam)
+
+    @staticmethod
+    @functools.lru_cache(maxsize=256, typed=True)      # (a loop asks for the same immutable value call after call; typed: 2.0 and True are not 2 and 1)
+    def of(method, acts: tuple, substeps: int = 1, externals: str = "hold") -> "GenericOpts":
+        method_id, stages, tab = method_info(method)
+        return GenericOpts(acts, tab, substeps, externals, method_id, stages)
+
+    def c_args(self, x_sub=None) -> list:
+        """The family's C arguments behind the args struct: none ("plain"); the acts ("act"); the acts and the tableau ("rk"); the acts,
+        the tableau or NULL (= the args' method) and a psnode_substeps_f32 with the sub-state rows `x_sub` or NULL ("sub", "lin").  The list
+        owns the structs: keep it until the call has returned."""
+        fam = self.family
+        if fam == "plain":
+            return []
+        out = _act_ptrs(self.acts)
+        if fam != "act":
+            out.append(ctypes.byref(self.tab.abi()) if self.tab is not None else None)
+        if fam in ("sub", "lin"):
+            s = _lib.SubstepsF32()
+            s.substeps = self.substeps
+            s.x_sub = x_sub.data_ptr() if x_sub is not None and x_sub.numel() else None
+            out.append(ctypes.byref(s))
+        return out
+
+    def dae_backward_args(self, rows: bool):
+        """The args struct of a dae_backward call: psnode_dae_bwd_tf_args_f32 (flags 0 = no dataset rows) for the families "rk", "sub" and
+        "lin" and for a call with dataset rows x_true / i_true ("tf": the family of such a call that would otherwise be "plain"), else
+        psnode_dae_bwd_args_f32.  Dataset rows next to a non-ELU act alone: no entry point takes both (`call_generic` asserts it too)."""
+        assert not (rows and self.family == "act"), "dae_backward: dataset rows with an activation other than ELU(1) have no entry point"
+        return _lib.DaeBwdTfArgsF32() if rows or self.family in ("rk", "sub", "lin") else _lib.DaeBwdArgsF32()
+
+    def _first_option(self) -> str:
+        """The first option the call carries, in the fixed order act, tableau, sub-steps, externals, as the subject of a refusal."""
+        if any(a is not None for a in self.acts):
+            return "an activation other than ELU(alpha=1) runs"
+        if self.tab is not None:
+            return f"a Runge-Kutta tableau ({self.tab.name}) runs"
+        if self.substeps != 1:
+            return f"sub-steps per grid interval (substeps={self.substeps}) run"
+        return "linearly interpolated external inputs (externals='linear') run"
+
+    def require_generic(self, what: str, kernel: str, saved: bool, teacher_forced: bool = False):
+        """The options run on the generic kernels only: UnsupportedShapeError, naming the first option in the order act, tableau, sub-steps,
+        externals, unless the kernel is "auto" / "generic" and no saved rows are asked for or given.  teacher_forced (an ode_backward with
+        dataset rows): K5 has no such form for an activation other than ELU(1)."""
+        if self.family == "plain":
+            return
+        if kernel not in ("auto", "generic") or saved:
+            raise _lib.UnsupportedShapeError(f"{what}: {self._first_option()} on the generic kernels K0 / K5 only (kernel 'auto' / 'generic', no saved rows); "
+                                             f"got kernel={kernel!r}, saved rows={saved}")
+        if teacher_forced and any(a is not None for a in self.acts):
+            raise _lib.UnsupportedShapeError(f"{what}: an activation other than ELU(alpha=1) runs on the generic backward K5 only "
+                                             "(kernel 'auto' / 'generic', no saved rows, no teacher forcing)")
+
+    def require_plain(self, what: str):
+        """(method id, stages) for the specialised, latent, encoded and saved-row entries, which carry the three built-in formulas with one
+        step per grid interval and held externals: UnsupportedShapeError for sub-steps, interpolated externals or a Tableau."""
+        if self.substeps != 1:
+            raise _lib.UnsupportedShapeError(f"{what}: sub-steps per grid interval (substeps={self.substeps}) run on the generic kernels K0 / K5 only "
+                                             "(kernel 'auto' / 'generic', no saved rows); this entry point takes one step per interval")
+        if self.externals == "linear":
+            raise _lib.UnsupportedShapeError(f"{what}: linearly interpolated external inputs (externals='linear') run on the generic kernels "
+                                             "K0 / K5 only (kernel 'auto' / 'generic', no saved rows); this entry point holds them over a step")
+        if self.tab is not None:
+            builtin_method(self.tab, what)
+        return self.method_id, self.stages
+
+
+def call_generic(lib, stem: str, kind: str, args, opts: GenericOpts, *tail, x_sub=None):
+    """The one place that picks an entry point of the generic-kernel families and calls it: psnode_<stem>[_<family>]_<kind>(args, the
+    family's `c_args`, *tail).  stem: "ode_integrate", "dae_integrate", "ode_backward", "dae_backward"; kind: "f32" (tail: workspace
+    pointer, its size, stream), "supported" or, for the backward stems, "workspace_bytes".  A dae_backward whose `args` is a
+    psnode_dae_bwd_tf_args_f32 (`dae_backward_args`) and whose family would be "plain" takes the "tf" entry points.  The workspace of
+    ode_backward, and of dae_backward in the families "plain" and "act", is the plain query's.  Returns (status or value, the symbol)."""
+    fam = opts.family
+    if isinstance(args, _lib.DaeBwdTfArgsF32):
+        assert stem == "dae_backward" and fam != "act", f"{stem}: no entry point takes dataset rows and the acts {opts.acts} alone"
+        fam = "tf" if fam == "plain" else fam
+    if kind == "workspace_bytes":
+        assert stem in ("ode_backward", "dae_backward"), f"{stem} has no workspace query of its own"
+        if stem == "ode_backward" or fam == "act":
+            fam = "plain"
+    if fam == "plain":
+        name = f"psnode_{stem}_{kind}"
+        return getattr(lib, name)(ctypes.byref(args), *tail), name
+    name = f"psnode_{stem}_{fam}_{kind}"
+    return getattr(lib, name)(ctypes.byref(args), *opts.c_args(x_sub), *tail), name
 
 
 def act_of_module(m) -> Optional[object]:

@@ -6,7 +6,7 @@ import ctypes
 import torch
 
 from .. import _lib
-from ._common import (KERNEL_ID, Layers, builtin_method, method_info, _aligned16, _aligned_ptr, _bind_jumps, _check_saved, _empty, _f32_dev, _mlp, _pad_rows, _padded_hidden, _split_grads, _view, call_entry, dae_acts, entry_supported, is_linear, no_linear, no_substeps, sub_family, sub_route_ok, substeps_abi)
+from ._common import (KERNEL_ID, GenericOpts, Layers, _aligned16, _aligned_ptr, _bind_jumps, _check_saved, _empty, _f32_dev, _mlp, _pad_rows, _padded_hidden, _split_grads, _view, call_generic, dae_acts)
 from .latent import latent_backward_wide, latent_wide_shape
 
 def dae_backward_supported(method, de_layers: Layers, ae_layers: Layers, x_dim, z_dim, v_dim, i_dim, act=None, kernel: str = "auto",
@@ -17,29 +17,18 @@ def dae_backward_supported(method, de_layers: Layers, ae_layers: Layers, x_dim, 
     externals="linear": K5's linear-externals build only (every substeps >= 1; it answers for its own LDS fit)."""
     if de_layers[0][0].device.type != "cuda" or max(len(de_layers), len(ae_layers)) > _lib.MAX_LAYERS:
         return False
-    acts = dae_acts(act)
-    tab = method_info(method)[2]
-    sub = substeps_abi(substeps, None, externals)
-    if tab is not None or sub is not None:
-        tf = _lib.DaeBwdTfArgsF32()
-        b = tf.base
-        b.method, b.kernel = method_info(method)[0], KERNEL_ID[kernel]
-        b.x_dim, b.z_dim, b.v_dim, b.i_dim, b.T, b.B = x_dim, z_dim, v_dim, i_dim, 2, 1
-        dev = de_layers[0][0].device
-        b.de, b.ae = _mlp(de_layers, dev, "de", []), _mlp(ae_layers, dev, "ae", [])
-        return entry_supported(_lib.load(), "dae_backward", tf, acts, tab, sub)
-    non_elu = any(q is not None for q in acts)
-    if not non_elu and kernel != "generic" and latent_wide_shape(de_layers, ae_layers, x_dim, z_dim, v_dim, i_dim):
+    opts = GenericOpts.of(method, dae_acts(act), substeps, externals)
+    if opts.family == "plain" and kernel != "generic" and latent_wide_shape(de_layers, ae_layers, x_dim, z_dim, v_dim, i_dim):
         return True                          # K3w (saving) + K9w + library GEMMs
-    a = _lib.DaeBwdArgsF32()
-    a.method = method_info(method)[0]
+    args = opts.dae_backward_args(rows=False)
+    a = args.base if isinstance(args, _lib.DaeBwdTfArgsF32) else args
+    a.method, a.kernel = opts.method_id, KERNEL_ID[kernel]
     a.x_dim, a.z_dim, a.v_dim, a.i_dim, a.T, a.B = x_dim, z_dim, v_dim, i_dim, 2, 1
     dev = de_layers[0][0].device
     a.de, a.ae = _mlp(de_layers, dev, "de", []), _mlp(ae_layers, dev, "ae", [])
-    a.kernel = KERNEL_ID[kernel]
-    if entry_supported(_lib.load(), "dae_backward", a, acts):      # K9 / K8 (latent shapes) or K5
+    if call_generic(_lib.load(), "dae_backward", "supported", args, opts)[0]:      # K9 / K8 (latent shapes) or K5
         return True
-    if non_elu or kernel == "generic":
+    if opts.family != "plain" or kernel == "generic":
         return False
     return dae_backward_wide_supported(method, de_layers, ae_layers, x_dim, z_dim, v_dim, i_dim)      # K7f: the DAE_01 class at hidden <= 128
 
@@ -48,13 +37,12 @@ def dae_backward_wide_supported(method: str, de_layers: Layers, ae_layers: Layer
                                 externals: str = "hold") -> bool:
     """Shapes of K7f (psnode_dae_backward_wide_f32): DE 3n -> h -> h -> h -> x and AE n+x+z+v -> h -> h -> h -> i with h <= 128,
     x <= 8, z+v+i <= 8."""
-    no_substeps(substeps, "dae_backward_wide_supported")
-    no_linear(externals, "dae_backward_wide_supported")
+    method_id = GenericOpts.of(method, (None, None), substeps, externals).require_plain("dae_backward_wide_supported")[0]
     if de_layers[0][0].device.type != "cuda" or len(de_layers) != 4 or len(ae_layers) != 4:
         return False
     lib = _lib.load()
     a = _lib.DaeBwdWideArgsF32()
-    a.method, a.x_dim, a.z_dim, a.v_dim, a.i_dim, a.T, a.B = builtin_method(method, "dae_backward_wide_supported")[0], x_dim, z_dim, v_dim, i_dim, 2, 1
+    a.method, a.x_dim, a.z_dim, a.v_dim, a.i_dim, a.T, a.B = method_id, x_dim, z_dim, v_dim, i_dim, 2, 1
     dev = de_layers[0][0].device
     a.de, a.ae = _mlp(de_layers, dev, "de", []), _mlp(ae_layers, dev, "ae", [])
     return bool(lib.psnode_dae_backward_wide_supported(ctypes.byref(a)))
@@ -71,8 +59,7 @@ def dae_backward_wide(method: str, de_layers: Layers, ae_layers: Layers, t, z, v
     DE / the heads; recompute form only.  A call whose head rows (6 x [T,B,H] + [T,B,40]) would not fit half of the free HBM is run over
     BATCH slices (trajectories are independent: parameter gradients add, per-trajectory gradients concatenate).
     Same return value as `dae_backward`."""
-    no_substeps(substeps, "dae_backward_wide")
-    no_linear(externals, "dae_backward_wide")
+    method_id, S = GenericOpts.of(method, (None, None), substeps, externals).require_plain("dae_backward_wide")
     lib = _lib.load()
     dev = xs.device
     T, B, xd = xs.shape
@@ -81,7 +68,6 @@ def dae_backward_wide(method: str, de_layers: Layers, ae_layers: Layers, t, z, v
     n = xd + ne
     Hr = de_layers[0][0].shape[0]                       # the MLPs' width; H = the width the kernel runs them at (zero-padded rows)
     H = _padded_hidden(Hr)
-    method_id, S = builtin_method(method, "dae_backward_wide")
     if saved is None and B > 16:
         # the recompute form stores the AE head's rows of EVERY grid point (6 x [T,B,H] + [T,B,16] + the u rows of K7h): a very long grid on
         # a full card goes through in batch slices (a saved-activation call is not sliced: its forward already held ~S times as much)
@@ -324,20 +310,11 @@ def dae_backward(method, de_layers: Layers, ae_layers: Layers, t, z, v, all_init
     Returns dict(x_init, z, v, z_jump, v_jump, all_initial, de=[...], ae=[...]) of gradients."""
     T, B, xd = xs.shape
     zd, vd, idim = z.shape[-1], v.shape[-1], is_.shape[-1]
-    acts = dae_acts(act)
-    if any(q is not None for q in acts):
-        if kernel not in ("auto", "generic") or saved is not None:
-            raise _lib.UnsupportedShapeError("dae_backward: an activation other than ELU(alpha=1) runs on the generic backward K5 only "
-                                             "(kernel 'auto' / 'generic', no saved rows)")
-        kernel = "generic"
-    tab = method_info(method)[2]
-    sub_route_ok("dae_backward", substeps, kernel, saved is not None, externals)
-    if tab is not None or substeps > 1 or is_linear(externals):
-        if tab is not None and (kernel not in ("auto", "generic") or saved is not None):
-            raise _lib.UnsupportedShapeError(f"dae_backward: a Runge-Kutta tableau ({tab.name}) runs on the generic backward K5 only "
-                                             "(kernel 'auto' / 'generic', no saved rows)")
-        return _dae_backward_entry(method, de_layers, ae_layers, t, z, v, all_initial, xs, is_, grad_xs, grad_is, event_idx, z_jump, v_jump,
-                                   kernel, None, acts, substeps=substeps, x_sub=x_sub, externals=externals)
+    opts = GenericOpts.of(method, dae_acts(act), substeps, externals)
+    opts.require_generic("dae_backward", kernel, saved is not None)
+    if opts.family != "plain":      # K5 alone (an activation other than ELU(1) asks for it by name, as it always did)
+        return _dae_backward_entry(opts, de_layers, ae_layers, t, z, v, all_initial, xs, is_, grad_xs, grad_is, event_idx, z_jump, v_jump,
+                                   "generic" if any(q is not None for q in opts.acts) else kernel, None, x_sub=x_sub)
     if kernel in ("wide", "mfma") and T < 2 and len(de_layers) == 4:
         kernel = "generic"       # no step to sweep: K7f has no head-only form, K5 handles the single grid point
     if saved is not None and latent_wide_shape(de_layers, ae_layers, xd, zd, vd, idim):
@@ -347,8 +324,8 @@ def dae_backward(method, de_layers: Layers, ae_layers: Layers, t, z, v, all_init
                             and dae_backward_wide_supported(method, de_layers, ae_layers, xd, zd, vd, idim)):
         return dae_backward_wide(method, de_layers, ae_layers, t, z, v, all_initial, xs, is_, grad_xs, grad_is, event_idx=event_idx,
                                  z_jump=z_jump, v_jump=v_jump, saved=saved)
-    return _dae_backward_entry(method, de_layers, ae_layers, t, z, v, all_initial, xs, is_, grad_xs, grad_is, event_idx, z_jump, v_jump,
-                               kernel, saved, acts)
+    return _dae_backward_entry(opts, de_layers, ae_layers, t, z, v, all_initial, xs, is_, grad_xs, grad_is, event_idx, z_jump, v_jump,
+                               kernel, saved)
 
 
 def dae_backward_tf(method, de_layers: Layers, ae_layers: Layers, t, z, v, all_initial, xs, is_, grad_xs, grad_is, event_idx=None,
@@ -367,14 +344,14 @@ def dae_backward_tf(method, de_layers: Layers, ae_layers: Layers, t, z, v, all_i
     for name, q, w in (("x_true", x_true, xd), ("i_true", i_true, is_.shape[-1])):
         if q is not None and tuple(q.shape) != (T, B, w):
             raise ValueError(f"{name} must be [T,B,{w}], got {tuple(q.shape)}")
-    return _dae_backward_entry(method, de_layers, ae_layers, t, z, v, all_initial, xs, is_, grad_xs, grad_is, event_idx, z_jump, v_jump,
-                               kernel, None, (None, None), x_true=x_true, i_true=i_true, substeps=substeps, x_sub=x_sub, externals=externals)
+    return _dae_backward_entry(GenericOpts.of(method, (None, None), substeps, externals), de_layers, ae_layers, t, z, v, all_initial, xs, is_, grad_xs,
+                               grad_is, event_idx, z_jump, v_jump, kernel, None, x_true=x_true, i_true=i_true, x_sub=x_sub)
 
 
-def _dae_backward_entry(method, de_layers, ae_layers, t, z, v, all_initial, xs, is_, grad_xs, grad_is, event_idx, z_jump, v_jump, kernel, saved,
-                        acts, x_true=None, i_true=None, substeps: int = 1, x_sub=None, externals: str = "hold"):
-    """psnode_dae_backward_f32 / _act_f32, or psnode_dae_backward_tf_f32 when dataset rows come along, or the _rk / _sub entry points: one
-    marshalling for all of them."""
+def _dae_backward_entry(opts, de_layers, ae_layers, t, z, v, all_initial, xs, is_, grad_xs, grad_is, event_idx, z_jump, v_jump, kernel, saved,
+                        x_true=None, i_true=None, x_sub=None):
+    """The DAE backward on whichever entry point `opts` and the dataset rows select (`call_generic`): one marshalling for all of them."""
+    substeps = opts.substeps
     lib = _lib.load()
     dev = xs.device
     T, B, xd = xs.shape
@@ -384,19 +361,17 @@ def _dae_backward_entry(method, de_layers, ae_layers, t, z, v, all_initial, xs, 
         raise ValueError(f"dae_backward: substeps={substeps} needs x_sub, the contiguous fp32 [{T - 1},{substeps - 1},{B},{xd}] tensor the "
                          "forward call returned with save_sub=True")
     keep: list = [x_sub]
-    sub = substeps_abi(substeps, x_sub, externals)
-    tf = None
-    method_id, S, tab = method_info(method)
-    if x_true is not None or i_true is not None or tab is not None or sub is not None:      # (the _rk / _sub entry points take the tf struct, flags 0 included)
-        tf = _lib.DaeBwdTfArgsF32()
+    args = opts.dae_backward_args(x_true is not None or i_true is not None)
+    tf = args if isinstance(args, _lib.DaeBwdTfArgsF32) else None
+    if tf is not None:
         xt_c = _f32_dev(x_true, dev, "x_true").contiguous() if x_true is not None else None
         it_c = _f32_dev(i_true, dev, "i_true").contiguous() if i_true is not None else None
         keep += [xt_c, it_c]
         tf.flags = (_lib.FLAG_INPUT_TRUE_X if xt_c is not None else 0) | (_lib.FLAG_INPUT_TRUE_I if it_c is not None else 0)
         tf.x_true = xt_c.data_ptr() if xt_c is not None else None
         tf.i_true = it_c.data_ptr() if it_c is not None else None
-    a = tf.base if tf is not None else _lib.DaeBwdArgsF32()      # (tf.base: a view of the struct's own memory)
-    a.method = method_id
+    a = tf.base if tf is not None else args      # (tf.base: a view of the struct's own memory)
+    a.method = opts.method_id
     a.kernel = KERNEL_ID[kernel]
     a.x_dim, a.z_dim, a.v_dim, a.i_dim, a.T, a.B = xd, zd, vd, idim, T, B
     a.de, a.ae = _mlp(de_layers, dev, "de", keep), _mlp(ae_layers, dev, "ae", keep)
@@ -436,7 +411,7 @@ def _dae_backward_entry(method, de_layers, ae_layers, t, z, v, all_initial, xs, 
         if saved is not None and T >= 2:        # (K9 reads them; the C side refuses them for the kernels that recompute)
             s_act, s_xst, s_ae, s_ev, s_evi = saved
             L = len(de_layers) - 1
-            _check_saved(s_act, s_xst, T, B, xd, S, L, dev)
+            _check_saved(s_act, s_xst, T, B, xd, opts.stages, L, dev)
             if tuple(s_ae.shape[:3]) != (L, T, B) or s_ae.shape[-1] != s_act.shape[-1] or not s_ae.is_contiguous() or s_ae.device != dev:
                 raise ValueError("saved AE activations do not belong to this call (shape / device)")
             keep += [s_act, s_xst, s_ae, s_ev, s_evi]
@@ -446,24 +421,10 @@ def _dae_backward_entry(method, de_layers, ae_layers, t, z, v, all_initial, xs, 
                 if s_ev is None or s_evi is None or s_ev.shape[0] != n_ev_ or s_ev.shape[2] != B or s_evi.shape[:2] != (n_ev_, B):
                     raise ValueError("saved event activations do not belong to this call (shape)")
                 a.saved_ev_act, a.saved_ev_i = s_ev.data_ptr(), s_evi.data_ptr()
-        if sub is not None:
-            arefs = [ctypes.byref(q.abi()) if q is not None else None for q in acts]
-            nbytes = getattr(lib, f"psnode_dae_backward_{sub_family(sub)}_workspace_bytes")(ctypes.byref(tf), *arefs, ctypes.byref(tab.abi()) if tab is not None else None,
-                                                                 ctypes.byref(sub))
-        elif tab is not None:
-            arefs = [ctypes.byref(q.abi()) if q is not None else None for q in acts]
-            nbytes = lib.psnode_dae_backward_rk_workspace_bytes(ctypes.byref(tf), *arefs, ctypes.byref(tab.abi()))
-        elif tf is not None:
-            nbytes = lib.psnode_dae_backward_tf_workspace_bytes(ctypes.byref(tf))
-        else:
-            nbytes = lib.psnode_dae_backward_workspace_bytes(ctypes.byref(a))
+        nbytes = call_generic(lib, "dae_backward", "workspace_bytes", args, opts, x_sub=x_sub)[0]
         ws = _empty(nbytes + 256, dtype=torch.uint8, device=dev)
         wp, wn = _aligned_ptr(ws)
-        st = torch.cuda.current_stream(dev).cuda_stream
-        if tab is not None or sub is not None:
-            rc = call_entry(lib, "dae_backward", tf, acts, wp, wn, st, tab, sub)
-        else:
-            rc = lib.psnode_dae_backward_tf_f32(ctypes.byref(tf), wp, wn, st) if tf is not None else call_entry(lib, "dae_backward", a, acts, wp, wn, st)
-    _lib.check(rc, f"psnode_dae_backward_{sub_family(sub)}_f32" if sub is not None else "psnode_dae_backward_rk_f32" if tab is not None else ("psnode_dae_backward_tf_f32" if tf is not None else "psnode_dae_backward_f32"))
+        rc, entry = call_generic(lib, "dae_backward", "f32", args, opts, wp, wn, torch.cuda.current_stream(dev).cuda_stream, x_sub=x_sub)
+    _lib.check(rc, entry)
     g["de"], g["ae"] = _split_grads(gde, de_layers), _split_grads(gae, ae_layers)
     return g

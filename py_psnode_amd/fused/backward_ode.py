@@ -5,12 +5,12 @@ import ctypes
 import torch
 
 from .. import _lib
-from ._common import (KERNEL_ID, Layers, method_info, _aligned16, _aligned_ptr, _bind_jumps, _check_saved, _empty, _f32_dev, _mlp, _split_grads, _view, call_entry, entry_supported, sub_family, sub_route_ok, substeps_abi)
+from ._common import (KERNEL_ID, GenericOpts, Layers, _aligned16, _aligned_ptr, _bind_jumps, _check_saved, _empty, _f32_dev, _mlp, _split_grads, _view, call_generic)
 from .latent import latent_backward_wide, latent_wide_shape
 
-def _bwd_args(method, de_layers, x_dim, z_dim, T, B, dev, keep, kernel="auto"):
+def _bwd_args(opts, de_layers, x_dim, z_dim, T, B, dev, keep, kernel="auto"):
     a = _lib.OdeBwdArgsF32()
-    a.method = method_info(method)[0]
+    a.method = opts.method_id
     a.kernel = KERNEL_ID[kernel]
     a.x_dim, a.z_dim, a.T, a.B = x_dim, z_dim, T, B
     a.de = _mlp(de_layers, dev, "de", keep)
@@ -25,18 +25,11 @@ def ode_backward_supported(method, de_layers: Layers, x_dim: int, z_dim: int, ke
     sub-step build only, under the same rules.  externals="linear": K5's linear-externals build only (every substeps >= 1; its own LDS fit)."""
     if de_layers[0][0].device.type != "cuda" or len(de_layers) > _lib.MAX_LAYERS:
         return False
-    tab = method_info(method)[2]
-    sub = substeps_abi(substeps, None, externals)
-    if sub is not None:
-        a = _bwd_args(method, de_layers, x_dim, z_dim, 2, 1, de_layers[0][0].device, [], kernel)
-        return entry_supported(_lib.load(), "ode_backward", a, (act,), tab, sub)
-    if tab is not None:
-        a = _bwd_args(method, de_layers, x_dim, z_dim, 2, 1, de_layers[0][0].device, [], kernel)
-        return entry_supported(_lib.load(), "ode_backward", a, (act,), tab)
-    if act is None and kernel in ("auto", "mfma") and latent_wide_shape(de_layers, None, x_dim, z_dim):
+    opts = GenericOpts.of(method, (act,), substeps, externals)
+    if opts.family == "plain" and kernel in ("auto", "mfma") and latent_wide_shape(de_layers, None, x_dim, z_dim):
         return True                          # K3w (saving) + K9w + library GEMMs
-    a = _bwd_args(method, de_layers, x_dim, z_dim, 2, 1, de_layers[0][0].device, [], kernel)
-    return entry_supported(_lib.load(), "ode_backward", a, (act,))
+    a = _bwd_args(opts, de_layers, x_dim, z_dim, 2, 1, de_layers[0][0].device, [], kernel)
+    return bool(call_generic(_lib.load(), "ode_backward", "supported", a, opts)[0])
 
 
 def ode_backward(method, de_layers: Layers, t, z, all_initial, xs, grad_xs, event_idx=None, z_jump=None, need_grad_z: bool = True,
@@ -63,25 +56,18 @@ def ode_backward(method, de_layers: Layers, t, z, all_initial, xs, grad_xs, even
     zd = z.shape[-1]
     # kernel: "auto" / "mfma" = the one-launch K4f at every hidden width <= 128 (z_dim <= 8), K8f / K9 / K9w for the latent shapes, else the
     # generic K5 ("auto" only); "wide" forces K4f
-    sub_route_ok("ode_backward", substeps, kernel, saved is not None, externals)
+    opts = GenericOpts.of(method, (act,), substeps, externals)
+    opts.require_generic("ode_backward", kernel, saved is not None, teacher_forced=input_true_x)
     if substeps > 1 and T >= 2 and (x_sub is None or tuple(x_sub.shape) != (T - 1, substeps - 1, B, xd) or not x_sub.is_contiguous()
                                     or x_sub.dtype != torch.float32 or x_sub.device != dev):
         raise ValueError(f"ode_backward: substeps={substeps} needs x_sub, the contiguous fp32 [{T - 1},{substeps - 1},{B},{xd}] tensor the "
                          "forward call returned with save_sub=True")
-    if act is not None and (kernel not in ("auto", "generic") or saved is not None or input_true_x):
-        raise _lib.UnsupportedShapeError("ode_backward: an activation other than ELU(alpha=1) runs on the generic backward K5 only "
-                                         "(kernel 'auto' / 'generic', no saved rows, no teacher forcing)")
-    method_id, S, tab = method_info(method)
-    if tab is not None and (kernel not in ("auto", "generic") or saved is not None):
-        raise _lib.UnsupportedShapeError(f"ode_backward: a Runge-Kutta tableau ({tab.name}) runs on the generic backward K5 only "
-                                         "(kernel 'auto' / 'generic', no saved rows)")
     if saved is not None and not input_true_x and latent_wide_shape(de_layers, None, xd, zd):
         g = latent_backward_wide(method, de_layers, None, t, z, None, all_initial, xs, None, grad_xs, None, event_idx=event_idx,
                                  z_jump=z_jump, saved=saved, need_grad_z=need_grad_z)
         return g["x_init"], g["z"], g["z_jump"], g["all_initial"], g["de"]
     keep: list = [x_sub]
-    sub = substeps_abi(substeps, x_sub, externals)
-    a = _bwd_args(method, de_layers, xd, zd, T, B, dev, keep, kernel)
+    a = _bwd_args(opts, de_layers, xd, zd, T, B, dev, keep, kernel)
     if input_true_x:
         if saved is not None:
             raise ValueError("a teacher-forced forward saves no activations")
@@ -111,12 +97,12 @@ def ode_backward(method, de_layers: Layers, t, z, all_initial, xs, grad_xs, even
         a.grad_x0, a.grad_all_initial, a.grad_params = gx0.data_ptr(), ga0.data_ptr(), gpar.data_ptr()
         a.grad_z = gz.data_ptr() if gz is not None else None
         if saved is not None and T >= 2:
-            _check_saved(saved[0], saved[1], T, B, xd, S, len(de_layers) - 1, dev)
+            _check_saved(saved[0], saved[1], T, B, xd, opts.stages, len(de_layers) - 1, dev)
             keep += [saved[0], saved[1]]
             a.saved_act, a.saved_xstage = saved[0].data_ptr(), saved[1].data_ptr()
-        nbytes = lib.psnode_ode_backward_workspace_bytes(ctypes.byref(a))
+        nbytes = call_generic(lib, "ode_backward", "workspace_bytes", a, opts)[0]
         ws = _empty(nbytes + 256, dtype=torch.uint8, device=dev)
         wp, wn = _aligned_ptr(ws)
-        rc = call_entry(lib, "ode_backward", a, (act,), wp, wn, torch.cuda.current_stream(dev).cuda_stream, tab, sub)
-    _lib.check(rc, f"psnode_ode_backward_{sub_family(sub)}_f32" if sub is not None else ("psnode_ode_backward_rk_f32" if tab is not None else "psnode_ode_backward_f32"))
+        rc, entry = call_generic(lib, "ode_backward", "f32", a, opts, wp, wn, torch.cuda.current_stream(dev).cuda_stream, x_sub=x_sub)
+    _lib.check(rc, entry)
     return gx0, gz, gzj, ga0, _split_grads(gpar, de_layers)

@@ -5,7 +5,7 @@ import ctypes
 import torch
 
 from .. import _lib
-from ._common import Layers, builtin_method, no_linear, no_substeps, _aligned_ptr, _check_jump, _empty, _f32_dev, _jump, _mlp, _view, event_table
+from ._common import GenericOpts, Layers, _aligned_ptr, _check_jump, _empty, _f32_dev, _jump, _mlp, _view, event_table
 
 def ode_encoded_supported(x_encoder: Layers, z_encoder: Layers, x_decoder: Layers, de_layers: Layers) -> bool:
     """Shapes of the fused direct_encode ODE forward (psnode_ode_encoded_integrate_f32): every MLP 2 layers with hidden 16."""
@@ -32,9 +32,7 @@ def ode_encoded_integrate(method: str, x_encoder: Layers, z_encoder: Layers, x_d
     dev = x.device
     keep: list = []
     a = _lib.OdeEncodedArgsF32()
-    no_substeps(substeps, "ode_encoded_integrate")
-    no_linear(externals, "ode_encoded_integrate")
-    a.method = builtin_method(method, "ode_encoded_integrate")[0]
+    a.method = GenericOpts.of(method, (None,), substeps, externals).require_plain("ode_encoded_integrate")[0]
     B, T, xd = x.shape
     zd = z.shape[-1]
     if t.shape[:2] != (B, T) or z.shape[:2] != (B, T):
@@ -118,9 +116,7 @@ def dae_encoded_integrate(method: str, x_encoder, z_encoder, v_encoder, i_encode
         zd = 0
     mlps = (x_encoder, z_encoder, v_encoder, i_encoder, x_decoder, i_decoder, de_layers, ae_layers)
     a = _dae_encoded_args(mlps, dev, keep, xd, zd, vd, idim)
-    no_substeps(substeps, "dae_encoded_integrate")
-    no_linear(externals, "dae_encoded_integrate")
-    a.method, a.T, a.B = builtin_method(method, "dae_encoded_integrate")[0], T, B
+    a.method, a.T, a.B = GenericOpts.of(method, (None, None), substeps, externals).require_plain("dae_encoded_integrate")[0], T, B
     if not lib.psnode_dae_encoded_supported(ctypes.byref(a)):
         raise _lib.UnsupportedShapeError("dae_encoded_integrate: needs encoders in->64->64 (x <= 16, z | v | i <= 8 wide), decoders "
                                          "64->64->out, de 12H|9H->64->64, ae 7H|5H->64->64")

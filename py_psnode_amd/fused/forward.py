@@ -6,7 +6,7 @@ from typing import Optional
 import torch
 
 from .. import _lib
-from ._common import (KERNEL_ID, Layers, Tableau, builtin_method, method_info, _aligned16, _aligned_ptr, _bind_events, _check_tb, _empty, _f32_dev, _mlp, _view, _workspace, call_entry, dae_acts, is_linear, sub_family, sub_route_ok, substeps_abi)
+from ._common import (KERNEL_ID, GenericOpts, Layers, Tableau, builtin_method, _aligned16, _aligned_ptr, _bind_events, _check_tb, _empty, _f32_dev, _mlp, _view, _workspace, call_generic, dae_acts, is_linear)
 
 _MFMA_CLASSES = ("MFMA integrators K1 / K2 cover `in -> H -> H -> H -> out` ELU-MLPs with H <= 128 (any x_dim <= 16 for the ODE, "
                  "x_dim <= 8 and z+v+i <= 8 for the DAE), and -- weights streamed from L2 -- the ODE up to H = 192 at any x_dim <= 16 and "
@@ -42,20 +42,6 @@ def _note_k0(lib, args, dae: bool, de_layers: Layers):
                       f"MFMA integrators.  {_MFMA_CLASSES}", RuntimeWarning, stacklevel=3)
 
 
-def _act_route_ok(what: str, non_elu: bool, kernel: str, save: bool):
-    """An activation other than ELU(1) runs on the generic kernels only: say so instead of a bare status."""
-    if non_elu and (kernel not in ("auto", "generic") or save):
-        raise _lib.UnsupportedShapeError(f"{what}: an activation other than ELU(alpha=1) runs on the generic kernel K0 only "
-                                         f"(kernel 'auto' / 'generic', no save=True); got kernel={kernel!r}, save={save}")
-
-
-def _rk_route_ok(what: str, tab, kernel: str, save: bool):
-    """A Runge-Kutta tableau runs on the generic kernels only."""
-    if tab is not None and (kernel not in ("auto", "generic") or save):
-        raise _lib.UnsupportedShapeError(f"{what}: a Runge-Kutta tableau ({tab.name}) runs on the generic kernel K0 only "
-                                         f"(kernel 'auto' / 'generic', no save=True); got kernel={kernel!r}, save={save}")
-
-
 def ode_integrate(method, de_layers: Layers, t, x, z, all_initial, event_t=None, z_jump=None,
                   input_true_x: bool = False, kernel: str = "auto", event_idx: Optional[torch.Tensor] = None,
                   check_events: bool = False, out: Optional[torch.Tensor] = None, save: bool = False, act=None, substeps: int = 1,
@@ -88,10 +74,8 @@ def ode_integrate(method, de_layers: Layers, t, x, z, all_initial, event_t=None,
     dev = x.device
     if dev.type != "cuda":
         raise ValueError("fused integrator needs tensors on a HIP device")
-    _act_route_ok("ode_integrate", act is not None, kernel, save)
-    method_id, S, tab = method_info(method)
-    _rk_route_ok("ode_integrate", tab, kernel, save)
-    sub_route_ok("ode_integrate", substeps, kernel, save, externals)
+    opts = GenericOpts.of(method, (act,), substeps, externals)
+    opts.require_generic("ode_integrate", kernel, save)
     T, B, xd = t.shape[0], x.shape[1], x.shape[2]
     if x.shape[0] < (T if input_true_x else 1):
         raise ValueError("x has fewer grid points than t")
@@ -100,7 +84,7 @@ def ode_integrate(method, de_layers: Layers, t, x, z, all_initial, event_t=None,
     _check_tb("z", z, T, B)
     keep: list = []
     a = _lib.OdeArgsF32()
-    a.method = method_id
+    a.method = opts.method_id
     a.kernel = KERNEL_ID[kernel]
     a.flags = _lib.FLAG_INPUT_TRUE_X if input_true_x else 0
     a.x_dim, a.z_dim, a.T, a.B = xd, zd, T, B
@@ -128,19 +112,17 @@ def ode_integrate(method, de_layers: Layers, t, x, z, all_initial, event_t=None,
             if Hp <= 0:
                 raise _lib.UnsupportedShapeError("ode_integrate(save=True): the MFMA integrator K1 does not take this shape")
             L = len(de_layers) - 1       # hidden layers: 3 for the no_encode MLPs (K1), 1 for the latent ones at hidden 64 (K3c)
-            saved = (_empty((max(T - 1, 0), S, L, B, Hp), dtype=torch.float32, device=dev),
-                     _empty((max(T - 1, 0), S, B, xd), dtype=torch.float32, device=dev))
+            saved = (_empty((max(T - 1, 0), opts.stages, L, B, Hp), dtype=torch.float32, device=dev),
+                     _empty((max(T - 1, 0), opts.stages, B, xd), dtype=torch.float32, device=dev))
             if T >= 2:
                 a.save_act, a.save_xstage = saved[0].data_ptr(), saved[1].data_ptr()
-        x_sub = _empty((max(T - 1, 0), substeps - 1, B, xd), dtype=torch.float32, device=dev) if save_sub and (substeps > 1 or is_linear(externals)) else None
-        sub = substeps_abi(substeps, x_sub, externals)
+        x_sub = _empty((max(T - 1, 0), substeps - 1, B, xd), dtype=torch.float32, device=dev) if save_sub and opts.family in ("sub", "lin") else None
         ws = _workspace(lib, a.de, None, dev)
         wp, wn = _aligned_ptr(ws)
-        rc = call_entry(lib, "ode_integrate", a, (act,), wp, wn, torch.cuda.current_stream(dev).cuda_stream, tab, sub)
-    entry = f"psnode_ode_integrate_{sub_family(sub)}_f32" if sub is not None else ("psnode_ode_integrate_rk_f32" if tab is not None else "psnode_ode_integrate_f32")
+        rc, entry = call_generic(lib, "ode_integrate", "f32", a, opts, wp, wn, torch.cuda.current_stream(dev).cuda_stream, x_sub=x_sub)
     _mfma_miss(rc, kernel, entry, de_layers)
     _lib.check(rc, entry)
-    if kernel == "auto" and act is None and tab is None and sub is None:
+    if kernel == "auto" and opts.family == "plain":
         _note_k0(lib, a, False, de_layers)
     # the stream-ordered caching allocator keeps `keep`/`ws` storage valid until the kernel has run
     if save_sub:
@@ -182,12 +164,8 @@ def dae_integrate(method, de_layers: Layers, ae_layers: Layers, x_init, t, x, z,
     dev = x_init.device
     if dev.type != "cuda":
         raise ValueError("fused integrator needs tensors on a HIP device")
-    acts = dae_acts(act)
-    non_elu = any(q is not None for q in acts)
-    _act_route_ok("dae_integrate", non_elu, kernel, save)
-    method_id, S, tab = method_info(method)
-    _rk_route_ok("dae_integrate", tab, kernel, save)
-    sub_route_ok("dae_integrate", substeps, kernel, save, externals)
+    opts = GenericOpts.of(method, dae_acts(act), substeps, externals)
+    opts.require_generic("dae_integrate", kernel, save)
     T, B = t.shape[0], t.shape[1]
     xd, zd, vd, idim = x_init.shape[-1], z.shape[-1], v.shape[-1], i.shape[-1]
     if x_init.dim() != 2 or x_init.shape[0] != B:
@@ -201,7 +179,7 @@ def dae_integrate(method, de_layers: Layers, ae_layers: Layers, x_init, t, x, z,
         _check_tb("i", i, T, B)
     keep: list = []
     a = _lib.DaeArgsF32()
-    a.method = method_id
+    a.method = opts.method_id
     a.kernel = KERNEL_ID[kernel]
     a.flags = (_lib.FLAG_INPUT_TRUE_X if input_true_x else 0) | (_lib.FLAG_INPUT_TRUE_I if input_true_i else 0)
     a.x_dim, a.z_dim, a.v_dim, a.i_dim, a.T, a.B = xd, zd, vd, idim, T, B
@@ -240,7 +218,7 @@ def dae_integrate(method, de_layers: Layers, ae_layers: Layers, x_init, t, x, z,
             f32 = dict(dtype=torch.float32, device=dev)
             n_ev = (z_jump if z_jump is not None else v_jump).shape[1] if event_idx is not None else 0
             L = len(de_layers) - 1       # hidden layers: 3 (K2), 1 for the latent shapes at hidden 64 (K3c; i0 rows are then i_dim wide)
-            saved = (_empty((max(T - 1, 0), S, L, B, Hp), **f32), _empty((max(T - 1, 0), S, B, xd), **f32),
+            saved = (_empty((max(T - 1, 0), opts.stages, L, B, Hp), **f32), _empty((max(T - 1, 0), opts.stages, B, xd), **f32),
                      _empty((L, T, B, Hp), **f32),
                      torch.zeros((n_ev, L, B, Hp), **f32) if n_ev else None,
                      torch.zeros((n_ev, B, 16 if L == 3 else idim), **f32) if n_ev else None)
@@ -251,15 +229,13 @@ def dae_integrate(method, de_layers: Layers, ae_layers: Layers, x_init, t, x, z,
                 a.save_act = a.save_xstage = dummy.data_ptr()
             if n_ev:
                 a.save_ev_act, a.save_ev_i = saved[3].data_ptr(), saved[4].data_ptr()
-        x_sub = _empty((max(T - 1, 0), substeps - 1, B, xd), dtype=torch.float32, device=dev) if save_sub and (substeps > 1 or is_linear(externals)) else None
-        sub = substeps_abi(substeps, x_sub, externals)
+        x_sub = _empty((max(T - 1, 0), substeps - 1, B, xd), dtype=torch.float32, device=dev) if save_sub and opts.family in ("sub", "lin") else None
         ws = _workspace(lib, a.de, a.ae, dev)
         wp, wn = _aligned_ptr(ws)
-        rc = call_entry(lib, "dae_integrate", a, acts, wp, wn, torch.cuda.current_stream(dev).cuda_stream, tab, sub)
-    entry = f"psnode_dae_integrate_{sub_family(sub)}_f32" if sub is not None else ("psnode_dae_integrate_rk_f32" if tab is not None else "psnode_dae_integrate_f32")
+        rc, entry = call_generic(lib, "dae_integrate", "f32", a, opts, wp, wn, torch.cuda.current_stream(dev).cuda_stream, x_sub=x_sub)
     _mfma_miss(rc, kernel, entry, de_layers)
     _lib.check(rc, entry)
-    if kernel == "auto" and not non_elu and tab is None and sub is None:
+    if kernel == "auto" and opts.family == "plain":
         _note_k0(lib, a, True, de_layers)
     if save_sub:
         return xs, is_, x_sub

@@ -7,7 +7,7 @@ from typing import Optional
 import torch
 
 from .. import _lib
-from ._common import Layers, builtin_method, no_linear, no_substeps, _aligned_ptr, _empty, _f32_dev, _gemm_tn, _mlp, _view, gemm_tn
+from ._common import GenericOpts, Layers, _aligned_ptr, _empty, _f32_dev, _gemm_tn, _mlp, _view, gemm_tn
 
 def latent_wide_shape(de_layers: Layers, ae_layers: Optional[Layers], x_dim: int, z_dim: int, v_dim: int = 0, i_dim: int = 0) -> bool:
     """The latent shapes of the direct_encode models at a hidden width the dedicated latent kernels do not take (every H <= 128 with
@@ -37,9 +37,7 @@ def latent_backward_wide(method: str, de_layers: Layers, ae_layers: Optional[Lay
     dae = ae_layers is not None
     T, B, H = xs.shape
     zd = z.shape[-1] if z is not None else 0
-    no_substeps(substeps, "latent_backward_wide")
-    no_linear(externals, "latent_backward_wide")
-    method_id, S = builtin_method(method, "latent_backward_wide")
+    method_id, S = GenericOpts.of(method, (None,) * (2 if dae else 1), substeps, externals).require_plain("latent_backward_wide")
     nblk = (4 if zd else 3) if dae else 2
     n = nblk * H
     f32 = dict(dtype=torch.float32, device=dev)

@@ -95,46 +95,37 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
                           "ODE_Event/DAE_Event callbacks; an ExplicitRK tableau, substeps > 1 or externals='linear' on kernel 'auto' / 'generic' only (substeps <= 1024); under autograd also a shape with a backward kernel; teacher-forced "
                           "training: ELU(1), dataset rows without grad) -- stepping through the Python callables instead", RuntimeWarning, stacklevel=3)
 
-    def _act_kernel_ok(self, what, acts) -> bool:
-        """An activation other than ELU(1) runs on the generic kernels K0 / K5 only: kernel 'wave' / 'tile' / 'mfma' / 'wide' with one walks
-        under fused='auto' and raises under 'require'."""
-        if all(a is None for a in acts) or self.kernel in ("auto", "generic"):
+    def _generic_only_ok(self, what, acts) -> bool:
+        """An activation other than ELU(1), a Runge-Kutta tableau (ExplicitRK: `method` is a fused.Tableau), sub-steps per grid interval
+        (up to 1024) and linearly interpolated externals run on the generic kernels K0 / K5 only: kernel 'wave' / 'tile' / 'mfma' / 'wide'
+        with one of them walks under fused='auto' and raises under 'require', naming the first in the order act, tableau, sub-steps,
+        externals (fused.GenericOpts.require_generic's)."""
+        generic = self.kernel in ("auto", "generic")
+        fits = generic and self.substeps <= _fused._lib.MAX_SUBSTEPS
+        if fits:
             return True
-        if self.fused == "require":
+        limits = "(kernel 'auto' / 'generic', substeps <= %d)" % _fused._lib.MAX_SUBSTEPS
+        if not generic and any(a is not None for a in acts):
             names = ", ".join(repr(a) for a in acts if a is not None)
-            raise UnsupportedShapeError(f"{what}: kernel={self.kernel!r} has no form for the activation {names}: activations other than "
-                                        "ELU(alpha=1) run on the generic kernels (kernel 'auto' / 'generic')")
-        return False
-
-    def _rk_kernel_ok(self, what) -> bool:
-        """A Runge-Kutta tableau (ExplicitRK: `method` is a fused.Tableau) runs on the generic kernels K0 / K5 only: kernel 'wave' / 'tile'
-        / 'mfma' / 'wide' with one walks under fused='auto' and raises under 'require'."""
-        if not isinstance(self.method, _fused.Tableau) or self.kernel in ("auto", "generic"):
+            text = f"has no form for the activation {names}: activations other than ELU(alpha=1) run on the generic kernels (kernel 'auto' / 'generic')"
+        elif not generic and isinstance(self.method, _fused.Tableau):
+            text = f"has no form for the Runge-Kutta tableau {self.method.name}: tableaus run on the generic kernels (kernel 'auto' / 'generic')"
+        elif not fits and self.substeps != 1:
+            text = f"with substeps={self.substeps} has no fused form: sub-steps per grid interval run on the generic kernels {limits}"
+        elif not fits and self.externals != "hold":
+            text = f"with externals='linear' has no fused form: interpolated external inputs run on the generic kernels {limits}"
+        else:
             return True
         if self.fused == "require":
-            raise UnsupportedShapeError(f"{what}: kernel={self.kernel!r} has no form for the Runge-Kutta tableau {self.method.name}: "
-                                        "tableaus run on the generic kernels (kernel 'auto' / 'generic')")
+            raise UnsupportedShapeError(f"{what}: kernel={self.kernel!r} {text}")
         return False
 
-    def _sub_kernel_ok(self, what) -> bool:
-        """Sub-steps per grid interval (substeps > 1) run on the generic kernels K0 / K5 only, up to 1024 of them: kernel 'wave' / 'tile' /
-        'mfma' / 'wide' with them walks under fused='auto' and raises under 'require'."""
-        if self.substeps == 1 or (self.kernel in ("auto", "generic") and self.substeps <= _fused._lib.MAX_SUBSTEPS):
-            return True
-        if self.fused == "require":
-            raise UnsupportedShapeError(f"{what}: kernel={self.kernel!r} with substeps={self.substeps} has no fused form: sub-steps per grid "
-                                        f"interval run on the generic kernels (kernel 'auto' / 'generic', substeps <= {_fused._lib.MAX_SUBSTEPS})")
-        return False
-
-    def _lin_kernel_ok(self, what) -> bool:
-        """Linearly interpolated externals (externals='linear') run on the generic kernels K0 / K5 only: kernel 'wave' / 'tile' / 'mfma' /
-        'wide' with them walks under fused='auto' and raises under 'require'."""
-        if self.externals == "hold" or (self.kernel in ("auto", "generic") and self.substeps <= _fused._lib.MAX_SUBSTEPS):
-            return True
-        if self.fused == "require":
-            raise UnsupportedShapeError(f"{what}: kernel={self.kernel!r} with externals='linear' has no fused form: interpolated external "
-                                        f"inputs run on the generic kernels (kernel 'auto' / 'generic', substeps <= {_fused._lib.MAX_SUBSTEPS})")
-        return False
+    def _generic_kwargs(self) -> dict:
+        """substeps= / externals= for the fused calls, left out at 1 / "hold": those calls are then the ones they always were."""
+        kw = dict(substeps=self.substeps) if self.substeps != 1 else {}
+        if self.externals != "hold":
+            kw["externals"] = self.externals
+        return kw
 
     def _step_func_lin(self, func, t0, dt, x0, ext_at, i0=None, all_initial=None):
         """-> dx of one (sub-)step whose stage at abscissa c reads the externals ext_at(c) = (z, v | None): the class's own formula with a
@@ -172,12 +163,9 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
             raise ValueError("integrate_ODE: x_init and input_true_x exclude each other (teacher forcing starts every step from x[k])")
         if self.fused != "off":
             plan = _fused.plan_ode(x_func, x, z, all_initial, event_fn, jump_change_fn, t=t, x_init=x_init)
-            if plan is not None and not (self._act_kernel_ok("integrate_ODE", plan[4:]) and self._rk_kernel_ok("integrate_ODE")
-                                         and self._sub_kernel_ok("integrate_ODE") and self._lin_kernel_ok("integrate_ODE")):
+            if plan is not None and not self._generic_only_ok("integrate_ODE", plan[4:]):
                 plan = None
-            sub = dict(substeps=self.substeps) if self.substeps != 1 else {}      # (substeps == 1: the calls as they always were)
-            if self.externals != "hold":                                          # ("hold" likewise)
-                sub["externals"] = self.externals
+            sub = self._generic_kwargs()
             if plan is not None:
                 layers, event_t, z_jump, needs_grad, act = plan
                 if not needs_grad:
@@ -241,12 +229,9 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
                       input_true_x=False, input_true_i=False):
         if self.fused != "off":
             plan = _fused.plan_dae(x_init, x_func, i_func, z, v, i, all_initial, event_fn, jump_change_fn, t=t)
-            if plan is not None and not (self._act_kernel_ok("integrate_DAE", plan[6:]) and self._rk_kernel_ok("integrate_DAE")
-                                         and self._sub_kernel_ok("integrate_DAE") and self._lin_kernel_ok("integrate_DAE")):
+            if plan is not None and not self._generic_only_ok("integrate_DAE", plan[6:]):
                 plan = None
-            sub = dict(substeps=self.substeps) if self.substeps != 1 else {}
-            if self.externals != "hold":
-                sub["externals"] = self.externals
+            sub = self._generic_kwargs()
             if plan is not None:
                 de, ae, event_t, z_jump, v_jump, needs_grad, de_act, ae_act = plan
                 act = None if de_act is None and ae_act is None else (de_act, ae_act)

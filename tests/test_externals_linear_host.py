@@ -533,20 +533,21 @@ def test_python_predicates_refusals_and_the_constructor():
         fused.dae_backward_wide("rk4", de, ae, None, None, None, None, torch.zeros(2, 1, 8), torch.zeros(2, 1, 2), None, None, **lin)
     with pytest.raises(_lib.UnsupportedShapeError):
         fused.latent_backward_wide("rk4", ode01, None, None, None, None, None, torch.zeros(2, 1, 16), None, None, None, saved=(), **lin)
+    opts = lambda substeps, externals: fused.GenericOpts.of("rk4", (None,), substeps, externals)
     with pytest.raises(_lib.UnsupportedShapeError):
-        fused.no_linear("linear", "a specialised entry")
-    fused.no_linear("hold", "a specialised entry")
+        opts(1, "linear").require_plain("a specialised entry")
+    opts(1, "hold").require_plain("a specialised entry")
     with pytest.raises(ValueError):
-        fused.no_linear("cubic", "a specialised entry")
+        opts(1, "cubic")
     for kernel, save in (("wave", False), ("mfma", False), ("auto", True)):
         with pytest.raises(_lib.UnsupportedShapeError, match="externals"):
-            fused.sub_route_ok("x", 1, kernel, save, "linear")
-    fused.sub_route_ok("x", 1, "generic", False, "linear")
-    fused.sub_route_ok("x", 1, "wave", True, "hold")
-    assert fused.substeps_abi(1) is None and fused.substeps_abi(1, None, "hold") is None
-    one = fused.substeps_abi(1, None, "linear")
-    assert one.substeps == 1 and not one.x_sub and fused.sub_family(one) == "lin" and fused.sub_family(fused.substeps_abi(5)) == "sub"
-    assert fused.sub_family(fused.substeps_abi(5, None, "linear")) == "lin"
+            opts(1, "linear").require_generic("x", kernel, save)
+    opts(1, "linear").require_generic("x", "generic", False)
+    opts(1, "hold").require_generic("x", "wave", True)
+    assert opts(1, "hold").family == "plain" and opts(1, "hold").c_args() == []
+    one = opts(1, "linear").c_args()[-1]._obj
+    assert one.substeps == 1 and not one.x_sub and opts(1, "linear").family == "lin" and opts(5, "hold").family == "sub"
+    assert opts(5, "linear").family == "lin"
     # the constructor: "hold" | "linear", reached through **kw by every solver class
     for cls in (nd.Euler, nd.Midpoint, nd.RK4, nd.Heun2, nd.Kutta3, nd.RK4Classic):
         assert cls().externals == "hold" and cls(externals="linear").externals == "linear" and cls(externals="hold").externals == "hold"
@@ -567,17 +568,25 @@ def test_routing_of_linear_externals_next_to_a_forced_kernel():
             for n in (1, 3):
                 s = cls(substeps=n, externals="linear")
                 s.kernel, s.fused = kernel, "require"
-                assert s._lin_kernel_ok("integrate_ODE") and s._sub_kernel_ok("integrate_ODE") and s._rk_kernel_ok("integrate_ODE")
+                assert s._generic_only_ok("integrate_ODE", (None,))
         for kernel in ("wave", "tile", "mfma", "wide"):
             s = cls(externals="linear")
             s.kernel, s.fused = kernel, "auto"
-            assert not s._lin_kernel_ok("integrate_ODE")
+            assert not s._generic_only_ok("integrate_ODE", (None,))
             s.fused = "require"
-            with pytest.raises(_lib.UnsupportedShapeError, match="externals"):
-                s._lin_kernel_ok("integrate_ODE")
+            with pytest.raises(_lib.UnsupportedShapeError, match="externals" if cls is nd.RK4 else "tableau"):      # (the Tableau comes first)
+                s._generic_only_ok("integrate_ODE", (None,))
             h = cls()
             h.kernel, h.fused = kernel, "require"
-            assert h._lin_kernel_ok("integrate_ODE")              # "hold": nothing to say
+            if cls is nd.RK4:
+                assert h._generic_only_ok("integrate_ODE", (None,))              # "hold": nothing to say
+            else:
+                with pytest.raises(_lib.UnsupportedShapeError, match="tableau"):
+                    h._generic_only_ok("integrate_ODE", (None,))
+        s = cls(substeps=1025, externals="linear")              # too many sub-steps next to "linear": the sub-steps are named first
+        s.kernel, s.fused = "auto", "require"
+        with pytest.raises(_lib.UnsupportedShapeError, match="substeps"):
+            s._generic_only_ok("integrate_ODE", (None,))
     # a direct_encode model with a "linear" solver does not take the one-launch encoded forward
     m = models.ODE_Model(8, 2, 16, direct_encode=True, solver=nd.RK4(externals="linear"))
     t = torch.zeros(3, 4, 1)

@@ -289,7 +289,7 @@ def test_null_act_is_the_elu1_entry_point(monkeypatch):
     c = lambda a: a.cuda()
     a0 = torch.cat((x[0], z[0]), -1).cuda()
     ref = fused.ode_integrate("rk4", layers, c(t), c(x), c(z), a0, event_t=c(ev), z_jump=c(zj), kernel="generic")
-    monkeypatch.setattr(_common, "_act_refs", lambda *a: ([None], True))
+    monkeypatch.setattr(_common, "_act_ptrs", lambda acts: [None])
     got = fused.ode_integrate("rk4", layers, c(t), c(x), c(z), a0, event_t=c(ev), z_jump=c(zj), kernel="generic", act=object())
     elu1 = fused.Act(fused._lib.ACT_ELU, alpha=1.0)
     monkeypatch.undo()

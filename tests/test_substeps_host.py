@@ -423,18 +423,21 @@ def test_python_predicates_refusals_and_the_constructor():
         fused.dae_backward_wide("rk4", de, ae, None, None, None, None, torch.zeros(2, 1, 8), torch.zeros(2, 1, 2), None, None, substeps=2)
     with pytest.raises(_lib.UnsupportedShapeError):
         fused.latent_backward_wide("rk4", ode01, None, None, None, None, None, torch.zeros(2, 1, 16), None, None, None, saved=(), substeps=2)
+    opts = lambda substeps: fused.GenericOpts.of("rk4", (None,), substeps)
     with pytest.raises(_lib.UnsupportedShapeError):
-        fused.no_substeps(2, "a specialised entry")
-    fused.no_substeps(1, "a specialised entry")
+        opts(2).require_plain("a specialised entry")
+    opts(1).require_plain("a specialised entry")
     for kernel, save in (("wave", False), ("mfma", False), ("auto", True)):
         with pytest.raises(_lib.UnsupportedShapeError):
-            fused.sub_route_ok("x", 2, kernel, save)
-    fused.sub_route_ok("x", 2, "generic", False)
-    fused.sub_route_ok("x", 1, "wave", True)
-    assert fused.substeps_abi(1) is None and fused.substeps_abi(5).substeps == 5 and not fused.substeps_abi(5).x_sub
+            opts(2).require_generic("x", kernel, save)
+    opts(2).require_generic("x", "generic", False)
+    opts(1).require_generic("x", "wave", True)
+    assert opts(1).family == "plain" and opts(1).c_args() == [] and opts(5).family == "sub"
+    five = opts(5).c_args()[-1]._obj          # (ode: act, tableau, psnode_substeps_f32)
+    assert opts(5).c_args()[:2] == [None, None] and five.substeps == 5 and not five.x_sub
     for bad in (0, -1, 1025, 2.0, True, None, "2"):
         with pytest.raises(ValueError):
-            fused.substeps_abi(bad)
+            opts(bad)
     # the constructor: an int >= 1, reached through **kw by every solver class
     for cls in (nd.Euler, nd.Midpoint, nd.RK4, nd.Heun2, nd.Kutta3, nd.RK4Classic):
         assert cls().substeps == 1 and cls(substeps=4).substeps == 4
@@ -446,23 +449,32 @@ def test_python_predicates_refusals_and_the_constructor():
 
 
 def test_routing_of_substeps_next_to_a_tableau_and_a_forced_kernel():
-    """The solver's route predicates, from the attributes alone: 'auto' / 'generic' keep a call fusable, a specialised kernel or more than
-    1024 sub-steps walks under fused = 'auto' and raises under 'require' -- for a built-in method and for a Tableau alike."""
+    """The solver's route predicate, from the attributes alone: 'auto' / 'generic' keep a call fusable, a specialised kernel or more than
+    1024 sub-steps walks under fused = 'auto' and raises under 'require' -- for a built-in method and for a Tableau alike (on a specialised
+    kernel the Tableau is what the one predicate names first, as integrate_ODE's chain of four always did)."""
     for cls in (nd.RK4, nd.Kutta3):
         for kernel in ("auto", "generic"):
             s = cls(substeps=3)
             s.kernel, s.fused = kernel, "require"
-            assert s._sub_kernel_ok("integrate_ODE") and s._rk_kernel_ok("integrate_ODE")
+            assert s._generic_only_ok("integrate_ODE", (None,))
         for kernel, sub in (("wave", 3), ("tile", 2), ("mfma", 2), ("wide", 4), ("auto", 1025)):
             s = cls(substeps=sub)
             s.kernel, s.fused = kernel, "auto"
-            assert not s._sub_kernel_ok("integrate_ODE")
+            assert not s._generic_only_ok("integrate_ODE", (None,))
             s.fused = "require"
-            with pytest.raises(_lib.UnsupportedShapeError, match="substeps"):
-                s._sub_kernel_ok("integrate_ODE")
+            with pytest.raises(_lib.UnsupportedShapeError, match="substeps" if cls is nd.RK4 or kernel == "auto" else "tableau"):
+                s._generic_only_ok("integrate_ODE", (None,))
         s = cls()
         s.kernel, s.fused = "wave", "require"
-        assert s._sub_kernel_ok("integrate_ODE")              # substeps == 1: nothing to say
+        if cls is nd.RK4:
+            assert s._generic_only_ok("integrate_ODE", (None,))              # substeps == 1: nothing to say
+        else:
+            with pytest.raises(_lib.UnsupportedShapeError, match="tableau"):
+                s._generic_only_ok("integrate_ODE", (None,))
+        s = nd.Kutta3(substeps=3)              # the order of complaint: act, tableau, sub-steps
+        s.kernel, s.fused = "wave", "require"
+        with pytest.raises(_lib.UnsupportedShapeError, match="activation"):
+            s._generic_only_ok("integrate_ODE", (fused.Act(_lib.ACT_TANH, name="Tanh"),))
     # a direct_encode model with sub-steps does not take the one-launch encoded forward
     m = models.ODE_Model(8, 2, 16, direct_encode=True, solver=nd.RK4(substeps=2))
     t = torch.zeros(3, 4, 1)
