@@ -503,17 +503,21 @@ bool bwd_x_preferred(const psnode_ode_bwd_args_f32* a) {
     if (a->z_dim > 0 && a->event_idx && a->z_jump && !span32_ok(a->B, a->zj_stride_b, a->z_dim)) return false;
     return a->kernel == PSNODE_KERNEL_MFMA_WAVE || a->B <= 4608;
 }
-size_t bwd_x_workspace_floats(const psnode_ode_bwd_args_f32* a) {
-    const size_t tiles = (size_t)((a->B + 3) / 4);
-    return (size_t)BXRegs::COUNT * 64 + (tiles + 1) * (size_t)BXPart::COUNT * 64 + 256;
+// K4x's workspace: the register image | one partial vector per tile of 4 trajectories | their sum (scatter_bx_kernel reads it)
+struct BwdXLayout { float *pack, *wpart, *red; };
+static BwdXLayout bwd_x_layout(long long B, Arena& A) {
+    const size_t tiles = (size_t)((B + 3) / 4), part = (size_t)BXPart::COUNT * 64;
+    BwdXLayout L{A.take((size_t)BXRegs::COUNT * 64), A.take(tiles * part), A.take(part)};
+    A.slack(256);      // kept from the parent, purpose not established
+    return L;
 }
+size_t bwd_x_workspace_floats(const psnode_ode_bwd_args_f32* a) { Arena A; bwd_x_layout(a->B, A); return A.floats(); }
 
 int bwd_x_launch(const psnode_ode_bwd_args_f32* p, float* workspace, hipStream_t s) {
     const int xd = p->x_dim, zd = p->z_dim, n = xd + zd, HR = p->de.out_dim[0];
-    float* pack = workspace;
-    float* wpart = pack + (size_t)BXRegs::COUNT * 64;
+    Arena A{workspace};
+    const auto [pack, wpart, red] = bwd_x_layout(p->B, A);
     const long long tiles = (p->B + 3) / 4;
-    float* red = wpart + (size_t)tiles * BXPart::COUNT * 64;
     PackBX pk{xd, zd, n, HR, p->de.weight[0], p->de.weight[1], p->de.weight[2], p->de.weight[3], pack};
     hipLaunchKernelGGL(pack_bx_kernel, dim3(16), dim3(256), 0, s, pk);
     if (hipGetLastError() != hipSuccess) return PSNODE_ERR_HIP;

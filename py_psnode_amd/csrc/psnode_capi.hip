@@ -1,4 +1,4 @@
-// C ABI of libpsnode_hip.so (see include/psnode_hip.h): argument validation, workspace carving,
+// C ABI of libpsnode_hip.so (see include/psnode_hip.h): argument validation, the forward workspace's layout (psnode_workspace.h),
 // weight packing and kernel dispatch.  Everything is enqueued on the caller's stream.
 #include <math.h>
 #include <stdio.h>
@@ -12,17 +12,6 @@ namespace {
 constexpr size_t kAlignFloats = 64;   // 256-byte alignment of every workspace segment
 
 inline size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-size_t generic_floats(const psnode_mlp_f32* m) {
-    if (!m) return 0;
-    size_t tot = 0;
-    int k = m->in_dim;
-    for (int l = 0; l < m->n_layers; ++l) {
-        tot += round_up(generic_image_floats(k, m->out_dim[l]), kAlignFloats);
-        k = m->out_dim[l];
-    }
-    return tot;
-}
 
 // the widths alone (the dims-only queries); `ptrs`: also every layer's weight and bias, in check_mlp's order of statuses
 int check_mlp_dims(const psnode_mlp_f32& m, int want_in, int want_out, bool ptrs = false) {
@@ -39,8 +28,8 @@ int check_mlp_dims(const psnode_mlp_f32& m, int want_in, int want_out, bool ptrs
 }
 int check_mlp(const psnode_mlp_f32& m, int want_in, int want_out) { return check_mlp_dims(m, want_in, want_out, true); }
 
-// Fills `d` and assigns the transposed-weight segments; returns the next free float of the workspace.
-float* bind_mlp(const psnode_mlp_f32& m, MlpDev& d, float* ws) {
+// Fills `d` and takes the MLP's image segments (K0's MFMA images, one per layer).
+void bind_mlp(const psnode_mlp_f32& m, MlpDev& d, Arena& A) {
     d.n_layers = m.n_layers;
     d.in_dim = m.in_dim;
     int k = m.in_dim;
@@ -48,11 +37,18 @@ float* bind_mlp(const psnode_mlp_f32& m, MlpDev& d, float* ws) {
         d.out_dim[l] = m.out_dim[l];
         d.w[l] = m.weight[l];
         d.bias[l] = m.bias[l];
-        d.wt[l] = ws;
-        ws += round_up(generic_image_floats(k, m.out_dim[l]), kAlignFloats);
+        d.wt[l] = A.take(round_up(generic_image_floats(k, m.out_dim[l]), kAlignFloats));
         k = m.out_dim[l];
     }
-    return ws;
+}
+// The forward workspace: K0's images of the DE | of the AE | the pack of the MFMA family that takes the shape (sized for the largest of
+// them: psnode_mfma.hip).  Returns the pack.
+float* forward_layout(const psnode_mlp_f32& de, const psnode_mlp_f32* ae, MlpDev& dde, MlpDev& dae, Arena& A) {
+    bind_mlp(de, dde, A);
+    if (ae) bind_mlp(*ae, dae, A);
+    float* pack = A.take(mfma_pack_floats(&de, ae));
+    A.slack(kAlignFloats);      // kept from the parent, purpose not established (every segment in front of it is a multiple of 64 floats)
+    return pack;
 }
 
 int max_width(const psnode_mlp_f32& m) {
@@ -99,9 +95,8 @@ int dispatch(IntegrateDev& d, bool dae, int kernel, const psnode_mlp_f32* de, co
              size_t workspace_bytes, hipStream_t stream, const K0Call& call) {
     if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 255u)) return PSNODE_ERR_WORKSPACE;
     if (workspace_bytes < psnode_workspace_bytes(de, ae)) return PSNODE_ERR_WORKSPACE;
-    float* ws = static_cast<float*>(workspace);
-    ws = bind_mlp(*de, d.de, ws);
-    if (dae) ws = bind_mlp(*ae, d.ae, ws);
+    Arena A{static_cast<float*>(workspace)};
+    float* pack = forward_layout(*de, dae ? ae : nullptr, d.de, d.ae, A);
     d.maxw = max_width(*de);
     if (dae && max_width(*ae) > d.maxw) d.maxw = max_width(*ae);
     d.maxo = max_out_width(*de, dae ? ae : nullptr);
@@ -113,7 +108,7 @@ int dispatch(IntegrateDev& d, bool dae, int kernel, const psnode_mlp_f32* de, co
     d.kern = kernel;
     const bool use_mfma = has_mfma && kernel != PSNODE_KERNEL_GENERIC;
     if (d.T < 1 || d.B < 1) return PSNODE_ERR_DIMS;
-    if (use_mfma) return launch_mfma(d, dae, ws, stream) == hipSuccess ? PSNODE_OK : PSNODE_ERR_HIP;
+    if (use_mfma) return launch_mfma(d, dae, pack, stream) == hipSuccess ? PSNODE_OK : PSNODE_ERR_HIP;
 
     if (generic_lds_bytes(d, dae, call.build == K0Call::kLin) > 160 * 1024) return PSNODE_ERR_UNSUPPORTED;
     hipError_t e = launch_pack_image(d.de, dae ? &d.ae : nullptr, d.xd, d.xd + d.zd + (dae ? d.vd + d.id : 0), d.zd + (dae ? d.vd : 0), stream);
@@ -401,9 +396,10 @@ const char* psnode_status_string(int32_t s) {
 }
 
 size_t psnode_workspace_bytes(const psnode_mlp_f32* de, const psnode_mlp_f32* ae) {
-    if (!de) return 0;
-    const size_t f = generic_floats(de) + generic_floats(ae) + mfma_pack_floats(de, ae) + kAlignFloats;
-    return f * sizeof(float);
+    if (!de || de->n_layers > kMaxLayers || (ae && ae->n_layers > kMaxLayers)) return 0;      // (the layout fills an MlpDev per MLP)
+    MlpDev dde, dae;
+    Arena A;
+    return forward_layout(*de, ae, dde, dae, A), A.bytes();
 }
 
 int32_t psnode_event_table_f32(int64_t n_steps, const float* clock, int64_t stride_k, const float* event_times,

@@ -5,6 +5,7 @@
 
 #include "psnode_generic_build.h"
 #include "psnode_hip.h"
+#include "psnode_workspace.h"
 
 namespace psnode {
 

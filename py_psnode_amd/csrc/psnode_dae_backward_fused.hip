@@ -1473,7 +1473,6 @@ int k7f_np(int hr, int xd, int ne) { const int n = xd + ne; return hr * 3 * n + 
 int k7f_npa(int nw, bool saved, int hr, int xd, int nzv, int ne) {
     return (nw <= 4 && saved) ? hr * (xd + ne + xd + nzv) + hr + 2 * (hr * hr + hr) + 16 * hr + 16 : 0;
 }
-size_t k7f_fwd_floats(int nw, int n) { return ((wide_fwd_floats(nw, n) + 63) / 64) * 64; }
 
 template <int METHOD, int NWV>
 hipError_t launch_k7f(const FusedDaeDev& a, int NZM, int NZA, const float* pde, const float* pae, const f4* pt, const f4* pf, const f4* pta,
@@ -1515,12 +1514,20 @@ hipError_t launch_k7f_method(const FusedDaeDev& a, int NZM, int NZA, const float
 }  // namespace
 
 // ---- entry points used by psnode_dae_backward_wide.hip (C ABI psnode_dae_backward_wide_f32 with grad_params_de set)
-size_t dae_fused_bwd_workspace_floats(const psnode_dae_bwd_wide_args_f32* p) {
-    const int nw = wide_hidden(p->de) / 16, ne = p->z_dim + p->v_dim + p->i_dim, n = p->x_dim + ne;
+// K7f's workspace: the forward images of the DE | of the AE | the transposed and plain tile images of the DE's W2, W3 | of the AE's | one
+// DE partial vector per workgroup | one AE-head partial vector per workgroup (<= 4 waves with saved rows) | the ring (8 waves only)
+struct K7fLayout { float *pde, *pae; f4 *pt, *pf, *pta, *pfa; float *wpart, *wpart_ae, *ring; };
+K7fLayout k7f_layout(const psnode_dae_bwd_wide_args_f32* p, Arena& A) {
+    const int nw = wide_hidden(p->de) / 16, nzv = p->z_dim + p->v_dim, ne = nzv + p->i_dim, n = p->x_dim + ne, HR = p->de.out_dim[0];
     const size_t nwg = (size_t)((p->B + TBM - 1) / TBM);
-    return 2 * k7f_fwd_floats(nw, n) + 4 * wide_t_floats(nw) + ((nwg * k7f_np(p->de.out_dim[0], p->x_dim, ne) + 63) / 64) * 64 +
-           ((nwg * k7f_npa(nw, p->saved_act != nullptr, p->de.out_dim[0], p->x_dim, p->z_dim + p->v_dim, ne) + 63) / 64) * 64 + k7f_ring_floats(nw, p->method, p->B) + 256;
+    auto tiles = [&] { return reinterpret_cast<f4*>(A.take(wide_t_floats(nw), 64)); };
+    K7fLayout L{A.take(wide_fwd_floats(nw, n)), A.take(wide_fwd_floats(nw, n), 64), tiles(), tiles(), tiles(), tiles(),
+                A.take(nwg * k7f_np(HR, p->x_dim, ne)), A.take(nwg * k7f_npa(nw, p->saved_act != nullptr, HR, p->x_dim, nzv, ne), 64),
+                A.take(k7f_ring_floats(nw, p->method, p->B), 64)};
+    A.slack(256);      // kept from the parent, purpose not established
+    return L;
 }
+size_t dae_fused_bwd_workspace_floats(const psnode_dae_bwd_wide_args_f32* p) { Arena A; k7f_layout(p, A); return A.floats(); }
 // floats of psnode_dae_bwd_wide_args_f32::grad_params_ae_raw (0: this width leaves the AE head's contractions to the caller, K7h)
 size_t dae_fused_bwd_ae_floats(const psnode_dae_bwd_wide_args_f32* p) {
     const int nw = wide_hidden(p->de) / 16;
@@ -1531,17 +1538,10 @@ int dae_fused_bwd_launch(const psnode_dae_bwd_wide_args_f32* p, float* workspace
     const int H = wide_hidden(p->de), nw = H / 16, xd = p->x_dim, zd = p->z_dim, vd = p->v_dim, id = p->i_dim, HR = p->de.out_dim[0];
     const int nzv = zd + vd, ne = nzv + id, n = xd + ne;
     const int NZM = (2 * ne + 3) / 4, NZA = (nzv + 3) / 4, NA = (n + 3) / 4;
-    float* pde = workspace;
-    float* pae = pde + k7f_fwd_floats(nw, n);
-    f4* pt = reinterpret_cast<f4*>(pae + k7f_fwd_floats(nw, n));
-    f4* pf = pt + wide_t_floats(nw) / 4;
-    f4* pta = pf + wide_t_floats(nw) / 4;
-    f4* pfa = pta + wide_t_floats(nw) / 4;
-    float* wpart = reinterpret_cast<float*>(pfa + wide_t_floats(nw) / 4);
+    Arena A{workspace};
+    const auto [pde, pae, pt, pf, pta, pfa, wpart, wpart_ae, ring] = k7f_layout(p, A);
     const size_t nwg = (size_t)((p->B + TBM - 1) / TBM);
     const int NP = k7f_np(HR, xd, ne), NPA = k7f_npa(nw, p->saved_act != nullptr, HR, xd, nzv, ne);
-    float* wpart_ae = wpart + ((nwg * NP + 63) / 64) * 64;
-    float* ring = wpart_ae + ((nwg * NPA + 63) / 64) * 64;
     if (NPA > 0 && !p->grad_params_ae_raw) return PSNODE_ERR_NULL;
     PackMfma f;
     memset(&f, 0, sizeof(f));

@@ -145,7 +145,7 @@ hipError_t launch_pack_plain_images(const MlpDev& m, float* const* img, float* c
     return hipGetLastError();
 }
 
-// floats of the generic forward's workspace segment of one layer (psnode_capi.hip carves the workspace with it)
+// floats of the generic forward's workspace segment of one layer (psnode_capi.hip: bind_mlp takes one per layer)
 size_t generic_image_floats(int K, int N) { return image_floats(K, N); }
 
 // the MFMA images of one or two MLPs (d.wt[l] = the layer's segment, generic_image_floats each), one launch

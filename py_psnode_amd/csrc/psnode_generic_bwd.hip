@@ -23,9 +23,12 @@ template int generic_backward_launch<Bd>(const GenericBwdCall&, const ActPair*, 
 
 // shared by the ODE and DAE entry points (psnode_backward.hip calls this for kernel = generic / unsupported MFMA shapes)
 size_t generic_bwd_workspace_floats(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, long long B) {
-    const size_t nwg = (size_t)((B + TB - 1) / TB);
-    return mlp_wt_floats(*de) + (ae ? mlp_wt_floats(*ae) : 0) + nwg * (size_t)(mlp_np(*de) + (ae ? mlp_np(*ae) : 0)) + 64 +
-           reg_image_floats(*de) + 64 + (ae ? reg_image_floats(*ae) + 64 : 0) + nwg * tm_floats(*de, ae) + 64;
+    GBwd a;
+    memset(&a, 0, sizeof(a));
+    fill_gmlp(*de, a.de);
+    if (ae) fill_gmlp(*ae, a.ae);
+    Arena A;
+    return gbwd_layout(*de, ae, B, a, A), A.floats();
 }
 
 // (the pre fields, which this object's GBwd does not have, are written by a launch only: the fit reads none of them)
@@ -33,11 +36,10 @@ int generic_bwd_fits(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, int xd,
     GBwd a;
     memset(&a, 0, sizeof(a));
     a.dae = ae != nullptr; a.xd = xd; a.zd = zd; a.vd = vd; a.id = id;
-    float* ws = nullptr;
-    int rows = fill_gmlp(*de, a.de, ws);
+    int rows = fill_gmlp(*de, a.de);
     a.maxw = mlp_maxw(*de);
     if (ae) {
-        const int r2 = fill_gmlp(*ae, a.ae, ws);
+        const int r2 = fill_gmlp(*ae, a.ae);
         rows = r2 > rows ? r2 : rows;
         a.maxw = mlp_maxw(*ae) > a.maxw ? mlp_maxw(*ae) : a.maxw;
     }

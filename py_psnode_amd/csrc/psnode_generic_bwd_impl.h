@@ -659,7 +659,8 @@ __device__ __forceinline__ float* g_vjp_str(const GMlp& m, const float* const* t
 // (the six kernels: psnode_generic_bwd{,_act,_pre,_rk,_sub,_lin}.hip around psnode_generic_bwd_body.h)
 template <class B> struct GenericBwdKernels;      // the kernels of policy B, by their template arguments: specialised by the object that defines them
 
-int fill_gmlp(const psnode_mlp_f32& m, GMlp& g, float*& ws) {
+// (g.wt, the transposed weights of the forward recomputation, are workspace segments: gbwd_layout)
+int fill_gmlp(const psnode_mlp_f32& m, GMlp& g) {
     g.L = m.n_layers;
     g.in_dim = m.in_dim;
     int k = m.in_dim, off = 0, rows = 0;
@@ -669,8 +670,6 @@ int fill_gmlp(const psnode_mlp_f32& m, GMlp& g, float*& ws) {
         g.out_dim[l] = m.out_dim[l];
         g.w[l] = m.weight[l];
         g.b[l] = m.bias[l];
-        g.wt[l] = ws;
-        ws += ((size_t)k * m.out_dim[l] + 63) / 64 * 64;
         g.gw[l] = off; off += m.out_dim[l] * k;
         g.gb[l] = off; off += m.out_dim[l];
         g.act[l + 1] = rows;
@@ -726,25 +725,32 @@ bool de_reg_class(const psnode_mlp_f32& de) {
         if (de.out_dim[l] > 64) return false;
     return true;
 }
-size_t tm_floats(const psnode_mlp_f32& de, const psnode_mlp_f32* ae) {      // one workgroup's tile-major global accumulators (both MLPs)
-    size_t tot = 0;
-    for (int m = 0; m < (ae ? 2 : 1); ++m) {
-        const psnode_mlp_f32& mm = m ? *ae : de;
-        size_t t = 0;
-        int k = mm.in_dim;
-        for (int l = 0; l < mm.n_layers; ++l) { t += (size_t)up16(mm.out_dim[l]) * up16(k) + mm.out_dim[l]; k = mm.out_dim[l]; }
-        tot += (t + 3) & ~(size_t)3;
-    }
-    return tot;
-}
-size_t reg_image_floats(const psnode_mlp_f32& de) {       // plain + transposed images of every layer
-    size_t tot = 0;
-    int k = de.in_dim;
-    for (int l = 0; l < de.n_layers; ++l) {
-        tot += (generic_image_floats(k, de.out_dim[l]) + 63) / 64 * 64 + (generic_image_floats(de.out_dim[l], k) + 63) / 64 * 64;
-        k = de.out_dim[l];
-    }
-    return tot;
+// K5's workspace, per MLP m (0 the DE, 1 the AE) and layer: the transposed weights of both MLPs | the plain and the transposed MFMA images
+// of both (register / streamed paths) | one natural-order partial vector per workgroup (both MLPs) | one tile-major accumulator slice per
+// workgroup (tm_total of both MLPs: the paths with global accumulators).  `a` (filled: fill_gmlp) gets the segments it carries.
+struct GBwdLayout { float *img[2][kMaxLayers], *imgT[2][kMaxLayers]; };
+inline size_t up64(size_t v) { return (v + 63) / 64 * 64; }
+GBwdLayout gbwd_layout(const psnode_mlp_f32& de, const psnode_mlp_f32* ae, long long B, GBwd& a, Arena& A) {
+    const size_t nwg = (size_t)((B + TB - 1) / TB);
+    const psnode_mlp_f32* mlp[2] = {&de, ae};
+    GMlp* g[2] = {&a.de, &a.ae};
+    GBwdLayout L{};
+    for (int m = 0; m < (ae ? 2 : 1); ++m)
+        for (int l = 0, k = mlp[m]->in_dim; l < mlp[m]->n_layers; k = mlp[m]->out_dim[l++])
+            g[m]->wt[l] = A.take(up64((size_t)k * mlp[m]->out_dim[l]));
+    for (int m = 0; m < (ae ? 2 : 1); ++m)
+        for (int l = 0, k = mlp[m]->in_dim; l < mlp[m]->n_layers; k = mlp[m]->out_dim[l++]) {
+            L.img[m][l] = A.take(up64(generic_image_floats(k, mlp[m]->out_dim[l])), 64);
+            L.imgT[m][l] = A.take(up64(generic_image_floats(mlp[m]->out_dim[l], k)));
+        }
+    a.wpart = A.take(nwg * (size_t)(a.de.np + (ae ? a.ae.np : 0)));
+    // The parent's size paid a whole 64 floats for each of its pointer round-ups (in front of the images -- which consumes nothing, the
+    // segments before it being multiples of 64 -- and in front of the tile-major slices) and one more per MLP's images; bytes are kept, so
+    // what the one real round-up leaves of them is stated as the remainder.  Beyond the round-ups: kept from the parent, purpose not established.
+    const size_t tm_pad = A.pad(64);
+    a.tmpart = A.take(nwg * (size_t)(tm_total(a.de) + (ae ? tm_total(a.ae) : 0)), 64);
+    A.slack((ae ? 4 : 3) * 64 - tm_pad);
+    return L;
 }
 // 1: everything in LDS; 2: only with the parameter-gradient accumulators in global memory; 0: does not fit.  a.de_reg (the DE's class
 // allows the register path) is kept when its quad-row buffers fit next to the LDS accumulators, else dropped.
@@ -774,12 +780,6 @@ int mlp_maxw(const psnode_mlp_f32& m) {
     for (int l = 0; l < m.n_layers; ++l) w = m.out_dim[l] > w ? m.out_dim[l] : w;
     return w;
 }
-size_t mlp_wt_floats(const psnode_mlp_f32& m) {
-    size_t tot = 0;
-    int k = m.in_dim;
-    for (int l = 0; l < m.n_layers; ++l) { tot += ((size_t)k * m.out_dim[l] + 63) / 64 * 64; k = m.out_dim[l]; }
-    return tot;
-}
 bool mlp_ok(const psnode_mlp_f32& m, int in_dim, int out_dim) {
     if (m.n_layers < 1 || m.n_layers > kMaxLayers || m.in_dim != in_dim || m.out_dim[m.n_layers - 1] != out_dim) return false;
     for (int l = 0; l < m.n_layers; ++l)
@@ -802,11 +802,10 @@ int generic_backward_launch(const GenericBwdCall& c, const ActPair* act, float* 
     GBwd a;
     memset(&a, 0, sizeof(a));
     a.method = c.method; a.dae = dae; a.xd = c.xd; a.zd = c.zd; a.vd = c.vd; a.id = c.id; a.T = c.T; a.B = B;
-    float* ws = workspace;
-    int rows = fill_gmlp(*de, a.de, ws);
+    int rows = fill_gmlp(*de, a.de);
     a.maxw = mlp_maxw(*de);
     if (dae) {
-        const int r2 = fill_gmlp(*ae, a.ae, ws);
+        const int r2 = fill_gmlp(*ae, a.ae);
         rows = r2 > rows ? r2 : rows;
         a.maxw = mlp_maxw(*ae) > a.maxw ? mlp_maxw(*ae) : a.maxw;
     }
@@ -816,27 +815,9 @@ int generic_backward_launch(const GenericBwdCall& c, const ActPair* act, float* 
     a.gzj = c.gzj; a.gvj = c.gvj; a.ga0 = c.ga0;
     a.flags = c.flags; a.xt = dae ? c.xt : c.xs; a.it = c.it;
     a.de_reg = de_reg_class(*de) ? 1 : 0;
-    float* img[kMaxLayers] = {}, *imgT[kMaxLayers] = {}, *imgA[kMaxLayers] = {}, *imgTA[kMaxLayers] = {};
-    {                           // the plain / transposed images of both MLPs sit in front of the per-workgroup partials
-        ws = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~(uintptr_t)255);
-        for (int m = 0; m < (dae ? 2 : 1); ++m) {
-            const psnode_mlp_f32* mm = m ? ae : de;
-            int k = mm->in_dim;
-            for (int l = 0; l < mm->n_layers; ++l) {
-                float* f = ws; ws += (generic_image_floats(k, mm->out_dim[l]) + 63) / 64 * 64;
-                float* t_ = ws; ws += (generic_image_floats(mm->out_dim[l], k) + 63) / 64 * 64;
-                if (m) { imgA[l] = f; imgTA[l] = t_; a.fimgA[l] = f; a.timgA[l] = t_; }
-                else { img[l] = f; imgT[l] = t_; a.fimg[l] = f; a.timg[l] = t_; }
-                k = mm->out_dim[l];
-            }
-        }
-    }
-    a.wpart = ws;
-    {
-        const size_t nwg_ = (size_t)((B + TB - 1) / TB);
-        float* tm = ws + nwg_ * (size_t)(a.de.np + (dae ? a.ae.np : 0));
-        a.tmpart = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(tm) + 255) & ~(uintptr_t)255);
-    }
+    Arena A{workspace};
+    const GBwdLayout L = gbwd_layout(*de, ae, B, a, A);
+    for (int l = 0; l < kMaxLayers; ++l) { a.fimg[l] = L.img[0][l]; a.timg[l] = L.imgT[0][l]; a.fimgA[l] = L.img[1][l]; a.timgA[l] = L.imgT[1][l]; }
     if (!gbwd_mode(a, Pol::pre, Pol::lin)) return PSNODE_ERR_UNSUPPORTED;
     const size_t lds = gbwd_lds_floats(a, Pol::pre, Pol::lin) * sizeof(float);
     place_u_region<Pol::pre>(a, gbwd_lds_floats(a, Pol::pre, Pol::lin), pre_floats(a));
@@ -851,8 +832,8 @@ int generic_backward_launch(const GenericBwdCall& c, const ActPair* act, float* 
     to_dev(a.de, mde);
     if (dae) to_dev(a.ae, mae);
     if (launch_pack_transpose(mde, dae ? &mae : nullptr, stream) != hipSuccess) return PSNODE_ERR_HIP;
-    if ((a.de_reg || a.str == 2) && launch_pack_plain_images(mde, img, imgT, stream) != hipSuccess) return PSNODE_ERR_HIP;
-    if (dae && a.str >= 1 && launch_pack_plain_images(mae, imgA, imgTA, stream) != hipSuccess) return PSNODE_ERR_HIP;
+    if ((a.de_reg || a.str == 2) && launch_pack_plain_images(mde, L.img[0], L.imgT[0], stream) != hipSuccess) return PSNODE_ERR_HIP;
+    if (dae && a.str >= 1 && launch_pack_plain_images(mae, L.img[1], L.imgT[1], stream) != hipSuccess) return PSNODE_ERR_HIP;
     // <DE accumulators global, DE on the register path, AE accumulators global, streamed MLPs>
     using K = GenericBwdKernels<Pol>;
     auto kern = K::template get<false, false, false, 0>();

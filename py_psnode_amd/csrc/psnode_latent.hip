@@ -277,7 +277,13 @@ bool latent_ptrs_ok(const IntegrateDev& a, bool dae) {
     return true;
 }
 
-size_t latent_pack_floats() { return 2 * (size_t)(8 * 4 + 12 + 16) * 64; }
+// K3a's pack: the register image of the DE | of the AE
+struct LatentPack { float *de, *ae; };
+static LatentPack latent_layout(Arena& A) {
+    const size_t image = (size_t)(8 * 4 + 12 + 16) * 64;
+    return {A.take(image), A.take(image)};      // (a braced list is evaluated left to right)
+}
+size_t latent_pack_floats() { Arena A; latent_layout(A); return A.floats(); }
 
 template <int METHOD>
 static hipError_t launch_latent_method(const IntegrateDev& a, bool dae, const float* pde, const float* pae, hipStream_t s) {
@@ -294,22 +300,23 @@ hipError_t launch_latent(const IntegrateDev& a, bool dae, float* pack, hipStream
     PackLatent p;
     p.ae = 0; p.nblk = nblk; p.n = nblk * LH; p.k1 = 3 * p.n;
     p.w1 = a.de.w[0]; p.b1 = a.de.bias[0]; p.w2 = a.de.w[1]; p.b2 = a.de.bias[1];
-    p.out = pack;
+    Arena A{pack};
+    const LatentPack L = latent_layout(A);
+    p.out = L.de;
     hipLaunchKernelGGL(pack_latent_kernel, dim3(4), dim3(256), 0, stream, p);
-    float* pack_ae = pack + latent_pack_floats() / 2;
     if (dae) {
         PackLatent q;
         q.ae = 1; q.nblk = nblk - 1; q.n = p.n; q.k1 = p.n + (nblk - 1) * LH;
         q.w1 = a.ae.w[0]; q.b1 = a.ae.bias[0]; q.w2 = a.ae.w[1]; q.b2 = a.ae.bias[1];
-        q.out = pack_ae;
+        q.out = L.ae;
         hipLaunchKernelGGL(pack_latent_kernel, dim3(4), dim3(256), 0, stream, q);
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     switch (a.method) {
-        case PSNODE_EULER: return launch_latent_method<PSNODE_EULER>(a, dae, pack, pack_ae, stream);
-        case PSNODE_MIDPOINT: return launch_latent_method<PSNODE_MIDPOINT>(a, dae, pack, pack_ae, stream);
-        default: return launch_latent_method<PSNODE_RK4_38>(a, dae, pack, pack_ae, stream);
+        case PSNODE_EULER: return launch_latent_method<PSNODE_EULER>(a, dae, L.de, L.ae, stream);
+        case PSNODE_MIDPOINT: return launch_latent_method<PSNODE_MIDPOINT>(a, dae, L.de, L.ae, stream);
+        default: return launch_latent_method<PSNODE_RK4_38>(a, dae, L.de, L.ae, stream);
     }
 }
 

@@ -812,29 +812,38 @@ bool latent64_ptrs_ok(const IntegrateDev& a, bool dae) {
     return true;
 }
 
-size_t latent64_pack_floats() { return 2 * (size_t)NW64 * (16 * 4 + 24 + 16 * 4) * 64; }
+// K3c's pack: the register image of the DE | of the AE.  K3g (enc_dec) puts the encoders' / decoders' image behind them.
+struct Latent64Pack { float *de, *ae, *enc_dec; };
+static Latent64Pack latent64_layout(bool enc_dec, Arena& A) {
+    const size_t image = (size_t)NW64 * (16 * 4 + 24 + 16 * 4) * 64;
+    Latent64Pack L{A.take(image), A.take(image), enc_dec ? A.take((size_t)NW64 * kEncDecRegs * 64) : nullptr};
+    if (enc_dec) A.slack(64);      // kept from the parent, purpose not established
+    return L;
+}
+size_t latent64_pack_floats() { Arena A; latent64_layout(false, A); return A.floats(); }
 
 hipError_t launch_latent64(const IntegrateDev& a, bool dae, float* pack, hipStream_t stream) {
     const int nblk = dae ? (a.zd ? 4 : 3) : 2;
     Pack64 p;
     p.ae = 0; p.nblk = nblk; p.nfront = nblk; p.k1 = 3 * nblk * H64;
     p.w1 = a.de.w[0]; p.b1 = a.de.bias[0]; p.w2 = a.de.w[1]; p.b2 = a.de.bias[1];
-    p.out = pack;
+    Arena A{pack};
+    const Latent64Pack L = latent64_layout(false, A);
+    p.out = L.de;
     hipLaunchKernelGGL(pack64_kernel, dim3(32), dim3(256), 0, stream, p);
-    float* pack_ae = pack + latent64_pack_floats() / 2;
     if (dae) {
         Pack64 q = p;
         q.ae = 1; q.nfront = nblk - 1; q.k1 = (2 * nblk - 1) * H64;
         q.w1 = a.ae.w[0]; q.b1 = a.ae.bias[0]; q.w2 = a.ae.w[1]; q.b2 = a.ae.bias[1];
-        q.out = pack_ae;
+        q.out = L.ae;
         hipLaunchKernelGGL(pack64_kernel, dim3(32), dim3(256), 0, stream, q);
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     switch (a.method) {
-        case PSNODE_EULER: return launch64_method<PSNODE_EULER>(a, dae, pack, pack_ae, stream);
-        case PSNODE_MIDPOINT: return launch64_method<PSNODE_MIDPOINT>(a, dae, pack, pack_ae, stream);
-        default: return launch64_method<PSNODE_RK4_38>(a, dae, pack, pack_ae, stream);
+        case PSNODE_EULER: return launch64_method<PSNODE_EULER>(a, dae, L.de, L.ae, stream);
+        case PSNODE_MIDPOINT: return launch64_method<PSNODE_MIDPOINT>(a, dae, L.de, L.ae, stream);
+        default: return launch64_method<PSNODE_RK4_38>(a, dae, L.de, L.ae, stream);
     }
 }
 
@@ -874,7 +883,8 @@ int32_t psnode_dae_encoded_supported(const psnode_dae_encoded_args_f32* p) {
 
 size_t psnode_dae_encoded_workspace_bytes(const psnode_dae_encoded_args_f32* p) {
     if (!p) return 0;
-    return (latent64_pack_floats() + (size_t)NW64 * kEncDecRegs * 64 + 64) * sizeof(float);
+    Arena A;
+    return latent64_layout(true, A), A.bytes();
 }
 
 int32_t psnode_dae_encoded_integrate_f32(const psnode_dae_encoded_args_f32* p, void* workspace, size_t workspace_bytes, void* stream) {
@@ -888,7 +898,8 @@ int32_t psnode_dae_encoded_integrate_f32(const psnode_dae_encoded_args_f32* p, v
     if (!psnode_dae_encoded_supported(p)) return PSNODE_ERR_UNSUPPORTED;
     if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 255) || workspace_bytes < psnode_dae_encoded_workspace_bytes(p)) return PSNODE_ERR_WORKSPACE;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    float* pack = static_cast<float*>(workspace);
+    Arena A{static_cast<float*>(workspace)};
+    const Latent64Pack L = latent64_layout(true, A);
     ModelDev md;
     memset(&md, 0, sizeof(md));
     IntegrateDev& a = md.a;
@@ -914,15 +925,13 @@ int32_t psnode_dae_encoded_integrate_f32(const psnode_dae_encoded_args_f32* p, v
     Pack64 pk;
     pk.ae = 0; pk.nblk = nblk; pk.nfront = nblk; pk.k1 = 3 * nblk * H64;
     pk.w1 = a.de.w[0]; pk.b1 = a.de.bias[0]; pk.w2 = a.de.w[1]; pk.b2 = a.de.bias[1];
-    pk.out = pack;
+    pk.out = L.de;
     hipLaunchKernelGGL(pack64_kernel, dim3(32), dim3(256), 0, s, pk);
-    float* pack_ae = pack + latent64_pack_floats() / 2;
     Pack64 qk = pk;
     qk.ae = 1; qk.nfront = nblk - 1; qk.k1 = (2 * nblk - 1) * H64;
     qk.w1 = a.ae.w[0]; qk.b1 = a.ae.bias[0]; qk.w2 = a.ae.w[1]; qk.b2 = a.ae.bias[1];
-    qk.out = pack_ae;
+    qk.out = L.ae;
     hipLaunchKernelGGL(pack64_kernel, dim3(32), dim3(256), 0, s, qk);
-    float* pack_ed = pack + latent64_pack_floats();
     PackEncDec pe;
     memset(&pe, 0, sizeof(pe));
     const psnode_mlp_f32* ms[6] = {&p->x_encoder, p->z_dim ? &p->z_encoder : nullptr, &p->v_encoder, &p->i_encoder, &p->x_decoder, &p->i_decoder};
@@ -932,14 +941,14 @@ int32_t psnode_dae_encoded_integrate_f32(const psnode_dae_encoded_args_f32* p, v
         pe.in_dim[m] = ms[m]->in_dim; pe.out_dim[m] = ms[m]->out_dim[1];
         if (!pe.w1[m] || !pe.b1[m] || !pe.w2[m] || !pe.b2[m]) return PSNODE_ERR_NULL;
     }
-    pe.out = pack_ed;
+    pe.out = L.enc_dec;
     hipLaunchKernelGGL(pack_encdec_kernel, dim3(32), dim3(256), 0, s, pe);
     if (hipGetLastError() != hipSuccess) return PSNODE_ERR_HIP;
     hipError_t e;
     switch (a.method) {
-        case PSNODE_EULER: e = launch_model_method<PSNODE_EULER>(md, pack, pack_ae, pack_ed, s); break;
-        case PSNODE_MIDPOINT: e = launch_model_method<PSNODE_MIDPOINT>(md, pack, pack_ae, pack_ed, s); break;
-        default: e = launch_model_method<PSNODE_RK4_38>(md, pack, pack_ae, pack_ed, s); break;
+        case PSNODE_EULER: e = launch_model_method<PSNODE_EULER>(md, L.de, L.ae, L.enc_dec, s); break;
+        case PSNODE_MIDPOINT: e = launch_model_method<PSNODE_MIDPOINT>(md, L.de, L.ae, L.enc_dec, s); break;
+        default: e = launch_model_method<PSNODE_RK4_38>(md, L.de, L.ae, L.enc_dec, s); break;
     }
     return e == hipSuccess ? PSNODE_OK : PSNODE_ERR_HIP;
 }

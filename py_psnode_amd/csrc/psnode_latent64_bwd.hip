@@ -644,11 +644,21 @@ hipError_t launch9_method(const Bwd9Dev& d, bool dae, const float* pde, const fl
     return launch9<METHOD, 2, true>(d, pde, pae, s);
 }
 
+// K9's workspace: the register image of the DE | of the AE (the ODE leaves that half unused) | per workgroup of 16 trajectories, one partial
+// vector of the DE's and (DAE) of the AE's parameters
+struct Layout9 { float *pack_de, *pack_ae, *wpart; };
+Layout9 layout9(bool dae, int nblk, long long B, Arena& A) {
+    const size_t np = (size_t)np9(3 * nblk * H9) + (dae ? np9((2 * nblk - 1) * H9) : 0);
+    Layout9 L{A.take(pack9_floats(nblk) / 2), A.take(pack9_floats(nblk) / 2), A.take((size_t)((B + 15) / 16) * np)};
+    A.slack(64);      // kept from the parent, purpose not established
+    return L;
+}
+
 int run9(Bwd9Dev& d, bool dae, int nblk, const psnode_mlp_f32& de, const psnode_mlp_f32* ae, float* workspace, float* gp_de, float* gp_ae,
          hipStream_t s) {
-    float* pack_de = workspace;
-    float* pack_ae = workspace + pack9_floats(nblk) / 2;
-    d.wpart = workspace + pack9_floats(nblk);
+    Arena A{workspace};
+    const auto [pack_de, pack_ae, wpart] = layout9(dae, nblk, d.a.B, A);
+    d.wpart = wpart;
     d.NP_de = np9(3 * nblk * H9);
     d.NP_ae = dae ? np9((2 * nblk - 1) * H9) : 0;
     Pack9 p;
@@ -687,7 +697,7 @@ bool latent64_ode_bwd_ptrs_ok(const psnode_ode_bwd_args_f32* a) {
     if (a->event_idx && (mis9(a->z_jump) || a->zj_stride_b % 4 || a->zj_stride_e % 4 || (a->grad_z_jump && mis9(a->grad_z_jump)))) return false;
     return true;
 }
-size_t latent64_ode_bwd_workspace_floats(long long B) { return pack9_floats(2) + (size_t)((B + 15) / 16) * np9(6 * H9) + 64; }
+size_t latent64_ode_bwd_workspace_floats(long long B) { Arena A; layout9(false, 2, B, A); return A.floats(); }
 int latent64_ode_bwd_launch(const psnode_ode_bwd_args_f32* a, float* workspace, hipStream_t s) {
     Bwd9Dev d;
     memset(&d, 0, sizeof(d));
@@ -721,8 +731,8 @@ bool latent64_dae_bwd_ptrs_ok(const psnode_dae_bwd_args_f32* a) {
     return true;
 }
 size_t latent64_dae_bwd_workspace_floats(const psnode_dae_bwd_args_f32* a) {
-    const int nblk = a->z_dim ? 4 : 3;
-    return pack9_floats(nblk) + (size_t)((a->B + 15) / 16) * (np9(3 * nblk * H9) + np9((2 * nblk - 1) * H9)) + 64;
+    Arena A;
+    return layout9(true, a->z_dim ? 4 : 3, a->B, A), A.floats();
 }
 int latent64_dae_bwd_launch(const psnode_dae_bwd_args_f32* a, float* workspace, hipStream_t s) {
     Bwd9Dev d;

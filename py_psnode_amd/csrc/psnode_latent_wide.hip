@@ -478,7 +478,13 @@ bool latentw_ptrs_ok(const IntegrateDev& a, bool dae) {
     return true;
 }
 
-size_t latentw_pack_floats() { return 4 * packw_f4(8, 4, 3, true) + 64; }
+// K3w's pack: one image, sized for the largest shape (8 waves, the DAE with z)
+static float* latentw_layout(Arena& A) {
+    float* img = A.take(4 * packw_f4(8, 4, 3, true));
+    A.slack(64);      // kept from the parent, purpose not established
+    return img;
+}
+size_t latentw_pack_floats() { Arena A; latentw_layout(A); return A.floats(); }
 
 hipError_t launch_latent_wide(const IntegrateDev& a, bool dae, float* pack, hipStream_t stream) {
     const int H = a.xd, nw = H <= 64 ? 4 : 8;
@@ -489,7 +495,8 @@ hipError_t launch_latent_wide(const IntegrateDev& a, bool dae, float* pack, hipS
     p.nbe = p.nblk - 1;
     p.dw1 = a.de.w[0]; p.db1 = a.de.bias[0]; p.dw2 = a.de.w[1]; p.db2 = a.de.bias[1];
     if (dae) { p.aw1 = a.ae.w[0]; p.ab1 = a.ae.bias[0]; p.aw2 = a.ae.w[1]; p.ab2 = a.ae.bias[1]; }
-    p.out = reinterpret_cast<f4*>(pack);
+    Arena A{pack};
+    p.out = reinterpret_cast<f4*>(latentw_layout(A));
     hipLaunchKernelGGL(packw_kernel, dim3(256), dim3(256), 0, stream, p);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;

@@ -71,10 +71,10 @@ size_t mfma_pack_floats(const psnode_mlp_f32* de, const psnode_mlp_f32* ae) {
     }
     if (!de || de->n_layers != 4) return 0;
     const int n = de->in_dim / 3, nw = (padded_hidden_fwd(de->out_dim[0]) ? padded_hidden_fwd(de->out_dim[0]) : de->out_dim[0] + 15) / 16;
-    const size_t one = (size_t)nw * (max_regs(nw) + (n + 3) / 4) * 64 + stream_image_floats(nw);
-    const size_t both = ae ? 2 * one : one;
+    Arena tile;
+    mfma_layout(nw, (n + 3) / 4, ae != nullptr, 0, 0, tile);
     const size_t wave = ae ? mfma_xd_pack_floats() : mfma_x_pack_floats();
-    return both > wave ? both : wave;
+    return tile.floats() > wave ? tile.floats() : wave;
 }
 
 hipError_t launch_mfma(const IntegrateDev& a, bool dae, float* pack, hipStream_t stream) {

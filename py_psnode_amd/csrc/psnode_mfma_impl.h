@@ -820,6 +820,23 @@ hipError_t launch_method(const IntegrateDev& a, bool dae, const float* pde, cons
     return launch_shape<NWV, METHOD>(a, dae, pde, pae, NA, s);
 }
 
+// K1 / K2's pack: per MLP (the DE, then the DAE's AE) a slot of the largest register image of the width class plus, where the class
+// streams its weights, the stream image.  Inside its slot the stream image sits right behind the registers the call's image really has
+// (Tail::gw; regs_*: pack_fwd_count of the call, 0 in the size query, which needs the slots alone).
+struct MfmaPack { float *de, *de_stream, *ae, *ae_stream; };
+inline MfmaPack mfma_layout(int nw, int na, bool dae, int regs_de, int regs_ae, Arena& A) {
+    const size_t slot = (size_t)nw * (max_regs(nw) + na) * 64 + stream_image_floats(nw);
+    MfmaPack L{};
+    Arena de{L.de = A.take(slot)};
+    de.take((size_t)nw * regs_de * 64);
+    L.de_stream = de.take(stream_image_floats(nw));
+    if (!dae) { L.ae = A.take(0); return L; }      // (the ODE kernels are handed the address behind the DE's slot and never read it)
+    Arena ae{L.ae = A.take(slot)};
+    ae.take((size_t)nw * regs_ae * 64);
+    L.ae_stream = ae.take(stream_image_floats(nw));
+    return L;
+}
+
 // pack the weights into the register images, then run the integrator (both on `stream`)
 template <int NWV>
 hipError_t launch_mfma_nw(const IntegrateDev& a, bool dae, float* pack, hipStream_t stream) {
@@ -831,32 +848,28 @@ hipError_t launch_mfma_nw(const IntegrateDev& a, bool dae, float* pack, hipStrea
     p.w1 = a.de.w[0]; p.b1 = a.de.bias[0]; p.w2 = a.de.w[1]; p.b2 = a.de.bias[1];
     p.w3 = a.de.w[2]; p.b3 = a.de.bias[2]; p.w4 = a.de.w[3]; p.b4 = a.de.bias[3];
     p.out_dim = a.xd;
-    p.out = pack;
     p.scaled = (a.sact || !PSNODE_SCALED_ELU) ? 0 : 1;        // the inference instances (SAVE = false) run the hidden layers in the log2e-scaled domain
+    PackMfma q = p;
+    q.ae = 1; q.NB = 0; q.NE = nza_of(a); q.fold = 0;
+    Arena A{pack};
+    const MfmaPack L = mfma_layout(NWV, NA, dae, pack_fwd_count(p), pack_fwd_count(q), A);
+    p.out = L.de;
     hipLaunchKernelGGL(pack_mfma_kernel, dim3(16), dim3(256), 0, stream, p);
-    const size_t one = (size_t)NWV * (max_regs(NWV) + NA) * 64 + stream_image_floats(NWV);
-    if constexpr (weights_streamed(NWV))     // the stream image sits right behind the register image of its MLP (Tail::gw)
-        hipLaunchKernelGGL(pack_stream_kernel, dim3(64), dim3(256), 0, stream, p,
-                           reinterpret_cast<f4*>(pack + (size_t)NWV * (pack_fwd_count(p)) * 64));
-    float* pack_ae = pack + one;
+    if constexpr (weights_streamed(NWV)) hipLaunchKernelGGL(pack_stream_kernel, dim3(64), dim3(256), 0, stream, p, reinterpret_cast<f4*>(L.de_stream));
     if (dae) {
-        PackMfma q = p;
-        q.ae = 1; q.NB = 0; q.NE = nza_of(a); q.fold = 0;
         q.w1 = a.ae.w[0]; q.b1 = a.ae.bias[0]; q.w2 = a.ae.w[1]; q.b2 = a.ae.bias[1];
         q.w3 = a.ae.w[2]; q.b3 = a.ae.bias[2]; q.w4 = a.ae.w[3]; q.b4 = a.ae.bias[3];
         q.out_dim = a.id;
-        q.out = pack_ae;
+        q.out = L.ae;
         hipLaunchKernelGGL(pack_mfma_kernel, dim3(16), dim3(256), 0, stream, q);
-        if constexpr (weights_streamed(NWV))
-            hipLaunchKernelGGL(pack_stream_kernel, dim3(64), dim3(256), 0, stream, q,
-                               reinterpret_cast<f4*>(pack_ae + (size_t)NWV * (pack_fwd_count(q)) * 64));
+        if constexpr (weights_streamed(NWV)) hipLaunchKernelGGL(pack_stream_kernel, dim3(64), dim3(256), 0, stream, q, reinterpret_cast<f4*>(L.ae_stream));
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     switch (a.method) {
-        case PSNODE_EULER: return launch_method<NWV, PSNODE_EULER>(a, dae, pack, pack_ae, NA, stream);
-        case PSNODE_MIDPOINT: return launch_method<NWV, PSNODE_MIDPOINT>(a, dae, pack, pack_ae, NA, stream);
-        default: return launch_method<NWV, PSNODE_RK4_38>(a, dae, pack, pack_ae, NA, stream);
+        case PSNODE_EULER: return launch_method<NWV, PSNODE_EULER>(a, dae, L.de, L.ae, NA, stream);
+        case PSNODE_MIDPOINT: return launch_method<NWV, PSNODE_MIDPOINT>(a, dae, L.de, L.ae, NA, stream);
+        default: return launch_method<NWV, PSNODE_RK4_38>(a, dae, L.de, L.ae, NA, stream);
     }
 }
 

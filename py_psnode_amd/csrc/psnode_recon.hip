@@ -244,6 +244,9 @@ long long recon_blocks(long long rows) {      // backward: three workgroups per 
     long long blocks = (tiles + 3) / 4;
     return blocks > 768 ? 768 : (blocks < 1 ? 1 : blocks);
 }
+// K3r's backward workspace: one partial vector per wave | `mid`, the slice sums of the two-stage reduction
+struct ReconPartsLayout { float *part, *mid; };
+ReconPartsLayout recon_parts_layout(long long parts, int np, Arena& A) { return {A.take((size_t)parts * np), A.take((size_t)kReconSlices * np)}; }
 
 bool recon_shape_ok(const psnode_mlp_f32* e, const psnode_mlp_f32* d) {
     return e && d && e->n_layers == 2 && d->n_layers == 2 && e->in_dim >= 1 && e->in_dim <= 16 && e->out_dim[0] == RH && e->out_dim[1] == RH &&
@@ -295,8 +298,8 @@ extern "C" int64_t psnode_recon_rows_param_count(const psnode_mlp_f32* enc, cons
 }
 extern "C" size_t psnode_recon_rows_backward_workspace_bytes(const psnode_mlp_f32* enc, const psnode_mlp_f32* dec, int64_t rows) {
     if (!recon_shape_ok(enc, dec) || rows < 0) return 0;
-    const size_t np = (size_t)recon_np_enc(enc->in_dim) + recon_np_dec(dec->out_dim[1]);
-    return ((size_t)recon_blocks(rows) * 4 + kReconSlices) * np * sizeof(float);
+    Arena A;
+    return recon_parts_layout(recon_blocks(rows) * 4, recon_np_enc(enc->in_dim) + recon_np_dec(dec->out_dim[1]), A), A.bytes();
 }
 extern "C" int32_t psnode_recon_rows_backward_f32(const psnode_mlp_f32* enc, const psnode_mlp_f32* dec, int64_t rows, const float* in,
                                                   int64_t in_row_stride, int64_t in_inner_rows, int64_t in_outer_stride, const float* grad_out,
@@ -311,14 +314,14 @@ extern "C" int32_t psnode_recon_rows_backward_f32(const psnode_mlp_f32* enc, con
     ReconDev a = bind(enc, dec);
     a.in = in; a.gout = grad_out; a.rows = rows; a.in_stride = in_row_stride; a.in_inner = (unsigned)in_inner_rows;
     a.in_outer = in_inner_rows > 0 ? in_outer_stride : 0; a.gout_stride = gout_row_stride;
-    a.wpart = static_cast<float*>(workspace);
     const long long blocks = recon_blocks(rows);
     const int np = recon_np_enc(enc->in_dim) + recon_np_dec(dec->out_dim[1]);
+    Arena A{static_cast<float*>(workspace)};
+    const ReconPartsLayout L = recon_parts_layout(blocks * 4, np, A);
+    a.wpart = L.part;
     hipLaunchKernelGGL(recon_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a);
     if (hipGetLastError() != hipSuccess) return PSNODE_ERR_HIP;
-    float* mid = static_cast<float*>(workspace) + (size_t)blocks * 4 * np;
-    hipLaunchKernelGGL(recon_reduce_stage1, dim3((np + 255) / 256, kReconSlices), dim3(256), 0, s, static_cast<const float*>(workspace), mid, np,
-                       (int)(blocks * 4));
-    hipLaunchKernelGGL(recon_reduce_stage2, dim3((np + 255) / 256), dim3(256), 0, s, mid, grad_params, np);
+    hipLaunchKernelGGL(recon_reduce_stage1, dim3((np + 255) / 256, kReconSlices), dim3(256), 0, s, L.part, L.mid, np, (int)(blocks * 4));
+    hipLaunchKernelGGL(recon_reduce_stage2, dim3((np + 255) / 256), dim3(256), 0, s, L.mid, grad_params, np);
     return hipGetLastError() == hipSuccess ? PSNODE_OK : PSNODE_ERR_HIP;
 }

@@ -497,6 +497,13 @@ long long rows_bwd_blocks(long long rows) {
     return blocks > 512 ? 512 : (blocks < 1 ? 1 : blocks);
 }
 
+// The partial vectors of the row backwards (K3b's and, one per module over several row sets, the reduce call's) | `mid`, the slice sums of
+// the two-stage reduction (absent where the call leaves its partials unreduced)
+struct RowsPartsLayout { float *part, *mid; };
+RowsPartsLayout rows_parts_layout(long long parts, int np, bool reduce, Arena& A) {
+    return {A.take((size_t)parts * np), reduce ? A.take((size_t)kRedSlices * np) : nullptr};
+}
+
 }  // namespace
 }  // namespace psnode
 
@@ -536,7 +543,8 @@ extern "C" int32_t psnode_mlp_rows_f32(const psnode_mlp_f32* m, int64_t rows, co
 
 extern "C" size_t psnode_mlp_rows_backward_workspace_bytes(const psnode_mlp_f32* m, int64_t rows) {
     if (!m || !psnode_mlp_rows_supported(m) || rows < 0) return 0;
-    return ((size_t)rows_bwd_blocks(rows) * 4 + kRedSlices) * rows_np(m) * sizeof(float);
+    Arena A;
+    return rows_parts_layout(rows_bwd_blocks(rows) * 4, rows_np(m), true, A), A.bytes();
 }
 
 extern "C" int32_t psnode_mlp_rows_backward_f32(const psnode_mlp_f32* m, int64_t rows, const float* in, int64_t in_row_stride,
@@ -547,13 +555,13 @@ extern "C" int32_t psnode_mlp_rows_backward_f32(const psnode_mlp_f32* m, int64_t
     if (!m->weight[0] || !m->weight[1] || !m->bias[0]) return PSNODE_ERR_NULL;
     if (rows < 0 || in_row_stride < m->in_dim || gout_row_stride < m->out_dim[1] || (grad_in && gin_row_stride < m->in_dim)) return PSNODE_ERR_DIMS;
     if (in_inner_rows < 0 || in_inner_rows > 0xffffffffll || (in_inner_rows > 0 && (rows > 0xffffffffll || in_outer_stride < 0))) return PSNODE_ERR_DIMS;
-    const size_t need = grad_params ? psnode_mlp_rows_backward_workspace_bytes(m, rows)
-                                    : (size_t)rows_bwd_blocks(rows) * 4 * rows_np(m) * sizeof(float);
-    if (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 15)) return PSNODE_ERR_WORKSPACE;
-    hipStream_t s = static_cast<hipStream_t>(stream);
     const int np = rows_np(m);
     const long long blocks = rows_bwd_blocks(rows);
-    RowsBwdArgs a{m->weight[0], m->bias[0], m->weight[1], in, grad_out, grad_in, static_cast<float*>(workspace), rows, in_row_stride,
+    Arena A{static_cast<float*>(workspace)};
+    const RowsPartsLayout L = rows_parts_layout(blocks * 4, np, grad_params != nullptr, A);
+    if (!workspace || workspace_bytes < A.bytes() || (reinterpret_cast<uintptr_t>(workspace) & 15)) return PSNODE_ERR_WORKSPACE;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    RowsBwdArgs a{m->weight[0], m->bias[0], m->weight[1], in, grad_out, grad_in, L.part, rows, in_row_stride,
                   gout_row_stride, gin_row_stride, m->in_dim, m->out_dim[1], np, (unsigned)in_inner_rows, in_inner_rows > 0 ? in_outer_stride : 0};
     const dim3 grid((unsigned)blocks), block(256);
     const int NM = (m->in_dim + 3) / 4, H = m->out_dim[0], OT = (m->out_dim[1] + 15) / 16;
@@ -562,10 +570,8 @@ extern "C" int32_t psnode_mlp_rows_backward_f32(const psnode_mlp_f32* m, int64_t
     else launch_rows_bwd<4, 4>(NM, grid, block, s, a);
     if (hipGetLastError() != hipSuccess) return PSNODE_ERR_HIP;
     if (!grad_params) return PSNODE_OK;
-    float* mid = static_cast<float*>(workspace) + (size_t)blocks * 4 * np;
-    hipLaunchKernelGGL(rows_reduce_stage1, dim3((np + 255) / 256, kRedSlices), dim3(256), 0, s, static_cast<const float*>(workspace), mid, np,
-                       (int)(blocks * 4));
-    hipLaunchKernelGGL(rows_reduce_stage2, dim3((np + 255) / 256), dim3(256), 0, s, mid, grad_params, np);
+    hipLaunchKernelGGL(rows_reduce_stage1, dim3((np + 255) / 256, kRedSlices), dim3(256), 0, s, L.part, L.mid, np, (int)(blocks * 4));
+    hipLaunchKernelGGL(rows_reduce_stage2, dim3((np + 255) / 256), dim3(256), 0, s, L.mid, grad_params, np);
     return hipGetLastError() == hipSuccess ? PSNODE_OK : PSNODE_ERR_HIP;
 }
 
@@ -579,7 +585,8 @@ extern "C" int64_t psnode_mlp_rows_backward_parts(const psnode_mlp_f32* m, int64
 }
 extern "C" size_t psnode_mlp_rows_reduce_workspace_bytes(const psnode_mlp_f32* m, int64_t n_parts) {
     if (!m || !psnode_mlp_rows_supported(m) || n_parts < 0) return 0;
-    return ((size_t)n_parts + kRedSlices) * rows_np(m) * sizeof(float);
+    Arena A;
+    return rows_parts_layout(n_parts, rows_np(m), true, A), A.bytes();
 }
 extern "C" int32_t psnode_mlp_rows_reduce_f32(const psnode_mlp_f32* m, int64_t n_parts, void* workspace, size_t workspace_bytes,
                                               float* grad_params, void* stream) {
@@ -589,8 +596,9 @@ extern "C" int32_t psnode_mlp_rows_reduce_f32(const psnode_mlp_f32* m, int64_t n
     if (workspace_bytes < psnode_mlp_rows_reduce_workspace_bytes(m, n_parts) || (reinterpret_cast<uintptr_t>(workspace) & 15)) return PSNODE_ERR_WORKSPACE;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int np = rows_np(m);
-    float* mid = static_cast<float*>(workspace) + (size_t)n_parts * np;
-    hipLaunchKernelGGL(rows_reduce_stage1, dim3((np + 255) / 256, kRedSlices), dim3(256), 0, s, static_cast<const float*>(workspace), mid, np, (int)n_parts);
-    hipLaunchKernelGGL(rows_reduce_stage2, dim3((np + 255) / 256), dim3(256), 0, s, mid, grad_params, np);
+    Arena A{static_cast<float*>(workspace)};
+    const RowsPartsLayout L = rows_parts_layout(n_parts, np, true, A);
+    hipLaunchKernelGGL(rows_reduce_stage1, dim3((np + 255) / 256, kRedSlices), dim3(256), 0, s, L.part, L.mid, np, (int)n_parts);
+    hipLaunchKernelGGL(rows_reduce_stage2, dim3((np + 255) / 256), dim3(256), 0, s, L.mid, grad_params, np);
     return hipGetLastError() == hipSuccess ? PSNODE_OK : PSNODE_ERR_HIP;
 }

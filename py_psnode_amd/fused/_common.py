@@ -651,14 +651,12 @@ def _dup_check_remember(t, event_t):
     _DUP_OK[ident] = (weakref.ref(eb, lambda _r, ident=ident: _DUP_OK.pop(ident, None)), ek, weakref.ref(tb), tk)
 
 
-def _workspace(lib, de: _lib.MlpF32, ae, dev) -> torch.Tensor:
-    nbytes = lib.psnode_workspace_bytes(ctypes.byref(de), ctypes.byref(ae) if ae is not None else None)
-    return _empty(nbytes + 256, dtype=torch.uint8, device=dev)
-
-
-def _aligned_ptr(ws: torch.Tensor):
+def _workspace_of(nbytes: int, dev):
+    """A workspace of `nbytes` (what the call's *_workspace_bytes query answered) for one library call: the tensor that owns it (keep it
+    until the call is enqueued), the 256-byte aligned address inside it and the bytes usable from there."""
+    ws = _empty(nbytes + 256, dtype=torch.uint8, device=dev)
     p = (ws.data_ptr() + 255) // 256 * 256
-    return p, ws.numel() - (p - ws.data_ptr())
+    return ws, p, ws.numel() - (p - ws.data_ptr())
 
 
 def _padded_hidden(h: int) -> int:
@@ -698,8 +696,7 @@ def gemm_tn(a2: torch.Tensor, b2: torch.Tensor, want_colsum: bool = False):
         cs = _empty((a.M,), dtype=torch.float32, device=dev) if want_colsum else None
         a.C = c.data_ptr()
         a.colsum_a = cs.data_ptr() if cs is not None else None
-        ws = _empty(lib.psnode_gemm_tn_workspace_bytes(ctypes.byref(a)) + 256, dtype=torch.uint8, device=dev)
-        wp, wn = _aligned_ptr(ws)
+        ws, wp, wn = _workspace_of(lib.psnode_gemm_tn_workspace_bytes(ctypes.byref(a)), dev)
         _lib.check(lib.psnode_gemm_tn_f32(ctypes.byref(a), wp, wn, torch.cuda.current_stream(dev).cuda_stream), "psnode_gemm_tn_f32")
     return (c, cs) if want_colsum else c
 

@@ -6,7 +6,7 @@ import ctypes
 import torch
 
 from .. import _lib
-from ._common import (KERNEL_ID, GenericOpts, Layers, _aligned16, _aligned_ptr, _bind_jumps, _check_saved, _empty, _f32_dev, _mlp, _pad_rows, _padded_hidden, _split_grads, _view, call_generic, dae_acts)
+from ._common import (KERNEL_ID, GenericOpts, Layers, _aligned16, _bind_jumps, _check_saved, _empty, _f32_dev, _mlp, _pad_rows, _padded_hidden, _split_grads, _view, _workspace_of, call_generic, dae_acts)
 from .latent import latent_backward_wide, latent_wide_shape
 
 def dae_backward_supported(method, de_layers: Layers, ae_layers: Layers, x_dim, z_dim, v_dim, i_dim, act=None, kernel: str = "auto",
@@ -166,8 +166,7 @@ def dae_backward_wide(method: str, de_layers: Layers, ae_layers: Layers, t, z, v
         h.grad_zv = gza.data_ptr() if gza is not None else None
         h.sa1, h.out = sa1.data_ptr(), out.data_ptr()
         nb = lib.psnode_dae_head_grads_workspace_bytes(ctypes.byref(h))
-        hws = _empty(nb + 256, dtype=torch.uint8, device=dev)
-        hp_, hn_ = _aligned_ptr(hws)
+        hws, hp_, hn_ = _workspace_of(nb, dev)
         _lib.check(lib.psnode_dae_head_grads_f32(ctypes.byref(h), hp_, hn_, torch.cuda.current_stream(dev).cuda_stream),
                    "psnode_dae_head_grads_f32")
         o = 0
@@ -216,8 +215,7 @@ def dae_backward_wide(method: str, de_layers: Layers, ae_layers: Layers, t, z, v
         a.ae_gi = agi.data_ptr()
     with torch.cuda.device(dev):
         nbytes = lib.psnode_dae_backward_wide_workspace_bytes(ctypes.byref(a))
-        ws = _empty(nbytes + 256, dtype=torch.uint8, device=dev)
-        wp, wn = _aligned_ptr(ws)
+        ws, wp, wn = _workspace_of(nbytes, dev)
         st = torch.cuda.current_stream(dev).cuda_stream
         _lib.check(lib.psnode_dae_backward_wide_f32(ctypes.byref(a), wp, wn, st), "psnode_dae_backward_wide_f32")
         if n_ae_raw:
@@ -422,8 +420,7 @@ def _dae_backward_entry(opts, de_layers, ae_layers, t, z, v, all_initial, xs, is
                     raise ValueError("saved event activations do not belong to this call (shape)")
                 a.saved_ev_act, a.saved_ev_i = s_ev.data_ptr(), s_evi.data_ptr()
         nbytes = call_generic(lib, "dae_backward", "workspace_bytes", args, opts, x_sub=x_sub)[0]
-        ws = _empty(nbytes + 256, dtype=torch.uint8, device=dev)
-        wp, wn = _aligned_ptr(ws)
+        ws, wp, wn = _workspace_of(nbytes, dev)
         rc, entry = call_generic(lib, "dae_backward", "f32", args, opts, wp, wn, torch.cuda.current_stream(dev).cuda_stream, x_sub=x_sub)
     _lib.check(rc, entry)
     g["de"], g["ae"] = _split_grads(gde, de_layers), _split_grads(gae, ae_layers)

@@ -5,7 +5,7 @@ import ctypes
 import torch
 
 from .. import _lib
-from ._common import (KERNEL_ID, GenericOpts, Layers, _aligned16, _aligned_ptr, _bind_jumps, _check_saved, _empty, _f32_dev, _mlp, _split_grads, _view, call_generic)
+from ._common import (KERNEL_ID, GenericOpts, Layers, _aligned16, _bind_jumps, _check_saved, _empty, _f32_dev, _mlp, _split_grads, _view, _workspace_of, call_generic)
 from .latent import latent_backward_wide, latent_wide_shape
 
 def _bwd_args(opts, de_layers, x_dim, z_dim, T, B, dev, keep, kernel="auto"):
@@ -101,8 +101,7 @@ def ode_backward(method, de_layers: Layers, t, z, all_initial, xs, grad_xs, even
             keep += [saved[0], saved[1]]
             a.saved_act, a.saved_xstage = saved[0].data_ptr(), saved[1].data_ptr()
         nbytes = call_generic(lib, "ode_backward", "workspace_bytes", a, opts)[0]
-        ws = _empty(nbytes + 256, dtype=torch.uint8, device=dev)
-        wp, wn = _aligned_ptr(ws)
+        ws, wp, wn = _workspace_of(nbytes, dev)
         rc, entry = call_generic(lib, "ode_backward", "f32", a, opts, wp, wn, torch.cuda.current_stream(dev).cuda_stream, x_sub=x_sub)
     _lib.check(rc, entry)
     return gx0, gz, gzj, ga0, _split_grads(gpar, de_layers)

@@ -5,7 +5,7 @@ import ctypes
 import torch
 
 from .. import _lib
-from ._common import GenericOpts, Layers, _aligned_ptr, _check_jump, _empty, _f32_dev, _jump, _mlp, _view, event_table
+from ._common import GenericOpts, Layers, _check_jump, _empty, _f32_dev, _jump, _mlp, _view, _workspace_of, event_table
 
 def ode_encoded_supported(x_encoder: Layers, z_encoder: Layers, x_decoder: Layers, de_layers: Layers) -> bool:
     """Shapes of the fused direct_encode ODE forward (psnode_ode_encoded_integrate_f32): every MLP 2 layers with hidden 16."""
@@ -154,8 +154,7 @@ def dae_encoded_integrate(method: str, x_encoder, z_encoder, v_encoder, i_encode
             i_re = _empty((B, T, idim), dtype=torch.float32, device=dev)
             a.x_re, a.xre_stride_t, a.xre_stride_b = x_re.data_ptr(), xd, T * xd
             a.i_re, a.ire_stride_t, a.ire_stride_b = i_re.data_ptr(), idim, T * idim
-        ws = _empty(lib.psnode_dae_encoded_workspace_bytes(ctypes.byref(a)) + 256, dtype=torch.uint8, device=dev)
-        wp, wn = _aligned_ptr(ws)
+        ws, wp, wn = _workspace_of(lib.psnode_dae_encoded_workspace_bytes(ctypes.byref(a)), dev)
         rc = lib.psnode_dae_encoded_integrate_f32(ctypes.byref(a), wp, wn, torch.cuda.current_stream(dev).cuda_stream)
     _lib.check(rc, "psnode_dae_encoded_integrate_f32")
     return x_pred.permute(1, 0, 2), i_pred.permute(1, 0, 2), x_re, i_re

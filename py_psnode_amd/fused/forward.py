@@ -6,7 +6,7 @@ from typing import Optional
 import torch
 
 from .. import _lib
-from ._common import (KERNEL_ID, GenericOpts, Layers, Tableau, builtin_method, _aligned16, _aligned_ptr, _bind_events, _check_tb, _empty, _f32_dev, _mlp, _view, _workspace, call_generic, dae_acts, is_linear)
+from ._common import (KERNEL_ID, GenericOpts, Layers, Tableau, builtin_method, _aligned16, _bind_events, _check_tb, _empty, _f32_dev, _mlp, _view, _workspace_of, call_generic, dae_acts, is_linear)
 
 _MFMA_CLASSES = ("MFMA integrators K1 / K2 cover `in -> H -> H -> H -> out` ELU-MLPs with H <= 128 (any x_dim <= 16 for the ODE, "
                  "x_dim <= 8 and z+v+i <= 8 for the DAE), and -- weights streamed from L2 -- the ODE up to H = 192 at any x_dim <= 16 and "
@@ -117,8 +117,7 @@ def ode_integrate(method, de_layers: Layers, t, x, z, all_initial, event_t=None,
             if T >= 2:
                 a.save_act, a.save_xstage = saved[0].data_ptr(), saved[1].data_ptr()
         x_sub = _empty((max(T - 1, 0), substeps - 1, B, xd), dtype=torch.float32, device=dev) if save_sub and opts.family in ("sub", "lin") else None
-        ws = _workspace(lib, a.de, None, dev)
-        wp, wn = _aligned_ptr(ws)
+        ws, wp, wn = _workspace_of(lib.psnode_workspace_bytes(ctypes.byref(a.de), None), dev)
         rc, entry = call_generic(lib, "ode_integrate", "f32", a, opts, wp, wn, torch.cuda.current_stream(dev).cuda_stream, x_sub=x_sub)
     _mfma_miss(rc, kernel, entry, de_layers)
     _lib.check(rc, entry)
@@ -230,8 +229,7 @@ def dae_integrate(method, de_layers: Layers, ae_layers: Layers, x_init, t, x, z,
             if n_ev:
                 a.save_ev_act, a.save_ev_i = saved[3].data_ptr(), saved[4].data_ptr()
         x_sub = _empty((max(T - 1, 0), substeps - 1, B, xd), dtype=torch.float32, device=dev) if save_sub and opts.family in ("sub", "lin") else None
-        ws = _workspace(lib, a.de, a.ae, dev)
-        wp, wn = _aligned_ptr(ws)
+        ws, wp, wn = _workspace_of(lib.psnode_workspace_bytes(ctypes.byref(a.de), ctypes.byref(a.ae)), dev)
         rc, entry = call_generic(lib, "dae_integrate", "f32", a, opts, wp, wn, torch.cuda.current_stream(dev).cuda_stream, x_sub=x_sub)
     _mfma_miss(rc, kernel, entry, de_layers)
     _lib.check(rc, entry)

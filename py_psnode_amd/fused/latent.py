@@ -7,7 +7,7 @@ from typing import Optional
 import torch
 
 from .. import _lib
-from ._common import GenericOpts, Layers, _aligned_ptr, _empty, _f32_dev, _gemm_tn, _mlp, _view, gemm_tn
+from ._common import GenericOpts, Layers, _empty, _f32_dev, _gemm_tn, _mlp, _view, _workspace_of, gemm_tn
 
 def latent_wide_shape(de_layers: Layers, ae_layers: Optional[Layers], x_dim: int, z_dim: int, v_dim: int = 0, i_dim: int = 0) -> bool:
     """The latent shapes of the direct_encode models at a hidden width the dedicated latent kernels do not take (every H <= 128 with
@@ -85,8 +85,7 @@ def latent_backward_wide(method: str, de_layers: Layers, ae_layers: Optional[Lay
                     raise ValueError("saved event activations do not belong to this call (shape)")
                 gi_ev, da1_ev = torch.zeros((n_ev, B, H), **f32), torch.zeros((n_ev, B, H), **f32)
                 a.gi_ev, a.da1_ev, a.saved_ev_act = gi_ev.data_ptr(), da1_ev.data_ptr(), s_ev.data_ptr()
-        ws = _empty(lib.psnode_latent_backward_wide_workspace_bytes(H) + 256, dtype=torch.uint8, device=dev)
-        wp, wn = _aligned_ptr(ws)
+        ws, wp, wn = _workspace_of(lib.psnode_latent_backward_wide_workspace_bytes(H), dev)
         _lib.check(lib.psnode_latent_backward_wide_f32(ctypes.byref(a), wp, wn, torch.cuda.current_stream(dev).cuda_stream),
                    "psnode_latent_backward_wide_f32")
         # ---- contractions over the stored rows

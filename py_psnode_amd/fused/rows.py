@@ -7,7 +7,7 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
-from ._common import Layers, _aligned_ptr, _empty, _f32_dev, _mlp, _split_grads, sequential_layers
+from ._common import Layers, _empty, _f32_dev, _mlp, _split_grads, _workspace_of, sequential_layers
 from .plan import _needs_autograd
 
 def _row_addressing(x: torch.Tensor):
@@ -202,8 +202,7 @@ def mlp_rows_backward(layers: Layers, inp: torch.Tensor, grad_out: torch.Tensor,
         npar = sum(w.numel() + b.numel() for w, b in layers)
         gp = _empty(npar, dtype=torch.float32, device=dev)
         nbytes = lib.psnode_mlp_rows_backward_workspace_bytes(ctypes.byref(m), rows)
-        ws = _empty(nbytes + 256, dtype=torch.uint8, device=dev)
-        wp, wn = _aligned_ptr(ws)
+        ws, wp, wn = _workspace_of(nbytes, dev)
         rc = lib.psnode_mlp_rows_backward_f32(ctypes.byref(m), rows, x2.data_ptr(), rstride, inner, outer, g2.data_ptr(), _ld(g2),
                                               gin.data_ptr() if gin is not None else None, inp.shape[-1], gp.data_ptr(), wp, wn,
                                               torch.cuda.current_stream(dev).cuda_stream)
@@ -254,8 +253,7 @@ def mlp_rows_backward_multi(layers: Layers, inps, grad_outs, need_grad_in):
             sets.append((k, x2, rows, rstride, inner, outer, g2, int(lib.psnode_mlp_rows_backward_parts(ctypes.byref(m), rows))))
         n_parts = sum(s_[-1] for s_ in sets)
         nbytes = lib.psnode_mlp_rows_reduce_workspace_bytes(ctypes.byref(m), n_parts)
-        ws = _empty(nbytes + 256, dtype=torch.uint8, device=dev)
-        wp, wn = _aligned_ptr(ws)
+        ws, wp, wn = _workspace_of(nbytes, dev)
         st = torch.cuda.current_stream(dev).cuda_stream
         off = 0
         for k, x2, rows, rstride, inner, outer, g2, parts in sets:
@@ -336,8 +334,7 @@ def recon_rows_backward(enc_layers: Layers, dec_layers: Layers, inp: torch.Tenso
         npar = int(lib.psnode_recon_rows_param_count(ctypes.byref(me), ctypes.byref(md)))
         gp = _empty(npar, dtype=torch.float32, device=dev)
         nbytes = lib.psnode_recon_rows_backward_workspace_bytes(ctypes.byref(me), ctypes.byref(md), rows)
-        ws = _empty(nbytes + 256, dtype=torch.uint8, device=dev)
-        wp, wn = _aligned_ptr(ws)
+        ws, wp, wn = _workspace_of(nbytes, dev)
         _lib.check(lib.psnode_recon_rows_backward_f32(ctypes.byref(me), ctypes.byref(md), rows, x2.data_ptr(), rstride, inner, outer, g2.data_ptr(),
                                                       _ld(g2), gp.data_ptr(), wp, wn, torch.cuda.current_stream(dev).cuda_stream),
                    "psnode_recon_rows_backward_f32")

@@ -19,7 +19,7 @@ from typing import Optional, Sequence
 import torch
 
 from . import _lib
-from .fused import _empty
+from .fused import _empty, _workspace_of
 
 
 def _view_bt(t: torch.Tensor, dev, name: str, keep: list) -> _lib.ViewF32:
@@ -82,8 +82,7 @@ def masked_mse_terms(pred, target, mask=None, col_weight=None, inv_norm: Optiona
     a.out = out.data_ptr()
     a.grad_pred = grad.data_ptr() if want_grad else None
     nbytes = lib.psnode_masked_mse_workspace_bytes(ctypes.byref(a))
-    ws = _empty(nbytes + 256, dtype=torch.uint8, device=dev)
-    p = (ws.data_ptr() + 255) // 256 * 256
+    ws, p, _ = _workspace_of(nbytes, dev)
     with torch.cuda.device(dev):
         st = torch.cuda.current_stream(dev).cuda_stream
         _lib.check(lib.psnode_masked_mse_f32(ctypes.byref(a), ctypes.c_void_p(p), ctypes.c_size_t(nbytes), ctypes.c_void_p(st)),
