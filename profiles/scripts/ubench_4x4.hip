@@ -14,6 +14,9 @@
 //   4  as 2 with the round-5 ELU (the clamp of the negative side rides on v_exp_f32's output modifier: 3 instead of 4 issue slots per value)
 //   5  64 MFMA without the A broadcast (CBSZ = 0): is the 10-cycle issue interval a property of the broadcast?
 //   6  the whole layer with the scaled-domain ELU;  7 / 8  64 MFMA with one / two SALU instructions behind each: are they free?
+//   11  64 MFMA on ONE accumulator chain as the compiler emits it (it places the s_nop 1 of a dependent SrcC itself);  12  the same as asm
+//       blocks of 4 k with an explicit s_nop 1 behind every MFMA;  13  the whole layer (scaled-domain ELU + transpose) on one chain;
+//   14  as 13 with the transpose's two butterfly stages in alternating order from layer to layer (vcc is handed on: 3 mask moves, not 4)
 // It also checks, bit for bit over 2^24 inputs, that the round-5 ELU form equals round 3's.
 // Grid: 1024 single-wave workgroups (= B 4096: one wave per SIMD), and 2048 (two per SIMD) for reference.
 #include <hip/hip_runtime.h>
@@ -62,6 +65,16 @@ __device__ __forceinline__ f4 elu_quad_scaled(f4 v) {
     const f2 ua = __builtin_elementwise_fma(c, ea, nc), ub = __builtin_elementwise_fma(c, eb, nc);
     return f4{fmaxf(v[0], ua[0]), fmaxf(v[1], ua[1]), fmaxf(v[2], ub[0]), fmaxf(v[3], ub[1])};
 }
+// the same on an accumulator as the MFMA left it (one chain: no sum in front): fmaxf would cost a canonicalising v_max_f32 more per
+// element, the NaN-propagating maximum (v_maximum3_f32) does not
+__device__ __forceinline__ f4 elu_quad_scaled_acc(f4 v) {
+    const f2 c = f2{1.44269504088896340736f, 1.44269504088896340736f}, nc = -c;
+    const f2 ea = f2{__builtin_amdgcn_fmed3f(__builtin_amdgcn_exp2f(v[0]), 0.f, 1.f), __builtin_amdgcn_fmed3f(__builtin_amdgcn_exp2f(v[1]), 0.f, 1.f)};
+    const f2 eb = f2{__builtin_amdgcn_fmed3f(__builtin_amdgcn_exp2f(v[2]), 0.f, 1.f), __builtin_amdgcn_fmed3f(__builtin_amdgcn_exp2f(v[3]), 0.f, 1.f)};
+    const f2 ua = __builtin_elementwise_fma(c, ea, nc), ub = __builtin_elementwise_fma(c, eb, nc);
+    return f4{__builtin_elementwise_maximum(v[0], ua[0]), __builtin_elementwise_maximum(v[1], ua[1]),
+              __builtin_elementwise_maximum(v[2], ub[0]), __builtin_elementwise_maximum(v[3], ub[1])};
+}
 __global__ void elu_forms(unsigned* ndiff) {
     // every float whose low 8 mantissa bits are a fixed pattern: 2^24 values over the whole exponent range, both signs
     const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -101,6 +114,56 @@ __device__ __forceinline__ f4 quad_transpose(f4 v, const int) {
     return f4{o0, o1, o2, o3};
 }
 
+// The same transpose with a compile-time stage order and the mask handed from seam to seam in vcc.  The two butterfly stages (lane bit 0 <->
+// register bit 0, lane bit 1 <-> register bit 1) commute.  ORD 0: enters with vcc = EVEN lanes, leaves with vcc = HI lanes (bit 1 set);
+// ORD 1: enters with HI, leaves with EVEN -- so alternating seams need 3 mask moves each instead of 4.
+template <int ORD>
+__device__ __forceinline__ f4 quad_transpose_seq(f4 v, unsigned long long& m) {
+    float a0, a1, a2, a3, o0, o1, o2, o3;
+    const unsigned long long ODD = 0xAAAAAAAAAAAAAAAAull, LO = 0x3333333333333333ull;
+    // the asm's mask operands ARE vcc's halves: what one seam leaves is what the next one reads, the compiler has no move to emit
+    // (a 64-bit register variable on vcc crashes this compiler's backend)
+    register unsigned mlo asm("vcc_lo") = (unsigned)m;
+    register unsigned mhi asm("vcc_hi") = (unsigned)(m >> 32);
+    if constexpr (ORD == 0) {
+        asm volatile(
+            "s_nop 1\n\t"
+            "v_cndmask_b32_dpp %0, %11, %10, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+            "v_cndmask_b32_dpp %2, %13, %12, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+            "s_not_b64 vcc, vcc\n\t"
+            "v_cndmask_b32_dpp %1, %10, %11, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+            "v_cndmask_b32_dpp %3, %12, %13, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+            "s_mov_b64 vcc, %14\n\t"
+            "v_cndmask_b32_dpp %4, %2, %0, vcc quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+            "v_cndmask_b32_dpp %5, %3, %1, vcc quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+            "s_not_b64 vcc, vcc\n\t"
+            "v_cndmask_b32_dpp %6, %0, %2, vcc quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+            "v_cndmask_b32_dpp %7, %1, %3, vcc quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf"
+            : "=&v"(a0), "=&v"(a1), "=&v"(a2), "=&v"(a3), "=&v"(o0), "=&v"(o1), "=&v"(o2), "=&v"(o3), "+s"(mlo), "+s"(mhi)
+            : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "s"(LO)
+            : "scc");
+    } else {
+        asm volatile(
+            "s_nop 1\n\t"
+            "v_cndmask_b32_dpp %2, %10, %12, vcc quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+            "v_cndmask_b32_dpp %3, %11, %13, vcc quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+            "s_not_b64 vcc, vcc\n\t"
+            "v_cndmask_b32_dpp %0, %12, %10, vcc quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+            "v_cndmask_b32_dpp %1, %13, %11, vcc quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+            "s_mov_b64 vcc, %14\n\t"
+            "v_cndmask_b32_dpp %5, %0, %1, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+            "v_cndmask_b32_dpp %7, %2, %3, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+            "s_not_b64 vcc, vcc\n\t"
+            "v_cndmask_b32_dpp %4, %1, %0, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+            "v_cndmask_b32_dpp %6, %3, %2, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf"
+            : "=&v"(a0), "=&v"(a1), "=&v"(a2), "=&v"(a3), "=&v"(o0), "=&v"(o1), "=&v"(o2), "=&v"(o3), "+s"(mlo), "+s"(mhi)
+            : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "s"(ODD)
+            : "scc");
+    }
+    m = (unsigned long long)mhi << 32 | mlo;
+    return f4{o0, o1, o2, o3};
+}
+
 template <int C, int B0, int NACC, bool BC = true, int FILL = 0>
 __device__ __forceinline__ void quarter(const float (&wreg)[64], const float hc, f4 (&acc)[4], unsigned& g_sfill) {
     // the 16 k's that register c of the A operand carries: k = 4b + c, ABID = b
@@ -136,6 +199,54 @@ __device__ __forceinline__ void block_vgpr(const float (&wk)[64], const f4 hA, f
         "s_nop 0"
         : "+v"(accA), "+v"(accB)
         : "v"(hA[0]), "v"(hA[1]), "v"(hA[2]), "v"(hA[3]), "v"(wk[4 * BB + 0]), "v"(wk[4 * BB + 1]), "v"(wk[4 * BB + 2]), "v"(wk[4 * BB + 3]), "n"(BB));
+}
+// mode 12: ONE accumulator chain, asm, an explicit s_nop 1 behind every MFMA (a dependent SrcC of a 2-pass MFMA needs 2 wait states)
+template <int BB>
+__device__ __forceinline__ void block_one(const float (&wk)[64], const f4 hA, f4& acc) {
+    asm volatile(
+        "v_mfma_f32_4x4x1_16b_f32 %0, %1, %5, %0 cbsz:4 abid:%9\n\t"
+        "s_nop 1\n\t"
+        "v_mfma_f32_4x4x1_16b_f32 %0, %2, %6, %0 cbsz:4 abid:%9\n\t"
+        "s_nop 1\n\t"
+        "v_mfma_f32_4x4x1_16b_f32 %0, %3, %7, %0 cbsz:4 abid:%9\n\t"
+        "s_nop 1\n\t"
+        "v_mfma_f32_4x4x1_16b_f32 %0, %4, %8, %0 cbsz:4 abid:%9\n\t"
+        "s_nop 1"
+        : "+v"(acc)
+        : "v"(hA[0]), "v"(hA[1]), "v"(hA[2]), "v"(hA[3]), "v"(wk[4 * BB + 0]), "v"(wk[4 * BB + 1]), "v"(wk[4 * BB + 2]), "v"(wk[4 * BB + 3]), "n"(BB));
+}
+__global__ __launch_bounds__(64) void bench_asm_one(float* out, long long* cyc, int niter, const float* __restrict__ wsrc) {
+    const int l = threadIdx.x;
+    float wreg[64];
+#pragma unroll
+    for (int i = 0; i < 64; ++i) wreg[i] = wsrc[i * 64 + l];
+    f4 h = f4{0.1f + 0.001f * l, 0.2f, 0.3f, 0.4f};
+    const long long t0 = __builtin_readcyclecounter();
+    for (int it = 0; it < niter; ++it) {
+        f4 a0 = f4{0.f, 0.f, 0.f, 0.f};
+        asm volatile("s_nop 1" : "+v"(a0));          // VALU write -> MFMA SrcC read
+#define BLK(B_) block_one<B_>(wreg, h, a0);
+        BLK(0) BLK(1) BLK(2) BLK(3) BLK(4) BLK(5) BLK(6) BLK(7) BLK(8) BLK(9) BLK(10) BLK(11) BLK(12) BLK(13) BLK(14) BLK(15)
+#undef BLK
+        asm volatile("s_nop 1" : "+v"(a0));          // (with the block's own s_nop 1: MFMA write, 2 passes -> VALU read)
+        h = a0 * 1e-3f;
+    }
+    const long long t1 = __builtin_readcyclecounter();
+    out[blockIdx.x * 64 + l] = h[0] + h[1] + h[2] + h[3];
+    if (blockIdx.x == 0 && l == 0) *cyc = t1 - t0;
+}
+void run_asm_one(const char* name, int nwg, float* out, long long* cyc, const float* w) {
+    const int niter = 4000;
+    hipEvent_t e0, e1;
+    hipEventCreate(&e0); hipEventCreate(&e1);
+    bench_asm_one<<<nwg, 64>>>(out, cyc, 10, w);
+    hipEventRecord(e0);
+    bench_asm_one<<<nwg, 64>>>(out, cyc, niter, w);
+    hipEventRecord(e1);
+    hipDeviceSynchronize();
+    float ms; hipEventElapsedTime(&ms, e0, e1);
+    long long c; hipMemcpy(&c, cyc, sizeof(c), hipMemcpyDeviceToHost);
+    printf("%-58s waves/SIMD=%d : %7.1f ns per layer (wall), s_memtime %.2f ticks\n", name, nwg / 1024, ms * 1e6 / niter, (double)c / niter);
 }
 template <bool ACC>
 __global__ __launch_bounds__(64) void bench_asm(float* out, long long* cyc, int niter, const float* __restrict__ wsrc) {
@@ -179,10 +290,14 @@ __global__ __launch_bounds__(64) void bench(float* out, long long* cyc, int nite
 #pragma unroll
     for (int i = 0; i < 64; ++i) wreg[i] = wsrc[i * 64 + l];
     f4 h = f4{0.1f + 0.001f * l, 0.2f, 0.3f, 0.4f};
-    constexpr int NACC = MODE == 3 ? 4 : 2;
+    constexpr int NACC = MODE == 3 ? 4 : (MODE == 11 || MODE == 13 || MODE == 14 ? 1 : 2);
+    constexpr int NLAYER = MODE == 14 ? 2 : 1;                         // layers per iteration (mode 14: one of each transpose order)
     unsigned sfill = 0;
+    unsigned long long vmask = 0x5555555555555555ull;                  // mode 14: the mask the next seam starts with (EVEN lanes)
     const long long t0 = __builtin_readcyclecounter();
-    for (int it = 0; it < niter; ++it) {
+    for (int it = 0; it < niter; it += NLAYER) {
+#pragma unroll
+      for (int ly = 0; ly < NLAYER; ++ly) {
         f4 acc[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) acc[i] = f4{0.f, 0.f, 0.f, 0.f};
@@ -192,17 +307,21 @@ __global__ __launch_bounds__(64) void bench(float* out, long long* cyc, int nite
         quarter<2, 0, NACC, MODE != 5, FILL>(wreg, h[2], acc, sfill);
         quarter<3, 0, NACC, MODE != 5, FILL>(wreg, h[3], acc, sfill);
         __builtin_amdgcn_sched_barrier(0);
-        f4 s = acc[0] + acc[1];
+        f4 s = acc[0];
+        if constexpr (NACC >= 2) s += acc[1];
         if constexpr (NACC == 4) s += acc[2] + acc[3];
         if constexpr (MODE == 6) s = elu_quad_scaled(s);
+        else if constexpr (MODE == 13 || MODE == 14) s = elu_quad_scaled_acc(s);
         else if constexpr (MODE == 4) s = elu_quad_clamp(s);
         else if constexpr (MODE >= 2 && MODE < 5) s = elu_quad(s);
-        if constexpr (MODE >= 1 && MODE != 5 && MODE < 7) s = quad_transpose(s, l);
+        if constexpr ((MODE >= 1 && MODE != 5 && MODE < 7) || MODE == 13) s = quad_transpose(s, l);
+        if constexpr (MODE == 14) { if (ly == 0) s = quad_transpose_seq<0>(s, vmask); else s = quad_transpose_seq<1>(s, vmask); }
         h = s * 1e-3f;      // keep the chain finite (one packed multiply pair; K1 has the accumulator sum in its place)
         __builtin_amdgcn_sched_barrier(0);
+      }
     }
     const long long t1 = __builtin_readcyclecounter();
-    out[blockIdx.x * 64 + l] = h[0] + h[1] + h[2] + h[3] + (float)sfill;
+    out[blockIdx.x * 64 + l] = h[0] + h[1] + h[2] + h[3] + (float)sfill + (float)(vmask & 1);
     if (blockIdx.x == 0 && l == 0) *cyc = t1 - t0;
 }
 
@@ -291,6 +410,22 @@ __global__ void check(const float* __restrict__ W, const float* __restrict__ act
     for (int c = 0; c < 4; ++c) res[(4 * b + c) * 4 + t] = s[c];
 }
 
+// the ordered transposes against the plain one, bit for bit, on one wave of distinct values (both orders, vcc handed on)
+__global__ void check_seq(unsigned* nbad) {
+    const int l = threadIdx.x;
+    const f4 v = f4{(float)(4 * l), (float)(4 * l + 1), (float)(4 * l + 2), (float)(4 * l + 3)};
+    const f4 ref = quad_transpose(v, l);
+    unsigned long long m = 0x5555555555555555ull;
+    const f4 t0 = quad_transpose_seq<0>(v, m);
+    const bool hi_ok = m == 0xCCCCCCCCCCCCCCCCull;
+    const f4 t1 = quad_transpose_seq<1>(v, m);
+    const bool even_ok = m == 0x5555555555555555ull;
+    unsigned bad = !hi_ok + !even_ok;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) bad += (t0[i] != ref[i]) + (t1[i] != ref[i]);
+    if (bad) atomicAdd(nbad, bad);
+}
+
 template <int MODE>
 void run(const char* name, int nwg, float* out, long long* cyc, const float* w) {
     const int niter = 4000;
@@ -327,7 +462,24 @@ int main() {
         }
     printf("mapping check (64 x 4x4x1 CBSZ=4/ABID=b + in-quad transpose vs a double-precision matvec): max abs diff %.3g %s\n", worst,
            worst < 1e-4 ? "OK" : "WRONG");
+    {
+        unsigned* nb; hipMalloc(&nb, 4); hipMemset(nb, 0, 4);
+        check_seq<<<1, 64>>>(nb);
+        unsigned hnb; hipMemcpy(&hnb, nb, 4, hipMemcpyDeviceToHost);
+        printf("ordered in-quad transposes (stage order 0 / 1, mask handed on in vcc) vs the plain one: %u mismatches %s\n", hnb, hnb ? "WRONG" : "OK");
+        hipFree(nb);
+    }
     run<0>("64 x 4x4x1 (2 chains), nothing else", 1024, out, cyc, w);
+    run<11>("64 x 4x4x1 on ONE chain (compiler form), nothing else", 1024, out, cyc, w);
+    run_asm_one("64 x 4x4x1 on ONE chain, asm with s_nop 1", 1024, out, cyc, w);
+    run<6>("the whole layer with the scaled-domain ELU (2 chains)", 1024, out, cyc, w);
+    run<13>("the whole layer, scaled ELU, ONE chain", 1024, out, cyc, w);
+    run<14>("the whole layer, ONE chain, alternating transpose order", 1024, out, cyc, w);
+    run<0>("64 x 4x4x1 (2 chains), nothing else (again)", 1024, out, cyc, w);
+    run<11>("64 x 4x4x1 on ONE chain (compiler form) (again)", 1024, out, cyc, w);
+    run<6>("the whole layer, scaled ELU, 2 chains (again)", 1024, out, cyc, w);
+    run<13>("the whole layer, scaled ELU, ONE chain (again)", 1024, out, cyc, w);
+    run<14>("the whole layer, ONE chain, alternating order (again)", 1024, out, cyc, w);
     run_asm<false>("64 x 4x4x1 as ONE asm block per 4 k, B in VGPRs", 1024, out, cyc, w);
     run_asm<true>("64 x 4x4x1 as ONE asm block per 4 k, B read from AccVGPRs", 1024, out, cyc, w);
     run<1>("64 x 4x4x1 + in-quad transpose", 1024, out, cyc, w);

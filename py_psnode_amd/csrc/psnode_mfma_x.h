@@ -44,6 +44,63 @@ __device__ __forceinline__ f4 quad_transpose(const f4 v) {
     return f4{o0, o1, o2, o3};
 }
 
+// The same transpose for a SEQUENCE of seams: the two butterfly stages (lane bit 0 <-> register bit 0, lane bit 1 <-> register bit 1) commute, so
+// consecutive seams alternate their order and each starts on the mask the one before left in vcc -- 3 mask moves per seam instead of 4
+// (with one wave per SIMD every SALU instruction between two MFMA streams is wall time).  Bit-exact: only moves.
+//   ORD 0: enters with vcc = the EVEN lanes, leaves with vcc = the lanes with bit 1 set;   ORD 1: enters with the latter, leaves with EVEN.
+// The mask travels as a VALUE (XMask) whose asm operands are pinned to vcc's halves: where nothing else needs vcc between two seams the
+// compiler has no move to emit, where something does it saves and restores -- the hand-over is never an assumption about the code between.
+// (Two 32-bit register variables: a 64-bit one on vcc crashes the backend of this compiler.)  The caller starts a sequence with xmask_even()
+// and keeps ORD alternating; wait states as above.
+struct XMask { unsigned lo, hi; };
+__device__ __forceinline__ XMask xmask_even() { return XMask{0x55555555u, 0x55555555u}; }
+template <int ORD>
+__device__ __forceinline__ f4 quad_transpose_seq(const f4 v, XMask& m) {
+    float a0, a1, a2, a3, o0, o1, o2, o3;
+    const unsigned long long ODD = 0xAAAAAAAAAAAAAAAAull, LO = 0x3333333333333333ull;
+    // (readfirstlane: a no-op on a value that is in SGPRs, as in the time loops; it keeps the copy into vcc legal where the compiler carries
+    //  the mask through a VGPR -- seen in the saving forwards, across their divergent store branches)
+    register unsigned mlo asm("vcc_lo") = __builtin_amdgcn_readfirstlane(m.lo);
+    register unsigned mhi asm("vcc_hi") = __builtin_amdgcn_readfirstlane(m.hi);
+    if constexpr (ORD == 0) {
+        asm volatile(
+            "s_nop 1\n\t"
+            "v_cndmask_b32_dpp %0, %11, %10, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+            "v_cndmask_b32_dpp %2, %13, %12, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+            "s_not_b64 vcc, vcc\n\t"
+            "v_cndmask_b32_dpp %1, %10, %11, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+            "v_cndmask_b32_dpp %3, %12, %13, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+            "s_mov_b64 vcc, %14\n\t"
+            "v_cndmask_b32_dpp %4, %2, %0, vcc quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+            "v_cndmask_b32_dpp %5, %3, %1, vcc quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+            "s_not_b64 vcc, vcc\n\t"
+            "v_cndmask_b32_dpp %6, %0, %2, vcc quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+            "v_cndmask_b32_dpp %7, %1, %3, vcc quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf"
+            : "=&v"(a0), "=&v"(a1), "=&v"(a2), "=&v"(a3), "=&v"(o0), "=&v"(o1), "=&v"(o2), "=&v"(o3), "+s"(mlo), "+s"(mhi)
+            : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "s"(LO)
+            : "scc");
+    } else {
+        asm volatile(
+            "s_nop 1\n\t"
+            "v_cndmask_b32_dpp %2, %10, %12, vcc quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+            "v_cndmask_b32_dpp %3, %11, %13, vcc quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+            "s_not_b64 vcc, vcc\n\t"
+            "v_cndmask_b32_dpp %0, %12, %10, vcc quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+            "v_cndmask_b32_dpp %1, %13, %11, vcc quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+            "s_mov_b64 vcc, %14\n\t"
+            "v_cndmask_b32_dpp %5, %0, %1, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+            "v_cndmask_b32_dpp %7, %2, %3, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+            "s_not_b64 vcc, vcc\n\t"
+            "v_cndmask_b32_dpp %4, %1, %0, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+            "v_cndmask_b32_dpp %6, %3, %2, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf"
+            : "=&v"(a0), "=&v"(a1), "=&v"(a2), "=&v"(a3), "=&v"(o0), "=&v"(o1), "=&v"(o2), "=&v"(o3), "+s"(mlo), "+s"(mhi)
+            : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "s"(ODD)
+            : "scc");
+    }
+    m.lo = mlo; m.hi = mhi;
+    return f4{o0, o1, o2, o3};
+}
+
 // (a, b) -> sums over the four blocks of each row of 16 lanes, in every lane: x += row_ror:8 (x); x += row_ror:4 (x) as v_add_f32_dpp.
 // One asm block (left to the compiler the rotation is a v_mov_b32_dpp into a zeroed register in front of a packed add: 4 instructions
 // per rotation); it carries its own wait states (VALU write -> DPP read: 2).
@@ -68,7 +125,9 @@ __device__ __forceinline__ float fold16(const float a, const float b) {
     return __uint_as_float(r[0]) + __uint_as_float(r[1]);
 }
 
-// all 64 k of one H -> H layer: k = 4 bb + cc <-> A register cc, ABID bb
+// all 64 k of one H -> H layer: k = 4 bb + cc <-> A register cc, ABID bb.  TWO accumulator chains: on one chain a lone wave issues a 4x4x1
+// MFMA every 13.3 cycles instead of every 9.95 (profiles/k1x_one_chain_ubench.txt: 848 against 636 ticks per 64) -- the two wait states of a
+// dependent SrcC are NOT hidden in the issue interval, the merge (two packed adds per layer) is the cheaper price.
 template <int BB>
 __device__ __forceinline__ void hh_block(const float (&wk)[64], const f4 hA, f4& accA, f4& accB) {
     accA = mfx<BB>(hA[0], wk[4 * BB + 0], accA);
@@ -83,14 +142,15 @@ __device__ __forceinline__ f4 elu_x(const f4 v) {
     if constexpr (SC) return elu_quad_scaled(v);
     else return elu_quad(v);
 }
-template <bool SC = true>
-__device__ __forceinline__ f4 hh_layer(const float (&wk)[64], const float bias, const f4 hA) {
+// ORD / m: this seam's place in the caller's sequence of transposes (quad_transpose_seq)
+template <bool SC, int ORD>
+__device__ __forceinline__ f4 hh_layer(const float (&wk)[64], const float bias, const f4 hA, XMask& m) {
     f4 accA = f4{bias, bias, bias, bias}, accB = f4{0.f, 0.f, 0.f, 0.f};
     hh_block<0>(wk, hA, accA, accB); hh_block<1>(wk, hA, accA, accB); hh_block<2>(wk, hA, accA, accB); hh_block<3>(wk, hA, accA, accB);
     hh_block<4>(wk, hA, accA, accB); hh_block<5>(wk, hA, accA, accB); hh_block<6>(wk, hA, accA, accB); hh_block<7>(wk, hA, accA, accB);
     hh_block<8>(wk, hA, accA, accB); hh_block<9>(wk, hA, accA, accB); hh_block<10>(wk, hA, accA, accB); hh_block<11>(wk, hA, accA, accB);
     hh_block<12>(wk, hA, accA, accB); hh_block<13>(wk, hA, accA, accB); hh_block<14>(wk, hA, accA, accB); hh_block<15>(wk, hA, accA, accB);
-    return quad_transpose(elu_x<SC>(accA + accB));
+    return quad_transpose_seq<ORD>(elu_x<SC>(accA + accB), m);
 }
 
 // The same layer with the weights in AccVGPRs (K2x's AE head: 128 B operands that do not fit the 256 architectural VGPRs next to the DE's).
@@ -109,8 +169,8 @@ __device__ __forceinline__ void hh_block_acc(const float (&wk)[64], const f4 hA,
         : "+v"(accA), "+v"(accB)
         : "v"(hA[0]), "v"(hA[1]), "v"(hA[2]), "v"(hA[3]), "a"(wk[4 * BB + 0]), "a"(wk[4 * BB + 1]), "a"(wk[4 * BB + 2]), "a"(wk[4 * BB + 3]), "n"(BB));
 }
-template <bool SC = true>
-__device__ __forceinline__ f4 hh_layer_acc(const float (&wk)[64], const float bias, const f4 hA) {
+template <bool SC, int ORD>
+__device__ __forceinline__ f4 hh_layer_acc(const float (&wk)[64], const float bias, const f4 hA, XMask& m) {
     f4 accA = f4{bias, bias, bias, bias}, accB = f4{0.f, 0.f, 0.f, 0.f};
     asm volatile("s_nop 1" : "+v"(accA), "+v"(accB));           // VALU write -> MFMA SrcC read
     hh_block_acc<0>(wk, hA, accA, accB); hh_block_acc<1>(wk, hA, accA, accB); hh_block_acc<2>(wk, hA, accA, accB); hh_block_acc<3>(wk, hA, accA, accB);
@@ -118,7 +178,7 @@ __device__ __forceinline__ f4 hh_layer_acc(const float (&wk)[64], const float bi
     hh_block_acc<8>(wk, hA, accA, accB); hh_block_acc<9>(wk, hA, accA, accB); hh_block_acc<10>(wk, hA, accA, accB); hh_block_acc<11>(wk, hA, accA, accB);
     hh_block_acc<12>(wk, hA, accA, accB); hh_block_acc<13>(wk, hA, accA, accB); hh_block_acc<14>(wk, hA, accA, accB); hh_block_acc<15>(wk, hA, accA, accB);
     asm volatile("s_nop 3" : "+v"(accA), "+v"(accB));           // MFMA write (2 passes) -> VALU read
-    return quad_transpose(elu_x<SC>(accA + accB));
+    return quad_transpose_seq<ORD>(elu_x<SC>(accA + accB), m);
 }
 
 template <int Q0, int NQ>

@@ -272,14 +272,18 @@ __global__ __launch_bounds__(64 * kXWaves * (ROLES ? 2 : 1)) void integrate_x_ke
         }
     };
 
-    // DE right-hand side in the state layout: k(X01, X23)
-    auto rhs = [&](const float s01, const float s23, const f4 cz, float& k01, float& k23) {
+    // The mask the next in-quad transpose starts on (psnode_mfma_x.h: quad_transpose_seq).  A stage has three seams, so consecutive stages
+    // alternate their parity P; an even number of stages per step hands the next step the mask it starts with.
+    XMask vm = xmask_even();
+    // DE right-hand side in the state layout: k(X01, X23).  P: the transpose order of the stage's first seam (orders P, !P, P)
+    auto rhs = [&](auto par_tag, const float s01, const float s23, const f4 cz, float& k01, float& k23) {
+        constexpr int P = decltype(par_tag)::value;
         f4 accA = cz, accB = f4{0.f, 0.f, 0.f, 0.f};
         accA = mfx<0>(s01, w1x[0], accA);  accB = mfx<4>(s01, w1x[1], accB);
         accA = mfx<8>(s01, w1x[2], accA);  accB = mfx<12>(s01, w1x[3], accB);
         accA = mfx<0>(s23, w1x[4], accA);  accB = mfx<4>(s23, w1x[5], accB);
         accA = mfx<8>(s23, w1x[6], accA);  accB = mfx<12>(s23, w1x[7], accB);
-        f4 hA = quad_transpose(elu_x<!SAVE>(accA + accB));
+        f4 hA = quad_transpose_seq<P>(elu_x<!SAVE>(accA + accB), vm);
         float* slot = ROLES ? ring_mine + (ring_half * 4 + ring_sl) * kXSlotFloats : nullptr;
         if constexpr (ROLES) {                                       // the stage's rows into the ring slot; the partner wave stores them
             *reinterpret_cast<f2*>(slot + 768 + 2 * l) = f2{s01, s23};
@@ -294,10 +298,10 @@ __global__ __launch_bounds__(64 * kXWaves * (ROLES ? 2 : 1)) void integrate_x_ke
             if constexpr (PSNODE_K1X_SAVE_ABL != 2) sx_run += xo_step;
             if (sa_on) stg<f4>((gptr<float>)(uintptr_t)sa_run, saoff, hA);
         }
-        hA = hh_layer<!SAVE>(w2, b2, hA);
+        hA = hh_layer<!SAVE, 1 - P>(w2, b2, hA, vm);
         if constexpr (ROLES) *reinterpret_cast<f4*>(slot + 256 + 4 * l) = hA;
         else if constexpr (SAVE) { if (sa_on) stg<f4>((gptr<float>)(uintptr_t)(sa_run + sa_layer), saoff, hA); }
-        hA = hh_layer<!SAVE>(w3, b3, hA);
+        hA = hh_layer<!SAVE, P>(w3, b3, hA, vm);
         if constexpr (ROLES) {
             *reinterpret_cast<f4*>(slot + 512 + 4 * l) = hA;
             if (++ring_sl == 4) { lds_barrier(); ring_sl = 0; ring_half ^= 1; }       // a half is complete: hand it over, fill the other one
@@ -323,9 +327,14 @@ __global__ __launch_bounds__(64 * kXWaves * (ROLES ? 2 : 1)) void integrate_x_ke
     //   two steps (FAST, Euler / Midpoint):     store(k-2), load t, load e, store(k-1)     -> vmcnt(4)
     // A 1 us Euler step does not cover a clock / z row that misses the caches (SQ_WAIT_ANY 28 % of the wave's cycles with one step of
     // look-ahead, profiles/r05g_k1x_euler_pmc_sq.txt); RK4's 3 us step does.
-    auto step = [&](const int k, float& tuse, float& euse, auto pf_tag, auto wait_tag) {
+    //   one step, two clock slots (FAST, RK4):  store(k-1)                                  -> vmcnt(1)
+    // `tprev`: the register that holds t[k].  The forms above keep it in t_cur and copy tuse there; with LAG (lag_tag) it is the OTHER clock
+    // slot, which is dead once h is formed -- the prefetch of t[k + 2] lands in IT, the next step uses the two slots with their roles swapped,
+    // and the source has no register to move at the end of a step.
+    auto step = [&](const int k, float& tprev, float& tuse, float& euse, auto pf_tag, auto wait_tag, auto lag_tag) {
         constexpr bool PF = decltype(pf_tag)::value;
         constexpr int WAITN = decltype(wait_tag)::value;
+        constexpr bool LAG = decltype(lag_tag)::value;
         // SAVE: a step also issued 4 stores per stage (xstage + three layers, every one from at least one lane of every wave) behind its prefetch
         constexpr int NSAVE = (SAVE && !ROLES) ? 4 * (METHOD == PSNODE_EULER ? 1 : (METHOD == PSNODE_MIDPOINT ? 2 : 4)) : 0;
         // ring of R steps of look-ahead (wait tag 100 + R): behind the loads in hand sit the rest of their own step (row store + saved rows) and
@@ -335,8 +344,8 @@ __global__ __launch_bounds__(64 * kXWaves * (ROLES ? 2 : 1)) void integrate_x_ke
         static_assert(WN <= 63, "vmcnt is 6 bits");
         if (pair_ok && WN > 0) __builtin_amdgcn_s_waitcnt(0x0F70 | (WN & 15) | ((WN >> 4) << 14));
         else __builtin_amdgcn_s_waitcnt(0x0F70);                              // vmcnt(0)
-        const float h_ = tuse - t_cur;
-        t_cur = tuse;
+        const float h_ = tuse - tprev;
+        if constexpr (!LAG) tprev = tuse;
         const float eA = eon ? (b < ne ? euse - a0e : euse) : 0.0f;
         float s01 = X01, s23 = X23;
         if constexpr (!FAST) {
@@ -349,7 +358,8 @@ __global__ __launch_bounds__(64 * kXWaves * (ROLES ? 2 : 1)) void integrate_x_ke
             xt_run += xst;
         }
         if constexpr (PF) {   // prefetch: the clock entry and the external row the running bases point at (the caller keeps them inside the grid)
-            tuse = ldg<float>(as_g(trun), toff);
+            if constexpr (LAG) tprev = ldg<float>(as_g(trun), toff);
+            else tuse = ldg<float>(as_g(trun), toff);
             if constexpr (FAST) {
                 euse = ldg<float>(as_g(zrun), zoff);
             } else {
@@ -366,19 +376,22 @@ __global__ __launch_bounds__(64 * kXWaves * (ROLES ? 2 : 1)) void integrate_x_ke
         xo_run += xo_step;
         const f4 cz = ext_mfmas<0, 4 * NZM>(w1e, eA, c0);            // per-step constant of L1
         float k1a, k1b;
-        rhs(s01, s23, cz, k1a, k1b);
+        using P0 = std::integral_constant<int, 0>;
+        using P1 = std::integral_constant<int, 1>;
+        if constexpr (METHOD == PSNODE_EULER) vm = xmask_even();     // (one stage per step: its three seams leave the other mask)
+        rhs(P0{}, s01, s23, cz, k1a, k1b);
         if constexpr (METHOD == PSNODE_EULER) {
             X01 = s01 + h_ * k1a; X23 = s23 + h_ * k1b;
         } else if constexpr (METHOD == PSNODE_MIDPOINT) {
             const float hh = 0.5f * h_;
             float k2a, k2b;
-            rhs(s01 + k1a * hh, s23 + k1b * hh, cz, k2a, k2b);
+            rhs(P1{}, s01 + k1a * hh, s23 + k1b * hh, cz, k2a, k2b);
             X01 = s01 + h_ * k2a; X23 = s23 + h_ * k2b;
         } else {
             float k2a, k2b, k3a, k3b, k4a, k4b;
-            rhs(s01 + h_ * k1a * kOneThird, s23 + h_ * k1b * kOneThird, cz, k2a, k2b);
-            rhs(s01 + h_ * (k2a - k1a * kOneThird), s23 + h_ * (k2b - k1b * kOneThird), cz, k3a, k3b);
-            rhs(s01 + h_ * (k1a - k2a + k3a), s23 + h_ * (k1b - k2b + k3b), cz, k4a, k4b);
+            rhs(P1{}, s01 + h_ * k1a * kOneThird, s23 + h_ * k1b * kOneThird, cz, k2a, k2b);
+            rhs(P0{}, s01 + h_ * (k2a - k1a * kOneThird), s23 + h_ * (k2b - k1b * kOneThird), cz, k3a, k3b);
+            rhs(P1{}, s01 + h_ * (k1a - k2a + k3a), s23 + h_ * (k1b - k2b + k3b), cz, k4a, k4b);
             X01 = s01 + (k1a + 3.0f * (k2a + k3a) + k4a) * h_ * 0.125f;
             X23 = s23 + (k1b + 3.0f * (k2b + k3b) + k4b) * h_ * 0.125f;
         }
@@ -387,7 +400,13 @@ __global__ __launch_bounds__(64 * kXWaves * (ROLES ? 2 : 1)) void integrate_x_ke
     using W0 = std::integral_constant<int, 0>;
     using W1 = std::integral_constant<int, 1>;
     using W4 = std::integral_constant<int, 4>;
+    using NOLAG = std::false_type;
     constexpr bool TWO_AHEAD = FAST && METHOD != PSNODE_RK4_38;
+    // RK4's 3 us step covers its loads with one step of look-ahead, but over ONE clock register the step ends in a rotation (t_nxt -> t_cur,
+    // the arrived values out of the way of the prefetch) behind a vmcnt(0), each instruction ~4.5 cycles of a lone wave.  Two clock slots and
+    // the loop unrolled by two (`step`: LAG) need no rotation in the source; in the listing 2 copies per TWO steps remain on the back edge
+    // (the allocator does not coalesce the loop-carried slots) and no wait is tighter than vmcnt(1) (profiles/k1x_seams_ab.txt).
+    constexpr bool TWO_SLOT = FAST && METHOD == PSNODE_RK4_38;
     // The saving forward: its 4 S stores per step retire IN ORDER in front of the next loads, so with one step of look-ahead a step cannot start
     // before the previous step's rows are acknowledged -- 17 KB in flight per wave, 3.2 TB/s (a plain fill writes this HBM at 6.9 TB/s,
     // profiles/r05ai_hbm_write_bw.txt).  A ring of R steps gives the stores R steps to drain: R = 3 at RK4 (55 operations behind the loads; vmcnt
@@ -409,7 +428,7 @@ __global__ __launch_bounds__(64 * kXWaves * (ROLES ? 2 : 1)) void integrate_x_ke
         int k = 0;
         for (; k + 2 * RING + 1 <= nT; k += RING) {  // RING steps that all prefetch: the last one requests row k + 2 RING - 1 <= T - 2
 #pragma unroll
-            for (int j = 0; j < RING; ++j) step(k + j, tq[j], eq[j], std::true_type{}, WR{});
+            for (int j = 0; j < RING; ++j) step(k + j, t_cur, tq[j], eq[j], std::true_type{}, WR{}, NOLAG{});
         }
         __builtin_amdgcn_s_waitcnt(0x0F70);           // the last (up to 2 RING) steps: what the ring holds has arrived; refills wait on the spot
         int slot = 0;                                 // k is a multiple of RING here
@@ -418,8 +437,8 @@ __global__ __launch_bounds__(64 * kXWaves * (ROLES ? 2 : 1)) void integrate_x_ke
 #pragma unroll
             for (int j = 0; j < RING; ++j) {
                 if (slot == j) {
-                    if (pf) step(k, tq[j], eq[j], std::true_type{}, W0{});
-                    else step(k, tq[j], eq[j], std::false_type{}, W0{});
+                    if (pf) step(k, t_cur, tq[j], eq[j], std::true_type{}, W0{}, NOLAG{});
+                    else step(k, t_cur, tq[j], eq[j], std::false_type{}, W0{}, NOLAG{});
                 }
             }
             slot = slot + 1 == RING ? 0 : slot + 1;
@@ -433,22 +452,36 @@ __global__ __launch_bounds__(64 * kXWaves * (ROLES ? 2 : 1)) void integrate_x_ke
         __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
         int k = 0;
         for (; k + 5 <= nT; k += 2) {         // steps k and k + 1 both prefetch: k + 1 <= T - 4
-            step(k, t_nxt, e_nxt, std::true_type{}, W4{});
-            step(k + 1, t_n2, e_n2, std::true_type{}, W4{});
+            step(k, t_cur, t_nxt, e_nxt, std::true_type{}, W4{}, NOLAG{});
+            step(k + 1, t_cur, t_n2, e_n2, std::true_type{}, W4{}, NOLAG{});
         }
         if (k + 4 <= nT) {                    // one more step that can still prefetch (t[k + 3] exists); k is even here
-            step(k, t_nxt, e_nxt, std::true_type{}, W4{});
+            step(k, t_cur, t_nxt, e_nxt, std::true_type{}, W4{}, NOLAG{});
             ++k;
         }
         __builtin_amdgcn_s_waitcnt(0x0F70);   // the last (up to two) steps: everything has arrived, nothing more is requested
         for (; k + 1 < nT; ++k) {
-            if (k & 1) step(k, t_n2, e_n2, std::false_type{}, W0{});
-            else step(k, t_nxt, e_nxt, std::false_type{}, W0{});
+            if (k & 1) step(k, t_cur, t_n2, e_n2, std::false_type{}, W0{}, NOLAG{});
+            else step(k, t_cur, t_nxt, e_nxt, std::false_type{}, W0{}, NOLAG{});
         }
+    } else if constexpr (TWO_SLOT) {
+        using LAG = std::true_type;           // (t_cur, t_nxt) are the two clock slots: even steps read t[k] from t_cur, odd ones from t_nxt
+        __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): the first step's inputs (no store is in flight yet for the loop's vmcnt(1) to skip)
+        int k = 0;
+        for (; k + 4 <= nT; k += 2) {         // steps k and k + 1 both prefetch: k + 1 <= T - 3
+            step(k, t_cur, t_nxt, e_nxt, std::true_type{}, W1{}, LAG{});
+            step(k + 1, t_nxt, t_cur, e_nxt, std::true_type{}, W1{}, LAG{});
+        }
+        if (k + 3 <= nT) {                    // one more step that prefetches (t[k + 2] exists); k is even here
+            step(k, t_cur, t_nxt, e_nxt, std::true_type{}, W1{}, LAG{});
+            ++k;
+        }
+        if (k & 1) step(k, t_nxt, t_cur, e_nxt, std::false_type{}, W0{}, LAG{});       // k = T - 2: the last step requests nothing
+        else step(k, t_cur, t_nxt, e_nxt, std::false_type{}, W0{}, LAG{});
     } else {
         __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): the first step's inputs (no store is in flight yet for the loop's vmcnt(1) to skip)
-        for (int k = 0; k + 2 < nT; ++k) step(k, t_nxt, e_nxt, std::true_type{}, W1{});
-        step(nT - 2, t_nxt, e_nxt, std::false_type{}, W0{});
+        for (int k = 0; k + 2 < nT; ++k) step(k, t_cur, t_nxt, e_nxt, std::true_type{}, W1{}, NOLAG{});
+        step(nT - 2, t_cur, t_nxt, e_nxt, std::false_type{}, W0{}, NOLAG{});
     }
     store_row(xo_run);
     };      // time_loop

@@ -226,14 +226,18 @@ __global__ __launch_bounds__(64 * kXWaves) void integrate_xd_kernel(const Integr
     float* sae_run = SAVE ? a.saeact : nullptr;                     // the AE head's rows of the NEXT grid point to be evaluated
     const unsigned saoff = SAVE ? (unsigned)(tr * hp + 4 * b) * 4u : 0u;
     const bool sa_on = SAVE && valid && 4 * b < hp;
-    // DE right-hand side in the state layout (K1x's rhs)
-    auto rhs = [&](const float s01, const float s23, const f4 cz, float& k01, float& k23) {
+    // The mask the next in-quad transpose starts on (psnode_mfma_x.h: quad_transpose_seq).  Every sequence of seams -- the DE stages of a step, one
+    // AE head (its own XMask) -- starts from xmask_even() and alternates the order from seam to seam: 3 mask moves per seam instead of 4.
+    XMask vm = xmask_even();
+    // DE right-hand side in the state layout (K1x's rhs).  P: the transpose order of the stage's first seam (orders P, !P, P)
+    auto rhs = [&](auto par_tag, const float s01, const float s23, const f4 cz, float& k01, float& k23) {
+        constexpr int P = decltype(par_tag)::value;
         f4 accA = cz, accB = f4{0.f, 0.f, 0.f, 0.f};
         accA = mfx<0>(s01, w1x[0], accA);  accB = mfx<4>(s01, w1x[1], accB);
         accA = mfx<8>(s01, w1x[2], accA);  accB = mfx<12>(s01, w1x[3], accB);
         accA = mfx<0>(s23, w1x[4], accA);  accB = mfx<4>(s23, w1x[5], accB);
         accA = mfx<8>(s23, w1x[6], accA);  accB = mfx<12>(s23, w1x[7], accB);
-        f4 hA = quad_transpose(elu_x<!SAVE>(accA + accB));
+        f4 hA = quad_transpose_seq<P>(elu_x<!SAVE>(accA + accB), vm);
         if constexpr (SAVE) {                                        // rows (step, stage): the stage input, then the three layers as they appear
             if (pair_ok) {
                 if (st01) stg<f2>((gptr<float>)(uintptr_t)sx_run, xooff, f2{s01, s23});
@@ -244,9 +248,9 @@ __global__ __launch_bounds__(64 * kXWaves) void integrate_xd_kernel(const Integr
             sx_run += xo_step;
             if (sa_on) stg<f4>((gptr<float>)(uintptr_t)sa_run, saoff, hA);
         }
-        hA = hh_layer<!SAVE>(w2, b2, hA);
+        hA = hh_layer<!SAVE, 1 - P>(w2, b2, hA, vm);
         if constexpr (SAVE) { if (sa_on) stg<f4>((gptr<float>)(uintptr_t)(sa_run + sa_layer), saoff, hA); }
-        hA = hh_layer<!SAVE>(w3, b3, hA);
+        hA = hh_layer<!SAVE, P>(w3, b3, hA, vm);
         if constexpr (SAVE) {
             if (sa_on) stg<f4>((gptr<float>)(uintptr_t)(sa_run + 2 * sa_layer), saoff, hA);
             sa_run += 3 * sa_layer;
@@ -272,11 +276,12 @@ __global__ __launch_bounds__(64 * kXWaves) void integrate_xd_kernel(const Integr
         accA = mfx<2>(eAE, aw1e[2], accA);  accB = mfx<3>(eAE, aw1e[3], accB);
         accA = mfx<4>(eAE, aw1e[4], accA);  accB = mfx<5>(eAE, aw1e[5], accB);
         accA = mfx<6>(eAE, aw1e[6], accA);  accB = mfx<7>(eAE, aw1e[7], accB);
-        f4 hA = quad_transpose(elu_x<!SAVE>(accA + accB));
+        XMask am = xmask_even();                                     // (the head also runs inside the event branch: its sequence is its own)
+        f4 hA = quad_transpose_seq<0>(elu_x<!SAVE>(accA + accB), am);
         if constexpr (SAVE) { if (sa_on) stg<f4>((gptr<float>)(uintptr_t)rows, saoff, hA); }
-        hA = hh_layer_acc<!SAVE>(aw2, ab2, hA);
+        hA = hh_layer_acc<!SAVE, 1>(aw2, ab2, hA, am);
         if constexpr (SAVE) { if (sa_on) stg<f4>((gptr<float>)(uintptr_t)(rows + lstride), saoff, hA); }
-        hA = hh_layer_acc<!SAVE>(aw3, ab3, hA);
+        hA = hh_layer_acc<!SAVE, 0>(aw3, ab3, hA, am);
         if constexpr (SAVE) { if (sa_on) stg<f4>((gptr<float>)(uintptr_t)(rows + 2 * lstride), saoff, hA); }
         f4 p0 = ab4c;
         p0 = mfn(aw4a[0], hA[0], p0);
@@ -392,19 +397,22 @@ __global__ __launch_bounds__(64 * kXWaves) void integrate_xd_kernel(const Integr
         const f4 cz = ext_mfmas<0, 16>(w1e, eA, c0);
         const float s01 = X01, s23 = X23;
         float k1a, k1b;
-        rhs(s01, s23, cz, k1a, k1b);
+        using P0 = std::integral_constant<int, 0>;
+        using P1 = std::integral_constant<int, 1>;
+        vm = xmask_even();                                           // (the AE head in front of this step used vcc for its own sequence)
+        rhs(P0{}, s01, s23, cz, k1a, k1b);
         if constexpr (METHOD == PSNODE_EULER) {
             X01 = s01 + h_ * k1a; X23 = s23 + h_ * k1b;
         } else if constexpr (METHOD == PSNODE_MIDPOINT) {
             const float hh = 0.5f * h_;
             float k2a, k2b;
-            rhs(s01 + k1a * hh, s23 + k1b * hh, cz, k2a, k2b);
+            rhs(P1{}, s01 + k1a * hh, s23 + k1b * hh, cz, k2a, k2b);
             X01 = s01 + h_ * k2a; X23 = s23 + h_ * k2b;
         } else {
             float k2a, k2b, k3a, k3b, k4a, k4b;
-            rhs(s01 + h_ * k1a * kOneThird, s23 + h_ * k1b * kOneThird, cz, k2a, k2b);
-            rhs(s01 + h_ * (k2a - k1a * kOneThird), s23 + h_ * (k2b - k1b * kOneThird), cz, k3a, k3b);
-            rhs(s01 + h_ * (k1a - k2a + k3a), s23 + h_ * (k1b - k2b + k3b), cz, k4a, k4b);
+            rhs(P1{}, s01 + h_ * k1a * kOneThird, s23 + h_ * k1b * kOneThird, cz, k2a, k2b);
+            rhs(P0{}, s01 + h_ * (k2a - k1a * kOneThird), s23 + h_ * (k2b - k1b * kOneThird), cz, k3a, k3b);
+            rhs(P1{}, s01 + h_ * (k1a - k2a + k3a), s23 + h_ * (k1b - k2b + k3b), cz, k4a, k4b);
             X01 = s01 + (k1a + 3.0f * (k2a + k3a) + k4a) * h_ * 0.125f;
             X23 = s23 + (k1b + 3.0f * (k2b + k3b) + k4b) * h_ * 0.125f;
         }
