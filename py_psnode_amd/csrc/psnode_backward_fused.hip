@@ -26,15 +26,80 @@
 #include <type_traits>
 #include <string.h>
 
+#include "psnode_tile_bwd.h"
 #include "psnode_wide_pack.h"
+
+// ---- knobs (make EXTRA=-DPSNODE_K4F_...=v BUILD=... OUT=...); the first group is read by the shared code through K4fTune
+#ifndef PSNODE_K4F_BOUND
+#define PSNODE_K4F_BOUND 3      // 0: never bound the scheduler's read-ahead in the layer loops, 1: always at 8 waves, 2: only at RK4, 3: RK4 + Midpoint
+                                // (profiles/r03m_bwd_ab.txt, hidden-128 training step rk4 / midpoint / euler: 0 -> 65.1 / 28.0 / 11.95 ms, 1 -> 52.8 / 22.9 / 12.19)
+#endif
+#ifndef PSNODE_K4F_BOUND_SAVED
+#define PSNODE_K4F_BOUND_SAVED 3      // the same knob for the instances that read saved activations (REC = false)
+#endif
+#ifndef PSNODE_K4F_EVERY
+#define PSNODE_K4F_EVERY 2      // a sched_barrier behind every EVERY-th chunk
+#endif
+#ifndef PSNODE_K4F_EVERY_SAVED
+#define PSNODE_K4F_EVERY_SAVED 2
+#endif
+#ifndef PSNODE_K4F_TREAD_AHEAD
+#define PSNODE_K4F_TREAD_AHEAD 1     // <= 4 waves (one wave per SIMD, registers to spare): every LDS read of the layer -- the other waves' tiles, the
+                                     // weight chunks and the transposed tiles of the weight gradient -- is in flight before the first MFMA that
+                                     // needs one.  Left to the scheduler the transposed reads recycled two registers, each pair of MFMAs behind
+                                     // its own lgkmcnt(0) (found in the ISA)
+#endif
+#ifndef PSNODE_K4F_DEFER_DW
+#define PSNODE_K4F_DEFER_DW 1        // <= 4 waves: the weight-gradient MFMAs of a layer are issued behind the NEXT exchange's LDS write, in front of its
+                                     // barrier -- one wave per SIMD has nothing else to keep the MFMA pipe busy while the tile travels
+#endif
+#ifndef PSNODE_K4F_DEFER8
+#define PSNODE_K4F_DEFER8 1         // 8 waves: the same deferral without holding the transposed tiles: they are re-read from the previous exchange's parity
+#endif
+#ifndef PSNODE_K4F_DW_PAIR
+#define PSNODE_K4F_DW_PAIR 4     // 8 waves: the weight-gradient MFMAs of this many chunks interleaved (one accumulator chain each, their transposed tiles read first)
+#endif
+#ifndef PSNODE_K4F_W_AHEAD
+#define PSNODE_K4F_W_AHEAD 1      // two-role chain: the layer's weight chunks are read from LDS BEFORE the exchange's barrier (they do not depend on it): behind it
+                                  // only the three tiles of the other waves are left to read -- half of the LDS traffic on the critical path
+#endif
+#ifndef PSNODE_K4F_DP_GROUP
+#define PSNODE_K4F_DP_GROUP 7      // 8 waves, transposed layers: tiles and weight chunks of this many chunks read ahead of their MFMAs (0: as the forward layers).
+                                     // hidden-128 training step RK4, 0 / 3 / 4 / 7: ODE (K4f) 35.9 / 34.6 / 36.0 / 34.5 ms, DAE (K7f) 52.1 / 51.9 / 51.9 / 52.0 (profiles/r03y_dp_group_ab.txt)
+#endif
+#ifndef PSNODE_K4F_ROLES_EARLY
+#define PSNODE_K4F_ROLES_EARLY 1       // chunks (4 MFMAs each) of a contraction issued in the interval its tiles are published in; the rest waits for the
+                                       // interval behind the stage's all-reduce, where the chain is latency-bound and leaves the MFMA pipe idle
+#endif
+#ifndef PSNODE_K4F_ROLES_SMALL
+#define PSNODE_K4F_ROLES_SMALL 1  // the gradient waves also own dW4 and the s columns of dW1 (gk / s / delta1 handed over in LDS tiles): no in-wave
+                                  // transpose is left on the chain
+#endif
+// ... and the ones only this file's step body and launcher read
+#ifndef PSNODE_K4F_ROLES
+#define PSNODE_K4F_ROLES 1      // <= 4 waves, saved activations: a second set of NWV waves per tile owns the H->H weight gradients (below)
+#endif
+#ifndef PSNODE_K4F_ROLES_PRIO
+#define PSNODE_K4F_ROLES_PRIO 1 // the chain waves run at a higher issue priority than the gradient waves
+#endif
+#ifndef PSNODE_K4F_SAVED_AHEAD
+#define PSNODE_K4F_SAVED_AHEAD 2      // 0: rows of a stage requested at its top; 1: a whole stage ahead; 2: late in the previous stage (in front of its last
+                                      // exchange).  vmcnt counts in order: every spilled-invariant reload behind an outstanding HBM request waits for it, so
+                                      // requesting EARLY is what exposed the latency at RK4 (43.8 / 39.2 / 37.9 ms per hidden-128 training step for 1 / 0 / 2;
+                                      // Euler, no spills: 9.3 / 10.5 / 9.4: profiles/r03t_ahead.txt)
+#endif
+#ifndef PSNODE_K4F_SAVED_AHEAD_ROLES
+#define PSNODE_K4F_SAVED_AHEAD_ROLES 3     // two-role form (registers to spare on the chain): 3 = the rows are requested TWO stages ahead
+#endif
+#ifndef PSNODE_K4F_NEXT_LATE
+#define PSNODE_K4F_NEXT_LATE 0
+#endif
+#ifndef PSNODE_K4F_RING_LATE
+#define PSNODE_K4F_RING_LATE 1
+#endif
 
 namespace psnode {
 namespace {
-
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef float f2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ f4 fm4(float a, float b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 
 struct FusedDev {
     int method, xd, zd, hreal, n_events, NP;
@@ -53,36 +118,6 @@ struct FusedDev {
     const float *sact, *sxst;             // saved by the forward call ([T-1,S,3,B,H] / [T-1,S,B,xd]) or null: recompute
 };
 
-#ifndef PSNODE_K4F_BOUND
-#define PSNODE_K4F_BOUND 3      // 0: never bound the scheduler's read-ahead in the layer loops, 1: always at 8 waves, 2: only at RK4, 3: RK4 + Midpoint
-                                // (profiles/r03m_bwd_ab.txt, hidden-128 training step rk4 / midpoint / euler: 0 -> 65.1 / 28.0 / 11.95 ms, 1 -> 52.8 / 22.9 / 12.19)
-#endif
-#ifndef PSNODE_K4F_BOUND_SAVED
-#define PSNODE_K4F_BOUND_SAVED 3      // the same knob for the instances that read saved activations (REC = false)
-#endif
-#ifndef PSNODE_K4F_EVERY_SAVED
-#define PSNODE_K4F_EVERY_SAVED 2
-#endif
-#ifndef PSNODE_K4F_EVERY
-#define PSNODE_K4F_EVERY 2      // a sched_barrier behind every EVERY-th chunk
-#endif
-constexpr int FTILE = 64 * 4 + 4 * 8;     // padded 16x16 tile (floats): lane l's four rows 4g..4g+3 of column j at 4l + 8g
-
-#ifndef PSNODE_K4F_ROLES
-#define PSNODE_K4F_ROLES 1      // <= 4 waves, saved activations: a second set of NWV waves per tile owns the H->H weight gradients (below)
-#endif
-#ifndef PSNODE_K4F_SAVED_AHEAD
-#define PSNODE_K4F_SAVED_AHEAD 2      // see the comment at its use in the stage loop
-#endif
-#define PSNODE_K4F_SAVED_AHEAD_DEFAULT PSNODE_K4F_SAVED_AHEAD
-#ifndef PSNODE_K4F_ROLES_SMALL
-#define PSNODE_K4F_ROLES_SMALL 1  // the gradient waves also own dW4 and the s columns of dW1 (gk / s / delta1 handed over in LDS tiles): no in-wave
-                                  // transpose is left on the chain
-#endif
-#ifndef PSNODE_K4F_ROLES_PRIO
-#define PSNODE_K4F_ROLES_PRIO 1 // the chain waves run at a higher issue priority than the gradient waves
-#endif
-
 // ROLES (round 4): the two-role form of the saved-activation instances at <= 4 waves per tile.  One wave per SIMD cannot hide an LDS
 // exchange or an MFMA result latency, and half of the backward's MFMAs -- the weight gradients dW2 / dW3 -- are not on the adjoint's
 // critical path at all.  The workgroup gets NWV more waves (one more per SIMD): waves 0..NWV-1 are the CHAIN (the sweep, as before, minus
@@ -95,6 +130,21 @@ constexpr int FTILE = 64 * 4 + 4 * 8;     // padded 16x16 tile (floats): lane l'
 template <int NWV> __device__ __forceinline__ float* roles_d1_tile(float* xb, const int wv) { return xb + (4 * NWV + wv) * FTILE; }
 template <int NWV> __device__ __forceinline__ float* roles_gk_tile(float* xb) { return xb + 5 * NWV * FTILE; }
 template <int NWV> __device__ __forceinline__ float* roles_s_tile(float* xb) { return xb + (5 * NWV + 1) * FTILE; }
+
+// what the shared text (psnode_tile_bwd_chain.h) reads: everything in which K4f's tile machinery differs from K7f's
+struct K4fTune {
+    static constexpr int bound(const bool rec) { return rec ? PSNODE_K4F_BOUND : PSNODE_K4F_BOUND_SAVED; }
+    static constexpr int every(const bool rec) { return rec ? PSNODE_K4F_EVERY : PSNODE_K4F_EVERY_SAVED; }
+    static constexpr bool TREAD_AHEAD = PSNODE_K4F_TREAD_AHEAD, DEFER_DW = PSNODE_K4F_DEFER_DW, DEFER8 = PSNODE_K4F_DEFER8;
+    static constexpr int DW_PAIR = PSNODE_K4F_DW_PAIR;
+    static constexpr bool PAIR_REC = false;      // DEFER8 and the paired dW arm: saved-activation instances only (recompute instance at RK4:
+                                                 // 48.2 -> 50.3 ms with it, profiles/r03y_dw_pair_ab.txt)
+    static constexpr bool W_AHEAD = PSNODE_K4F_W_AHEAD;
+    static constexpr int DP_GROUP = PSNODE_K4F_DP_GROUP;
+    static constexpr bool ROLES_SMALL = PSNODE_K4F_ROLES_SMALL;
+    // image `layer` of wT for mid_lds, in 64-bit arithmetic (K7f: 32-bit): either form moves the other kernel's register allocation at 8 waves
+    template <int NWV> static __device__ __forceinline__ const f4* image(const f4* wT, const int layer, const int w, const int l) { return wT + ((size_t)layer * NWV * NWV + w) * 64 + l; }
+};
 
 template <int METHOD, int NZM, int NWV>
 __device__ __forceinline__ void fused_gradient_wave(const FusedDev& a, float* __restrict__ xb, const int l, const int wg) {
@@ -126,10 +176,6 @@ __device__ __forceinline__ void fused_gradient_wave(const FusedDev& a, float* __
     f4 sv1 = zero4, sv2 = zero4, sv3 = zero4;
     if (nT >= 2) load_saved((nT - 1) * S - 1, sv1, sv2, sv3);
     int p = 0;
-#ifndef PSNODE_K4F_ROLES_EARLY
-#define PSNODE_K4F_ROLES_EARLY 1       // chunks (4 MFMAs each) of a contraction issued in the interval its tiles are published in; the rest waits for the
-                                       // interval behind the stage's all-reduce, where the chain is latency-bound and leaves the MFMA pipe idle
-#endif
     constexpr int E = PSNODE_K4F_ROLES_EARLY < NWV ? PSNODE_K4F_ROLES_EARLY : NWV;
     auto read_tiles = [&](const int par, f4 (&dT)[NWV]) {
 #pragma unroll
@@ -261,14 +307,11 @@ __global__ __launch_bounds__(64 * NWV * (ROLES ? 2 : 1)) void ode_backward_fused
     // ---- forward image -> registers (as K1), transposed images -> LDS
     const float* pw = pack_de + (size_t)w * (RD::COUNT + NA) * 64 + l;
     constexpr bool STREAM = NWV >= 8 && REC;     // forward / transposed images swapped in LDS per phase; activations through the ring
-    constexpr int BMODE = REC ? PSNODE_K4F_BOUND : PSNODE_K4F_BOUND_SAVED;
     // (rounds 3's exception for the recompute instance <Midpoint, NZM = 0, 8 waves> is gone: its wrong dL/dall_initial / dW1 were a VGPR
     //  spill -- of `l & 15`, live from the prologue to the epilogue -- that the register allocator had placed inside the `4 + g < x_dim`
     //  arm of load_x2, a divergent region whose EXEC is EMPTY at x_dim = 8: nothing was saved, and the epilogue's `i < n` predicates read
     //  whatever the scratch slot held (zeros: every lane acted as column 0).  Dropping the sched_barriers only moved the spill.  load_x2
     //  is branch-free now (psnode_common.h: ldg_sel); profiles/scripts/isa_lint.py check A watches for the pattern.  DESIGN.md, round 4.)
-    constexpr bool BOUND = NWV >= 8 && (BMODE == 1 || (BMODE == 2 && S >= 4) || (BMODE == 3 && S >= 2));
-    constexpr int EVERY = REC ? PSNODE_K4F_EVERY : PSNODE_K4F_EVERY_SAVED;
     float w1xs[NX], w1z[NZ], w2r[STREAM ? 1 : 4 * NWV], w3r[STREAM ? 1 : 4 * NWV], w4[4];
     f4 b1r, b2, b3, b4;
 #pragma unroll
@@ -282,27 +325,7 @@ __global__ __launch_bounds__(64 * NWV * (ROLES ? 2 : 1)) void ode_backward_fused
         w4[r] = pw[(RD::W4 + r) * 64];
         b1r[r] = pw[(RD::B1 + r) * 64]; b2[r] = pw[(RD::B2 + r) * 64]; b3[r] = pw[(RD::B3 + r) * 64]; b4[r] = pw[(RD::B4 + r) * 64];
     }
-    // LDS-DMA of one layer's image (0: W2, 1: W3) into its region: slot (layer, c, w) <- 64 lanes x 16 B, lane-linear.  The statement
-    // first drains this wave's LDS reads (they are the only readers of these slots) and is invisible to the compiler's wait counts:
-    // dma_wait() before the first use.
-    const unsigned wT_lds = __builtin_amdgcn_readfirstlane((unsigned)reinterpret_cast<uintptr_t>(wT));
-    const unsigned lane16 = 16u * (unsigned)l;
-    auto dma_layer = [&](const f4* __restrict__ img, const int layer) {
-#pragma unroll
-        for (int c = 0; c < NWV; ++c) {
-            const int slot = (layer * NWV + c) * NWV + w;
-            // source = <uniform slot base in SGPRs> + <lane * 16 bytes>: one VGPR for all 32 slots (a per-lane 64-bit pointer per slot is
-            // loop-invariant, and the compiler kept -- and spilled -- all of them)
-            const uintptr_t sb = reinterpret_cast<uintptr_t>(img + (size_t)slot * 64);
-            const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)sb), hi = __builtin_amdgcn_readfirstlane((unsigned)(sb >> 32));
-            const unsigned long long base = ((unsigned long long)hi << 32) | lo;
-            const unsigned dst = __builtin_amdgcn_readfirstlane(wT_lds + (unsigned)slot * 1024u);
-            unsigned keep;
-            asm volatile(PSNODE_LDS_DMA_ASM
-                         : "=&s"(keep) : "v"(lane16), "s"(dst), "s"(base) : "memory");
-        }
-    };
-    auto dma_wait = [&]() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); };
+#include "psnode_tile_bwd_dma.h"
     if constexpr (STREAM) {
         dma_layer(pack_f, 0);
         dma_layer(pack_f, 1);
@@ -353,238 +376,9 @@ __global__ __launch_bounds__(64 * NWV * (ROLES ? 2 : 1)) void ode_backward_fused
     // row of a padded tile that holds column i of the stage input s = (x dims | z dims):  x-dim d sits in row 4(d&3) + (d>>2) (registers
     // 0..1 of lane group d&3), z-dim e in row 4(e&3) + 2 + (e>>2) (registers 2..3 of lane group e&3)
     const int srow = i < xd ? 4 * (i & 3) + (i >> 2) : (i < n ? 4 * ((i - xd) & 3) + 2 + ((i - xd) >> 2) : -1);
-
-    // ---- LDS tiles
-    const int toff = 4 * l + 8 * g;                                   // own slot of a tile
-    const int roff = 72 * (i >> 2) + 4 * g + (i & 3);                 // row i of a tile, columns g, g+4, g+8, g+12
-    auto tile = [&](const int par, const int wv) -> float* { return xb + (par * NWV + wv) * FTILE; };
-    auto put = [&](float* t_, const f4 v) { *reinterpret_cast<f4*>(t_ + toff) = v; };
-    auto getl = [&](const float* t_) -> f4 { return *reinterpret_cast<const f4*>(t_ + toff); };
-    auto get_row = [&](const float* t_, const int ro) -> f4 { const float* s_ = t_ + ro; return f4{s_[0], s_[16], s_[32], s_[48]}; };
-    auto transpose = [&](const f4 v) -> f4 {
-        put(scr, v); return get_row(scr, roff);
-    };   // own D tile -> operand layout (trajectory g + 4kk)
-
-    int p = 0;
-    constexpr bool PREFETCH_ALL = NWV <= 4;
-    // forward H->H layer with the weights in registers (K1's `mid`), returns the pre-activation
-    auto mid = [&](const float (&wm)[4 * NWV], const f4 bias, const f4 h) -> f4 {
-        put(tile(p, w), h);
-        f4 accA = bias, accB = f4{0.f, 0.f, 0.f, 0.f};
-        accA = fm4(wm[0], h[0], accA); accB = fm4(wm[1], h[1], accB);
-        accA = fm4(wm[2], h[2], accA); accB = fm4(wm[3], h[3], accB);
-        __builtin_amdgcn_sched_barrier(0);
-        lds_barrier();
-        f4 vq[NWV];
-        if constexpr (PREFETCH_ALL) {
-#pragma unroll
-            for (int c = 1; c < NWV; ++c) vq[c] = getl(tile(p, (w + c) & (NWV - 1)));
-            __builtin_amdgcn_sched_barrier(0);
-        }
-#pragma unroll
-        for (int c = 1; c < NWV; ++c) {
-            const f4 v = PREFETCH_ALL ? vq[c] : getl(tile(p, (w + c) & (NWV - 1)));
-            accA = fm4(wm[4 * c + 0], v[0], accA); accB = fm4(wm[4 * c + 1], v[1], accB);
-            accA = fm4(wm[4 * c + 2], v[2], accA); accB = fm4(wm[4 * c + 3], v[3], accB);
-        }
-        p ^= 1;
-        return accA + accB;
-    };
-    // the same forward layer with the image of `layer` in LDS (8 waves)
-    auto mid_lds = [&](const int layer, const f4 bias, const f4 h) -> f4 {
-        put(tile(p, w), h);
-        const f4* wl = wT + ((size_t)layer * NWV * NWV + w) * 64 + l;
-        f4 wq = wl[0];
-        f4 accA = bias, accB = f4{0.f, 0.f, 0.f, 0.f};
-        accA = fm4(wq[0], h[0], accA); accB = fm4(wq[1], h[1], accB);
-        accA = fm4(wq[2], h[2], accA); accB = fm4(wq[3], h[3], accB);
-        __builtin_amdgcn_sched_barrier(0);
-        lds_barrier();
-#pragma unroll
-        for (int c = 1; c < NWV; ++c) {
-            const f4 v = getl(tile(p, (w + c) & (NWV - 1)));
-            wq = wl[c * NWV * 64];
-            accA = fm4(wq[0], v[0], accA); accB = fm4(wq[1], v[1], accB);
-            accA = fm4(wq[2], v[2], accA); accB = fm4(wq[3], v[3], accB);
-            if constexpr (BOUND) { if (c % EVERY == EVERY - 1) __builtin_amdgcn_sched_barrier(0); }   // 8 waves: bound the scheduler's read-ahead (registers)
-        }
-        p ^= 1;
-        return accA + accB;
-    };
-    // transposed H->H layer (image in LDS): returns sum_k W[k][own] d[k]; and, from the very tiles the all-gather published, the weight
-    // gradient of that layer: acc[c] += delta(block (w+c) % NWV)^T (x) hT, hT = this wave's own input activations in operand layout
-#ifndef PSNODE_K4F_DEFER_DW
-#define PSNODE_K4F_DEFER_DW 1        // <= 4 waves: the weight-gradient MFMAs of a layer are issued behind the NEXT exchange's LDS write, in front of its
-                                     // barrier -- one wave per SIMD has nothing else to keep the MFMA pipe busy while the tile travels
-#endif
-#ifndef PSNODE_K4F_TREAD_AHEAD
-#define PSNODE_K4F_TREAD_AHEAD 1
-#endif
-    constexpr bool RSM = ROLES && PSNODE_K4F_ROLES_SMALL;
-    constexpr bool DEFER = PREFETCH_ALL && PSNODE_K4F_TREAD_AHEAD && PSNODE_K4F_DEFER_DW && !ROLES;
-    f4 pendT[DEFER ? NWV : 1], pend_h = f4{0.f, 0.f, 0.f, 0.f};      // transposed tiles / own activations of the layer whose gradient is still owed
-#ifndef PSNODE_K4F_DEFER8
-#define PSNODE_K4F_DEFER8 1         // 8 waves: the same deferral without holding the transposed tiles: they are re-read from the previous exchange's parity
-#endif
-#ifndef PSNODE_K4F_DW_PAIR
-#define PSNODE_K4F_DW_PAIR 4
-#endif
-    constexpr bool DEFER8 = NWV >= 8 && PSNODE_K4F_DEFER8 && PSNODE_K4F_DW_PAIR && !REC;
-    int pend_par = 0;
-    auto dw_groups = [&](const int par, const f4 hT, f4 (&acc)[NWV]) {
-        constexpr int DG = PSNODE_K4F_DW_PAIR <= 1 ? 2 : PSNODE_K4F_DW_PAIR;      // chunks per group
-#pragma unroll
-        for (int c = 0; c < NWV; c += DG) {
-            f4 dTg[DG];
-#pragma unroll
-            for (int q = 0; q < DG; ++q) dTg[q] = get_row(tile(par, (w + c + q) & (NWV - 1)), roff);
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-                for (int q = 0; q < DG; ++q) acc[c + q] = fm4(dTg[q][kk], hT[kk], acc[c + q]);
-            if constexpr (BOUND) __builtin_amdgcn_sched_barrier(0);
-        }
-    };
-    auto flush = [&](f4 (&pacc)[NWV]) {
-        if constexpr (DEFER8) dw_groups(pend_par, pend_h, pacc);
-        if constexpr (DEFER) {
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-                for (int c = 0; c < NWV; ++c) pacc[c] = fm4(pendT[c][kk], pend_h[kk], pacc[c]);
-        }
-    };
-    // pacc: the accumulators of the layer handled by the previous call (its gradient MFMAs run here, between this layer's LDS write and barrier)
-    auto midT = [&](const int layer, const f4 d, const f4 hT, f4 (&acc)[NWV], f4 (*pacc)[NWV] = nullptr) -> f4 {
-        put(tile(p, w), d);
-        const f4* wl = wT + ((size_t)layer * NWV * NWV + w) * 64 + l;
-        f4 wq = wl[0];
-#ifndef PSNODE_K4F_W_AHEAD
-#define PSNODE_K4F_W_AHEAD 1      // two-role chain: the layer's weight chunks are read from LDS BEFORE the exchange's barrier (they do not depend on it): behind it
-                                  // only the three tiles of the other waves are left to read -- half of the LDS traffic on the critical path
-#endif
-        constexpr bool WAH = ROLES && PSNODE_K4F_W_AHEAD;
-        f4 wah[WAH ? NWV : 1];
-        if constexpr (WAH) {
-#pragma unroll
-            for (int c = 1; c < NWV; ++c) wah[c] = wl[c * NWV * 64];
-        }
-        f4 accA = fm4(wq[0], d[0], f4{0.f, 0.f, 0.f, 0.f}), accB = fm4(wq[1], d[1], f4{0.f, 0.f, 0.f, 0.f});
-        accA = fm4(wq[2], d[2], accA); accB = fm4(wq[3], d[3], accB);
-        if constexpr (DEFER || DEFER8) { if (pacc) flush(*pacc); }
-        __builtin_amdgcn_sched_barrier(0);
-        lds_barrier();
-#ifndef PSNODE_K4F_TREAD_AHEAD
-#define PSNODE_K4F_TREAD_AHEAD 1     // <= 4 waves (one wave per SIMD, registers to spare): every LDS read of the layer -- the other waves' tiles, the
-                                     // weight chunks and the transposed tiles of the weight gradient -- is in flight before the first MFMA that
-                                     // needs one.  Left to the scheduler the transposed reads recycled two registers, each pair of MFMAs behind
-                                     // its own lgkmcnt(0) (found in the ISA)
-#endif
-        if constexpr (PREFETCH_ALL && PSNODE_K4F_TREAD_AHEAD) {
-            f4 vq[NWV], wqq[NWV], dTq[ROLES ? 1 : NWV];
-#pragma unroll
-            for (int c = 1; c < NWV; ++c) { vq[c] = getl(tile(p, (w + c) & (NWV - 1))); wqq[c] = WAH ? wah[WAH ? c : 0] : wl[c * NWV * 64]; }
-            if constexpr (!ROLES) {
-#pragma unroll
-                for (int c = 0; c < NWV; ++c) dTq[c] = get_row(tile(p, (w + c) & (NWV - 1)), roff);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int c = 1; c < NWV; ++c) {
-                accA = fm4(wqq[c][0], vq[c][0], accA); accB = fm4(wqq[c][1], vq[c][1], accB);
-                accA = fm4(wqq[c][2], vq[c][2], accA); accB = fm4(wqq[c][3], vq[c][3], accB);
-            }
-            if constexpr (ROLES) {
-                (void)dTq; (void)hT; (void)acc;       // the gradient waves' work
-            } else if constexpr (DEFER) {
-#pragma unroll
-                for (int c = 0; c < NWV; ++c) pendT[c] = dTq[c];
-                pend_h = hT;
-            } else {
-#pragma unroll
-                for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-                    for (int c = 0; c < NWV; ++c) acc[c] = fm4(dTq[c][kk], hT[kk], acc[c]);      // NWV independent chains
-            }
-            p ^= 1;
-            return accA + accB;
-        }
-#ifndef PSNODE_K4F_DP_GROUP
-#define PSNODE_K4F_DP_GROUP 7      // 8 waves, transposed layers: tiles and weight chunks of this many chunks read ahead of their MFMAs (0: as the forward layers).
-                                     // hidden-128 training step RK4, 0 / 3 / 4 / 7: ODE (K4f) 35.9 / 34.6 / 36.0 / 34.5 ms, DAE (K7f) 52.1 / 51.9 / 51.9 / 52.0 (profiles/r03y_dp_group_ab.txt)
-#endif
-        if constexpr (PSNODE_K4F_DP_GROUP > 0 && NWV >= 8) {
-            constexpr int PG = PSNODE_K4F_DP_GROUP > 0 ? PSNODE_K4F_DP_GROUP : 1;
-#pragma unroll
-            for (int c0 = 1; c0 < NWV; c0 += PG) {
-                f4 vg[PG], wg[PG];
-#pragma unroll
-                for (int q = 0; q < PG; ++q) if (c0 + q < NWV) { vg[q] = getl(tile(p, (w + c0 + q) & (NWV - 1))); wg[q] = wl[(c0 + q) * NWV * 64]; }
-#pragma unroll
-                for (int q = 0; q < PG; ++q) if (c0 + q < NWV) {
-                    accA = fm4(wg[q][0], vg[q][0], accA); accB = fm4(wg[q][1], vg[q][1], accB);
-                    accA = fm4(wg[q][2], vg[q][2], accA); accB = fm4(wg[q][3], vg[q][3], accB);
-                }
-                if constexpr (BOUND) __builtin_amdgcn_sched_barrier(0);
-            }
-        } else
-#pragma unroll
-        for (int c = 1; c < NWV; ++c) {
-            const f4 v = getl(tile(p, (w + c) & (NWV - 1)));
-            wq = wl[c * NWV * 64];
-            accA = fm4(wq[0], v[0], accA); accB = fm4(wq[1], v[1], accB);
-            accA = fm4(wq[2], v[2], accA); accB = fm4(wq[3], v[3], accB);
-            if constexpr (BOUND) { if (c % EVERY == EVERY - 1) __builtin_amdgcn_sched_barrier(0); }
-        }
-#ifndef PSNODE_K4F_DW_PAIR
-#define PSNODE_K4F_DW_PAIR 4     // 8 waves: the weight-gradient MFMAs of two chunks interleaved (two accumulator chains, both transposed tiles read first)
-#endif
-        {
-        if constexpr (PSNODE_K4F_DW_PAIR && NWV >= 8 && !REC) {      // (recompute instance at RK4: 48.2 -> 50.3 ms with it, profiles/r03y_dw_pair_ab.txt)
-            if constexpr (DEFER8) { pend_par = p; pend_h = hT; }      // (the tiles of this parity stay intact until the exchange after next)
-            else dw_groups(p, hT, acc);
-        } else {
-#pragma unroll
-        for (int c = 0; c < NWV; ++c) {
-            const f4 dT = get_row(tile(p, (w + c) & (NWV - 1)), roff);
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) acc[c] = fm4(dT[kk], hT[kk], acc[c]);
-            if constexpr (BOUND) { if (c % EVERY == EVERY - 1) __builtin_amdgcn_sched_barrier(0); }
-        }
-        }
-        }
-        p ^= 1;
-        return accA + accB;
-    };
-    // 8-byte all-reduce of rows r < 2 over the waves (fixed order)
-    auto allreduce2 = [&](const f2 part, const f2 init, f4 (*pacc)[NWV] = nullptr) -> f2 {
-        f2* xb2 = reinterpret_cast<f2*>(tile(p, 0));
-        xb2[w * 64 + l] = part;
-        if constexpr (DEFER || DEFER8) { if (pacc) flush(*pacc); }
-        lds_barrier();
-        f2 out = init;
-#pragma unroll
-        for (int c = 0; c < NWV; ++c) out += xb2[c * 64 + l];
-        p ^= 1;
-        return out;
-    };
-    // 16-byte form: the last stage's dL/dx rides with the step's dL/dz (one exchange less per step: a quarter of them at Euler)
-    auto allreduce4 = [&](const f4 part, f4 (*pacc)[NWV] = nullptr) -> f4 {
-        put(tile(p, w), part);
-        if constexpr (DEFER || DEFER8) { if (pacc) flush(*pacc); }
-        lds_barrier();
-        f4 out = f4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int c = 0; c < NWV; ++c) out += getl(tile(p, c));
-        p ^= 1;
-        return out;
-    };
-    // split-K over the waves' own units (4 MFMAs)
-    auto own4 = [&](const float (&wq)[4], const f4 h) -> f4 {
-        f4 accA = fm4(wq[0], h[0], f4{0.f, 0.f, 0.f, 0.f}), accB = fm4(wq[1], h[1], f4{0.f, 0.f, 0.f, 0.f});
-        accA = fm4(wq[2], h[2], accA); accB = fm4(wq[3], h[3], accB);
-        return accA + accB;
-    };
+    using Tune = K4fTune;
+#include "psnode_tile_bwd_chain.h"
+    constexpr bool RSM = ROLES && K4fTune::ROLES_SMALL;
 
     // addressing: sbase(uniform row base) + 32-bit per-lane BYTE offset (psnode_common.h: ldg / stg)
     const unsigned offH = 4u * ((unsigned)(b * H) + 16 * w + 4 * g);
@@ -651,10 +445,7 @@ __global__ __launch_bounds__(64 * NWV * (ROLES ? 2 : 1)) void ode_backward_fused
     };
     f4 sv1 = zero4, sv2 = zero4, sv3 = zero4;
     float svx[NX] = {};
-#ifndef PSNODE_K4F_SAVED_AHEAD_ROLES
-#define PSNODE_K4F_SAVED_AHEAD_ROLES 3     // two-role form (registers to spare on the chain): 3 = the rows are requested TWO stages ahead
-#endif
-    constexpr int SAHEAD = ROLES ? PSNODE_K4F_SAVED_AHEAD_ROLES : PSNODE_K4F_SAVED_AHEAD_DEFAULT;
+    constexpr int SAHEAD = ROLES ? PSNODE_K4F_SAVED_AHEAD_ROLES : PSNODE_K4F_SAVED_AHEAD;
     // SAHEAD == 3: two register sets; the rows of linear index idx live in set (idx parity) -- a compile-time index: `s & 1` when the
     // stage count is even, the parity of the step body (KP) at Euler, whose time loop is therefore written out twice per iteration.  (Moving
     // the second set up with register copies instead would wait for the younger request at the copy.)
@@ -742,9 +533,6 @@ __global__ __launch_bounds__(64 * NWV * (ROLES ? 2 : 1)) void ode_backward_fused
             t_hi = t_lo;
             t_lo = load_t(kp);
         };
-#ifndef PSNODE_K4F_NEXT_LATE
-#define PSNODE_K4F_NEXT_LATE 0
-#endif
         constexpr bool NEXT_LATE = !REC && NWV >= 8 && PSNODE_K4F_NEXT_LATE;
         if constexpr (!STREAM && !NEXT_LATE) prefetch_next();
         (void)cz; (void)x0;
@@ -763,12 +551,6 @@ __global__ __launch_bounds__(64 * NWV * (ROLES ? 2 : 1)) void ode_backward_fused
         for (int s = S - 1; s >= 0; --s) {
             f4 a1, a2, a3;
             if constexpr (!REC) {
-#ifndef PSNODE_K4F_SAVED_AHEAD
-#define PSNODE_K4F_SAVED_AHEAD 2      // 0: rows of a stage requested at its top; 1: a whole stage ahead; 2: late in the previous stage (in front of its last
-                                      // exchange).  vmcnt counts in order: every spilled-invariant reload behind an outstanding HBM request waits for it, so
-                                      // requesting EARLY is what exposed the latency at RK4 (43.8 / 39.2 / 37.9 ms per hidden-128 training step for 1 / 0 / 2;
-                                      // Euler, no spills: 9.3 / 10.5 / 9.4: profiles/r03t_ahead.txt)
-#endif
                 const long long idx = k * S + s;
                 if constexpr (SAHEAD) {
                     if constexpr (SAHEAD == 3) {      // two stages ahead: this stage's set is consumed and refilled with the rows of idx - 2
@@ -796,9 +578,6 @@ __global__ __launch_bounds__(64 * NWV * (ROLES ? 2 : 1)) void ode_backward_fused
                     for (int r = 0; r < NX; ++r) X[s][r] = x2on(r) ? svx[r] : 0.0f;
                 }
             } else if constexpr (STREAM) {
-#ifndef PSNODE_K4F_RING_LATE
-#define PSNODE_K4F_RING_LATE 1
-#endif
                 a1 = na1; a2 = na2; a3 = na3;
                 if constexpr (!PSNODE_K4F_RING_LATE) {
                     if (s > 0) {
@@ -863,7 +642,7 @@ __global__ __launch_bounds__(64 * NWV * (ROLES ? 2 : 1)) void ode_backward_fused
             }
             f2 gx;
             if (NZM > 0 && s == 0) {      // (compile-time once the stage loop is unrolled)
-                const f4 r4 = allreduce4(f4{ft[0], ft[1], gzp[0], gzp[1]}, &accW2);
+                const f4 r4 = allreduce4(f4{ft[0], ft[1], gzp[0], gzp[1]}, zero4, &accW2);
                 gx = f2{r4[0], r4[1]};
                 gzr = f2{r4[2], r4[3]};
             } else gx = allreduce2(f2{ft[0], ft[1]}, f2{0.f, 0.f}, &accW2);

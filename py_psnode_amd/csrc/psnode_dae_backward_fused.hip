@@ -16,15 +16,73 @@
 #include <string.h>
 #include <type_traits>
 
+#include "psnode_tile_bwd.h"
 #include "psnode_wide_pack.h"
+
+// ---- knobs (make EXTRA=-DPSNODE_K7F_...=v BUILD=... OUT=...); the first group is read by the shared code through K7fTune
+#ifndef PSNODE_K7F_BOUND
+#define PSNODE_K7F_BOUND 3      // as PSNODE_K4F_BOUND: 0 never, 1 always at 8 waves, 2 RK4 only, 3 RK4 + Midpoint
+#endif
+#ifndef PSNODE_K7F_EVERY
+#define PSNODE_K7F_EVERY 2      // 8 waves, RK4 / Midpoint: a sched_barrier behind every EVERY-th chunk of the layer loops (K4f: PSNODE_K4F_EVERY)
+#endif
+#ifndef PSNODE_K7F_TREAD_AHEAD
+#define PSNODE_K7F_TREAD_AHEAD 1     // <= 4 waves: every LDS read of the layer in flight before the first MFMA that needs one (K4f: PSNODE_K4F_TREAD_AHEAD)
+#endif
+#ifndef PSNODE_K7F_DEFER_DW
+#define PSNODE_K7F_DEFER_DW 1        // <= 4 waves: a layer's weight-gradient MFMAs run behind the NEXT exchange's LDS write (K4f: PSNODE_K4F_DEFER_DW)
+#endif
+#ifndef PSNODE_K7F_DEFER8
+#define PSNODE_K7F_DEFER8 1         // 8 waves: the same deferral without holding the transposed tiles: they are re-read from the previous exchange's parity
+#endif
+#ifndef PSNODE_K7F_DW_PAIR
+#define PSNODE_K7F_DW_PAIR 4     // 8 waves: the weight-gradient MFMAs of this many chunks interleaved (K4f: PSNODE_K4F_DW_PAIR)
+#endif
+#ifndef PSNODE_K7F_W_AHEAD
+#define PSNODE_K7F_W_AHEAD 1      // two-role chain: the layer's weight chunks are read from LDS BEFORE the exchange's barrier (they do not depend on it): behind it
+                                  // only the three tiles of the other waves are left to read -- half of the LDS traffic on the critical path
+#endif
+#ifndef PSNODE_K7F_DP_GROUP
+#define PSNODE_K7F_DP_GROUP 0      // 8 waves, transposed layers: tiles and weight chunks of this many chunks read ahead of their MFMAs (0: as the forward layers).
+                                     // hidden-128 training step RK4, 0 / 3 / 4 / 7: ODE (K4f) 35.9 / 34.6 / 36.0 / 34.5 ms, DAE (K7f) 52.1 / 51.9 / 51.9 / 52.0 (profiles/r03y_dp_group_ab.txt)
+#endif
+#ifndef PSNODE_K7F_ROLES_EARLY
+#define PSNODE_K7F_ROLES_EARLY 1     // chunks of a contraction issued in the interval its tiles are published in (K4f: PSNODE_K4F_ROLES_EARLY)
+#endif
+#ifndef PSNODE_K7F_ROLES_SMALL
+#define PSNODE_K7F_ROLES_SMALL 1  // the gradient waves also own dW4 / dW1 (s columns) / dAW4 (P3) / dAW1 (u columns): no in-wave transpose left on the chain
+#endif
+// ... and the ones only this file's step body and launcher read
+#ifndef PSNODE_K7F_ROLES
+#define PSNODE_K7F_ROLES 1      // <= 4 waves, saved activations: NWV gradient waves per tile own the four H->H weight gradients (K4f: PSNODE_K4F_ROLES)
+#endif
+#ifndef PSNODE_K7F_AE_GRADS
+#define PSNODE_K7F_AE_GRADS 1   // <= 4 waves, saved activations: the AE head's gradients are formed in the kernel (see AEW below)
+#endif
+#ifndef PSNODE_K7F_HEAD_AHEAD
+#define PSNODE_K7F_HEAD_AHEAD 1      // REC = false: the saved rows of the next grid point's head are requested late in the step's last stage (next to
+                                     // the next stage's rows) instead of at the top of the next step, where the head needs them at once
+#endif
+#ifndef PSNODE_K7F_INPUTS_AHEAD
+#define PSNODE_K7F_INPUTS_AHEAD 1    // <= 4 waves: the per-step inputs are requested one step ahead (see AHEAD below)
+#endif
 
 namespace psnode {
 namespace {
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef float f2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ f4 fm4(float a, float b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+// what the shared text (psnode_tile_bwd_chain.h) reads: everything in which K7f's tile machinery differs from K4f's
+struct K7fTune {
+    static constexpr int bound(const bool) { return PSNODE_K7F_BOUND; }
+    static constexpr int every(const bool) { return PSNODE_K7F_EVERY; }
+    static constexpr bool TREAD_AHEAD = PSNODE_K7F_TREAD_AHEAD, DEFER_DW = PSNODE_K7F_DEFER_DW, DEFER8 = PSNODE_K7F_DEFER8;
+    static constexpr int DW_PAIR = PSNODE_K7F_DW_PAIR;
+    static constexpr bool PAIR_REC = true;       // DEFER8 and the paired dW arm: recompute instances too
+    static constexpr bool W_AHEAD = PSNODE_K7F_W_AHEAD;
+    static constexpr int DP_GROUP = PSNODE_K7F_DP_GROUP;
+    static constexpr bool ROLES_SMALL = PSNODE_K7F_ROLES_SMALL;
+    // image `layer` of wT for mid_lds, in 32-bit arithmetic (K4f: 64-bit): either form moves the other kernel's register allocation at 8 waves
+    template <int NWV> static __device__ __forceinline__ const f4* image(const f4* wT, const int layer, const int w, const int l) { return wT + layer * NWV * NWV * 64 + w * 64 + l; }
+};
 
 struct FusedDaeDev {
     int method, xd, zd, vd, id, hreal, n_events, NP;
@@ -50,23 +108,8 @@ struct FusedDaeDev {
     const float *sact, *sxst, *saeact, *sevact, *sevi;
 };
 
-#ifndef PSNODE_K7F_EVERY
-#define PSNODE_K7F_EVERY 2      // 8 waves, RK4 / Midpoint: a sched_barrier behind every EVERY-th chunk of the layer loops (K4f: PSNODE_K4F_EVERY)
-#endif
-constexpr int FTILE = 64 * 4 + 4 * 8;     // padded 16x16 tile (floats): lane l's four rows 4g..4g+3 of column j at 4l + 8g
-
 __host__ __device__ constexpr bool aet_in_lds(int nwv) { return nwv <= 4; }
 
-#ifndef PSNODE_K7F_AE_GRADS
-#define PSNODE_K7F_AE_GRADS 1
-#endif
-#define PSNODE_K7F_AE_GRADS_DEFAULT PSNODE_K7F_AE_GRADS
-#ifndef PSNODE_K7F_ROLES
-#define PSNODE_K7F_ROLES 1      // <= 4 waves, saved activations: NWV gradient waves per tile own the four H->H weight gradients (K4f: PSNODE_K4F_ROLES)
-#endif
-#ifndef PSNODE_K7F_ROLES_EARLY
-#define PSNODE_K7F_ROLES_EARLY 1
-#endif
 // Two-role form (round 4; psnode_backward_fused.hip: fused_gradient_wave): waves NWV..2NWV-1 of the workgroup follow the chain's barrier
 // sequence -- per step: the head at grid point k+1 (3 exchanges), 3 per stage, the step's external-input all-reduce, the event's head
 // (3) -- and contract the delta tiles the chain's all-gathers publish with their own 16 units of the SAVED activations (DE stage rows,
@@ -81,9 +124,6 @@ template <int NWV> __device__ __forceinline__ float* k7f_roles_xbox(float* xb, c
 template <int NWV> __device__ __forceinline__ float* k7f_roles_d1_tile(float* xb, const int wv) { return xb + (size_t)(11 * NWV + wv) * FTILE; }
 template <int NWV> __device__ __forceinline__ float* k7f_roles_g_tile(float* xb) { return xb + (size_t)(12 * NWV) * FTILE; }
 template <int NWV> __device__ __forceinline__ float* k7f_roles_u_tile(float* xb) { return xb + (size_t)(12 * NWV + 1) * FTILE; }
-#ifndef PSNODE_K7F_ROLES_SMALL
-#define PSNODE_K7F_ROLES_SMALL 1  // the gradient waves also own dW4 / dW1 (s columns) / dAW4 (P3) / dAW1 (u columns): no in-wave transpose left on the chain
-#endif
 
 template <int METHOD, int NZM, int NWV>
 __device__ __forceinline__ void dae_fused_gradient_wave(const FusedDaeDev& a, float* __restrict__ xb, const int l, const int wg) {
@@ -318,11 +358,6 @@ __global__ __launch_bounds__(64 * NWV * (ROLES ? 2 : 1)) void dae_backward_fused
     constexpr bool STREAM = NWV >= 8 && REC; // DE forward / transposed images swapped in LDS per phase; activations through the ring
     constexpr bool AEG = NWV >= 8;           // AE images read from L2
     constexpr bool AET_LDS = aet_in_lds(NWV);
-#ifndef PSNODE_K7F_BOUND
-#define PSNODE_K7F_BOUND 3      // as PSNODE_K4F_BOUND: 0 never, 1 always at 8 waves, 2 RK4 only, 3 RK4 + Midpoint
-#endif
-    constexpr bool BOUND = NWV >= 8 && (PSNODE_K7F_BOUND == 1 || (PSNODE_K7F_BOUND == 2 && S >= 4) || (PSNODE_K7F_BOUND == 3 && S >= 2));
-    constexpr int EVERY = PSNODE_K7F_EVERY;
     constexpr int TSZ = 2 * NWV * NWV * 64;  // f4 per pair of H->H images
     extern __shared__ __attribute__((aligned(16))) float lds[];
     f4* wT = reinterpret_cast<f4*>(lds);                                  // DE: [layer 0: W2 | 1: W3][chunk][wave][lane]; AET_LDS: the AE's transposes behind it
@@ -338,7 +373,7 @@ __global__ __launch_bounds__(64 * NWV * (ROLES ? 2 : 1)) void dae_backward_fused
         }
     }
     const int g = l >> 4, j = l & 15, i = j;
-    float* scr = xb + 2 * NWV * FTILE + w * FTILE;                       // this wave's private transpose tile
+    float* scr = xb + 2 * NWV * FTILE + w * FTILE;           // this wave's private transpose tile
     const long long b0 = (long long)blockIdx.x * TBM;
     const bool valid = b0 + j < a.B;
     const long long b = valid ? b0 + j : a.B - 1;
@@ -371,23 +406,7 @@ __global__ __launch_bounds__(64 * NWV * (ROLES ? 2 : 1)) void dae_backward_fused
         ab2[r] = pwa[(RA::B2 + r) * 64]; ab3[r] = pwa[(RA::B3 + r) * 64];
         ab4[r] = AEG ? 0.0f : pwa[(RA::B4 + r) * 64];
     }
-    // LDS-DMA of one DE layer's image (0: W2, 1: W3) into its region (K4f: psnode_backward_fused.hip:dma_layer)
-    const unsigned wT_lds = __builtin_amdgcn_readfirstlane((unsigned)reinterpret_cast<uintptr_t>(wT));
-    const unsigned lane16 = 16u * (unsigned)l;
-    auto dma_layer = [&](const f4* __restrict__ img, const int layer) {
-#pragma unroll
-        for (int c = 0; c < NWV; ++c) {
-            const int slot = (layer * NWV + c) * NWV + w;
-            const uintptr_t sb = reinterpret_cast<uintptr_t>(img + (size_t)slot * 64);
-            const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)sb), hi = __builtin_amdgcn_readfirstlane((unsigned)(sb >> 32));
-            const unsigned long long base = ((unsigned long long)hi << 32) | lo;
-            const unsigned dst = __builtin_amdgcn_readfirstlane(wT_lds + (unsigned)slot * 1024u);
-            unsigned keep;
-            asm volatile(PSNODE_LDS_DMA_ASM
-                         : "=&s"(keep) : "v"(lane16), "s"(dst), "s"(base) : "memory");
-        }
-    };
-    auto dma_wait = [&]() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); };
+#include "psnode_tile_bwd_dma.h"
     if constexpr (STREAM) {
         dma_layer(pack_f, 0);
         dma_layer(pack_f, 1);
@@ -470,249 +489,11 @@ __global__ __launch_bounds__(64 * NWV * (ROLES ? 2 : 1)) void dae_backward_fused
     const int srow = (inx_ & rowx_) | (~inx_ & ((ins_ & rowe_) | ~ins_));          // -1 outside of (x | ext)
     // ... and the same for the AE head's first-layer input behind all_initial, u = (x dims | z | v)
     const int arow = (inx_ & rowx_) | (~inx_ & ((ina_ & rowe_) | ~ina_));
-
-    // ---- LDS tiles
-    const int toff = 4 * l + 8 * g;                                   // own slot of a tile
-    const int roff = 72 * (i >> 2) + 4 * g + (i & 3);                 // row i of a tile, columns g, g+4, g+8, g+12
-    auto tile = [&](const int par, const int wv) -> float* { return xb + (par * NWV + wv) * FTILE; };
-    auto put = [&](float* t_, const f4 v) { *reinterpret_cast<f4*>(t_ + toff) = v; };
-    auto getl = [&](const float* t_) -> f4 { return *reinterpret_cast<const f4*>(t_ + toff); };
-    auto get_row = [&](const float* t_, const int ro) -> f4 { const float* s_ = t_ + ro; return f4{s_[0], s_[16], s_[32], s_[48]}; };
-    auto transpose = [&](const f4 v) -> f4 { put(scr, v); return get_row(scr, roff); };   // own D tile -> operand layout (trajectory g + 4kk)
-
-    int p = 0;
-    constexpr bool PREFETCH_ALL = NWV <= 4;
+    using Tune = K7fTune;
+#include "psnode_tile_bwd_chain.h"
     const f4 zero4 = f4{0.f, 0.f, 0.f, 0.f};
-    // forward H->H layer, weights in registers (K1's `mid`); returns the pre-activation
-    auto mid = [&](const float (&wm)[4 * NWV], const f4 bias, const f4 h) -> f4 {
-        put(tile(p, w), h);
-        f4 accA = bias, accB = zero4;
-        accA = fm4(wm[0], h[0], accA); accB = fm4(wm[1], h[1], accB);
-        accA = fm4(wm[2], h[2], accA); accB = fm4(wm[3], h[3], accB);
-        __builtin_amdgcn_sched_barrier(0);
-        lds_barrier();
-        f4 vq[NWV];
-        if constexpr (PREFETCH_ALL) {
-#pragma unroll
-            for (int c = 1; c < NWV; ++c) vq[c] = getl(tile(p, (w + c) & (NWV - 1)));
-            __builtin_amdgcn_sched_barrier(0);
-        }
-#pragma unroll
-        for (int c = 1; c < NWV; ++c) {
-            const f4 v = PREFETCH_ALL ? vq[c] : getl(tile(p, (w + c) & (NWV - 1)));
-            accA = fm4(wm[4 * c + 0], v[0], accA); accB = fm4(wm[4 * c + 1], v[1], accB);
-            accA = fm4(wm[4 * c + 2], v[2], accA); accB = fm4(wm[4 * c + 3], v[3], accB);
-        }
-        p ^= 1;
-        return accA + accB;
-    };
-    // H->H layer with the image at f4 offset `base` of wT (forward image: pre-activation from `bias`; transposed image: sum_k W[k][own] d[k])
-    auto mid_lds = [&](const int base, const f4 bias, const f4 h) -> f4 {
-        put(tile(p, w), h);
-        const f4* wl = wT + base + w * 64 + l;
-        f4 wq = wl[0];
-        f4 accA = bias, accB = zero4;
-        accA = fm4(wq[0], h[0], accA); accB = fm4(wq[1], h[1], accB);
-        accA = fm4(wq[2], h[2], accA); accB = fm4(wq[3], h[3], accB);
-        __builtin_amdgcn_sched_barrier(0);
-        lds_barrier();
-#pragma unroll
-        for (int c = 1; c < NWV; ++c) {
-            const f4 v = getl(tile(p, (w + c) & (NWV - 1)));
-            wq = wl[c * NWV * 64];
-            accA = fm4(wq[0], v[0], accA); accB = fm4(wq[1], v[1], accB);
-            accA = fm4(wq[2], v[2], accA); accB = fm4(wq[3], v[3], accB);
-            if constexpr (BOUND) { if (c % EVERY == EVERY - 1) __builtin_amdgcn_sched_barrier(0); }
-        }
-        p ^= 1;
-        return accA + accB;
-    };
-    // the same with the image read from a packed tensor in global memory (8 waves: the AE's images; the LDS holds the DE's): all chunks
-    // are requested before the exchange so that their latency overlaps it
-    auto mid_g = [&](const f4* __restrict__ img, const f4 bias, const f4 h) -> f4 {
-        const f4* wlo = img + w * 64 + l;
-        asm volatile("" : "+v"(wlo));      // opaque: the loads are loop-invariant and would be hoisted out of the time loop (and spilled)
-        const gptr<const f4> wl = (gptr<const f4>)wlo;
-        f4 wq[NWV];
-#pragma unroll
-        for (int c = 0; c < NWV; ++c) wq[c] = wl[c * NWV * 64];
-        put(tile(p, w), h);
-        f4 accA = bias, accB = zero4;
-        accA = fm4(wq[0][0], h[0], accA); accB = fm4(wq[0][1], h[1], accB);
-        accA = fm4(wq[0][2], h[2], accA); accB = fm4(wq[0][3], h[3], accB);
-        lds_barrier();
-#pragma unroll
-        for (int c = 1; c < NWV; ++c) {
-            const f4 v = getl(tile(p, (w + c) & (NWV - 1)));
-            accA = fm4(wq[c][0], v[0], accA); accB = fm4(wq[c][1], v[1], accB);
-            accA = fm4(wq[c][2], v[2], accA); accB = fm4(wq[c][3], v[3], accB);
-        }
-        p ^= 1;
-        return accA + accB;
-    };
-    // transposed DE layer (image in LDS) + the weight gradient of that layer from the very tiles the all-gather published:
-    // acc[c] += delta(block (w+c) % NWV)^T (x) hT, hT = this wave's own input activations in operand layout (K4f: midT)
-#ifndef PSNODE_K7F_TREAD_AHEAD
-#define PSNODE_K7F_TREAD_AHEAD 1     // <= 4 waves: every LDS read of the layer in flight before the first MFMA that needs one (K4f: PSNODE_K4F_TREAD_AHEAD)
-#endif
-#ifndef PSNODE_K7F_DEFER_DW
-#define PSNODE_K7F_DEFER_DW 1        // <= 4 waves: a layer's weight-gradient MFMAs run behind the NEXT exchange's LDS write (K4f: PSNODE_K4F_DEFER_DW)
-#endif
-    constexpr bool RSM = ROLES && PSNODE_K7F_ROLES_SMALL;
-    constexpr bool DEFER = PREFETCH_ALL && PSNODE_K7F_TREAD_AHEAD && PSNODE_K7F_DEFER_DW && !ROLES;
-    f4 pendT[DEFER ? NWV : 1], pend_h = zero4;
-#ifndef PSNODE_K7F_DEFER8
-#define PSNODE_K7F_DEFER8 1         // 8 waves: the same deferral without holding the transposed tiles: they are re-read from the previous exchange's parity
-#endif
-#ifndef PSNODE_K7F_DW_PAIR
-#define PSNODE_K7F_DW_PAIR 4
-#endif
-    constexpr bool DEFER8 = NWV >= 8 && PSNODE_K7F_DEFER8 && PSNODE_K7F_DW_PAIR;
-    int pend_par = 0;
-    auto dw_groups = [&](const int par, const f4 hT, f4 (&acc)[NWV]) {
-        constexpr int DG = PSNODE_K7F_DW_PAIR <= 1 ? 2 : PSNODE_K7F_DW_PAIR;      // chunks per group
-#pragma unroll
-        for (int c = 0; c < NWV; c += DG) {
-            f4 dTg[DG];
-#pragma unroll
-            for (int q = 0; q < DG; ++q) dTg[q] = get_row(tile(par, (w + c + q) & (NWV - 1)), roff);
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-                for (int q = 0; q < DG; ++q) acc[c + q] = fm4(dTg[q][kk], hT[kk], acc[c + q]);
-            if constexpr (BOUND) __builtin_amdgcn_sched_barrier(0);
-        }
-    };
-    auto flush = [&](f4 (&pacc)[NWV]) {
-        if constexpr (DEFER8) dw_groups(pend_par, pend_h, pacc);
-        if constexpr (DEFER) {
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-                for (int c = 0; c < NWV; ++c) pacc[c] = fm4(pendT[c][kk], pend_h[kk], pacc[c]);
-        }
-    };
-    auto midT = [&](const int layer, const f4 d, const f4 hT, f4 (&acc)[NWV], f4 (*pacc)[NWV] = nullptr) -> f4 {
-        put(tile(p, w), d);
-        const f4* wl = wT + ((size_t)layer * NWV * NWV + w) * 64 + l;
-        f4 wq = wl[0];
-#ifndef PSNODE_K7F_W_AHEAD
-#define PSNODE_K7F_W_AHEAD 1      // two-role chain: the layer's weight chunks are read from LDS BEFORE the exchange's barrier (they do not depend on it): behind it
-                                  // only the three tiles of the other waves are left to read -- half of the LDS traffic on the critical path
-#endif
-        constexpr bool WAH = ROLES && PSNODE_K7F_W_AHEAD;
-        f4 wah[WAH ? NWV : 1];
-        if constexpr (WAH) {
-#pragma unroll
-            for (int c = 1; c < NWV; ++c) wah[c] = wl[c * NWV * 64];
-        }
-        f4 accA = fm4(wq[0], d[0], zero4), accB = fm4(wq[1], d[1], zero4);
-        accA = fm4(wq[2], d[2], accA); accB = fm4(wq[3], d[3], accB);
-        if constexpr (DEFER || DEFER8) { if (pacc) flush(*pacc); }
-        __builtin_amdgcn_sched_barrier(0);
-        lds_barrier();
-        if constexpr (PREFETCH_ALL && PSNODE_K7F_TREAD_AHEAD) {
-            f4 vq[NWV], wqq[NWV], dTq[ROLES ? 1 : NWV];
-#pragma unroll
-            for (int c = 1; c < NWV; ++c) { vq[c] = getl(tile(p, (w + c) & (NWV - 1))); wqq[c] = WAH ? wah[WAH ? c : 0] : wl[c * NWV * 64]; }
-            if constexpr (!ROLES) {
-#pragma unroll
-                for (int c = 0; c < NWV; ++c) dTq[c] = get_row(tile(p, (w + c) & (NWV - 1)), roff);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int c = 1; c < NWV; ++c) {
-                accA = fm4(wqq[c][0], vq[c][0], accA); accB = fm4(wqq[c][1], vq[c][1], accB);
-                accA = fm4(wqq[c][2], vq[c][2], accA); accB = fm4(wqq[c][3], vq[c][3], accB);
-            }
-            if constexpr (ROLES) {
-                (void)dTq; (void)hT; (void)acc;       // the gradient waves' work
-            } else if constexpr (DEFER) {
-#pragma unroll
-                for (int c = 0; c < NWV; ++c) pendT[c] = dTq[c];
-                pend_h = hT;
-            } else {
-#pragma unroll
-                for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-                    for (int c = 0; c < NWV; ++c) acc[c] = fm4(dTq[c][kk], hT[kk], acc[c]);      // NWV independent chains
-            }
-            p ^= 1;
-            return accA + accB;
-        }
-#ifndef PSNODE_K7F_DP_GROUP
-#define PSNODE_K7F_DP_GROUP 0      // 8 waves, transposed layers: tiles and weight chunks of this many chunks read ahead of their MFMAs (0: as the forward layers).
-                                     // hidden-128 training step RK4, 0 / 3 / 4 / 7: ODE (K4f) 35.9 / 34.6 / 36.0 / 34.5 ms, DAE (K7f) 52.1 / 51.9 / 51.9 / 52.0 (profiles/r03y_dp_group_ab.txt)
-#endif
-        if constexpr (PSNODE_K7F_DP_GROUP > 0 && NWV >= 8) {
-            constexpr int PG = PSNODE_K7F_DP_GROUP > 0 ? PSNODE_K7F_DP_GROUP : 1;
-#pragma unroll
-            for (int c0 = 1; c0 < NWV; c0 += PG) {
-                f4 vg[PG], wg[PG];
-#pragma unroll
-                for (int q = 0; q < PG; ++q) if (c0 + q < NWV) { vg[q] = getl(tile(p, (w + c0 + q) & (NWV - 1))); wg[q] = wl[(c0 + q) * NWV * 64]; }
-#pragma unroll
-                for (int q = 0; q < PG; ++q) if (c0 + q < NWV) {
-                    accA = fm4(wg[q][0], vg[q][0], accA); accB = fm4(wg[q][1], vg[q][1], accB);
-                    accA = fm4(wg[q][2], vg[q][2], accA); accB = fm4(wg[q][3], vg[q][3], accB);
-                }
-                if constexpr (BOUND) __builtin_amdgcn_sched_barrier(0);
-            }
-        } else
-#pragma unroll
-        for (int c = 1; c < NWV; ++c) {
-            const f4 v = getl(tile(p, (w + c) & (NWV - 1)));
-            wq = wl[c * NWV * 64];
-            accA = fm4(wq[0], v[0], accA); accB = fm4(wq[1], v[1], accB);
-            accA = fm4(wq[2], v[2], accA); accB = fm4(wq[3], v[3], accB);
-            if constexpr (BOUND) { if (c % EVERY == EVERY - 1) __builtin_amdgcn_sched_barrier(0); }
-        }
-#ifndef PSNODE_K7F_DW_PAIR
-#define PSNODE_K7F_DW_PAIR 4     // 8 waves: the weight-gradient MFMAs of two chunks interleaved (K4f: PSNODE_K4F_DW_PAIR)
-#endif
-        if constexpr (PSNODE_K7F_DW_PAIR && NWV >= 8) {
-            if constexpr (DEFER8) { pend_par = p; pend_h = hT; }      // (the tiles of this parity stay intact until the exchange after next)
-            else dw_groups(p, hT, acc);
-        } else {
-#pragma unroll
-        for (int c = 0; c < NWV; ++c) {
-            const f4 dT = get_row(tile(p, (w + c) & (NWV - 1)), roff);
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) acc[c] = fm4(dT[kk], hT[kk], acc[c]);
-            if constexpr (BOUND) { if (c % EVERY == EVERY - 1) __builtin_amdgcn_sched_barrier(0); }
-        }
-        }
-        p ^= 1;
-        return accA + accB;
-    };
-    // split-K over the waves' own units (4 MFMAs)
-    auto own4 = [&](const float (&wq)[4], const f4 h) -> f4 {
-        f4 accA = fm4(wq[0], h[0], zero4), accB = fm4(wq[1], h[1], zero4);
-        accA = fm4(wq[2], h[2], accA); accB = fm4(wq[3], h[3], accB);
-        return accA + accB;
-    };
-    // all-reduce of the output rows over the waves (fixed order): 2 rows (x-layout) or 4 rows (slot layout)
-    auto allreduce2 = [&](const f2 part, const f2 init, f4 (*pacc)[NWV] = nullptr) -> f2 {
-        f2* xb2 = reinterpret_cast<f2*>(tile(p, 0));
-        xb2[w * 64 + l] = part;
-        if constexpr (DEFER || DEFER8) { if (pacc) flush(*pacc); }
-        lds_barrier();
-        f2 out = init;
-#pragma unroll
-        for (int c = 0; c < NWV; ++c) out += xb2[c * 64 + l];
-        p ^= 1;
-        return out;
-    };
-    auto allreduce4 = [&](const f4 part, const f4 init, f4 (*pacc)[NWV] = nullptr) -> f4 {
-        put(tile(p, w), part);
-        if constexpr (DEFER || DEFER8) { if (pacc) flush(*pacc); }
-        lds_barrier();
-        f4 out = init;
-#pragma unroll
-        for (int c = 0; c < NWV; ++c) out += getl(tile(p, c));
-        p ^= 1;
-        return out;
-    };
+
+    constexpr bool RSM = ROLES && K7fTune::ROLES_SMALL;
 
     // per-lane BYTE offsets next to a scalar row base (psnode_common.h: sbase / ldg / stg)
     const unsigned offH = 4u * ((unsigned)(b * H) + 16 * w + 4 * g);      // rows of H floats: this lane's 4 units of its trajectory
@@ -764,9 +545,6 @@ __global__ __launch_bounds__(64 * NWV * (ROLES ? 2 : 1)) void dae_backward_fused
             a3 = elu_quad(mid(aw3r, ab3, a2));
         }
     };
-#ifndef PSNODE_K7F_AE_GRADS
-#define PSNODE_K7F_AE_GRADS 1
-#endif
     // Round 4, <= 4 waves (hidden <= 64: 512 registers per lane, the AE's transposed images already in LDS): everything that rounds 2-3
     // contracted over the head's STORED rows -- K7h, one more launch, 6 x [T,B,H] rows written here and read back there, ~1.6 ms + ~0.8 ms
     // of host glue per 4096 x 1000 batch -- is formed in this kernel, by the means the DE's gradients are: the transposed layers run
@@ -825,8 +603,8 @@ __global__ __launch_bounds__(64 * NWV * (ROLES ? 2 : 1)) void dae_backward_fused
         }
         f4 d2, d1;
         if constexpr (AET_LDS) {
-            d2 = mid_lds(TSZ + NWV * NWV * 64, zero4, d3) * elu_grad_quad(a2);
-            d1 = mid_lds(TSZ, zero4, d2) * elu_grad_quad(a1);
+            d2 = mid_lds(3, zero4, d3) * elu_grad_quad(a2);
+            d1 = mid_lds(2, zero4, d2) * elu_grad_quad(a1);
         } else {
             d2 = mid_g(pack_ta + NWV * NWV * 64, zero4, d3) * elu_grad_quad(a2);
             d1 = mid_g(pack_ta, zero4, d2) * elu_grad_quad(a1);
@@ -905,10 +683,6 @@ __global__ __launch_bounds__(64 * NWV * (ROLES ? 2 : 1)) void dae_backward_fused
     };
     f4 sv1 = zero4, sv2 = zero4, sv3 = zero4;
     float svx[NX] = {};
-#ifndef PSNODE_K7F_HEAD_AHEAD
-#define PSNODE_K7F_HEAD_AHEAD 1      // REC = false: the saved rows of the next grid point's head are requested late in the step's last stage (next to
-                                     // the next stage's rows) instead of at the top of the next step, where the head needs them at once
-#endif
     // (<= 4 waves only: hidden-64 training step 20.9 -> 20.6 ms; at 8 waves the twelve registers cost more in spills than the latency they
     //  hide -- RK4 49.9 -> 56.3 ms, profiles/r03y_head_ahead_ab.txt)
     constexpr bool HEAD_AHEAD = !REC && NWV <= 4 && PSNODE_K7F_HEAD_AHEAD && !ROLES;
@@ -923,9 +697,6 @@ __global__ __launch_bounds__(64 * NWV * (ROLES ? 2 : 1)) void dae_backward_fused
         const f4* m4 = reinterpret_cast<const f4*>(k7f_roles_mailbox<NWV>(xb, kind, w)) + l;
         q1 = m4[0]; q2 = m4[64]; q3 = m4[128];
     };
-#ifndef PSNODE_K7F_INPUTS_AHEAD
-#define PSNODE_K7F_INPUTS_AHEAD 1
-#endif
     // Round 4, <= 4 waves: the per-step inputs -- event index, dL/dis and dL/dxs rows, the z | v | i rows, the clock, (recompute form) the
     // state row -- are requested one step AHEAD, in the middle of the previous step, and stay raw until the step consumes them.  Rounds
     // 2-3 loaded each of them where it was used: six `global_load ..; s_waitcnt vmcnt(0)` round trips per step, each of which also waited
@@ -1132,7 +903,7 @@ __global__ __launch_bounds__(64 * NWV * (ROLES ? 2 : 1)) void dae_backward_fused
             if constexpr (STREAM) {
                 a2 = elu_quad(mid_lds(0, b2, a1));
                 if (s == S - 1) dma_layer(pack_t, 0);      // W2's region is free until phase B's SECOND transposed layer
-                a3 = elu_quad(mid_lds(NWV * NWV * 64, b3, a2));
+                a3 = elu_quad(mid_lds(1, b3, a2));
                 if (s == S - 1) dma_layer(pack_t, 1);
                 if (s < S - 1) {     // park the stage's activations in the ring (each lane re-reads exactly what it wrote)
                     const size_t rb = (size_t)(3 * s) * nrow * H;
@@ -1477,7 +1248,7 @@ int k7f_npa(int nw, bool saved, int hr, int xd, int nzv, int ne) {
 template <int METHOD, int NWV>
 hipError_t launch_k7f(const FusedDaeDev& a, int NZM, int NZA, const float* pde, const float* pae, const f4* pt, const f4* pf, const f4* pta,
                       const f4* pfa, int NA, hipStream_t s) {
-    constexpr bool RL = PSNODE_K7F_ROLES && PSNODE_K7F_AE_GRADS_DEFAULT && NWV <= 4;
+    constexpr bool RL = PSNODE_K7F_ROLES && PSNODE_K7F_AE_GRADS && NWV <= 4;
     const bool roles = RL && a.sact != nullptr;
     const dim3 grid((unsigned)((a.B + TBM - 1) / TBM)), block(64 * NWV * (roles ? 2 : 1));
     const size_t lds = k7f_lds_bytes(NWV, roles);

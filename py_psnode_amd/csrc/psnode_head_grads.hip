@@ -12,14 +12,11 @@
 // order by reduce_partials.  No weights are resident: ~110 registers, the loads of the next row are in flight during the MFMAs of this one.
 #include <string.h>
 
+#include "psnode_tile_bwd.h"
 #include "psnode_wide_pack.h"
 
 namespace psnode {
 namespace {
-
-typedef float f4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ f4 hm4(float a, float b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 
 struct HeadDev {
     long long R, B;
@@ -45,8 +42,6 @@ __global__ void sum_splits_kernel(const float* __restrict__ part, float* __restr
     out[i] = acc;
 }
 
-constexpr int HTILE = 64 * 4 + 4 * 8;     // padded 16x16 tile (K4f: FTILE)
-
 template <int NWV>
 __global__ __launch_bounds__(64 * NWV) void head_grads_kernel(const HeadDev a) {
     constexpr int H = 16 * NWV;
@@ -55,8 +50,8 @@ __global__ __launch_bounds__(64 * NWV) void head_grads_kernel(const HeadDev a) {
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int g = l >> 4, j = l & 15, i = j;
     // tiles: [parity][0: delta2 | 1: delta3 | 2: gza partials][wave], then one private transpose tile per wave
-    auto tile = [&](const int par, const int which, const int wv) -> float* { return lds + ((par * 3 + which) * NWV + wv) * HTILE; };
-    float* scr = lds + 6 * NWV * HTILE + w * HTILE;
+    auto tile = [&](const int par, const int which, const int wv) -> float* { return lds + ((par * 3 + which) * NWV + wv) * FTILE; };
+    float* scr = lds + 6 * NWV * FTILE + w * FTILE;
     const long long b0 = (long long)blockIdx.x * TBM;
     const bool valid = b0 + j < a.B;
     const long long b = valid ? b0 + j : a.B - 1;
@@ -113,8 +108,8 @@ __global__ __launch_bounds__(64 * NWV) void head_grads_kernel(const HeadDev a) {
         put(tile(p, 0, w), q.d2);
         put(tile(p, 1, w), q.d3);
         if (want_gza) {
-            f4 pa = hm4(aeT[0], q.d1[0], zero4), pb = hm4(aeT[1], q.d1[1], zero4);
-            pa = hm4(aeT[2], q.d1[2], pa); pb = hm4(aeT[3], q.d1[3], pb);
+            f4 pa = fm4(aeT[0], q.d1[0], zero4), pb = fm4(aeT[1], q.d1[1], zero4);
+            pa = fm4(aeT[2], q.d1[2], pa); pb = fm4(aeT[3], q.d1[3], pb);
             put(tile(p, 2, w), pa + pb);
         }
         S1 += q.d1; S2 += q.d2; S3 += q.d3; SG += q.gs;
@@ -122,11 +117,11 @@ __global__ __launch_bounds__(64 * NWV) void head_grads_kernel(const HeadDev a) {
             const f4 gT = transpose(q.gs);
             const f4 h3T = transpose(q.h3);
 #pragma unroll
-            for (int kk = 0; kk < 4; ++kk) accP3 = hm4(gT[kk], h3T[kk], accP3);
+            for (int kk = 0; kk < 4; ++kk) accP3 = fm4(gT[kk], h3T[kk], accP3);
             const f4 dT = transpose(q.d1);
             const f4 uT = transpose(q.u4);
 #pragma unroll
-            for (int kk = 0; kk < 4; ++kk) accP0 = hm4(dT[kk], uT[kk], accP0);
+            for (int kk = 0; kk < 4; ++kk) accP0 = fm4(dT[kk], uT[kk], accP0);
         }
         const f4 h1T = transpose(q.h1);
         const f4 h2T = transpose(q.h2);
@@ -150,8 +145,8 @@ __global__ __launch_bounds__(64 * NWV) void head_grads_kernel(const HeadDev a) {
                 for (int kk = 0; kk < 4; ++kk)
 #pragma unroll
                     for (int q = 0; q < G; ++q) {      // 2 G independent accumulator chains
-                        acc2[c0 + q] = hm4(d2T[q][kk], h1T[kk], acc2[c0 + q]);
-                        acc3[c0 + q] = hm4(d3T[q][kk], h2T[kk], acc3[c0 + q]);
+                        acc2[c0 + q] = fm4(d2T[q][kk], h1T[kk], acc2[c0 + q]);
+                        acc3[c0 + q] = fm4(d3T[q][kk], h2T[kk], acc3[c0 + q]);
                     }
             }
         } else {
@@ -161,7 +156,7 @@ __global__ __launch_bounds__(64 * NWV) void head_grads_kernel(const HeadDev a) {
             const f4 d2T = get_row(tile(p, 0, ws));
             const f4 d3T = get_row(tile(p, 1, ws));
 #pragma unroll
-            for (int kk = 0; kk < 4; ++kk) { acc2[c] = hm4(d2T[kk], h1T[kk], acc2[c]); acc3[c] = hm4(d3T[kk], h2T[kk], acc3[c]); }
+            for (int kk = 0; kk < 4; ++kk) { acc2[c] = fm4(d2T[kk], h1T[kk], acc2[c]); acc3[c] = fm4(d3T[kk], h2T[kk], acc3[c]); }
         }
         }
         if (want_gza) {
@@ -265,7 +260,7 @@ int32_t psnode_dae_head_grads_f32(const psnode_dae_head_grads_args_f32* p, void*
     float* sa1_part = a.wpart + (((size_t)rs * nwg * a.NP + 63) / 64) * 64;
     a.sa1 = rs > 1 ? sa1_part : p->sa1;
     const dim3 grid((unsigned)nwg, (unsigned)rs), block(64 * nw);
-    const size_t lds = (size_t)7 * nw * HTILE * sizeof(float);
+    const size_t lds = (size_t)7 * nw * FTILE * sizeof(float);
     hipError_t e = hipSuccess;
     switch (nw) {
         case 2: hipLaunchKernelGGL(head_grads_kernel<2>, grid, block, lds, s, a); break;
