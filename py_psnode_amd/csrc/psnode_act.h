@@ -5,14 +5,21 @@
 // psnode_generic_bwd_act.hip) take an ActDev per MLP as a kernel argument and switch on its kind, which is uniform over the launch
 // (scalar branches, no divergence).
 //
-// Every listed activation has a derivative that is a function of the layer OUTPUT h (K5 rebuilds and keeps layer outputs, not
+// Every listed activation but one has a derivative that is a function of the layer OUTPUT h (K5 rebuilds and keeps layer outputs, not
 // pre-activations):
 //   ELU(alpha)              x > 0 ? x : alpha (e^x - 1)                          h > 0 ? 1 : h + alpha
 //   Tanh                    tanh x                                               1 - h^2
 //   Sigmoid                 1 / (1 + e^-x)                                       h (1 - h)
 //   ReLU                    max(x, 0)                                            h > 0 ? 1 : 0        (torch's rule at 0)
 //   LeakyReLU(s), s >= 0    x > 0 ? x : s x                                      h > 0 ? 1 : s
-//   Softplus(beta, thr)     beta x > thr ? x : log(1 + e^(beta x)) / beta        beta h > thr ? 1 : 1 - e^(-beta h)
+//   Softplus(beta, thr)     beta x > thr ? x : log(1 + e^(beta x)) / beta        beta h > thr ? 1 : 1 - e^(-beta h)     (thr >= 24 ln 2 only)
+// Softplus is the exception.  Torch decides its derivative on the INPUT (beta x > thr ? 1 : sigmoid(beta x)), and the forward jumps at
+// beta x = thr from log1p(e^thr) down to thr, so h is not monotonic in x: for beta x in (log(e^thr - 1), thr] the rule on h above returns 1
+// where torch returns sigmoid(beta x), an error of up to e^-thr (0.37 at thr = 1; every x <= 0 at thr <= 0).  That is below fp32
+// resolution (2^-24) only from thr >= 24 ln 2 = 16.64 (kSoftplusCut): a Softplus with such a threshold (torch's default 20) keeps the rule
+// on h in the act build, any other runs K5's pre build (act_keeps_u), which keeps u and takes beta u > thr ? 1 : 1 / (1 + e^(-beta u))
+// (softplus_grad_u: free of cancellation on both sides; e^(-beta u) = inf gives 0).  The builds that keep u for every kind (tableau,
+// sub-steps, linear externals) take that form for every threshold.
 // Accuracy (DESIGN.md "Activations"): the exponentials go through v_exp_f32 (exp2, 1 ulp), the reciprocals through v_rcp_f32 (1 ulp),
 // the logarithm through v_log_f32.  Each value carries an ABSOLUTE error of about 1e-7, the same budget as the round-3 ELU form that the
 // ELU(1) kernels ship (psnode_common.h).
@@ -114,6 +121,16 @@ __device__ __forceinline__ act_f4 act_grad_quad(const act_f4 h, const ActDev& a)
     }
 }
 
+// Softplus' from the pre-activation u (torch's rule): the pre build's form, and the only correct one below kSoftplusCut (head of this file)
+constexpr float kSoftplusCut = 16.6355323f;      // 24 ln 2: from here e^-thr < 2^-24 and the rule on h is torch's to fp32 precision
+__device__ __forceinline__ float softplus_grad_u(float u, const ActDev& a) {
+    const float y = u * a.beta;
+    return y > a.thr ? 1.0f : __builtin_amdgcn_rcpf(1.0f + act_exp(-y));
+}
+__device__ __forceinline__ act_f4 softplus_grad_u_quad(const act_f4 u, const ActDev& a) {
+    return act_f4{softplus_grad_u(u[0], a), softplus_grad_u(u[1], a), softplus_grad_u(u[2], a), softplus_grad_u(u[3], a)};
+}
+
 // wave-uniform copy (the kind drives scalar branches; selects between the DE's and the AE's act stay scalar)
 __device__ __forceinline__ ActDev act_pick(bool first, const ActDev& x, const ActDev& y) {
     auto u = [](float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); };
@@ -129,7 +146,9 @@ __device__ __forceinline__ ActDev act_pick(bool first, const ActDev& x, const Ac
 // ---- the pre-activation family (kind >= PSNODE_ACT_PRE_FAMILY): SiLU, GELU (erf / tanh form), Mish.  Their derivatives are functions of the
 // PRE-activation u, not of h, so K5 keeps u for them (its pre build: psnode_generic_bwd_pre.hip).  New functions, kept out of act_quad /
 // act_grad_quad, so that the six-kind kernels keep their instruction stream.  Every form below is finite for every finite u (|u| up to the
-// fp32 range: each exponential that can overflow is taken of a non-positive argument or guarded) and keeps the ~1e-7 absolute budget:
+// fp32 range: each exponential that can overflow is taken of a non-positive argument or guarded, and GELU(tanh)' clamps u^2 at 1e4 --
+// e^(-2|z|) is exactly 0 from |u| = 11 up, so the clamp changes no value and keeps 0 * (1 + 3 k u^2) from becoming 0 * inf beyond
+// |u| = 1.8e19) and keeps the ~1e-7 absolute budget:
 //   SiLU        u s,  s = 1 / (1 + e^-u)                          s (1 + u (1 - s)),  1 - s = e^-u s for u >= 0 (no cancellation)
 //   GELU        u Phi(u),  Phi(u) = erfc(-u / sqrt 2) / 2          Phi(u) + u phi(u)   (erfc: no cancellation of 1 + erf for u < 0)
 //   GELU(tanh)  u (1 + t) / 2,  t = tanh z,  z = c (u + k u^3)    (1 + t) / 2 + u (1 - t^2) c (1 + 3 k u^2) / 2
@@ -164,7 +183,7 @@ __device__ __forceinline__ float pre_grad1_k(float u) {
     } else if constexpr (KIND == PSNODE_ACT_GELU) {
         return 0.5f * erfcf(-u * kSqrtHalf) + u * (kInvSqrt2Pi * act_exp(-0.5f * u * u));
     } else if constexpr (KIND == PSNODE_ACT_GELU_TANH) {
-        const float u2 = u * u, z = kGeluC * (u + kGeluK * u2 * u);
+        const float u2 = fminf(u * u, 1e4f), z = kGeluC * (u + kGeluK * u2 * u);      // (|u| > 100: z stays beyond +-3.5e4, e = 0)
         const float e = __builtin_amdgcn_exp2f(-2.0f * kLog2e * fabsf(z)), r = __builtin_amdgcn_rcpf(1.0f + e);
         return r * (z < 0.0f ? e : 1.0f) + (u * (2.0f * e * r * r)) * (kGeluC * (1.0f + 3.0f * kGeluK * u2));
     } else {    // PSNODE_ACT_MISH
@@ -182,7 +201,9 @@ __device__ __forceinline__ act_f4 pre_grad_quad_k(const act_f4 u) {
     return act_f4{pre_grad1_k<KIND>(u[0]), pre_grad1_k<KIND>(u[1]), pre_grad1_k<KIND>(u[2]), pre_grad1_k<KIND>(u[3])};
 }
 // the pre build's forms over all ten kinds (an ActPair may mix the families): kinds < 32 are act1 / act_quad and take their derivative
-// from h (act_grad1 / act_grad_quad, the numbers of the act build), the family >= 32 from u.  One branch per quad, as act_quad.
+// from h (the forms of act_grad1, the numbers of the act build) -- but Softplus, which takes it from u (softplus_grad_u) --, the family >= 32
+// from u.  One branch per quad, as act_quad: pre_grad_quad switches over the six low kinds itself, Softplus in the default arm (a test for
+// Softplus in front of act_grad_quad made the tableau build copy a VGPR to an AGPR under partial EXEC, which the ISA lint refuses).
 __device__ __forceinline__ act_f4 pre_act_quad(const act_f4 v, const ActDev& a) {
     if (a.kind < PSNODE_ACT_PRE_FAMILY) return act_quad(v, a);
     switch (a.kind) {
@@ -193,7 +214,16 @@ __device__ __forceinline__ act_f4 pre_act_quad(const act_f4 v, const ActDev& a) 
     }
 }
 __device__ __forceinline__ act_f4 pre_grad_quad(const act_f4 h, const act_f4 u, const ActDev& a) {
-    if (a.kind < PSNODE_ACT_PRE_FAMILY) return act_grad_quad(h, a);
+    if (a.kind < PSNODE_ACT_PRE_FAMILY) {
+        switch (a.kind) {
+            case PSNODE_ACT_ELU: return act_grad_quad_k<PSNODE_ACT_ELU>(h, a);
+            case PSNODE_ACT_TANH: return act_grad_quad_k<PSNODE_ACT_TANH>(h, a);
+            case PSNODE_ACT_SIGMOID: return act_grad_quad_k<PSNODE_ACT_SIGMOID>(h, a);
+            case PSNODE_ACT_RELU: return act_grad_quad_k<PSNODE_ACT_RELU>(h, a);
+            case PSNODE_ACT_LEAKY_RELU: return act_grad_quad_k<PSNODE_ACT_LEAKY_RELU>(h, a);
+            default: return softplus_grad_u_quad(u, a);
+        }
+    }
     switch (a.kind) {
         case PSNODE_ACT_SILU: return pre_grad_quad_k<PSNODE_ACT_SILU>(u);
         case PSNODE_ACT_GELU: return pre_grad_quad_k<PSNODE_ACT_GELU>(u);
@@ -211,7 +241,7 @@ __device__ __forceinline__ float pre_act1(float x, const ActDev& a) {
     }
 }
 __device__ __forceinline__ float pre_grad1(float h, float u, const ActDev& a) {
-    if (a.kind < PSNODE_ACT_PRE_FAMILY) return act_grad1(h, a);
+    if (a.kind < PSNODE_ACT_PRE_FAMILY) return a.kind == PSNODE_ACT_SOFTPLUS ? softplus_grad_u(u, a) : act_grad1(h, a);
     switch (a.kind) {
         case PSNODE_ACT_SILU: return pre_grad1_k<PSNODE_ACT_SILU>(u);
         case PSNODE_ACT_GELU: return pre_grad1_k<PSNODE_ACT_GELU>(u);
@@ -221,6 +251,10 @@ __device__ __forceinline__ float pre_grad1(float h, float u, const ActDev& a) {
 }
 // a call with an activation of the pre-activation family on either MLP runs the pre build
 inline bool act_pair_pre(const ActPair& p) { return p.de.kind >= PSNODE_ACT_PRE_FAMILY || p.ae.kind >= PSNODE_ACT_PRE_FAMILY; }
+// K5 needs u for the derivative: the pre-activation family, and a Softplus whose threshold is below kSoftplusCut (head of this file).  Such a
+// call runs K5's pre build; K0 keeps no u and asks act_pair_pre alone.
+inline bool act_keeps_u(const ActDev& a) { return a.kind >= PSNODE_ACT_PRE_FAMILY || (a.kind == PSNODE_ACT_SOFTPLUS && !(a.thr >= kSoftplusCut)); }
+inline bool act_pair_keeps_u(const ActPair& p) { return act_keeps_u(p.de) || act_keeps_u(p.ae); }
 
 // psnode_capi.hip: validates a psnode_act_f32 and converts it (NULL = ELU(1)).  Returns PSNODE_OK / PSNODE_ERR_*; `is_elu1` = the
 // existing ELU(1) routes apply.

@@ -94,7 +94,7 @@ int generic_backward(const GenericBwdCall& c, const ActPair* act, void* workspac
     if (c.rk && c.lin) return generic_backward_launch<BuildLin>(c, act, static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
     if (c.rk && c.substeps > 1) return generic_backward_launch<BuildSub>(c, act, static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
     if (c.rk) return generic_backward_launch<BuildRk>(c, act, static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
-    const auto launch = !act ? generic_backward_launch<BuildElu1> : (act_pair_pre(*act) ? generic_backward_launch<BuildPre> : generic_backward_launch<BuildAct>);
+    const auto launch = !act ? generic_backward_launch<BuildElu1> : (act_pair_keeps_u(*act) ? generic_backward_launch<BuildPre> : generic_backward_launch<BuildAct>);
     return launch(c, act, static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
 }
 // K4f: every width <= 128 (z_dim up to 8), saved-activation and recompute forms
@@ -273,7 +273,7 @@ bool k5_route_ok(K5Family fam, const Args& a, const ActPair& p, bool elu1, bool 
     if ((flags & ~tf_mask(a)) || (flags && !elu1)) return false;      // (teacher forcing: ELU(1) only)
     if (saved_rows(b, fam != kFamAct ? kSavedAll : query ? kSavedAct : kSavedActCall)) return false;
     // the fit of the build: _tf runs the ELU(1) build, _act the act or the pre build, the others keep the pre-activations for every kind
-    const bool pre = fam == kFamAct ? act_pair_pre(p) : fam != kFamTf;
+    const bool pre = fam == kFamAct ? act_pair_keeps_u(p) : fam != kFamTf;
     return generic_ok(&b, pre, fam == kFamLin) != 0;
 }
 // the struct of a _sub / _lin call; substeps == 1 on _sub is the family without sub-steps

@@ -18,7 +18,7 @@ Which form of ELU each kernel carries (read from csrc/):
 The probes below do not trust this table: an instance gets the plain-domain contract unless it is an inference instance of K1 / K1x /
 K2 / K2x, and one that were filed wrongly would fail the exactness clause of that contract (u > 0 returns u bit for bit).
 Out of scope: the latent backwards (K8*, K9*), the row kernels (test_inline_elu_accuracy_contract pins their ELU), and the builds with
-another activation than ELU(1) (test_gpu_activations*.py have their own test_wide_range_inputs).
+another activation than ELU(1) (test_gpu_act_range.py runs these probes with every other kind).
 
 Every test prints its figures (-s); profiles/elu_range_report.txt is that output of one run.
 """
