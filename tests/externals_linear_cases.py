@@ -2,7 +2,7 @@
 
 1. `refine_rows_linear`: the n-times refined problem on which the one-step-per-interval Euler call -- the CPU oracle's -- is what Euler with
    `substeps = n` and `externals = "linear"` computes on the coarse problem (no teacher forcing): clock t'[kn + j] = t[k] + j h
-   (substeps_cases.refine_clock), rows z'[kn + j] = w_L + (j / n) (w_R - w_L) with w_R = z[k + 1] and w_L = z[k], or the jumped values on an
+   (generic_cases.refine_clock), rows z'[kn + j] = w_L + (j / n) (w_R - w_L) with w_R = z[k + 1] and w_L = z[k], or the jumped values on an
    interval that starts with an event; there row kn keeps the dataset value, which the event replaces.
 
 2. A stand-alone restatement of an explicit Runge-Kutta step with linearly interpolated externals, for an arbitrary tableau:

@@ -1,11 +1,14 @@
 """Hidden-layer activations other than ELU(1): recognition, the model classes' `activation` keyword and the C ABI's argument checks
 (no GPU)."""
 import ctypes
+import functools
 
 import pytest
 import torch
 import torch.nn as nn
 
+from capi_args import act as _act
+from capi_args import dae_bwd_args, ode_args, ode_bwd_args
 from py_psnode_amd import _lib, fused, models
 
 
@@ -108,19 +111,7 @@ def test_model_activation_keyword_defaults_to_the_reference_modules():
     torch.jit.script(c)          # the export path still scripts
 
 
-def _act(kind, alpha=0.0, beta=1.0, threshold=20.0):
-    a = _lib.ActF32()
-    a.kind, a.alpha, a.beta, a.threshold = kind, alpha, beta, threshold
-    return a
-
-
-def _ode_args(kernel=_lib.KERNEL_AUTO):
-    a = _lib.OdeArgsF32()
-    a.method, a.kernel, a.x_dim, a.z_dim, a.T, a.B = _lib.RK4_38, kernel, 8, 2, 10, 4
-    a.de.n_layers, a.de.in_dim = 4, 30
-    for k, o in enumerate((64, 64, 64, 8)):
-        a.de.out_dim[k] = o
-    return a
+_ode_args = functools.partial(ode_args, method=_lib.RK4_38, T=10, B=4)
 
 
 def test_capi_act_argument_checks():
@@ -158,11 +149,7 @@ def test_capi_act_argument_checks():
 def test_capi_act_backward_checks():
     lib = _lib.load()
     R = ctypes.byref
-    b = _lib.OdeBwdArgsF32()
-    b.method, b.kernel, b.x_dim, b.z_dim, b.T, b.B = _lib.MIDPOINT, _lib.KERNEL_AUTO, 8, 2, 10, 4
-    b.de.n_layers, b.de.in_dim = 4, 30
-    for k, o in enumerate((64, 64, 64, 8)):
-        b.de.out_dim[k] = o
+    b = ode_bwd_args(method=_lib.MIDPOINT, T=10, B=4)
     tanh = _act(_lib.ACT_TANH)
     assert lib.psnode_ode_backward_act_supported(R(b), R(tanh)) == 1
     assert lib.psnode_ode_backward_act_f32(R(b), R(_act(6)), None, 0, None) == -3
@@ -178,15 +165,7 @@ def test_capi_act_backward_checks():
     b.flags = 0
     assert lib.psnode_ode_backward_act_supported(R(b), None) == lib.psnode_ode_backward_supported(R(b))
 
-    g = _lib.DaeBwdArgsF32()
-    g.method, g.kernel, g.x_dim, g.z_dim, g.v_dim, g.i_dim, g.T, g.B = _lib.RK4_38, _lib.KERNEL_AUTO, 4, 2, 1, 2, 5, 3
-    n = 9
-    g.de.n_layers, g.de.in_dim = 3, 3 * n
-    g.ae.n_layers, g.ae.in_dim = 2, n + 7
-    for k, o in enumerate((48, 48, 4)):
-        g.de.out_dim[k] = o
-    for k, o in enumerate((32, 2)):
-        g.ae.out_dim[k] = o
+    g = dae_bwd_args(xd=4, zd=2, vd=1, idim=2, hidden=(48, 48), ae_hidden=(32,), method=_lib.RK4_38, T=5, B=3).base
     assert lib.psnode_dae_backward_act_supported(R(g), R(tanh), R(_act(_lib.ACT_SIGMOID))) == 1
     assert lib.psnode_dae_backward_act_supported(R(g), None, R(_act(_lib.ACT_RELU))) == 1
     assert lib.psnode_dae_backward_act_f32(R(g), R(tanh), R(_act(99)), None, 0, None) == -3

@@ -1,10 +1,13 @@
 """The pre-activation family (SiLU, GELU erf / tanh form, Mish): recognition and the C ABI's argument checks and fit queries (no GPU)."""
 import ctypes
+import functools
 
 import pytest
 import torch
 import torch.nn as nn
 
+from capi_args import act as _act
+from capi_args import dae_args, dae_bwd_args, ode_args, ode_bwd_args
 from py_psnode_amd import _lib, fused, models
 
 PRE = [
@@ -87,41 +90,13 @@ def test_recipe_probe_uses_the_modules_activation():
 
 
 # ----------------------------------------------------------------------------- C ABI
-def _act(kind, alpha=0.0, beta=1.0, threshold=20.0):
-    a = _lib.ActF32()
-    a.kind, a.alpha, a.beta, a.threshold = kind, alpha, beta, threshold
-    return a
-
-
-def _ode_args(kernel=_lib.KERNEL_AUTO, xd=8, zd=2, hidden=(64, 64, 64)):
-    a = _lib.OdeArgsF32()
-    a.method, a.kernel, a.x_dim, a.z_dim, a.T, a.B = _lib.RK4_38, kernel, xd, zd, 10, 4
-    a.de.n_layers, a.de.in_dim = len(hidden) + 1, 3 * (xd + zd)
-    for k, o in enumerate(hidden + (xd,)):
-        a.de.out_dim[k] = o
-    return a
-
-
-def _ode_bwd(kernel=_lib.KERNEL_AUTO, xd=8, zd=2, hidden=(64, 64, 64)):
-    b = _lib.OdeBwdArgsF32()
-    b.method, b.kernel, b.x_dim, b.z_dim, b.T, b.B = _lib.MIDPOINT, kernel, xd, zd, 10, 4
-    b.de.n_layers, b.de.in_dim = len(hidden) + 1, 3 * (xd + zd)
-    for k, o in enumerate(hidden + (xd,)):
-        b.de.out_dim[k] = o
-    return b
+_ode_args = functools.partial(ode_args, hidden=(64, 64, 64), method=_lib.RK4_38, T=10, B=4)
+_ode_bwd = functools.partial(ode_bwd_args, hidden=(64, 64, 64), method=_lib.MIDPOINT, T=10, B=4)
+DAE = dict(xd=4, zd=2, vd=1, idim=2, hidden=(48, 48), ae_hidden=(32,), method=_lib.RK4_38, T=5, B=3)
 
 
 def _dae(cls, kernel=_lib.KERNEL_AUTO):
-    g = cls()
-    g.method, g.kernel, g.x_dim, g.z_dim, g.v_dim, g.i_dim, g.T, g.B = _lib.RK4_38, kernel, 4, 2, 1, 2, 5, 3
-    n = 9
-    g.de.n_layers, g.de.in_dim = 3, 3 * n
-    g.ae.n_layers, g.ae.in_dim = 2, n + 7
-    for k, o in enumerate((48, 48, 4)):
-        g.de.out_dim[k] = o
-    for k, o in enumerate((32, 2)):
-        g.ae.out_dim[k] = o
-    return g
+    return dae_args(kernel, **DAE) if cls is _lib.DaeArgsF32 else dae_bwd_args(kernel, **DAE).base
 
 
 KINDS = [_lib.ACT_SILU, _lib.ACT_GELU, _lib.ACT_GELU_TANH, _lib.ACT_MISH]

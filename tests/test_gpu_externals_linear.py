@@ -4,7 +4,7 @@ Yardsticks.  Euler without teacher forcing on a whole clock: the fp32 CPU oracle
 (tests/externals_linear_cases.py), read at rows ::n, under helpers.TOL_GPU on traj_rel_err.  Every other case: the package's callback walk of
 the same modules in float64 on the CPU -- the definition of the semantics, pinned to the oracle and to a stand-alone restatement by
 tests/test_externals_linear_host.py -- under the same gate.  Gradients: torch autograd through that float64 walk, each tensor within
-TOL_GPU of its own max (`_close` of tests/test_gpu_rk_tableau.py).  B = 33: three tiles of 16 trajectories, the last with one; T = 6;
+TOL_GPU of its own max (`close` of tests/generic_cases.py).  B = 33: three tiles of 16 trajectories, the last with one; T = 6;
 events at steps 0 and 3.
 
 An ODE output must also differ from the "hold" run on the same inputs by more than 100 x TOL_GPU, so that a kernel that silently holds cannot
@@ -12,45 +12,32 @@ pass.  The one exception is Euler with one sub-step: its only stage has theta = 
 definition and the test asserts that instead (within TOL_GPU)."""
 import copy
 import functools
-import warnings
 
 import pytest
 import torch
 import torch.nn as nn
 
 import externals_linear_cases as L
-import substeps_cases as C
+import generic_cases as C
+from generic_cases import DAE_SHAPES, K5_DAE_SHAPES, ODE_FWD_SHAPES
 from helpers import TOL_GPU, traj_rel_err
 from oracle import psnode_oracle as O
 from py_psnode_amd import _lib, fused, models
 from py_psnode_amd import neural_dae as nd
-from test_gpu_rk_tableau import DAE_SHAPES, K5_DAE_SHAPES, ODE_FWD_SHAPES, _close
 
 pytestmark = pytest.mark.gpu
 
 SOLVERS = {"euler": nd.Euler, "rk4": nd.RK4, "Heun2": nd.Heun2, "Kutta3": nd.Kutta3, "RK4Classic": nd.RK4Classic}
 B0, T0 = 33, 6
+EV = (0, 3)          # the grid rows that carry the events
+_c = C.to_cuda
+_close = functools.partial(C.close, tol=TOL_GPU)
 
 
 def _solver(name, n, mode="require", kernel="auto", externals="linear"):
     s = SOLVERS[name](substeps=n, externals=externals)
     s.fused, s.kernel = mode, kernel
     return s
-
-
-def _d(a):
-    return None if a is None else a.double()
-
-
-def _c(a):
-    return None if a is None else a.cuda()
-
-
-def _padded(t):
-    """the last grid points of some trajectories are -1, as the datasets pad short curves (trajectory 0, whose clock decides the events, whole)"""
-    t = t.clone()
-    t[-2:, 2::3] = -1.0
-    return t
 
 
 def _ode_reference(name, n, de, t, x, z, ev, zj, tx=False, oracle=True):
@@ -61,14 +48,11 @@ def _ode_reference(name, n, de, t, x, z, ev, zj, tx=False, oracle=True):
             xf = torch.zeros(tf.shape[0], x.shape[1], x.shape[2])
             xf[0] = x[0]
             return O.integrate_ode(name, C.layers_of(de.x_dot), tf, xf, L.refine_rows_linear(z, n, t, ev, zj), a0, ev, zj)[::n]
-        return C.run_ode(_solver(name, n, "off"), copy.deepcopy(de).double(), _d(t), _d(x), _d(z), _d(a0), _d(ev), _d(zj), tx)
+    return C.ode_walk64(_solver(name, n, "off"), de, t, x, z, ev, zj, tx)
 
 
 def _ode_gpu(name, n, de, t, x, z, ev, zj, tx=False, mode="require", kernel="auto", externals="linear"):
-    xc, zc = _c(x), _c(z)
-    with torch.no_grad():
-        return C.run_ode(_solver(name, n, mode, kernel, externals), copy.deepcopy(de).cuda(), _c(t), xc, zc, torch.cat((xc[0], zc[0]), -1),
-                         _c(ev), _c(zj), tx)
+    return C.ode_gpu(_solver(name, n, mode, kernel, externals), de, t, x, z, ev, zj, tx)
 
 
 # ----------------------------------------------------------------------------- ODE forward
@@ -81,7 +65,7 @@ def test_ode_forward(shape, name, n):
     with two sub-steps differs from the hold by 4e-4 only, below what the second gate asks of a kernel that does interpolate."""
     xd, zd, hidden = ODE_FWD_SHAPES[shape]
     t = C.dyadic_clock(T0, B0, n) * 4.0
-    de, x, z, ev, zj = C.ode_problem(xd, zd, hidden, B0, T0, seed=3 + xd + len(hidden) + n, t=t)
+    de, _, x, z, ev, zj = C.ode_case(xd, zd, hidden, B0, T0, seed=3 + xd + len(hidden) + n, t=t, ev_rows=EV)
     z, zj = 4.0 * z, 4.0 * zj
     out = _ode_gpu(name, n, de, t, x, z, ev, zj)          # fused = "require"
     hold = _ode_gpu(name, n, de, t, x, z, ev, zj, externals="hold")
@@ -102,8 +86,8 @@ def test_ode_forward_teacher_forced_and_ragged(case, name, n):
     xd, zd, hidden = ODE_FWD_SHAPES["streamed" if n == 3 else "reg"]
     t = C.dyadic_clock(T0, B0, n) * 0.7          # (no longer dyadic: h is a rounded quotient)
     if "ragged" in case:
-        t = _padded(t)                           # (theta does not depend on the clock: h = 0 or h < 0 needs no special case)
-    de, x, z, ev, zj = C.ode_problem(xd, zd, hidden, B0, T0, seed=40 + n, t=t)
+        t = C.padded(t)                           # (theta does not depend on the clock: h = 0 or h < 0 needs no special case)
+    de, _, x, z, ev, zj = C.ode_case(xd, zd, hidden, B0, T0, seed=40 + n, t=t, ev_rows=EV)
     tx = "truex" in case
     out = _ode_gpu(name, n, de, t, x, z, ev, zj, tx)
     ref = _ode_reference(name, n, de, t, x, z, ev, zj, tx, oracle=False)
@@ -115,7 +99,7 @@ def test_ode_forward_teacher_forced_and_ragged(case, name, n):
 @pytest.mark.parametrize("B,Tn", [(B0, 1), (B0, 2), (16, T0), (1, T0)])
 def test_ode_forward_short_grids_and_batch_edges(B, Tn, n):
     t = C.dyadic_clock(Tn, B, n)
-    de, x, z, ev, zj = C.ode_problem(8, 2, (64, 64, 64), B, Tn, seed=B + Tn, t=t)
+    de, _, x, z, ev, zj = C.ode_case(8, 2, (64, 64, 64), B, Tn, seed=B + Tn, t=t, ev_rows=EV)
     out = _ode_gpu("rk4", n, de, t, x, z, ev, zj, kernel="generic")
     ref = _ode_reference("rk4", n, de, t, x, z, ev, zj)
     assert out.shape == ref.shape and traj_rel_err(out.cpu(), ref.float()) <= TOL_GPU
@@ -127,7 +111,7 @@ def test_rows_beyond_the_last_grid_point_are_never_read(dae):
     t = C.dyadic_clock(T0, B0, 2)
     canary = lambda a: torch.cat((a, torch.full((1, *a.shape[1:]), float("nan"))), 0).cuda()[:-1]
     if not dae:
-        de, x, z, ev, zj = C.ode_problem(8, 2, (64, 64, 64), B0, T0, seed=91, t=t)
+        de, _, x, z, ev, zj = C.ode_case(8, 2, (64, 64, 64), B0, T0, seed=91, t=t, ev_rows=EV)
         xc, m = _c(x), copy.deepcopy(de).cuda()
         outs = []
         for zc in (_c(z), canary(z)):
@@ -136,14 +120,14 @@ def test_rows_beyond_the_last_grid_point_are_never_read(dae):
                 outs.append(C.run_ode(_solver("rk4", 2), m, _c(t), xc, zc, torch.cat((xc[0], _c(z)[0]), -1), _c(ev), _c(zj)))
         assert torch.isfinite(outs[1]).all() and torch.equal(outs[0], outs[1])
         return
-    case = list(C.dae_problem(5, 4, 6, 6, (64, 64, 64), (64, 64, 64), B0, T0, seed=93, t=t))
+    case = C.dae_case(5, 4, 6, 6, (64, 64, 64), (64, 64, 64), B0, T0, seed=93, t=t, ev_rows=EV)
     de, ae = copy.deepcopy(case[0]).cuda(), copy.deepcopy(case[1]).cuda()
     outs = []
     for wrap in (_c, canary):
         rest = [_c(q) for q in case[2:]]
-        rest[1], rest[2] = wrap(case[3]), wrap(case[4])          # z, v
+        rest[2], rest[3] = wrap(case[4]), wrap(case[5])          # z, v
         with torch.no_grad():
-            outs.append(C.run_dae(_solver("rk4", 2), de, ae, _c(t), *rest))
+            outs.append(C.run_dae(_solver("rk4", 2), de, ae, *rest))
     assert all(torch.isfinite(q).all() for q in outs[1])
     assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
 
@@ -153,10 +137,8 @@ def test_rows_beyond_the_last_grid_point_are_never_read(dae):
 def _dae_forward_case(shape, n, no_x):
     xd, zd, vd, idim, dh, ah = DAE_SHAPES[shape]
     t = C.dyadic_clock(T0, B0, n)
-    case = list(C.dae_problem(xd, zd, vd, idim, dh, ah, B0, T0, seed=17 + xd + n, t=t))
-    if no_x:
-        case[2] = case[2][:, :, :0]          # the dataset x is not read without teacher forcing: what the models pass then
-    return t, tuple(case)
+    case = C.dae_case(xd, zd, vd, idim, dh, ah, B0, T0, seed=17 + xd + n, t=t, ev_rows=EV)
+    return C.without_x(case) if no_x else case
 
 
 @pytest.mark.parametrize("n", [1, 2])
@@ -165,13 +147,11 @@ def _dae_forward_case(shape, n, no_x):
 @pytest.mark.parametrize("mode", ["events_no_x", "tx0_ti0", "tx1_ti0", "tx0_ti1", "tx1_ti1"])
 def test_dae_forward(mode, shape, name, n):
     xd, zd, vd, idim, dh, ah = DAE_SHAPES[shape]
-    t, case = _dae_forward_case(shape, n, mode == "events_no_x")
+    case = _dae_forward_case(shape, n, mode == "events_no_x")
     tx, ti = "tx1" in mode, "ti1" in mode
-    with torch.no_grad():
-        out = C.run_dae(_solver(name, n), copy.deepcopy(case[0]).cuda(), copy.deepcopy(case[1]).cuda(), _c(t), *(_c(q) for q in case[2:]), tx, ti)
-        hold = C.run_dae(_solver(name, n, externals="hold"), copy.deepcopy(case[0]).cuda(), copy.deepcopy(case[1]).cuda(), _c(t),
-                         *(_c(q) for q in case[2:]), tx, ti)
-        ref = C.run_dae(_solver(name, n, "off"), copy.deepcopy(case[0]).double(), copy.deepcopy(case[1]).double(), _d(t), *(_d(q) for q in case[2:]), tx, ti)
+    out = C.dae_gpu(_solver(name, n), case, tx, ti)
+    hold = C.dae_gpu(_solver(name, n, externals="hold"), case, tx, ti)
+    ref = C.dae_walk64(_solver(name, n, "off"), case, tx, ti)
     ex, ei = traj_rel_err(out[0].cpu(), ref[0].float()), traj_rel_err(out[1].cpu(), ref[1].float())
     print(mode, shape, name, n, f"{ex:.3e} {ei:.3e}", f"against hold {traj_rel_err(out[0].cpu(), hold[0].cpu()):.3e}")
     assert out[0].shape == (T0, B0, xd) and out[1].shape == (T0, B0, idim) and ex <= TOL_GPU and ei <= TOL_GPU
@@ -179,39 +159,15 @@ def test_dae_forward(mode, shape, name, n):
 
 
 # ----------------------------------------------------------------------------- training
-def _ode_train(name, n, de, t, x, z, ev, zj, G, dev, tx=False):
-    dtype = torch.float32 if dev == "cuda" else torch.float64
-    cv = lambda a: None if a is None else a.to(device=dev, dtype=dtype)
-    m = copy.deepcopy(de).to(device=dev, dtype=dtype)
-    xg = cv(x) if tx else cv(x).requires_grad_(True)           # (teacher forcing: the dataset rows get no gradient)
-    zg = cv(z).requires_grad_(True)
-    a0 = torch.cat((cv(x)[0], cv(z)[0]), -1).requires_grad_(True)
-    zjg = cv(zj).requires_grad_(True) if zj is not None else None
-    xs = C.run_ode(_solver(name, n, "require" if dev == "cuda" else "off"), m, cv(t), xg, zg, a0, cv(ev), zjg, tx)
-    (xs * cv(G)).sum().backward()
-    grads = {"z": zg.grad, "a0": a0.grad, "zj": zjg.grad if zjg is not None else None}
-    if not tx:
-        grads["x"] = xg.grad                                    # (x0: the only row of x the integration reads)
-    grads.update({f"p{k}": p.grad for k, p in enumerate(m.parameters())})
-    return xs, grads
+# the file's gate: cotangent G from seed 3 unless given, the fused function ran, helpers.TOL_GPU of each tensor's max; the reference trajectory
+# rounded to float32 first
+def _check_ode(name, n, de, t, x, z, ev, zj, tx=False, G=None):
+    G = C.cotangents(3, x.shape)[0] if G is None else G
+    return C.check_ode_training(functools.partial(_solver, name, n), (de, t, x, z, ev, zj), G, "_FusedOdeLin", TOL_GPU, tx, what=f"{name} n={n}",
+                                ref_float=True)
 
 
-def _check_ode_training(name, n, de, t, x, z, ev, zj, tx=False, G=None):
-    G = torch.randn(x.shape, generator=torch.Generator().manual_seed(3)) if G is None else G
-    ref_xs, ref = _ode_train(name, n, de, t, x, z, ev, zj, G, "cpu", tx)
-    with warnings.catch_warnings():
-        warnings.simplefilter("error", RuntimeWarning)
-        xs, got = _ode_train(name, n, de, t, x, z, ev, zj, G, "cuda", tx)
-        _, again = _ode_train(name, n, de, t, x, z, ev, zj, G, "cuda", tx)
-    assert type(xs.grad_fn).__name__.startswith("_FusedOdeLin"), xs.grad_fn
-    assert traj_rel_err(xs.detach().cpu(), ref_xs.detach().float()) <= TOL_GPU
-    for k in ref:
-        _close(got[k], ref[k], f"{name} n={n} grad {k}")
-        assert (got[k] is None and again[k] is None) or torch.equal(got[k], again[k]), f"backward not repeatable: {k}"
-    return got, ref
-
-
-# K5's paths (tests/test_gpu_rk_tableau.py, K5_ODE_SHAPES): the register path, the streamed path (hidden 128, global accumulators) and a wide
+# K5's paths (tests/generic_cases.py, K5_ODE_SHAPES): the register path, the streamed path (hidden 128, global accumulators) and a wide
 # input on the register path (108 columns, z_dim 4); LIN_STAGED is the staged path (132 input columns) with externals -- the list's own
 # staged entry has z_dim 0, where there is nothing to interpolate
 LIN_K5_ODE_SHAPES = [(8, 2, 64, 3), (8, 2, 128, 3), (32, 4, 48, 2)]
@@ -225,16 +181,16 @@ TRAIN = ["euler", "Heun2", "RK4Classic"]
 @pytest.mark.parametrize("xd,zd,H,nh", LIN_K5_ODE_SHAPES)
 def test_ode_training(xd, zd, H, nh, events, name, n):
     t = C.dyadic_clock(T0, B0, n) * 0.7
-    de, x, z, ev, zj = C.ode_problem(xd, zd, (H,) * nh, B0, T0, seed=5 + xd + n, t=t, ev_steps=(0, 3) if events else ())
-    _check_ode_training(name, n, de, t, x, z, ev, zj)
+    de, _, x, z, ev, zj = C.ode_case(xd, zd, (H,) * nh, B0, T0, seed=5 + xd + n, t=t, ev_rows=EV if events else ())
+    _check_ode(name, n, de, t, x, z, ev, zj)
 
 
 @pytest.mark.parametrize("n", [1, 3])
 def test_ode_training_on_the_staged_path(n):
     xd, zd, H, nh = LIN_STAGED
     t = C.dyadic_clock(T0, B0, n) * 0.7
-    de, x, z, ev, zj = C.ode_problem(xd, zd, (H,) * nh, B0, T0, seed=6 + n, t=t)
-    _check_ode_training("RK4Classic", n, de, t, x, z, ev, zj)
+    de, _, x, z, ev, zj = C.ode_case(xd, zd, (H,) * nh, B0, T0, seed=6 + n, t=t, ev_rows=EV)
+    _check_ode("RK4Classic", n, de, t, x, z, ev, zj)
 
 
 @pytest.mark.parametrize("n", [1, 3])
@@ -242,8 +198,8 @@ def test_ode_training_on_the_staged_path(n):
 @pytest.mark.parametrize("xd,zd,hidden", [(8, 2, (64, 64, 64)), (8, 2, (128, 128, 128))])
 def test_ode_teacher_forced_training(xd, zd, hidden, name, n):
     t = C.dyadic_clock(T0, B0, n) * 0.7
-    de, x, z, ev, zj = C.ode_problem(xd, zd, hidden, B0, T0, seed=9 + xd + n, t=t)
-    _check_ode_training(name, n, de, t, x, z, ev, zj, tx=True)
+    de, _, x, z, ev, zj = C.ode_case(xd, zd, hidden, B0, T0, seed=9 + xd + n, t=t, ev_rows=EV)
+    _check_ode(name, n, de, t, x, z, ev, zj, tx=True)
 
 
 @pytest.mark.parametrize("n", [1, 3])
@@ -254,10 +210,10 @@ def test_the_right_hand_contribution_reaches_the_next_rows_gradient(name, n):
     only: zero there too."""
     k = 2
     t = C.dyadic_clock(T0, B0, n) * 0.7
-    de, x, z, ev, zj = C.ode_problem(8, 2, (64, 64, 64), B0, T0, seed=13 + n, t=t, ev_steps=())
+    de, _, x, z, ev, zj = C.ode_case(8, 2, (64, 64, 64), B0, T0, seed=13 + n, t=t, ev_rows=())
     G = torch.zeros(x.shape)
     G[k + 1] = torch.randn(x.shape[1:], generator=torch.Generator().manual_seed(8))
-    got, ref = _check_ode_training(name, n, de, t, x, z, ev, zj, G=G)
+    got, ref = _check_ode(name, n, de, t, x, z, ev, zj, G=G)
     gz, rz = got["z"].cpu(), ref["z"]
     assert float(gz[k + 2:].abs().max()) == 0.0 and float(rz[k + 2:].abs().max()) == 0.0
     if name == "euler" and n == 1:
@@ -267,35 +223,9 @@ def test_the_right_hand_contribution_reaches_the_next_rows_gradient(name, n):
         _close(gz[k + 1], rz[k + 1], f"{name} n={n} grad z[k + 1]")
 
 
-def _dae_train(name, n, case, t, G, Gi, dev, tx=False, ti=False):
-    dtype = torch.float32 if dev == "cuda" else torch.float64
-    cv = lambda a: None if a is None else a.to(device=dev, dtype=dtype)
-    de, ae, x, z, v, i, x_init, a0, ev, zj, vj = case
-    de, ae = copy.deepcopy(de).to(device=dev, dtype=dtype), copy.deepcopy(ae).to(device=dev, dtype=dtype)
-    leaf = lambda a: None if a is None else cv(a).requires_grad_(True)
-    xi, zg, vg, a0g, zjg, vjg = leaf(x_init), leaf(z), leaf(v), leaf(a0), leaf(zj), leaf(vj)
-    xs, is_ = C.run_dae(_solver(name, n, "require" if dev == "cuda" else "off"), de, ae, cv(t), cv(x), zg, vg, cv(i), xi, a0g, cv(ev), zjg, vjg, tx, ti)
-    ((xs * cv(G)).sum() + (is_ * cv(Gi)).sum()).backward()
-    grads = {"x_init": xi.grad, "z": zg.grad, "v": vg.grad, "a0": a0g.grad, "zj": zjg.grad if zjg is not None else None,
-             "vj": vjg.grad if vjg is not None else None}
-    grads.update({f"de{k}": p.grad for k, p in enumerate(de.parameters())})
-    grads.update({f"ae{k}": p.grad for k, p in enumerate(ae.parameters())})
-    return xs, is_, grads
-
-
-def _check_dae_training(name, n, case, t, tx=False, ti=False):
-    g = torch.Generator().manual_seed(4)
-    G, Gi = torch.randn(case[2].shape, generator=g), torch.randn(case[5].shape, generator=g)
-    rx, ri, ref = _dae_train(name, n, case, t, G, Gi, "cpu", tx, ti)
-    with warnings.catch_warnings():
-        warnings.simplefilter("error", RuntimeWarning)
-        xs, is_, got = _dae_train(name, n, case, t, G, Gi, "cuda", tx, ti)
-        _, _, again = _dae_train(name, n, case, t, G, Gi, "cuda", tx, ti)
-    assert type(xs.grad_fn).__name__.startswith("_FusedDaeLin"), xs.grad_fn
-    assert traj_rel_err(xs.detach().cpu(), rx.detach().float()) <= TOL_GPU and traj_rel_err(is_.detach().cpu(), ri.detach().float()) <= TOL_GPU
-    for k in ref:
-        _close(got[k], ref[k], f"{name} n={n} grad {k}")
-        assert (got[k] is None and again[k] is None) or torch.equal(got[k], again[k]), f"backward not repeatable: {k}"
+def _check_dae(name, n, case, tx=False, ti=False):
+    G, Gi = C.cotangents(4, case[3].shape, case[6].shape)
+    C.check_dae_training(functools.partial(_solver, name, n), case, G, Gi, "_FusedDaeLin", TOL_GPU, tx, ti, what=f"{name} n={n}", ref_float=True)
 
 
 @pytest.mark.parametrize("n", [1, 3])
@@ -305,14 +235,14 @@ def _check_dae_training(name, n, case, t, tx=False, ti=False):
 def test_dae_training(shape, events, name, n):
     xd, zd, vd, idim, dh, ah = K5_DAE_SHAPES[shape]
     t = C.dyadic_clock(T0, B0, n) * 0.7
-    _check_dae_training(name, n, C.dae_problem(xd, zd, vd, idim, dh, ah, B0, T0, seed=21 + xd + n, t=t, ev_steps=(0, 3) if events else ()), t)
+    _check_dae(name, n, C.dae_case(xd, zd, vd, idim, dh, ah, B0, T0, seed=21 + xd + n, t=t, ev_rows=EV if events else ()))
 
 
 @pytest.mark.parametrize("shape", ["streamed", "h128", "deep"])
 def test_dae_training_on_the_other_k5_paths(shape):
     xd, zd, vd, idim, dh, ah = K5_DAE_SHAPES[shape]
     t = C.dyadic_clock(T0, B0, 3) * 0.7
-    _check_dae_training("RK4Classic", 3, C.dae_problem(xd, zd, vd, idim, dh, ah, B0, T0, seed=27 + xd, t=t), t)
+    _check_dae("RK4Classic", 3, C.dae_case(xd, zd, vd, idim, dh, ah, B0, T0, seed=27 + xd, t=t, ev_rows=EV))
 
 
 @pytest.mark.parametrize("n", [1, 3])
@@ -320,27 +250,27 @@ def test_dae_training_on_the_other_k5_paths(shape):
 @pytest.mark.parametrize("tx,ti", [(True, False), (False, True), (True, True)])
 def test_dae_teacher_forced_training(tx, ti, name, n):
     t = C.dyadic_clock(T0, B0, n) * 0.7
-    _check_dae_training(name, n, C.dae_problem(5, 4, 6, 6, (64, 64, 64), (64, 64, 64), B0, T0, seed=23 + n, t=t), t, tx, ti)
+    _check_dae(name, n, C.dae_case(5, 4, 6, 6, (64, 64, 64), (64, 64, 64), B0, T0, seed=23 + n, t=t, ev_rows=EV), tx, ti)
 
 
 # ----------------------------------------------------------------------------- activations
 @pytest.mark.parametrize("act", [nn.Tanh, nn.SiLU])
 def test_other_activations_ode(act):
     t = C.dyadic_clock(T0, B0, 3) * 0.7
-    de, x, z, ev, zj = C.ode_problem(8, 2, (64, 64, 64), B0, T0, seed=31, t=t, act=act)
-    _check_ode_training("rk4", 3, de, t, x, z, ev, zj)
+    de, _, x, z, ev, zj = C.ode_case(8, 2, (64, 64, 64), B0, T0, seed=31, t=t, act=act, ev_rows=EV)
+    _check_ode("rk4", 3, de, t, x, z, ev, zj)
 
 
 def test_silu_de_tanh_ae_dae():
     t = C.dyadic_clock(T0, B0, 2) * 0.7
-    _check_dae_training("Kutta3", 2, C.dae_problem(4, 2, 1, 2, (48, 48), (32, 32), B0, T0, seed=33, t=t, de_act=nn.SiLU, ae_act=nn.Tanh), t)
+    _check_dae("Kutta3", 2, C.dae_case(4, 2, 1, 2, (48, 48), (32, 32), B0, T0, seed=33, t=t, de_act=nn.SiLU, ae_act=nn.Tanh, ev_rows=EV))
 
 
 # ----------------------------------------------------------------------------- routing
 def test_kernel_wave_raises_under_require_and_walks_under_auto():
     """one sub-step, so that it is the externals' predicate that speaks (with more, the sub-steps' one refuses the kernel first)"""
     t = C.dyadic_clock(T0, B0, 1)
-    de, x, z, ev, zj = C.ode_problem(8, 2, (64, 64, 64), B0, T0, seed=41, t=t)
+    de, _, x, z, ev, zj = C.ode_case(8, 2, (64, 64, 64), B0, T0, seed=41, t=t, ev_rows=EV)
     with pytest.raises(_lib.UnsupportedShapeError, match="externals"):
         _ode_gpu("rk4", 1, de, t, x, z, ev, zj, mode="require", kernel="wave")
     with pytest.raises(_lib.UnsupportedShapeError):
@@ -383,24 +313,21 @@ def test_direct_encode_model_takes_rows_and_k0():
 def test_externals_hold_is_bitwise_the_present_route(n):
     """through the solver, and through the fused entries with externals="hold" spelled out: the same kernels, the same bits"""
     t = C.dyadic_clock(T0, B0, n) * 0.7
-    de, x, z, ev, zj = C.ode_problem(8, 2, (64, 64, 64), B0, T0, seed=81, t=t)
+    de, _, x, z, ev, zj = C.ode_case(8, 2, (64, 64, 64), B0, T0, seed=81, t=t, ev_rows=EV)
     for name in ("rk4", "Kutta3"):
         a = _ode_gpu(name, n, de, t, x, z, ev, zj, externals="hold")
         s = SOLVERS[name](substeps=n)
         s.fused = "require"
-        xc, zc = _c(x), _c(z)
-        with torch.no_grad():
-            b = C.run_ode(s, copy.deepcopy(de).cuda(), _c(t), xc, zc, torch.cat((xc[0], zc[0]), -1), _c(ev), _c(zj))
+        b = C.ode_gpu(s, de, t, x, z, ev, zj)
         assert torch.equal(a, b)
     layers = [(w.cuda(), b.cuda()) for w, b in C.layers_of(de.x_dot)]
     args = ("rk4", layers, _c(t), _c(x[:1]), _c(z), _c(torch.cat((x[0], z[0]), -1)))
     kw = dict(event_t=_c(ev), z_jump=_c(zj), kernel="generic", substeps=n)
     assert torch.equal(fused.ode_integrate(*args, externals="hold", **kw), fused.ode_integrate(*args, **kw))
-    case = C.dae_problem(8, 2, 2, 2, (64, 64, 64), (64, 64, 64), B0, T0, seed=83, t=t)
+    case = C.dae_case(8, 2, 2, 2, (64, 64, 64), (64, 64, 64), B0, T0, seed=83, t=t, ev_rows=EV)
     for name in ("rk4", "Kutta3"):
         outs = []
         for s in (_solver(name, n, externals="hold"), SOLVERS[name](substeps=n)):
             s.fused = "require"
-            with torch.no_grad():
-                outs.append(C.run_dae(s, copy.deepcopy(case[0]).cuda(), copy.deepcopy(case[1]).cuda(), _c(t), *(_c(q) for q in case[2:])))
+            outs.append(C.dae_gpu(s, case))
         assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])

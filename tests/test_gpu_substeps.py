@@ -1,50 +1,38 @@
 """Sub-steps per grid interval (solver.substeps) on the generic kernels: K0 forward, K0 + K5 training, ODE and DAE.
 
-Yardsticks.  Where the n-times refined problem (tests/substeps_cases.py) expresses the case -- no teacher forcing, a whole clock, one of the
+Yardsticks.  Where the n-times refined problem (tests/generic_cases.py) expresses the case -- no teacher forcing, a whole clock, one of the
 reference's three formulas -- the fp32 CPU oracle on that problem, read at rows ::n, under helpers.TOL_GPU on traj_rel_err.  Otherwise
 (teacher forcing, a -1-padded ragged clock, Kutta3, other activations) the package's callback walk of the same modules with the same
 substeps in float64 on the CPU -- the definition of the semantics, pinned to the oracle by tests/test_substeps_host.py -- under the same
-gate.  Gradients: torch autograd through that float64 walk, each tensor within TOL_GPU of its own max (the gate `_close` of
-tests/test_gpu_rk_tableau.py).  B = 33: three tiles of 16 trajectories, the last with one; T = 6; events at steps 0 and 3."""
+gate.  Gradients: torch autograd through that float64 walk, each tensor within TOL_GPU of its own max (the gate `close` of
+tests/generic_cases.py).  B = 33: three tiles of 16 trajectories, the last with one; T = 6; events at steps 0 and 3."""
 import copy
-import warnings
+import functools
 
 import pytest
 import torch
 import torch.nn as nn
 
-import substeps_cases as C
+import generic_cases as C
+from generic_cases import DAE_SHAPES, K5_DAE_SHAPES, ODE_FWD_SHAPES
 from helpers import TOL_GPU, traj_rel_err
 from oracle import psnode_oracle as O
 from py_psnode_amd import _lib, fused, models
 from py_psnode_amd import neural_dae as nd
-from test_gpu_rk_tableau import DAE_SHAPES, K5_DAE_SHAPES, ODE_FWD_SHAPES, _close
 
 pytestmark = pytest.mark.gpu
 
 SOLVERS = {"euler": nd.Euler, "rk4": nd.RK4, "Kutta3": nd.Kutta3}
 B0, T0 = 33, 6
+EV = (0, 3)          # the grid rows that carry the events
+_c = C.to_cuda
+_close = functools.partial(C.close, tol=TOL_GPU)
 
 
 def _solver(name, n, mode="require", kernel="auto"):
     s = SOLVERS[name](substeps=n)
     s.fused, s.kernel = mode, kernel
     return s
-
-
-def _d(a):
-    return None if a is None else a.double()
-
-
-def _c(a):
-    return None if a is None else a.cuda()
-
-
-def _padded(t):
-    """the last grid points of some trajectories are -1, as the datasets pad short curves (trajectory 0, whose clock decides the events, whole)"""
-    t = t.clone()
-    t[-2:, 2::3] = -1.0
-    return t
 
 
 def _ode_reference(name, n, de, t, x, z, ev, zj, tx=False, oracle=True):
@@ -55,13 +43,11 @@ def _ode_reference(name, n, de, t, x, z, ev, zj, tx=False, oracle=True):
             xf = torch.zeros(tf.shape[0], x.shape[1], x.shape[2])
             xf[0] = x[0]
             return O.integrate_ode(name, C.layers_of(de.x_dot), tf, xf, C.refine_rows(z, n, t, ev, zj), a0, ev, zj)[::n]
-        return C.run_ode(_solver(name, n, "off"), copy.deepcopy(de).double(), _d(t), _d(x), _d(z), _d(a0), _d(ev), _d(zj), tx)
+    return C.ode_walk64(_solver(name, n, "off"), de, t, x, z, ev, zj, tx)
 
 
 def _ode_gpu(name, n, de, t, x, z, ev, zj, tx=False, mode="require", kernel="auto"):
-    xc, zc = _c(x), _c(z)
-    with torch.no_grad():
-        return C.run_ode(_solver(name, n, mode, kernel), copy.deepcopy(de).cuda(), _c(t), xc, zc, torch.cat((xc[0], zc[0]), -1), _c(ev), _c(zj), tx)
+    return C.ode_gpu(_solver(name, n, mode, kernel), de, t, x, z, ev, zj, tx)
 
 
 # ----------------------------------------------------------------------------- ODE forward
@@ -72,7 +58,7 @@ def test_ode_forward(shape, name, n):
     """every form of K0 -- register, streamed, wide register, the eight-layer instances -- with events at steps 0 and 3"""
     xd, zd, hidden = ODE_FWD_SHAPES[shape]
     t = C.dyadic_clock(T0, B0, n)
-    de, x, z, ev, zj = C.ode_problem(xd, zd, hidden, B0, T0, seed=3 + xd + len(hidden) + n, t=t)
+    de, _, x, z, ev, zj = C.ode_case(xd, zd, hidden, B0, T0, seed=3 + xd + len(hidden) + n, t=t, ev_rows=EV)
     out = _ode_gpu(name, n, de, t, x, z, ev, zj)          # fused = "require"
     e = traj_rel_err(out.cpu(), _ode_reference(name, n, de, t, x, z, ev, zj))
     print(shape, name, n, f"{e:.3e}")
@@ -86,8 +72,8 @@ def test_ode_forward_teacher_forced_and_ragged(case, name, n):
     xd, zd, hidden = ODE_FWD_SHAPES["streamed" if n == 3 else "reg"]
     t = C.dyadic_clock(T0, B0, n) * 0.7          # (no longer dyadic: h is a rounded quotient)
     if "ragged" in case:
-        t = _padded(t)
-    de, x, z, ev, zj = C.ode_problem(xd, zd, hidden, B0, T0, seed=40 + n, t=t)
+        t = C.padded(t)
+    de, _, x, z, ev, zj = C.ode_case(xd, zd, hidden, B0, T0, seed=40 + n, t=t, ev_rows=EV)
     tx = "truex" in case
     out = _ode_gpu(name, n, de, t, x, z, ev, zj, tx)
     ref = _ode_reference(name, n, de, t, x, z, ev, zj, tx, oracle=False)
@@ -98,15 +84,15 @@ def test_ode_forward_teacher_forced_and_ragged(case, name, n):
 @pytest.mark.parametrize("B,Tn", [(B0, 1), (B0, 2), (16, T0), (1, T0)])
 def test_ode_forward_short_grids_and_batch_edges(B, Tn, n):
     t = C.dyadic_clock(Tn, B, n)
-    de, x, z, ev, zj = C.ode_problem(8, 2, (64, 64, 64), B, Tn, seed=B + Tn, t=t)
+    de, _, x, z, ev, zj = C.ode_case(8, 2, (64, 64, 64), B, Tn, seed=B + Tn, t=t, ev_rows=EV)
     out = _ode_gpu("rk4", n, de, t, x, z, ev, zj, kernel="generic")
     ref = _ode_reference("rk4", n, de, t, x, z, ev, zj)
     assert out.shape == ref.shape and traj_rel_err(out.cpu(), ref) <= TOL_GPU
 
 
 # ----------------------------------------------------------------------------- DAE forward
-def _dae_reference(name, n, case, t, tx, ti, oracle):
-    de, ae, x, z, v, i, x_init, a0, ev, zj, vj = case
+def _dae_reference(name, n, case, tx, ti, oracle):
+    de, ae, t, x, z, v, i, x_init, a0, ev, zj, vj = case
     with torch.no_grad():
         if oracle and name != "Kutta3" and not (tx or ti):
             tf = C.refine_clock(t, n)
@@ -114,7 +100,7 @@ def _dae_reference(name, n, case, t, tx, ti, oracle):
             rx, ri = O.integrate_dae(name, C.layers_of(de.x_dot), C.layers_of(ae.i_calculator), x_init, tf, xf, C.refine_rows(z, n, t, ev, zj),
                                      C.refine_rows(v, n, t, ev, vj), i_f, a0, ev, zj, vj)
             return rx[::n], ri[::n]
-        return C.run_dae(_solver(name, n, "off"), copy.deepcopy(de).double(), copy.deepcopy(ae).double(), _d(t), *(_d(q) for q in case[2:]), tx, ti)
+    return C.dae_walk64(_solver(name, n, "off"), case, tx, ti)
 
 
 @pytest.mark.parametrize("n", [2, 3])
@@ -124,13 +110,12 @@ def _dae_reference(name, n, case, t, tx, ti, oracle):
 def test_dae_forward(mode, shape, name, n):
     xd, zd, vd, idim, dh, ah = DAE_SHAPES[shape]
     t = C.dyadic_clock(T0, B0, n)
-    case = list(C.dae_problem(xd, zd, vd, idim, dh, ah, B0, T0, seed=17 + xd + n, t=t))
+    case = C.dae_case(xd, zd, vd, idim, dh, ah, B0, T0, seed=17 + xd + n, t=t, ev_rows=EV)
     tx, ti = "tx1" in mode, "ti1" in mode
     if mode == "events_no_x":
-        case[2] = case[2][:, :, :0]          # the dataset x is not read without teacher forcing: what the models pass then
-    with torch.no_grad():
-        out = C.run_dae(_solver(name, n), copy.deepcopy(case[0]).cuda(), copy.deepcopy(case[1]).cuda(), _c(t), *(_c(q) for q in case[2:]), tx, ti)
-    ref = _dae_reference(name, n, case, t, tx, ti, oracle=True)
+        case = C.without_x(case)
+    out = C.dae_gpu(_solver(name, n), case, tx, ti)
+    ref = _dae_reference(name, n, case, tx, ti, oracle=True)
     ex, ei = traj_rel_err(out[0].cpu(), ref[0]), traj_rel_err(out[1].cpu(), ref[1])
     print(mode, shape, name, n, f"{ex:.3e} {ei:.3e}")
     assert out[0].shape == (T0, B0, xd) and out[1].shape == (T0, B0, idim) and ex <= TOL_GPU and ei <= TOL_GPU
@@ -141,7 +126,7 @@ def test_dae_forward(mode, shape, name, n):
 def test_x_sub_rows_are_the_refined_runs_intermediate_rows_ode(n):
     xd, zd, hidden = 8, 2, (64, 64, 64)
     t = C.dyadic_clock(T0, B0, n)
-    de, x, z, ev, zj = C.ode_problem(xd, zd, hidden, B0, T0, seed=60 + n, t=t)
+    de, _, x, z, ev, zj = C.ode_case(xd, zd, hidden, B0, T0, seed=60 + n, t=t, ev_rows=EV)
     a0 = torch.cat((x[0], z[0]), -1)
     tf = C.refine_clock(t, n)
     xf = torch.zeros(tf.shape[0], B0, xd)
@@ -164,7 +149,7 @@ def test_x_sub_rows_are_the_refined_runs_intermediate_rows_ode(n):
 def test_x_sub_rows_are_the_refined_runs_intermediate_rows_dae(n):
     xd, zd, vd, idim, dh, ah = DAE_SHAPES["x5z4v6i6"]
     t = C.dyadic_clock(T0, B0, n)
-    de, ae, x, z, v, i, x_init, a0, ev, zj, vj = C.dae_problem(xd, zd, vd, idim, dh, ah, B0, T0, seed=70 + n, t=t)
+    de, ae, _, x, z, v, i, x_init, a0, ev, zj, vj = C.dae_case(xd, zd, vd, idim, dh, ah, B0, T0, seed=70 + n, t=t, ev_rows=EV)
     tf = C.refine_clock(t, n)
     xf, i_f = torch.zeros(tf.shape[0], B0, xd), torch.zeros(tf.shape[0], B0, idim)
     fine, _ = O.integrate_dae("rk4", C.layers_of(de.x_dot), C.layers_of(ae.i_calculator), x_init, tf, xf, C.refine_rows(z, n, t, ev, zj),
@@ -181,38 +166,13 @@ def test_x_sub_rows_are_the_refined_runs_intermediate_rows_dae(n):
 
 
 # ----------------------------------------------------------------------------- training
-def _ode_train(name, n, de, t, x, z, ev, zj, G, dev, tx=False):
-    dtype = torch.float32 if dev == "cuda" else torch.float64
-    cv = lambda a: None if a is None else a.to(device=dev, dtype=dtype)
-    m = copy.deepcopy(de).to(device=dev, dtype=dtype)
-    xg = cv(x) if tx else cv(x).requires_grad_(True)           # (teacher forcing: the dataset rows get no gradient)
-    zg = cv(z).requires_grad_(True)
-    a0 = torch.cat((cv(x)[0], cv(z)[0]), -1).requires_grad_(True)
-    zjg = cv(zj).requires_grad_(True) if zj is not None else None
-    xs = C.run_ode(_solver(name, n, "require" if dev == "cuda" else "off"), m, cv(t), xg, zg, a0, cv(ev), zjg, tx)
-    (xs * cv(G)).sum().backward()
-    grads = {"z": zg.grad, "a0": a0.grad, "zj": zjg.grad if zjg is not None else None}
-    if not tx:
-        grads["x"] = xg.grad                                    # (x0: the only row of x the integration reads)
-    grads.update({f"p{k}": p.grad for k, p in enumerate(m.parameters())})
-    return xs, grads
+# the file's gate: cotangent G from seed 3 unless given, the fused function ran, helpers.TOL_GPU of each tensor's max
+def _check_ode(name, n, de, t, x, z, ev, zj, tx=False, G=None):
+    G = C.cotangents(3, x.shape)[0] if G is None else G
+    return C.check_ode_training(functools.partial(_solver, name, n), (de, t, x, z, ev, zj), G, "_FusedOdeSub", TOL_GPU, tx, what=f"{name} n={n}")
 
 
-def _check_ode_training(name, n, de, t, x, z, ev, zj, tx=False):
-    G = torch.randn(x.shape, generator=torch.Generator().manual_seed(3))
-    ref_xs, ref = _ode_train(name, n, de, t, x, z, ev, zj, G, "cpu", tx)
-    with warnings.catch_warnings():
-        warnings.simplefilter("error", RuntimeWarning)
-        xs, got = _ode_train(name, n, de, t, x, z, ev, zj, G, "cuda", tx)
-        _, again = _ode_train(name, n, de, t, x, z, ev, zj, G, "cuda", tx)
-    assert type(xs.grad_fn).__name__.startswith("_FusedOdeSub"), xs.grad_fn
-    assert traj_rel_err(xs.detach().cpu(), ref_xs.detach()) <= TOL_GPU
-    for k in ref:
-        _close(got[k], ref[k], f"{name} n={n} grad {k}")
-        assert (got[k] is None and again[k] is None) or torch.equal(got[k], again[k]), f"backward not repeatable: {k}"
-
-
-# K5's paths (tests/test_gpu_rk_tableau.py, K5_ODE_SHAPES): the register path and one of its edges, the streamed path with LDS (hidden 96)
+# K5's paths (tests/generic_cases.py, K5_ODE_SHAPES): the register path and one of its edges, the streamed path with LDS (hidden 96)
 # and with global (hidden 128) accumulators, the staged path (132 input columns)
 SUB_K5_ODE_SHAPES = [(8, 2, 64, 3), (5, 3, 24, 2), (8, 2, 96, 2), (8, 2, 128, 3), (44, 0, 40, 2)]
 
@@ -222,16 +182,16 @@ SUB_K5_ODE_SHAPES = [(8, 2, 64, 3), (5, 3, 24, 2), (8, 2, 96, 2), (8, 2, 128, 3)
 @pytest.mark.parametrize("xd,zd,H,nh", SUB_K5_ODE_SHAPES)
 def test_ode_training(xd, zd, H, nh, name, n):
     t = C.dyadic_clock(T0, B0, n) * 0.7
-    de, x, z, ev, zj = C.ode_problem(xd, zd, (H,) * nh, B0, T0, seed=5 + xd + n, t=t)          # (z_dim 0: no events)
-    _check_ode_training(name, n, de, t, x, z, ev, zj)
+    de, _, x, z, ev, zj = C.ode_case(xd, zd, (H,) * nh, B0, T0, seed=5 + xd + n, t=t, ev_rows=EV)          # (z_dim 0: no events)
+    _check_ode(name, n, de, t, x, z, ev, zj)
 
 
 @pytest.mark.parametrize("n", [2, 3])
 @pytest.mark.parametrize("name", list(SOLVERS))
 def test_ode_training_without_events(name, n):
     t = C.dyadic_clock(T0, B0, n) * 0.7
-    de, x, z, ev, zj = C.ode_problem(8, 2, (64, 64, 64), B0, T0, seed=7 + n, t=t, ev_steps=())
-    _check_ode_training(name, n, de, t, x, z, ev, zj)
+    de, _, x, z, ev, zj = C.ode_case(8, 2, (64, 64, 64), B0, T0, seed=7 + n, t=t, ev_rows=())
+    _check_ode(name, n, de, t, x, z, ev, zj)
 
 
 @pytest.mark.parametrize("n", [2, 3])
@@ -239,39 +199,13 @@ def test_ode_training_without_events(name, n):
 @pytest.mark.parametrize("xd,zd,hidden", [(8, 2, (64, 64, 64)), (20, 3, (96, 96))])
 def test_ode_teacher_forced_training(xd, zd, hidden, name, n):
     t = C.dyadic_clock(T0, B0, n) * 0.7
-    de, x, z, ev, zj = C.ode_problem(xd, zd, hidden, B0, T0, seed=9 + xd + n, t=t)
-    _check_ode_training(name, n, de, t, x, z, ev, zj, tx=True)
+    de, _, x, z, ev, zj = C.ode_case(xd, zd, hidden, B0, T0, seed=9 + xd + n, t=t, ev_rows=EV)
+    _check_ode(name, n, de, t, x, z, ev, zj, tx=True)
 
 
-def _dae_train(name, n, case, t, G, Gi, dev, tx=False, ti=False):
-    dtype = torch.float32 if dev == "cuda" else torch.float64
-    cv = lambda a: None if a is None else a.to(device=dev, dtype=dtype)
-    de, ae, x, z, v, i, x_init, a0, ev, zj, vj = case
-    de, ae = copy.deepcopy(de).to(device=dev, dtype=dtype), copy.deepcopy(ae).to(device=dev, dtype=dtype)
-    leaf = lambda a: None if a is None else cv(a).requires_grad_(True)
-    xi, zg, vg, a0g, zjg, vjg = leaf(x_init), leaf(z), leaf(v), leaf(a0), leaf(zj), leaf(vj)
-    xs, is_ = C.run_dae(_solver(name, n, "require" if dev == "cuda" else "off"), de, ae, cv(t), cv(x), zg, vg, cv(i), xi, a0g, cv(ev), zjg, vjg, tx, ti)
-    ((xs * cv(G)).sum() + (is_ * cv(Gi)).sum()).backward()
-    grads = {"x_init": xi.grad, "z": zg.grad, "v": vg.grad, "a0": a0g.grad, "zj": zjg.grad if zjg is not None else None,
-             "vj": vjg.grad if vjg is not None else None}
-    grads.update({f"de{k}": p.grad for k, p in enumerate(de.parameters())})
-    grads.update({f"ae{k}": p.grad for k, p in enumerate(ae.parameters())})
-    return xs, is_, grads
-
-
-def _check_dae_training(name, n, case, t, tx=False, ti=False):
-    g = torch.Generator().manual_seed(4)
-    G, Gi = torch.randn(case[2].shape, generator=g), torch.randn(case[5].shape, generator=g)
-    rx, ri, ref = _dae_train(name, n, case, t, G, Gi, "cpu", tx, ti)
-    with warnings.catch_warnings():
-        warnings.simplefilter("error", RuntimeWarning)
-        xs, is_, got = _dae_train(name, n, case, t, G, Gi, "cuda", tx, ti)
-        _, _, again = _dae_train(name, n, case, t, G, Gi, "cuda", tx, ti)
-    assert type(xs.grad_fn).__name__.startswith("_FusedDaeSub"), xs.grad_fn
-    assert traj_rel_err(xs.detach().cpu(), rx.detach()) <= TOL_GPU and traj_rel_err(is_.detach().cpu(), ri.detach()) <= TOL_GPU
-    for k in ref:
-        _close(got[k], ref[k], f"{name} n={n} grad {k}")
-        assert (got[k] is None and again[k] is None) or torch.equal(got[k], again[k]), f"backward not repeatable: {k}"
+def _check_dae(name, n, case, tx=False, ti=False):
+    G, Gi = C.cotangents(4, case[3].shape, case[6].shape)
+    C.check_dae_training(functools.partial(_solver, name, n), case, G, Gi, "_FusedDaeSub", TOL_GPU, tx, ti, what=f"{name} n={n}")
 
 
 @pytest.mark.parametrize("n", [2, 3])
@@ -280,14 +214,14 @@ def _check_dae_training(name, n, case, t, tx=False, ti=False):
 def test_dae_training(shape, name, n):
     xd, zd, vd, idim, dh, ah = K5_DAE_SHAPES[shape]
     t = C.dyadic_clock(T0, B0, n) * 0.7
-    _check_dae_training(name, n, C.dae_problem(xd, zd, vd, idim, dh, ah, B0, T0, seed=21 + xd + n, t=t), t)
+    _check_dae(name, n, C.dae_case(xd, zd, vd, idim, dh, ah, B0, T0, seed=21 + xd + n, t=t, ev_rows=EV))
 
 
 @pytest.mark.parametrize("n", [2, 3])
 @pytest.mark.parametrize("name", list(SOLVERS))
 def test_dae_training_without_events(name, n):
     t = C.dyadic_clock(T0, B0, n) * 0.7
-    _check_dae_training(name, n, C.dae_problem(8, 2, 2, 2, (64, 64, 64), (64, 64, 64), B0, T0, seed=25 + n, t=t, ev_steps=()), t)
+    _check_dae(name, n, C.dae_case(8, 2, 2, 2, (64, 64, 64), (64, 64, 64), B0, T0, seed=25 + n, t=t, ev_rows=()))
 
 
 @pytest.mark.parametrize("n", [2, 3])
@@ -295,36 +229,36 @@ def test_dae_training_without_events(name, n):
 @pytest.mark.parametrize("tx,ti", [(True, False), (False, True), (True, True)])
 def test_dae_teacher_forced_training(tx, ti, name, n):
     t = C.dyadic_clock(T0, B0, n) * 0.7
-    _check_dae_training(name, n, C.dae_problem(5, 4, 6, 6, (64, 64, 64), (64, 64, 64), B0, T0, seed=23 + n, t=t), t, tx, ti)
+    _check_dae(name, n, C.dae_case(5, 4, 6, 6, (64, 64, 64), (64, 64, 64), B0, T0, seed=23 + n, t=t, ev_rows=EV), tx, ti)
 
 
 # ----------------------------------------------------------------------------- activations
 @pytest.mark.parametrize("act", [nn.Tanh, nn.SiLU])
 def test_other_activations_ode(act):
     t = C.dyadic_clock(T0, B0, 3) * 0.7
-    de, x, z, ev, zj = C.ode_problem(8, 2, (64, 64, 64), B0, T0, seed=31, t=t, act=act)
+    de, _, x, z, ev, zj = C.ode_case(8, 2, (64, 64, 64), B0, T0, seed=31, t=t, act=act, ev_rows=EV)
     out = _ode_gpu("rk4", 3, de, t, x, z, ev, zj)
     assert traj_rel_err(out.cpu(), _ode_reference("rk4", 3, de, t, x, z, ev, zj, oracle=False)) <= TOL_GPU
-    _check_ode_training("rk4", 3, de, t, x, z, ev, zj)
+    _check_ode("rk4", 3, de, t, x, z, ev, zj)
 
 
 def test_silu_de_tanh_ae_dae():
     t = C.dyadic_clock(T0, B0, 2) * 0.7
-    _check_dae_training("Kutta3", 2, C.dae_problem(4, 2, 1, 2, (48, 48), (32, 32), B0, T0, seed=33, t=t, de_act=nn.SiLU, ae_act=nn.Tanh), t)
+    _check_dae("Kutta3", 2, C.dae_case(4, 2, 1, 2, (48, 48), (32, 32), B0, T0, seed=33, t=t, de_act=nn.SiLU, ae_act=nn.Tanh, ev_rows=EV))
 
 
 def test_teacher_forced_tanh_training_is_not_fusable():
     t = C.dyadic_clock(T0, B0, 2)
-    de, x, z, ev, zj = C.ode_problem(8, 2, (64, 64, 64), B0, T0, seed=43, t=t, act=nn.Tanh)
-    G = torch.randn(x.shape, generator=torch.Generator().manual_seed(3))
+    de, _, x, z, ev, zj = C.ode_case(8, 2, (64, 64, 64), B0, T0, seed=43, t=t, act=nn.Tanh, ev_rows=EV)
+    G, = C.cotangents(3, x.shape)
     with pytest.raises(nd.NotFusableError):
-        _ode_train("rk4", 2, de, t, x, z, ev, zj, G, "cuda", tx=True)
+        C.ode_train(functools.partial(_solver, "rk4", 2), (de, t, x, z, ev, zj), G, "cuda", tx=True)
 
 
 # ----------------------------------------------------------------------------- routing
 def test_kernel_wave_raises_under_require_and_walks_under_auto():
     t = C.dyadic_clock(T0, B0, 2)
-    de, x, z, ev, zj = C.ode_problem(8, 2, (64, 64, 64), B0, T0, seed=41, t=t)
+    de, _, x, z, ev, zj = C.ode_case(8, 2, (64, 64, 64), B0, T0, seed=41, t=t, ev_rows=EV)
     with pytest.raises(_lib.UnsupportedShapeError):
         _ode_gpu("rk4", 2, de, t, x, z, ev, zj, mode="require", kernel="wave")
     with pytest.warns(RuntimeWarning, match="not fusable"):
@@ -365,25 +299,22 @@ def test_direct_encode_model_takes_rows_and_k0():
 def test_substeps_one_is_bitwise_the_route_without_substeps():
     """through the solver, and through the fused entries with substeps=1 spelled out: the same kernels, the same bits"""
     t = C.dyadic_clock(T0, B0, 1) * 0.7
-    de, x, z, ev, zj = C.ode_problem(8, 2, (64, 64, 64), B0, T0, seed=81, t=t)
+    de, _, x, z, ev, zj = C.ode_case(8, 2, (64, 64, 64), B0, T0, seed=81, t=t, ev_rows=EV)
     for name in ("rk4", "Kutta3"):
         a = _ode_gpu(name, 1, de, t, x, z, ev, zj)
         s = SOLVERS[name]()
         s.fused = "require"
-        xc, zc = _c(x), _c(z)
-        with torch.no_grad():
-            b = C.run_ode(s, copy.deepcopy(de).cuda(), _c(t), xc, zc, torch.cat((xc[0], zc[0]), -1), _c(ev), _c(zj))
+        b = C.ode_gpu(s, de, t, x, z, ev, zj)
         assert torch.equal(a, b)
     layers = [(w.cuda(), b.cuda()) for w, b in C.layers_of(de.x_dot)]
     args = ("rk4", layers, _c(t), _c(x[:1]), _c(z), _c(torch.cat((x[0], z[0]), -1)))
     kw = dict(event_t=_c(ev), z_jump=_c(zj), kernel="generic")
     xs, x_sub = fused.ode_integrate(*args, substeps=1, save_sub=True, **kw)
     assert x_sub is None and torch.equal(xs, fused.ode_integrate(*args, **kw))
-    case = C.dae_problem(8, 2, 2, 2, (64, 64, 64), (64, 64, 64), B0, T0, seed=83, t=t)
+    case = C.dae_case(8, 2, 2, 2, (64, 64, 64), (64, 64, 64), B0, T0, seed=83, t=t, ev_rows=EV)
     for name in ("rk4", "Kutta3"):
         outs = []
         for s in (_solver(name, 1), SOLVERS[name]()):
             s.fused = "require"
-            with torch.no_grad():
-                outs.append(C.run_dae(s, copy.deepcopy(case[0]).cuda(), copy.deepcopy(case[1]).cuda(), _c(t), *(_c(q) for q in case[2:])))
+            outs.append(C.dae_gpu(s, case))
         assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])

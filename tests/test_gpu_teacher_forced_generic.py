@@ -3,11 +3,13 @@ every call here runs under solver.fused = "require".  References: the reference'
 this package's walk of the SAME modules in float64 on the CPU with gradients from torch autograd (the method of test_gpu_activations.py).
 Gates: test_grad_goldens.TOL_GPU (1e-5 of each tensor's max) against G8 and across kernels, 2e-4 of the tensor's max against the fp64 walk."""
 import copy
+import functools
 import warnings
 
 import pytest
 import torch
 
+import generic_cases as C
 from helpers import T, load
 from py_psnode_amd import autograd as pag
 from py_psnode_amd import fused, models
@@ -17,6 +19,8 @@ from test_grad_goldens import SOLVERS, TOL_GPU, _close
 pytestmark = pytest.mark.gpu
 
 TOL_WALK = 2e-4     # gradient gate of tests/test_gpu_backward.py / test_gpu_activations.py (max abs error <= TOL x the tensor's max)
+# against the fp64 walk: a gradient the fused run leaves None stands for zeros
+_close_walk = functools.partial(C.close, tol=TOL_WALK, none_is_zero=True)
 METHODS = ["euler", "midpoint", "rk4"]
 P = lambda a: a.permute(1, 0, 2)
 ODE_FLAGS = [(True, False)]
@@ -107,66 +111,17 @@ def _solver(method, fused_mode, kernel="auto"):
     return s
 
 
-def _grid(Tn, B, g, dt=0.01):
-    t = (torch.arange(Tn, dtype=torch.float32) * dt).view(Tn, 1, 1).repeat(1, B, 1)
-    if B > 1:
-        t[:, 1:] = t[:, 1:] * (0.5 + torch.rand(1, B - 1, 1, generator=g))
-    return t
-
-
 def _event_steps(events, Tn):
     return {"none": [], "mid": [Tn // 2], "first": [0], "two": [1, Tn // 2 + 1]}[events]
 
 
 def _ode_case(xd, zd, hidden, B, Tn, seed, events):
-    g = torch.Generator().manual_seed(seed)
-    torch.manual_seed(seed)
-    de = models.DE_Func(xd + zd, hidden, xd)
-    t = _grid(Tn, B, g)
-    x = 0.5 * torch.randn(Tn, B, xd, generator=g)
-    z = 0.5 * torch.randn(Tn, B, zd, generator=g)
-    ev = zj = None
-    steps = _event_steps(events, Tn)
-    if steps:
-        ev = t[steps].permute(1, 0, 2).contiguous()            # [B, nE, 1]: trajectory 0's clock decides
-        zj = 0.5 * torch.randn(B, len(steps), zd, generator=g)
-    return de, t, x, z, ev, zj
+    return C.ode_case(xd, zd, hidden, B, Tn, seed, ev_rows=_event_steps(events, Tn))
 
 
-def _ode_train(method, case, G, dev, dtype, kernel="auto", x_grad=False):
-    de, t, x, z, ev, zj = case
-    cv = lambda a: None if a is None else a.to(device=dev, dtype=dtype, copy=True)
-    m = copy.deepcopy(de).to(device=dev, dtype=dtype)
-    xc, zg = cv(x), cv(z).requires_grad_(True)
-    if x_grad:
-        xc.requires_grad_(True)
-    a0 = torch.cat((cv(x)[0], cv(z)[0]), -1).requires_grad_(True)
-    zjg = cv(zj).requires_grad_(True) if zj is not None else None
-    event = nd.ODE_Event()
-    if ev is not None:
-        event.set_event(cv(ev), zjg)
-    solver = _solver(method, "require" if dev == "cuda" else "off", kernel)
-    xs = solver.integrate_ODE(x_func=m, t=cv(t), x=xc, z=zg, all_initial=a0, event_fn=event.event_fn if ev is not None else None,
-                              jump_change_fn=event.jump_change_fn if ev is not None else None, input_true_x=True)
-    (xs * cv(G)).sum().backward()
-    grads = {"z": zg.grad, "a0": a0.grad, "zj": zjg.grad if zjg is not None else None}
-    grads.update({f"p{k}": p.grad for k, p in enumerate(m.parameters())})
-    return xs, grads
-
-
-def _close_walk(a, b, what):
-    if a is None and b is None:
-        return
-    if b is None:
-        b = torch.zeros(a.shape, dtype=torch.float64)
-    if a is None:
-        a = torch.zeros(b.shape)
-    assert a.shape == b.shape, (what, a.shape, b.shape)
-    if b.numel() == 0:
-        return
-    scale = float(b.abs().max())
-    err = float((a.double().cpu() - b.double().cpu()).abs().max())
-    assert err <= TOL_WALK * max(scale, 1e-6), f"{what}: err {err:.3e} vs scale {scale:.3e}"
+def _train_ode(method, case, G, dev, kernel="auto", x_grad=False):
+    """teacher-forced throughout; the dataset x is a leaf only where a test asks what that raises"""
+    return C.ode_train(functools.partial(_solver, method, kernel=kernel), case, G, dev, tx=True, x_leaf=x_grad, copy=True)
 
 
 ODE_SHAPES = {"x20_h96x2": (20, 3, (96, 96)), "one_hidden": (6, 2, (48,)), "five_hidden": (5, 1, (40, 32, 40, 32, 40)),
@@ -180,59 +135,19 @@ def test_ode_shapes_only_k5_covers(shape, method, events):
     xd, zd, hidden = ODE_SHAPES[shape]
     case = _ode_case(xd, zd, hidden, 19, 9, seed=3 + len(shape), events=events)          # B = 19: not a multiple of 16
     G = torch.randn(case[2].shape, generator=torch.Generator().manual_seed(3))
-    _, ref = _ode_train(method, case, G, "cpu", torch.float64)
+    _, ref = _train_ode(method, case, G, "cpu")
     with warnings.catch_warnings():
         warnings.simplefilter("error", RuntimeWarning)
-        xs, got = _ode_train(method, case, G, "cuda", torch.float32)
-    assert type(xs.grad_fn).__name__.startswith("_FusedOde")
-    for k, r in ref.items():
-        _close_walk(got[k], r, f"{shape} {method} {events} grad {k}")
+        xs, got = _train_ode(method, case, G, "cuda")
+    C.judge_ode_training(ref, got, None, xs, None, "_FusedOde", TOL_WALK, f"{shape} {method} {events}", none_is_zero=True)
 
 
 def _dae_case(xd, zd, vd, idim, de_hidden, ae_hidden, B, Tn, seed, events):
-    g = torch.Generator().manual_seed(seed)
-    torch.manual_seed(seed)
-    n = xd + zd + vd + idim
-    de = models.DAE_DE_Func(n, de_hidden, xd)
-    ae = models.AE_Func(n + xd + zd + vd, ae_hidden, idim)
-    t = _grid(Tn, B, g)
-    x = 0.5 * torch.randn(Tn, B, xd, generator=g)
-    z = 0.5 * torch.randn(Tn, B, zd, generator=g)
-    v = 0.5 * torch.randn(Tn, B, vd, generator=g)
-    i = 0.5 * torch.randn(Tn, B, idim, generator=g)
-    x_init = x[0] + 0.1 * torch.randn(B, xd, generator=g)          # not the dataset row: the two are different inputs of the call
-    a0 = torch.cat((x[0], z[0], v[0], i[0]), -1)
-    ev = zj = vj = None
-    steps = _event_steps(events, Tn)
-    if steps:
-        ev = t[steps].permute(1, 0, 2).contiguous()
-        zj = 0.5 * torch.randn(B, len(steps), zd, generator=g)
-        vj = 0.5 * torch.randn(B, len(steps), vd, generator=g)
-    return de, ae, t, x, z, v, i, x_init, a0, ev, zj, vj
+    return C.dae_case(xd, zd, vd, idim, de_hidden, ae_hidden, B, Tn, seed, ev_rows=_event_steps(events, Tn), perturb_x_init=True)
 
 
-def _dae_train(method, case, G, Hi, tx, ti, dev, dtype, kernel="auto", i_grad=False):
-    de, ae, t, x, z, v, i, x_init, a0, ev, zj, vj = case
-    cv = lambda a: None if a is None else a.to(device=dev, dtype=dtype, copy=True)
-    dm, am = copy.deepcopy(de).to(device=dev, dtype=dtype), copy.deepcopy(ae).to(device=dev, dtype=dtype)
-    xi, zg, vg, a0g = (cv(q).requires_grad_(True) for q in (x_init, z, v, a0))
-    zjg = cv(zj).requires_grad_(True) if zj is not None else None
-    vjg = cv(vj).requires_grad_(True) if vj is not None else None
-    ic = cv(i)
-    if i_grad:
-        ic.requires_grad_(True)
-    event = nd.DAE_Event()
-    if ev is not None:
-        event.set_event(cv(ev), zjg, vjg)
-    solver = _solver(method, "require" if dev == "cuda" else "off", kernel)
-    xs, is_ = solver.integrate_DAE(x_init=xi, x_func=dm, i_func=am, t=cv(t), x=cv(x), z=zg, v=vg, i=ic, all_initial=a0g,
-                                   event_fn=event.event_fn if ev is not None else None,
-                                   jump_change_fn=event.jump_change_fn if ev is not None else None, input_true_x=tx, input_true_i=ti)
-    ((xs * cv(G)).sum() + (is_ * cv(Hi)).sum()).backward()
-    g = {"x_init": xi.grad, "z": zg.grad, "v": vg.grad, "a0": a0g.grad, "zj": zjg.grad if zjg is not None else None,
-         "vj": vjg.grad if vjg is not None else None}
-    g.update({f"de{k}": p.grad for k, p in enumerate(dm.parameters())})
-    g.update({f"ae{k}": p.grad for k, p in enumerate(am.parameters())})
+def _train_dae(method, case, G, Hi, tx, ti, dev, kernel="auto", i_grad=False):
+    xs, _, g = C.dae_train(functools.partial(_solver, method, kernel=kernel), case, G, Hi, dev, tx, ti, i_leaf=i_grad, copy=True)
     return xs, g
 
 
@@ -245,15 +160,12 @@ def _dae_check(shape, method, tx, ti, events, Tn=9, B=19):
     case = _dae_case(xd, zd, vd, idim, dh, ah, B, Tn, seed=5 + len(shape), events=events)
     G = torch.randn(case[3].shape, generator=torch.Generator().manual_seed(6))
     Hi = torch.randn(case[6].shape, generator=torch.Generator().manual_seed(7))
-    _, ref = _dae_train(method, case, G, Hi, tx, ti, "cpu", torch.float64)
+    _, ref = _train_dae(method, case, G, Hi, tx, ti, "cpu")
     with warnings.catch_warnings():
         warnings.simplefilter("error", RuntimeWarning)
-        xs, got = _dae_train(method, case, G, Hi, tx, ti, "cuda", torch.float32)
-    assert type(xs.grad_fn).__name__.startswith("_FusedDaeTeacherForced")
-    for k, r in ref.items():
-        if r is None and got[k] is None:
-            continue
-        _close_walk(got[k], r, f"{shape} {method} tx{int(tx)} ti{int(ti)} {events} grad {k}")
+        xs, got = _train_dae(method, case, G, Hi, tx, ti, "cuda")
+    C.judge_dae_training(ref, got, None, (xs, None), None, "_FusedDaeTeacherForced", TOL_WALK,
+                         f"{shape} {method} tx{int(tx)} ti{int(ti)} {events}", none_is_zero=True)
 
 
 @pytest.mark.parametrize("events", ["none", "mid", "first"])
@@ -273,8 +185,8 @@ def test_two_grid_points(method, tx, ti):
         if tx and not ti:
             case = _ode_case(20, 3, (96, 96), 19, 2, seed=8, events=events)
             G = torch.randn(case[2].shape, generator=torch.Generator().manual_seed(3))
-            _, ref = _ode_train(method, case, G, "cpu", torch.float64)
-            _, got = _ode_train(method, case, G, "cuda", torch.float32)
+            _, ref = _train_ode(method, case, G, "cpu")
+            _, got = _train_ode(method, case, G, "cuda")
             for k, r in ref.items():
                 _close_walk(got[k], r, f"ode T=2 {method} {events} grad {k}")
 
@@ -324,7 +236,7 @@ def test_ode_no_adjoint_travels_from_step_to_step(method):
     case = _ode_case(20, 3, (96, 96), 19, Tn, seed=11, events="none")
     G = torch.zeros(case[2].shape)
     G[k + 1] = torch.randn(G[k + 1].shape, generator=torch.Generator().manual_seed(1))
-    _, got = _ode_train(method, case, G, "cuda", torch.float32)
+    _, got = _train_ode(method, case, G, "cuda")
     gz = got["z"]
     assert float(gz[k].abs().max()) > 0
     assert torch.equal(gz[:k], torch.zeros_like(gz[:k])) and torch.equal(gz[k + 1:], torch.zeros_like(gz[k + 1:]))
@@ -338,7 +250,7 @@ def test_dae_no_adjoint_travels_through_x_without_events(method):
     G = torch.zeros(case[3].shape)
     G[k + 1] = torch.randn(G[k + 1].shape, generator=torch.Generator().manual_seed(1))
     Hi = torch.zeros(case[6].shape)
-    _, got = _dae_train(method, case, G, Hi, True, False, "cuda", torch.float32)
+    _, got = _train_dae(method, case, G, Hi, True, False, "cuda")
     for name in ("z", "v"):
         g = got[name]
         assert float(g[k].abs().max()) > 0, name
@@ -360,8 +272,8 @@ def test_dae_event_head_is_the_one_link_through_x(method, ahead):
     G = torch.zeros(case[3].shape)
     G[e + 1 + ahead] = torch.randn(G[0].shape, generator=torch.Generator().manual_seed(1))
     Hi = torch.zeros(case[6].shape)
-    _, ref = _dae_train(method, case, G, Hi, True, False, "cpu", torch.float64)
-    _, got = _dae_train(method, case, G, Hi, True, False, "cuda", torch.float32)
+    _, ref = _train_dae(method, case, G, Hi, True, False, "cpu")
+    _, got = _train_dae(method, case, G, Hi, True, False, "cuda")
     for k, r in ref.items():
         _close_walk(got[k], r, f"{method} ahead {ahead} grad {k}")
     gz = got["z"]
@@ -382,20 +294,20 @@ def test_true_i_cuts_the_head_from_the_de(method, events):
     case = _dae_case(xd, zd, vd, idim, dh, ah, 19, 9, seed=14, events=events)
     G = torch.zeros(case[3].shape)
     Hi = torch.randn(case[6].shape, generator=torch.Generator().manual_seed(7))
-    _, ref = _dae_train(method, case, G, Hi, True, True, "cpu", torch.float64)
-    _, got = _dae_train(method, case, G, Hi, True, True, "cuda", torch.float32)
+    _, ref = _train_dae(method, case, G, Hi, True, True, "cpu")
+    _, got = _train_dae(method, case, G, Hi, True, True, "cuda")
     for k, g in got.items():
         if k.startswith("de"):
             assert torch.equal(g, torch.zeros_like(g)), k
         elif k.startswith("ae"):
             assert float(g.abs().max()) > 0, k
             _close_walk(g, ref[k], f"{method} {events} grad {k}")
-    _, got0 = _dae_train(method, case, G, torch.zeros_like(Hi), True, True, "cuda", torch.float32)
+    _, got0 = _train_dae(method, case, G, torch.zeros_like(Hi), True, True, "cuda")
     for k, g in got0.items():
         if k.startswith("ae") or k.startswith("de"):
             assert torch.equal(g, torch.zeros_like(g)), k               # no grad_is, no AE gradient: it depends on grad_is alone
-    _, ref1 = _dae_train(method, case, G, Hi, False, True, "cpu", torch.float64)
-    _, got1 = _dae_train(method, case, G, Hi, False, True, "cuda", torch.float32)
+    _, ref1 = _train_dae(method, case, G, Hi, False, True, "cpu")
+    _, got1 = _train_dae(method, case, G, Hi, False, True, "cuda")
     for k, r in ref1.items():
         if r is not None or got1[k] is not None:
             _close_walk(got1[k], r, f"{method} {events} true_i alone grad {k}")
@@ -408,15 +320,15 @@ def test_backward_is_bitwise_repeatable(tx, ti):
     case = _dae_case(xd, zd, vd, idim, dh, ah, 200, 12, seed=15, events="two")
     G = torch.randn(case[3].shape, generator=torch.Generator().manual_seed(6))
     Hi = torch.randn(case[6].shape, generator=torch.Generator().manual_seed(7))
-    _, g1 = _dae_train("rk4", case, G, Hi, tx, ti, "cuda", torch.float32)
-    _, g2 = _dae_train("rk4", case, G, Hi, tx, ti, "cuda", torch.float32)
+    _, g1 = _train_dae("rk4", case, G, Hi, tx, ti, "cuda")
+    _, g2 = _train_dae("rk4", case, G, Hi, tx, ti, "cuda")
     for k in g1:
         assert torch.equal(g1[k], g2[k]), k
     if tx and not ti:
         oc = _ode_case(20, 3, (96, 96), 200, 12, seed=16, events="two")
         Go = torch.randn(oc[2].shape, generator=torch.Generator().manual_seed(5))
-        _, o1 = _ode_train("rk4", oc, Go, "cuda", torch.float32)
-        _, o2 = _ode_train("rk4", oc, Go, "cuda", torch.float32)
+        _, o1 = _train_ode("rk4", oc, Go, "cuda")
+        _, o2 = _train_ode("rk4", oc, Go, "cuda")
         for k in o1:
             assert (o1[k] is None and o2[k] is None) or torch.equal(o1[k], o2[k]), k
 
@@ -427,22 +339,22 @@ def test_x20_teacher_forced_training_runs_under_require():
     case = _ode_case(20, 3, (64, 64, 64), 19, 8, seed=17, events="mid")
     G = torch.randn(case[2].shape, generator=torch.Generator().manual_seed(3))
     for kernel in ("auto", "generic"):
-        xs, got = _ode_train("rk4", case, G, "cuda", torch.float32, kernel=kernel)
+        xs, got = _train_ode("rk4", case, G, "cuda", kernel=kernel)
         assert type(xs.grad_fn).__name__.startswith("_FusedOde") and all(torch.isfinite(g).all() for g in got.values() if g is not None)
     with pytest.raises(nd.NotFusableError):
-        _ode_train("rk4", case, G, "cuda", torch.float32, kernel="mfma")          # no K4f at x_dim 20, and "mfma" excludes K5
+        _train_ode("rk4", case, G, "cuda", kernel="mfma")          # no K4f at x_dim 20, and "mfma" excludes K5
 
 
 def test_dataset_rows_with_grad_still_raise():
     case = _ode_case(20, 3, (64, 64, 64), 19, 8, seed=17, events="none")
     G = torch.randn(case[2].shape, generator=torch.Generator().manual_seed(3))
     with pytest.raises(nd.NotFusableError):
-        _ode_train("rk4", case, G, "cuda", torch.float32, x_grad=True)
+        _train_ode("rk4", case, G, "cuda", x_grad=True)
     xd, zd, vd, idim, dh, ah = DAE_SHAPES["z4_v6_i6"]
     dc = _dae_case(xd, zd, vd, idim, dh, ah, 19, 8, seed=18, events="none")
     Gd, Hi = torch.zeros(dc[3].shape), torch.ones(dc[6].shape)
     with pytest.raises(nd.NotFusableError):
-        _dae_train("rk4", dc, Gd, Hi, False, True, "cuda", torch.float32, i_grad=True)
+        _train_dae("rk4", dc, Gd, Hi, False, True, "cuda", i_grad=True)
 
 
 def test_a_tanh_de_still_raises():
@@ -451,7 +363,7 @@ def test_a_tanh_de_still_raises():
     case = (de,) + _ode_case(20, 3, (64, 64, 64), 19, 8, seed=17, events="none")[1:]
     G = torch.randn(case[2].shape, generator=torch.Generator().manual_seed(3))
     with pytest.raises(nd.NotFusableError):
-        _ode_train("rk4", case, G, "cuda", torch.float32)
+        _train_ode("rk4", case, G, "cuda")
 
 
 # ----------------------------------------------------------------------------- 7. dataset rows at the end of their allocation

@@ -2,6 +2,7 @@
 ExplicitRK against the reference-captured goldens (which pins the tableau formula to the reference itself), the order of accuracy of the
 named methods in fp64, and the additive C ABI (psnode_rk_tableau_f32 and its nine entry points: argument checks from the dims alone)."""
 import ctypes
+import functools
 import math
 
 import pytest
@@ -10,9 +11,11 @@ import torch.nn as nn
 
 from py_psnode_amd import _lib, autograd, fused, models
 from py_psnode_amd import neural_dae as nd
+import capi_args as A
+from capi_args import R
+from capi_args import state_dict_of as _sd
 from helpers import TOL_GPU, T, load, traj_rel_err
 
-R = ctypes.byref
 NAMED = {"Heun2": (nd.Heun2, 2), "Ralston2": (nd.Ralston2, 2), "Kutta3": (nd.Kutta3, 3), "SSPRK3": (nd.SSPRK3, 3), "RK4Classic": (nd.RK4Classic, 4)}
 # the three formulas of the reference (my_fixed_grid.py:12-59) as tableaus
 BUILTIN = {
@@ -85,10 +88,6 @@ def dataclasses_error():
 
 
 # ----------------------------------------------------------------------------- the walk against the reference's goldens
-def _sd(d, prefix):
-    return {k[len(prefix):].replace("__", "."): T(v) for k, v in d.items() if k.startswith(prefix)}
-
-
 @pytest.mark.parametrize("method", list(BUILTIN))
 def test_walk_reproduces_g1_single_step(method):
     d = load("g1_single_step.npz")
@@ -205,56 +204,12 @@ def _tab(name="RK4Classic"):
     return NAMED[name][0]().method.abi()
 
 
-def _mlp3(m, in_dim, hidden, out):
-    m.n_layers, m.in_dim = 4, in_dim
-    for k, o in enumerate((hidden, hidden, hidden, out)):
-        m.out_dim[k] = o
-
-
-def _ode_args(kernel=_lib.KERNEL_AUTO, xd=8, zd=2, hidden=64):
-    a = _lib.OdeArgsF32()
-    a.method, a.kernel, a.x_dim, a.z_dim, a.T, a.B = 77, kernel, xd, zd, 12, 5          # (`method` is not read)
-    _mlp3(a.de, 3 * (xd + zd), hidden, xd)
-    return a
-
-
-def _dae_args(kernel=_lib.KERNEL_AUTO, xd=8, zd=2, vd=2, idim=2, hidden=64):
-    a = _lib.DaeArgsF32()
-    a.method, a.kernel, a.x_dim, a.z_dim, a.v_dim, a.i_dim, a.T, a.B = 77, kernel, xd, zd, vd, idim, 12, 5
-    n = xd + zd + vd + idim
-    _mlp3(a.de, 3 * n, hidden, xd)
-    _mlp3(a.ae, n + xd + zd + vd, hidden, idim)
-    return a
-
-
-def _ode_bwd_args(kernel=_lib.KERNEL_AUTO, xd=8, zd=2, hidden=64, flags=0):
-    a = _lib.OdeBwdArgsF32()
-    a.method, a.kernel, a.x_dim, a.z_dim, a.T, a.B, a.flags = 77, kernel, xd, zd, 12, 5, flags
-    _mlp3(a.de, 3 * (xd + zd), hidden, xd)
-    return a
-
-
-def _dae_bwd_args(kernel=_lib.KERNEL_AUTO, xd=8, zd=2, vd=2, idim=2, hidden=64, flags=0):
-    a = _lib.DaeBwdTfArgsF32()
-    b = a.base
-    b.method, b.kernel, b.x_dim, b.z_dim, b.v_dim, b.i_dim, b.T, b.B = 77, kernel, xd, zd, vd, idim, 12, 5
-    n = xd + zd + vd + idim
-    _mlp3(b.de, 3 * n, hidden, xd)
-    _mlp3(b.ae, n + xd + zd + vd, hidden, idim)
-    a.flags = flags
-    return a
-
-
+# `method` 77: not read next to a tableau
+DIMS = dict(method=77, T=12, B=5)
+_ode_args, _dae_args, _ode_bwd_args, _dae_bwd_args = A.bound(**DIMS)
 # (stem, args builder, number of activations)
 ENTRIES = (("ode_integrate", _ode_args, 1), ("dae_integrate", _dae_args, 2), ("ode_backward", _ode_bwd_args, 1), ("dae_backward", _dae_bwd_args, 2))
-
-
-def _supported(lib, stem, a, n_act, tab, act=None):
-    return getattr(lib, f"psnode_{stem}_rk_supported")(R(a), *([act] * n_act), tab)
-
-
-def _call(lib, stem, a, n_act, tab, act=None):
-    return getattr(lib, f"psnode_{stem}_rk_f32")(R(a) if a is not None else None, *([act] * n_act), tab, None, 0, None)
+_supported, _call = functools.partial(A.supported, family="rk"), functools.partial(A.call, family="rk")
 
 
 def test_symbols_are_exported_and_bound_and_the_abi_version_stays():
@@ -284,7 +239,7 @@ def test_supported_for_the_ode01_class_and_not_on_wave(stem, make, n_act, name):
         assert _call(lib, stem, make(kernel=kernel), n_act, tab) == -5
     tanh = R(fused.Act(_lib.ACT_TANH).abi())
     silu = R(fused.Act(_lib.ACT_SILU).abi())
-    assert _supported(lib, stem, make(), n_act, tab, tanh) == 1 and _supported(lib, stem, make(), n_act, tab, silu) == 1
+    assert _supported(lib, stem, make(), n_act, tab, act=tanh) == 1 and _supported(lib, stem, make(), n_act, tab, act=silu) == 1
 
 
 @pytest.mark.parametrize("stem,make,n_act", ENTRIES)
@@ -314,7 +269,7 @@ def test_tableau_argument_checks(stem, make, n_act):
     assert _call(lib, stem, make(), n_act, R(_tab())) == -1
     unknown = _lib.ActF32()
     unknown.kind = 17
-    assert _call(lib, stem, make(), n_act, R(_tab()), R(unknown)) == -3
+    assert _call(lib, stem, make(), n_act, R(_tab()), act=R(unknown)) == -3
 
 
 def test_side_outputs_and_teacher_forced_activations_are_refused():
@@ -339,7 +294,7 @@ def test_side_outputs_and_teacher_forced_activations_are_refused():
     elu1.kind, elu1.alpha = _lib.ACT_ELU, 1.0
     tfo = _ode_bwd_args(flags=_lib.FLAG_INPUT_TRUE_X)
     assert lib.psnode_ode_backward_rk_supported(R(tfo), None, tab) == 1 and lib.psnode_ode_backward_rk_supported(R(tfo), R(elu1), tab) == 1
-    assert lib.psnode_ode_backward_rk_supported(R(tfo), tanh, tab) == 0 and _call(lib, "ode_backward", tfo, 1, tab, tanh) == -5
+    assert lib.psnode_ode_backward_rk_supported(R(tfo), tanh, tab) == 0 and _call(lib, "ode_backward", tfo, 1, tab, act=tanh) == -5
     for flags in (1, 2, 3):
         tfd = _dae_bwd_args(flags=flags)
         assert lib.psnode_dae_backward_rk_supported(R(tfd), None, None, tab) == 1
@@ -366,17 +321,7 @@ def test_existing_entry_points_keep_their_method_range():
 
 
 # ----------------------------------------------------------------------------- the Python predicates
-class _OnHip(torch.Tensor):
-    """A host tensor that reports a HIP device (the library answers `supported` queries from the dims alone)."""
-
-    @property
-    def device(self):
-        return torch.device("cuda", 0)
-
-
-def _layers(seq):
-    hip = lambda q: torch.Tensor._make_subclass(_OnHip, q.detach())
-    return [(hip(m.weight), hip(m.bias)) for m in seq if isinstance(m, nn.Linear)]
+_layers = A.hip_layers
 
 
 def test_python_predicates_and_refusals():

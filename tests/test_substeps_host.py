@@ -1,28 +1,33 @@
 """Sub-steps per grid interval (solver.substeps), host side (no GPU): the callback walk against the CPU oracle on the n-times refined
-problem (tests/substeps_cases.py), its observed order in the number of sub-steps, teacher forcing, substeps = 1 against the walk as it was
+problem (tests/generic_cases.py), its observed order in the number of sub-steps, teacher forcing, substeps = 1 against the walk as it was
 before sub-steps existed, and the additive C ABI (psnode_substeps_f32 and its nine entry points: argument checks from the dims alone).
 
 The oracle carries the reference's three formulas.  Kutta3 has no oracle form: its yardstick is this package's own one-step-per-interval
 walk on the same refined problem, the walk the oracle pins for the three built-in formulas in this file and the goldens pin elsewhere."""
 import ctypes
+import functools
 import math
 
 import pytest
 import torch
 import torch.nn as nn
 
-import substeps_cases as C
+import capi_args as A
+import generic_cases as C
+from capi_args import R
+from capi_args import state_dict_of as _sd
+from capi_args import sub as _sub
 from helpers import TOL_ORACLE, T, load, rel_err
 from oracle import psnode_oracle as O
 from py_psnode_amd import _lib, autograd, fused, models
 from py_psnode_amd import neural_dae as nd
 
-R = ctypes.byref
 SOLVERS = {"euler": nd.Euler, "midpoint": nd.Midpoint, "rk4": nd.RK4, "Kutta3": nd.Kutta3}
 SUB_EXPORTS = ("psnode_ode_integrate_sub_supported", "psnode_ode_integrate_sub_f32", "psnode_dae_integrate_sub_supported",
                "psnode_dae_integrate_sub_f32", "psnode_ode_backward_sub_supported", "psnode_ode_backward_sub_f32",
                "psnode_dae_backward_sub_supported", "psnode_dae_backward_sub_workspace_bytes", "psnode_dae_backward_sub_f32")
 B0, T0 = 5, 6
+EV = (0, 3)          # the grid rows that carry the events
 
 
 def _solver(name, n=1):
@@ -36,7 +41,7 @@ def _solver(name, n=1):
 @pytest.mark.parametrize("name", list(SOLVERS))
 def test_ode_walk_equals_the_refined_problem(name, n):
     t = C.dyadic_clock(T0, B0, n)
-    de, x, z, ev, zj = C.ode_problem(6, 2, (32, 32), B0, T0, seed=10 + n, t=t)          # events at steps 0 and 3
+    de, _, x, z, ev, zj = C.ode_case(6, 2, (32, 32), B0, T0, seed=10 + n, t=t, ev_rows=EV)          # events at steps 0 and 3
     a0 = torch.cat((x[0], z[0]), -1)
     tf, zf = C.refine_clock(t, n), C.refine_rows(z, n, t, ev, zj)
     xf = torch.zeros(tf.shape[0], B0, 6)
@@ -58,7 +63,7 @@ def test_ode_walk_equals_the_refined_problem(name, n):
 @pytest.mark.parametrize("no_x", [False, True])
 def test_dae_walk_equals_the_refined_problem(name, n, no_x):
     t = C.dyadic_clock(T0, B0, n)
-    de, ae, x, z, v, i, x_init, a0, ev, zj, vj = C.dae_problem(5, 2, 3, 2, (32, 32), (24, 24), B0, T0, seed=20 + n, t=t)
+    de, ae, _, x, z, v, i, x_init, a0, ev, zj, vj = C.dae_case(5, 2, 3, 2, (32, 32), (24, 24), B0, T0, seed=20 + n, t=t, ev_rows=EV)
     if no_x:
         x = x[:, :, :0]                      # the dataset x is not read without teacher forcing: what the models pass then
     tf, zf, vf = C.refine_clock(t, n), C.refine_rows(z, n, t, ev, zj), C.refine_rows(v, n, t, ev, vj)
@@ -119,7 +124,7 @@ def test_observed_order_in_the_number_of_substeps(name, cls, order):
 @pytest.mark.parametrize("n", [2, 3])
 def test_teacher_forced_intervals_start_from_their_dataset_row_only(n):
     t = C.dyadic_clock(T0, B0, n)
-    de, x, z, ev, zj = C.ode_problem(6, 2, (32, 32), B0, T0, seed=31, t=t)
+    de, _, x, z, ev, zj = C.ode_case(6, 2, (32, 32), B0, T0, seed=31, t=t, ev_rows=EV)
     a0 = torch.cat((x[0], z[0]), -1)
     s = _solver("rk4", n)
     with torch.no_grad():
@@ -131,7 +136,7 @@ def test_teacher_forced_intervals_start_from_their_dataset_row_only(n):
         free = C.run_ode(s, de, t, x, z, a0, ev, zj)
     assert not torch.equal(free[2], base[2])
     # DAE: with input_true_x the running state never enters an interval; with input_true_i no head is evaluated inside one
-    de, ae, x, z, v, i, x_init, a0, ev, zj, vj = C.dae_problem(5, 2, 3, 2, (32, 32), (24, 24), B0, T0, seed=33, t=t)
+    de, ae, _, x, z, v, i, x_init, a0, ev, zj, vj = C.dae_case(5, 2, 3, 2, (32, 32), (24, 24), B0, T0, seed=33, t=t, ev_rows=EV)
     calls = []
     hook = ae.register_forward_hook(lambda *_: calls.append(1))          # (a hook keeps the walk: this solver is fused = "off" anyway)
     with torch.no_grad():
@@ -148,45 +153,7 @@ def test_teacher_forced_intervals_start_from_their_dataset_row_only(n):
 
 
 # ----------------------------------------------------------------------------- 4. substeps = 1 is the walk as it was
-def _walk_ode_before(s, x_func, t, x, z, all_initial, event_fn, jump_change_fn, input_true_x):
-    """FixedGridODESolver._walk_ode as it stood before sub-steps (x_init None)."""
-    xs = torch.zeros(x.shape, dtype=x.dtype, device=x.device)
-    cur = x[0]
-    xs[0] = cur
-    for k in range(t.shape[0] - 1):
-        t0, t1, zk = t[k], t[k + 1], z[k]
-        if event_fn is not None and event_fn(t0) == True:  # noqa: E712
-            zk = jump_change_fn(t0, zk)
-        start = x[k] if input_true_x else cur
-        cur, _ = s.step_integrate(func=x_func, t0=t0, dt=t1 - t0, t1=t1, x0=start, z0=zk, all_initial=all_initial)
-        xs[k + 1] = cur
-    return xs
-
-
-def _walk_dae_before(s, x_init, x_func, i_func, t, x, z, v, i, all_initial, event_fn, jump_change_fn, input_true_x, input_true_i):
-    """FixedGridODESolver._walk_dae as it stood before sub-steps."""
-    cur_x = x_init
-    cur_i = i_func(xt=x[0] if input_true_x else cur_x, zt=z[0], vt=v[0], all_initial=all_initial)
-    xs = torch.zeros(x.shape, dtype=x.dtype, device=x.device)
-    is_ = torch.zeros(i.shape, dtype=i.dtype, device=i.device)
-    xs[0], is_[0] = cur_x, cur_i
-    for k in range(t.shape[0] - 1):
-        t0, t1, zk, vk = t[k], t[k + 1], z[k], v[k]
-        if event_fn is not None and event_fn(t0) == True:  # noqa: E712
-            zk, vk = jump_change_fn(t0, zk, vk)
-            cur_i = i_func(xt=cur_x, zt=zk, vt=vk, all_initial=all_initial)
-        start = x[k] if input_true_x else cur_x
-        i_in = i[k] if input_true_i else cur_i
-        cur_x, _ = s.step_integrate(func=x_func, t0=t0, dt=t1 - t0, t1=t1, x0=start, z0=zk, v0=vk, i0=i_in, all_initial=all_initial)
-        cur_i = i_func(xt=x[k + 1] if input_true_x else cur_x, zt=z[k + 1], vt=v[k + 1], all_initial=all_initial)
-        xs[k + 1], is_[k + 1] = cur_x, cur_i
-    return xs, is_
-
-
-def _sd(d, prefix):
-    return {k[len(prefix):].replace("__", "."): T(v) for k, v in d.items() if k.startswith(prefix)}
-
-
+# generic_cases.walk_*_hold with substeps == 1: the walk as it stood before sub-steps existed
 @pytest.mark.parametrize("name", ["euler", "midpoint", "rk4", "Kutta3"])
 def test_substeps_one_is_bitwise_the_walk_as_it_was_g2(name):
     d = load("g2_ode.npz")
@@ -202,7 +169,7 @@ def test_substeps_one_is_bitwise_the_walk_as_it_was_g2(name):
         for clock in (t, tr):
             for tx in (False, True):
                 got = s.integrate_ODE(de, clock, x, z, a0, ev.event_fn, ev.jump_change_fn, input_true_x=tx)
-                assert torch.equal(got, _walk_ode_before(s, de, clock, x, z, a0, ev.event_fn, ev.jump_change_fn, tx))
+                assert torch.equal(got, C.walk_ode_hold(s, de, clock, x, z, a0, ev.event_fn, ev.jump_change_fn, tx))
 
 
 @pytest.mark.parametrize("name", ["euler", "midpoint", "rk4", "Kutta3"])
@@ -221,67 +188,15 @@ def test_substeps_one_is_bitwise_the_walk_as_it_was_g3(name):
         for tx in (False, True):
             for ti in (False, True):
                 got = s.integrate_DAE(xi, de, ae, t, x, z, v, i, a0, ev.event_fn, ev.jump_change_fn, input_true_x=tx, input_true_i=ti)
-                ref = _walk_dae_before(s, xi, de, ae, t, x, z, v, i, a0, ev.event_fn, ev.jump_change_fn, tx, ti)
+                ref = C.walk_dae_hold(s, xi, de, ae, t, x, z, v, i, a0, ev.event_fn, ev.jump_change_fn, tx, ti)
                 assert torch.equal(got[0], ref[0]) and torch.equal(got[1], ref[1]), (tx, ti)
 
 
 # ----------------------------------------------------------------------------- 5. C ABI, dims only; routing; the constructor
-def _mlp3(m, in_dim, hidden, out):
-    m.n_layers, m.in_dim = 4, in_dim
-    for k, o in enumerate((hidden, hidden, hidden, out)):
-        m.out_dim[k] = o
-
-
-def _ode_args(kernel=_lib.KERNEL_AUTO, xd=8, zd=2, hidden=64, method=_lib.RK4_38):
-    a = _lib.OdeArgsF32()
-    a.method, a.kernel, a.x_dim, a.z_dim, a.T, a.B = method, kernel, xd, zd, 12, 5
-    _mlp3(a.de, 3 * (xd + zd), hidden, xd)
-    return a
-
-
-def _dae_args(kernel=_lib.KERNEL_AUTO, xd=8, zd=2, vd=2, idim=2, hidden=64, method=_lib.RK4_38):
-    a = _lib.DaeArgsF32()
-    a.method, a.kernel, a.x_dim, a.z_dim, a.v_dim, a.i_dim, a.T, a.B = method, kernel, xd, zd, vd, idim, 12, 5
-    n = xd + zd + vd + idim
-    _mlp3(a.de, 3 * n, hidden, xd)
-    _mlp3(a.ae, n + xd + zd + vd, hidden, idim)
-    return a
-
-
-def _ode_bwd_args(kernel=_lib.KERNEL_AUTO, xd=8, zd=2, hidden=64, method=_lib.RK4_38, flags=0):
-    a = _lib.OdeBwdArgsF32()
-    a.method, a.kernel, a.x_dim, a.z_dim, a.T, a.B, a.flags = method, kernel, xd, zd, 12, 5, flags
-    _mlp3(a.de, 3 * (xd + zd), hidden, xd)
-    return a
-
-
-def _dae_bwd_args(kernel=_lib.KERNEL_AUTO, xd=8, zd=2, vd=2, idim=2, hidden=64, method=_lib.RK4_38, flags=0):
-    a = _lib.DaeBwdTfArgsF32()
-    b = a.base
-    b.method, b.kernel, b.x_dim, b.z_dim, b.v_dim, b.i_dim, b.T, b.B = method, kernel, xd, zd, vd, idim, 12, 5
-    n = xd + zd + vd + idim
-    _mlp3(b.de, 3 * n, hidden, xd)
-    _mlp3(b.ae, n + xd + zd + vd, hidden, idim)
-    a.flags = flags
-    return a
-
-
+DIMS = dict(method=_lib.RK4_38, T=12, B=5)
+_ode_args, _dae_args, _ode_bwd_args, _dae_bwd_args = A.bound(**DIMS)
 ENTRIES = (("ode_integrate", _ode_args, 1), ("dae_integrate", _dae_args, 2), ("ode_backward", _ode_bwd_args, 1), ("dae_backward", _dae_bwd_args, 2))
-
-
-def _sub(n, x_sub=None):
-    s = _lib.SubstepsF32()
-    s.substeps, s.x_sub = n, x_sub
-    return s
-
-
-def _supported(lib, stem, a, n_act, tab, sub, act=None):
-    return getattr(lib, f"psnode_{stem}_sub_supported")(R(a), *([act] * n_act), tab, R(sub) if sub is not None else None)
-
-
-def _call(lib, stem, a, n_act, tab, sub, act=None):
-    return getattr(lib, f"psnode_{stem}_sub_f32")(R(a) if a is not None else None, *([act] * n_act), tab, R(sub) if sub is not None else None,
-                                                 None, 0, None)
+_supported, _call = functools.partial(A.supported, family="sub"), functools.partial(A.call, family="sub")
 
 
 def test_symbols_are_exported_and_bound_and_the_abi_version_stays():
@@ -379,17 +294,7 @@ def test_side_outputs_teacher_forced_activations_and_a_missing_x_sub_are_refused
     assert _call(lib, "dae_backward", e, 2, None, _sub(2, 256)) == -4
 
 
-class _OnHip(torch.Tensor):
-    """A host tensor that reports a HIP device (the library answers `supported` queries from the dims alone)."""
-
-    @property
-    def device(self):
-        return torch.device("cuda", 0)
-
-
-def _layers(seq):
-    hip = lambda q: torch.Tensor._make_subclass(_OnHip, q.detach())
-    return [(hip(m.weight), hip(m.bias)) for m in seq if isinstance(m, nn.Linear)]
+_layers = A.hip_layers
 
 
 def test_python_predicates_refusals_and_the_constructor():

@@ -4,30 +4,18 @@ the call's dims alone."""
 import ctypes
 
 import pytest
-import torch
-import torch.nn as nn
 
+from capi_args import R, dae_bwd_args, ode_bwd_args
+from capi_args import hip_layers as _layers
 from py_psnode_amd import _lib, autograd, fused, models
 
-R = ctypes.byref
 TF_EXPORTS = ("psnode_dae_backward_tf_supported", "psnode_dae_backward_tf_workspace_bytes", "psnode_dae_backward_tf_f32")
 FLAGS = (_lib.FLAG_INPUT_TRUE_X, _lib.FLAG_INPUT_TRUE_I, _lib.FLAG_INPUT_TRUE_X | _lib.FLAG_INPUT_TRUE_I)
 
 
-def _dae_tf_args(flags, kernel=_lib.KERNEL_AUTO, zd=4, vd=6, idim=6, xd=8, hidden=64):
+def _dae_tf_args(flags, kernel=_lib.KERNEL_AUTO):
     """DAE z4 v6 i6 at hidden 64: a shape without a specialisation (z + v + i > 8)"""
-    a = _lib.DaeBwdTfArgsF32()
-    b = a.base
-    b.method, b.kernel, b.x_dim, b.z_dim, b.v_dim, b.i_dim, b.T, b.B = _lib.RK4_38, kernel, xd, zd, vd, idim, 12, 5
-    n = xd + zd + vd + idim
-    b.de.n_layers, b.de.in_dim = 4, 3 * n
-    b.ae.n_layers, b.ae.in_dim = 4, n + xd + zd + vd
-    for k, o in enumerate((hidden, hidden, hidden, xd)):
-        b.de.out_dim[k] = o
-    for k, o in enumerate((hidden, hidden, hidden, idim)):
-        b.ae.out_dim[k] = o
-    a.flags = flags
-    return a
+    return dae_bwd_args(kernel, xd=8, zd=4, vd=6, idim=6, hidden=64, flags=flags, method=_lib.RK4_38, T=12, B=5)
 
 
 def test_the_three_symbols_are_exported_and_bound():
@@ -113,13 +101,7 @@ def test_ode_entry_point_takes_the_flag_on_k5():
     lib = _lib.load()
 
     def args(xd, kernel):
-        b = _lib.OdeBwdArgsF32()
-        b.method, b.kernel, b.x_dim, b.z_dim, b.T, b.B = _lib.EULER, kernel, xd, 2, 10, 4
-        b.de.n_layers, b.de.in_dim = 4, 3 * (xd + 2)
-        for k, o in enumerate((64, 64, 64, xd)):
-            b.de.out_dim[k] = o
-        b.flags = _lib.FLAG_INPUT_TRUE_X
-        return b
+        return ode_bwd_args(kernel, xd=xd, flags=_lib.FLAG_INPUT_TRUE_X, method=_lib.EULER, T=10, B=4)
 
     buf = (ctypes.c_float * 4096)()
     p = ctypes.addressof(buf)
@@ -143,20 +125,6 @@ def test_ode_entry_point_takes_the_flag_on_k5():
     b = bind(args(20, _lib.KERNEL_AUTO))
     b.saved_act = b.saved_xstage = p
     assert lib.psnode_ode_backward_f32(R(b), wp, lib.psnode_ode_backward_workspace_bytes(R(b)), None) == -5
-
-
-class _OnHip(torch.Tensor):
-    """A host tensor that reports a HIP device: the predicates refuse other devices before they ask the library, and the library's
-    answer to a `supported` query depends on the dims alone (no pointer is followed)."""
-
-    @property
-    def device(self):
-        return torch.device("cuda", 0)
-
-
-def _layers(seq):
-    hip = lambda q: torch.Tensor._make_subclass(_OnHip, q.detach())
-    return [(hip(m.weight), hip(m.bias)) for m in seq if isinstance(m, nn.Linear)]
 
 
 def test_python_predicates():
