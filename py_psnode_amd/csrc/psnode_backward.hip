@@ -13,6 +13,7 @@
 #include <type_traits>
 
 #include "psnode_act.h"
+#include "psnode_launch.h"
 #include "psnode_pack.h"
 
 using namespace psnode;
@@ -46,9 +47,6 @@ bool ptrs_ok(const psnode_dae_bwd_args_f32* a) {
     if ((a->z_dim > 0 && !a->z.ptr) || (a->v_dim > 0 && !a->v.ptr)) return false;
     return !(a->event_idx && ((a->z_dim > 0 && !a->z_jump) || (a->v_dim > 0 && !a->v_jump)));
 }
-bool workspace_ok(const void* workspace, size_t workspace_bytes, size_t need) {
-    return workspace && !(reinterpret_cast<uintptr_t>(workspace) & 255u) && workspace_bytes >= need;
-}
 
 // ---- K5 (psnode_generic_bwd_impl.h): the recipe dims it takes, its call struct, the choice among its three builds
 // pre: K5's builds that keep the pre-activations (their own LDS fit: psnode_generic_bwd_impl.h, pre_floats); lin: the linear-externals build's
@@ -68,12 +66,12 @@ int dae_generic_ok(const psnode_dae_bwd_args_f32* a, bool pre = false, bool lin 
     if (g.in_dim != n + a->x_dim + a->z_dim + a->v_dim || g.out_dim[g.n_layers - 1] != a->i_dim) return 0;
     return generic_bwd_fits(&a->de, &a->ae, a->x_dim, a->z_dim, a->v_dim, a->i_dim, pre, lin);
 }
-ViewDev view(const psnode_view_f32& v) { return ViewDev{v.ptr, v.stride_t, v.stride_b}; }
 GenericBwdCall generic_bwd_call(const psnode_ode_bwd_args_f32& a) {
     GenericBwdCall c{};
     c.method = a.method; c.xd = a.x_dim; c.zd = a.z_dim; c.T = a.T; c.B = a.B; c.de = &a.de;
     c.t = view(a.t); c.z = view(a.z); c.a0 = a.all_initial;
-    c.ev = a.event_idx; c.zj = a.z_jump; c.zjb = a.zj_stride_b; c.zje = a.zj_stride_e; c.n_events = a.n_events;
+    c.ev = a.event_idx; c.n_events = a.n_events;
+    bind_jumps(c, a);
     c.xs = a.xs; c.gxs = a.grad_xs; c.flags = a.flags;
     c.gx0 = a.grad_x0; c.gz = a.grad_z; c.gzj = a.grad_z_jump; c.ga0 = a.grad_all_initial; c.gparams_de = a.grad_params;
     return c;
@@ -82,8 +80,8 @@ GenericBwdCall generic_bwd_call(const psnode_dae_bwd_args_f32& a) {
     GenericBwdCall c{};
     c.method = a.method; c.xd = a.x_dim; c.zd = a.z_dim; c.vd = a.v_dim; c.id = a.i_dim; c.T = a.T; c.B = a.B; c.de = &a.de; c.ae = &a.ae;
     c.t = view(a.t); c.z = view(a.z); c.v = view(a.v); c.a0 = a.all_initial;
-    c.ev = a.event_idx; c.zj = a.z_jump; c.zjb = a.zj_stride_b; c.zje = a.zj_stride_e; c.vj = a.v_jump; c.vjb = a.vj_stride_b;
-    c.vje = a.vj_stride_e; c.n_events = a.n_events;
+    c.ev = a.event_idx; c.n_events = a.n_events;
+    bind_jumps(c, a);
     c.xs = a.xs; c.is_ = a.is; c.gxs = a.grad_xs; c.gis = a.grad_is;
     c.gx0 = a.grad_x_init; c.gz = a.grad_z; c.gv = a.grad_v; c.gzj = a.grad_z_jump; c.gvj = a.grad_v_jump; c.ga0 = a.grad_all_initial;
     c.gparams_de = a.grad_params_de; c.gparams_ae = a.grad_params_ae;

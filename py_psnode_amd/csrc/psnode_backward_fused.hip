@@ -26,6 +26,7 @@
 #include <type_traits>
 #include <string.h>
 
+#include "psnode_launch.h"
 #include "psnode_tile_bwd.h"
 #include "psnode_wide_pack.h"
 
@@ -796,32 +797,11 @@ hipError_t launch_fused(const FusedDev& a, int NZM, const float* pde, const f4* 
     const bool roles = RL && a.sact != nullptr;
     const dim3 grid((unsigned)((a.B + TBM - 1) / TBM)), block(64 * NWV * (roles ? 2 : 1));
     const size_t lds = fused_lds_bytes(NWV, roles);
-#define PSNODE_FUSED(NZM_)                                                                                                      \
-    {                                                                                                                           \
-        auto kern = a.sact ? &ode_backward_fused_kernel<METHOD, NZM_, NWV, false, RL> : &ode_backward_fused_kernel<METHOD, NZM_, NWV, true>; \
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        if (e != hipSuccess) return e;                                                                                          \
-        hipLaunchKernelGGL(kern, grid, block, lds, s, a, pde, pt, pf, NA);                                                      \
-        return hipGetLastError();                                                                                               \
-    }
-    switch (NZM) {
-        case 0: PSNODE_FUSED(0)
-        case 1: PSNODE_FUSED(1)
-        case 2: PSNODE_FUSED(2)
-        case 3: PSNODE_FUSED(3)
-        case 4: PSNODE_FUSED(4)
-        default: return hipErrorNotSupported;
-    }
-#undef PSNODE_FUSED
-}
-
-template <int NWV>
-hipError_t launch_fused_method(const FusedDev& a, int NZM, const float* pde, const f4* pt, const f4* pf, int NA, hipStream_t s) {
-    switch (a.method) {
-        case PSNODE_EULER: return launch_fused<PSNODE_EULER, NWV>(a, NZM, pde, pt, pf, NA, s);
-        case PSNODE_MIDPOINT: return launch_fused<PSNODE_MIDPOINT, NWV>(a, NZM, pde, pt, pf, NA, s);
-        default: return launch_fused<PSNODE_RK4_38, NWV>(a, NZM, pde, pt, pf, NA, s);
-    }
+    return pick<0, 1, 2, 3, 4>(NZM, [&](auto nzm) {
+        constexpr int Z = decltype(nzm)::value;
+        auto kern = a.sact ? &ode_backward_fused_kernel<METHOD, Z, NWV, false, RL> : &ode_backward_fused_kernel<METHOD, Z, NWV, true>;
+        return launch(kern, grid, block, lds, s, a, pde, pt, pf, NA);
+    });
 }
 
 }  // namespace
@@ -867,8 +847,7 @@ int fused_bwd_launch(const psnode_ode_bwd_args_f32* p, float* workspace, hipStre
     memset(&f, 0, sizeof(f));
     f.ae = 0; f.nw = nw; f.xd = xd; f.ne = zd; f.n = n; f.nzv = zd; f.NX = kNXc; f.NB = 0; f.NE = NZM; f.NA = NA; f.fold = 1;
     f.hreal = HR;
-    f.w1 = p->de.weight[0]; f.b1 = p->de.bias[0]; f.w2 = p->de.weight[1]; f.b2 = p->de.bias[1];
-    f.w3 = p->de.weight[2]; f.b3 = p->de.bias[2]; f.w4 = p->de.weight[3]; f.b4 = p->de.bias[3];
+    set_layers(f, p->de);
     f.out_dim = xd; f.out = pde;
     hipLaunchKernelGGL(pack_wide_fwd_kernel, dim3(32), dim3(256), 0, s, f);
     PackWideT t{nw, HR, p->de.weight[1], p->de.weight[2], pt};
@@ -882,23 +861,20 @@ int fused_bwd_launch(const psnode_ode_bwd_args_f32* p, float* workspace, hipStre
     memset(&a, 0, sizeof(a));
     a.method = p->method; a.xd = xd; a.zd = zd; a.hreal = HR; a.n_events = p->n_events; a.NP = NP; a.T = p->T; a.B = p->B;
     a.w1 = p->de.weight[0]; a.w4 = p->de.weight[3];
-    a.t = ViewDev{p->t.ptr, p->t.stride_t, p->t.stride_b};
-    a.z = ViewDev{p->z.ptr, p->z.stride_t, p->z.stride_b};
-    a.a0 = p->all_initial; a.ev = p->event_idx; a.zj = p->z_jump; a.zjb = p->zj_stride_b; a.zje = p->zj_stride_e;
+    a.t = view(p->t); a.z = view(p->z);
+    a.a0 = p->all_initial; a.ev = p->event_idx;
+    bind_jumps(a, *p);
     a.xs = p->xs; a.gout = p->grad_xs; a.gx0 = p->grad_x0; a.gz = p->grad_z; a.gzj = p->grad_z_jump; a.ga0 = p->grad_all_initial;
     a.wpart = wpart; a.ring = ring;
     a.sact = p->saved_act; a.sxst = p->saved_xstage;
     a.true_x = (p->flags & PSNODE_FLAG_INPUT_TRUE_X) ? 1 : 0;
     if (a.true_x && a.sact) return PSNODE_ERR_UNSUPPORTED;     // a teacher-forced forward saves nothing: recompute form only
-    hipError_t e;
-    switch (nw) {
-        case 2: e = launch_fused_method<2>(a, NZM, pde, pt, pf, NA, s); break;
-        case 4: e = launch_fused_method<4>(a, NZM, pde, pt, pf, NA, s); break;
-        default: e = launch_fused_method<8>(a, NZM, pde, pt, pf, NA, s); break;
-    }
+    const hipError_t e = with_method(a.method, [&](auto m) {
+        return pick<2, 4, 8>(nw, [&](auto w) { return launch_fused<decltype(m)::value, decltype(w)::value>(a, NZM, pde, pt, pf, NA, s); });
+    });
     if (e == hipErrorNotSupported) return PSNODE_ERR_UNSUPPORTED;
     if (e != hipSuccess) return PSNODE_ERR_HIP;
-    return launch_reduce_partials(wpart, p->grad_params, nullptr, NP, 0, (int)nwg, s) == hipSuccess ? PSNODE_OK : PSNODE_ERR_HIP;
+    return ok_or_hip(launch_reduce_partials(wpart, p->grad_params, nullptr, NP, 0, (int)nwg, s));
 }
 
 }  // namespace psnode

@@ -524,27 +524,21 @@ int bwd_x_launch(const psnode_ode_bwd_args_f32* p, float* workspace, hipStream_t
     BwdXDev a;
     memset(&a, 0, sizeof(a));
     a.xd = xd; a.zd = zd; a.hreal = HR; a.n_events = p->n_events; a.T = p->T; a.B = p->B;
-    a.t = ViewDev{p->t.ptr, p->t.stride_t, p->t.stride_b};
-    a.z = ViewDev{p->z.ptr, p->z.stride_t, p->z.stride_b};
-    a.a0 = p->all_initial; a.ev = p->event_idx; a.zj = p->z_jump; a.zjb = p->zj_stride_b; a.zje = p->zj_stride_e;
+    a.t = view(p->t); a.z = view(p->z);
+    a.a0 = p->all_initial; a.ev = p->event_idx;
+    bind_jumps(a, *p);
     a.gout = p->grad_xs; a.gx0 = p->grad_x0; a.gz = p->grad_z; a.gzj = p->grad_z_jump; a.ga0 = p->grad_all_initial;
     a.wpart = wpart; a.sact = p->saved_act; a.sxst = p->saved_xstage;
     const bool gz = zd > 0 && (a.gz || a.gzj);
     const dim3 grid((unsigned)((tiles + kXWaves - 1) / kXWaves)), block(64 * kXWaves);
-#define PSNODE_BX(M_)                                                                                   \
-    if (gz) hipLaunchKernelGGL((ode_backward_x_kernel<M_, true>), grid, block, 0, s, a, pack);          \
-    else hipLaunchKernelGGL((ode_backward_x_kernel<M_, false>), grid, block, 0, s, a, pack);
-    switch (p->method) {
-        case PSNODE_EULER: PSNODE_BX(PSNODE_EULER) break;
-        case PSNODE_MIDPOINT: PSNODE_BX(PSNODE_MIDPOINT) break;
-        default: PSNODE_BX(PSNODE_RK4_38) break;
-    }
-#undef PSNODE_BX
-    if (hipGetLastError() != hipSuccess) return PSNODE_ERR_HIP;
+    const hipError_t e = with_method(p->method, [&](auto m) {
+        return with_flag(gz, [&](auto g) { return launch(&ode_backward_x_kernel<decltype(m)::value, decltype(g)::value>, grid, block, 0, s, a, pack); });
+    });
+    if (e != hipSuccess) return PSNODE_ERR_HIP;
     if (launch_reduce_partials(wpart, red, nullptr, BXPart::COUNT * 64, 0, (int)tiles, s) != hipSuccess) return PSNODE_ERR_HIP;
     const int NP = HR * 3 * n + HR + 2 * (HR * HR + HR) + xd * HR + xd;
     hipLaunchKernelGGL(scatter_bx_kernel, dim3((NP + 255) / 256), dim3(256), 0, s, red, p->grad_params, HR, xd, n);
-    return hipGetLastError() == hipSuccess ? PSNODE_OK : PSNODE_ERR_HIP;
+    return ok_or_hip(hipGetLastError());
 }
 
 }  // namespace psnode

@@ -5,6 +5,7 @@
 #include <string.h>
 
 #include "psnode_act.h"
+#include "psnode_launch.h"
 
 namespace psnode {
 namespace {
@@ -28,24 +29,20 @@ int check_mlp_dims(const psnode_mlp_f32& m, int want_in, int want_out, bool ptrs
 }
 int check_mlp(const psnode_mlp_f32& m, int want_in, int want_out) { return check_mlp_dims(m, want_in, want_out, true); }
 
-// Fills `d` and takes the MLP's image segments (K0's MFMA images, one per layer).
-void bind_mlp(const psnode_mlp_f32& m, MlpDev& d, Arena& A) {
-    d.n_layers = m.n_layers;
-    d.in_dim = m.in_dim;
-    int k = m.in_dim;
-    for (int l = 0; l < m.n_layers; ++l) {
-        d.out_dim[l] = m.out_dim[l];
-        d.w[l] = m.weight[l];
-        d.bias[l] = m.bias[l];
-        d.wt[l] = A.take(round_up(generic_image_floats(k, m.out_dim[l]), kAlignFloats));
-        k = m.out_dim[l];
+// takes the MLP's image segments (K0's MFMA images, one per layer)
+void take_images(MlpDev& d, Arena& A) {
+    int k = d.in_dim;
+    for (int l = 0; l < d.n_layers; ++l) {
+        d.wt[l] = A.take(round_up(generic_image_floats(k, d.out_dim[l]), kAlignFloats));
+        k = d.out_dim[l];
     }
 }
 // The forward workspace: K0's images of the DE | of the AE | the pack of the MFMA family that takes the shape (sized for the largest of
 // them: psnode_mfma.hip).  Returns the pack.
 float* forward_layout(const psnode_mlp_f32& de, const psnode_mlp_f32* ae, MlpDev& dde, MlpDev& dae, Arena& A) {
-    bind_mlp(de, dde, A);
-    if (ae) bind_mlp(*ae, dae, A);
+    bind_mlp(de, dde);
+    take_images(dde, A);
+    if (ae) { bind_mlp(*ae, dae); take_images(dae, A); }
     float* pack = A.take(mfma_pack_floats(&de, ae));
     A.slack(kAlignFloats);      // kept from the parent, purpose not established (every segment in front of it is a multiple of 64 floats)
     return pack;
@@ -80,8 +77,6 @@ __global__ void event_table_kernel(long long n_steps, const float* clock, long l
     if (cnt > 1 && dup_flag) *dup_flag = 1;
 }
 
-ViewDev view(const psnode_view_f32& v) { return ViewDev{v.ptr, v.stride_t, v.stride_b}; }
-
 // What a K0 call carries beyond its args: the build of the generic kernel that runs it (psnode_generic_build.h) and that build's kernel
 // arguments.  The plain entry points pass K0Call{}: ELU(1), the args' method, one step per interval -- the only call the MFMA kernels take.
 struct K0Call {
@@ -93,8 +88,7 @@ struct K0Call {
 
 int dispatch(IntegrateDev& d, bool dae, int kernel, const psnode_mlp_f32* de, const psnode_mlp_f32* ae, void* workspace,
              size_t workspace_bytes, hipStream_t stream, const K0Call& call) {
-    if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 255u)) return PSNODE_ERR_WORKSPACE;
-    if (workspace_bytes < psnode_workspace_bytes(de, ae)) return PSNODE_ERR_WORKSPACE;
+    if (!workspace_ok(workspace, workspace_bytes, psnode_workspace_bytes(de, ae))) return PSNODE_ERR_WORKSPACE;
     Arena A{static_cast<float*>(workspace)};
     float* pack = forward_layout(*de, dae ? ae : nullptr, d.de, d.ae, A);
     d.maxw = max_width(*de);
@@ -108,7 +102,7 @@ int dispatch(IntegrateDev& d, bool dae, int kernel, const psnode_mlp_f32* de, co
     d.kern = kernel;
     const bool use_mfma = has_mfma && kernel != PSNODE_KERNEL_GENERIC;
     if (d.T < 1 || d.B < 1) return PSNODE_ERR_DIMS;
-    if (use_mfma) return launch_mfma(d, dae, pack, stream) == hipSuccess ? PSNODE_OK : PSNODE_ERR_HIP;
+    if (use_mfma) return ok_or_hip(launch_mfma(d, dae, pack, stream));
 
     if (generic_lds_bytes(d, dae, call.build == K0Call::kLin) > 160 * 1024) return PSNODE_ERR_UNSUPPORTED;
     hipError_t e = launch_pack_image(d.de, dae ? &d.ae : nullptr, d.xd, d.xd + d.zd + (dae ? d.vd + d.id : 0), d.zd + (dae ? d.vd : 0), stream);
@@ -120,16 +114,11 @@ int dispatch(IntegrateDev& d, bool dae, int kernel, const psnode_mlp_f32* de, co
         case K0Call::kSub: e = launch_generic_sub(d, dae, call.act, call.rk, call.sub, stream); break;
         case K0Call::kLin: e = launch_generic_lin(d, dae, call.act, call.rk, call.sub, stream); break;
     }
-    return e == hipSuccess ? PSNODE_OK : PSNODE_ERR_HIP;
+    return ok_or_hip(e);
 }
 
 // dims-only view of the args: what the *_save_hidden / *_kernel_for / *_act_supported queries ask the kernel families with (no pointers),
 // and what fill_ode / fill_dae start from
-void bind_dims(const psnode_mlp_f32& m, MlpDev& d) {
-    d.n_layers = m.n_layers;
-    d.in_dim = m.in_dim;
-    for (int l = 0; l < m.n_layers && l < kMaxLayers; ++l) d.out_dim[l] = m.out_dim[l];
-}
 IntegrateDev dims_only(const psnode_ode_args_f32& a) {
     IntegrateDev d;
     memset(&d, 0, sizeof(d));
@@ -165,9 +154,7 @@ int fill_ode(const psnode_ode_args_f32* a, IntegrateDev& d) {
     d.z = view(a->z);
     d.a0 = a->all_initial;
     d.ev = a->event_idx;
-    d.zj = a->z_jump;
-    d.zjb = a->zj_stride_b;
-    d.zje = a->zj_stride_e;
+    bind_jumps(d, *a);
     d.xo = a->x_out;
     if ((a->save_act != nullptr) != (a->save_xstage != nullptr)) return PSNODE_ERR_NULL;
     d.sact = a->save_act;
@@ -199,12 +186,7 @@ int fill_dae(const psnode_dae_args_f32* a, IntegrateDev& d) {
     d.x_init = a->x_init;
     d.a0 = a->all_initial;
     d.ev = a->event_idx;
-    d.zj = a->z_jump;
-    d.zjb = a->zj_stride_b;
-    d.zje = a->zj_stride_e;
-    d.vj = a->v_jump;
-    d.vjb = a->vj_stride_b;
-    d.vje = a->vj_stride_e;
+    bind_jumps(d, *a);
     d.xo = a->x_out;
     d.io = a->i_out;
     const bool sv = a->save_act != nullptr;
@@ -378,8 +360,6 @@ extern "C" {
 
 int32_t psnode_abi_version(void) { return PSNODE_ABI_VERSION; }
 
-#define PSNODE_STR2(x) #x
-#define PSNODE_STR(x) PSNODE_STR2(x)
 const char* psnode_build_info(void) { return "psnode_hip abi " PSNODE_STR(PSNODE_ABI_VERSION) " gfx950 (generic + mfma kernels), built " __DATE__; }
 
 const char* psnode_status_string(int32_t s) {
@@ -410,7 +390,7 @@ int32_t psnode_event_table_f32(int64_t n_steps, const float* clock, int64_t stri
     const unsigned grid = (unsigned)((n_steps + 255) / 256);
     hipLaunchKernelGGL(event_table_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), (long long)n_steps, clock,
                        (long long)stride_k, event_times, (long long)stride_e, (int)n_events, event_idx, dup_flag);
-    return hipGetLastError() == hipSuccess ? PSNODE_OK : PSNODE_ERR_HIP;
+    return ok_or_hip(hipGetLastError());
 }
 
 int32_t psnode_ode_save_hidden(const psnode_ode_args_f32* a) {

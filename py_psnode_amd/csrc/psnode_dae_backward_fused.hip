@@ -16,6 +16,7 @@
 #include <string.h>
 #include <type_traits>
 
+#include "psnode_launch.h"
 #include "psnode_tile_bwd.h"
 #include "psnode_wide_pack.h"
 
@@ -1252,34 +1253,11 @@ hipError_t launch_k7f(const FusedDaeDev& a, int NZM, int NZA, const float* pde, 
     const bool roles = RL && a.sact != nullptr;
     const dim3 grid((unsigned)((a.B + TBM - 1) / TBM)), block(64 * NWV * (roles ? 2 : 1));
     const size_t lds = k7f_lds_bytes(NWV, roles);
-#define PSNODE_K7F(NZM_, NZA_)                                                                                                  \
-    {                                                                                                                           \
-        auto kern = a.sact ? &dae_backward_fused_kernel<METHOD, NZM_, NZA_, NWV, false, RL> : &dae_backward_fused_kernel<METHOD, NZM_, NZA_, NWV, true>; \
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        if (e != hipSuccess) return e;                                                                                          \
-        hipLaunchKernelGGL(kern, grid, block, lds, s, a, pde, pae, pt, pf, pta, pfa, NA);                                       \
-        return hipGetLastError();                                                                                               \
-    }
-    switch (NZM * 10 + NZA) {
-        case 11: PSNODE_K7F(1, 1)
-        case 21: PSNODE_K7F(2, 1)
-        case 31: PSNODE_K7F(3, 1)
-        case 41: PSNODE_K7F(4, 1)
-        case 32: PSNODE_K7F(3, 2)
-        case 42: PSNODE_K7F(4, 2)
-        default: return hipErrorNotSupported;
-    }
-#undef PSNODE_K7F
-}
-
-template <int NWV>
-hipError_t launch_k7f_method(const FusedDaeDev& a, int NZM, int NZA, const float* pde, const float* pae, const f4* pt, const f4* pf,
-                             const f4* pta, const f4* pfa, int NA, hipStream_t s) {
-    switch (a.method) {
-        case PSNODE_EULER: return launch_k7f<PSNODE_EULER, NWV>(a, NZM, NZA, pde, pae, pt, pf, pta, pfa, NA, s);
-        case PSNODE_MIDPOINT: return launch_k7f<PSNODE_MIDPOINT, NWV>(a, NZM, NZA, pde, pae, pt, pf, pta, pfa, NA, s);
-        default: return launch_k7f<PSNODE_RK4_38, NWV>(a, NZM, NZA, pde, pae, pt, pf, pta, pfa, NA, s);
-    }
+    return pick<11, 21, 31, 41, 32, 42>(NZM * 10 + NZA, [&](auto pair) {
+        constexpr int ZM = decltype(pair)::value / 10, ZA = decltype(pair)::value % 10;
+        auto kern = a.sact ? &dae_backward_fused_kernel<METHOD, ZM, ZA, NWV, false, RL> : &dae_backward_fused_kernel<METHOD, ZM, ZA, NWV, true>;
+        return launch(kern, grid, block, lds, s, a, pde, pae, pt, pf, pta, pfa, NA);
+    });
 }
 
 }  // namespace
@@ -1318,15 +1296,10 @@ int dae_fused_bwd_launch(const psnode_dae_bwd_wide_args_f32* p, float* workspace
     memset(&f, 0, sizeof(f));
     f.ae = 0; f.nw = nw; f.xd = xd; f.ne = ne; f.n = n; f.nzv = nzv; f.NX = kNXc; f.NB = 0; f.NE = NZM; f.NA = NA; f.fold = 1;
     f.hreal = HR;
-    f.w1 = p->de.weight[0]; f.b1 = p->de.bias[0]; f.w2 = p->de.weight[1]; f.b2 = p->de.bias[1];
-    f.w3 = p->de.weight[2]; f.b3 = p->de.bias[2]; f.w4 = p->de.weight[3]; f.b4 = p->de.bias[3];
+    set_layers(f, p->de);
     f.out_dim = xd; f.out = pde;
     hipLaunchKernelGGL(pack_wide_fwd_kernel, dim3(32), dim3(256), 0, s, f);
-    PackMfma q = f;
-    q.ae = 1; q.NE = NZA; q.fold = 0;
-    q.w1 = p->ae.weight[0]; q.b1 = p->ae.bias[0]; q.w2 = p->ae.weight[1]; q.b2 = p->ae.bias[1];
-    q.w3 = p->ae.weight[2]; q.b3 = p->ae.bias[2]; q.w4 = p->ae.weight[3]; q.b4 = p->ae.bias[3];
-    q.out_dim = id; q.out = pae;
+    const PackMfma q = ae_pack(f, NZA, p->ae, id, pae);
     hipLaunchKernelGGL(pack_wide_fwd_kernel, dim3(32), dim3(256), 0, s, q);
     PackWideT t{nw, HR, p->de.weight[1], p->de.weight[2], pt};
     hipLaunchKernelGGL(pack_wide_t_kernel, dim3(64), dim3(256), 0, s, t);
@@ -1343,12 +1316,9 @@ int dae_fused_bwd_launch(const psnode_dae_bwd_wide_args_f32* p, float* workspace
     memset(&a, 0, sizeof(a));
     a.method = p->method; a.xd = xd; a.zd = zd; a.vd = vd; a.id = id; a.hreal = HR; a.n_events = p->n_events; a.NP = NP; a.T = p->T; a.B = p->B;
     a.w1 = p->de.weight[0]; a.w4 = p->de.weight[3]; a.aw1 = p->ae.weight[0]; a.aw4 = p->ae.weight[3];
-    a.t = ViewDev{p->t.ptr, p->t.stride_t, p->t.stride_b};
-    a.z = ViewDev{p->z.ptr, p->z.stride_t, p->z.stride_b};
-    a.v = ViewDev{p->v.ptr, p->v.stride_t, p->v.stride_b};
+    a.t = view(p->t); a.z = view(p->z); a.v = view(p->v);
     a.a0 = p->all_initial; a.ev = p->event_idx;
-    a.zj = p->z_jump; a.zjb = p->zj_stride_b; a.zje = p->zj_stride_e;
-    a.vj = p->v_jump; a.vjb = p->vj_stride_b; a.vje = p->vj_stride_e;
+    bind_jumps(a, *p);
     a.xs = p->xs; a.is = p->is; a.gxs = p->grad_xs; a.gis = p->grad_is;
     a.tx = (p->flags & PSNODE_FLAG_INPUT_TRUE_X) ? 1 : 0; a.ti = (p->flags & PSNODE_FLAG_INPUT_TRUE_I) ? 1 : 0;
     a.xtrue = p->x_true; a.itrue = p->i_true;
@@ -1363,12 +1333,11 @@ int dae_fused_bwd_launch(const psnode_dae_bwd_wide_args_f32* p, float* workspace
     }
     a.agi = p->ae_gi; a.egi = p->ev_gi; a.ei = p->ev_i;
     a.sact = p->saved_act; a.sxst = p->saved_xstage; a.saeact = p->saved_ae_act; a.sevact = p->saved_ev_act; a.sevi = p->saved_ev_i;
-    hipError_t e;
-    switch (nw) {
-        case 2: e = launch_k7f_method<2>(a, NZM, NZA, pde, pae, pt, pf, pta, pfa, NA, s); break;
-        case 4: e = launch_k7f_method<4>(a, NZM, NZA, pde, pae, pt, pf, pta, pfa, NA, s); break;
-        default: e = launch_k7f_method<8>(a, NZM, NZA, pde, pae, pt, pf, pta, pfa, NA, s); break;
-    }
+    const hipError_t e = with_method(a.method, [&](auto m) {
+        return pick<2, 4, 8>(nw, [&](auto w) {
+            return launch_k7f<decltype(m)::value, decltype(w)::value>(a, NZM, NZA, pde, pae, pt, pf, pta, pfa, NA, s);
+        });
+    });
     if (e == hipErrorNotSupported) return PSNODE_ERR_UNSUPPORTED;
     if (e != hipSuccess) return PSNODE_ERR_HIP;
     if (launch_reduce_partials(wpart, p->grad_params_de, nullptr, NP, 0, (int)nwg, s) != hipSuccess) return PSNODE_ERR_HIP;

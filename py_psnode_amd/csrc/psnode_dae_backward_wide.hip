@@ -6,6 +6,7 @@
 // profiles/scripts/variants/k7w_dae_backward_split.hip.txt keeps its source.
 #include <string.h>
 
+#include "psnode_launch.h"
 #include "psnode_pack.h"
 
 using namespace psnode;
@@ -58,8 +59,7 @@ int32_t psnode_dae_backward_wide_f32(const psnode_dae_bwd_wide_args_f32* p, void
         if (!ae_in_kernel && !p->ev_gi) return PSNODE_ERR_NULL;
         for (int l = 0; l < 3; ++l) if (!p->ev_act[l] || (!ae_in_kernel && !p->ev_delta[l])) return PSNODE_ERR_NULL;
     }
-    if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 255u) || workspace_bytes < psnode_dae_backward_wide_workspace_bytes(p))
-        return PSNODE_ERR_WORKSPACE;
+    if (!workspace_ok(workspace, workspace_bytes, psnode_dae_backward_wide_workspace_bytes(p))) return PSNODE_ERR_WORKSPACE;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int H = wide_hidden(p->de), zd = p->z_dim, vd = p->v_dim;
     {   // per-lane offsets inside a row are 32-bit byte offsets next to a scalar row base

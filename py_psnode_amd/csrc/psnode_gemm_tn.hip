@@ -11,7 +11,7 @@
 // (a 16-element column set with stride 4 -- any partition of the columns into sets of 16 is a valid tiling; this one needs no shuffle).
 // A workgroup = 4 waves over the same rows: every wave loads all of A (<= 2 float4) and its own quarter of B's tiles, and owns the
 // (<= 8) x (<= 2) tiles of C between them: <= 16 accumulators of 4 registers.
-#include "psnode_common.h"
+#include "psnode_launch.h"
 
 namespace psnode {
 namespace {
@@ -179,7 +179,7 @@ extern "C" int32_t psnode_gemm_tn_f32(const psnode_gemm_tn_args_f32* a, void* wo
     if (!a) return PSNODE_ERR_NULL;
     if (!psnode_gemm_tn_supported(a)) return PSNODE_ERR_UNSUPPORTED;
     if (!a->A || !a->B || !a->C) return PSNODE_ERR_NULL;
-    if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 255u) || workspace_bytes < psnode_gemm_tn_workspace_bytes(a)) return PSNODE_ERR_WORKSPACE;
+    if (!workspace_ok(workspace, workspace_bytes, psnode_gemm_tn_workspace_bytes(a))) return PSNODE_ERR_WORKSPACE;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const long long nwg = tn_workgroups(a->rows);
     GemmTnDev d;
@@ -195,5 +195,5 @@ extern "C" int32_t psnode_gemm_tn_f32(const psnode_gemm_tn_args_f32* a, void* wo
     if (hipGetLastError() != hipSuccess) return PSNODE_ERR_HIP;
     // the column sums ride behind C in every partial vector; a caller that does not want them gets them into the tail of the workspace
     float* cs = a->colsum_a ? a->colsum_a : d.part + (size_t)nwg * ((size_t)a->M * a->N + a->M);
-    return launch_reduce_partials(d.part, a->C, cs, a->M * a->N, a->M, (int)nwg, s) == hipSuccess ? PSNODE_OK : PSNODE_ERR_HIP;
+    return ok_or_hip(launch_reduce_partials(d.part, a->C, cs, a->M * a->N, a->M, (int)nwg, s));
 }

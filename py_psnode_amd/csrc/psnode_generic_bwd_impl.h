@@ -33,7 +33,7 @@
 // `if constexpr` in the kernel body and the launcher.  The host's fit and layout functions take `pre` at run time.
 #pragma once
 #include "psnode_act.h"
-#include "psnode_common.h"
+#include "psnode_launch.h"
 
 namespace psnode {
 namespace {
@@ -842,15 +842,15 @@ int generic_backward_launch(const GenericBwdCall& c, const ActPair* act, float* 
     else if (a.de_reg) kern = g == 1 ? K::template get<true, true, true, 0>() : (g == 2 ? K::template get<false, true, true, 0>() : K::template get<false, true, false, 0>());
     else if (a.str == 2) kern = g == 1 ? K::template get<true, false, true, 2>() : (g == 2 ? K::template get<false, false, true, 2>() : K::template get<false, false, false, 2>());
     else kern = g ? K::template get<true, false, true, 0>() : K::template get<false, false, false, 0>();
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return PSNODE_ERR_HIP;
     const unsigned nwg = (unsigned)((B + TB - 1) / TB);
-    if constexpr (Pol::sub) hipLaunchKernelGGL(kern, dim3(nwg), dim3(NT), lds, stream, a, *act, *c.rk, SubDev{c.substeps, const_cast<float*>(c.x_sub)});
-    else if constexpr (Pol::rk) hipLaunchKernelGGL(kern, dim3(nwg), dim3(NT), lds, stream, a, *act, *c.rk);
-    else if constexpr (Pol::act) hipLaunchKernelGGL(kern, dim3(nwg), dim3(NT), lds, stream, a, *act);
-    else hipLaunchKernelGGL(kern, dim3(nwg), dim3(NT), lds, stream, a);
-    if (hipGetLastError() != hipSuccess) return PSNODE_ERR_HIP;
-    return launch_reduce_partials(a.wpart, c.gparams_de, c.gparams_ae, a.de.np, dae ? a.ae.np : 0, (int)nwg, stream) == hipSuccess ? PSNODE_OK : PSNODE_ERR_HIP;
+    auto go = [&](const auto&... extra) { return launch_attr(true, kern, dim3(nwg), dim3(NT), lds, stream, a, extra...); };
+    hipError_t e;
+    if constexpr (Pol::sub) e = go(*act, *c.rk, SubDev{c.substeps, const_cast<float*>(c.x_sub)});
+    else if constexpr (Pol::rk) e = go(*act, *c.rk);
+    else if constexpr (Pol::act) e = go(*act);
+    else e = go();
+    if (e != hipSuccess) return PSNODE_ERR_HIP;
+    return ok_or_hip(launch_reduce_partials(a.wpart, c.gparams_de, c.gparams_ae, a.de.np, dae ? a.ae.np : 0, (int)nwg, stream));
 }
 
 }  // namespace psnode

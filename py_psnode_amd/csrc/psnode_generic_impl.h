@@ -42,7 +42,7 @@
 // psnode_generic.hip.
 #pragma once
 #include "psnode_act.h"
-#include "psnode_common.h"
+#include "psnode_launch.h"
 
 namespace psnode {
 
@@ -619,12 +619,7 @@ hipError_t launch_generic_build(const IntegrateDev& a_in, bool dae, hipStream_t 
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
     const size_t lds_launch = (grid <= (unsigned)cus && lds < 81 * 1024) ? 81 * 1024 : lds;
-    auto go = [&](auto kern) -> hipError_t {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_launch);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), lds_launch, stream_, a, extra...);
-        return hipGetLastError();
-    };
+    auto go = [&](auto kern) { return launch_attr(true, kern, dim3(grid), dim3(NT), lds_launch, stream_, a, extra...); };
     const int qm = generic_reg_mode(a, dae);
     const bool deep = a.de.n_layers > 4 || (dae && a.ae.n_layers > 4);      // the layer loop is unrolled 4 or kMaxLayers times
     if (qm && deep) return qm == 4 ? go(GenericKernels<B>::template get<false, 0, kMaxLayers, 4>()) : go(GenericKernels<B>::template get<false, 0, kMaxLayers, 8>());

@@ -12,6 +12,7 @@
 // order by reduce_partials.  No weights are resident: ~110 registers, the loads of the next row are in flight during the MFMAs of this one.
 #include <string.h>
 
+#include "psnode_launch.h"
 #include "psnode_tile_bwd.h"
 #include "psnode_wide_pack.h"
 
@@ -242,8 +243,7 @@ int32_t psnode_dae_head_grads_f32(const psnode_dae_head_grads_args_f32* p, void*
     if (p->hidden < 1 || p->hidden > 128 || p->B < 1 || p->R < 1 || p->n_zv < 0 || p->n_zv > 8) return PSNODE_ERR_DIMS;
     for (int l = 0; l < 3; ++l) if (!p->act[l] || !p->delta[l]) return PSNODE_ERR_NULL;
     if (!p->gi || !p->u || !p->out || !p->sa1 || (p->n_zv > 0 && p->grad_zv && !p->aw1)) return PSNODE_ERR_NULL;
-    if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 255u) || workspace_bytes < psnode_dae_head_grads_workspace_bytes(p))
-        return PSNODE_ERR_WORKSPACE;
+    if (!workspace_ok(workspace, workspace_bytes, psnode_dae_head_grads_workspace_bytes(p))) return PSNODE_ERR_WORKSPACE;
     const int H = padded_hidden(p->hidden), nw = H / 16;
     if (!H) return PSNODE_ERR_UNSUPPORTED;
     if (p->B * (int64_t)H + 64 >= ((int64_t)1 << 30)) return PSNODE_ERR_DIMS;      // 32-bit per-lane byte offsets inside a row
@@ -261,24 +261,15 @@ int32_t psnode_dae_head_grads_f32(const psnode_dae_head_grads_args_f32* p, void*
     a.sa1 = rs > 1 ? sa1_part : p->sa1;
     const dim3 grid((unsigned)nwg, (unsigned)rs), block(64 * nw);
     const size_t lds = (size_t)7 * nw * FTILE * sizeof(float);
-    hipError_t e = hipSuccess;
-    switch (nw) {
-        case 2: hipLaunchKernelGGL(head_grads_kernel<2>, grid, block, lds, s, a); break;
-        case 4: hipLaunchKernelGGL(head_grads_kernel<4>, grid, block, lds, s, a); break;
-        default: {
-            auto kern = &head_grads_kernel<8>;
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return PSNODE_ERR_HIP;
-            hipLaunchKernelGGL(kern, grid, block, lds, s, a);
-        }
-    }
-    if (hipGetLastError() != hipSuccess) return PSNODE_ERR_HIP;
+    // (the 2- and 4-wave instances stay under the 48 KiB default and never set the attribute)
+    const hipError_t e = pick<2, 4, 8>(nw, [&](auto w) { return launch_attr(nw == 8, &head_grads_kernel<decltype(w)::value>, grid, block, lds, s, a); });
+    if (e != hipSuccess) return PSNODE_ERR_HIP;
     if (rs > 1) {
         const long long n = p->B * (long long)H;
         hipLaunchKernelGGL(sum_splits_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, sa1_part, p->sa1, n, rs);
         if (hipGetLastError() != hipSuccess) return PSNODE_ERR_HIP;
     }
-    return launch_reduce_partials(a.wpart, p->out, nullptr, a.NP, 0, (int)(nwg * rs), s) == hipSuccess ? PSNODE_OK : PSNODE_ERR_HIP;
+    return ok_or_hip(launch_reduce_partials(a.wpart, p->out, nullptr, a.NP, 0, (int)(nwg * rs), s));
 }
 
 }  // extern "C"

@@ -9,7 +9,7 @@
 // operands for the next layer, and every per-step global access of a lane (state, z|v blocks, outputs) is one
 // aligned float4.  Weights stay in VGPRs; the a0 columns of L1 are folded into a per-trajectory constant, the
 // external-input columns into a per-step constant (zero-order hold).
-#include "psnode_common.h"
+#include "psnode_launch.h"
 
 namespace psnode {
 namespace {
@@ -250,7 +250,7 @@ __global__ __launch_bounds__(64) void latent_kernel(const IntegrateDev a, const 
 bool two_layer(const MlpDev& m, int in_dim) {
     return m.n_layers == 2 && m.in_dim == in_dim && m.out_dim[0] == LH && m.out_dim[1] == LH;
 }
-bool aligned4(const ViewDev& v) { return v.p && (reinterpret_cast<uintptr_t>(v.p) & 15) == 0 && v.st % 4 == 0 && v.sb % 4 == 0; }
+bool aligned4(const ViewDev& v) { return v.p && !misaligned16(v.p) && v.st % 4 == 0 && v.sb % 4 == 0; }
 
 }  // namespace
 
@@ -266,13 +266,13 @@ bool latent_shape_ok(const IntegrateDev& a, bool dae) {
 
 bool latent_ptrs_ok(const IntegrateDev& a, bool dae) {
     if (!dae) return true;   // K3f reads lane-granular
-    if ((reinterpret_cast<uintptr_t>(a.a0) & 15) || (reinterpret_cast<uintptr_t>(a.xo) & 15)) return false;
-    if ((reinterpret_cast<uintptr_t>(a.x_init) & 15) || (reinterpret_cast<uintptr_t>(a.io) & 15)) return false;
+    if (misaligned16(a.a0) || misaligned16(a.xo)) return false;
+    if (misaligned16(a.x_init) || misaligned16(a.io)) return false;
     if (a.zd && !aligned4(a.z)) return false;
     if (!aligned4(a.v)) return false;
     if (a.ev) {
-        if (a.zd && ((reinterpret_cast<uintptr_t>(a.zj) & 15) || a.zjb % 4 || a.zje % 4)) return false;
-        if ((reinterpret_cast<uintptr_t>(a.vj) & 15) || a.vjb % 4 || a.vje % 4) return false;
+        if (a.zd && (misaligned16(a.zj) || a.zjb % 4 || a.zje % 4)) return false;
+        if (misaligned16(a.vj) || a.vjb % 4 || a.vje % 4) return false;
     }
     return true;
 }
@@ -288,10 +288,9 @@ size_t latent_pack_floats() { Arena A; latent_layout(A); return A.floats(); }
 template <int METHOD>
 static hipError_t launch_latent_method(const IntegrateDev& a, bool dae, const float* pde, const float* pae, hipStream_t s) {
     const dim3 grid((unsigned)((a.B + LTB - 1) / LTB)), block(64);
-    if (!dae) hipLaunchKernelGGL((latent_kernel<METHOD, 1, false>), grid, block, 0, s, a, pde, pae);
-    else if (a.zd) hipLaunchKernelGGL((latent_kernel<METHOD, 3, true>), grid, block, 0, s, a, pde, pae);
-    else hipLaunchKernelGGL((latent_kernel<METHOD, 2, true>), grid, block, 0, s, a, pde, pae);
-    return hipGetLastError();
+    if (!dae) return launch(&latent_kernel<METHOD, 1, false>, grid, block, 0, s, a, pde, pae);
+    if (a.zd) return launch(&latent_kernel<METHOD, 3, true>, grid, block, 0, s, a, pde, pae);
+    return launch(&latent_kernel<METHOD, 2, true>, grid, block, 0, s, a, pde, pae);
 }
 
 hipError_t launch_latent(const IntegrateDev& a, bool dae, float* pack, hipStream_t stream) {
@@ -299,7 +298,7 @@ hipError_t launch_latent(const IntegrateDev& a, bool dae, float* pack, hipStream
     const int nblk = dae ? (a.zd ? 4 : 3) : 2;
     PackLatent p;
     p.ae = 0; p.nblk = nblk; p.n = nblk * LH; p.k1 = 3 * p.n;
-    p.w1 = a.de.w[0]; p.b1 = a.de.bias[0]; p.w2 = a.de.w[1]; p.b2 = a.de.bias[1];
+    set_layers2(p, a.de);
     Arena A{pack};
     const LatentPack L = latent_layout(A);
     p.out = L.de;
@@ -307,17 +306,13 @@ hipError_t launch_latent(const IntegrateDev& a, bool dae, float* pack, hipStream
     if (dae) {
         PackLatent q;
         q.ae = 1; q.nblk = nblk - 1; q.n = p.n; q.k1 = p.n + (nblk - 1) * LH;
-        q.w1 = a.ae.w[0]; q.b1 = a.ae.bias[0]; q.w2 = a.ae.w[1]; q.b2 = a.ae.bias[1];
+        set_layers2(q, a.ae);
         q.out = L.ae;
         hipLaunchKernelGGL(pack_latent_kernel, dim3(4), dim3(256), 0, stream, q);
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    switch (a.method) {
-        case PSNODE_EULER: return launch_latent_method<PSNODE_EULER>(a, dae, L.de, L.ae, stream);
-        case PSNODE_MIDPOINT: return launch_latent_method<PSNODE_MIDPOINT>(a, dae, L.de, L.ae, stream);
-        default: return launch_latent_method<PSNODE_RK4_38>(a, dae, L.de, L.ae, stream);
-    }
+    return with_method(a.method, [&](auto m) { return launch_latent_method<decltype(m)::value>(a, dae, L.de, L.ae, stream); });
 }
 
 }  // namespace psnode

@@ -14,7 +14,7 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "psnode_common.h"
+#include "psnode_launch.h"
 
 namespace psnode {
 namespace {
@@ -773,21 +773,17 @@ __global__ __launch_bounds__(512) void latent64_model2_kernel(const ModelDev md,
 }
 
 bool two64(const MlpDev& m, int in_dim) { return m.n_layers == 2 && m.in_dim == in_dim && m.out_dim[0] == H64 && m.out_dim[1] == H64; }
-bool al4(const ViewDev& v) { return v.p && (reinterpret_cast<uintptr_t>(v.p) & 15) == 0 && v.st % 4 == 0 && v.sb % 4 == 0; }
+bool al4(const ViewDev& v) { return v.p && !misaligned16(v.p) && v.st % 4 == 0 && v.sb % 4 == 0; }
 
 template <int METHOD>
 hipError_t launch64_method(const IntegrateDev& a, bool dae, const float* pde, const float* pae, hipStream_t s) {
     const dim3 grid((unsigned)((a.B + 15) / 16)), block(256);
-    if (a.sact) {       // training forward
-        if (!dae) hipLaunchKernelGGL((latent64_kernel<METHOD, 1, false, true>), grid, block, 0, s, a, pde, pae);
-        else if (a.zd) hipLaunchKernelGGL((latent64_kernel<METHOD, 3, true, true>), grid, block, 0, s, a, pde, pae);
-        else hipLaunchKernelGGL((latent64_kernel<METHOD, 2, true, true>), grid, block, 0, s, a, pde, pae);
-        return hipGetLastError();
-    }
-    if (!dae) hipLaunchKernelGGL((latent64_kernel<METHOD, 1, false>), grid, block, 0, s, a, pde, pae);
-    else if (a.zd) hipLaunchKernelGGL((latent64_kernel<METHOD, 3, true>), grid, block, 0, s, a, pde, pae);
-    else hipLaunchKernelGGL((latent64_kernel<METHOD, 2, true>), grid, block, 0, s, a, pde, pae);
-    return hipGetLastError();
+    return with_flag(a.sact != nullptr, [&](auto save) {       // saved rows: the training forward
+        constexpr bool SAVE = decltype(save)::value;
+        if (!dae) return launch(&latent64_kernel<METHOD, 1, false, SAVE>, grid, block, 0, s, a, pde, pae);
+        if (a.zd) return launch(&latent64_kernel<METHOD, 3, true, SAVE>, grid, block, 0, s, a, pde, pae);
+        return launch(&latent64_kernel<METHOD, 2, true, SAVE>, grid, block, 0, s, a, pde, pae);
+    });
 }
 
 }  // namespace
@@ -801,13 +797,12 @@ bool latent64_shape_ok(const IntegrateDev& a, bool dae) {
 }
 
 bool latent64_ptrs_ok(const IntegrateDev& a, bool dae) {
-    auto mis = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
-    if (mis(a.a0) || mis(a.xo)) return false;
-    if (!dae) return al4(a.x) && al4(a.z) && (!a.ev || (!mis(a.zj) && a.zjb % 4 == 0 && a.zje % 4 == 0));
-    if (mis(a.x_init) || mis(a.io) || !al4(a.v) || (a.zd && !al4(a.z))) return false;
+    if (misaligned16(a.a0) || misaligned16(a.xo)) return false;
+    if (!dae) return al4(a.x) && al4(a.z) && (!a.ev || (!misaligned16(a.zj) && a.zjb % 4 == 0 && a.zje % 4 == 0));
+    if (misaligned16(a.x_init) || misaligned16(a.io) || !al4(a.v) || (a.zd && !al4(a.z))) return false;
     if (a.ev) {
-        if (a.zd && (mis(a.zj) || a.zjb % 4 || a.zje % 4)) return false;
-        if (mis(a.vj) || a.vjb % 4 || a.vje % 4) return false;
+        if (a.zd && (misaligned16(a.zj) || a.zjb % 4 || a.zje % 4)) return false;
+        if (misaligned16(a.vj) || a.vjb % 4 || a.vje % 4) return false;
     }
     return true;
 }
@@ -822,29 +817,29 @@ static Latent64Pack latent64_layout(bool enc_dec, Arena& A) {
 }
 size_t latent64_pack_floats() { Arena A; latent64_layout(false, A); return A.floats(); }
 
-hipError_t launch_latent64(const IntegrateDev& a, bool dae, float* pack, hipStream_t stream) {
+// the latent DE's image and, for the DAE, the AE's (K3c and K3g)
+static void pack64_images(const IntegrateDev& a, bool dae, const Latent64Pack& L, hipStream_t s) {
     const int nblk = dae ? (a.zd ? 4 : 3) : 2;
     Pack64 p;
     p.ae = 0; p.nblk = nblk; p.nfront = nblk; p.k1 = 3 * nblk * H64;
-    p.w1 = a.de.w[0]; p.b1 = a.de.bias[0]; p.w2 = a.de.w[1]; p.b2 = a.de.bias[1];
+    set_layers2(p, a.de);
+    p.out = L.de;
+    hipLaunchKernelGGL(pack64_kernel, dim3(32), dim3(256), 0, s, p);
+    if (!dae) return;
+    Pack64 q = p;
+    q.ae = 1; q.nfront = nblk - 1; q.k1 = (2 * nblk - 1) * H64;
+    set_layers2(q, a.ae);
+    q.out = L.ae;
+    hipLaunchKernelGGL(pack64_kernel, dim3(32), dim3(256), 0, s, q);
+}
+
+hipError_t launch_latent64(const IntegrateDev& a, bool dae, float* pack, hipStream_t stream) {
     Arena A{pack};
     const Latent64Pack L = latent64_layout(false, A);
-    p.out = L.de;
-    hipLaunchKernelGGL(pack64_kernel, dim3(32), dim3(256), 0, stream, p);
-    if (dae) {
-        Pack64 q = p;
-        q.ae = 1; q.nfront = nblk - 1; q.k1 = (2 * nblk - 1) * H64;
-        q.w1 = a.ae.w[0]; q.b1 = a.ae.bias[0]; q.w2 = a.ae.w[1]; q.b2 = a.ae.bias[1];
-        q.out = L.ae;
-        hipLaunchKernelGGL(pack64_kernel, dim3(32), dim3(256), 0, stream, q);
-    }
+    pack64_images(a, dae, L, stream);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    switch (a.method) {
-        case PSNODE_EULER: return launch64_method<PSNODE_EULER>(a, dae, L.de, L.ae, stream);
-        case PSNODE_MIDPOINT: return launch64_method<PSNODE_MIDPOINT>(a, dae, L.de, L.ae, stream);
-        default: return launch64_method<PSNODE_RK4_38>(a, dae, L.de, L.ae, stream);
-    }
+    return with_method(a.method, [&](auto m) { return launch64_method<decltype(m)::value>(a, dae, L.de, L.ae, stream); });
 }
 
 
@@ -852,12 +847,7 @@ namespace {
 template <int METHOD>
 hipError_t launch_model_method(const ModelDev& md, const float* pde, const float* pae, const float* ped, hipStream_t s) {
     const dim3 grid((unsigned)((md.a.B + 15) / 16));
-    auto go = [&](auto kern) -> hipError_t {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kModel2Lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, grid, dim3(512), kModel2Lds, s, md, pde, pae, ped);
-        return hipGetLastError();
-    };
+    auto go = [&](auto kern) { return launch(kern, grid, dim3(512), kModel2Lds, s, md, pde, pae, ped); };
     return md.a.zd ? go(&latent64_model2_kernel<METHOD, true>) : go(&latent64_model2_kernel<METHOD, false>);
 }
 bool enc_ok(const psnode_mlp_f32& m, int in, int maxin) {
@@ -896,7 +886,7 @@ int32_t psnode_dae_encoded_integrate_f32(const psnode_dae_encoded_args_f32* p, v
     if (p->x_re && !p->x.ptr) return PSNODE_ERR_NULL;
     if (p->event_idx && (!p->v_jump || (p->z_dim && !p->z_jump))) return PSNODE_ERR_NULL;
     if (!psnode_dae_encoded_supported(p)) return PSNODE_ERR_UNSUPPORTED;
-    if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 255) || workspace_bytes < psnode_dae_encoded_workspace_bytes(p)) return PSNODE_ERR_WORKSPACE;
+    if (!workspace_ok(workspace, workspace_bytes, psnode_dae_encoded_workspace_bytes(p))) return PSNODE_ERR_WORKSPACE;
     hipStream_t s = static_cast<hipStream_t>(stream);
     Arena A{static_cast<float*>(workspace)};
     const Latent64Pack L = latent64_layout(true, A);
@@ -904,34 +894,16 @@ int32_t psnode_dae_encoded_integrate_f32(const psnode_dae_encoded_args_f32* p, v
     memset(&md, 0, sizeof(md));
     IntegrateDev& a = md.a;
     a.method = p->method; a.xd = p->x_dim; a.zd = p->z_dim; a.vd = p->v_dim; a.id = p->i_dim; a.T = p->T; a.B = p->B;
-    auto bind = [](const psnode_mlp_f32& m, MlpDev& d) {
-        d.n_layers = m.n_layers; d.in_dim = m.in_dim;
-        for (int l = 0; l < m.n_layers; ++l) { d.out_dim[l] = m.out_dim[l]; d.w[l] = m.weight[l]; d.bias[l] = m.bias[l]; }
-    };
-    bind(p->de, a.de); bind(p->ae, a.ae);
-    a.t = ViewDev{p->t.ptr, p->t.stride_t, p->t.stride_b};
-    a.x = ViewDev{p->x.ptr, p->x.stride_t, p->x.stride_b};
-    a.z = ViewDev{p->z.ptr, p->z.stride_t, p->z.stride_b};
-    a.v = ViewDev{p->v.ptr, p->v.stride_t, p->v.stride_b};
-    a.i = ViewDev{p->i.ptr, p->i.stride_t, p->i.stride_b};
-    a.ev = p->event_idx; a.zj = p->z_jump; a.zjb = p->zj_stride_b; a.zje = p->zj_stride_e;
-    a.vj = p->v_jump; a.vjb = p->vj_stride_b; a.vje = p->vj_stride_e;
+    bind_mlp(p->de, a.de); bind_mlp(p->ae, a.ae);
+    a.t = view(p->t); a.x = view(p->x); a.z = view(p->z); a.v = view(p->v); a.i = view(p->i);
+    a.ev = p->event_idx;
+    bind_jumps(a, *p);
     a.xo = p->x_pred; a.io = p->i_pred;
     md.x0 = p->x0;
     md.xre = p->x_re; md.xre_st = p->xre_stride_t; md.xre_sb = p->xre_stride_b;
     md.ire = p->i_re; md.ire_st = p->ire_stride_t; md.ire_sb = p->ire_stride_b;
     // packed images: latent DE | AE (as K3c), then the encoders / decoders
-    const int nblk = a.zd ? 4 : 3;
-    Pack64 pk;
-    pk.ae = 0; pk.nblk = nblk; pk.nfront = nblk; pk.k1 = 3 * nblk * H64;
-    pk.w1 = a.de.w[0]; pk.b1 = a.de.bias[0]; pk.w2 = a.de.w[1]; pk.b2 = a.de.bias[1];
-    pk.out = L.de;
-    hipLaunchKernelGGL(pack64_kernel, dim3(32), dim3(256), 0, s, pk);
-    Pack64 qk = pk;
-    qk.ae = 1; qk.nfront = nblk - 1; qk.k1 = (2 * nblk - 1) * H64;
-    qk.w1 = a.ae.w[0]; qk.b1 = a.ae.bias[0]; qk.w2 = a.ae.w[1]; qk.b2 = a.ae.bias[1];
-    qk.out = L.ae;
-    hipLaunchKernelGGL(pack64_kernel, dim3(32), dim3(256), 0, s, qk);
+    pack64_images(a, true, L, s);
     PackEncDec pe;
     memset(&pe, 0, sizeof(pe));
     const psnode_mlp_f32* ms[6] = {&p->x_encoder, p->z_dim ? &p->z_encoder : nullptr, &p->v_encoder, &p->i_encoder, &p->x_decoder, &p->i_decoder};
@@ -944,13 +916,7 @@ int32_t psnode_dae_encoded_integrate_f32(const psnode_dae_encoded_args_f32* p, v
     pe.out = L.enc_dec;
     hipLaunchKernelGGL(pack_encdec_kernel, dim3(32), dim3(256), 0, s, pe);
     if (hipGetLastError() != hipSuccess) return PSNODE_ERR_HIP;
-    hipError_t e;
-    switch (a.method) {
-        case PSNODE_EULER: e = launch_model_method<PSNODE_EULER>(md, L.de, L.ae, L.enc_dec, s); break;
-        case PSNODE_MIDPOINT: e = launch_model_method<PSNODE_MIDPOINT>(md, L.de, L.ae, L.enc_dec, s); break;
-        default: e = launch_model_method<PSNODE_RK4_38>(md, L.de, L.ae, L.enc_dec, s); break;
-    }
-    return e == hipSuccess ? PSNODE_OK : PSNODE_ERR_HIP;
+    return ok_or_hip(with_method(a.method, [&](auto m) { return launch_model_method<decltype(m)::value>(md, L.de, L.ae, L.enc_dec, s); }));
 }
 
 }  // extern "C"

@@ -1,7 +1,7 @@
 // Shared between psnode_latent64_bwd.hip (K9, one-role kernels + host side) and psnode_latent64_bwd_roles.hip (the two-role form of the
 // saved-activation DAE instance, compiled with the VGPR form of the MFMA accumulators: 2 waves per SIMD leave it 256 registers).
 #pragma once
-#include "psnode_common.h"
+#include "psnode_launch.h"
 
 namespace psnode {
 

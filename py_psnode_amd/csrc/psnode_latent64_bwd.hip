@@ -615,8 +615,7 @@ __global__ __launch_bounds__(256) void latent64_backward_kernel(const Bwd9Dev d,
 
 int np9(int k1) { return H9 * k1 + H9 + H9 * H9 + H9; }
 bool two9(const psnode_mlp_f32& m, int in_dim) { return m.n_layers == 2 && m.in_dim == in_dim && m.out_dim[0] == H9 && m.out_dim[1] == H9; }
-bool mis9(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
-bool view9(const psnode_view_f32& v) { return v.ptr && !mis9(v.ptr) && v.stride_t % 4 == 0 && v.stride_b % 4 == 0; }
+bool view9(const psnode_view_f32& v) { return v.ptr && !misaligned16(v.ptr) && v.stride_t % 4 == 0 && v.stride_b % 4 == 0; }
 // per-lane offsets inside a row are 32-bit element offsets next to a scalar row base (psnode_common.h: sbase)
 bool fits9(long long B, long long stride_b) { return stride_b >= 0 && (unsigned long long)B * (unsigned long long)stride_b + 64 < (1ull << 30); }   // byte offsets fit 32 bits
 size_t pack9_floats(int nblk) { return (size_t)2 * NW9 * p9_regs(nblk, nblk) * 64; }
@@ -631,10 +630,7 @@ hipError_t launch9(const Bwd9Dev& d, const float* pde, const float* pae, hipStre
     constexpr bool REC_SAVED = DAE;      // 4th parameter of the saved-activation instance: false (reads the saved rows) for the ODE only
     auto kern = (!DAE && d.a.sact) ? &latent64_backward_kernel<METHOD, NBE, DAE, REC_SAVED> : &latent64_backward_kernel<METHOD, NBE, DAE, true>;
     const size_t lds = lds9_bytes((DAE && !d.a.sact) ? 2 * NBE : 0);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3((unsigned)((d.a.B + 15) / 16)), dim3(256), lds, s, d, pde, pae);
-    return hipGetLastError();
+    return launch(kern, dim3((unsigned)((d.a.B + 15) / 16)), dim3(256), lds, s, d, pde, pae);
 }
 
 template <int METHOD>
@@ -663,26 +659,21 @@ int run9(Bwd9Dev& d, bool dae, int nblk, const psnode_mlp_f32& de, const psnode_
     d.NP_ae = dae ? np9((2 * nblk - 1) * H9) : 0;
     Pack9 p;
     p.ae = 0; p.nblk = nblk; p.nfront = nblk; p.k1 = 3 * nblk * H9;
-    p.w1 = de.weight[0]; p.b1 = de.bias[0]; p.w2 = de.weight[1]; p.b2 = de.bias[1];
+    set_layers2(p, de);
     p.out = pack_de;
     hipLaunchKernelGGL(pack9_kernel, dim3(64), dim3(256), 0, s, p);
     if (dae) {
         Pack9 pq = p;
         pq.ae = 1; pq.nfront = nblk - 1; pq.k1 = (2 * nblk - 1) * H9;
-        pq.w1 = ae->weight[0]; pq.b1 = ae->bias[0]; pq.w2 = ae->weight[1]; pq.b2 = ae->bias[1];
+        set_layers2(pq, *ae);
         pq.out = pack_ae;
         hipLaunchKernelGGL(pack9_kernel, dim3(64), dim3(256), 0, s, pq);
     }
     if (hipGetLastError() != hipSuccess) return PSNODE_ERR_HIP;
-    hipError_t e;
-    switch (d.a.method) {
-        case PSNODE_EULER: e = launch9_method<PSNODE_EULER>(d, dae, pack_de, pack_ae, s); break;
-        case PSNODE_MIDPOINT: e = launch9_method<PSNODE_MIDPOINT>(d, dae, pack_de, pack_ae, s); break;
-        default: e = launch9_method<PSNODE_RK4_38>(d, dae, pack_de, pack_ae, s); break;
-    }
+    const hipError_t e = with_method(d.a.method, [&](auto m) { return launch9_method<decltype(m)::value>(d, dae, pack_de, pack_ae, s); });
     if (e != hipSuccess) return PSNODE_ERR_HIP;
     const int nwg = (int)((d.a.B + 15) / 16);
-    return launch_reduce_partials(d.wpart, gp_de, gp_ae, d.NP_de, d.NP_ae, nwg, s) == hipSuccess ? PSNODE_OK : PSNODE_ERR_HIP;
+    return ok_or_hip(launch_reduce_partials(d.wpart, gp_de, gp_ae, d.NP_de, d.NP_ae, nwg, s));
 }
 
 }  // namespace
@@ -690,11 +681,11 @@ int run9(Bwd9Dev& d, bool dae, int nblk, const psnode_mlp_f32& de, const psnode_
 // ---------------------------------------------------------------------------------------------------------------- ODE
 bool latent64_ode_bwd_shape_ok(const psnode_ode_bwd_args_f32* a) { return a->x_dim == H9 && a->z_dim == H9 && two9(a->de, 6 * H9); }
 bool latent64_ode_bwd_ptrs_ok(const psnode_ode_bwd_args_f32* a) {
-    if (mis9(a->all_initial) || mis9(a->xs) || mis9(a->grad_xs) || mis9(a->grad_x0) || mis9(a->grad_all_initial) || !view9(a->z)) return false;
-    if (a->grad_z && mis9(a->grad_z)) return false;
+    if (misaligned16(a->all_initial) || misaligned16(a->xs) || misaligned16(a->grad_xs) || misaligned16(a->grad_x0) || misaligned16(a->grad_all_initial) || !view9(a->z)) return false;
+    if (a->grad_z && misaligned16(a->grad_z)) return false;
     if (!fits9(a->B, a->t.stride_b) || !fits9(a->B, a->z.stride_b) || !fits9(a->B, (long long)H9 * (a->n_events > 0 ? a->n_events : 1))) return false;
     if (a->event_idx && !fits9(a->B, a->zj_stride_b)) return false;
-    if (a->event_idx && (mis9(a->z_jump) || a->zj_stride_b % 4 || a->zj_stride_e % 4 || (a->grad_z_jump && mis9(a->grad_z_jump)))) return false;
+    if (a->event_idx && (misaligned16(a->z_jump) || a->zj_stride_b % 4 || a->zj_stride_e % 4 || (a->grad_z_jump && misaligned16(a->grad_z_jump)))) return false;
     return true;
 }
 size_t latent64_ode_bwd_workspace_floats(long long B) { Arena A; layout9(false, 2, B, A); return A.floats(); }
@@ -702,9 +693,9 @@ int latent64_ode_bwd_launch(const psnode_ode_bwd_args_f32* a, float* workspace, 
     Bwd9Dev d;
     memset(&d, 0, sizeof(d));
     d.a.method = a->method; d.a.xd = H9; d.a.zd = H9; d.a.T = a->T; d.a.B = a->B;
-    d.a.t = ViewDev{a->t.ptr, a->t.stride_t, a->t.stride_b};
-    d.a.z = ViewDev{a->z.ptr, a->z.stride_t, a->z.stride_b};
-    d.a.a0 = a->all_initial; d.a.ev = a->event_idx; d.a.zj = a->z_jump; d.a.zjb = a->zj_stride_b; d.a.zje = a->zj_stride_e;
+    d.a.t = view(a->t); d.a.z = view(a->z);
+    d.a.a0 = a->all_initial; d.a.ev = a->event_idx;
+    bind_jumps(d.a, *a);
     d.xs = a->xs; d.gxs = a->grad_xs; d.gx0 = a->grad_x0; d.gz = a->grad_z; d.gzj = a->grad_z_jump; d.ga0 = a->grad_all_initial;
     d.n_events = a->n_events;
     d.a.sact = const_cast<float*>(a->saved_act); d.a.sxst = const_cast<float*>(a->saved_xstage);
@@ -718,15 +709,15 @@ bool latent64_dae_bwd_shape_ok(const psnode_dae_bwd_args_f32* a) {
     return two9(a->de, 3 * nblk * H9) && two9(a->ae, (2 * nblk - 1) * H9);
 }
 bool latent64_dae_bwd_ptrs_ok(const psnode_dae_bwd_args_f32* a) {
-    if (mis9(a->all_initial) || mis9(a->xs) || mis9(a->is) || mis9(a->grad_xs) || mis9(a->grad_x_init) || mis9(a->grad_all_initial)) return false;
-    if ((a->grad_is && mis9(a->grad_is)) || !view9(a->v) || (a->z_dim && !view9(a->z))) return false;
-    if ((a->grad_z && mis9(a->grad_z)) || (a->grad_v && mis9(a->grad_v))) return false;
+    if (misaligned16(a->all_initial) || misaligned16(a->xs) || misaligned16(a->is) || misaligned16(a->grad_xs) || misaligned16(a->grad_x_init) || misaligned16(a->grad_all_initial)) return false;
+    if ((a->grad_is && misaligned16(a->grad_is)) || !view9(a->v) || (a->z_dim && !view9(a->z))) return false;
+    if ((a->grad_z && misaligned16(a->grad_z)) || (a->grad_v && misaligned16(a->grad_v))) return false;
     if (!fits9(a->B, a->t.stride_b) || !fits9(a->B, a->v.stride_b) || (a->z_dim && !fits9(a->B, a->z.stride_b))
         || !fits9(a->B, (long long)H9 * (a->n_events > 0 ? a->n_events : 1))) return false;
     if (a->event_idx && (!fits9(a->B, a->vj_stride_b) || (a->z_dim && !fits9(a->B, a->zj_stride_b)))) return false;
     if (a->event_idx) {
-        if (a->z_dim && (mis9(a->z_jump) || a->zj_stride_b % 4 || a->zj_stride_e % 4 || (a->grad_z_jump && mis9(a->grad_z_jump)))) return false;
-        if (mis9(a->v_jump) || a->vj_stride_b % 4 || a->vj_stride_e % 4 || (a->grad_v_jump && mis9(a->grad_v_jump))) return false;
+        if (a->z_dim && (misaligned16(a->z_jump) || a->zj_stride_b % 4 || a->zj_stride_e % 4 || (a->grad_z_jump && misaligned16(a->grad_z_jump)))) return false;
+        if (misaligned16(a->v_jump) || a->vj_stride_b % 4 || a->vj_stride_e % 4 || (a->grad_v_jump && misaligned16(a->grad_v_jump))) return false;
     }
     return true;
 }
@@ -738,12 +729,9 @@ int latent64_dae_bwd_launch(const psnode_dae_bwd_args_f32* a, float* workspace, 
     Bwd9Dev d;
     memset(&d, 0, sizeof(d));
     d.a.method = a->method; d.a.xd = H9; d.a.zd = a->z_dim; d.a.vd = H9; d.a.id = H9; d.a.T = a->T; d.a.B = a->B;
-    d.a.t = ViewDev{a->t.ptr, a->t.stride_t, a->t.stride_b};
-    d.a.z = ViewDev{a->z.ptr, a->z.stride_t, a->z.stride_b};
-    d.a.v = ViewDev{a->v.ptr, a->v.stride_t, a->v.stride_b};
+    d.a.t = view(a->t); d.a.z = view(a->z); d.a.v = view(a->v);
     d.a.a0 = a->all_initial; d.a.ev = a->event_idx;
-    d.a.zj = a->z_jump; d.a.zjb = a->zj_stride_b; d.a.zje = a->zj_stride_e;
-    d.a.vj = a->v_jump; d.a.vjb = a->vj_stride_b; d.a.vje = a->vj_stride_e;
+    bind_jumps(d.a, *a);
     d.xs = a->xs; d.is_ = a->is; d.gxs = a->grad_xs; d.gis = a->grad_is;
     d.gx0 = a->grad_x_init; d.gz = a->grad_z; d.gv = a->grad_v; d.gzj = a->grad_z_jump; d.gvj = a->grad_v_jump; d.ga0 = a->grad_all_initial;
     d.n_events = a->n_events;

@@ -461,29 +461,15 @@ __global__ __launch_bounds__(512) void latent64_backward_roles_kernel(const Bwd9
 size_t lds9_roles_bytes(int nae) { return (size_t)(2 * NW9 * NW9 * 64 + 3 * 4 * NW9 * 64 + nae * 4 * NW9 * 64 + 3 * NW9 * 64) * sizeof(f4) + (size_t)(2 * NW9 + NW9) * SCR9 * sizeof(float); }
 
 
-template <int METHOD>
-hipError_t launch9_roles_m(int nbe, const Bwd9Dev& d, const float* pde, const float* pae, hipStream_t s) {
-    const size_t ldsr = lds9_roles_bytes(nbe);
-#define PSNODE_K9R(NBE_)                                                                                                          \
-    {                                                                                                                             \
-        auto kr = &latent64_backward_roles_kernel<METHOD, NBE_>;                                                                  \
-        hipError_t er = hipFuncSetAttribute(reinterpret_cast<const void*>(kr), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsr); \
-        if (er != hipSuccess) return er;                                                                                          \
-        hipLaunchKernelGGL(kr, dim3((unsigned)((d.a.B + 15) / 16)), dim3(512), ldsr, s, d, pde, pae);                             \
-        return hipGetLastError();                                                                                                 \
-    }
-    if (nbe == 3) PSNODE_K9R(3)
-    PSNODE_K9R(2)
-#undef PSNODE_K9R
-}
 }  // namespace
 
 hipError_t launch9_roles(int method, int nbe, const Bwd9Dev& d, const float* pde, const float* pae, hipStream_t s) {
-    switch (method) {
-        case PSNODE_EULER: return launch9_roles_m<PSNODE_EULER>(nbe, d, pde, pae, s);
-        case PSNODE_MIDPOINT: return launch9_roles_m<PSNODE_MIDPOINT>(nbe, d, pde, pae, s);
-        default: return launch9_roles_m<PSNODE_RK4_38>(nbe, d, pde, pae, s);
-    }
+    return with_method(method, [&](auto m) {
+        return pick<2, 3>(nbe, [&](auto e) {
+            return launch(&latent64_backward_roles_kernel<decltype(m)::value, decltype(e)::value>, dim3((unsigned)((d.a.B + 15) / 16)), dim3(512),
+                          lds9_roles_bytes(nbe), s, d, pde, pae);
+        });
+    });
 }
 
 }  // namespace psnode

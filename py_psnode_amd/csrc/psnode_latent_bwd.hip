@@ -17,7 +17,7 @@
 #define PSNODE_ELU_LITERALS   // register-bound kernels: ELU coefficients as literals, not as 8 resident VGPRs (psnode_common.h)
 #include <string.h>
 
-#include "psnode_common.h"
+#include "psnode_launch.h"
 
 namespace psnode {
 namespace {
@@ -317,8 +317,6 @@ __global__ __launch_bounds__(64) void latent16_dae_backward_kernel(const LatentD
     }
 }
 
-bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace
 
 bool latent_bwd_shape_ok(const psnode_ode_bwd_args_f32* a) {
@@ -342,52 +340,50 @@ bool latent16_dae_bwd_shape_ok(const psnode_dae_bwd_args_f32* a) {
 }
 
 bool latent16_dae_bwd_ptrs_ok(const psnode_dae_bwd_args_f32* a) {
-    auto view_ok = [](const psnode_view_f32& v) { return v.ptr && al16(v.ptr) && v.stride_t % 4 == 0 && v.stride_b % 4 == 0; };
-    if (!al16(a->all_initial) || !al16(a->xs) || !al16(a->is) || !al16(a->grad_xs) || !al16(a->grad_x_init) || !al16(a->grad_all_initial)) return false;
-    if ((a->grad_is && !al16(a->grad_is)) || !view_ok(a->v) || (a->z_dim && !view_ok(a->z))) return false;
-    if ((a->grad_z && !al16(a->grad_z)) || (a->grad_v && !al16(a->grad_v))) return false;
+    auto view_ok = [](const psnode_view_f32& v) { return v.ptr && !misaligned16(v.ptr) && v.stride_t % 4 == 0 && v.stride_b % 4 == 0; };
+    if (misaligned16(a->all_initial) || misaligned16(a->xs) || misaligned16(a->is) || misaligned16(a->grad_xs) || misaligned16(a->grad_x_init) || misaligned16(a->grad_all_initial)) return false;
+    if ((a->grad_is && misaligned16(a->grad_is)) || !view_ok(a->v) || (a->z_dim && !view_ok(a->z))) return false;
+    if ((a->grad_z && misaligned16(a->grad_z)) || (a->grad_v && misaligned16(a->grad_v))) return false;
     if (a->event_idx) {
-        if (a->z_dim && (!al16(a->z_jump) || a->zj_stride_b % 4 || a->zj_stride_e % 4 || (a->grad_z_jump && !al16(a->grad_z_jump)))) return false;
-        if (!al16(a->v_jump) || a->vj_stride_b % 4 || a->vj_stride_e % 4 || (a->grad_v_jump && !al16(a->grad_v_jump))) return false;
+        if (a->z_dim && (misaligned16(a->z_jump) || a->zj_stride_b % 4 || a->zj_stride_e % 4 || (a->grad_z_jump && misaligned16(a->grad_z_jump)))) return false;
+        if (misaligned16(a->v_jump) || a->vj_stride_b % 4 || a->vj_stride_e % 4 || (a->grad_v_jump && misaligned16(a->grad_v_jump))) return false;
     }
     return true;
 }
 
 static int np16(int k1) { return LH * k1 + LH + LH * LH + LH; }
 
-size_t latent16_dae_bwd_workspace_floats(const psnode_dae_bwd_args_f32* a) {
+// K8's workspace: per workgroup of LTB trajectories, one partial vector of the DE's and of the AE's parameters
+static float* layout16(const psnode_dae_bwd_args_f32* a, Arena& A) {
     const int nblk = a->z_dim ? 4 : 3;
-    return (size_t)((a->B + LTB - 1) / LTB) * (np16(3 * nblk * LH) + np16((2 * nblk - 1) * LH)) + 64;
+    float* wpart = A.take((size_t)((a->B + LTB - 1) / LTB) * (np16(3 * nblk * LH) + np16((2 * nblk - 1) * LH)));
+    A.slack(64);      // kept from the parent, purpose not established
+    return wpart;
 }
+size_t latent16_dae_bwd_workspace_floats(const psnode_dae_bwd_args_f32* a) { Arena A; layout16(a, A); return A.floats(); }
 
 int latent16_dae_bwd_launch(const psnode_dae_bwd_args_f32* a, float* workspace, hipStream_t s) {
     LatentDaeBwdDev d;
     memset(&d, 0, sizeof(d));
     d.a.method = a->method; d.a.xd = LH; d.a.zd = a->z_dim; d.a.vd = LH; d.a.id = LH; d.a.T = a->T; d.a.B = a->B;
-    d.a.t = ViewDev{a->t.ptr, a->t.stride_t, a->t.stride_b};
-    d.a.z = ViewDev{a->z.ptr, a->z.stride_t, a->z.stride_b};
-    d.a.v = ViewDev{a->v.ptr, a->v.stride_t, a->v.stride_b};
+    d.a.t = view(a->t); d.a.z = view(a->z); d.a.v = view(a->v);
     d.a.a0 = a->all_initial; d.a.ev = a->event_idx;
-    d.a.zj = a->z_jump; d.a.zjb = a->zj_stride_b; d.a.zje = a->zj_stride_e;
-    d.a.vj = a->v_jump; d.a.vjb = a->vj_stride_b; d.a.vje = a->vj_stride_e;
+    bind_jumps(d.a, *a);
     for (int l = 0; l < 2; ++l) { d.a.de.w[l] = a->de.weight[l]; d.a.de.bias[l] = a->de.bias[l]; d.a.ae.w[l] = a->ae.weight[l]; d.a.ae.bias[l] = a->ae.bias[l]; }
     d.xs = a->xs; d.is_ = a->is; d.gxs = a->grad_xs; d.gis = a->grad_is;
     d.gx0 = a->grad_x_init; d.gz = a->grad_z; d.gv = a->grad_v; d.gzj = a->grad_z_jump; d.gvj = a->grad_v_jump; d.ga0 = a->grad_all_initial;
-    d.wpart = workspace; d.n_events = a->n_events;
+    Arena A{workspace};
+    float* wpart = layout16(a, A);
+    d.wpart = wpart; d.n_events = a->n_events;
     const int nblk = a->z_dim ? 4 : 3, npd = np16(3 * nblk * LH), npa = np16((2 * nblk - 1) * LH);
     const int nwg = (int)((a->B + LTB - 1) / LTB);
     const dim3 grid((unsigned)nwg), block(64);
-#define PSNODE_L16(M_)                                                                                              \
-    if (a->z_dim) hipLaunchKernelGGL((latent16_dae_backward_kernel<M_, 3>), grid, block, 0, s, d);                 \
-    else hipLaunchKernelGGL((latent16_dae_backward_kernel<M_, 2>), grid, block, 0, s, d);
-    switch (a->method) {
-        case PSNODE_EULER: PSNODE_L16(PSNODE_EULER) break;
-        case PSNODE_MIDPOINT: PSNODE_L16(PSNODE_MIDPOINT) break;
-        default: PSNODE_L16(PSNODE_RK4_38) break;
-    }
-#undef PSNODE_L16
-    if (hipGetLastError() != hipSuccess) return PSNODE_ERR_HIP;
-    return launch_reduce_partials(workspace, a->grad_params_de, a->grad_params_ae, npd, npa, nwg, s) == hipSuccess ? PSNODE_OK : PSNODE_ERR_HIP;
+    const hipError_t e = with_method(a->method, [&](auto m) {
+        if (a->z_dim) return launch(&latent16_dae_backward_kernel<decltype(m)::value, 3>, grid, block, 0, s, d);
+        return launch(&latent16_dae_backward_kernel<decltype(m)::value, 2>, grid, block, 0, s, d);
+    });
+    if (e != hipSuccess) return PSNODE_ERR_HIP;
+    return ok_or_hip(launch_reduce_partials(wpart, a->grad_params_de, a->grad_params_ae, npd, npa, nwg, s));
 }
 
 }  // namespace psnode

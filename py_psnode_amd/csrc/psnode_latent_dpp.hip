@@ -20,7 +20,7 @@
 // state-step; Xh, Zh and Xh_solution never exist in memory.
 #include <string.h>
 
-#include "psnode_common.h"
+#include "psnode_launch.h"
 
 namespace psnode {
 namespace {
@@ -1060,12 +1060,7 @@ __global__ __launch_bounds__(512) void latent_ode_backward_dpp_kernel(const Late
 template <bool ENC>
 hipError_t launch_dpp(const LatentDppDev& a, hipStream_t s) {
     const dim3 grid((unsigned)((a.B + DTB - 1) / DTB)), block(ENC ? 512 : 256);
-    switch (a.method) {
-        case PSNODE_EULER: hipLaunchKernelGGL((latent_dpp_kernel<PSNODE_EULER, ENC>), grid, block, 0, s, a); break;
-        case PSNODE_MIDPOINT: hipLaunchKernelGGL((latent_dpp_kernel<PSNODE_MIDPOINT, ENC>), grid, block, 0, s, a); break;
-        default: hipLaunchKernelGGL((latent_dpp_kernel<PSNODE_RK4_38, ENC>), grid, block, 0, s, a); break;
-    }
-    return hipGetLastError();
+    return with_method(a.method, [&](auto m) { return launch(&latent_dpp_kernel<decltype(m)::value, ENC>, grid, block, 0, s, a); });
 }
 
 bool mlp2_ok(const psnode_mlp_f32& m, int in, int out) {
@@ -1094,20 +1089,16 @@ int latent_bwd_dpp_launch(const psnode_ode_bwd_args_f32* p, float* workspace, hi
     memset(&a, 0, sizeof(a));
     a.method = p->method; a.n_events = p->n_events; a.T = p->T; a.B = p->B;
     a.de_w1 = p->de.weight[0]; a.de_b1 = p->de.bias[0]; a.de_w2 = p->de.weight[1]; a.de_b2 = p->de.bias[1];
-    a.t = ViewDev{p->t.ptr, p->t.stride_t, p->t.stride_b};
-    a.z = ViewDev{p->z.ptr, p->z.stride_t, p->z.stride_b};
-    a.a0 = p->all_initial; a.ev = p->event_idx; a.zj = p->z_jump; a.zjb = p->zj_stride_b; a.zje = p->zj_stride_e;
+    a.t = view(p->t); a.z = view(p->z);
+    a.a0 = p->all_initial; a.ev = p->event_idx;
+    bind_jumps(a, *p);
     a.xs = p->xs; a.gout = p->grad_xs; a.gx0 = p->grad_x0; a.gz = p->grad_z; a.gzj = p->grad_z_jump; a.ga0 = p->grad_all_initial;
     a.wpart = workspace;
     const int nwg = (int)((p->B + DTB - 1) / DTB);
     const dim3 grid((unsigned)nwg), block(512);      // 4 sweep waves + their 4 partner waves (phase A on MFMA tiles)
-    switch (p->method) {
-        case PSNODE_EULER: hipLaunchKernelGGL((latent_ode_backward_dpp_kernel<PSNODE_EULER>), grid, block, 0, s, a); break;
-        case PSNODE_MIDPOINT: hipLaunchKernelGGL((latent_ode_backward_dpp_kernel<PSNODE_MIDPOINT>), grid, block, 0, s, a); break;
-        default: hipLaunchKernelGGL((latent_ode_backward_dpp_kernel<PSNODE_RK4_38>), grid, block, 0, s, a); break;
-    }
-    if (hipGetLastError() != hipSuccess) return PSNODE_ERR_HIP;
-    return launch_reduce_partials(workspace, p->grad_params, nullptr, BNP, 0, nwg * 4, s) == hipSuccess ? PSNODE_OK : PSNODE_ERR_HIP;
+    const hipError_t e = with_method(p->method, [&](auto m) { return launch(&latent_ode_backward_dpp_kernel<decltype(m)::value>, grid, block, 0, s, a); });
+    if (e != hipSuccess) return PSNODE_ERR_HIP;
+    return ok_or_hip(launch_reduce_partials(workspace, p->grad_params, nullptr, BNP, 0, nwg * 4, s));
 }
 
 }  // namespace psnode
@@ -1135,12 +1126,11 @@ int32_t psnode_ode_encoded_integrate_f32(const psnode_ode_encoded_args_f32* p, v
     a.method = p->method; a.xd = p->x_dim; a.zd = p->z_dim; a.T = p->T; a.B = p->B;
     a.xenc = bind2(p->x_encoder); a.zenc = bind2(p->z_encoder); a.xdec = bind2(p->x_decoder);
     a.de_w1 = p->de.weight[0]; a.de_b1 = p->de.bias[0]; a.de_w2 = p->de.weight[1]; a.de_b2 = p->de.bias[1];
-    a.t = ViewDev{p->t.ptr, p->t.stride_t, p->t.stride_b};
-    a.x = ViewDev{p->x.ptr, p->x.stride_t, p->x.stride_b};
-    a.z = ViewDev{p->z.ptr, p->z.stride_t, p->z.stride_b};
-    a.ev = p->event_idx; a.zj = p->z_jump; a.zjb = p->zj_stride_b; a.zje = p->zj_stride_e;
+    a.t = view(p->t); a.x = view(p->x); a.z = view(p->z);
+    a.ev = p->event_idx;
+    bind_jumps(a, *p);
     a.xo = p->x_pred; a.xre = p->x_re; a.xre_st = p->xre_stride_t; a.xre_sb = p->xre_stride_b; a.xh_out = p->xh_out;
-    return launch_dpp<true>(a, static_cast<hipStream_t>(stream)) == hipSuccess ? PSNODE_OK : PSNODE_ERR_HIP;
+    return ok_or_hip(launch_dpp<true>(a, static_cast<hipStream_t>(stream)));
 }
 
 }  // extern "C"

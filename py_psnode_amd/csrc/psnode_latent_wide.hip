@@ -16,7 +16,7 @@
 // beyond H are redirected to column 0 and masked.
 #include <cstring>
 
-#include "psnode_common.h"
+#include "psnode_launch.h"
 
 namespace psnode {
 namespace {
@@ -428,29 +428,17 @@ __global__ __launch_bounds__(64 * NWV) void latent_wide_bwd_kernel(const BwdWDev
 }
 
 bool two_h(const MlpDev& m, int in_dim, int H) { return m.n_layers == 2 && m.in_dim == in_dim && m.out_dim[0] == H && m.out_dim[1] == H; }
-bool al4w(const ViewDev& v) { return v.p && (reinterpret_cast<uintptr_t>(v.p) & 15) == 0 && v.st % 4 == 0 && v.sb % 4 == 0; }
+bool al4w(const ViewDev& v) { return v.p && !misaligned16(v.p) && v.st % 4 == 0 && v.sb % 4 == 0; }
 
 template <int METHOD, int NWV>
 hipError_t launchw_method(const IntegrateDev& a, bool dae, const f4* img, hipStream_t s) {
     const dim3 grid((unsigned)((a.B + 15) / 16)), block(64 * NWV);
-    if (a.sact) {       // training forward
-        if (!dae) hipLaunchKernelGGL((latent_wide_kernel<METHOD, 1, false, NWV, true>), grid, block, 0, s, a, img);
-        else if (a.zd) hipLaunchKernelGGL((latent_wide_kernel<METHOD, 3, true, NWV, true>), grid, block, 0, s, a, img);
-        else hipLaunchKernelGGL((latent_wide_kernel<METHOD, 2, true, NWV, true>), grid, block, 0, s, a, img);
-        return hipGetLastError();
-    }
-    if (!dae) hipLaunchKernelGGL((latent_wide_kernel<METHOD, 1, false, NWV>), grid, block, 0, s, a, img);
-    else if (a.zd) hipLaunchKernelGGL((latent_wide_kernel<METHOD, 3, true, NWV>), grid, block, 0, s, a, img);
-    else hipLaunchKernelGGL((latent_wide_kernel<METHOD, 2, true, NWV>), grid, block, 0, s, a, img);
-    return hipGetLastError();
-}
-template <int NWV>
-hipError_t launchw_nw(const IntegrateDev& a, bool dae, const f4* img, hipStream_t s) {
-    switch (a.method) {
-        case PSNODE_EULER: return launchw_method<PSNODE_EULER, NWV>(a, dae, img, s);
-        case PSNODE_MIDPOINT: return launchw_method<PSNODE_MIDPOINT, NWV>(a, dae, img, s);
-        default: return launchw_method<PSNODE_RK4_38, NWV>(a, dae, img, s);
-    }
+    return with_flag(a.sact != nullptr, [&](auto save) {       // saved rows: the training forward
+        constexpr bool SAVE = decltype(save)::value;
+        if (!dae) return launch(&latent_wide_kernel<METHOD, 1, false, NWV, SAVE>, grid, block, 0, s, a, img);
+        if (a.zd) return launch(&latent_wide_kernel<METHOD, 3, true, NWV, SAVE>, grid, block, 0, s, a, img);
+        return launch(&latent_wide_kernel<METHOD, 2, true, NWV, SAVE>, grid, block, 0, s, a, img);
+    });
 }
 
 }  // namespace
@@ -467,13 +455,12 @@ bool latentw_shape_ok(const IntegrateDev& a, bool dae) {
 }
 
 bool latentw_ptrs_ok(const IntegrateDev& a, bool dae) {
-    auto mis = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
-    if (mis(a.a0) || mis(a.xo)) return false;
-    if (!dae) return al4w(a.x) && al4w(a.z) && (!a.ev || (!mis(a.zj) && a.zjb % 4 == 0 && a.zje % 4 == 0));
-    if (mis(a.x_init) || mis(a.io) || !al4w(a.v) || (a.zd && !al4w(a.z))) return false;
+    if (misaligned16(a.a0) || misaligned16(a.xo)) return false;
+    if (!dae) return al4w(a.x) && al4w(a.z) && (!a.ev || (!misaligned16(a.zj) && a.zjb % 4 == 0 && a.zje % 4 == 0));
+    if (misaligned16(a.x_init) || misaligned16(a.io) || !al4w(a.v) || (a.zd && !al4w(a.z))) return false;
     if (a.ev) {
-        if (a.zd && (mis(a.zj) || a.zjb % 4 || a.zje % 4)) return false;
-        if (mis(a.vj) || a.vjb % 4 || a.vje % 4) return false;
+        if (a.zd && (misaligned16(a.zj) || a.zjb % 4 || a.zje % 4)) return false;
+        if (misaligned16(a.vj) || a.vjb % 4 || a.vje % 4) return false;
     }
     return true;
 }
@@ -500,7 +487,10 @@ hipError_t launch_latent_wide(const IntegrateDev& a, bool dae, float* pack, hipS
     hipLaunchKernelGGL(packw_kernel, dim3(256), dim3(256), 0, stream, p);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    return nw == 4 ? launchw_nw<4>(a, dae, p.out, stream) : launchw_nw<8>(a, dae, p.out, stream);
+    const f4* img = p.out;
+    return with_method(a.method, [&](auto m) {
+        return pick<4, 8>(nw, [&](auto w) { return launchw_method<decltype(m)::value, decltype(w)::value>(a, dae, img, stream); });
+    });
 }
 
 
@@ -531,10 +521,9 @@ int32_t psnode_latent_backward_wide_f32(const psnode_latent_bwd_wide_args_f32* p
     if (p->T > 1 && (!p->saved_act || !p->gk || !p->d1 || !p->d1s)) return PSNODE_ERR_NULL;
     if (p->dae && (!p->saved_ae_act || !p->gi || !p->da1 || !p->ae.weight[0] || !p->ae.weight[1])) return PSNODE_ERR_NULL;
     if (p->dae && p->event_idx && (!p->saved_ev_act || !p->gi_ev || !p->da1_ev)) return PSNODE_ERR_NULL;
-    auto mis = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) != 0; };
-    if (mis(p->grad_xs) || mis(p->grad_is) || mis(p->saved_act) || mis(p->saved_ae_act) || mis(p->saved_ev_act) || mis(p->gk) || mis(p->d1) ||
-        mis(p->d1s) || mis(p->gi) || mis(p->da1) || mis(p->gi_ev) || mis(p->da1_ev) || mis(p->grad_x0)) return PSNODE_ERR_DIMS;
-    if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 255) || workspace_bytes < psnode_latent_backward_wide_workspace_bytes(H)) return PSNODE_ERR_WORKSPACE;
+    if (misaligned16(p->grad_xs) || misaligned16(p->grad_is) || misaligned16(p->saved_act) || misaligned16(p->saved_ae_act) || misaligned16(p->saved_ev_act) || misaligned16(p->gk) || misaligned16(p->d1) ||
+        misaligned16(p->d1s) || misaligned16(p->gi) || misaligned16(p->da1) || misaligned16(p->gi_ev) || misaligned16(p->da1_ev) || misaligned16(p->grad_x0)) return PSNODE_ERR_DIMS;
+    if (!workspace_ok(workspace, workspace_bytes, psnode_latent_backward_wide_workspace_bytes(H))) return PSNODE_ERR_WORKSPACE;
     hipStream_t s = static_cast<hipStream_t>(stream);
     PackWT pk;
     pk.nw = nw; pk.H = H; pk.nblk = nblk; pk.dae = p->dae ? 1 : 0;
@@ -545,32 +534,19 @@ int32_t psnode_latent_backward_wide_f32(const psnode_latent_bwd_wide_args_f32* p
     BwdWDev a;
     memset(&a, 0, sizeof(a));
     a.method = p->method; a.H = H; a.zd = p->z_dim; a.dae = p->dae; a.T = p->T; a.B = p->B;
-    a.t = ViewDev{p->t.ptr, p->t.stride_t, p->t.stride_b};
+    a.t = view(p->t);
     a.ev = p->event_idx; a.gxs = p->grad_xs; a.gis = p->grad_is;
     a.sact = p->saved_act; a.saeact = p->saved_ae_act; a.sevact = p->saved_ev_act;
     a.gk = p->gk; a.d1 = p->d1; a.d1s = p->d1s; a.gi = p->gi; a.da1 = p->da1; a.gi_ev = p->gi_ev; a.da1_ev = p->da1_ev; a.gx0 = p->grad_x0;
     const dim3 grid((unsigned)((a.B + 15) / 16));
     const f4* img = pk.out;
-#define PSNODE_LW(METHOD_, DAE_)                                                                                                         \
-    {                                                                                                                                    \
-        if (nw == 4) hipLaunchKernelGGL((latent_wide_bwd_kernel<METHOD_, DAE_, 4>), grid, dim3(256), 0, s, a, img);                      \
-        else hipLaunchKernelGGL((latent_wide_bwd_kernel<METHOD_, DAE_, 8>), grid, dim3(512), 0, s, a, img);                              \
-    }
-    if (p->dae) {
-        switch (p->method) {
-            case PSNODE_EULER: PSNODE_LW(PSNODE_EULER, true) break;
-            case PSNODE_MIDPOINT: PSNODE_LW(PSNODE_MIDPOINT, true) break;
-            default: PSNODE_LW(PSNODE_RK4_38, true) break;
-        }
-    } else {
-        switch (p->method) {
-            case PSNODE_EULER: PSNODE_LW(PSNODE_EULER, false) break;
-            case PSNODE_MIDPOINT: PSNODE_LW(PSNODE_MIDPOINT, false) break;
-            default: PSNODE_LW(PSNODE_RK4_38, false) break;
-        }
-    }
-#undef PSNODE_LW
-    return hipGetLastError() == hipSuccess ? PSNODE_OK : PSNODE_ERR_HIP;
+    return ok_or_hip(with_method(p->method, [&](auto m) {
+        return with_flag(p->dae != 0, [&](auto dae) {
+            return pick<4, 8>(nw, [&](auto w) {
+                return launch(&latent_wide_bwd_kernel<decltype(m)::value, decltype(dae)::value, decltype(w)::value>, grid, dim3(64 * decltype(w)::value), 0, s, a, img);
+            });
+        });
+    }));
 }
 
 }  // extern "C"

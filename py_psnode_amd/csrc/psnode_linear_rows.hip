@@ -14,7 +14,7 @@
 // a row's loads 64 contiguous bytes per instruction.  Scalar path (K < 16 or unaligned: the encoders' first layer, the decoders' gradient):
 // column 4 m + k.  Output: lane (g, j), register r = Y[row j][16 nt + 4 g + r]: one float4 store per lane and output tile (scalar stores
 // where Y's rows are not all 16-byte aligned; the same for the float4 loads of Hh).
-#include "psnode_common.h"
+#include "psnode_launch.h"
 
 namespace psnode {
 namespace {
@@ -130,17 +130,11 @@ template <int KS, bool VEC>
 hipError_t lr_launch(const LinRowsDev& d, hipStream_t s) {
     const int NT = (d.N + 15) / 16, steps = VEC ? 4 * KS : KS;
     const size_t lds = (size_t)NT * steps * 64 * sizeof(float);
-    auto kern = &linear_rows_kernel<KS, VEC>;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
     const long long tiles = (d.rows + 16 * kLrRT - 1) / (16 * kLrRT);
     long long nwg = (tiles + 3) / 4;
     if (nwg > 2048) nwg = 2048;                 // grid-stride over the row tiles: the weight image is built once per workgroup
     if (nwg < 1) nwg = 1;
-    hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(256), lds, s, d);
-    return hipGetLastError();
+    return launch_attr(lds > 48 * 1024, &linear_rows_kernel<KS, VEC>, dim3((unsigned)nwg), dim3(256), lds, s, d);
 }
 
 }  // namespace
@@ -170,24 +164,11 @@ extern "C" int32_t psnode_linear_rows_f32(const psnode_linear_rows_args_f32* a, 
     const bool vec = (a->K % 16 == 0) && lr_vec4(a->X, a->ldx);
     hipError_t e;
     if (vec) {
-        switch (a->K / 16) {
-            case 1: e = lr_launch<1, true>(d, s); break;
-            case 2: e = lr_launch<2, true>(d, s); break;
-            case 3: e = lr_launch<3, true>(d, s); break;
-            case 4: e = lr_launch<4, true>(d, s); break;
-            case 5: e = lr_launch<5, true>(d, s); break;
-            case 6: e = lr_launch<6, true>(d, s); break;
-            case 7: e = lr_launch<7, true>(d, s); break;
-            default: e = lr_launch<8, true>(d, s); break;
-        }
+        e = pick<1, 2, 3, 4, 5, 6, 7, 8>(a->K / 16, [&](auto ks) { return lr_launch<decltype(ks)::value, true>(d, s); });      // K <= 128
     } else {
-        const int ks = (a->K + 3) / 4;
-        if (ks <= 1) e = lr_launch<1, false>(d, s);
-        else if (ks <= 2) e = lr_launch<2, false>(d, s);
-        else if (ks <= 4) e = lr_launch<4, false>(d, s);
-        else if (ks <= 8) e = lr_launch<8, false>(d, s);
-        else if (ks <= 16) e = lr_launch<16, false>(d, s);
-        else e = lr_launch<32, false>(d, s);
+        int ks = 1;      // (K + 3) / 4 rounded up to a power of two, <= 32
+        while (ks < (a->K + 3) / 4) ks *= 2;
+        e = pick<1, 2, 4, 8, 16, 32>(ks, [&](auto k) { return lr_launch<decltype(k)::value, false>(d, s); });
     }
-    return e == hipSuccess ? PSNODE_OK : PSNODE_ERR_HIP;
+    return ok_or_hip(e);
 }

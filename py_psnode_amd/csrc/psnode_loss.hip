@@ -9,7 +9,7 @@
 // row per workgroup -> a second tiny kernel adds the partial rows in double, fixed order (run-to-run bit-identical).
 // Shapes off the fast path (D not a power of two, unaligned or oddly strided views) take the scalar kernel below it.
 // Replaces: neural_00_ODE_01_no_encode.py:353-355, neural_01_DAE_01_no_encode.py:414-419 (include/psnode_hip.h).
-#include "psnode_common.h"
+#include "psnode_launch.h"
 
 namespace psnode {
 namespace {
@@ -361,5 +361,5 @@ extern "C" int32_t psnode_masked_mse_f32(const psnode_loss_args_f32* a, void* wo
     }
     if (e != hipSuccess) return PSNODE_ERR_HIP;
     hipLaunchKernelGGL(masked_mse_finish_kernel, dim3(1), dim3(NT), 0, s, d.partial, rows, a->D, a->out);
-    return hipGetLastError() == hipSuccess ? PSNODE_OK : PSNODE_ERR_HIP;
+    return ok_or_hip(hipGetLastError());
 }

@@ -31,6 +31,7 @@
 #pragma once
 #include <type_traits>
 
+#include "psnode_launch.h"
 #include "psnode_pack.h"
 
 namespace psnode {
@@ -722,96 +723,39 @@ template <int NWV, int METHOD, int NXR = kNXc>
 hipError_t launch_shape(const IntegrateDev& a, bool dae, const float* pde, const float* pae, int NA, hipStream_t s) {
     const dim3 grid((unsigned)((a.B + TBM - 1) / TBM)), block(64 * NWV);
     const int NZM = nzm_of(a, dae), NZA = dae ? nza_of(a) : 0;
-#define PSNODE_LAUNCH(NZM_, NZA_, DAE_)                                                                                    \
-    {                                                                                                                      \
-        auto kern = &integrate_mfma_kernel<METHOD, NXR, NZM_, NZA_, DAE_, NWV>;                                           \
-        const size_t lds = ae_weights_in_lds(DAE_, NWV) ? ae_lds_bytes(NWV) : 0;                                           \
-        if (lds) {                                                                                                         \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                                        \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                      \
-            if (e != hipSuccess) return e;                                                                                 \
-        }                                                                                                                  \
-        hipLaunchKernelGGL(kern, grid, block, lds, s, a, pde, pae, NA);                                                    \
-        return hipGetLastError();                                                                                          \
-    }
+    // one instance: NZM alone (ODE) or the pair NZM * 10 + NZA (DAE), as pick() hands it over
+    auto ode = [&](auto save) {
+        return [&, save](auto nzm) {
+            return launch(&integrate_mfma_kernel<METHOD, NXR, decltype(nzm)::value, 0, false, NWV, decltype(save)::value>, grid, block, 0, s,
+                          a, pde, pae, NA);
+        };
+    };
+    auto daek = [&](auto save) {
+        return [&, save](auto pair) {
+            constexpr int P = decltype(pair)::value;
+            return launch(&integrate_mfma_kernel<METHOD, NXR, P / 10, P % 10, true, NWV, decltype(save)::value>, grid, block,
+                          ae_weights_in_lds(true, NWV) ? ae_lds_bytes(NWV) : 0, s, a, pde, pae, NA);
+        };
+    };
     if constexpr (NXR == kNXc && !weights_streamed(NWV)) {      // the training forwards exist where a fused backward does (hidden <= 128)
         if (!dae && a.sact) {
             if (a.flags & PSNODE_FLAG_INPUT_TRUE_X) return hipErrorNotSupported;
-#define PSNODE_LAUNCH_SAVE(NZM_)                                                                                           \
-    {                                                                                                                      \
-        hipLaunchKernelGGL((integrate_mfma_kernel<METHOD, NXR, NZM_, 0, false, NWV, true>), grid, block, 0, s, a, pde, pae, NA); \
-        return hipGetLastError();                                                                                          \
-    }
-            switch (NZM) {
-                case 0: PSNODE_LAUNCH_SAVE(0)
-                case 1: PSNODE_LAUNCH_SAVE(1)
-                case 2: PSNODE_LAUNCH_SAVE(2)
-                case 3: PSNODE_LAUNCH_SAVE(3)
-                case 4: PSNODE_LAUNCH_SAVE(4)
-                default: return hipErrorNotSupported;
-            }
-#undef PSNODE_LAUNCH_SAVE
+            return pick<0, 1, 2, 3, 4>(NZM, ode(std::true_type{}));
         }
-    }
-    if constexpr (NXR == kNXc && !weights_streamed(NWV)) {
         if (dae && a.sact) {
             if (a.flags & (PSNODE_FLAG_INPUT_TRUE_I | PSNODE_FLAG_INPUT_TRUE_X)) return hipErrorNotSupported;
-#define PSNODE_LAUNCH_SAVE(NZM_, NZA_)                                                                                     \
-    {                                                                                                                      \
-        auto kern = &integrate_mfma_kernel<METHOD, NXR, NZM_, NZA_, true, NWV, true>;                              \
-        const size_t lds = ae_weights_in_lds(true, NWV) ? ae_lds_bytes(NWV) : 0;                                           \
-        if (lds) {                                                                                                         \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                                        \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                      \
-            if (e != hipSuccess) return e;                                                                                 \
-        }                                                                                                                  \
-        hipLaunchKernelGGL(kern, grid, block, lds, s, a, pde, pae, NA);                                                    \
-        return hipGetLastError();                                                                                          \
-    }
-            switch (NZM * 10 + NZA) {
-                case 11: PSNODE_LAUNCH_SAVE(1, 1)
-                case 21: PSNODE_LAUNCH_SAVE(2, 1)
-                case 31: PSNODE_LAUNCH_SAVE(3, 1)
-                case 41: PSNODE_LAUNCH_SAVE(4, 1)
-                case 32: PSNODE_LAUNCH_SAVE(3, 2)
-                case 42: PSNODE_LAUNCH_SAVE(4, 2)
-                default: return hipErrorNotSupported;
-            }
-#undef PSNODE_LAUNCH_SAVE
+            return pick<11, 21, 31, 41, 32, 42>(NZM * 10 + NZA, daek(std::true_type{}));
         }
     }
     if (a.sact) return hipErrorNotSupported;
     if (!streamed_class_ok(NWV, dae, NXR != kNXc, NZM)) return hipErrorNotSupported;
     if (!dae) {
         if constexpr (!streamed_class_ok(NWV, false, NXR != kNXc, 0)) return hipErrorNotSupported;
-        else
-        switch (NZM) {
-            case 0: PSNODE_LAUNCH(0, 0, false)
-            case 1: PSNODE_LAUNCH(1, 0, false)
-            case 2: PSNODE_LAUNCH(2, 0, false)
-            case 3: PSNODE_LAUNCH(3, 0, false)
-            case 4: PSNODE_LAUNCH(4, 0, false)
-            default: return hipErrorNotSupported;
-        }
+        else return pick<0, 1, 2, 3, 4>(NZM, ode(std::false_type{}));
     }
     if constexpr (NXR != kNXc || !streamed_class_ok(NWV, true, false, 1)) return hipErrorNotSupported;     // the DAE kernels hold two register-resident MLPs: x_dim <= 8
-    else
-    switch (NZM * 10 + NZA) {
-        case 11: PSNODE_LAUNCH(1, 1, true)
-        case 21: PSNODE_LAUNCH(2, 1, true)
-        case 31: PSNODE_LAUNCH(3, 1, true)
-        case 32: PSNODE_LAUNCH(3, 2, true)
-        default:
-            if constexpr (streamed_class_ok(NWV, true, false, 4)) {
-                switch (NZM * 10 + NZA) {
-                    case 41: PSNODE_LAUNCH(4, 1, true)
-                    case 42: PSNODE_LAUNCH(4, 2, true)
-                    default: return hipErrorNotSupported;
-                }
-            }
-            return hipErrorNotSupported;
-    }
-#undef PSNODE_LAUNCH
+    else if constexpr (streamed_class_ok(NWV, true, false, 4)) return pick<11, 21, 31, 32, 41, 42>(NZM * 10 + NZA, daek(std::false_type{}));
+    else return pick<11, 21, 31, 32>(NZM * 10 + NZA, daek(std::false_type{}));
 }
 
 template <int NWV, int METHOD>
@@ -845,32 +789,23 @@ hipError_t launch_mfma_nw(const IntegrateDev& a, bool dae, float* pack, hipStrea
     PackMfma p;
     p.ae = 0; p.nw = NWV; p.xd = a.xd; p.ne = ne; p.n = a.xd + ne; p.nzv = a.zd + (dae ? a.vd : 0);
     p.NX = a.xd > 4 * kNXc ? kNXw : kNXc; p.NB = 0; p.NE = NZM; p.NA = NA; p.fold = 1; p.hreal = a.de.out_dim[0];
-    p.w1 = a.de.w[0]; p.b1 = a.de.bias[0]; p.w2 = a.de.w[1]; p.b2 = a.de.bias[1];
-    p.w3 = a.de.w[2]; p.b3 = a.de.bias[2]; p.w4 = a.de.w[3]; p.b4 = a.de.bias[3];
+    set_layers(p, a.de);
     p.out_dim = a.xd;
     p.scaled = (a.sact || !PSNODE_SCALED_ELU) ? 0 : 1;        // the inference instances (SAVE = false) run the hidden layers in the log2e-scaled domain
-    PackMfma q = p;
-    q.ae = 1; q.NB = 0; q.NE = nza_of(a); q.fold = 0;
+    PackMfma q = ae_pack(p, nza_of(a), a.ae, a.id, nullptr);      // (the ODE's is counted only)
     Arena A{pack};
     const MfmaPack L = mfma_layout(NWV, NA, dae, pack_fwd_count(p), pack_fwd_count(q), A);
     p.out = L.de;
     hipLaunchKernelGGL(pack_mfma_kernel, dim3(16), dim3(256), 0, stream, p);
     if constexpr (weights_streamed(NWV)) hipLaunchKernelGGL(pack_stream_kernel, dim3(64), dim3(256), 0, stream, p, reinterpret_cast<f4*>(L.de_stream));
     if (dae) {
-        q.w1 = a.ae.w[0]; q.b1 = a.ae.bias[0]; q.w2 = a.ae.w[1]; q.b2 = a.ae.bias[1];
-        q.w3 = a.ae.w[2]; q.b3 = a.ae.bias[2]; q.w4 = a.ae.w[3]; q.b4 = a.ae.bias[3];
-        q.out_dim = a.id;
         q.out = L.ae;
         hipLaunchKernelGGL(pack_mfma_kernel, dim3(16), dim3(256), 0, stream, q);
         if constexpr (weights_streamed(NWV)) hipLaunchKernelGGL(pack_stream_kernel, dim3(64), dim3(256), 0, stream, q, reinterpret_cast<f4*>(L.ae_stream));
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    switch (a.method) {
-        case PSNODE_EULER: return launch_method<NWV, PSNODE_EULER>(a, dae, L.de, L.ae, NA, stream);
-        case PSNODE_MIDPOINT: return launch_method<NWV, PSNODE_MIDPOINT>(a, dae, L.de, L.ae, NA, stream);
-        default: return launch_method<NWV, PSNODE_RK4_38>(a, dae, L.de, L.ae, NA, stream);
-    }
+    return with_method(a.method, [&](auto m) { return launch_method<NWV, decltype(m)::value>(a, dae, L.de, L.ae, NA, stream); });
 }
 
 }  // namespace

@@ -3,6 +3,7 @@
 #pragma once
 #include <type_traits>
 
+#include "psnode_launch.h"
 #include "psnode_pack.h"
 
 namespace psnode {

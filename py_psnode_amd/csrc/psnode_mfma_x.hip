@@ -501,26 +501,9 @@ hipError_t launch_x_method(const IntegrateDev& a, const float* pack, hipStream_t
     const long long tiles = (a.B + 3) / 4;
     const dim3 grid((unsigned)((tiles + kXWaves - 1) / kXWaves)), block(64 * kXWaves * (ROLES ? 2 : 1));
     const size_t lds = ROLES ? (size_t)kXWaves * kXRingFloats * sizeof(float) : 0;
-#define PSNODE_X(NZM_)                                                                                                            \
-    {                                                                                                                             \
-        auto kern = &integrate_x_kernel<METHOD, NZM_, SAVE, ROLES>;                                                               \
-        if (lds > 48 * 1024) {                                                                                                    \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-            if (e != hipSuccess) return e;                                                                                        \
-        }                                                                                                                         \
-        hipLaunchKernelGGL(kern, grid, block, lds, s, a, pack);                                                                   \
-    }                                                                                                                             \
-    break;
-    switch ((2 * a.zd + 3) / 4) {
-        case 0: PSNODE_X(0)
-        case 1: PSNODE_X(1)
-        case 2: PSNODE_X(2)
-        case 3: PSNODE_X(3)
-        case 4: PSNODE_X(4)
-        default: return hipErrorNotSupported;
-    }
-#undef PSNODE_X
-    return hipGetLastError();
+    return pick<0, 1, 2, 3, 4>((2 * a.zd + 3) / 4, [&](auto nzm) {
+        return launch(&integrate_x_kernel<METHOD, decltype(nzm)::value, SAVE, ROLES>, grid, block, lds, s, a, pack);
+    });
 }
 
 }  // namespace
@@ -551,25 +534,15 @@ size_t mfma_x_pack_floats() { return (size_t)XRegs::COUNT * 64; }
 hipError_t launch_mfma_x(const IntegrateDev& a, float* pack, hipStream_t stream) {
     PackX p;
     p.xd = a.xd; p.zd = a.zd; p.n = a.xd + a.zd; p.hreal = a.de.out_dim[0];
-    p.w1 = a.de.w[0]; p.b1 = a.de.bias[0]; p.w2 = a.de.w[1]; p.b2 = a.de.bias[1];
-    p.w3 = a.de.w[2]; p.b3 = a.de.bias[2]; p.w4 = a.de.w[3]; p.b4 = a.de.bias[3];
+    set_layers(p, a.de);
     p.out = pack;
     p.sc = a.sact ? 1.0f : kLog2e;
     hipLaunchKernelGGL(pack_x_kernel, dim3(16), dim3(256), 0, stream, p);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    if (a.sact) {
-        switch (a.method) {
-            case PSNODE_EULER: return launch_x_method<PSNODE_EULER, true>(a, pack, stream);
-            case PSNODE_MIDPOINT: return launch_x_method<PSNODE_MIDPOINT, true>(a, pack, stream);
-            default: return launch_x_method<PSNODE_RK4_38, true>(a, pack, stream);
-        }
-    }
-    switch (a.method) {
-        case PSNODE_EULER: return launch_x_method<PSNODE_EULER, false>(a, pack, stream);
-        case PSNODE_MIDPOINT: return launch_x_method<PSNODE_MIDPOINT, false>(a, pack, stream);
-        default: return launch_x_method<PSNODE_RK4_38, false>(a, pack, stream);
-    }
+    return with_method(a.method, [&](auto m) {
+        return with_flag(a.sact != nullptr, [&](auto save) { return launch_x_method<decltype(m)::value, decltype(save)::value>(a, pack, stream); });
+    });
 }
 
 }  // namespace psnode

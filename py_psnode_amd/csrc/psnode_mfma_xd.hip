@@ -463,8 +463,7 @@ size_t mfma_xd_pack_floats() { return (size_t)XDRegs::COUNT * 64 + (size_t)XDReg
 hipError_t launch_mfma_xd(const IntegrateDev& a, float* pack, hipStream_t stream) {
     PackXD p;
     p.xd = a.xd; p.zd = a.zd; p.vd = a.vd; p.id = a.id; p.hreal = a.de.out_dim[0];
-    p.w1 = a.de.w[0]; p.b1 = a.de.bias[0]; p.w2 = a.de.w[1]; p.b2 = a.de.bias[1];
-    p.w3 = a.de.w[2]; p.b3 = a.de.bias[2]; p.w4 = a.de.w[3]; p.b4 = a.de.bias[3];
+    set_layers(p, a.de);
     p.aw1 = a.ae.w[0]; p.ab1 = a.ae.bias[0]; p.aw2 = a.ae.w[1]; p.ab2 = a.ae.bias[1];
     p.aw3 = a.ae.w[2]; p.ab3 = a.ae.bias[2]; p.aw4 = a.ae.w[3]; p.ab4 = a.ae.bias[3];
     p.out = pack;
@@ -474,16 +473,11 @@ hipError_t launch_mfma_xd(const IntegrateDev& a, float* pack, hipStream_t stream
     if (e != hipSuccess) return e;
     const long long tiles = (a.B + 3) / 4;
     const dim3 grid((unsigned)((tiles + kXWaves - 1) / kXWaves)), block(64 * kXWaves);
-#define PSNODE_XD(M_)                                                                                          \
-    if (a.sact) hipLaunchKernelGGL((integrate_xd_kernel<M_, true>), grid, block, 0, stream, a, pack);          \
-    else hipLaunchKernelGGL((integrate_xd_kernel<M_, false>), grid, block, 0, stream, a, pack);
-    switch (a.method) {
-        case PSNODE_EULER: PSNODE_XD(PSNODE_EULER) break;
-        case PSNODE_MIDPOINT: PSNODE_XD(PSNODE_MIDPOINT) break;
-        default: PSNODE_XD(PSNODE_RK4_38) break;
-    }
-#undef PSNODE_XD
-    return hipGetLastError();
+    return with_method(a.method, [&](auto m) {
+        return with_flag(a.sact != nullptr, [&](auto save) {
+            return launch(&integrate_xd_kernel<decltype(m)::value, decltype(save)::value>, grid, block, 0, stream, a, pack);
+        });
+    });
 }
 
 }  // namespace psnode

@@ -14,7 +14,7 @@
 // Gradients accumulate in registers over all of a wave's tiles; per-wave partials, summed in a fixed order (deterministic).
 #include <string.h>
 
-#include "psnode_common.h"
+#include "psnode_launch.h"
 
 namespace psnode {
 namespace {
@@ -290,7 +290,7 @@ extern "C" int32_t psnode_recon_rows_f32(const psnode_mlp_f32* enc, const psnode
     long long blocks = (tiles + 3) / 4;
     if (blocks > 256 * 8) blocks = 256 * 8;
     hipLaunchKernelGGL(recon_fwd_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), a);
-    return hipGetLastError() == hipSuccess ? PSNODE_OK : PSNODE_ERR_HIP;
+    return ok_or_hip(hipGetLastError());
 }
 
 extern "C" int64_t psnode_recon_rows_param_count(const psnode_mlp_f32* enc, const psnode_mlp_f32* dec) {
@@ -323,5 +323,5 @@ extern "C" int32_t psnode_recon_rows_backward_f32(const psnode_mlp_f32* enc, con
     if (hipGetLastError() != hipSuccess) return PSNODE_ERR_HIP;
     hipLaunchKernelGGL(recon_reduce_stage1, dim3((np + 255) / 256, kReconSlices), dim3(256), 0, s, L.part, L.mid, np, (int)(blocks * 4));
     hipLaunchKernelGGL(recon_reduce_stage2, dim3((np + 255) / 256), dim3(256), 0, s, L.mid, grad_params, np);
-    return hipGetLastError() == hipSuccess ? PSNODE_OK : PSNODE_ERR_HIP;
+    return ok_or_hip(hipGetLastError());
 }

@@ -6,7 +6,7 @@
 // coalesced 8/16-byte accesses (lane (g, row) reads columns NM*g .. NM*g+NM-1), keeps the hidden tile in registers
 // (D rows of L1 are the B operands of L2, as in psnode_latent.hip) and writes one float4 per lane.  Weights (< 1 KB)
 // sit in VGPRs; nothing is staged through LDS.
-#include "psnode_common.h"
+#include "psnode_launch.h"
 
 namespace psnode {
 namespace {
@@ -538,7 +538,7 @@ extern "C" int32_t psnode_mlp_rows_f32(const psnode_mlp_f32* m, int64_t rows, co
     if (H == 16) launch_rows<1, 1>(NM, grid, block, s, a);
     else if (OT == 1) launch_rows<4, 1>(NM, grid, block, s, a);
     else launch_rows<4, 4>(NM, grid, block, s, a);
-    return hipGetLastError() == hipSuccess ? PSNODE_OK : PSNODE_ERR_HIP;
+    return ok_or_hip(hipGetLastError());
 }
 
 extern "C" size_t psnode_mlp_rows_backward_workspace_bytes(const psnode_mlp_f32* m, int64_t rows) {
@@ -572,7 +572,7 @@ extern "C" int32_t psnode_mlp_rows_backward_f32(const psnode_mlp_f32* m, int64_t
     if (!grad_params) return PSNODE_OK;
     hipLaunchKernelGGL(rows_reduce_stage1, dim3((np + 255) / 256, kRedSlices), dim3(256), 0, s, L.part, L.mid, np, (int)(blocks * 4));
     hipLaunchKernelGGL(rows_reduce_stage2, dim3((np + 255) / 256), dim3(256), 0, s, L.mid, grad_params, np);
-    return hipGetLastError() == hipSuccess ? PSNODE_OK : PSNODE_ERR_HIP;
+    return ok_or_hip(hipGetLastError());
 }
 
 // One module applied to several row sets in a step (x_encoder over the grid rows AND the first row, z_encoder over grid rows, first row and
@@ -600,5 +600,5 @@ extern "C" int32_t psnode_mlp_rows_reduce_f32(const psnode_mlp_f32* m, int64_t n
     const RowsPartsLayout L = rows_parts_layout(n_parts, np, true, A);
     hipLaunchKernelGGL(rows_reduce_stage1, dim3((np + 255) / 256, kRedSlices), dim3(256), 0, s, L.part, L.mid, np, (int)n_parts);
     hipLaunchKernelGGL(rows_reduce_stage2, dim3((np + 255) / 256), dim3(256), 0, s, L.mid, grad_params, np);
-    return hipGetLastError() == hipSuccess ? PSNODE_OK : PSNODE_ERR_HIP;
+    return ok_or_hip(hipGetLastError());
 }
