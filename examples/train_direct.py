@@ -3,8 +3,8 @@
 
     npz dataset -> ResidentDataset/ResidentLoader (batches formed on the device)
                 -> ODE_Model / DAE_Model (fused integrator; direct_encode variants with the row kernels)
-                -> the script's loss on the fused loss kernel -> fused backward kernels -> Adam
-                -> evaluation (the scripts' per-dimension masked MSE) -> TorchScript export (save_model)
+                -> the script's loss on the fused loss kernel (--loss: the scripts' `Loss_func`, line 49) -> fused backward kernels -> Adam
+                -> evaluation (the scripts' per-sample, per-dimension table on the fused kernel) -> TorchScript export (save_model)
 
 It is the body of neural_00_ODE_01_no_encode.py:339-400 / neural_01_DAE_01_no_encode.py:405-470 without the logging,
 plotting and replay-buffer bookkeeping.  With --synthetic it writes a small dataset in the scripts' npz format first
@@ -12,6 +12,7 @@ plotting and replay-buffer bookkeeping.  With --synthetic it writes a small data
 
     python examples/train_direct.py --model ode01 --synthetic --epochs 3
     python examples/train_direct.py --model dae02 --train-data training.npz --test-data testing.npz --solver euler
+    python examples/train_direct.py --model dae02 --synthetic --loss huber --loss-param 0.05
 """
 import argparse
 import os
@@ -56,7 +57,7 @@ def build(model, solver):
     return models.DAE_Model(8, 2, 2, 2, H, direct_encode=model.endswith("02"), solver=s)
 
 
-def step_loss(model_name, model, batch):
+def step_loss(model_name, model, batch, loss_func=None):
     """forward + THAT script's training loss -- the four differ (py_psnode_amd/loss.py): ODE_01 masked term only
     (neural_00_ODE_01_no_encode.py:353-355), ODE_02 + x0 term + reconstruction (neural_00_ODE_02_direct_encode.py:267-270),
     DAE_01 with the 9x extra weight on x column 1 (neural_01_DAE_01_no_encode.py:414-419), DAE_02 without it and with both
@@ -65,20 +66,22 @@ def step_loss(model_name, model, batch):
         t, x, z, event_t, z_jump, mask = batch
         out = model(t=t, x=x, z=z, event_t=event_t, z_jump=z_jump)
         if model_name == "ode01":
-            return L.ode01_loss(out, x, mask)[0]
-        return L.ode02_loss(out[0], out[1], x, mask)[0]
+            return L.ode01_loss(out, x, mask, loss_func=loss_func)[0]
+        return L.ode02_loss(out[0], out[1], x, mask, loss_func=loss_func)[0]
     t, x, z, v, i, event_t, z_jump, v_jump, mask = batch
     out = model(t=t, x=x, z=z, v=v, i=i, event_t=event_t, z_jump=z_jump, v_jump=v_jump)
     if model_name == "dae01":
-        return L.dae01_loss(out[0], x, out[1], i, mask)[0]
-    return L.dae02_loss(out[0], out[1], out[2], out[3], x, i, mask)[0]
+        return L.dae01_loss(out[0], x, out[1], i, mask, loss_func=loss_func)[0]
+    return L.dae02_loss(out[0], out[1], out[2], out[3], x, i, mask, loss_func=loss_func)[0]
 
 
 @torch.no_grad()
-def evaluate(model_name, model, loader):
-    """x_loss_total of evalute_model (neural_00_ODE_01_no_encode.py:104-129): masked squared error over sum(mask)"""
-    num = torch.zeros((), device=loader.dataset.device)
-    den = torch.zeros((), device=loader.dataset.device)
+def evaluate(model_name, model, loader, loss_func=None):
+    """evalute_model (neural_00_ODE_01_no_encode.py:104-129): the per-sample table
+    `torch.sum(Loss_func(x_pred * mask, x * mask, reduction='none'), dim=1)` of every batch, summed over the samples and divided by the
+    mask count -> (x_loss_dim_i for every column, x_loss_total)."""
+    dev = loader.dataset.device
+    num, den = None, torch.zeros((), device=dev)
     for batch in loader:
         x, mask = batch[1], batch[-1]
         if model_name.startswith("ode"):
@@ -86,10 +89,17 @@ def evaluate(model_name, model, loader):
         else:
             out = model(t=batch[0], x=x, z=batch[2], v=batch[3], i=batch[4], event_t=batch[5], z_jump=batch[6], v_jump=batch[7])
         pred = out[0] if isinstance(out, tuple) else out
-        terms = L.masked_mse_terms(pred, x, mask.expand_as(x).contiguous() if mask.shape[-1] not in (1, x.shape[-1]) else mask)[0]
-        num += terms[:x.shape[-1]].sum()
+        table = L.per_sample_loss(pred, x, mask.expand_as(x).contiguous() if mask.shape[-1] not in (1, x.shape[-1]) else mask, loss_func)
+        num = table.sum(0) if num is None else num + table.sum(0)
         den += mask.sum()
-    return float(num / den)
+    dims = (num / den).tolist()
+    return dims, float(num.sum() / den)
+
+
+def report(epoch, dims, total):
+    for k, v in enumerate(dims):
+        print(f"epoch {epoch}: x_loss_dim_{k} {v:.6e}")
+    print(f"epoch {epoch}: test x_loss_total {total:.6e}")
 
 
 def main(argv=None):
@@ -104,6 +114,8 @@ def main(argv=None):
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--epochs", type=int, default=3)
     ap.add_argument("--lr", type=float, default=1e-3)
+    ap.add_argument("--loss", default="mse", choices=["mse", "l1", "smooth_l1", "huber"], help="the scripts' Loss_func (line 49 of each)")
+    ap.add_argument("--loss-param", type=float, default=None, help="beta of smooth_l1 / delta of huber (torch's default: 1)")
     ap.add_argument("--save", default=None, help="directory for the TorchScript export (save_model)")
     args = ap.parse_args(argv)
     dev = torch.device("cuda", 0)
@@ -122,8 +134,10 @@ def main(argv=None):
     model = build(args.model, args.solver).to(dev)
     model.solver.fused = "require"           # fail loudly rather than walk the time loop in Python
     opt = torch.optim.Adam(model.parameters(), lr=args.lr)
-    history = [evaluate(args.model, model, test_loader)]
-    print(f"epoch 0: test x_loss_total {history[0]:.6e}")
+    loss_func = L.loss_kind_of(args.loss if args.loss_param is None else (args.loss, args.loss_param))
+    dims, total = evaluate(args.model, model, test_loader, loss_func)
+    history = [total]
+    report(0, dims, total)
     for epoch in range(1, args.epochs + 1):
         model.train()
         torch.cuda.synchronize()
@@ -131,14 +145,16 @@ def main(argv=None):
         steps = 0
         for batch in train_loader:
             opt.zero_grad()
-            loss = step_loss(args.model, model, batch)
+            loss = step_loss(args.model, model, batch, loss_func)
             loss.backward()
             opt.step()
             steps += batch[0].shape[0] * (batch[0].shape[1] - 1)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         model.eval()
-        history.append(evaluate(args.model, model, test_loader))
+        dims, total = evaluate(args.model, model, test_loader, loss_func)
+        history.append(total)
+        report(epoch, dims, total)
         print(f"epoch {epoch}: train loss {float(loss.detach()):.6e}  test x_loss_total {history[-1]:.6e}  {steps / dt / 1e6:.1f} M state-steps/s")
     if args.save:
         model.save_model(args.save)

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define PSNODE_ABI_VERSION 10    /* 10 also carries the additive psnode_act_f32 / *_act_*, psnode_rk_tableau_f32 / *_rk_*, psnode_substeps_f32 / *_sub_* and *_lin_* entry points (end of this file) */
+#define PSNODE_ABI_VERSION 10    /* 10 also carries the additive psnode_act_f32 / *_act_*, psnode_rk_tableau_f32 / *_rk_*, psnode_substeps_f32 / *_sub_* and *_lin_* entry points (end of this file), and psnode_loss_fn_f32 / psnode_masked_loss_* / psnode_loss_per_sample_f32 (next to psnode_masked_mse_f32) */
 #define PSNODE_MAX_LAYERS 8      /* Linear layers per MLP */
 #define PSNODE_MAX_WIDTH 1024    /* widest layer OUTPUT the kernels accept */
 #define PSNODE_MAX_IN_WIDTH 2048 /* widest first-layer INPUT (the latent DE of DAE_02 at --hidden 128 is 12 x 128 = 1536 wide) */
@@ -527,6 +527,38 @@ typedef struct {
 
 size_t psnode_masked_mse_workspace_bytes(const psnode_loss_args_f32* args);
 int32_t psnode_masked_mse_f32(const psnode_loss_args_f32* args, void* workspace, size_t workspace_bytes, void* stream);
+
+/* K6 with another pointwise loss (additive, same ABI version): with e = pred - target,
+ *   PSNODE_LOSS_MSE        rho = e^2                                                   rho' = 2e
+ *   PSNODE_LOSS_L1         rho = |e|                                                   rho' = sign(e), 0 at e == 0 (torch's rule)
+ *   PSNODE_LOSS_SMOOTH_L1  rho = |e| < beta ? e^2 / (2 beta) : |e| - beta / 2          rho' = clamp(e / beta, -1, 1)       param = beta > 0
+ *   PSNODE_LOSS_HUBER      rho = |e| < delta ? e^2 / 2 : delta * (|e| - delta / 2)     rho' = clamp(e, -delta, delta)      param = delta > 0
+ * i.e. torch.nn.functional.mse_loss / l1_loss / smooth_l1_loss / huber_loss, the values `Loss_func`
+ * (neural_00_ODE_01_no_encode.py:49) takes.
+ *
+ * Training form: the contract above with rho in place of the square and rho' in grad_pred -- same args, same out[D+2], same
+ * grad_pred, same partial rows: psnode_masked_mse_workspace_bytes(args) is the workspace size of this call as well.  Kind MSE, or a
+ * NULL fn, forwards to the squared-error entry point above (bitwise its result).
+ *
+ * Per-sample evaluation form (all four kinds), the scripts' evalute_model line
+ *   `torch.sum(Loss_func(x_pred * mask, x * mask, reduction='none'), dim=1)` (neural_00_ODE_01_no_encode.py:123):
+ *   out[b,d] = sum_t rho(pred[t,b,d] * m[t,b,(d)] - target[t,b,d] * m[t,b,(d)])        args->out = device [B,D], contiguous
+ * The mask multiplies both operands as written (two rounded products, one rounded subtraction).  Every out[b,d] has one writer and one
+ * summation order: bitwise repeatable, no workspace.  col_weight / inv_norm / grad_pred must be NULL, scale 1 and t0_coef 0.
+ *
+ * Order of the checks, all before any launch: NULL args -> PSNODE_ERR_NULL; a kind outside 0..3, or a parameter of kinds 2 / 3 that is
+ * <= 0 or not finite -> PSNODE_ERR_UNSUPPORTED; (per-sample: a weight, norm, scale, t0_coef or grad_pred -> PSNODE_ERR_UNSUPPORTED;)
+ * then the checks of the squared-error entry point in its order with its statuses.  The `supported` query answers 1 where the training
+ * call gets as far as its workspace check (host only). */
+typedef enum { PSNODE_LOSS_MSE = 0, PSNODE_LOSS_L1 = 1, PSNODE_LOSS_SMOOTH_L1 = 2, PSNODE_LOSS_HUBER = 3 } psnode_loss_kind;
+typedef struct {
+    int32_t kind;                    /* psnode_loss_kind */
+    float param;                     /* beta / delta; ignored for MSE, L1 */
+} psnode_loss_fn_f32;
+
+int32_t psnode_masked_loss_supported(const psnode_loss_args_f32* args, const psnode_loss_fn_f32* fn);
+int32_t psnode_masked_loss_f32(const psnode_loss_args_f32* args, const psnode_loss_fn_f32* fn, void* workspace, size_t workspace_bytes, void* stream);
+int32_t psnode_loss_per_sample_f32(const psnode_loss_args_f32* args, const psnode_loss_fn_f32* fn, void* stream);
 
 /* The WHOLE forward of the direct_encode ODE model in one launch -- replaces ODE_Model.forward of
  * neural_00_ODE_02_direct_encode.py:74-89 (hidden_dim = 16, the script's default):

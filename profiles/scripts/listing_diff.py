@@ -1,6 +1,6 @@
 """Compare the device listings (*-hip-amdgcn-amd-amdhsa-gfx950.s, kept by the Makefile next to each object) of two builds, kernel by kernel.
 
-    python profiles/scripts/listing_diff.py BUILD_DIR_A BUILD_DIR_B [OBJECT_STEM ...]
+    python profiles/scripts/listing_diff.py [--rename REGEX=REPL ...] BUILD_DIR_A BUILD_DIR_B [OBJECT_STEM ...]
 
 Per object: the number of kernels, how many are identical, the names of those that differ and of those only one side has.  A kernel is
 identical when its instruction stream, its .amdhsa_* directives, its resource symbols (.set NAME.num_vgpr, ...) and its metadata entry
@@ -8,7 +8,11 @@ identical when its instruction stream, its .amdhsa_* directives, its resource sy
 comparison: the per-translation-unit __hip_cuid_<hash> symbol (a hash of the source path) and the function index inside local labels
 (.LBB<n>_<m>, .Lfunc_end<n>: the position of the kernel in its file) and the listing's comments (they carry the compiler's IR
 block names, `; %vector.body3159`, numbered through the whole file; every resource figure they repeat is compared as a directive).  Objects named as OBJECT_STEM (e.g. psnode_generic_bwd) are compared
-per kernel; every other object has to be the same file, apart from the cuid.  Exit status 1 if anything differs."""
+per kernel; every other object has to be the same file, apart from the cuid.  Exit status 1 if anything differs.
+
+--rename REGEX=REPL (repeatable) rewrites symbol names in the listings of BOTH builds before anything is compared: a kernel whose source moved
+into a template with another name (K6's `masked_mse_fast_kernel<D, VT>` -> `loss_fast_kernel<RhoMse, LossDev, D, VT, false>`) is compared
+under one neutral name given for its old and its new mangled spelling.  Nothing but the text the regex matches changes."""
 import glob
 import os
 import re
@@ -17,7 +21,12 @@ import sys
 SUFFIX = "-hip-amdgcn-amd-amdhsa-gfx950.s"
 
 
+RENAMES = []     # (compiled regex, replacement) from --rename
+
+
 def norm(text):
+    for rx, repl in RENAMES:
+        text = rx.sub(repl, text)
     text = re.sub(r"__hip_cuid_[0-9a-f]+", "__hip_cuid_X", text)
     text = re.sub(r"\.LBB\d+_", ".LBB_", text)
     text = re.sub(r"\.Lfunc_(begin|end)\d+", r".Lfunc_\1", text)
@@ -49,8 +58,13 @@ def kernels(path):
 
 
 def main():
-    a, b = sys.argv[1], sys.argv[2]
-    per_kernel = set(sys.argv[3:])
+    argv = sys.argv[1:]
+    while argv and argv[0] == "--rename":
+        rx, repl = argv[1].split("=", 1)
+        RENAMES.append((re.compile(rx), repl))
+        argv = argv[2:]
+    a, b = argv[0], argv[1]
+    per_kernel = set(argv[2:])
     stems = sorted({os.path.basename(p)[:-len(SUFFIX)] for d in (a, b) for p in glob.glob(os.path.join(d, "*" + SUFFIX))})
     bad = 0
     for stem in stems:

@@ -36,7 +36,9 @@ ABI_VERSION = 10         # == PSNODE_ABI_VERSION of include/psnode_hip.h (2: rou
                          #     additive, same version: psnode_substeps_f32 and the psnode_{ode,dae}_{integrate,backward}_sub_* entry points --
                          #     sub-steps per grid interval on K0 / K5;
                          #     additive, same version: the psnode_{ode,dae}_{integrate,backward}_lin_* entry points -- z | v interpolated
-                         #     linearly inside every grid interval on K0 / K5)
+                         #     linearly inside every grid interval on K0 / K5;
+                         #     additive, same version: psnode_loss_fn_f32 and psnode_masked_loss_* / psnode_loss_per_sample_f32 -- L1, SmoothL1 and
+                         #     Huber on K6, and the per-sample evaluation table of all four kinds)
 LIB_NAME = "libpsnode_hip.so"
 # PSNODE_LIB_PATH lets kernel experiments (profiles/scripts/*) load an alternative build of the same ABI
 LIB_PATH = os.environ.get("PSNODE_LIB_PATH") or os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
@@ -49,6 +51,7 @@ EXPORTS = (
     "psnode_ode_backward_supported", "psnode_ode_backward_param_count", "psnode_ode_backward_workspace_bytes",
     "psnode_ode_backward_f32", "psnode_dae_backward_supported", "psnode_dae_backward_workspace_bytes", "psnode_dae_backward_f32",
     "psnode_masked_mse_workspace_bytes", "psnode_masked_mse_f32",
+    "psnode_masked_loss_supported", "psnode_masked_loss_f32", "psnode_loss_per_sample_f32",
     "psnode_mlp_rows_backward_workspace_bytes", "psnode_mlp_rows_backward_f32",
     "psnode_mlp_rows_backward_parts", "psnode_mlp_rows_reduce_workspace_bytes", "psnode_mlp_rows_reduce_f32",
     "psnode_recon_rows_supported", "psnode_recon_rows_f32", "psnode_recon_rows_param_count", "psnode_recon_rows_backward_workspace_bytes",
@@ -233,6 +236,14 @@ class LossArgsF32(ctypes.Structure):
                 ("out", c_void_p), ("grad_pred", c_void_p)]
 
 
+LOSS_MSE, LOSS_L1, LOSS_SMOOTH_L1, LOSS_HUBER = 0, 1, 2, 3
+
+
+class LossFnF32(ctypes.Structure):
+    """psnode_loss_fn_f32: the pointwise loss of K6 (kind = LOSS_*) and its beta / delta."""
+    _fields_ = [("kind", c_int32), ("param", ctypes.c_float)]
+
+
 _lib = None
 
 
@@ -366,6 +377,12 @@ def load():
     lib.psnode_masked_mse_workspace_bytes.argtypes = [ctypes.POINTER(LossArgsF32)]
     lib.psnode_masked_mse_f32.restype = c_int32
     lib.psnode_masked_mse_f32.argtypes = [ctypes.POINTER(LossArgsF32), c_void_p, c_size_t, c_void_p]
+    lib.psnode_masked_loss_supported.restype = c_int32
+    lib.psnode_masked_loss_supported.argtypes = [ctypes.POINTER(LossArgsF32), ctypes.POINTER(LossFnF32)]
+    lib.psnode_masked_loss_f32.restype = c_int32
+    lib.psnode_masked_loss_f32.argtypes = [ctypes.POINTER(LossArgsF32), ctypes.POINTER(LossFnF32), c_void_p, c_size_t, c_void_p]
+    lib.psnode_loss_per_sample_f32.restype = c_int32
+    lib.psnode_loss_per_sample_f32.argtypes = [ctypes.POINTER(LossArgsF32), ctypes.POINTER(LossFnF32), c_void_p]
     lib.psnode_ode_encoded_supported.restype = c_int32
     lib.psnode_ode_encoded_supported.argtypes = [ctypes.POINTER(OdeEncodedArgsF32)]
     lib.psnode_ode_encoded_integrate_f32.restype = c_int32

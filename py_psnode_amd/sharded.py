@@ -6,6 +6,7 @@ cross-batch coupling of the reference is that trajectory 0 decides the event ste
 (neural_base.py:54,61): rank 0 builds the int32 event table from the global trajectory 0 and broadcasts it.
 One all-gather of the [T, B/G, D] shards reassembles the batch "for the loss" (BASELINE.json north_star).
 """
+import functools
 from typing import Callable, Optional
 
 import torch
@@ -269,7 +270,7 @@ def integrate_dae_sharded(method, de_layers, ae_layers, x_init, t, x, z, v, i, a
 
 
 def masked_mse_sharded(pred, target, mask, col_weight=None, t0_weight: float = 0.0, global_batch: Optional[int] = None, group=None,
-                       local_fn: Optional[Callable] = None):
+                       local_fn: Optional[Callable] = None, loss_func=None):
     """The scripts' masked MSE (neural_00_ODE_01_no_encode.py:353-355, neural_01_DAE_01_no_encode.py:414-419) over a batch
     that is sharded across ranks, WITHOUT gathering the predictions: two scalar-sized all-reduces instead of the
     [T,B,D] all-gather.
@@ -279,10 +280,15 @@ def masked_mse_sharded(pred, target, mask, col_weight=None, t0_weight: float = 0
     autograd, exactly the global loss's gradient w.r.t. the local predictions); the per-column terms are all-reduced for
     logging.  Returns (local_share, global_terms): call .backward() on local_share, then all_reduce_param_grads().
     t0_weight = coefficient of the mean squared error at t = 0 (`Loss_func(x[:,0,:], x_pred[:,0,:])`), normalised by the
-    GLOBAL batch (global_batch, default world * Bl)."""
+    GLOBAL batch (global_batch, default world * Bl).
+    loss_func: the scripts' `Loss_func` (loss.loss_kind_of) of the default local kernel call, loss.masked_loss; the normalisation by the
+    global mask count does not depend on it.  An explicit local_fn is called as before and decides its own pointwise loss (giving both
+    is a ValueError)."""
+    if local_fn is not None and loss_func is not None:
+        raise ValueError("masked_mse_sharded: loss_func goes to the default local call; an explicit local_fn carries its own")
     if local_fn is None:
         from . import loss
-        local_fn = loss.masked_mse
+        local_fn = functools.partial(loss.masked_loss, loss_func=loss_func)
     world = dist.get_world_size(group)
     Bl, _, D = pred.shape
     msum = torch.sum(mask).reshape(1)
