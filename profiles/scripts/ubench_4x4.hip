@@ -17,6 +17,10 @@
 //   11  64 MFMA on ONE accumulator chain as the compiler emits it (it places the s_nop 1 of a dependent SrcC itself);  12  the same as asm
 //       blocks of 4 k with an explicit s_nop 1 behind every MFMA;  13  the whole layer (scaled-domain ELU + transpose) on one chain;
 //   14  as 13 with the transpose's two butterfly stages in alternating order from layer to layer (vcc is handed on: 3 mask moves, not 4)
+//   20 / 21  the waist of K1x's stage, 64 -> 8 -> 64: the output layer (8 MFMAs) -> block fold -> one RK stage input -> L1 (8 MFMAs), as ticks
+//       per pass.  20 = the 16-block form (two dim-tiles, permlane32 + permlane16 folds, the RK operations on two scalars); 21 = the
+//       8-block form (B-operand lane-group broadcast BLGP 1 / 2, two chains merged by packed adds, permlane16 fold, packed RK operations).
+//       The 8-block form also gets a mapping check against a double-precision matvec (does BLGP broadcast what the ISA text says?).
 // It also checks, bit for bit over 2^24 inputs, that the round-5 ELU form equals round 3's.
 // Grid: 1024 single-wave workgroups (= B 4096: one wave per SIMD), and 2048 (two per SIMD) for reference.
 #include <hip/hip_runtime.h>
@@ -426,6 +430,180 @@ __global__ void check_seq(unsigned* nbad) {
     if (bad) atomicAdd(nbad, bad);
 }
 
+// ---- the waist (modes 20 / 21).  The image functions are copies of psnode_mfma_x.h's (this file stands alone).
+constexpr int l4_k(int m, int lane) { return 32 * (m >> 2) + 4 * ((lane >> 2) & 7) + (m & 3); }
+constexpr int l4_dim(int lane) { return 4 * (lane >> 5) + (lane & 3); }
+constexpr int l4_bias_dim(int r, int lane) { return ((lane >> 2) & 7) == 0 ? 4 * (lane >> 5) + r : -1; }
+template <int BLGP>
+__device__ __forceinline__ f4 mfl(float a, float b, f4 c) { return __builtin_amdgcn_mfma_f32_4x4x1f32(a, b, c, 0, 0, BLGP); }
+__device__ __forceinline__ void row_sum2(float& a, float& b) {
+    asm volatile(
+        "s_nop 1\n\t"
+        "v_add_f32_dpp %0, %0, %0 row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
+        "v_add_f32_dpp %1, %1, %1 row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 0\n\t"
+        "v_add_f32_dpp %0, %0, %0 row_ror:4 row_mask:0xf bank_mask:0xf\n\t"
+        "v_add_f32_dpp %1, %1, %1 row_ror:4 row_mask:0xf bank_mask:0xf"
+        : "+v"(a), "+v"(b));
+}
+__device__ __forceinline__ f2 row_sum2(const f2 k) {
+    float a, b;
+    asm volatile(
+        "s_nop 1\n\t"
+        "v_add_f32_dpp %0, %2, %2 row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
+        "v_add_f32_dpp %1, %3, %3 row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 0\n\t"
+        "v_add_f32_dpp %0, %0, %0 row_ror:4 row_mask:0xf bank_mask:0xf\n\t"
+        "v_add_f32_dpp %1, %1, %1 row_ror:4 row_mask:0xf bank_mask:0xf"
+        : "=&v"(a), "=&v"(b)
+        : "v"(k[0]), "v"(k[1]));
+    return f2{a, b};
+}
+__device__ __forceinline__ float fold32(const float a, const float b) {
+    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
+    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
+__device__ __forceinline__ float fold16(const float a, const float b) {
+    const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false, false);
+    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
+// 16-block form: A register 4 j + cc, lane (b, r) = W4[4 j + r][4 b + cc]; C tile j register r, block 0 = bias of dim 4 j + r
+__device__ __forceinline__ f2 l4_16(const float (&w4a)[8], const f4 (&b4c)[2], const f4 hA) {
+    f4 p0 = b4c[0], p1 = b4c[1];
+    p0 = mf<0, false>(w4a[0], hA[0], p0); p1 = mf<0, false>(w4a[4], hA[0], p1);
+    p0 = mf<0, false>(w4a[1], hA[1], p0); p1 = mf<0, false>(w4a[5], hA[1], p1);
+    p0 = mf<0, false>(w4a[2], hA[2], p0); p1 = mf<0, false>(w4a[6], hA[2], p1);
+    p0 = mf<0, false>(w4a[3], hA[3], p0); p1 = mf<0, false>(w4a[7], hA[3], p1);
+    const float q0 = fold32(p0[0], p1[0]), q1 = fold32(p0[1], p1[1]), q2 = fold32(p0[2], p1[2]), q3 = fold32(p0[3], p1[3]);
+    float k01 = fold16(q0, q2), k23 = fold16(q1, q3);
+    row_sum2(k01, k23);
+    return f2{k01, k23};
+}
+// 8-block form: A register m = 4 half + cc, lane = W4[l4_dim(lane)][l4_k(m, lane)]; C register r = bias of l4_bias_dim(r, lane)
+__device__ __forceinline__ f2 l4_8(const float (&w4a)[8], const f4 b4c, const f4 hA) {
+    f4 lo = b4c, hi = f4{0.f, 0.f, 0.f, 0.f};
+    lo = mfl<1>(w4a[0], hA[0], lo); hi = mfl<2>(w4a[4], hA[0], hi);
+    lo = mfl<1>(w4a[1], hA[1], lo); hi = mfl<2>(w4a[5], hA[1], hi);
+    lo = mfl<1>(w4a[2], hA[2], lo); hi = mfl<2>(w4a[6], hA[2], hi);
+    lo = mfl<1>(w4a[3], hA[3], lo); hi = mfl<2>(w4a[7], hA[3], hi);
+    const f4 q = lo + hi;
+    const auto e = __builtin_amdgcn_permlane16_swap(__float_as_uint(q[0]), __float_as_uint(q[2]), false, false);
+    const auto o = __builtin_amdgcn_permlane16_swap(__float_as_uint(q[1]), __float_as_uint(q[3]), false, false);
+    return row_sum2(f2{__uint_as_float(e[0]), __uint_as_float(o[0])} + f2{__uint_as_float(e[1]), __uint_as_float(o[1])});
+}
+// out[dim][traj] = b4[dim] + sum_k W4[dim][k] act[k][traj] through either form; img = the form's 8 A registers + its C registers, [reg][lane]
+template <bool NEW>
+__global__ void check_l4(const float* __restrict__ img, const float* __restrict__ act, float* __restrict__ res) {
+    const int l = threadIdx.x, b = l >> 2, t = l & 3;
+    float w4a[8];
+#pragma unroll
+    for (int m = 0; m < 8; ++m) w4a[m] = img[m * 64 + l];
+    f4 h;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) h[c] = act[(4 * b + c) * 4 + t];
+    f2 k;
+    if constexpr (NEW) {
+        f4 b4c;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) b4c[r] = img[(8 + r) * 64 + l];
+        k = l4_8(w4a, b4c, h);
+    } else {
+        f4 b4c[2];
+#pragma unroll
+        for (int r = 0; r < 8; ++r) b4c[r >> 2][r & 3] = img[(8 + r) * 64 + l];
+        k = l4_16(w4a, b4c, h);
+    }
+    res[l * 2 + 0] = k[0];                                     // every lane reports, [lane][2]: the state layout holds a row's two dims in EVERY block
+    res[l * 2 + 1] = k[1];                                     // of the row (the host works out a lane's dims and trajectory)
+}
+template <bool NEW>
+__global__ __launch_bounds__(64) void bench_waist(float* out, long long* cyc, int niter, const float* __restrict__ wsrc) {
+    const int l = threadIdx.x;
+    float w4a[8], w1x[8];
+    f4 b4c[2];
+#pragma unroll
+    for (int m = 0; m < 8; ++m) { w4a[m] = wsrc[m * 64 + l]; w1x[m] = wsrc[(8 + m) * 64 + l]; b4c[m >> 2][m & 3] = wsrc[(16 + m) * 64 + l]; }
+    f4 h = f4{0.1f + 0.001f * l, 0.2f, 0.3f, 0.4f};
+    const f4 c0 = f4{0.01f, 0.02f, 0.03f, 0.04f};
+    f2 X = f2{0.1f, 0.2f};
+    const float hs = 1e-3f + 1e-6f * (float)niter;             // (a run-time value: the step)
+    const long long t0 = __builtin_readcyclecounter();
+    for (int it = 0; it < niter; ++it) {
+        f2 s;
+        if constexpr (NEW) {
+            const f2 k = l4_8(w4a, b4c[0], h);
+            s = X + hs * k;                                    // one stage input: two packed operations
+        } else {
+            const f2 k = l4_16(w4a, b4c, h);
+            const float s01 = X[0] + hs * k[0], s23 = X[1] + hs * k[1];      // ... four scalar ones
+            s = f2{s01, s23};
+        }
+        f4 accA = c0, accB = f4{0.f, 0.f, 0.f, 0.f};
+        accA = mf<0>(s[0], w1x[0], accA);  accB = mf<4>(s[0], w1x[1], accB);
+        accA = mf<8>(s[0], w1x[2], accA);  accB = mf<12>(s[0], w1x[3], accB);
+        accA = mf<0>(s[1], w1x[4], accA);  accB = mf<4>(s[1], w1x[5], accB);
+        accA = mf<8>(s[1], w1x[6], accA);  accB = mf<12>(s[1], w1x[7], accB);
+        h = (accA + accB) * 1e-3f;
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    const long long t1 = __builtin_readcyclecounter();
+    out[blockIdx.x * 64 + l] = h[0] + h[1] + h[2] + h[3];
+    if (blockIdx.x == 0 && l == 0) *cyc = t1 - t0;
+}
+template <bool NEW>
+void run_waist(const char* name, int nwg, float* out, long long* cyc, const float* w) {
+    const int niter = 4000;
+    hipEvent_t e0, e1;
+    hipEventCreate(&e0); hipEventCreate(&e1);
+    bench_waist<NEW><<<nwg, 64>>>(out, cyc, 10, w);
+    hipEventRecord(e0);
+    bench_waist<NEW><<<nwg, 64>>>(out, cyc, niter, w);
+    hipEventRecord(e1);
+    hipDeviceSynchronize();
+    float ms; hipEventElapsedTime(&ms, e0, e1);
+    long long c; hipMemcpy(&c, cyc, sizeof(c), hipMemcpyDeviceToHost);
+    printf("%-58s waves/SIMD=%d : %7.1f ns per pass (wall), s_memtime %.2f ticks\n", name, nwg / 1024, ms * 1e6 / niter, (double)c / niter);
+}
+// both forms of the output layer against a double-precision matvec, every (dim, k) of a dense W4 and the bias
+bool check_waist() {
+    float W4[8 * 64], b4[8], ha[64 * 4], img[16 * 64], hr[64 * 2];
+    for (int i = 0; i < 8 * 64; ++i) W4[i] = (float)((i * 7919 + 13) % 1000) * 1e-3f - 0.5f;
+    for (int i = 0; i < 8; ++i) b4[i] = 0.25f * (float)(i + 1);
+    for (int i = 0; i < 64 * 4; ++i) ha[i] = (float)((i * 104729 + 7) % 1000) * 1e-3f - 0.5f;
+    float *dimg, *dact, *dres;
+    hipMalloc(&dimg, sizeof(img)); hipMalloc(&dact, sizeof(ha)); hipMalloc(&dres, sizeof(hr));
+    hipMemcpy(dact, ha, sizeof(ha), hipMemcpyHostToDevice);
+    bool all_ok = true;
+    for (int form = 0; form < 2; ++form) {
+        for (int i = 0; i < 16 * 64; ++i) img[i] = 0.f;
+        for (int lane = 0; lane < 64; ++lane) {
+            const int b = lane >> 2, r = lane & 3;
+            for (int m = 0; m < 8; ++m)
+                img[m * 64 + lane] = form ? W4[l4_dim(lane) * 64 + l4_k(m, lane)] : W4[(4 * (m >> 2) + r) * 64 + 4 * b + (m & 3)];
+            if (form) { for (int q = 0; q < 4; ++q) if (l4_bias_dim(q, lane) >= 0) img[(8 + q) * 64 + lane] = b4[l4_bias_dim(q, lane)]; }
+            else if (b == 0) { for (int q = 0; q < 8; ++q) img[(8 + q) * 64 + lane] = b4[q]; }
+        }
+        hipMemcpy(dimg, img, sizeof(img), hipMemcpyHostToDevice);
+        hipMemset(dres, 0, sizeof(hr));
+        if (form) check_l4<true><<<1, 64>>>(dimg, dact, dres); else check_l4<false><<<1, 64>>>(dimg, dact, dres);
+        hipMemcpy(hr, dres, sizeof(hr), hipMemcpyDeviceToHost);
+        double worst = 0;
+        for (int lane = 0; lane < 64; ++lane)
+            for (int e = 0; e < 2; ++e) {
+                const int rho = lane >> 4, t = lane & 3, d = 4 * (rho >> 1) + 2 * (rho & 1) + e;
+                double ref = b4[d];
+                for (int k = 0; k < 64; ++k) ref += (double)W4[d * 64 + k] * ha[k * 4 + t];
+                const double df = fabs(ref - hr[lane * 2 + e]);
+                if (df > worst) worst = df;
+            }
+        printf("output layer mapping check, %s + fold, all 64 lanes x 2 dims vs a double-precision matvec: max abs diff %.3g %s\n",
+               form ? "8-block form (BLGP 1 / 2 broadcast, two chains)" : "16-block form (two dim-tiles)", worst, worst < 1e-4 ? "OK" : "WRONG");
+        all_ok = all_ok && worst < 1e-4;
+    }
+    hipFree(dimg); hipFree(dact); hipFree(dres);
+    return all_ok;
+}
+
 template <int MODE>
 void run(const char* name, int nwg, float* out, long long* cyc, const float* w) {
     const int niter = 4000;
@@ -469,6 +647,13 @@ int main() {
         printf("ordered in-quad transposes (stage order 0 / 1, mask handed on in vcc) vs the plain one: %u mismatches %s\n", hnb, hnb ? "WRONG" : "OK");
         hipFree(nb);
     }
+    check_waist();
+    run_waist<false>("waist 64 -> 8 -> 64, 16-block fold, scalar RK", 1024, out, cyc, w);
+    run_waist<true>("waist 64 -> 8 -> 64, 8-block fold (BLGP), packed RK", 1024, out, cyc, w);
+    run_waist<false>("waist, 16-block fold, scalar RK (again)", 1024, out, cyc, w);
+    run_waist<true>("waist, 8-block fold (BLGP), packed RK (again)", 1024, out, cyc, w);
+    run_waist<false>("waist, 16-block fold, scalar RK (third)", 1024, out, cyc, w);
+    run_waist<true>("waist, 8-block fold (BLGP), packed RK (third)", 1024, out, cyc, w);
     run<0>("64 x 4x4x1 (2 chains), nothing else", 1024, out, cyc, w);
     run<11>("64 x 4x4x1 on ONE chain (compiler form), nothing else", 1024, out, cyc, w);
     run_asm_one("64 x 4x4x1 on ONE chain, asm with s_nop 1", 1024, out, cyc, w);

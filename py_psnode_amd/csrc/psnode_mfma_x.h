@@ -15,9 +15,19 @@ typedef float f2 __attribute__((ext_vector_type(2)));
 // dim that MFMA m of L1 multiplies: register X01 (m < 4) or X23, ABID = 4 (m & 3)
 __host__ __device__ constexpr int l1_dim(int m) { return 4 * ((m & 3) >> 1) + 2 * ((m & 3) & 1) + (m >= 4 ? 1 : 0); }
 
+// A image of K1x's output layer (l4_out below).  Weight register m = 4 half + cc multiplies, in block b = lane >> 2, the activation row
+// k = 32 half + 4 (b & 7) + cc (the half's blocks are broadcast to the other lane group); row r = lane & 3 of blocks 0..7 belongs to dim r,
+// of blocks 8..15 to dim 4 + r.  The bias enters in the first block of each dim-tile (blocks 0 and 8), in the lo chain only.
+__host__ __device__ constexpr int l4_k(int m, int lane) { return 32 * (m >> 2) + 4 * ((lane >> 2) & 7) + (m & 3); }
+__host__ __device__ constexpr int l4_dim(int lane) { return 4 * (lane >> 5) + (lane & 3); }
+__host__ __device__ constexpr int l4_bias_dim(int r, int lane) { return ((lane >> 2) & 7) == 0 ? 4 * (lane >> 5) + r : -1; }     // C register r; -1: zero
+
 template <int ABID>
 __device__ __forceinline__ f4 mfx(float a, float b, f4 c) { return __builtin_amdgcn_mfma_f32_4x4x1f32(a, b, c, 4, ABID, 0); }
 __device__ __forceinline__ f4 mfn(float a, float b, f4 c) { return __builtin_amdgcn_mfma_f32_4x4x1f32(a, b, c, 0, 0, 0); }
+// BLGP 1: every block reads its B row from lanes 0..31 (block b from block b & 7's lanes); 2: from lanes 32..63 (block 8 + (b & 7))
+template <int BLGP>
+__device__ __forceinline__ f4 mfl(float a, float b, f4 c) { return __builtin_amdgcn_mfma_f32_4x4x1f32(a, b, c, 0, 0, BLGP); }
 
 // 4 x 4 transpose of registers (r0..r3) x lanes (4q..4q+3): two butterfly stages of four v_cndmask_b32_dpp (D = vcc ? src1 : dpp(src0)).
 // One asm block (the hazard recognizer does not look inside): s_nop 1 covers VALU write -> DPP read (2 wait states); inside, every DPP
@@ -124,6 +134,39 @@ __device__ __forceinline__ float fold32(const float a, const float b) {
 __device__ __forceinline__ float fold16(const float a, const float b) {
     const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false, false);
     return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
+
+// The same on the halves of a register pair, into a fresh pair (operands tied to halves of a pair cost the allocator a copy in and out).
+__device__ __forceinline__ f2 row_sum2(const f2 k) {
+    float a, b;
+    asm volatile(
+        "s_nop 1\n\t"
+        "v_add_f32_dpp %0, %2, %2 row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
+        "v_add_f32_dpp %1, %3, %3 row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 0\n\t"
+        "v_add_f32_dpp %0, %0, %0 row_ror:4 row_mask:0xf bank_mask:0xf\n\t"
+        "v_add_f32_dpp %1, %1, %1 row_ror:4 row_mask:0xf bank_mask:0xf"
+        : "=&v"(a), "=&v"(b)
+        : "v"(k[0]), "v"(k[1]));
+    return f2{a, b};
+}
+
+// K1x's output layer (64 -> x_dim <= 8), split K over the blocks with the roles swapped (A = weights, B = activations).  The B operand's
+// lane-group broadcast lets ONE MFMA serve both dim-tiles: blocks 0..7 accumulate dims 0..3, blocks 8..15 dims 4..7, each over the 8
+// activation blocks of one half of k (image: l4_k / l4_dim).  Two chains (k < 32, k >= 32) merged by two packed adds leave what a
+// lane-bit-5 fold would: only 8 blocks per dim remain to be summed -- one v_permlane16_swap per register pair (both results are the
+// halves of one register pair: one packed add) and the two row rotations.  Returns the state layout {X01, X23}.
+__device__ __forceinline__ f2 l4_out(const float (&w4a)[8], const f4 b4c, const f4 hA) {
+    f4 lo = b4c, hi = f4{0.f, 0.f, 0.f, 0.f};
+    lo = mfl<1>(w4a[0], hA[0], lo); hi = mfl<2>(w4a[4], hA[0], hi);
+    lo = mfl<1>(w4a[1], hA[1], lo); hi = mfl<2>(w4a[5], hA[1], hi);
+    lo = mfl<1>(w4a[2], hA[2], lo); hi = mfl<2>(w4a[6], hA[2], hi);
+    lo = mfl<1>(w4a[3], hA[3], lo); hi = mfl<2>(w4a[7], hA[3], hi);
+    const f4 q = lo + hi;
+    // (pairs (0,2) / (1,3): a row ends up with two ADJACENT dims)
+    const auto e = __builtin_amdgcn_permlane16_swap(__float_as_uint(q[0]), __float_as_uint(q[2]), false, false);
+    const auto o = __builtin_amdgcn_permlane16_swap(__float_as_uint(q[1]), __float_as_uint(q[3]), false, false);
+    return row_sum2(f2{__uint_as_float(e[0]), __uint_as_float(o[0])} + f2{__uint_as_float(e[1]), __uint_as_float(o[1])});
 }
 
 // all 64 k of one H -> H layer: k = 4 bb + cc <-> A register cc, ABID bb.  TWO accumulator chains: on one chain a lone wave issues a 4x4x1

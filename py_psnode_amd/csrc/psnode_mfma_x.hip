@@ -2,7 +2,7 @@
 // units of `3n -> H -> H -> H -> x_dim` (H <= 64, x_dim <= 8, z_dim <= 8), so nothing crosses waves: no LDS, no barrier.  At the headline
 // batch (4096 trajectories = 1024 waves = one per SIMD) K1's 4-wave tile spends ~23 % of a stage in its three LDS exchanges
 // (ds_write -> s_barrier -> ds_read with nothing else to issue); here the layer-to-layer re-layout is a 4 x 4 transpose inside every lane
-// quad (8 v_cndmask_b32_dpp) and the L4 reduction a 4-stage lane butterfly (profiles/r05_ubench_4x4.txt: 325 vs 402 ns per H -> H layer).
+// quad (8 v_cndmask_b32_dpp) and the L4 reduction a 3-stage lane fold (profiles/r05_ubench_4x4.txt: 325 vs 402 ns per H -> H layer).
 //
 // Arithmetic on v_mfma_f32_4x4x1_16B_f32 (16 blocks of D_b(4x4) += A_b(4x1) B_b(1x4); exact fp32, the same 64 flop/clk/SIMD peak as
 // 16x16x4 -- it issues every 10 cycles instead of 8).  Lane l = (block b = l >> 2, c = l & 3).
@@ -10,13 +10,16 @@
 //       A layout: four registers hA[cc], lane (b, t) holds act[k = 4b + cc][trajectory t]; CBSZ = 4 / ABID = b hands block b's rows to all
 //       16 blocks, so ONE MFMA adds one k for all 64 units and 4 trajectories; B = one VGPR per k (64 per H -> H matrix, resident).
 //       D layout: register r = trajectory, lane (b', c') = unit 4b' + c'.  ELU runs on D; the in-quad transpose turns D into the next A.
-//   L4 (64 -> x_dim <= 8), split K over the BLOCKS, roles swapped (A = weights, B = activations, no broadcast):
-//       P_j[dim 4j + r][traj c] (block b) += W4[4j + r][4b + cc] * act[4b + cc][c]      8 MFMAs, then the sum over the 16 blocks:
-//       v_permlane32_swap (lane bit 5), v_permlane16_swap (bit 4) -- each folds TWO registers into one -- and two DPP row rotations
-//       (bits 3, 2).  Result = the state layout below, so the RK update is 2 registers wide and feeds L1 without any data movement.
-//   State layout: X01 / X23, lane in row rho = l >> 4, trajectory t = l & 3:  X01 = x[4 (rho >> 1) + 2 (rho & 1)][t],  X23 = the NEXT dim
-//       (adjacent dims: a row's two state values are one 8-byte store).  L1 reads dim d with ABID = 4 rho(d) from X01 or X23 (8 MFMAs per
-//       stage, folded image as K1).
+//   L4 (64 -> x_dim <= 8), split K over the BLOCKS, roles swapped (A = weights, B = activations), B on the lane-group broadcast:
+//       BLGP 1 hands the activations of lanes 0..31 (k < 32) to both lane groups, BLGP 2 those of lanes 32..63, so blocks 0..7 work
+//       on dims 0..3 and blocks 8..15 on dims 4..7 (j = b >> 3), each over its half's 8 activation blocks:
+//       Q_half[dim 4j + r][traj c] (block b) += W4[4j + r][k] * act[k][c],  k = 32 half + 4 (b & 7) + cc     8 MFMAs in two chains
+//       (psnode_mfma_x.h: l4_out; image l4_k / l4_dim).  The chains' sum (two packed adds) leaves 8 blocks per dim: v_permlane16_swap
+//       (lane bit 4) folds two register PAIRS into one, two DPP row rotations (bits 3, 2) finish.  Result = the state layout below, so
+//       the RK update is one register pair wide and feeds L1 without any data movement.
+//   State layout: the pair X = {X01, X23}, lane in row rho = l >> 4, trajectory t = l & 3:  X01 = x[4 (rho >> 1) + 2 (rho & 1)][t],  X23 = the
+//       NEXT dim (adjacent dims: a row's two state values are one 8-byte store; the RK arithmetic is packed, v_pk_mul_f32 / v_pk_add_f32).
+//       L1 reads dim d with ABID = 4 rho(d) from X01 or X23 (8 MFMAs per stage, folded image as K1).
 // External inputs: slot q (K1's order: q < ne -> ext[q] - a0, ne <= q < 2 ne -> ext[q - ne]) lives in block q of ONE register (lane (q, t));
 // the per-step constant of L1 is 4 NZM MFMAs with ABID = q.  Hidden layers run in the log2e-scaled domain (psnode_common.h:
 // elu_quad_scaled).  Inference only (no saved activations); teacher forcing (input_true_x) is a uniform runtime branch.
@@ -30,6 +33,7 @@ namespace {
 // register image: pack[reg][lane] (64 lanes)
 struct XRegs {
     static constexpr int W2 = 0, W3 = 64, W1X = 128, W1E = 136, W1A = 152, B1 = 168, B2 = 169, B3 = 170, W4A = 171, B4C = 179, COUNT = 187;
+    // (B4C: the 4 C registers of L4's lo chain; 183 .. 186 are spare -- the pack buffer keeps its recorded size)
 };
 struct PackX {
     int xd, zd, n, hreal;
@@ -41,7 +45,7 @@ __global__ void pack_x_kernel(const PackX p) {
     const int H = p.hreal, n = p.n, xd = p.xd, ne = p.zd, K1 = 3 * n;
     const float kLog2e = p.sc;                                 // (shadows the constant: 1 for the training forward's plain-domain image)
     for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < XRegs::COUNT * 64; idx += gridDim.x * blockDim.x) {
-        const int reg = idx >> 6, l = idx & 63, b = l >> 2, c = l & 3, u = l;      // B operands: lane (b', c') = unit 4b' + c' = l
+        const int reg = idx >> 6, l = idx & 63, u = l;      // B operands: lane (b', c') = unit 4b' + c' = l
         float v = 0.0f;
         if (reg < XRegs::W1X) {                         // H -> H matrices, k in MFMA order: k = 4 bb + cc  (scale-free)
             const int k = reg & 63;
@@ -64,12 +68,12 @@ __global__ void pack_x_kernel(const PackX p) {
         } else if (reg == XRegs::B1) { if (u < H) v = p.b1[u] * kLog2e;
         } else if (reg == XRegs::B2) { if (u < H) v = p.b2[u] * kLog2e;
         } else if (reg == XRegs::B3) { if (u < H) v = p.b3[u] * kLog2e;
-        } else if (reg < XRegs::B4C) {                  // L4 as A operand: lane (b, r = c) = W4[dim 4j + r][k = 4b + cc] / log2e
-            const int j = (reg - XRegs::W4A) >> 2, cc = (reg - XRegs::W4A) & 3, d = 4 * j + c, k = 4 * b + cc;
+        } else if (reg < XRegs::B4C) {                  // L4 as A operand: lane (b, r = c) = W4[dim l4_dim][k = l4_k] / log2e (psnode_mfma_x.h)
+            const int d = l4_dim(l), k = l4_k(reg - XRegs::W4A, l);
             if (d < xd && k < H) v = p.w4[d * H + k] / kLog2e;
-        } else {                                        // C init of L4: D lane (b, c), register r -> dim 4j + r: the bias enters in block 0 only
-            const int j = (reg - XRegs::B4C) >> 2, r = (reg - XRegs::B4C) & 3, d = 4 * j + r;
-            if (b == 0 && d < xd) v = p.b4[d];
+        } else if (reg < XRegs::B4C + 4) {              // C init of L4's lo chain: D lane (b, c), register r: the bias enters in blocks 0 and 8
+            const int d = l4_bias_dim(reg - XRegs::B4C, l);
+            if (d >= 0 && d < xd) v = p.b4[d];
         }
         p.out[idx] = v;
     }
@@ -163,7 +167,7 @@ __global__ __launch_bounds__(64 * kXWaves * (ROLES ? 2 : 1)) void integrate_x_ke
     // ---- weights -> registers (once per launch)
     const float* pw = pack + l;
     float w2[64], w3[64], w1x[8], w1e[16], w4a[8];
-    f4 b4c[2];
+    f4 b4c;
 #pragma unroll
     for (int k = 0; k < 64; ++k) { w2[k] = pw[(XRegs::W2 + k) * 64]; w3[k] = pw[(XRegs::W3 + k) * 64]; }
 #pragma unroll
@@ -172,9 +176,7 @@ __global__ __launch_bounds__(64 * kXWaves * (ROLES ? 2 : 1)) void integrate_x_ke
     for (int q = 0; q < 16; ++q) w1e[q] = q < 4 * NZM ? pw[(XRegs::W1E + q) * 64] : 0.0f;
     const float b1 = pw[XRegs::B1 * 64], b2 = pw[XRegs::B2 * 64], b3 = pw[XRegs::B3 * 64];
 #pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) b4c[j][r] = pw[(XRegs::B4C + 4 * j + r) * 64];
+    for (int r = 0; r < 4; ++r) b4c[r] = pw[(XRegs::B4C + r) * 64];
 
     // ---- per-trajectory constants
     const int d01 = 4 * (rho >> 1) + 2 * (rho & 1), d23 = d01 + 1;  // the dims this lane's row carries in X01 / X23 (adjacent)
@@ -190,17 +192,17 @@ __global__ __launch_bounds__(64 * kXWaves * (ROLES ? 2 : 1)) void integrate_x_ke
     const int ecol = b < ne ? b : (b < 2 * ne ? b - ne : 0);        // z column of this lane's ext slot (slot q = block b)
     const float a0e = b < ne ? a0p[xd + b] : 0.0f;
     const bool eon = b < 2 * ne;
-    float X01 = 0.0f, X23 = 0.0f;
+    f2 X = f2{0.0f, 0.0f};                                          // the state {X01, X23}: one register pair through the RK arithmetic
     {
         const float* x0 = a.x.p + tr * a.x.sb;
-        if (d01 < xd) X01 = x0[d01];
-        if (d23 < xd) X23 = x0[d23];
+        if (d01 < xd) X[0] = x0[d01];
+        if (d23 < xd) X[1] = x0[d23];
     }
     const bool storer = (b & 3) == 0 && valid;                      // the first block of each row writes the row's two dims
     if (a.T < 2 && storer) {                                         // (T >= 2: row 0 is stored by the first pass of the time loop)
         float* row = a.xo + tr * xd;
-        if (d01 < xd) row[d01] = X01;
-        if (d23 < xd) row[d23] = X23;
+        if (d01 < xd) row[d01] = X[0];
+        if (d23 < xd) row[d23] = X[1];
     }
     const int nT = (int)a.T;                                         // (32-bit loop counters: there is no 64-bit scalar compare, a `long long` k puts
     if (nT < 2) return;                                              //  every end-of-grid test on the VALU; the launcher refuses T >= 2^31)
@@ -265,18 +267,19 @@ __global__ __launch_bounds__(64 * kXWaves * (ROLES ? 2 : 1)) void integrate_x_ke
     const bool pair_ok = FAST || (xd & 1) == 0;                       // even x_dim: both dims exist together and the pair is 8-byte aligned
     auto store_row = [&](float* row) {
         if (pair_ok) {
-            if (st01) stg<f2>((gptr<float>)(uintptr_t)row, xooff, f2{X01, X23});
+            if (st01) stg<f2>((gptr<float>)(uintptr_t)row, xooff, X);
         } else {
-            if (st01) stg<float>((gptr<float>)(uintptr_t)row, xooff, X01);
-            if (st23) stg<float>((gptr<float>)(uintptr_t)row, xooff + 4u, X23);
+            if (st01) stg<float>((gptr<float>)(uintptr_t)row, xooff, X[0]);
+            if (st23) stg<float>((gptr<float>)(uintptr_t)row, xooff + 4u, X[1]);
         }
     };
 
     // The mask the next in-quad transpose starts on (psnode_mfma_x.h: quad_transpose_seq).  A stage has three seams, so consecutive stages
     // alternate their parity P; an even number of stages per step hands the next step the mask it starts with.
     XMask vm = xmask_even();
-    // DE right-hand side in the state layout: k(X01, X23).  P: the transpose order of the stage's first seam (orders P, !P, P)
-    auto rhs = [&](auto par_tag, const float s01, const float s23, const f4 cz, float& k01, float& k23) {
+    // DE right-hand side in the state layout: k({X01, X23}).  P: the transpose order of the stage's first seam (orders P, !P, P)
+    auto rhs = [&](auto par_tag, const f2 s, const f4 cz) -> f2 {
+        const float s01 = s[0], s23 = s[1];
         constexpr int P = decltype(par_tag)::value;
         f4 accA = cz, accB = f4{0.f, 0.f, 0.f, 0.f};
         accA = mfx<0>(s01, w1x[0], accA);  accB = mfx<4>(s01, w1x[1], accB);
@@ -286,11 +289,11 @@ __global__ __launch_bounds__(64 * kXWaves * (ROLES ? 2 : 1)) void integrate_x_ke
         f4 hA = quad_transpose_seq<P>(elu_x<!SAVE>(accA + accB), vm);
         float* slot = ROLES ? ring_mine + (ring_half * 4 + ring_sl) * kXSlotFloats : nullptr;
         if constexpr (ROLES) {                                       // the stage's rows into the ring slot; the partner wave stores them
-            *reinterpret_cast<f2*>(slot + 768 + 2 * l) = f2{s01, s23};
+            *reinterpret_cast<f2*>(slot + 768 + 2 * l) = s;
             *reinterpret_cast<f4*>(slot + 4 * l) = hA;
         } else if constexpr (SAVE) {                                 // rows (step, stage): the stage input, then the three layers as they appear
             if (pair_ok) {
-                if (st01) stg<f2>((gptr<float>)(uintptr_t)sx_run, xooff, f2{s01, s23});
+                if (st01) stg<f2>((gptr<float>)(uintptr_t)sx_run, xooff, s);
             } else {
                 if (st01) stg<float>((gptr<float>)(uintptr_t)sx_run, xooff, s01);
                 if (st23) stg<float>((gptr<float>)(uintptr_t)sx_run, xooff + 4u, s23);
@@ -309,15 +312,7 @@ __global__ __launch_bounds__(64 * kXWaves * (ROLES ? 2 : 1)) void integrate_x_ke
             if (sa_on) stg<f4>((gptr<float>)(uintptr_t)(sa_run + 2 * sa_layer), saoff, hA);
             if constexpr (PSNODE_K1X_SAVE_ABL != 2) sa_run += sa_stage;
         }
-        f4 p0 = b4c[0], p1 = b4c[1];
-        p0 = mfn(w4a[0], hA[0], p0); p1 = mfn(w4a[4], hA[0], p1);
-        p0 = mfn(w4a[1], hA[1], p0); p1 = mfn(w4a[5], hA[1], p1);
-        p0 = mfn(w4a[2], hA[2], p0); p1 = mfn(w4a[6], hA[2], p1);
-        p0 = mfn(w4a[3], hA[3], p0); p1 = mfn(w4a[7], hA[3], p1);
-        // sum over the 16 blocks: lane bits 5, 4 fold two registers into one each; bits 3, 2 are row rotations
-        const float q0 = fold32(p0[0], p1[0]), q1 = fold32(p0[1], p1[1]), q2 = fold32(p0[2], p1[2]), q3 = fold32(p0[3], p1[3]);
-        k01 = fold16(q0, q2); k23 = fold16(q1, q3);          // (pairs (0,2) / (1,3): a row ends up with two ADJACENT dims)
-        row_sum2(k01, k23);
+        return l4_out(w4a, b4c, hA);
     };
 
     // One step.  `tuse` / `euse`: the registers that hold t[k + 1] and the external value of step k; with PF the step re-issues loads INTO
@@ -347,13 +342,12 @@ __global__ __launch_bounds__(64 * kXWaves * (ROLES ? 2 : 1)) void integrate_x_ke
         const float h_ = tuse - tprev;
         if constexpr (!LAG) tprev = tuse;
         const float eA = eon ? (b < ne ? euse - a0e : euse) : 0.0f;
-        float s01 = X01, s23 = X23;
+        f2 s = X;
         if constexpr (!FAST) {
             if (true_x) {                                            // teacher forcing: the step starts from the dataset's x[k] (uniform branch)
                 const float v01 = ldg<float>(as_g(xt_run), xtoff01), v23 = ldg<float>(as_g(xt_run), xtoff23);
                 __builtin_amdgcn_s_waitcnt(0x0F70);
-                s01 = d01 < xd ? v01 : 0.0f;
-                s23 = d23 < xd ? v23 : 0.0f;
+                s = f2{d01 < xd ? v01 : 0.0f, d23 < xd ? v23 : 0.0f};
             }
             xt_run += xst;
         }
@@ -375,25 +369,22 @@ __global__ __launch_bounds__(64 * kXWaves * (ROLES ? 2 : 1)) void integrate_x_ke
         store_row(xo_run);                                           // deferred store of the previous step's result, BEHIND the prefetch (above)
         xo_run += xo_step;
         const f4 cz = ext_mfmas<0, 4 * NZM>(w1e, eA, c0);            // per-step constant of L1
-        float k1a, k1b;
+        // (the RK arithmetic is elementwise on the pair: the same multiplies and adds, in the same order, as on two scalars -- packed)
         using P0 = std::integral_constant<int, 0>;
         using P1 = std::integral_constant<int, 1>;
         if constexpr (METHOD == PSNODE_EULER) vm = xmask_even();     // (one stage per step: its three seams leave the other mask)
-        rhs(P0{}, s01, s23, cz, k1a, k1b);
+        const f2 k1 = rhs(P0{}, s, cz);
         if constexpr (METHOD == PSNODE_EULER) {
-            X01 = s01 + h_ * k1a; X23 = s23 + h_ * k1b;
+            X = s + h_ * k1;
         } else if constexpr (METHOD == PSNODE_MIDPOINT) {
             const float hh = 0.5f * h_;
-            float k2a, k2b;
-            rhs(P1{}, s01 + k1a * hh, s23 + k1b * hh, cz, k2a, k2b);
-            X01 = s01 + h_ * k2a; X23 = s23 + h_ * k2b;
+            const f2 k2 = rhs(P1{}, s + k1 * hh, cz);
+            X = s + h_ * k2;
         } else {
-            float k2a, k2b, k3a, k3b, k4a, k4b;
-            rhs(P1{}, s01 + h_ * k1a * kOneThird, s23 + h_ * k1b * kOneThird, cz, k2a, k2b);
-            rhs(P0{}, s01 + h_ * (k2a - k1a * kOneThird), s23 + h_ * (k2b - k1b * kOneThird), cz, k3a, k3b);
-            rhs(P1{}, s01 + h_ * (k1a - k2a + k3a), s23 + h_ * (k1b - k2b + k3b), cz, k4a, k4b);
-            X01 = s01 + (k1a + 3.0f * (k2a + k3a) + k4a) * h_ * 0.125f;
-            X23 = s23 + (k1b + 3.0f * (k2b + k3b) + k4b) * h_ * 0.125f;
+            const f2 k2 = rhs(P1{}, s + h_ * k1 * kOneThird, cz);
+            const f2 k3 = rhs(P0{}, s + h_ * (k2 - k1 * kOneThird), cz);
+            const f2 k4 = rhs(P1{}, s + h_ * (k1 - k2 + k3), cz);
+            X = s + (k1 + 3.0f * (k2 + k3) + k4) * h_ * 0.125f;
         }
         if constexpr (SAVE && PSNODE_K1X_SAVE_ABL == 4) sa_run += 3 * (size_t)a.B * hp * kStg - (size_t)768 * kStg;
     };
