@@ -13,6 +13,7 @@ plotting and replay-buffer bookkeeping.  With --synthetic it writes a small data
     python examples/train_direct.py --model ode01 --synthetic --epochs 3
     python examples/train_direct.py --model dae02 --train-data training.npz --test-data testing.npz --solver euler
     python examples/train_direct.py --model dae02 --synthetic --loss huber --loss-param 0.05
+    python examples/train_direct.py --model dae01 --synthetic --scattered-events      # every sample's fault at its own step
 """
 import argparse
 import os
@@ -31,20 +32,24 @@ from py_psnode_amd.neural_dae.neural_base import DAE_Curves_Sample, ODE_Curves_S
 HIDDEN = {"ode01": 64, "ode02": 16, "dae01": 64, "dae02": 64}      # what the scripts ship with (their debug override)
 
 
-def write_synthetic(path, n, T, dae, seed):
-    """Damped oscillators driven by a piecewise-constant input: enough structure for the loss to go down."""
+def write_synthetic(path, n, T, dae, seed, scattered=False):
+    """Damped oscillators driven by a piecewise-constant input: enough structure for the loss to go down.  scattered: every sample's
+    input steps at a grid point drawn on its own (between T / 4 and 3 T / 4) instead of at T / 2 for all -- the dataset a model whose event
+    object is per-trajectory is for."""
     r = np.random.default_rng(seed)
     t = np.tile((np.arange(T, dtype=np.float32) * 0.01).reshape(1, T, 1), (n, 1, 1))
     z = np.repeat(r.standard_normal((n, 1, 2)).astype(np.float32) * 0.3, T, axis=1)
-    z[:, T // 2:] += 0.2
+    k = r.integers(T // 4, max(3 * T // 4, T // 4 + 1), n) if scattered else np.full(n, T // 2)          # the fault step of each sample
+    z += np.float32(0.2) * (np.arange(T).reshape(1, T, 1) >= k.reshape(n, 1, 1)).astype(np.float32)
+    at = lambda a: a[np.arange(n), k][:, None].copy()          # [n, 1, D]: row k[s] of sample s
     w = 2.0 + r.random((n, 1, 8)).astype(np.float32) * 3.0
     ph = r.random((n, 1, 8)).astype(np.float32) * 6.28
     x = (0.3 * np.exp(-0.5 * t) * np.sin(w * t + ph) + 0.1 * z.sum(-1, keepdims=True)).astype(np.float32)
     d = dict(name=np.array([[f"x{k}", "pu"] for k in range(8)], dtype=object), t=t, x=x, z=z,
-             event_t=np.full((n, 1, 1), 0.01 * (T // 2), dtype=np.float32), z_jump=z[:, T // 2:T // 2 + 1].copy())
+             event_t=at(t) if scattered else np.full((n, 1, 1), 0.01 * (T // 2), dtype=np.float32), z_jump=at(z))
     if dae:
         v = (0.5 * z + 0.05 * r.standard_normal((n, T, 2))).astype(np.float32)
-        d.update(v=v, i=(x[:, :, :2] * 0.5 + v * 0.2).astype(np.float32), v_jump=v[:, T // 2:T // 2 + 1].copy(),
+        d.update(v=v, i=(x[:, :, :2] * 0.5 + v * 0.2).astype(np.float32), v_jump=at(v),
                  mask=np.ones((n, T, 1), dtype=np.float32))
     np.savez(path, **d)
 
@@ -109,6 +114,10 @@ def main(argv=None):
     ap.add_argument("--train-data")
     ap.add_argument("--test-data")
     ap.add_argument("--synthetic", action="store_true", help="write a small synthetic dataset first")
+    ap.add_argument("--scattered-events", action="store_true",
+                    help="the synthetic dataset draws each sample's fault step on its own, and the model's event object applies the events per "
+                         "trajectory (model.event.per_trajectory = True: the generic kernels K0 / K5; ode01 / dae01 -- the latent integrators of "
+                         "the direct_encode models have no generic backward at every width)")
     ap.add_argument("--num", type=int, default=320)
     ap.add_argument("--step", type=int, default=201, help="grid points per sample (cut_length)")
     ap.add_argument("--batch", type=int, default=64)
@@ -124,8 +133,8 @@ def main(argv=None):
     if args.synthetic:
         tmp = tempfile.TemporaryDirectory()
         args.train_data, args.test_data = os.path.join(tmp.name, "training.npz"), os.path.join(tmp.name, "testing.npz")
-        write_synthetic(args.train_data, args.num, args.step, dae, 0)
-        write_synthetic(args.test_data, max(args.num // 4, 8), args.step, dae, 1)
+        write_synthetic(args.train_data, args.num, args.step, dae, 0, args.scattered_events)
+        write_synthetic(args.test_data, max(args.num // 4, 8), args.step, dae, 1, args.scattered_events)
     cls = DAE_Curves_Sample if dae else ODE_Curves_Sample
     train = datapath.ResidentDataset(cls(args.train_data, dev, num_sample=args.num, cut_length=args.step), dev)
     test = datapath.ResidentDataset(cls(args.test_data, dev), dev)
@@ -133,6 +142,7 @@ def main(argv=None):
     test_loader = datapath.ResidentLoader(test, batch_size=max(len(test) // 10, 1), shuffle=False)
     model = build(args.model, args.solver).to(dev)
     model.solver.fused = "require"           # fail loudly rather than walk the time loop in Python
+    model.event.per_trajectory = args.scattered_events      # a sample jumps where ITS clock meets ITS event time, not where sample 0's does
     opt = torch.optim.Adam(model.parameters(), lr=args.lr)
     loss_func = L.loss_kind_of(args.loss if args.loss_param is None else (args.loss, args.loss_param))
     dims, total = evaluate(args.model, model, test_loader, loss_func)

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define PSNODE_ABI_VERSION 10    /* 10 also carries the additive psnode_act_f32 / *_act_*, psnode_rk_tableau_f32 / *_rk_*, psnode_substeps_f32 / *_sub_* and *_lin_* entry points (end of this file), and psnode_loss_fn_f32 / psnode_masked_loss_* / psnode_loss_per_sample_f32 (next to psnode_masked_mse_f32) */
+#define PSNODE_ABI_VERSION 10    /* 10 also carries the additive psnode_act_f32 / *_act_*, psnode_rk_tableau_f32 / *_rk_*, psnode_substeps_f32 / *_sub_*, *_lin_* and *_pev_* / psnode_event_table_pt_f32 entry points (end of this file), and psnode_loss_fn_f32 / psnode_masked_loss_* / psnode_loss_per_sample_f32 (next to psnode_masked_mse_f32) */
 #define PSNODE_MAX_LAYERS 8      /* Linear layers per MLP */
 #define PSNODE_MAX_WIDTH 1024    /* widest layer OUTPUT the kernels accept */
 #define PSNODE_MAX_IN_WIDTH 2048 /* widest first-layer INPUT (the latent DE of DAE_02 at --hidden 128 is 12 x 128 = 1536 wide) */
@@ -837,6 +837,50 @@ int32_t psnode_dae_backward_lin_supported(const psnode_dae_bwd_tf_args_f32* args
 size_t psnode_dae_backward_lin_workspace_bytes(const psnode_dae_bwd_tf_args_f32* args, const psnode_act_f32* de_act,
                                                const psnode_act_f32* ae_act, const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub);
 int32_t psnode_dae_backward_lin_f32(const psnode_dae_bwd_tf_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                    const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, void* workspace, size_t workspace_bytes,
+                                    void* stream);
+
+/* ---- Per-trajectory events on the generic kernels (additive to ABI 10; DESIGN.md "Per-trajectory events on K0 / K5").
+ * The entry point itself means that the args' event_idx is an int32 [T-1, B] table, row-major [k][b]: the index of the event trajectory b
+ * takes at step k, -1 = none.  A trajectory with an index >= 0 reads z_jump[b, idx] / v_jump[b, idx] in place of row k of z / v for that
+ * interval (all its sub-steps) and, in a DAE, replaces the algebraic variable it carries by the head at (x_k; the jumped rows); a
+ * trajectory with -1 reads the dataset rows and keeps the variable it carries.  That is, trajectory b is computed as the shared rule
+ * (psnode_event_table_f32, event_idx [T-1]) computes it in a batch that consists of b alone.  Sub-steps, the tableau, the activations
+ * and both teacher-forcing flags are what the _sub entry points define.  A backward call writes a hit trajectory's external adjoint to
+ * grad_z_jump / grad_v_jump [b, idx] and zero to row k of grad_z / grad_v, another trajectory's to row k; no atomics, bitwise repeatable.
+ * psnode_event_table_pt_f32 builds the table: one thread per (k, b) compares clock[k * stride_k + b * stride_b] with
+ * event_times[b * stride_eb + e * stride_e], e < n_events (strides in elements), exact float equality, lowest matching e; an entry that
+ * matches no clock value (NaN, the padding of a shorter list) never fires; *dup_flag (may be NULL) is set to 1 if any trajectory has two
+ * entries that match one step, and is otherwise left as it is.
+ * Rules (the entry points take exactly what their _sub siblings take):
+ *   - a NULL psnode_substeps_f32 means one sub-step; otherwise substeps outside 1..1024 gives PSNODE_ERR_DIMS; every substeps >= 1 runs here;
+ *   - a NULL act is ELU(1); a NULL tableau is the built-in `method` of the args written as its tableau;
+ *   - `kernel` must be PSNODE_KERNEL_AUTO or _GENERIC and the save_* / saved_* pointers NULL (PSNODE_ERR_UNSUPPORTED); a teacher-forced
+ *     backward needs ELU(1); the _supported queries answer for the LDS fit, which is the _sub build's;
+ *   - a NULL event_idx gives PSNODE_ERR_NULL (event-less calls take the other families); a backward call with substeps > 1, T >= 2 and
+ *     a NULL x_sub gives PSNODE_ERR_NULL.
+ * Every check returns its status before anything is launched.  Workspaces: those of the _rk entry points, as for the _lin family (the
+ * DAE backward's: psnode_dae_backward_rk_workspace_bytes with the same args and acts and any valid tableau -- the size does not depend
+ * on the tableau, on the number of sub-steps or on the event table); this family has no query of its own. */
+int32_t psnode_event_table_pt_f32(int64_t n_steps, int64_t B, const float* clock, int64_t stride_k, int64_t stride_b,
+                                  const float* event_times, int64_t stride_eb, int64_t stride_e, int32_t n_events, int32_t* event_idx,
+                                  int32_t* dup_flag, void* stream);
+int32_t psnode_ode_integrate_pev_supported(const psnode_ode_args_f32* args, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
+                                           const psnode_substeps_f32* sub);
+int32_t psnode_ode_integrate_pev_f32(const psnode_ode_args_f32* args, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
+                                     const psnode_substeps_f32* sub, void* workspace, size_t workspace_bytes, void* stream);
+int32_t psnode_dae_integrate_pev_supported(const psnode_dae_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                           const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub);
+int32_t psnode_dae_integrate_pev_f32(const psnode_dae_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                     const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, void* workspace, size_t workspace_bytes,
+                                     void* stream);
+int32_t psnode_ode_backward_pev_supported(const psnode_ode_bwd_args_f32* args, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
+                                          const psnode_substeps_f32* sub);
+int32_t psnode_ode_backward_pev_f32(const psnode_ode_bwd_args_f32* args, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
+                                    const psnode_substeps_f32* sub, void* workspace, size_t workspace_bytes, void* stream);
+int32_t psnode_dae_backward_pev_supported(const psnode_dae_bwd_tf_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                          const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub);
+int32_t psnode_dae_backward_pev_f32(const psnode_dae_bwd_tf_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
                                     const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, void* workspace, size_t workspace_bytes,
                                     void* stream);
 

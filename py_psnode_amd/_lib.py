@@ -37,6 +37,8 @@ ABI_VERSION = 10         # == PSNODE_ABI_VERSION of include/psnode_hip.h (2: rou
                          #     sub-steps per grid interval on K0 / K5;
                          #     additive, same version: the psnode_{ode,dae}_{integrate,backward}_lin_* entry points -- z | v interpolated
                          #     linearly inside every grid interval on K0 / K5;
+                         #     additive, same version: psnode_event_table_pt_f32 and the psnode_{ode,dae}_{integrate,backward}_pev_* entry
+                         #     points -- per-trajectory events (an event table [T-1, B]) on K0 / K5;
                          #     additive, same version: psnode_loss_fn_f32 and psnode_masked_loss_* / psnode_loss_per_sample_f32 -- L1, SmoothL1 and
                          #     Huber on K6, and the per-sample evaluation table of all four kinds)
 LIB_NAME = "libpsnode_hip.so"
@@ -75,6 +77,10 @@ EXPORTS = (
     "psnode_ode_integrate_lin_supported", "psnode_ode_integrate_lin_f32", "psnode_dae_integrate_lin_supported", "psnode_dae_integrate_lin_f32",
     "psnode_ode_backward_lin_supported", "psnode_ode_backward_lin_f32",
     "psnode_dae_backward_lin_supported", "psnode_dae_backward_lin_workspace_bytes", "psnode_dae_backward_lin_f32",
+    "psnode_event_table_pt_f32",
+    "psnode_ode_integrate_pev_supported", "psnode_ode_integrate_pev_f32", "psnode_dae_integrate_pev_supported", "psnode_dae_integrate_pev_f32",
+    "psnode_ode_backward_pev_supported", "psnode_ode_backward_pev_f32",
+    "psnode_dae_backward_pev_supported", "psnode_dae_backward_pev_f32",
 )
 
 
@@ -290,6 +296,9 @@ def load():
     lib.psnode_workspace_bytes.argtypes = [ctypes.POINTER(MlpF32), ctypes.POINTER(MlpF32)]
     lib.psnode_event_table_f32.restype = c_int32
     lib.psnode_event_table_f32.argtypes = [c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p]
+    lib.psnode_event_table_pt_f32.restype = c_int32
+    lib.psnode_event_table_pt_f32.argtypes = [c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p,
+                                              c_void_p]
     lib.psnode_ode_integrate_f32.restype = c_int32
     lib.psnode_ode_integrate_f32.argtypes = [ctypes.POINTER(OdeArgsF32), c_void_p, c_size_t, c_void_p]
     lib.psnode_dae_integrate_f32.restype = c_int32
@@ -342,7 +351,7 @@ def load():
     sub_p = ctypes.POINTER(SubstepsF32)
     for name, args_t, n_act in (("ode_integrate", OdeArgsF32, 1), ("dae_integrate", DaeArgsF32, 2), ("ode_backward", OdeBwdArgsF32, 1),
                                 ("dae_backward", DaeBwdTfArgsF32, 2)):
-        for fam in ("sub", "lin"):      # (the _lin entry points take exactly what their _sub siblings take)
+        for fam in ("sub", "lin", "pev"):      # (the _lin and _pev entry points take exactly what their _sub siblings take)
             q = getattr(lib, f"psnode_{name}_{fam}_supported")
             q.restype, q.argtypes = c_int32, [ctypes.POINTER(args_t)] + [act_p] * n_act + [rk_p, sub_p]
             f = getattr(lib, f"psnode_{name}_{fam}_f32")

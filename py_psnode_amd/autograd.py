@@ -50,17 +50,19 @@ def _generic_only_training(opts, kernel, teacher_forced, T=2) -> bool:
 
 
 def ode_training_supported(method, layers, x_dim, z_dim, T, B, kernel="auto", act=None, input_true_x=False, substeps=1,
-                           externals="hold") -> bool:
+                           externals="hold", per_trajectory=False) -> bool:
     """What the solver asks before it routes a call that needs autograd to the fused forward + backward pair.  act (fused.Act; None =
     ELU(1)): an activation other than ELU(1) trains on K0 + K5 alone, so K5 answers.  input_true_x: teacher-forced training -- K4f's
     recompute form on kernel "auto" / "mfma" where the shape is its, else K5 on "auto" / "generic"; ELU(1) only.
     method a fused.Tableau: K0 + K5 on kernel "auto" / "generic" (K5's tableau build answers for its fit), the same teacher-forcing rule.
     substeps > 1: K0 + K5 in their sub-step builds on kernel "auto" / "generic" (K5's answers for its fit), the same teacher-forcing rule.
-    externals="linear": K0 + K5 in their linear-externals builds for every substeps >= 1, the same rules."""
-    opts = fused.GenericOpts.of(method, (act,), substeps, externals)
+    externals="linear": K0 + K5 in their linear-externals builds for every substeps >= 1, the same rules.
+    per_trajectory=True (a call WITH events): K0 + K5 in their per-trajectory builds for every substeps >= 1, the same rules; never
+    together with externals="linear"."""
+    opts = fused.GenericOpts.of(method, (act,), substeps, externals, bool(per_trajectory))
     if opts.family != "plain":
         return _generic_only_training(opts, kernel, input_true_x) and fused.ode_backward_supported(
-            method, layers, x_dim, z_dim, kernel, act=act, substeps=substeps, externals=externals)
+            method, layers, x_dim, z_dim, kernel, act=act, substeps=substeps, externals=externals, per_trajectory=per_trajectory)
     if input_true_x:
         if kernel in ("auto", "mfma") and fused.ode_backward_supported(method, layers, x_dim, z_dim, "wide"):
             return True
@@ -75,19 +77,21 @@ def _dae_tf_on_k7f(method, kernel, de, ae, x_dim, z_dim, v_dim, i_dim) -> bool:
 
 
 def dae_training_supported(method, de, ae, x_dim, z_dim, v_dim, i_dim, T, B, act=None, kernel="auto", input_true_x=False,
-                           input_true_i=False, substeps=1, externals="hold") -> bool:
+                           input_true_i=False, substeps=1, externals="hold", per_trajectory=False) -> bool:
     """act: None (both MLPs ELU(1)) or (de_act, ae_act); an activation other than ELU(1) trains on K0 + K5 alone, so K5 answers.
     input_true_x / input_true_i: teacher-forced training (T >= 2, ELU(1) only) -- K7f's recompute form on kernel "auto" / "mfma" where the
     shape is its, else K5 on "auto" / "generic".  method a fused.Tableau: K0 + K5 on kernel "auto" / "generic", the same rules.
     substeps > 1: K0 + K5 in their sub-step builds on kernel "auto" / "generic", the same rules.
-    externals="linear": K0 + K5 in their linear-externals builds for every substeps >= 1, the same rules."""
-    opts = fused.GenericOpts.of(method, fused.dae_acts(act), substeps, externals)
+    externals="linear": K0 + K5 in their linear-externals builds for every substeps >= 1, the same rules.
+    per_trajectory=True (a call WITH events): K0 + K5 in their per-trajectory builds for every substeps >= 1, the same rules."""
+    opts = fused.GenericOpts.of(method, fused.dae_acts(act), substeps, externals, bool(per_trajectory))
     teacher_forced = input_true_x or input_true_i
     if opts.family != "plain":
         if opts.family == "act":      # (an activation alone: asked without the caller's kernel, as the ELU(1) call at the bottom is)
             kernel = "auto"
         return _generic_only_training(opts, kernel, teacher_forced, T) and fused.dae_backward_supported(
-            method, de, ae, x_dim, z_dim, v_dim, i_dim, act=act, kernel=kernel, substeps=substeps, externals=externals)
+            method, de, ae, x_dim, z_dim, v_dim, i_dim, act=act, kernel=kernel, substeps=substeps, externals=externals,
+            per_trajectory=per_trajectory)
     if teacher_forced:
         if T < 2:
             return False
@@ -270,15 +274,18 @@ class _FusedOde(torch.autograd.Function):
         return _grad_tuple(ctx, _FusedOde, dict(x0=gx0, z=gz, all_initial=ga0, z_jump=gzj), gpar)
 
 
-def _ode_sub_forward(externals):
-    """The forward of _FusedOdeSub ("hold") / _FusedOdeLin ("linear"): one body, `externals` travels to both calls."""
+def _ode_sub_forward(externals, per_trajectory=False):
+    """The forward of _FusedOdeSub ("hold") / _FusedOdeLin ("linear") / _FusedOdePev ("hold", per-trajectory events: event_idx is the
+    [T-1, B] table): one body, `externals` and `per_trajectory` travel to both calls."""
     def forward(ctx, method, kernel, act, substeps, tx, event_idx, t, x0, z, all_initial, z_jump, *params):
         global last_saved_bytes
         x_in = x0.detach().contiguous() if tx else x0.unsqueeze(0)      # tx: the whole dataset x [T,B,xd]
         xs, x_sub = fused.ode_integrate(method, _layers(params), t, x_in, z, all_initial, z_jump=z_jump, event_idx=event_idx, kernel=kernel,
-                                        input_true_x=tx, act=act, substeps=substeps, save_sub=True, externals=externals)
+                                        input_true_x=tx, act=act, substeps=substeps, save_sub=True, externals=externals,
+                                        per_trajectory=per_trajectory)
         last_saved_bytes = x_sub.numel() * x_sub.element_size()
         ctx.method, ctx.kernel, ctx.act, ctx.substeps, ctx.tx, ctx.event_idx, ctx.externals = method, kernel, act, substeps, tx, event_idx, externals
+        ctx.per_trajectory = per_trajectory
         # (tx: the backward starts every interval from the dataset row and reads no xs)
         ctx.save_for_backward(*_pack(ctx, (t, z, all_initial, x_in if tx else xs, x_sub), dict(z_jump=z_jump), params))
         return xs
@@ -297,7 +304,7 @@ class _FusedOdeSub(torch.autograd.Function):
         gx0, gz, gzj, ga0, gpar = fused.ode_backward(ctx.method, _layers(params), t, z, a0, xs, grad_xs, event_idx=ctx.event_idx, z_jump=opt["z_jump"],
                                                      need_grad_z=need_z, need_grad_zj=_needs(ctx, _FusedOdeSub, "z_jump"), kernel=ctx.kernel,
                                                      input_true_x=ctx.tx, act=ctx.act, substeps=ctx.substeps, x_sub=x_sub,
-                                                     externals=ctx.externals)
+                                                     externals=ctx.externals, per_trajectory=ctx.per_trajectory)
         if gz is None and need_z:
             gz = torch.zeros_like(z)
         return _grad_tuple(ctx, _FusedOdeSub, dict(x0=None if ctx.tx else gx0, z=gz, all_initial=ga0, z_jump=gzj), gpar)
@@ -309,18 +316,28 @@ class _FusedOdeLin(_FusedOdeSub):
     forward = _ode_sub_forward("linear")
 
 
+class _FusedOdePev(_FusedOdeSub):
+    """integrate_ODE with per-trajectory events (ODE_Event(per_trajectory=True) with events set), every substeps >= 1: _FusedOdeSub on the
+    per-trajectory builds of K0 / K5 -- event_idx is the [T-1, B] table, a trajectory's jump gradient goes to its own row of z_jump."""
+    forward = _ode_sub_forward("hold", True)
+
+
 def fused_ode_integrate(method, kernel, layers, t, x, z, all_initial, event_t=None, z_jump=None, check_events=False, input_true_x=False,
-                        x_init=None, act=None, substeps=1, externals="hold"):
+                        x_init=None, act=None, substeps=1, externals="hold", per_trajectory=False):
     """Differentiable fused integrate_ODE: gradients flow to x[0], z, all_initial, z_jump and the MLP.  input_true_x (teacher forcing,
     my_solvers.py:72-74): every step starts from the dataset row x[k]; gradients flow to z, all_initial, z_jump and the MLP (the dataset
     x gets none: callers whose x requires grad take the callback walk).  act: the MLP's activation (fused.Act), None = ELU(1); any other
-    trains on K0 + K5 (no teacher forcing)."""
+    trains on K0 + K5 (no teacher forcing).  per_trajectory: every trajectory jumps at its own event times (fused.event_table(...,
+    per_trajectory=True)); a call without events is the call it is without the flag."""
     with torch.no_grad():
-        event_idx = fused.event_table(t, event_t, check_events)
+        event_idx = fused.event_table(t, event_t, check_events, per_trajectory=per_trajectory)
     if event_idx is None:
         z_jump = None
     params = [p for wb in layers for p in wb]
     x0 = x.detach() if input_true_x else (x[0] if x_init is None else x_init)     # (x_init: integrate_ODE's extension -- no SelectBackward)
+    if per_trajectory and event_idx is not None:
+        fused.GenericOpts.of(method, (act,), substeps, externals, True).require_generic("fused_ode_integrate", kernel, False)
+        return _FusedOdePev.apply(method, kernel, act, substeps, bool(input_true_x), event_idx, t, x0, z, all_initial, z_jump, *params)
     if fused.is_linear(externals):
         return _FusedOdeLin.apply(method, kernel, act, substeps, bool(input_true_x), event_idx, t, x0, z, all_initial, z_jump, *params)
     if substeps != 1:
@@ -396,18 +413,19 @@ class _FusedDaeTeacherForced(torch.autograd.Function):
         return _dae_grads(ctx, _FusedDaeTeacherForced, g, z, v)
 
 
-def _dae_sub_forward(externals):
-    """The forward of _FusedDaeSub ("hold") / _FusedDaeLin ("linear"): one body, `externals` travels to both calls."""
+def _dae_sub_forward(externals, per_trajectory=False):
+    """The forward of _FusedDaeSub ("hold") / _FusedDaeLin ("linear") / _FusedDaePev ("hold", per-trajectory events): one body, `externals`
+    and `per_trajectory` travel to both calls."""
     def forward(ctx, method, kernel, act, substeps, tx, ti, event_idx, n_de, t, x_init, x, z, v, i, all_initial, z_jump, v_jump, *params):
         de, ae = _layers(params, n_de)
         non_elu = act is not None and any(a is not None for a in act)
         xs, is_, x_sub = fused.dae_integrate(method, de, ae, x_init, t, x, z, v, i, all_initial, z_jump=z_jump, v_jump=v_jump, event_idx=event_idx,
                                              kernel=kernel, input_true_x=tx, input_true_i=ti, act=act if non_elu else None, substeps=substeps,
-                                             save_sub=True, externals=externals)
+                                             save_sub=True, externals=externals, per_trajectory=per_trajectory)
         global last_saved_bytes
         last_saved_bytes = x_sub.numel() * x_sub.element_size()
         ctx.method, ctx.kernel, ctx.act, ctx.substeps, ctx.tx, ctx.ti = method, kernel, act if non_elu else None, substeps, tx, ti
-        ctx.n_de, ctx.event_idx, ctx.externals = n_de, event_idx, externals
+        ctx.n_de, ctx.event_idx, ctx.externals, ctx.per_trajectory = n_de, event_idx, externals, per_trajectory
         ctx.save_for_backward(*_pack(ctx, (t, z, v, all_initial, xs, is_, x_sub, x, i), dict(z_jump=z_jump, v_jump=v_jump), params))
         return xs, is_
     return staticmethod(forward)
@@ -422,7 +440,8 @@ class _FusedDaeSub(torch.autograd.Function):
     def backward(ctx, grad_xs, grad_is):
         (t, z, v, a0, xs, is_, x_sub, x, i), opt, params = _unpack(ctx, 9)
         de, ae = _layers(params, ctx.n_de)
-        common = dict(event_idx=ctx.event_idx, kernel=ctx.kernel, substeps=ctx.substeps, x_sub=x_sub, externals=ctx.externals, **opt)
+        common = dict(event_idx=ctx.event_idx, kernel=ctx.kernel, substeps=ctx.substeps, x_sub=x_sub, externals=ctx.externals,
+                      per_trajectory=ctx.per_trajectory, **opt)
         if ctx.tx or ctx.ti:
             g = fused.dae_backward_tf(ctx.method, de, ae, t, z, v, a0, xs, is_, grad_xs, grad_is, x_true=x if ctx.tx else None,
                                       i_true=i if ctx.ti else None, **common)
@@ -436,23 +455,33 @@ class _FusedDaeLin(_FusedDaeSub):
     forward = _dae_sub_forward("linear")
 
 
+class _FusedDaePev(_FusedDaeSub):
+    """integrate_DAE with per-trajectory events (DAE_Event(per_trajectory=True) with events set), every substeps >= 1: _FusedDaeSub on the
+    per-trajectory builds of K0 / K5."""
+    forward = _dae_sub_forward("hold", True)
+
+
 def fused_dae_integrate(method, kernel, de_layers, ae_layers, x_init, t, z, v, i, all_initial, event_t=None, z_jump=None, v_jump=None,
-                        check_events=False, x=None, input_true_x=False, input_true_i=False, act=None, substeps=1, externals="hold"):
+                        check_events=False, x=None, input_true_x=False, input_true_i=False, act=None, substeps=1, externals="hold",
+                        per_trajectory=False):
     """Differentiable fused integrate_DAE: gradients flow to x_init, z, v, all_initial, the jump inputs and both MLPs.  Without teacher
     forcing `i` only provides the width of the algebraic variable.  input_true_x / input_true_i: `x` / `i` are the dataset rows the DE
     and the heads are fed (my_solvers.py:111-121); they get no gradient.  act: None or (de_act, ae_act) (fused.Act, None = ELU(1)); an
-    activation other than ELU(1) trains on K0 + K5 (no teacher forcing)."""
+    activation other than ELU(1) trains on K0 + K5 (no teacher forcing).  per_trajectory: as fused_ode_integrate."""
     with torch.no_grad():
-        event_idx = fused.event_table(t, event_t, check_events)
+        event_idx = fused.event_table(t, event_t, check_events, per_trajectory=per_trajectory)
     if event_idx is None:
         z_jump = v_jump = None
     else:
         z_jump = z_jump if (z_jump is not None and z_jump.shape[-1] > 0) else None
         v_jump = v_jump if (v_jump is not None and v_jump.shape[-1] > 0) else None
     params = [p for wb in list(de_layers) + list(ae_layers) for p in wb]
-    if substeps != 1 or fused.is_linear(externals):
+    pev = bool(per_trajectory) and event_idx is not None
+    if pev:
+        fused.GenericOpts.of(method, fused.dae_acts(act), substeps, externals, True).require_generic("fused_dae_integrate", kernel, False)
+    if pev or substeps != 1 or fused.is_linear(externals):
         xd_ = x.detach() if input_true_x else x_init.new_zeros((1, t.shape[1], 0))
-        return (_FusedDaeLin if fused.is_linear(externals) else _FusedDaeSub).apply(method, kernel, act, substeps, bool(input_true_x), bool(input_true_i), event_idx, len(de_layers), t, x_init, xd_,
+        return (_FusedDaePev if pev else _FusedDaeLin if fused.is_linear(externals) else _FusedDaeSub).apply(method, kernel, act, substeps, bool(input_true_x), bool(input_true_i), event_idx, len(de_layers), t, x_init, xd_,
                                   z, v, i.detach(), all_initial, z_jump, v_jump, *params)
     if input_true_x or input_true_i:
         xd_ = x.detach() if input_true_x else x_init.new_zeros((1, t.shape[1], 0))

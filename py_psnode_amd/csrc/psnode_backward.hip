@@ -89,6 +89,7 @@ GenericBwdCall generic_bwd_call(const psnode_dae_bwd_args_f32& a) {
 }
 // act: the activations of a non-ELU(1) call, or nullptr
 int generic_backward(const GenericBwdCall& c, const ActPair* act, void* workspace, void* stream) {
+    if (c.rk && c.pev) return generic_backward_launch<BuildPev>(c, act, static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
     if (c.rk && c.lin) return generic_backward_launch<BuildLin>(c, act, static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
     if (c.rk && c.substeps > 1) return generic_backward_launch<BuildSub>(c, act, static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
     if (c.rk) return generic_backward_launch<BuildRk>(c, act, static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
@@ -207,7 +208,7 @@ extern "C" int32_t psnode_dae_backward_f32(const psnode_dae_bwd_args_f32* a, voi
     return generic_backward(generic_bwd_call(*a), nullptr, workspace, stream);
 }
 
-// ---- The K5 entry-point families psnode_dae_backward_tf_* and psnode_{ode,dae}_backward_{act,rk,sub,lin}_*: one checked call path
+// ---- The K5 entry-point families psnode_dae_backward_tf_* and psnode_{ode,dae}_backward_{act,rk,sub,lin,pev}_*: one checked call path
 // (k5_backward), one query (k5_supported).  Order of checks per family, which is the order of the statuses of a call that is wrong in
 // several ways:
 //
@@ -218,12 +219,14 @@ extern "C" int32_t psnode_dae_backward_f32(const psnode_dae_bwd_args_f32* a, voi
 //          tableau (NULL: the args' method as one) | T, B | route | pointers, x_sub where T >= 2 | workspace
 //   _lin   struct (NULL: one sub-step) | act pair | NULL args | tableau (as _sub) | T, B | route | pointers, x_sub where substeps > 1 and
 //          T >= 2 | workspace
+//   _pev   as _lin; event_idx -- here the [T-1, B] table -- is one of the pointers (NULL: PSNODE_ERR_NULL, event-less calls take the
+//          other families)
 //   T, B: a DAE call with flags needs T >= 2.  Route (k5_route_ok): kernel AUTO / GENERIC, no saved_* rows, flags within the struct's and
 //   only next to an ELU(1) pair, the recipe dims and the LDS fit of the family's build.  Pointers: the teacher-forcing rows among them.
 //   The DAE's _act family takes psnode_dae_bwd_args_f32, the others the _tf struct: its _sub with substeps == 1 and no tableau goes to _tf
 //   (ELU(1) pair) or refuses flags (PSNODE_ERR_UNSUPPORTED, before the method is looked at) and goes to _act with the base args.
 namespace {
-enum K5Family { kFamTf, kFamAct, kFamRk, kFamSub, kFamLin };
+enum K5Family { kFamTf, kFamAct, kFamRk, kFamSub, kFamLin, kFamPev };
 constexpr uint32_t kTfFlags = PSNODE_FLAG_INPUT_TRUE_X | PSNODE_FLAG_INPUT_TRUE_I;
 
 // the difference between the three args structs: the base call, the flags and the ones the struct knows, the AE, the plain entry points
@@ -274,9 +277,9 @@ bool k5_route_ok(K5Family fam, const Args& a, const ActPair& p, bool elu1, bool 
     const bool pre = fam == kFamAct ? act_pair_keeps_u(p) : fam != kFamTf;
     return generic_ok(&b, pre, fam == kFamLin) != 0;
 }
-// the struct of a _sub / _lin call; substeps == 1 on _sub is the family without sub-steps
+// the struct of a _sub / _lin / _pev call; substeps == 1 on _sub is the family without sub-steps
 int k5_substeps(K5Family& fam, const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub) {
-    if (fam != kFamSub && !(fam == kFamLin && sub)) return PSNODE_OK;
+    if (fam != kFamSub && !((fam == kFamLin || fam == kFamPev) && sub)) return PSNODE_OK;
     const int rc = substeps_check(sub);
     if (rc == PSNODE_OK && fam == kFamSub && sub->substeps == 1) fam = tab ? kFamRk : kFamAct;
     return rc;
@@ -309,11 +312,11 @@ int k5_backward(K5Family fam, const Args* a, const psnode_act_f32* de_act, const
     if (b.T < 1 || b.B < 1 || (tf_struct && tf_flags(*a) && b.T < 2)) return PSNODE_ERR_DIMS;
     if (!k5_route_ok(fam, *a, p, elu1, false)) return PSNODE_ERR_UNSUPPORTED;
     const int nsub = fam >= kFamSub && sub ? sub->substeps : 1;
-    if (!ptrs_ok(a) || (nsub > 1 && b.T >= 2 && !sub->x_sub)) return PSNODE_ERR_NULL;
+    if (!ptrs_ok(a) || (nsub > 1 && b.T >= 2 && !sub->x_sub) || (fam == kFamPev && !b.event_idx)) return PSNODE_ERR_NULL;
     if (!workspace_ok(workspace, workspace_bytes, generic_bwd_workspace_floats(&b.de, ae_of(b), b.B) * sizeof(float))) return PSNODE_ERR_WORKSPACE;
     GenericBwdCall c = generic_bwd_call(*a);
     if (fam >= kFamRk) c.rk = &t;
-    if (fam >= kFamSub) { c.substeps = nsub; c.x_sub = sub ? sub->x_sub : nullptr; c.lin = fam == kFamLin; }
+    if (fam >= kFamSub) { c.substeps = nsub; c.x_sub = sub ? sub->x_sub : nullptr; c.lin = fam == kFamLin; c.pev = fam == kFamPev; }
     return generic_backward(c, fam == kFamTf ? nullptr : &p, workspace, stream);
 }
 
@@ -443,4 +446,24 @@ extern "C" int32_t psnode_dae_backward_lin_f32(const psnode_dae_bwd_tf_args_f32*
                                                const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, void* workspace,
                                                size_t workspace_bytes, void* stream) {
     return k5_backward(kFamLin, a, de_act, ae_act, tab, sub, workspace, workspace_bytes, stream);
+}
+
+// (per-trajectory events: the args' event_idx is the [T-1, B] table of psnode_event_table_pt_f32)
+extern "C" int32_t psnode_ode_backward_pev_supported(const psnode_ode_bwd_args_f32* a, const psnode_act_f32* de_act,
+                                                     const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub) {
+    return k5_supported(kFamPev, a, de_act, nullptr, tab, sub);
+}
+extern "C" int32_t psnode_ode_backward_pev_f32(const psnode_ode_bwd_args_f32* a, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
+                                               const psnode_substeps_f32* sub, void* workspace, size_t workspace_bytes, void* stream) {
+    return k5_backward(kFamPev, a, de_act, nullptr, tab, sub, workspace, workspace_bytes, stream);
+}
+extern "C" int32_t psnode_dae_backward_pev_supported(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act,
+                                                     const psnode_act_f32* ae_act, const psnode_rk_tableau_f32* tab,
+                                                     const psnode_substeps_f32* sub) {
+    return k5_supported(kFamPev, a, de_act, ae_act, tab, sub);
+}
+extern "C" int32_t psnode_dae_backward_pev_f32(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                               const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, void* workspace,
+                                               size_t workspace_bytes, void* stream) {
+    return k5_backward(kFamPev, a, de_act, ae_act, tab, sub, workspace, workspace_bytes, stream);
 }

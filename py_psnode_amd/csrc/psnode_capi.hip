@@ -80,10 +80,10 @@ __global__ void event_table_kernel(long long n_steps, const float* clock, long l
 // What a K0 call carries beyond its args: the build of the generic kernel that runs it (psnode_generic_build.h) and that build's kernel
 // arguments.  The plain entry points pass K0Call{}: ELU(1), the args' method, one step per interval -- the only call the MFMA kernels take.
 struct K0Call {
-    enum Build { kElu1, kAct, kRk, kSub, kLin } build;      // kAct: the act or the pre build, by the pair's kinds
+    enum Build { kElu1, kAct, kRk, kSub, kLin, kPev } build;      // kAct: the act or the pre build, by the pair's kinds
     ActPair act;                   // every build but kElu1
     psnode_rk_tableau_f32 rk;      // kRk, kSub, kLin: given, or the args' method written as one (sub_tableau)
-    SubDev sub;                    // kSub, kLin: sub-steps per grid interval and x_sub
+    SubDev sub;                    // kSub, kLin, kPev: sub-steps per grid interval and x_sub
 };
 
 int dispatch(IntegrateDev& d, bool dae, int kernel, const psnode_mlp_f32* de, const psnode_mlp_f32* ae, void* workspace,
@@ -113,6 +113,7 @@ int dispatch(IntegrateDev& d, bool dae, int kernel, const psnode_mlp_f32* de, co
         case K0Call::kRk: e = launch_generic_rk(d, dae, call.act, call.rk, stream); break;
         case K0Call::kSub: e = launch_generic_sub(d, dae, call.act, call.rk, call.sub, stream); break;
         case K0Call::kLin: e = launch_generic_lin(d, dae, call.act, call.rk, call.sub, stream); break;
+        case K0Call::kPev: e = launch_generic_pev(d, dae, call.act, call.rk, call.sub, stream); break;
     }
     return ok_or_hip(e);
 }
@@ -200,7 +201,7 @@ int fill_dae(const psnode_dae_args_f32* a, IntegrateDev& d) {
     return PSNODE_OK;
 }
 
-// ---- The K0 entry-point families psnode_{ode,dae}_integrate_{act,rk,sub,lin}_*: one checked call path (k0_integrate) and one query
+// ---- The K0 entry-point families psnode_{ode,dae}_integrate_{act,rk,sub,lin,pev}_*: one checked call path (k0_integrate) and one query
 // (k0_supported).  Order of checks per family, which is the order of the statuses of a call that is wrong in several ways:
 //
 //   _act   act pair | ELU(1) pair -> the plain entry point | NULL args | route (kernel, save_act alone) | fill_* (method, dims, pointers)
@@ -208,9 +209,10 @@ int fill_dae(const psnode_dae_args_f32* a, IntegrateDev& d) {
 //   _sub   struct (NULL: PSNODE_ERR_NULL) | substeps == 1 -> the _rk (tableau given) or the _act family | act pair | NULL args |
 //          tableau (NULL: the args' method as one) | route | fill_*
 //   _lin   struct (NULL: one sub-step) | act pair | NULL args | tableau (as _sub) | route | fill_*
+//   _pev   as _lin, then event_idx -- here the [T-1, B] table -- (NULL: PSNODE_ERR_NULL, event-less calls take the other families)
 //   then dispatch: workspace | T, B | LDS fit of the build.
 // _act_supported with an ELU(1) pair answers from method and dims alone (the plain entry point picks its own kernel).
-enum K0Family { kFamAct, kFamRk, kFamSub, kFamLin };
+enum K0Family { kFamAct, kFamRk, kFamSub, kFamLin, kFamPev };
 
 // the ODE / DAE difference: the side outputs, the recipe widths, fill_*, the AE, the plain entry point
 bool side_outputs(const psnode_ode_args_f32& a) { return a.save_act || a.save_xstage; }
@@ -236,9 +238,9 @@ bool k0_route_ok(K0Family fam, const Args& a) {
     if (a.kernel != PSNODE_KERNEL_AUTO && a.kernel != PSNODE_KERNEL_GENERIC) return false;
     return fam == kFamAct ? !a.save_act : !side_outputs(a);
 }
-// the struct of a _sub / _lin call; substeps == 1 on _sub is the family without sub-steps
+// the struct of a _sub / _lin / _pev call; substeps == 1 on _sub is the family without sub-steps
 int k0_substeps(K0Family& fam, const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub) {
-    if (fam != kFamSub && !(fam == kFamLin && sub)) return PSNODE_OK;
+    if (fam != kFamSub && !((fam == kFamLin || fam == kFamPev) && sub)) return PSNODE_OK;
     const int rc = substeps_check(sub);
     if (rc == PSNODE_OK && fam == kFamSub && sub->substeps == 1) fam = tab ? kFamRk : kFamAct;
     return rc;
@@ -266,7 +268,8 @@ int k0_integrate(K0Family fam, const Args* args, const psnode_act_f32* de_act, c
     IntegrateDev d;
     rc = fill(&c, d);
     if (rc) return rc;
-    call.build = fam == kFamAct ? K0Call::kAct : fam == kFamRk ? K0Call::kRk : fam == kFamSub ? K0Call::kSub : K0Call::kLin;
+    if (fam == kFamPev && !d.ev) return PSNODE_ERR_NULL;
+    call.build = fam == kFamAct ? K0Call::kAct : fam == kFamRk ? K0Call::kRk : fam == kFamSub ? K0Call::kSub : fam == kFamLin ? K0Call::kLin : K0Call::kPev;
     call.sub = SubDev{sub ? sub->substeps : 1, sub ? sub->x_sub : nullptr};
     return dispatch(d, ae_of(c) != nullptr, c.kernel, &c.de, ae_of(c), workspace, workspace_bytes, static_cast<hipStream_t>(stream), call);
 }
@@ -485,6 +488,25 @@ int32_t psnode_dae_integrate_lin_f32(const psnode_dae_args_f32* args, const psno
                                      const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, void* workspace, size_t workspace_bytes,
                                      void* stream) {
     return k0_integrate(kFamLin, args, de_act, ae_act, tab, sub, workspace, workspace_bytes, stream);
+}
+
+// (per-trajectory events: the args' event_idx is the [T-1, B] table of psnode_event_table_pt_f32)
+int32_t psnode_ode_integrate_pev_supported(const psnode_ode_args_f32* a, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
+                                           const psnode_substeps_f32* sub) {
+    return k0_supported(kFamPev, a, de_act, nullptr, tab, sub);
+}
+int32_t psnode_ode_integrate_pev_f32(const psnode_ode_args_f32* args, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
+                                     const psnode_substeps_f32* sub, void* workspace, size_t workspace_bytes, void* stream) {
+    return k0_integrate(kFamPev, args, de_act, nullptr, tab, sub, workspace, workspace_bytes, stream);
+}
+int32_t psnode_dae_integrate_pev_supported(const psnode_dae_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                           const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub) {
+    return k0_supported(kFamPev, a, de_act, ae_act, tab, sub);
+}
+int32_t psnode_dae_integrate_pev_f32(const psnode_dae_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                     const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, void* workspace, size_t workspace_bytes,
+                                     void* stream) {
+    return k0_integrate(kFamPev, args, de_act, ae_act, tab, sub, workspace, workspace_bytes, stream);
 }
 
 int32_t psnode_ode_kernel_for(const psnode_ode_args_f32* a) {

@@ -326,6 +326,7 @@ struct GenericBwdCall {
     int substeps;              // generic_backward_launch<BuildSub> (with rk): sub-steps per grid interval, > 1, and the sub-states K0 wrote
     const float* x_sub;        // [T-1, substeps-1, B, xd]
     bool lin;                  // generic_backward_launch<BuildLin> (with rk; substeps >= 1): z | v interpolated linearly inside every grid interval
+    bool pev;                  // generic_backward_launch<BuildPev> (with rk; substeps >= 1; not with lin): `ev` is the [T-1, B] table of per-trajectory events
 };
 struct ActPair;     // psnode_act.h: the DE's and the AE's activation of a non-ELU(1) call
 size_t generic_bwd_workspace_floats(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, long long B);
@@ -336,7 +337,8 @@ int generic_bwd_fits(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, int xd,
 // (ignores `act`), BuildAct (the activations of psnode_act.h), BuildPre (those and the pre-activation family), BuildRk (the tableau build:
 // every activation kind -- `act` is required, ELU(1) runs as ELU with alpha = 1 -- and c.rk in place of c.method; it keeps the
 // pre-activations like the pre build), BuildSub (the tableau build with c.substeps sub-steps per grid interval, read from c.x_sub), BuildLin
-// (the sub-step build, any c.substeps >= 1, with linearly interpolated externals: c.lin).
+// (the sub-step build, any c.substeps >= 1, with linearly interpolated externals: c.lin), BuildPev (the sub-step build, any c.substeps >= 1,
+// with per-trajectory events: c.pev, c.ev not null).
 // psnode_backward.hip: generic_backward picks among them.
 template <class B>
 int generic_backward_launch(const GenericBwdCall& c, const ActPair* act, float* workspace, hipStream_t stream);

@@ -1,6 +1,6 @@
-// The body of K0's kernel (psnode_generic_impl.h), as text: each of the six objects writes its own __global__ -- generic_kernel(a),
+// The body of K0's kernel (psnode_generic_impl.h), as text: each of the seven objects writes its own __global__ -- generic_kernel(a),
 // generic_act_kernel(a, act), generic_pre_act_kernel(a, act), generic_rk_kernel(a, act, rk), generic_sub_kernel(a, act, rk, sub),
-// generic_lin_kernel(a, act, rk, sub) -- and includes this file between its braces.
+// generic_lin_kernel(a, act, rk, sub), generic_pev_kernel(a, act, rk, sub) -- and includes this file between its braces.
 // Template parameters in scope: DAE, MODE, ML, QM.  Names in scope: a, act (ActPair; NoActPair in the ELU(1) object), rk (read under
 // Bd::rk only) and sub (SubDev, read under Bd::sub only); the objects without one declare an unread one.  The build policy Bd decides the
 // rest with `if constexpr`.
@@ -137,7 +137,12 @@
     // the next step's event index travels through a VECTOR load (every lane the same address): a scalar load would be waited for by the
     // very next LDS wait (SMEM returns out of order, so any lgkmcnt wait is lgkmcnt(0)) -- an L2 round trip at the top of every step
     const int* evp = a.ev ? a.ev : reinterpret_cast<const int*>(a.t.p);      // (a valid address when there are no events)
+    // Per-trajectory events (Bd::pev): the table is [T - 1][B] and every thread carries the index of ITS column -- every loop below walks
+    // idx = tid + NT j, so a thread only ever touches column tid % TB -- loaded one step ahead like the shared one.  The host refuses a
+    // call of this build without a table.
+    static_assert(NT % TB == 0 && TB <= 64 && 64 % TB == 0, "a thread owns one trajectory column, and every wave holds all of them");
     int evn_v = (a.ev && a.T > 1) ? __builtin_nontemporal_load(evp) : -1;
+    if constexpr (Bd::pev) evn_v = a.T > 1 ? evp[gb(tid % TB)] : -1;
 
     float pz[PF];
     // Linear externals (Bd::lin): stage s of sub-step j reads z | v at theta = (j + c_s) / nsub between the interval's left rows (wl) and the
@@ -150,7 +155,12 @@
     // (my_solvers.py:95, 121); the pseudo-step k = -1 of the DAE is that last slot alone, for grid point 0.
     for (long long k = DAE ? -1 : 0; k + 1 < (Bd::sub ? Tn : a.T); ++k) {
         K0_PROF(5)
-        const int ev = k >= 0 ? __builtin_amdgcn_readfirstlane(evn_v) : -1;
+        // ev: the event index of this step -- launch-uniform, or (Bd::pev) this thread's column's; any_ev: some trajectory of the workgroup
+        // has one (workgroup-uniform: each wave holds every column), which is what decides whether the event slot runs
+        // (the constant conditions on Bd::pev keep the statements of the other builds where they were: their code does not change)
+        const int ev = k >= 0 ? (Bd::pev ? evn_v : __builtin_amdgcn_readfirstlane(evn_v)) : -1;
+        [[maybe_unused]] bool any_ev = false;
+        if constexpr (Bd::pev) any_ev = __builtin_amdgcn_ballot_w64(ev >= 0) != 0;
         if (k >= 0) {
             // ---- this step's inputs (zero-order hold: the left grid point feeds every stage)
             if constexpr (Bd::sub) { if (tid < TB) dts[tid] = (tn - tc) / (float)nsub; }
@@ -183,6 +193,7 @@
             const long long k1 = k + 1, k2 = k + 2 < a.T ? k + 2 : a.T - 1;
             if (tid < TB) { tc = tn; tn = a.t.p[k2 * a.t.st + gb(tid) * a.t.sb]; }
             evn_v = (a.ev && k1 + 1 < a.T) ? evp[k1] : -1;
+            if constexpr (Bd::pev) evn_v = k1 + 1 < a.T ? evp[k1 * a.B + gb(tid % TB)] : -1;
 #pragma unroll
             for (int j = 0; j < PF; ++j) {
                 const int idx = tid + NT * j;
@@ -198,7 +209,7 @@
         SubIter<Bd::sub> si(k >= 0 ? nsub : 1);
         do {
         const int e_end = (DAE && si.last()) ? nstage + 1 : nstage;
-        for (int e = k < 0 ? nstage + 1 : ((DAE && (si.first() ? ev >= 0 : !true_i)) ? 0 : 1); e <= e_end; ++e) {
+        for (int e = k < 0 ? nstage + 1 : ((DAE && (si.first() ? (Bd::pev ? any_ev : ev >= 0) : !true_i)) ? 0 : 1); e <= e_end; ++e) {
             const bool is_ae = DAE && (e == 0 || e == nstage + 1);
             const bool ae_next = DAE && e == nstage && (si.last() || !true_i);
             int f;
@@ -228,6 +239,8 @@
                     for (int idx = tid; idx < id * TB; idx += NT) {
                         const int r = idx / TB, c = idx % TB;
                         const float v = lds[f + qi(r, c)];
+                        // (per-trajectory events: the event-time head ran because SOME column has a hit; the others keep the i they carry)
+                        if constexpr (Bd::pev) { if (e == 0 && si.first() && ev < 0) continue; }
                         icur[idx] = v;       // read back by the same thread (below, or at the top of the next step)
                         if (e == 0) put_ext(nzv + r, c, true_i ? a.i.p[k * a.i.st + gb(c) * a.i.sb + r] : v);
                         else if (b0 + c < a.B) a.io[((k + 1) * a.B + b0 + c) * id + r] = v;

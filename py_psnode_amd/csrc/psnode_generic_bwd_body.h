@@ -1,7 +1,7 @@
-// The body of K5's kernel (psnode_generic_bwd_impl.h), as text: each of the six objects writes its own __global__ --
+// The body of K5's kernel (psnode_generic_bwd_impl.h), as text: each of the seven objects writes its own __global__ --
 // generic_backward_kernel(a), generic_backward_act_kernel(a, act), generic_backward_pre_act_kernel(a, act),
-// generic_backward_rk_kernel(a, act, rk), generic_backward_sub_kernel(a, act, rk, sub), generic_backward_lin_kernel(a, act, rk, sub) -- and
-// includes this file between its braces.
+// generic_backward_rk_kernel(a, act, rk), generic_backward_sub_kernel(a, act, rk, sub), generic_backward_lin_kernel(a, act, rk, sub),
+// generic_backward_pev_kernel(a, act, rk, sub) -- and includes this file between its braces.
 // Template parameters in scope: gg, REG, ggA, STR.  Names in scope: a, act (ActPair; NoActPair in the ELU(1) object), rk (read under
 // Bd::rk only) and sub (SubDev, read under Bd::sub only); the objects without one declare an unread one.
     constexpr bool DE_TM = REG || STR == 2;      // the DE's LDS accumulators are tile-major
@@ -146,6 +146,7 @@
                     continue;
                 }
             }
+            if constexpr (Bd::pev) { if (jzv < 0 && ev < 0) continue; }      // (the event-time head of a column without a hit: no jump row is its)
             if (jzv >= 0) {
                 float* dst = isz ? a.gz : a.gv;
                 if (dst) dst[(jzv * a.B + b0 + c) * w_ + d_] += g;
@@ -181,7 +182,14 @@
         look_ahead(a.T - 2);
     }
     for (long long k = a.T - 2; k >= 0; --k) {
-        const int ev = a.ev ? a.ev[k] : -1;
+        // ev: the event index of this step -- launch-uniform, or (Bd::pev: a [T - 1][B] table, which the host requires) that of this
+        // thread's column: every TILE_LOOP and look-ahead item of a thread lies in column tid % TB.  any_ev: some column of the workgroup
+        // has a hit (workgroup-uniform: each wave holds every column) -- what decides whether the event-time head is evaluated at all.
+        // (the constant conditions on Bd::pev keep the statements of the other builds where they were: their code does not change)
+        static_assert(NT % TB == 0 && 64 % TB == 0, "a thread owns one trajectory column, and every wave holds all of them");
+        const int ev = Bd::pev ? a.ev[k * a.B + gb(tid % TB)] : (a.ev ? a.ev[k] : -1);
+        [[maybe_unused]] bool any_ev = false;
+        if constexpr (Bd::pev) any_ev = __builtin_amdgcn_ballot_w64(ev >= 0) != 0;
         if constexpr (Bd::sub) { if (tid < TB) dts[tid] = (la_tn - la_t) / (float)nsub; }
         else { if (tid < TB) dts[tid] = la_tn - la_t; }
         float gx_in[LA];                             // the incoming gradient of grid point k, consumed at the bottom of the step
@@ -257,7 +265,7 @@
             // (2) algebraic input of this step's DE (ti: the dataset row, also on event steps)
             if (ti) {
                 TILE_LOOP(id) ext[(nzv + r) * TP + c] = a.it[(k * a.B + gb(c)) * id + r];
-            } else if (ev >= 0 || inner) {
+            } else if ((Bd::pev ? any_ev : ev >= 0) || inner) {
                 const float* xr = x0;
                 if (tx && !inner) {       // the event-time head reads the RUNNING state xs[k], not the row the DE starts from (xst is free until (3a))
                     TILE_LOOP(xd) xst[r * TP + c] = a.xs[(k * a.B + gb(c)) * xd + r];
@@ -267,7 +275,11 @@
                 ae_input(xr, -1);
                 if constexpr (STR >= 1) g_forward_str(a.ae, a.fimgA, acts, qb, qoA, ActCtx{act.ae, upre}); else g_forward(a.ae, acts, wbuf, ActCtx{act.ae, upre});
                 const float* out = acts + a.ae.act[a.ae.L] * TP;
-                TILE_LOOP(id) ext[(nzv + r) * TP + c] = out[r * TP + c];
+                if constexpr (Bd::pev) {      // the event-time head is taken by the columns with a hit; the others read the i they carried
+                    TILE_LOOP(id) ext[(nzv + r) * TP + c] = (inner || ev >= 0) ? out[r * TP + c] : a.is_[(k * a.B + gb(c)) * id + r];
+                } else {
+                    TILE_LOOP(id) ext[(nzv + r) * TP + c] = out[r * TP + c];
+                }
             } else {
                 TILE_LOOP(id) ext[(nzv + r) * TP + c] = a.is_[(k * a.B + gb(c)) * id + r];
             }
@@ -376,7 +388,17 @@
             __syncthreads();
             if (ti) {        // the DE read i_true[k]: nothing flows back through the algebraic variable
                 TILE_LOOP(id) gic[r * TP + c] = (on(c) && a.gis) ? a.gis[(k * a.B + gb(c)) * id + r] : 0.0f;
-            } else if (ev >= 0) {   // i_in = g(x_k; jumps): its gradient flows into x_k and the jump inputs; i_k itself was unused
+            } else if (Bd::pev ? any_ev : ev >= 0) {   // i_in = g(x_k; jumps): its gradient flows into x_k and the jump inputs; i_k itself was unused
+                if constexpr (Bd::pev) {
+                    // ... in the columns with a hit.  The others fed the DE the i they carried: their adjoint goes on into gic (the arm
+                    // below), and their output gradient is ZERO in the head's VJP, so that they add nothing to its weight gradients, to
+                    // ga0s, to gx0 or to a jump row.  (Each thread rewrites the gext elements it reads; ae_vjp's first barrier orders the rest.)
+                    TILE_LOOP(id) {
+                        const float g = gext[(nzv + r) * TP + c];
+                        gic[r * TP + c] = (ev >= 0 ? 0.0f : g) + ((on(c) && a.gis) ? a.gis[(k * a.B + gb(c)) * id + r] : 0.0f);
+                        if (ev < 0) gext[(nzv + r) * TP + c] = 0.0f;
+                    }
+                }
                 const float* xr = x0;
                 if (tx) {    // (the stages are done with xst)
                     TILE_LOOP(xd) xst[r * TP + c] = a.xs[(k * a.B + gb(c)) * xd + r];
@@ -384,7 +406,7 @@
                     xr = xst;
                 }
                 ae_vjp(xr, -1, ev, gext + nzv * TP, gx0);
-                TILE_LOOP(id) gic[r * TP + c] = (on(c) && a.gis) ? a.gis[(k * a.B + gb(c)) * id + r] : 0.0f;
+                if constexpr (!Bd::pev) { TILE_LOOP(id) gic[r * TP + c] = (on(c) && a.gis) ? a.gis[(k * a.B + gb(c)) * id + r] : 0.0f; }
             } else {
                 TILE_LOOP(id) gic[r * TP + c] = gext[(nzv + r) * TP + c] + ((on(c) && a.gis) ? a.gis[(k * a.B + gb(c)) * id + r] : 0.0f);
             }

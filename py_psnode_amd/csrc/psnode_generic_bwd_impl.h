@@ -15,7 +15,7 @@
 // Teacher forcing (GBwd::flags) changes the outer sweep only: which rows a step starts from and which adjoints travel to the step before.
 #include <string.h>
 
-// Six objects are compiled from this header, one per build policy (psnode_generic_build.h).  Each of psnode_generic_bwd{,_act,_pre,_rk,_sub,_lin}.hip
+// Seven objects are compiled from this header, one per build policy (psnode_generic_build.h).  Each of psnode_generic_bwd{,_act,_pre,_rk,_sub,_lin,_pev}.hip
 // names its policy `Bd` in front of the include, writes its kernel around psnode_generic_bwd_body.h and instantiates the launcher:
 //   BuildElu1  generic_backward_kernel(a)                    ELU(1) and its derivative
 //   BuildAct   generic_backward_act_kernel(a, act)           the DE's and the AE's activation as a second kernel argument (ActPair)
@@ -28,6 +28,9 @@
 //              around (2) .. (3b) of the kernel body that starts each sub-step from the state K0 stored in SubDev::x_sub; no LDS of its own
 //   BuildLin   generic_backward_lin_kernel(a, act, rk, sub)  the sub-step build (every n >= 1) with z | v interpolated linearly per stage: ext's
 //              z | v rows are refilled per stage from the interval's two ends, a second accumulator takes the right end's adjoint; 3 nzv rows of LDS
+//   BuildPev   generic_backward_pev_kernel(a, act, rk, sub)  the sub-step build (every n >= 1) with a [T-1, B] event table: a thread reads its own
+//              column's event index, the event-time head is evaluated where any column of the workgroup has a hit and taken -- forward and
+//              in the VJP, whose output gradient is zero in the other columns -- per column; no LDS and no workspace of its own
 // The policy decides in the language: the kernel-argument structs (GMlpT / GBwdT: the pre fields are a base that is empty elsewhere), the
 // activation context ActCtx every device function takes, the stage coefficients (coef_a, coef_b) and
 // `if constexpr` in the kernel body and the launcher.  The host's fit and layout functions take `pre` at run time.

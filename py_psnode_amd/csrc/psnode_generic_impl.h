@@ -25,7 +25,7 @@
 // Padded columns: the image holds zeros there and the input builders write zeros into the pad columns of the first layer's input; a
 // hidden layer's pad units come out of the MFMA as ELU(0 + 0) = 0.
 //
-// Six objects are compiled from this header, one per build policy (psnode_generic_build.h).  Each of psnode_generic{,_act,_pre,_rk,_sub,_lin}.hip
+// Seven objects are compiled from this header, one per build policy (psnode_generic_build.h).  Each of psnode_generic{,_act,_pre,_rk,_sub,_lin,_pev}.hip
 // names its policy `Bd` in front of the include, writes its kernel around psnode_generic_body.h and its exported launcher over
 // launch_generic_build:
 //   BuildElu1  generic_kernel(a), launch_generic                    ELU(1)
@@ -37,6 +37,9 @@
 //              evaluation loop of a step runs n times on h / n, outputs and look-ahead rows advance behind the last one; no LDS of its own
 //   BuildLin   generic_lin_kernel(a, act, rk, sub), launch_generic_lin   the sub-step build (every n >= 1) with z | v interpolated linearly per
 //              stage between the interval's left rows and the next grid point's; nzv * TB floats of LDS of its own (generic_lds_bytes(.., lin))
+//   BuildPev   generic_pev_kernel(a, act, rk, sub), launch_generic_pev   the sub-step build (every n >= 1) with a [T-1, B] event table: every
+//              thread carries its own column's event index in a register, the event slot runs where any column of the workgroup has a
+//              hit and is taken per column; no LDS of its own
 // The device functions take the activation as one ordinary parameter, ActCtx; the kernel body chooses the tableau code with
 // `if constexpr (Bd::rk)`, the sub-step code with `if constexpr (Bd::sub)`.  The host's plan / fit / pack code is compiled once, in
 // psnode_generic.hip.

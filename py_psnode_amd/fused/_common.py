@@ -191,21 +191,29 @@ class GenericOpts:
     externals -- the Python counterpart of the library's K0Call: every public function builds one from its `method`, `act`, `substeps`
     and `externals` (`of`), and the value says which entry-point family the call takes (`family`, `call_generic`) and which calls are
     refused (`require_generic`, `require_plain`).  acts: one Act | None per MLP (ODE 1, DAE 2); tab: the Tableau of `method`, if it is one;
-    method_id / stages: what the args struct and the saved rows need of `method` (`method_info`)."""
+    method_id / stages: what the args struct and the saved rows need of `method` (`method_info`); per_trajectory: the call's event table
+    is [T-1, B], every trajectory jumps at its own steps (only a call that HAS events carries it: `has_events`)."""
     acts: tuple
     tab: Optional[Tableau]
     substeps: int = 1
     externals: str = "hold"
     method_id: int = _lib.EULER
     stages: int = 1
+    per_trajectory: bool = False
     family: str = dataclasses.field(init=False)
 
     def __post_init__(self):
-        """Validates substeps and externals, and names the entry-point family: "lin" (interpolated externals, every substeps >= 1), else
-        "sub" (substeps > 1), else "rk" (a Tableau), else "act" (an activation other than ELU(1)), else "plain"."""
+        """Validates substeps and externals, and names the entry-point family: "pev" (per-trajectory events, every substeps >= 1; together
+        with interpolated externals "none": no kernel carries both, `require_generic` refuses the call), else "lin" (interpolated
+        externals, every substeps >= 1), else "sub" (substeps > 1), else "rk" (a Tableau), else "act" (an activation other than ELU(1)),
+        else "plain"."""
         if isinstance(self.substeps, bool) or not isinstance(self.substeps, int) or not 1 <= self.substeps <= _lib.MAX_SUBSTEPS:
             raise ValueError(f"substeps must be an int in 1..{_lib.MAX_SUBSTEPS}, got {self.substeps!r}")
-        if is_linear(self.externals):
+        if not isinstance(self.per_trajectory, bool):
+            raise ValueError(f"per_trajectory must be a bool, got {self.per_trajectory!r}")
+        if self.per_trajectory:
+            fam = "none" if is_linear(self.externals) else "pev"
+        elif is_linear(self.externals):
             fam = "lin"
         elif self.substeps > 1:
             fam = "sub"
@@ -217,13 +225,13 @@ class GenericOpts:
 
     @staticmethod
     @functools.lru_cache(maxsize=256, typed=True)      # (a loop asks for the same immutable value call after call; typed: 2.0 and True are not 2 and 1)
-    def of(method, acts: tuple, substeps: int = 1, externals: str = "hold") -> "GenericOpts":
+    def of(method, acts: tuple, substeps: int = 1, externals: str = "hold", per_trajectory: bool = False) -> "GenericOpts":
         method_id, stages, tab = method_info(method)
-        return GenericOpts(acts, tab, substeps, externals, method_id, stages)
+        return GenericOpts(acts, tab, substeps, externals, method_id, stages, per_trajectory)
 
     def c_args(self, x_sub=None) -> list:
         """The family's C arguments behind the args struct: none ("plain"); the acts ("act"); the acts and the tableau ("rk"); the acts,
-        the tableau or NULL (= the args' method) and a psnode_substeps_f32 with the sub-state rows `x_sub` or NULL ("sub", "lin").  The list
+        the tableau or NULL (= the args' method) and a psnode_substeps_f32 with the sub-state rows `x_sub` or NULL ("sub", "lin", "pev").  The list
         owns the structs: keep it until the call has returned."""
         fam = self.family
         if fam == "plain":
@@ -231,7 +239,7 @@ class GenericOpts:
         out = _act_ptrs(self.acts)
         if fam != "act":
             out.append(ctypes.byref(self.tab.abi()) if self.tab is not None else None)
-        if fam in ("sub", "lin"):
+        if fam in ("sub", "lin", "pev"):
             s = _lib.SubstepsF32()
             s.substeps = self.substeps
             s.x_sub = x_sub.data_ptr() if x_sub is not None and x_sub.numel() else None
@@ -243,7 +251,7 @@ class GenericOpts:
         "lin" and for a call with dataset rows x_true / i_true ("tf": the family of such a call that would otherwise be "plain"), else
         psnode_dae_bwd_args_f32.  Dataset rows next to a non-ELU act alone: no entry point takes both (`call_generic` asserts it too)."""
         assert not (rows and self.family == "act"), "dae_backward: dataset rows with an activation other than ELU(1) have no entry point"
-        return _lib.DaeBwdTfArgsF32() if rows or self.family in ("rk", "sub", "lin") else _lib.DaeBwdArgsF32()
+        return _lib.DaeBwdTfArgsF32() if rows or self.family in ("rk", "sub", "lin", "pev") else _lib.DaeBwdArgsF32()
 
     def _first_option(self) -> str:
         """The first option the call carries, in the fixed order act, tableau, sub-steps, externals, as the subject of a refusal."""
@@ -253,14 +261,20 @@ class GenericOpts:
             return f"a Runge-Kutta tableau ({self.tab.name}) runs"
         if self.substeps != 1:
             return f"sub-steps per grid interval (substeps={self.substeps}) run"
-        return "linearly interpolated external inputs (externals='linear') run"
+        if self.externals == "linear":
+            return "linearly interpolated external inputs (externals='linear') run"
+        return "per-trajectory events (per_trajectory=True) run"
 
     def require_generic(self, what: str, kernel: str, saved: bool, teacher_forced: bool = False):
         """The options run on the generic kernels only: UnsupportedShapeError, naming the first option in the order act, tableau, sub-steps,
         externals, unless the kernel is "auto" / "generic" and no saved rows are asked for or given.  teacher_forced (an ode_backward with
-        dataset rows): K5 has no such form for an activation other than ELU(1)."""
+        dataset rows): K5 has no such form for an activation other than ELU(1).  The fifth option in that order is per-trajectory events;
+        together with interpolated externals they have no kernel at all."""
         if self.family == "plain":
             return
+        if self.family == "none":
+            raise _lib.UnsupportedShapeError(f"{what}: per-trajectory events (per_trajectory=True) together with linearly interpolated external "
+                                             "inputs (externals='linear') have no fused form: K0 / K5 carry either, not both")
         if kernel not in ("auto", "generic") or saved:
             raise _lib.UnsupportedShapeError(f"{what}: {self._first_option()} on the generic kernels K0 / K5 only (kernel 'auto' / 'generic', no saved rows); "
                                              f"got kernel={kernel!r}, saved rows={saved}")
@@ -279,6 +293,10 @@ class GenericOpts:
                                              "K0 / K5 only (kernel 'auto' / 'generic', no saved rows); this entry point holds them over a step")
         if self.tab is not None:
             builtin_method(self.tab, what)
+        if self.per_trajectory:
+            raise _lib.UnsupportedShapeError(f"{what}: per-trajectory events (per_trajectory=True) run on the generic kernels K0 / K5 only "
+                                             "(kernel 'auto' / 'generic', no saved rows); this entry point jumps the whole batch at the steps "
+                                             "of one int32[T-1] table")
         return self.method_id, self.stages
 
 
@@ -287,8 +305,14 @@ def call_generic(lib, stem: str, kind: str, args, opts: GenericOpts, *tail, x_su
     family's `c_args`, *tail).  stem: "ode_integrate", "dae_integrate", "ode_backward", "dae_backward"; kind: "f32" (tail: workspace
     pointer, its size, stream), "supported" or, for the backward stems, "workspace_bytes".  A dae_backward whose `args` is a
     psnode_dae_bwd_tf_args_f32 (`dae_backward_args`) and whose family would be "plain" takes the "tf" entry points.  The workspace of
-    ode_backward, and of dae_backward in the families "plain" and "act", is the plain query's.  Returns (status or value, the symbol)."""
+    ode_backward, and of dae_backward in the families "plain" and "act", is the plain query's; that of dae_backward in the family "pev" is
+    the "rk" query's (the same build policy and layout; the family has no query of its own).  The family "none" (`GenericOpts.__post_init__`) has no
+    entry point: its "supported" is 0, any other kind is the caller's mistake (`require_generic` refuses such a call first).
+    Returns (status or value, the symbol)."""
     fam = opts.family
+    if fam == "none":
+        assert kind == "supported", f"{stem}: per-trajectory events with interpolated externals have no entry point"
+        return 0, f"psnode_{stem}_{kind}"
     if isinstance(args, _lib.DaeBwdTfArgsF32):
         assert stem == "dae_backward" and fam != "act", f"{stem}: no entry point takes dataset rows and the acts {opts.acts} alone"
         fam = "tf" if fam == "plain" else fam
@@ -296,6 +320,15 @@ def call_generic(lib, stem: str, kind: str, args, opts: GenericOpts, *tail, x_su
         assert stem in ("ode_backward", "dae_backward"), f"{stem} has no workspace query of its own"
         if stem == "ode_backward" or fam == "act":
             fam = "plain"
+        elif fam == "pev":
+            # the _rk query with the call's acts and tableau -- a built-in method's stand-in is the one-stage tableau, the size does not
+            # depend on it: the same policy (every activation kind, the pre-activations kept), so the same fit, the same checks and the same
+            # layout as this family's build, whatever the number of sub-steps
+            tab = opts.tab.abi() if opts.tab is not None else _lib.RkTableauF32()
+            if opts.tab is None:
+                tab.stages, tab.b[0] = 1, 1.0
+            name = f"psnode_{stem}_rk_{kind}"
+            return getattr(lib, name)(ctypes.byref(args), *_act_ptrs(opts.acts), ctypes.byref(tab), *tail), name
     if fam == "plain":
         name = f"psnode_{stem}_{kind}"
         return getattr(lib, name)(ctypes.byref(args), *tail), name
@@ -580,14 +613,32 @@ def _bind_jumps(a, event_idx, jumps, dev, keep: list):
         setattr(a, f"{name[0]}j_stride_e", se)
 
 
-def _bind_events(a, t, event_t, event_idx, check_events: bool, jumps, B: int, dev, keep: list):
-    """Event prologue of the forward entry points: the caller's `event_idx` (int32[T-1], validated) or the table of `event_t`
-    (`event_table`), the jumps' shapes (`jumps` = ((name, tensor, width), ...)) and `_bind_jumps`.  Returns the table, None = no events."""
-    T = t.shape[0]
-    if event_idx is None:
-        event_idx = event_table(t, event_t, check_events)
+def has_events(t, event_t, event_idx=None) -> bool:
+    """Does a call with these arguments have an event table (the caller's, or `event_table`'s: not None)?  Only such a call carries the
+    event rule: a per-trajectory call without events is the event-less call."""
+    return event_idx is not None or (event_t is not None and t.shape[0] >= 2 and event_t.shape[1] > 0)
+
+
+def check_event_idx(event_idx, T: int, B: int, per_trajectory: bool, dev):
+    """A caller's event table reaches the kernels as a raw pointer: int32[T-1], or -- per-trajectory events -- a contiguous int32[T-1, B]
+    on the call's device (a shorter one would be read out of bounds)."""
+    if per_trajectory:
+        if event_idx.dtype != torch.int32 or tuple(event_idx.shape) != (T - 1, B) or not event_idx.is_contiguous() or event_idx.device != dev:
+            raise ValueError(f"event_idx must be a contiguous int32[T-1={T - 1}, B={B}] on {dev} (per-trajectory events), got "
+                             f"{event_idx.dtype}{list(event_idx.shape)} on {event_idx.device}")
     elif event_idx.numel() < T - 1 or event_idx.dtype != torch.int32:
         raise ValueError(f"event_idx must be int32[T-1={T - 1}], got {event_idx.dtype}[{event_idx.numel()}]")
+
+
+def _bind_events(a, t, event_t, event_idx, check_events: bool, jumps, B: int, dev, keep: list, per_trajectory: bool = False):
+    """Event prologue of the forward entry points: the caller's `event_idx` (int32[T-1], or int32[T-1, B] for per-trajectory events;
+    validated) or the table of `event_t` (`event_table`), the jumps' shapes (`jumps` = ((name, tensor, width), ...)) and `_bind_jumps`.
+    Returns the table, None = no events."""
+    T = t.shape[0]
+    if event_idx is None:
+        event_idx = event_table(t, event_t, check_events, per_trajectory=per_trajectory)
+    else:
+        check_event_idx(event_idx, T, B, per_trajectory, dev)
     if event_idx is not None:
         for name, j, width in jumps:
             _check_jump(name, j, B, width, event_idx)
@@ -595,13 +646,18 @@ def _bind_events(a, t, event_t, event_idx, check_events: bool, jumps, B: int, de
     return event_idx
 
 
-def event_table(t: torch.Tensor, event_t: Optional[torch.Tensor], check_duplicates: bool = False) -> Optional[torch.Tensor]:
+def event_table(t: torch.Tensor, event_t: Optional[torch.Tensor], check_duplicates: bool = False,
+                per_trajectory: bool = False) -> Optional[torch.Tensor]:
     """int32[T-1] device table: index of the event at each step, -1 = none.
 
     Same decision as ODE_Event.event_fn / jump_change_fn (neural_base.py:52-62): trajectory 0's clock
     against trajectory 0's event list, exact fp32 equality -- resolved by one tiny kernel instead of one
     host sync per step.  `check_duplicates` synchronises and raises where the reference would
     (two events at one time make its `.view(z0.shape)` fail).
+
+    per_trajectory=True: int32[T-1, B], row-major [k][b] -- trajectory b's clock t[k, b] against trajectory b's own list event_t[b, :],
+    the same equality, the lowest matching column; an entry that matches no clock value (NaN: the padding of a shorter list) never
+    fires; `check_duplicates` then raises for a duplicate in ANY trajectory (ODE_Event.hit_mask / jump_change_fn are the definition).
     """
     T = t.shape[0]
     if event_t is None or T < 2 or event_t.shape[1] == 0:      # an empty event list is "no events", as in the reference
@@ -611,18 +667,29 @@ def event_table(t: torch.Tensor, event_t: Optional[torch.Tensor], check_duplicat
     t_arg, event_arg = t, event_t          # the caller's objects: what the duplicate-check memo is keyed on (detach() makes new ones)
     t = _f32_dev(t, dev, "t")
     event_t = _f32_dev(event_t, dev, "event_t")
-    tab = _empty(T - 1, dtype=torch.int32, device=dev)
     dup = torch.zeros(1, dtype=torch.int32, device=dev)
     n_ev = event_t.shape[1]
     st = torch.cuda.current_stream(dev).cuda_stream
-    rc = lib.psnode_event_table_f32(T - 1, t.data_ptr(), t.stride(0), event_t.data_ptr(), event_t.stride(1), n_ev,
-                                    tab.data_ptr(), dup.data_ptr(), st)
-    _lib.check(rc, "psnode_event_table_f32")
-    if check_duplicates and not _dup_check_known(t_arg, event_arg):
+    if per_trajectory:
+        B = t.shape[1]
+        if t.dim() != 3 or event_t.dim() not in (2, 3) or event_t.shape[0] != B:
+            raise ValueError(f"per-trajectory events need t [T, B, 1] and event_t [B, nE(, 1)], got {tuple(t.shape)} and {tuple(event_t.shape)}")
+        tab = _empty((T - 1, B), dtype=torch.int32, device=dev)
+        rc = lib.psnode_event_table_pt_f32(T - 1, B, t.data_ptr(), t.stride(0), t.stride(1), event_t.data_ptr(), event_t.stride(0),
+                                           event_t.stride(1), n_ev, tab.data_ptr(), dup.data_ptr(), st)
+        _lib.check(rc, "psnode_event_table_pt_f32")
+    else:
+        tab = _empty(T - 1, dtype=torch.int32, device=dev)
+        rc = lib.psnode_event_table_f32(T - 1, t.data_ptr(), t.stride(0), event_t.data_ptr(), event_t.stride(1), n_ev,
+                                        tab.data_ptr(), dup.data_ptr(), st)
+        _lib.check(rc, "psnode_event_table_f32")
+    if check_duplicates and not _dup_check_known(t_arg, event_arg, per_trajectory):
         if int(dup.item()):
-            raise RuntimeError("two events share one time stamp: the reference's jump_change_fn cannot view "
+            raise RuntimeError("two events of one trajectory share one time stamp: jump_change_fn takes one event per trajectory and step"
+                               if per_trajectory else
+                               "two events share one time stamp: the reference's jump_change_fn cannot view "
                                "z_jump[:, mask] as z0.shape (neural_base.py:61)")
-        _dup_check_remember(t_arg, event_arg)
+        _dup_check_remember(t_arg, event_arg, per_trajectory)
     return tab
 
 
@@ -637,18 +704,20 @@ def _dup_key(t):
     return base, (t.data_ptr(), tuple(t.shape), tuple(t.stride()), base._version)
 
 
-def _dup_check_known(t, event_t) -> bool:
+def _dup_check_known(t, event_t, per_trajectory: bool = False) -> bool:
+    """(per_trajectory: the rule a pair was checked under is remembered with it -- trajectory 0 free of duplicates says nothing about the
+    other trajectories)"""
     eb, ek = _dup_key(event_t)
     tb, tk = _dup_key(t)
     hit = _DUP_OK.get(id(eb))
-    return hit is not None and hit[0]() is eb and hit[1] == ek and hit[2]() is tb and hit[3] == tk
+    return hit is not None and hit[0]() is eb and hit[1] == ek and hit[2]() is tb and hit[3] == tk and hit[4] == bool(per_trajectory)
 
 
-def _dup_check_remember(t, event_t):
+def _dup_check_remember(t, event_t, per_trajectory: bool = False):
     eb, ek = _dup_key(event_t)
     tb, tk = _dup_key(t)
     ident = id(eb)
-    _DUP_OK[ident] = (weakref.ref(eb, lambda _r, ident=ident: _DUP_OK.pop(ident, None)), ek, weakref.ref(tb), tk)
+    _DUP_OK[ident] = (weakref.ref(eb, lambda _r, ident=ident: _DUP_OK.pop(ident, None)), ek, weakref.ref(tb), tk, bool(per_trajectory))
 
 
 def _workspace_of(nbytes: int, dev):

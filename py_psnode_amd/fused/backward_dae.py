@@ -6,18 +6,19 @@ import ctypes
 import torch
 
 from .. import _lib
-from ._common import (KERNEL_ID, GenericOpts, Layers, _aligned16, _bind_jumps, _check_saved, _empty, _f32_dev, _mlp, _pad_rows, _padded_hidden, _split_grads, _view, _workspace_of, call_generic, dae_acts)
+from ._common import (KERNEL_ID, GenericOpts, Layers, _aligned16, _bind_jumps, _check_saved, _empty, _f32_dev, _mlp, _pad_rows, _padded_hidden, _split_grads, _view, _workspace_of, call_generic, check_event_idx, dae_acts)
 from .latent import latent_backward_wide, latent_wide_shape
 
 def dae_backward_supported(method, de_layers: Layers, ae_layers: Layers, x_dim, z_dim, v_dim, i_dim, act=None, kernel: str = "auto",
-                           substeps: int = 1, externals: str = "hold") -> bool:
+                           substeps: int = 1, externals: str = "hold", per_trajectory: bool = False) -> bool:
     """act: None (both MLPs ELU(1)) or (de_act, ae_act); an activation other than ELU(1) is K5's alone.  kernel="generic": does K5 take
     the shape (the question a teacher-forced call outside K7f's class asks).  method a fused.Tableau: K5's tableau build only (kernel
     "auto" / "generic"; it answers for its own LDS fit).  substeps > 1: K5's sub-step build only, under the same rules.
-    externals="linear": K5's linear-externals build only (every substeps >= 1; it answers for its own LDS fit)."""
+    externals="linear": K5's linear-externals build only (every substeps >= 1; it answers for its own LDS fit).
+    per_trajectory=True (a call WITH events): K5's per-trajectory build only (every substeps >= 1; never together with externals="linear")."""
     if de_layers[0][0].device.type != "cuda" or max(len(de_layers), len(ae_layers)) > _lib.MAX_LAYERS:
         return False
-    opts = GenericOpts.of(method, dae_acts(act), substeps, externals)
+    opts = GenericOpts.of(method, dae_acts(act), substeps, externals, bool(per_trajectory))
     if opts.family == "plain" and kernel != "generic" and latent_wide_shape(de_layers, ae_layers, x_dim, z_dim, v_dim, i_dim):
         return True                          # K3w (saving) + K9w + library GEMMs
     args = opts.dae_backward_args(rows=False)
@@ -296,7 +297,8 @@ def _dae_backward_wide_sliced(step, method, de_layers, ae_layers, t, z, v, all_i
 
 
 def dae_backward(method, de_layers: Layers, ae_layers: Layers, t, z, v, all_initial, xs, is_, grad_xs, grad_is, event_idx=None,
-                 z_jump=None, v_jump=None, kernel: str = "auto", saved=None, act=None, substeps: int = 1, x_sub=None, externals: str = "hold"):
+                 z_jump=None, v_jump=None, kernel: str = "auto", saved=None, act=None, substeps: int = 1, x_sub=None, externals: str = "hold",
+                 per_trajectory: bool = False):
     """Backward pass of `dae_integrate` (no teacher forcing): the one-launch K7f (`dae_backward_wide`) for the DAE_01 shape class at
     hidden <= 128, K9 / K8 / K9w for the latent shapes of the direct_encode models, else the generic backward kernel (K5);
     `kernel` = "auto" | "mfma" | "generic" | "wide" (K7f or an error).
@@ -305,10 +307,12 @@ def dae_backward(method, de_layers: Layers, ae_layers: Layers, t, z, v, all_init
     method: "euler" | "midpoint" | "rk4", or a fused.Tableau -- K5 only (kernel "auto" / "generic", no saved rows).
     substeps > 1: backward of `dae_integrate(..., substeps=, save_sub=True)` with the x_sub it returned -- K5 only, the same rules.
     externals="linear": backward of `dae_integrate(..., externals="linear")` -- K5's linear-externals build only, the same rules.
+    per_trajectory=True: backward of `dae_integrate(..., per_trajectory=True)`; `event_idx` is the int32 [T-1, B] table -- K5's
+    per-trajectory build only, the same rules (x_sub where substeps > 1).  Without an event table the flag means nothing.
     Returns dict(x_init, z, v, z_jump, v_jump, all_initial, de=[...], ae=[...]) of gradients."""
     T, B, xd = xs.shape
     zd, vd, idim = z.shape[-1], v.shape[-1], is_.shape[-1]
-    opts = GenericOpts.of(method, dae_acts(act), substeps, externals)
+    opts = GenericOpts.of(method, dae_acts(act), substeps, externals, bool(per_trajectory) and event_idx is not None)
     opts.require_generic("dae_backward", kernel, saved is not None)
     if opts.family != "plain":      # K5 alone (an activation other than ELU(1) asks for it by name, as it always did)
         return _dae_backward_entry(opts, de_layers, ae_layers, t, z, v, all_initial, xs, is_, grad_xs, grad_is, event_idx, z_jump, v_jump,
@@ -328,12 +332,13 @@ def dae_backward(method, de_layers: Layers, ae_layers: Layers, t, z, v, all_init
 
 def dae_backward_tf(method, de_layers: Layers, ae_layers: Layers, t, z, v, all_initial, xs, is_, grad_xs, grad_is, event_idx=None,
                     z_jump=None, v_jump=None, kernel: str = "auto", x_true=None, i_true=None, substeps: int = 1, x_sub=None,
-                    externals: str = "hold"):
+                    externals: str = "hold", per_trajectory: bool = False):
     """Backward of a teacher-forced `dae_integrate` (input_true_x / input_true_i, my_solvers.py:111-121) on the generic backward K5
     (psnode_dae_backward_tf_f32): every shape K5 takes untied.  x_true [T,B,x_dim] / i_true [T,B,i_dim]: the dataset rows the forward call
     fed the DE / the heads (None = that flag was not set; both None = `dae_backward` on K5's entry point); they get no gradient.  xs / is_:
     the forward results (an event step's recomputed head reads the running state xs[k]).  kernel: "auto" | "generic".  substeps > 1: with the
-    x_sub of the forward call (`dae_integrate(..., substeps=, save_sub=True)`).
+    x_sub of the forward call (`dae_integrate(..., substeps=, save_sub=True)`).  per_trajectory=True: `event_idx` is the int32 [T-1, B]
+    table of the forward call (K5's per-trajectory build).
     Same return value as `dae_backward`."""
     if kernel not in ("auto", "generic"):
         raise _lib.UnsupportedShapeError("dae_backward_tf: the teacher-forced backward behind this entry point is K5's (kernel 'auto' / 'generic'); "
@@ -342,7 +347,9 @@ def dae_backward_tf(method, de_layers: Layers, ae_layers: Layers, t, z, v, all_i
     for name, q, w in (("x_true", x_true, xd), ("i_true", i_true, is_.shape[-1])):
         if q is not None and tuple(q.shape) != (T, B, w):
             raise ValueError(f"{name} must be [T,B,{w}], got {tuple(q.shape)}")
-    return _dae_backward_entry(GenericOpts.of(method, (None, None), substeps, externals), de_layers, ae_layers, t, z, v, all_initial, xs, is_, grad_xs,
+    opts = GenericOpts.of(method, (None, None), substeps, externals, bool(per_trajectory) and event_idx is not None)
+    opts.require_generic("dae_backward_tf", kernel, False)
+    return _dae_backward_entry(opts, de_layers, ae_layers, t, z, v, all_initial, xs, is_, grad_xs,
                                grad_is, event_idx, z_jump, v_jump, kernel, None, x_true=x_true, i_true=i_true, x_sub=x_sub)
 
 
@@ -358,6 +365,8 @@ def _dae_backward_entry(opts, de_layers, ae_layers, t, z, v, all_initial, xs, is
                                     or x_sub.dtype != torch.float32 or x_sub.device != dev):
         raise ValueError(f"dae_backward: substeps={substeps} needs x_sub, the contiguous fp32 [{T - 1},{substeps - 1},{B},{xd}] tensor the "
                          "forward call returned with save_sub=True")
+    if opts.per_trajectory:
+        check_event_idx(event_idx, T, B, True, dev)
     keep: list = [x_sub]
     args = opts.dae_backward_args(x_true is not None or i_true is not None)
     tf = args if isinstance(args, _lib.DaeBwdTfArgsF32) else None

@@ -5,7 +5,7 @@ import ctypes
 import torch
 
 from .. import _lib
-from ._common import (KERNEL_ID, GenericOpts, Layers, _aligned16, _bind_jumps, _check_saved, _empty, _f32_dev, _mlp, _split_grads, _view, _workspace_of, call_generic)
+from ._common import (KERNEL_ID, GenericOpts, Layers, _aligned16, _bind_jumps, _check_saved, _empty, _f32_dev, _mlp, _split_grads, _view, _workspace_of, call_generic, check_event_idx)
 from .latent import latent_backward_wide, latent_wide_shape
 
 def _bwd_args(opts, de_layers, x_dim, z_dim, T, B, dev, keep, kernel="auto"):
@@ -18,14 +18,15 @@ def _bwd_args(opts, de_layers, x_dim, z_dim, T, B, dev, keep, kernel="auto"):
 
 
 def ode_backward_supported(method, de_layers: Layers, x_dim: int, z_dim: int, kernel: str = "auto", act=None, substeps: int = 1,
-                           externals: str = "hold") -> bool:
+                           externals: str = "hold", per_trajectory: bool = False) -> bool:
     """True if a fused backward kernel covers this shape: the MFMA class (3n->64->64->64->x, x<=8, z<=4) or any MLP whose
     activations and parameter gradients fit the LDS (generic backward).  act (fused.Act) other than None = ELU(1): K5 only.
     method a fused.Tableau: K5's tableau build only (kernel "auto" / "generic"; it answers for its own LDS fit).  substeps > 1: K5's
-    sub-step build only, under the same rules.  externals="linear": K5's linear-externals build only (every substeps >= 1; its own LDS fit)."""
+    sub-step build only, under the same rules.  externals="linear": K5's linear-externals build only (every substeps >= 1; its own LDS fit).
+    per_trajectory=True (a call WITH events): K5's per-trajectory build only (every substeps >= 1; never together with externals="linear")."""
     if de_layers[0][0].device.type != "cuda" or len(de_layers) > _lib.MAX_LAYERS:
         return False
-    opts = GenericOpts.of(method, (act,), substeps, externals)
+    opts = GenericOpts.of(method, (act,), substeps, externals, bool(per_trajectory))
     if opts.family == "plain" and kernel in ("auto", "mfma") and latent_wide_shape(de_layers, None, x_dim, z_dim):
         return True                          # K3w (saving) + K9w + library GEMMs
     a = _bwd_args(opts, de_layers, x_dim, z_dim, 2, 1, de_layers[0][0].device, [], kernel)
@@ -34,7 +35,7 @@ def ode_backward_supported(method, de_layers: Layers, x_dim: int, z_dim: int, ke
 
 def ode_backward(method, de_layers: Layers, t, z, all_initial, xs, grad_xs, event_idx=None, z_jump=None, need_grad_z: bool = True,
                  kernel: str = "auto", saved=None, input_true_x: bool = False, need_grad_zj: bool = True, act=None, substeps: int = 1,
-                 x_sub=None, externals: str = "hold"):
+                 x_sub=None, externals: str = "hold", per_trajectory: bool = False):
     """Backward pass of `ode_integrate` in one launch.  `saved` = what `ode_integrate(save=True)` returned next to
     xs: K4f then skips the recompute of the stage evaluations.  input_true_x: backward of a teacher-forced call (my_solvers.py:72-74) --
     `xs` must then be the DATASET x the forward call started every step from; K4f where the shape is its (hidden <= 128, x_dim <= 8) and
@@ -49,6 +50,10 @@ def ode_backward(method, de_layers: Layers, t, z, all_initial, xs, grad_xs, even
     (kernel "auto" / "generic", no saved rows; teacher forcing with ELU(1) only).
     externals="linear": backward of `ode_integrate(..., externals="linear")` -- K5's linear-externals build, the same rules; grad_z row k + 1
     also receives the right-hand share theta g of interval k's stages.
+    per_trajectory=True: backward of `ode_integrate(..., per_trajectory=True)`; `event_idx` is the int32 [T-1, B] table -- K5's
+    per-trajectory build, the rules of substeps (x_sub where substeps > 1).  grad_z_jump[b, e] receives the adjoint of trajectory b's
+    interval that event e opens (exactly 0 where it never fires), grad_z[k, b] is exactly 0 where b jumps at k.  Without an event table
+    the flag means nothing.
     Returns (grad_x0 [B,xd], grad_z [T,B,zd] | None, grad_z_jump | None, grad_all_initial [B,n], [grad W1, b1, ..., W4, b4])."""
     lib = _lib.load()
     dev = xs.device
@@ -56,8 +61,11 @@ def ode_backward(method, de_layers: Layers, t, z, all_initial, xs, grad_xs, even
     zd = z.shape[-1]
     # kernel: "auto" / "mfma" = the one-launch K4f at every hidden width <= 128 (z_dim <= 8), K8f / K9 / K9w for the latent shapes, else the
     # generic K5 ("auto" only); "wide" forces K4f
-    opts = GenericOpts.of(method, (act,), substeps, externals)
+    per_trajectory = bool(per_trajectory) and event_idx is not None
+    opts = GenericOpts.of(method, (act,), substeps, externals, per_trajectory)
     opts.require_generic("ode_backward", kernel, saved is not None, teacher_forced=input_true_x)
+    if per_trajectory:
+        check_event_idx(event_idx, T, B, True, dev)
     if substeps > 1 and T >= 2 and (x_sub is None or tuple(x_sub.shape) != (T - 1, substeps - 1, B, xd) or not x_sub.is_contiguous()
                                     or x_sub.dtype != torch.float32 or x_sub.device != dev):
         raise ValueError(f"ode_backward: substeps={substeps} needs x_sub, the contiguous fp32 [{T - 1},{substeps - 1},{B},{xd}] tensor the "

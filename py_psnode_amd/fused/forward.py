@@ -6,7 +6,7 @@ from typing import Optional
 import torch
 
 from .. import _lib
-from ._common import (KERNEL_ID, GenericOpts, Layers, Tableau, builtin_method, _aligned16, _bind_events, _check_tb, _empty, _f32_dev, _mlp, _view, _workspace_of, call_generic, dae_acts, is_linear)
+from ._common import (KERNEL_ID, GenericOpts, Layers, Tableau, builtin_method, _aligned16, _bind_events, _check_tb, _empty, _f32_dev, _mlp, _view, _workspace_of, call_generic, dae_acts, has_events, is_linear)
 
 _MFMA_CLASSES = ("MFMA integrators K1 / K2 cover `in -> H -> H -> H -> out` ELU-MLPs with H <= 128 (any x_dim <= 16 for the ODE, "
                  "x_dim <= 8 and z+v+i <= 8 for the DAE), and -- weights streamed from L2 -- the ODE up to H = 192 at any x_dim <= 16 and "
@@ -45,7 +45,7 @@ def _note_k0(lib, args, dae: bool, de_layers: Layers):
 def ode_integrate(method, de_layers: Layers, t, x, z, all_initial, event_t=None, z_jump=None,
                   input_true_x: bool = False, kernel: str = "auto", event_idx: Optional[torch.Tensor] = None,
                   check_events: bool = False, out: Optional[torch.Tensor] = None, save: bool = False, act=None, substeps: int = 1,
-                  save_sub: bool = False, externals: str = "hold"):
+                  save_sub: bool = False, externals: str = "hold", per_trajectory: bool = False):
     """Fused integrate_ODE (replaces my_solvers.py:52-80 + my_fixed_grid.py + DE_Func.forward).
 
     method: "euler" | "midpoint" | "rk4" (the 3/8 rule), or a fused.Tableau -- any explicit Runge-Kutta method of up to four stages, on
@@ -62,6 +62,12 @@ def ode_integrate(method, de_layers: Layers, t, x, z, all_initial, event_t=None,
     z[k] + theta (z[k+1] - z[k]) at theta = (j + c_s) / substeps, z[k] being the jumped row behind an event; the generic kernel K0 in its
     linear-externals build for every substeps >= 1 (kernel "auto" / "generic"; save=True is refused; save_sub then always returns a tensor).
 
+    per_trajectory=True: trajectory b jumps where ITS clock t[k, b] equals one of ITS event times event_t[b, :] (exact equality, lowest
+    matching column; NaN entries never fire) -- it is computed as the shared rule computes it in a batch of b alone.  `event_idx`, if
+    given, is then the int32 [T-1, B] table of `event_table(..., per_trajectory=True)`.  The generic kernel K0 in its per-trajectory
+    build for every substeps >= 1 (kernel "auto" / "generic"; save=True and externals="linear" are refused; save_sub then always returns a
+    tensor).  A call without events (no event_t and no event_idx, T == 1, an empty list) is the call it is without the flag.
+
     save=True (training forward, K1 shapes only -- `ode_save_hidden`): the kernel also writes what autograd would save, the hidden
     activations [T-1,S,3,B,Hp] and the stage inputs [T-1,S,B,xd]; returns (xs, (act, xstage)) for `ode_backward(..., saved=)`.
 
@@ -74,7 +80,8 @@ def ode_integrate(method, de_layers: Layers, t, x, z, all_initial, event_t=None,
     dev = x.device
     if dev.type != "cuda":
         raise ValueError("fused integrator needs tensors on a HIP device")
-    opts = GenericOpts.of(method, (act,), substeps, externals)
+    per_trajectory = bool(per_trajectory) and has_events(t, event_t, event_idx)
+    opts = GenericOpts.of(method, (act,), substeps, externals, per_trajectory)
     opts.require_generic("ode_integrate", kernel, save)
     T, B, xd = t.shape[0], x.shape[1], x.shape[2]
     if x.shape[0] < (T if input_true_x else 1):
@@ -100,7 +107,7 @@ def ode_integrate(method, de_layers: Layers, t, x, z, all_initial, event_t=None,
     keep.append(a0)
     a.all_initial = a0.data_ptr()
     with torch.cuda.device(dev):
-        _bind_events(a, t, event_t, event_idx, check_events, (("z_jump", z_jump, zd),), B, dev, keep)
+        _bind_events(a, t, event_t, event_idx, check_events, (("z_jump", z_jump, zd),), B, dev, keep, per_trajectory)
         if out is None:
             out = _empty((T, B, xd), dtype=torch.float32, device=dev)
         elif out.shape != (T, B, xd) or not out.is_contiguous() or out.dtype != torch.float32 or out.device != dev:
@@ -116,7 +123,7 @@ def ode_integrate(method, de_layers: Layers, t, x, z, all_initial, event_t=None,
                      _empty((max(T - 1, 0), opts.stages, B, xd), dtype=torch.float32, device=dev))
             if T >= 2:
                 a.save_act, a.save_xstage = saved[0].data_ptr(), saved[1].data_ptr()
-        x_sub = _empty((max(T - 1, 0), substeps - 1, B, xd), dtype=torch.float32, device=dev) if save_sub and opts.family in ("sub", "lin") else None
+        x_sub = _empty((max(T - 1, 0), substeps - 1, B, xd), dtype=torch.float32, device=dev) if save_sub and opts.family in ("sub", "lin", "pev") else None
         ws, wp, wn = _workspace_of(lib.psnode_workspace_bytes(ctypes.byref(a.de), None), dev)
         rc, entry = call_generic(lib, "ode_integrate", "f32", a, opts, wp, wn, torch.cuda.current_stream(dev).cuda_stream, x_sub=x_sub)
     _mfma_miss(rc, kernel, entry, de_layers)
@@ -144,7 +151,8 @@ def ode_save_hidden(method, de_layers: Layers, x_dim: int, z_dim: int, kernel: s
 def dae_integrate(method, de_layers: Layers, ae_layers: Layers, x_init, t, x, z, v, i, all_initial,
                   event_t=None, z_jump=None, v_jump=None, input_true_x: bool = False, input_true_i: bool = False,
                   kernel: str = "auto", event_idx: Optional[torch.Tensor] = None, check_events: bool = False, out=None,
-                  save: bool = False, act=None, substeps: int = 1, save_sub: bool = False, externals: str = "hold"):
+                  save: bool = False, act=None, substeps: int = 1, save_sub: bool = False, externals: str = "hold",
+                  per_trajectory: bool = False):
     """Fused integrate_DAE (replaces my_solvers.py:82-131 + step functions + DE_Func/AE_Func forwards).
     method: "euler" | "midpoint" | "rk4", or a fused.Tableau (generic kernel K0 only: kernel "auto" / "generic"; save=True is refused).
     act: None (both MLPs ELU(1)) or (de_act, ae_act), each a fused.Act or None = ELU(1); an activation other than ELU(1) runs on the
@@ -155,6 +163,9 @@ def dae_integrate(method, de_layers: Layers, ae_layers: Layers, x_init, t, x, z,
     externals: "hold", or "linear" -- every stage reads z | v interpolated between grid points k (the jumped rows behind an event) and k + 1
     at theta = (j + c_s) / substeps, as does the head in front of sub-step j >= 1 (theta = j / substeps); i is never interpolated.  K0's
     linear-externals build for every substeps >= 1 (kernel "auto" / "generic", no save).
+    per_trajectory=True: as `ode_integrate`, for z | v together; the event-time head i0 = g(x_k; z_jump, v_jump) replaces the carried
+    algebraic variable of the trajectories with a hit at step k only, the others keep theirs.  K0's per-trajectory build for every
+    substeps >= 1 (kernel "auto" / "generic", no save, not with externals="linear").
     `out` = (xs, is) contiguous [T,B,xd] / [T,B,id] tensors to write into (time-chunked launches).
     save=True (training forward, K2 shapes without teacher forcing -- `dae_save_hidden`): the kernel also writes what autograd would
     save (psnode_dae_args_f32::save_*); returns (xs, is, saved) with saved = (act [T-1,S,3,B,Hp], xstage [T-1,S,B,xd],
@@ -163,7 +174,8 @@ def dae_integrate(method, de_layers: Layers, ae_layers: Layers, x_init, t, x, z,
     dev = x_init.device
     if dev.type != "cuda":
         raise ValueError("fused integrator needs tensors on a HIP device")
-    opts = GenericOpts.of(method, dae_acts(act), substeps, externals)
+    per_trajectory = bool(per_trajectory) and has_events(t, event_t, event_idx)
+    opts = GenericOpts.of(method, dae_acts(act), substeps, externals, per_trajectory)
     opts.require_generic("dae_integrate", kernel, save)
     T, B = t.shape[0], t.shape[1]
     xd, zd, vd, idim = x_init.shape[-1], z.shape[-1], v.shape[-1], i.shape[-1]
@@ -200,7 +212,8 @@ def dae_integrate(method, de_layers: Layers, ae_layers: Layers, x_init, t, x, z,
     keep += [xi, a0]
     a.x_init, a.all_initial = xi.data_ptr(), a0.data_ptr()
     with torch.cuda.device(dev):
-        event_idx = _bind_events(a, t, event_t, event_idx, check_events, (("z_jump", z_jump, zd), ("v_jump", v_jump, vd)), B, dev, keep)
+        event_idx = _bind_events(a, t, event_t, event_idx, check_events, (("z_jump", z_jump, zd), ("v_jump", v_jump, vd)), B, dev, keep,
+                                 per_trajectory)
         if out is None:
             xs = _empty((T, B, xd), dtype=torch.float32, device=dev)
             is_ = _empty((T, B, idim), dtype=torch.float32, device=dev)
@@ -228,7 +241,7 @@ def dae_integrate(method, de_layers: Layers, ae_layers: Layers, x_init, t, x, z,
                 a.save_act = a.save_xstage = dummy.data_ptr()
             if n_ev:
                 a.save_ev_act, a.save_ev_i = saved[3].data_ptr(), saved[4].data_ptr()
-        x_sub = _empty((max(T - 1, 0), substeps - 1, B, xd), dtype=torch.float32, device=dev) if save_sub and opts.family in ("sub", "lin") else None
+        x_sub = _empty((max(T - 1, 0), substeps - 1, B, xd), dtype=torch.float32, device=dev) if save_sub and opts.family in ("sub", "lin", "pev") else None
         ws, wp, wn = _workspace_of(lib.psnode_workspace_bytes(ctypes.byref(a.de), ctypes.byref(a.ae)), dev)
         rc, entry = call_generic(lib, "dae_integrate", "f32", a, opts, wp, wn, torch.cuda.current_stream(dev).cuda_stream, x_sub=x_sub)
     _mfma_miss(rc, kernel, entry, de_layers)

@@ -23,6 +23,13 @@ def _event_tensors(event_fn, jump_change_fn, want_v: bool):
     return True, ev.event_t, ev.z_jump, (getattr(ev, "v_jump", None) if want_v else None)
 
 
+def per_trajectory_events(event_fn) -> bool:
+    """Is `event_fn` the bound method of an event object that has events set and applies them per trajectory (ODE_Event / DAE_Event with
+    per_trajectory=True)?  Such an object without events is the event-less call: False."""
+    ev = getattr(event_fn, "__self__", None)
+    return ev is not None and bool(getattr(ev, "per_trajectory", False)) and getattr(ev, "event_t", None) is not None
+
+
 def _needs_autograd(tensors) -> bool:
     return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
 

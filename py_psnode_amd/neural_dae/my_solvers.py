@@ -92,17 +92,20 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
             self._walk_warned = True
             warnings.warn(f"{what}: this call is not fusable (needs fp32 HIP tensors, DE_Func/AE_Func-style MLPs with one activation "
                           "of ELU / Tanh / Sigmoid / ReLU / LeakyReLU / Softplus / SiLU / GELU / Mish -- other than ELU(1) on kernel 'auto' / 'generic' only --, "
-                          "ODE_Event/DAE_Event callbacks; an ExplicitRK tableau, substeps > 1 or externals='linear' on kernel 'auto' / 'generic' only (substeps <= 1024); under autograd also a shape with a backward kernel; teacher-forced "
+                          "ODE_Event/DAE_Event callbacks -- with per_trajectory=True on kernel 'auto' / 'generic' only and not together with externals='linear' --; "
+                          "an ExplicitRK tableau, substeps > 1 or externals='linear' on kernel 'auto' / 'generic' only (substeps <= 1024); under autograd also a shape with a backward kernel; teacher-forced "
                           "training: ELU(1), dataset rows without grad) -- stepping through the Python callables instead", RuntimeWarning, stacklevel=3)
 
-    def _generic_only_ok(self, what, acts) -> bool:
+    def _generic_only_ok(self, what, acts, per_trajectory=False) -> bool:
         """An activation other than ELU(1), a Runge-Kutta tableau (ExplicitRK: `method` is a fused.Tableau), sub-steps per grid interval
-        (up to 1024) and linearly interpolated externals run on the generic kernels K0 / K5 only: kernel 'wave' / 'tile' / 'mfma' / 'wide'
+        (up to 1024), linearly interpolated externals and per-trajectory events (`per_trajectory`: the call has events and its event
+        object applies them per trajectory) run on the generic kernels K0 / K5 only: kernel 'wave' / 'tile' / 'mfma' / 'wide'
         with one of them walks under fused='auto' and raises under 'require', naming the first in the order act, tableau, sub-steps,
-        externals (fused.GenericOpts.require_generic's)."""
+        externals, events (fused.GenericOpts.require_generic's).  Per-trajectory events together with externals='linear' have no kernel."""
         generic = self.kernel in ("auto", "generic")
+        lin_pt = per_trajectory and self.externals != "hold"
         fits = generic and self.substeps <= _fused._lib.MAX_SUBSTEPS
-        if fits:
+        if fits and not lin_pt:
             return True
         limits = "(kernel 'auto' / 'generic', substeps <= %d)" % _fused._lib.MAX_SUBSTEPS
         if not generic and any(a is not None for a in acts):
@@ -114,17 +117,24 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
             text = f"with substeps={self.substeps} has no fused form: sub-steps per grid interval run on the generic kernels {limits}"
         elif not fits and self.externals != "hold":
             text = f"with externals='linear' has no fused form: interpolated external inputs run on the generic kernels {limits}"
+        elif lin_pt:
+            text = "with per-trajectory events and externals='linear' has no fused form: the generic kernels carry either, not both"
+        elif not generic and per_trajectory:
+            text = "has no form for per-trajectory events (per_trajectory=True): they run on the generic kernels (kernel 'auto' / 'generic')"
         else:
             return True
         if self.fused == "require":
             raise UnsupportedShapeError(f"{what}: kernel={self.kernel!r} {text}")
         return False
 
-    def _generic_kwargs(self) -> dict:
-        """substeps= / externals= for the fused calls, left out at 1 / "hold": those calls are then the ones they always were."""
+    def _generic_kwargs(self, per_trajectory=False) -> dict:
+        """substeps= / externals= / per_trajectory= for the fused calls, left out at 1 / "hold" / False: those calls are then the ones they
+        always were."""
         kw = dict(substeps=self.substeps) if self.substeps != 1 else {}
         if self.externals != "hold":
             kw["externals"] = self.externals
+        if per_trajectory:
+            kw["per_trajectory"] = True
         return kw
 
     def _step_func_lin(self, func, t0, dt, x0, ext_at, i0=None, all_initial=None):
@@ -163,9 +173,11 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
             raise ValueError("integrate_ODE: x_init and input_true_x exclude each other (teacher forcing starts every step from x[k])")
         if self.fused != "off":
             plan = _fused.plan_ode(x_func, x, z, all_initial, event_fn, jump_change_fn, t=t, x_init=x_init)
-            if plan is not None and not self._generic_only_ok("integrate_ODE", plan[4:]):
+            # (per-trajectory events: only a call that has events carries the rule)
+            per_traj = plan is not None and plan[1] is not None and _fused.per_trajectory_events(event_fn)
+            if plan is not None and not self._generic_only_ok("integrate_ODE", plan[4:], per_traj):
                 plan = None
-            sub = self._generic_kwargs()
+            sub = self._generic_kwargs(per_traj)
             if plan is not None:
                 layers, event_t, z_jump, needs_grad, act = plan
                 if not needs_grad:
@@ -229,9 +241,10 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
                       input_true_x=False, input_true_i=False):
         if self.fused != "off":
             plan = _fused.plan_dae(x_init, x_func, i_func, z, v, i, all_initial, event_fn, jump_change_fn, t=t)
-            if plan is not None and not self._generic_only_ok("integrate_DAE", plan[6:]):
+            per_traj = plan is not None and plan[2] is not None and _fused.per_trajectory_events(event_fn)
+            if plan is not None and not self._generic_only_ok("integrate_DAE", plan[6:], per_traj):
                 plan = None
-            sub = self._generic_kwargs()
+            sub = self._generic_kwargs(per_traj)
             if plan is not None:
                 de, ae, event_t, z_jump, v_jump, needs_grad, de_act, ae_act = plan
                 act = None if de_act is None and ae_act is None else (de_act, ae_act)
@@ -278,7 +291,11 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
             t0, t1, zk, vk = t[k], t[k + 1], z[k], v[k]
             if event_fn is not None and event_fn(t0) == True:  # noqa: E712
                 zk, vk = jump_change_fn(t0, zk, vk)
-                cur_i = i_func(xt=cur_x, zt=zk, vt=vk, all_initial=all_initial)
+                if _fused.per_trajectory_events(event_fn):      # the event-time head replaces the carried i of the hit trajectories only
+                    hit = event_fn.__self__.hit_mask(t0)
+                    cur_i = torch.where(hit.view(-1, 1), i_func(xt=cur_x, zt=zk, vt=vk, all_initial=all_initial), cur_i)
+                else:
+                    cur_i = i_func(xt=cur_x, zt=zk, vt=vk, all_initial=all_initial)
             start = x[k] if input_true_x else cur_x
             i_in = i[k] if input_true_i else cur_i
             if self.externals == "linear":      # as the ODE, for z | v; i is frozen over a sub-step's stages and never interpolated; the head in

@@ -15,27 +15,62 @@ from .my_solvers import FixedGridODESolver
 
 # ----------------------------------------------------------------------------- events
 class ODE_Event:
-    """Step jumps of the external input z at fault times (neural_base.py:43-65).
+    """Step jumps of the external input z at fault times (neural_base.py:43-65).  event_t [B, nE, 1], z_jump [B, nE, zd].
 
-    event_fn: trajectory 0's clock against trajectory 0's event list, exact float equality, decides for the
-    whole batch.  jump_change_fn: the whole batch's z is replaced by z_jump[:, e] for that one step.
+    per_trajectory=False (the default, the reference's rule -- which upstream itself marks as a stop-gap, its per-trajectory loops are
+    commented out): event_fn holds trajectory 0's clock against trajectory 0's event list, exact float equality, and decides for the
+    whole batch; jump_change_fn replaces the whole batch's z by z_jump[:, e] for that one step.  A trajectory whose fault times differ
+    from trajectory 0's is then jumped at trajectory 0's steps.
+
+    per_trajectory=True (constructor flag or plain attribute): trajectory b has an event at a step iff ITS clock t0[b] equals one of ITS
+    event times event_t[b, :], the same exact equality; the column is the lowest matching one; an entry that matches no clock value
+    never fires (NaN pads a list that is shorter than nE).  hit_mask(t0) -> bool[B] is the hit mask of the step, event_fn(t0) says
+    whether any trajectory hits, jump_change_fn returns the rows with the hit trajectories' replaced and the others' as they came.
+    Trajectory b is so computed as the default rule computes it in a batch that consists of b alone.  Two entries of one trajectory that
+    match one step are an error, as two matching entries of trajectory 0 are under the default rule.
     """
     _psnode_event = True   # lets the fused path read event_t / z_jump instead of calling back per step
+    per_trajectory = False
 
-    def __init__(self):
+    def __init__(self, per_trajectory=False):
         self.event_t = None
         self.z_jump = None
+        self.per_trajectory = bool(per_trajectory)
 
     def set_event(self, t: torch.Tensor, z: torch.Tensor):
         self.event_t = t
         self.z_jump = z
 
+    def _matches(self, t0: torch.Tensor):
+        """bool[B, nE]: entry e of trajectory b equals trajectory b's clock (per-trajectory rule)."""
+        B = self.event_t.shape[0]
+        return self.event_t.reshape(B, -1) == t0.reshape(B, 1)
+
+    def hit_mask(self, t0: torch.Tensor):
+        """bool[B]: the trajectories with an event at the step whose clocks are t0 [B, 1] -- under the default rule trajectory 0's
+        answer for all of them."""
+        B = t0.shape[0]
+        if self.event_t is None:
+            return torch.zeros(B, dtype=torch.bool, device=t0.device)
+        if not self.per_trajectory:
+            return (self.event_t[0] == t0[0]).any().expand(B)
+        return self._matches(t0).any(1)
+
     def event_fn(self, t0: torch.Tensor):
         if self.event_t is None:
             return False
+        if self.per_trajectory:
+            return bool(self._matches(t0).any())
         return bool((self.event_t[0] == t0[0]).any())
 
     def _column(self, jump: torch.Tensor, t0: torch.Tensor, like: torch.Tensor):
+        if self.per_trajectory:
+            eq = self._matches(t0)
+            if bool((eq.sum(1) > 1).any()):
+                raise RuntimeError("two events of one trajectory share one time stamp: jump_change_fn takes one event per trajectory and step")
+            col = eq.to(torch.int8).argmax(1)      # the lowest matching column (0 where there is none: masked out below)
+            rows = jump[torch.arange(jump.shape[0], device=jump.device), col]
+            return torch.where(eq.any(1).view(-1, *([1] * (like.dim() - 1))), rows.view(like.shape), like)
         hit = (self.event_t[0] == t0[0][0]).view(-1)
         out = like.clone().detach()
         out[:] = jump[:, hit].view(out.shape)      # exactly one event may match, as upstream
@@ -46,10 +81,10 @@ class ODE_Event:
 
 
 class DAE_Event(ODE_Event):
-    """z and v jump together (neural_base.py:169-196)."""
+    """z and v jump together (neural_base.py:169-196); per_trajectory as ODE_Event."""
 
-    def __init__(self):
-        super().__init__()
+    def __init__(self, per_trajectory=False):
+        super().__init__(per_trajectory)
         self.v_jump = None
 
     def set_event(self, t: torch.Tensor, z: torch.Tensor, v: torch.Tensor):
