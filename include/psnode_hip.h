@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define PSNODE_ABI_VERSION 10    /* 10 also carries the additive psnode_act_f32 / *_act_*, psnode_rk_tableau_f32 / *_rk_*, psnode_substeps_f32 / *_sub_*, *_lin_* and *_pev_* / psnode_event_table_pt_f32 entry points (end of this file), and psnode_loss_fn_f32 / psnode_masked_loss_* / psnode_loss_per_sample_f32 (next to psnode_masked_mse_f32) */
+#define PSNODE_ABI_VERSION 10    /* 10 also carries the additive psnode_act_f32 / *_act_*, psnode_rk_tableau_f32 / *_rk_*, psnode_substeps_f32 / *_sub_*, *_lin_*, *_pev_* / psnode_event_table_pt_f32 and *_ab_* entry points (end of this file), and psnode_loss_fn_f32 / psnode_masked_loss_* / psnode_loss_per_sample_f32 (next to psnode_masked_mse_f32) */
 #define PSNODE_MAX_LAYERS 8      /* Linear layers per MLP */
 #define PSNODE_MAX_WIDTH 1024    /* widest layer OUTPUT the kernels accept */
 #define PSNODE_MAX_IN_WIDTH 2048 /* widest first-layer INPUT (the latent DE of DAE_02 at --hidden 128 is 12 x 128 = 1536 wide) */
@@ -883,6 +883,33 @@ int32_t psnode_dae_backward_pev_supported(const psnode_dae_bwd_tf_args_f32* args
 int32_t psnode_dae_backward_pev_f32(const psnode_dae_bwd_tf_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
                                     const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, void* workspace, size_t workspace_bytes,
                                     void* stream);
+
+/* ---- Two-step Adams-Bashforth on the generic kernels (additive to ABI 10; DESIGN.md "Adams-Bashforth 2 on K0 / K5").
+ * Step k, per trajectory, with h_k = t[k+1] - t[k] and f_k the DE at the inputs Euler's single stage reads (state x_k; row k of z | v or the
+ * jumped rows; in a DAE the carried head or the event-time head):
+ *     x_{k+1} = x_k + c0 f_k + c1 f_{k-1};   restart (k = 0, an event of the trajectory at step k, h_{k-1} == 0): c0 = h_k, c1 = 0;
+ *     otherwise rho = h_k / h_{k-1}, c0 = h_k (1 + rho / 2), c1 = -h_k (rho / 2).
+ * Outputs, the heads at the grid points and at an event, and the gradients' destinations are Euler's.  A backward call feeds the DE's VJP of
+ * step k the cotangent c0_k g_{k+1} + c1_{k+1} g_{k+2} (g: the total adjoint of a state); no atomics, bitwise repeatable; the clock gets
+ * no gradient.  One DE evaluation per step, no sub-steps, no interpolation, no tableau: the args' `method` is not read.
+ * event_idx may be NULL (no events); otherwise per_trajectory != 0 says that it is the int32 [T-1, B] table of psnode_event_table_pt_f32
+ * (the rule of the _pev family), 0 that it is the shared int32 [T-1] of psnode_event_table_f32.
+ * Rules: a NULL act is ELU(1); `kernel` must be PSNODE_KERNEL_AUTO or _GENERIC, the save_* / saved_* pointers NULL and no teacher-forcing
+ * flag set -- every teacher-forced step starts from a dataset row, a multistep history does not exist -- (PSNODE_ERR_UNSUPPORTED); the
+ * _supported queries answer for the LDS fit, which is the _pev (= _sub) build's.  Every check returns its status before anything is
+ * launched.  Workspaces: those of the _rk entry points with a one-stage tableau, as for the _pev family; no query of its own. */
+int32_t psnode_ode_integrate_ab_supported(const psnode_ode_args_f32* args, const psnode_act_f32* de_act);
+int32_t psnode_ode_integrate_ab_f32(const psnode_ode_args_f32* args, const psnode_act_f32* de_act, int32_t per_trajectory, void* workspace,
+                                    size_t workspace_bytes, void* stream);
+int32_t psnode_dae_integrate_ab_supported(const psnode_dae_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act);
+int32_t psnode_dae_integrate_ab_f32(const psnode_dae_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                    int32_t per_trajectory, void* workspace, size_t workspace_bytes, void* stream);
+int32_t psnode_ode_backward_ab_supported(const psnode_ode_bwd_args_f32* args, const psnode_act_f32* de_act);
+int32_t psnode_ode_backward_ab_f32(const psnode_ode_bwd_args_f32* args, const psnode_act_f32* de_act, int32_t per_trajectory, void* workspace,
+                                   size_t workspace_bytes, void* stream);
+int32_t psnode_dae_backward_ab_supported(const psnode_dae_bwd_tf_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act);
+int32_t psnode_dae_backward_ab_f32(const psnode_dae_bwd_tf_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                   int32_t per_trajectory, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -39,6 +39,8 @@ ABI_VERSION = 10         # == PSNODE_ABI_VERSION of include/psnode_hip.h (2: rou
                          #     linearly inside every grid interval on K0 / K5;
                          #     additive, same version: psnode_event_table_pt_f32 and the psnode_{ode,dae}_{integrate,backward}_pev_* entry
                          #     points -- per-trajectory events (an event table [T-1, B]) on K0 / K5;
+                         #     additive, same version: the psnode_{ode,dae}_{integrate,backward}_ab_* entry points -- two-step
+                         #     Adams-Bashforth on K0 / K5;
                          #     additive, same version: psnode_loss_fn_f32 and psnode_masked_loss_* / psnode_loss_per_sample_f32 -- L1, SmoothL1 and
                          #     Huber on K6, and the per-sample evaluation table of all four kinds)
 LIB_NAME = "libpsnode_hip.so"
@@ -81,6 +83,9 @@ EXPORTS = (
     "psnode_ode_integrate_pev_supported", "psnode_ode_integrate_pev_f32", "psnode_dae_integrate_pev_supported", "psnode_dae_integrate_pev_f32",
     "psnode_ode_backward_pev_supported", "psnode_ode_backward_pev_f32",
     "psnode_dae_backward_pev_supported", "psnode_dae_backward_pev_f32",
+    "psnode_ode_integrate_ab_supported", "psnode_ode_integrate_ab_f32", "psnode_dae_integrate_ab_supported", "psnode_dae_integrate_ab_f32",
+    "psnode_ode_backward_ab_supported", "psnode_ode_backward_ab_f32",
+    "psnode_dae_backward_ab_supported", "psnode_dae_backward_ab_f32",
 )
 
 
@@ -356,6 +361,11 @@ def load():
             q.restype, q.argtypes = c_int32, [ctypes.POINTER(args_t)] + [act_p] * n_act + [rk_p, sub_p]
             f = getattr(lib, f"psnode_{name}_{fam}_f32")
             f.restype, f.argtypes = c_int32, [ctypes.POINTER(args_t)] + [act_p] * n_act + [rk_p, sub_p, c_void_p, c_size_t, c_void_p]
+        # (the _ab entry points: no tableau, no sub-steps; the call takes per_trajectory -- is event_idx the [T-1, B] table? -- behind the acts)
+        q = getattr(lib, f"psnode_{name}_ab_supported")
+        q.restype, q.argtypes = c_int32, [ctypes.POINTER(args_t)] + [act_p] * n_act
+        f = getattr(lib, f"psnode_{name}_ab_f32")
+        f.restype, f.argtypes = c_int32, [ctypes.POINTER(args_t)] + [act_p] * n_act + [c_int32, c_void_p, c_size_t, c_void_p]
     for fam in ("sub", "lin"):
         w = getattr(lib, f"psnode_dae_backward_{fam}_workspace_bytes")
         w.restype, w.argtypes = c_size_t, [ctypes.POINTER(DaeBwdTfArgsF32), act_p, act_p, rk_p, sub_p]

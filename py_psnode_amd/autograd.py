@@ -46,6 +46,8 @@ def latent_wide_training_fits(method, de, ae, hidden, T, B, dev) -> bool:
 def _generic_only_training(opts, kernel, teacher_forced, T=2) -> bool:
     """The gate of a training call that carries an option of the generic kernels (fused.GenericOpts.family other than "plain"): K0 + K5
     alone, so kernel "auto" / "generic"; teacher forcing with ELU(1) only and, for the DAE, on a grid of T >= 2.  K5 then answers for its fit."""
+    if opts.ab and teacher_forced:      # (Adams-Bashforth 2 has no teacher-forced form on any path: the solver raises before it asks)
+        return False
     return kernel in ("auto", "generic") and not (teacher_forced and (T < 2 or any(a is not None for a in opts.acts)))
 
 
@@ -322,6 +324,17 @@ class _FusedOdePev(_FusedOdeSub):
     forward = _ode_sub_forward("hold", True)
 
 
+class _FusedOdeAb(_FusedOdeSub):
+    """integrate_ODE with the AB2 solver (method "ab2"), no events or the shared event rule: _FusedOdeSub on the Adams-Bashforth builds of
+    K0 / K5 -- one DE evaluation per step forward, one VJP per step backward; x_sub is empty."""
+    forward = _ode_sub_forward("hold")
+
+
+class _FusedOdeAbPev(_FusedOdeSub):
+    """... with per-trajectory events: event_idx is the [T-1, B] table, the restart is taken per trajectory."""
+    forward = _ode_sub_forward("hold", True)
+
+
 def fused_ode_integrate(method, kernel, layers, t, x, z, all_initial, event_t=None, z_jump=None, check_events=False, input_true_x=False,
                         x_init=None, act=None, substeps=1, externals="hold", per_trajectory=False):
     """Differentiable fused integrate_ODE: gradients flow to x[0], z, all_initial, z_jump and the MLP.  input_true_x (teacher forcing,
@@ -335,6 +348,10 @@ def fused_ode_integrate(method, kernel, layers, t, x, z, all_initial, event_t=No
         z_jump = None
     params = [p for wb in layers for p in wb]
     x0 = x.detach() if input_true_x else (x[0] if x_init is None else x_init)     # (x_init: integrate_ODE's extension -- no SelectBackward)
+    if fused.is_ab(method):
+        pev = bool(per_trajectory) and event_idx is not None
+        fused.GenericOpts.of(method, (act,), substeps, externals, pev).require_generic("fused_ode_integrate", kernel, False, bool(input_true_x))
+        return (_FusedOdeAbPev if pev else _FusedOdeAb).apply(method, kernel, act, substeps, False, event_idx, t, x0, z, all_initial, z_jump, *params)
     if per_trajectory and event_idx is not None:
         fused.GenericOpts.of(method, (act,), substeps, externals, True).require_generic("fused_ode_integrate", kernel, False)
         return _FusedOdePev.apply(method, kernel, act, substeps, bool(input_true_x), event_idx, t, x0, z, all_initial, z_jump, *params)
@@ -461,6 +478,17 @@ class _FusedDaePev(_FusedDaeSub):
     forward = _dae_sub_forward("hold", True)
 
 
+class _FusedDaeAb(_FusedDaeSub):
+    """integrate_DAE with the AB2 solver (method "ab2"), no events or the shared event rule: _FusedDaeSub on the Adams-Bashforth builds of
+    K0 / K5."""
+    forward = _dae_sub_forward("hold")
+
+
+class _FusedDaeAbPev(_FusedDaeSub):
+    """... with per-trajectory events: event_idx is the [T-1, B] table, the restart is taken per trajectory."""
+    forward = _dae_sub_forward("hold", True)
+
+
 def fused_dae_integrate(method, kernel, de_layers, ae_layers, x_init, t, z, v, i, all_initial, event_t=None, z_jump=None, v_jump=None,
                         check_events=False, x=None, input_true_x=False, input_true_i=False, act=None, substeps=1, externals="hold",
                         per_trajectory=False):
@@ -477,6 +505,12 @@ def fused_dae_integrate(method, kernel, de_layers, ae_layers, x_init, t, z, v, i
         v_jump = v_jump if (v_jump is not None and v_jump.shape[-1] > 0) else None
     params = [p for wb in list(de_layers) + list(ae_layers) for p in wb]
     pev = bool(per_trajectory) and event_idx is not None
+    if fused.is_ab(method):
+        fused.GenericOpts.of(method, fused.dae_acts(act), substeps, externals, pev).require_generic(
+            "fused_dae_integrate", kernel, False, bool(input_true_x or input_true_i))
+        return (_FusedDaeAbPev if pev else _FusedDaeAb).apply(method, kernel, act, substeps, False, False, event_idx, len(de_layers), t, x_init,
+                                                             x_init.new_zeros((1, t.shape[1], 0)), z, v, i.detach(), all_initial, z_jump, v_jump,
+                                                             *params)
     if pev:
         fused.GenericOpts.of(method, fused.dae_acts(act), substeps, externals, True).require_generic("fused_dae_integrate", kernel, False)
     if pev or substeps != 1 or fused.is_linear(externals):

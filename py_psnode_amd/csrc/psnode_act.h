@@ -288,5 +288,8 @@ hipError_t launch_generic_lin(const IntegrateDev& a, bool dae, const ActPair& ac
 // psnode_generic_pev.hip: the sub-step build (sub.n >= 1) with per-trajectory events: a.ev is the [T-1, B] table and must not be null
 hipError_t launch_generic_pev(const IntegrateDev& a, bool dae, const ActPair& act, const psnode_rk_tableau_f32& rk, const SubDev& sub,
                               hipStream_t stream);
+// psnode_generic_ab.hip: two-step Adams-Bashforth on the per-trajectory build's policy; rk is the one-stage tableau, a.ev may be null
+hipError_t launch_generic_ab(const IntegrateDev& a, bool dae, const ActPair& act, const psnode_rk_tableau_f32& rk, const AbDev& ab,
+                             hipStream_t stream);
 
 }  // namespace psnode

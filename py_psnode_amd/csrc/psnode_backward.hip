@@ -89,6 +89,7 @@ GenericBwdCall generic_bwd_call(const psnode_dae_bwd_args_f32& a) {
 }
 // act: the activations of a non-ELU(1) call, or nullptr
 int generic_backward(const GenericBwdCall& c, const ActPair* act, void* workspace, void* stream) {
+    if (c.rk && c.ab) return generic_backward_launch<BuildAb>(c, act, static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
     if (c.rk && c.pev) return generic_backward_launch<BuildPev>(c, act, static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
     if (c.rk && c.lin) return generic_backward_launch<BuildLin>(c, act, static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
     if (c.rk && c.substeps > 1) return generic_backward_launch<BuildSub>(c, act, static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
@@ -208,7 +209,7 @@ extern "C" int32_t psnode_dae_backward_f32(const psnode_dae_bwd_args_f32* a, voi
     return generic_backward(generic_bwd_call(*a), nullptr, workspace, stream);
 }
 
-// ---- The K5 entry-point families psnode_dae_backward_tf_* and psnode_{ode,dae}_backward_{act,rk,sub,lin,pev}_*: one checked call path
+// ---- The K5 entry-point families psnode_dae_backward_tf_* and psnode_{ode,dae}_backward_{act,rk,sub,lin,pev,ab}_*: one checked call path
 // (k5_backward), one query (k5_supported).  Order of checks per family, which is the order of the statuses of a call that is wrong in
 // several ways:
 //
@@ -221,12 +222,13 @@ extern "C" int32_t psnode_dae_backward_f32(const psnode_dae_bwd_args_f32* a, voi
 //          T >= 2 | workspace
 //   _pev   as _lin; event_idx -- here the [T-1, B] table -- is one of the pointers (NULL: PSNODE_ERR_NULL, event-less calls take the
 //          other families)
+//   _ab    act pair | NULL args | T, B | route (and no teacher-forcing flag) | pointers (event_idx may be NULL) | workspace   (`method` is not read)
 //   T, B: a DAE call with flags needs T >= 2.  Route (k5_route_ok): kernel AUTO / GENERIC, no saved_* rows, flags within the struct's and
 //   only next to an ELU(1) pair, the recipe dims and the LDS fit of the family's build.  Pointers: the teacher-forcing rows among them.
 //   The DAE's _act family takes psnode_dae_bwd_args_f32, the others the _tf struct: its _sub with substeps == 1 and no tableau goes to _tf
 //   (ELU(1) pair) or refuses flags (PSNODE_ERR_UNSUPPORTED, before the method is looked at) and goes to _act with the base args.
 namespace {
-enum K5Family { kFamTf, kFamAct, kFamRk, kFamSub, kFamLin, kFamPev };
+enum K5Family { kFamTf, kFamAct, kFamRk, kFamSub, kFamLin, kFamPev, kFamAb };
 constexpr uint32_t kTfFlags = PSNODE_FLAG_INPUT_TRUE_X | PSNODE_FLAG_INPUT_TRUE_I;
 
 // the difference between the three args structs: the base call, the flags and the ones the struct knows, the AE, the plain entry points
@@ -272,6 +274,7 @@ bool k5_route_ok(K5Family fam, const Args& a, const ActPair& p, bool elu1, bool 
     const uint32_t flags = tf_flags(a);
     if (b.kernel != PSNODE_KERNEL_AUTO && b.kernel != PSNODE_KERNEL_GENERIC) return false;
     if ((flags & ~tf_mask(a)) || (flags && !elu1)) return false;      // (teacher forcing: ELU(1) only)
+    if (fam == kFamAb && flags) return false;                         // (a multistep history has no teacher-forced form)
     if (saved_rows(b, fam != kFamAct ? kSavedAll : query ? kSavedAct : kSavedActCall)) return false;
     // the fit of the build: _tf runs the ELU(1) build, _act the act or the pre build, the others keep the pre-activations for every kind
     const bool pre = fam == kFamAct ? act_pair_keeps_u(p) : fam != kFamTf;
@@ -287,7 +290,7 @@ int k5_substeps(K5Family& fam, const psnode_rk_tableau_f32* tab, const psnode_su
 
 template <class Args>
 int k5_backward(K5Family fam, const Args* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act, const psnode_rk_tableau_f32* tab,
-                const psnode_substeps_f32* sub, void* workspace, size_t workspace_bytes, void* stream) {
+                const psnode_substeps_f32* sub, void* workspace, size_t workspace_bytes, void* stream, int ev_pt = 0) {
     constexpr bool tf_struct = std::is_same<Args, psnode_dae_bwd_tf_args_f32>::value;
     ActPair p;
     psnode_rk_tableau_f32 t;
@@ -307,7 +310,7 @@ int k5_backward(K5Family fam, const Args* a, const psnode_act_f32* de_act, const
     if (rc) return rc;
     if (!a) return PSNODE_ERR_NULL;
     const auto& b = base(*a);
-    rc = fam <= kFamAct ? (method_ok(&b) ? PSNODE_OK : PSNODE_ERR_METHOD) : sub_tableau(tab, b.method, t);
+    rc = fam <= kFamAct ? (method_ok(&b) ? PSNODE_OK : PSNODE_ERR_METHOD) : sub_tableau(tab, fam == kFamAb ? (int)PSNODE_EULER : b.method, t);
     if (rc) return rc;
     if (b.T < 1 || b.B < 1 || (tf_struct && tf_flags(*a) && b.T < 2)) return PSNODE_ERR_DIMS;
     if (!k5_route_ok(fam, *a, p, elu1, false)) return PSNODE_ERR_UNSUPPORTED;
@@ -316,7 +319,7 @@ int k5_backward(K5Family fam, const Args* a, const psnode_act_f32* de_act, const
     if (!workspace_ok(workspace, workspace_bytes, generic_bwd_workspace_floats(&b.de, ae_of(b), b.B) * sizeof(float))) return PSNODE_ERR_WORKSPACE;
     GenericBwdCall c = generic_bwd_call(*a);
     if (fam >= kFamRk) c.rk = &t;
-    if (fam >= kFamSub) { c.substeps = nsub; c.x_sub = sub ? sub->x_sub : nullptr; c.lin = fam == kFamLin; c.pev = fam == kFamPev; }
+    if (fam >= kFamSub) { c.substeps = nsub; c.x_sub = sub ? sub->x_sub : nullptr; c.lin = fam == kFamLin; c.pev = fam == kFamPev; c.ab = fam == kFamAb; c.ab_pt = ev_pt != 0; }
     return generic_backward(c, fam == kFamTf ? nullptr : &p, workspace, stream);
 }
 
@@ -332,7 +335,7 @@ int k5_supported(K5Family fam, const Args* a, const psnode_act_f32* de_act, cons
         if (fam == kFamAct) return a->flags == 0 && k5_supported(kFamAct, &a->base, de_act, ae_act, nullptr, nullptr);
     }
     const auto& b = base(*a);
-    if (fam <= kFamAct ? !method_ok(&b) : (fam == kFamRk && !tab) || sub_tableau(tab, b.method, t)) return 0;
+    if (fam <= kFamAct ? !method_ok(&b) : (fam == kFamRk && !tab) || sub_tableau(tab, fam == kFamAb ? (int)PSNODE_EULER : b.method, t)) return 0;
     return k5_route_ok(fam, *a, p, elu1, true);
 }
 
@@ -466,4 +469,21 @@ extern "C" int32_t psnode_dae_backward_pev_f32(const psnode_dae_bwd_tf_args_f32*
                                                const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, void* workspace,
                                                size_t workspace_bytes, void* stream) {
     return k5_backward(kFamPev, a, de_act, ae_act, tab, sub, workspace, workspace_bytes, stream);
+}
+
+// (two-step Adams-Bashforth: per_trajectory says whether a non-NULL event_idx is the [T-1, B] table or the shared [T-1])
+extern "C" int32_t psnode_ode_backward_ab_supported(const psnode_ode_bwd_args_f32* a, const psnode_act_f32* de_act) {
+    return k5_supported(kFamAb, a, de_act, nullptr, nullptr, nullptr);
+}
+extern "C" int32_t psnode_ode_backward_ab_f32(const psnode_ode_bwd_args_f32* a, const psnode_act_f32* de_act, int32_t per_trajectory,
+                                              void* workspace, size_t workspace_bytes, void* stream) {
+    return k5_backward(kFamAb, a, de_act, nullptr, nullptr, nullptr, workspace, workspace_bytes, stream, per_trajectory);
+}
+extern "C" int32_t psnode_dae_backward_ab_supported(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act,
+                                                    const psnode_act_f32* ae_act) {
+    return k5_supported(kFamAb, a, de_act, ae_act, nullptr, nullptr);
+}
+extern "C" int32_t psnode_dae_backward_ab_f32(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                              int32_t per_trajectory, void* workspace, size_t workspace_bytes, void* stream) {
+    return k5_backward(kFamAb, a, de_act, ae_act, nullptr, nullptr, workspace, workspace_bytes, stream, per_trajectory);
 }

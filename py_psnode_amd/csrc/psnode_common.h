@@ -62,6 +62,17 @@ struct SubDev {
     int n;
     float* x_sub;
 };
+// What the Adams-Bashforth builds of K0 / K5 take in SubDev's place (the bodies read it under the same name): one sub-step, no x_sub, and
+// the shape of the event table -- ev_pt != 0: int32 [T-1, B], every trajectory its own column; 0: the shared int32 [T-1], which every
+// column reads through a column stride of 0.  The table may be null (no events).
+struct AbDev {
+    int n;
+    float* x_sub;
+    int ev_pt;
+};
+// (the bodies ask through an overload: a discarded `if constexpr` arm of a non-dependent SubDev is still type-checked)
+__host__ __device__ inline int ev_table_pt(const SubDev&) { return 0; }
+__host__ __device__ inline int ev_table_pt(const AbDev& s) { return s.ev_pt; }
 
 // ELU(alpha=1) with the negative branch at expm1 quality: ATen's CPU kernel (what the reference runs) returns
 // expm1(x) for x <= 0 -- checked bitwise in the build container ("ELU").
@@ -327,6 +338,8 @@ struct GenericBwdCall {
     const float* x_sub;        // [T-1, substeps-1, B, xd]
     bool lin;                  // generic_backward_launch<BuildLin> (with rk; substeps >= 1): z | v interpolated linearly inside every grid interval
     bool pev;                  // generic_backward_launch<BuildPev> (with rk; substeps >= 1; not with lin): `ev` is the [T-1, B] table of per-trajectory events
+    bool ab;                   // generic_backward_launch<BuildAb> (with a one-stage rk; substeps 1): two-step Adams-Bashforth; `ev` is null, the shared
+    bool ab_pt;                //   [T-1] table, or -- ab_pt -- the [T-1, B] table
 };
 struct ActPair;     // psnode_act.h: the DE's and the AE's activation of a non-ELU(1) call
 size_t generic_bwd_workspace_floats(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, long long B);
@@ -338,7 +351,7 @@ int generic_bwd_fits(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, int xd,
 // every activation kind -- `act` is required, ELU(1) runs as ELU with alpha = 1 -- and c.rk in place of c.method; it keeps the
 // pre-activations like the pre build), BuildSub (the tableau build with c.substeps sub-steps per grid interval, read from c.x_sub), BuildLin
 // (the sub-step build, any c.substeps >= 1, with linearly interpolated externals: c.lin), BuildPev (the sub-step build, any c.substeps >= 1,
-// with per-trajectory events: c.pev, c.ev not null).
+// with per-trajectory events: c.pev, c.ev not null), BuildAb (BuildPev's policy as two-step Adams-Bashforth: c.ab, c.ab_pt).
 // psnode_backward.hip: generic_backward picks among them.
 template <class B>
 int generic_backward_launch(const GenericBwdCall& c, const ActPair* act, float* workspace, hipStream_t stream);

@@ -1,6 +1,7 @@
-// The body of K0's kernel (psnode_generic_impl.h), as text: each of the seven objects writes its own __global__ -- generic_kernel(a),
+// The body of K0's kernel (psnode_generic_impl.h), as text: each of the eight objects writes its own __global__ -- generic_kernel(a),
 // generic_act_kernel(a, act), generic_pre_act_kernel(a, act), generic_rk_kernel(a, act, rk), generic_sub_kernel(a, act, rk, sub),
-// generic_lin_kernel(a, act, rk, sub), generic_pev_kernel(a, act, rk, sub) -- and includes this file between its braces.
+// generic_lin_kernel(a, act, rk, sub), generic_pev_kernel(a, act, rk, sub), generic_ab_kernel(a, act, rk, sub: an AbDev) -- and includes
+// this file between its braces.
 // Template parameters in scope: DAE, MODE, ML, QM.  Names in scope: a, act (ActPair; NoActPair in the ELU(1) object), rk (read under
 // Bd::rk only) and sub (SubDev, read under Bd::sub only); the objects without one declare an unread one.  The build policy Bd decides the
 // rest with `if constexpr`.
@@ -142,7 +143,17 @@
     // call of this build without a table.
     static_assert(NT % TB == 0 && TB <= 64 && 64 % TB == 0, "a thread owns one trajectory column, and every wave holds all of them");
     int evn_v = (a.ev && a.T > 1) ? __builtin_nontemporal_load(evp) : -1;
-    if constexpr (Bd::pev) evn_v = a.T > 1 ? evp[gb(tid % TB)] : -1;
+    if constexpr (Bd::pev && !Bd::ab) evn_v = a.T > 1 ? evp[gb(tid % TB)] : -1;
+    // Adams-Bashforth 2 (Bd::ab; one DE stage per step, one sub-step): x_{k+1} = x_k + c0 f_k + c1 f_{k-1} with per-column c0 / c1 from this
+    // step's h, the previous one's (hp, a register of the threads < TB that hold the clocks) and the restart bit (k = 0, an event of the
+    // column, hp == 0).  c0 takes h's place in dts; c1 and the previous slope live in kbuf's slots 1 and 0, which a one-stage build never
+    // writes.  The event table is read through strides: [T - 1][B], or the shared [T - 1] with a column stride of 0; it may be null.
+    [[maybe_unused]] long long ev_sk = 1, ev_sb = 0;
+    [[maybe_unused]] float hp = 0.0f;
+    if constexpr (Bd::ab) {
+        if (ev_table_pt(sub)) { ev_sk = a.B; ev_sb = 1; }
+        evn_v = (a.ev && a.T > 1) ? evp[gb(tid % TB) * ev_sb] : -1;
+    }
 
     float pz[PF];
     // Linear externals (Bd::lin): stage s of sub-step j reads z | v at theta = (j + c_s) / nsub between the interval's left rows (wl) and the
@@ -163,7 +174,16 @@
         if constexpr (Bd::pev) any_ev = __builtin_amdgcn_ballot_w64(ev >= 0) != 0;
         if (k >= 0) {
             // ---- this step's inputs (zero-order hold: the left grid point feeds every stage)
-            if constexpr (Bd::sub) { if (tid < TB) dts[tid] = (tn - tc) / (float)nsub; }
+            if constexpr (Bd::ab) {
+                if (tid < TB) {      // (a thread < TB owns column tid: `ev` is that column's)
+                    const float h = tn - tc;
+                    const bool restart = k == 0 || ev >= 0 || hp == 0.0f;
+                    const float half_rho = (h / hp) / 2.0f;
+                    dts[tid] = restart ? h : h * (1.0f + half_rho);
+                    kbuf[nx + tid] = restart ? 0.0f : -(h * half_rho);
+                    hp = h;
+                }
+            } else if constexpr (Bd::sub) { if (tid < TB) dts[tid] = (tn - tc) / (float)nsub; }
             else { if (tid < TB) dts[tid] = tn - tc; }
             for (int idx = tid; idx < nzv * TB; idx += NT) {
                 const int r = idx / TB, c = idx % TB;
@@ -193,7 +213,8 @@
             const long long k1 = k + 1, k2 = k + 2 < a.T ? k + 2 : a.T - 1;
             if (tid < TB) { tc = tn; tn = a.t.p[k2 * a.t.st + gb(tid) * a.t.sb]; }
             evn_v = (a.ev && k1 + 1 < a.T) ? evp[k1] : -1;
-            if constexpr (Bd::pev) evn_v = k1 + 1 < a.T ? evp[k1 * a.B + gb(tid % TB)] : -1;
+            if constexpr (Bd::pev && !Bd::ab) evn_v = k1 + 1 < a.T ? evp[k1 * a.B + gb(tid % TB)] : -1;
+            if constexpr (Bd::ab) evn_v = (a.ev && k1 + 1 < a.T) ? evp[k1 * ev_sk + gb(tid % TB) * ev_sb] : -1;
 #pragma unroll
             for (int j = 0; j < PF; ++j) {
                 const int idx = tid + NT * j;
@@ -303,6 +324,11 @@
                 if (c2 != 0.0f) acc += c2 * (s_ == 2 ? ks : kbuf[2 * nx + idx]);
                 if (c3 != 0.0f) acc += c3 * ks;
                 v = x0 + h * acc;
+                if constexpr (Bd::ab) {      // h is this column's c0 and acc the slope (b = {1}); c1 is 0 on a restart step, where slot 0 may be unwritten
+                    const float c1_ = kbuf[nx + c];
+                    if (c1_ != 0.0f) v = v + c1_ * kbuf[idx];
+                    kbuf[idx] = ks;          // f_k for step k + 1: written and read by this thread alone
+                }
                 } else {
                 if (a.method == PSNODE_EULER) {
                     v = x0 + h * ks;

@@ -1,4 +1,5 @@
-// The body of K5's kernel (psnode_generic_bwd_impl.h), as text: each of the seven objects writes its own __global__ --
+// The body of K5's kernel (psnode_generic_bwd_impl.h), as text: each of the eight objects (the eighth: generic_backward_ab_kernel(a, act,
+// rk, sub: an AbDev)) writes its own __global__ --
 // generic_backward_kernel(a), generic_backward_act_kernel(a, act), generic_backward_pre_act_kernel(a, act),
 // generic_backward_rk_kernel(a, act, rk), generic_backward_sub_kernel(a, act, rk, sub), generic_backward_lin_kernel(a, act, rk, sub),
 // generic_backward_pev_kernel(a, act, rk, sub) -- and includes this file between its braces.
@@ -177,20 +178,53 @@
         }
         if (tid < TB) la_t = a.t.p[kk * a.t.st + gb(tid) * a.t.sb];
     };
-    if (a.T >= 2) {
+    // (the Adams-Bashforth build pins the grid length in scalar registers, as K0's sub-step builds do: left to the compiler the sweep's loop
+    //  guard becomes a vector compare, and what it then parks in AGPRs in front of the loop counts as stored under partial EXEC)
+    [[maybe_unused]] long long Tu = 0;
+    if constexpr (Bd::ab) {
+        const unsigned long long u = (unsigned long long)a.T;
+        Tu = (long long)(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(u >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)u));
+    }
+    if ((Bd::ab ? Tu : a.T) >= 2) {
         if (tid < TB) la_tn = a.t.p[(a.T - 1) * a.t.st + gb(tid) * a.t.sb];
         look_ahead(a.T - 2);
     }
-    for (long long k = a.T - 2; k >= 0; --k) {
+    // Adams-Bashforth 2 (Bd::ab; one stage, one sub-step): the DE's VJP of step k takes phi_k = c0_k g_{k+1} + c1_{k+1} g_{k+2}.  gxc is
+    // g_{k+1}; g_{k+2} is kept in gks' slot 1 and the per-column c1_{k+1} in its slot 2 (a one-stage build uses slot 0 alone); c0_k takes h's
+    // place in dts.  The threads < TB, which hold the clocks, keep what the coefficients need beyond t[k], t[k+1]: t[k-1] (la_tm, requested
+    // one step early like the other look-ahead rows), h_{k+1} (h_n) and step k + 1's event index (ev_n).  K0's expressions, so K0's values.
+    // The event table is read through strides: [T - 1][B], or the shared [T - 1] with a column stride of 0; it may be null.
+    [[maybe_unused]] long long ev_sk = 1, ev_sb = 0;
+    [[maybe_unused]] float la_tm = 0.0f, h_n = 0.0f;
+    [[maybe_unused]] int ev_n = -1;
+    if constexpr (Bd::ab) {
+        if (ev_table_pt(sub)) { ev_sk = a.B; ev_sb = 1; }
+        la_tm = a.t.p[(a.T >= 3 ? a.T - 3 : 0) * a.t.st + gb(tid % TB) * a.t.sb];      // (every lane, no branch: see the top of the step; read for k >= 1 only)
+    }
+    for (long long k = (Bd::ab ? Tu : a.T) - 2; k >= 0; --k) {
         // ev: the event index of this step -- launch-uniform, or (Bd::pev: a [T - 1][B] table, which the host requires) that of this
         // thread's column: every TILE_LOOP and look-ahead item of a thread lies in column tid % TB.  any_ev: some column of the workgroup
         // has a hit (workgroup-uniform: each wave holds every column) -- what decides whether the event-time head is evaluated at all.
         // (the constant conditions on Bd::pev keep the statements of the other builds where they were: their code does not change)
         static_assert(NT % TB == 0 && 64 % TB == 0, "a thread owns one trajectory column, and every wave holds all of them");
-        const int ev = Bd::pev ? a.ev[k * a.B + gb(tid % TB)] : (a.ev ? a.ev[k] : -1);
+        const int ev = Bd::ab ? (a.ev ? a.ev[k * ev_sk + gb(tid % TB) * ev_sb] : -1)
+                              : (Bd::pev ? a.ev[k * a.B + gb(tid % TB)] : (a.ev ? a.ev[k] : -1));
         [[maybe_unused]] bool any_ev = false;
         if constexpr (Bd::pev) any_ev = __builtin_amdgcn_ballot_w64(ev >= 0) != 0;
-        if constexpr (Bd::sub) { if (tid < TB) dts[tid] = (la_tn - la_t) / (float)nsub; }
+        if constexpr (Bd::ab) {
+            // (a thread < TB owns column tid: `ev`, `ev_n` are that column's.  Every lane runs the arithmetic -- the others on zeros, whose
+            //  results nobody reads -- and only the stores are guarded: registers that live across steps are then written under full EXEC)
+            const float h = la_tn - la_t, hm = la_t - la_tm;      // h_k, h_{k-1} (the latter read for k >= 1 only)
+            const bool restart = k == 0 || ev >= 0 || hm == 0.0f;
+            const float c0k = restart ? h : h * (1.0f + (h / hm) / 2.0f);
+            // c1_{k+1}: absent behind the last step, 0 where step k + 1 restarts (its event, or h_k == 0)
+            const bool none = k + 2 > a.T - 1 || ev_n >= 0 || h == 0.0f;
+            const float c1n = none ? 0.0f : -(h_n * ((h_n / h) / 2.0f));
+            if (tid < TB) { dts[tid] = c0k; gks[2 * nx + tid] = c1n; }
+            h_n = h;
+            la_tm = a.t.p[(k >= 2 ? k - 2 : 0) * a.t.st + gb(tid % TB) * a.t.sb];      // t[(k - 1) - 1], for the next step of the sweep
+            ev_n = ev;
+        } else if constexpr (Bd::sub) { if (tid < TB) dts[tid] = (la_tn - la_t) / (float)nsub; }
         else { if (tid < TB) dts[tid] = la_tn - la_t; }
         float gx_in[LA];                             // the incoming gradient of grid point k, consumed at the bottom of the step
         [[maybe_unused]] float x_keep[LA];           // sub-step build: xs[k] of the look-ahead, for sub-step 0 (x0 holds the later ones' starts first)
@@ -311,7 +345,15 @@
         TILE_LOOP(xd) {
             const float g1 = gxc[r * TP + c];
             gx0[r * TP + c] = g1;
+            if constexpr (Bd::ab) {      // phi_k; g_{k+2}'s slot is unwritten at the first step of the sweep, where c1 is 0
+                const float c1n = gks[2 * nx + c];
+                float phi = dts[c] * g1;
+                if (c1n != 0.0f) phi = phi + c1n * gks[nx + r * TP + c];
+                gks[r * TP + c] = phi;
+                gks[nx + r * TP + c] = g1;      // g_{k+1} for step k - 1: written and read by this thread alone
+            } else {
             for (int s = 0; s < S; ++s) gks[s * nx + r * TP + c] = dts[c] * coef_b(a.method, ks, nx, s) * g1;
+            }
         }
         if constexpr (Bd::lin) { if (si.first()) { TILE_LOOP(nzv) gexr[r * TP + c] = 0.0f; } }
         if constexpr (Bd::sub) { TILE_LOOP(ne) if (r >= nzv || si.first()) gext[r * TP + c] = 0.0f; }

@@ -25,7 +25,7 @@
 // Padded columns: the image holds zeros there and the input builders write zeros into the pad columns of the first layer's input; a
 // hidden layer's pad units come out of the MFMA as ELU(0 + 0) = 0.
 //
-// Seven objects are compiled from this header, one per build policy (psnode_generic_build.h).  Each of psnode_generic{,_act,_pre,_rk,_sub,_lin,_pev}.hip
+// Eight objects are compiled from this header, one per build policy (psnode_generic_build.h).  Each of psnode_generic{,_act,_pre,_rk,_sub,_lin,_pev,_ab}.hip
 // names its policy `Bd` in front of the include, writes its kernel around psnode_generic_body.h and its exported launcher over
 // launch_generic_build:
 //   BuildElu1  generic_kernel(a), launch_generic                    ELU(1)
@@ -40,6 +40,10 @@
 //   BuildPev   generic_pev_kernel(a, act, rk, sub), launch_generic_pev   the sub-step build (every n >= 1) with a [T-1, B] event table: every
 //              thread carries its own column's event index in a register, the event slot runs where any column of the workgroup has a
 //              hit and is taken per column; no LDS of its own
+//   BuildAb    generic_ab_kernel(a, act, rk, ab), launch_generic_ab   the per-trajectory build as two-step Adams-Bashforth (one stage, one
+//              sub-step; AbDev in SubDev's place): the final pass forms x + c0 f_k + c1 f_{k-1} with per-column c0 / c1; the previous slope
+//              and c1 live in the kbuf slots a one-stage build never writes; the event table is [T-1, B], the shared [T-1] (column stride
+//              0) or null; no LDS of its own
 // The device functions take the activation as one ordinary parameter, ActCtx; the kernel body chooses the tableau code with
 // `if constexpr (Bd::rk)`, the sub-step code with `if constexpr (Bd::sub)`.  The host's plan / fit / pack code is compiled once, in
 // psnode_generic.hip.

@@ -80,11 +80,21 @@ class Tableau:
         return self.name
 
 
+AB2 = "ab2"      # the `method` value of two-step Adams-Bashforth (neural_dae.AB2): the _ab entry points of K0 / K5, no other kernel
+
+
+def is_ab(method) -> bool:
+    return isinstance(method, str) and method == AB2
+
+
 def method_info(method):
     """(method id for the args struct, right-hand-side evaluations per step, Tableau | None) of a `method` of the generic route: one of the
-    built-in names, or a Tableau (whose calls go to the _rk entry points, which do not read the id)."""
+    built-in names, a Tableau (whose calls go to the _rk entry points, which do not read the id) or "ab2" (two-step Adams-Bashforth: one
+    evaluation per step; its calls go to the _ab entry points, which do not read the id either)."""
     if isinstance(method, Tableau):
         return _lib.EULER, method.stages, method
+    if is_ab(method):
+        return _lib.EULER, 1, None
     return METHOD_ID[method], STAGES[method], None
 
 
@@ -192,7 +202,9 @@ class GenericOpts:
     and `externals` (`of`), and the value says which entry-point family the call takes (`family`, `call_generic`) and which calls are
     refused (`require_generic`, `require_plain`).  acts: one Act | None per MLP (ODE 1, DAE 2); tab: the Tableau of `method`, if it is one;
     method_id / stages: what the args struct and the saved rows need of `method` (`method_info`); per_trajectory: the call's event table
-    is [T-1, B], every trajectory jumps at its own steps (only a call that HAS events carries it: `has_events`)."""
+    is [T-1, B], every trajectory jumps at its own steps (only a call that HAS events carries it: `has_events`); ab: the method is two-step
+    Adams-Bashforth ("ab2") -- the sixth and last option in the naming order; never together with a Tableau, sub-steps or interpolated
+    externals (the solver's constructor refuses them; here a ValueError), with per_trajectory it stays the family "ab"."""
     acts: tuple
     tab: Optional[Tableau]
     substeps: int = 1
@@ -200,10 +212,12 @@ class GenericOpts:
     method_id: int = _lib.EULER
     stages: int = 1
     per_trajectory: bool = False
+    ab: bool = False
     family: str = dataclasses.field(init=False)
 
     def __post_init__(self):
-        """Validates substeps and externals, and names the entry-point family: "pev" (per-trajectory events, every substeps >= 1; together
+        """Validates substeps and externals, and names the entry-point family: "ab" (two-step Adams-Bashforth, with or without
+        per-trajectory events; a ValueError together with a Tableau, sub-steps or interpolated externals), else "pev" (per-trajectory events, every substeps >= 1; together
         with interpolated externals "none": no kernel carries both, `require_generic` refuses the call), else "lin" (interpolated
         externals, every substeps >= 1), else "sub" (substeps > 1), else "rk" (a Tableau), else "act" (an activation other than ELU(1)),
         else "plain"."""
@@ -211,7 +225,12 @@ class GenericOpts:
             raise ValueError(f"substeps must be an int in 1..{_lib.MAX_SUBSTEPS}, got {self.substeps!r}")
         if not isinstance(self.per_trajectory, bool):
             raise ValueError(f"per_trajectory must be a bool, got {self.per_trajectory!r}")
-        if self.per_trajectory:
+        if self.ab:
+            if self.substeps != 1 or is_linear(self.externals) or self.tab is not None:
+                raise ValueError("Adams-Bashforth 2 reads the right-hand side at grid points only: substeps != 1 and externals='linear' would "
+                                 f"need inputs between the dataset rows (got substeps={self.substeps}, externals={self.externals!r})")
+            fam = "ab"
+        elif self.per_trajectory:
             fam = "none" if is_linear(self.externals) else "pev"
         elif is_linear(self.externals):
             fam = "lin"
@@ -227,7 +246,7 @@ class GenericOpts:
     @functools.lru_cache(maxsize=256, typed=True)      # (a loop asks for the same immutable value call after call; typed: 2.0 and True are not 2 and 1)
     def of(method, acts: tuple, substeps: int = 1, externals: str = "hold", per_trajectory: bool = False) -> "GenericOpts":
         method_id, stages, tab = method_info(method)
-        return GenericOpts(acts, tab, substeps, externals, method_id, stages, per_trajectory)
+        return GenericOpts(acts, tab, substeps, externals, method_id, stages, per_trajectory, is_ab(method))
 
     def c_args(self, x_sub=None) -> list:
         """The family's C arguments behind the args struct: none ("plain"); the acts ("act"); the acts and the tableau ("rk"); the acts,
@@ -237,6 +256,8 @@ class GenericOpts:
         if fam == "plain":
             return []
         out = _act_ptrs(self.acts)
+        if fam == "ab":      # the acts and per_trajectory: is the event table, if there is one, [T-1, B]?
+            return out + [ctypes.c_int32(1 if self.per_trajectory else 0)]
         if fam != "act":
             out.append(ctypes.byref(self.tab.abi()) if self.tab is not None else None)
         if fam in ("sub", "lin", "pev"):
@@ -251,7 +272,7 @@ class GenericOpts:
         "lin" and for a call with dataset rows x_true / i_true ("tf": the family of such a call that would otherwise be "plain"), else
         psnode_dae_bwd_args_f32.  Dataset rows next to a non-ELU act alone: no entry point takes both (`call_generic` asserts it too)."""
         assert not (rows and self.family == "act"), "dae_backward: dataset rows with an activation other than ELU(1) have no entry point"
-        return _lib.DaeBwdTfArgsF32() if rows or self.family in ("rk", "sub", "lin", "pev") else _lib.DaeBwdArgsF32()
+        return _lib.DaeBwdTfArgsF32() if rows or self.family in ("rk", "sub", "lin", "pev", "ab") else _lib.DaeBwdArgsF32()
 
     def _first_option(self) -> str:
         """The first option the call carries, in the fixed order act, tableau, sub-steps, externals, as the subject of a refusal."""
@@ -263,7 +284,9 @@ class GenericOpts:
             return f"sub-steps per grid interval (substeps={self.substeps}) run"
         if self.externals == "linear":
             return "linearly interpolated external inputs (externals='linear') run"
-        return "per-trajectory events (per_trajectory=True) run"
+        if self.per_trajectory:
+            return "per-trajectory events (per_trajectory=True) run"
+        return "two-step Adams-Bashforth (AB2) runs"
 
     def require_generic(self, what: str, kernel: str, saved: bool, teacher_forced: bool = False):
         """The options run on the generic kernels only: UnsupportedShapeError, naming the first option in the order act, tableau, sub-steps,
@@ -272,6 +295,7 @@ class GenericOpts:
         together with interpolated externals they have no kernel at all."""
         if self.family == "plain":
             return
+        self.no_teacher_forcing(what, teacher_forced)
         if self.family == "none":
             raise _lib.UnsupportedShapeError(f"{what}: per-trajectory events (per_trajectory=True) together with linearly interpolated external "
                                              "inputs (externals='linear') have no fused form: K0 / K5 carry either, not both")
@@ -281,6 +305,12 @@ class GenericOpts:
         if teacher_forced and any(a is not None for a in self.acts):
             raise _lib.UnsupportedShapeError(f"{what}: an activation other than ELU(alpha=1) runs on the generic backward K5 only "
                                              "(kernel 'auto' / 'generic', no saved rows, no teacher forcing)")
+
+    def no_teacher_forcing(self, what: str, teacher_forced: bool):
+        """Adams-Bashforth 2 with input_true_x / input_true_i: ValueError, on every path."""
+        if self.ab and teacher_forced:
+            raise ValueError(f"{what}: Adams-Bashforth 2 has no teacher-forced form -- every teacher-forced step starts from a dataset row, "
+                             "so the previous slope a multistep method carries is undefined")
 
     def require_plain(self, what: str):
         """(method id, stages) for the specialised, latent, encoded and saved-row entries, which carry the three built-in formulas with one
@@ -297,6 +327,9 @@ class GenericOpts:
             raise _lib.UnsupportedShapeError(f"{what}: per-trajectory events (per_trajectory=True) run on the generic kernels K0 / K5 only "
                                              "(kernel 'auto' / 'generic', no saved rows); this entry point jumps the whole batch at the steps "
                                              "of one int32[T-1] table")
+        if self.ab:
+            raise _lib.UnsupportedShapeError(f"{what}: two-step Adams-Bashforth (AB2) runs on the generic kernels K0 / K5 only "
+                                             "(kernel 'auto' / 'generic', no saved rows); this entry point carries euler / midpoint / rk4")
         return self.method_id, self.stages
 
 
@@ -320,7 +353,7 @@ def call_generic(lib, stem: str, kind: str, args, opts: GenericOpts, *tail, x_su
         assert stem in ("ode_backward", "dae_backward"), f"{stem} has no workspace query of its own"
         if stem == "ode_backward" or fam == "act":
             fam = "plain"
-        elif fam == "pev":
+        elif fam in ("pev", "ab"):
             # the _rk query with the call's acts and tableau -- a built-in method's stand-in is the one-stage tableau, the size does not
             # depend on it: the same policy (every activation kind, the pre-activations kept), so the same fit, the same checks and the same
             # layout as this family's build, whatever the number of sub-steps

@@ -349,6 +349,7 @@ def dae_backward_tf(method, de_layers: Layers, ae_layers: Layers, t, z, v, all_i
             raise ValueError(f"{name} must be [T,B,{w}], got {tuple(q.shape)}")
     opts = GenericOpts.of(method, (None, None), substeps, externals, bool(per_trajectory) and event_idx is not None)
     opts.require_generic("dae_backward_tf", kernel, False)
+    opts.no_teacher_forcing("dae_backward_tf", x_true is not None or i_true is not None)
     return _dae_backward_entry(opts, de_layers, ae_layers, t, z, v, all_initial, xs, is_, grad_xs,
                                grad_is, event_idx, z_jump, v_jump, kernel, None, x_true=x_true, i_true=i_true, x_sub=x_sub)
 

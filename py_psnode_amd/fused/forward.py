@@ -83,6 +83,7 @@ def ode_integrate(method, de_layers: Layers, t, x, z, all_initial, event_t=None,
     per_trajectory = bool(per_trajectory) and has_events(t, event_t, event_idx)
     opts = GenericOpts.of(method, (act,), substeps, externals, per_trajectory)
     opts.require_generic("ode_integrate", kernel, save)
+    opts.no_teacher_forcing("ode_integrate", input_true_x)
     T, B, xd = t.shape[0], x.shape[1], x.shape[2]
     if x.shape[0] < (T if input_true_x else 1):
         raise ValueError("x has fewer grid points than t")
@@ -123,7 +124,7 @@ def ode_integrate(method, de_layers: Layers, t, x, z, all_initial, event_t=None,
                      _empty((max(T - 1, 0), opts.stages, B, xd), dtype=torch.float32, device=dev))
             if T >= 2:
                 a.save_act, a.save_xstage = saved[0].data_ptr(), saved[1].data_ptr()
-        x_sub = _empty((max(T - 1, 0), substeps - 1, B, xd), dtype=torch.float32, device=dev) if save_sub and opts.family in ("sub", "lin", "pev") else None
+        x_sub = _empty((max(T - 1, 0), substeps - 1, B, xd), dtype=torch.float32, device=dev) if save_sub and opts.family in ("sub", "lin", "pev", "ab") else None
         ws, wp, wn = _workspace_of(lib.psnode_workspace_bytes(ctypes.byref(a.de), None), dev)
         rc, entry = call_generic(lib, "ode_integrate", "f32", a, opts, wp, wn, torch.cuda.current_stream(dev).cuda_stream, x_sub=x_sub)
     _mfma_miss(rc, kernel, entry, de_layers)
@@ -177,6 +178,7 @@ def dae_integrate(method, de_layers: Layers, ae_layers: Layers, x_init, t, x, z,
     per_trajectory = bool(per_trajectory) and has_events(t, event_t, event_idx)
     opts = GenericOpts.of(method, dae_acts(act), substeps, externals, per_trajectory)
     opts.require_generic("dae_integrate", kernel, save)
+    opts.no_teacher_forcing("dae_integrate", input_true_x or input_true_i)
     T, B = t.shape[0], t.shape[1]
     xd, zd, vd, idim = x_init.shape[-1], z.shape[-1], v.shape[-1], i.shape[-1]
     if x_init.dim() != 2 or x_init.shape[0] != B:
@@ -241,7 +243,7 @@ def dae_integrate(method, de_layers: Layers, ae_layers: Layers, x_init, t, x, z,
                 a.save_act = a.save_xstage = dummy.data_ptr()
             if n_ev:
                 a.save_ev_act, a.save_ev_i = saved[3].data_ptr(), saved[4].data_ptr()
-        x_sub = _empty((max(T - 1, 0), substeps - 1, B, xd), dtype=torch.float32, device=dev) if save_sub and opts.family in ("sub", "lin", "pev") else None
+        x_sub = _empty((max(T - 1, 0), substeps - 1, B, xd), dtype=torch.float32, device=dev) if save_sub and opts.family in ("sub", "lin", "pev", "ab") else None
         ws, wp, wn = _workspace_of(lib.psnode_workspace_bytes(ctypes.byref(a.de), ctypes.byref(a.ae)), dev)
         rc, entry = call_generic(lib, "dae_integrate", "f32", a, opts, wp, wn, torch.cuda.current_stream(dev).cuda_stream, x_sub=x_sub)
     _mfma_miss(rc, kernel, entry, de_layers)

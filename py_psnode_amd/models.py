@@ -274,7 +274,7 @@ class ODE_Model(nn.Module):
             return None
         if getattr(solver, "kernel", "auto") == "generic":        # PSNODE_KERNEL=generic asks for K0: row kernels + solver route
             return None
-        if isinstance(solver.method, fused.Tableau):               # a Runge-Kutta tableau runs on K0 / K5: row kernels + solver route
+        if isinstance(solver.method, fused.Tableau) or fused.is_ab(solver.method):      # a Runge-Kutta tableau and Adams-Bashforth 2 run on K0 / K5: row kernels + solver route
             return None
         if getattr(solver, "substeps", 1) > 1 or getattr(solver, "externals", "hold") != "hold":      # so do sub-steps and linear externals
             return None
@@ -389,7 +389,7 @@ class DAE_Model(nn.Module):
         solver = self.solver
         if not isinstance(solver, FixedGridODESolver) or getattr(solver, "fused", "off") == "off" or not solver.method:
             return None
-        if getattr(solver, "kernel", "auto") == "generic" or isinstance(solver.method, fused.Tableau):      # (a tableau runs on K0 / K5)
+        if getattr(solver, "kernel", "auto") == "generic" or isinstance(solver.method, fused.Tableau) or fused.is_ab(solver.method):      # (a tableau and Adams-Bashforth 2 run on K0 / K5)
             return None
         if getattr(solver, "substeps", 1) > 1 or getattr(solver, "externals", "hold") != "hold" or (getattr(self.event, "per_trajectory", False) and event_t is not None):      # (so do sub-steps, linear externals and per-trajectory events of a call that has events)
             return None

@@ -8,6 +8,8 @@ the callback walk (user callables / autograd).  Callback convention (my_fixed_gr
 `_step_func_lin` is each class's formula once more for `externals="linear"` (my_solvers.py): the stage at abscissa c reads the externals
 `ext_at(c)` instead of the step's frozen ones.  `_step_func`, its signature and the "hold" path are untouched by it.
 """
+import torch
+
 from .. import fused as _fused
 from .my_solvers import FixedGridODESolver
 
@@ -162,3 +164,123 @@ class RK4Classic(_NamedRK):
     """The classic fourth-order Runge-Kutta method."""
     order = 4
     _a, _b = ((), (0.5,), (0.0, 0.5), (0.0, 0.0, 1.0)), (1 / 6, 1 / 3, 1 / 3, 1 / 6)
+
+
+class AB2(FixedGridODESolver):
+    """Two-step Adams-Bashforth: the right-hand side is evaluated at grid points only -- where the dataset rows z | v are exact and where a
+    DAE's head i_k = g(x_k, z_k, v_k) is evaluated anyway -- so it is second order for ODE and DAE alike at ONE DE evaluation per step
+    (Euler's cost).  Step k from grid point k to k + 1, per trajectory, h_k = t[k+1] - t[k], f_k the DE at the inputs Euler's stage reads:
+        x_{k+1} = x_k + c0 f_k + c1 f_{k-1}
+        restart (k = 0, an event fires at step k -- per trajectory under per_trajectory events --, or h_{k-1} == 0):  c0 = h_k, c1 = 0
+        otherwise  rho = h_k / h_{k-1},  c0 = h_k (1 + rho / 2),  c1 = -h_k (rho / 2)
+    written once (`_ab2_step`), in the tensors' dtype, uncontracted; the generic kernels K0 / K5 (kernel 'auto' / 'generic') use the same
+    order of operations.  The walk (`_walk_ode` / `_walk_dae`, overridden here: every other solver runs the base class's statements)
+    carries the previous slope and step.  `_step_func` is the Euler step, so `step_integrate` alone is a restart step.
+    No sub-steps and no interpolated externals (the method reads grid rows only; both would need inputs between the rows), no teacher
+    forcing (every teacher-forced step starts from a dataset row: a multistep history is undefined) -- ValueError.  Stability: the
+    real-axis interval is |h lambda| < 1, half of Euler's."""
+    order = 2
+    method = _fused.AB2
+
+    def __init__(self, **kw):
+        if kw.get("substeps", 1) != 1:
+            raise ValueError("AB2 reads the right-hand side at grid points only: substeps != 1 would need inputs between the dataset rows "
+                             f"(got substeps={kw.get('substeps')!r})")
+        if kw.get("externals", "hold") != "hold":
+            raise ValueError("AB2 reads the right-hand side at grid points only: externals='linear' would need inputs between the dataset rows "
+                             f"(got externals={kw.get('externals')!r})")
+        super().__init__(**kw)
+
+    def _step_func(self, func, t0, dt, t1, x0, z0=None, v0=None, i0=None, all_initial=None):
+        """The Euler step: a single step has no history, so `step_integrate` alone is a restart step."""
+        f0 = _rhs(func, z0, v0, i0, all_initial)(t0, x0)
+        return dt * f0, f0
+
+    def _generic_only_ok(self, what, acts, per_trajectory=False) -> bool:
+        """AB2 runs on the generic kernels K0 / K5 only: kernel 'wave' / 'tile' / 'mfma' / 'wide' walks under fused='auto' and raises under
+        'require'."""
+        if self.kernel in ("auto", "generic"):
+            return True
+        if self.fused == "require":
+            raise _fused._lib.UnsupportedShapeError(f"{what}: kernel={self.kernel!r} has no form for two-step Adams-Bashforth: AB2 runs on the "
+                                                    "generic kernels (kernel 'auto' / 'generic')")
+        return False
+
+    @staticmethod
+    def _no_teacher_forcing(what, forced):
+        if forced:
+            raise ValueError(f"{what}: AB2 has no teacher-forced form -- every teacher-forced step starts from a dataset row, so the "
+                             "previous slope a multistep method carries is undefined")
+
+    @staticmethod
+    def _restart_mask(event_fn, t0):
+        """The trajectories whose step restarts because an event fired: bool [B, 1] under per-trajectory events, else True (all)."""
+        if _fused.per_trajectory_events(event_fn):
+            return event_fn.__self__.hit_mask(t0).view(-1, 1)
+        return True
+
+    @staticmethod
+    def _ab2_step(x, f, h, f_prev, h_prev, hit):
+        """x_{k+1} of the class docstring.  f_prev / h_prev: None at k = 0; hit: None (no event), True (every trajectory restarts) or
+        bool [B, 1].  The clock carries no gradient."""
+        euler = x + h * f
+        if f_prev is None or hit is True:
+            return euler
+        restart = h_prev == 0
+        if hit is not None:
+            restart = restart | hit
+        half_rho = (h / torch.where(restart, torch.ones_like(h_prev), h_prev)) / 2
+        c0 = h * (1 + half_rho)
+        c1 = -(h * half_rho)
+        return torch.where(restart, euler, x + c0 * f + c1 * f_prev)
+
+    def integrate_ODE(self, x_func, t, x, z, all_initial, event_fn=None, jump_change_fn=None, input_true_x=False, x_init=None):
+        self._no_teacher_forcing("integrate_ODE", input_true_x)
+        return super().integrate_ODE(x_func, t, x, z, all_initial, event_fn, jump_change_fn, input_true_x, x_init)
+
+    def integrate_DAE(self, x_init, x_func, i_func, t, x, z, v, i, all_initial, event_fn=None, jump_change_fn=None,
+                      input_true_x=False, input_true_i=False):
+        self._no_teacher_forcing("integrate_DAE", input_true_x or input_true_i)
+        return super().integrate_DAE(x_init, x_func, i_func, t, x, z, v, i, all_initial, event_fn, jump_change_fn, input_true_x, input_true_i)
+
+    def _walk_ode(self, x_func, t, x, z, all_initial, event_fn, jump_change_fn, input_true_x, x_init=None):
+        self._no_teacher_forcing("integrate_ODE", input_true_x)
+        xs = torch.zeros(x.shape, dtype=x.dtype, device=x.device)
+        cur = x[0] if x_init is None else x_init
+        xs[0] = cur
+        f_prev = h_prev = None
+        for k in range(t.shape[0] - 1):
+            t0, zk, hit = t[k], z[k], None
+            if event_fn is not None and event_fn(t0) == True:  # noqa: E712 (callbacks may return tensors)
+                zk = jump_change_fn(t0, zk)
+                hit = self._restart_mask(event_fn, t0)
+            h = t[k + 1] - t0
+            f = x_func(t0=t0, xt=cur, zt=zk, all_initial=all_initial)
+            cur = self._ab2_step(cur, f, h, f_prev, h_prev, hit)
+            f_prev, h_prev = f, h
+            xs[k + 1] = cur
+        return xs
+
+    def _walk_dae(self, x_init, x_func, i_func, t, x, z, v, i, all_initial, event_fn, jump_change_fn, input_true_x, input_true_i):
+        self._no_teacher_forcing("integrate_DAE", input_true_x or input_true_i)
+        cur_x = x_init
+        cur_i = i_func(xt=cur_x, zt=z[0], vt=v[0], all_initial=all_initial)
+        x_shape = (*x.shape[0:2], x_init.shape[-1]) if x.shape[-1] == 0 else x.shape
+        xs = torch.zeros(x_shape, dtype=x_init.dtype if x.shape[-1] == 0 else x.dtype, device=x.device)
+        is_ = torch.zeros(i.shape, dtype=i.dtype, device=i.device)
+        xs[0], is_[0] = cur_x, cur_i
+        f_prev = h_prev = None
+        for k in range(t.shape[0] - 1):
+            t0, zk, vk, hit = t[k], z[k], v[k], None
+            if event_fn is not None and event_fn(t0) == True:  # noqa: E712
+                zk, vk = jump_change_fn(t0, zk, vk)
+                hit = self._restart_mask(event_fn, t0)
+                head = i_func(xt=cur_x, zt=zk, vt=vk, all_initial=all_initial)
+                cur_i = head if hit is True else torch.where(hit, head, cur_i)      # (per trajectory: the hit ones take the event-time head)
+            h = t[k + 1] - t0
+            f = x_func(t0=t0, xt=cur_x, zt=zk, vt=vk, it=cur_i, all_initial=all_initial)
+            cur_x = self._ab2_step(cur_x, f, h, f_prev, h_prev, hit)
+            f_prev, h_prev = f, h
+            cur_i = i_func(xt=cur_x, zt=z[k + 1], vt=v[k + 1], all_initial=all_initial)
+            xs[k + 1], is_[k + 1] = cur_x, cur_i
+        return xs, is_
