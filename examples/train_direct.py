@@ -14,6 +14,7 @@ plotting and replay-buffer bookkeeping.  With --synthetic it writes a small data
     python examples/train_direct.py --model dae02 --train-data training.npz --test-data testing.npz --solver euler
     python examples/train_direct.py --model dae02 --synthetic --loss huber --loss-param 0.05
     python examples/train_direct.py --model dae01 --synthetic --scattered-events      # every sample's fault at its own step
+    python examples/train_direct.py --model dae01 --synthetic --segment 25            # multiple shooting: restart from the data every 25 steps
 """
 import argparse
 import os
@@ -54,8 +55,8 @@ def write_synthetic(path, n, T, dae, seed, scattered=False):
     np.savez(path, **d)
 
 
-def build(model, solver):
-    s = {"euler": nd.Euler, "midpoint": nd.Midpoint, "rk4": nd.RK4}[solver]()
+def build(model, solver, segment=None):
+    s = {"euler": nd.Euler, "midpoint": nd.Midpoint, "rk4": nd.RK4}[solver](segment=segment)
     H = HIDDEN[model]
     if model.startswith("ode"):
         return models.ODE_Model(8, 2, H, direct_encode=model.endswith("02"), solver=s)
@@ -84,9 +85,18 @@ def step_loss(model_name, model, batch, loss_func=None):
 def evaluate(model_name, model, loader, loss_func=None):
     """evalute_model (neural_00_ODE_01_no_encode.py:104-129): the per-sample table
     `torch.sum(Loss_func(x_pred * mask, x * mask, reduction='none'), dim=1)` of every batch, summed over the samples and divided by the
-    mask count -> (x_loss_dim_i for every column, x_loss_total)."""
+    mask count -> (x_loss_dim_i for every column, x_loss_total).  Always the FREE rollout: a solver that trains with multiple-shooting
+    segments (--segment) is evaluated with segment = None, so the test loss is the one every other run reports."""
     dev = loader.dataset.device
     num, den = None, torch.zeros((), device=dev)
+    segment, model.solver.segment = model.solver.segment, None
+    try:
+        return _evaluate(model_name, model, loader, loss_func, dev, num, den)
+    finally:
+        model.solver.segment = segment
+
+
+def _evaluate(model_name, model, loader, loss_func, dev, num, den):
     for batch in loader:
         x, mask = batch[1], batch[-1]
         if model_name.startswith("ode"):
@@ -118,6 +128,10 @@ def main(argv=None):
                     help="the synthetic dataset draws each sample's fault step on its own, and the model's event object applies the events per "
                          "trajectory (model.event.per_trajectory = True: the generic kernels K0 / K5; ode01 / dae01 -- the latent integrators of "
                          "the direct_encode models have no generic backward at every width)")
+    ap.add_argument("--segment", type=int, default=None, metavar="W",
+                    help="multiple shooting (default off): every W-th grid point the rollout restarts from the dataset row x[k], free inside a "
+                         "segment (solver.segment = W: the generic kernels K0 / K5, one launch each way; training only -- the test loss is always the free rollout's; ode01 / dae01 -- the latent state "
+                         "of the direct_encode models is an encoder output, which the restarts cannot read as data)")
     ap.add_argument("--num", type=int, default=320)
     ap.add_argument("--step", type=int, default=201, help="grid points per sample (cut_length)")
     ap.add_argument("--batch", type=int, default=64)
@@ -140,7 +154,7 @@ def main(argv=None):
     test = datapath.ResidentDataset(cls(args.test_data, dev), dev)
     train_loader = datapath.ResidentLoader(train, batch_size=args.batch, shuffle=True)
     test_loader = datapath.ResidentLoader(test, batch_size=max(len(test) // 10, 1), shuffle=False)
-    model = build(args.model, args.solver).to(dev)
+    model = build(args.model, args.solver, args.segment).to(dev)
     model.solver.fused = "require"           # fail loudly rather than walk the time loop in Python
     model.event.per_trajectory = args.scattered_events      # a sample jumps where ITS clock meets ITS event time, not where sample 0's does
     opt = torch.optim.Adam(model.parameters(), lr=args.lr)

@@ -911,6 +911,51 @@ int32_t psnode_dae_backward_ab_supported(const psnode_dae_bwd_tf_args_f32* args,
 int32_t psnode_dae_backward_ab_f32(const psnode_dae_bwd_tf_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
                                    int32_t per_trajectory, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Multiple-shooting segments on the generic kernels (additive to ABI 10; DESIGN.md "Multiple-shooting segments on K0 / K5").
+ * Grid point k is a restart point iff k > 0 and k % every == 0.  The step that leaves a restart point starts from the dataset row x[k]
+ * instead of the running state (its first sub-step only), and in a DAE its DE reads the head at that row, g(x[k]; row k of z | v, or the
+ * jumped rows if event_idx[k] >= 0), in place of the algebraic variable it carries.  The outputs x_out[k] / i_out[k] of a restart point
+ * stay the previous segment's prediction; every grid-point head reads the running state.  So output rows m every + 1 ..
+ * min((m + 1) every, T - 1) are what the _sub call returns in its rows 1 .. on the slices [m every : (m + 1) every + 1] started from
+ * x[m every].  A forward call reads the rows from args->x, which must then hold all T of them (an ODE's row 0 is the start of the call,
+ * as always; a DAE starts from x_init); a backward call reads them from x_true.  The dataset rows get no gradient: a backward call drops
+ * the start adjoint of a restart step and the x part of the restart head's VJP; that head's z | v part goes to row k of grad_z / grad_v, or
+ * to the event's jump row; grad_x0 / grad_x_init is segment 0's.  No atomics, bitwise repeatable.  Sub-steps, the tableau, the
+ * activations and the shared event table are what the _sub entry points define.
+ * Rules (the entry points take what their _sub siblings take, plus the segments struct in front of the workspace):
+ *   - a NULL psnode_segments_f32 gives PSNODE_ERR_NULL, every < 1 PSNODE_ERR_DIMS -- before anything else is looked at;
+ *   - a NULL psnode_substeps_f32 means one sub-step; a NULL act is ELU(1); a NULL tableau is the built-in `method` of the args;
+ *   - `kernel` must be PSNODE_KERNEL_AUTO or _GENERIC, the save_* / saved_* pointers NULL and no teacher-forcing flag set -- every
+ *     teacher-forced step restarts already --, and a DAE forward call's x view must not be empty (PSNODE_ERR_UNSUPPORTED); the _supported
+ *     queries answer for the LDS fit, which is the _sub build's;
+ *   - a backward call with T - 1 > every and a NULL x_true gives PSNODE_ERR_NULL.
+ * Every check returns its status before anything is launched.  Workspaces: those of the _rk entry points, as for the _pev family; this
+ * family has no query of its own. */
+typedef struct {
+    int32_t every;         /* >= 1: grid point k > 0 with k % every == 0 restarts from the dataset row */
+    const float* x_true;   /* [T,B,x_dim] contiguous dataset rows; read by the backward calls (a forward call reads args->x), may be NULL there */
+} psnode_segments_f32;
+int32_t psnode_ode_integrate_ms_supported(const psnode_ode_args_f32* args, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
+                                          const psnode_substeps_f32* sub, const psnode_segments_f32* seg);
+int32_t psnode_ode_integrate_ms_f32(const psnode_ode_args_f32* args, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
+                                    const psnode_substeps_f32* sub, const psnode_segments_f32* seg, void* workspace, size_t workspace_bytes,
+                                    void* stream);
+int32_t psnode_dae_integrate_ms_supported(const psnode_dae_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                          const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, const psnode_segments_f32* seg);
+int32_t psnode_dae_integrate_ms_f32(const psnode_dae_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                    const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, const psnode_segments_f32* seg,
+                                    void* workspace, size_t workspace_bytes, void* stream);
+int32_t psnode_ode_backward_ms_supported(const psnode_ode_bwd_args_f32* args, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
+                                         const psnode_substeps_f32* sub, const psnode_segments_f32* seg);
+int32_t psnode_ode_backward_ms_f32(const psnode_ode_bwd_args_f32* args, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
+                                   const psnode_substeps_f32* sub, const psnode_segments_f32* seg, void* workspace, size_t workspace_bytes,
+                                   void* stream);
+int32_t psnode_dae_backward_ms_supported(const psnode_dae_bwd_tf_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                         const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, const psnode_segments_f32* seg);
+int32_t psnode_dae_backward_ms_f32(const psnode_dae_bwd_tf_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                   const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, const psnode_segments_f32* seg,
+                                   void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

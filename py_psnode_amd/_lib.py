@@ -41,6 +41,8 @@ ABI_VERSION = 10         # == PSNODE_ABI_VERSION of include/psnode_hip.h (2: rou
                          #     points -- per-trajectory events (an event table [T-1, B]) on K0 / K5;
                          #     additive, same version: the psnode_{ode,dae}_{integrate,backward}_ab_* entry points -- two-step
                          #     Adams-Bashforth on K0 / K5;
+                         #     additive, same version: psnode_segments_f32 and the psnode_{ode,dae}_{integrate,backward}_ms_* entry points --
+                         #     multiple-shooting segments on K0 / K5;
                          #     additive, same version: psnode_loss_fn_f32 and psnode_masked_loss_* / psnode_loss_per_sample_f32 -- L1, SmoothL1 and
                          #     Huber on K6, and the per-sample evaluation table of all four kinds)
 LIB_NAME = "libpsnode_hip.so"
@@ -86,6 +88,9 @@ EXPORTS = (
     "psnode_ode_integrate_ab_supported", "psnode_ode_integrate_ab_f32", "psnode_dae_integrate_ab_supported", "psnode_dae_integrate_ab_f32",
     "psnode_ode_backward_ab_supported", "psnode_ode_backward_ab_f32",
     "psnode_dae_backward_ab_supported", "psnode_dae_backward_ab_f32",
+    "psnode_ode_integrate_ms_supported", "psnode_ode_integrate_ms_f32", "psnode_dae_integrate_ms_supported", "psnode_dae_integrate_ms_f32",
+    "psnode_ode_backward_ms_supported", "psnode_ode_backward_ms_f32",
+    "psnode_dae_backward_ms_supported", "psnode_dae_backward_ms_f32",
 )
 
 
@@ -114,6 +119,12 @@ class ActF32(ctypes.Structure):
 class RkTableauF32(ctypes.Structure):
     """psnode_rk_tableau_f32: an explicit Runge-Kutta method of 1..4 stages (a strictly lower triangular)."""
     _fields_ = [("stages", c_int32), ("a", (ctypes.c_float * 4) * 4), ("b", ctypes.c_float * 4)]
+
+
+class SegmentsF32(ctypes.Structure):
+    """psnode_segments_f32: grid point k > 0 with k % every == 0 restarts from the dataset row; x_true [T, B, x_dim]: those rows for a
+    backward call (a forward call reads its args' x; NULL there)."""
+    _fields_ = [("every", c_int32), ("x_true", c_void_p)]
 
 
 class SubstepsF32(ctypes.Structure):
@@ -362,6 +373,12 @@ def load():
             f = getattr(lib, f"psnode_{name}_{fam}_f32")
             f.restype, f.argtypes = c_int32, [ctypes.POINTER(args_t)] + [act_p] * n_act + [rk_p, sub_p, c_void_p, c_size_t, c_void_p]
         # (the _ab entry points: no tableau, no sub-steps; the call takes per_trajectory -- is event_idx the [T-1, B] table? -- behind the acts)
+        # (the _ms entry points: what their _sub siblings take, plus the segments struct in front of the workspace)
+        seg_p = ctypes.POINTER(SegmentsF32)
+        q = getattr(lib, f"psnode_{name}_ms_supported")
+        q.restype, q.argtypes = c_int32, [ctypes.POINTER(args_t)] + [act_p] * n_act + [rk_p, sub_p, seg_p]
+        f = getattr(lib, f"psnode_{name}_ms_f32")
+        f.restype, f.argtypes = c_int32, [ctypes.POINTER(args_t)] + [act_p] * n_act + [rk_p, sub_p, seg_p, c_void_p, c_size_t, c_void_p]
         q = getattr(lib, f"psnode_{name}_ab_supported")
         q.restype, q.argtypes = c_int32, [ctypes.POINTER(args_t)] + [act_p] * n_act
         f = getattr(lib, f"psnode_{name}_ab_f32")

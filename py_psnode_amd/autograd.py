@@ -46,13 +46,13 @@ def latent_wide_training_fits(method, de, ae, hidden, T, B, dev) -> bool:
 def _generic_only_training(opts, kernel, teacher_forced, T=2) -> bool:
     """The gate of a training call that carries an option of the generic kernels (fused.GenericOpts.family other than "plain"): K0 + K5
     alone, so kernel "auto" / "generic"; teacher forcing with ELU(1) only and, for the DAE, on a grid of T >= 2.  K5 then answers for its fit."""
-    if opts.ab and teacher_forced:      # (Adams-Bashforth 2 has no teacher-forced form on any path: the solver raises before it asks)
+    if (opts.ab or opts.segment is not None) and teacher_forced:      # (neither Adams-Bashforth 2 nor segments have a teacher-forced form on any path: the solver raises before it asks)
         return False
     return kernel in ("auto", "generic") and not (teacher_forced and (T < 2 or any(a is not None for a in opts.acts)))
 
 
 def ode_training_supported(method, layers, x_dim, z_dim, T, B, kernel="auto", act=None, input_true_x=False, substeps=1,
-                           externals="hold", per_trajectory=False) -> bool:
+                           externals="hold", per_trajectory=False, segment=None) -> bool:
     """What the solver asks before it routes a call that needs autograd to the fused forward + backward pair.  act (fused.Act; None =
     ELU(1)): an activation other than ELU(1) trains on K0 + K5 alone, so K5 answers.  input_true_x: teacher-forced training -- K4f's
     recompute form on kernel "auto" / "mfma" where the shape is its, else K5 on "auto" / "generic"; ELU(1) only.
@@ -60,11 +60,14 @@ def ode_training_supported(method, layers, x_dim, z_dim, T, B, kernel="auto", ac
     substeps > 1: K0 + K5 in their sub-step builds on kernel "auto" / "generic" (K5's answers for its fit), the same teacher-forcing rule.
     externals="linear": K0 + K5 in their linear-externals builds for every substeps >= 1, the same rules.
     per_trajectory=True (a call WITH events): K0 + K5 in their per-trajectory builds for every substeps >= 1, the same rules; never
-    together with externals="linear"."""
-    opts = fused.GenericOpts.of(method, (act,), substeps, externals, bool(per_trajectory))
+    together with externals="linear".
+    segment (an int >= 1): K0 + K5 in their multiple-shooting builds for every substeps >= 1; never teacher-forced, never together with
+    externals="linear" or per-trajectory events."""
+    opts = fused.GenericOpts.of(method, (act,), substeps, externals, bool(per_trajectory), segment)
     if opts.family != "plain":
         return _generic_only_training(opts, kernel, input_true_x) and fused.ode_backward_supported(
-            method, layers, x_dim, z_dim, kernel, act=act, substeps=substeps, externals=externals, per_trajectory=per_trajectory)
+            method, layers, x_dim, z_dim, kernel, act=act, substeps=substeps, externals=externals, per_trajectory=per_trajectory,
+            segment=segment)
     if input_true_x:
         if kernel in ("auto", "mfma") and fused.ode_backward_supported(method, layers, x_dim, z_dim, "wide"):
             return True
@@ -79,21 +82,22 @@ def _dae_tf_on_k7f(method, kernel, de, ae, x_dim, z_dim, v_dim, i_dim) -> bool:
 
 
 def dae_training_supported(method, de, ae, x_dim, z_dim, v_dim, i_dim, T, B, act=None, kernel="auto", input_true_x=False,
-                           input_true_i=False, substeps=1, externals="hold", per_trajectory=False) -> bool:
+                           input_true_i=False, substeps=1, externals="hold", per_trajectory=False, segment=None) -> bool:
     """act: None (both MLPs ELU(1)) or (de_act, ae_act); an activation other than ELU(1) trains on K0 + K5 alone, so K5 answers.
     input_true_x / input_true_i: teacher-forced training (T >= 2, ELU(1) only) -- K7f's recompute form on kernel "auto" / "mfma" where the
     shape is its, else K5 on "auto" / "generic".  method a fused.Tableau: K0 + K5 on kernel "auto" / "generic", the same rules.
     substeps > 1: K0 + K5 in their sub-step builds on kernel "auto" / "generic", the same rules.
     externals="linear": K0 + K5 in their linear-externals builds for every substeps >= 1, the same rules.
-    per_trajectory=True (a call WITH events): K0 + K5 in their per-trajectory builds for every substeps >= 1, the same rules."""
-    opts = fused.GenericOpts.of(method, fused.dae_acts(act), substeps, externals, bool(per_trajectory))
+    per_trajectory=True (a call WITH events): K0 + K5 in their per-trajectory builds for every substeps >= 1, the same rules.
+    segment (an int >= 1): K0 + K5 in their multiple-shooting builds, as ode_training_supported."""
+    opts = fused.GenericOpts.of(method, fused.dae_acts(act), substeps, externals, bool(per_trajectory), segment)
     teacher_forced = input_true_x or input_true_i
     if opts.family != "plain":
         if opts.family == "act":      # (an activation alone: asked without the caller's kernel, as the ELU(1) call at the bottom is)
             kernel = "auto"
         return _generic_only_training(opts, kernel, teacher_forced, T) and fused.dae_backward_supported(
             method, de, ae, x_dim, z_dim, v_dim, i_dim, act=act, kernel=kernel, substeps=substeps, externals=externals,
-            per_trajectory=per_trajectory)
+            per_trajectory=per_trajectory, segment=segment)
     if teacher_forced:
         if T < 2:
             return False
@@ -335,8 +339,35 @@ class _FusedOdeAbPev(_FusedOdeSub):
     forward = _ode_sub_forward("hold", True)
 
 
+class _FusedOdeMs(torch.autograd.Function):
+    """integrate_ODE with segment=w (multiple shooting), every substeps >= 1: K0 forward and K5 backward in their multiple-shooting builds.
+    x_data: the detached dataset rows the restarts read, [T, B, xd] with row 0 the start of the call ([1, B, xd] where no step restarts);
+    it gets no gradient, x0 gets segment 0's."""
+
+    @staticmethod
+    def forward(ctx, method, kernel, act, substeps, segment, event_idx, t, x0, x_data, z, all_initial, z_jump, *params):
+        global last_saved_bytes
+        xs, x_sub = fused.ode_integrate(method, _layers(params), t, x_data, z, all_initial, z_jump=z_jump, event_idx=event_idx, kernel=kernel,
+                                        act=act, substeps=substeps, save_sub=True, segment=segment)
+        last_saved_bytes = x_sub.numel() * x_sub.element_size()
+        ctx.method, ctx.kernel, ctx.act, ctx.substeps, ctx.segment, ctx.event_idx = method, kernel, act, substeps, segment, event_idx
+        ctx.save_for_backward(*_pack(ctx, (t, z, all_initial, xs, x_sub, x_data), dict(z_jump=z_jump), params))
+        return xs
+
+    @staticmethod
+    def backward(ctx, grad_xs):
+        (t, z, a0, xs, x_sub, x_data), opt, params = _unpack(ctx, 6)
+        need_z = _needs(ctx, _FusedOdeMs, "z")
+        gx0, gz, gzj, ga0, gpar = fused.ode_backward(ctx.method, _layers(params), t, z, a0, xs, grad_xs, event_idx=ctx.event_idx, z_jump=opt["z_jump"],
+                                                     need_grad_z=need_z, need_grad_zj=_needs(ctx, _FusedOdeMs, "z_jump"), kernel=ctx.kernel,
+                                                     act=ctx.act, substeps=ctx.substeps, x_sub=x_sub, segment=ctx.segment, x_true=x_data)
+        if gz is None and need_z:
+            gz = torch.zeros_like(z)
+        return _grad_tuple(ctx, _FusedOdeMs, dict(x0=gx0, z=gz, all_initial=ga0, z_jump=gzj), gpar)
+
+
 def fused_ode_integrate(method, kernel, layers, t, x, z, all_initial, event_t=None, z_jump=None, check_events=False, input_true_x=False,
-                        x_init=None, act=None, substeps=1, externals="hold", per_trajectory=False):
+                        x_init=None, act=None, substeps=1, externals="hold", per_trajectory=False, segment=None):
     """Differentiable fused integrate_ODE: gradients flow to x[0], z, all_initial, z_jump and the MLP.  input_true_x (teacher forcing,
     my_solvers.py:72-74): every step starts from the dataset row x[k]; gradients flow to z, all_initial, z_jump and the MLP (the dataset
     x gets none: callers whose x requires grad take the callback walk).  act: the MLP's activation (fused.Act), None = ELU(1); any other
@@ -348,6 +379,15 @@ def fused_ode_integrate(method, kernel, layers, t, x, z, all_initial, event_t=No
         z_jump = None
     params = [p for wb in layers for p in wb]
     x0 = x.detach() if input_true_x else (x[0] if x_init is None else x_init)     # (x_init: integrate_ODE's extension -- no SelectBackward)
+    if segment is not None:      # multiple shooting: the dataset rows get no gradient (a caller whose x requires grad and restarts walks)
+        pev = bool(per_trajectory) and event_idx is not None
+        fused.GenericOpts.of(method, (act,), substeps, externals, pev, segment).require_generic("fused_ode_integrate", kernel, False,
+                                                                                              bool(input_true_x))
+        if t.shape[0] - 1 > segment:
+            x_data = x.detach() if x_init is None else torch.cat((x_init.detach().unsqueeze(0), x.detach()[1:]))
+        else:
+            x_data = x0.detach().unsqueeze(0)
+        return _FusedOdeMs.apply(method, kernel, act, substeps, segment, event_idx, t, x0, x_data, z, all_initial, z_jump, *params)
     if fused.is_ab(method):
         pev = bool(per_trajectory) and event_idx is not None
         fused.GenericOpts.of(method, (act,), substeps, externals, pev).require_generic("fused_ode_integrate", kernel, False, bool(input_true_x))
@@ -489,9 +529,35 @@ class _FusedDaeAbPev(_FusedDaeSub):
     forward = _dae_sub_forward("hold", True)
 
 
+class _FusedDaeMs(torch.autograd.Function):
+    """integrate_DAE with segment=w (multiple shooting), every substeps >= 1: K0 forward and K5 backward in their multiple-shooting builds.
+    x: the detached dataset rows [T, B, xd] the restarts read; they get no gradient, x_init gets segment 0's."""
+
+    @staticmethod
+    def forward(ctx, method, kernel, act, substeps, segment, event_idx, n_de, t, x_init, x, z, v, i, all_initial, z_jump, v_jump, *params):
+        de, ae = _layers(params, n_de)
+        non_elu = act is not None and any(a is not None for a in act)
+        xs, is_, x_sub = fused.dae_integrate(method, de, ae, x_init, t, x, z, v, i, all_initial, z_jump=z_jump, v_jump=v_jump, event_idx=event_idx,
+                                             kernel=kernel, act=act if non_elu else None, substeps=substeps, save_sub=True, segment=segment)
+        global last_saved_bytes
+        last_saved_bytes = x_sub.numel() * x_sub.element_size()
+        ctx.method, ctx.kernel, ctx.act, ctx.substeps, ctx.segment = method, kernel, act if non_elu else None, substeps, segment
+        ctx.n_de, ctx.event_idx = n_de, event_idx
+        ctx.save_for_backward(*_pack(ctx, (t, z, v, all_initial, xs, is_, x_sub, x), dict(z_jump=z_jump, v_jump=v_jump), params))
+        return xs, is_
+
+    @staticmethod
+    def backward(ctx, grad_xs, grad_is):
+        (t, z, v, a0, xs, is_, x_sub, x), opt, params = _unpack(ctx, 8)
+        de, ae = _layers(params, ctx.n_de)
+        g = fused.dae_backward(ctx.method, de, ae, t, z, v, a0, xs, is_, grad_xs, grad_is, act=ctx.act, event_idx=ctx.event_idx,
+                               kernel=ctx.kernel, substeps=ctx.substeps, x_sub=x_sub, segment=ctx.segment, x_true=x, **opt)
+        return _dae_grads(ctx, _FusedDaeMs, g, z, v)
+
+
 def fused_dae_integrate(method, kernel, de_layers, ae_layers, x_init, t, z, v, i, all_initial, event_t=None, z_jump=None, v_jump=None,
                         check_events=False, x=None, input_true_x=False, input_true_i=False, act=None, substeps=1, externals="hold",
-                        per_trajectory=False):
+                        per_trajectory=False, segment=None):
     """Differentiable fused integrate_DAE: gradients flow to x_init, z, v, all_initial, the jump inputs and both MLPs.  Without teacher
     forcing `i` only provides the width of the algebraic variable.  input_true_x / input_true_i: `x` / `i` are the dataset rows the DE
     and the heads are fed (my_solvers.py:111-121); they get no gradient.  act: None or (de_act, ae_act) (fused.Act, None = ELU(1)); an
@@ -505,6 +571,13 @@ def fused_dae_integrate(method, kernel, de_layers, ae_layers, x_init, t, z, v, i
         v_jump = v_jump if (v_jump is not None and v_jump.shape[-1] > 0) else None
     params = [p for wb in list(de_layers) + list(ae_layers) for p in wb]
     pev = bool(per_trajectory) and event_idx is not None
+    if segment is not None:      # multiple shooting: `x` is the dataset rows the restarts read; they get no gradient
+        fused.GenericOpts.of(method, fused.dae_acts(act), substeps, externals, pev, segment).require_generic(
+            "fused_dae_integrate", kernel, False, bool(input_true_x or input_true_i))
+        if x is None or x.shape[-1] == 0:
+            raise ValueError(f"fused_dae_integrate: segment={segment} restarts from the dataset rows x[k]; this call has none")
+        return _FusedDaeMs.apply(method, kernel, act, substeps, segment, event_idx, len(de_layers), t, x_init, x.detach(), z, v, i.detach(),
+                                 all_initial, z_jump, v_jump, *params)
     if fused.is_ab(method):
         fused.GenericOpts.of(method, fused.dae_acts(act), substeps, externals, pev).require_generic(
             "fused_dae_integrate", kernel, False, bool(input_true_x or input_true_i))

@@ -291,5 +291,8 @@ hipError_t launch_generic_pev(const IntegrateDev& a, bool dae, const ActPair& ac
 // psnode_generic_ab.hip: two-step Adams-Bashforth on the per-trajectory build's policy; rk is the one-stage tableau, a.ev may be null
 hipError_t launch_generic_ab(const IntegrateDev& a, bool dae, const ActPair& act, const psnode_rk_tableau_f32& rk, const AbDev& ab,
                              hipStream_t stream);
+// psnode_generic_ms.hip: the sub-step build (ms.n >= 1) with multiple-shooting restarts from the rows of a.x, which then has all T of them
+hipError_t launch_generic_ms(const IntegrateDev& a, bool dae, const ActPair& act, const psnode_rk_tableau_f32& rk, const MsDev& ms,
+                             hipStream_t stream);
 
 }  // namespace psnode

@@ -89,6 +89,7 @@ GenericBwdCall generic_bwd_call(const psnode_dae_bwd_args_f32& a) {
 }
 // act: the activations of a non-ELU(1) call, or nullptr
 int generic_backward(const GenericBwdCall& c, const ActPair* act, void* workspace, void* stream) {
+    if (c.rk && c.ms_every > 0) return generic_backward_launch<BuildMs>(c, act, static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
     if (c.rk && c.ab) return generic_backward_launch<BuildAb>(c, act, static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
     if (c.rk && c.pev) return generic_backward_launch<BuildPev>(c, act, static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
     if (c.rk && c.lin) return generic_backward_launch<BuildLin>(c, act, static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
@@ -209,7 +210,7 @@ extern "C" int32_t psnode_dae_backward_f32(const psnode_dae_bwd_args_f32* a, voi
     return generic_backward(generic_bwd_call(*a), nullptr, workspace, stream);
 }
 
-// ---- The K5 entry-point families psnode_dae_backward_tf_* and psnode_{ode,dae}_backward_{act,rk,sub,lin,pev,ab}_*: one checked call path
+// ---- The K5 entry-point families psnode_dae_backward_tf_* and psnode_{ode,dae}_backward_{act,rk,sub,lin,pev,ab,ms}_*: one checked call path
 // (k5_backward), one query (k5_supported).  Order of checks per family, which is the order of the statuses of a call that is wrong in
 // several ways:
 //
@@ -223,12 +224,15 @@ extern "C" int32_t psnode_dae_backward_f32(const psnode_dae_bwd_args_f32* a, voi
 //   _pev   as _lin; event_idx -- here the [T-1, B] table -- is one of the pointers (NULL: PSNODE_ERR_NULL, event-less calls take the
 //          other families)
 //   _ab    act pair | NULL args | T, B | route (and no teacher-forcing flag) | pointers (event_idx may be NULL) | workspace   (`method` is not read)
+//   _ms    segments struct (NULL: PSNODE_ERR_NULL; every < 1: PSNODE_ERR_DIMS) | then as _lin; the route refuses every teacher-forcing flag;
+//          x_true is one of the pointers where a step restarts (T - 1 > every)
 //   T, B: a DAE call with flags needs T >= 2.  Route (k5_route_ok): kernel AUTO / GENERIC, no saved_* rows, flags within the struct's and
 //   only next to an ELU(1) pair, the recipe dims and the LDS fit of the family's build.  Pointers: the teacher-forcing rows among them.
 //   The DAE's _act family takes psnode_dae_bwd_args_f32, the others the _tf struct: its _sub with substeps == 1 and no tableau goes to _tf
 //   (ELU(1) pair) or refuses flags (PSNODE_ERR_UNSUPPORTED, before the method is looked at) and goes to _act with the base args.
 namespace {
-enum K5Family { kFamTf, kFamAct, kFamRk, kFamSub, kFamLin, kFamPev, kFamAb };
+enum K5Family { kFamTf, kFamAct, kFamRk, kFamSub, kFamLin, kFamPev, kFamAb, kFamMs };
+int segments_check(const psnode_segments_f32* seg) { return !seg ? PSNODE_ERR_NULL : seg->every < 1 ? PSNODE_ERR_DIMS : PSNODE_OK; }
 constexpr uint32_t kTfFlags = PSNODE_FLAG_INPUT_TRUE_X | PSNODE_FLAG_INPUT_TRUE_I;
 
 // the difference between the three args structs: the base call, the flags and the ones the struct knows, the AE, the plain entry points
@@ -274,7 +278,7 @@ bool k5_route_ok(K5Family fam, const Args& a, const ActPair& p, bool elu1, bool 
     const uint32_t flags = tf_flags(a);
     if (b.kernel != PSNODE_KERNEL_AUTO && b.kernel != PSNODE_KERNEL_GENERIC) return false;
     if ((flags & ~tf_mask(a)) || (flags && !elu1)) return false;      // (teacher forcing: ELU(1) only)
-    if (fam == kFamAb && flags) return false;                         // (a multistep history has no teacher-forced form)
+    if ((fam == kFamAb || fam == kFamMs) && flags) return false;      // (_ab: a multistep history has no teacher-forced form; _ms: every teacher-forced step restarts already)
     if (saved_rows(b, fam != kFamAct ? kSavedAll : query ? kSavedAct : kSavedActCall)) return false;
     // the fit of the build: _tf runs the ELU(1) build, _act the act or the pre build, the others keep the pre-activations for every kind
     const bool pre = fam == kFamAct ? act_pair_keeps_u(p) : fam != kFamTf;
@@ -282,7 +286,7 @@ bool k5_route_ok(K5Family fam, const Args& a, const ActPair& p, bool elu1, bool 
 }
 // the struct of a _sub / _lin / _pev call; substeps == 1 on _sub is the family without sub-steps
 int k5_substeps(K5Family& fam, const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub) {
-    if (fam != kFamSub && !((fam == kFamLin || fam == kFamPev) && sub)) return PSNODE_OK;
+    if (fam != kFamSub && !((fam == kFamLin || fam == kFamPev || fam == kFamMs) && sub)) return PSNODE_OK;
     const int rc = substeps_check(sub);
     if (rc == PSNODE_OK && fam == kFamSub && sub->substeps == 1) fam = tab ? kFamRk : kFamAct;
     return rc;
@@ -290,12 +294,15 @@ int k5_substeps(K5Family& fam, const psnode_rk_tableau_f32* tab, const psnode_su
 
 template <class Args>
 int k5_backward(K5Family fam, const Args* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act, const psnode_rk_tableau_f32* tab,
-                const psnode_substeps_f32* sub, void* workspace, size_t workspace_bytes, void* stream, int ev_pt = 0) {
+                const psnode_substeps_f32* sub, void* workspace, size_t workspace_bytes, void* stream, int ev_pt = 0,
+                const psnode_segments_f32* seg = nullptr) {
     constexpr bool tf_struct = std::is_same<Args, psnode_dae_bwd_tf_args_f32>::value;
     ActPair p;
     psnode_rk_tableau_f32 t;
     bool elu1 = true;
-    int rc = k5_substeps(fam, tab, sub);
+    int rc = fam == kFamMs ? segments_check(seg) : PSNODE_OK;
+    if (rc) return rc;
+    rc = k5_substeps(fam, tab, sub);
     if (rc == PSNODE_OK) rc = act_pair(de_act, ae_act, p, elu1);
     if (rc) return rc;
     if (fam == kFamAct && elu1) return backward_elu1(a, workspace, workspace_bytes, stream);
@@ -316,19 +323,22 @@ int k5_backward(K5Family fam, const Args* a, const psnode_act_f32* de_act, const
     if (!k5_route_ok(fam, *a, p, elu1, false)) return PSNODE_ERR_UNSUPPORTED;
     const int nsub = fam >= kFamSub && sub ? sub->substeps : 1;
     if (!ptrs_ok(a) || (nsub > 1 && b.T >= 2 && !sub->x_sub) || (fam == kFamPev && !b.event_idx)) return PSNODE_ERR_NULL;
+    if (fam == kFamMs && b.T - 1 > seg->every && !seg->x_true) return PSNODE_ERR_NULL;
     if (!workspace_ok(workspace, workspace_bytes, generic_bwd_workspace_floats(&b.de, ae_of(b), b.B) * sizeof(float))) return PSNODE_ERR_WORKSPACE;
     GenericBwdCall c = generic_bwd_call(*a);
     if (fam >= kFamRk) c.rk = &t;
     if (fam >= kFamSub) { c.substeps = nsub; c.x_sub = sub ? sub->x_sub : nullptr; c.lin = fam == kFamLin; c.pev = fam == kFamPev; c.ab = fam == kFamAb; c.ab_pt = ev_pt != 0; }
+    if (fam == kFamMs) { c.ms_every = seg->every; c.ms_x_true = seg->x_true; }
     return generic_backward(c, fam == kFamTf ? nullptr : &p, workspace, stream);
 }
 
 template <class Args>
 int k5_supported(K5Family fam, const Args* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act, const psnode_rk_tableau_f32* tab,
-                 const psnode_substeps_f32* sub) {
+                 const psnode_substeps_f32* sub, const psnode_segments_f32* seg = nullptr) {
     ActPair p;
     psnode_rk_tableau_f32 t;
     bool elu1 = true;
+    if (fam == kFamMs && segments_check(seg)) return 0;
     if (!a || k5_substeps(fam, tab, sub) || act_pair(de_act, ae_act, p, elu1)) return 0;
     if (fam == kFamAct && elu1) return supported_elu1(a);
     if constexpr (std::is_same<Args, psnode_dae_bwd_tf_args_f32>::value) {
@@ -486,4 +496,26 @@ extern "C" int32_t psnode_dae_backward_ab_supported(const psnode_dae_bwd_tf_args
 extern "C" int32_t psnode_dae_backward_ab_f32(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
                                               int32_t per_trajectory, void* workspace, size_t workspace_bytes, void* stream) {
     return k5_backward(kFamAb, a, de_act, ae_act, nullptr, nullptr, workspace, workspace_bytes, stream, per_trajectory);
+}
+
+// (multiple shooting: the step that leaves grid point k > 0 with k % seg->every == 0 started from seg->x_true[k])
+extern "C" int32_t psnode_ode_backward_ms_supported(const psnode_ode_bwd_args_f32* a, const psnode_act_f32* de_act,
+                                                    const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub,
+                                                    const psnode_segments_f32* seg) {
+    return k5_supported(kFamMs, a, de_act, nullptr, tab, sub, seg);
+}
+extern "C" int32_t psnode_ode_backward_ms_f32(const psnode_ode_bwd_args_f32* a, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
+                                              const psnode_substeps_f32* sub, const psnode_segments_f32* seg, void* workspace,
+                                              size_t workspace_bytes, void* stream) {
+    return k5_backward(kFamMs, a, de_act, nullptr, tab, sub, workspace, workspace_bytes, stream, 0, seg);
+}
+extern "C" int32_t psnode_dae_backward_ms_supported(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act,
+                                                    const psnode_act_f32* ae_act, const psnode_rk_tableau_f32* tab,
+                                                    const psnode_substeps_f32* sub, const psnode_segments_f32* seg) {
+    return k5_supported(kFamMs, a, de_act, ae_act, tab, sub, seg);
+}
+extern "C" int32_t psnode_dae_backward_ms_f32(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                              const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, const psnode_segments_f32* seg,
+                                              void* workspace, size_t workspace_bytes, void* stream) {
+    return k5_backward(kFamMs, a, de_act, ae_act, tab, sub, workspace, workspace_bytes, stream, 0, seg);
 }

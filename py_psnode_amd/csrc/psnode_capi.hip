@@ -80,11 +80,12 @@ __global__ void event_table_kernel(long long n_steps, const float* clock, long l
 // What a K0 call carries beyond its args: the build of the generic kernel that runs it (psnode_generic_build.h) and that build's kernel
 // arguments.  The plain entry points pass K0Call{}: ELU(1), the args' method, one step per interval -- the only call the MFMA kernels take.
 struct K0Call {
-    enum Build { kElu1, kAct, kRk, kSub, kLin, kPev, kAb } build;      // kAct: the act or the pre build, by the pair's kinds
+    enum Build { kElu1, kAct, kRk, kSub, kLin, kPev, kAb, kMs } build;      // kAct: the act or the pre build, by the pair's kinds
     ActPair act;                   // every build but kElu1
     psnode_rk_tableau_f32 rk;      // kRk, kSub, kLin: given, or the args' method written as one (sub_tableau)
     SubDev sub;                    // kSub, kLin, kPev: sub-steps per grid interval and x_sub
     int ev_pt;                     // kAb: the event table is [T-1, B] (else the shared [T-1], or none)
+    int ms_every;                  // kMs: grid point k > 0 with k % ms_every == 0 restarts from row k of the args' x
 };
 
 int dispatch(IntegrateDev& d, bool dae, int kernel, const psnode_mlp_f32* de, const psnode_mlp_f32* ae, void* workspace,
@@ -116,6 +117,7 @@ int dispatch(IntegrateDev& d, bool dae, int kernel, const psnode_mlp_f32* de, co
         case K0Call::kLin: e = launch_generic_lin(d, dae, call.act, call.rk, call.sub, stream); break;
         case K0Call::kPev: e = launch_generic_pev(d, dae, call.act, call.rk, call.sub, stream); break;
         case K0Call::kAb: e = launch_generic_ab(d, dae, call.act, call.rk, AbDev{1, nullptr, call.ev_pt}, stream); break;
+        case K0Call::kMs: e = launch_generic_ms(d, dae, call.act, call.rk, MsDev{call.sub.n, call.sub.x_sub, call.ms_every, nullptr}, stream); break;
     }
     return ok_or_hip(e);
 }
@@ -203,7 +205,7 @@ int fill_dae(const psnode_dae_args_f32* a, IntegrateDev& d) {
     return PSNODE_OK;
 }
 
-// ---- The K0 entry-point families psnode_{ode,dae}_integrate_{act,rk,sub,lin,pev,ab}_*: one checked call path (k0_integrate) and one query
+// ---- The K0 entry-point families psnode_{ode,dae}_integrate_{act,rk,sub,lin,pev,ab,ms}_*: one checked call path (k0_integrate) and one query
 // (k0_supported).  Order of checks per family, which is the order of the statuses of a call that is wrong in several ways:
 //
 //   _act   act pair | ELU(1) pair -> the plain entry point | NULL args | route (kernel, save_act alone) | fill_* (method, dims, pointers)
@@ -213,9 +215,12 @@ int fill_dae(const psnode_dae_args_f32* a, IntegrateDev& d) {
 //   _lin   struct (NULL: one sub-step) | act pair | NULL args | tableau (as _sub) | route | fill_*
 //   _pev   as _lin, then event_idx -- here the [T-1, B] table -- (NULL: PSNODE_ERR_NULL, event-less calls take the other families)
 //   _ab    act pair | NULL args | route (kernel, every save_*, no teacher-forcing flag) | fill_* (`method` is not read; event_idx may be NULL)
+//   _ms    segments struct (NULL: PSNODE_ERR_NULL; every < 1: PSNODE_ERR_DIMS) | then as _lin; the route also refuses every teacher-forcing
+//          flag and a DAE whose x view is empty (the restarts read its rows)
 //   then dispatch: workspace | T, B | LDS fit of the build.
 // _act_supported with an ELU(1) pair answers from method and dims alone (the plain entry point picks its own kernel).
-enum K0Family { kFamAct, kFamRk, kFamSub, kFamLin, kFamPev, kFamAb };
+enum K0Family { kFamAct, kFamRk, kFamSub, kFamLin, kFamPev, kFamAb, kFamMs };
+int segments_check(const psnode_segments_f32* seg) { return !seg ? PSNODE_ERR_NULL : seg->every < 1 ? PSNODE_ERR_DIMS : PSNODE_OK; }
 
 // the ODE / DAE difference: the side outputs, the recipe widths, fill_*, the AE, the plain entry point
 bool side_outputs(const psnode_ode_args_f32& a) { return a.save_act || a.save_xstage; }
@@ -232,6 +237,8 @@ int fill(const psnode_ode_args_f32* a, IntegrateDev& d) { return fill_ode(a, d);
 int fill(const psnode_dae_args_f32* a, IntegrateDev& d) { return fill_dae(a, d); }
 const psnode_mlp_f32* ae_of(const psnode_ode_args_f32&) { return nullptr; }
 const psnode_mlp_f32* ae_of(const psnode_dae_args_f32& a) { return &a.ae; }
+bool has_dataset_x(const psnode_ode_args_f32&) { return true; }      // (fill_ode requires the pointer)
+bool has_dataset_x(const psnode_dae_args_f32& a) { return a.x.ptr != nullptr; }
 int integrate_elu1(const psnode_ode_args_f32* a, void* ws, size_t bytes, void* stream) { return psnode_ode_integrate_f32(a, ws, bytes, stream); }
 int integrate_elu1(const psnode_dae_args_f32* a, void* ws, size_t bytes, void* stream) { return psnode_dae_integrate_f32(a, ws, bytes, stream); }
 
@@ -240,11 +247,12 @@ template <class Args>
 bool k0_route_ok(K0Family fam, const Args& a) {
     if (a.kernel != PSNODE_KERNEL_AUTO && a.kernel != PSNODE_KERNEL_GENERIC) return false;
     if (fam == kFamAb && (a.flags & (PSNODE_FLAG_INPUT_TRUE_X | PSNODE_FLAG_INPUT_TRUE_I))) return false;      // (a multistep history has no teacher-forced form)
+    if (fam == kFamMs && ((a.flags & (PSNODE_FLAG_INPUT_TRUE_X | PSNODE_FLAG_INPUT_TRUE_I)) || side_outputs(a) || !has_dataset_x(a))) return false;      // (every teacher-forced step restarts already; the restarts read x)
     return fam == kFamAct ? !a.save_act : !side_outputs(a);
 }
 // the struct of a _sub / _lin / _pev call; substeps == 1 on _sub is the family without sub-steps
 int k0_substeps(K0Family& fam, const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub) {
-    if (fam != kFamSub && !((fam == kFamLin || fam == kFamPev) && sub)) return PSNODE_OK;
+    if (fam != kFamSub && !((fam == kFamLin || fam == kFamPev || fam == kFamMs) && sub)) return PSNODE_OK;
     const int rc = substeps_check(sub);
     if (rc == PSNODE_OK && fam == kFamSub && sub->substeps == 1) fam = tab ? kFamRk : kFamAct;
     return rc;
@@ -252,10 +260,13 @@ int k0_substeps(K0Family& fam, const psnode_rk_tableau_f32* tab, const psnode_su
 
 template <class Args>
 int k0_integrate(K0Family fam, const Args* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act, const psnode_rk_tableau_f32* tab,
-                 const psnode_substeps_f32* sub, void* workspace, size_t workspace_bytes, void* stream, int ev_pt = 0) {
+                 const psnode_substeps_f32* sub, void* workspace, size_t workspace_bytes, void* stream, int ev_pt = 0,
+                 const psnode_segments_f32* seg = nullptr) {
     K0Call call{};
     bool elu1 = true;
-    int rc = k0_substeps(fam, tab, sub);
+    int rc = fam == kFamMs ? segments_check(seg) : PSNODE_OK;
+    if (rc) return rc;
+    rc = k0_substeps(fam, tab, sub);
     if (rc == PSNODE_OK) rc = act_pair(de_act, ae_act, call.act, elu1);
     if (rc) return rc;
     if (fam == kFamAct && elu1) return integrate_elu1(args, workspace, workspace_bytes, stream);
@@ -273,8 +284,9 @@ int k0_integrate(K0Family fam, const Args* args, const psnode_act_f32* de_act, c
     rc = fill(&c, d);
     if (rc) return rc;
     if (fam == kFamPev && !d.ev) return PSNODE_ERR_NULL;
-    call.build = fam == kFamAct ? K0Call::kAct : fam == kFamRk ? K0Call::kRk : fam == kFamSub ? K0Call::kSub : fam == kFamLin ? K0Call::kLin : fam == kFamPev ? K0Call::kPev : K0Call::kAb;
+    call.build = fam == kFamAct ? K0Call::kAct : fam == kFamRk ? K0Call::kRk : fam == kFamSub ? K0Call::kSub : fam == kFamLin ? K0Call::kLin : fam == kFamPev ? K0Call::kPev : fam == kFamAb ? K0Call::kAb : K0Call::kMs;
     call.ev_pt = ev_pt ? 1 : 0;
+    call.ms_every = seg ? seg->every : 0;
     call.sub = SubDev{sub ? sub->substeps : 1, sub ? sub->x_sub : nullptr};
     return dispatch(d, ae_of(c) != nullptr, c.kernel, &c.de, ae_of(c), workspace, workspace_bytes, static_cast<hipStream_t>(stream), call);
 }
@@ -282,10 +294,11 @@ int k0_integrate(K0Family fam, const Args* args, const psnode_act_f32* de_act, c
 // the same checks from the dims alone, and the LDS fit of the family's build
 template <class Args>
 int k0_supported(K0Family fam, const Args* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act, const psnode_rk_tableau_f32* tab,
-                 const psnode_substeps_f32* sub) {
+                 const psnode_substeps_f32* sub, const psnode_segments_f32* seg = nullptr) {
     ActPair p;
     psnode_rk_tableau_f32 t;
     bool elu1 = true;
+    if (fam == kFamMs && segments_check(seg)) return 0;
     if (!a || k0_substeps(fam, tab, sub) || act_pair(de_act, ae_act, p, elu1)) return 0;
     if (fam == kFamAct ? (a->method < PSNODE_EULER || a->method > PSNODE_RK4_38) : (fam == kFamRk && !tab) || sub_tableau(tab, fam == kFamAb ? (int)PSNODE_EULER : a->method, t)) return 0;
     if (!recipe_ok(*a)) return 0;
@@ -528,6 +541,26 @@ int32_t psnode_dae_integrate_ab_supported(const psnode_dae_args_f32* a, const ps
 int32_t psnode_dae_integrate_ab_f32(const psnode_dae_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
                                     int32_t per_trajectory, void* workspace, size_t workspace_bytes, void* stream) {
     return k0_integrate(kFamAb, args, de_act, ae_act, nullptr, nullptr, workspace, workspace_bytes, stream, per_trajectory);
+}
+
+// (multiple shooting: grid point k > 0 with k % seg->every == 0 restarts from row k of the args' x, which then holds all T rows)
+int32_t psnode_ode_integrate_ms_supported(const psnode_ode_args_f32* a, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
+                                          const psnode_substeps_f32* sub, const psnode_segments_f32* seg) {
+    return k0_supported(kFamMs, a, de_act, nullptr, tab, sub, seg);
+}
+int32_t psnode_ode_integrate_ms_f32(const psnode_ode_args_f32* args, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
+                                    const psnode_substeps_f32* sub, const psnode_segments_f32* seg, void* workspace, size_t workspace_bytes,
+                                    void* stream) {
+    return k0_integrate(kFamMs, args, de_act, nullptr, tab, sub, workspace, workspace_bytes, stream, 0, seg);
+}
+int32_t psnode_dae_integrate_ms_supported(const psnode_dae_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                          const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, const psnode_segments_f32* seg) {
+    return k0_supported(kFamMs, a, de_act, ae_act, tab, sub, seg);
+}
+int32_t psnode_dae_integrate_ms_f32(const psnode_dae_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                    const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, const psnode_segments_f32* seg,
+                                    void* workspace, size_t workspace_bytes, void* stream) {
+    return k0_integrate(kFamMs, args, de_act, ae_act, tab, sub, workspace, workspace_bytes, stream, 0, seg);
 }
 
 int32_t psnode_ode_kernel_for(const psnode_ode_args_f32* a) {

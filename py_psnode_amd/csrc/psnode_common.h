@@ -73,6 +73,21 @@ struct AbDev {
 // (the bodies ask through an overload: a discarded `if constexpr` arm of a non-dependent SubDev is still type-checked)
 __host__ __device__ inline int ev_table_pt(const SubDev&) { return 0; }
 __host__ __device__ inline int ev_table_pt(const AbDev& s) { return s.ev_pt; }
+// What the multiple-shooting builds of K0 / K5 take in SubDev's place (psnode_segments_f32, include/psnode_hip.h): the sub-step build's
+// argument plus `every` >= 1 -- grid point k > 0 with k % every == 0 restarts from the dataset row -- and, for K5, those rows x_true
+// [T, B, xd] (K0 reads IntegrateDev::x; null where no step restarts).
+struct MsDev {
+    int n;
+    float* x_sub;
+    int every;
+    const float* x_true;
+};
+__host__ __device__ inline int ev_table_pt(const MsDev&) { return 0; }
+// (asked through overloads for the reason above)
+template <class S> __host__ __device__ inline int ms_every(const S&) { return 0; }
+__host__ __device__ inline int ms_every(const MsDev& s) { return s.every; }
+template <class S> __host__ __device__ inline const float* ms_x_true(const S&) { return nullptr; }
+__host__ __device__ inline const float* ms_x_true(const MsDev& s) { return s.x_true; }
 
 // ELU(alpha=1) with the negative branch at expm1 quality: ATen's CPU kernel (what the reference runs) returns
 // expm1(x) for x <= 0 -- checked bitwise in the build container ("ELU").
@@ -340,6 +355,8 @@ struct GenericBwdCall {
     bool pev;                  // generic_backward_launch<BuildPev> (with rk; substeps >= 1; not with lin): `ev` is the [T-1, B] table of per-trajectory events
     bool ab;                   // generic_backward_launch<BuildAb> (with a one-stage rk; substeps 1): two-step Adams-Bashforth; `ev` is null, the shared
     bool ab_pt;                //   [T-1] table, or -- ab_pt -- the [T-1, B] table
+    int ms_every;              // generic_backward_launch<BuildMs> (with rk; substeps >= 1; not with lin / pev / ab) where > 0: grid point k > 0 with
+    const float* ms_x_true;    //   k % ms_every == 0 restarted from the dataset row ms_x_true[k] ([T, B, xd]; may be null where T - 1 <= ms_every)
 };
 struct ActPair;     // psnode_act.h: the DE's and the AE's activation of a non-ELU(1) call
 size_t generic_bwd_workspace_floats(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, long long B);
@@ -351,7 +368,8 @@ int generic_bwd_fits(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, int xd,
 // every activation kind -- `act` is required, ELU(1) runs as ELU with alpha = 1 -- and c.rk in place of c.method; it keeps the
 // pre-activations like the pre build), BuildSub (the tableau build with c.substeps sub-steps per grid interval, read from c.x_sub), BuildLin
 // (the sub-step build, any c.substeps >= 1, with linearly interpolated externals: c.lin), BuildPev (the sub-step build, any c.substeps >= 1,
-// with per-trajectory events: c.pev, c.ev not null), BuildAb (BuildPev's policy as two-step Adams-Bashforth: c.ab, c.ab_pt).
+// with per-trajectory events: c.pev, c.ev not null), BuildAb (BuildPev's policy as two-step Adams-Bashforth: c.ab, c.ab_pt), BuildMs (the
+// sub-step build, any c.substeps >= 1, with multiple-shooting restarts: c.ms_every, c.ms_x_true).
 // psnode_backward.hip: generic_backward picks among them.
 template <class B>
 int generic_backward_launch(const GenericBwdCall& c, const ActPair* act, float* workspace, hipStream_t stream);

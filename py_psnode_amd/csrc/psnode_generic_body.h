@@ -1,7 +1,7 @@
-// The body of K0's kernel (psnode_generic_impl.h), as text: each of the eight objects writes its own __global__ -- generic_kernel(a),
+// The body of K0's kernel (psnode_generic_impl.h), as text: each of the nine objects writes its own __global__ -- generic_kernel(a),
 // generic_act_kernel(a, act), generic_pre_act_kernel(a, act), generic_rk_kernel(a, act, rk), generic_sub_kernel(a, act, rk, sub),
-// generic_lin_kernel(a, act, rk, sub), generic_pev_kernel(a, act, rk, sub), generic_ab_kernel(a, act, rk, sub: an AbDev) -- and includes
-// this file between its braces.
+// generic_lin_kernel(a, act, rk, sub), generic_pev_kernel(a, act, rk, sub), generic_ab_kernel(a, act, rk, sub: an AbDev),
+// generic_ms_kernel(a, act, rk, sub: an MsDev) -- and includes this file between its braces.
 // Template parameters in scope: DAE, MODE, ML, QM.  Names in scope: a, act (ActPair; NoActPair in the ELU(1) object), rk (read under
 // Bd::rk only) and sub (SubDev, read under Bd::sub only); the objects without one declare an unread one.  The build policy Bd decides the
 // rest with `if constexpr`.
@@ -155,6 +155,12 @@
         evn_v = (a.ev && a.T > 1) ? evp[gb(tid % TB) * ev_sb] : -1;
     }
 
+    // Multiple shooting (Bd::ms): grid point k > 0 with k % every == 0 is a restart point -- the step that leaves it starts from the dataset
+    // row a.x[k] and, in a DAE, feeds the DE the head at that row (the event slot, which then runs without an event too).  Launch-uniform:
+    // ms_cnt counts the steps since the last restart in a scalar register, so no step pays a 64-bit remainder.
+    [[maybe_unused]] int ms_cnt = 0, ms_w = 0;
+    if constexpr (Bd::ms) ms_w = __builtin_amdgcn_readfirstlane(ms_every(sub));
+
     float pz[PF];
     // Linear externals (Bd::lin): stage s of sub-step j reads z | v at theta = (j + c_s) / nsub between the interval's left rows (wl) and the
     // dataset's rows of grid point k + 1 (zvn, which the first stage pass of the interval fills from the look-ahead registers).  th_in: the
@@ -172,6 +178,13 @@
         const int ev = k >= 0 ? (Bd::pev ? evn_v : __builtin_amdgcn_readfirstlane(evn_v)) : -1;
         [[maybe_unused]] bool any_ev = false;
         if constexpr (Bd::pev) any_ev = __builtin_amdgcn_ballot_w64(ev >= 0) != 0;
+        [[maybe_unused]] bool ms_rs = false;      // (Bd::ms) this step leaves a restart point
+        if constexpr (Bd::ms) {
+            if (k >= 0) {
+                ms_rs = ms_cnt == ms_w;      // (k == 0: ms_cnt is 0 and every >= 1)
+                ms_cnt = __builtin_amdgcn_readfirstlane(ms_rs ? 1 : ms_cnt + 1);
+            }
+        }
         if (k >= 0) {
             // ---- this step's inputs (zero-order hold: the left grid point feeds every stage)
             if constexpr (Bd::ab) {
@@ -197,13 +210,17 @@
             if constexpr (Bd::lin) th_in = 0.0f;
             for (int idx = tid; idx < nx; idx += NT) {
                 const int r = idx / TB, c = idx % TB;
-                const float v = true_x ? a.x.p[k * a.x.st + gb(c) * a.x.sb + r] : xcur[idx];
+                const float v = (Bd::ms ? ms_rs : true_x) ? a.x.p[k * a.x.st + gb(c) * a.x.sb + r] : xcur[idx];
                 xsrc[idx] = v;
                 put_x(r, c, v);
+                if constexpr (Bd::ms) {      // (the restart head reads the dataset row, an event's inside a segment the computed state)
+                    if constexpr (DAE) if (ev >= 0 || ms_rs) lds[inAE + qi(r, c)] = v;
+                } else {
                 if constexpr (DAE) if (ev >= 0) lds[inAE + qi(r, c)] = xcur[idx];   // ... and the computed state
+                }
             }
             if constexpr (DAE) {
-                if (ev < 0)
+                if (ev < 0 && !(Bd::ms && ms_rs))
                     for (int idx = tid; idx < id * TB; idx += NT) {
                         const int r = idx / TB, c = idx % TB;
                         put_ext(nzv + r, c, true_i ? a.i.p[k * a.i.st + gb(c) * a.i.sb + r] : icur[idx]);
@@ -230,7 +247,7 @@
         SubIter<Bd::sub> si(k >= 0 ? nsub : 1);
         do {
         const int e_end = (DAE && si.last()) ? nstage + 1 : nstage;
-        for (int e = k < 0 ? nstage + 1 : ((DAE && (si.first() ? (Bd::pev ? any_ev : ev >= 0) : !true_i)) ? 0 : 1); e <= e_end; ++e) {
+        for (int e = k < 0 ? nstage + 1 : ((DAE && (si.first() ? (Bd::pev ? any_ev : (ev >= 0 || (Bd::ms && ms_rs))) : !true_i)) ? 0 : 1); e <= e_end; ++e) {
             const bool is_ae = DAE && (e == 0 || e == nstage + 1);
             const bool ae_next = DAE && e == nstage && (si.last() || !true_i);
             int f;

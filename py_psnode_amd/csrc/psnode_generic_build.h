@@ -1,10 +1,10 @@
-// The build policy of the generic kernels K0 (psnode_generic_impl.h) and K5 (psnode_generic_bwd_impl.h): what separates the eight objects each
+// The build policy of the generic kernels K0 (psnode_generic_impl.h) and K5 (psnode_generic_bwd_impl.h): what separates the nine objects each
 // is compiled into, as constants the language can see.
 #pragma once
 
 namespace psnode {
 
-template <bool ACT, bool PRE, bool RK, bool SUB = false, bool LIN = false, bool PEV = false, bool AB = false>
+template <bool ACT, bool PRE, bool RK, bool SUB = false, bool LIN = false, bool PEV = false, bool AB = false, bool MS = false>
 struct GenericBuild {
     static constexpr bool act = ACT;      // the hidden-layer activation is a kernel argument (ActPair, psnode_act.h), not ELU(1)
     static constexpr bool pre = PRE;      // the hidden layers' pre-activations u are kept next to h (SiLU / GELU / Mish differentiate from u)
@@ -14,6 +14,8 @@ struct GenericBuild {
     static constexpr bool pev = PEV;      // the event table is [T-1, B]: every trajectory jumps at its own steps (needs sub; not with lin)
     static constexpr bool ab = AB;        // two-step Adams-Bashforth: one DE evaluation per step, the previous slope and per-column c0 / c1 (AbDev,
                                           // psnode_common.h; needs pev, whose per-column event index also serves a shared table through a column stride of 0)
+    static constexpr bool ms = MS;        // multiple shooting: every MsDev::every-th grid point restarts from the dataset row (MsDev, psnode_common.h;
+                                          // needs sub; not with lin, pev or ab)
     // K5's waves per SIMD: the fully streamed instances (STR 2) that fitted 256 registers keep two workgroups per CU -- every one of the
     // act build, the ELU(1) build's with the accumulators in LDS, none of the builds that keep u
     static constexpr int two_waves(bool gg, int str) { return PRE ? 1 : (str == 2 && (ACT || !gg) ? 2 : 1); }
@@ -43,5 +45,6 @@ using BuildSub = GenericBuild<true, true, true, true>;      // BuildRk's policy 
 using BuildLin = GenericBuild<true, true, true, true, true>;      // BuildSub's policy with linearly interpolated externals; every substeps >= 1
 using BuildPev = GenericBuild<true, true, true, true, false, true>;      // BuildSub's policy with per-trajectory events; every substeps >= 1
 using BuildAb = GenericBuild<true, true, true, true, false, true, true>;      // BuildPev's policy as Adams-Bashforth 2; one sub-step, a one-stage tableau
+using BuildMs = GenericBuild<true, true, true, true, false, false, false, true>;      // BuildSub's policy with multiple-shooting restarts; every substeps >= 1
 
 }  // namespace psnode

@@ -1,5 +1,5 @@
-// The body of K5's kernel (psnode_generic_bwd_impl.h), as text: each of the eight objects (the eighth: generic_backward_ab_kernel(a, act,
-// rk, sub: an AbDev)) writes its own __global__ --
+// The body of K5's kernel (psnode_generic_bwd_impl.h), as text: each of the nine objects (the eighth: generic_backward_ab_kernel(a, act,
+// rk, sub: an AbDev); the ninth: generic_backward_ms_kernel(a, act, rk, sub: an MsDev)) writes its own __global__ --
 // generic_backward_kernel(a), generic_backward_act_kernel(a, act), generic_backward_pre_act_kernel(a, act),
 // generic_backward_rk_kernel(a, act, rk), generic_backward_sub_kernel(a, act, rk, sub), generic_backward_lin_kernel(a, act, rk, sub),
 // generic_backward_pev_kernel(a, act, rk, sub) -- and includes this file between its braces.
@@ -201,6 +201,16 @@
         if (ev_table_pt(sub)) { ev_sk = a.B; ev_sb = 1; }
         la_tm = a.t.p[(a.T >= 3 ? a.T - 3 : 0) * a.t.st + gb(tid % TB) * a.t.sb];      // (every lane, no branch: see the top of the step; read for k >= 1 only)
     }
+    // Multiple shooting (Bd::ms): the step that leaves grid point k > 0 with k % every == 0 started from the dataset row xtr[k] -- and a
+    // DAE's DE read the head at that row.  Its stages are recomputed from there; neither its start adjoint nor the x part of that head's VJP
+    // travels on.  Launch-uniform: ms_rem is k % every, counted down in a scalar register from one remainder taken in front of the sweep.
+    [[maybe_unused]] int ms_w = 0, ms_rem = 0;
+    [[maybe_unused]] const float* __restrict__ xtr = nullptr;
+    if constexpr (Bd::ms) {
+        ms_w = __builtin_amdgcn_readfirstlane(ms_every(sub));
+        ms_rem = __builtin_amdgcn_readfirstlane((a.T >= 2 && ms_w > 0) ? (int)((a.T - 2) % ms_w) : 0);
+        xtr = ms_x_true(sub);
+    }
     for (long long k = (Bd::ab ? Tu : a.T) - 2; k >= 0; --k) {
         // ev: the event index of this step -- launch-uniform, or (Bd::pev: a [T - 1][B] table, which the host requires) that of this
         // thread's column: every TILE_LOOP and look-ahead item of a thread lies in column tid % TB.  any_ev: some column of the workgroup
@@ -226,6 +236,19 @@
             ev_n = ev;
         } else if constexpr (Bd::sub) { if (tid < TB) dts[tid] = (la_tn - la_t) / (float)nsub; }
         else { if (tid < TB) dts[tid] = la_tn - la_t; }
+        [[maybe_unused]] bool ms_rs = false;         // (Bd::ms) this step left a restart point
+        if constexpr (Bd::ms) {
+            ms_rs = ms_rem == 0 && k > 0;
+            ms_rem = __builtin_amdgcn_readfirstlane(ms_rem == 0 ? ms_w - 1 : ms_rem - 1);
+            if (ms_rs) {      // the look-ahead brought xs[k], the previous segment's prediction: the step started from the dataset row
+#pragma unroll
+                for (int j = 0; j < LA; ++j) {
+                    const int idx = tid + NT * j;
+                    const int ix = idx < xd * TB ? idx : 0;
+                    la_x[j] = xtr[(k * a.B + gb(ix % TB)) * xd + ix / TB];
+                }
+            }
+        }
         float gx_in[LA];                             // the incoming gradient of grid point k, consumed at the bottom of the step
         [[maybe_unused]] float x_keep[LA];           // sub-step build: xs[k] of the look-ahead, for sub-step 0 (x0 holds the later ones' starts first)
 #pragma unroll
@@ -236,7 +259,7 @@
             if (idx < xd * TB) x0[(idx / TB) * TP + idx % TB] = la_x[j];
             if (idx < nzv * TB && ev < 0) ext[(idx / TB) * TP + idx % TB] = la_zv[j];
         }
-        for (int idx = tid + NT * LA; idx < xd * TB; idx += NT) x0[(idx / TB) * TP + idx % TB] = xsrc[(k * a.B + gb(idx % TB)) * xd + idx / TB];
+        for (int idx = tid + NT * LA; idx < xd * TB; idx += NT) x0[(idx / TB) * TP + idx % TB] = ((Bd::ms && ms_rs) ? xtr : xsrc)[(k * a.B + gb(idx % TB)) * xd + idx / TB];
         TILE_LOOP(nzv) {
             if (ev < 0 && idx < NT * LA) continue;                                      // (came through the look-ahead registers)
             const long long b = gb(c);
@@ -282,7 +305,7 @@
                         const int idx = tid + NT * j;
                         if (idx < xd * TB) x0[(idx / TB) * TP + idx % TB] = x_keep[j];
                     }
-                    for (int idx = tid + NT * LA; idx < xd * TB; idx += NT) x0[(idx / TB) * TP + idx % TB] = xsrc[(k * a.B + gb(idx % TB)) * xd + idx / TB];
+                    for (int idx = tid + NT * LA; idx < xd * TB; idx += NT) x0[(idx / TB) * TP + idx % TB] = ((Bd::ms && ms_rs) ? xtr : xsrc)[(k * a.B + gb(idx % TB)) * xd + idx / TB];
                 }
                 if constexpr (Bd::lin) lin_ext(theta(0));      // what the head in front of this sub-step (or the event's) saw
                 __syncthreads();
@@ -299,7 +322,7 @@
             // (2) algebraic input of this step's DE (ti: the dataset row, also on event steps)
             if (ti) {
                 TILE_LOOP(id) ext[(nzv + r) * TP + c] = a.it[(k * a.B + gb(c)) * id + r];
-            } else if ((Bd::pev ? any_ev : ev >= 0) || inner) {
+            } else if ((Bd::pev ? any_ev : (ev >= 0 || (Bd::ms && ms_rs))) || inner) {      // (a restart's head: x0 is the dataset row, ext's z | v rows those of grid point k or the jumped ones)
                 const float* xr = x0;
                 if (tx && !inner) {       // the event-time head reads the RUNNING state xs[k], not the row the DE starts from (xst is free until (3a))
                     TILE_LOOP(xd) xst[r * TP + c] = a.xs[(k * a.B + gb(c)) * xd + r];
@@ -408,6 +431,7 @@
         // tx: the step started from a dataset row -- its start adjoint goes nowhere (an ODE keeps step 0's: grad_x0 = grad_xs[0] + it), and
         // gx0 from here on collects what still reaches the running state xs[k]: the event-time head's x-adjoint
         if (tx && (dae || k > 0)) { TILE_LOOP(xd) gx0[r * TP + c] = 0.0f; }
+        if constexpr (Bd::ms) { if (ms_rs) { TILE_LOOP(xd) gx0[r * TP + c] = 0.0f; } }      // (likewise: gxc becomes gxs[k] alone)
         // (4) gradients of this step's external inputs
         TILE_LOOP(nzv) {
             if (!on(c)) continue;
@@ -430,7 +454,7 @@
             __syncthreads();
             if (ti) {        // the DE read i_true[k]: nothing flows back through the algebraic variable
                 TILE_LOOP(id) gic[r * TP + c] = (on(c) && a.gis) ? a.gis[(k * a.B + gb(c)) * id + r] : 0.0f;
-            } else if (Bd::pev ? any_ev : ev >= 0) {   // i_in = g(x_k; jumps): its gradient flows into x_k and the jump inputs; i_k itself was unused
+            } else if (Bd::pev ? any_ev : (ev >= 0 || (Bd::ms && ms_rs))) {   // i_in = g(x_k; jumps): its gradient flows into x_k and the jump inputs; i_k itself was unused
                 if constexpr (Bd::pev) {
                     // ... in the columns with a hit.  The others fed the DE the i they carried: their adjoint goes on into gic (the arm
                     // below), and their output gradient is ZERO in the head's VJP, so that they add nothing to its weight gradients, to
@@ -447,7 +471,15 @@
                     __syncthreads();
                     xr = xst;
                 }
+                if constexpr (Bd::ms) {
+                    // a restart's head read the dataset row: the x part of its VJP is discarded.  ae_vjp ADDS it to its destination, so it
+                    // is given xst's slot 0 as a sink: the stages are done with xst, which holds this step's stage inputs (finite), and (1) /
+                    // (3a) of the next step rewrite every element before anything reads it.  Without an event its z | v rows are grid point k's, whose gradient rows this thread wrote in (4): the event
+                    // arm's ordering.
+                    ae_vjp(xr, (ms_rs && ev < 0) ? k : -1, ev, gext + nzv * TP, ms_rs ? xst : gx0);
+                } else {
                 ae_vjp(xr, -1, ev, gext + nzv * TP, gx0);
+                }
                 if constexpr (!Bd::pev) { TILE_LOOP(id) gic[r * TP + c] = (on(c) && a.gis) ? a.gis[(k * a.B + gb(c)) * id + r] : 0.0f; }
             } else {
                 TILE_LOOP(id) gic[r * TP + c] = gext[(nzv + r) * TP + c] + ((on(c) && a.gis) ? a.gis[(k * a.B + gb(c)) * id + r] : 0.0f);

@@ -15,7 +15,7 @@
 // Teacher forcing (GBwd::flags) changes the outer sweep only: which rows a step starts from and which adjoints travel to the step before.
 #include <string.h>
 
-// Eight objects are compiled from this header, one per build policy (psnode_generic_build.h).  Each of psnode_generic_bwd{,_act,_pre,_rk,_sub,_lin,_pev,_ab}.hip
+// Nine objects are compiled from this header, one per build policy (psnode_generic_build.h).  Each of psnode_generic_bwd{,_act,_pre,_rk,_sub,_lin,_pev,_ab,_ms}.hip
 // names its policy `Bd` in front of the include, writes its kernel around psnode_generic_bwd_body.h and instantiates the launcher:
 //   BuildElu1  generic_backward_kernel(a)                    ELU(1) and its derivative
 //   BuildAct   generic_backward_act_kernel(a, act)           the DE's and the AE's activation as a second kernel argument (ActPair)
@@ -34,6 +34,9 @@
 //   BuildAb    generic_backward_ab_kernel(a, act, rk, ab)    the per-trajectory build as two-step Adams-Bashforth (one stage, one sub-step; AbDev in
 //              SubDev's place): the DE's VJP takes phi_k = c0_k g_{k+1} + c1_{k+1} g_{k+2}, g_{k+2} and the per-column c1 live in the gks slots a
 //              one-stage build leaves free; the event table is [T-1, B], the shared [T-1] (column stride 0) or null; no LDS of its own
+//   BuildMs    generic_backward_ms_kernel(a, act, rk, ms)    the sub-step build (every n >= 1) with multiple-shooting restarts (MsDev in SubDev's
+//              place): a restart step recomputes from MsDev::x_true[k] and the head at that row, and lets neither its start adjoint nor the
+//              x part of that head's VJP travel on; the restart is a countdown in a scalar; no LDS and no workspace of its own
 // The policy decides in the language: the kernel-argument structs (GMlpT / GBwdT: the pre fields are a base that is empty elsewhere), the
 // activation context ActCtx every device function takes, the stage coefficients (coef_a, coef_b) and
 // `if constexpr` in the kernel body and the launcher.  The host's fit and layout functions take `pre` at run time.
@@ -852,6 +855,7 @@ int generic_backward_launch(const GenericBwdCall& c, const ActPair* act, float* 
     auto go = [&](const auto&... extra) { return launch_attr(true, kern, dim3(nwg), dim3(NT), lds, stream, a, extra...); };
     hipError_t e;
     if constexpr (Pol::ab) e = go(*act, *c.rk, AbDev{1, nullptr, c.ab_pt ? 1 : 0});
+    else if constexpr (Pol::ms) e = go(*act, *c.rk, MsDev{c.substeps, const_cast<float*>(c.x_sub), c.ms_every, c.ms_x_true});
     else if constexpr (Pol::sub) e = go(*act, *c.rk, SubDev{c.substeps, const_cast<float*>(c.x_sub)});
     else if constexpr (Pol::rk) e = go(*act, *c.rk);
     else if constexpr (Pol::act) e = go(*act);

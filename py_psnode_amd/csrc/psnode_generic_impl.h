@@ -25,7 +25,7 @@
 // Padded columns: the image holds zeros there and the input builders write zeros into the pad columns of the first layer's input; a
 // hidden layer's pad units come out of the MFMA as ELU(0 + 0) = 0.
 //
-// Eight objects are compiled from this header, one per build policy (psnode_generic_build.h).  Each of psnode_generic{,_act,_pre,_rk,_sub,_lin,_pev,_ab}.hip
+// Nine objects are compiled from this header, one per build policy (psnode_generic_build.h).  Each of psnode_generic{,_act,_pre,_rk,_sub,_lin,_pev,_ab,_ms}.hip
 // names its policy `Bd` in front of the include, writes its kernel around psnode_generic_body.h and its exported launcher over
 // launch_generic_build:
 //   BuildElu1  generic_kernel(a), launch_generic                    ELU(1)
@@ -44,6 +44,9 @@
 //              sub-step; AbDev in SubDev's place): the final pass forms x + c0 f_k + c1 f_{k-1} with per-column c0 / c1; the previous slope
 //              and c1 live in the kbuf slots a one-stage build never writes; the event table is [T-1, B], the shared [T-1] (column stride
 //              0) or null; no LDS of its own
+//   BuildMs    generic_ms_kernel(a, act, rk, ms), launch_generic_ms   the sub-step build (every n >= 1) with multiple-shooting restarts (MsDev
+//              in SubDev's place): at every MsDev::every-th grid point the step-input pass takes the dataset row of a.x as the step's start
+//              and as the AE input's x, and the event slot runs as the restart head; a countdown in a scalar; no LDS of its own
 // The device functions take the activation as one ordinary parameter, ActCtx; the kernel body chooses the tableau code with
 // `if constexpr (Bd::rk)`, the sub-step code with `if constexpr (Bd::sub)`.  The host's plan / fit / pack code is compiled once, in
 // psnode_generic.hip.

@@ -203,8 +203,10 @@ class GenericOpts:
     refused (`require_generic`, `require_plain`).  acts: one Act | None per MLP (ODE 1, DAE 2); tab: the Tableau of `method`, if it is one;
     method_id / stages: what the args struct and the saved rows need of `method` (`method_info`); per_trajectory: the call's event table
     is [T-1, B], every trajectory jumps at its own steps (only a call that HAS events carries it: `has_events`); ab: the method is two-step
-    Adams-Bashforth ("ab2") -- the sixth and last option in the naming order; never together with a Tableau, sub-steps or interpolated
-    externals (the solver's constructor refuses them; here a ValueError), with per_trajectory it stays the family "ab"."""
+    Adams-Bashforth ("ab2") -- the last option in the naming order; never together with a Tableau, sub-steps or interpolated
+    externals (the solver's constructor refuses them; here a ValueError), with per_trajectory it stays the family "ab"; segment: None, or
+    an int w >= 1 -- multiple shooting, grid point k > 0 with k % w == 0 restarts from the dataset row (the family "ms", the sixth option in
+    the naming order, in front of AB2, which refuses it; next to interpolated externals or per-trajectory events "none": no kernel)."""
     acts: tuple
     tab: Optional[Tableau]
     substeps: int = 1
@@ -212,6 +214,7 @@ class GenericOpts:
     method_id: int = _lib.EULER
     stages: int = 1
     per_trajectory: bool = False
+    segment: Optional[int] = None
     ab: bool = False
     family: str = dataclasses.field(init=False)
 
@@ -225,7 +228,14 @@ class GenericOpts:
             raise ValueError(f"substeps must be an int in 1..{_lib.MAX_SUBSTEPS}, got {self.substeps!r}")
         if not isinstance(self.per_trajectory, bool):
             raise ValueError(f"per_trajectory must be a bool, got {self.per_trajectory!r}")
-        if self.ab:
+        if self.segment is not None and (isinstance(self.segment, bool) or not isinstance(self.segment, int) or self.segment < 1):
+            raise ValueError(f"segment must be None or an int >= 1, got {self.segment!r}")
+        if self.ab and self.segment is not None:
+            raise ValueError("Adams-Bashforth 2 carries the previous slope from step to step: a multiple-shooting restart (segment=) has no "
+                             f"form here (got segment={self.segment!r})")
+        if self.segment is not None:
+            fam = "none" if (is_linear(self.externals) or self.per_trajectory) else "ms"
+        elif self.ab:
             if self.substeps != 1 or is_linear(self.externals) or self.tab is not None:
                 raise ValueError("Adams-Bashforth 2 reads the right-hand side at grid points only: substeps != 1 and externals='linear' would "
                                  f"need inputs between the dataset rows (got substeps={self.substeps}, externals={self.externals!r})")
@@ -244,14 +254,15 @@ class GenericOpts:
 
     @staticmethod
     @functools.lru_cache(maxsize=256, typed=True)      # (a loop asks for the same immutable value call after call; typed: 2.0 and True are not 2 and 1)
-    def of(method, acts: tuple, substeps: int = 1, externals: str = "hold", per_trajectory: bool = False) -> "GenericOpts":
+    def of(method, acts: tuple, substeps: int = 1, externals: str = "hold", per_trajectory: bool = False, segment=None) -> "GenericOpts":
         method_id, stages, tab = method_info(method)
-        return GenericOpts(acts, tab, substeps, externals, method_id, stages, per_trajectory, is_ab(method))
+        return GenericOpts(acts, tab, substeps, externals, method_id, stages, per_trajectory, segment, is_ab(method))
 
-    def c_args(self, x_sub=None) -> list:
+    def c_args(self, x_sub=None, x_true=None) -> list:
         """The family's C arguments behind the args struct: none ("plain"); the acts ("act"); the acts and the tableau ("rk"); the acts,
         the tableau or NULL (= the args' method) and a psnode_substeps_f32 with the sub-state rows `x_sub` or NULL ("sub", "lin", "pev").  The list
-        owns the structs: keep it until the call has returned."""
+        owns the structs: keep it until the call has returned.  "ms": those of "sub" and a psnode_segments_f32 with `segment` and the
+        dataset rows `x_true` of a backward call or NULL."""
         fam = self.family
         if fam == "plain":
             return []
@@ -260,11 +271,16 @@ class GenericOpts:
             return out + [ctypes.c_int32(1 if self.per_trajectory else 0)]
         if fam != "act":
             out.append(ctypes.byref(self.tab.abi()) if self.tab is not None else None)
-        if fam in ("sub", "lin", "pev"):
+        if fam in ("sub", "lin", "pev", "ms"):
             s = _lib.SubstepsF32()
             s.substeps = self.substeps
             s.x_sub = x_sub.data_ptr() if x_sub is not None and x_sub.numel() else None
             out.append(ctypes.byref(s))
+        if fam == "ms":
+            g = _lib.SegmentsF32()
+            g.every = min(self.segment, 0x7fffffff)      # (a segment longer than any record: no restart)
+            g.x_true = x_true.data_ptr() if x_true is not None and x_true.numel() else None
+            out.append(ctypes.byref(g))
         return out
 
     def dae_backward_args(self, rows: bool):
@@ -272,7 +288,7 @@ class GenericOpts:
         "lin" and for a call with dataset rows x_true / i_true ("tf": the family of such a call that would otherwise be "plain"), else
         psnode_dae_bwd_args_f32.  Dataset rows next to a non-ELU act alone: no entry point takes both (`call_generic` asserts it too)."""
         assert not (rows and self.family == "act"), "dae_backward: dataset rows with an activation other than ELU(1) have no entry point"
-        return _lib.DaeBwdTfArgsF32() if rows or self.family in ("rk", "sub", "lin", "pev", "ab") else _lib.DaeBwdArgsF32()
+        return _lib.DaeBwdTfArgsF32() if rows or self.family in ("rk", "sub", "lin", "pev", "ab", "ms") else _lib.DaeBwdArgsF32()
 
     def _first_option(self) -> str:
         """The first option the call carries, in the fixed order act, tableau, sub-steps, externals, as the subject of a refusal."""
@@ -286,6 +302,8 @@ class GenericOpts:
             return "linearly interpolated external inputs (externals='linear') run"
         if self.per_trajectory:
             return "per-trajectory events (per_trajectory=True) run"
+        if self.segment is not None:
+            return f"multiple-shooting segments (segment={self.segment}) run"
         return "two-step Adams-Bashforth (AB2) runs"
 
     def require_generic(self, what: str, kernel: str, saved: bool, teacher_forced: bool = False):
@@ -296,6 +314,11 @@ class GenericOpts:
         if self.family == "plain":
             return
         self.no_teacher_forcing(what, teacher_forced)
+        if self.family == "none" and self.segment is not None:
+            raise _lib.UnsupportedShapeError(f"{what}: multiple-shooting segments (segment={self.segment}) together with "
+                                             + ("linearly interpolated external inputs (externals='linear')" if is_linear(self.externals)
+                                                else "per-trajectory events (per_trajectory=True)")
+                                             + " have no fused form: the multiple-shooting build of K0 / K5 holds the externals and takes the shared event table")
         if self.family == "none":
             raise _lib.UnsupportedShapeError(f"{what}: per-trajectory events (per_trajectory=True) together with linearly interpolated external "
                                              "inputs (externals='linear') have no fused form: K0 / K5 carry either, not both")
@@ -307,7 +330,10 @@ class GenericOpts:
                                              "(kernel 'auto' / 'generic', no saved rows, no teacher forcing)")
 
     def no_teacher_forcing(self, what: str, teacher_forced: bool):
-        """Adams-Bashforth 2 with input_true_x / input_true_i: ValueError, on every path."""
+        """Adams-Bashforth 2, or segments, with input_true_x / input_true_i: ValueError, on every path."""
+        if self.segment is not None and teacher_forced:
+            raise ValueError(f"{what}: segment={self.segment} and input_true_x / input_true_i exclude each other (every teacher-forced step "
+                             "restarts from the dataset already)")
         if self.ab and teacher_forced:
             raise ValueError(f"{what}: Adams-Bashforth 2 has no teacher-forced form -- every teacher-forced step starts from a dataset row, "
                              "so the previous slope a multistep method carries is undefined")
@@ -327,13 +353,16 @@ class GenericOpts:
             raise _lib.UnsupportedShapeError(f"{what}: per-trajectory events (per_trajectory=True) run on the generic kernels K0 / K5 only "
                                              "(kernel 'auto' / 'generic', no saved rows); this entry point jumps the whole batch at the steps "
                                              "of one int32[T-1] table")
+        if self.segment is not None:
+            raise _lib.UnsupportedShapeError(f"{what}: multiple-shooting segments (segment={self.segment}) run on the generic kernels K0 / K5 only "
+                                             "(kernel 'auto' / 'generic', no saved rows); this entry point runs free from the first row to the last")
         if self.ab:
             raise _lib.UnsupportedShapeError(f"{what}: two-step Adams-Bashforth (AB2) runs on the generic kernels K0 / K5 only "
                                              "(kernel 'auto' / 'generic', no saved rows); this entry point carries euler / midpoint / rk4")
         return self.method_id, self.stages
 
 
-def call_generic(lib, stem: str, kind: str, args, opts: GenericOpts, *tail, x_sub=None):
+def call_generic(lib, stem: str, kind: str, args, opts: GenericOpts, *tail, x_sub=None, x_true=None):
     """The one place that picks an entry point of the generic-kernel families and calls it: psnode_<stem>[_<family>]_<kind>(args, the
     family's `c_args`, *tail).  stem: "ode_integrate", "dae_integrate", "ode_backward", "dae_backward"; kind: "f32" (tail: workspace
     pointer, its size, stream), "supported" or, for the backward stems, "workspace_bytes".  A dae_backward whose `args` is a
@@ -344,7 +373,7 @@ def call_generic(lib, stem: str, kind: str, args, opts: GenericOpts, *tail, x_su
     Returns (status or value, the symbol)."""
     fam = opts.family
     if fam == "none":
-        assert kind == "supported", f"{stem}: per-trajectory events with interpolated externals have no entry point"
+        assert kind == "supported", f"{stem}: per-trajectory events with interpolated externals (or segments next to either) have no entry point"
         return 0, f"psnode_{stem}_{kind}"
     if isinstance(args, _lib.DaeBwdTfArgsF32):
         assert stem == "dae_backward" and fam != "act", f"{stem}: no entry point takes dataset rows and the acts {opts.acts} alone"
@@ -353,7 +382,7 @@ def call_generic(lib, stem: str, kind: str, args, opts: GenericOpts, *tail, x_su
         assert stem in ("ode_backward", "dae_backward"), f"{stem} has no workspace query of its own"
         if stem == "ode_backward" or fam == "act":
             fam = "plain"
-        elif fam in ("pev", "ab"):
+        elif fam in ("pev", "ab", "ms"):
             # the _rk query with the call's acts and tableau -- a built-in method's stand-in is the one-stage tableau, the size does not
             # depend on it: the same policy (every activation kind, the pre-activations kept), so the same fit, the same checks and the same
             # layout as this family's build, whatever the number of sub-steps
@@ -366,7 +395,7 @@ def call_generic(lib, stem: str, kind: str, args, opts: GenericOpts, *tail, x_su
         name = f"psnode_{stem}_{kind}"
         return getattr(lib, name)(ctypes.byref(args), *tail), name
     name = f"psnode_{stem}_{fam}_{kind}"
-    return getattr(lib, name)(ctypes.byref(args), *opts.c_args(x_sub), *tail), name
+    return getattr(lib, name)(ctypes.byref(args), *opts.c_args(x_sub, x_true), *tail), name
 
 
 def act_of_module(m) -> Optional[object]:
@@ -602,6 +631,17 @@ def _mlp(layers: Layers, dev, name: str, keep: list) -> _lib.MlpF32:
         m.weight[k] = w.data_ptr()
         m.bias[k] = b.data_ptr()
     return m
+
+
+def _ms_rows(what: str, segment, x_true, T: int, B: int, xd: int, dev):
+    """The dataset rows a backward call with `segment` reads where a step restarts (T - 1 > segment): contiguous fp32 [T, B, xd] on the
+    call's device (a shorter tensor would be read out of bounds); None where no step restarts."""
+    if segment is None or T - 1 <= segment:
+        return None
+    if x_true is None or x_true.dim() != 3 or x_true.shape[0] < T or tuple(x_true.shape[1:]) != (B, xd):
+        raise ValueError(f"{what}: segment={segment} needs x_true, the dataset rows [T={T}, B={B}, {xd}] the forward call restarted from, got "
+                         f"{None if x_true is None else tuple(x_true.shape)}")
+    return _f32_dev(x_true.detach(), dev, "x_true").contiguous()
 
 
 def _check_tb(name: str, a: Optional[torch.Tensor], T: int, B: int, min_T: Optional[int] = None):

@@ -5,7 +5,7 @@ import ctypes
 import torch
 
 from .. import _lib
-from ._common import (KERNEL_ID, GenericOpts, Layers, _aligned16, _bind_jumps, _check_saved, _empty, _f32_dev, _mlp, _split_grads, _view, _workspace_of, call_generic, check_event_idx)
+from ._common import (KERNEL_ID, GenericOpts, Layers, _aligned16, _bind_jumps, _check_saved, _empty, _f32_dev, _mlp, _split_grads, _view, _workspace_of, call_generic, check_event_idx, _ms_rows)
 from .latent import latent_backward_wide, latent_wide_shape
 
 def _bwd_args(opts, de_layers, x_dim, z_dim, T, B, dev, keep, kernel="auto"):
@@ -18,15 +18,16 @@ def _bwd_args(opts, de_layers, x_dim, z_dim, T, B, dev, keep, kernel="auto"):
 
 
 def ode_backward_supported(method, de_layers: Layers, x_dim: int, z_dim: int, kernel: str = "auto", act=None, substeps: int = 1,
-                           externals: str = "hold", per_trajectory: bool = False) -> bool:
+                           externals: str = "hold", per_trajectory: bool = False, segment=None) -> bool:
     """True if a fused backward kernel covers this shape: the MFMA class (3n->64->64->64->x, x<=8, z<=4) or any MLP whose
     activations and parameter gradients fit the LDS (generic backward).  act (fused.Act) other than None = ELU(1): K5 only.
     method a fused.Tableau: K5's tableau build only (kernel "auto" / "generic"; it answers for its own LDS fit).  substeps > 1: K5's
     sub-step build only, under the same rules.  externals="linear": K5's linear-externals build only (every substeps >= 1; its own LDS fit).
-    per_trajectory=True (a call WITH events): K5's per-trajectory build only (every substeps >= 1; never together with externals="linear")."""
+    per_trajectory=True (a call WITH events): K5's per-trajectory build only (every substeps >= 1; never together with externals="linear").
+    segment (an int >= 1): K5's multiple-shooting build only (every substeps >= 1; never together with either of the two before)."""
     if de_layers[0][0].device.type != "cuda" or len(de_layers) > _lib.MAX_LAYERS:
         return False
-    opts = GenericOpts.of(method, (act,), substeps, externals, bool(per_trajectory))
+    opts = GenericOpts.of(method, (act,), substeps, externals, bool(per_trajectory), segment)
     if opts.family == "plain" and kernel in ("auto", "mfma") and latent_wide_shape(de_layers, None, x_dim, z_dim):
         return True                          # K3w (saving) + K9w + library GEMMs
     a = _bwd_args(opts, de_layers, x_dim, z_dim, 2, 1, de_layers[0][0].device, [], kernel)
@@ -35,7 +36,7 @@ def ode_backward_supported(method, de_layers: Layers, x_dim: int, z_dim: int, ke
 
 def ode_backward(method, de_layers: Layers, t, z, all_initial, xs, grad_xs, event_idx=None, z_jump=None, need_grad_z: bool = True,
                  kernel: str = "auto", saved=None, input_true_x: bool = False, need_grad_zj: bool = True, act=None, substeps: int = 1,
-                 x_sub=None, externals: str = "hold", per_trajectory: bool = False):
+                 x_sub=None, externals: str = "hold", per_trajectory: bool = False, segment=None, x_true=None):
     """Backward pass of `ode_integrate` in one launch.  `saved` = what `ode_integrate(save=True)` returned next to
     xs: K4f then skips the recompute of the stage evaluations.  input_true_x: backward of a teacher-forced call (my_solvers.py:72-74) --
     `xs` must then be the DATASET x the forward call started every step from; K4f where the shape is its (hidden <= 128, x_dim <= 8) and
@@ -54,6 +55,9 @@ def ode_backward(method, de_layers: Layers, t, z, all_initial, xs, grad_xs, even
     per-trajectory build, the rules of substeps (x_sub where substeps > 1).  grad_z_jump[b, e] receives the adjoint of trajectory b's
     interval that event e opens (exactly 0 where it never fires), grad_z[k, b] is exactly 0 where b jumps at k.  Without an event table
     the flag means nothing.
+    segment (an int w >= 1): backward of `ode_integrate(..., segment=w)` -- K5's multiple-shooting build, the rules of substeps; x_true
+    [T, B, xd] is the dataset x of the forward call (needed where T - 1 > w; it gets no gradient).  The start adjoint of a restart step
+    is dropped: grad_x0 is segment 0's, grad_xs[k] of a restart point still travels back into the segment before it.
     Returns (grad_x0 [B,xd], grad_z [T,B,zd] | None, grad_z_jump | None, grad_all_initial [B,n], [grad W1, b1, ..., W4, b4])."""
     lib = _lib.load()
     dev = xs.device
@@ -62,8 +66,9 @@ def ode_backward(method, de_layers: Layers, t, z, all_initial, xs, grad_xs, even
     # kernel: "auto" / "mfma" = the one-launch K4f at every hidden width <= 128 (z_dim <= 8), K8f / K9 / K9w for the latent shapes, else the
     # generic K5 ("auto" only); "wide" forces K4f
     per_trajectory = bool(per_trajectory) and event_idx is not None
-    opts = GenericOpts.of(method, (act,), substeps, externals, per_trajectory)
+    opts = GenericOpts.of(method, (act,), substeps, externals, per_trajectory, segment)
     opts.require_generic("ode_backward", kernel, saved is not None, teacher_forced=input_true_x)
+    x_true = _ms_rows("ode_backward", segment, x_true, T, B, xd, dev)
     if per_trajectory:
         check_event_idx(event_idx, T, B, True, dev)
     if substeps > 1 and T >= 2 and (x_sub is None or tuple(x_sub.shape) != (T - 1, substeps - 1, B, xd) or not x_sub.is_contiguous()
@@ -74,7 +79,7 @@ def ode_backward(method, de_layers: Layers, t, z, all_initial, xs, grad_xs, even
         g = latent_backward_wide(method, de_layers, None, t, z, None, all_initial, xs, None, grad_xs, None, event_idx=event_idx,
                                  z_jump=z_jump, saved=saved, need_grad_z=need_grad_z)
         return g["x_init"], g["z"], g["z_jump"], g["all_initial"], g["de"]
-    keep: list = [x_sub]
+    keep: list = [x_sub, x_true]
     a = _bwd_args(opts, de_layers, xd, zd, T, B, dev, keep, kernel)
     if input_true_x:
         if saved is not None:
@@ -110,6 +115,6 @@ def ode_backward(method, de_layers: Layers, t, z, all_initial, xs, grad_xs, even
             a.saved_act, a.saved_xstage = saved[0].data_ptr(), saved[1].data_ptr()
         nbytes = call_generic(lib, "ode_backward", "workspace_bytes", a, opts)[0]
         ws, wp, wn = _workspace_of(nbytes, dev)
-        rc, entry = call_generic(lib, "ode_backward", "f32", a, opts, wp, wn, torch.cuda.current_stream(dev).cuda_stream, x_sub=x_sub)
+        rc, entry = call_generic(lib, "ode_backward", "f32", a, opts, wp, wn, torch.cuda.current_stream(dev).cuda_stream, x_sub=x_sub, x_true=x_true)
     _lib.check(rc, entry)
     return gx0, gz, gzj, ga0, _split_grads(gpar, de_layers)

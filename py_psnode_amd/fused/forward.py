@@ -45,7 +45,7 @@ def _note_k0(lib, args, dae: bool, de_layers: Layers):
 def ode_integrate(method, de_layers: Layers, t, x, z, all_initial, event_t=None, z_jump=None,
                   input_true_x: bool = False, kernel: str = "auto", event_idx: Optional[torch.Tensor] = None,
                   check_events: bool = False, out: Optional[torch.Tensor] = None, save: bool = False, act=None, substeps: int = 1,
-                  save_sub: bool = False, externals: str = "hold", per_trajectory: bool = False):
+                  save_sub: bool = False, externals: str = "hold", per_trajectory: bool = False, segment=None):
     """Fused integrate_ODE (replaces my_solvers.py:52-80 + my_fixed_grid.py + DE_Func.forward).
 
     method: "euler" | "midpoint" | "rk4" (the 3/8 rule), or a fused.Tableau -- any explicit Runge-Kutta method of up to four stages, on
@@ -68,6 +68,12 @@ def ode_integrate(method, de_layers: Layers, t, x, z, all_initial, event_t=None,
     build for every substeps >= 1 (kernel "auto" / "generic"; save=True and externals="linear" are refused; save_sub then always returns a
     tensor).  A call without events (no event_t and no event_idx, T == 1, an empty list) is the call it is without the flag.
 
+    segment (None, or an int w >= 1): multiple shooting -- the step that leaves grid point k > 0 with k % w == 0 starts from the dataset
+    row x[k] (its first sub-step only), so rows m w + 1 .. (m + 1) w are the free run on the slices [m w : (m + 1) w + 1] from x[m w];
+    row 0 of x is the start of the call, and x must hold all T rows where T - 1 > w.  The generic kernel K0 in its multiple-shooting
+    build for every substeps >= 1 (kernel "auto" / "generic"; save=True, externals="linear" and per_trajectory events are refused, and
+    input_true_x is a ValueError; save_sub then always returns a tensor).
+
     save=True (training forward, K1 shapes only -- `ode_save_hidden`): the kernel also writes what autograd would save, the hidden
     activations [T-1,S,3,B,Hp] and the stage inputs [T-1,S,B,xd]; returns (xs, (act, xstage)) for `ode_backward(..., saved=)`.
 
@@ -81,11 +87,11 @@ def ode_integrate(method, de_layers: Layers, t, x, z, all_initial, event_t=None,
     if dev.type != "cuda":
         raise ValueError("fused integrator needs tensors on a HIP device")
     per_trajectory = bool(per_trajectory) and has_events(t, event_t, event_idx)
-    opts = GenericOpts.of(method, (act,), substeps, externals, per_trajectory)
+    opts = GenericOpts.of(method, (act,), substeps, externals, per_trajectory, segment)
     opts.require_generic("ode_integrate", kernel, save)
     opts.no_teacher_forcing("ode_integrate", input_true_x)
     T, B, xd = t.shape[0], x.shape[1], x.shape[2]
-    if x.shape[0] < (T if input_true_x else 1):
+    if x.shape[0] < (T if input_true_x or (segment is not None and T - 1 > segment) else 1):
         raise ValueError("x has fewer grid points than t")
     zd = z.shape[-1]
     _check_tb("t", t, T, B)
@@ -124,7 +130,7 @@ def ode_integrate(method, de_layers: Layers, t, x, z, all_initial, event_t=None,
                      _empty((max(T - 1, 0), opts.stages, B, xd), dtype=torch.float32, device=dev))
             if T >= 2:
                 a.save_act, a.save_xstage = saved[0].data_ptr(), saved[1].data_ptr()
-        x_sub = _empty((max(T - 1, 0), substeps - 1, B, xd), dtype=torch.float32, device=dev) if save_sub and opts.family in ("sub", "lin", "pev", "ab") else None
+        x_sub = _empty((max(T - 1, 0), substeps - 1, B, xd), dtype=torch.float32, device=dev) if save_sub and opts.family in ("sub", "lin", "pev", "ab", "ms") else None
         ws, wp, wn = _workspace_of(lib.psnode_workspace_bytes(ctypes.byref(a.de), None), dev)
         rc, entry = call_generic(lib, "ode_integrate", "f32", a, opts, wp, wn, torch.cuda.current_stream(dev).cuda_stream, x_sub=x_sub)
     _mfma_miss(rc, kernel, entry, de_layers)
@@ -153,7 +159,7 @@ def dae_integrate(method, de_layers: Layers, ae_layers: Layers, x_init, t, x, z,
                   event_t=None, z_jump=None, v_jump=None, input_true_x: bool = False, input_true_i: bool = False,
                   kernel: str = "auto", event_idx: Optional[torch.Tensor] = None, check_events: bool = False, out=None,
                   save: bool = False, act=None, substeps: int = 1, save_sub: bool = False, externals: str = "hold",
-                  per_trajectory: bool = False):
+                  per_trajectory: bool = False, segment=None):
     """Fused integrate_DAE (replaces my_solvers.py:82-131 + step functions + DE_Func/AE_Func forwards).
     method: "euler" | "midpoint" | "rk4", or a fused.Tableau (generic kernel K0 only: kernel "auto" / "generic"; save=True is refused).
     act: None (both MLPs ELU(1)) or (de_act, ae_act), each a fused.Act or None = ELU(1); an activation other than ELU(1) runs on the
@@ -167,6 +173,9 @@ def dae_integrate(method, de_layers: Layers, ae_layers: Layers, x_init, t, x, z,
     per_trajectory=True: as `ode_integrate`, for z | v together; the event-time head i0 = g(x_k; z_jump, v_jump) replaces the carried
     algebraic variable of the trajectories with a hit at step k only, the others keep theirs.  K0's per-trajectory build for every
     substeps >= 1 (kernel "auto" / "generic", no save, not with externals="linear").
+    segment (None, or an int w >= 1): multiple shooting, as `ode_integrate`; the DE of a restart step reads the head at the dataset row,
+    g(x[k]; z_k, v_k) with the jumped rows behind an event, while xs[k] / is[k] stay the previous segment's prediction.  Needs the dataset
+    x [T, B, x_dim] (ValueError without); teacher forcing is a ValueError.  K0's multiple-shooting build (kernel "auto" / "generic", no save).
     `out` = (xs, is) contiguous [T,B,xd] / [T,B,id] tensors to write into (time-chunked launches).
     save=True (training forward, K2 shapes without teacher forcing -- `dae_save_hidden`): the kernel also writes what autograd would
     save (psnode_dae_args_f32::save_*); returns (xs, is, saved) with saved = (act [T-1,S,3,B,Hp], xstage [T-1,S,B,xd],
@@ -176,9 +185,11 @@ def dae_integrate(method, de_layers: Layers, ae_layers: Layers, x_init, t, x, z,
     if dev.type != "cuda":
         raise ValueError("fused integrator needs tensors on a HIP device")
     per_trajectory = bool(per_trajectory) and has_events(t, event_t, event_idx)
-    opts = GenericOpts.of(method, dae_acts(act), substeps, externals, per_trajectory)
+    opts = GenericOpts.of(method, dae_acts(act), substeps, externals, per_trajectory, segment)
     opts.require_generic("dae_integrate", kernel, save)
     opts.no_teacher_forcing("dae_integrate", input_true_x or input_true_i)
+    if segment is not None and x.shape[-1] == 0:
+        raise ValueError(f"dae_integrate: segment={segment} restarts from the dataset rows x[k]; this call has none (x.shape[-1] == 0)")
     T, B = t.shape[0], t.shape[1]
     xd, zd, vd, idim = x_init.shape[-1], z.shape[-1], v.shape[-1], i.shape[-1]
     if x_init.dim() != 2 or x_init.shape[0] != B:
@@ -186,7 +197,7 @@ def dae_integrate(method, de_layers: Layers, ae_layers: Layers, x_init, t, x, z,
     _check_tb("t", t, T, B)
     _check_tb("z", z, T, B)
     _check_tb("v", v, T, B)
-    if input_true_x:
+    if input_true_x or segment is not None:
         _check_tb("x", x, T, B)
     if input_true_i:
         _check_tb("i", i, T, B)
@@ -201,12 +212,12 @@ def dae_integrate(method, de_layers: Layers, ae_layers: Layers, x_init, t, x, z,
     if save:      # (as ode_integrate)
         x_init, z, v, z_jump, v_jump = _aligned16(x_init), _aligned16(z), _aligned16(v), _aligned16(z_jump), _aligned16(v_jump)
     a.t = _view(t, dev, "t", keep)
-    a.x = _view(x if input_true_x else None, dev, "x", keep)
+    a.x = _view(x if input_true_x or segment is not None else None, dev, "x", keep)
     a.z = _view(z, dev, "z", keep)
     a.v = _view(v, dev, "v", keep)
     a.i = _view(i if input_true_i else None, dev, "i", keep)
-    if input_true_x and x.shape[-1] != xd:
-        raise ValueError("input_true_x needs dataset x of width x_init.shape[-1]")
+    if (input_true_x or segment is not None) and x.shape[-1] != xd:
+        raise ValueError("input_true_x / segment need dataset x of width x_init.shape[-1]")
     xi = _f32_dev(x_init, dev, "x_init").contiguous()
     a0 = _f32_dev(all_initial, dev, "all_initial").contiguous()
     if a0.shape != (B, xd + zd + vd + idim):
@@ -243,7 +254,7 @@ def dae_integrate(method, de_layers: Layers, ae_layers: Layers, x_init, t, x, z,
                 a.save_act = a.save_xstage = dummy.data_ptr()
             if n_ev:
                 a.save_ev_act, a.save_ev_i = saved[3].data_ptr(), saved[4].data_ptr()
-        x_sub = _empty((max(T - 1, 0), substeps - 1, B, xd), dtype=torch.float32, device=dev) if save_sub and opts.family in ("sub", "lin", "pev", "ab") else None
+        x_sub = _empty((max(T - 1, 0), substeps - 1, B, xd), dtype=torch.float32, device=dev) if save_sub and opts.family in ("sub", "lin", "pev", "ab", "ms") else None
         ws, wp, wn = _workspace_of(lib.psnode_workspace_bytes(ctypes.byref(a.de), ctypes.byref(a.ae)), dev)
         rc, entry = call_generic(lib, "dae_integrate", "f32", a, opts, wp, wn, torch.cuda.current_stream(dev).cuda_stream, x_sub=x_sub)
     _mfma_miss(rc, kernel, entry, de_layers)

@@ -280,6 +280,8 @@ class ODE_Model(nn.Module):
             return None
         if getattr(self.event, "per_trajectory", False) and event_t is not None:      # ... and per-trajectory events (a call that has events)
             return None
+        if getattr(solver, "segment", None) is not None:      # ... and multiple-shooting segments
+            return None
         if any(fused._overrides_forward_hooks(m) for m in (self, self.x_encoder, self.z_encoder, self.x_decoder, self.de_func,
                                                           self.de_func.x_dot)):
             return None                                            # user hooks must fire: module-by-module route
@@ -391,7 +393,7 @@ class DAE_Model(nn.Module):
             return None
         if getattr(solver, "kernel", "auto") == "generic" or isinstance(solver.method, fused.Tableau) or fused.is_ab(solver.method):      # (a tableau and Adams-Bashforth 2 run on K0 / K5)
             return None
-        if getattr(solver, "substeps", 1) > 1 or getattr(solver, "externals", "hold") != "hold" or (getattr(self.event, "per_trajectory", False) and event_t is not None):      # (so do sub-steps, linear externals and per-trajectory events of a call that has events)
+        if getattr(solver, "substeps", 1) > 1 or getattr(solver, "externals", "hold") != "hold" or (getattr(self.event, "per_trajectory", False) and event_t is not None) or getattr(solver, "segment", None) is not None:      # (so do sub-steps, linear externals, per-trajectory events of a call that has events and multiple-shooting segments)
             return None
         # Measured (profiles/r04m_dae02_routes.txt, 4096 x 1000 steps): the one launch moves 140 B per state-step instead of 3.4 KB (13.7 GB vs 0.586 GB per batch, measured) and needs
         # none of the six [T,B,64] latent tensors (6.3 GB at that size), but at hidden 64 the encoders / decoders are MFMA work that the

@@ -189,6 +189,9 @@ class AB2(FixedGridODESolver):
         if kw.get("externals", "hold") != "hold":
             raise ValueError("AB2 reads the right-hand side at grid points only: externals='linear' would need inputs between the dataset rows "
                              f"(got externals={kw.get('externals')!r})")
+        if kw.get("segment") is not None:
+            raise ValueError("AB2 carries the previous slope from step to step: a multiple-shooting restart (segment=) has no form here "
+                             f"(got segment={kw.get('segment')!r})")
         super().__init__(**kw)
 
     def _step_func(self, func, t0, dt, t1, x0, z0=None, v0=None, i0=None, all_initial=None):

@@ -36,8 +36,15 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
     order: int
     method = ""        # "euler" | "midpoint" | "rk4", a fused.Tableau (my_fixed_grid.ExplicitRK) or "ab2" (my_fixed_grid.AB2): the formula the fused kernels run
 
-    def __init__(self, step_size=None, grid_constructor=None, interp="linear", substeps=1, externals="hold"):
-        """externals ("hold", the default and the reference's behaviour, or "linear"): what the stages of a grid interval read of the
+    def __init__(self, step_size=None, grid_constructor=None, interp="linear", substeps=1, externals="hold", segment=None):
+        """segment (None, the default, or an int w >= 1): multiple shooting.  Grid point k is a restart point iff k > 0 and k % w == 0: the
+        step that leaves it starts from the dataset row x[k] instead of the running state, and a DAE's DE reads the head at that row,
+        g(x[k]; z_k, v_k) with the jumped rows if an event fires at k.  Output rows m w + 1 .. min((m + 1) w, T - 1) are then exactly what
+        the free-running call returns in its rows 1 .. on the slices [m w : (m + 1) w + 1] started from x[m w]; xs[k] / is[k] of a restart
+        point stay the previous segment's prediction.  Only sub-step 0 of the interval starts from x[k].  The dataset x gets no gradient
+        (`_walk_ode` / `_walk_dae` are the definition; fused on the generic kernels K0 / K5, kernel 'auto' / 'generic').  Not together with
+        input_true_x / input_true_i (every step restarts already), and a DAE needs its dataset x: ValueError.
+        externals ("hold", the default and the reference's behaviour, or "linear"): what the stages of a grid interval read of the
         external inputs z | v.  "hold": the left grid point's rows (the jumped ones behind an event) for every stage and sub-step -- which
         leaves an O(interval) error that no method order and no number of sub-steps removes.  "linear": stage s (abscissa c_s) of sub-step j
         reads w_L + theta (w_R - w_L) at theta = (j + c_s) / substeps, w_L the left rows (jumped behind an event), w_R the dataset's rows of
@@ -54,6 +61,9 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
         if externals not in _fused.EXTERNALS:
             raise ValueError(f"externals must be one of {_fused.EXTERNALS}, got {externals!r}")
         self.externals = externals
+        if segment is not None and (isinstance(segment, bool) or not isinstance(segment, int) or segment < 1):
+            raise ValueError(f"segment must be None or an int >= 1, got {segment!r}")
+        self.segment = segment
         # public attributes of the reference (my_solvers.py:13-18)
         self.step_size = step_size
         self.interp = interp
@@ -93,7 +103,7 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
             warnings.warn(f"{what}: this call is not fusable (needs fp32 HIP tensors, DE_Func/AE_Func-style MLPs with one activation "
                           "of ELU / Tanh / Sigmoid / ReLU / LeakyReLU / Softplus / SiLU / GELU / Mish -- other than ELU(1) on kernel 'auto' / 'generic' only --, "
                           "ODE_Event/DAE_Event callbacks -- with per_trajectory=True on kernel 'auto' / 'generic' only and not together with externals='linear' --; "
-                          "an ExplicitRK tableau, substeps > 1 or externals='linear' on kernel 'auto' / 'generic' only (substeps <= 1024); under autograd also a shape with a backward kernel; teacher-forced "
+                          "an ExplicitRK tableau, substeps > 1 or externals='linear' on kernel 'auto' / 'generic' only (substeps <= 1024); segment= on kernel 'auto' / 'generic' only, with held externals and shared events, dataset x without grad; under autograd also a shape with a backward kernel; teacher-forced "
                           "training: ELU(1), dataset rows without grad) -- stepping through the Python callables instead", RuntimeWarning, stacklevel=3)
 
     def _generic_only_ok(self, what, acts, per_trajectory=False) -> bool:
@@ -105,7 +115,8 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
         generic = self.kernel in ("auto", "generic")
         lin_pt = per_trajectory and self.externals != "hold"
         fits = generic and self.substeps <= _fused._lib.MAX_SUBSTEPS
-        if fits and not lin_pt:
+        ms_none = self.segment is not None and (per_trajectory or self.externals != "hold")      # no kernel carries these combinations
+        if fits and not lin_pt and not ms_none:
             return True
         limits = "(kernel 'auto' / 'generic', substeps <= %d)" % _fused._lib.MAX_SUBSTEPS
         if not generic and any(a is not None for a in acts):
@@ -121,6 +132,11 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
             text = "with per-trajectory events and externals='linear' has no fused form: the generic kernels carry either, not both"
         elif not generic and per_trajectory:
             text = "has no form for per-trajectory events (per_trajectory=True): they run on the generic kernels (kernel 'auto' / 'generic')"
+        elif ms_none:
+            text = (f"with segment={self.segment} next to " + ("externals='linear'" if self.externals != "hold" else "per-trajectory events")
+                    + " has no fused form: the multiple-shooting build of the generic kernels holds the externals and takes the shared event table")
+        elif not generic and self.segment is not None:
+            text = f"has no form for multiple-shooting segments (segment={self.segment}): they run on the generic kernels (kernel 'auto' / 'generic')"
         else:
             return True
         if self.fused == "require":
@@ -135,6 +151,8 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
             kw["externals"] = self.externals
         if per_trajectory:
             kw["per_trajectory"] = True
+        if self.segment is not None:
+            kw["segment"] = self.segment
         return kw
 
     def _step_func_lin(self, func, t0, dt, x0, ext_at, i0=None, all_initial=None):
@@ -151,6 +169,20 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
             theta = (j + c) / n
             return tuple(wl + theta * (wr - wl) for wl, wr in zip(left, right))
         return ext_at
+
+    def _check_segment(self, what, teacher_forced, x=None):
+        """The refusals of `segment`: teacher forcing (every step restarts already) and, for a DAE (`x` given), no dataset x."""
+        if self.segment is None:
+            return
+        if teacher_forced:
+            raise ValueError(f"{what}: segment={self.segment} and input_true_x / input_true_i exclude each other (every teacher-forced step "
+                             "restarts from the dataset already)")
+        if x is not None and x.shape[-1] == 0:
+            raise ValueError(f"{what}: segment={self.segment} restarts from the dataset rows x[k]; this call has none (x.shape[-1] == 0)")
+
+    def _restart(self, k) -> bool:
+        """Is grid point k a restart point of `segment`?"""
+        return self.segment is not None and k > 0 and k % self.segment == 0
 
     def _check_events_now(self, event_t):
         return (self.check_events and event_t is not None and event_t.dim() == 3 and event_t.shape[1] > 1
@@ -171,7 +203,10 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
         d loss / d x back as a [T,B,x_dim] tensor that is zero except for row 0 -- allocated, filled and ADDED to x's other gradient."""
         if x_init is not None and input_true_x:
             raise ValueError("integrate_ODE: x_init and input_true_x exclude each other (teacher forcing starts every step from x[k])")
-        if self.fused != "off":
+        self._check_segment("integrate_ODE", input_true_x)
+        # (segment: a dataset x that requires grad gets none -- such a call with a restart walks, as teacher forcing does)
+        ms_walk = self.segment is not None and t.shape[0] - 1 > self.segment and torch.is_grad_enabled() and x.requires_grad
+        if self.fused != "off" and not ms_walk:
             plan = _fused.plan_ode(x_func, x, z, all_initial, event_fn, jump_change_fn, t=t, x_init=x_init)
             # (per-trajectory events: only a call that has events carries the rule)
             per_traj = plan is not None and plan[1] is not None and _fused.per_trajectory_events(event_fn)
@@ -182,7 +217,10 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
                 layers, event_t, z_jump, needs_grad, act = plan
                 if not needs_grad:
                     try:
-                        return _fused.ode_integrate(self.method, layers, t, x if x_init is None else x_init.unsqueeze(0), z, all_initial,
+                        x_in = x if x_init is None else x_init.unsqueeze(0)
+                        if x_init is not None and self.segment is not None and t.shape[0] - 1 > self.segment:
+                            x_in = torch.cat((x_in, x[1:]))      # (the restarts read rows 1 ..; row 0 is the start of the call)
+                        return _fused.ode_integrate(self.method, layers, t, x_in, z, all_initial,
                                                     event_t=event_t, z_jump=z_jump,
                                                     input_true_x=input_true_x, kernel=self.kernel,
                                                     check_events=self._check_events_now(event_t), act=act, **sub)
@@ -207,6 +245,11 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
                                       "activation of ELU / Tanh / Sigmoid / ReLU / LeakyReLU / Softplus / SiLU / GELU / Mish, ODE_Event callbacks; with autograd: "
                                       "a shape with a backward kernel; teacher-forced training: ELU(1), kernel 'auto' / 'mfma' / 'generic', x without grad)")
             self._note_walk("integrate_ODE", x)
+        if self.fused != "off" and ms_walk:
+            if self.fused == "require":
+                raise NotFusableError(f"integrate_ODE: segment={self.segment} with a dataset x that requires grad is not fusable (the dataset "
+                                      "rows get no gradient; pass the start through x_init)")
+            self._note_walk("integrate_ODE", x)
         return self._walk_ode(x_func, t, x, z, all_initial, event_fn, jump_change_fn, input_true_x, x_init)
 
     def _walk_ode(self, x_func, t, x, z, all_initial, event_fn, jump_change_fn, input_true_x, x_init=None):
@@ -219,6 +262,10 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
             if event_fn is not None and event_fn(t0) == True:  # noqa: E712 (callbacks may return tensors)
                 zk = jump_change_fn(t0, zk)
             start = x[k] if input_true_x else cur
+            if self.segment is not None:
+                self._check_segment("integrate_ODE", input_true_x)
+                if self._restart(k):      # multiple shooting: this segment starts from the dataset row, which gets no gradient
+                    start = x[k].detach()
             if self.externals == "linear":      # stage s of sub-step j reads zk + theta (z[k + 1] - zk), theta = (j + c_s) / n; zk jumped behind an event
                 h = (t1 - t0) / self.substeps
                 cur = start
@@ -239,7 +286,9 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
     # ------------------------------------------------------------------ DAE
     def integrate_DAE(self, x_init, x_func, i_func, t, x, z, v, i, all_initial, event_fn=None, jump_change_fn=None,
                       input_true_x=False, input_true_i=False):
-        if self.fused != "off":
+        self._check_segment("integrate_DAE", input_true_x or input_true_i, x)
+        ms_walk = self.segment is not None and t.shape[0] - 1 > self.segment and torch.is_grad_enabled() and x.requires_grad
+        if self.fused != "off" and not ms_walk:
             plan = _fused.plan_dae(x_init, x_func, i_func, z, v, i, all_initial, event_fn, jump_change_fn, t=t)
             per_traj = plan is not None and plan[2] is not None and _fused.per_trajectory_events(event_fn)
             if plan is not None and not self._generic_only_ok("integrate_DAE", plan[6:], per_traj):
@@ -261,7 +310,8 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
                         self.method, de, ae, x_init.shape[-1], z.shape[-1], v.shape[-1], i.shape[-1], t.shape[0], t.shape[1], act=act, **sub):
                     from ..autograd import fused_dae_integrate
                     return fused_dae_integrate(self.method, self.kernel, de, ae, x_init, t, z, v, i, all_initial, event_t, z_jump, v_jump,
-                                               check_events=self._check_events_now(event_t), act=act, **sub)
+                                               check_events=self._check_events_now(event_t), act=act, **sub,
+                                               **(dict(x=x) if self.segment is not None else {}))
                 # teacher-forced training (my_solvers.py:111-121): K7f in its recompute form where the shape is its, else K5 (ELU(1) only);
                 # the dataset rows get no gradient
                 elif act is None and (input_true_x or input_true_i) and not (input_true_x and x.requires_grad) and not (input_true_i and i.requires_grad) \
@@ -275,6 +325,11 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
             if self.fused == "require":
                 raise NotFusableError("integrate_DAE: call is not fusable (needs fp32 HIP tensors, DE_Func/AE_Func-style "
                                       "MLPs with one activation each of ELU / Tanh / Sigmoid / ReLU / LeakyReLU / Softplus / SiLU / GELU / Mish, DAE_Event callbacks; with autograd: a shape with a backward kernel; teacher-forced training: ELU(1), kernel 'auto' / 'mfma' / 'generic', T >= 2, dataset rows without grad)")
+            self._note_walk("integrate_DAE", z if z.numel() else v)
+        if self.fused != "off" and ms_walk:
+            if self.fused == "require":
+                raise NotFusableError(f"integrate_DAE: segment={self.segment} with a dataset x that requires grad is not fusable (the dataset "
+                                      "rows get no gradient)")
             self._note_walk("integrate_DAE", z if z.numel() else v)
         return self._walk_dae(x_init, x_func, i_func, t, x, z, v, i, all_initial, event_fn, jump_change_fn,
                               input_true_x, input_true_i)
@@ -298,6 +353,11 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
                     cur_i = i_func(xt=cur_x, zt=zk, vt=vk, all_initial=all_initial)
             start = x[k] if input_true_x else cur_x
             i_in = i[k] if input_true_i else cur_i
+            if self.segment is not None:
+                self._check_segment("integrate_DAE", input_true_x or input_true_i, x)
+                if self._restart(k):      # multiple shooting: the DE starts from the dataset row and reads the head AT that row (zk | vk: the
+                    start = x[k].detach()      # jumped rows behind an event); xs[k] / is[k] stay the previous segment's prediction
+                    i_in = i_func(xt=start, zt=zk, vt=vk, all_initial=all_initial)
             if self.externals == "linear":      # as the ODE, for z | v; i is frozen over a sub-step's stages and never interpolated; the head in
                 h = (t1 - t0) / self.substeps   # front of sub-step j >= 1 sees the state and the z | v of theta = j / n
                 cur_x = start

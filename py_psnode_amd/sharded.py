@@ -174,6 +174,14 @@ def _pipelined(launch, T: int, Bl: int, widths, dtype, device, chunks: int, grou
     return local, gathered, works
 
 
+def _no_segments(what: str, kw: dict):
+    """A time-chunked launch restarts every chunk from the previous chunk's last row and hands the kernels one row of x: it has neither
+    the dataset rows of a multiple-shooting restart nor the restart's phase inside a chunk.  `segment=` is refused, not dropped."""
+    if kw.get("segment") is not None:
+        raise ValueError(f"{what}: segment={kw['segment']!r} has no time-chunked form (a chunk carries neither the dataset rows x[k] nor the "
+                         "phase of the restarts); integrate the shard in one launch (fused.ode_integrate / dae_integrate)")
+
+
 def integrate_ode_pipelined(method, de_layers, t, x, z, all_initial, event_idx=None, z_jump=None, chunks: int = 4, group=None,
                             local_fn: Optional[Callable] = None, gather: bool = True, wait: bool = True, want_local: bool = True,
                             check_shards: bool = True, layout: str = "chunks", algo: str = "rccl", **kw):
@@ -188,6 +196,7 @@ def integrate_ode_pipelined(method, de_layers, t, x, z, all_initial, event_idx=N
     layout="batch", the plain [T, G*Bl, xd] tensor the chunks were gathered INTO (see _pipelined).  `want_local=False`
     skips the concatenation of the local chunks (this rank's rows are in `gathered` anyway).
     """
+    _no_segments("integrate_ode_pipelined", kw)
     if local_fn is None:
         from . import fused
         local_fn = fused.ode_integrate
@@ -213,6 +222,7 @@ def integrate_dae_pipelined(method, de_layers, ae_layers, x_init, t, z, v, i, al
     how is[s] was produced (my_solvers.py:121 uses the un-jumped z, v of the right grid point), so the restart is bit-identical
     to one long launch -- including an event at step s, whose i0 recomputation with the jumped inputs happens inside the loop.
     Returns ((xs_local, is_local), (gathered_x, gathered_i))."""
+    _no_segments("integrate_dae_pipelined", kw)
     if local_fn is None:
         from . import fused
         local_fn = fused.dae_integrate
