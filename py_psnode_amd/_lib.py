@@ -341,51 +341,22 @@ def load():
     lib.psnode_dae_backward_workspace_bytes.argtypes = [ctypes.POINTER(DaeBwdArgsF32)]
     lib.psnode_dae_backward_f32.restype = c_int32
     lib.psnode_dae_backward_f32.argtypes = [ctypes.POINTER(DaeBwdArgsF32), c_void_p, c_size_t, c_void_p]
-    if hasattr(lib, "psnode_dae_backward_tf_f32"):
-        lib.psnode_dae_backward_tf_supported.restype = c_int32
-        lib.psnode_dae_backward_tf_supported.argtypes = [ctypes.POINTER(DaeBwdTfArgsF32)]
-        lib.psnode_dae_backward_tf_workspace_bytes.restype = c_size_t
-        lib.psnode_dae_backward_tf_workspace_bytes.argtypes = [ctypes.POINTER(DaeBwdTfArgsF32)]
-        lib.psnode_dae_backward_tf_f32.restype = c_int32
-        lib.psnode_dae_backward_tf_f32.argtypes = [ctypes.POINTER(DaeBwdTfArgsF32), c_void_p, c_size_t, c_void_p]
-    act_p = ctypes.POINTER(ActF32)
-    for name, args_t, n_act in (("ode_integrate", OdeArgsF32, 1), ("dae_integrate", DaeArgsF32, 2), ("ode_backward", OdeBwdArgsF32, 1),
+    # the option families of the generic kernels K0 / K5: what each takes behind the args struct is a row of fused/_common.py's FAMILIES
+    from .fused._common import FAMILIES      # (here, not at the top: that module imports this one)
+    ptr = ctypes.POINTER
+    for stem, args_t, n_act in (("ode_integrate", OdeArgsF32, 1), ("dae_integrate", DaeArgsF32, 2), ("ode_backward", OdeBwdArgsF32, 1),
                                 ("dae_backward", DaeBwdArgsF32, 2)):
-        q = getattr(lib, f"psnode_{name}_act_supported")
-        q.restype, q.argtypes = c_int32, [ctypes.POINTER(args_t)] + [act_p] * n_act
-        f = getattr(lib, f"psnode_{name}_act_f32")
-        f.restype, f.argtypes = c_int32, [ctypes.POINTER(args_t)] + [act_p] * n_act + [c_void_p, c_size_t, c_void_p]
-    rk_p = ctypes.POINTER(RkTableauF32)
-    for name, args_t, n_act in (("ode_integrate", OdeArgsF32, 1), ("dae_integrate", DaeArgsF32, 2), ("ode_backward", OdeBwdArgsF32, 1),
-                                ("dae_backward", DaeBwdTfArgsF32, 2)):
-        q = getattr(lib, f"psnode_{name}_rk_supported")
-        q.restype, q.argtypes = c_int32, [ctypes.POINTER(args_t)] + [act_p] * n_act + [rk_p]
-        f = getattr(lib, f"psnode_{name}_rk_f32")
-        f.restype, f.argtypes = c_int32, [ctypes.POINTER(args_t)] + [act_p] * n_act + [rk_p, c_void_p, c_size_t, c_void_p]
-    lib.psnode_dae_backward_rk_workspace_bytes.restype = c_size_t
-    lib.psnode_dae_backward_rk_workspace_bytes.argtypes = [ctypes.POINTER(DaeBwdTfArgsF32), act_p, act_p, rk_p]
-    sub_p = ctypes.POINTER(SubstepsF32)
-    for name, args_t, n_act in (("ode_integrate", OdeArgsF32, 1), ("dae_integrate", DaeArgsF32, 2), ("ode_backward", OdeBwdArgsF32, 1),
-                                ("dae_backward", DaeBwdTfArgsF32, 2)):
-        for fam in ("sub", "lin", "pev"):      # (the _lin and _pev entry points take exactly what their _sub siblings take)
-            q = getattr(lib, f"psnode_{name}_{fam}_supported")
-            q.restype, q.argtypes = c_int32, [ctypes.POINTER(args_t)] + [act_p] * n_act + [rk_p, sub_p]
-            f = getattr(lib, f"psnode_{name}_{fam}_f32")
-            f.restype, f.argtypes = c_int32, [ctypes.POINTER(args_t)] + [act_p] * n_act + [rk_p, sub_p, c_void_p, c_size_t, c_void_p]
-        # (the _ab entry points: no tableau, no sub-steps; the call takes per_trajectory -- is event_idx the [T-1, B] table? -- behind the acts)
-        # (the _ms entry points: what their _sub siblings take, plus the segments struct in front of the workspace)
-        seg_p = ctypes.POINTER(SegmentsF32)
-        q = getattr(lib, f"psnode_{name}_ms_supported")
-        q.restype, q.argtypes = c_int32, [ctypes.POINTER(args_t)] + [act_p] * n_act + [rk_p, sub_p, seg_p]
-        f = getattr(lib, f"psnode_{name}_ms_f32")
-        f.restype, f.argtypes = c_int32, [ctypes.POINTER(args_t)] + [act_p] * n_act + [rk_p, sub_p, seg_p, c_void_p, c_size_t, c_void_p]
-        q = getattr(lib, f"psnode_{name}_ab_supported")
-        q.restype, q.argtypes = c_int32, [ctypes.POINTER(args_t)] + [act_p] * n_act
-        f = getattr(lib, f"psnode_{name}_ab_f32")
-        f.restype, f.argtypes = c_int32, [ctypes.POINTER(args_t)] + [act_p] * n_act + [c_int32, c_void_p, c_size_t, c_void_p]
-    for fam in ("sub", "lin"):
-        w = getattr(lib, f"psnode_dae_backward_{fam}_workspace_bytes")
-        w.restype, w.argtypes = c_size_t, [ctypes.POINTER(DaeBwdTfArgsF32), act_p, act_p, rk_p, sub_p]
+        for fam, f in FAMILIES.items():
+            if fam in ("plain", "none") or (fam == "tf" and stem != "dae_backward"):
+                continue
+            query = [ptr(DaeBwdTfArgsF32 if stem == "dae_backward" and f.tf_args else args_t)] + [ptr(ActF32)] * (n_act if f.acts else 0) + \
+                    [ptr(RkTableauF32)] * f.tab + [ptr(SubstepsF32)] * f.sub + [ptr(SegmentsF32)] * f.seg
+            protos = {"supported": (c_int32, query), "f32": (c_int32, query + [c_int32] * f.pt + [c_void_p, c_size_t, c_void_p])}
+            if stem == "dae_backward" and f.workspace == "own":
+                protos["workspace_bytes"] = (c_size_t, query)
+            for kind, (restype, argtypes) in protos.items():
+                fn = getattr(lib, f"psnode_{stem}_{fam}_{kind}")
+                fn.restype, fn.argtypes = restype, argtypes
     lib.psnode_mlp_rows_backward_workspace_bytes.restype = c_size_t
     lib.psnode_mlp_rows_backward_workspace_bytes.argtypes = [ctypes.POINTER(MlpF32), c_int64]
     lib.psnode_mlp_rows_backward_f32.restype = c_int32

@@ -4,7 +4,7 @@
 //   K4f (psnode_backward_fused.hip)      ODE, in -> H -> H -> H -> x at hidden <= 128: one launch, saved-activation and recompute forms
 //   K8f / K9 (psnode_latent_dpp.hip / psnode_latent64_bwd*.hip)   the latent integrators of the direct_encode models at hidden 16 / 64
 //   K8 (psnode_latent_bwd.hip)           the latent DAE at hidden 16
-//   K5 (psnode_generic_bwd_impl.h)       anything else that fits the LDS, with or without teacher forcing
+//   K5 (psnode_generic_bwd_impl.h)       anything else that fits the LDS, with or without teacher forcing (its option families: psnode_generic_family.h)
 // (the DAE's no_encode shapes go through psnode_dae_backward_wide_f32 -> K7f, psnode_dae_backward_fused.hip).
 // Rounds 1-4 also carried K4 / K7, hidden-64 specialisations of the recompute form; K4f / K7f cover their shapes (round 5:
 // profiles/scripts/variants/ keeps the sources).
@@ -12,8 +12,7 @@
 
 #include <type_traits>
 
-#include "psnode_act.h"
-#include "psnode_launch.h"
+#include "psnode_generic_family.h"
 #include "psnode_pack.h"
 
 using namespace psnode;
@@ -87,16 +86,22 @@ GenericBwdCall generic_bwd_call(const psnode_dae_bwd_args_f32& a) {
     c.gparams_de = a.grad_params_de; c.gparams_ae = a.grad_params_ae;
     return c;
 }
-// act: the activations of a non-ELU(1) call, or nullptr
-int generic_backward(const GenericBwdCall& c, const ActPair* act, void* workspace, void* stream) {
-    if (c.rk && c.ms_every > 0) return generic_backward_launch<BuildMs>(c, act, static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
-    if (c.rk && c.ab) return generic_backward_launch<BuildAb>(c, act, static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
-    if (c.rk && c.pev) return generic_backward_launch<BuildPev>(c, act, static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
-    if (c.rk && c.lin) return generic_backward_launch<BuildLin>(c, act, static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
-    if (c.rk && c.substeps > 1) return generic_backward_launch<BuildSub>(c, act, static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
-    if (c.rk) return generic_backward_launch<BuildRk>(c, act, static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
-    const auto launch = !act ? generic_backward_launch<BuildElu1> : (act_pair_keeps_u(*act) ? generic_backward_launch<BuildPre> : generic_backward_launch<BuildAct>);
-    return launch(c, act, static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
+// act: the activations of every build but kBuildElu1, which ignores them
+int generic_backward(BuildId build, const GenericBwdCall& c, const ActPair* act, void* workspace, void* stream) {
+    float* ws = static_cast<float*>(workspace);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    switch (build) {
+        case kBuildElu1: return generic_backward_launch<BuildElu1>(c, act, ws, s);
+        case kBuildAct: return generic_backward_launch<BuildAct>(c, act, ws, s);
+        case kBuildPre: return generic_backward_launch<BuildPre>(c, act, ws, s);
+        case kBuildRk: return generic_backward_launch<BuildRk>(c, act, ws, s);
+        case kBuildSub: return generic_backward_launch<BuildSub>(c, act, ws, s);
+        case kBuildLin: return generic_backward_launch<BuildLin>(c, act, ws, s);
+        case kBuildPev: return generic_backward_launch<BuildPev>(c, act, ws, s);
+        case kBuildAb: return generic_backward_launch<BuildAb>(c, act, ws, s);
+        case kBuildMs: return generic_backward_launch<BuildMs>(c, act, ws, s);
+    }
+    return PSNODE_ERR_UNSUPPORTED;      // (no such build)
 }
 // K4f: every width <= 128 (z_dim up to 8), saved-activation and recompute forms
 bool use_fused_bwd(const psnode_ode_bwd_args_f32* a) { return a->kernel != PSNODE_KERNEL_GENERIC && fused_bwd_shape_ok(a); }
@@ -147,14 +152,14 @@ extern "C" int32_t psnode_ode_backward_f32(const psnode_ode_bwd_args_f32* a, voi
         if (a->saved_act || a->kernel == PSNODE_KERNEL_MFMA_WAVE) return PSNODE_ERR_UNSUPPORTED;
         if (use_fused_bwd(a)) return fused_bwd_launch(a, static_cast<float*>(workspace), s);
         if ((a->kernel != PSNODE_KERNEL_AUTO && a->kernel != PSNODE_KERNEL_GENERIC) || !ode_generic_ok(a)) return PSNODE_ERR_UNSUPPORTED;
-        return generic_backward(generic_bwd_call(*a), nullptr, workspace, stream);
+        return generic_backward(kBuildElu1, generic_bwd_call(*a), nullptr, workspace, stream);
     }
     if (bwd_x_preferred(a)) return bwd_x_launch(a, static_cast<float*>(workspace), s);      // K4x: up to one wave per SIMD at hidden 33..64
     if (use_latent_bwd(a)) return latent_bwd_launch(a, static_cast<float*>(workspace), s);
     if (use_latent64_bwd(a)) return latent64_ode_bwd_launch(a, static_cast<float*>(workspace), s);
     if (use_fused_bwd(a)) return fused_bwd_launch(a, static_cast<float*>(workspace), s);
     if (a->kernel == PSNODE_KERNEL_MFMA) return PSNODE_ERR_UNSUPPORTED;   // latent shape, unaligned views
-    return generic_backward(generic_bwd_call(*a), nullptr, workspace, stream);
+    return generic_backward(kBuildElu1, generic_bwd_call(*a), nullptr, workspace, stream);
 }
 
 namespace {
@@ -207,32 +212,12 @@ extern "C" int32_t psnode_dae_backward_f32(const psnode_dae_bwd_args_f32* a, voi
     if (use_latent64_dae_bwd(a)) return latent64_dae_bwd_launch(a, static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
     if (use_latent16_dae_bwd(a)) return latent16_dae_bwd_launch(a, static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
     if (a->kernel == PSNODE_KERNEL_MFMA) return PSNODE_ERR_UNSUPPORTED;
-    return generic_backward(generic_bwd_call(*a), nullptr, workspace, stream);
+    return generic_backward(kBuildElu1, generic_bwd_call(*a), nullptr, workspace, stream);
 }
 
 // ---- The K5 entry-point families psnode_dae_backward_tf_* and psnode_{ode,dae}_backward_{act,rk,sub,lin,pev,ab,ms}_*: one checked call path
-// (k5_backward), one query (k5_supported).  Order of checks per family, which is the order of the statuses of a call that is wrong in
-// several ways:
-//
-//   _tf    NULL args | flags == 0 -> the plain entry point | method | T, B (T >= 2) | route | pointers | workspace
-//   _act   act pair | ELU(1) pair -> the plain entry point | NULL args | method | T, B | route | pointers | workspace
-//   _rk    act pair | tableau | NULL args | T, B | route | pointers | workspace            (`method` is not read)
-//   _sub   struct (NULL: PSNODE_ERR_NULL) | substeps == 1 -> the _rk family (tableau given) or the _act family | act pair | NULL args |
-//          tableau (NULL: the args' method as one) | T, B | route | pointers, x_sub where T >= 2 | workspace
-//   _lin   struct (NULL: one sub-step) | act pair | NULL args | tableau (as _sub) | T, B | route | pointers, x_sub where substeps > 1 and
-//          T >= 2 | workspace
-//   _pev   as _lin; event_idx -- here the [T-1, B] table -- is one of the pointers (NULL: PSNODE_ERR_NULL, event-less calls take the
-//          other families)
-//   _ab    act pair | NULL args | T, B | route (and no teacher-forcing flag) | pointers (event_idx may be NULL) | workspace   (`method` is not read)
-//   _ms    segments struct (NULL: PSNODE_ERR_NULL; every < 1: PSNODE_ERR_DIMS) | then as _lin; the route refuses every teacher-forcing flag;
-//          x_true is one of the pointers where a step restarts (T - 1 > every)
-//   T, B: a DAE call with flags needs T >= 2.  Route (k5_route_ok): kernel AUTO / GENERIC, no saved_* rows, flags within the struct's and
-//   only next to an ELU(1) pair, the recipe dims and the LDS fit of the family's build.  Pointers: the teacher-forcing rows among them.
-//   The DAE's _act family takes psnode_dae_bwd_args_f32, the others the _tf struct: its _sub with substeps == 1 and no tableau goes to _tf
-//   (ELU(1) pair) or refuses flags (PSNODE_ERR_UNSUPPORTED, before the method is looked at) and goes to _act with the base args.
+// (k5_backward), one query (k5_supported) over the family table of psnode_generic_family.h, which also holds the order of the checks per family.
 namespace {
-enum K5Family { kFamTf, kFamAct, kFamRk, kFamSub, kFamLin, kFamPev, kFamAb, kFamMs };
-int segments_check(const psnode_segments_f32* seg) { return !seg ? PSNODE_ERR_NULL : seg->every < 1 ? PSNODE_ERR_DIMS : PSNODE_OK; }
 constexpr uint32_t kTfFlags = PSNODE_FLAG_INPUT_TRUE_X | PSNODE_FLAG_INPUT_TRUE_I;
 
 // the difference between the three args structs: the base call, the flags and the ones the struct knows, the AE, the plain entry points
@@ -273,249 +258,231 @@ GenericBwdCall generic_bwd_call(const psnode_dae_bwd_tf_args_f32& a) {
 }
 
 template <class Args>
-bool k5_route_ok(K5Family fam, const Args& a, const ActPair& p, bool elu1, bool query) {
+bool k5_route_ok(const FamilyRow& f, const Args& a, const ActPair& p, bool elu1, bool query) {
     const auto& b = base(a);
     const uint32_t flags = tf_flags(a);
     if (b.kernel != PSNODE_KERNEL_AUTO && b.kernel != PSNODE_KERNEL_GENERIC) return false;
     if ((flags & ~tf_mask(a)) || (flags && !elu1)) return false;      // (teacher forcing: ELU(1) only)
-    if ((fam == kFamAb || fam == kFamMs) && flags) return false;      // (_ab: a multistep history has no teacher-forced form; _ms: every teacher-forced step restarts already)
-    if (saved_rows(b, fam != kFamAct ? kSavedAll : query ? kSavedAct : kSavedActCall)) return false;
-    // the fit of the build: _tf runs the ELU(1) build, _act the act or the pre build, the others keep the pre-activations for every kind
-    const bool pre = fam == kFamAct ? act_pair_keeps_u(p) : fam != kFamTf;
-    return generic_ok(&b, pre, fam == kFamLin) != 0;
-}
-// the struct of a _sub / _lin / _pev call; substeps == 1 on _sub is the family without sub-steps
-int k5_substeps(K5Family& fam, const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub) {
-    if (fam != kFamSub && !((fam == kFamLin || fam == kFamPev || fam == kFamMs) && sub)) return PSNODE_OK;
-    const int rc = substeps_check(sub);
-    if (rc == PSNODE_OK && fam == kFamSub && sub->substeps == 1) fam = tab ? kFamRk : kFamAct;
-    return rc;
+    if (f.no_tf && flags) return false;
+    if (saved_rows(b, f.saved_all ? kSavedAll : query ? kSavedAct : kSavedActCall)) return false;
+    return generic_ok(&b, f.pre || family_build(f, act_pair_keeps_u(p)) == kBuildPre, f.lin) != 0;      // (the fit of the build)
 }
 
 template <class Args>
-int k5_backward(K5Family fam, const Args* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act, const psnode_rk_tableau_f32* tab,
-                const psnode_substeps_f32* sub, void* workspace, size_t workspace_bytes, void* stream, int ev_pt = 0,
-                const psnode_segments_f32* seg = nullptr) {
+int k5_backward(Family fam, const Args* a, const CallOpts& o, void* workspace, size_t workspace_bytes, void* stream) {
     constexpr bool tf_struct = std::is_same<Args, psnode_dae_bwd_tf_args_f32>::value;
     ActPair p;
     psnode_rk_tableau_f32 t;
     bool elu1 = true;
-    int rc = fam == kFamMs ? segments_check(seg) : PSNODE_OK;
+    int rc = family_front(fam, o, p, elu1);
     if (rc) return rc;
-    rc = k5_substeps(fam, tab, sub);
-    if (rc == PSNODE_OK) rc = act_pair(de_act, ae_act, p, elu1);
-    if (rc) return rc;
-    if (fam == kFamAct && elu1) return backward_elu1(a, workspace, workspace_bytes, stream);
+    const FamilyRow& f = kFamilies[fam];
+    if (f.elu1_plain && elu1) return backward_elu1(a, workspace, workspace_bytes, stream);
     if constexpr (tf_struct) {
-        if (fam == kFamAct) {      // (_sub, substeps == 1, no tableau)
+        if (fam == kFamAct) {      // (_sub, substeps == 1, no tableau: the _act family takes the base args)
             if (!a) return PSNODE_ERR_NULL;
             if (a->flags) return PSNODE_ERR_UNSUPPORTED;
-            return k5_backward(kFamAct, &a->base, de_act, ae_act, nullptr, nullptr, workspace, workspace_bytes, stream);
+            return k5_backward(kFamAct, &a->base, {o.de_act, o.ae_act}, workspace, workspace_bytes, stream);
         }
     }
-    if (fam == kFamRk) rc = rk_tableau_check(tab);
+    rc = family_tableau(f, o.tab, a ? &base(*a).method : nullptr, t);
     if (rc) return rc;
-    if (!a) return PSNODE_ERR_NULL;
     const auto& b = base(*a);
-    rc = fam <= kFamAct ? (method_ok(&b) ? PSNODE_OK : PSNODE_ERR_METHOD) : sub_tableau(tab, fam == kFamAb ? (int)PSNODE_EULER : b.method, t);
-    if (rc) return rc;
     if (b.T < 1 || b.B < 1 || (tf_struct && tf_flags(*a) && b.T < 2)) return PSNODE_ERR_DIMS;
-    if (!k5_route_ok(fam, *a, p, elu1, false)) return PSNODE_ERR_UNSUPPORTED;
-    const int nsub = fam >= kFamSub && sub ? sub->substeps : 1;
-    if (!ptrs_ok(a) || (nsub > 1 && b.T >= 2 && !sub->x_sub) || (fam == kFamPev && !b.event_idx)) return PSNODE_ERR_NULL;
-    if (fam == kFamMs && b.T - 1 > seg->every && !seg->x_true) return PSNODE_ERR_NULL;
+    if (!k5_route_ok(f, *a, p, elu1, false)) return PSNODE_ERR_UNSUPPORTED;
+    const int nsub = family_substeps(f, o);
+    if (!ptrs_ok(a) || (nsub > 1 && b.T >= 2 && !o.sub->x_sub) || (f.needs_events && !b.event_idx)) return PSNODE_ERR_NULL;
+    if (f.seg && b.T - 1 > o.seg->every && !o.seg->x_true) return PSNODE_ERR_NULL;
     if (!workspace_ok(workspace, workspace_bytes, generic_bwd_workspace_floats(&b.de, ae_of(b), b.B) * sizeof(float))) return PSNODE_ERR_WORKSPACE;
-    GenericBwdCall c = generic_bwd_call(*a);
-    if (fam >= kFamRk) c.rk = &t;
-    if (fam >= kFamSub) { c.substeps = nsub; c.x_sub = sub ? sub->x_sub : nullptr; c.lin = fam == kFamLin; c.pev = fam == kFamPev; c.ab = fam == kFamAb; c.ab_pt = ev_pt != 0; }
-    if (fam == kFamMs) { c.ms_every = seg->every; c.ms_x_true = seg->x_true; }
-    return generic_backward(c, fam == kFamTf ? nullptr : &p, workspace, stream);
+    GenericBwdCall c = generic_bwd_call(*a);      // (the build is named below: c.lin / c.pev / c.ab stay unset, no launcher reads them)
+    if (f.tab != kTabNone) c.rk = &t;
+    c.substeps = nsub;
+    c.x_sub = o.sub ? o.sub->x_sub : nullptr;
+    c.ab_pt = o.per_trajectory != 0;
+    if (f.seg) { c.ms_every = o.seg->every; c.ms_x_true = o.seg->x_true; }
+    return generic_backward(family_build(f, act_pair_keeps_u(p)), c, &p, workspace, stream);
 }
 
 template <class Args>
-int k5_supported(K5Family fam, const Args* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act, const psnode_rk_tableau_f32* tab,
-                 const psnode_substeps_f32* sub, const psnode_segments_f32* seg = nullptr) {
+int k5_supported(Family fam, const Args* a, const CallOpts& o) {
     ActPair p;
     psnode_rk_tableau_f32 t;
     bool elu1 = true;
-    if (fam == kFamMs && segments_check(seg)) return 0;
-    if (!a || k5_substeps(fam, tab, sub) || act_pair(de_act, ae_act, p, elu1)) return 0;
-    if (fam == kFamAct && elu1) return supported_elu1(a);
+    if (!a || family_front(fam, o, p, elu1)) return 0;
+    const FamilyRow& f = kFamilies[fam];
+    if (f.elu1_plain && elu1) return supported_elu1(a);
     if constexpr (std::is_same<Args, psnode_dae_bwd_tf_args_f32>::value) {
-        if (fam == kFamAct) return a->flags == 0 && k5_supported(kFamAct, &a->base, de_act, ae_act, nullptr, nullptr);
+        if (fam == kFamAct) return a->flags == 0 && k5_supported(kFamAct, &a->base, {o.de_act, o.ae_act});      // (as k5_backward's)
     }
-    const auto& b = base(*a);
-    if (fam <= kFamAct ? !method_ok(&b) : (fam == kFamRk && !tab) || sub_tableau(tab, fam == kFamAb ? (int)PSNODE_EULER : b.method, t)) return 0;
-    return k5_route_ok(fam, *a, p, elu1, true);
+    if (family_tableau(f, o.tab, &base(*a).method, t)) return 0;
+    return k5_route_ok(f, *a, p, elu1, true);
 }
 
 // (DAE: the ODE's sizes come from psnode_ode_backward_workspace_bytes)
-size_t k5_workspace_bytes(K5Family fam, const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
-                          const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub) {
-    if (!k5_supported(fam, a, de_act, ae_act, tab, sub)) return 0;
-    if (fam == kFamSub && sub->substeps == 1 && !tab) {      // the entry point that call goes to
+size_t k5_workspace_bytes(Family fam, const psnode_dae_bwd_tf_args_f32* a, const CallOpts& o) {
+    if (!k5_supported(fam, a, o)) return 0;
+    if (kFamilies[fam].demotes && o.sub->substeps == 1 && !o.tab) {      // the entry point that call goes to
         ActPair p;
         bool elu1 = true;
-        act_pair(de_act, ae_act, p, elu1);
+        act_pair(o.de_act, o.ae_act, p, elu1);
         return elu1 ? psnode_dae_backward_tf_workspace_bytes(a) : psnode_dae_backward_workspace_bytes(&a->base);
     }
     return generic_bwd_workspace_floats(&a->base.de, &a->base.ae, a->base.B) * sizeof(float);
 }
 }  // namespace
 
-// ---- the K5 families (the table of their checks: above).  Each wrapper names its family and forwards; flags == 0 on _tf is the plain call.
+// ---- the K5 families (their table and the order of their checks: psnode_generic_family.h).  Each wrapper names its family and what it
+// takes; flags == 0 on _tf is the plain call.
 extern "C" int32_t psnode_dae_backward_tf_supported(const psnode_dae_bwd_tf_args_f32* a) {
     if (a && a->flags == 0) return psnode_dae_backward_supported(&a->base);
-    return k5_supported(kFamTf, a, nullptr, nullptr, nullptr, nullptr);
+    return k5_supported(kFamTf, a, {});
 }
 extern "C" size_t psnode_dae_backward_tf_workspace_bytes(const psnode_dae_bwd_tf_args_f32* a) {
     if (a && a->flags == 0) return psnode_dae_backward_workspace_bytes(&a->base);
-    return k5_workspace_bytes(kFamTf, a, nullptr, nullptr, nullptr, nullptr);
+    return k5_workspace_bytes(kFamTf, a, {});
 }
 extern "C" int32_t psnode_dae_backward_tf_f32(const psnode_dae_bwd_tf_args_f32* a, void* workspace, size_t workspace_bytes, void* stream) {
     if (a && a->flags == 0) return psnode_dae_backward_f32(&a->base, workspace, workspace_bytes, stream);
-    return k5_backward(kFamTf, a, nullptr, nullptr, nullptr, nullptr, workspace, workspace_bytes, stream);
+    return k5_backward(kFamTf, a, {}, workspace, workspace_bytes, stream);
 }
 
 extern "C" int32_t psnode_ode_backward_act_supported(const psnode_ode_bwd_args_f32* a, const psnode_act_f32* de_act) {
-    return k5_supported(kFamAct, a, de_act, nullptr, nullptr, nullptr);
+    return k5_supported(kFamAct, a, {de_act});
 }
-extern "C" int32_t psnode_ode_backward_act_f32(const psnode_ode_bwd_args_f32* a, const psnode_act_f32* de_act, void* workspace,
-                                               size_t workspace_bytes, void* stream) {
-    return k5_backward(kFamAct, a, de_act, nullptr, nullptr, nullptr, workspace, workspace_bytes, stream);
+extern "C" int32_t psnode_ode_backward_act_f32(const psnode_ode_bwd_args_f32* a, const psnode_act_f32* de_act, void* ws, size_t bytes, void* stream) {
+    return k5_backward(kFamAct, a, {de_act}, ws, bytes, stream);
 }
 extern "C" int32_t psnode_dae_backward_act_supported(const psnode_dae_bwd_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act) {
-    return k5_supported(kFamAct, a, de_act, ae_act, nullptr, nullptr);
+    return k5_supported(kFamAct, a, {de_act, ae_act});
 }
-extern "C" int32_t psnode_dae_backward_act_f32(const psnode_dae_bwd_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
-                                               void* workspace, size_t workspace_bytes, void* stream) {
-    return k5_backward(kFamAct, a, de_act, ae_act, nullptr, nullptr, workspace, workspace_bytes, stream);
+extern "C" int32_t psnode_dae_backward_act_f32(const psnode_dae_bwd_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act, void* ws,
+                                               size_t bytes, void* stream) {
+    return k5_backward(kFamAct, a, {de_act, ae_act}, ws, bytes, stream);
 }
 
 extern "C" int32_t psnode_ode_backward_rk_supported(const psnode_ode_bwd_args_f32* a, const psnode_act_f32* de_act,
                                                     const psnode_rk_tableau_f32* tab) {
-    return k5_supported(kFamRk, a, de_act, nullptr, tab, nullptr);
+    return k5_supported(kFamRk, a, {de_act, nullptr, tab});
 }
 extern "C" int32_t psnode_ode_backward_rk_f32(const psnode_ode_bwd_args_f32* a, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
-                                              void* workspace, size_t workspace_bytes, void* stream) {
-    return k5_backward(kFamRk, a, de_act, nullptr, tab, nullptr, workspace, workspace_bytes, stream);
+                                              void* ws, size_t bytes, void* stream) {
+    return k5_backward(kFamRk, a, {de_act, nullptr, tab}, ws, bytes, stream);
 }
 extern "C" int32_t psnode_dae_backward_rk_supported(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act,
                                                     const psnode_act_f32* ae_act, const psnode_rk_tableau_f32* tab) {
-    return k5_supported(kFamRk, a, de_act, ae_act, tab, nullptr);
+    return k5_supported(kFamRk, a, {de_act, ae_act, tab});
 }
 extern "C" size_t psnode_dae_backward_rk_workspace_bytes(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act,
                                                          const psnode_act_f32* ae_act, const psnode_rk_tableau_f32* tab) {
-    return k5_workspace_bytes(kFamRk, a, de_act, ae_act, tab, nullptr);
+    return k5_workspace_bytes(kFamRk, a, {de_act, ae_act, tab});
 }
 extern "C" int32_t psnode_dae_backward_rk_f32(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
-                                              const psnode_rk_tableau_f32* tab, void* workspace, size_t workspace_bytes, void* stream) {
-    return k5_backward(kFamRk, a, de_act, ae_act, tab, nullptr, workspace, workspace_bytes, stream);
+                                              const psnode_rk_tableau_f32* tab, void* ws, size_t bytes, void* stream) {
+    return k5_backward(kFamRk, a, {de_act, ae_act, tab}, ws, bytes, stream);
 }
 
 extern "C" int32_t psnode_ode_backward_sub_supported(const psnode_ode_bwd_args_f32* a, const psnode_act_f32* de_act,
                                                      const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub) {
-    return k5_supported(kFamSub, a, de_act, nullptr, tab, sub);
+    return k5_supported(kFamSub, a, {de_act, nullptr, tab, sub});
 }
 extern "C" int32_t psnode_ode_backward_sub_f32(const psnode_ode_bwd_args_f32* a, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
-                                               const psnode_substeps_f32* sub, void* workspace, size_t workspace_bytes, void* stream) {
-    return k5_backward(kFamSub, a, de_act, nullptr, tab, sub, workspace, workspace_bytes, stream);
+                                               const psnode_substeps_f32* sub, void* ws, size_t bytes, void* stream) {
+    return k5_backward(kFamSub, a, {de_act, nullptr, tab, sub}, ws, bytes, stream);
 }
 extern "C" int32_t psnode_dae_backward_sub_supported(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act,
                                                      const psnode_act_f32* ae_act, const psnode_rk_tableau_f32* tab,
                                                      const psnode_substeps_f32* sub) {
-    return k5_supported(kFamSub, a, de_act, ae_act, tab, sub);
+    return k5_supported(kFamSub, a, {de_act, ae_act, tab, sub});
 }
 extern "C" size_t psnode_dae_backward_sub_workspace_bytes(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act,
                                                           const psnode_act_f32* ae_act, const psnode_rk_tableau_f32* tab,
                                                           const psnode_substeps_f32* sub) {
-    return k5_workspace_bytes(kFamSub, a, de_act, ae_act, tab, sub);
+    return k5_workspace_bytes(kFamSub, a, {de_act, ae_act, tab, sub});
 }
 extern "C" int32_t psnode_dae_backward_sub_f32(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
-                                               const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, void* workspace,
-                                               size_t workspace_bytes, void* stream) {
-    return k5_backward(kFamSub, a, de_act, ae_act, tab, sub, workspace, workspace_bytes, stream);
+                                               const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, void* ws, size_t bytes,
+                                               void* stream) {
+    return k5_backward(kFamSub, a, {de_act, ae_act, tab, sub}, ws, bytes, stream);
 }
 
 extern "C" int32_t psnode_ode_backward_lin_supported(const psnode_ode_bwd_args_f32* a, const psnode_act_f32* de_act,
                                                      const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub) {
-    return k5_supported(kFamLin, a, de_act, nullptr, tab, sub);
+    return k5_supported(kFamLin, a, {de_act, nullptr, tab, sub});
 }
 extern "C" int32_t psnode_ode_backward_lin_f32(const psnode_ode_bwd_args_f32* a, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
-                                               const psnode_substeps_f32* sub, void* workspace, size_t workspace_bytes, void* stream) {
-    return k5_backward(kFamLin, a, de_act, nullptr, tab, sub, workspace, workspace_bytes, stream);
+                                               const psnode_substeps_f32* sub, void* ws, size_t bytes, void* stream) {
+    return k5_backward(kFamLin, a, {de_act, nullptr, tab, sub}, ws, bytes, stream);
 }
 extern "C" int32_t psnode_dae_backward_lin_supported(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act,
                                                      const psnode_act_f32* ae_act, const psnode_rk_tableau_f32* tab,
                                                      const psnode_substeps_f32* sub) {
-    return k5_supported(kFamLin, a, de_act, ae_act, tab, sub);
+    return k5_supported(kFamLin, a, {de_act, ae_act, tab, sub});
 }
 extern "C" size_t psnode_dae_backward_lin_workspace_bytes(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act,
                                                           const psnode_act_f32* ae_act, const psnode_rk_tableau_f32* tab,
                                                           const psnode_substeps_f32* sub) {
-    return k5_workspace_bytes(kFamLin, a, de_act, ae_act, tab, sub);
+    return k5_workspace_bytes(kFamLin, a, {de_act, ae_act, tab, sub});
 }
 extern "C" int32_t psnode_dae_backward_lin_f32(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
-                                               const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, void* workspace,
-                                               size_t workspace_bytes, void* stream) {
-    return k5_backward(kFamLin, a, de_act, ae_act, tab, sub, workspace, workspace_bytes, stream);
+                                               const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, void* ws, size_t bytes,
+                                               void* stream) {
+    return k5_backward(kFamLin, a, {de_act, ae_act, tab, sub}, ws, bytes, stream);
 }
 
 // (per-trajectory events: the args' event_idx is the [T-1, B] table of psnode_event_table_pt_f32)
 extern "C" int32_t psnode_ode_backward_pev_supported(const psnode_ode_bwd_args_f32* a, const psnode_act_f32* de_act,
                                                      const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub) {
-    return k5_supported(kFamPev, a, de_act, nullptr, tab, sub);
+    return k5_supported(kFamPev, a, {de_act, nullptr, tab, sub});
 }
 extern "C" int32_t psnode_ode_backward_pev_f32(const psnode_ode_bwd_args_f32* a, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
-                                               const psnode_substeps_f32* sub, void* workspace, size_t workspace_bytes, void* stream) {
-    return k5_backward(kFamPev, a, de_act, nullptr, tab, sub, workspace, workspace_bytes, stream);
+                                               const psnode_substeps_f32* sub, void* ws, size_t bytes, void* stream) {
+    return k5_backward(kFamPev, a, {de_act, nullptr, tab, sub}, ws, bytes, stream);
 }
 extern "C" int32_t psnode_dae_backward_pev_supported(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act,
                                                      const psnode_act_f32* ae_act, const psnode_rk_tableau_f32* tab,
                                                      const psnode_substeps_f32* sub) {
-    return k5_supported(kFamPev, a, de_act, ae_act, tab, sub);
+    return k5_supported(kFamPev, a, {de_act, ae_act, tab, sub});
 }
 extern "C" int32_t psnode_dae_backward_pev_f32(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
-                                               const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, void* workspace,
-                                               size_t workspace_bytes, void* stream) {
-    return k5_backward(kFamPev, a, de_act, ae_act, tab, sub, workspace, workspace_bytes, stream);
+                                               const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, void* ws, size_t bytes,
+                                               void* stream) {
+    return k5_backward(kFamPev, a, {de_act, ae_act, tab, sub}, ws, bytes, stream);
 }
 
 // (two-step Adams-Bashforth: per_trajectory says whether a non-NULL event_idx is the [T-1, B] table or the shared [T-1])
 extern "C" int32_t psnode_ode_backward_ab_supported(const psnode_ode_bwd_args_f32* a, const psnode_act_f32* de_act) {
-    return k5_supported(kFamAb, a, de_act, nullptr, nullptr, nullptr);
+    return k5_supported(kFamAb, a, {de_act});
 }
-extern "C" int32_t psnode_ode_backward_ab_f32(const psnode_ode_bwd_args_f32* a, const psnode_act_f32* de_act, int32_t per_trajectory,
-                                              void* workspace, size_t workspace_bytes, void* stream) {
-    return k5_backward(kFamAb, a, de_act, nullptr, nullptr, nullptr, workspace, workspace_bytes, stream, per_trajectory);
+extern "C" int32_t psnode_ode_backward_ab_f32(const psnode_ode_bwd_args_f32* a, const psnode_act_f32* de_act, int32_t per_trajectory, void* ws,
+                                              size_t bytes, void* stream) {
+    return k5_backward(kFamAb, a, {de_act, nullptr, nullptr, nullptr, nullptr, per_trajectory}, ws, bytes, stream);
 }
 extern "C" int32_t psnode_dae_backward_ab_supported(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act,
                                                     const psnode_act_f32* ae_act) {
-    return k5_supported(kFamAb, a, de_act, ae_act, nullptr, nullptr);
+    return k5_supported(kFamAb, a, {de_act, ae_act});
 }
 extern "C" int32_t psnode_dae_backward_ab_f32(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
-                                              int32_t per_trajectory, void* workspace, size_t workspace_bytes, void* stream) {
-    return k5_backward(kFamAb, a, de_act, ae_act, nullptr, nullptr, workspace, workspace_bytes, stream, per_trajectory);
+                                              int32_t per_trajectory, void* ws, size_t bytes, void* stream) {
+    return k5_backward(kFamAb, a, {de_act, ae_act, nullptr, nullptr, nullptr, per_trajectory}, ws, bytes, stream);
 }
 
 // (multiple shooting: the step that leaves grid point k > 0 with k % seg->every == 0 started from seg->x_true[k])
 extern "C" int32_t psnode_ode_backward_ms_supported(const psnode_ode_bwd_args_f32* a, const psnode_act_f32* de_act,
                                                     const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub,
                                                     const psnode_segments_f32* seg) {
-    return k5_supported(kFamMs, a, de_act, nullptr, tab, sub, seg);
+    return k5_supported(kFamMs, a, {de_act, nullptr, tab, sub, seg});
 }
 extern "C" int32_t psnode_ode_backward_ms_f32(const psnode_ode_bwd_args_f32* a, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
-                                              const psnode_substeps_f32* sub, const psnode_segments_f32* seg, void* workspace,
-                                              size_t workspace_bytes, void* stream) {
-    return k5_backward(kFamMs, a, de_act, nullptr, tab, sub, workspace, workspace_bytes, stream, 0, seg);
+                                              const psnode_substeps_f32* sub, const psnode_segments_f32* seg, void* ws, size_t bytes, void* stream) {
+    return k5_backward(kFamMs, a, {de_act, nullptr, tab, sub, seg}, ws, bytes, stream);
 }
 extern "C" int32_t psnode_dae_backward_ms_supported(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act,
                                                     const psnode_act_f32* ae_act, const psnode_rk_tableau_f32* tab,
                                                     const psnode_substeps_f32* sub, const psnode_segments_f32* seg) {
-    return k5_supported(kFamMs, a, de_act, ae_act, tab, sub, seg);
+    return k5_supported(kFamMs, a, {de_act, ae_act, tab, sub, seg});
 }
 extern "C" int32_t psnode_dae_backward_ms_f32(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
                                               const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, const psnode_segments_f32* seg,
-                                              void* workspace, size_t workspace_bytes, void* stream) {
-    return k5_backward(kFamMs, a, de_act, ae_act, tab, sub, workspace, workspace_bytes, stream, 0, seg);
+                                              void* ws, size_t bytes, void* stream) {
+    return k5_backward(kFamMs, a, {de_act, ae_act, tab, sub, seg}, ws, bytes, stream);
 }

@@ -1,11 +1,10 @@
 // C ABI of libpsnode_hip.so (see include/psnode_hip.h): argument validation, the forward workspace's layout (psnode_workspace.h),
-// weight packing and kernel dispatch.  Everything is enqueued on the caller's stream.
+// weight packing and kernel dispatch.  Everything is enqueued on the caller's stream.  (K0's option families: psnode_generic_family.h.)
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
 
-#include "psnode_act.h"
-#include "psnode_launch.h"
+#include "psnode_generic_family.h"
 
 namespace psnode {
 namespace {
@@ -77,15 +76,14 @@ __global__ void event_table_kernel(long long n_steps, const float* clock, long l
     if (cnt > 1 && dup_flag) *dup_flag = 1;
 }
 
-// What a K0 call carries beyond its args: the build of the generic kernel that runs it (psnode_generic_build.h) and that build's kernel
+// What a K0 call carries beyond its args: the build of the generic kernel that runs it (psnode_generic_family.h) and that build's kernel
 // arguments.  The plain entry points pass K0Call{}: ELU(1), the args' method, one step per interval -- the only call the MFMA kernels take.
 struct K0Call {
-    enum Build { kElu1, kAct, kRk, kSub, kLin, kPev, kAb, kMs } build;      // kAct: the act or the pre build, by the pair's kinds
-    ActPair act;                   // every build but kElu1
-    psnode_rk_tableau_f32 rk;      // kRk, kSub, kLin: given, or the args' method written as one (sub_tableau)
-    SubDev sub;                    // kSub, kLin, kPev: sub-steps per grid interval and x_sub
-    int ev_pt;                     // kAb: the event table is [T-1, B] (else the shared [T-1], or none)
-    int ms_every;                  // kMs: grid point k > 0 with k % ms_every == 0 restarts from row k of the args' x
+    BuildId build;
+    ActPair act;                   // every build but kBuildElu1
+    psnode_rk_tableau_f32 rk;      // the builds with a tableau: given, or the args' method written as one (family_tableau)
+    SubDev sub;                    // kBuildSub, kBuildLin, kBuildPev, kBuildMs: sub-steps per grid interval and x_sub
+    int ev_pt, ms_every;           // kBuildAb: the event table is [T-1, B]; kBuildMs: grid point k > 0 with k % ms_every == 0 restarts from row k of x
 };
 
 int dispatch(IntegrateDev& d, bool dae, int kernel, const psnode_mlp_f32* de, const psnode_mlp_f32* ae, void* workspace,
@@ -97,7 +95,7 @@ int dispatch(IntegrateDev& d, bool dae, int kernel, const psnode_mlp_f32* de, co
     if (dae && max_width(*ae) > d.maxw) d.maxw = max_width(*ae);
     d.maxo = max_out_width(*de, dae ? ae : nullptr);
 
-    const bool has_mfma = call.build == K0Call::kElu1 && (dae ? mfma_dae_supported(d) : mfma_ode_supported(d));
+    const bool has_mfma = call.build == kBuildElu1 && (dae ? mfma_dae_supported(d) : mfma_ode_supported(d));
     const bool want_mfma = kernel == PSNODE_KERNEL_MFMA || kernel == PSNODE_KERNEL_MFMA_TILE || kernel == PSNODE_KERNEL_MFMA_WAVE;
     if (want_mfma && !has_mfma) return PSNODE_ERR_UNSUPPORTED;
     if (kernel == PSNODE_KERNEL_MFMA_WAVE && !(dae ? mfma_x_dae_supported(d) : mfma_x_ode_supported(d))) return PSNODE_ERR_UNSUPPORTED;
@@ -106,18 +104,19 @@ int dispatch(IntegrateDev& d, bool dae, int kernel, const psnode_mlp_f32* de, co
     if (d.T < 1 || d.B < 1) return PSNODE_ERR_DIMS;
     if (use_mfma) return ok_or_hip(launch_mfma(d, dae, pack, stream));
 
-    if (generic_lds_bytes(d, dae, call.build == K0Call::kLin) > 160 * 1024) return PSNODE_ERR_UNSUPPORTED;
+    if (generic_lds_bytes(d, dae, call.build == kBuildLin) > 160 * 1024) return PSNODE_ERR_UNSUPPORTED;
     hipError_t e = launch_pack_image(d.de, dae ? &d.ae : nullptr, d.xd, d.xd + d.zd + (dae ? d.vd + d.id : 0), d.zd + (dae ? d.vd : 0), stream);
     if (e != hipSuccess) return PSNODE_ERR_HIP;
     switch (call.build) {
-        case K0Call::kElu1: e = launch_generic(d, dae, stream); break;
-        case K0Call::kAct: e = act_pair_pre(call.act) ? launch_generic_pre(d, dae, call.act, stream) : launch_generic_act(d, dae, call.act, stream); break;
-        case K0Call::kRk: e = launch_generic_rk(d, dae, call.act, call.rk, stream); break;
-        case K0Call::kSub: e = launch_generic_sub(d, dae, call.act, call.rk, call.sub, stream); break;
-        case K0Call::kLin: e = launch_generic_lin(d, dae, call.act, call.rk, call.sub, stream); break;
-        case K0Call::kPev: e = launch_generic_pev(d, dae, call.act, call.rk, call.sub, stream); break;
-        case K0Call::kAb: e = launch_generic_ab(d, dae, call.act, call.rk, AbDev{1, nullptr, call.ev_pt}, stream); break;
-        case K0Call::kMs: e = launch_generic_ms(d, dae, call.act, call.rk, MsDev{call.sub.n, call.sub.x_sub, call.ms_every, nullptr}, stream); break;
+        case kBuildElu1: e = launch_generic(d, dae, stream); break;
+        case kBuildAct: e = launch_generic_act(d, dae, call.act, stream); break;
+        case kBuildPre: e = launch_generic_pre(d, dae, call.act, stream); break;
+        case kBuildRk: e = launch_generic_rk(d, dae, call.act, call.rk, stream); break;
+        case kBuildSub: e = launch_generic_sub(d, dae, call.act, call.rk, call.sub, stream); break;
+        case kBuildLin: e = launch_generic_lin(d, dae, call.act, call.rk, call.sub, stream); break;
+        case kBuildPev: e = launch_generic_pev(d, dae, call.act, call.rk, call.sub, stream); break;
+        case kBuildAb: e = launch_generic_ab(d, dae, call.act, call.rk, AbDev{1, nullptr, call.ev_pt}, stream); break;
+        case kBuildMs: e = launch_generic_ms(d, dae, call.act, call.rk, MsDev{call.sub.n, call.sub.x_sub, call.ms_every, nullptr}, stream); break;
     }
     return ok_or_hip(e);
 }
@@ -206,22 +205,7 @@ int fill_dae(const psnode_dae_args_f32* a, IntegrateDev& d) {
 }
 
 // ---- The K0 entry-point families psnode_{ode,dae}_integrate_{act,rk,sub,lin,pev,ab,ms}_*: one checked call path (k0_integrate) and one query
-// (k0_supported).  Order of checks per family, which is the order of the statuses of a call that is wrong in several ways:
-//
-//   _act   act pair | ELU(1) pair -> the plain entry point | NULL args | route (kernel, save_act alone) | fill_* (method, dims, pointers)
-//   _rk    act pair | tableau | NULL args | route (kernel, every save_*) | fill_* (`method` is not read: the copy carries EULER)
-//   _sub   struct (NULL: PSNODE_ERR_NULL) | substeps == 1 -> the _rk (tableau given) or the _act family | act pair | NULL args |
-//          tableau (NULL: the args' method as one) | route | fill_*
-//   _lin   struct (NULL: one sub-step) | act pair | NULL args | tableau (as _sub) | route | fill_*
-//   _pev   as _lin, then event_idx -- here the [T-1, B] table -- (NULL: PSNODE_ERR_NULL, event-less calls take the other families)
-//   _ab    act pair | NULL args | route (kernel, every save_*, no teacher-forcing flag) | fill_* (`method` is not read; event_idx may be NULL)
-//   _ms    segments struct (NULL: PSNODE_ERR_NULL; every < 1: PSNODE_ERR_DIMS) | then as _lin; the route also refuses every teacher-forcing
-//          flag and a DAE whose x view is empty (the restarts read its rows)
-//   then dispatch: workspace | T, B | LDS fit of the build.
-// _act_supported with an ELU(1) pair answers from method and dims alone (the plain entry point picks its own kernel).
-enum K0Family { kFamAct, kFamRk, kFamSub, kFamLin, kFamPev, kFamAb, kFamMs };
-int segments_check(const psnode_segments_f32* seg) { return !seg ? PSNODE_ERR_NULL : seg->every < 1 ? PSNODE_ERR_DIMS : PSNODE_OK; }
-
+// (k0_supported) over the family table of psnode_generic_family.h, which also holds the order of the checks per family.
 // the ODE / DAE difference: the side outputs, the recipe widths, fill_*, the AE, the plain entry point
 bool side_outputs(const psnode_ode_args_f32& a) { return a.save_act || a.save_xstage; }
 bool side_outputs(const psnode_dae_args_f32& a) { return a.save_act || a.save_xstage || a.save_ae_act || a.save_ev_act || a.save_ev_i; }
@@ -244,69 +228,51 @@ int integrate_elu1(const psnode_dae_args_f32* a, void* ws, size_t bytes, void* s
 
 // K0 only (AUTO / GENERIC) and no training side outputs; the _act family looks at save_act alone (a lone save_xstage is fill_*'s status)
 template <class Args>
-bool k0_route_ok(K0Family fam, const Args& a) {
+bool k0_route_ok(const FamilyRow& f, const Args& a) {
     if (a.kernel != PSNODE_KERNEL_AUTO && a.kernel != PSNODE_KERNEL_GENERIC) return false;
-    if (fam == kFamAb && (a.flags & (PSNODE_FLAG_INPUT_TRUE_X | PSNODE_FLAG_INPUT_TRUE_I))) return false;      // (a multistep history has no teacher-forced form)
-    if (fam == kFamMs && ((a.flags & (PSNODE_FLAG_INPUT_TRUE_X | PSNODE_FLAG_INPUT_TRUE_I)) || side_outputs(a) || !has_dataset_x(a))) return false;      // (every teacher-forced step restarts already; the restarts read x)
-    return fam == kFamAct ? !a.save_act : !side_outputs(a);
-}
-// the struct of a _sub / _lin / _pev call; substeps == 1 on _sub is the family without sub-steps
-int k0_substeps(K0Family& fam, const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub) {
-    if (fam != kFamSub && !((fam == kFamLin || fam == kFamPev || fam == kFamMs) && sub)) return PSNODE_OK;
-    const int rc = substeps_check(sub);
-    if (rc == PSNODE_OK && fam == kFamSub && sub->substeps == 1) fam = tab ? kFamRk : kFamAct;
-    return rc;
+    if (f.no_tf && (a.flags & (PSNODE_FLAG_INPUT_TRUE_X | PSNODE_FLAG_INPUT_TRUE_I))) return false;
+    if (f.seg && !has_dataset_x(a)) return false;      // (the restarts read x)
+    return f.saved_all ? !side_outputs(a) : !a.save_act;
 }
 
 template <class Args>
-int k0_integrate(K0Family fam, const Args* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act, const psnode_rk_tableau_f32* tab,
-                 const psnode_substeps_f32* sub, void* workspace, size_t workspace_bytes, void* stream, int ev_pt = 0,
-                 const psnode_segments_f32* seg = nullptr) {
+int k0_integrate(Family fam, const Args* args, const CallOpts& o, void* workspace, size_t workspace_bytes, void* stream) {
     K0Call call{};
     bool elu1 = true;
-    int rc = fam == kFamMs ? segments_check(seg) : PSNODE_OK;
+    int rc = family_front(fam, o, call.act, elu1);
     if (rc) return rc;
-    rc = k0_substeps(fam, tab, sub);
-    if (rc == PSNODE_OK) rc = act_pair(de_act, ae_act, call.act, elu1);
-    if (rc) return rc;
-    if (fam == kFamAct && elu1) return integrate_elu1(args, workspace, workspace_bytes, stream);
-    if (fam == kFamRk) rc = rk_tableau_check(tab);
-    if (rc) return rc;
-    if (!args) return PSNODE_ERR_NULL;
+    const FamilyRow& f = kFamilies[fam];
+    if (f.elu1_plain && elu1) return integrate_elu1(args, workspace, workspace_bytes, stream);
+    rc = family_tableau(f, o.tab, args ? &args->method : nullptr, call.rk);
+    if (rc && !(f.tab == kTabNone && rc == PSNODE_ERR_METHOD)) return rc;      // (a call without a tableau leaves a bad method to fill_*, behind the route; its query refuses it in front)
     Args c = *args;
-    if (fam != kFamAct) {
-        rc = sub_tableau(tab, fam == kFamAb ? (int)PSNODE_EULER : c.method, call.rk);      // (_ab: always the one-stage tableau)
-        if (rc) return rc;
-        c.method = PSNODE_EULER;
-    }
-    if (!k0_route_ok(fam, c)) return PSNODE_ERR_UNSUPPORTED;
+    if (f.tab != kTabNone) c.method = PSNODE_EULER;      // (not read by the build; fill_* checks it)
+    if (!k0_route_ok(f, c)) return PSNODE_ERR_UNSUPPORTED;
     IntegrateDev d;
     rc = fill(&c, d);
     if (rc) return rc;
-    if (fam == kFamPev && !d.ev) return PSNODE_ERR_NULL;
-    call.build = fam == kFamAct ? K0Call::kAct : fam == kFamRk ? K0Call::kRk : fam == kFamSub ? K0Call::kSub : fam == kFamLin ? K0Call::kLin : fam == kFamPev ? K0Call::kPev : fam == kFamAb ? K0Call::kAb : K0Call::kMs;
-    call.ev_pt = ev_pt ? 1 : 0;
-    call.ms_every = seg ? seg->every : 0;
-    call.sub = SubDev{sub ? sub->substeps : 1, sub ? sub->x_sub : nullptr};
+    if (f.needs_events && !d.ev) return PSNODE_ERR_NULL;
+    call.build = family_build(f, act_pair_pre(call.act));      // (K0 keeps no u)
+    call.ev_pt = o.per_trajectory ? 1 : 0;
+    call.ms_every = o.seg ? o.seg->every : 0;
+    call.sub = SubDev{family_substeps(f, o), o.sub ? o.sub->x_sub : nullptr};
     return dispatch(d, ae_of(c) != nullptr, c.kernel, &c.de, ae_of(c), workspace, workspace_bytes, static_cast<hipStream_t>(stream), call);
 }
 
 // the same checks from the dims alone, and the LDS fit of the family's build
 template <class Args>
-int k0_supported(K0Family fam, const Args* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act, const psnode_rk_tableau_f32* tab,
-                 const psnode_substeps_f32* sub, const psnode_segments_f32* seg = nullptr) {
+int k0_supported(Family fam, const Args* a, const CallOpts& o) {
     ActPair p;
     psnode_rk_tableau_f32 t;
     bool elu1 = true;
-    if (fam == kFamMs && segments_check(seg)) return 0;
-    if (!a || k0_substeps(fam, tab, sub) || act_pair(de_act, ae_act, p, elu1)) return 0;
-    if (fam == kFamAct ? (a->method < PSNODE_EULER || a->method > PSNODE_RK4_38) : (fam == kFamRk && !tab) || sub_tableau(tab, fam == kFamAb ? (int)PSNODE_EULER : a->method, t)) return 0;
-    if (!recipe_ok(*a)) return 0;
-    if (fam == kFamAct && elu1) return 1;
-    if (!k0_route_ok(fam, *a)) return 0;
+    if (!a || family_front(fam, o, p, elu1)) return 0;
+    const FamilyRow& f = kFamilies[fam];
+    if (family_tableau(f, o.tab, &a->method, t) || !recipe_ok(*a)) return 0;
+    if (f.elu1_plain && elu1) return 1;
+    if (!k0_route_ok(f, *a)) return 0;
     IntegrateDev d = dims_only(*a);
     d.maxo = max_out_width(a->de, ae_of(*a));
-    return generic_lds_bytes(d, ae_of(*a) != nullptr, fam == kFamLin) <= 160 * 1024;
+    return generic_lds_bytes(d, ae_of(*a) != nullptr, f.lin) <= 160 * 1024;
 }
 
 }  // namespace
@@ -440,127 +406,122 @@ int32_t psnode_dae_integrate_f32(const psnode_dae_args_f32* args, void* workspac
     return dispatch(d, true, args->kernel, &args->de, &args->ae, workspace, workspace_bytes, static_cast<hipStream_t>(stream), K0Call{});
 }
 
-// ---- the K0 families (the table of their checks: k0_integrate above).  Each wrapper names its family and forwards.
+// ---- the K0 families (their table and the order of their checks: psnode_generic_family.h).  Each wrapper names its family and what it takes.
 int32_t psnode_ode_integrate_act_supported(const psnode_ode_args_f32* a, const psnode_act_f32* de_act) {
-    return k0_supported(kFamAct, a, de_act, nullptr, nullptr, nullptr);
+    return k0_supported(kFamAct, a, {de_act});
 }
-int32_t psnode_ode_integrate_act_f32(const psnode_ode_args_f32* args, const psnode_act_f32* de_act, void* workspace, size_t workspace_bytes,
-                                     void* stream) {
-    return k0_integrate(kFamAct, args, de_act, nullptr, nullptr, nullptr, workspace, workspace_bytes, stream);
+int32_t psnode_ode_integrate_act_f32(const psnode_ode_args_f32* args, const psnode_act_f32* de_act, void* ws, size_t bytes, void* stream) {
+    return k0_integrate(kFamAct, args, {de_act}, ws, bytes, stream);
 }
 int32_t psnode_dae_integrate_act_supported(const psnode_dae_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act) {
-    return k0_supported(kFamAct, a, de_act, ae_act, nullptr, nullptr);
+    return k0_supported(kFamAct, a, {de_act, ae_act});
 }
-int32_t psnode_dae_integrate_act_f32(const psnode_dae_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
-                                     void* workspace, size_t workspace_bytes, void* stream) {
-    return k0_integrate(kFamAct, args, de_act, ae_act, nullptr, nullptr, workspace, workspace_bytes, stream);
+int32_t psnode_dae_integrate_act_f32(const psnode_dae_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act, void* ws,
+                                     size_t bytes, void* stream) {
+    return k0_integrate(kFamAct, args, {de_act, ae_act}, ws, bytes, stream);
 }
 
 int32_t psnode_ode_integrate_rk_supported(const psnode_ode_args_f32* a, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab) {
-    return k0_supported(kFamRk, a, de_act, nullptr, tab, nullptr);
+    return k0_supported(kFamRk, a, {de_act, nullptr, tab});
 }
-int32_t psnode_ode_integrate_rk_f32(const psnode_ode_args_f32* args, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
-                                    void* workspace, size_t workspace_bytes, void* stream) {
-    return k0_integrate(kFamRk, args, de_act, nullptr, tab, nullptr, workspace, workspace_bytes, stream);
+int32_t psnode_ode_integrate_rk_f32(const psnode_ode_args_f32* args, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab, void* ws,
+                                    size_t bytes, void* stream) {
+    return k0_integrate(kFamRk, args, {de_act, nullptr, tab}, ws, bytes, stream);
 }
 int32_t psnode_dae_integrate_rk_supported(const psnode_dae_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
                                           const psnode_rk_tableau_f32* tab) {
-    return k0_supported(kFamRk, a, de_act, ae_act, tab, nullptr);
+    return k0_supported(kFamRk, a, {de_act, ae_act, tab});
 }
 int32_t psnode_dae_integrate_rk_f32(const psnode_dae_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
-                                    const psnode_rk_tableau_f32* tab, void* workspace, size_t workspace_bytes, void* stream) {
-    return k0_integrate(kFamRk, args, de_act, ae_act, tab, nullptr, workspace, workspace_bytes, stream);
+                                    const psnode_rk_tableau_f32* tab, void* ws, size_t bytes, void* stream) {
+    return k0_integrate(kFamRk, args, {de_act, ae_act, tab}, ws, bytes, stream);
 }
 
 int32_t psnode_ode_integrate_sub_supported(const psnode_ode_args_f32* a, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
                                            const psnode_substeps_f32* sub) {
-    return k0_supported(kFamSub, a, de_act, nullptr, tab, sub);
+    return k0_supported(kFamSub, a, {de_act, nullptr, tab, sub});
 }
 int32_t psnode_ode_integrate_sub_f32(const psnode_ode_args_f32* args, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
-                                     const psnode_substeps_f32* sub, void* workspace, size_t workspace_bytes, void* stream) {
-    return k0_integrate(kFamSub, args, de_act, nullptr, tab, sub, workspace, workspace_bytes, stream);
+                                     const psnode_substeps_f32* sub, void* ws, size_t bytes, void* stream) {
+    return k0_integrate(kFamSub, args, {de_act, nullptr, tab, sub}, ws, bytes, stream);
 }
 int32_t psnode_dae_integrate_sub_supported(const psnode_dae_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
                                            const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub) {
-    return k0_supported(kFamSub, a, de_act, ae_act, tab, sub);
+    return k0_supported(kFamSub, a, {de_act, ae_act, tab, sub});
 }
 int32_t psnode_dae_integrate_sub_f32(const psnode_dae_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
-                                     const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, void* workspace, size_t workspace_bytes,
-                                     void* stream) {
-    return k0_integrate(kFamSub, args, de_act, ae_act, tab, sub, workspace, workspace_bytes, stream);
+                                     const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, void* ws, size_t bytes, void* stream) {
+    return k0_integrate(kFamSub, args, {de_act, ae_act, tab, sub}, ws, bytes, stream);
 }
 
 int32_t psnode_ode_integrate_lin_supported(const psnode_ode_args_f32* a, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
                                            const psnode_substeps_f32* sub) {
-    return k0_supported(kFamLin, a, de_act, nullptr, tab, sub);
+    return k0_supported(kFamLin, a, {de_act, nullptr, tab, sub});
 }
 int32_t psnode_ode_integrate_lin_f32(const psnode_ode_args_f32* args, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
-                                     const psnode_substeps_f32* sub, void* workspace, size_t workspace_bytes, void* stream) {
-    return k0_integrate(kFamLin, args, de_act, nullptr, tab, sub, workspace, workspace_bytes, stream);
+                                     const psnode_substeps_f32* sub, void* ws, size_t bytes, void* stream) {
+    return k0_integrate(kFamLin, args, {de_act, nullptr, tab, sub}, ws, bytes, stream);
 }
 int32_t psnode_dae_integrate_lin_supported(const psnode_dae_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
                                            const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub) {
-    return k0_supported(kFamLin, a, de_act, ae_act, tab, sub);
+    return k0_supported(kFamLin, a, {de_act, ae_act, tab, sub});
 }
 int32_t psnode_dae_integrate_lin_f32(const psnode_dae_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
-                                     const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, void* workspace, size_t workspace_bytes,
-                                     void* stream) {
-    return k0_integrate(kFamLin, args, de_act, ae_act, tab, sub, workspace, workspace_bytes, stream);
+                                     const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, void* ws, size_t bytes, void* stream) {
+    return k0_integrate(kFamLin, args, {de_act, ae_act, tab, sub}, ws, bytes, stream);
 }
 
 // (per-trajectory events: the args' event_idx is the [T-1, B] table of psnode_event_table_pt_f32)
 int32_t psnode_ode_integrate_pev_supported(const psnode_ode_args_f32* a, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
                                            const psnode_substeps_f32* sub) {
-    return k0_supported(kFamPev, a, de_act, nullptr, tab, sub);
+    return k0_supported(kFamPev, a, {de_act, nullptr, tab, sub});
 }
 int32_t psnode_ode_integrate_pev_f32(const psnode_ode_args_f32* args, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
-                                     const psnode_substeps_f32* sub, void* workspace, size_t workspace_bytes, void* stream) {
-    return k0_integrate(kFamPev, args, de_act, nullptr, tab, sub, workspace, workspace_bytes, stream);
+                                     const psnode_substeps_f32* sub, void* ws, size_t bytes, void* stream) {
+    return k0_integrate(kFamPev, args, {de_act, nullptr, tab, sub}, ws, bytes, stream);
 }
 int32_t psnode_dae_integrate_pev_supported(const psnode_dae_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
                                            const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub) {
-    return k0_supported(kFamPev, a, de_act, ae_act, tab, sub);
+    return k0_supported(kFamPev, a, {de_act, ae_act, tab, sub});
 }
 int32_t psnode_dae_integrate_pev_f32(const psnode_dae_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
-                                     const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, void* workspace, size_t workspace_bytes,
-                                     void* stream) {
-    return k0_integrate(kFamPev, args, de_act, ae_act, tab, sub, workspace, workspace_bytes, stream);
+                                     const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, void* ws, size_t bytes, void* stream) {
+    return k0_integrate(kFamPev, args, {de_act, ae_act, tab, sub}, ws, bytes, stream);
 }
 
 // (two-step Adams-Bashforth: per_trajectory says whether a non-NULL event_idx is the [T-1, B] table or the shared [T-1])
 int32_t psnode_ode_integrate_ab_supported(const psnode_ode_args_f32* a, const psnode_act_f32* de_act) {
-    return k0_supported(kFamAb, a, de_act, nullptr, nullptr, nullptr);
+    return k0_supported(kFamAb, a, {de_act});
 }
-int32_t psnode_ode_integrate_ab_f32(const psnode_ode_args_f32* args, const psnode_act_f32* de_act, int32_t per_trajectory, void* workspace,
-                                    size_t workspace_bytes, void* stream) {
-    return k0_integrate(kFamAb, args, de_act, nullptr, nullptr, nullptr, workspace, workspace_bytes, stream, per_trajectory);
+int32_t psnode_ode_integrate_ab_f32(const psnode_ode_args_f32* args, const psnode_act_f32* de_act, int32_t per_trajectory, void* ws, size_t bytes,
+                                    void* stream) {
+    return k0_integrate(kFamAb, args, {de_act, nullptr, nullptr, nullptr, nullptr, per_trajectory}, ws, bytes, stream);
 }
 int32_t psnode_dae_integrate_ab_supported(const psnode_dae_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act) {
-    return k0_supported(kFamAb, a, de_act, ae_act, nullptr, nullptr);
+    return k0_supported(kFamAb, a, {de_act, ae_act});
 }
 int32_t psnode_dae_integrate_ab_f32(const psnode_dae_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
-                                    int32_t per_trajectory, void* workspace, size_t workspace_bytes, void* stream) {
-    return k0_integrate(kFamAb, args, de_act, ae_act, nullptr, nullptr, workspace, workspace_bytes, stream, per_trajectory);
+                                    int32_t per_trajectory, void* ws, size_t bytes, void* stream) {
+    return k0_integrate(kFamAb, args, {de_act, ae_act, nullptr, nullptr, nullptr, per_trajectory}, ws, bytes, stream);
 }
 
 // (multiple shooting: grid point k > 0 with k % seg->every == 0 restarts from row k of the args' x, which then holds all T rows)
 int32_t psnode_ode_integrate_ms_supported(const psnode_ode_args_f32* a, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
                                           const psnode_substeps_f32* sub, const psnode_segments_f32* seg) {
-    return k0_supported(kFamMs, a, de_act, nullptr, tab, sub, seg);
+    return k0_supported(kFamMs, a, {de_act, nullptr, tab, sub, seg});
 }
 int32_t psnode_ode_integrate_ms_f32(const psnode_ode_args_f32* args, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
-                                    const psnode_substeps_f32* sub, const psnode_segments_f32* seg, void* workspace, size_t workspace_bytes,
-                                    void* stream) {
-    return k0_integrate(kFamMs, args, de_act, nullptr, tab, sub, workspace, workspace_bytes, stream, 0, seg);
+                                    const psnode_substeps_f32* sub, const psnode_segments_f32* seg, void* ws, size_t bytes, void* stream) {
+    return k0_integrate(kFamMs, args, {de_act, nullptr, tab, sub, seg}, ws, bytes, stream);
 }
 int32_t psnode_dae_integrate_ms_supported(const psnode_dae_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
                                           const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, const psnode_segments_f32* seg) {
-    return k0_supported(kFamMs, a, de_act, ae_act, tab, sub, seg);
+    return k0_supported(kFamMs, a, {de_act, ae_act, tab, sub, seg});
 }
 int32_t psnode_dae_integrate_ms_f32(const psnode_dae_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
-                                    const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, const psnode_segments_f32* seg,
-                                    void* workspace, size_t workspace_bytes, void* stream) {
-    return k0_integrate(kFamMs, args, de_act, ae_act, tab, sub, workspace, workspace_bytes, stream, 0, seg);
+                                    const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, const psnode_segments_f32* seg, void* ws,
+                                    size_t bytes, void* stream) {
+    return k0_integrate(kFamMs, args, {de_act, ae_act, tab, sub, seg}, ws, bytes, stream);
 }
 
 int32_t psnode_ode_kernel_for(const psnode_ode_args_f32* a) {

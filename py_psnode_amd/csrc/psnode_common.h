@@ -351,11 +351,11 @@ struct GenericBwdCall {
     const psnode_rk_tableau_f32* rk;      // generic_backward_launch<BuildRk>: the tableau (checked: rk_tableau_check); `method` is then not read
     int substeps;              // generic_backward_launch<BuildSub> (with rk): sub-steps per grid interval, > 1, and the sub-states K0 wrote
     const float* x_sub;        // [T-1, substeps-1, B, xd]
-    bool lin;                  // generic_backward_launch<BuildLin> (with rk; substeps >= 1): z | v interpolated linearly inside every grid interval
-    bool pev;                  // generic_backward_launch<BuildPev> (with rk; substeps >= 1; not with lin): `ev` is the [T-1, B] table of per-trajectory events
-    bool ab;                   // generic_backward_launch<BuildAb> (with a one-stage rk; substeps 1): two-step Adams-Bashforth; `ev` is null, the shared
+    bool lin;                  // (lin, pev, ab: not read -- psnode_backward.hip names the build, a BuildId of psnode_generic_family.h; kept, since
+    bool pev;                  //  the nine kernel objects are compiled against this layout.  BuildLin / BuildPev: with rk, substeps >= 1; BuildPev's
+    bool ab;                   //  `ev` is the [T-1, B] table.)  generic_backward_launch<BuildAb> (with a one-stage rk; substeps 1): `ev` is null, the shared
     bool ab_pt;                //   [T-1] table, or -- ab_pt -- the [T-1, B] table
-    int ms_every;              // generic_backward_launch<BuildMs> (with rk; substeps >= 1; not with lin / pev / ab) where > 0: grid point k > 0 with
+    int ms_every;              // generic_backward_launch<BuildMs> (with rk; substeps >= 1): grid point k > 0 with
     const float* ms_x_true;    //   k % ms_every == 0 restarted from the dataset row ms_x_true[k] ([T, B, xd]; may be null where T - 1 <= ms_every)
 };
 struct ActPair;     // psnode_act.h: the DE's and the AE's activation of a non-ELU(1) call
@@ -367,10 +367,10 @@ int generic_bwd_fits(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, int xd,
 // (ignores `act`), BuildAct (the activations of psnode_act.h), BuildPre (those and the pre-activation family), BuildRk (the tableau build:
 // every activation kind -- `act` is required, ELU(1) runs as ELU with alpha = 1 -- and c.rk in place of c.method; it keeps the
 // pre-activations like the pre build), BuildSub (the tableau build with c.substeps sub-steps per grid interval, read from c.x_sub), BuildLin
-// (the sub-step build, any c.substeps >= 1, with linearly interpolated externals: c.lin), BuildPev (the sub-step build, any c.substeps >= 1,
-// with per-trajectory events: c.pev, c.ev not null), BuildAb (BuildPev's policy as two-step Adams-Bashforth: c.ab, c.ab_pt), BuildMs (the
+// (the sub-step build, any c.substeps >= 1, with linearly interpolated externals), BuildPev (the sub-step build, any c.substeps >= 1,
+// with per-trajectory events: c.ev not null), BuildAb (BuildPev's policy as two-step Adams-Bashforth: c.ab_pt), BuildMs (the
 // sub-step build, any c.substeps >= 1, with multiple-shooting restarts: c.ms_every, c.ms_x_true).
-// psnode_backward.hip: generic_backward picks among them.
+// psnode_backward.hip: generic_backward picks among them by the call's BuildId (psnode_generic_family.h).
 template <class B>
 int generic_backward_launch(const GenericBwdCall& c, const ActPair* act, float* workspace, hipStream_t stream);
 // psnode_capi.hip: PSNODE_OK, PSNODE_ERR_NULL (no tableau) or PSNODE_ERR_METHOD (stages outside 1..4, a coefficient that is not finite, a

@@ -1,6 +1,7 @@
 """Shared host-side plumbing of the fused HIP integrator: recognising the reference's MLP right-hand sides, marshalling tensors into the
 C ABI structs (include/psnode_hip.h), the device-side event table, workspaces.  Nothing here computes on the CPU and nothing here
 imports oracle/."""
+import collections
 import ctypes
 import dataclasses
 import functools
@@ -195,6 +196,27 @@ def _act_ptrs(acts):
     return [ctypes.byref(a.abi()) if a is not None else None for a in acts]
 
 
+# What the entry points psnode_<stem>_<family>_* take behind the args struct, in this order: one psnode_act_f32 per MLP (acts), the tableau (tab),
+# the sub-steps struct (sub), the segments struct (seg) and -- the _f32 call alone -- the per_trajectory int (pt).  tf_args: its dae_backward takes
+# psnode_dae_bwd_tf_args_f32; x_sub: a forward call that saves for K5 keeps sub-state rows; workspace: the query that sizes its dae_backward -- "plain",
+# its "own", or the "rk" family's (the same policy, so the same fit, checks and layout for any sub-steps).
+Family = collections.namedtuple("Family", "acts tab sub seg pt tf_args x_sub workspace", defaults=(True, False, False, False, False, True, False, "own"))
+# The Python counterpart of kFamilies (csrc/psnode_generic_family.h): `GenericOpts`, `call_generic` and the prototypes of _lib.load read it.
+# "plain": the entry points without a family in their name; "none": no entry point at all; "tf": the "plain" dae_backward with dataset rows.
+FAMILIES = {
+    "plain": Family(acts=False, tf_args=False, workspace="plain"),
+    "none": Family(acts=False, tf_args=False, workspace="plain"),
+    "tf": Family(acts=False),
+    "act": Family(tf_args=False, workspace="plain"),
+    "rk": Family(tab=True),
+    "sub": Family(tab=True, sub=True, x_sub=True),
+    "lin": Family(tab=True, sub=True, x_sub=True),
+    "pev": Family(tab=True, sub=True, x_sub=True, workspace="rk"),
+    "ab": Family(pt=True, x_sub=True, workspace="rk"),
+    "ms": Family(tab=True, sub=True, seg=True, x_sub=True, workspace="rk"),
+}
+
+
 @dataclasses.dataclass(frozen=True)
 class GenericOpts:
     """What a call asks of the generic kernels K0 / K5 beyond the three built-in formulas with ELU(1), one step per grid interval and held
@@ -251,6 +273,7 @@ class GenericOpts:
         else:
             fam = "act" if any(a is not None for a in self.acts) else "plain"
         object.__setattr__(self, "family", fam)
+        object.__setattr__(self, "takes", FAMILIES[fam])      # (the family's row; an attribute, not a field of the dataclass)
 
     @staticmethod
     @functools.lru_cache(maxsize=256, typed=True)      # (a loop asks for the same immutable value call after call; typed: 2.0 and True are not 2 and 1)
@@ -258,37 +281,28 @@ class GenericOpts:
         method_id, stages, tab = method_info(method)
         return GenericOpts(acts, tab, substeps, externals, method_id, stages, per_trajectory, segment, is_ab(method))
 
-    def c_args(self, x_sub=None, x_true=None) -> list:
-        """The family's C arguments behind the args struct: none ("plain"); the acts ("act"); the acts and the tableau ("rk"); the acts,
-        the tableau or NULL (= the args' method) and a psnode_substeps_f32 with the sub-state rows `x_sub` or NULL ("sub", "lin", "pev").  The list
-        owns the structs: keep it until the call has returned.  "ms": those of "sub" and a psnode_segments_f32 with `segment` and the
-        dataset rows `x_true` of a backward call or NULL."""
-        fam = self.family
-        if fam == "plain":
-            return []
-        out = _act_ptrs(self.acts)
-        if fam == "ab":      # the acts and per_trajectory: is the event table, if there is one, [T-1, B]?
-            return out + [ctypes.c_int32(1 if self.per_trajectory else 0)]
-        if fam != "act":
+    def c_args(self, x_sub=None, x_true=None, family: Optional[str] = None) -> list:
+        """The C arguments behind the args struct that the family's row of FAMILIES lists: the acts, the tableau or NULL (= the args' method),
+        the sub-steps struct with `x_sub` or NULL, the segments struct with a backward call's `x_true` or NULL, per_trajectory.  The list
+        owns the structs: keep it until the call has returned.  family: the entry point's, where it is not the options' own."""
+        f = self.takes if family is None else FAMILIES[family]
+        out = _act_ptrs(self.acts) if f.acts else []
+        if f.tab:
             out.append(ctypes.byref(self.tab.abi()) if self.tab is not None else None)
-        if fam in ("sub", "lin", "pev", "ms"):
-            s = _lib.SubstepsF32()
-            s.substeps = self.substeps
-            s.x_sub = x_sub.data_ptr() if x_sub is not None and x_sub.numel() else None
-            out.append(ctypes.byref(s))
-        if fam == "ms":
-            g = _lib.SegmentsF32()
-            g.every = min(self.segment, 0x7fffffff)      # (a segment longer than any record: no restart)
-            g.x_true = x_true.data_ptr() if x_true is not None and x_true.numel() else None
-            out.append(ctypes.byref(g))
+        if f.sub:
+            out.append(ctypes.byref(_lib.SubstepsF32(self.substeps, x_sub.data_ptr() if x_sub is not None and x_sub.numel() else None)))
+        if f.seg:
+            rows = x_true.data_ptr() if x_true is not None and x_true.numel() else None
+            out.append(ctypes.byref(_lib.SegmentsF32(min(self.segment, 0x7fffffff), rows)))      # (a segment longer than any record: no restart)
+        if f.pt:      # (handed to the query too, which does not declare it and never reads it)
+            out.append(ctypes.c_int32(1 if self.per_trajectory else 0))
         return out
 
     def dae_backward_args(self, rows: bool):
-        """The args struct of a dae_backward call: psnode_dae_bwd_tf_args_f32 (flags 0 = no dataset rows) for the families "rk", "sub" and
-        "lin" and for a call with dataset rows x_true / i_true ("tf": the family of such a call that would otherwise be "plain"), else
-        psnode_dae_bwd_args_f32.  Dataset rows next to a non-ELU act alone: no entry point takes both (`call_generic` asserts it too)."""
+        """The args struct of a dae_backward call: psnode_dae_bwd_tf_args_f32 (flags 0 = no dataset rows) where the family's row of FAMILIES
+        says so and for a call with dataset rows x_true / i_true (which is "tf" where it would be "plain"), else psnode_dae_bwd_args_f32."""
         assert not (rows and self.family == "act"), "dae_backward: dataset rows with an activation other than ELU(1) have no entry point"
-        return _lib.DaeBwdTfArgsF32() if rows or self.family in ("rk", "sub", "lin", "pev", "ab", "ms") else _lib.DaeBwdArgsF32()
+        return _lib.DaeBwdTfArgsF32() if rows or self.takes.tf_args else _lib.DaeBwdArgsF32()
 
     def _first_option(self) -> str:
         """The first option the call carries, in the fixed order act, tableau, sub-steps, externals, as the subject of a refusal."""
@@ -367,9 +381,8 @@ def call_generic(lib, stem: str, kind: str, args, opts: GenericOpts, *tail, x_su
     family's `c_args`, *tail).  stem: "ode_integrate", "dae_integrate", "ode_backward", "dae_backward"; kind: "f32" (tail: workspace
     pointer, its size, stream), "supported" or, for the backward stems, "workspace_bytes".  A dae_backward whose `args` is a
     psnode_dae_bwd_tf_args_f32 (`dae_backward_args`) and whose family would be "plain" takes the "tf" entry points.  The workspace of
-    ode_backward, and of dae_backward in the families "plain" and "act", is the plain query's; that of dae_backward in the family "pev" is
-    the "rk" query's (the same build policy and layout; the family has no query of its own).  The family "none" (`GenericOpts.__post_init__`) has no
-    entry point: its "supported" is 0, any other kind is the caller's mistake (`require_generic` refuses such a call first).
+    ode_backward is the plain query's, that of dae_backward the one its family's row of FAMILIES names.  The family "none" has no entry
+    point: its "supported" is 0, any other kind is the caller's mistake (`require_generic` refuses such a call first).
     Returns (status or value, the symbol)."""
     fam = opts.family
     if fam == "none":
@@ -380,12 +393,11 @@ def call_generic(lib, stem: str, kind: str, args, opts: GenericOpts, *tail, x_su
         fam = "tf" if fam == "plain" else fam
     if kind == "workspace_bytes":
         assert stem in ("ode_backward", "dae_backward"), f"{stem} has no workspace query of its own"
-        if stem == "ode_backward" or fam == "act":
+        query = "plain" if stem == "ode_backward" else FAMILIES[fam].workspace
+        if query == "plain":
             fam = "plain"
-        elif fam in ("pev", "ab", "ms"):
-            # the _rk query with the call's acts and tableau -- a built-in method's stand-in is the one-stage tableau, the size does not
-            # depend on it: the same policy (every activation kind, the pre-activations kept), so the same fit, the same checks and the same
-            # layout as this family's build, whatever the number of sub-steps
+        elif query == "rk":
+            # the _rk query with the call's acts and tableau -- a built-in method's stand-in is the one-stage tableau, the size does not depend on it
             tab = opts.tab.abi() if opts.tab is not None else _lib.RkTableauF32()
             if opts.tab is None:
                 tab.stages, tab.b[0] = 1, 1.0
@@ -395,7 +407,7 @@ def call_generic(lib, stem: str, kind: str, args, opts: GenericOpts, *tail, x_su
         name = f"psnode_{stem}_{kind}"
         return getattr(lib, name)(ctypes.byref(args), *tail), name
     name = f"psnode_{stem}_{fam}_{kind}"
-    return getattr(lib, name)(ctypes.byref(args), *opts.c_args(x_sub, x_true), *tail), name
+    return getattr(lib, name)(ctypes.byref(args), *opts.c_args(x_sub, x_true, fam), *tail), name
 
 
 def act_of_module(m) -> Optional[object]:

@@ -130,7 +130,7 @@ def ode_integrate(method, de_layers: Layers, t, x, z, all_initial, event_t=None,
                      _empty((max(T - 1, 0), opts.stages, B, xd), dtype=torch.float32, device=dev))
             if T >= 2:
                 a.save_act, a.save_xstage = saved[0].data_ptr(), saved[1].data_ptr()
-        x_sub = _empty((max(T - 1, 0), substeps - 1, B, xd), dtype=torch.float32, device=dev) if save_sub and opts.family in ("sub", "lin", "pev", "ab", "ms") else None
+        x_sub = _empty((max(T - 1, 0), substeps - 1, B, xd), dtype=torch.float32, device=dev) if save_sub and opts.takes.x_sub else None
         ws, wp, wn = _workspace_of(lib.psnode_workspace_bytes(ctypes.byref(a.de), None), dev)
         rc, entry = call_generic(lib, "ode_integrate", "f32", a, opts, wp, wn, torch.cuda.current_stream(dev).cuda_stream, x_sub=x_sub)
     _mfma_miss(rc, kernel, entry, de_layers)
@@ -254,7 +254,7 @@ def dae_integrate(method, de_layers: Layers, ae_layers: Layers, x_init, t, x, z,
                 a.save_act = a.save_xstage = dummy.data_ptr()
             if n_ev:
                 a.save_ev_act, a.save_ev_i = saved[3].data_ptr(), saved[4].data_ptr()
-        x_sub = _empty((max(T - 1, 0), substeps - 1, B, xd), dtype=torch.float32, device=dev) if save_sub and opts.family in ("sub", "lin", "pev", "ab", "ms") else None
+        x_sub = _empty((max(T - 1, 0), substeps - 1, B, xd), dtype=torch.float32, device=dev) if save_sub and opts.takes.x_sub else None
         ws, wp, wn = _workspace_of(lib.psnode_workspace_bytes(ctypes.byref(a.de), ctypes.byref(a.ae)), dev)
         rc, entry = call_generic(lib, "dae_integrate", "f32", a, opts, wp, wn, torch.cuda.current_stream(dev).cuda_stream, x_sub=x_sub)
     _mfma_miss(rc, kernel, entry, de_layers)

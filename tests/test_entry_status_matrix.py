@@ -1,19 +1,22 @@
 """The status of every K0 / K5 entry point of the C ABI over a grid of argument defects, against a recorded file (no GPU, nothing launches).
 
-The 38 exported functions of the _act, _tf, _rk, _sub and _lin families (psnode_{ode,dae}_{integrate,backward}_{act,rk,sub,lin}_{supported,f32},
-psnode_dae_backward_{tf,rk,sub,lin}_workspace_bytes, psnode_dae_backward_tf_{supported,f32}) and the four plain _f32 entry points they
-forward to are called with valid dims-only args spoiled by no defect, by each single defect and by each pair of defects; with no data
-pointer set or with every required one set to a dummy; and, for the families that take them, with every act x tableau x sub-steps x
-workspace combination.  The order in which an entry point checks its arguments is behaviour (py_psnode_amd/_lib.py maps statuses to
-exception types): a call that is wrong in two ways has to go on answering with the status it answered with.
+The 62 exported functions of the _act, _tf, _rk, _sub, _lin, _pev, _ab and _ms families
+(psnode_{ode,dae}_{integrate,backward}_{act,rk,sub,lin,pev,ab,ms}_{supported,f32}, psnode_dae_backward_{tf,rk,sub,lin}_workspace_bytes,
+psnode_dae_backward_tf_{supported,f32}) and the four plain _f32 entry points they forward to are called with valid dims-only args spoiled
+by no defect, by each single defect and by each pair of defects; with no data pointer set or with every required one set to a dummy; and,
+for the families that take them, with every act x tableau x sub-steps x segments x per_trajectory x workspace combination.  The defect
+"ev" (event_idx set, the jumps it makes required set with the other pointers) is recorded for the _pev, _ab and _ms families alone.  The
+order in which an entry point checks its arguments is behaviour (py_psnode_amd/_lib.py maps statuses to exception types): a call that is
+wrong in two ways has to go on answering with the status it answered with.
 
 A row is one (entry point, defect set, pointers) with one character per remaining grid column:
     _f32               the digit n of status -n (1 NULL, 2 DIMS, 3 METHOD, 4 WORKSPACE, 5 UNSUPPORTED, 6 HIP); never 0 -- no case launches
     _supported         the value returned
     _workspace_bytes   0, or + for any other size
-Columns run act-major (groups parted by a blank), then tableau, sub-steps, workspace; a family has the columns of the arguments it takes.
-Rows of two defects carry a thinned act x sub-steps grid (PAIR_ACTS, PAIR_SUBS), rows of none or one the whole grid.
-tests/entry_status_matrix.txt holds the 6312 rows grouped: per entry point, each distinct row once, followed by the cases (defect set and
+Columns run act-major (groups parted by a blank), then tableau, sub-steps, segments (_ms), per_trajectory (the _ab call), workspace; a
+family has the columns of the arguments it takes.
+Rows of two defects carry a thinned act x sub-steps x segments grid (PAIR_ACTS, PAIR_SUBS, PAIR_SEGS), rows of none or one the whole grid.
+tests/entry_status_matrix.txt holds the 10584 rows grouped: per entry point, each distinct row once, followed by the cases (defect set and
 pointers, in the short codes of CODES) that give it.  A case whose status changes moves to another group in the file's diff, and the
 failing test names it in full.
 
@@ -37,25 +40,30 @@ DUMMY = 256          # a non-NULL, 256-byte aligned address that nothing on the 
 XD, ZD, VD, ID, HIDDEN, T, B = 8, 2, 2, 2, 64, 12, 5          # the dims-only args of tests/test_substeps_host.py
 
 # ---- the grid
-DEFECTS = ("method", "T0", "T1", "xdim0", "indim", "wide", "h512", "generic", "mfma", "wave", "save", "savex", "tf")
+DEFECTS = ("method", "T0", "T1", "xdim0", "indim", "wide", "h512", "generic", "mfma", "wave", "save", "savex", "tf", "ev")
 EXCLUSIVE = (("T0", "T1"), ("generic", "mfma"), ("generic", "wave"), ("mfma", "wave"))      # pairs that set one field twice
+EV_FAMILIES = ("pev", "ab", "ms")          # "ev" (event_idx set) is recorded for these alone: _pev needs the table, _ab reads it as shared or [T-1, B]
 SINGLE_ONLY = ("savex",)          # save_xstage / saved_xstage alone (the families differ in which pointers they look at): in no pair, for the file's size
 ACTS = ("null", "elu1", "tanh", "silu", "kind17", "elu-1")
 TABS = ("null", "heun", "stages5")
 SUBS = ("null", "0", "1", "2", "2+x_sub")
+SEGS = ("null", "0", "2", "2+x_true")          # _ms: T - 1 > 2, so a backward call restarts and needs x_true
+PTS = ("0", "1")          # _ab's call: per_trajectory
 WORKSPACES = ((None, 0), (DUMMY, 16))          # never a valid one: the last status a call can reach is PSNODE_ERR_WORKSPACE
 PAIR_ACTS = ("null", "tanh", "kind17")
 PAIR_SUBS = ("null", "1", "2", "2+x_sub")
+PAIR_SEGS = ("null", "2", "2+x_true")
 # stem -> (args kind, act arity, the families next to the plain entry point); "dae_backward_base": the entry points of the DAE backward that
 # take psnode_dae_bwd_args_f32 (no flags: the "tf" defect does not exist for them)
 STEMS = {
-    "ode_integrate": ("ode_fwd", 1, ("plain", "act", "rk", "sub", "lin")),
-    "dae_integrate": ("dae_fwd", 2, ("plain", "act", "rk", "sub", "lin")),
-    "ode_backward": ("ode_bwd", 1, ("plain", "act", "rk", "sub", "lin")),
+    "ode_integrate": ("ode_fwd", 1, ("plain", "act", "rk", "sub", "lin", "pev", "ab", "ms")),
+    "dae_integrate": ("dae_fwd", 2, ("plain", "act", "rk", "sub", "lin", "pev", "ab", "ms")),
+    "ode_backward": ("ode_bwd", 1, ("plain", "act", "rk", "sub", "lin", "pev", "ab", "ms")),
     "dae_backward_base": ("dae_bwd", 2, ("plain", "act")),
-    "dae_backward": ("dae_bwd", 2, ("tf", "rk", "sub", "lin")),
+    "dae_backward": ("dae_bwd", 2, ("tf", "rk", "sub", "lin", "pev", "ab", "ms")),
 }
-FAMILY_COLUMNS = {"plain": (), "tf": (), "act": ("act",), "rk": ("act", "tab"), "sub": ("act", "tab", "sub"), "lin": ("act", "tab", "sub")}
+FAMILY_COLUMNS = {"plain": (), "tf": (), "act": ("act",), "rk": ("act", "tab"), "sub": ("act", "tab", "sub"), "lin": ("act", "tab", "sub"),
+                  "pev": ("act", "tab", "sub"), "ab": ("act", "pt"), "ms": ("act", "tab", "sub", "seg")}          # pt: an int of the _f32 call alone
 
 
 def _act(name):
@@ -83,6 +91,14 @@ def _sub(name):
     s = _lib.SubstepsF32()
     s.substeps, s.x_sub = int(name[0]), DUMMY if name.endswith("x_sub") else None
     return s
+
+
+def _seg(name):
+    if name == "null":
+        return None
+    g = _lib.SegmentsF32()
+    g.every, g.x_true = int(name[0]), DUMMY if name.endswith("x_true") else None
+    return g
 
 
 def _mlp(m, in_dim, out, ptrs):
@@ -138,6 +154,12 @@ def _args(kind, defects, ptrs):
                 setattr(b, ("save_" if fwd else "saved_") + f, DUMMY)
         elif d == "tf":
             a.flags = 3 if dae else 1
+        elif d == "ev":          # the table, and with `ptrs` the jumps it makes required
+            b.event_idx = DUMMY
+            if ptrs:
+                b.z_jump = DUMMY
+                if dae:
+                    b.v_jump = DUMMY
     return a
 
 
@@ -156,7 +178,7 @@ def functions(stem):
             out.append((f"psnode_{name}_f32", fam, "f32"))
             continue
         out.append((f"psnode_{name}_{fam}_supported", fam, "supported"))
-        if name == "dae_backward" and fam != "act":
+        if name == "dae_backward" and fam in ("tf", "rk", "sub", "lin"):
             out.append((f"psnode_{name}_{fam}_workspace_bytes", fam, "workspace_bytes"))
         out.append((f"psnode_{name}_{fam}_f32", fam, "f32"))
     return out
@@ -167,21 +189,24 @@ def _columns(fam, thin):
     acts = (PAIR_ACTS if thin else ACTS) if "act" in cols else ("null",)
     tabs = TABS if "tab" in cols else ("null",)
     subs = (PAIR_SUBS if thin else SUBS) if "sub" in cols else ("null",)
-    return cols, acts, tabs, subs
+    segs = (PAIR_SEGS if thin else SEGS) if "seg" in cols else ("null",)
+    return cols, acts, tabs, subs, segs
 
 
 def _row(lib, stem, fn_name, fam, what, a, thin, extras):
     fn = getattr(lib, fn_name)
     n_act = STEMS[stem][1]
     arg0 = R(a.base) if stem == "dae_backward_base" else R(a)
-    cols, acts, tabs, subs = _columns(fam, thin)
+    cols, acts, tabs, subs, segs = _columns(fam, thin)
+    pts = PTS if "pt" in cols and what == "f32" else ("0",)
     groups = []
     for act in acts:
         chars = []
         for tab in tabs:
-            for sub in subs:
+            for sub, seg, pt in itertools.product(subs, segs, pts):
                 extra = ([extras["act", act]] * n_act if "act" in cols else []) + ([extras["tab", tab]] if "tab" in cols else []) + \
-                        ([extras["sub", sub]] if "sub" in cols else [])
+                        ([extras["sub", sub]] if "sub" in cols else []) + ([extras["seg", seg]] if "seg" in cols else []) + \
+                        ([int(pt)] if "pt" in cols and what == "f32" else [])
                 if what == "f32":
                     for ws, nbytes in WORKSPACES:
                         rc = fn(arg0, *extra, ws, nbytes, None)
@@ -200,7 +225,7 @@ def matrix():
     """{row label: row} over the whole grid, computed once."""
     lib = _lib.load()
     extras = {}
-    for kind, names, make in (("act", ACTS, _act), ("tab", TABS, _tab), ("sub", SUBS, _sub)):
+    for kind, names, make in (("act", ACTS, _act), ("tab", TABS, _tab), ("sub", SUBS, _sub), ("seg", SEGS, _seg)):
         for nm in names:
             obj = make(nm)
             extras[kind, nm] = (obj, R(obj) if obj is not None else None)
@@ -211,6 +236,8 @@ def matrix():
             for ptrs in (False, True):
                 a = _args(kind, ds, ptrs)
                 for fn_name, fam, what in functions(stem):
+                    if "ev" in ds and fam not in EV_FAMILIES:
+                        continue
                     label = f"{fn_name[len('psnode_'):]} {'+'.join(ds) or 'none'} {'ptrs' if ptrs else 'null'}"
                     rows[label] = _row(lib, stem, fn_name, fam, what, a, len(ds) == 2, refs)
     return rows
@@ -218,7 +245,7 @@ def matrix():
 
 # ---- the recorded file: per entry point, one group per distinct row -- the row, then every (defect set, pointers) that gives it
 CODES = {"method": "M", "T0": "T0", "T1": "T1", "xdim0": "X", "indim": "I", "wide": "W", "h512": "H", "generic": "g", "mfma": "f", "wave": "v",
-         "save": "S", "savex": "Sx", "tf": "F"}
+         "save": "S", "savex": "Sx", "tf": "F", "ev": "E"}
 NAMES = {c: d for d, c in CODES.items()}
 
 
@@ -231,7 +258,8 @@ def write_recorded(rows, commit):
     with open(RECORDED, "w") as f:
         f.write(f"# tests/test_entry_status_matrix.py --record, from the library built at commit {commit}\n")
         f.write(f"# columns: act {ACTS} x tableau {TABS} x sub-steps {SUBS} x workspace (NULL, 16 bytes)\n")
-        f.write(f"# rows of two defects: act {PAIR_ACTS}, sub-steps {PAIR_SUBS}\n")
+        f.write(f"# _ms: segments {SEGS} between sub-steps and workspace; the _ab call: per_trajectory {PTS} in front of the workspace\n")
+        f.write(f"# rows of two defects: act {PAIR_ACTS}, sub-steps {PAIR_SUBS}, segments {PAIR_SEGS}\n")
         f.write("# cases: " + " ".join(f"{c}={d}" for d, c in CODES.items()) + " ok=none, joined by '.'; then + every required pointer set, - none\n")
         for fn, groups in by_fn.items():
             f.write(f"== {fn}\n")
@@ -259,8 +287,8 @@ def read_recorded():
 
 def test_grid_covers_every_entry_point_and_launches_nothing():
     names = {fn for stem in STEMS for fn, _, _ in functions(stem)}
-    fams = [n for n in _lib.EXPORTS if any(f"_{f}_" in n for f in ("act", "tf", "rk", "sub", "lin")) and ("_integrate_" in n or "_backward_" in n)]
-    assert len(fams) == 38 and set(fams) <= names and len(names) == 42
+    fams = [n for n in _lib.EXPORTS if any(f"_{f}_" in n for f in ("act", "tf", "rk", "sub", "lin", "pev", "ab", "ms")) and ("_integrate_" in n or "_backward_" in n)]
+    assert len(fams) == 62 and set(fams) <= names and len(names) == 66
     seen = set()
     for label, row in matrix().items():
         if label.split()[0].endswith("_f32"):

@@ -5,10 +5,16 @@ tests/generic_entry_table.txt has one line per case, `<case> -> <outcome>`:
     <stem> <kind> acts=.. tab=.. substeps=.. externals=.. rows=..    the symbol called and, per argument, its ctypes struct, NULL or int
     refuse <name> kernel=.. saved=.. act=.. tab=.. substeps=.. externals=..    "ok", or the option the refusal names
 Lines that end in `# rule` are written from the rule below (`rule`), not recorded: the backward calls with dataset rows and every
-workspace query sit inside functions that need device tensors.  Every other line is recorded by driving the helpers `GenericOpts`
-replaces (`call_entry` / `entry_supported` with the structs their callers hand them; `_act_route_ok`, `_rk_route_ok`, `sub_route_ok` in the
-order the forward functions call them) with the same stand-in, at the commit BEFORE the change, never from the changed code:
+workspace query sat inside functions that need device tensors.  Every other line in front of the second header was recorded by driving
+the helpers `GenericOpts` replaced (`call_entry` / `entry_supported` with the structs their callers hand them; `_act_route_ok`,
+`_rk_route_ok`, `sub_route_ok` in the order the forward functions called them) with the same stand-in, at commit 4b90c56.
+The lines behind the second header carry per_trajectory (`pt=`), segment and the method "ab2" (`tab=ab2`), which became the families
+_pev, _ms and _ab later: `<case> pt=.. segment=..` with the call as above, "0 without a call" (the family "none"), or the exception type and
+the options its message names; and `refuse <require_generic | require_plain | no_teacher_forcing> ..` with "ok" or the same.  They are
+recorded by driving `GenericOpts` / `call_generic` themselves with the stand-in, at the commit BEFORE a change to them, never from the
+changed code:
     git checkout <that commit> -- py_psnode_amd && python tests/test_generic_opts_host.py --record [--commit <its id>]"""
+import ctypes
 import dataclasses
 import inspect
 import itertools
@@ -53,9 +59,13 @@ class Recorder:
 def describe(arg) -> str:
     if arg is None:
         return "NULL"
+    if isinstance(arg, ctypes.c_int32):
+        return f"int32[{arg.value}]"
     obj = getattr(arg, "_obj", None)          # ctypes.byref(obj)
     if obj is None:
         return type(arg).__name__
+    if isinstance(obj, _lib.SegmentsF32):
+        return f"SegmentsF32[{obj.every}]"
     return f"SubstepsF32[{obj.substeps}]" if isinstance(obj, _lib.SubstepsF32) else type(obj).__name__
 
 
@@ -255,37 +265,102 @@ def test_saved_tensors_unpack_by_name():
     assert autograd._layers((a, b, c, p), 1) == ([(a, b)], [(c, p)]) and autograd._layers((a, b, c, p)) == [(a, b), (c, p)]
 
 
-# ---- the recorder (run at the commit before the change: it drives the helpers that commit has)
+# ---- 4. per-trajectory events, segments and "ab2": the rows added to the table when those options had become three families
+AB2 = "ab2"
+NAMED = {"act": "activation other than ELU", "tableau": "Runge-Kutta tableau", "substeps": "substeps", "externals": "externals='linear'",
+         "per_trajectory": "per_trajectory=True", "segment": "segment=", "ab2": "Adams-Bashforth"}
+EXT_HEADER = "# the rows of per_trajectory, segment and the method 'ab2'"
+EXT_KINDS = {"ode_integrate": ("f32", "supported"), "dae_integrate": ("f32", "supported"), "ode_backward": ("f32", "supported", "workspace_bytes"),
+             "dae_backward": ("f32", "supported", "workspace_bytes")}
+
+
+def named_options(e) -> str:
+    """The exception's type and every option its message names in front of the values it got, in the order of NAMED."""
+    return f"{type(e).__name__} {'+'.join(k for k, text in NAMED.items() if text in str(e).split('got ')[0])}"
+
+
+def extended_rows(stem):
+    """option_rows x the method 'ab2' x per_trajectory x segment, without the rows option_rows has."""
+    n = STEMS[stem][0]
+    for acts, method, (sub, ext), pt, seg in itertools.product(itertools.product((None, TANH), repeat=n), ("rk4", HEUN, AB2), SUB_EXT, (False, True),
+                                                               (None, 2)):
+        if method == AB2 or pt or seg is not None:
+            yield acts, method, sub, ext, pt, seg
+
+
+def _method_name(method) -> str:
+    return "-" if method == "rk4" else str(method)
+
+
+def extended_case(stem, kind, acts, method, substeps, externals, pt, seg) -> str:
+    return (f"{stem} {kind} acts={','.join('Tanh' if a else '-' for a in acts)} tab={_method_name(method)} substeps={substeps} "
+            f"externals={externals} rows=- pt={int(pt)} segment={seg or '-'}")
+
+
+def extended_now(stem, kind, acts, method, substeps, externals, pt, seg) -> str:
+    """The call the case makes, "<value> without a call" (the family "none"), or the exception: what `__post_init__` or `call_generic` raise."""
+    lib = Recorder()
+    try:
+        opts = _common.GenericOpts.of(method, acts, substeps, externals, pt, seg)
+        args = STEMS[stem][1]() if STEMS[stem][1] else opts.dae_backward_args(False)
+        value, _ = _common.call_generic(lib, stem, kind, args, opts, *((1, 2, 3) if kind == "f32" else ()))
+    except (ValueError, AssertionError) as e:
+        return named_options(e) if isinstance(e, ValueError) else "AssertionError"
+    assert value == 0 and len(lib.calls) <= 1, lib.calls
+    return lib.calls[0] if lib.calls else f"{value} without a call"
+
+
+def refusal_cases():
+    """(case, thunk): require_generic over kernel, saved rows and teacher forcing, require_plain and no_teacher_forcing, for every valid
+    set of the three options (and interpolated externals, which two of them refuse) that has at least one of them."""
+    sets = [(m, pt, seg, ext) for m, pt, seg, ext in itertools.product(("rk4", AB2), (False, True), (None, 2), ("hold", "linear"))
+            if (m == AB2 and seg is None and ext == "hold") or (m != AB2 and (pt or seg is not None))]
+    for m, pt, seg, ext in sets:
+        tag = f"method={m} pt={int(pt)} segment={seg or '-'} externals={ext}"
+        for name, kernel, saved, tf in itertools.product(STEMS, ("auto", "mfma"), (False, True), (False, True)):
+            yield (f"refuse require_generic {name} kernel={kernel} saved={int(saved)} tf={int(tf)} {tag}",
+                   lambda o=(m, (None,) * STEMS[name][0], 1, ext, pt, seg), a=(name, kernel, saved, tf):
+                   _common.GenericOpts.of(*o).require_generic(a[0], a[1], a[2], teacher_forced=a[3]))
+        o = (m, (None,), 1, ext, pt, seg)
+        yield f"refuse require_plain {tag}", lambda o=o: _common.GenericOpts.of(*o).require_plain("x")
+        for tf in (False, True):
+            yield f"refuse no_teacher_forcing tf={int(tf)} {tag}", lambda o=o, tf=tf: _common.GenericOpts.of(*o).no_teacher_forcing("x", tf)
+
+
+def refusal_now(thunk) -> str:
+    try:
+        thunk()
+    except (ValueError, _lib.UnsupportedShapeError) as e:
+        return named_options(e)
+    return "ok"
+
+
+def test_every_extended_entry_and_refusal_is_the_recorded_one():
+    table, ruled = read_recorded()
+    cases = [(extended_case(stem, kind, *row), (stem, kind) + row) for stem in STEMS for kind in EXT_KINDS[stem] for row in extended_rows(stem)]
+    assert len(cases) == (2 + 2 + 3 + 3) * 80 + (2 + 3) * 80 and not ruled & {c for c, _ in cases}          # 80 rows per act tuple: 2 + 2 * 2 of them
+    got = {table[c] for c, _ in cases}
+    for fam in ("pev", "ab", "ms"):          # each family is reached from every stem, and so are "none" and the constructor's refusals
+        assert all(any(q.startswith(f"psnode_{stem}_{fam}_") for q in got) for stem in STEMS), fam
+    assert {"0 without a call", "AssertionError", "ValueError segment+ab2", "ValueError substeps+externals+ab2"} <= got
+    bad = [f"{c}\n    table {table[c]}\n    now   {extended_now(*a)}" for c, a in cases if extended_now(*a) != table[c]]
+    refusals = list(refusal_cases())
+    assert len(refusals) == 8 * (4 * 8 + 1 + 2) and {table[c] for c, _ in refusals} >= {"ok", "ValueError segment", "ValueError ab2"}
+    bad += [f"{c}\n    table {table[c]}\n    now   {refusal_now(t)}" for c, t in refusals if refusal_now(t) != table[c]]
+    assert not bad, "\n".join(bad[:40])
+    assert len(table) == 914 - 2 + len(cases) + len(refusals)          # and the file holds nothing else
+
+
+# ---- the recorder of section 4 (run at the commit before the change).  The lines in front of EXT_HEADER were recorded at commit 4b90c56 from
+# helpers that `GenericOpts` has since replaced; they are kept as they are.
 def record(commit):
-    lines = []
-    for stem in STEMS:
-        for kind in ("f32", "supported"):
-            for acts, tab, (n, ext) in option_rows(stem):
-                lib = Recorder()
-                sub = _common.substeps_abi(n, None, ext)
-                args = STEMS[stem][1]() if STEMS[stem][1] else (_lib.DaeBwdTfArgsF32() if tab is not None or sub is not None else _lib.DaeBwdArgsF32())
-                if kind == "f32":
-                    _common.call_entry(lib, stem, args, acts, 1, 2, 3, tab, sub)
-                else:
-                    _common.entry_supported(lib, stem, args, acts, tab, sub)
-                assert len(lib.calls) == 1 and lib.calls[0] == rule(stem, kind, acts, tab, n, ext), (lib.calls, rule(stem, kind, acts, tab, n, ext))
-                lines.append(f"{entry_case(stem, kind, acts, tab, n, ext)} -> {lib.calls[0]}")
-    for c in rule_cases():
-        lines.append(f"{entry_case(*c)} -> {rule(*c)}  # rule")
-    from py_psnode_amd.fused import forward
-    for name, kernel, saved, act, tab, substeps, externals in itertools.product(
-            ("ode_integrate", "dae_integrate"), KERNELS, (False, True), (False, True), (False, True), (1, 2), ("hold", "linear")):
-        try:
-            forward._act_route_ok(name, act, kernel, saved)
-            forward._rk_route_ok(name, HEUN if tab else None, kernel, saved)
-            _common.sub_route_ok(name, substeps, kernel, saved, externals)
-            outcome = "ok"
-        except _lib.UnsupportedShapeError as e:
-            outcome = named_option(str(e))
-        lines.append(f"{refuse_case(name, kernel, saved, act, tab, substeps, externals)} -> {outcome}")
+    with open(RECORDED) as f:
+        kept = f.read().split(EXT_HEADER)[0]
+    lines = [f"{extended_case(stem, kind, *row)} -> {extended_now(stem, kind, *row)}" for stem in STEMS for kind in EXT_KINDS[stem]
+             for row in extended_rows(stem)]
+    lines += [f"{case} -> {refusal_now(thunk)}" for case, thunk in refusal_cases()]
     with open(RECORDED, "w") as f:
-        f.write(f"# tests/test_generic_opts_host.py --record, from py_psnode_amd at commit {commit}\n")
-        f.write("# lines that end in '# rule' are written from the rule (tests/test_generic_opts_host.py: rule), not recorded\n")
+        f.write(kept + f"{EXT_HEADER}: tests/test_generic_opts_host.py --record, from py_psnode_amd at commit {commit}\n")
         f.write("\n".join(lines) + "\n")
     print(f"{len(lines)} lines -> {RECORDED} ({os.path.getsize(RECORDED)} bytes)")
 
