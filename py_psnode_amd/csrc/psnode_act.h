@@ -1,9 +1,8 @@
 // Hidden-layer activations other than ELU(1) for the generic kernels K0 (psnode_generic_impl.h) and K5 (psnode_generic_bwd_impl.h).
 //
 // The ELU(1) kernels of both files do not see any of this: they keep elu_quad / elu_grad_quad (psnode_common.h).  The activation kernels
-// (generic_act_kernel / generic_backward_act_kernel: the same sources compiled a second time, psnode_generic_act.hip /
-// psnode_generic_bwd_act.hip) take an ActDev per MLP as a kernel argument and switch on its kind, which is uniform over the launch
-// (scalar branches, no divergence).
+// (the same sources compiled a second time under the BuildAct policy, psnode_generic_act.hip / psnode_generic_bwd_act.hip) take an
+// ActDev per MLP as a kernel argument and switch on its kind, which is uniform over the launch (scalar branches, no divergence).
 //
 // Every listed activation but one has a derivative that is a function of the layer OUTPUT h (K5 rebuilds and keeps layer outputs, not
 // pre-activations):
@@ -25,6 +24,7 @@
 // ELU(1) kernels ship (psnode_common.h).
 #pragma once
 #include "psnode_common.h"
+#include "psnode_generic_build.h"
 
 namespace psnode {
 
@@ -272,27 +272,18 @@ inline int act_pair(const psnode_act_f32* de, const psnode_act_f32* ae, ActPair&
 size_t generic_plan(const IntegrateDev& a, bool dae, unsigned& mask, bool lin = false);      // lin: the linear-externals build's layout
 int generic_reg_mode(const IntegrateDev& a, bool dae);
 bool generic_wide_mode(const IntegrateDev& a, bool dae);
-// psnode_generic_act.hip: K0 with the activations of `act` (the ELU(1) call is launch_generic)
-hipError_t launch_generic_act(const IntegrateDev& a, bool dae, const ActPair& act, hipStream_t stream);
-// psnode_generic_pre.hip: the same for an ActPair with a kind of the pre-activation family (act_pair_pre)
-// (K5's launchers: psnode_common.h, generic_backward_launch<Bd>)
-hipError_t launch_generic_pre(const IntegrateDev& a, bool dae, const ActPair& act, hipStream_t stream);
-// psnode_generic_rk.hip: K0 with the Butcher tableau `rk` in place of a.method, every activation kind (ELU(1) as ELU with alpha = 1)
-hipError_t launch_generic_rk(const IntegrateDev& a, bool dae, const ActPair& act, const psnode_rk_tableau_f32& rk, hipStream_t stream);
-// psnode_generic_sub.hip: the tableau build with sub.n sub-steps per grid interval (sub.x_sub: the sub-states for K5, or null)
-hipError_t launch_generic_sub(const IntegrateDev& a, bool dae, const ActPair& act, const psnode_rk_tableau_f32& rk, const SubDev& sub,
-                              hipStream_t stream);
-// psnode_generic_lin.hip: the sub-step build (sub.n >= 1) with z | v interpolated linearly inside every grid interval
-hipError_t launch_generic_lin(const IntegrateDev& a, bool dae, const ActPair& act, const psnode_rk_tableau_f32& rk, const SubDev& sub,
-                              hipStream_t stream);
-// psnode_generic_pev.hip: the sub-step build (sub.n >= 1) with per-trajectory events: a.ev is the [T-1, B] table and must not be null
-hipError_t launch_generic_pev(const IntegrateDev& a, bool dae, const ActPair& act, const psnode_rk_tableau_f32& rk, const SubDev& sub,
-                              hipStream_t stream);
-// psnode_generic_ab.hip: two-step Adams-Bashforth on the per-trajectory build's policy; rk is the one-stage tableau, a.ev may be null
-hipError_t launch_generic_ab(const IntegrateDev& a, bool dae, const ActPair& act, const psnode_rk_tableau_f32& rk, const AbDev& ab,
-                             hipStream_t stream);
-// psnode_generic_ms.hip: the sub-step build (ms.n >= 1) with multiple-shooting restarts from the rows of a.x, which then has all T of them
-hipError_t launch_generic_ms(const IntegrateDev& a, bool dae, const ActPair& act, const psnode_rk_tableau_f32& rk, const MsDev& ms,
-                             hipStream_t stream);
+// What a K0 call carries beyond its args: the build of the generic kernel that runs it and that build's kernel arguments.  The plain entry
+// points pass K0Call{}: ELU(1), the args' method, one step per interval -- the only call the MFMA kernels take.
+struct K0Call {
+    BuildId build;
+    ActPair act;                   // every build but kBuildElu1
+    psnode_rk_tableau_f32 rk;      // the builds with a tableau: given, or the args' method written as one (family_tableau)
+    SubDev sub;                    // kBuildSub, kBuildLin, kBuildPev, kBuildMs: sub-steps per grid interval and x_sub
+    int ev_pt, ms_every;           // kBuildAb: the event table is [T-1, B]; kBuildMs: grid point k > 0 with k % ms_every == 0 restarts from row k of x
+};
+// K0's launcher (psnode_generic_impl.h), instantiated once per build policy in that policy's object, as K5's generic_backward_launch<B>
+// (psnode_common.h) is: reads of `call` what B's kernels take.  BuildPev: a.ev is the [T-1, B] table and not null; BuildMs: a.x has all T rows.
+template <class B>
+hipError_t launch_generic(const IntegrateDev& a, bool dae, const K0Call& call, hipStream_t stream);
 
 }  // namespace psnode

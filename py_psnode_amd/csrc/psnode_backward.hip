@@ -294,7 +294,7 @@ int k5_backward(Family fam, const Args* a, const CallOpts& o, void* workspace, s
     if (!ptrs_ok(a) || (nsub > 1 && b.T >= 2 && !o.sub->x_sub) || (f.needs_events && !b.event_idx)) return PSNODE_ERR_NULL;
     if (f.seg && b.T - 1 > o.seg->every && !o.seg->x_true) return PSNODE_ERR_NULL;
     if (!workspace_ok(workspace, workspace_bytes, generic_bwd_workspace_floats(&b.de, ae_of(b), b.B) * sizeof(float))) return PSNODE_ERR_WORKSPACE;
-    GenericBwdCall c = generic_bwd_call(*a);      // (the build is named below: c.lin / c.pev / c.ab stay unset, no launcher reads them)
+    GenericBwdCall c = generic_bwd_call(*a);
     if (f.tab != kTabNone) c.rk = &t;
     c.substeps = nsub;
     c.x_sub = o.sub ? o.sub->x_sub : nullptr;

@@ -76,16 +76,7 @@ __global__ void event_table_kernel(long long n_steps, const float* clock, long l
     if (cnt > 1 && dup_flag) *dup_flag = 1;
 }
 
-// What a K0 call carries beyond its args: the build of the generic kernel that runs it (psnode_generic_family.h) and that build's kernel
-// arguments.  The plain entry points pass K0Call{}: ELU(1), the args' method, one step per interval -- the only call the MFMA kernels take.
-struct K0Call {
-    BuildId build;
-    ActPair act;                   // every build but kBuildElu1
-    psnode_rk_tableau_f32 rk;      // the builds with a tableau: given, or the args' method written as one (family_tableau)
-    SubDev sub;                    // kBuildSub, kBuildLin, kBuildPev, kBuildMs: sub-steps per grid interval and x_sub
-    int ev_pt, ms_every;           // kBuildAb: the event table is [T-1, B]; kBuildMs: grid point k > 0 with k % ms_every == 0 restarts from row k of x
-};
-
+// (call: psnode_act.h, K0Call -- the plain entry points pass K0Call{})
 int dispatch(IntegrateDev& d, bool dae, int kernel, const psnode_mlp_f32* de, const psnode_mlp_f32* ae, void* workspace,
              size_t workspace_bytes, hipStream_t stream, const K0Call& call) {
     if (!workspace_ok(workspace, workspace_bytes, psnode_workspace_bytes(de, ae))) return PSNODE_ERR_WORKSPACE;
@@ -108,15 +99,15 @@ int dispatch(IntegrateDev& d, bool dae, int kernel, const psnode_mlp_f32* de, co
     hipError_t e = launch_pack_image(d.de, dae ? &d.ae : nullptr, d.xd, d.xd + d.zd + (dae ? d.vd + d.id : 0), d.zd + (dae ? d.vd : 0), stream);
     if (e != hipSuccess) return PSNODE_ERR_HIP;
     switch (call.build) {
-        case kBuildElu1: e = launch_generic(d, dae, stream); break;
-        case kBuildAct: e = launch_generic_act(d, dae, call.act, stream); break;
-        case kBuildPre: e = launch_generic_pre(d, dae, call.act, stream); break;
-        case kBuildRk: e = launch_generic_rk(d, dae, call.act, call.rk, stream); break;
-        case kBuildSub: e = launch_generic_sub(d, dae, call.act, call.rk, call.sub, stream); break;
-        case kBuildLin: e = launch_generic_lin(d, dae, call.act, call.rk, call.sub, stream); break;
-        case kBuildPev: e = launch_generic_pev(d, dae, call.act, call.rk, call.sub, stream); break;
-        case kBuildAb: e = launch_generic_ab(d, dae, call.act, call.rk, AbDev{1, nullptr, call.ev_pt}, stream); break;
-        case kBuildMs: e = launch_generic_ms(d, dae, call.act, call.rk, MsDev{call.sub.n, call.sub.x_sub, call.ms_every, nullptr}, stream); break;
+        case kBuildElu1: e = launch_generic<BuildElu1>(d, dae, call, stream); break;
+        case kBuildAct: e = launch_generic<BuildAct>(d, dae, call, stream); break;
+        case kBuildPre: e = launch_generic<BuildPre>(d, dae, call, stream); break;
+        case kBuildRk: e = launch_generic<BuildRk>(d, dae, call, stream); break;
+        case kBuildSub: e = launch_generic<BuildSub>(d, dae, call, stream); break;
+        case kBuildLin: e = launch_generic<BuildLin>(d, dae, call, stream); break;
+        case kBuildPev: e = launch_generic<BuildPev>(d, dae, call, stream); break;
+        case kBuildAb: e = launch_generic<BuildAb>(d, dae, call, stream); break;
+        case kBuildMs: e = launch_generic<BuildMs>(d, dae, call, stream); break;
     }
     return ok_or_hip(e);
 }

@@ -55,40 +55,6 @@ struct IntegrateDev {
     unsigned k0_res;       // generic kernel: which layers' weight images are resident in LDS (bit l: DE layer l, bit 8 + l: AE layer l)
 };
 
-// Sub-steps per grid interval (psnode_substeps_f32, include/psnode_hip.h), as the sub-step builds of K0 / K5 take them: one further kernel
-// argument behind the tableau.  Every grid interval [t[k], t[k + 1]] runs n equal sub-steps; x_sub [T-1, n-1, B, xd] keeps the start state
-// of sub-steps 1 .. n-1 of every interval (row (k, j - 1): sub-step j) -- written by K0 when the pointer is not null, read by K5.
-struct SubDev {
-    int n;
-    float* x_sub;
-};
-// What the Adams-Bashforth builds of K0 / K5 take in SubDev's place (the bodies read it under the same name): one sub-step, no x_sub, and
-// the shape of the event table -- ev_pt != 0: int32 [T-1, B], every trajectory its own column; 0: the shared int32 [T-1], which every
-// column reads through a column stride of 0.  The table may be null (no events).
-struct AbDev {
-    int n;
-    float* x_sub;
-    int ev_pt;
-};
-// (the bodies ask through an overload: a discarded `if constexpr` arm of a non-dependent SubDev is still type-checked)
-__host__ __device__ inline int ev_table_pt(const SubDev&) { return 0; }
-__host__ __device__ inline int ev_table_pt(const AbDev& s) { return s.ev_pt; }
-// What the multiple-shooting builds of K0 / K5 take in SubDev's place (psnode_segments_f32, include/psnode_hip.h): the sub-step build's
-// argument plus `every` >= 1 -- grid point k > 0 with k % every == 0 restarts from the dataset row -- and, for K5, those rows x_true
-// [T, B, xd] (K0 reads IntegrateDev::x; null where no step restarts).
-struct MsDev {
-    int n;
-    float* x_sub;
-    int every;
-    const float* x_true;
-};
-__host__ __device__ inline int ev_table_pt(const MsDev&) { return 0; }
-// (asked through overloads for the reason above)
-template <class S> __host__ __device__ inline int ms_every(const S&) { return 0; }
-__host__ __device__ inline int ms_every(const MsDev& s) { return s.every; }
-template <class S> __host__ __device__ inline const float* ms_x_true(const S&) { return nullptr; }
-__host__ __device__ inline const float* ms_x_true(const MsDev& s) { return s.x_true; }
-
 // ELU(alpha=1) with the negative branch at expm1 quality: ATen's CPU kernel (what the reference runs) returns
 // expm1(x) for x <= 0 -- checked bitwise in the build container ("ELU").
 // libm flavour, used by the generic kernel:
@@ -261,7 +227,6 @@ __host__ __device__ __forceinline__ constexpr float rk_b(int method, int s) {
 }
 
 // psnode_generic.hip
-hipError_t launch_generic(const IntegrateDev& a, bool dae, hipStream_t stream);
 size_t generic_lds_bytes(const IntegrateDev& a, bool dae, bool lin = false);      // lin: K0's linear-externals build (nzv more rows)
 hipError_t launch_pack_transpose(const MlpDev& de, const MlpDev* ae, hipStream_t stream);   // generic backward: transposed weights
 hipError_t launch_pack_image(const MlpDev& de, const MlpDev* ae, int xd, int n, int nzv, hipStream_t stream);   // generic forward: MFMA images
@@ -351,10 +316,8 @@ struct GenericBwdCall {
     const psnode_rk_tableau_f32* rk;      // generic_backward_launch<BuildRk>: the tableau (checked: rk_tableau_check); `method` is then not read
     int substeps;              // generic_backward_launch<BuildSub> (with rk): sub-steps per grid interval, > 1, and the sub-states K0 wrote
     const float* x_sub;        // [T-1, substeps-1, B, xd]
-    bool lin;                  // (lin, pev, ab: not read -- psnode_backward.hip names the build, a BuildId of psnode_generic_family.h; kept, since
-    bool pev;                  //  the nine kernel objects are compiled against this layout.  BuildLin / BuildPev: with rk, substeps >= 1; BuildPev's
-    bool ab;                   //  `ev` is the [T-1, B] table.)  generic_backward_launch<BuildAb> (with a one-stage rk; substeps 1): `ev` is null, the shared
-    bool ab_pt;                //   [T-1] table, or -- ab_pt -- the [T-1, B] table
+    bool ab_pt;                // generic_backward_launch<BuildAb> (with a one-stage rk; substeps 1): `ev` is null, the shared [T-1] table, or -- ab_pt --
+                               //   the [T-1, B] table.  (BuildLin / BuildPev: with rk, substeps >= 1; BuildPev's `ev` is the [T-1, B] table.)
     int ms_every;              // generic_backward_launch<BuildMs> (with rk; substeps >= 1): grid point k > 0 with
     const float* ms_x_true;    //   k % ms_every == 0 restarted from the dataset row ms_x_true[k] ([T, B, xd]; may be null where T - 1 <= ms_every)
 };
@@ -370,7 +333,7 @@ int generic_bwd_fits(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, int xd,
 // (the sub-step build, any c.substeps >= 1, with linearly interpolated externals), BuildPev (the sub-step build, any c.substeps >= 1,
 // with per-trajectory events: c.ev not null), BuildAb (BuildPev's policy as two-step Adams-Bashforth: c.ab_pt), BuildMs (the
 // sub-step build, any c.substeps >= 1, with multiple-shooting restarts: c.ms_every, c.ms_x_true).
-// psnode_backward.hip: generic_backward picks among them by the call's BuildId (psnode_generic_family.h).
+// psnode_backward.hip: generic_backward picks among them by the call's BuildId.
 template <class B>
 int generic_backward_launch(const GenericBwdCall& c, const ActPair* act, float* workspace, hipStream_t stream);
 // psnode_capi.hip: PSNODE_OK, PSNODE_ERR_NULL (no tableau) or PSNODE_ERR_METHOD (stages outside 1..4, a coefficient that is not finite, a

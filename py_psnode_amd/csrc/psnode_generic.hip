@@ -1,28 +1,8 @@
-// K0, the ELU(1) object (psnode_generic_impl.h): generic_kernel, launch_generic, and the host's plan / fit / pack code, which every build
-// shares and which is compiled here once.
-#include "psnode_generic_build.h"
-namespace psnode { namespace { using Bd = BuildElu1; } }
+// K0, the ELU(1) object (psnode_generic_impl.h), and the host's plan / fit / pack code, which every build shares and which is compiled here once.
+#define PSNODE_BUILD BuildElu1
 #include "psnode_generic_impl.h"
 
 namespace psnode {
-namespace {
-
-template <bool DAE, int MODE, int ML, int QM = 4>
-__global__ __launch_bounds__(NT) void generic_kernel(const IntegrateDev a) {
-    const NoActPair act;                   // no activation argument: ActCtx is empty
-    const psnode_rk_tableau_f32 rk{};      // never read: the tableau code is under `if constexpr (Bd::rk)`
-    const SubDev sub{};                    // never read: the sub-step code is under `if constexpr (Bd::sub)`
-#include "psnode_generic_body.h"
-}
-template <> struct GenericKernels<Bd> {
-    template <bool DAE, int MODE, int ML, int QM = 4> static constexpr auto get() { return &generic_kernel<DAE, MODE, ML, QM>; }
-};
-
-}  // namespace
-
-hipError_t launch_generic(const IntegrateDev& a, bool dae, hipStream_t stream) {
-    return launch_generic_build<Bd>(a, dae, stream);
-}
 
 namespace {
 struct PackArgs {

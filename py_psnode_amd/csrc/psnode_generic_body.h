@@ -1,10 +1,7 @@
-// The body of K0's kernel (psnode_generic_impl.h), as text: each of the nine objects writes its own __global__ -- generic_kernel(a),
-// generic_act_kernel(a, act), generic_pre_act_kernel(a, act), generic_rk_kernel(a, act, rk), generic_sub_kernel(a, act, rk, sub),
-// generic_lin_kernel(a, act, rk, sub), generic_pev_kernel(a, act, rk, sub), generic_ab_kernel(a, act, rk, sub: an AbDev),
-// generic_ms_kernel(a, act, rk, sub: an MsDev) -- and includes this file between its braces.
+// The body of K0's kernel, as text: generic_kernel (psnode_generic_impl.h) includes this file between its braces.
 // Template parameters in scope: DAE, MODE, ML, QM.  Names in scope: a, act (ActPair; NoActPair in the ELU(1) object), rk (read under
-// Bd::rk only) and sub (SubDev, read under Bd::sub only); the objects without one declare an unread one.  The build policy Bd decides the
-// rest with `if constexpr`.
+// Bd::rk only) and sub (Bd::Sub, read under Bd::sub only); a build whose kernel takes fewer arguments sees an unread default.  The build
+// policy Bd decides the rest with `if constexpr`.
     constexpr bool STREAM = MODE == 2;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x;

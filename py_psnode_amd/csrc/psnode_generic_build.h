@@ -1,21 +1,66 @@
 // The build policy of the generic kernels K0 (psnode_generic_impl.h) and K5 (psnode_generic_bwd_impl.h): what separates the nine objects each
-// is compiled into, as constants the language can see.
+// is compiled into, as constants the language can see.  Each object is one file that names its policy and includes the impl header:
+//   #define PSNODE_BUILD BuildAct
+//   #include "psnode_generic_impl.h"
+// The kernel, its instance table and the launcher are written once, in the impl header; what a policy's kernels take behind their args struct
+// follows from the policy (n_extra, Sub).
 #pragma once
+#include <hip/hip_runtime.h>
+#include <type_traits>
 
 namespace psnode {
+
+// Sub-steps per grid interval (psnode_substeps_f32, include/psnode_hip.h), as the sub-step builds of K0 / K5 take them: one further kernel
+// argument behind the tableau.  Every grid interval [t[k], t[k + 1]] runs n equal sub-steps; x_sub [T-1, n-1, B, xd] keeps the start state
+// of sub-steps 1 .. n-1 of every interval (row (k, j - 1): sub-step j) -- written by K0 when the pointer is not null, read by K5.
+struct SubDev {
+    int n;
+    float* x_sub;
+};
+// What the Adams-Bashforth builds of K0 / K5 take in SubDev's place (the bodies read it under the same name): one sub-step, no x_sub, and
+// the shape of the event table -- ev_pt != 0: int32 [T-1, B], every trajectory its own column; 0: the shared int32 [T-1], which every
+// column reads through a column stride of 0.  The table may be null (no events).
+struct AbDev {
+    int n;
+    float* x_sub;
+    int ev_pt;
+};
+// (the bodies ask through an overload: a discarded `if constexpr` arm of a non-dependent SubDev is still type-checked)
+__host__ __device__ inline int ev_table_pt(const SubDev&) { return 0; }
+__host__ __device__ inline int ev_table_pt(const AbDev& s) { return s.ev_pt; }
+// What the multiple-shooting builds of K0 / K5 take in SubDev's place (psnode_segments_f32, include/psnode_hip.h): the sub-step build's
+// argument plus `every` >= 1 -- grid point k > 0 with k % every == 0 restarts from the dataset row -- and, for K5, those rows x_true
+// [T, B, xd] (K0 reads IntegrateDev::x, psnode_common.h; null where no step restarts).
+struct MsDev {
+    int n;
+    float* x_sub;
+    int every;
+    const float* x_true;
+};
+__host__ __device__ inline int ev_table_pt(const MsDev&) { return 0; }
+// (asked through overloads for the reason above)
+template <class S> __host__ __device__ inline int ms_every(const S&) { return 0; }
+__host__ __device__ inline int ms_every(const MsDev& s) { return s.every; }
+template <class S> __host__ __device__ inline const float* ms_x_true(const S&) { return nullptr; }
+__host__ __device__ inline const float* ms_x_true(const MsDev& s) { return s.x_true; }
+
 
 template <bool ACT, bool PRE, bool RK, bool SUB = false, bool LIN = false, bool PEV = false, bool AB = false, bool MS = false>
 struct GenericBuild {
     static constexpr bool act = ACT;      // the hidden-layer activation is a kernel argument (ActPair, psnode_act.h), not ELU(1)
     static constexpr bool pre = PRE;      // the hidden layers' pre-activations u are kept next to h (SiLU / GELU / Mish differentiate from u)
     static constexpr bool rk = RK;        // the stage loops read a psnode_rk_tableau_f32 kernel argument instead of a.method
-    static constexpr bool sub = SUB;      // every grid interval runs SubDev::n equal sub-steps (a further kernel argument, psnode_common.h)
+    static constexpr bool sub = SUB;      // every grid interval runs SubDev::n equal sub-steps (a further kernel argument, above)
     static constexpr bool lin = LIN;      // every stage reads z | v interpolated linearly between the interval's two grid points (needs sub)
     static constexpr bool pev = PEV;      // the event table is [T-1, B]: every trajectory jumps at its own steps (needs sub; not with lin)
-    static constexpr bool ab = AB;        // two-step Adams-Bashforth: one DE evaluation per step, the previous slope and per-column c0 / c1 (AbDev,
-                                          // psnode_common.h; needs pev, whose per-column event index also serves a shared table through a column stride of 0)
-    static constexpr bool ms = MS;        // multiple shooting: every MsDev::every-th grid point restarts from the dataset row (MsDev, psnode_common.h;
+    static constexpr bool ab = AB;        // two-step Adams-Bashforth: one DE evaluation per step, the previous slope and per-column c0 / c1 (AbDev;
+                                          // needs pev, whose per-column event index also serves a shared table through a column stride of 0)
+    static constexpr bool ms = MS;        // multiple shooting: every MsDev::every-th grid point restarts from the dataset row (MsDev;
                                           // needs sub; not with lin, pev or ab)
+    // The kernels' arguments behind the args struct, each a by-value parameter of its own: ActPair (act) | psnode_rk_tableau_f32 (rk) | Sub (sub).
+    // A kernel without one of them names the never-read default of kernel_arg in its place.
+    static constexpr int n_extra = SUB ? 3 : (RK ? 2 : (ACT ? 1 : 0));
+    using Sub = std::conditional_t<AB, AbDev, std::conditional_t<MS, MsDev, SubDev>>;
     // K5's waves per SIMD: the fully streamed instances (STR 2) that fitted 256 registers keep two workgroups per CU -- every one of the
     // act build, the ELU(1) build's with the accumulators in LDS, none of the builds that keep u
     static constexpr int two_waves(bool gg, int str) { return PRE ? 1 : (str == 2 && (ACT || !gg) ? 2 : 1); }
@@ -37,6 +82,20 @@ template <> struct SubIter<false> {
     static constexpr bool more() { return false; }
 };
 
+// Kernel argument I behind the args struct: the I-th of `extra`, or -- the build takes fewer -- a local default that is never read
+template <int I, class D> __host__ __device__ constexpr D kernel_arg(const D& dflt) { return dflt; }
+template <int I, class D, class E0, class... E>
+__host__ __device__ constexpr decltype(auto) kernel_arg(const D& dflt, const E0& e0, const E&... e) {
+    if constexpr (I == 0) return (e0); else return kernel_arg<I - 1>(dflt, e...);
+}
+// The policy's Sub argument from what a call carries, for both directions (K0 writes x_sub and has no x_true; K5 reads both)
+template <class B>
+typename B::Sub build_sub(int n, float* x_sub, int ev_pt, int ms_every, const float* x_true) {
+    if constexpr (B::ab) return AbDev{1, nullptr, ev_pt};
+    else if constexpr (B::ms) return MsDev{n, x_sub, ms_every, x_true};
+    else return SubDev{n, x_sub};
+}
+
 using BuildElu1 = GenericBuild<false, false, false>;
 using BuildAct = GenericBuild<true, false, false>;
 using BuildPre = GenericBuild<true, true, false>;
@@ -46,5 +105,6 @@ using BuildLin = GenericBuild<true, true, true, true, true>;      // BuildSub's 
 using BuildPev = GenericBuild<true, true, true, true, false, true>;      // BuildSub's policy with per-trajectory events; every substeps >= 1
 using BuildAb = GenericBuild<true, true, true, true, false, true, true>;      // BuildPev's policy as Adams-Bashforth 2; one sub-step, a one-stage tableau
 using BuildMs = GenericBuild<true, true, true, true, false, false, false, true>;      // BuildSub's policy with multiple-shooting restarts; every substeps >= 1
+enum BuildId { kBuildElu1, kBuildAct, kBuildPre, kBuildRk, kBuildSub, kBuildLin, kBuildPev, kBuildAb, kBuildMs };      // what a call names its build with
 
 }  // namespace psnode

@@ -1,25 +1,8 @@
-// K5, the ELU(1) object (psnode_generic_bwd_impl.h): generic_backward_kernel, its launcher, and the exported host queries of all four builds.
-#include "psnode_generic_build.h"
-namespace psnode { namespace { using Bd = BuildElu1; } }
+// K5, the ELU(1) object (psnode_generic_bwd_impl.h), and the exported host queries of every build.
+#define PSNODE_BUILD BuildElu1
 #include "psnode_generic_bwd_impl.h"
 
 namespace psnode {
-namespace {
-
-template <bool gg, bool REG, bool ggA = gg, int STR = 0>
-__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(Bd::two_waves(gg, STR), 8))) void generic_backward_kernel(const GBwd a) {
-    const NoActPair act;                   // no activation argument: ActCtx is empty
-    const psnode_rk_tableau_f32 rk{};      // never read: the tableau code is under `if constexpr (Bd::rk)`
-    const SubDev sub{};                    // never read: the sub-step code is under `if constexpr (Bd::sub)`
-#include "psnode_generic_bwd_body.h"
-}
-template <> struct GenericBwdKernels<Bd> {
-    template <bool gg, bool REG, bool ggA, int STR> static constexpr auto get() { return &generic_backward_kernel<gg, REG, ggA, STR>; }
-};
-
-}  // namespace
-
-template int generic_backward_launch<Bd>(const GenericBwdCall&, const ActPair*, float*, hipStream_t);
 
 // shared by the ODE and DAE entry points (psnode_backward.hip calls this for kernel = generic / unsupported MFMA shapes)
 size_t generic_bwd_workspace_floats(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, long long B) {

@@ -1,10 +1,6 @@
-// The body of K5's kernel (psnode_generic_bwd_impl.h), as text: each of the nine objects (the eighth: generic_backward_ab_kernel(a, act,
-// rk, sub: an AbDev); the ninth: generic_backward_ms_kernel(a, act, rk, sub: an MsDev)) writes its own __global__ --
-// generic_backward_kernel(a), generic_backward_act_kernel(a, act), generic_backward_pre_act_kernel(a, act),
-// generic_backward_rk_kernel(a, act, rk), generic_backward_sub_kernel(a, act, rk, sub), generic_backward_lin_kernel(a, act, rk, sub),
-// generic_backward_pev_kernel(a, act, rk, sub) -- and includes this file between its braces.
+// The body of K5's kernel, as text: generic_backward_kernel (psnode_generic_bwd_impl.h) includes this file between its braces.
 // Template parameters in scope: gg, REG, ggA, STR.  Names in scope: a, act (ActPair; NoActPair in the ELU(1) object), rk (read under
-// Bd::rk only) and sub (SubDev, read under Bd::sub only); the objects without one declare an unread one.
+// Bd::rk only) and sub (Bd::Sub, read under Bd::sub only); a build whose kernel takes fewer arguments sees an unread default.
     constexpr bool DE_TM = REG || STR == 2;      // the DE's LDS accumulators are tile-major
     constexpr bool AE_TM = STR >= 1;
     extern __shared__ __attribute__((aligned(16))) float lds[];

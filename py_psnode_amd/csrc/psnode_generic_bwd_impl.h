@@ -15,41 +15,23 @@
 // Teacher forcing (GBwd::flags) changes the outer sweep only: which rows a step starts from and which adjoints travel to the step before.
 #include <string.h>
 
-// Nine objects are compiled from this header, one per build policy (psnode_generic_build.h).  Each of psnode_generic_bwd{,_act,_pre,_rk,_sub,_lin,_pev,_ab,_ms}.hip
-// names its policy `Bd` in front of the include, writes its kernel around psnode_generic_bwd_body.h and instantiates the launcher:
-//   BuildElu1  generic_backward_kernel(a)                    ELU(1) and its derivative
-//   BuildAct   generic_backward_act_kernel(a, act)           the DE's and the AE's activation as a second kernel argument (ActPair)
-//   BuildPre   generic_backward_pre_act_kernel(a, act)       also keeps each hidden layer's pre-activation u in a region of its own at the end of
-//              the LDS layout (GMlpT<true>::pre, UpreOff<true>: [unit][TP] rows on the staged path, quad-row images on the register / streamed
-//              paths); the derivative reads u next to h (from u for SiLU / GELU / Mish, from h for the other kinds)
-//   BuildRk    generic_backward_rk_kernel(a, act, rk)        the pre build whose stage loops (3a) / (3b) read the stage count and the coefficients
-//              from a launch-uniform psnode_rk_tableau_f32 instead of rk_stages / rk_a / rk_b of a.method, which it does not read
-//   BuildSub   generic_backward_sub_kernel(a, act, rk, sub)  the tableau build with SubDev::n sub-steps per grid interval: an inner reverse loop
-//              around (2) .. (3b) of the kernel body that starts each sub-step from the state K0 stored in SubDev::x_sub; no LDS of its own
-//   BuildLin   generic_backward_lin_kernel(a, act, rk, sub)  the sub-step build (every n >= 1) with z | v interpolated linearly per stage: ext's
-//              z | v rows are refilled per stage from the interval's two ends, a second accumulator takes the right end's adjoint; 3 nzv rows of LDS
-//   BuildPev   generic_backward_pev_kernel(a, act, rk, sub)  the sub-step build (every n >= 1) with a [T-1, B] event table: a thread reads its own
-//              column's event index, the event-time head is evaluated where any column of the workgroup has a hit and taken -- forward and
-//              in the VJP, whose output gradient is zero in the other columns -- per column; no LDS and no workspace of its own
-//   BuildAb    generic_backward_ab_kernel(a, act, rk, ab)    the per-trajectory build as two-step Adams-Bashforth (one stage, one sub-step; AbDev in
-//              SubDev's place): the DE's VJP takes phi_k = c0_k g_{k+1} + c1_{k+1} g_{k+2}, g_{k+2} and the per-column c1 live in the gks slots a
-//              one-stage build leaves free; the event table is [T-1, B], the shared [T-1] (column stride 0) or null; no LDS of its own
-//   BuildMs    generic_backward_ms_kernel(a, act, rk, ms)    the sub-step build (every n >= 1) with multiple-shooting restarts (MsDev in SubDev's
-//              place): a restart step recomputes from MsDev::x_true[k] and the head at that row, and lets neither its start adjoint nor the
-//              x part of that head's VJP travel on; the restart is a countdown in a scalar; no LDS and no workspace of its own
+// One object per build policy is compiled from this header (psnode_generic_build.h: each alias with its one-line description).  A policy's
+// file psnode_generic_bwd_<fam>.hip names it as PSNODE_BUILD in front of the include; the kernel (generic_backward_kernel, around
+// psnode_generic_bwd_body.h) and the launcher (generic_backward_launch<Bd>) are written below, once.
 // The policy decides in the language: the kernel-argument structs (GMlpT / GBwdT: the pre fields are a base that is empty elsewhere), the
 // activation context ActCtx every device function takes, the stage coefficients (coef_a, coef_b) and
 // `if constexpr` in the kernel body and the launcher.  The host's fit and layout functions take `pre` at run time.
 #pragma once
 #include "psnode_act.h"
+#include "psnode_generic_tile.h"
 #include "psnode_launch.h"
 
 namespace psnode {
 namespace {
 
-constexpr int TB = 16;    // trajectories per workgroup
+using Bd = PSNODE_BUILD;
+
 constexpr int TP = 20;    // padded row stride (floats)
-constexpr int NT = 256;
 
 // Kernel-argument structs.  The pre and tableau builds carry two more fields, at the end of each struct: they are a base class that is empty
 // in the other builds, so that the ELU(1) and act kernels' argument layout has no trace of them.
@@ -112,14 +94,11 @@ template <bool PRE> __device__ __forceinline__ float* u_region(float* lds, const
 }
 
 __device__ __forceinline__ float delu(float h) { return elu_grad(h); }   // ELU'(pre) from h = ELU(pre)
-typedef float f4 __attribute__((ext_vector_type(4)));
 
 // The hidden-layer activation of one MLP as the device functions below see it: one ordinary parameter, shaped by the build policy.
 // act1 / actq: the activation of a value / of four.  keep1 / keepq: store a hidden layer's pre-activation u at [row][c] of its [unit][TP]
 // rows / at quad idx of its quad-row image (layer l's region, GMlp::pre[l]).  dact1 / dactq: the derivative, from h and -- where the build
 // keeps it -- the u stored there.
-struct NoAct {};                            // what the ELU(1) kernel, which has no `act` argument, names act.de / act.ae
-struct NoActPair { NoAct de, ae; };
 template <bool ACT, bool PRE> struct ActCtxT;
 template <> struct ActCtxT<false, false> {      // ELU(1): nothing to carry, nothing kept
     __device__ __forceinline__ ActCtxT(NoAct, float*) {}
@@ -316,41 +295,7 @@ __device__ __forceinline__ float* g_vjp(const GMlp& m, const float* acts, float*
 // pass (psnode_generic.hip).  Activations and deltas additionally live in QUAD-ROW buffers (float index ((col / 4) * 16 + traj) * 4 + col % 4:
 // the B operands of four MFMA steps are one lane-linear ds_read_b128, a D tile one ds_write_b128); the [unit][TP] copies stay, they are what
 // the weight-gradient MFMAs (contraction over the trajectories) and the step's glue read.
-__host__ __device__ constexpr int up16(int v) { return (v + 15) & ~15; }
-__device__ __forceinline__ int qi(int r, int c) { return ((((r >> 2) * TB) + c) << 2) | (r & 3); }
-__device__ __forceinline__ void mfma_quad(const f4 av, const f4 bv, f4& acc) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[e], bv[e], acc, 0, 0, 0);
-}
-template <int Q, int QM>
-__device__ __forceinline__ f4 tile_reg(const f4* bq, const f4 (&wa)[QM]) {
-    f4 bv[Q];
-#pragma unroll
-    for (int c = 0; c < Q; ++c) bv[c] = bq[c * 64];
-    __builtin_amdgcn_sched_barrier(0);
-    f4 acc = f4{0.f, 0.f, 0.f, 0.f}, acc2 = acc;
-#pragma unroll
-    for (int c = 0; c < Q; ++c) mfma_quad(wa[c], bv[c], (c & 1) ? acc2 : acc);
-    return Q > 1 ? acc + acc2 : acc;
-}
-template <int QM>
-__device__ __forceinline__ f4 tile_reg_any(int S4, const f4* bq, const f4 (&wa)[QM]) {
-    if constexpr (QM > 4) {
-        switch (S4) {
-            case 5: return tile_reg<5, QM>(bq, wa);
-            case 6: return tile_reg<6, QM>(bq, wa);
-            case 7: return tile_reg<7, QM>(bq, wa);
-            case 8: return tile_reg<8, QM>(bq, wa);
-            default: break;
-        }
-    }
-    switch (S4) {
-        case 1: return tile_reg<1, QM>(bq, wa);
-        case 2: return tile_reg<2, QM>(bq, wa);
-        case 3: return tile_reg<3, QM>(bq, wa);
-        default: return tile_reg<4, QM>(bq, wa);
-    }
-}
+// (up16, qi, mfma_quad, tile_reg, tile_reg_any: psnode_generic_tile.h)
 
 struct RegFwd { f4 first[8]; f4 rest[3][4]; };          // layer 0: <= 128 input columns; layers 1..3: <= 64
 struct RegBwd { f4 first[2][4]; f4 rest[3][4]; };       // transposed: layer 0 has <= 8 tiles over its inputs (two per wave), the others <= 4
@@ -665,8 +610,19 @@ __device__ __forceinline__ float* g_vjp_str(const GMlp& m, const float* const* t
 // head streamed, 2 = both MLPs streamed (0: whatever is not on the register path stages its weights through LDS).
 // (waves per SIMD, Bd::two_waves: the fully streamed instances that fitted 256 registers -- two workgroups per CU where their LDS allows
 //  it -- keep that budget: the sweep-level flag values must not cost them the second workgroup)
-// (the six kernels: psnode_generic_bwd{,_act,_pre,_rk,_sub,_lin}.hip around psnode_generic_bwd_body.h)
-template <class B> struct GenericBwdKernels;      // the kernels of policy B, by their template arguments: specialised by the object that defines them
+// Extra: Bd::n_extra by-value arguments behind `a`, in the order act | rk | sub; the body sees all three names.  (B = Bd, named in the template
+// for the kernel's symbol alone.)
+template <class B, bool gg, bool REG, bool ggA, int STR, class... Extra>
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(Bd::two_waves(gg, STR), 8))) void generic_backward_kernel(const GBwd a, const Extra... extra) {
+    static_assert(std::is_same_v<B, Bd> && sizeof...(Extra) == B::n_extra, "the policy's argument list");
+    const auto& act = kernel_arg<0>(NoActPair{}, extra...);                // ELU(1): no activation argument, ActCtx is empty
+    const auto& rk = kernel_arg<1>(psnode_rk_tableau_f32{}, extra...);     // never read without one: the tableau code is under `if constexpr (Bd::rk)`
+    const auto& sub = kernel_arg<2>(SubDev{}, extra...);                   // never read without one: the sub-step code is under `if constexpr (Bd::sub)`
+#include "psnode_generic_bwd_body.h"
+}
+template <class B, class... Extra> struct GenericBwdKernels {
+    template <bool gg, bool REG, bool ggA, int STR> static constexpr auto get() { return &generic_backward_kernel<B, gg, REG, ggA, STR, Extra...>; }
+};
 
 // (g.wt, the transposed weights of the forward recomputation, are workspace segments: gbwd_layout)
 int fill_gmlp(const psnode_mlp_f32& m, GMlp& g) {
@@ -844,24 +800,25 @@ int generic_backward_launch(const GenericBwdCall& c, const ActPair* act, float* 
     if ((a.de_reg || a.str == 2) && launch_pack_plain_images(mde, L.img[0], L.imgT[0], stream) != hipSuccess) return PSNODE_ERR_HIP;
     if (dae && a.str >= 1 && launch_pack_plain_images(mae, L.img[1], L.imgT[1], stream) != hipSuccess) return PSNODE_ERR_HIP;
     // <DE accumulators global, DE on the register path, AE accumulators global, streamed MLPs>
-    using K = GenericBwdKernels<Pol>;
-    auto kern = K::template get<false, false, false, 0>();
-    const int g = a.gacc_global;
-    if (a.de_reg && a.str == 1) kern = g == 1 ? K::template get<true, true, true, 1>() : (g == 2 ? K::template get<false, true, true, 1>() : K::template get<false, true, false, 1>());
-    else if (a.de_reg) kern = g == 1 ? K::template get<true, true, true, 0>() : (g == 2 ? K::template get<false, true, true, 0>() : K::template get<false, true, false, 0>());
-    else if (a.str == 2) kern = g == 1 ? K::template get<true, false, true, 2>() : (g == 2 ? K::template get<false, false, true, 2>() : K::template get<false, false, false, 2>());
-    else kern = g ? K::template get<true, false, true, 0>() : K::template get<false, false, false, 0>();
     const unsigned nwg = (unsigned)((B + TB - 1) / TB);
-    auto go = [&](const auto&... extra) { return launch_attr(true, kern, dim3(nwg), dim3(NT), lds, stream, a, extra...); };
+    auto go = [&](const auto&... extra) {
+        using K = GenericBwdKernels<Pol, std::decay_t<decltype(extra)>...>;
+        auto kern = K::template get<false, false, false, 0>();
+        const int g = a.gacc_global;
+        if (a.de_reg && a.str == 1) kern = g == 1 ? K::template get<true, true, true, 1>() : (g == 2 ? K::template get<false, true, true, 1>() : K::template get<false, true, false, 1>());
+        else if (a.de_reg) kern = g == 1 ? K::template get<true, true, true, 0>() : (g == 2 ? K::template get<false, true, true, 0>() : K::template get<false, true, false, 0>());
+        else if (a.str == 2) kern = g == 1 ? K::template get<true, false, true, 2>() : (g == 2 ? K::template get<false, false, true, 2>() : K::template get<false, false, false, 2>());
+        else kern = g ? K::template get<true, false, true, 0>() : K::template get<false, false, false, 0>();
+        return launch_attr(true, kern, dim3(nwg), dim3(NT), lds, stream, a, extra...);
+    };
     hipError_t e;
-    if constexpr (Pol::ab) e = go(*act, *c.rk, AbDev{1, nullptr, c.ab_pt ? 1 : 0});
-    else if constexpr (Pol::ms) e = go(*act, *c.rk, MsDev{c.substeps, const_cast<float*>(c.x_sub), c.ms_every, c.ms_x_true});
-    else if constexpr (Pol::sub) e = go(*act, *c.rk, SubDev{c.substeps, const_cast<float*>(c.x_sub)});
+    if constexpr (Pol::sub) e = go(*act, *c.rk, build_sub<Pol>(c.substeps, const_cast<float*>(c.x_sub), c.ab_pt ? 1 : 0, c.ms_every, c.ms_x_true));
     else if constexpr (Pol::rk) e = go(*act, *c.rk);
     else if constexpr (Pol::act) e = go(*act);
     else e = go();
     if (e != hipSuccess) return PSNODE_ERR_HIP;
     return ok_or_hip(launch_reduce_partials(a.wpart, c.gparams_de, c.gparams_ae, a.de.np, dae ? a.ae.np : 0, (int)nwg, stream));
 }
+template int generic_backward_launch<Bd>(const GenericBwdCall&, const ActPair*, float*, hipStream_t);
 
 }  // namespace psnode

@@ -1,23 +1,3 @@
-// K5 with sub-steps per grid interval (SubDev: psnode_substeps_f32), a launch-time Butcher tableau and every activation kind: the BuildSub
-// object of psnode_generic_bwd_impl.h.  A translation unit of its own, so that the kernels of the other four K5 objects stay exactly what
-// they are.
-#include "psnode_generic_build.h"
-namespace psnode { namespace { using Bd = BuildSub; } }
+// K5 with sub-steps per grid interval on the tableau build: the BuildSub object (psnode_generic_build.h).
+#define PSNODE_BUILD BuildSub
 #include "psnode_generic_bwd_impl.h"
-
-namespace psnode {
-namespace {
-
-template <bool gg, bool REG, bool ggA = gg, int STR = 0>
-__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(Bd::two_waves(gg, STR), 8))) void generic_backward_sub_kernel(const GBwd a, const ActPair act, const psnode_rk_tableau_f32 rk, const SubDev sub) {
-#include "psnode_generic_bwd_body.h"
-}
-template <> struct GenericBwdKernels<Bd> {
-    template <bool gg, bool REG, bool ggA, int STR> static constexpr auto get() { return &generic_backward_sub_kernel<gg, REG, ggA, STR>; }
-};
-
-}  // namespace
-
-template int generic_backward_launch<Bd>(const GenericBwdCall&, const ActPair*, float*, hipStream_t);
-
-}  // namespace psnode

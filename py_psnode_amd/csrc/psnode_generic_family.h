@@ -18,7 +18,8 @@
 //   only next to an ELU(1) pair, the recipe dims and the LDS fit of the family's build.  Pointers: the teacher-forcing rows among them.
 //   The DAE's _act family takes psnode_dae_bwd_args_f32, the others the _tf struct: its _sub with substeps == 1 and no tableau goes to _tf
 //   (ELU(1) pair) or refuses flags (PSNODE_ERR_UNSUPPORTED, before the method is looked at) and goes to _act with the base args.
-// A new family adds a value of Family, its row, its wrappers; a new build also a BuildId and its case in dispatch and generic_backward.
+// A new family adds a value of Family, its row, its wrappers; a new build also a policy alias and a BuildId (psnode_generic_build.h), its line
+// in dispatch and in generic_backward, and one two-line file per direction (psnode_generic_<fam>.hip, psnode_generic_bwd_<fam>.hip).
 // Code of one direction on purpose, and no column: DESIGN.md, "One family table for both directions".
 #pragma once
 
@@ -27,7 +28,6 @@
 
 namespace psnode {
 
-enum BuildId { kBuildElu1, kBuildAct, kBuildPre, kBuildRk, kBuildSub, kBuildLin, kBuildPev, kBuildAb, kBuildMs };      // psnode_generic_build.h
 enum Family { kFamTf, kFamAct, kFamRk, kFamSub, kFamLin, kFamPev, kFamAb, kFamMs };
 // the tableau: no argument, `method` is read | NULL is PSNODE_ERR_NULL | NULL is the args' method as one | no argument, always one stage
 enum Tab { kTabNone, kTabRequired, kTabOrMethod, kTabOneStage };

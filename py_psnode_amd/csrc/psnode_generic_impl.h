@@ -25,45 +25,25 @@
 // Padded columns: the image holds zeros there and the input builders write zeros into the pad columns of the first layer's input; a
 // hidden layer's pad units come out of the MFMA as ELU(0 + 0) = 0.
 //
-// Nine objects are compiled from this header, one per build policy (psnode_generic_build.h).  Each of psnode_generic{,_act,_pre,_rk,_sub,_lin,_pev,_ab,_ms}.hip
-// names its policy `Bd` in front of the include, writes its kernel around psnode_generic_body.h and its exported launcher over
-// launch_generic_build:
-//   BuildElu1  generic_kernel(a), launch_generic                    ELU(1)
-//   BuildAct   generic_act_kernel(a, act), launch_generic_act       the DE's and the AE's activation as a second kernel argument (six kinds)
-//   BuildPre   generic_pre_act_kernel(a, act), launch_generic_pre   all ten kinds (SiLU / GELU / GELU(tanh) / Mish too; the forward keeps no u)
-//   BuildRk    generic_rk_kernel(a, act, rk), launch_generic_rk     the pre build with a launch-uniform Butcher tableau of up to four stages
-//              (psnode_rk_tableau_f32) applied in the stage pass instead of the three built-in formulas; a.method is not read
-//   BuildSub   generic_sub_kernel(a, act, rk, sub), launch_generic_sub   the tableau build with SubDev::n sub-steps per grid interval: the
-//              evaluation loop of a step runs n times on h / n, outputs and look-ahead rows advance behind the last one; no LDS of its own
-//   BuildLin   generic_lin_kernel(a, act, rk, sub), launch_generic_lin   the sub-step build (every n >= 1) with z | v interpolated linearly per
-//              stage between the interval's left rows and the next grid point's; nzv * TB floats of LDS of its own (generic_lds_bytes(.., lin))
-//   BuildPev   generic_pev_kernel(a, act, rk, sub), launch_generic_pev   the sub-step build (every n >= 1) with a [T-1, B] event table: every
-//              thread carries its own column's event index in a register, the event slot runs where any column of the workgroup has a
-//              hit and is taken per column; no LDS of its own
-//   BuildAb    generic_ab_kernel(a, act, rk, ab), launch_generic_ab   the per-trajectory build as two-step Adams-Bashforth (one stage, one
-//              sub-step; AbDev in SubDev's place): the final pass forms x + c0 f_k + c1 f_{k-1} with per-column c0 / c1; the previous slope
-//              and c1 live in the kbuf slots a one-stage build never writes; the event table is [T-1, B], the shared [T-1] (column stride
-//              0) or null; no LDS of its own
-//   BuildMs    generic_ms_kernel(a, act, rk, ms), launch_generic_ms   the sub-step build (every n >= 1) with multiple-shooting restarts (MsDev
-//              in SubDev's place): at every MsDev::every-th grid point the step-input pass takes the dataset row of a.x as the step's start
-//              and as the AE input's x, and the event slot runs as the restart head; a countdown in a scalar; no LDS of its own
+// One object per build policy is compiled from this header (psnode_generic_build.h: each alias with its one-line description).  A policy's
+// file psnode_generic_<fam>.hip names it as PSNODE_BUILD in front of the include; the kernel (generic_kernel, around psnode_generic_body.h)
+// and the launcher (launch_generic<Bd>) are written below, once.
 // The device functions take the activation as one ordinary parameter, ActCtx; the kernel body chooses the tableau code with
 // `if constexpr (Bd::rk)`, the sub-step code with `if constexpr (Bd::sub)`.  The host's plan / fit / pack code is compiled once, in
 // psnode_generic.hip.
 #pragma once
 #include "psnode_act.h"
+#include "psnode_generic_tile.h"
 #include "psnode_launch.h"
 
 namespace psnode {
 
 namespace {
 
-typedef float f4 __attribute__((ext_vector_type(4)));
+using Bd = PSNODE_BUILD;
 
 // The hidden-layer activation of one MLP as mlp_eval / mlp_reg / mlp_regw see it: ELU(1) carries nothing, the act build the MLP's ActDev
 // (six kinds, act_quad), the pre and tableau builds the same for all ten kinds (pre_act_quad; the forward needs no pre-activation)
-struct NoAct {};                           // what the ELU(1) kernel, which has no `act` argument, names act.de / act.ae
-struct NoActPair { NoAct de, ae; };
 __device__ __forceinline__ NoAct act_pick(bool, NoAct, NoAct) { return {}; }
 template <bool ACT, bool PRE> struct ActCtxT;
 template <> struct ActCtxT<false, false> {
@@ -80,12 +60,6 @@ template <> struct ActCtxT<true, true> {
 };
 using ActCtx = ActCtxT<Bd::act, Bd::pre>;
 
-constexpr int TB = 16;    // trajectories per workgroup
-constexpr int NT = 256;   // threads per workgroup (4 waves)
-
-__host__ __device__ constexpr int up16(int v) { return (v + 15) & ~15; }
-// float offset of (column r, trajectory c) in a quad-row activation buffer
-__device__ __forceinline__ int qi(int r, int c) { return ((((r >> 2) * TB) + c) << 2) | (r & 3); }
 // Column order of the two MLP inputs (the first layers' images use the same one): the columns that change most often come first and end on
 // a quad boundary, so that the register forms can fold everything behind them into a per-step (DE) / per-trajectory (AE) constant.
 //   DE  cat(a0, s - a0, s) (DE_Func.forward):   [ (s - a0)_x | s_x | pad to SX ] [ a0 | (s - a0)_ext | s_ext | pad ]    ext = z | v | i
@@ -216,14 +190,8 @@ struct Pref {
     const f4* tag;
 };
 
-#ifndef PSNODE_K0_ABL      // ablation builds (timing only, wrong results): 1 = a quarter of the MFMAs, 2 = no ELU, 3 = no layer barrier, 4 = no MLP at all, 5 = no operand reads / MFMAs, 6 = no look-ahead read
-#define PSNODE_K0_ABL 0
-#endif
-__device__ __forceinline__ void mfma_quad(const f4 av, const f4 bv, f4& acc) {
-#pragma unroll
-    for (int e = 0; e < (PSNODE_K0_ABL == 1 ? 1 : 4); ++e) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[e], bv[e], acc, 0, 0, 0);
-}
-
+// (PSNODE_K0_ABL, psnode_generic_tile.h: ablation builds, timing only, wrong results -- 1 = a quarter of the MFMAs, 2 = no ELU, 3 = no layer barrier,
+//  4 = no MLP at all, 5 = no operand reads / MFMAs, 6 = no look-ahead read)
 // One output tile with both operands in LDS, Q quads, straight-line: every read in flight before the first MFMA, two accumulator chains.
 // PA: the A operands of quads 0 .. 3 come from `pa` (read in front of the layer barrier).  With one wave per SIMD nothing hides a taken
 // branch (an instruction-cache round trip each): a loop over the quads with its guards and tails cost more than the MFMAs it issued
@@ -380,21 +348,8 @@ __device__ __forceinline__ int mlp_eval(const Tab<ML>& T, float* lds, int in, co
 
 // ---- register mode: every layer has at most four output tiles (one per wave), the first contraction at most 16 QM columns (QM = 4 or 8),
 // the others at most 64.  The wave's A operands of the WHOLE MLP stay in registers for the launch (wr[l][q]: quad q of its tile of layer l, zero where
-// the wave has no tile or the tile is shorter), as in the specialised tile integrators: a layer then reads only the activations from LDS.
-// Why it matters: a ds_read_b128 costs a wave about 64 cycles of LDS-to-register transfer, so reading both operands from LDS (8 reads per
-// 16 MFMAs) takes as long as the MFMAs themselves (ablation builds, profiles/r06_k0_generic_mfma.txt).
-template <int Q, int QM>
-__device__ __forceinline__ f4 tile_reg(const f4* bq, const f4 (&wa)[QM]) {
-    f4 bv[Q];
-#pragma unroll
-    for (int c = 0; c < Q; ++c) bv[c] = bq[c * 64];
-    __builtin_amdgcn_sched_barrier(0);
-    f4 acc = f4{0.f, 0.f, 0.f, 0.f}, acc2 = acc;
-#pragma unroll
-    for (int c = 0; c < Q; ++c) mfma_quad(wa[c], bv[c], (c & 1) ? acc2 : acc);
-    return Q > 1 ? acc + acc2 : acc;
-}
-
+// the wave has no tile or the tile is shorter), as in the specialised tile integrators: a layer then reads only the activations from LDS
+// (tile_reg / tile_reg_any: psnode_generic_tile.h).
 // the wave's operand registers of one MLP: layer 0 (the only one whose contraction can exceed 64 columns: the other layers read a layer
 // output of at most 64 units) holds QM quads, the others four
 template <int ML, int QM>
@@ -450,25 +405,6 @@ __device__ __forceinline__ void load_regs(const MlpDev& m, const Tab<ML>& t, WRe
             const f4 v = (w < NTL && q < (l ? S4 : t.qx)) ? A[q * 64] : f4{0.f, 0.f, 0.f, 0.f};      // layer 0: its leading block only
             if (l == 0) wr.first[q] = v; else wr.rest[l - 1][q] = v;
         }
-    }
-}
-
-template <int QM>
-__device__ __forceinline__ f4 tile_reg_any(int S4, const f4* bq, const f4 (&wa)[QM]) {
-    if constexpr (QM > 4) {
-        switch (S4) {
-            case 5: return tile_reg<5, QM>(bq, wa);
-            case 6: return tile_reg<6, QM>(bq, wa);
-            case 7: return tile_reg<7, QM>(bq, wa);
-            case 8: return tile_reg<8, QM>(bq, wa);
-            default: break;
-        }
-    }
-    switch (S4) {
-        case 1: return tile_reg<1, QM>(bq, wa);
-        case 2: return tile_reg<2, QM>(bq, wa);
-        case 3: return tile_reg<3, QM>(bq, wa);
-        default: return tile_reg<4, QM>(bq, wa);
     }
 }
 
@@ -608,16 +544,27 @@ __device__ __forceinline__ long long uniform64(long long v) {
 // PF: z | v values a thread keeps in flight for the next grid point (items tid + 256 j); rows beyond 16 PF are loaded where they are used
 constexpr int PF = 4;
 
-// The kernels of policy B, by their template arguments <DAE, MODE, ML, QM>: specialised by the object that defines them (around
-// psnode_generic_body.h).  MODE 0: weights in registers (mlp_reg; QM = 4 or 8 quads per tile), 1: every image resident in LDS, 2: some
-// layers streamed, 3: the DE in the wide register form (mlp_regw)
-template <class B> struct GenericKernels;
+// The kernel of policy B = Bd (named in the template for the kernel's symbol alone: the body reads Bd).  Extra: B::n_extra by-value arguments
+// behind `a`, in the order act | rk | sub; the body sees all three names.  MODE 0: weights in registers (mlp_reg; QM = 4 or 8 quads per
+// tile), 1: every image resident in LDS, 2: some layers streamed, 3: the DE in the wide register form (mlp_regw)
+template <class B, bool DAE, int MODE, int ML, int QM, class... Extra>
+__global__ __launch_bounds__(NT) void generic_kernel(const IntegrateDev a, const Extra... extra) {
+    static_assert(std::is_same_v<B, Bd> && sizeof...(Extra) == B::n_extra, "the policy's argument list");
+    const auto& act = kernel_arg<0>(NoActPair{}, extra...);                // ELU(1): no activation argument, ActCtx is empty
+    const auto& rk = kernel_arg<1>(psnode_rk_tableau_f32{}, extra...);     // never read without one: the tableau code is under `if constexpr (Bd::rk)`
+    const auto& sub = kernel_arg<2>(SubDev{}, extra...);                   // never read without one: the sub-step code is under `if constexpr (Bd::sub)`
+#include "psnode_generic_body.h"
+}
+template <class B, class... Extra> struct GenericKernels {
+    template <bool DAE, int MODE, int ML, int QM = 4> static constexpr auto get() { return &generic_kernel<B, DAE, MODE, ML, QM, Extra...>; }
+};
 
 }  // namespace
 
 // plans, sets the dynamic-LDS limit and launches the instance of policy B for this call; extra: the kernel's arguments behind `a`
 template <class B, class... Extra>
 hipError_t launch_generic_build(const IntegrateDev& a_in, bool dae, hipStream_t stream_, const Extra&... extra) {
+    using K = GenericKernels<B, Extra...>;
     IntegrateDev a = a_in;
     const size_t lds = generic_plan(a, dae, a.k0_res, B::lin);
     const unsigned grid = (unsigned)((a.B + TB - 1) / TB);
@@ -632,16 +579,26 @@ hipError_t launch_generic_build(const IntegrateDev& a_in, bool dae, hipStream_t 
     auto go = [&](auto kern) { return launch_attr(true, kern, dim3(grid), dim3(NT), lds_launch, stream_, a, extra...); };
     const int qm = generic_reg_mode(a, dae);
     const bool deep = a.de.n_layers > 4 || (dae && a.ae.n_layers > 4);      // the layer loop is unrolled 4 or kMaxLayers times
-    if (qm && deep) return qm == 4 ? go(GenericKernels<B>::template get<false, 0, kMaxLayers, 4>()) : go(GenericKernels<B>::template get<false, 0, kMaxLayers, 8>());
-    if (qm == 4) return dae ? go(GenericKernels<B>::template get<true, 0, 4, 4>()) : go(GenericKernels<B>::template get<false, 0, 4, 4>());
-    if (qm == 8) return dae ? go(GenericKernels<B>::template get<true, 0, 4, 8>()) : go(GenericKernels<B>::template get<false, 0, 4, 8>());
-    if (generic_wide_mode(a, dae)) return go(GenericKernels<B>::template get<false, 3, 4>());
+    if (qm && deep) return qm == 4 ? go(K::template get<false, 0, kMaxLayers, 4>()) : go(K::template get<false, 0, kMaxLayers, 8>());
+    if (qm == 4) return dae ? go(K::template get<true, 0, 4, 4>()) : go(K::template get<false, 0, 4, 4>());
+    if (qm == 8) return dae ? go(K::template get<true, 0, 4, 8>()) : go(K::template get<false, 0, 4, 8>());
+    if (generic_wide_mode(a, dae)) return go(K::template get<false, 3, 4>());
     if (deep) {
-        if (dae) return stream ? go(GenericKernels<B>::template get<true, 2, kMaxLayers>()) : go(GenericKernels<B>::template get<true, 1, kMaxLayers>());
-        return stream ? go(GenericKernels<B>::template get<false, 2, kMaxLayers>()) : go(GenericKernels<B>::template get<false, 1, kMaxLayers>());
+        if (dae) return stream ? go(K::template get<true, 2, kMaxLayers>()) : go(K::template get<true, 1, kMaxLayers>());
+        return stream ? go(K::template get<false, 2, kMaxLayers>()) : go(K::template get<false, 1, kMaxLayers>());
     }
-    if (dae) return stream ? go(GenericKernels<B>::template get<true, 2, 4>()) : go(GenericKernels<B>::template get<true, 1, 4>());
-    return stream ? go(GenericKernels<B>::template get<false, 2, 4>()) : go(GenericKernels<B>::template get<false, 1, 4>());
+    if (dae) return stream ? go(K::template get<true, 2, 4>()) : go(K::template get<true, 1, 4>());
+    return stream ? go(K::template get<false, 2, 4>()) : go(K::template get<false, 1, 4>());
 }
+
+template <class B>
+hipError_t launch_generic(const IntegrateDev& a, bool dae, const K0Call& call, hipStream_t stream) {
+    if constexpr (B::sub) {
+        return launch_generic_build<B>(a, dae, stream, call.act, call.rk, build_sub<B>(call.sub.n, call.sub.x_sub, call.ev_pt, call.ms_every, nullptr));
+    } else if constexpr (B::rk) return launch_generic_build<B>(a, dae, stream, call.act, call.rk);
+    else if constexpr (B::act) return launch_generic_build<B>(a, dae, stream, call.act);
+    else return launch_generic_build<B>(a, dae, stream);
+}
+template hipError_t launch_generic<Bd>(const IntegrateDev&, bool, const K0Call&, hipStream_t);
 
 }  // namespace psnode

@@ -1,20 +1,9 @@
-// K0 with per-trajectory events -- the event table is [T-1, B], every trajectory jumps at its own steps -- on the sub-step build's policy
-// (sub-steps per grid interval, every n >= 1; a launch-time Butcher tableau; every activation kind): the BuildPev object of
-// psnode_generic_impl.h.  A translation unit of its own, so that the kernels of the other six K0 objects stay exactly what they are.
-#include "psnode_generic_build.h"
-namespace psnode { namespace { using Bd = BuildPev; } }
+// K0 with per-trajectory events on the sub-step build: the BuildPev object (psnode_generic_build.h), and the kernel that makes its event table.
+#define PSNODE_BUILD BuildPev
 #include "psnode_generic_impl.h"
 
 namespace psnode {
 namespace {
-
-template <bool DAE, int MODE, int ML, int QM = 4>
-__global__ __launch_bounds__(NT) void generic_pev_kernel(const IntegrateDev a, const ActPair act, const psnode_rk_tableau_f32 rk, const SubDev sub) {
-#include "psnode_generic_body.h"
-}
-template <> struct GenericKernels<Bd> {
-    template <bool DAE, int MODE, int ML, int QM = 4> static constexpr auto get() { return &generic_pev_kernel<DAE, MODE, ML, QM>; }
-};
 
 // The table this build reads, [n_steps][B]: one thread per (k, b) holds trajectory b's clock at step k against trajectory b's own event
 // list -- the exact equality and the lowest-index rule of the shared table (psnode_capi.hip: event_table_kernel), so a NaN entry (the
@@ -38,11 +27,6 @@ __global__ void event_table_pt_kernel(long long n_steps, long long B, const floa
 }
 
 }  // namespace
-
-hipError_t launch_generic_pev(const IntegrateDev& a, bool dae, const ActPair& act, const psnode_rk_tableau_f32& rk, const SubDev& sub,
-                              hipStream_t stream) {
-    return launch_generic_build<Bd>(a, dae, stream, act, rk, sub);
-}
 
 }  // namespace psnode
 

@@ -1,25 +1,3 @@
-// K0 with sub-steps per grid interval (SubDev: psnode_substeps_f32), a launch-time Butcher tableau and every activation kind: the BuildSub
-// object of psnode_generic_impl.h.  A translation unit of its own, so that the kernels of the other four K0 objects stay exactly what they are.
-#include "psnode_generic_build.h"
-namespace psnode { namespace { using Bd = BuildSub; } }
+// K0 with sub-steps per grid interval on the tableau build: the BuildSub object (psnode_generic_build.h).
+#define PSNODE_BUILD BuildSub
 #include "psnode_generic_impl.h"
-
-namespace psnode {
-namespace {
-
-template <bool DAE, int MODE, int ML, int QM = 4>
-__global__ __launch_bounds__(NT) void generic_sub_kernel(const IntegrateDev a, const ActPair act, const psnode_rk_tableau_f32 rk, const SubDev sub) {
-#include "psnode_generic_body.h"
-}
-template <> struct GenericKernels<Bd> {
-    template <bool DAE, int MODE, int ML, int QM = 4> static constexpr auto get() { return &generic_sub_kernel<DAE, MODE, ML, QM>; }
-};
-
-}  // namespace
-
-hipError_t launch_generic_sub(const IntegrateDev& a, bool dae, const ActPair& act, const psnode_rk_tableau_f32& rk, const SubDev& sub,
-                              hipStream_t stream) {
-    return launch_generic_build<Bd>(a, dae, stream, act, rk, sub);
-}
-
-}  // namespace psnode
