@@ -27,20 +27,27 @@ def _is_tableau(method) -> bool:
     return isinstance(method, fused.Tableau)
 
 
+def _rows_fit(need: int, dev) -> bool:
+    """Do `need` bytes of saved rows fit into half of the free HBM of `dev`?  PSNODE_SAVE_ACTIVATIONS=1 says yes without asking."""
+    if SAVE_ACTIVATIONS == "1":
+        return True
+    free, _ = torch.cuda.mem_get_info(dev)
+    return need <= free // 2
+
+
 def latent_wide_training_fits(method, de, ae, hidden, T, B, dev) -> bool:
     """Training at the latent-wide hidden widths exists in ONE form: K3w saves its rows, K9w writes as many adjoint rows again and the
     host contracts them (fused.latent_backward_wide) -- there is no recompute form to fall back to.  True if all of that fits half of the
     free HBM and PSNODE_SAVE_ACTIVATIONS is not "0"; otherwise the solver takes the walk through the user's callables (with its warning)."""
     if SAVE_ACTIVATIONS == "0":
         return False
-    if SAVE_ACTIVATIONS == "1" or T < 2:         # (T = 1: no step, nothing to save)
+    if T < 2:                                        # (T = 1: no step, nothing to save)
         return True
     S = fused.method_info(method)[1]
     rows = (T - 1) * S * B * hidden * 4              # one [T-1,S,B,H] tensor
     grid = T * B * hidden * 4                        # one [T,B,H] tensor
-    need = 4 * rows + (6 if ae is None else 12) * grid       # saved act + xst, gk + d1; d1s, the where / contiguous copies of the external blocks, (DAE) gi, da1, s_ae
-    free, _ = torch.cuda.mem_get_info(dev)
-    return need <= free // 2
+    # saved act + xst, gk + d1; d1s, the where / contiguous copies of the external blocks, (DAE) gi, da1, s_ae
+    return _rows_fit(4 * rows + (6 if ae is None else 12) * grid, dev)
 
 
 def _generic_only_training(opts, kernel, teacher_forced, T=2) -> bool:
@@ -120,12 +127,8 @@ def _want_saved(method, kernel, layers, x_dim, z_dim, T, B):
     latent = len(layers) == 2            # the direct_encode latent shape at hidden 64: K3c saves, K9 reads
     if Hp <= 0 or not (latent or fused.ode_backward_supported(method, layers, x_dim, z_dim, "wide")):
         return False
-    if SAVE_ACTIVATIONS == "1":
-        return True
     S = fused.method_info(method)[1]
-    need = (T - 1) * S * B * ((len(layers) - 1) * Hp + x_dim) * 4
-    free, _ = torch.cuda.mem_get_info(layers[0][0].device)
-    return need <= free // 2
+    return _rows_fit((T - 1) * S * B * ((len(layers) - 1) * Hp + x_dim) * 4, layers[0][0].device)
 
 
 def _want_saved_dae(method, kernel, de, ae, x_dim, z_dim, v_dim, i_dim, T, B):
@@ -140,23 +143,15 @@ def _want_saved_dae(method, kernel, de, ae, x_dim, z_dim, v_dim, i_dim, T, B):
     if len(de) == 2:                     # the direct_encode latent shape at hidden 64 (K3c saves, K9 reads); hidden 16 (K3a / K8) recomputes
         if fused.dae_save_hidden(method, de, ae, x_dim, z_dim, v_dim, i_dim, kernel) != 64:
             return False
-        if SAVE_ACTIVATIONS == "1":
-            return True
-        S = fused.method_info(method)[1]
-        free, _ = torch.cuda.mem_get_info(de[0][0].device)
-        return ((T - 1) * S * 2 + T) * 64 * B * 4 <= free // 2
+        return _rows_fit(((T - 1) * fused.method_info(method)[1] * 2 + T) * 64 * B * 4, de[0][0].device)
     # hidden 64 also has the one-launch kernel K7 (recompute).  The saved form beats it at every method since round 4 (K7f requests its
     # per-step inputs a step ahead: training step at 4096 x 1000 RK4 19.7 vs 23.0 ms, Euler 9.6 vs 10.6 -- gpurun_out/r04g.log; round 3:
     # Euler 11.0 vs 10.65, which kept K7 for Euler)
     Hp = fused.dae_save_hidden(method, de, ae, x_dim, z_dim, v_dim, i_dim, kernel)
     if Hp <= 0 or not fused.dae_backward_wide_supported(method, de, ae, x_dim, z_dim, v_dim, i_dim):
         return False
-    if SAVE_ACTIVATIONS == "1":
-        return True
     S = fused.method_info(method)[1]
-    need = ((T - 1) * S * (3 * Hp + x_dim) + 3 * T * Hp) * B * 4
-    free, _ = torch.cuda.mem_get_info(de[0][0].device)
-    return need <= free // 2
+    return _rows_fit(((T - 1) * S * (3 * Hp + x_dim) + 3 * T * Hp) * B * 4, de[0][0].device)
 
 
 def _layers(params, n_de=None):
@@ -280,90 +275,72 @@ class _FusedOde(torch.autograd.Function):
         return _grad_tuple(ctx, _FusedOde, dict(x0=gx0, z=gz, all_initial=ga0, z_jump=gzj), gpar)
 
 
-def _ode_sub_forward(externals, per_trajectory=False):
-    """The forward of _FusedOdeSub ("hold") / _FusedOdeLin ("linear") / _FusedOdePev ("hold", per-trajectory events: event_idx is the
-    [T-1, B] table): one body, `externals` and `per_trajectory` travel to both calls."""
-    def forward(ctx, method, kernel, act, substeps, tx, event_idx, t, x0, z, all_initial, z_jump, *params):
+class _FusedOdeGeneric(torch.autograd.Function):
+    """integrate_ODE on the option families of the generic kernels that save sub-state rows ("sub", "lin", "pev", "ab", "ms" of
+    fused.GenericOpts.family), plain or teacher-forced: K0 forward in the family's build, which also writes the start state of every
+    sub-step behind an interval's first (x_sub, saved next to xs; empty for one step per interval), K5 backward in the same build.
+    opts: the call's fused.GenericOpts -- its fields travel to both calls; tx: x0 is the whole dataset x [T,B,xd] (no gradient);
+    event_idx: the [T-1] table, or the [T-1, B] one of per-trajectory events (a trajectory's jump gradient goes to its own row of z_jump);
+    x_data: the detached dataset rows the restarts of the family "ms" read, [T, B, xd] with row 0 the start of the call ([1, B, xd] where no
+    step restarts) -- no gradient, x0 gets segment 0's; None for every other family.
+    The classes autograd reports (`_FAMILY_CLASSES`) are empty subclasses: one name per family, this one body."""
+
+    @staticmethod
+    def forward(ctx, method, opts, kernel, tx, event_idx, t, x0, x_data, z, all_initial, z_jump, *params):
         global last_saved_bytes
-        x_in = x0.detach().contiguous() if tx else x0.unsqueeze(0)      # tx: the whole dataset x [T,B,xd]
+        x_in = x_data if x_data is not None else (x0.detach().contiguous() if tx else x0.unsqueeze(0))
         xs, x_sub = fused.ode_integrate(method, _layers(params), t, x_in, z, all_initial, z_jump=z_jump, event_idx=event_idx, kernel=kernel,
-                                        input_true_x=tx, act=act, substeps=substeps, save_sub=True, externals=externals,
-                                        per_trajectory=per_trajectory)
+                                        input_true_x=tx, act=opts.acts[0], substeps=opts.substeps, save_sub=True, externals=opts.externals,
+                                        per_trajectory=opts.per_trajectory, segment=opts.segment)
         last_saved_bytes = x_sub.numel() * x_sub.element_size()
-        ctx.method, ctx.kernel, ctx.act, ctx.substeps, ctx.tx, ctx.event_idx, ctx.externals = method, kernel, act, substeps, tx, event_idx, externals
-        ctx.per_trajectory = per_trajectory
+        ctx.method, ctx.opts, ctx.kernel, ctx.tx, ctx.event_idx = method, opts, kernel, tx, event_idx
         # (tx: the backward starts every interval from the dataset row and reads no xs)
-        ctx.save_for_backward(*_pack(ctx, (t, z, all_initial, x_in if tx else xs, x_sub), dict(z_jump=z_jump), params))
+        ctx.save_for_backward(*_pack(ctx, (t, z, all_initial, x_in if tx else xs, x_sub), dict(z_jump=z_jump, x_data=x_data), params))
         return xs
-    return staticmethod(forward)
-
-
-class _FusedOdeSub(torch.autograd.Function):
-    """integrate_ODE with substeps > 1, plain or teacher-forced: K0 forward in its sub-step build, which also writes the start state of every
-    sub-step behind an interval's first (x_sub, saved next to xs), K5 backward in its sub-step build."""
-    forward = _ode_sub_forward("hold")
 
     @staticmethod
     def backward(ctx, grad_xs):
         (t, z, a0, xs, x_sub), opt, params = _unpack(ctx, 5)
-        need_z = _needs(ctx, _FusedOdeSub, "z")
+        opts, cls = ctx.opts, _FusedOdeGeneric
+        need_z = _needs(ctx, cls, "z")
         gx0, gz, gzj, ga0, gpar = fused.ode_backward(ctx.method, _layers(params), t, z, a0, xs, grad_xs, event_idx=ctx.event_idx, z_jump=opt["z_jump"],
-                                                     need_grad_z=need_z, need_grad_zj=_needs(ctx, _FusedOdeSub, "z_jump"), kernel=ctx.kernel,
-                                                     input_true_x=ctx.tx, act=ctx.act, substeps=ctx.substeps, x_sub=x_sub,
-                                                     externals=ctx.externals, per_trajectory=ctx.per_trajectory)
+                                                     need_grad_z=need_z, need_grad_zj=_needs(ctx, cls, "z_jump"), kernel=ctx.kernel,
+                                                     input_true_x=ctx.tx, act=opts.acts[0], substeps=opts.substeps, x_sub=x_sub,
+                                                     externals=opts.externals, per_trajectory=opts.per_trajectory, segment=opts.segment,
+                                                     x_true=opt["x_data"])
         if gz is None and need_z:
             gz = torch.zeros_like(z)
-        return _grad_tuple(ctx, _FusedOdeSub, dict(x0=None if ctx.tx else gx0, z=gz, all_initial=ga0, z_jump=gzj), gpar)
+        return _grad_tuple(ctx, cls, dict(x0=None if ctx.tx else gx0, z=gz, all_initial=ga0, z_jump=gzj), gpar)
 
 
-class _FusedOdeLin(_FusedOdeSub):
-    """integrate_ODE with externals="linear", every substeps >= 1: _FusedOdeSub on the linear-externals builds of K0 / K5 (grad z[k + 1]
-    also takes the right-hand share of interval k)."""
-    forward = _ode_sub_forward("linear")
+# fused.GenericOpts.family ("ab": with per_trajectory) -> the name of its Function: `_FusedOde<name>` / `_FusedDae<name>`, an empty subclass of
+# the model's one body, is what xs.grad_fn reports.  A further family of K0 / K5 that saves sub-state rows adds a row here, not a class.
+_FAMILY_CLASSES = {"sub": "Sub", "lin": "Lin", "pev": "Pev", ("ab", False): "Ab", ("ab", True): "AbPev", "ms": "Ms"}
+# the families that go to _FusedOde / _FusedDae / _FusedDaeTeacherForced
+_OWN_CLASS = ("plain", "act", "rk")
+# ... and those whose forward (fused.ode_integrate / fused.dae_integrate) is the first to check the call
+_CHECKED_BY_FORWARD = _OWN_CLASS + ("sub", "lin")
 
 
-class _FusedOdePev(_FusedOdeSub):
-    """integrate_ODE with per-trajectory events (ODE_Event(per_trajectory=True) with events set), every substeps >= 1: _FusedOdeSub on the
-    per-trajectory builds of K0 / K5 -- event_idx is the [T-1, B] table, a trajectory's jump gradient goes to its own row of z_jump."""
-    forward = _ode_sub_forward("hold", True)
+def _family_classes(body, prefix) -> dict:
+    return {key: type(prefix + name, (body,), {"__doc__": f"{body.__name__} for the family {key!r} of fused.GenericOpts."})
+            for key, name in _FAMILY_CLASSES.items()}
 
 
-class _FusedOdeAb(_FusedOdeSub):
-    """integrate_ODE with the AB2 solver (method "ab2"), no events or the shared event rule: _FusedOdeSub on the Adams-Bashforth builds of
-    K0 / K5 -- one DE evaluation per step forward, one VJP per step backward; x_sub is empty."""
-    forward = _ode_sub_forward("hold")
+def _family_class(classes, opts):
+    return classes[(opts.family, opts.per_trajectory) if opts.family == "ab" else opts.family]
 
 
-class _FusedOdeAbPev(_FusedOdeSub):
-    """... with per-trajectory events: event_idx is the [T-1, B] table, the restart is taken per trajectory."""
-    forward = _ode_sub_forward("hold", True)
+def _refuse(what, opts, kernel, teacher_forced):
+    """The refusals of a differentiable call, under the name `what`: teacher forcing next to Adams-Bashforth 2 or segments (ValueError), the
+    families that have no kernel, a kernel other than "auto" / "generic" (UnsupportedShapeError)."""
+    if opts.family not in _CHECKED_BY_FORWARD:
+        opts.no_teacher_forcing(what, teacher_forced)
+        opts.require_generic(what, kernel, False)
 
 
-class _FusedOdeMs(torch.autograd.Function):
-    """integrate_ODE with segment=w (multiple shooting), every substeps >= 1: K0 forward and K5 backward in their multiple-shooting builds.
-    x_data: the detached dataset rows the restarts read, [T, B, xd] with row 0 the start of the call ([1, B, xd] where no step restarts);
-    it gets no gradient, x0 gets segment 0's."""
-
-    @staticmethod
-    def forward(ctx, method, kernel, act, substeps, segment, event_idx, t, x0, x_data, z, all_initial, z_jump, *params):
-        global last_saved_bytes
-        xs, x_sub = fused.ode_integrate(method, _layers(params), t, x_data, z, all_initial, z_jump=z_jump, event_idx=event_idx, kernel=kernel,
-                                        act=act, substeps=substeps, save_sub=True, segment=segment)
-        last_saved_bytes = x_sub.numel() * x_sub.element_size()
-        ctx.method, ctx.kernel, ctx.act, ctx.substeps, ctx.segment, ctx.event_idx = method, kernel, act, substeps, segment, event_idx
-        ctx.save_for_backward(*_pack(ctx, (t, z, all_initial, xs, x_sub, x_data), dict(z_jump=z_jump), params))
-        return xs
-
-    @staticmethod
-    def backward(ctx, grad_xs):
-        (t, z, a0, xs, x_sub, x_data), opt, params = _unpack(ctx, 6)
-        need_z = _needs(ctx, _FusedOdeMs, "z")
-        gx0, gz, gzj, ga0, gpar = fused.ode_backward(ctx.method, _layers(params), t, z, a0, xs, grad_xs, event_idx=ctx.event_idx, z_jump=opt["z_jump"],
-                                                     need_grad_z=need_z, need_grad_zj=_needs(ctx, _FusedOdeMs, "z_jump"), kernel=ctx.kernel,
-                                                     act=ctx.act, substeps=ctx.substeps, x_sub=x_sub, segment=ctx.segment, x_true=x_data)
-        if gz is None and need_z:
-            gz = torch.zeros_like(z)
-        return _grad_tuple(ctx, _FusedOdeMs, dict(x0=gx0, z=gz, all_initial=ga0, z_jump=gzj), gpar)
+_ODE_CLASSES = _family_classes(_FusedOdeGeneric, "_FusedOde")
+globals().update({cls.__name__: cls for cls in _ODE_CLASSES.values()})      # _FusedOdeSub, ..Lin, ..Pev, ..Ab, ..AbPev, ..Ms
 
 
 def fused_ode_integrate(method, kernel, layers, t, x, z, all_initial, event_t=None, z_jump=None, check_events=False, input_true_x=False,
@@ -372,34 +349,30 @@ def fused_ode_integrate(method, kernel, layers, t, x, z, all_initial, event_t=No
     my_solvers.py:72-74): every step starts from the dataset row x[k]; gradients flow to z, all_initial, z_jump and the MLP (the dataset
     x gets none: callers whose x requires grad take the callback walk).  act: the MLP's activation (fused.Act), None = ELU(1); any other
     trains on K0 + K5 (no teacher forcing).  per_trajectory: every trajectory jumps at its own event times (fused.event_table(...,
-    per_trajectory=True)); a call without events is the call it is without the flag."""
+    per_trajectory=True)); a call without events is the call it is without the flag.  segment: multiple shooting -- the dataset rows get
+    no gradient (a caller whose x requires grad and restarts walks)."""
     with torch.no_grad():
         event_idx = fused.event_table(t, event_t, check_events, per_trajectory=per_trajectory)
     if event_idx is None:
         z_jump = None
     params = [p for wb in layers for p in wb]
-    x0 = x.detach() if input_true_x else (x[0] if x_init is None else x_init)     # (x_init: integrate_ODE's extension -- no SelectBackward)
-    if segment is not None:      # multiple shooting: the dataset rows get no gradient (a caller whose x requires grad and restarts walks)
-        pev = bool(per_trajectory) and event_idx is not None
-        fused.GenericOpts.of(method, (act,), substeps, externals, pev, segment).require_generic("fused_ode_integrate", kernel, False,
-                                                                                              bool(input_true_x))
-        if t.shape[0] - 1 > segment:
-            x_data = x.detach() if x_init is None else torch.cat((x_init.detach().unsqueeze(0), x.detach()[1:]))
-        else:
-            x_data = x0.detach().unsqueeze(0)
-        return _FusedOdeMs.apply(method, kernel, act, substeps, segment, event_idx, t, x0, x_data, z, all_initial, z_jump, *params)
-    if fused.is_ab(method):
-        pev = bool(per_trajectory) and event_idx is not None
-        fused.GenericOpts.of(method, (act,), substeps, externals, pev).require_generic("fused_ode_integrate", kernel, False, bool(input_true_x))
-        return (_FusedOdeAbPev if pev else _FusedOdeAb).apply(method, kernel, act, substeps, False, event_idx, t, x0, z, all_initial, z_jump, *params)
-    if per_trajectory and event_idx is not None:
-        fused.GenericOpts.of(method, (act,), substeps, externals, True).require_generic("fused_ode_integrate", kernel, False)
-        return _FusedOdePev.apply(method, kernel, act, substeps, bool(input_true_x), event_idx, t, x0, z, all_initial, z_jump, *params)
-    if fused.is_linear(externals):
-        return _FusedOdeLin.apply(method, kernel, act, substeps, bool(input_true_x), event_idx, t, x0, z, all_initial, z_jump, *params)
-    if substeps != 1:
-        return _FusedOdeSub.apply(method, kernel, act, substeps, bool(input_true_x), event_idx, t, x0, z, all_initial, z_jump, *params)
-    return _FusedOde.apply(method, kernel, act, event_idx, t, x0, z, all_initial, z_jump, *params)
+    tx = bool(input_true_x)
+    x0 = x.detach() if tx else (x[0] if x_init is None else x_init)     # (x_init: integrate_ODE's extension -- no SelectBackward)
+    opts = fused.GenericOpts.of(method, (act,), substeps, externals, bool(per_trajectory) and event_idx is not None, segment)
+    _refuse("fused_ode_integrate", opts, kernel, tx)
+    if opts.family in _OWN_CLASS:
+        return _FusedOde.apply(method, kernel, act, event_idx, t, x0, z, all_initial, z_jump, *params)
+    x_data = None
+    if opts.segment is not None and t.shape[0] - 1 > opts.segment:
+        x_data = x.detach() if x_init is None else torch.cat((x_init.detach().unsqueeze(0), x.detach()[1:]))
+    elif opts.segment is not None:      # no step restarts: row 0, the start of the call, is all that is read
+        x_data = x0.detach().unsqueeze(0)
+    return _family_class(_ODE_CLASSES, opts).apply(method, opts, kernel, tx, event_idx, t, x0, x_data, z, all_initial, z_jump, *params)
+
+
+def _dae_act(acts):
+    """The `act=` of a fused DAE call from a call's pair of activations (fused.dae_acts): None where both are ELU(1)."""
+    return acts if any(a is not None for a in acts) else None
 
 
 def _dae_grads(ctx, cls, g, z, v) -> tuple:
@@ -420,9 +393,8 @@ class _FusedDae(torch.autograd.Function):
         if kernel == "generic" and not _is_tableau(method) and fused.latent_wide_shape(de, ae, x_init.shape[-1], z.shape[-1], v.shape[-1],
                                                                                         i_shape_like.shape[-1]):
             kernel = "auto"
-        non_elu = act is not None and any(a is not None for a in act)
-        ctx.act = act if non_elu else None
-        save = not non_elu and _want_saved_dae(method, kernel, de, ae, x_init.shape[-1], z.shape[-1], v.shape[-1], i_shape_like.shape[-1], T, B)
+        ctx.act = _dae_act(fused.dae_acts(act))
+        save = ctx.act is None and _want_saved_dae(method, kernel, de, ae, x_init.shape[-1], z.shape[-1], v.shape[-1], i_shape_like.shape[-1], T, B)
         res = fused.dae_integrate(method, de, ae, x_init, t, x_dummy, z, v, i_shape_like, all_initial, z_jump=z_jump, v_jump=v_jump,
                                   event_idx=event_idx, kernel=kernel, save=save, act=ctx.act)
         xs, is_ = res[0], res[1]
@@ -470,89 +442,43 @@ class _FusedDaeTeacherForced(torch.autograd.Function):
         return _dae_grads(ctx, _FusedDaeTeacherForced, g, z, v)
 
 
-def _dae_sub_forward(externals, per_trajectory=False):
-    """The forward of _FusedDaeSub ("hold") / _FusedDaeLin ("linear") / _FusedDaePev ("hold", per-trajectory events): one body, `externals`
-    and `per_trajectory` travel to both calls."""
-    def forward(ctx, method, kernel, act, substeps, tx, ti, event_idx, n_de, t, x_init, x, z, v, i, all_initial, z_jump, v_jump, *params):
+class _FusedDaeGeneric(torch.autograd.Function):
+    """integrate_DAE on the option families of the generic kernels that save sub-state rows ("sub", "lin", "pev", "ab", "ms"), plain or
+    teacher-forced: K0 forward and K5 backward in the family's builds, x_sub saved next to xs / is -- as _FusedOdeGeneric.  x / i: the
+    detached dataset rows of a teacher-forced call (tx / ti) and, x, the rows [T, B, xd] the restarts of the family "ms" read; they get
+    no gradient (x_init gets segment 0's)."""
+
+    @staticmethod
+    def forward(ctx, method, opts, kernel, tx, ti, event_idx, n_de, t, x_init, x, z, v, i, all_initial, z_jump, v_jump, *params):
         de, ae = _layers(params, n_de)
-        non_elu = act is not None and any(a is not None for a in act)
+        act = _dae_act(opts.acts)
         xs, is_, x_sub = fused.dae_integrate(method, de, ae, x_init, t, x, z, v, i, all_initial, z_jump=z_jump, v_jump=v_jump, event_idx=event_idx,
-                                             kernel=kernel, input_true_x=tx, input_true_i=ti, act=act if non_elu else None, substeps=substeps,
-                                             save_sub=True, externals=externals, per_trajectory=per_trajectory)
+                                             kernel=kernel, input_true_x=tx, input_true_i=ti, act=act, substeps=opts.substeps, save_sub=True,
+                                             externals=opts.externals, per_trajectory=opts.per_trajectory, segment=opts.segment)
         global last_saved_bytes
         last_saved_bytes = x_sub.numel() * x_sub.element_size()
-        ctx.method, ctx.kernel, ctx.act, ctx.substeps, ctx.tx, ctx.ti = method, kernel, act if non_elu else None, substeps, tx, ti
-        ctx.n_de, ctx.event_idx, ctx.externals, ctx.per_trajectory = n_de, event_idx, externals, per_trajectory
+        ctx.method, ctx.opts, ctx.kernel, ctx.act, ctx.tx, ctx.ti, ctx.n_de, ctx.event_idx = method, opts, kernel, act, tx, ti, n_de, event_idx
         ctx.save_for_backward(*_pack(ctx, (t, z, v, all_initial, xs, is_, x_sub, x, i), dict(z_jump=z_jump, v_jump=v_jump), params))
         return xs, is_
-    return staticmethod(forward)
-
-
-class _FusedDaeSub(torch.autograd.Function):
-    """integrate_DAE with substeps > 1, plain or teacher-forced: K0 forward and K5 backward in their sub-step builds, x_sub saved next to
-    xs / is.  The dataset rows of a teacher-forced call get no gradient."""
-    forward = _dae_sub_forward("hold")
 
     @staticmethod
     def backward(ctx, grad_xs, grad_is):
         (t, z, v, a0, xs, is_, x_sub, x, i), opt, params = _unpack(ctx, 9)
         de, ae = _layers(params, ctx.n_de)
-        common = dict(event_idx=ctx.event_idx, kernel=ctx.kernel, substeps=ctx.substeps, x_sub=x_sub, externals=ctx.externals,
-                      per_trajectory=ctx.per_trajectory, **opt)
+        opts = ctx.opts
+        common = dict(event_idx=ctx.event_idx, kernel=ctx.kernel, substeps=opts.substeps, x_sub=x_sub, externals=opts.externals,
+                      per_trajectory=opts.per_trajectory, **opt)
         if ctx.tx or ctx.ti:
             g = fused.dae_backward_tf(ctx.method, de, ae, t, z, v, a0, xs, is_, grad_xs, grad_is, x_true=x if ctx.tx else None,
                                       i_true=i if ctx.ti else None, **common)
         else:
-            g = fused.dae_backward(ctx.method, de, ae, t, z, v, a0, xs, is_, grad_xs, grad_is, act=ctx.act, **common)
-        return _dae_grads(ctx, _FusedDaeSub, g, z, v)
+            g = fused.dae_backward(ctx.method, de, ae, t, z, v, a0, xs, is_, grad_xs, grad_is, act=ctx.act, segment=opts.segment,
+                                   x_true=x if opts.segment is not None else None, **common)
+        return _dae_grads(ctx, _FusedDaeGeneric, g, z, v)
 
 
-class _FusedDaeLin(_FusedDaeSub):
-    """integrate_DAE with externals="linear", every substeps >= 1: _FusedDaeSub on the linear-externals builds of K0 / K5."""
-    forward = _dae_sub_forward("linear")
-
-
-class _FusedDaePev(_FusedDaeSub):
-    """integrate_DAE with per-trajectory events (DAE_Event(per_trajectory=True) with events set), every substeps >= 1: _FusedDaeSub on the
-    per-trajectory builds of K0 / K5."""
-    forward = _dae_sub_forward("hold", True)
-
-
-class _FusedDaeAb(_FusedDaeSub):
-    """integrate_DAE with the AB2 solver (method "ab2"), no events or the shared event rule: _FusedDaeSub on the Adams-Bashforth builds of
-    K0 / K5."""
-    forward = _dae_sub_forward("hold")
-
-
-class _FusedDaeAbPev(_FusedDaeSub):
-    """... with per-trajectory events: event_idx is the [T-1, B] table, the restart is taken per trajectory."""
-    forward = _dae_sub_forward("hold", True)
-
-
-class _FusedDaeMs(torch.autograd.Function):
-    """integrate_DAE with segment=w (multiple shooting), every substeps >= 1: K0 forward and K5 backward in their multiple-shooting builds.
-    x: the detached dataset rows [T, B, xd] the restarts read; they get no gradient, x_init gets segment 0's."""
-
-    @staticmethod
-    def forward(ctx, method, kernel, act, substeps, segment, event_idx, n_de, t, x_init, x, z, v, i, all_initial, z_jump, v_jump, *params):
-        de, ae = _layers(params, n_de)
-        non_elu = act is not None and any(a is not None for a in act)
-        xs, is_, x_sub = fused.dae_integrate(method, de, ae, x_init, t, x, z, v, i, all_initial, z_jump=z_jump, v_jump=v_jump, event_idx=event_idx,
-                                             kernel=kernel, act=act if non_elu else None, substeps=substeps, save_sub=True, segment=segment)
-        global last_saved_bytes
-        last_saved_bytes = x_sub.numel() * x_sub.element_size()
-        ctx.method, ctx.kernel, ctx.act, ctx.substeps, ctx.segment = method, kernel, act if non_elu else None, substeps, segment
-        ctx.n_de, ctx.event_idx = n_de, event_idx
-        ctx.save_for_backward(*_pack(ctx, (t, z, v, all_initial, xs, is_, x_sub, x), dict(z_jump=z_jump, v_jump=v_jump), params))
-        return xs, is_
-
-    @staticmethod
-    def backward(ctx, grad_xs, grad_is):
-        (t, z, v, a0, xs, is_, x_sub, x), opt, params = _unpack(ctx, 8)
-        de, ae = _layers(params, ctx.n_de)
-        g = fused.dae_backward(ctx.method, de, ae, t, z, v, a0, xs, is_, grad_xs, grad_is, act=ctx.act, event_idx=ctx.event_idx,
-                               kernel=ctx.kernel, substeps=ctx.substeps, x_sub=x_sub, segment=ctx.segment, x_true=x, **opt)
-        return _dae_grads(ctx, _FusedDaeMs, g, z, v)
+_DAE_CLASSES = _family_classes(_FusedDaeGeneric, "_FusedDae")
+globals().update({cls.__name__: cls for cls in _DAE_CLASSES.values()})      # _FusedDaeSub, ..Lin, ..Pev, ..Ab, ..AbPev, ..Ms
 
 
 def fused_dae_integrate(method, kernel, de_layers, ae_layers, x_init, t, z, v, i, all_initial, event_t=None, z_jump=None, v_jump=None,
@@ -561,7 +487,8 @@ def fused_dae_integrate(method, kernel, de_layers, ae_layers, x_init, t, z, v, i
     """Differentiable fused integrate_DAE: gradients flow to x_init, z, v, all_initial, the jump inputs and both MLPs.  Without teacher
     forcing `i` only provides the width of the algebraic variable.  input_true_x / input_true_i: `x` / `i` are the dataset rows the DE
     and the heads are fed (my_solvers.py:111-121); they get no gradient.  act: None or (de_act, ae_act) (fused.Act, None = ELU(1)); an
-    activation other than ELU(1) trains on K0 + K5 (no teacher forcing).  per_trajectory: as fused_ode_integrate."""
+    activation other than ELU(1) trains on K0 + K5 (no teacher forcing).  per_trajectory: as fused_ode_integrate.  segment: multiple
+    shooting -- `x` is the dataset rows the restarts read; they get no gradient."""
     with torch.no_grad():
         event_idx = fused.event_table(t, event_t, check_events, per_trajectory=per_trajectory)
     if event_idx is None:
@@ -570,28 +497,16 @@ def fused_dae_integrate(method, kernel, de_layers, ae_layers, x_init, t, z, v, i
         z_jump = z_jump if (z_jump is not None and z_jump.shape[-1] > 0) else None
         v_jump = v_jump if (v_jump is not None and v_jump.shape[-1] > 0) else None
     params = [p for wb in list(de_layers) + list(ae_layers) for p in wb]
-    pev = bool(per_trajectory) and event_idx is not None
-    if segment is not None:      # multiple shooting: `x` is the dataset rows the restarts read; they get no gradient
-        fused.GenericOpts.of(method, fused.dae_acts(act), substeps, externals, pev, segment).require_generic(
-            "fused_dae_integrate", kernel, False, bool(input_true_x or input_true_i))
-        if x is None or x.shape[-1] == 0:
-            raise ValueError(f"fused_dae_integrate: segment={segment} restarts from the dataset rows x[k]; this call has none")
-        return _FusedDaeMs.apply(method, kernel, act, substeps, segment, event_idx, len(de_layers), t, x_init, x.detach(), z, v, i.detach(),
-                                 all_initial, z_jump, v_jump, *params)
-    if fused.is_ab(method):
-        fused.GenericOpts.of(method, fused.dae_acts(act), substeps, externals, pev).require_generic(
-            "fused_dae_integrate", kernel, False, bool(input_true_x or input_true_i))
-        return (_FusedDaeAbPev if pev else _FusedDaeAb).apply(method, kernel, act, substeps, False, False, event_idx, len(de_layers), t, x_init,
-                                                             x_init.new_zeros((1, t.shape[1], 0)), z, v, i.detach(), all_initial, z_jump, v_jump,
-                                                             *params)
-    if pev:
-        fused.GenericOpts.of(method, fused.dae_acts(act), substeps, externals, True).require_generic("fused_dae_integrate", kernel, False)
-    if pev or substeps != 1 or fused.is_linear(externals):
-        xd_ = x.detach() if input_true_x else x_init.new_zeros((1, t.shape[1], 0))
-        return (_FusedDaePev if pev else _FusedDaeLin if fused.is_linear(externals) else _FusedDaeSub).apply(method, kernel, act, substeps, bool(input_true_x), bool(input_true_i), event_idx, len(de_layers), t, x_init, xd_,
-                                  z, v, i.detach(), all_initial, z_jump, v_jump, *params)
-    if input_true_x or input_true_i:
-        xd_ = x.detach() if input_true_x else x_init.new_zeros((1, t.shape[1], 0))
-        return _FusedDaeTeacherForced.apply(method, kernel, event_idx, len(de_layers), bool(input_true_x), bool(input_true_i), t, x_init, xd_,
-                                            z, v, i.detach(), all_initial, z_jump, v_jump, *params)
-    return _FusedDae.apply(method, kernel, act, event_idx, len(de_layers), t, x_init, z, v, i.detach(), all_initial, z_jump, v_jump, *params)
+    tx, ti = bool(input_true_x), bool(input_true_i)
+    opts = fused.GenericOpts.of(method, fused.dae_acts(act), substeps, externals, bool(per_trajectory) and event_idx is not None, segment)
+    _refuse("fused_dae_integrate", opts, kernel, tx or ti)
+    if opts.segment is not None and (x is None or x.shape[-1] == 0):
+        raise ValueError(f"fused_dae_integrate: segment={segment} restarts from the dataset rows x[k]; this call has none")
+    if opts.family in _OWN_CLASS and not (tx or ti):
+        return _FusedDae.apply(method, kernel, act, event_idx, len(de_layers), t, x_init, z, v, i.detach(), all_initial, z_jump, v_jump, *params)
+    rows = x.detach() if (tx or opts.segment is not None) else x_init.new_zeros((1, t.shape[1], 0))
+    if opts.family in _OWN_CLASS:
+        return _FusedDaeTeacherForced.apply(method, kernel, event_idx, len(de_layers), tx, ti, t, x_init, rows, z, v, i.detach(), all_initial,
+                                            z_jump, v_jump, *params)
+    return _family_class(_DAE_CLASSES, opts).apply(method, opts, kernel, tx, ti, event_idx, len(de_layers), t, x_init, rows, z, v, i.detach(),
+                                                   all_initial, z_jump, v_jump, *params)

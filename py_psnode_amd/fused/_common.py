@@ -656,6 +656,15 @@ def _ms_rows(what: str, segment, x_true, T: int, B: int, xd: int, dev):
     return _f32_dev(x_true.detach(), dev, "x_true").contiguous()
 
 
+def _check_x_sub(what: str, substeps: int, x_sub, T: int, B: int, xd: int, dev):
+    """A backward call with substeps > 1 reads x_sub as a raw pointer: the contiguous fp32 [T-1, substeps-1, B, xd] tensor on the call's
+    device that the forward call returned (a shorter one would be read out of bounds)."""
+    if substeps > 1 and T >= 2 and (x_sub is None or tuple(x_sub.shape) != (T - 1, substeps - 1, B, xd) or not x_sub.is_contiguous()
+                                    or x_sub.dtype != torch.float32 or x_sub.device != dev):
+        raise ValueError(f"{what}: substeps={substeps} needs x_sub, the contiguous fp32 [{T - 1},{substeps - 1},{B},{xd}] tensor the "
+                         "forward call returned with save_sub=True")
+
+
 def _check_tb(name: str, a: Optional[torch.Tensor], T: int, B: int, min_T: Optional[int] = None):
     """Leading dims of a time-major input against the call's (T, B): a mismatch would be an out-of-bounds device read."""
     if a is None or a.shape[-1] == 0:

@@ -2,11 +2,12 @@
 the AE head's rows where the kernel does not form the head's gradients itself), K9 / K8 / K9w for the latent shapes, the generic K5
 otherwise (psnode_dae_backward_f32); teacher-forced calls outside K7f's class go to K5 through psnode_dae_backward_tf_f32."""
 import ctypes
+import types
 
 import torch
 
 from .. import _lib
-from ._common import (KERNEL_ID, GenericOpts, Layers, _aligned16, _bind_jumps, _check_saved, _empty, _f32_dev, _mlp, _pad_rows, _padded_hidden, _split_grads, _view, _workspace_of, call_generic, check_event_idx, dae_acts, _ms_rows)
+from ._common import (KERNEL_ID, GenericOpts, Layers, _aligned16, _bind_jumps, _check_saved, _check_x_sub, _empty, _f32_dev, _mlp, _pad_rows, _padded_hidden, _split_grads, _view, _workspace_of, call_generic, check_event_idx, dae_acts, _ms_rows)
 from .latent import latent_backward_wide, latent_wide_shape
 
 def dae_backward_supported(method, de_layers: Layers, ae_layers: Layers, x_dim, z_dim, v_dim, i_dim, act=None, kernel: str = "auto",
@@ -49,12 +50,36 @@ def dae_backward_wide_supported(method: str, de_layers: Layers, ae_layers: Layer
     return bool(lib.psnode_dae_backward_wide_supported(ctypes.byref(a)))
 
 
+def _bind_dae_inputs(a, all_initial, xs, is_, grad_xs, grad_is, dev, keep):
+    """The inputs every DAE backward struct carries under these names, as contiguous fp32 device tensors: all_initial, xs, is, grad_xs (None:
+    zeros) and grad_is (None goes to the kernels as NULL).  Returns them; `keep` holds them until the call has returned."""
+    a0 = _f32_dev(all_initial, dev, "all_initial").contiguous()
+    xs_c, is_c = _f32_dev(xs, dev, "xs").contiguous(), _f32_dev(is_, dev, "is").contiguous()
+    gx_c = _f32_dev(grad_xs, dev, "grad_xs").contiguous() if grad_xs is not None else torch.zeros_like(xs_c)
+    gi_c = _f32_dev(grad_is, dev, "grad_is").contiguous() if grad_is is not None else None
+    keep += [a0, xs_c, is_c, gx_c, gi_c]
+    a.all_initial, a.xs, a.is_, a.grad_xs = a0.data_ptr(), xs_c.data_ptr(), is_c.data_ptr(), gx_c.data_ptr()
+    a.grad_is = gi_c.data_ptr() if gi_c is not None else None
+    return a0, xs_c, is_c, gx_c, gi_c
+
+
+def _bind_true_rows(a, x_true, i_true, dev, keep):
+    """The dataset rows of a teacher-forced call (either may be None) as contiguous fp32 device tensors, with the struct's flags and pointers."""
+    xt_c = _f32_dev(x_true, dev, "x_true").contiguous() if x_true is not None else None
+    it_c = _f32_dev(i_true, dev, "i_true").contiguous() if i_true is not None else None
+    keep += [xt_c, it_c]
+    a.flags = (_lib.FLAG_INPUT_TRUE_X if xt_c is not None else 0) | (_lib.FLAG_INPUT_TRUE_I if it_c is not None else 0)
+    a.x_true = xt_c.data_ptr() if xt_c is not None else None
+    a.i_true = it_c.data_ptr() if it_c is not None else None
+    return xt_c, it_c
+
+
 def dae_backward_wide(method: str, de_layers: Layers, ae_layers: Layers, t, z, v, all_initial, xs, is_, grad_xs, grad_is, event_idx=None,
                       z_jump=None, v_jump=None, saved=None, x_true=None, i_true=None, substeps: int = 1, externals: str = "hold"):
     """Backward of `dae_integrate` at hidden <= 128 (the DAE_01 shape class): K7f (psnode_dae_backward_wide_f32) -- ONE launch over the
     whole grid that sweeps the adjoint through the DE stages, the AE head per grid point and the event-time recomputes and forms the DE's
     parameter gradients and the DE's share of the input gradients in the kernel.  With saved activations at hidden <= 64 the head's
-    gradients are formed in the kernel too; otherwise its rows (one set per grid point) are contracted by K7h (`head_grads_hip`).
+    gradients are formed in the kernel too; otherwise its rows (one set per grid point) are contracted by K7h (`_wide_head_k7h`).
     saved = what `dae_integrate(save=True)` returned for the same call: the kernel evaluates nothing forwards.  x_true / i_true [T,B,.]:
     backward of a teacher-forced call (input_true_x / input_true_i, my_solvers.py:111-121) -- the dataset rows the forward call fed the
     DE / the heads; recompute form only.  A call whose head rows (6 x [T,B,H] + [T,B,40]) would not fit half of the free HBM is run over
@@ -63,12 +88,8 @@ def dae_backward_wide(method: str, de_layers: Layers, ae_layers: Layers, t, z, v
     method_id, S = GenericOpts.of(method, (None, None), substeps, externals).require_plain("dae_backward_wide")
     lib = _lib.load()
     dev = xs.device
-    T, B, xd = xs.shape
-    zd, vd, idim = z.shape[-1], v.shape[-1], is_.shape[-1]
-    nzv, ne = zd + vd, zd + vd + idim
-    n = xd + ne
-    Hr = de_layers[0][0].shape[0]                       # the MLPs' width; H = the width the kernel runs them at (zero-padded rows)
-    H = _padded_hidden(Hr)
+    T, B, _ = xs.shape
+    H = _padded_hidden(de_layers[0][0].shape[0])        # the width the kernel runs the MLPs at (zero-padded rows)
     if saved is None and B > 16:
         # the recompute form stores the AE head's rows of EVERY grid point (6 x [T,B,H] + [T,B,16] + the u rows of K7h): a very long grid on
         # a full card goes through in batch slices (a saved-activation call is not sliced: its forward already held ~S times as much)
@@ -79,20 +100,55 @@ def dae_backward_wide(method: str, de_layers: Layers, ae_layers: Layers, t, z, v
             step = -(-((B + nsl - 1) // nsl) // 16) * 16
             return _dae_backward_wide_sliced(step, method, de_layers, ae_layers, t, z, v, all_initial, xs, is_, grad_xs, grad_is,
                                              event_idx, z_jump, v_jump, x_true, i_true)
+    c = _wide_marshal(lib, method_id, S, de_layers, ae_layers, t, z, v, all_initial, xs, is_, grad_xs, grad_is, event_idx, z_jump, v_jump,
+                      saved, x_true, i_true)
+    with torch.cuda.device(dev):
+        nbytes = lib.psnode_dae_backward_wide_workspace_bytes(ctypes.byref(c.a))
+        ws, wp, wn = _workspace_of(nbytes, dev)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(lib.psnode_dae_backward_wide_f32(ctypes.byref(c.a), wp, wn, st), "psnode_dae_backward_wide_f32")
+        if c.gae_raw is not None:      # one launch did everything (the kernel added the AE's share to grad all_initial, too)
+            g_ae, ga0 = _wide_head_in_kernel(c), c.ga0_de
+        else:
+            g_ae, Sa1 = _wide_head_k7h(lib, c, z, v, event_idx)
+            ga0 = c.ga0_de + Sa1 @ _pad_rows(c.A[0][:, 0:c.n], H)
+    zd, vd, n_ev = c.zd, c.vd, c.n_ev
+    g = {"z_jump": None, "v_jump": None}
+    g["x_init"] = c.carry_x + c.gx_c[0]
+    g["all_initial"] = ga0
+    g["z"] = c.gzv[..., :zd].contiguous() if zd > 0 else None
+    g["v"] = c.gzv[..., zd:].contiguous() if vd > 0 else None
+    if n_ev:
+        g["z_jump"] = c.gjump[..., :zd].contiguous() if zd > 0 else None
+        g["v_jump"] = c.gjump[..., zd:].contiguous() if vd > 0 else None
+    g["de"] = _split_grads(c.gp_de, de_layers)
+    g["ae"] = g_ae
+    return g
+
+
+def _wide_marshal(lib, method_id, S, de_layers, ae_layers, t, z, v, all_initial, xs, is_, grad_xs, grad_is, event_idx, z_jump, v_jump, saved,
+                  x_true, i_true):
+    """The args struct of one K7f launch (`a`) and every tensor it points to or that the routes behind the launch read, as one namespace."""
+    dev = xs.device
+    T, B, xd = xs.shape
+    zd, vd, idim = z.shape[-1], v.shape[-1], is_.shape[-1]
+    nzv, ne = zd + vd, zd + vd + idim
+    n = xd + ne
+    Hr = de_layers[0][0].shape[0]                       # the MLPs' width; H = the width the kernel runs them at (zero-padded rows)
+    H = _padded_hidden(Hr)
+    f32 = dict(dtype=torch.float32, device=dev)
     keep: list = []
     a = _lib.DaeBwdWideArgsF32()
     a.method, a.x_dim, a.z_dim, a.v_dim, a.i_dim, a.T, a.B = method_id, xd, zd, vd, idim, T, B
     a.de, a.ae = _mlp(de_layers, dev, "de", keep), _mlp(ae_layers, dev, "ae", keep)
     a.t, a.z, a.v = _view(t, dev, "t", keep), _view(z, dev, "z", keep), _view(v, dev, "v", keep)
-    a0 = _f32_dev(all_initial, dev, "all_initial").contiguous()
-    xs_c, is_c = _f32_dev(xs, dev, "xs").contiguous(), _f32_dev(is_, dev, "is").contiguous()
-    gx_c = _f32_dev(grad_xs, dev, "grad_xs").contiguous() if grad_xs is not None else torch.zeros_like(xs_c)
-    gi_c = _f32_dev(grad_is, dev, "grad_is").contiguous() if grad_is is not None else None
-    keep += [a0, xs_c, is_c, gx_c, gi_c]
-    a.all_initial, a.xs, a.is_, a.grad_xs = a0.data_ptr(), xs_c.data_ptr(), is_c.data_ptr(), gx_c.data_ptr()
-    a.grad_is = gi_c.data_ptr() if gi_c is not None else None
-    f32 = dict(dtype=torch.float32, device=dev)
+    a0, xs_c, _, gx_c, _ = _bind_dae_inputs(a, all_initial, xs, is_, grad_xs, grad_is, dev, keep)
+    # (grad_is = None goes to the kernels as NULL: they read the rows of `is` instead and mask them out, branch-free.  Round 3 passed an
+    #  explicit zero tensor here because NULL gave wrong AE gradients on one register class; round 4 found the cause -- a uniform
+    #  `if (grad_is)` branch scheduled between an MFMA and the consumer of its result, psnode_dae_backward_wide.hip:add_gis -- and removed
+    #  the branch, so the C ABI's documented NULL is safe for every caller)
     n_ev = 0
+    ev_rows = ev_gi = None
     _bind_jumps(a, event_idx, (("z_jump", z_jump), ("v_jump", v_jump)), dev, keep)
     if event_idx is not None:
         n_ev = (z_jump if z_jump is not None else v_jump).shape[1]
@@ -103,38 +159,22 @@ def dae_backward_wide(method: str, de_layers: Layers, ae_layers: Layers, t, z, v
         for q in range(3):
             a.ev_act[q], a.ev_delta[q] = ev_rows[q].data_ptr(), ev_rows[3 + q].data_ptr()
         a.ev_gi, a.ev_i = ev_gi.data_ptr(), ev_i.data_ptr()
-    W1, W2, W3, W4 = (w.detach() for w, _ in de_layers)
-    A1, A2, A3, A4 = (w.detach() for w, _ in ae_layers)
-    # Host-side accumulators of the AE head's K7h route: made on demand.  The one-launch route at hidden <= 64 (every gradient formed in
-    # the kernel) needs none of them -- 18 fills, a [T,B,z+v] copy and 2 small GEMM operands per call that the step's profile showed as
-    # glue (profiles/r04o_glue_dae01.txt).
-    zv_all = None
-    gA, gab, Sa1 = [None] * 4, [None] * 4, None
-
-    def host_accumulators():
-        nonlocal gA, gab, Sa1, zv_all
-        gA = [torch.zeros_like(w) for w in (A1, A2, A3, A4)]
-        gab = [torch.zeros(w.shape[0], **f32) for w in (A1, A2, A3, A4)]
-        Sa1 = torch.zeros((B, H), **f32)                    # sum over the heads of the AE's delta_1
-        zv_all = torch.cat((z.detach(), v.detach()), -1)    # [T, B, nzv] (one copy of the two input views)
-
+        keep.append(ev_i)
+    # The host-side accumulators of the AE head's K7h route are made on demand (`_wide_head_k7h`).  The one-launch route at hidden <= 64
+    # (every gradient formed in the kernel) needs none of them -- 18 fills, a [T,B,z+v] copy and 2 small GEMM operands per call that the
+    # step's profile showed as glue (profiles/r04o_glue_dae01.txt).
     gzv = torch.zeros((T, B, nzv), **f32)                       # dL/d(z|v) of the un-jumped inputs
     gjump = torch.zeros((B, n_ev, nzv), **f32) if n_ev else None
     carry_x = torch.zeros((B, xd), **f32)
     a.carry_x = carry_x.data_ptr()
-    xt_c = it_c = None
+    xt_c = None
     if x_true is not None or i_true is not None:
         if saved is not None:
             raise ValueError("teacher forcing: the recompute form only (a teacher-forced forward saves nothing)")
-        xt_c = _f32_dev(x_true, dev, "x_true").contiguous() if x_true is not None else None
-        it_c = _f32_dev(i_true, dev, "i_true").contiguous() if i_true is not None else None
+        xt_c, it_c = _bind_true_rows(a, x_true, i_true, dev, keep)
         if (xt_c is not None and tuple(xt_c.shape) != (T, B, xd)) or (it_c is not None and tuple(it_c.shape) != (T, B, idim)):
             raise ValueError("x_true / i_true must be [T,B,x_dim] / [T,B,i_dim]")
-        keep += [xt_c, it_c]
-        a.flags = (_lib.FLAG_INPUT_TRUE_X if xt_c is not None else 0) | (_lib.FLAG_INPUT_TRUE_I if it_c is not None else 0)
-        a.x_true = xt_c.data_ptr() if xt_c is not None else None
-        a.i_true = it_c.data_ptr() if it_c is not None else None
-    gp_de = _empty(sum(w.numel() + w.shape[0] for w in (W1, W2, W3, W4)), **f32)
+    gp_de = _empty(sum(w.numel() + w.shape[0] for w, _ in de_layers), **f32)
     ga0_de = _empty((B, n), **f32)
     a.grad_params_de, a.grad_all_initial_de = gp_de.data_ptr(), ga0_de.data_ptr()
     a.grad_zv = gzv.data_ptr()
@@ -143,10 +183,63 @@ def dae_backward_wide(method: str, de_layers: Layers, ae_layers: Layers, t, z, v
     if n_ev:
         parts = ([z_jump.detach()] if zd > 0 else []) + ([v_jump.detach()] if vd > 0 else [])
         jump_all = torch.cat(parts, -1)                         # [B, n_ev, nzv]
+    if saved is not None:
+        s_act, s_xst, s_ae, s_ev, s_evi = saved
+        if s_ae.shape != (3, T, B, H) or s_act.shape != (T - 1, S, 3, B, H) or (n_ev and (s_ev is None or s_ev.shape != (n_ev, 3, B, H))):
+            raise ValueError("saved activations do not belong to this call (shape)")
+        keep += [s_act, s_xst, s_ae, s_ev, s_evi]
+        a.saved_act, a.saved_xstage, a.saved_ae_act = s_act.data_ptr(), s_xst.data_ptr(), s_ae.data_ptr()
+        if n_ev:
+            a.saved_ev_act, a.saved_ev_i = s_ev.data_ptr(), s_evi.data_ptr()
+            for q in range(3):
+                ev_rows[q] = s_ev[:, q]
+    # > 0 (hidden <= 64, saved activations): the AE head's gradients are formed in the kernel too -- no head rows, no K7h
+    n_ae_raw = int(lib.psnode_dae_backward_wide_ae_floats(ctypes.byref(a)))
+    arows = gae_raw = agi = None
+    if n_ae_raw:
+        gae_raw = _empty(n_ae_raw, **f32)
+        a.grad_params_ae_raw = gae_raw.data_ptr()
+    else:
+        arows = ([s_ae[0], s_ae[1], s_ae[2]] if saved is not None else [_empty((T, B, H), **f32) for _ in range(3)])
+        arows += [_empty((T, B, H), **f32) for _ in range(3)]
+        agi = _empty((T, B, 16), **f32)
+        for q in range(3):
+            a.ae_act[q], a.ae_delta[q] = arows[q].data_ptr(), arows[3 + q].data_ptr()
+        a.ae_gi = agi.data_ptr()
+    return types.SimpleNamespace(a=a, keep=keep, dev=dev, f32=f32, T=T, B=B, xd=xd, zd=zd, vd=vd, nzv=nzv, ne=ne, n=n, Hr=Hr, H=H, n_ev=n_ev,
+                                 A=[w.detach() for w, _ in ae_layers], a0=a0, xs_c=xs_c, gx_c=gx_c, xt_c=xt_c, ev_rows=ev_rows, ev_gi=ev_gi,
+                                 gzv=gzv, gjump=gjump, carry_x=carry_x, gp_de=gp_de, ga0_de=ga0_de, jump_all=jump_all, arows=arows, agi=agi,
+                                 gae_raw=gae_raw)
 
-    def head_grads_hip(act, act_row_stride, delta, gi_slots, x_rows, zv_rows):
-        """the same contractions on K7h (psnode_dae_head_grads_f32): act = 3 device pointers' tensors whose row r lies r*act_row_stride
-        floats behind the first; delta / gi_slots / x_rows / zv_rows [R, B, .] contiguous"""
+
+def _wide_head_in_kernel(c) -> list:
+    """The AE's parameter gradients of a launch that formed them itself, from its raw block
+    [dAW1 | db1 | dAW2 | db2 | dAW3 | db3 | P3 (16 slots x h) | sg (16 slots)]."""
+    Hr, nzv, ne, raw = c.Hr, c.nzv, c.ne, c.gae_raw
+    out, o = [], 0
+    for cols in (c.n + c.xd + nzv, Hr, Hr):
+        out.append(raw[o:o + Hr * cols].view(Hr, cols)); o += Hr * cols
+        out.append(raw[o:o + Hr]); o += Hr
+    P3 = raw[o:o + 16 * Hr].view(16, Hr); o += 16 * Hr
+    sg = raw[o:o + 16]
+    return out + [P3[nzv:ne] + P3[ne + nzv:2 * ne], sg[nzv:ne] + sg[ne + nzv:2 * ne]]
+
+
+def _wide_head_k7h(lib, c, z, v, event_idx):
+    """The AE head's rows of a K7f launch -> its parameter gradients and its share of the input gradients, contracted by K7h
+    (psnode_dae_head_grads_f32) once over the grid points and once over the events taken.  Adds the share of z | v to c.gzv / c.gjump;
+    returns ([dAW1, db1, ..., dAW4, db4], the sum over the heads of the AE's delta_1 [B, H])."""
+    B, H, T, f32, dev = c.B, c.H, c.T, c.f32, c.dev
+    xd, nzv, ne, n, Hr, a0 = c.xd, c.nzv, c.ne, c.n, c.Hr, c.a0
+    A1 = c.A[0]
+    gA = [torch.zeros_like(w) for w in c.A]
+    gab = [torch.zeros(w.shape[0], **f32) for w in c.A]
+    Sa1 = torch.zeros((B, H), **f32)
+    zv_all = torch.cat((z.detach(), v.detach()), -1)    # [T, B, nzv] (one copy of the two input views)
+
+    def head_grads(act, act_row_stride, delta, gi_slots, x_rows, zv_rows):
+        """act = 3 device pointers' tensors whose row r lies r*act_row_stride floats behind the first; delta / gi_slots / x_rows / zv_rows
+        [R, B, .] contiguous"""
         nonlocal Sa1
         R = delta[0].shape[0]
         u = torch.zeros((R, B, 16), **f32)
@@ -185,90 +278,20 @@ def dae_backward_wide(method: str, de_layers: Layers, ae_layers: Layers, t, z, v
         Sa1 += sa1
         return gza[..., :nzv] if gza is not None else None
 
-    # (grad_is = None goes to the kernels as NULL: they read the rows of `is` instead and mask them out, branch-free.  Round 3 passed an
-    #  explicit zero tensor here because NULL gave wrong AE gradients on one register class; round 4 found the cause -- a uniform
-    #  `if (grad_is)` branch scheduled between an MFMA and the consumer of its result, psnode_dae_backward_wide.hip:add_gis -- and removed
-    #  the branch, so the C ABI's documented NULL is safe for every caller)
-    if saved is not None:
-        s_act, s_xst, s_ae, s_ev, s_evi = saved
-        if s_ae.shape != (3, T, B, H) or s_act.shape != (T - 1, S, 3, B, H) or (n_ev and (s_ev is None or s_ev.shape != (n_ev, 3, B, H))):
-            raise ValueError("saved activations do not belong to this call (shape)")
-        keep += [s_act, s_xst, s_ae, s_ev, s_evi]
-        a.saved_act, a.saved_xstage, a.saved_ae_act = s_act.data_ptr(), s_xst.data_ptr(), s_ae.data_ptr()
-        if n_ev:
-            a.saved_ev_act, a.saved_ev_i = s_ev.data_ptr(), s_evi.data_ptr()
-            for q in range(3):
-                ev_rows[q] = s_ev[:, q]
-        # > 0 (hidden <= 64, saved activations): the AE head's gradients are formed in the kernel too -- no head rows, no K7h
-        n_ae_raw = int(lib.psnode_dae_backward_wide_ae_floats(ctypes.byref(a)))
-        arows = None if n_ae_raw else [s_ae[0], s_ae[1], s_ae[2]] + [_empty((T, B, H), **f32) for _ in range(3)]
-    else:
-        n_ae_raw = int(lib.psnode_dae_backward_wide_ae_floats(ctypes.byref(a)))
-        arows = None if n_ae_raw else [_empty((T, B, H), **f32) for _ in range(6)]
-    gae_raw = agi = None
-    if n_ae_raw:
-        gae_raw = _empty(n_ae_raw, **f32)
-        a.grad_params_ae_raw = gae_raw.data_ptr()
-    else:
-        agi = _empty((T, B, 16), **f32)
-        for q in range(3):
-            a.ae_act[q], a.ae_delta[q] = arows[q].data_ptr(), arows[3 + q].data_ptr()
-        a.ae_gi = agi.data_ptr()
-    with torch.cuda.device(dev):
-        nbytes = lib.psnode_dae_backward_wide_workspace_bytes(ctypes.byref(a))
-        ws, wp, wn = _workspace_of(nbytes, dev)
-        st = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(lib.psnode_dae_backward_wide_f32(ctypes.byref(a), wp, wn, st), "psnode_dae_backward_wide_f32")
-        if n_ae_raw:
-            # one launch did everything: unpack [dAW1 | db1 | dAW2 | db2 | dAW3 | db3 | P3 (16 slots x h) | sg (16 slots)]
-            K1a, o = n + xd + nzv, 0
-            gA[0] = gae_raw[o:o + Hr * K1a].view(Hr, K1a); o += Hr * K1a
-            gab[0] = gae_raw[o:o + Hr]; o += Hr
-            gA[1] = gae_raw[o:o + Hr * Hr].view(Hr, Hr); o += Hr * Hr
-            gab[1] = gae_raw[o:o + Hr]; o += Hr
-            gA[2] = gae_raw[o:o + Hr * Hr].view(Hr, Hr); o += Hr * Hr
-            gab[2] = gae_raw[o:o + Hr]; o += Hr
-            P3 = gae_raw[o:o + 16 * Hr].view(16, Hr); o += 16 * Hr
-            sg = gae_raw[o:o + 16]
-            gA[3] = P3[nzv:ne] + P3[ne + nzv:2 * ne]
-            gab[3] = sg[nzv:ne] + sg[ne + nzv:2 * ne]
-            g = {"z_jump": None, "v_jump": None}
-            g["x_init"] = carry_x + gx_c[0]
-            g["all_initial"] = ga0_de                      # (the kernel added the AE's share)
-            g["z"] = gzv[..., :zd].contiguous() if zd > 0 else None
-            g["v"] = gzv[..., zd:].contiguous() if vd > 0 else None
-            if n_ev:
-                g["z_jump"] = gjump[..., :zd].contiguous() if zd > 0 else None
-                g["v_jump"] = gjump[..., zd:].contiguous() if vd > 0 else None
-            g["de"] = _split_grads(gp_de, de_layers)
-            g["ae"] = [gA[0], gab[0], gA[1], gab[1], gA[2], gab[2], gA[3], gab[3]]
-            return g
-        host_accumulators()
-        # the AE head's rows -> its parameter gradients and its share of the input gradients (K7h)
-        # (the heads at the grid points read the dataset rows under input_true_x; the event heads below always the running state)
-        gza = head_grads_hip(arows[:3], B * H, arows[3:], agi, xt_c if x_true is not None else xs_c, zv_all)
+    # (the heads at the grid points read the dataset rows under input_true_x; the event heads below always the running state)
+    gza = head_grads(c.arows[:3], B * H, c.arows[3:], c.agi, c.xt_c if c.xt_c is not None else c.xs_c, zv_all)
+    if nzv > 0:
+        c.gzv += gza
+    c.arows = c.agi = None
+    if c.n_ev:
+        evl = event_idx.long()
+        step_of = torch.zeros(c.n_ev, dtype=torch.long, device=dev).scatter_reduce_(
+            0, evl.clamp_min(0), torch.arange(T - 1, device=dev) * (evl >= 0), "amax")
+        ev_stride = c.ev_rows[0].stride(0)         # B*H (own buffers) or 3*B*H (layer q of the forward call's [nE,3,B,H])
+        gza = head_grads(c.ev_rows[:3], ev_stride, c.ev_rows[3:], c.ev_gi, c.xs_c[step_of], c.jump_all.permute(1, 0, 2))
         if nzv > 0:
-            gzv += gza
-        del arows, agi
-        if n_ev:
-            evl = event_idx.long()
-            step_of = torch.zeros(n_ev, dtype=torch.long, device=dev).scatter_reduce_(
-                0, evl.clamp_min(0), torch.arange(T - 1, device=dev) * (evl >= 0), "amax")
-            ev_stride = ev_rows[0].stride(0)         # B*H (own buffers) or 3*B*H (layer q of the forward call's [nE,3,B,H])
-            gza = head_grads_hip(ev_rows[:3], ev_stride, ev_rows[3:], ev_gi, xs_c[step_of], jump_all.permute(1, 0, 2))
-            if nzv > 0:
-                gjump += gza.permute(1, 0, 2)
-    g = {"z_jump": None, "v_jump": None}
-    g["x_init"] = carry_x + gx_c[0]
-    g["all_initial"] = ga0_de + Sa1 @ _pad_rows(A1[:, 0:n], H)
-    g["z"] = gzv[..., :zd].contiguous() if zd > 0 else None
-    g["v"] = gzv[..., zd:].contiguous() if vd > 0 else None
-    if n_ev:
-        g["z_jump"] = gjump[..., :zd].contiguous() if zd > 0 else None
-        g["v_jump"] = gjump[..., zd:].contiguous() if vd > 0 else None
-    g["de"] = _split_grads(gp_de, de_layers)
-    g["ae"] = [gA[0], gab[0], gA[1], gab[1], gA[2], gab[2], gA[3], gab[3]]
-    return g
+            c.gjump += gza.permute(1, 0, 2)
+    return [q for pair in zip(gA, gab) for q in pair], Sa1
 
 
 def _dae_backward_wide_sliced(step, method, de_layers, ae_layers, t, z, v, all_initial, xs, is_, grad_xs, grad_is, event_idx, z_jump, v_jump,
@@ -361,27 +384,18 @@ def dae_backward_tf(method, de_layers: Layers, ae_layers: Layers, t, z, v, all_i
 def _dae_backward_entry(opts, de_layers, ae_layers, t, z, v, all_initial, xs, is_, grad_xs, grad_is, event_idx, z_jump, v_jump, kernel, saved,
                         x_true=None, i_true=None, x_sub=None, ms_x_true=None):
     """The DAE backward on whichever entry point `opts` and the dataset rows select (`call_generic`): one marshalling for all of them."""
-    substeps = opts.substeps
     lib = _lib.load()
     dev = xs.device
     T, B, xd = xs.shape
     zd, vd, idim = z.shape[-1], v.shape[-1], is_.shape[-1]
-    if substeps > 1 and T >= 2 and (x_sub is None or tuple(x_sub.shape) != (T - 1, substeps - 1, B, xd) or not x_sub.is_contiguous()
-                                    or x_sub.dtype != torch.float32 or x_sub.device != dev):
-        raise ValueError(f"dae_backward: substeps={substeps} needs x_sub, the contiguous fp32 [{T - 1},{substeps - 1},{B},{xd}] tensor the "
-                         "forward call returned with save_sub=True")
+    _check_x_sub("dae_backward", opts.substeps, x_sub, T, B, xd, dev)
     if opts.per_trajectory:
         check_event_idx(event_idx, T, B, True, dev)
     keep: list = [x_sub, ms_x_true]
     args = opts.dae_backward_args(x_true is not None or i_true is not None)
     tf = args if isinstance(args, _lib.DaeBwdTfArgsF32) else None
     if tf is not None:
-        xt_c = _f32_dev(x_true, dev, "x_true").contiguous() if x_true is not None else None
-        it_c = _f32_dev(i_true, dev, "i_true").contiguous() if i_true is not None else None
-        keep += [xt_c, it_c]
-        tf.flags = (_lib.FLAG_INPUT_TRUE_X if xt_c is not None else 0) | (_lib.FLAG_INPUT_TRUE_I if it_c is not None else 0)
-        tf.x_true = xt_c.data_ptr() if xt_c is not None else None
-        tf.i_true = it_c.data_ptr() if it_c is not None else None
+        _bind_true_rows(tf, x_true, i_true, dev, keep)
     a = tf.base if tf is not None else args      # (tf.base: a view of the struct's own memory)
     a.method = opts.method_id
     a.kernel = KERNEL_ID[kernel]
@@ -389,13 +403,7 @@ def _dae_backward_entry(opts, de_layers, ae_layers, t, z, v, all_initial, xs, is
     a.de, a.ae = _mlp(de_layers, dev, "de", keep), _mlp(ae_layers, dev, "ae", keep)
     z, v, z_jump, v_jump = _aligned16(z), _aligned16(v), _aligned16(z_jump), _aligned16(v_jump)
     a.t, a.z, a.v = _view(t, dev, "t", keep), _view(z, dev, "z", keep), _view(v, dev, "v", keep)
-    a0 = _f32_dev(all_initial, dev, "all_initial").contiguous()
-    xs_c, is_c = _f32_dev(xs, dev, "xs").contiguous(), _f32_dev(is_, dev, "is").contiguous()
-    gx_c = _f32_dev(grad_xs, dev, "grad_xs").contiguous() if grad_xs is not None else torch.zeros_like(xs_c)
-    gi_c = _f32_dev(grad_is, dev, "grad_is").contiguous() if grad_is is not None else None
-    keep += [a0, xs_c, is_c, gx_c, gi_c]
-    a.all_initial, a.xs, a.is_, a.grad_xs = a0.data_ptr(), xs_c.data_ptr(), is_c.data_ptr(), gx_c.data_ptr()
-    a.grad_is = gi_c.data_ptr() if gi_c is not None else None
+    _bind_dae_inputs(a, all_initial, xs, is_, grad_xs, grad_is, dev, keep)
     g = {"z_jump": None, "v_jump": None}
     _bind_jumps(a, event_idx, (("z_jump", z_jump), ("v_jump", v_jump)), dev, keep)
     if event_idx is not None:

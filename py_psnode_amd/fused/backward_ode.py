@@ -5,7 +5,7 @@ import ctypes
 import torch
 
 from .. import _lib
-from ._common import (KERNEL_ID, GenericOpts, Layers, _aligned16, _bind_jumps, _check_saved, _empty, _f32_dev, _mlp, _split_grads, _view, _workspace_of, call_generic, check_event_idx, _ms_rows)
+from ._common import (KERNEL_ID, GenericOpts, Layers, _aligned16, _bind_jumps, _check_saved, _check_x_sub, _empty, _f32_dev, _mlp, _split_grads, _view, _workspace_of, call_generic, check_event_idx, _ms_rows)
 from .latent import latent_backward_wide, latent_wide_shape
 
 def _bwd_args(opts, de_layers, x_dim, z_dim, T, B, dev, keep, kernel="auto"):
@@ -71,10 +71,7 @@ def ode_backward(method, de_layers: Layers, t, z, all_initial, xs, grad_xs, even
     x_true = _ms_rows("ode_backward", segment, x_true, T, B, xd, dev)
     if per_trajectory:
         check_event_idx(event_idx, T, B, True, dev)
-    if substeps > 1 and T >= 2 and (x_sub is None or tuple(x_sub.shape) != (T - 1, substeps - 1, B, xd) or not x_sub.is_contiguous()
-                                    or x_sub.dtype != torch.float32 or x_sub.device != dev):
-        raise ValueError(f"ode_backward: substeps={substeps} needs x_sub, the contiguous fp32 [{T - 1},{substeps - 1},{B},{xd}] tensor the "
-                         "forward call returned with save_sub=True")
+    _check_x_sub("ode_backward", substeps, x_sub, T, B, xd, dev)
     if saved is not None and not input_true_x and latent_wide_shape(de_layers, None, xd, zd):
         g = latent_backward_wide(method, de_layers, None, t, z, None, all_initial, xs, None, grad_xs, None, event_idx=event_idx,
                                  z_jump=z_jump, saved=saved, need_grad_z=need_grad_z)
