@@ -956,6 +956,51 @@ int32_t psnode_dae_backward_ms_f32(const psnode_dae_bwd_tf_args_f32* args, const
                                    const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, const psnode_segments_f32* seg,
                                    void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Multiple-shooting segments in parallel (additive to ABI 10; DESIGN.md "Segments in parallel on K0 / K5 (BuildMsp)").
+ * The _ms call, computed by a launch grid of tiles x C workgroups instead of tiles: the dataset rows get no gradient, so the segments of a
+ * record are independent, forward and backward.  A record of T grid points has n_seg = ceil((T - 1) / every) segments; per_group
+ * consecutive ones form a time chunk, C = max(1, ceil(n_seg / per_group)) chunks; chunk c covers the steps c per_group every ..
+ * min((c + 1) per_group every, T - 1) - 1, and workgroup (tile, c) integrates its 16 trajectories over that chunk alone, or sweeps it
+ * backward.  What is computed is the _ms call's: x_out / i_out / x_sub, grad_x0 / grad_x_init, grad_z / grad_v and the jump gradients
+ * bit for bit; grad_params and grad_all_initial are sums over tiles x C partials (chunk 0's grad_all_initial plus the later chunks' in
+ * ascending order), so they differ from the _ms call's by the order of the additions.  Nothing crosses a chunk border inside a kernel
+ * -- no atomics, no flags, no fences: a small launch behind the backward sweep adds the grad_all_initial partials and, for a DAE, the
+ * z | v share of the head at a chunk's last grid point onto that row of grad_z / grad_v.  Bitwise repeatable.
+ * Rules: those of the _ms entry points with psnode_segment_groups_f32 in the segments struct's place -- NULL gives PSNODE_ERR_NULL,
+ * every < 1 or per_group < 1 PSNODE_ERR_DIMS, before anything else is looked at; per_group >= n_seg is legal and runs one chunk; more
+ * than 65535 chunks give PSNODE_ERR_UNSUPPORTED.  The forward workspace is psnode_workspace_bytes'; a backward call's is its own query's
+ * (one parameter partial per workgroup of the grid, and what crosses the chunk borders), 0 for a call the _supported query refuses. */
+typedef struct {
+    int32_t every;         /* >= 1: grid point k > 0 with k % every == 0 restarts from the dataset row */
+    const float* x_true;   /* as psnode_segments_f32::x_true */
+    int32_t per_group;     /* >= 1: segments per time chunk */
+} psnode_segment_groups_f32;
+int32_t psnode_ode_integrate_msp_supported(const psnode_ode_args_f32* args, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
+                                           const psnode_substeps_f32* sub, const psnode_segment_groups_f32* grp);
+int32_t psnode_ode_integrate_msp_f32(const psnode_ode_args_f32* args, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
+                                     const psnode_substeps_f32* sub, const psnode_segment_groups_f32* grp, void* workspace, size_t workspace_bytes,
+                                     void* stream);
+int32_t psnode_dae_integrate_msp_supported(const psnode_dae_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                           const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, const psnode_segment_groups_f32* grp);
+int32_t psnode_dae_integrate_msp_f32(const psnode_dae_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                     const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, const psnode_segment_groups_f32* grp,
+                                     void* workspace, size_t workspace_bytes, void* stream);
+int32_t psnode_ode_backward_msp_supported(const psnode_ode_bwd_args_f32* args, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
+                                          const psnode_substeps_f32* sub, const psnode_segment_groups_f32* grp);
+size_t psnode_ode_backward_msp_workspace_size(const psnode_ode_bwd_args_f32* args, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
+                                              const psnode_substeps_f32* sub, const psnode_segment_groups_f32* grp);
+int32_t psnode_ode_backward_msp_f32(const psnode_ode_bwd_args_f32* args, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
+                                    const psnode_substeps_f32* sub, const psnode_segment_groups_f32* grp, void* workspace, size_t workspace_bytes,
+                                    void* stream);
+int32_t psnode_dae_backward_msp_supported(const psnode_dae_bwd_tf_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                          const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, const psnode_segment_groups_f32* grp);
+size_t psnode_dae_backward_msp_workspace_size(const psnode_dae_bwd_tf_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                              const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub,
+                                              const psnode_segment_groups_f32* grp);
+int32_t psnode_dae_backward_msp_f32(const psnode_dae_bwd_tf_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                    const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, const psnode_segment_groups_f32* grp,
+                                    void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -43,6 +43,8 @@ ABI_VERSION = 10         # == PSNODE_ABI_VERSION of include/psnode_hip.h (2: rou
                          #     Adams-Bashforth on K0 / K5;
                          #     additive, same version: psnode_segments_f32 and the psnode_{ode,dae}_{integrate,backward}_ms_* entry points --
                          #     multiple-shooting segments on K0 / K5;
+                         #     additive, same version: psnode_segment_groups_f32 and the psnode_{ode,dae}_{integrate,backward}_msp_* entry points
+                         #     (with psnode_{ode,dae}_backward_msp_workspace_size) -- those segments spread over a tiles x chunks launch grid;
                          #     additive, same version: psnode_loss_fn_f32 and psnode_masked_loss_* / psnode_loss_per_sample_f32 -- L1, SmoothL1 and
                          #     Huber on K6, and the per-sample evaluation table of all four kinds)
 LIB_NAME = "libpsnode_hip.so"
@@ -91,6 +93,9 @@ EXPORTS = (
     "psnode_ode_integrate_ms_supported", "psnode_ode_integrate_ms_f32", "psnode_dae_integrate_ms_supported", "psnode_dae_integrate_ms_f32",
     "psnode_ode_backward_ms_supported", "psnode_ode_backward_ms_f32",
     "psnode_dae_backward_ms_supported", "psnode_dae_backward_ms_f32",
+    "psnode_ode_integrate_msp_supported", "psnode_ode_integrate_msp_f32", "psnode_dae_integrate_msp_supported", "psnode_dae_integrate_msp_f32",
+    "psnode_ode_backward_msp_supported", "psnode_ode_backward_msp_workspace_size", "psnode_ode_backward_msp_f32",
+    "psnode_dae_backward_msp_supported", "psnode_dae_backward_msp_workspace_size", "psnode_dae_backward_msp_f32",
 )
 
 
@@ -125,6 +130,11 @@ class SegmentsF32(ctypes.Structure):
     """psnode_segments_f32: grid point k > 0 with k % every == 0 restarts from the dataset row; x_true [T, B, x_dim]: those rows for a
     backward call (a forward call reads its args' x; NULL there)."""
     _fields_ = [("every", c_int32), ("x_true", c_void_p)]
+
+
+class SegmentGroupsF32(ctypes.Structure):
+    """psnode_segment_groups_f32: psnode_segments_f32 plus per_group >= 1, the segments per time chunk of the tiles x chunks launch grid."""
+    _fields_ = [("every", c_int32), ("x_true", c_void_p), ("per_group", c_int32)]
 
 
 class SubstepsF32(ctypes.Structure):
@@ -350,10 +360,12 @@ def load():
             if fam in ("plain", "none") or (fam == "tf" and stem != "dae_backward"):
                 continue
             query = [ptr(DaeBwdTfArgsF32 if stem == "dae_backward" and f.tf_args else args_t)] + [ptr(ActF32)] * (n_act if f.acts else 0) + \
-                    [ptr(RkTableauF32)] * f.tab + [ptr(SubstepsF32)] * f.sub + [ptr(SegmentsF32)] * f.seg
+                    [ptr(RkTableauF32)] * f.tab + [ptr(SubstepsF32)] * f.sub + [ptr(SegmentGroupsF32 if f.par else SegmentsF32)] * f.seg
             protos = {"supported": (c_int32, query), "f32": (c_int32, query + [c_int32] * f.pt + [c_void_p, c_size_t, c_void_p])}
-            if stem == "dae_backward" and f.workspace == "own":
+            if stem == "dae_backward" and f.workspace == "own" and not f.par:
                 protos["workspace_bytes"] = (c_size_t, query)
+            if f.par and stem in ("ode_backward", "dae_backward"):      # (both directions of the family size their own workspace)
+                protos["workspace_size"] = (c_size_t, query)
             for kind, (restype, argtypes) in protos.items():
                 fn = getattr(lib, f"psnode_{stem}_{fam}_{kind}")
                 fn.restype, fn.argtypes = restype, argtypes

@@ -59,7 +59,7 @@ def _generic_only_training(opts, kernel, teacher_forced, T=2) -> bool:
 
 
 def ode_training_supported(method, layers, x_dim, z_dim, T, B, kernel="auto", act=None, input_true_x=False, substeps=1,
-                           externals="hold", per_trajectory=False, segment=None) -> bool:
+                           externals="hold", per_trajectory=False, segment=None, segment_parallel=None) -> bool:
     """What the solver asks before it routes a call that needs autograd to the fused forward + backward pair.  act (fused.Act; None =
     ELU(1)): an activation other than ELU(1) trains on K0 + K5 alone, so K5 answers.  input_true_x: teacher-forced training -- K4f's
     recompute form on kernel "auto" / "mfma" where the shape is its, else K5 on "auto" / "generic"; ELU(1) only.
@@ -69,12 +69,14 @@ def ode_training_supported(method, layers, x_dim, z_dim, T, B, kernel="auto", ac
     per_trajectory=True (a call WITH events): K0 + K5 in their per-trajectory builds for every substeps >= 1, the same rules; never
     together with externals="linear".
     segment (an int >= 1): K0 + K5 in their multiple-shooting builds for every substeps >= 1; never teacher-forced, never together with
-    externals="linear" or per-trajectory events."""
-    opts = fused.GenericOpts.of(method, (act,), substeps, externals, bool(per_trajectory), segment)
+    externals="linear" or per-trajectory events.  segment_parallel (None, "auto", an int >= 1): the segment-parallel builds answer
+    where this record of T grid points and B trajectories splits into more than one time chunk."""
+    opts = fused.GenericOpts.of(method, (act,), substeps, externals, bool(per_trajectory), segment,
+                                fused.resolve_segment_parallel(segment_parallel, segment, T, B, layers[0][0].device))
     if opts.family != "plain":
         return _generic_only_training(opts, kernel, input_true_x) and fused.ode_backward_supported(
             method, layers, x_dim, z_dim, kernel, act=act, substeps=substeps, externals=externals, per_trajectory=per_trajectory,
-            segment=segment)
+            segment=segment, segment_parallel=opts.chunks(T))
     if input_true_x:
         if kernel in ("auto", "mfma") and fused.ode_backward_supported(method, layers, x_dim, z_dim, "wide"):
             return True
@@ -89,22 +91,23 @@ def _dae_tf_on_k7f(method, kernel, de, ae, x_dim, z_dim, v_dim, i_dim) -> bool:
 
 
 def dae_training_supported(method, de, ae, x_dim, z_dim, v_dim, i_dim, T, B, act=None, kernel="auto", input_true_x=False,
-                           input_true_i=False, substeps=1, externals="hold", per_trajectory=False, segment=None) -> bool:
+                           input_true_i=False, substeps=1, externals="hold", per_trajectory=False, segment=None, segment_parallel=None) -> bool:
     """act: None (both MLPs ELU(1)) or (de_act, ae_act); an activation other than ELU(1) trains on K0 + K5 alone, so K5 answers.
     input_true_x / input_true_i: teacher-forced training (T >= 2, ELU(1) only) -- K7f's recompute form on kernel "auto" / "mfma" where the
     shape is its, else K5 on "auto" / "generic".  method a fused.Tableau: K0 + K5 on kernel "auto" / "generic", the same rules.
     substeps > 1: K0 + K5 in their sub-step builds on kernel "auto" / "generic", the same rules.
     externals="linear": K0 + K5 in their linear-externals builds for every substeps >= 1, the same rules.
     per_trajectory=True (a call WITH events): K0 + K5 in their per-trajectory builds for every substeps >= 1, the same rules.
-    segment (an int >= 1): K0 + K5 in their multiple-shooting builds, as ode_training_supported."""
-    opts = fused.GenericOpts.of(method, fused.dae_acts(act), substeps, externals, bool(per_trajectory), segment)
+    segment (an int >= 1): K0 + K5 in their multiple-shooting builds, as ode_training_supported; segment_parallel: as there."""
+    opts = fused.GenericOpts.of(method, fused.dae_acts(act), substeps, externals, bool(per_trajectory), segment,
+                                fused.resolve_segment_parallel(segment_parallel, segment, T, B, de[0][0].device))
     teacher_forced = input_true_x or input_true_i
     if opts.family != "plain":
         if opts.family == "act":      # (an activation alone: asked without the caller's kernel, as the ELU(1) call at the bottom is)
             kernel = "auto"
         return _generic_only_training(opts, kernel, teacher_forced, T) and fused.dae_backward_supported(
             method, de, ae, x_dim, z_dim, v_dim, i_dim, act=act, kernel=kernel, substeps=substeps, externals=externals,
-            per_trajectory=per_trajectory, segment=segment)
+            per_trajectory=per_trajectory, segment=segment, segment_parallel=opts.chunks(T))
     if teacher_forced:
         if T < 2:
             return False
@@ -291,7 +294,7 @@ class _FusedOdeGeneric(torch.autograd.Function):
         x_in = x_data if x_data is not None else (x0.detach().contiguous() if tx else x0.unsqueeze(0))
         xs, x_sub = fused.ode_integrate(method, _layers(params), t, x_in, z, all_initial, z_jump=z_jump, event_idx=event_idx, kernel=kernel,
                                         input_true_x=tx, act=opts.acts[0], substeps=opts.substeps, save_sub=True, externals=opts.externals,
-                                        per_trajectory=opts.per_trajectory, segment=opts.segment)
+                                        per_trajectory=opts.per_trajectory, segment=opts.segment, segment_parallel=opts.chunks(t.shape[0]))
         last_saved_bytes = x_sub.numel() * x_sub.element_size()
         ctx.method, ctx.opts, ctx.kernel, ctx.tx, ctx.event_idx = method, opts, kernel, tx, event_idx
         # (tx: the backward starts every interval from the dataset row and reads no xs)
@@ -307,7 +310,7 @@ class _FusedOdeGeneric(torch.autograd.Function):
                                                      need_grad_z=need_z, need_grad_zj=_needs(ctx, cls, "z_jump"), kernel=ctx.kernel,
                                                      input_true_x=ctx.tx, act=opts.acts[0], substeps=opts.substeps, x_sub=x_sub,
                                                      externals=opts.externals, per_trajectory=opts.per_trajectory, segment=opts.segment,
-                                                     x_true=opt["x_data"])
+                                                     x_true=opt["x_data"], segment_parallel=opts.chunks(t.shape[0]))
         if gz is None and need_z:
             gz = torch.zeros_like(z)
         return _grad_tuple(ctx, cls, dict(x0=None if ctx.tx else gx0, z=gz, all_initial=ga0, z_jump=gzj), gpar)
@@ -315,7 +318,7 @@ class _FusedOdeGeneric(torch.autograd.Function):
 
 # fused.GenericOpts.family ("ab": with per_trajectory) -> the name of its Function: `_FusedOde<name>` / `_FusedDae<name>`, an empty subclass of
 # the model's one body, is what xs.grad_fn reports.  A further family of K0 / K5 that saves sub-state rows adds a row here, not a class.
-_FAMILY_CLASSES = {"sub": "Sub", "lin": "Lin", "pev": "Pev", ("ab", False): "Ab", ("ab", True): "AbPev", "ms": "Ms"}
+_FAMILY_CLASSES = {"sub": "Sub", "lin": "Lin", "pev": "Pev", ("ab", False): "Ab", ("ab", True): "AbPev", "ms": "Ms", "msp": "Msp"}
 # the families that go to _FusedOde / _FusedDae / _FusedDaeTeacherForced
 _OWN_CLASS = ("plain", "act", "rk")
 # ... and those whose forward (fused.ode_integrate / fused.dae_integrate) is the first to check the call
@@ -340,17 +343,18 @@ def _refuse(what, opts, kernel, teacher_forced):
 
 
 _ODE_CLASSES = _family_classes(_FusedOdeGeneric, "_FusedOde")
-globals().update({cls.__name__: cls for cls in _ODE_CLASSES.values()})      # _FusedOdeSub, ..Lin, ..Pev, ..Ab, ..AbPev, ..Ms
+globals().update({cls.__name__: cls for cls in _ODE_CLASSES.values()})      # _FusedOdeSub, ..Lin, ..Pev, ..Ab, ..AbPev, ..Ms, ..Msp
 
 
 def fused_ode_integrate(method, kernel, layers, t, x, z, all_initial, event_t=None, z_jump=None, check_events=False, input_true_x=False,
-                        x_init=None, act=None, substeps=1, externals="hold", per_trajectory=False, segment=None):
+                        x_init=None, act=None, substeps=1, externals="hold", per_trajectory=False, segment=None, segment_parallel=None):
     """Differentiable fused integrate_ODE: gradients flow to x[0], z, all_initial, z_jump and the MLP.  input_true_x (teacher forcing,
     my_solvers.py:72-74): every step starts from the dataset row x[k]; gradients flow to z, all_initial, z_jump and the MLP (the dataset
     x gets none: callers whose x requires grad take the callback walk).  act: the MLP's activation (fused.Act), None = ELU(1); any other
     trains on K0 + K5 (no teacher forcing).  per_trajectory: every trajectory jumps at its own event times (fused.event_table(...,
     per_trajectory=True)); a call without events is the call it is without the flag.  segment: multiple shooting -- the dataset rows get
-    no gradient (a caller whose x requires grad and restarts walks)."""
+    no gradient (a caller whose x requires grad and restarts walks).  segment_parallel (None, "auto", an int >= 1): the segments on a
+    tiles x chunks launch grid, forward and backward (fused.ode_integrate); one chunk is the call without it."""
     with torch.no_grad():
         event_idx = fused.event_table(t, event_t, check_events, per_trajectory=per_trajectory)
     if event_idx is None:
@@ -358,7 +362,8 @@ def fused_ode_integrate(method, kernel, layers, t, x, z, all_initial, event_t=No
     params = [p for wb in layers for p in wb]
     tx = bool(input_true_x)
     x0 = x.detach() if tx else (x[0] if x_init is None else x_init)     # (x_init: integrate_ODE's extension -- no SelectBackward)
-    opts = fused.GenericOpts.of(method, (act,), substeps, externals, bool(per_trajectory) and event_idx is not None, segment)
+    opts = fused.GenericOpts.of(method, (act,), substeps, externals, bool(per_trajectory) and event_idx is not None, segment,
+                                fused.resolve_segment_parallel(segment_parallel, segment, t.shape[0], t.shape[1], t.device))
     _refuse("fused_ode_integrate", opts, kernel, tx)
     if opts.family in _OWN_CLASS:
         return _FusedOde.apply(method, kernel, act, event_idx, t, x0, z, all_initial, z_jump, *params)
@@ -454,7 +459,8 @@ class _FusedDaeGeneric(torch.autograd.Function):
         act = _dae_act(opts.acts)
         xs, is_, x_sub = fused.dae_integrate(method, de, ae, x_init, t, x, z, v, i, all_initial, z_jump=z_jump, v_jump=v_jump, event_idx=event_idx,
                                              kernel=kernel, input_true_x=tx, input_true_i=ti, act=act, substeps=opts.substeps, save_sub=True,
-                                             externals=opts.externals, per_trajectory=opts.per_trajectory, segment=opts.segment)
+                                             externals=opts.externals, per_trajectory=opts.per_trajectory, segment=opts.segment,
+                                             segment_parallel=opts.chunks(t.shape[0]))
         global last_saved_bytes
         last_saved_bytes = x_sub.numel() * x_sub.element_size()
         ctx.method, ctx.opts, ctx.kernel, ctx.act, ctx.tx, ctx.ti, ctx.n_de, ctx.event_idx = method, opts, kernel, act, tx, ti, n_de, event_idx
@@ -473,22 +479,22 @@ class _FusedDaeGeneric(torch.autograd.Function):
                                       i_true=i if ctx.ti else None, **common)
         else:
             g = fused.dae_backward(ctx.method, de, ae, t, z, v, a0, xs, is_, grad_xs, grad_is, act=ctx.act, segment=opts.segment,
-                                   x_true=x if opts.segment is not None else None, **common)
+                                   x_true=x if opts.segment is not None else None, segment_parallel=opts.chunks(t.shape[0]), **common)
         return _dae_grads(ctx, _FusedDaeGeneric, g, z, v)
 
 
 _DAE_CLASSES = _family_classes(_FusedDaeGeneric, "_FusedDae")
-globals().update({cls.__name__: cls for cls in _DAE_CLASSES.values()})      # _FusedDaeSub, ..Lin, ..Pev, ..Ab, ..AbPev, ..Ms
+globals().update({cls.__name__: cls for cls in _DAE_CLASSES.values()})      # _FusedDaeSub, ..Lin, ..Pev, ..Ab, ..AbPev, ..Ms, ..Msp
 
 
 def fused_dae_integrate(method, kernel, de_layers, ae_layers, x_init, t, z, v, i, all_initial, event_t=None, z_jump=None, v_jump=None,
                         check_events=False, x=None, input_true_x=False, input_true_i=False, act=None, substeps=1, externals="hold",
-                        per_trajectory=False, segment=None):
+                        per_trajectory=False, segment=None, segment_parallel=None):
     """Differentiable fused integrate_DAE: gradients flow to x_init, z, v, all_initial, the jump inputs and both MLPs.  Without teacher
     forcing `i` only provides the width of the algebraic variable.  input_true_x / input_true_i: `x` / `i` are the dataset rows the DE
     and the heads are fed (my_solvers.py:111-121); they get no gradient.  act: None or (de_act, ae_act) (fused.Act, None = ELU(1)); an
     activation other than ELU(1) trains on K0 + K5 (no teacher forcing).  per_trajectory: as fused_ode_integrate.  segment: multiple
-    shooting -- `x` is the dataset rows the restarts read; they get no gradient."""
+    shooting -- `x` is the dataset rows the restarts read; they get no gradient.  segment_parallel: as fused_ode_integrate."""
     with torch.no_grad():
         event_idx = fused.event_table(t, event_t, check_events, per_trajectory=per_trajectory)
     if event_idx is None:
@@ -498,7 +504,8 @@ def fused_dae_integrate(method, kernel, de_layers, ae_layers, x_init, t, z, v, i
         v_jump = v_jump if (v_jump is not None and v_jump.shape[-1] > 0) else None
     params = [p for wb in list(de_layers) + list(ae_layers) for p in wb]
     tx, ti = bool(input_true_x), bool(input_true_i)
-    opts = fused.GenericOpts.of(method, fused.dae_acts(act), substeps, externals, bool(per_trajectory) and event_idx is not None, segment)
+    opts = fused.GenericOpts.of(method, fused.dae_acts(act), substeps, externals, bool(per_trajectory) and event_idx is not None, segment,
+                                fused.resolve_segment_parallel(segment_parallel, segment, t.shape[0], t.shape[1], t.device))
     _refuse("fused_dae_integrate", opts, kernel, tx or ti)
     if opts.segment is not None and (x is None or x.shape[-1] == 0):
         raise ValueError(f"fused_dae_integrate: segment={segment} restarts from the dataset rows x[k]; this call has none")

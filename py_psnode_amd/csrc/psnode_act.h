@@ -280,9 +280,10 @@ struct K0Call {
     psnode_rk_tableau_f32 rk;      // the builds with a tableau: given, or the args' method written as one (family_tableau)
     SubDev sub;                    // kBuildSub, kBuildLin, kBuildPev, kBuildMs: sub-steps per grid interval and x_sub
     int ev_pt, ms_every;           // kBuildAb: the event table is [T-1, B]; kBuildMs: grid point k > 0 with k % ms_every == 0 restarts from row k of x
+    int per_group;                 // kBuildMsp: segments per time chunk (the grid is tiles x msp_chunks(T, ms_every, per_group))
 };
 // K0's launcher (psnode_generic_impl.h), instantiated once per build policy in that policy's object, as K5's generic_backward_launch<B>
-// (psnode_common.h) is: reads of `call` what B's kernels take.  BuildPev: a.ev is the [T-1, B] table and not null; BuildMs: a.x has all T rows.
+// (psnode_common.h) is: reads of `call` what B's kernels take.  BuildPev: a.ev is the [T-1, B] table and not null; BuildMs, BuildMsp: a.x has all T rows.
 template <class B>
 hipError_t launch_generic(const IntegrateDev& a, bool dae, const K0Call& call, hipStream_t stream);
 

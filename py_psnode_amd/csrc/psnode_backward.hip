@@ -100,6 +100,7 @@ int generic_backward(BuildId build, const GenericBwdCall& c, const ActPair* act,
         case kBuildPev: return generic_backward_launch<BuildPev>(c, act, ws, s);
         case kBuildAb: return generic_backward_launch<BuildAb>(c, act, ws, s);
         case kBuildMs: return generic_backward_launch<BuildMs>(c, act, ws, s);
+        case kBuildMsp: return generic_backward_launch<BuildMsp>(c, act, ws, s);
     }
     return PSNODE_ERR_UNSUPPORTED;      // (no such build)
 }
@@ -215,7 +216,7 @@ extern "C" int32_t psnode_dae_backward_f32(const psnode_dae_bwd_args_f32* a, voi
     return generic_backward(kBuildElu1, generic_bwd_call(*a), nullptr, workspace, stream);
 }
 
-// ---- The K5 entry-point families psnode_dae_backward_tf_* and psnode_{ode,dae}_backward_{act,rk,sub,lin,pev,ab,ms}_*: one checked call path
+// ---- The K5 entry-point families psnode_dae_backward_tf_* and psnode_{ode,dae}_backward_{act,rk,sub,lin,pev,ab,ms,msp}_*: one checked call path
 // (k5_backward), one query (k5_supported) over the family table of psnode_generic_family.h, which also holds the order of the checks per family.
 namespace {
 constexpr uint32_t kTfFlags = PSNODE_FLAG_INPUT_TRUE_X | PSNODE_FLAG_INPUT_TRUE_I;
@@ -267,6 +268,14 @@ bool k5_route_ok(const FamilyRow& f, const Args& a, const ActPair& p, bool elu1,
     if (saved_rows(b, f.saved_all ? kSavedAll : query ? kSavedAct : kSavedActCall)) return false;
     return generic_ok(&b, f.pre || family_build(f, act_pair_keeps_u(p)) == kBuildPre, f.lin) != 0;      // (the fit of the build)
 }
+// K5's workspace for the family's call: gbwd_layout, or the segment-parallel build's own layout for the call's chunks
+template <class Base>
+size_t k5_workspace_floats(const FamilyRow& f, const Base& b, const CallOpts& o) {
+    if (!f.par) return generic_bwd_workspace_floats(&b.de, ae_of(b), b.B);
+    const psnode_mlp_f32* ae = ae_of(b);
+    const int n = b.de.in_dim / 3;      // (the recipe: 3 n input columns, checked by the route)
+    return generic_bwd_msp_workspace_floats(&b.de, ae, b.B, n, ae ? ae->in_dim - n - b.x_dim : 0, family_chunks(f, o, b.T));
+}
 
 template <class Args>
 int k5_backward(Family fam, const Args* a, const CallOpts& o, void* workspace, size_t workspace_bytes, void* stream) {
@@ -289,17 +298,17 @@ int k5_backward(Family fam, const Args* a, const CallOpts& o, void* workspace, s
     if (rc) return rc;
     const auto& b = base(*a);
     if (b.T < 1 || b.B < 1 || (tf_struct && tf_flags(*a) && b.T < 2)) return PSNODE_ERR_DIMS;
-    if (!k5_route_ok(f, *a, p, elu1, false)) return PSNODE_ERR_UNSUPPORTED;
+    if (!k5_route_ok(f, *a, p, elu1, false) || family_chunks(f, o, b.T) > kMaxChunks) return PSNODE_ERR_UNSUPPORTED;
     const int nsub = family_substeps(f, o);
     if (!ptrs_ok(a) || (nsub > 1 && b.T >= 2 && !o.sub->x_sub) || (f.needs_events && !b.event_idx)) return PSNODE_ERR_NULL;
-    if (f.seg && b.T - 1 > o.seg->every && !o.seg->x_true) return PSNODE_ERR_NULL;
-    if (!workspace_ok(workspace, workspace_bytes, generic_bwd_workspace_floats(&b.de, ae_of(b), b.B) * sizeof(float))) return PSNODE_ERR_WORKSPACE;
+    if (f.seg && b.T - 1 > o.every() && !o.x_true()) return PSNODE_ERR_NULL;
+    if (!workspace_ok(workspace, workspace_bytes, k5_workspace_floats(f, b, o) * sizeof(float))) return PSNODE_ERR_WORKSPACE;
     GenericBwdCall c = generic_bwd_call(*a);
     if (f.tab != kTabNone) c.rk = &t;
     c.substeps = nsub;
     c.x_sub = o.sub ? o.sub->x_sub : nullptr;
     c.ab_pt = o.per_trajectory != 0;
-    if (f.seg) { c.ms_every = o.seg->every; c.ms_x_true = o.seg->x_true; }
+    if (f.seg) { c.ms_every = o.every(); c.ms_x_true = o.x_true(); c.ms_per_group = o.per_group(); }
     return generic_backward(family_build(f, act_pair_keeps_u(p)), c, &p, workspace, stream);
 }
 
@@ -315,7 +324,7 @@ int k5_supported(Family fam, const Args* a, const CallOpts& o) {
         if (fam == kFamAct) return a->flags == 0 && k5_supported(kFamAct, &a->base, {o.de_act, o.ae_act});      // (as k5_backward's)
     }
     if (family_tableau(f, o.tab, &base(*a).method, t)) return 0;
-    return k5_route_ok(f, *a, p, elu1, true);
+    return k5_route_ok(f, *a, p, elu1, true) && family_chunks(f, o, base(*a).T) <= kMaxChunks;
 }
 
 // (DAE: the ODE's sizes come from psnode_ode_backward_workspace_bytes)
@@ -327,7 +336,7 @@ size_t k5_workspace_bytes(Family fam, const psnode_dae_bwd_tf_args_f32* a, const
         act_pair(o.de_act, o.ae_act, p, elu1);
         return elu1 ? psnode_dae_backward_tf_workspace_bytes(a) : psnode_dae_backward_workspace_bytes(&a->base);
     }
-    return generic_bwd_workspace_floats(&a->base.de, &a->base.ae, a->base.B) * sizeof(float);
+    return k5_workspace_floats(kFamilies[fam], a->base, o) * sizeof(float);
 }
 }  // namespace
 
@@ -485,4 +494,38 @@ extern "C" int32_t psnode_dae_backward_ms_f32(const psnode_dae_bwd_tf_args_f32* 
                                               const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, const psnode_segments_f32* seg,
                                               void* ws, size_t bytes, void* stream) {
     return k5_backward(kFamMs, a, {de_act, ae_act, tab, sub, seg}, ws, bytes, stream);
+}
+
+// (segments in parallel: the _ms call swept by a tiles x chunks grid; its workspace is its own -- one parameter partial per workgroup, and
+//  what crosses a chunk border)
+extern "C" int32_t psnode_ode_backward_msp_supported(const psnode_ode_bwd_args_f32* a, const psnode_act_f32* de_act,
+                                                     const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub,
+                                                     const psnode_segment_groups_f32* grp) {
+    return k5_supported(kFamMsp, a, {de_act, nullptr, tab, sub, nullptr, 0, grp});
+}
+extern "C" size_t psnode_ode_backward_msp_workspace_size(const psnode_ode_bwd_args_f32* a, const psnode_act_f32* de_act,
+                                                         const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub,
+                                                         const psnode_segment_groups_f32* grp) {
+    const CallOpts o{de_act, nullptr, tab, sub, nullptr, 0, grp};
+    return k5_supported(kFamMsp, a, o) ? k5_workspace_floats(kFamilies[kFamMsp], *a, o) * sizeof(float) : 0;
+}
+extern "C" int32_t psnode_ode_backward_msp_f32(const psnode_ode_bwd_args_f32* a, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
+                                               const psnode_substeps_f32* sub, const psnode_segment_groups_f32* grp, void* ws, size_t bytes,
+                                               void* stream) {
+    return k5_backward(kFamMsp, a, {de_act, nullptr, tab, sub, nullptr, 0, grp}, ws, bytes, stream);
+}
+extern "C" int32_t psnode_dae_backward_msp_supported(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act,
+                                                     const psnode_act_f32* ae_act, const psnode_rk_tableau_f32* tab,
+                                                     const psnode_substeps_f32* sub, const psnode_segment_groups_f32* grp) {
+    return k5_supported(kFamMsp, a, {de_act, ae_act, tab, sub, nullptr, 0, grp});
+}
+extern "C" size_t psnode_dae_backward_msp_workspace_size(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act,
+                                                         const psnode_act_f32* ae_act, const psnode_rk_tableau_f32* tab,
+                                                         const psnode_substeps_f32* sub, const psnode_segment_groups_f32* grp) {
+    return k5_workspace_bytes(kFamMsp, a, {de_act, ae_act, tab, sub, nullptr, 0, grp});
+}
+extern "C" int32_t psnode_dae_backward_msp_f32(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                               const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub,
+                                               const psnode_segment_groups_f32* grp, void* ws, size_t bytes, void* stream) {
+    return k5_backward(kFamMsp, a, {de_act, ae_act, tab, sub, nullptr, 0, grp}, ws, bytes, stream);
 }

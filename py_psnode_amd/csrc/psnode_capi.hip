@@ -108,6 +108,7 @@ int dispatch(IntegrateDev& d, bool dae, int kernel, const psnode_mlp_f32* de, co
         case kBuildPev: e = launch_generic<BuildPev>(d, dae, call, stream); break;
         case kBuildAb: e = launch_generic<BuildAb>(d, dae, call, stream); break;
         case kBuildMs: e = launch_generic<BuildMs>(d, dae, call, stream); break;
+        case kBuildMsp: e = launch_generic<BuildMsp>(d, dae, call, stream); break;
     }
     return ok_or_hip(e);
 }
@@ -195,7 +196,7 @@ int fill_dae(const psnode_dae_args_f32* a, IntegrateDev& d) {
     return PSNODE_OK;
 }
 
-// ---- The K0 entry-point families psnode_{ode,dae}_integrate_{act,rk,sub,lin,pev,ab,ms}_*: one checked call path (k0_integrate) and one query
+// ---- The K0 entry-point families psnode_{ode,dae}_integrate_{act,rk,sub,lin,pev,ab,ms,msp}_*: one checked call path (k0_integrate) and one query
 // (k0_supported) over the family table of psnode_generic_family.h, which also holds the order of the checks per family.
 // the ODE / DAE difference: the side outputs, the recipe widths, fill_*, the AE, the plain entry point
 bool side_outputs(const psnode_ode_args_f32& a) { return a.save_act || a.save_xstage; }
@@ -238,14 +239,15 @@ int k0_integrate(Family fam, const Args* args, const CallOpts& o, void* workspac
     if (rc && !(f.tab == kTabNone && rc == PSNODE_ERR_METHOD)) return rc;      // (a call without a tableau leaves a bad method to fill_*, behind the route; its query refuses it in front)
     Args c = *args;
     if (f.tab != kTabNone) c.method = PSNODE_EULER;      // (not read by the build; fill_* checks it)
-    if (!k0_route_ok(f, c)) return PSNODE_ERR_UNSUPPORTED;
+    if (!k0_route_ok(f, c) || family_chunks(f, o, c.T) > kMaxChunks) return PSNODE_ERR_UNSUPPORTED;
     IntegrateDev d;
     rc = fill(&c, d);
     if (rc) return rc;
     if (f.needs_events && !d.ev) return PSNODE_ERR_NULL;
     call.build = family_build(f, act_pair_pre(call.act));      // (K0 keeps no u)
     call.ev_pt = o.per_trajectory ? 1 : 0;
-    call.ms_every = o.seg ? o.seg->every : 0;
+    call.ms_every = o.has_seg() ? o.every() : 0;
+    call.per_group = o.per_group();
     call.sub = SubDev{family_substeps(f, o), o.sub ? o.sub->x_sub : nullptr};
     return dispatch(d, ae_of(c) != nullptr, c.kernel, &c.de, ae_of(c), workspace, workspace_bytes, static_cast<hipStream_t>(stream), call);
 }
@@ -260,7 +262,7 @@ int k0_supported(Family fam, const Args* a, const CallOpts& o) {
     const FamilyRow& f = kFamilies[fam];
     if (family_tableau(f, o.tab, &a->method, t) || !recipe_ok(*a)) return 0;
     if (f.elu1_plain && elu1) return 1;
-    if (!k0_route_ok(f, *a)) return 0;
+    if (!k0_route_ok(f, *a) || family_chunks(f, o, a->T) > kMaxChunks) return 0;
     IntegrateDev d = dims_only(*a);
     d.maxo = max_out_width(a->de, ae_of(*a));
     return generic_lds_bytes(d, ae_of(*a) != nullptr, f.lin) <= 160 * 1024;
@@ -513,6 +515,25 @@ int32_t psnode_dae_integrate_ms_f32(const psnode_dae_args_f32* args, const psnod
                                     const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, const psnode_segments_f32* seg, void* ws,
                                     size_t bytes, void* stream) {
     return k0_integrate(kFamMs, args, {de_act, ae_act, tab, sub, seg}, ws, bytes, stream);
+}
+
+// (segments in parallel: the _ms call over a tiles x chunks grid, chunk c the grp->per_group consecutive segments from c per_group every on)
+int32_t psnode_ode_integrate_msp_supported(const psnode_ode_args_f32* a, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
+                                           const psnode_substeps_f32* sub, const psnode_segment_groups_f32* grp) {
+    return k0_supported(kFamMsp, a, {de_act, nullptr, tab, sub, nullptr, 0, grp});
+}
+int32_t psnode_ode_integrate_msp_f32(const psnode_ode_args_f32* args, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
+                                     const psnode_substeps_f32* sub, const psnode_segment_groups_f32* grp, void* ws, size_t bytes, void* stream) {
+    return k0_integrate(kFamMsp, args, {de_act, nullptr, tab, sub, nullptr, 0, grp}, ws, bytes, stream);
+}
+int32_t psnode_dae_integrate_msp_supported(const psnode_dae_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                           const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, const psnode_segment_groups_f32* grp) {
+    return k0_supported(kFamMsp, a, {de_act, ae_act, tab, sub, nullptr, 0, grp});
+}
+int32_t psnode_dae_integrate_msp_f32(const psnode_dae_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                     const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, const psnode_segment_groups_f32* grp, void* ws,
+                                     size_t bytes, void* stream) {
+    return k0_integrate(kFamMsp, args, {de_act, ae_act, tab, sub, nullptr, 0, grp}, ws, bytes, stream);
 }
 
 int32_t psnode_ode_kernel_for(const psnode_ode_args_f32* a) {

@@ -320,9 +320,12 @@ struct GenericBwdCall {
                                //   the [T-1, B] table.  (BuildLin / BuildPev: with rk, substeps >= 1; BuildPev's `ev` is the [T-1, B] table.)
     int ms_every;              // generic_backward_launch<BuildMs> (with rk; substeps >= 1): grid point k > 0 with
     const float* ms_x_true;    //   k % ms_every == 0 restarted from the dataset row ms_x_true[k] ([T, B, xd]; may be null where T - 1 <= ms_every)
+    int ms_per_group;          // generic_backward_launch<BuildMsp> (BuildMs's call): segments per time chunk of its tiles x chunks grid
 };
 struct ActPair;     // psnode_act.h: the DE's and the AE's activation of a non-ELU(1) call
 size_t generic_bwd_workspace_floats(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, long long B);
+// the segment-parallel build's (gbwd_msp_layout): n = the width of all_initial, nzv = zd + vd (read for a DAE), chunks >= 1
+size_t generic_bwd_msp_workspace_floats(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, long long B, int n, int nzv, long long chunks);
 // K5's mode for these dims, 0 if the shape does not fit: the one fit query of all four builds.  pre: the fit of the builds that keep u in LDS
 // as well -- the pre-activation build and the tableau build, whose LDS layouts are the same
 int generic_bwd_fits(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, int xd, int zd, int vd, int id, bool pre, bool lin = false);      // lin: the linear-externals build's layout
@@ -332,7 +335,8 @@ int generic_bwd_fits(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, int xd,
 // pre-activations like the pre build), BuildSub (the tableau build with c.substeps sub-steps per grid interval, read from c.x_sub), BuildLin
 // (the sub-step build, any c.substeps >= 1, with linearly interpolated externals), BuildPev (the sub-step build, any c.substeps >= 1,
 // with per-trajectory events: c.ev not null), BuildAb (BuildPev's policy as two-step Adams-Bashforth: c.ab_pt), BuildMs (the
-// sub-step build, any c.substeps >= 1, with multiple-shooting restarts: c.ms_every, c.ms_x_true).
+// sub-step build, any c.substeps >= 1, with multiple-shooting restarts: c.ms_every, c.ms_x_true), BuildMsp (BuildMs's call with its
+// segments spread over a tiles x chunks grid: c.ms_per_group).
 // psnode_backward.hip: generic_backward picks among them by the call's BuildId.
 template <class B>
 int generic_backward_launch(const GenericBwdCall& c, const ActPair* act, float* workspace, hipStream_t stream);

@@ -75,6 +75,16 @@
         lds[inDE + qi(xd + r, c)] = v;
     };
 
+    // Segments in parallel (Bd::par): this workgroup runs steps k_lo .. k_hi - 1 alone, the segments of time chunk blockIdx.y.  Chunk 0 starts
+    // as every other build does; a later chunk starts on a restart point, so it writes no row 0, runs no pseudo-step, and its first step finds
+    // z | v of grid point k_lo where a step finds them "from the previous step's final pass".  (0 and a.T - 1 in every other build.)
+    [[maybe_unused]] long long k_lo = 0, k_hi = 0;
+    if constexpr (Bd::par) {
+        const MspChunk ch = msp_chunk(sub, a.T);
+        k_lo = uniform64(ch.k_lo);
+        k_hi = uniform64(ch.k_hi);
+    }
+
     // ---- per-trajectory constants, the constant and pad columns of both inputs, the initial state, z | v of grid point 0
     for (int idx = tid; idx < n * TB; idx += NT) {
         const int r = idx / TB, c = idx % TB;
@@ -93,11 +103,12 @@
         const long long b = gb(c);
         const float v = DAE ? a.x_init[b * xd + r] : a.x.p[b * a.x.sb + r];
         xcur[idx] = v;
+        if constexpr (Bd::par) { if (k_lo > 0) continue; }      // (a later chunk: row 0 is chunk 0's; its first step restarts from a.x[k_lo], its head reads that row)
         if (b0 + c < a.B) a.xo[b * xd + r] = v;
         if constexpr (DAE) lds[inAE + qi(r, c)] = true_x ? a.x.p[b * a.x.sb + r] : v;      // my_solvers.py:95
     }
     for (int idx = tid; idx < nzv * TB; idx += NT) {
-        const float v = zv_at(0, idx / TB, idx % TB);
+        const float v = zv_at(Bd::par ? k_lo : 0, idx / TB, idx % TB);
         zvn[idx] = v;
         if constexpr (DAE) lds[inAE + qi(xd + idx / TB, idx % TB)] = v;
     }
@@ -128,9 +139,16 @@
     }
     // look-ahead registers: clocks (threads < TB), the next step's event index, the next grid point's z | v
     float tc = 0.0f, tn = 0.0f;
+    if constexpr (Bd::par) {      // (k_lo + 1 <= k_hi <= T - 1 where the record has a step; T == 1: k_lo = k_hi = 0)
+        if (tid < TB) {
+            tc = a.t.p[k_lo * a.t.st + gb(tid) * a.t.sb];
+            tn = a.T > 1 ? a.t.p[(k_lo + 1) * a.t.st + gb(tid) * a.t.sb] : tc;
+        }
+    } else {
     if (tid < TB) {
         tc = a.t.p[gb(tid) * a.t.sb];
         tn = a.T > 1 ? a.t.p[a.t.st + gb(tid) * a.t.sb] : tc;
+    }
     }
     // the next step's event index travels through a VECTOR load (every lane the same address): a scalar load would be waited for by the
     // very next LDS wait (SMEM returns out of order, so any lgkmcnt wait is lgkmcnt(0)) -- an L2 round trip at the top of every step
@@ -139,7 +157,7 @@
     // idx = tid + NT j, so a thread only ever touches column tid % TB -- loaded one step ahead like the shared one.  The host refuses a
     // call of this build without a table.
     static_assert(NT % TB == 0 && TB <= 64 && 64 % TB == 0, "a thread owns one trajectory column, and every wave holds all of them");
-    int evn_v = (a.ev && a.T > 1) ? __builtin_nontemporal_load(evp) : -1;
+    int evn_v = (a.ev && a.T > 1) ? __builtin_nontemporal_load(evp + (Bd::par ? k_lo : 0)) : -1;
     if constexpr (Bd::pev && !Bd::ab) evn_v = a.T > 1 ? evp[gb(tid % TB)] : -1;
     // Adams-Bashforth 2 (Bd::ab; one DE stage per step, one sub-step): x_{k+1} = x_k + c0 f_k + c1 f_{k-1} with per-column c0 / c1 from this
     // step's h, the previous one's (hp, a register of the threads < TB that hold the clocks) and the restart bit (k = 0, an event of the
@@ -157,6 +175,7 @@
     // ms_cnt counts the steps since the last restart in a scalar register, so no step pays a 64-bit remainder.
     [[maybe_unused]] int ms_cnt = 0, ms_w = 0;
     if constexpr (Bd::ms) ms_w = __builtin_amdgcn_readfirstlane(ms_every(sub));
+    if constexpr (Bd::par) { if (k_lo > 0) ms_cnt = ms_w; }      // (a later chunk's first step leaves a restart point)
 
     float pz[PF];
     // Linear externals (Bd::lin): stage s of sub-step j reads z | v at theta = (j + c_s) / nsub between the interval's left rows (wl) and the
@@ -167,7 +186,7 @@
     // One MLP call site for every evaluation (the unrolled layer code exists once: it has to stay inside the instruction cache).  Slots of
     // step k: 0 = the AE head at an event (my_solvers.py:110), 1 .. S = the DE stages, S + 1 = the AE head at grid point k + 1
     // (my_solvers.py:95, 121); the pseudo-step k = -1 of the DAE is that last slot alone, for grid point 0.
-    for (long long k = DAE ? -1 : 0; k + 1 < (Bd::sub ? Tn : a.T); ++k) {
+    for (long long k = Bd::par ? ((DAE && k_lo == 0) ? -1 : k_lo) : (DAE ? -1 : 0); Bd::par ? k < k_hi : k + 1 < (Bd::sub ? Tn : a.T); ++k) {
         K0_PROF(5)
         // ev: the event index of this step -- launch-uniform, or (Bd::pev) this thread's column's; any_ev: some trajectory of the workgroup
         // has one (workgroup-uniform: each wave holds every column), which is what decides whether the event slot runs

@@ -1,4 +1,4 @@
-// The build policy of the generic kernels K0 (psnode_generic_impl.h) and K5 (psnode_generic_bwd_impl.h): what separates the nine objects each
+// The build policy of the generic kernels K0 (psnode_generic_impl.h) and K5 (psnode_generic_bwd_impl.h): what separates the ten objects each
 // is compiled into, as constants the language can see.  Each object is one file that names its policy and includes the impl header:
 //   #define PSNODE_BUILD BuildAct
 //   #include "psnode_generic_impl.h"
@@ -43,9 +43,42 @@ template <class S> __host__ __device__ inline int ms_every(const S&) { return 0;
 __host__ __device__ inline int ms_every(const MsDev& s) { return s.every; }
 template <class S> __host__ __device__ inline const float* ms_x_true(const S&) { return nullptr; }
 __host__ __device__ inline const float* ms_x_true(const MsDev& s) { return s.x_true; }
+// What the segment-parallel builds of K0 / K5 take in MsDev's place (psnode_segment_groups_f32, include/psnode_hip.h): the multiple-shooting
+// argument plus `per_group` >= 1 -- workgroup (tile, c = blockIdx.y) runs the steps of the per_group consecutive segments
+// c per_group every .. min((c + 1) per_group every, T - 1) alone -- and, for K5, what crosses a chunk border (folded by the launch behind
+// the sweep; workspace segments, gbwd_msp_layout): ga0_part [C - 1, B, n], the grad_all_initial partial of every chunk c > 0, and border
+// [C - 1, B, zd + vd], the z | v part of the head VJP at grid point k_hi of every chunk c < C - 1 (a DAE's; that row is chunk c + 1's).
+struct MspDev {
+    int n;
+    float* x_sub;
+    int every;
+    const float* x_true;
+    int per_group;
+    float* ga0_part;
+    float* border;
+};
+__host__ __device__ inline int ev_table_pt(const MspDev&) { return 0; }
+__host__ __device__ inline int ms_every(const MspDev& s) { return s.every; }
+__host__ __device__ inline const float* ms_x_true(const MspDev& s) { return s.x_true; }
+// the chunk of the calling workgroup: steps k_lo .. k_hi - 1 of a record of T grid points (k_lo < k_hi <= T - 1: the launcher's grid)
+// (host) the chunks of a record: n_seg = ceil((T - 1) / every) segments in groups of per_group, at least one (a record without a step)
+inline long long msp_chunks(long long T, long long every, long long per_group) {
+    const long long n_seg = T > 1 ? (T - 1 + every - 1) / every : 0, C = (n_seg + per_group - 1) / per_group;
+    return C > 1 ? C : 1;
+}
+struct MspChunk { long long k_lo, k_hi; };
+template <class S> __device__ inline MspChunk msp_chunk(const S&, long long T) { return MspChunk{0, T - 1}; }
+__device__ inline MspChunk msp_chunk(const MspDev& s, long long T) {
+    const long long span = (long long)s.per_group * s.every, lo = (long long)blockIdx.y * span, hi = lo + span;
+    return MspChunk{lo, hi < T - 1 ? hi : T - 1};
+}
+template <class S> __device__ inline float* msp_ga0_part(const S&) { return nullptr; }
+__device__ inline float* msp_ga0_part(const MspDev& s) { return s.ga0_part; }
+template <class S> __device__ inline float* msp_border(const S&) { return nullptr; }
+__device__ inline float* msp_border(const MspDev& s) { return s.border; }
 
 
-template <bool ACT, bool PRE, bool RK, bool SUB = false, bool LIN = false, bool PEV = false, bool AB = false, bool MS = false>
+template <bool ACT, bool PRE, bool RK, bool SUB = false, bool LIN = false, bool PEV = false, bool AB = false, bool MS = false, bool PAR = false>
 struct GenericBuild {
     static constexpr bool act = ACT;      // the hidden-layer activation is a kernel argument (ActPair, psnode_act.h), not ELU(1)
     static constexpr bool pre = PRE;      // the hidden layers' pre-activations u are kept next to h (SiLU / GELU / Mish differentiate from u)
@@ -57,10 +90,12 @@ struct GenericBuild {
                                           // needs pev, whose per-column event index also serves a shared table through a column stride of 0)
     static constexpr bool ms = MS;        // multiple shooting: every MsDev::every-th grid point restarts from the dataset row (MsDev;
                                           // needs sub; not with lin, pev or ab)
+    static constexpr bool par = PAR;      // segments in parallel: the launch grid is tiles x chunks, workgroup (tile, c) runs the segments of time chunk c
+                                          // alone (MspDev; needs ms)
     // The kernels' arguments behind the args struct, each a by-value parameter of its own: ActPair (act) | psnode_rk_tableau_f32 (rk) | Sub (sub).
     // A kernel without one of them names the never-read default of kernel_arg in its place.
     static constexpr int n_extra = SUB ? 3 : (RK ? 2 : (ACT ? 1 : 0));
-    using Sub = std::conditional_t<AB, AbDev, std::conditional_t<MS, MsDev, SubDev>>;
+    using Sub = std::conditional_t<AB, AbDev, std::conditional_t<PAR, MspDev, std::conditional_t<MS, MsDev, SubDev>>>;
     // K5's waves per SIMD: the fully streamed instances (STR 2) that fitted 256 registers keep two workgroups per CU -- every one of the
     // act build, the ELU(1) build's with the accumulators in LDS, none of the builds that keep u
     static constexpr int two_waves(bool gg, int str) { return PRE ? 1 : (str == 2 && (ACT || !gg) ? 2 : 1); }
@@ -90,8 +125,10 @@ __host__ __device__ constexpr decltype(auto) kernel_arg(const D& dflt, const E0&
 }
 // The policy's Sub argument from what a call carries, for both directions (K0 writes x_sub and has no x_true; K5 reads both)
 template <class B>
-typename B::Sub build_sub(int n, float* x_sub, int ev_pt, int ms_every, const float* x_true) {
+typename B::Sub build_sub(int n, float* x_sub, int ev_pt, int ms_every, const float* x_true, int per_group = 1, float* ga0_part = nullptr,
+                          float* border = nullptr) {
     if constexpr (B::ab) return AbDev{1, nullptr, ev_pt};
+    else if constexpr (B::par) return MspDev{n, x_sub, ms_every, x_true, per_group, ga0_part, border};
     else if constexpr (B::ms) return MsDev{n, x_sub, ms_every, x_true};
     else return SubDev{n, x_sub};
 }
@@ -105,6 +142,7 @@ using BuildLin = GenericBuild<true, true, true, true, true>;      // BuildSub's 
 using BuildPev = GenericBuild<true, true, true, true, false, true>;      // BuildSub's policy with per-trajectory events; every substeps >= 1
 using BuildAb = GenericBuild<true, true, true, true, false, true, true>;      // BuildPev's policy as Adams-Bashforth 2; one sub-step, a one-stage tableau
 using BuildMs = GenericBuild<true, true, true, true, false, false, false, true>;      // BuildSub's policy with multiple-shooting restarts; every substeps >= 1
-enum BuildId { kBuildElu1, kBuildAct, kBuildPre, kBuildRk, kBuildSub, kBuildLin, kBuildPev, kBuildAb, kBuildMs };      // what a call names its build with
+using BuildMsp = GenericBuild<true, true, true, true, false, false, false, true, true>;      // BuildMs's policy with the segments spread over workgroups: a tiles x chunks grid
+enum BuildId { kBuildElu1, kBuildAct, kBuildPre, kBuildRk, kBuildSub, kBuildLin, kBuildPev, kBuildAb, kBuildMs, kBuildMsp };      // what a call names its build with
 
 }  // namespace psnode

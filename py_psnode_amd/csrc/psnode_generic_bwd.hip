@@ -14,6 +14,15 @@ size_t generic_bwd_workspace_floats(const psnode_mlp_f32* de, const psnode_mlp_f
     return gbwd_layout(*de, ae, B, a, A), A.floats();
 }
 
+size_t generic_bwd_msp_workspace_floats(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, long long B, int n, int nzv, long long chunks) {
+    GBwd a;
+    memset(&a, 0, sizeof(a));
+    fill_gmlp(*de, a.de);
+    if (ae) fill_gmlp(*ae, a.ae);
+    Arena A;
+    return gbwd_msp_layout(*de, ae, B, n, nzv, (size_t)chunks, a, A), A.floats();
+}
+
 // (the pre fields, which this object's GBwd does not have, are written by a launch only: the fit reads none of them)
 int generic_bwd_fits(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, int xd, int zd, int vd, int id, bool pre, bool lin) {
     GBwd a;

@@ -6,6 +6,18 @@
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x;
     const long long b0 = (long long)blockIdx.x * TB;
+    // Segments in parallel (Bd::par): this workgroup sweeps steps k_hi - 1 .. k_lo alone, the segments of time chunk blockIdx.y; wg is its slice
+    // of the per-workgroup partials (tiles x chunks of them).  The sweep of a chunk c > 0 ends on the restart step at k_lo, behind which the
+    // sequential sweep carries nothing but grad_xs[k_lo] / grad_is[k_lo] -- what chunk c - 1 reads for itself.
+    [[maybe_unused]] long long k_lo = 0, k_hi = 0;
+    [[maybe_unused]] bool last_chunk = true;
+    if constexpr (Bd::par) {
+        const MspChunk ch = msp_chunk(sub, a.T);
+        k_lo = ch.k_lo;
+        k_hi = ch.k_hi;
+        last_chunk = blockIdx.y + 1 == gridDim.y;
+    }
+    [[maybe_unused]] const size_t wg = Bd::par ? (size_t)blockIdx.y * gridDim.x + blockIdx.x : (size_t)blockIdx.x;
     const bool dae = a.dae != 0;
     const int xd = a.xd, zd = a.zd, vd = dae ? a.vd : 0, id = dae ? a.id : 0;
     const int nzv = zd + vd, ne = nzv + id, n = xd + ne;
@@ -43,7 +55,7 @@
     float* wbuf = dts + TP + (Bd::lin ? 3 * nzv * TP : 0);        // [kWBuf] staged weights
     // [np_de + np_ae]: in LDS when it fits, else this workgroup's partial slice in global memory (each element is owned by
     // one thread either way, so the read-modify-write needs no atomics)
-    float* gacc_g = a.wpart + (size_t)blockIdx.x * (a.de.np + (a.dae ? a.ae.np : 0));      // (used when gg)
+    float* gacc_g = a.wpart + (Bd::par ? wg : (size_t)blockIdx.x) * (a.de.np + (a.dae ? a.ae.np : 0));      // (used when gg)
     const bool stages = (!REG && STR != 2) || (a.dae && STR == 0);      // some MLP still stages its weights through LDS
     float* gacc_l = wbuf + (stages ? kWBuf : 0);
     // register path of the DE: quad-row buffers behind the accumulators, the wave's MFMA operands of both passes in VGPRs
@@ -69,7 +81,7 @@
     }
     for (int e = tid; e < np_all; e += NT) gacc_l[e] = 0.0f;
     // global accumulators: tile-major slices (tmpart) for the MLPs off the staged path, the natural partial slice itself for a staged one
-    float* tmg = a.tmpart + (size_t)blockIdx.x * (tm_total(a.de) + (a.dae ? tm_total(a.ae) : 0));
+    float* tmg = a.tmpart + (Bd::par ? wg : (size_t)blockIdx.x) * (tm_total(a.de) + (a.dae ? tm_total(a.ae) : 0));
     float* tmgA = tmg + tm_total(a.de);
     if constexpr (gg) {
         if constexpr (DE_TM) { for (int e = tid; e < tm_total(a.de); e += NT) tmg[e] = 0.0f; }
@@ -82,10 +94,12 @@
         }
     }
     TILE_LOOP(n) { a0s[r * TP + c] = a.a0[gb(c) * n + r]; ga0s[r * TP + c] = 0.0f; }
-    TILE_LOOP(xd) gxc[r * TP + c] = on(c) ? a.gxs[((a.T - 1) * a.B + gb(c)) * xd + r] : 0.0f;
-    TILE_LOOP(id) gic[r * TP + c] = (on(c) && a.gis) ? a.gis[((a.T - 1) * a.B + gb(c)) * id + r] : 0.0f;
+    // (Bd::par: the chunk's last grid point k_hi -- T - 1, or the restart point behind which the sequential sweep holds these two rows alone)
+    TILE_LOOP(xd) gxc[r * TP + c] = on(c) ? a.gxs[((Bd::par ? k_hi : a.T - 1) * a.B + gb(c)) * xd + r] : 0.0f;
+    TILE_LOOP(id) gic[r * TP + c] = (on(c) && a.gis) ? a.gis[((Bd::par ? k_hi : a.T - 1) * a.B + gb(c)) * id + r] : 0.0f;
     TILE_LOOP(nzv) {   // the last grid point's z|v only receive the AE part (DAE) or nothing (ODE)
         if (!on(c)) continue;
+        if constexpr (Bd::par) { if (!last_chunk) continue; }      // (row k_hi of another chunk is chunk c + 1's, written in its step (4))
         const bool isz = r < zd;
         float* dst = isz ? a.gz : a.gv;
         if (dst) dst[((a.T - 1) * a.B + b0 + c) * (isz ? zd : vd) + (isz ? r : r - zd)] = 0.0f;
@@ -144,6 +158,12 @@
                 }
             }
             if constexpr (Bd::pev) { if (jzv < 0 && ev < 0) continue; }      // (the event-time head of a column without a hit: no jump row is its)
+            if constexpr (Bd::par) {
+                // the head at the chunk's last grid point: row k_hi is chunk c + 1's, which writes it with `=` -- the share goes to this
+                // chunk's border slot, and the fold behind the sweep adds it onto the row (the sequential order: step k_hi's value, the
+                // restart head's, then this one)
+                if (jzv == k_hi && !last_chunk) { msp_border(sub)[((size_t)blockIdx.y * a.B + b0 + c) * nzv + r] = g; continue; }
+            }
             if (jzv >= 0) {
                 float* dst = isz ? a.gz : a.gv;
                 if (dst) dst[(jzv * a.B + b0 + c) * w_ + d_] += g;
@@ -181,9 +201,16 @@
         const unsigned long long u = (unsigned long long)a.T;
         Tu = (long long)(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(u >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)u));
     }
+    if constexpr (Bd::par) {
+        if (k_hi > k_lo) {
+            if (tid < TB) la_tn = a.t.p[k_hi * a.t.st + gb(tid) * a.t.sb];
+            look_ahead(k_hi - 1);
+        }
+    } else {
     if ((Bd::ab ? Tu : a.T) >= 2) {
         if (tid < TB) la_tn = a.t.p[(a.T - 1) * a.t.st + gb(tid) * a.t.sb];
         look_ahead(a.T - 2);
+    }
     }
     // Adams-Bashforth 2 (Bd::ab; one stage, one sub-step): the DE's VJP of step k takes phi_k = c0_k g_{k+1} + c1_{k+1} g_{k+2}.  gxc is
     // g_{k+1}; g_{k+2} is kept in gks' slot 1 and the per-column c1_{k+1} in its slot 2 (a one-stage build uses slot 0 alone); c0_k takes h's
@@ -204,10 +231,12 @@
     [[maybe_unused]] const float* __restrict__ xtr = nullptr;
     if constexpr (Bd::ms) {
         ms_w = __builtin_amdgcn_readfirstlane(ms_every(sub));
+        if constexpr (Bd::par) ms_rem = __builtin_amdgcn_readfirstlane((k_hi > k_lo && ms_w > 0) ? (int)((k_hi - 1) % ms_w) : 0);
+        else
         ms_rem = __builtin_amdgcn_readfirstlane((a.T >= 2 && ms_w > 0) ? (int)((a.T - 2) % ms_w) : 0);
         xtr = ms_x_true(sub);
     }
-    for (long long k = (Bd::ab ? Tu : a.T) - 2; k >= 0; --k) {
+    for (long long k = Bd::par ? k_hi - 1 : (Bd::ab ? Tu : a.T) - 2; k >= (Bd::par ? k_lo : 0); --k) {
         // ev: the event index of this step -- launch-uniform, or (Bd::pev: a [T - 1][B] table, which the host requires) that of this
         // thread's column: every TILE_LOOP and look-ahead item of a thread lies in column tid % TB.  any_ev: some column of the workgroup
         // has a hit (workgroup-uniform: each wave holds every column) -- what decides whether the event-time head is evaluated at all.
@@ -494,14 +523,24 @@
         __syncthreads();
         } while (si.more());
     }
-    if (dae) {   // i_0 = g(x_0; z[0], v[0])   (my_solvers.py:95)
+    if (dae && !(Bd::par && k_lo > 0)) {   // i_0 = g(x_0; z[0], v[0])   (my_solvers.py:95)
         TILE_LOOP(xd) x0[r * TP + c] = xsrc[gb(c) * xd + r];
         __syncthreads();
         ae_vjp(x0, 0, -1, gic, tx ? gx0 : gxc);
     }
+    if constexpr (Bd::par) {      // chunk 0 alone reaches grid point 0; a later chunk leaves its grad_all_initial partial for the fold
+        if (k_lo > 0) {
+            float* gp = msp_ga0_part(sub) + (size_t)(blockIdx.y - 1) * a.B * n;
+            TILE_LOOP(n) if (on(c)) gp[(b0 + c) * n + r] = ga0s[r * TP + c];
+        } else {
+            TILE_LOOP(xd) if (on(c)) a.gx0[(b0 + c) * xd + r] = gxc[r * TP + c];
+            TILE_LOOP(n) if (on(c)) a.ga0[(b0 + c) * n + r] = ga0s[r * TP + c];
+        }
+    } else {
     TILE_LOOP(xd) if (on(c)) a.gx0[(b0 + c) * xd + r] = gxc[r * TP + c];
     TILE_LOOP(n) if (on(c)) a.ga0[(b0 + c) * n + r] = ga0s[r * TP + c];
-    float* wp = a.wpart + (size_t)blockIdx.x * (a.de.np + (dae ? a.ae.np : 0));
+    }
+    float* wp = a.wpart + (Bd::par ? wg : (size_t)blockIdx.x) * (a.de.np + (dae ? a.ae.np : 0));
     // the LDS accumulators -> this workgroup's partial in nn.Linear order (tile-major ones un-permuted)
     // (volatile: the global tile-major slices were written by other lanes of this workgroup; read them past the vector L1)
     auto unpermute = [&](const GMlp& m, const volatile float* base, float* dst) {

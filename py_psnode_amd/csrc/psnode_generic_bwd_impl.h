@@ -695,8 +695,9 @@ bool de_reg_class(const psnode_mlp_f32& de) {
 // workgroup (tm_total of both MLPs: the paths with global accumulators).  `a` (filled: fill_gmlp) gets the segments it carries.
 struct GBwdLayout { float *img[2][kMaxLayers], *imgT[2][kMaxLayers]; };
 inline size_t up64(size_t v) { return (v + 63) / 64 * 64; }
-GBwdLayout gbwd_layout(const psnode_mlp_f32& de, const psnode_mlp_f32* ae, long long B, GBwd& a, Arena& A) {
-    const size_t nwg = (size_t)((B + TB - 1) / TB);
+// (chunks: 1, or the time chunks of the segment-parallel build -- one partial and one slice per workgroup of its tiles x chunks grid)
+GBwdLayout gbwd_layout(const psnode_mlp_f32& de, const psnode_mlp_f32* ae, long long B, GBwd& a, Arena& A, size_t chunks = 1) {
+    const size_t nwg = (size_t)((B + TB - 1) / TB) * chunks;
     const psnode_mlp_f32* mlp[2] = {&de, ae};
     GMlp* g[2] = {&a.de, &a.ae};
     GBwdLayout L{};
@@ -717,6 +718,38 @@ GBwdLayout gbwd_layout(const psnode_mlp_f32& de, const psnode_mlp_f32* ae, long 
     A.slack((ae ? 4 : 3) * 64 - tm_pad);
     return L;
 }
+// The segment-parallel build's workspace: gbwd_layout with one partial per workgroup of the tiles x chunks grid | the grad_all_initial
+// partials of the chunks c > 0, [chunks - 1][B][n] | (DAE) the border slots of the chunks c < chunks - 1, [chunks - 1][B][zd + vd]: the
+// z | v part of the head VJP at the chunk's last grid point, which is the next chunk's row (msp_fold_kernel adds both where they belong).
+struct GBwdMspLayout { GBwdLayout base; float *ga0_part, *border; };
+GBwdMspLayout gbwd_msp_layout(const psnode_mlp_f32& de, const psnode_mlp_f32* ae, long long B, int n, int nzv, size_t chunks, GBwd& a, Arena& A) {
+    GBwdMspLayout L{};
+    L.base = gbwd_layout(de, ae, B, a, A, chunks);
+    L.ga0_part = A.take((chunks - 1) * (size_t)B * n);
+    L.border = A.take(ae ? (chunks - 1) * (size_t)B * nzv : 0);
+    return L;
+}
+// Behind the sweep of the segment-parallel build, on its stream: grad_all_initial (chunk 0's) += the partials of chunks 1 .. chunks - 1 in
+// ascending order, and row (c + 1) span of grad_z / grad_v += chunk c's border slot (span = per_group every grid steps per chunk).  One
+// thread per element, each the only writer of its element: bitwise repeatable.  (B_ = the policy: instantiated in its object alone.)
+template <class B_>
+__global__ void msp_fold_kernel(float* __restrict__ ga0, const float* __restrict__ ga0_part, float* __restrict__ gz, float* __restrict__ gv,
+                                const float* __restrict__ border, long long B, int n, int zd, int vd, long long span, int chunks) {
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x, n_a0 = B * n, nzv = zd + vd;
+    if (e < n_a0) {
+        float acc = ga0[e];
+        for (int c = 1; c < chunks; ++c) acc += ga0_part[(size_t)(c - 1) * n_a0 + e];
+        ga0[e] = acc;
+        return;
+    }
+    if (!border || e >= n_a0 + (long long)(chunks - 1) * B * nzv) return;
+    const long long q = e - n_a0, c = q / (B * nzv), b = (q / nzv) % B;
+    const int r = (int)(q % nzv);
+    const bool isz = r < zd;
+    float* dst = isz ? gz : gv;
+    if (dst) dst[((c + 1) * span * B + b) * (isz ? zd : vd) + (isz ? r : r - zd)] += border[q];
+}
+
 // 1: everything in LDS; 2: only with the parameter-gradient accumulators in global memory; 0: does not fit.  a.de_reg (the DE's class
 // allows the register path) is kept when its quad-row buffers fit next to the LDS accumulators, else dropped.
 int gbwd_mode(GBwd& a, bool pre, bool lin = false) {
@@ -781,7 +814,17 @@ int generic_backward_launch(const GenericBwdCall& c, const ActPair* act, float* 
     a.flags = c.flags; a.xt = dae ? c.xt : c.xs; a.it = c.it;
     a.de_reg = de_reg_class(*de) ? 1 : 0;
     Arena A{workspace};
-    const GBwdLayout L = gbwd_layout(*de, ae, B, a, A);
+    // (the segment-parallel build: a tiles x chunks grid, one partial per workgroup and what crosses a chunk border behind them)
+    [[maybe_unused]] unsigned chunks = 1;
+    [[maybe_unused]] float *ga0_part = nullptr, *border = nullptr;
+    GBwdLayout L;
+    if constexpr (Pol::par) {
+        chunks = (unsigned)msp_chunks(c.T, c.ms_every, c.ms_per_group);
+        const GBwdMspLayout M = gbwd_msp_layout(*de, ae, B, n, c.zd + (dae ? c.vd : 0), chunks, a, A);
+        L = M.base; ga0_part = M.ga0_part; border = M.border;
+    } else {
+        L = gbwd_layout(*de, ae, B, a, A);
+    }
     for (int l = 0; l < kMaxLayers; ++l) { a.fimg[l] = L.img[0][l]; a.timg[l] = L.imgT[0][l]; a.fimgA[l] = L.img[1][l]; a.timgA[l] = L.imgT[1][l]; }
     if (!gbwd_mode(a, Pol::pre, Pol::lin)) return PSNODE_ERR_UNSUPPORTED;
     const size_t lds = gbwd_lds_floats(a, Pol::pre, Pol::lin) * sizeof(float);
@@ -809,15 +852,25 @@ int generic_backward_launch(const GenericBwdCall& c, const ActPair* act, float* 
         else if (a.de_reg) kern = g == 1 ? K::template get<true, true, true, 0>() : (g == 2 ? K::template get<false, true, true, 0>() : K::template get<false, true, false, 0>());
         else if (a.str == 2) kern = g == 1 ? K::template get<true, false, true, 2>() : (g == 2 ? K::template get<false, false, true, 2>() : K::template get<false, false, false, 2>());
         else kern = g ? K::template get<true, false, true, 0>() : K::template get<false, false, false, 0>();
-        return launch_attr(true, kern, dim3(nwg), dim3(NT), lds, stream, a, extra...);
+        return launch_attr(true, kern, dim3(nwg, Pol::par ? chunks : 1u), dim3(NT), lds, stream, a, extra...);
     };
     hipError_t e;
-    if constexpr (Pol::sub) e = go(*act, *c.rk, build_sub<Pol>(c.substeps, const_cast<float*>(c.x_sub), c.ab_pt ? 1 : 0, c.ms_every, c.ms_x_true));
+    if constexpr (Pol::par) e = go(*act, *c.rk, build_sub<Pol>(c.substeps, const_cast<float*>(c.x_sub), 0, c.ms_every, c.ms_x_true, c.ms_per_group, ga0_part, border));
+    else if constexpr (Pol::sub) e = go(*act, *c.rk, build_sub<Pol>(c.substeps, const_cast<float*>(c.x_sub), c.ab_pt ? 1 : 0, c.ms_every, c.ms_x_true));
     else if constexpr (Pol::rk) e = go(*act, *c.rk);
     else if constexpr (Pol::act) e = go(*act);
     else e = go();
     if (e != hipSuccess) return PSNODE_ERR_HIP;
-    return ok_or_hip(launch_reduce_partials(a.wpart, c.gparams_de, c.gparams_ae, a.de.np, dae ? a.ae.np : 0, (int)nwg, stream));
+    if constexpr (Pol::par) {
+        if (chunks > 1) {
+            const int nzv = c.zd + (dae ? c.vd : 0);
+            const long long items = B * n + (dae ? (long long)(chunks - 1) * B * nzv : 0);
+            hipLaunchKernelGGL(msp_fold_kernel<Pol>, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, stream, c.ga0, ga0_part, c.gz, c.gv,
+                               dae ? border : nullptr, B, n, c.zd, dae ? c.vd : 0, (long long)c.ms_per_group * c.ms_every, (int)chunks);
+            if (hipGetLastError() != hipSuccess) return PSNODE_ERR_HIP;
+        }
+    }
+    return ok_or_hip(launch_reduce_partials(a.wpart, c.gparams_de, c.gparams_ae, a.de.np, dae ? a.ae.np : 0, (int)(nwg * (Pol::par ? chunks : 1u)), stream));
 }
 template int generic_backward_launch<Bd>(const GenericBwdCall&, const ActPair*, float*, hipStream_t);
 

@@ -4,11 +4,13 @@
 //
 // Order of checks = order of the statuses of a call that is wrong in several ways (py_psnode_amd/_lib.py maps statuses to exception types).
 // Every family runs this one sequence; a step in brackets exists where the family's row says so, [K0] / [K5] in that direction alone:
-//   [segments struct: NULL PSNODE_ERR_NULL, every < 1 PSNODE_ERR_DIMS] | [sub-steps struct; substeps == 1 on _sub -> the _rk family (tableau
+//   [segments struct: NULL PSNODE_ERR_NULL, every < 1 (_msp: or per_group < 1) PSNODE_ERR_DIMS] | [sub-steps struct; substeps == 1 on _sub -> the _rk family (tableau
 //   given) or the _act family] | act pair | [ELU(1) pair -> the plain entry point] | [the required tableau] | NULL args | [the tableau: given,
 //   or the args' method as one; K5, no tableau: the method] | [K5] T, B | route | [K0] fill_* (method, dims, pointers), then [event_idx] |
 //   [K5] pointers, among them [x_sub where substeps > 1 and T >= 2], [event_idx], [x_true where a step restarts: T - 1 > every] |
 //   workspace | [K0, in dispatch] T, B, LDS fit of the build.
+//   _msp: the _ms family's sequence with psnode_segment_groups_f32 in the segments struct's place; more than 65535 chunks (the grid's second
+//   dimension) are PSNODE_ERR_UNSUPPORTED with the route; [K5] its workspace is its own layout's (gbwd_msp_layout).
 //   _tf [K5; K0 has no such wrapper]: flags == 0 is the plain entry point, in front of all of it.  _rk and _ab do not read `method` (K0's copy
 //   of the args carries EULER); _pev's event_idx is the [T-1, B] table (event-less calls take the other families), _ab's may be NULL.
 //   [K0] route (k0_route_ok): kernel AUTO / GENERIC and no training side outputs -- the _act family looks at save_act alone (a lone
@@ -28,7 +30,7 @@
 
 namespace psnode {
 
-enum Family { kFamTf, kFamAct, kFamRk, kFamSub, kFamLin, kFamPev, kFamAb, kFamMs };
+enum Family { kFamTf, kFamAct, kFamRk, kFamSub, kFamLin, kFamPev, kFamAb, kFamMs, kFamMsp };
 // the tableau: no argument, `method` is read | NULL is PSNODE_ERR_NULL | NULL is the args' method as one | no argument, always one stage
 enum Tab { kTabNone, kTabRequired, kTabOrMethod, kTabOneStage };
 // the sub-steps struct: no argument | NULL is PSNODE_ERR_NULL | NULL is one sub-step
@@ -43,9 +45,10 @@ struct FamilyRow {
     bool no_tf;             // refuses every teacher-forcing flag
     bool saved_all;         // refuses every saved_* row / side output; false: the _act family's own rule, which differs by direction
     bool pre, lin;          // the LDS fit of its build: the pre-activations kept (K5; kBuildPre's too), the linear-externals layout
+    bool par;               // the segments struct is psnode_segment_groups_f32: the grid is tiles x chunks, K5's workspace its own layout
 };
 constexpr FamilyRow kFamilies[] = {
-    //          build       elu1   tableau       sub-steps     demotes seg    events no_tf  saved  pre    lin
+    //          build       elu1   tableau       sub-steps     demotes seg    events no_tf  saved  pre    lin    par
     /* _tf  */ {kBuildElu1, false, kTabNone,     kSubNone,     false,  false, false, false, true,  false, false},
     /* _act */ {kBuildAct,  true,  kTabNone,     kSubNone,     false,  false, false, false, false, false, false},
     /* _rk  */ {kBuildRk,   false, kTabRequired, kSubNone,     false,  false, false, false, true,  true,  false},
@@ -54,6 +57,7 @@ constexpr FamilyRow kFamilies[] = {
     /* _pev */ {kBuildPev,  false, kTabOrMethod, kSubOrOne,    false,  false, true,  false, true,  true,  false},
     /* _ab  */ {kBuildAb,   false, kTabOneStage, kSubNone,     false,  false, false, true,  true,  true,  false},      // (a multistep history has no teacher-forced form)
     /* _ms  */ {kBuildMs,   false, kTabOrMethod, kSubOrOne,    false,  true,  false, true,  true,  true,  false},      // (every teacher-forced step restarts already)
+    /* _msp */ {kBuildMsp,  false, kTabOrMethod, kSubOrOne,    false,  true,  false, true,  true,  true,  false, true},      // (_ms over a tiles x chunks grid)
 };
 struct CallOpts {      // what a call carries behind its args; a family's wrappers leave what it does not take at NULL / 0
     const psnode_act_f32 *de_act, *ae_act;
@@ -61,11 +65,21 @@ struct CallOpts {      // what a call carries behind its args; a family's wrappe
     const psnode_substeps_f32* sub;
     const psnode_segments_f32* seg;
     int per_trajectory;      // _ab: a non-NULL event_idx is the [T-1, B] table (else the shared [T-1])
+    const psnode_segment_groups_f32* grp;      // _msp: in seg's place
+    // what a family with segments reads, from whichever of the two structs it takes
+    bool has_seg() const { return seg || grp; }
+    int every() const { return grp ? grp->every : seg->every; }
+    const float* x_true() const { return grp ? grp->x_true : seg->x_true; }
+    int per_group() const { return grp ? grp->per_group : 1; }
 };
+// the time chunks of a segment-parallel call (1 for every other family)
+inline long long family_chunks(const FamilyRow& f, const CallOpts& o, long long T) { return f.par ? msp_chunks(T, o.every(), o.per_group()) : 1; }
+constexpr long long kMaxChunks = 65535;      // (the launch grid's second dimension)
 // The front of every call and query (which answers 0 for every status): segments | sub-steps, where substeps == 1 demotes `fam` | act pair
 inline int family_front(Family& fam, const CallOpts& o, ActPair& p, bool& elu1) {
     const FamilyRow& f = kFamilies[fam];
-    if (f.seg && (!o.seg || o.seg->every < 1)) return !o.seg ? PSNODE_ERR_NULL : PSNODE_ERR_DIMS;
+    if (f.seg && (f.par ? !o.grp : !o.seg)) return PSNODE_ERR_NULL;
+    if (f.seg && (o.every() < 1 || o.per_group() < 1)) return PSNODE_ERR_DIMS;
     if (f.sub == kSubRequired || (f.sub == kSubOrOne && o.sub)) {
         const int rc = substeps_check(o.sub);
         if (rc) return rc;

@@ -563,7 +563,7 @@ template <class B, class... Extra> struct GenericKernels {
 
 // plans, sets the dynamic-LDS limit and launches the instance of policy B for this call; extra: the kernel's arguments behind `a`
 template <class B, class... Extra>
-hipError_t launch_generic_build(const IntegrateDev& a_in, bool dae, hipStream_t stream_, const Extra&... extra) {
+hipError_t launch_generic_build(const IntegrateDev& a_in, bool dae, unsigned chunks, hipStream_t stream_, const Extra&... extra) {
     using K = GenericKernels<B, Extra...>;
     IntegrateDev a = a_in;
     const size_t lds = generic_plan(a, dae, a.k0_res, B::lin);
@@ -575,8 +575,9 @@ hipError_t launch_generic_build(const IntegrateDev& a_in, bool dae, hipStream_t 
     // (two waves per SIMD sharing the MFMA pipe) while other CUs stay empty.
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
-    const size_t lds_launch = (grid <= (unsigned)cus && lds < 81 * 1024) ? 81 * 1024 : lds;
-    auto go = [&](auto kern) { return launch_attr(true, kern, dim3(grid), dim3(NT), lds_launch, stream_, a, extra...); };
+    // (chunks: 1, or the time chunks of the segment-parallel build -- the grid's second dimension; the workgroups of all of them share the CUs)
+    const size_t lds_launch = ((unsigned long long)grid * chunks <= (unsigned long long)cus && lds < 81 * 1024) ? 81 * 1024 : lds;
+    auto go = [&](auto kern) { return launch_attr(true, kern, dim3(grid, chunks), dim3(NT), lds_launch, stream_, a, extra...); };
     const int qm = generic_reg_mode(a, dae);
     const bool deep = a.de.n_layers > 4 || (dae && a.ae.n_layers > 4);      // the layer loop is unrolled 4 or kMaxLayers times
     if (qm && deep) return qm == 4 ? go(K::template get<false, 0, kMaxLayers, 4>()) : go(K::template get<false, 0, kMaxLayers, 8>());
@@ -593,11 +594,14 @@ hipError_t launch_generic_build(const IntegrateDev& a_in, bool dae, hipStream_t 
 
 template <class B>
 hipError_t launch_generic(const IntegrateDev& a, bool dae, const K0Call& call, hipStream_t stream) {
-    if constexpr (B::sub) {
-        return launch_generic_build<B>(a, dae, stream, call.act, call.rk, build_sub<B>(call.sub.n, call.sub.x_sub, call.ev_pt, call.ms_every, nullptr));
-    } else if constexpr (B::rk) return launch_generic_build<B>(a, dae, stream, call.act, call.rk);
-    else if constexpr (B::act) return launch_generic_build<B>(a, dae, stream, call.act);
-    else return launch_generic_build<B>(a, dae, stream);
+    if constexpr (B::par) {
+        return launch_generic_build<B>(a, dae, (unsigned)msp_chunks(a.T, call.ms_every, call.per_group), stream, call.act, call.rk,
+                                       build_sub<B>(call.sub.n, call.sub.x_sub, call.ev_pt, call.ms_every, nullptr, call.per_group));
+    } else if constexpr (B::sub) {
+        return launch_generic_build<B>(a, dae, 1u, stream, call.act, call.rk, build_sub<B>(call.sub.n, call.sub.x_sub, call.ev_pt, call.ms_every, nullptr));
+    } else if constexpr (B::rk) return launch_generic_build<B>(a, dae, 1u, stream, call.act, call.rk);
+    else if constexpr (B::act) return launch_generic_build<B>(a, dae, 1u, stream, call.act);
+    else return launch_generic_build<B>(a, dae, 1u, stream);
 }
 template hipError_t launch_generic<Bd>(const IntegrateDev&, bool, const K0Call&, hipStream_t);
 

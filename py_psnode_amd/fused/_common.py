@@ -199,8 +199,9 @@ def _act_ptrs(acts):
 # What the entry points psnode_<stem>_<family>_* take behind the args struct, in this order: one psnode_act_f32 per MLP (acts), the tableau (tab),
 # the sub-steps struct (sub), the segments struct (seg) and -- the _f32 call alone -- the per_trajectory int (pt).  tf_args: its dae_backward takes
 # psnode_dae_bwd_tf_args_f32; x_sub: a forward call that saves for K5 keeps sub-state rows; workspace: the query that sizes its dae_backward -- "plain",
-# its "own", or the "rk" family's (the same policy, so the same fit, checks and layout for any sub-steps).
-Family = collections.namedtuple("Family", "acts tab sub seg pt tf_args x_sub workspace", defaults=(True, False, False, False, False, True, False, "own"))
+# its "own", or the "rk" family's (the same policy, so the same fit, checks and layout for any sub-steps).  par: the segments struct is
+# psnode_segment_groups_f32, and both backward stems size their workspace with the family's own psnode_<stem>_<family>_workspace_size.
+Family = collections.namedtuple("Family", "acts tab sub seg pt tf_args x_sub workspace par", defaults=(True, False, False, False, False, True, False, "own", False))
 # The Python counterpart of kFamilies (csrc/psnode_generic_family.h): `GenericOpts`, `call_generic` and the prototypes of _lib.load read it.
 # "plain": the entry points without a family in their name; "none": no entry point at all; "tf": the "plain" dae_backward with dataset rows.
 FAMILIES = {
@@ -214,7 +215,53 @@ FAMILIES = {
     "pev": Family(tab=True, sub=True, x_sub=True, workspace="rk"),
     "ab": Family(pt=True, x_sub=True, workspace="rk"),
     "ms": Family(tab=True, sub=True, seg=True, x_sub=True, workspace="rk"),
+    "msp": Family(tab=True, sub=True, seg=True, x_sub=True, workspace="own", par=True),
 }
+
+MAX_CHUNKS = 65535      # the launch grid's second dimension (csrc/psnode_generic_family.h: kMaxChunks)
+
+
+def check_segment_parallel(segment_parallel, segment):
+    """The value rules of `segment_parallel`: None, "auto" or an int g >= 1 (no bool); anything but None needs `segment`.  ValueError."""
+    if segment_parallel is None:
+        return
+    if segment_parallel != "auto" and (isinstance(segment_parallel, bool) or not isinstance(segment_parallel, int) or segment_parallel < 1):
+        raise ValueError(f"segment_parallel must be None, 'auto' or an int >= 1, got {segment_parallel!r}")
+    if segment is None:
+        raise ValueError(f"segment_parallel={segment_parallel!r} spreads the segments of segment= over workgroups: it needs segment (got None)")
+
+
+def segment_chunks(T: int, segment: int, groups: int):
+    """(per_group, [(k_lo, k_hi), ...]): the time chunks of a record of T grid points with a restart every `segment` steps when `groups`
+    chunks are wanted -- n_seg = ceil((T - 1) / segment) segments, per_group = ceil(n_seg / min(groups, n_seg)) consecutive ones per chunk,
+    chunk c the steps c per_group segment .. min((c + 1) per_group segment, T - 1) - 1.  A record without a step: (1, [])."""
+    n_seg = -(-(T - 1) // segment) if T > 1 else 0
+    if n_seg == 0:
+        return 1, []
+    per_group = -(-n_seg // min(groups, n_seg))
+    span = per_group * segment
+    return per_group, [(c * span, min((c + 1) * span, T - 1)) for c in range(-(-n_seg // per_group))]
+
+
+def auto_segment_groups(B: int, cus: int) -> int:
+    """The chunks segment_parallel="auto" asks for: as many as leave every CU at most one workgroup, max(1, CUs // tiles) with
+    tiles = ceil(B / 16).  ("Segments in parallel on K0 / K5": what the measurements say of it.)"""
+    return max(1, cus // max(1, -(-B // 16)))
+
+
+def resolve_segment_parallel(segment_parallel, segment, T: int, B: int, dev=None, cus: Optional[int] = None) -> Optional[int]:
+    """What a call with `segment_parallel` hands GenericOpts: the segments per chunk (`per_group`) where the record splits into more than
+    one chunk, else None -- one chunk is the family "ms" unchanged.  "auto": `auto_segment_groups` from the device's multiprocessor count
+    (`cus`, or read from `dev`).  An int the call got back from `GenericOpts.chunks` resolves to the same per_group again."""
+    check_segment_parallel(segment_parallel, segment)
+    if segment_parallel is None:
+        return None
+    if segment_parallel == "auto":
+        if cus is None:
+            cus = torch.cuda.get_device_properties(dev).multi_processor_count
+        segment_parallel = auto_segment_groups(B, cus)
+    per_group, chunks = segment_chunks(T, segment, min(segment_parallel, MAX_CHUNKS))
+    return per_group if len(chunks) > 1 else None
 
 
 @dataclasses.dataclass(frozen=True)
@@ -228,7 +275,9 @@ class GenericOpts:
     Adams-Bashforth ("ab2") -- the last option in the naming order; never together with a Tableau, sub-steps or interpolated
     externals (the solver's constructor refuses them; here a ValueError), with per_trajectory it stays the family "ab"; segment: None, or
     an int w >= 1 -- multiple shooting, grid point k > 0 with k % w == 0 restarts from the dataset row (the family "ms", the sixth option in
-    the naming order, in front of AB2, which refuses it; next to interpolated externals or per-trajectory events "none": no kernel)."""
+    the naming order, in front of AB2, which refuses it; next to interpolated externals or per-trajectory events "none": no kernel);
+    segment_parallel: None, or the segments per time chunk (an int >= 1, `resolve_segment_parallel`) of a call whose segments run side by
+    side on a tiles x chunks launch grid -- the family "msp" in "ms"'s place; where the computation runs, never what is computed."""
     acts: tuple
     tab: Optional[Tableau]
     substeps: int = 1
@@ -238,9 +287,12 @@ class GenericOpts:
     per_trajectory: bool = False
     segment: Optional[int] = None
     ab: bool = False
+    # (init-only: behind `ab` in the constructor and an attribute of the value like every option, but no entry of dataclasses.fields() --
+    #  the recorded field lists end with ab, family; the family, which is compared, tells "ms" from "msp")
+    segment_parallel: dataclasses.InitVar[Optional[int]] = None
     family: str = dataclasses.field(init=False)
 
-    def __post_init__(self):
+    def __post_init__(self, segment_parallel=None):
         """Validates substeps and externals, and names the entry-point family: "ab" (two-step Adams-Bashforth, with or without
         per-trajectory events; a ValueError together with a Tableau, sub-steps or interpolated externals), else "pev" (per-trajectory events, every substeps >= 1; together
         with interpolated externals "none": no kernel carries both, `require_generic` refuses the call), else "lin" (interpolated
@@ -255,8 +307,13 @@ class GenericOpts:
         if self.ab and self.segment is not None:
             raise ValueError("Adams-Bashforth 2 carries the previous slope from step to step: a multiple-shooting restart (segment=) has no "
                              f"form here (got segment={self.segment!r})")
+        sp = segment_parallel
+        object.__setattr__(self, "segment_parallel", sp)
+        if sp is not None and (isinstance(sp, bool) or not isinstance(sp, int) or sp < 1 or self.segment is None):
+            raise ValueError(f"segment_parallel must be None or the segments per chunk (an int >= 1) of a call with segment, got {sp!r} "
+                             f"(segment={self.segment!r})")
         if self.segment is not None:
-            fam = "none" if (is_linear(self.externals) or self.per_trajectory) else "ms"
+            fam = "none" if (is_linear(self.externals) or self.per_trajectory) else ("ms" if sp is None else "msp")
         elif self.ab:
             if self.substeps != 1 or is_linear(self.externals) or self.tab is not None:
                 raise ValueError("Adams-Bashforth 2 reads the right-hand side at grid points only: substeps != 1 and externals='linear' would "
@@ -277,9 +334,17 @@ class GenericOpts:
 
     @staticmethod
     @functools.lru_cache(maxsize=256, typed=True)      # (a loop asks for the same immutable value call after call; typed: 2.0 and True are not 2 and 1)
-    def of(method, acts: tuple, substeps: int = 1, externals: str = "hold", per_trajectory: bool = False, segment=None) -> "GenericOpts":
+    def of(method, acts: tuple, substeps: int = 1, externals: str = "hold", per_trajectory: bool = False, segment=None,
+           segment_parallel=None) -> "GenericOpts":
         method_id, stages, tab = method_info(method)
-        return GenericOpts(acts, tab, substeps, externals, method_id, stages, per_trajectory, segment, is_ab(method))
+        return GenericOpts(acts, tab, substeps, externals, method_id, stages, per_trajectory, segment, is_ab(method), segment_parallel)
+
+    def chunks(self, T: int) -> Optional[int]:
+        """The time chunks of a record of T grid points under these options (None without segment_parallel): as `segment_parallel=` of a
+        further call on the same record it names the same grouping."""
+        if self.segment_parallel is None:
+            return None
+        return max(1, -(-(-(-(T - 1) // self.segment)) // self.segment_parallel)) if T > 1 else 1
 
     def c_args(self, x_sub=None, x_true=None, family: Optional[str] = None) -> list:
         """The C arguments behind the args struct that the family's row of FAMILIES lists: the acts, the tableau or NULL (= the args' method),
@@ -293,7 +358,11 @@ class GenericOpts:
             out.append(ctypes.byref(_lib.SubstepsF32(self.substeps, x_sub.data_ptr() if x_sub is not None and x_sub.numel() else None)))
         if f.seg:
             rows = x_true.data_ptr() if x_true is not None and x_true.numel() else None
-            out.append(ctypes.byref(_lib.SegmentsF32(min(self.segment, 0x7fffffff), rows)))      # (a segment longer than any record: no restart)
+            every = min(self.segment, 0x7fffffff)      # (a segment longer than any record: no restart)
+            if f.par:
+                out.append(ctypes.byref(_lib.SegmentGroupsF32(every, rows, min(self.segment_parallel or 1, 0x7fffffff))))
+            else:
+                out.append(ctypes.byref(_lib.SegmentsF32(every, rows)))
         if f.pt:      # (handed to the query too, which does not declare it and never reads it)
             out.append(ctypes.c_int32(1 if self.per_trajectory else 0))
         return out
@@ -391,6 +460,9 @@ def call_generic(lib, stem: str, kind: str, args, opts: GenericOpts, *tail, x_su
     if isinstance(args, _lib.DaeBwdTfArgsF32):
         assert stem == "dae_backward" and fam != "act", f"{stem}: no entry point takes dataset rows and the acts {opts.acts} alone"
         fam = "tf" if fam == "plain" else fam
+    if kind == "workspace_bytes" and FAMILIES[fam].par:      # (the segment-parallel family sizes both backward stems itself)
+        name = f"psnode_{stem}_{fam}_workspace_size"
+        return getattr(lib, name)(ctypes.byref(args), *opts.c_args(x_sub, x_true, fam), *tail), name
     if kind == "workspace_bytes":
         assert stem in ("ode_backward", "dae_backward"), f"{stem} has no workspace query of its own"
         query = "plain" if stem == "ode_backward" else FAMILIES[fam].workspace

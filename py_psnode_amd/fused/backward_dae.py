@@ -7,19 +7,22 @@ import types
 import torch
 
 from .. import _lib
-from ._common import (KERNEL_ID, GenericOpts, Layers, _aligned16, _bind_jumps, _check_saved, _check_x_sub, _empty, _f32_dev, _mlp, _pad_rows, _padded_hidden, _split_grads, _view, _workspace_of, call_generic, check_event_idx, dae_acts, _ms_rows)
+from ._common import (KERNEL_ID, GenericOpts, Layers, _aligned16, _bind_jumps, _check_saved, _check_x_sub, _empty, _f32_dev, _mlp, _pad_rows, _padded_hidden, _split_grads, _view, _workspace_of, call_generic, check_event_idx, dae_acts, _ms_rows, check_segment_parallel, resolve_segment_parallel)
 from .latent import latent_backward_wide, latent_wide_shape
 
 def dae_backward_supported(method, de_layers: Layers, ae_layers: Layers, x_dim, z_dim, v_dim, i_dim, act=None, kernel: str = "auto",
-                           substeps: int = 1, externals: str = "hold", per_trajectory: bool = False, segment=None) -> bool:
+                           substeps: int = 1, externals: str = "hold", per_trajectory: bool = False, segment=None, segment_parallel=None) -> bool:
     """act: None (both MLPs ELU(1)) or (de_act, ae_act); an activation other than ELU(1) is K5's alone.  kernel="generic": does K5 take
     the shape (the question a teacher-forced call outside K7f's class asks).  method a fused.Tableau: K5's tableau build only (kernel
     "auto" / "generic"; it answers for its own LDS fit).  substeps > 1: K5's sub-step build only, under the same rules.
     externals="linear": K5's linear-externals build only (every substeps >= 1; it answers for its own LDS fit).
-    per_trajectory=True (a call WITH events): K5's per-trajectory build only (every substeps >= 1; never together with externals="linear")."""
+    per_trajectory=True (a call WITH events): K5's per-trajectory build only (every substeps >= 1; never together with externals="linear").
+    segment_parallel (not None; needs segment): K5's segment-parallel build answers -- its fit is the multiple-shooting build's."""
+    check_segment_parallel(segment_parallel, segment)
     if de_layers[0][0].device.type != "cuda" or max(len(de_layers), len(ae_layers)) > _lib.MAX_LAYERS:
         return False
-    opts = GenericOpts.of(method, dae_acts(act), substeps, externals, bool(per_trajectory), segment)      # (segment: K5's multiple-shooting build only)
+    opts = GenericOpts.of(method, dae_acts(act), substeps, externals, bool(per_trajectory), segment,      # (segment: K5's multiple-shooting build only)
+                          None if segment_parallel is None else 1)
     if opts.family == "plain" and kernel != "generic" and latent_wide_shape(de_layers, ae_layers, x_dim, z_dim, v_dim, i_dim):
         return True                          # K3w (saving) + K9w + library GEMMs
     args = opts.dae_backward_args(rows=False)
@@ -321,7 +324,7 @@ def _dae_backward_wide_sliced(step, method, de_layers, ae_layers, t, z, v, all_i
 
 def dae_backward(method, de_layers: Layers, ae_layers: Layers, t, z, v, all_initial, xs, is_, grad_xs, grad_is, event_idx=None,
                  z_jump=None, v_jump=None, kernel: str = "auto", saved=None, act=None, substeps: int = 1, x_sub=None, externals: str = "hold",
-                 per_trajectory: bool = False, segment=None, x_true=None):
+                 per_trajectory: bool = False, segment=None, x_true=None, segment_parallel=None):
     """Backward pass of `dae_integrate` (no teacher forcing): the one-launch K7f (`dae_backward_wide`) for the DAE_01 shape class at
     hidden <= 128, K9 / K8 / K9w for the latent shapes of the direct_encode models, else the generic backward kernel (K5);
     `kernel` = "auto" | "mfma" | "generic" | "wide" (K7f or an error).
@@ -335,10 +338,13 @@ def dae_backward(method, de_layers: Layers, ae_layers: Layers, t, z, v, all_init
     segment (an int w >= 1): backward of `dae_integrate(..., segment=w)` -- K5's multiple-shooting build only, the same rules; x_true
     [T, B, xd] is the dataset x of the forward call (needed where T - 1 > w; no gradient).  A restart step's start adjoint and the x part of
     its head's VJP are dropped; that head's z | v part goes to row k of grad z / v, or to the event's jump row.
+    segment_parallel (None, "auto" or an int g >= 1; needs segment): as `ode_backward` -- x_init, z, v and the jump gradients bit for bit
+    those of the call without it, both MLPs' gradients and all_initial the same sums in another order.
     Returns dict(x_init, z, v, z_jump, v_jump, all_initial, de=[...], ae=[...]) of gradients."""
     T, B, xd = xs.shape
     zd, vd, idim = z.shape[-1], v.shape[-1], is_.shape[-1]
-    opts = GenericOpts.of(method, dae_acts(act), substeps, externals, bool(per_trajectory) and event_idx is not None, segment)
+    opts = GenericOpts.of(method, dae_acts(act), substeps, externals, bool(per_trajectory) and event_idx is not None, segment,
+                          resolve_segment_parallel(segment_parallel, segment, T, B, xs.device))
     opts.require_generic("dae_backward", kernel, saved is not None)
     if opts.family != "plain":      # K5 alone (an activation other than ELU(1) asks for it by name, as it always did)
         return _dae_backward_entry(opts, de_layers, ae_layers, t, z, v, all_initial, xs, is_, grad_xs, grad_is, event_idx, z_jump, v_jump,
@@ -441,7 +447,7 @@ def _dae_backward_entry(opts, de_layers, ae_layers, t, z, v, all_initial, xs, is
                 if s_ev is None or s_evi is None or s_ev.shape[0] != n_ev_ or s_ev.shape[2] != B or s_evi.shape[:2] != (n_ev_, B):
                     raise ValueError("saved event activations do not belong to this call (shape)")
                 a.saved_ev_act, a.saved_ev_i = s_ev.data_ptr(), s_evi.data_ptr()
-        nbytes = call_generic(lib, "dae_backward", "workspace_bytes", args, opts, x_sub=x_sub)[0]
+        nbytes = call_generic(lib, "dae_backward", "workspace_bytes", args, opts, x_sub=x_sub, x_true=ms_x_true)[0]
         ws, wp, wn = _workspace_of(nbytes, dev)
         rc, entry = call_generic(lib, "dae_backward", "f32", args, opts, wp, wn, torch.cuda.current_stream(dev).cuda_stream, x_sub=x_sub, x_true=ms_x_true)
     _lib.check(rc, entry)

@@ -5,7 +5,7 @@ import ctypes
 import torch
 
 from .. import _lib
-from ._common import (KERNEL_ID, GenericOpts, Layers, _aligned16, _bind_jumps, _check_saved, _check_x_sub, _empty, _f32_dev, _mlp, _split_grads, _view, _workspace_of, call_generic, check_event_idx, _ms_rows)
+from ._common import (KERNEL_ID, GenericOpts, Layers, _aligned16, _bind_jumps, _check_saved, _check_x_sub, _empty, _f32_dev, _mlp, _split_grads, _view, _workspace_of, call_generic, check_event_idx, _ms_rows, check_segment_parallel, resolve_segment_parallel)
 from .latent import latent_backward_wide, latent_wide_shape
 
 def _bwd_args(opts, de_layers, x_dim, z_dim, T, B, dev, keep, kernel="auto"):
@@ -18,16 +18,18 @@ def _bwd_args(opts, de_layers, x_dim, z_dim, T, B, dev, keep, kernel="auto"):
 
 
 def ode_backward_supported(method, de_layers: Layers, x_dim: int, z_dim: int, kernel: str = "auto", act=None, substeps: int = 1,
-                           externals: str = "hold", per_trajectory: bool = False, segment=None) -> bool:
+                           externals: str = "hold", per_trajectory: bool = False, segment=None, segment_parallel=None) -> bool:
     """True if a fused backward kernel covers this shape: the MFMA class (3n->64->64->64->x, x<=8, z<=4) or any MLP whose
     activations and parameter gradients fit the LDS (generic backward).  act (fused.Act) other than None = ELU(1): K5 only.
     method a fused.Tableau: K5's tableau build only (kernel "auto" / "generic"; it answers for its own LDS fit).  substeps > 1: K5's
     sub-step build only, under the same rules.  externals="linear": K5's linear-externals build only (every substeps >= 1; its own LDS fit).
     per_trajectory=True (a call WITH events): K5's per-trajectory build only (every substeps >= 1; never together with externals="linear").
-    segment (an int >= 1): K5's multiple-shooting build only (every substeps >= 1; never together with either of the two before)."""
+    segment (an int >= 1): K5's multiple-shooting build only (every substeps >= 1; never together with either of the two before).
+    segment_parallel (not None; needs segment): K5's segment-parallel build answers -- its fit is the multiple-shooting build's."""
+    check_segment_parallel(segment_parallel, segment)
     if de_layers[0][0].device.type != "cuda" or len(de_layers) > _lib.MAX_LAYERS:
         return False
-    opts = GenericOpts.of(method, (act,), substeps, externals, bool(per_trajectory), segment)
+    opts = GenericOpts.of(method, (act,), substeps, externals, bool(per_trajectory), segment, None if segment_parallel is None else 1)
     if opts.family == "plain" and kernel in ("auto", "mfma") and latent_wide_shape(de_layers, None, x_dim, z_dim):
         return True                          # K3w (saving) + K9w + library GEMMs
     a = _bwd_args(opts, de_layers, x_dim, z_dim, 2, 1, de_layers[0][0].device, [], kernel)
@@ -36,7 +38,7 @@ def ode_backward_supported(method, de_layers: Layers, x_dim: int, z_dim: int, ke
 
 def ode_backward(method, de_layers: Layers, t, z, all_initial, xs, grad_xs, event_idx=None, z_jump=None, need_grad_z: bool = True,
                  kernel: str = "auto", saved=None, input_true_x: bool = False, need_grad_zj: bool = True, act=None, substeps: int = 1,
-                 x_sub=None, externals: str = "hold", per_trajectory: bool = False, segment=None, x_true=None):
+                 x_sub=None, externals: str = "hold", per_trajectory: bool = False, segment=None, x_true=None, segment_parallel=None):
     """Backward pass of `ode_integrate` in one launch.  `saved` = what `ode_integrate(save=True)` returned next to
     xs: K4f then skips the recompute of the stage evaluations.  input_true_x: backward of a teacher-forced call (my_solvers.py:72-74) --
     `xs` must then be the DATASET x the forward call started every step from; K4f where the shape is its (hidden <= 128, x_dim <= 8) and
@@ -58,6 +60,9 @@ def ode_backward(method, de_layers: Layers, t, z, all_initial, xs, grad_xs, even
     segment (an int w >= 1): backward of `ode_integrate(..., segment=w)` -- K5's multiple-shooting build, the rules of substeps; x_true
     [T, B, xd] is the dataset x of the forward call (needed where T - 1 > w; it gets no gradient).  The start adjoint of a restart step
     is dropped: grad_x0 is segment 0's, grad_xs[k] of a restart point still travels back into the segment before it.
+    segment_parallel (None, "auto" or an int g >= 1; needs segment): K5 on a tiles x chunks launch grid, workgroup (tile, c) sweeping time
+    chunk c alone (the grouping of `ode_integrate`).  grad_x0, grad_z and grad_z_jump are bit for bit those of the call without it; the
+    parameter gradients and grad_all_initial are the same sums in another order (one partial per workgroup / per chunk).
     Returns (grad_x0 [B,xd], grad_z [T,B,zd] | None, grad_z_jump | None, grad_all_initial [B,n], [grad W1, b1, ..., W4, b4])."""
     lib = _lib.load()
     dev = xs.device
@@ -66,7 +71,7 @@ def ode_backward(method, de_layers: Layers, t, z, all_initial, xs, grad_xs, even
     # kernel: "auto" / "mfma" = the one-launch K4f at every hidden width <= 128 (z_dim <= 8), K8f / K9 / K9w for the latent shapes, else the
     # generic K5 ("auto" only); "wide" forces K4f
     per_trajectory = bool(per_trajectory) and event_idx is not None
-    opts = GenericOpts.of(method, (act,), substeps, externals, per_trajectory, segment)
+    opts = GenericOpts.of(method, (act,), substeps, externals, per_trajectory, segment, resolve_segment_parallel(segment_parallel, segment, T, B, dev))
     opts.require_generic("ode_backward", kernel, saved is not None, teacher_forced=input_true_x)
     x_true = _ms_rows("ode_backward", segment, x_true, T, B, xd, dev)
     if per_trajectory:
@@ -110,7 +115,7 @@ def ode_backward(method, de_layers: Layers, t, z, all_initial, xs, grad_xs, even
             _check_saved(saved[0], saved[1], T, B, xd, opts.stages, len(de_layers) - 1, dev)
             keep += [saved[0], saved[1]]
             a.saved_act, a.saved_xstage = saved[0].data_ptr(), saved[1].data_ptr()
-        nbytes = call_generic(lib, "ode_backward", "workspace_bytes", a, opts)[0]
+        nbytes = call_generic(lib, "ode_backward", "workspace_bytes", a, opts, x_sub=x_sub)[0]
         ws, wp, wn = _workspace_of(nbytes, dev)
         rc, entry = call_generic(lib, "ode_backward", "f32", a, opts, wp, wn, torch.cuda.current_stream(dev).cuda_stream, x_sub=x_sub, x_true=x_true)
     _lib.check(rc, entry)

@@ -6,7 +6,7 @@ from typing import Optional
 import torch
 
 from .. import _lib
-from ._common import (KERNEL_ID, GenericOpts, Layers, Tableau, builtin_method, _aligned16, _bind_events, _check_tb, _empty, _f32_dev, _mlp, _view, _workspace_of, call_generic, dae_acts, has_events, is_linear)
+from ._common import (KERNEL_ID, GenericOpts, resolve_segment_parallel, Layers, Tableau, builtin_method, _aligned16, _bind_events, _check_tb, _empty, _f32_dev, _mlp, _view, _workspace_of, call_generic, dae_acts, has_events, is_linear)
 
 _MFMA_CLASSES = ("MFMA integrators K1 / K2 cover `in -> H -> H -> H -> out` ELU-MLPs with H <= 128 (any x_dim <= 16 for the ODE, "
                  "x_dim <= 8 and z+v+i <= 8 for the DAE), and -- weights streamed from L2 -- the ODE up to H = 192 at any x_dim <= 16 and "
@@ -45,7 +45,7 @@ def _note_k0(lib, args, dae: bool, de_layers: Layers):
 def ode_integrate(method, de_layers: Layers, t, x, z, all_initial, event_t=None, z_jump=None,
                   input_true_x: bool = False, kernel: str = "auto", event_idx: Optional[torch.Tensor] = None,
                   check_events: bool = False, out: Optional[torch.Tensor] = None, save: bool = False, act=None, substeps: int = 1,
-                  save_sub: bool = False, externals: str = "hold", per_trajectory: bool = False, segment=None):
+                  save_sub: bool = False, externals: str = "hold", per_trajectory: bool = False, segment=None, segment_parallel=None):
     """Fused integrate_ODE (replaces my_solvers.py:52-80 + my_fixed_grid.py + DE_Func.forward).
 
     method: "euler" | "midpoint" | "rk4" (the 3/8 rule), or a fused.Tableau -- any explicit Runge-Kutta method of up to four stages, on
@@ -74,6 +74,11 @@ def ode_integrate(method, de_layers: Layers, t, x, z, all_initial, event_t=None,
     build for every substeps >= 1 (kernel "auto" / "generic"; save=True, externals="linear" and per_trajectory events are refused, and
     input_true_x is a ValueError; save_sub then always returns a tensor).
 
+    segment_parallel (None, "auto" or an int g >= 1; needs segment): where the call runs, never what it computes.  The n_seg =
+    ceil((T - 1) / w) segments are grouped into up to g time chunks of ceil(n_seg / min(g, n_seg)) consecutive segments, and K0 runs on a
+    tiles x chunks launch grid, workgroup (tile, c) integrating its 16 trajectories over chunk c alone; xs (and x_sub) are bit for bit
+    those of the call without the option.  "auto": g = max(1, CUs // tiles).  One chunk is the call without the option.
+
     save=True (training forward, K1 shapes only -- `ode_save_hidden`): the kernel also writes what autograd would save, the hidden
     activations [T-1,S,3,B,Hp] and the stage inputs [T-1,S,B,xd]; returns (xs, (act, xstage)) for `ode_backward(..., saved=)`.
 
@@ -87,7 +92,8 @@ def ode_integrate(method, de_layers: Layers, t, x, z, all_initial, event_t=None,
     if dev.type != "cuda":
         raise ValueError("fused integrator needs tensors on a HIP device")
     per_trajectory = bool(per_trajectory) and has_events(t, event_t, event_idx)
-    opts = GenericOpts.of(method, (act,), substeps, externals, per_trajectory, segment)
+    per_group = resolve_segment_parallel(segment_parallel, segment, t.shape[0], x.shape[1], dev)
+    opts = GenericOpts.of(method, (act,), substeps, externals, per_trajectory, segment, per_group)
     opts.require_generic("ode_integrate", kernel, save)
     opts.no_teacher_forcing("ode_integrate", input_true_x)
     T, B, xd = t.shape[0], x.shape[1], x.shape[2]
@@ -159,7 +165,7 @@ def dae_integrate(method, de_layers: Layers, ae_layers: Layers, x_init, t, x, z,
                   event_t=None, z_jump=None, v_jump=None, input_true_x: bool = False, input_true_i: bool = False,
                   kernel: str = "auto", event_idx: Optional[torch.Tensor] = None, check_events: bool = False, out=None,
                   save: bool = False, act=None, substeps: int = 1, save_sub: bool = False, externals: str = "hold",
-                  per_trajectory: bool = False, segment=None):
+                  per_trajectory: bool = False, segment=None, segment_parallel=None):
     """Fused integrate_DAE (replaces my_solvers.py:82-131 + step functions + DE_Func/AE_Func forwards).
     method: "euler" | "midpoint" | "rk4", or a fused.Tableau (generic kernel K0 only: kernel "auto" / "generic"; save=True is refused).
     act: None (both MLPs ELU(1)) or (de_act, ae_act), each a fused.Act or None = ELU(1); an activation other than ELU(1) runs on the
@@ -176,6 +182,8 @@ def dae_integrate(method, de_layers: Layers, ae_layers: Layers, x_init, t, x, z,
     segment (None, or an int w >= 1): multiple shooting, as `ode_integrate`; the DE of a restart step reads the head at the dataset row,
     g(x[k]; z_k, v_k) with the jumped rows behind an event, while xs[k] / is[k] stay the previous segment's prediction.  Needs the dataset
     x [T, B, x_dim] (ValueError without); teacher forcing is a ValueError.  K0's multiple-shooting build (kernel "auto" / "generic", no save).
+    segment_parallel (None, "auto" or an int g >= 1; needs segment): as `ode_integrate` -- the segments in up to g time chunks on a
+    tiles x chunks launch grid; xs, is and x_sub bit for bit those of the call without it.
     `out` = (xs, is) contiguous [T,B,xd] / [T,B,id] tensors to write into (time-chunked launches).
     save=True (training forward, K2 shapes without teacher forcing -- `dae_save_hidden`): the kernel also writes what autograd would
     save (psnode_dae_args_f32::save_*); returns (xs, is, saved) with saved = (act [T-1,S,3,B,Hp], xstage [T-1,S,B,xd],
@@ -185,7 +193,8 @@ def dae_integrate(method, de_layers: Layers, ae_layers: Layers, x_init, t, x, z,
     if dev.type != "cuda":
         raise ValueError("fused integrator needs tensors on a HIP device")
     per_trajectory = bool(per_trajectory) and has_events(t, event_t, event_idx)
-    opts = GenericOpts.of(method, dae_acts(act), substeps, externals, per_trajectory, segment)
+    per_group = resolve_segment_parallel(segment_parallel, segment, t.shape[0], t.shape[1], dev)
+    opts = GenericOpts.of(method, dae_acts(act), substeps, externals, per_trajectory, segment, per_group)
     opts.require_generic("dae_integrate", kernel, save)
     opts.no_teacher_forcing("dae_integrate", input_true_x or input_true_i)
     if segment is not None and x.shape[-1] == 0:

@@ -36,8 +36,15 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
     order: int
     method = ""        # "euler" | "midpoint" | "rk4", a fused.Tableau (my_fixed_grid.ExplicitRK) or "ab2" (my_fixed_grid.AB2): the formula the fused kernels run
 
-    def __init__(self, step_size=None, grid_constructor=None, interp="linear", substeps=1, externals="hold", segment=None):
-        """segment (None, the default, or an int w >= 1): multiple shooting.  Grid point k is a restart point iff k > 0 and k % w == 0: the
+    def __init__(self, step_size=None, grid_constructor=None, interp="linear", substeps=1, externals="hold", segment=None,
+                 segment_parallel=None):
+        """segment_parallel (None, the default: the call it was; "auto" or an int g >= 1; needs segment): where a fused call with segments
+        runs, never what it computes -- the segments of a record get no gradient through the dataset rows, so they are independent, and the
+        generic kernels K0 / K5 then run them side by side: the n_seg = ceil((T - 1) / w) segments in up to g time chunks of
+        ceil(n_seg / min(g, n_seg)) consecutive ones, on a launch grid of tiles x chunks workgroups.  "auto": g = max(1, CUs // tiles) with
+        tiles = ceil(B / 16) -- a small batch on a long record fills the device, a batch that fills it already stays as it was.  The walks
+        and fused="off" ignore it; every refusal of `segment` applies unchanged.
+        segment (None, the default, or an int w >= 1): multiple shooting.  Grid point k is a restart point iff k > 0 and k % w == 0: the
         step that leaves it starts from the dataset row x[k] instead of the running state, and a DAE's DE reads the head at that row,
         g(x[k]; z_k, v_k) with the jumped rows if an event fires at k.  Output rows m w + 1 .. min((m + 1) w, T - 1) are then exactly what
         the free-running call returns in its rows 1 .. on the slices [m w : (m + 1) w + 1] started from x[m w]; xs[k] / is[k] of a restart
@@ -64,6 +71,8 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
         if segment is not None and (isinstance(segment, bool) or not isinstance(segment, int) or segment < 1):
             raise ValueError(f"segment must be None or an int >= 1, got {segment!r}")
         self.segment = segment
+        _fused.check_segment_parallel(segment_parallel, segment)
+        self.segment_parallel = segment_parallel
         # public attributes of the reference (my_solvers.py:13-18)
         self.step_size = step_size
         self.interp = interp
@@ -153,6 +162,8 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
             kw["per_trajectory"] = True
         if self.segment is not None:
             kw["segment"] = self.segment
+        if self.segment_parallel is not None:
+            kw["segment_parallel"] = self.segment_parallel
         return kw
 
     def _step_func_lin(self, func, t0, dt, x0, ext_at, i0=None, all_initial=None):

@@ -180,6 +180,9 @@ def _no_segments(what: str, kw: dict):
     if kw.get("segment") is not None:
         raise ValueError(f"{what}: segment={kw['segment']!r} has no time-chunked form (a chunk carries neither the dataset rows x[k] nor the "
                          "phase of the restarts); integrate the shard in one launch (fused.ode_integrate / dae_integrate)")
+    if kw.get("segment_parallel") is not None:      # (likewise: it spreads the segments a pipelined call cannot have)
+        raise ValueError(f"{what}: segment_parallel={kw['segment_parallel']!r} needs segment=, which has no time-chunked form; integrate the "
+                         "shard in one launch (fused.ode_integrate / dae_integrate)")
 
 
 def integrate_ode_pipelined(method, de_layers, t, x, z, all_initial, event_idx=None, z_jump=None, chunks: int = 4, group=None,
