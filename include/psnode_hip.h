@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define PSNODE_ABI_VERSION 10    /* 10 also carries the additive psnode_act_f32 / *_act_*, psnode_rk_tableau_f32 / *_rk_*, psnode_substeps_f32 / *_sub_*, *_lin_*, *_pev_* / psnode_event_table_pt_f32 and *_ab_* entry points (end of this file), and psnode_loss_fn_f32 / psnode_masked_loss_* / psnode_loss_per_sample_f32 (next to psnode_masked_mse_f32) */
+#define PSNODE_ABI_VERSION 10    /* 10 also carries the additive psnode_act_f32 / *_act_*, psnode_rk_tableau_f32 / *_rk_*, psnode_substeps_f32 / *_sub_*, *_lin_*, *_pev_* / psnode_event_table_pt_f32, *_ab_* and *_ab3_* entry points (end of this file), and psnode_loss_fn_f32 / psnode_masked_loss_* / psnode_loss_per_sample_f32 (next to psnode_masked_mse_f32) */
 #define PSNODE_MAX_LAYERS 8      /* Linear layers per MLP */
 #define PSNODE_MAX_WIDTH 1024    /* widest layer OUTPUT the kernels accept */
 #define PSNODE_MAX_IN_WIDTH 2048 /* widest first-layer INPUT (the latent DE of DAE_02 at --hidden 128 is 12 x 128 = 1536 wide) */
@@ -1000,6 +1000,33 @@ size_t psnode_dae_backward_msp_workspace_size(const psnode_dae_bwd_tf_args_f32* 
 int32_t psnode_dae_backward_msp_f32(const psnode_dae_bwd_tf_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
                                     const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, const psnode_segment_groups_f32* grp,
                                     void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- Three-step Adams-Bashforth with a predictor-corrector restart step on the generic kernels (additive to ABI 10; DESIGN.md
+ * "Adams-Bashforth 3 on K0 / K5").  Step k, per trajectory, with h_k = t[k+1] - t[k] and f_k the DE at the inputs the _ab family's stage reads.
+ * Restart flag R_k: k = 0, an event of the trajectory at step k, or h_{k-1} == 0.  Depth d_k: 0 if R_k; 1 if R_{k-1} or
+ * h_{k-1} + h_{k-2} == 0; 2 otherwise.
+ *     d_k = 2, h0, h1, h2 = h_k, h_{k-1}, h_{k-2}:  g1 = h0^2 / 2, g2 = h0^3 / 3 + h1 g1, D = g2 / (h1 + h2),
+ *              c0 = h0 + g1 / h1 + D / h1, c1 = -g1 / h1 - D / h1 - D / h2, c2 = D / h2;   x_{k+1} = x_k + c0 f_k + c1 f_{k-1} + c2 f_{k-2}
+ *     d_k = 1: the _ab family's step.
+ *     d_k = 0: x~ = x_k + h f_k;  f~ = the DE at (x~; rows k + 1 of z | v, never jumped; a DAE: i~ = AE(x~; z[k+1], v[k+1]), no output);
+ *              x_{k+1} = x_k + (h / 2)(f_k + f~);  the slope kept for the history is f_k.
+ * Outputs, the heads at the grid points and at an event are the _ab family's.  A backward call runs the corrector's VJP in front of the
+ * DE's on a restart step and adds its z | v part to row k + 1 of grad_z / grad_v; the DE's VJP of step k takes
+ * a_k g_{k+1} + c1_{k+1} g_{k+2} + c2_{k+2} g_{k+3} (+ h (df~/dx~)^T (h / 2) g_{k+1} on a restart step, where a_k = h / 2).  No atomics,
+ * bitwise repeatable; the clock gets no gradient.  Rows beyond T - 1 are never read.
+ * Arguments, rules, the order of checks and the workspaces are the _ab family's, prototype for prototype. */
+int32_t psnode_ode_integrate_ab3_supported(const psnode_ode_args_f32* args, const psnode_act_f32* de_act);
+int32_t psnode_ode_integrate_ab3_f32(const psnode_ode_args_f32* args, const psnode_act_f32* de_act, int32_t per_trajectory, void* workspace,
+                                     size_t workspace_bytes, void* stream);
+int32_t psnode_dae_integrate_ab3_supported(const psnode_dae_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act);
+int32_t psnode_dae_integrate_ab3_f32(const psnode_dae_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                     int32_t per_trajectory, void* workspace, size_t workspace_bytes, void* stream);
+int32_t psnode_ode_backward_ab3_supported(const psnode_ode_bwd_args_f32* args, const psnode_act_f32* de_act);
+int32_t psnode_ode_backward_ab3_f32(const psnode_ode_bwd_args_f32* args, const psnode_act_f32* de_act, int32_t per_trajectory, void* workspace,
+                                    size_t workspace_bytes, void* stream);
+int32_t psnode_dae_backward_ab3_supported(const psnode_dae_bwd_tf_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act);
+int32_t psnode_dae_backward_ab3_f32(const psnode_dae_bwd_tf_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                    int32_t per_trajectory, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

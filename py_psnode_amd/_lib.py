@@ -41,6 +41,8 @@ ABI_VERSION = 10         # == PSNODE_ABI_VERSION of include/psnode_hip.h (2: rou
                          #     points -- per-trajectory events (an event table [T-1, B]) on K0 / K5;
                          #     additive, same version: the psnode_{ode,dae}_{integrate,backward}_ab_* entry points -- two-step
                          #     Adams-Bashforth on K0 / K5;
+                         #     additive, same version: the psnode_{ode,dae}_{integrate,backward}_ab3_* entry points -- three-step
+                         #     Adams-Bashforth with a predictor-corrector restart step on K0 / K5;
                          #     additive, same version: psnode_segments_f32 and the psnode_{ode,dae}_{integrate,backward}_ms_* entry points --
                          #     multiple-shooting segments on K0 / K5;
                          #     additive, same version: psnode_segment_groups_f32 and the psnode_{ode,dae}_{integrate,backward}_msp_* entry points
@@ -90,6 +92,9 @@ EXPORTS = (
     "psnode_ode_integrate_ab_supported", "psnode_ode_integrate_ab_f32", "psnode_dae_integrate_ab_supported", "psnode_dae_integrate_ab_f32",
     "psnode_ode_backward_ab_supported", "psnode_ode_backward_ab_f32",
     "psnode_dae_backward_ab_supported", "psnode_dae_backward_ab_f32",
+    "psnode_ode_integrate_ab3_supported", "psnode_ode_integrate_ab3_f32", "psnode_dae_integrate_ab3_supported", "psnode_dae_integrate_ab3_f32",
+    "psnode_ode_backward_ab3_supported", "psnode_ode_backward_ab3_f32",
+    "psnode_dae_backward_ab3_supported", "psnode_dae_backward_ab3_f32",
     "psnode_ode_integrate_ms_supported", "psnode_ode_integrate_ms_f32", "psnode_dae_integrate_ms_supported", "psnode_dae_integrate_ms_f32",
     "psnode_ode_backward_ms_supported", "psnode_ode_backward_ms_f32",
     "psnode_dae_backward_ms_supported", "psnode_dae_backward_ms_f32",

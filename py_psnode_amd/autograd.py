@@ -53,7 +53,7 @@ def latent_wide_training_fits(method, de, ae, hidden, T, B, dev) -> bool:
 def _generic_only_training(opts, kernel, teacher_forced, T=2) -> bool:
     """The gate of a training call that carries an option of the generic kernels (fused.GenericOpts.family other than "plain"): K0 + K5
     alone, so kernel "auto" / "generic"; teacher forcing with ELU(1) only and, for the DAE, on a grid of T >= 2.  K5 then answers for its fit."""
-    if (opts.ab or opts.segment is not None) and teacher_forced:      # (neither Adams-Bashforth 2 nor segments have a teacher-forced form on any path: the solver raises before it asks)
+    if (opts.ab or opts.segment is not None) and teacher_forced:      # (neither Adams-Bashforth 2 / 3 nor segments have a teacher-forced form on any path: the solver raises before it asks)
         return False
     return kernel in ("auto", "generic") and not (teacher_forced and (T < 2 or any(a is not None for a in opts.acts)))
 
@@ -318,7 +318,7 @@ class _FusedOdeGeneric(torch.autograd.Function):
 
 # fused.GenericOpts.family ("ab": with per_trajectory) -> the name of its Function: `_FusedOde<name>` / `_FusedDae<name>`, an empty subclass of
 # the model's one body, is what xs.grad_fn reports.  A further family of K0 / K5 that saves sub-state rows adds a row here, not a class.
-_FAMILY_CLASSES = {"sub": "Sub", "lin": "Lin", "pev": "Pev", ("ab", False): "Ab", ("ab", True): "AbPev", "ms": "Ms", "msp": "Msp"}
+_FAMILY_CLASSES = {"sub": "Sub", "lin": "Lin", "pev": "Pev", ("ab", False): "Ab", ("ab", True): "AbPev", ("ab3", False): "Ab3", ("ab3", True): "Ab3Pev", "ms": "Ms", "msp": "Msp"}
 # the families that go to _FusedOde / _FusedDae / _FusedDaeTeacherForced
 _OWN_CLASS = ("plain", "act", "rk")
 # ... and those whose forward (fused.ode_integrate / fused.dae_integrate) is the first to check the call
@@ -331,11 +331,11 @@ def _family_classes(body, prefix) -> dict:
 
 
 def _family_class(classes, opts):
-    return classes[(opts.family, opts.per_trajectory) if opts.family == "ab" else opts.family]
+    return classes[(opts.family, opts.per_trajectory) if opts.family in ("ab", "ab3") else opts.family]
 
 
 def _refuse(what, opts, kernel, teacher_forced):
-    """The refusals of a differentiable call, under the name `what`: teacher forcing next to Adams-Bashforth 2 or segments (ValueError), the
+    """The refusals of a differentiable call, under the name `what`: teacher forcing next to Adams-Bashforth 2 / 3 or segments (ValueError), the
     families that have no kernel, a kernel other than "auto" / "generic" (UnsupportedShapeError)."""
     if opts.family not in _CHECKED_BY_FORWARD:
         opts.no_teacher_forcing(what, teacher_forced)

@@ -101,6 +101,7 @@ int generic_backward(BuildId build, const GenericBwdCall& c, const ActPair* act,
         case kBuildAb: return generic_backward_launch<BuildAb>(c, act, ws, s);
         case kBuildMs: return generic_backward_launch<BuildMs>(c, act, ws, s);
         case kBuildMsp: return generic_backward_launch<BuildMsp>(c, act, ws, s);
+        case kBuildAb3: return generic_backward_launch<BuildAb3>(c, act, ws, s);
     }
     return PSNODE_ERR_UNSUPPORTED;      // (no such build)
 }
@@ -473,6 +474,23 @@ extern "C" int32_t psnode_dae_backward_ab_supported(const psnode_dae_bwd_tf_args
 extern "C" int32_t psnode_dae_backward_ab_f32(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
                                               int32_t per_trajectory, void* ws, size_t bytes, void* stream) {
     return k5_backward(kFamAb, a, {de_act, ae_act, nullptr, nullptr, nullptr, per_trajectory}, ws, bytes, stream);
+}
+
+// (three-step Adams-Bashforth with the Heun restart step: the _ab family's prototypes and order of checks)
+extern "C" int32_t psnode_ode_backward_ab3_supported(const psnode_ode_bwd_args_f32* a, const psnode_act_f32* de_act) {
+    return k5_supported(kFamAb3, a, {de_act});
+}
+extern "C" int32_t psnode_ode_backward_ab3_f32(const psnode_ode_bwd_args_f32* a, const psnode_act_f32* de_act, int32_t per_trajectory, void* ws,
+                                              size_t bytes, void* stream) {
+    return k5_backward(kFamAb3, a, {de_act, nullptr, nullptr, nullptr, nullptr, per_trajectory}, ws, bytes, stream);
+}
+extern "C" int32_t psnode_dae_backward_ab3_supported(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act,
+                                                    const psnode_act_f32* ae_act) {
+    return k5_supported(kFamAb3, a, {de_act, ae_act});
+}
+extern "C" int32_t psnode_dae_backward_ab3_f32(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                              int32_t per_trajectory, void* ws, size_t bytes, void* stream) {
+    return k5_backward(kFamAb3, a, {de_act, ae_act, nullptr, nullptr, nullptr, per_trajectory}, ws, bytes, stream);
 }
 
 // (multiple shooting: the step that leaves grid point k > 0 with k % seg->every == 0 started from seg->x_true[k])

@@ -109,6 +109,7 @@ int dispatch(IntegrateDev& d, bool dae, int kernel, const psnode_mlp_f32* de, co
         case kBuildAb: e = launch_generic<BuildAb>(d, dae, call, stream); break;
         case kBuildMs: e = launch_generic<BuildMs>(d, dae, call, stream); break;
         case kBuildMsp: e = launch_generic<BuildMsp>(d, dae, call, stream); break;
+        case kBuildAb3: e = launch_generic<BuildAb3>(d, dae, call, stream); break;
     }
     return ok_or_hip(e);
 }
@@ -496,6 +497,22 @@ int32_t psnode_dae_integrate_ab_supported(const psnode_dae_args_f32* a, const ps
 int32_t psnode_dae_integrate_ab_f32(const psnode_dae_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
                                     int32_t per_trajectory, void* ws, size_t bytes, void* stream) {
     return k0_integrate(kFamAb, args, {de_act, ae_act, nullptr, nullptr, nullptr, per_trajectory}, ws, bytes, stream);
+}
+
+// (three-step Adams-Bashforth with the Heun restart step: the _ab family's prototypes and order of checks)
+int32_t psnode_ode_integrate_ab3_supported(const psnode_ode_args_f32* a, const psnode_act_f32* de_act) {
+    return k0_supported(kFamAb3, a, {de_act});
+}
+int32_t psnode_ode_integrate_ab3_f32(const psnode_ode_args_f32* args, const psnode_act_f32* de_act, int32_t per_trajectory, void* ws, size_t bytes,
+                                    void* stream) {
+    return k0_integrate(kFamAb3, args, {de_act, nullptr, nullptr, nullptr, nullptr, per_trajectory}, ws, bytes, stream);
+}
+int32_t psnode_dae_integrate_ab3_supported(const psnode_dae_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act) {
+    return k0_supported(kFamAb3, a, {de_act, ae_act});
+}
+int32_t psnode_dae_integrate_ab3_f32(const psnode_dae_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                    int32_t per_trajectory, void* ws, size_t bytes, void* stream) {
+    return k0_integrate(kFamAb3, args, {de_act, ae_act, nullptr, nullptr, nullptr, per_trajectory}, ws, bytes, stream);
 }
 
 // (multiple shooting: grid point k > 0 with k % seg->every == 0 restarts from row k of the args' x, which then holds all T rows)

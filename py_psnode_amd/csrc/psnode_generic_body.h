@@ -169,6 +169,18 @@
         if (ev_table_pt(sub)) { ev_sk = a.B; ev_sb = 1; }
         evn_v = (a.ev && a.T > 1) ? evp[gb(tid % TB) * ev_sb] : -1;
     }
+    // Adams-Bashforth 3 (Bd::ab3, on Bd::ab's policy): x_{k+1} = x_k + c0 f_k + c1 f_{k-1} + c2 f_{k-2} with the per-column coefficients of
+    // ab3_coef (psnode_generic_build.h) by the depth of the history, and on a restart step (k = 0, an event of the column, h_{k-1} == 0) a Heun
+    // corrector on the rows of grid point k + 1: two more evaluation slots, run only where some column of the workgroup restarts, selected
+    // per column.  EVERY thread carries the clocks of ITS column (tid % TB: the column of every item a thread touches), the two previous
+    // steps, the restart flags and the coefficients in registers -- nothing per column goes through LDS; f_{k-1} / f_{k-2} live in kbuf's
+    // slots 0 / 2, written and read by the owning thread alone.
+    [[maybe_unused]] float ab_h0 = 0.0f, ab_h1 = 0.0f, ab_h2 = 0.0f, ab_c0 = 0.0f, ab_c1 = 0.0f, ab_c2 = 0.0f;
+    [[maybe_unused]] bool ab_rs = true, ab_rp = true, any_rs = false;
+    if constexpr (Bd::ab3) {
+        tc = a.t.p[gb(tid % TB) * a.t.sb];
+        tn = a.T > 1 ? a.t.p[a.t.st + gb(tid % TB) * a.t.sb] : tc;
+    }
 
     // Multiple shooting (Bd::ms): grid point k > 0 with k % every == 0 is a restart point -- the step that leaves it starts from the dataset
     // row a.x[k] and, in a DAE, feeds the DE the head at that row (the event slot, which then runs without an event too).  Launch-uniform:
@@ -203,7 +215,18 @@
         }
         if (k >= 0) {
             // ---- this step's inputs (zero-order hold: the left grid point feeds every stage)
-            if constexpr (Bd::ab) {
+            if constexpr (Bd::ab3) {      // (every thread, for its column tid % TB: `ev` is that column's)
+                ab_h2 = ab_h1;
+                ab_h1 = ab_h0;
+                ab_rp = ab_rs;
+                ab_h0 = tn - tc;
+                ab_rs = k == 0 || ev >= 0 || ab_h1 == 0.0f;
+                const Ab3Coef cf = ab3_coef(ab_h0, ab_h1, ab_h2, ab_rs, ab_rp || ab_h1 + ab_h2 == 0.0f);
+                ab_c0 = cf.c0;
+                ab_c1 = cf.c1;
+                ab_c2 = cf.c2;
+                any_rs = __builtin_amdgcn_ballot_w64(ab_rs) != 0;      // (workgroup-uniform: each wave holds every column)
+            } else if constexpr (Bd::ab) {
                 if (tid < TB) {      // (a thread < TB owns column tid: `ev` is that column's)
                     const float h = tn - tc;
                     const bool restart = k == 0 || ev >= 0 || hp == 0.0f;
@@ -244,6 +267,8 @@
             }
             // ---- look-ahead for grid point k + 1
             const long long k1 = k + 1, k2 = k + 2 < a.T ? k + 2 : a.T - 1;
+            if constexpr (Bd::ab3) { tc = tn; tn = a.t.p[k2 * a.t.st + gb(tid % TB) * a.t.sb]; }
+            else
             if (tid < TB) { tc = tn; tn = a.t.p[k2 * a.t.st + gb(tid) * a.t.sb]; }
             evn_v = (a.ev && k1 + 1 < a.T) ? evp[k1] : -1;
             if constexpr (Bd::pev && !Bd::ab) evn_v = k1 + 1 < a.T ? evp[k1 * a.B + gb(tid % TB)] : -1;
@@ -262,15 +287,18 @@
         // in the event slot's form -- the algebraic variable follows the state inside the interval
         SubIter<Bd::sub> si(k >= 0 ? nsub : 1);
         do {
-        const int e_end = (DAE && si.last()) ? nstage + 1 : nstage;
-        for (int e = k < 0 ? nstage + 1 : ((DAE && (si.first() ? (Bd::pev ? any_ev : (ev >= 0 || (Bd::ms && ms_rs))) : !true_i)) ? 0 : 1); e <= e_end; ++e) {
-            const bool is_ae = DAE && (e == 0 || e == nstage + 1);
-            const bool ae_next = DAE && e == nstage && (si.last() || !true_i);
+        // (Bd::ab3: slot 2 = the AE head at the predictor x~ and rows k + 1, slot 3 = the corrector's DE stage -- both only where some column
+        //  restarts --, slot 4 = the AE head at grid point k + 1)
+        const int e_end = Bd::ab3 ? (DAE ? 4 : (any_rs ? 3 : 1)) : ((DAE && si.last()) ? nstage + 1 : nstage);
+        for (int e = k < 0 ? (Bd::ab3 ? 4 : nstage + 1) : ((DAE && (si.first() ? (Bd::pev ? any_ev : (ev >= 0 || (Bd::ms && ms_rs))) : !true_i)) ? 0 : 1); e <= e_end; ++e) {
+            if constexpr (Bd::ab3) { if ((e == 2 && !(DAE && any_rs)) || (e == 3 && !any_rs)) continue; }
+            const bool is_ae = DAE && (e == 0 || e == (Bd::ab3 ? 4 : nstage + 1) || (Bd::ab3 && e == 2));
+            const bool ae_next = Bd::ab3 ? (DAE && (e == 1 || e == 3)) : (DAE && e == nstage && (si.last() || !true_i));
             int f;
             if constexpr (MODE == 0 || MODE == 3) {
                 // (sub-steps: the externals change inside an interval only where the DAE's own i does)
                 // (linear externals: and in front of every stage whose theta is not the one folded)
-                if ((e == 1 && (si.first() || (DAE && !true_i))) || (Bd::lin && !is_ae && th_in != th_fd)) {       // the step's externals are in place (behind an event's AE evaluation too): the DE's per-step constant
+                if ((e == 1 && (si.first() || (DAE && !true_i))) || (Bd::lin && !is_ae && th_in != th_fd) || (Bd::ab3 && e == 3)) {       // the step's externals are in place (behind an event's AE evaluation too): the DE's per-step constant
                     const int nt0 = tab_tiles(tde.dims[0]);
                     if (wv < nt0) cde = fold0<ML>(tde, lds, inDE, wv);
                     if (MODE == 3 && wv + 4 < nt0) cde2 = fold0<ML>(tde, lds, inDE, wv + 4);
@@ -293,19 +321,66 @@
                     for (int idx = tid; idx < id * TB; idx += NT) {
                         const int r = idx / TB, c = idx % TB;
                         const float v = lds[f + qi(r, c)];
+                        if constexpr (Bd::ab3) { if (e == 2) { put_ext(nzv + r, c, v); continue; } }      // i~: the corrector's algebraic input, no output
                         // (per-trajectory events: the event-time head ran because SOME column has a hit; the others keep the i they carry)
                         if constexpr (Bd::pev) { if (e == 0 && si.first() && ev < 0) continue; }
                         icur[idx] = v;       // read back by the same thread (below, or at the top of the next step)
                         if (e == 0) put_ext(nzv + r, c, true_i ? a.i.p[k * a.i.st + gb(c) * a.i.sb + r] : v);
                         else if (b0 + c < a.B) a.io[((k + 1) * a.B + b0 + c) * id + r] = v;
                     }
-                    if (e == 0) lds_barrier();
+                    if (e == 0 || (Bd::ab3 && e == 2)) lds_barrier();
                 }
                 K0_PROF(4)
                 continue;
             }
             // ---- stage s: ONE pass that forms the next stage's argument straight into the DE input (my_fixed_grid.py:15-18, 23-32, 38-51)
             //      or, behind the last stage, the new state, its output row, the AE input and the look-ahead rows
+            if constexpr (Bd::ab3) {
+                // e == 1: the step's one stage -- the multistep update with this thread's coefficients (a restart column: c0 = h, the Euler
+                // predictor x~) -- which shifts the slope history; where some column restarts, x~ and the rows of grid point k + 1 become the
+                // next evaluations' inputs instead of the step's result.  e == 3: the corrector, taken by the restart columns alone.
+                const bool corr = e == 3;
+                const bool pred = !corr && any_rs;
+                for (int idx = tid; idx < nx; idx += NT) {
+                    const int r = idx / TB, c = idx % TB;
+                    const float x0 = xsrc[idx];
+                    const float ks = lds[f + qi(r, c)];
+                    float v;
+                    if (!corr) {      // (c1 / c2 are 0 where the history is not read: its slots may be unwritten)
+                        v = x0 + ab_c0 * ks;
+                        if (ab_c1 != 0.0f) v = v + ab_c1 * kbuf[idx];
+                        if (ab_c2 != 0.0f) v = v + ab_c2 * kbuf[2 * nx + idx];
+                        kbuf[2 * nx + idx] = kbuf[idx];
+                        kbuf[idx] = ks;          // f_k, the slope kept for the history (never the corrector's)
+                    } else {
+                        v = ab_rs ? x0 + (ab_h0 * 0.5f) * (kbuf[idx] + ks) : xcur[idx];
+                    }
+                    xcur[idx] = v;
+                    if (pred) put_x(r, c, v);
+                    else if (b0 + c < a.B) a.xo[((k + 1) * a.B + b0 + c) * xd + r] = v;
+                    if constexpr (DAE) lds[inAE + qi(r, c)] = v;
+                }
+                if (!corr) {      // z | v of grid point k + 1: the next step's rows, the heads' -- and the corrector's, never jumped
+#pragma unroll
+                    for (int j = 0; j < PF; ++j) {
+                        const int idx = tid + NT * j;
+                        if (idx < nzv * TB) {
+                            zvn[idx] = pz[j];
+                            if constexpr (DAE) lds[inAE + qi(xd + idx / TB, idx % TB)] = pz[j];
+                            if (pred) put_ext(idx / TB, idx % TB, pz[j]);
+                        }
+                    }
+                    for (int idx = tid + NT * PF; idx < nzv * TB; idx += NT) {
+                        const float v = zv_at(k + 1, idx / TB, idx % TB);
+                        zvn[idx] = v;
+                        if constexpr (DAE) lds[inAE + qi(xd + idx / TB, idx % TB)] = v;
+                        if (pred) put_ext(idx / TB, idx % TB, v);
+                    }
+                }
+                lds_barrier();
+                K0_PROF(3)
+                continue;
+            }
             const int s_ = e - 1;
             const bool final_stage = s_ + 1 == nstage;
             float c0 = 0.0f, c1 = 0.0f, c2 = 0.0f, c3 = 0.0f;

@@ -78,7 +78,24 @@ template <class S> __device__ inline float* msp_border(const S&) { return nullpt
 __device__ inline float* msp_border(const MspDev& s) { return s.border; }
 
 
-template <bool ACT, bool PRE, bool RK, bool SUB = false, bool LIN = false, bool PEV = false, bool AB = false, bool MS = false, bool PAR = false>
+// The coefficients of step k of the Adams-Bashforth 3 builds (Bd::ab3) for one trajectory column, from h0, h1, h2 = h_k, h_{k-1}, h_{k-2},
+// the step's restart flag R_k and `shallow` = R_{k-1} || h_{k-1} + h_{k-2} == 0 (depth 1).  One function for K0 and K5: the same
+// expressions on the same values, so K5's coefficients are K0's bit for bit (the objects are built without contraction).  The order of
+// operations is neural_dae.AB3._ab3_step's.  A restart step's c0 is h: the Euler predictor of its corrector.
+struct Ab3Coef { float c0, c1, c2; };
+__device__ __forceinline__ Ab3Coef ab3_coef(float h0, float h1, float h2, bool restart, bool shallow) {
+    const float half_rho = (h0 / h1) / 2.0f;                       // depth 1: AB2's step
+    const float g1 = h0 * h0 / 2.0f, g2 = h0 * h0 * h0 / 3.0f + h1 * g1, D = g2 / (h1 + h2);      // depth 2
+    const float p = g1 / h1, q = D / h1, u = D / h2;
+    Ab3Coef cf;
+    cf.c0 = restart ? h0 : (shallow ? h0 * (1.0f + half_rho) : h0 + p + q);
+    cf.c1 = restart ? 0.0f : (shallow ? -(h0 * half_rho) : -p - q - u);
+    cf.c2 = (restart || shallow) ? 0.0f : u;
+    return cf;
+}
+
+template <bool ACT, bool PRE, bool RK, bool SUB = false, bool LIN = false, bool PEV = false, bool AB = false, bool MS = false, bool PAR = false,
+          bool AB3 = false>
 struct GenericBuild {
     static constexpr bool act = ACT;      // the hidden-layer activation is a kernel argument (ActPair, psnode_act.h), not ELU(1)
     static constexpr bool pre = PRE;      // the hidden layers' pre-activations u are kept next to h (SiLU / GELU / Mish differentiate from u)
@@ -90,6 +107,9 @@ struct GenericBuild {
                                           // needs pev, whose per-column event index also serves a shared table through a column stride of 0)
     static constexpr bool ms = MS;        // multiple shooting: every MsDev::every-th grid point restarts from the dataset row (MsDev;
                                           // needs sub; not with lin, pev or ab)
+    static constexpr bool ab3 = AB3;      // three-step Adams-Bashforth with a predictor-corrector restart step: two previous slopes, per-column c0 / c1 / c2,
+                                          // and on restart steps a second DE stage (a DAE: behind a head evaluation of its own) on the rows of grid
+                                          // point k + 1 (AbDev; needs ab)
     static constexpr bool par = PAR;      // segments in parallel: the launch grid is tiles x chunks, workgroup (tile, c) runs the segments of time chunk c
                                           // alone (MspDev; needs ms)
     // The kernels' arguments behind the args struct, each a by-value parameter of its own: ActPair (act) | psnode_rk_tableau_f32 (rk) | Sub (sub).
@@ -143,6 +163,7 @@ using BuildPev = GenericBuild<true, true, true, true, false, true>;      // Buil
 using BuildAb = GenericBuild<true, true, true, true, false, true, true>;      // BuildPev's policy as Adams-Bashforth 2; one sub-step, a one-stage tableau
 using BuildMs = GenericBuild<true, true, true, true, false, false, false, true>;      // BuildSub's policy with multiple-shooting restarts; every substeps >= 1
 using BuildMsp = GenericBuild<true, true, true, true, false, false, false, true, true>;      // BuildMs's policy with the segments spread over workgroups: a tiles x chunks grid
-enum BuildId { kBuildElu1, kBuildAct, kBuildPre, kBuildRk, kBuildSub, kBuildLin, kBuildPev, kBuildAb, kBuildMs, kBuildMsp };      // what a call names its build with
+using BuildAb3 = GenericBuild<true, true, true, true, false, true, true, false, false, true>;      // BuildAb's policy as Adams-Bashforth 3 with the Heun restart step
+enum BuildId { kBuildElu1, kBuildAct, kBuildPre, kBuildRk, kBuildSub, kBuildLin, kBuildPev, kBuildAb, kBuildMs, kBuildMsp, kBuildAb3 };      // what a call names its build with
 
 }  // namespace psnode

@@ -17,6 +17,14 @@
         k_hi = ch.k_hi;
         last_chunk = blockIdx.y + 1 == gridDim.y;
     }
+    // (Bd::ab3 pins the grid length in scalar registers up here, in front of the first divergent loop: read where Bd::ab pins it, below,
+    //  the value reaches that place through both arms of the loop guard in a vector register, and the spills of the longer set-up in
+    //  front of the sweep then count as stored under partial EXEC)
+    [[maybe_unused]] long long T3 = 0;
+    if constexpr (Bd::ab3) {
+        const unsigned long long u = (unsigned long long)a.T;
+        T3 = (long long)(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(u >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)u));
+    }
     [[maybe_unused]] const size_t wg = Bd::par ? (size_t)blockIdx.y * gridDim.x + blockIdx.x : (size_t)blockIdx.x;
     const bool dae = a.dae != 0;
     const int xd = a.xd, zd = a.zd, vd = dae ? a.vd : 0, id = dae ? a.id : 0;
@@ -197,7 +205,8 @@
     // (the Adams-Bashforth build pins the grid length in scalar registers, as K0's sub-step builds do: left to the compiler the sweep's loop
     //  guard becomes a vector compare, and what it then parks in AGPRs in front of the loop counts as stored under partial EXEC)
     [[maybe_unused]] long long Tu = 0;
-    if constexpr (Bd::ab) {
+    if constexpr (Bd::ab3) Tu = T3;
+    else if constexpr (Bd::ab) {
         const unsigned long long u = (unsigned long long)a.T;
         Tu = (long long)(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(u >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)u));
     }
@@ -224,6 +233,15 @@
         if (ev_table_pt(sub)) { ev_sk = a.B; ev_sb = 1; }
         la_tm = a.t.p[(a.T >= 3 ? a.T - 3 : 0) * a.t.st + gb(tid % TB) * a.t.sb];      // (every lane, no branch: see the top of the step; read for k >= 1 only)
     }
+    // Adams-Bashforth 3 (Bd::ab3, on Bd::ab's policy): the DE's VJP of step k takes
+    //     phi_k = a_k g_{k+1} + c1_{k+1} g_{k+2} + c2_{k+2} g_{k+3} [+ h gamma],   g_k = w_k + g_{k+1} [+ gamma] + (df_k/dx_k)^T phi_k
+    // with a_k = h / 2 on a restart step, else c0_k, and gamma the x~ part of the corrector's VJP, run in front of the DE's on a restart step
+    // (below, behind (3a)).  g_{k+2} / g_{k+3} live in gks' slots 1 / 3, the per-column a_k, c1_{k+1}, c2_{k+2} and hr = (R_k ? h_k : 0) in
+    // dts, gks' slot 2 and ks' slots 0 / 1 (a one-stage build uses neither), x~ and gamma in xst's slots 1 / 2.  Step k computes ITS
+    // coefficients with K0's function on K0's values (ab3_coef: t[k-2 .. k+1], the event indices of steps k - 1 and k) and hands c1_k, c2_k
+    // on to the next two steps of the sweep in registers of the threads < TB: no forward recurrence.
+    [[maybe_unused]] float la_tmm = 0.0f, ab_c1n = 0.0f, ab_c2n = 0.0f, ab_c2nn = 0.0f;
+    if constexpr (Bd::ab3) la_tmm = a.t.p[(a.T >= 4 ? a.T - 4 : 0) * a.t.st + gb(tid % TB) * a.t.sb];
     // Multiple shooting (Bd::ms): the step that leaves grid point k > 0 with k % every == 0 started from the dataset row xtr[k] -- and a
     // DAE's DE read the head at that row.  Its stages are recomputed from there; neither its start adjoint nor the x part of that head's VJP
     // travels on.  Launch-uniform: ms_rem is k % every, counted down in a scalar register from one remainder taken in front of the sweep.
@@ -246,7 +264,25 @@
                               : (Bd::pev ? a.ev[k * a.B + gb(tid % TB)] : (a.ev ? a.ev[k] : -1));
         [[maybe_unused]] bool any_ev = false;
         if constexpr (Bd::pev) any_ev = __builtin_amdgcn_ballot_w64(ev >= 0) != 0;
-        if constexpr (Bd::ab) {
+        if constexpr (Bd::ab3) {
+            // (as the Adams-Bashforth 2 arm below: every lane runs the arithmetic, the stores are guarded)
+            const int ev_m = (a.ev && k >= 1) ? a.ev[(k - 1) * ev_sk + gb(tid % TB) * ev_sb] : -1;      // step k - 1's event, for R_{k-1}
+            const float h0 = la_tn - la_t, h1 = la_t - la_tm, h2 = la_tm - la_tmm;                   // h_k, h_{k-1}, h_{k-2}
+            const bool rs = k == 0 || ev >= 0 || h1 == 0.0f;
+            const bool rp = k <= 1 || ev_m >= 0 || h2 == 0.0f;
+            const Ab3Coef cf = ab3_coef(h0, h1, h2, rs, rp || h1 + h2 == 0.0f);
+            if (tid < TB) {
+                dts[tid] = rs ? h0 * 0.5f : cf.c0;
+                gks[2 * nx + tid] = ab_c1n;
+                ks[tid] = ab_c2nn;
+                ks[nx + tid] = rs ? h0 : 0.0f;
+            }
+            ab_c2nn = ab_c2n;
+            ab_c2n = cf.c2;
+            ab_c1n = cf.c1;
+            la_tm = la_tmm;
+            la_tmm = a.t.p[(k >= 3 ? k - 3 : 0) * a.t.st + gb(tid % TB) * a.t.sb];      // t[(k - 1) - 2], for the next step of the sweep
+        } else if constexpr (Bd::ab) {
             // (a thread < TB owns column tid: `ev`, `ev_n` are that column's.  Every lane runs the arithmetic -- the others on zeros, whose
             //  results nobody reads -- and only the stores are guarded: registers that live across steps are then written under full EXEC)
             const float h = la_tn - la_t, hm = la_t - la_tm;      // h_k, h_{k-1} (the latter read for k >= 1 only)
@@ -389,11 +425,83 @@
                 __syncthreads();
             }
         }
+        // (Bd::ab3) The corrector's VJP, where some column of the workgroup restarts with h != 0 (workgroup-uniform: each wave holds every
+        // column; a restart with h == 0 feeds it a zero cotangent).  f_k and x~ = x_k + h f_k are recomputed, then i~ = AE(x~; rows k + 1)
+        // for a DAE, then the DE at (x~; rows k + 1, i~) with the cotangent (h / 2) g_{k+1} -- zero in the columns that do not restart, so
+        // that they add nothing anywhere.  Its z | v part is ADDED to row k + 1 of grad_z / grad_v by the thread that wrote that row one
+        // step earlier (the last row: zeroed up front) and that alone has added to it since; the algebraic part goes through the head at
+        // x~; the x~ parts of both are gamma.  gext keeps the step's ext rows meanwhile, gic (free between (1) and (4)) i~'s adjoint.
+        if constexpr (Bd::ab3) {
+            if (__builtin_amdgcn_ballot_w64(ks[nx + tid % TB] != 0.0f) != 0) {
+                float* xp = xst + nx;          // x~
+                float* gam = xst + 2 * nx;     // gamma
+                de_input(xst);
+                if constexpr (REG) g_forward_reg(a, acts, qb, qo, rfw, ActCtx{act.de, upre});
+                else if constexpr (STR == 2) g_forward_str(a.de, a.fimg, acts, qb, qo, ActCtx{act.de, upre});
+                else g_forward(a.de, acts, wbuf, ActCtx{act.de, upre});
+                {
+                    const float* out = acts + a.de.act[a.de.L] * TP;
+                    TILE_LOOP(xd) xp[r * TP + c] = x0[r * TP + c] + ks[nx + c] * out[r * TP + c];
+                }
+                TILE_LOOP(ne) gext[r * TP + c] = ext[r * TP + c];
+                TILE_LOOP(nzv) {
+                    const long long b = gb(c);
+                    ext[r * TP + c] = r < zd ? a.z.p[(k + 1) * a.z.st + b * a.z.sb + r] : a.v.p[(k + 1) * a.v.st + b * a.v.sb + (r - zd)];
+                }
+                __syncthreads();
+                if (dae) {
+                    ae_input(xp, k + 1);
+                    if constexpr (STR >= 1) g_forward_str(a.ae, a.fimgA, acts, qb, qoA, ActCtx{act.ae, upre}); else g_forward(a.ae, acts, wbuf, ActCtx{act.ae, upre});
+                    const float* out = acts + a.ae.act[a.ae.L] * TP;
+                    TILE_LOOP(id) ext[(nzv + r) * TP + c] = out[r * TP + c];
+                    __syncthreads();
+                }
+                de_input(xp);
+                if constexpr (REG) g_forward_reg(a, acts, qb, qo, rfw, ActCtx{act.de, upre});
+                else if constexpr (STR == 2) g_forward_str(a.de, a.fimg, acts, qb, qo, ActCtx{act.de, upre});
+                else g_forward(a.de, acts, wbuf, ActCtx{act.de, upre});
+                TILE_LOOP(xd) dA[r * TP + c] = (ks[nx + c] * 0.5f) * gxc[r * TP + c];
+                __syncthreads();
+                const float* gu = REG ? g_vjp_reg<gg>(a, acts, dA, dB, gacc_l, tmg, qb, qo, rbw, ActCtx{act.de, upre})
+                                      : (STR == 2 ? g_vjp_str<gg>(a.de, a.timg, acts, dA, dB, gacc_l, tmg, qb, qo, ActCtx{act.de, upre})
+                                                  : g_vjp<gg>(a.de, acts, dA, dB, gacc_l, gacc_g, wbuf, ActCtx{act.de, upre}));
+                TILE_LOOP(n) {      // (ext's corrector rows are spent: it stages their adjoints for the threads that own the rows)
+                    const float gs = gu[(n + r) * TP + c] + gu[(2 * n + r) * TP + c];
+                    ga0s[r * TP + c] += gu[r * TP + c] - gu[(n + r) * TP + c];
+                    if (r < xd) gam[r * TP + c] = gs; else ext[(r - xd) * TP + c] = gs;
+                }
+                __syncthreads();
+                TILE_LOOP(nzv) {
+                    if (!on(c)) continue;
+                    const bool isz = r < zd;
+                    float* dst = isz ? a.gz : a.gv;
+                    if (dst) dst[((k + 1) * a.B + b0 + c) * (isz ? zd : vd) + (isz ? r : r - zd)] += ext[r * TP + c];
+                }
+                TILE_LOOP(id) gic[r * TP + c] = ext[(nzv + r) * TP + c];
+                __syncthreads();
+                if (dae) ae_vjp(xp, k + 1, -1, gic, gam);
+                TILE_LOOP(ne) ext[r * TP + c] = gext[r * TP + c];
+                __syncthreads();
+            }
+        }
         // (3b) stages backwards
         TILE_LOOP(xd) {
             const float g1 = gxc[r * TP + c];
             gx0[r * TP + c] = g1;
-            if constexpr (Bd::ab) {      // phi_k; g_{k+2}'s slot is unwritten at the first step of the sweep, where c1 is 0
+            if constexpr (Bd::ab3) {      // phi_k; the history's slots are unwritten at the first steps of the sweep, where c1 / c2 are 0
+                const float c1n = gks[2 * nx + c], c2nn = ks[c], hr = ks[nx + c];
+                float phi = dts[c] * g1;
+                if (c1n != 0.0f) phi = phi + c1n * gks[nx + r * TP + c];
+                if (c2nn != 0.0f) phi = phi + c2nn * gks[3 * nx + r * TP + c];
+                if (hr != 0.0f) {
+                    const float gm = xst[2 * nx + r * TP + c];
+                    phi = phi + hr * gm;
+                    gx0[r * TP + c] = g1 + gm;
+                }
+                gks[r * TP + c] = phi;
+                gks[3 * nx + r * TP + c] = gks[nx + r * TP + c];      // g_{k+2} -> g_{k+3}, g_{k+1} -> g_{k+2} for step k - 1: this thread's alone
+                gks[nx + r * TP + c] = g1;
+            } else if constexpr (Bd::ab) {      // phi_k; g_{k+2}'s slot is unwritten at the first step of the sweep, where c1 is 0
                 const float c1n = gks[2 * nx + c];
                 float phi = dts[c] * g1;
                 if (c1n != 0.0f) phi = phi + c1n * gks[nx + r * TP + c];

@@ -11,8 +11,8 @@
 //   workspace | [K0, in dispatch] T, B, LDS fit of the build.
 //   _msp: the _ms family's sequence with psnode_segment_groups_f32 in the segments struct's place; more than 65535 chunks (the grid's second
 //   dimension) are PSNODE_ERR_UNSUPPORTED with the route; [K5] its workspace is its own layout's (gbwd_msp_layout).
-//   _tf [K5; K0 has no such wrapper]: flags == 0 is the plain entry point, in front of all of it.  _rk and _ab do not read `method` (K0's copy
-//   of the args carries EULER); _pev's event_idx is the [T-1, B] table (event-less calls take the other families), _ab's may be NULL.
+//   _tf [K5; K0 has no such wrapper]: flags == 0 is the plain entry point, in front of all of it.  _rk, _ab and _ab3 do not read `method` (K0's copy
+//   of the args carries EULER); _pev's event_idx is the [T-1, B] table (event-less calls take the other families), _ab's and _ab3's may be NULL.
 //   [K0] route (k0_route_ok): kernel AUTO / GENERIC and no training side outputs -- the _act family looks at save_act alone (a lone
 //   save_xstage is fill_*'s status); _ms needs the DAE's x view (the restarts read its rows).  A call without a tableau leaves a bad method
 //   to fill_*, its query refuses it in front; _act_supported with an ELU(1) pair answers from method and dims alone.
@@ -30,7 +30,7 @@
 
 namespace psnode {
 
-enum Family { kFamTf, kFamAct, kFamRk, kFamSub, kFamLin, kFamPev, kFamAb, kFamMs, kFamMsp };
+enum Family { kFamTf, kFamAct, kFamRk, kFamSub, kFamLin, kFamPev, kFamAb, kFamMs, kFamMsp, kFamAb3 };
 // the tableau: no argument, `method` is read | NULL is PSNODE_ERR_NULL | NULL is the args' method as one | no argument, always one stage
 enum Tab { kTabNone, kTabRequired, kTabOrMethod, kTabOneStage };
 // the sub-steps struct: no argument | NULL is PSNODE_ERR_NULL | NULL is one sub-step
@@ -58,13 +58,14 @@ constexpr FamilyRow kFamilies[] = {
     /* _ab  */ {kBuildAb,   false, kTabOneStage, kSubNone,     false,  false, false, true,  true,  true,  false},      // (a multistep history has no teacher-forced form)
     /* _ms  */ {kBuildMs,   false, kTabOrMethod, kSubOrOne,    false,  true,  false, true,  true,  true,  false},      // (every teacher-forced step restarts already)
     /* _msp */ {kBuildMsp,  false, kTabOrMethod, kSubOrOne,    false,  true,  false, true,  true,  true,  false, true},      // (_ms over a tiles x chunks grid)
+    /* _ab3 */ {kBuildAb3,  false, kTabOneStage, kSubNone,     false,  false, false, true,  true,  true,  false},      // (_ab's row: the same arguments, checks and fit)
 };
 struct CallOpts {      // what a call carries behind its args; a family's wrappers leave what it does not take at NULL / 0
     const psnode_act_f32 *de_act, *ae_act;
     const psnode_rk_tableau_f32* tab;
     const psnode_substeps_f32* sub;
     const psnode_segments_f32* seg;
-    int per_trajectory;      // _ab: a non-NULL event_idx is the [T-1, B] table (else the shared [T-1])
+    int per_trajectory;      // _ab, _ab3: a non-NULL event_idx is the [T-1, B] table (else the shared [T-1])
     const psnode_segment_groups_f32* grp;      // _msp: in seg's place
     // what a family with segments reads, from whichever of the two structs it takes
     bool has_seg() const { return seg || grp; }

@@ -84,8 +84,16 @@ class Tableau:
 AB2 = "ab2"      # the `method` value of two-step Adams-Bashforth (neural_dae.AB2): the _ab entry points of K0 / K5, no other kernel
 
 
+AB3 = "ab3"      # three-step Adams-Bashforth with a predictor-corrector restart step (neural_dae.AB3): the _ab3 entry points of K0 / K5
+
+
 def is_ab(method) -> bool:
-    return isinstance(method, str) and method == AB2
+    return isinstance(method, str) and method in (AB2, AB3)
+
+
+def ab_order(method) -> int:
+    """2 for "ab2", 3 for "ab3" (and 2 for every method that is no Adams-Bashforth method, where nothing reads it)."""
+    return 3 if isinstance(method, str) and method == AB3 else 2
 
 
 def method_info(method):
@@ -214,6 +222,7 @@ FAMILIES = {
     "lin": Family(tab=True, sub=True, x_sub=True),
     "pev": Family(tab=True, sub=True, x_sub=True, workspace="rk"),
     "ab": Family(pt=True, x_sub=True, workspace="rk"),
+    "ab3": Family(pt=True, x_sub=True, workspace="rk"),
     "ms": Family(tab=True, sub=True, seg=True, x_sub=True, workspace="rk"),
     "msp": Family(tab=True, sub=True, seg=True, x_sub=True, workspace="own", par=True),
 }
@@ -273,7 +282,8 @@ class GenericOpts:
     method_id / stages: what the args struct and the saved rows need of `method` (`method_info`); per_trajectory: the call's event table
     is [T-1, B], every trajectory jumps at its own steps (only a call that HAS events carries it: `has_events`); ab: the method is two-step
     Adams-Bashforth ("ab2") -- the last option in the naming order; never together with a Tableau, sub-steps or interpolated
-    externals (the solver's constructor refuses them; here a ValueError), with per_trajectory it stays the family "ab"; segment: None, or
+    externals (the solver's constructor refuses them; here a ValueError), with per_trajectory it stays the family "ab"; the value 3 is
+    three-step Adams-Bashforth ("ab3", `ab_order`): the family "ab3", the same rules and refusals in its own words; segment: None, or
     an int w >= 1 -- multiple shooting, grid point k > 0 with k % w == 0 restarts from the dataset row (the family "ms", the sixth option in
     the naming order, in front of AB2, which refuses it; next to interpolated externals or per-trajectory events "none": no kernel);
     segment_parallel: None, or the segments per time chunk (an int >= 1, `resolve_segment_parallel`) of a call whose segments run side by
@@ -286,11 +296,17 @@ class GenericOpts:
     stages: int = 1
     per_trajectory: bool = False
     segment: Optional[int] = None
-    ab: bool = False
+    ab: bool = False      # (or 3: Adams-Bashforth 3, `ab_order`)
     # (init-only: behind `ab` in the constructor and an attribute of the value like every option, but no entry of dataclasses.fields() --
     #  the recorded field lists end with ab, family; the family, which is compared, tells "ms" from "msp")
     segment_parallel: dataclasses.InitVar[Optional[int]] = None
     family: str = dataclasses.field(init=False)
+
+    @property
+    def ab_order(self) -> int:
+        """2, or 3 where `ab` is 3: three-step Adams-Bashforth ("ab3"), the family "ab3" in "ab"'s place.  (`ab` itself carries it -- False,
+        True for "ab2", 3 for "ab3" -- because the recorded lists of fields and of constructor arguments end with ab / ab, segment_parallel.)"""
+        return 3 if self.ab == 3 else 2
 
     def __post_init__(self, segment_parallel=None):
         """Validates substeps and externals, and names the entry-point family: "ab" (two-step Adams-Bashforth, with or without
@@ -304,6 +320,12 @@ class GenericOpts:
             raise ValueError(f"per_trajectory must be a bool, got {self.per_trajectory!r}")
         if self.segment is not None and (isinstance(self.segment, bool) or not isinstance(self.segment, int) or self.segment < 1):
             raise ValueError(f"segment must be None or an int >= 1, got {self.segment!r}")
+        if self.ab not in (False, True, 3):
+            raise ValueError(f"ab must be False, True (Adams-Bashforth 2) or 3 (Adams-Bashforth 3), got {self.ab!r}")
+        ab_order = self.ab_order
+        if self.ab and ab_order == 3 and self.segment is not None:
+            raise ValueError("Adams-Bashforth 3 carries the previous slopes from step to step: a multiple-shooting restart (segment=) has no "
+                             f"form here (got segment={self.segment!r})")
         if self.ab and self.segment is not None:
             raise ValueError("Adams-Bashforth 2 carries the previous slope from step to step: a multiple-shooting restart (segment=) has no "
                              f"form here (got segment={self.segment!r})")
@@ -314,6 +336,11 @@ class GenericOpts:
                              f"(segment={self.segment!r})")
         if self.segment is not None:
             fam = "none" if (is_linear(self.externals) or self.per_trajectory) else ("ms" if sp is None else "msp")
+        elif self.ab and ab_order == 3:
+            if self.substeps != 1 or is_linear(self.externals) or self.tab is not None:
+                raise ValueError("Adams-Bashforth 3 reads the right-hand side at grid points only: substeps != 1 and externals='linear' would "
+                                 f"need inputs between the dataset rows (got substeps={self.substeps}, externals={self.externals!r})")
+            fam = "ab3"
         elif self.ab:
             if self.substeps != 1 or is_linear(self.externals) or self.tab is not None:
                 raise ValueError("Adams-Bashforth 2 reads the right-hand side at grid points only: substeps != 1 and externals='linear' would "
@@ -337,7 +364,7 @@ class GenericOpts:
     def of(method, acts: tuple, substeps: int = 1, externals: str = "hold", per_trajectory: bool = False, segment=None,
            segment_parallel=None) -> "GenericOpts":
         method_id, stages, tab = method_info(method)
-        return GenericOpts(acts, tab, substeps, externals, method_id, stages, per_trajectory, segment, is_ab(method), segment_parallel)
+        return GenericOpts(acts, tab, substeps, externals, method_id, stages, per_trajectory, segment, 3 if ab_order(method) == 3 else is_ab(method), segment_parallel)
 
     def chunks(self, T: int) -> Optional[int]:
         """The time chunks of a record of T grid points under these options (None without segment_parallel): as `segment_parallel=` of a
@@ -387,7 +414,7 @@ class GenericOpts:
             return "per-trajectory events (per_trajectory=True) run"
         if self.segment is not None:
             return f"multiple-shooting segments (segment={self.segment}) run"
-        return "two-step Adams-Bashforth (AB2) runs"
+        return "three-step Adams-Bashforth (AB3) runs" if self.ab_order == 3 else "two-step Adams-Bashforth (AB2) runs"
 
     def require_generic(self, what: str, kernel: str, saved: bool, teacher_forced: bool = False):
         """The options run on the generic kernels only: UnsupportedShapeError, naming the first option in the order act, tableau, sub-steps,
@@ -417,6 +444,9 @@ class GenericOpts:
         if self.segment is not None and teacher_forced:
             raise ValueError(f"{what}: segment={self.segment} and input_true_x / input_true_i exclude each other (every teacher-forced step "
                              "restarts from the dataset already)")
+        if self.ab and self.ab_order == 3 and teacher_forced:
+            raise ValueError(f"{what}: Adams-Bashforth 3 has no teacher-forced form -- every teacher-forced step starts from a dataset row, "
+                             "so the previous slopes a multistep method carries are undefined")
         if self.ab and teacher_forced:
             raise ValueError(f"{what}: Adams-Bashforth 2 has no teacher-forced form -- every teacher-forced step starts from a dataset row, "
                              "so the previous slope a multistep method carries is undefined")
@@ -439,6 +469,9 @@ class GenericOpts:
         if self.segment is not None:
             raise _lib.UnsupportedShapeError(f"{what}: multiple-shooting segments (segment={self.segment}) run on the generic kernels K0 / K5 only "
                                              "(kernel 'auto' / 'generic', no saved rows); this entry point runs free from the first row to the last")
+        if self.ab and self.ab_order == 3:
+            raise _lib.UnsupportedShapeError(f"{what}: three-step Adams-Bashforth (AB3) runs on the generic kernels K0 / K5 only "
+                                             "(kernel 'auto' / 'generic', no saved rows); this entry point carries euler / midpoint / rk4")
         if self.ab:
             raise _lib.UnsupportedShapeError(f"{what}: two-step Adams-Bashforth (AB2) runs on the generic kernels K0 / K5 only "
                                              "(kernel 'auto' / 'generic', no saved rows); this entry point carries euler / midpoint / rk4")

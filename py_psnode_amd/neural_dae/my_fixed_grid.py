@@ -287,3 +287,143 @@ class AB2(FixedGridODESolver):
             cur_i = i_func(xt=cur_x, zt=z[k + 1], vt=v[k + 1], all_initial=all_initial)
             xs[k + 1], is_[k + 1] = cur_x, cur_i
         return xs, is_
+
+
+class AB3(AB2):
+    """Three-step Adams-Bashforth with a predictor-corrector restart step: like AB2 the right-hand side is read at grid points only, so it
+    is third order for ODE and DAE alike on sampled inputs, at one DE evaluation per step away from the restarts.  Step k, per trajectory,
+    h_k = t[k+1] - t[k], f_k the DE at the inputs AB2's / Euler's stage reads.  Restart flag and depth (both local):
+        R_k: k == 0, an event fires at step k (per trajectory under per_trajectory events), or h_{k-1} == 0
+        d_k = 0 if R_k;  1 if R_{k-1} or h_{k-1} + h_{k-2} == 0;  2 otherwise
+    d_k = 2, with h0, h1, h2 = h_k, h_{k-1}, h_{k-2}:  g1 = h0^2 / 2, g2 = h0^3 / 3 + h1 g1, D = g2 / (h1 + h2),
+        c0 = h0 + g1 / h1 + D / h1,  c1 = -g1 / h1 - D / h1 - D / h2,  c2 = D / h2;   x_{k+1} = x_k + c0 f_k + c1 f_{k-1} + c2 f_{k-2}
+        (23/12, -16/12, 5/12 times h on a uniform grid)
+    d_k = 1: AB2's step.   d_k = 0, the restart step, a Heun predictor-corrector on grid rows only:
+        x~ = x_k + h f_k;  f~ the DE at (x~; rows k + 1 of z | v, never jumped; in a DAE i~ = AE(x~; z[k+1], v[k+1]), an evaluation of its
+        own and no output);  x_{k+1} = x_k + (h / 2)(f_k + f~).  The slope kept for the history is f_k, never f~.
+    Heads at grid points, outputs and the event-time head are AB2's.  Written once (`_ab3_step`), in the tensors' dtype, uncontracted;
+    the generic kernels K0 / K5 (kernel 'auto' / 'generic') use the same order of operations.  Where only some trajectories of a batch
+    restart, the walk evaluates the corrector for all of them and selects.  `_step_func` is the Euler step, as in AB2.  No sub-steps, no
+    interpolated externals, no segments, no teacher forcing -- ValueError.  The clock gets no gradient.  Stability: the real-axis interval
+    is |h lambda| < 6/11, about half of AB2's."""
+    order = 3
+    method = _fused.AB3
+
+    def __init__(self, **kw):
+        if kw.get("substeps", 1) != 1:
+            raise ValueError("AB3 reads the right-hand side at grid points only: substeps != 1 would need inputs between the dataset rows "
+                             f"(got substeps={kw.get('substeps')!r})")
+        if kw.get("externals", "hold") != "hold":
+            raise ValueError("AB3 reads the right-hand side at grid points only: externals='linear' would need inputs between the dataset rows "
+                             f"(got externals={kw.get('externals')!r})")
+        if kw.get("segment") is not None:
+            raise ValueError("AB3 carries the previous slopes from step to step: a multiple-shooting restart (segment=) has no form here "
+                             f"(got segment={kw.get('segment')!r})")
+        FixedGridODESolver.__init__(self, **kw)
+
+    def _generic_only_ok(self, what, acts, per_trajectory=False) -> bool:
+        if self.kernel in ("auto", "generic"):
+            return True
+        if self.fused == "require":
+            raise _fused._lib.UnsupportedShapeError(f"{what}: kernel={self.kernel!r} has no form for three-step Adams-Bashforth: AB3 runs on "
+                                                    "the generic kernels (kernel 'auto' / 'generic')")
+        return False
+
+    @staticmethod
+    def _no_teacher_forcing(what, forced):
+        if forced:
+            raise ValueError(f"{what}: AB3 has no teacher-forced form -- every teacher-forced step starts from a dataset row, so the "
+                             "previous slopes a multistep method carries are undefined")
+
+    @staticmethod
+    def _ab3_step(x, f, h0, f1, h1, f2, h2, restart, shallow, f_corr):
+        """x_{k+1} of the class docstring.  f1, h1 / f2, h2: the slopes and steps of k - 1 / k - 2 (anything finite where the depth does not
+        read them); restart: R_k, shallow: d_k <= 1, both bool [B, 1]; f_corr: f~, or None where no trajectory restarts."""
+        one = torch.ones_like(h0)
+        deep = ~(restart | shallow)
+        s1 = torch.where(restart, one, h1)
+        s2 = torch.where(deep, h2, one)
+        s12 = torch.where(deep, h1 + h2, one)
+        half_rho = (h0 / s1) / 2
+        x_ab2 = x + (h0 * (1 + half_rho)) * f + (-(h0 * half_rho)) * f1
+        g1 = h0 * h0 / 2
+        g2 = h0 * h0 * h0 / 3 + s1 * g1
+        D = g2 / s12
+        c0 = h0 + g1 / s1 + D / s1
+        c1 = -g1 / s1 - D / s1 - D / s2
+        c2 = D / s2
+        out = torch.where(deep, x + c0 * f + c1 * f1 + c2 * f2, x_ab2)
+        if f_corr is None:
+            return out
+        return torch.where(restart, x + (h0 * 0.5) * (f + f_corr), out)
+
+    def _flags(self, k, h, h1, h2, r_prev, hit):
+        """(R_k, d_k <= 1) as bool [B, 1] from this step's hit (None, True or bool [B, 1]) and the carried steps and flag."""
+        if k == 0 or hit is True:
+            restart = torch.ones_like(h, dtype=torch.bool)
+        else:
+            restart = h1 == 0
+            if hit is not None:
+                restart = restart | hit
+        shallow = restart | r_prev | ((h1 + h2) == 0)
+        return restart, shallow
+
+    def _walk_ode(self, x_func, t, x, z, all_initial, event_fn, jump_change_fn, input_true_x, x_init=None):
+        self._no_teacher_forcing("integrate_ODE", input_true_x)
+        xs = torch.zeros(x.shape, dtype=x.dtype, device=x.device)
+        cur = x[0] if x_init is None else x_init
+        xs[0] = cur
+        f1 = f2 = None
+        for k in range(t.shape[0] - 1):
+            t0, zk, hit = t[k], z[k], None
+            if event_fn is not None and event_fn(t0) == True:  # noqa: E712 (callbacks may return tensors)
+                zk = jump_change_fn(t0, zk)
+                hit = self._restart_mask(event_fn, t0)
+            h = t[k + 1] - t0
+            f = x_func(t0=t0, xt=cur, zt=zk, all_initial=all_initial)
+            if f1 is None:
+                f1 = f2 = torch.zeros_like(f)
+                h1 = h2 = torch.zeros_like(h)
+                r_prev = torch.ones_like(h, dtype=torch.bool)
+            restart, shallow = self._flags(k, h, h1, h2, r_prev, hit)
+            f_corr = None
+            if bool(restart.any()):
+                f_corr = x_func(t0=t[k + 1], xt=cur + h * f, zt=z[k + 1], all_initial=all_initial)
+            cur = self._ab3_step(cur, f, h, f1, h1, f2, h2, restart, shallow, f_corr)
+            f2, h2, f1, h1, r_prev = f1, h1, f, h, restart
+            xs[k + 1] = cur
+        return xs
+
+    def _walk_dae(self, x_init, x_func, i_func, t, x, z, v, i, all_initial, event_fn, jump_change_fn, input_true_x, input_true_i):
+        self._no_teacher_forcing("integrate_DAE", input_true_x or input_true_i)
+        cur_x = x_init
+        cur_i = i_func(xt=cur_x, zt=z[0], vt=v[0], all_initial=all_initial)
+        x_shape = (*x.shape[0:2], x_init.shape[-1]) if x.shape[-1] == 0 else x.shape
+        xs = torch.zeros(x_shape, dtype=x_init.dtype if x.shape[-1] == 0 else x.dtype, device=x.device)
+        is_ = torch.zeros(i.shape, dtype=i.dtype, device=i.device)
+        xs[0], is_[0] = cur_x, cur_i
+        f1 = f2 = None
+        for k in range(t.shape[0] - 1):
+            t0, zk, vk, hit = t[k], z[k], v[k], None
+            if event_fn is not None and event_fn(t0) == True:  # noqa: E712
+                zk, vk = jump_change_fn(t0, zk, vk)
+                hit = self._restart_mask(event_fn, t0)
+                head = i_func(xt=cur_x, zt=zk, vt=vk, all_initial=all_initial)
+                cur_i = head if hit is True else torch.where(hit, head, cur_i)      # (per trajectory: the hit ones take the event-time head)
+            h = t[k + 1] - t0
+            f = x_func(t0=t0, xt=cur_x, zt=zk, vt=vk, it=cur_i, all_initial=all_initial)
+            if f1 is None:
+                f1 = f2 = torch.zeros_like(f)
+                h1 = h2 = torch.zeros_like(h)
+                r_prev = torch.ones_like(h, dtype=torch.bool)
+            restart, shallow = self._flags(k, h, h1, h2, r_prev, hit)
+            f_corr = None
+            if bool(restart.any()):
+                x_pred = cur_x + h * f
+                i_pred = i_func(xt=x_pred, zt=z[k + 1], vt=v[k + 1], all_initial=all_initial)
+                f_corr = x_func(t0=t[k + 1], xt=x_pred, zt=z[k + 1], vt=v[k + 1], it=i_pred, all_initial=all_initial)
+            cur_x = self._ab3_step(cur_x, f, h, f1, h1, f2, h2, restart, shallow, f_corr)
+            f2, h2, f1, h1, r_prev = f1, h1, f, h, restart
+            cur_i = i_func(xt=cur_x, zt=z[k + 1], vt=v[k + 1], all_initial=all_initial)
+            xs[k + 1], is_[k + 1] = cur_x, cur_i
+        return xs, is_

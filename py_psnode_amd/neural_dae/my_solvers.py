@@ -34,7 +34,7 @@ def _autograd():
 
 class FixedGridODESolver(metaclass=abc.ABCMeta):
     order: int
-    method = ""        # "euler" | "midpoint" | "rk4", a fused.Tableau (my_fixed_grid.ExplicitRK) or "ab2" (my_fixed_grid.AB2): the formula the fused kernels run
+    method = ""        # "euler" | "midpoint" | "rk4", a fused.Tableau (my_fixed_grid.ExplicitRK), "ab2" (my_fixed_grid.AB2) or "ab3" (my_fixed_grid.AB3): the formula the fused kernels run
 
     def __init__(self, step_size=None, grid_constructor=None, interp="linear", substeps=1, externals="hold", segment=None,
                  segment_parallel=None):
