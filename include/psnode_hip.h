@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define PSNODE_ABI_VERSION 10    /* 10 also carries the additive psnode_act_f32 / *_act_*, psnode_rk_tableau_f32 / *_rk_*, psnode_substeps_f32 / *_sub_*, *_lin_*, *_pev_* / psnode_event_table_pt_f32, *_ab_* and *_ab3_* entry points (end of this file), and psnode_loss_fn_f32 / psnode_masked_loss_* / psnode_loss_per_sample_f32 (next to psnode_masked_mse_f32) */
+#define PSNODE_ABI_VERSION 10    /* 10 also carries the additive psnode_act_f32 / *_act_*, psnode_rk_tableau_f32 / *_rk_*, psnode_substeps_f32 / *_sub_*, *_lin_*, *_pev_* / psnode_event_table_pt_f32, *_ab_*, *_ab3_* and *_lag_* / psnode_ext_stencil_f32 entry points (end of this file), and psnode_loss_fn_f32 / psnode_masked_loss_* / psnode_loss_per_sample_f32 (next to psnode_masked_mse_f32) */
 #define PSNODE_MAX_LAYERS 8      /* Linear layers per MLP */
 #define PSNODE_MAX_WIDTH 1024    /* widest layer OUTPUT the kernels accept */
 #define PSNODE_MAX_IN_WIDTH 2048 /* widest first-layer INPUT (the latent DE of DAE_02 at --hidden 128 is 12 x 128 = 1536 wide) */
@@ -1027,6 +1027,54 @@ int32_t psnode_ode_backward_ab3_f32(const psnode_ode_bwd_args_f32* args, const p
 int32_t psnode_dae_backward_ab3_supported(const psnode_dae_bwd_tf_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act);
 int32_t psnode_dae_backward_ab3_f32(const psnode_dae_bwd_tf_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
                                     int32_t per_trajectory, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- Four-point Lagrange interpolation of z | v inside every grid interval on the generic kernels (additive to ABI 10; DESIGN.md
+ * "Lagrange externals on K0 / K5").  The _lin family with another interpolant: stage s of sub-step j of interval k reads, per trajectory
+ * and per column of z | v,
+ *     w(theta) = sum_{m < q} l_m(off + theta) node_{s+m},   l_m(u) = prod_{r != m, r < q} (u - r) / (m - r),   theta = (j + c_s) / substeps,
+ * the polynomial through q = 2 .. 4 consecutive dataset rows s .. s + q - 1, taken as equally spaced, with s = k - off.  Node s is the
+ * jumped row (z_jump / v_jump of event_idx[s]) where event_idx[s] >= 0, every other node the dataset row.  At theta = 0 and 1 the weights
+ * are exactly 0 / 1.  q and off come from the stencil table, one code byte per grid interval and trajectory:
+ *     psnode_ext_stencil_f32 table[(T - 1) * B], row-major [T-1, B];   code = off | (q << 2),   off = code & 3,   q = (code >> 2) & 7.
+ * The table's author (py_psnode_amd.fused.lagrange_stencils) cuts every trajectory's record into pieces -- maximal runs of intervals with
+ * t[k+1] > t[k] and no event step inside -- and gives interval k of piece [a, e] q = min(4, e - a + 1), s = clamp(k - 1, a, e - q + 1); an
+ * interval with t[k+1] <= t[k] is a piece of its own (q = 2, off = 0).  A NULL table is one piece 0 .. T - 1 for every trajectory:
+ * q = min(4, T), s = clamp(k - 1, 0, T - q).  The kernels clamp q to 2 .. min(4, T) and s to 0 .. T - q, so no byte makes them read
+ * outside rows 0 .. T - 1.  A backward call adds l_m(u) times a stage's external adjoint to row s + m of grad_z / grad_v (to the jump
+ * gradient of event_idx[s] for a jumped node s), by the thread that owns the element: no atomics, bitwise repeatable; it zeroes every
+ * row of grad_z / grad_v / grad_z_jump / grad_v_jump itself.  The clock gets no gradient.
+ * Everything else -- h, sub-steps, tableau, activations, teacher forcing, the heads, x_sub, the statuses and their order, the workspaces --
+ * is the _lin family's, prototype for prototype plus the table; psnode_dae_backward_lag_workspace_size is the family's workspace query
+ * (bytes; what psnode_dae_backward_lin_workspace_bytes is to _lin). */
+typedef int8_t psnode_ext_stencil_f32;
+#define PSNODE_STENCIL_CODE(off, q) ((psnode_ext_stencil_f32)((off) | ((q) << 2)))
+#define PSNODE_STENCIL_OFF(code) ((code) & 3)
+#define PSNODE_STENCIL_Q(code) (((code) >> 2) & 7)
+int32_t psnode_ode_integrate_lag_supported(const psnode_ode_args_f32* args, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
+                                           const psnode_substeps_f32* sub, const psnode_ext_stencil_f32* stencil);
+int32_t psnode_ode_integrate_lag_f32(const psnode_ode_args_f32* args, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
+                                     const psnode_substeps_f32* sub, const psnode_ext_stencil_f32* stencil, void* workspace,
+                                     size_t workspace_bytes, void* stream);
+int32_t psnode_dae_integrate_lag_supported(const psnode_dae_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                           const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub,
+                                           const psnode_ext_stencil_f32* stencil);
+int32_t psnode_dae_integrate_lag_f32(const psnode_dae_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                     const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, const psnode_ext_stencil_f32* stencil,
+                                     void* workspace, size_t workspace_bytes, void* stream);
+int32_t psnode_ode_backward_lag_supported(const psnode_ode_bwd_args_f32* args, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
+                                          const psnode_substeps_f32* sub, const psnode_ext_stencil_f32* stencil);
+int32_t psnode_ode_backward_lag_f32(const psnode_ode_bwd_args_f32* args, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
+                                    const psnode_substeps_f32* sub, const psnode_ext_stencil_f32* stencil, void* workspace,
+                                    size_t workspace_bytes, void* stream);
+int32_t psnode_dae_backward_lag_supported(const psnode_dae_bwd_tf_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                          const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub,
+                                          const psnode_ext_stencil_f32* stencil);
+size_t psnode_dae_backward_lag_workspace_size(const psnode_dae_bwd_tf_args_f32* args, const psnode_act_f32* de_act,
+                                              const psnode_act_f32* ae_act, const psnode_rk_tableau_f32* tab,
+                                              const psnode_substeps_f32* sub, const psnode_ext_stencil_f32* stencil);
+int32_t psnode_dae_backward_lag_f32(const psnode_dae_bwd_tf_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                    const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, const psnode_ext_stencil_f32* stencil,
+                                    void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

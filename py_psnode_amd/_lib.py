@@ -41,6 +41,8 @@ ABI_VERSION = 10         # == PSNODE_ABI_VERSION of include/psnode_hip.h (2: rou
                          #     points -- per-trajectory events (an event table [T-1, B]) on K0 / K5;
                          #     additive, same version: the psnode_{ode,dae}_{integrate,backward}_ab_* entry points -- two-step
                          #     Adams-Bashforth on K0 / K5;
+                         #     additive, same version: the psnode_{ode,dae}_{integrate,backward}_lag_* entry points -- z | v interpolated by the
+                         #     polynomial through the up to four neighbouring dataset rows (a stencil table int8 [T-1, B]) on K0 / K5;
                          #     additive, same version: the psnode_{ode,dae}_{integrate,backward}_ab3_* entry points -- three-step
                          #     Adams-Bashforth with a predictor-corrector restart step on K0 / K5;
                          #     additive, same version: psnode_segments_f32 and the psnode_{ode,dae}_{integrate,backward}_ms_* entry points --
@@ -92,6 +94,9 @@ EXPORTS = (
     "psnode_ode_integrate_ab_supported", "psnode_ode_integrate_ab_f32", "psnode_dae_integrate_ab_supported", "psnode_dae_integrate_ab_f32",
     "psnode_ode_backward_ab_supported", "psnode_ode_backward_ab_f32",
     "psnode_dae_backward_ab_supported", "psnode_dae_backward_ab_f32",
+    "psnode_ode_integrate_lag_supported", "psnode_ode_integrate_lag_f32", "psnode_dae_integrate_lag_supported", "psnode_dae_integrate_lag_f32",
+    "psnode_ode_backward_lag_supported", "psnode_ode_backward_lag_f32",
+    "psnode_dae_backward_lag_supported", "psnode_dae_backward_lag_workspace_size", "psnode_dae_backward_lag_f32",
     "psnode_ode_integrate_ab3_supported", "psnode_ode_integrate_ab3_f32", "psnode_dae_integrate_ab3_supported", "psnode_dae_integrate_ab3_f32",
     "psnode_ode_backward_ab3_supported", "psnode_ode_backward_ab3_f32",
     "psnode_dae_backward_ab3_supported", "psnode_dae_backward_ab3_f32",
@@ -365,10 +370,11 @@ def load():
             if fam in ("plain", "none") or (fam == "tf" and stem != "dae_backward"):
                 continue
             query = [ptr(DaeBwdTfArgsF32 if stem == "dae_backward" and f.tf_args else args_t)] + [ptr(ActF32)] * (n_act if f.acts else 0) + \
-                    [ptr(RkTableauF32)] * f.tab + [ptr(SubstepsF32)] * f.sub + [ptr(SegmentGroupsF32 if f.par else SegmentsF32)] * f.seg
+                    [ptr(RkTableauF32)] * f.tab + [ptr(SubstepsF32)] * f.sub + [ptr(SegmentGroupsF32 if f.par else SegmentsF32)] * f.seg + \
+                    [c_void_p] * f.stencil      # (the device pointer of the int8 [T-1, B] stencil table, or NULL)
             protos = {"supported": (c_int32, query), "f32": (c_int32, query + [c_int32] * f.pt + [c_void_p, c_size_t, c_void_p])}
-            if stem == "dae_backward" and f.workspace == "own" and not f.par:
-                protos["workspace_bytes"] = (c_size_t, query)
+            if stem == "dae_backward" and f.workspace == "own" and not f.par:      # (the family with a stencil table names its query _workspace_size)
+                protos["workspace_size" if f.stencil else "workspace_bytes"] = (c_size_t, query)
             if f.par and stem in ("ode_backward", "dae_backward"):      # (both directions of the family size their own workspace)
                 protos["workspace_size"] = (c_size_t, query)
             for kind, (restype, argtypes) in protos.items():

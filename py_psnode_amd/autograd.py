@@ -65,7 +65,7 @@ def ode_training_supported(method, layers, x_dim, z_dim, T, B, kernel="auto", ac
     recompute form on kernel "auto" / "mfma" where the shape is its, else K5 on "auto" / "generic"; ELU(1) only.
     method a fused.Tableau: K0 + K5 on kernel "auto" / "generic" (K5's tableau build answers for its fit), the same teacher-forcing rule.
     substeps > 1: K0 + K5 in their sub-step builds on kernel "auto" / "generic" (K5's answers for its fit), the same teacher-forcing rule.
-    externals="linear": K0 + K5 in their linear-externals builds for every substeps >= 1, the same rules.
+    externals="linear" / "lagrange": K0 + K5 in their linear-externals / Lagrange builds for every substeps >= 1, the same rules.
     per_trajectory=True (a call WITH events): K0 + K5 in their per-trajectory builds for every substeps >= 1, the same rules; never
     together with externals="linear".
     segment (an int >= 1): K0 + K5 in their multiple-shooting builds for every substeps >= 1; never teacher-forced, never together with
@@ -96,7 +96,7 @@ def dae_training_supported(method, de, ae, x_dim, z_dim, v_dim, i_dim, T, B, act
     input_true_x / input_true_i: teacher-forced training (T >= 2, ELU(1) only) -- K7f's recompute form on kernel "auto" / "mfma" where the
     shape is its, else K5 on "auto" / "generic".  method a fused.Tableau: K0 + K5 on kernel "auto" / "generic", the same rules.
     substeps > 1: K0 + K5 in their sub-step builds on kernel "auto" / "generic", the same rules.
-    externals="linear": K0 + K5 in their linear-externals builds for every substeps >= 1, the same rules.
+    externals="linear" / "lagrange": K0 + K5 in their linear-externals / Lagrange builds for every substeps >= 1, the same rules.
     per_trajectory=True (a call WITH events): K0 + K5 in their per-trajectory builds for every substeps >= 1, the same rules.
     segment (an int >= 1): K0 + K5 in their multiple-shooting builds, as ode_training_supported; segment_parallel: as there."""
     opts = fused.GenericOpts.of(method, fused.dae_acts(act), substeps, externals, bool(per_trajectory), segment,
@@ -318,11 +318,11 @@ class _FusedOdeGeneric(torch.autograd.Function):
 
 # fused.GenericOpts.family ("ab": with per_trajectory) -> the name of its Function: `_FusedOde<name>` / `_FusedDae<name>`, an empty subclass of
 # the model's one body, is what xs.grad_fn reports.  A further family of K0 / K5 that saves sub-state rows adds a row here, not a class.
-_FAMILY_CLASSES = {"sub": "Sub", "lin": "Lin", "pev": "Pev", ("ab", False): "Ab", ("ab", True): "AbPev", ("ab3", False): "Ab3", ("ab3", True): "Ab3Pev", "ms": "Ms", "msp": "Msp"}
+_FAMILY_CLASSES = {"sub": "Sub", "lin": "Lin", "lag": "Lag", "pev": "Pev", ("ab", False): "Ab", ("ab", True): "AbPev", ("ab3", False): "Ab3", ("ab3", True): "Ab3Pev", "ms": "Ms", "msp": "Msp"}
 # the families that go to _FusedOde / _FusedDae / _FusedDaeTeacherForced
 _OWN_CLASS = ("plain", "act", "rk")
 # ... and those whose forward (fused.ode_integrate / fused.dae_integrate) is the first to check the call
-_CHECKED_BY_FORWARD = _OWN_CLASS + ("sub", "lin")
+_CHECKED_BY_FORWARD = _OWN_CLASS + ("sub", "lin", "lag")
 
 
 def _family_classes(body, prefix) -> dict:

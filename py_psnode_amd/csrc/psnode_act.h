@@ -269,7 +269,7 @@ inline int act_pair(const psnode_act_f32* de, const psnode_act_f32* ae, ActPair&
 }
 
 // psnode_generic.hip: K0's launch planning, shared by both builds
-size_t generic_plan(const IntegrateDev& a, bool dae, unsigned& mask, bool lin = false);      // lin: the linear-externals build's layout
+size_t generic_plan(const IntegrateDev& a, bool dae, unsigned& mask, int lin = 0);      // lin: 1 the linear-externals build's layout, 2 the Lagrange build's
 int generic_reg_mode(const IntegrateDev& a, bool dae);
 bool generic_wide_mode(const IntegrateDev& a, bool dae);
 // What a K0 call carries beyond its args: the build of the generic kernel that runs it and that build's kernel arguments.  The plain entry
@@ -281,6 +281,7 @@ struct K0Call {
     SubDev sub;                    // kBuildSub, kBuildLin, kBuildPev, kBuildMs: sub-steps per grid interval and x_sub
     int ev_pt, ms_every;           // kBuildAb: the event table is [T-1, B]; kBuildMs: grid point k > 0 with k % ms_every == 0 restarts from row k of x
     int per_group;                 // kBuildMsp: segments per time chunk (the grid is tiles x msp_chunks(T, ms_every, per_group))
+    const signed char* stencil;    // kBuildLag: the stencil table int8 [T-1, B], or null (one piece 0 .. T - 1)
 };
 // K0's launcher (psnode_generic_impl.h), instantiated once per build policy in that policy's object, as K5's generic_backward_launch<B>
 // (psnode_common.h) is: reads of `call` what B's kernels take.  BuildPev: a.ev is the [T-1, B] table and not null; BuildMs, BuildMsp: a.x has all T rows.

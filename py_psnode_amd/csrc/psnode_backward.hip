@@ -49,14 +49,14 @@ bool ptrs_ok(const psnode_dae_bwd_args_f32* a) {
 
 // ---- K5 (psnode_generic_bwd_impl.h): the recipe dims it takes, its call struct, the choice among its three builds
 // pre: K5's builds that keep the pre-activations (their own LDS fit: psnode_generic_bwd_impl.h, pre_floats); lin: the linear-externals build's
-bool ode_generic_ok(const psnode_ode_bwd_args_f32* a, bool pre = false, bool lin = false) {
+bool ode_generic_ok(const psnode_ode_bwd_args_f32* a, bool pre = false, int lin = 0) {
     const psnode_mlp_f32& m = a->de;
     if (a->x_dim < 1 || a->z_dim < 0 || m.n_layers < 1 || m.n_layers > kMaxLayers) return false;
     if (m.in_dim != 3 * (a->x_dim + a->z_dim) || m.out_dim[m.n_layers - 1] != a->x_dim) return false;
     return generic_bwd_fits(&a->de, nullptr, a->x_dim, a->z_dim, 0, 0, pre, lin) != 0;
 }
 // (K5's mode for the shape, 0 = not taken: what psnode_dae_backward_supported returns)
-int dae_generic_ok(const psnode_dae_bwd_args_f32* a, bool pre = false, bool lin = false) {
+int dae_generic_ok(const psnode_dae_bwd_args_f32* a, bool pre = false, int lin = 0) {
     if (a->x_dim < 1 || a->z_dim < 0 || a->v_dim < 0 || a->i_dim < 1) return 0;
     const int n = a->x_dim + a->z_dim + a->v_dim + a->i_dim;
     const psnode_mlp_f32 &d = a->de, &g = a->ae;
@@ -102,6 +102,7 @@ int generic_backward(BuildId build, const GenericBwdCall& c, const ActPair* act,
         case kBuildMs: return generic_backward_launch<BuildMs>(c, act, ws, s);
         case kBuildMsp: return generic_backward_launch<BuildMsp>(c, act, ws, s);
         case kBuildAb3: return generic_backward_launch<BuildAb3>(c, act, ws, s);
+        case kBuildLag: return generic_backward_launch<BuildLag>(c, act, ws, s);
     }
     return PSNODE_ERR_UNSUPPORTED;      // (no such build)
 }
@@ -217,7 +218,7 @@ extern "C" int32_t psnode_dae_backward_f32(const psnode_dae_bwd_args_f32* a, voi
     return generic_backward(kBuildElu1, generic_bwd_call(*a), nullptr, workspace, stream);
 }
 
-// ---- The K5 entry-point families psnode_dae_backward_tf_* and psnode_{ode,dae}_backward_{act,rk,sub,lin,pev,ab,ms,msp}_*: one checked call path
+// ---- The K5 entry-point families psnode_dae_backward_tf_* and psnode_{ode,dae}_backward_{act,rk,sub,lin,lag,pev,ab,ab3,ms,msp}_*: one checked call path
 // (k5_backward), one query (k5_supported) over the family table of psnode_generic_family.h, which also holds the order of the checks per family.
 namespace {
 constexpr uint32_t kTfFlags = PSNODE_FLAG_INPUT_TRUE_X | PSNODE_FLAG_INPUT_TRUE_I;
@@ -234,8 +235,8 @@ uint32_t tf_mask(const psnode_dae_bwd_args_f32&) { return 0; }
 uint32_t tf_mask(const psnode_dae_bwd_tf_args_f32&) { return kTfFlags; }
 const psnode_mlp_f32* ae_of(const psnode_ode_bwd_args_f32&) { return nullptr; }
 const psnode_mlp_f32* ae_of(const psnode_dae_bwd_args_f32& a) { return &a.ae; }
-int generic_ok(const psnode_ode_bwd_args_f32* a, bool pre, bool lin) { return ode_generic_ok(a, pre, lin); }
-int generic_ok(const psnode_dae_bwd_args_f32* a, bool pre, bool lin) { return dae_generic_ok(a, pre, lin); }
+int generic_ok(const psnode_ode_bwd_args_f32* a, bool pre, int lin) { return ode_generic_ok(a, pre, lin); }
+int generic_ok(const psnode_dae_bwd_args_f32* a, bool pre, int lin) { return dae_generic_ok(a, pre, lin); }
 int backward_elu1(const psnode_ode_bwd_args_f32* a, void* ws, size_t bytes, void* stream) { return psnode_ode_backward_f32(a, ws, bytes, stream); }
 int backward_elu1(const psnode_dae_bwd_args_f32* a, void* ws, size_t bytes, void* stream) { return psnode_dae_backward_f32(a, ws, bytes, stream); }
 int backward_elu1(const psnode_dae_bwd_tf_args_f32* a, void* ws, size_t bytes, void* stream) { return psnode_dae_backward_tf_f32(a, ws, bytes, stream); }
@@ -308,6 +309,7 @@ int k5_backward(Family fam, const Args* a, const CallOpts& o, void* workspace, s
     if (f.tab != kTabNone) c.rk = &t;
     c.substeps = nsub;
     c.x_sub = o.sub ? o.sub->x_sub : nullptr;
+    c.stencil = o.stencil;
     c.ab_pt = o.per_trajectory != 0;
     if (f.seg) { c.ms_every = o.every(); c.ms_x_true = o.x_true(); c.ms_per_group = o.per_group(); }
     return generic_backward(family_build(f, act_pair_keeps_u(p)), c, &p, workspace, stream);
@@ -474,6 +476,31 @@ extern "C" int32_t psnode_dae_backward_ab_supported(const psnode_dae_bwd_tf_args
 extern "C" int32_t psnode_dae_backward_ab_f32(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
                                               int32_t per_trajectory, void* ws, size_t bytes, void* stream) {
     return k5_backward(kFamAb, a, {de_act, ae_act, nullptr, nullptr, nullptr, per_trajectory}, ws, bytes, stream);
+}
+
+// (four-point Lagrange externals: the _lin family's prototypes and order of checks, plus the stencil table -- NULL: one piece 0 .. T - 1)
+extern "C" int32_t psnode_ode_backward_lag_supported(const psnode_ode_bwd_args_f32* a, const psnode_act_f32* de_act,
+                                                     const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, const psnode_ext_stencil_f32* st) {
+    return k5_supported(kFamLag, a, {de_act, nullptr, tab, sub, nullptr, 0, nullptr, st});
+}
+extern "C" int32_t psnode_ode_backward_lag_f32(const psnode_ode_bwd_args_f32* a, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
+                                               const psnode_substeps_f32* sub, const psnode_ext_stencil_f32* st, void* ws, size_t bytes, void* stream) {
+    return k5_backward(kFamLag, a, {de_act, nullptr, tab, sub, nullptr, 0, nullptr, st}, ws, bytes, stream);
+}
+extern "C" int32_t psnode_dae_backward_lag_supported(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act,
+                                                     const psnode_act_f32* ae_act, const psnode_rk_tableau_f32* tab,
+                                                     const psnode_substeps_f32* sub, const psnode_ext_stencil_f32* st) {
+    return k5_supported(kFamLag, a, {de_act, ae_act, tab, sub, nullptr, 0, nullptr, st});
+}
+extern "C" size_t psnode_dae_backward_lag_workspace_size(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act,
+                                                         const psnode_act_f32* ae_act, const psnode_rk_tableau_f32* tab,
+                                                         const psnode_substeps_f32* sub, const psnode_ext_stencil_f32* st) {
+    return k5_workspace_bytes(kFamLag, a, {de_act, ae_act, tab, sub, nullptr, 0, nullptr, st});
+}
+extern "C" int32_t psnode_dae_backward_lag_f32(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                               const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, const psnode_ext_stencil_f32* st,
+                                               void* ws, size_t bytes, void* stream) {
+    return k5_backward(kFamLag, a, {de_act, ae_act, tab, sub, nullptr, 0, nullptr, st}, ws, bytes, stream);
 }
 
 // (three-step Adams-Bashforth with the Heun restart step: the _ab family's prototypes and order of checks)

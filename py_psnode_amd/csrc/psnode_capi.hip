@@ -95,7 +95,7 @@ int dispatch(IntegrateDev& d, bool dae, int kernel, const psnode_mlp_f32* de, co
     if (d.T < 1 || d.B < 1) return PSNODE_ERR_DIMS;
     if (use_mfma) return ok_or_hip(launch_mfma(d, dae, pack, stream));
 
-    if (generic_lds_bytes(d, dae, call.build == kBuildLin) > 160 * 1024) return PSNODE_ERR_UNSUPPORTED;
+    if (generic_lds_bytes(d, dae, call.build == kBuildLag ? 2 : (call.build == kBuildLin ? 1 : 0)) > 160 * 1024) return PSNODE_ERR_UNSUPPORTED;
     hipError_t e = launch_pack_image(d.de, dae ? &d.ae : nullptr, d.xd, d.xd + d.zd + (dae ? d.vd + d.id : 0), d.zd + (dae ? d.vd : 0), stream);
     if (e != hipSuccess) return PSNODE_ERR_HIP;
     switch (call.build) {
@@ -110,6 +110,7 @@ int dispatch(IntegrateDev& d, bool dae, int kernel, const psnode_mlp_f32* de, co
         case kBuildMs: e = launch_generic<BuildMs>(d, dae, call, stream); break;
         case kBuildMsp: e = launch_generic<BuildMsp>(d, dae, call, stream); break;
         case kBuildAb3: e = launch_generic<BuildAb3>(d, dae, call, stream); break;
+        case kBuildLag: e = launch_generic<BuildLag>(d, dae, call, stream); break;
     }
     return ok_or_hip(e);
 }
@@ -197,7 +198,7 @@ int fill_dae(const psnode_dae_args_f32* a, IntegrateDev& d) {
     return PSNODE_OK;
 }
 
-// ---- The K0 entry-point families psnode_{ode,dae}_integrate_{act,rk,sub,lin,pev,ab,ms,msp}_*: one checked call path (k0_integrate) and one query
+// ---- The K0 entry-point families psnode_{ode,dae}_integrate_{act,rk,sub,lin,lag,pev,ab,ab3,ms,msp}_*: one checked call path (k0_integrate) and one query
 // (k0_supported) over the family table of psnode_generic_family.h, which also holds the order of the checks per family.
 // the ODE / DAE difference: the side outputs, the recipe widths, fill_*, the AE, the plain entry point
 bool side_outputs(const psnode_ode_args_f32& a) { return a.save_act || a.save_xstage; }
@@ -250,6 +251,7 @@ int k0_integrate(Family fam, const Args* args, const CallOpts& o, void* workspac
     call.ms_every = o.has_seg() ? o.every() : 0;
     call.per_group = o.per_group();
     call.sub = SubDev{family_substeps(f, o), o.sub ? o.sub->x_sub : nullptr};
+    call.stencil = o.stencil;
     return dispatch(d, ae_of(c) != nullptr, c.kernel, &c.de, ae_of(c), workspace, workspace_bytes, static_cast<hipStream_t>(stream), call);
 }
 
@@ -497,6 +499,25 @@ int32_t psnode_dae_integrate_ab_supported(const psnode_dae_args_f32* a, const ps
 int32_t psnode_dae_integrate_ab_f32(const psnode_dae_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
                                     int32_t per_trajectory, void* ws, size_t bytes, void* stream) {
     return k0_integrate(kFamAb, args, {de_act, ae_act, nullptr, nullptr, nullptr, per_trajectory}, ws, bytes, stream);
+}
+
+// (four-point Lagrange externals: the _lin family's prototypes and order of checks, plus the stencil table -- NULL: one piece 0 .. T - 1)
+int32_t psnode_ode_integrate_lag_supported(const psnode_ode_args_f32* a, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
+                                           const psnode_substeps_f32* sub, const psnode_ext_stencil_f32* st) {
+    return k0_supported(kFamLag, a, {de_act, nullptr, tab, sub, nullptr, 0, nullptr, st});
+}
+int32_t psnode_ode_integrate_lag_f32(const psnode_ode_args_f32* args, const psnode_act_f32* de_act, const psnode_rk_tableau_f32* tab,
+                                     const psnode_substeps_f32* sub, const psnode_ext_stencil_f32* st, void* ws, size_t bytes, void* stream) {
+    return k0_integrate(kFamLag, args, {de_act, nullptr, tab, sub, nullptr, 0, nullptr, st}, ws, bytes, stream);
+}
+int32_t psnode_dae_integrate_lag_supported(const psnode_dae_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                           const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, const psnode_ext_stencil_f32* st) {
+    return k0_supported(kFamLag, a, {de_act, ae_act, tab, sub, nullptr, 0, nullptr, st});
+}
+int32_t psnode_dae_integrate_lag_f32(const psnode_dae_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                     const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, const psnode_ext_stencil_f32* st, void* ws,
+                                     size_t bytes, void* stream) {
+    return k0_integrate(kFamLag, args, {de_act, ae_act, tab, sub, nullptr, 0, nullptr, st}, ws, bytes, stream);
 }
 
 // (three-step Adams-Bashforth with the Heun restart step: the _ab family's prototypes and order of checks)

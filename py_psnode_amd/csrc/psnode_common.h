@@ -227,7 +227,7 @@ __host__ __device__ __forceinline__ constexpr float rk_b(int method, int s) {
 }
 
 // psnode_generic.hip
-size_t generic_lds_bytes(const IntegrateDev& a, bool dae, bool lin = false);      // lin: K0's linear-externals build (nzv more rows)
+size_t generic_lds_bytes(const IntegrateDev& a, bool dae, int lin = 0);      // lin: 1 K0's linear-externals build (nzv more rows), 2 the Lagrange build (4 nzv more)
 hipError_t launch_pack_transpose(const MlpDev& de, const MlpDev* ae, hipStream_t stream);   // generic backward: transposed weights
 hipError_t launch_pack_image(const MlpDev& de, const MlpDev* ae, int xd, int n, int nzv, hipStream_t stream);   // generic forward: MFMA images
 size_t generic_image_floats(int K, int N);
@@ -321,6 +321,7 @@ struct GenericBwdCall {
     int ms_every;              // generic_backward_launch<BuildMs> (with rk; substeps >= 1): grid point k > 0 with
     const float* ms_x_true;    //   k % ms_every == 0 restarted from the dataset row ms_x_true[k] ([T, B, xd]; may be null where T - 1 <= ms_every)
     int ms_per_group;          // generic_backward_launch<BuildMsp> (BuildMs's call): segments per time chunk of its tiles x chunks grid
+    const signed char* stencil;      // generic_backward_launch<BuildLag> (BuildLin's call): the stencil table int8 [T-1, B], or null
 };
 struct ActPair;     // psnode_act.h: the DE's and the AE's activation of a non-ELU(1) call
 size_t generic_bwd_workspace_floats(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, long long B);
@@ -328,7 +329,7 @@ size_t generic_bwd_workspace_floats(const psnode_mlp_f32* de, const psnode_mlp_f
 size_t generic_bwd_msp_workspace_floats(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, long long B, int n, int nzv, long long chunks);
 // K5's mode for these dims, 0 if the shape does not fit: the one fit query of all four builds.  pre: the fit of the builds that keep u in LDS
 // as well -- the pre-activation build and the tableau build, whose LDS layouts are the same
-int generic_bwd_fits(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, int xd, int zd, int vd, int id, bool pre, bool lin = false);      // lin: the linear-externals build's layout
+int generic_bwd_fits(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, int xd, int zd, int vd, int id, bool pre, int lin = 0);      // lin: 1 the linear-externals build's layout, 2 the Lagrange build's
 // K5's launcher (psnode_generic_bwd_impl.h), instantiated once per build policy (psnode_generic_build.h) in that policy's object: BuildElu1
 // (ignores `act`), BuildAct (the activations of psnode_act.h), BuildPre (those and the pre-activation family), BuildRk (the tableau build:
 // every activation kind -- `act` is required, ELU(1) runs as ELU with alpha = 1 -- and c.rk in place of c.method; it keeps the

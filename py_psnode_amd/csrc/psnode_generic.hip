@@ -140,13 +140,13 @@ hipError_t launch_pack_image(const MlpDev& de, const MlpDev* ae, int xd, int n, 
 }
 
 // LDS of the kernel without any resident image: activations, state, biases
-size_t generic_lds_bytes(const IntegrateDev& a, bool dae, bool lin) {
+size_t generic_lds_bytes(const IntegrateDev& a, bool dae, int lin) {
     const int vd = dae ? a.vd : 0, id = dae ? a.id : 0;
     const int n = a.xd + a.zd + vd + id;
     const int nzv = a.zd + vd;
-    // DE input, AE input, two layer-output buffers, a0, ext, xcur + xsrc, kbuf, icur, zvn, dts; lin: the interval's left z | v rows
+    // DE input, AE input, two layer-output buffers, a0, ext, xcur + xsrc, kbuf, icur, zvn, dts; lin 1: the interval's left z | v rows, 2: the four node rows of the Lagrange stencil
     const size_t rows = (size_t)de_k16(a.xd, n) + (dae ? ae_k16(a.xd, nzv, n) : 0) + 2 * (size_t)up16(a.maxo) + n + (n - a.xd) + 2 * (size_t)a.xd +
-                        4 * (size_t)a.xd + id + nzv + 1 + (lin ? nzv : 0);
+                        4 * (size_t)a.xd + id + nzv + 1 + (lin == 2 ? 4 * nzv : (lin ? nzv : 0));
     return (rows * TB + generic_bias_floats(a, dae)) * sizeof(float);
 }
 
@@ -176,7 +176,7 @@ bool generic_wide_mode(const IntegrateDev& a, bool dae) {
     return true;
 }
 
-size_t generic_plan(const IntegrateDev& a, bool dae, unsigned& mask, bool lin) {
+size_t generic_plan(const IntegrateDev& a, bool dae, unsigned& mask, int lin) {
     size_t bytes = generic_lds_bytes(a, dae, lin);
     mask = 0;
     if (generic_reg_mode(a, dae) || generic_wide_mode(a, dae)) return bytes;

@@ -28,6 +28,7 @@
     float* zvn = icur + id * TB;       // [nzv][TB] dataset z | v of the NEXT grid point
     float* dts = zvn + nzv * TB;       // [TB]
     [[maybe_unused]] float* wl = dts + TB;      // Bd::lin only: [nzv][TB] z | v at the interval's left end (the jumped values behind an event)
+    [[maybe_unused]] float* wn = dts + TB;      // Bd::lag, in wl's place: [4][nzv][TB] the node rows of the interval's stencil (node 0 jumped where the table says so)
 
 #ifdef PSNODE_K0_PROF      // discriminator builds only: cycles per phase of workgroup 0, printed by its first thread
     long long prof[6] = {0, 0, 0, 0, 0, 0};
@@ -39,7 +40,7 @@
     Pref pf;
     pf.tag = nullptr;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    unsigned bias_at = (unsigned)(dts + TB - lds) + (Bd::lin ? (unsigned)(nzv * TB) : 0u), img_at = bias_at + (unsigned)generic_bias_floats(a, DAE);
+    unsigned bias_at = (unsigned)(dts + TB - lds) + (Bd::lin ? (unsigned)((Bd::lag ? 4 : 1) * nzv * TB) : 0u), img_at = bias_at + (unsigned)generic_bias_floats(a, DAE);
     const Tab<ML> tde = make_tab<ML>(a.de, wv, a.k0_res & 0xffu, bias_at, img_at, de_k16(xd, n), SX >> 4);
     const Tab<ML> tae = DAE ? make_tab<ML>(a.ae, wv, (a.k0_res >> 8) & 0xffu, bias_at, img_at, ae_k16(xd, nzv, n), SA >> 4) : tde;
     load_resident(a.de, tde, lds);
@@ -194,6 +195,16 @@
     // dataset's rows of grid point k + 1 (zvn, which the first stage pass of the interval fills from the look-ahead registers).  th_in: the
     // theta of the rows the DE input holds; th_fd: the one the register forms' fold0 was taken at.  Both are wave-uniform.
     [[maybe_unused]] float th_in = 0.0f, th_fd = 0.0f;
+    // Lagrange externals (Bd::lag, on Bd::lin's policy): the same passes, with the polynomial through the q <= 4 node rows of the column's
+    // stencil (lag_stencil, psnode_generic_build.h) in the straight line's place.  Every thread carries the stencil of ITS column (tid % TB:
+    // the column of every item a thread touches); the node rows go to wn behind the interval's first evaluation, whose theta is 0 -- the
+    // left rows themselves.  The weights are per thread, theta is wave-uniform.  Like the other look-ahead values the code byte is loaded
+    // one interval ahead (lag_cn) and the node rows of a thread's first item are requested at the top of the step (pn): their latency -- the
+    // event index at the first node, then the rows -- hides behind the first evaluation.
+    [[maybe_unused]] LagStencil lag_st{0, 2, 0};
+    [[maybe_unused]] int lag_cn = 0, lag_evs = -1;
+    [[maybe_unused]] float pn[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if constexpr (Bd::lag) { if (a.T > 1) lag_cn = lag_code(lag_table(sub), 0, a.B, gb(tid % TB)); }
 
     // One MLP call site for every evaluation (the unrolled layer code exists once: it has to stay inside the instruction cache).  Slots of
     // step k: 0 = the AE head at an event (my_solvers.py:110), 1 .. S = the DE stages, S + 1 = the AE head at grid point k + 1
@@ -243,10 +254,29 @@
                 if (ev >= 0) { const long long b = gb(c); v = r < zd ? a.zj[b * a.zjb + ev * a.zje + r] : a.vj[b * a.vjb + ev * a.vje + (r - zd)]; }
                 else v = zvn[idx];
                 put_ext(r, c, v);
-                if constexpr (Bd::lin) wl[idx] = v;
+                if constexpr (Bd::lin && !Bd::lag) wl[idx] = v;
                 if constexpr (DAE) if (ev >= 0) lds[inAE + qi(xd + r, c)] = v;      // the event's AE evaluation sees the jumped rows
             }
             if constexpr (Bd::lin) th_in = 0.0f;
+            if constexpr (Bd::lag) {
+                lag_st = lag_decode(lag_cn, k, a.T);
+                lag_cn = k + 2 < a.T ? lag_code(lag_table(sub), k + 1, a.B, gb(tid % TB)) : 0;
+                if (nstage > 1 || nsub > 1) {      // (a one-stage, one-sub-step interval reads theta = 0 alone)
+                    // the stencil's node rows of this thread's first item: dataset rows lag_st.s .. + q - 1 of its column, node 0 from the
+                    // jump rows where the event table has an event at step s (0 beyond q); every lane loads, from a valid address
+                    lag_evs = a.ev ? evp[lag_st.s] : -1;
+                    const int ii = tid < nzv * TB ? tid : 0, r = ii / TB, c = ii % TB;
+#pragma unroll
+                    for (int m = 0; m < 4; ++m) {
+                        float v = 0.0f;
+                        if (nzv > 0 && m < lag_st.q) {
+                            if (m == 0 && lag_evs >= 0) { const long long b = gb(c); v = r < zd ? a.zj[b * a.zjb + lag_evs * a.zje + r] : a.vj[b * a.vjb + lag_evs * a.vje + (r - zd)]; }
+                            else v = zv_at(lag_st.s + m, r, c);
+                        }
+                        pn[m] = v;
+                    }
+                }
+            }
             for (int idx = tid; idx < nx; idx += NT) {
                 const int r = idx / TB, c = idx % TB;
                 const float v = (Bd::ms ? ms_rs : true_x) ? a.x.p[k * a.x.st + gb(c) * a.x.sb + r] : xcur[idx];
@@ -402,15 +432,43 @@
                         if (idx < nzv * TB) zvn[idx] = pz[j];
                     }
                     for (int idx = tid + NT * PF; idx < nzv * TB; idx += NT) zvn[idx] = zv_at(k + 1, idx / TB, idx % TB);
+                    if constexpr (Bd::lag) {
+                        if (!(final_stage && si.last())) {      // (a one-stage, one-sub-step interval reads theta = 0 alone)
+                            // the node rows: a thread's first item from the look-ahead registers, items beyond them loaded here
+                            if (tid < nzv * TB) {
+#pragma unroll
+                                for (int m = 0; m < 4; ++m) wn[m * nzv * TB + tid] = pn[m];
+                            }
+                            for (int idx = tid + NT; idx < nzv * TB; idx += NT) {
+                                const int r = idx / TB, c = idx % TB;
+#pragma unroll
+                                for (int m = 0; m < 4; ++m) {
+                                    float v = 0.0f;
+                                    if (m < lag_st.q) {
+                                        if (m == 0 && lag_evs >= 0) { const long long b = gb(c); v = r < zd ? a.zj[b * a.zjb + lag_evs * a.zje + r] : a.vj[b * a.vjb + lag_evs * a.vje + (r - zd)]; }
+                                        else v = zv_at(lag_st.s + m, r, c);
+                                    }
+                                    wn[m * nzv * TB + idx] = v;
+                                }
+                            }
+                        }
+                    }
                 }
                 if (!(final_stage && si.last())) {
                     // the externals of the next stage, or of the next sub-step's first one (and of the head in front of it): c_{s + 1} is the
                     // row sum just read, in increasing index
                     const float th = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(((float)si.i + (final_stage ? 1.0f : (c0 + c1) + c2)) / (float)nsub)));
+                    [[maybe_unused]] LagW lw{};
+                    if constexpr (Bd::lag) lw = lag_weights(lag_st.off, lag_st.q, th);
                     for (int idx = tid; idx < nzv * TB; idx += NT) {      // (each thread reads back what it wrote itself)
                         const int r = idx / TB, c = idx % TB;
+                        float v;
+                        if constexpr (Bd::lag) {
+                            v = lag_eval(lw, lag_st.q, wn[idx], wn[nzv * TB + idx], wn[2 * nzv * TB + idx], wn[3 * nzv * TB + idx]);
+                        } else {
                         const float l_ = wl[idx];
-                        const float v = l_ + th * (zvn[idx] - l_);
+                        v = l_ + th * (zvn[idx] - l_);
+                        }
                         put_ext(r, c, v);
                         if constexpr (DAE) if (final_stage) lds[inAE + qi(xd + r, c)] = v;
                     }

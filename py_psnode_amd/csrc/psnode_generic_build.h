@@ -1,4 +1,4 @@
-// The build policy of the generic kernels K0 (psnode_generic_impl.h) and K5 (psnode_generic_bwd_impl.h): what separates the ten objects each
+// The build policy of the generic kernels K0 (psnode_generic_impl.h) and K5 (psnode_generic_bwd_impl.h): what separates the eleven objects each
 // is compiled into, as constants the language can see.  Each object is one file that names its policy and includes the impl header:
 //   #define PSNODE_BUILD BuildAct
 //   #include "psnode_generic_impl.h"
@@ -38,6 +38,17 @@ struct MsDev {
     const float* x_true;
 };
 __host__ __device__ inline int ev_table_pt(const MsDev&) { return 0; }
+// What the Lagrange-externals builds of K0 / K5 take in SubDev's place: the sub-step build's argument plus the stencil table
+// (psnode_ext_stencil_f32, include/psnode_hip.h) -- int8 [T-1, B], one code byte per grid interval and trajectory; null: one piece
+// 0 .. T - 1 for every trajectory.
+struct LagDev {
+    int n;
+    float* x_sub;
+    const signed char* stencil;
+};
+__host__ __device__ inline int ev_table_pt(const LagDev&) { return 0; }
+template <class S> __host__ __device__ inline const signed char* lag_table(const S&) { return nullptr; }
+__host__ __device__ inline const signed char* lag_table(const LagDev& s) { return s.stencil; }
 // (asked through overloads for the reason above)
 template <class S> __host__ __device__ inline int ms_every(const S&) { return 0; }
 __host__ __device__ inline int ms_every(const MsDev& s) { return s.every; }
@@ -94,8 +105,56 @@ __device__ __forceinline__ Ab3Coef ab3_coef(float h0, float h1, float h2, bool r
     return cf;
 }
 
+// The stencil of grid interval k of one trajectory column in the Lagrange-externals builds (Bd::lag): q = 2 .. 4 consecutive nodes from
+// row s on, off = k - s; the value at theta is sum_m l_m(off + theta) node_{s+m}.  Decoded from the column's code byte (off in bits 0-1, q in
+// bits 2-4), or, without a table, from k and T alone (one piece 0 .. T - 1).  Clamped so that no byte makes a kernel read outside rows
+// 0 .. T - 1 (T >= 2 wherever an interval exists): 2 <= q <= min(4, T), 0 <= s <= T - q.
+struct LagStencil { long long s; int q, off; };
+// the column's code byte of interval k (a kernel loads it one interval ahead); without a table: q = 4 from k - 1 on, which lag_decode clamps
+__device__ __forceinline__ int lag_code(const signed char* tab, long long k, long long B, long long b) {
+    return tab ? (int)tab[k * B + b] : ((k > 0 ? 1 : 0) | (4 << 2));
+}
+__device__ __forceinline__ LagStencil lag_decode(int code, long long k, long long T) {
+    int off = code & 3, q = (code >> 2) & 7;
+    q = q < 2 ? 2 : (q > 4 ? 4 : q);
+    if (q > T) q = (int)T;
+    long long s = k - off;
+    if (s + q > T) s = T - q;
+    if (s < 0) s = 0;
+    return LagStencil{s, q, (int)(k - s)};
+}
+__device__ __forceinline__ LagStencil lag_stencil(const signed char* tab, long long k, long long T, long long B, long long b) {
+    return lag_decode(lag_code(tab, k, B, b), k, T);
+}
+// The weights l_m(u) = (prod_{r != m} (u - r)) / (prod_{r != m} (m - r)), u = off + theta, of the q nodes (0 beyond them): numerator and
+// denominator each a product in increasing r from 1 -- the denominator a small integer --, one division per weight.  At theta = 0 and
+// theta = 1 u is an integer, so the numerator is the denominator or 0 and the weights are exactly 1 / 0.  One function for K0 and K5:
+// K5's weights are K0's bit for bit (the objects are built without contraction).  lag_eval: the sum in increasing m.
+struct LagW { float w[4]; };
+__device__ __forceinline__ LagW lag_weights(int off, int q, float theta) {
+    const float u = (float)off + theta;
+    LagW o;
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        float num = 1.0f;
+        int den = 1;
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            if (r != m && r < q) { num = num * (u - (float)r); den = den * (m - r); }
+        o.w[m] = m < q ? num / (float)den : 0.0f;
+    }
+    return o;
+}
+__device__ __forceinline__ float lag_eval(const LagW& w, int q, float n0, float n1, float n2, float n3) {
+    float acc = w.w[0] * n0;
+    acc = acc + w.w[1] * n1;
+    if (q > 2) acc = acc + w.w[2] * n2;
+    if (q > 3) acc = acc + w.w[3] * n3;
+    return acc;
+}
+
 template <bool ACT, bool PRE, bool RK, bool SUB = false, bool LIN = false, bool PEV = false, bool AB = false, bool MS = false, bool PAR = false,
-          bool AB3 = false>
+          bool AB3 = false, bool LAG = false>
 struct GenericBuild {
     static constexpr bool act = ACT;      // the hidden-layer activation is a kernel argument (ActPair, psnode_act.h), not ELU(1)
     static constexpr bool pre = PRE;      // the hidden layers' pre-activations u are kept next to h (SiLU / GELU / Mish differentiate from u)
@@ -110,12 +169,15 @@ struct GenericBuild {
     static constexpr bool ab3 = AB3;      // three-step Adams-Bashforth with a predictor-corrector restart step: two previous slopes, per-column c0 / c1 / c2,
                                           // and on restart steps a second DE stage (a DAE: behind a head evaluation of its own) on the rows of grid
                                           // point k + 1 (AbDev; needs ab)
+    static constexpr bool lag = LAG;      // the interpolant of lin is the polynomial through the up to four neighbouring dataset rows of the interval's
+                                          // piece, by the stencil table (LagDev; needs lin)
+    static constexpr int lin_layout = LAG ? 2 : (LIN ? 1 : 0);      // the LDS layout the fit queries count: none, lin's regions, lag's
     static constexpr bool par = PAR;      // segments in parallel: the launch grid is tiles x chunks, workgroup (tile, c) runs the segments of time chunk c
                                           // alone (MspDev; needs ms)
     // The kernels' arguments behind the args struct, each a by-value parameter of its own: ActPair (act) | psnode_rk_tableau_f32 (rk) | Sub (sub).
     // A kernel without one of them names the never-read default of kernel_arg in its place.
     static constexpr int n_extra = SUB ? 3 : (RK ? 2 : (ACT ? 1 : 0));
-    using Sub = std::conditional_t<AB, AbDev, std::conditional_t<PAR, MspDev, std::conditional_t<MS, MsDev, SubDev>>>;
+    using Sub = std::conditional_t<LAG, LagDev, std::conditional_t<AB, AbDev, std::conditional_t<PAR, MspDev, std::conditional_t<MS, MsDev, SubDev>>>>;
     // K5's waves per SIMD: the fully streamed instances (STR 2) that fitted 256 registers keep two workgroups per CU -- every one of the
     // act build, the ELU(1) build's with the accumulators in LDS, none of the builds that keep u
     static constexpr int two_waves(bool gg, int str) { return PRE ? 1 : (str == 2 && (ACT || !gg) ? 2 : 1); }
@@ -146,8 +208,9 @@ __host__ __device__ constexpr decltype(auto) kernel_arg(const D& dflt, const E0&
 // The policy's Sub argument from what a call carries, for both directions (K0 writes x_sub and has no x_true; K5 reads both)
 template <class B>
 typename B::Sub build_sub(int n, float* x_sub, int ev_pt, int ms_every, const float* x_true, int per_group = 1, float* ga0_part = nullptr,
-                          float* border = nullptr) {
-    if constexpr (B::ab) return AbDev{1, nullptr, ev_pt};
+                          float* border = nullptr, const signed char* stencil = nullptr) {
+    if constexpr (B::lag) return LagDev{n, x_sub, stencil};
+    else if constexpr (B::ab) return AbDev{1, nullptr, ev_pt};
     else if constexpr (B::par) return MspDev{n, x_sub, ms_every, x_true, per_group, ga0_part, border};
     else if constexpr (B::ms) return MsDev{n, x_sub, ms_every, x_true};
     else return SubDev{n, x_sub};
@@ -164,6 +227,7 @@ using BuildAb = GenericBuild<true, true, true, true, false, true, true>;      //
 using BuildMs = GenericBuild<true, true, true, true, false, false, false, true>;      // BuildSub's policy with multiple-shooting restarts; every substeps >= 1
 using BuildMsp = GenericBuild<true, true, true, true, false, false, false, true, true>;      // BuildMs's policy with the segments spread over workgroups: a tiles x chunks grid
 using BuildAb3 = GenericBuild<true, true, true, true, false, true, true, false, false, true>;      // BuildAb's policy as Adams-Bashforth 3 with the Heun restart step
-enum BuildId { kBuildElu1, kBuildAct, kBuildPre, kBuildRk, kBuildSub, kBuildLin, kBuildPev, kBuildAb, kBuildMs, kBuildMsp, kBuildAb3 };      // what a call names its build with
+using BuildLag = GenericBuild<true, true, true, true, true, false, false, false, false, false, true>;      // BuildLin's policy with the four-point Lagrange interpolant of the stencil table
+enum BuildId { kBuildElu1, kBuildAct, kBuildPre, kBuildRk, kBuildSub, kBuildLin, kBuildPev, kBuildAb, kBuildMs, kBuildMsp, kBuildAb3, kBuildLag };      // what a call names its build with
 
 }  // namespace psnode

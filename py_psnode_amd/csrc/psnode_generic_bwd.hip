@@ -24,7 +24,7 @@ size_t generic_bwd_msp_workspace_floats(const psnode_mlp_f32* de, const psnode_m
 }
 
 // (the pre fields, which this object's GBwd does not have, are written by a launch only: the fit reads none of them)
-int generic_bwd_fits(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, int xd, int zd, int vd, int id, bool pre, bool lin) {
+int generic_bwd_fits(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, int xd, int zd, int vd, int id, bool pre, int lin) {
     GBwd a;
     memset(&a, 0, sizeof(a));
     a.dae = ae != nullptr; a.xd = xd; a.zd = zd; a.vd = vd; a.id = id;

@@ -60,7 +60,14 @@
     [[maybe_unused]] float* wl = dts + TP;                        // [nzv][TP]
     [[maybe_unused]] float* wr = wl + nzv * TP;                   // [nzv][TP]
     [[maybe_unused]] float* gexr = wr + nzv * TP;                 // [nzv][TP]
-    float* wbuf = dts + TP + (Bd::lin ? 3 * nzv * TP : 0);        // [kWBuf] staged weights
+    // Lagrange externals (Bd::lag, in those three regions' place and five more): the node rows of the interval's stencil (node 0 jumped where
+    // the event table has an event at step s) and their adjoints, which (4) adds to the rows s .. s + q - 1 of grad_z / grad_v.  Every thread
+    // carries the stencil of ITS column (tid % TB: the column of every TILE_LOOP item of a thread) and the event index at its first node.
+    [[maybe_unused]] float* wn = dts + TP;                        // [4][nzv][TP]
+    [[maybe_unused]] float* gn = wn + 4 * nzv * TP;               // [4][nzv][TP]
+    [[maybe_unused]] LagStencil lag_st{0, 2, 0};
+    [[maybe_unused]] int lag_evs = -1;
+    float* wbuf = dts + TP + (Bd::lin ? 3 * nzv * TP : 0) + (Bd::lag ? 5 * nzv * TP : 0);        // [kWBuf] staged weights
     // [np_de + np_ae]: in LDS when it fits, else this workgroup's partial slice in global memory (each element is owned by
     // one thread either way, so the read-modify-write needs no atomics)
     float* gacc_g = a.wpart + (Bd::par ? wg : (size_t)blockIdx.x) * (a.de.np + (a.dae ? a.ae.np : 0));      // (used when gg)
@@ -112,6 +119,19 @@
         float* dst = isz ? a.gz : a.gv;
         if (dst) dst[((a.T - 1) * a.B + b0 + c) * (isz ? zd : vd) + (isz ? r : r - zd)] = 0.0f;
     }
+    if constexpr (Bd::lag) {
+        // every row of grad_z / grad_v and every jump gradient starts at zero: a row collects the shares of up to five intervals, each added
+        // in (4) by the thread that owns the element here too (idx -> (r, c) is the same in every TILE_LOOP)
+        TILE_LOOP(nzv) {
+            if (!on(c)) continue;
+            const bool isz = r < zd;
+            const int d_ = isz ? r : r - zd, w_ = isz ? zd : vd;
+            float* dst = isz ? a.gz : a.gv;
+            float* dj = isz ? a.gzj : a.gvj;
+            if (dst) for (long long j = 0; j < a.T; ++j) dst[(j * a.B + b0 + c) * w_ + d_] = 0.0f;
+            if (dj) for (int e = 0; e < a.n_events; ++e) dj[((b0 + c) * a.n_events + e) * w_ + d_] = 0.0f;
+        }
+    }
     __syncthreads();
 
     // DE input rows of acts: a0 | s - a0 | s  with s = x | ext
@@ -160,6 +180,12 @@
             const int d_ = isz ? r : r - zd, w_ = isz ? zd : vd;
             if constexpr (Bd::sub) {
                 if (ev == -2) {
+                    if constexpr (Bd::lag) {
+                        const LagW lw = lag_weights(lag_st.off, lag_st.q, th_head);
+#pragma unroll
+                        for (int m = 0; m < 4; ++m)
+                            if (m < lag_st.q) gn[(m * nzv + r) * TP + c] += lw.w[m] * g;
+                    } else
                     if constexpr (Bd::lin) { gext[r * TP + c] += (1.0f - th_head) * g; gexr[r * TP + c] += th_head * g; }
                     else gext[r * TP + c] += g;
                     continue;
@@ -329,6 +355,22 @@
             else v = ev >= 0 ? a.vj[b * a.vjb + ev * a.vje + (r - zd)] : a.v.p[k * a.v.st + b * a.v.sb + (r - zd)];
             ext[r * TP + c] = v;
         }
+        if constexpr (Bd::lag) {      // the stencil of this thread's column and its node rows (0 beyond q)
+            lag_st = lag_stencil(lag_table(sub), k, a.T, a.B, gb(tid % TB));
+            lag_evs = a.ev ? a.ev[lag_st.s] : -1;
+            TILE_LOOP(nzv) {
+                const long long b = gb(c);
+#pragma unroll
+                for (int m = 0; m < 4; ++m) {
+                    float v = 0.0f;
+                    if (m < lag_st.q) {
+                        if (m == 0 && lag_evs >= 0) v = r < zd ? a.zj[b * a.zjb + lag_evs * a.zje + r] : a.vj[b * a.vjb + lag_evs * a.vje + (r - zd)];
+                        else v = r < zd ? a.z.p[(lag_st.s + m) * a.z.st + b * a.z.sb + r] : a.v.p[(lag_st.s + m) * a.v.st + b * a.v.sb + (r - zd)];
+                    }
+                    wn[(m * nzv + r) * TP + c] = v;
+                }
+            }
+        } else
         if constexpr (Bd::lin) {      // (each thread copies the ext values it wrote itself; the right rows are the dataset's, never jumped)
             TILE_LOOP(nzv) {
                 const long long b = gb(c);
@@ -353,7 +395,12 @@
             return rk_u(((float)(nsub - 1 - si.i) + cs) / (float)nsub);
         };
         [[maybe_unused]] auto lin_ext = [&](float th) {      // (no barrier of its own)
+            if constexpr (Bd::lag) {      // K0's weights and K0's sum (lag_weights, lag_eval)
+                const LagW lw = lag_weights(lag_st.off, lag_st.q, th);
+                TILE_LOOP(nzv) ext[r * TP + c] = lag_eval(lw, lag_st.q, wn[r * TP + c], wn[(nzv + r) * TP + c], wn[(2 * nzv + r) * TP + c], wn[(3 * nzv + r) * TP + c]);
+            } else {
             TILE_LOOP(nzv) { const float l_ = wl[r * TP + c]; ext[r * TP + c] = l_ + th * (wr[r * TP + c] - l_); }
+            }
         };
         if constexpr (Bd::sub) {
             if (nsub > 1) {      // (defensive: the host never launches this build with one sub-step -- substeps == 1 takes the other entry points)
@@ -511,6 +558,9 @@
             for (int s = 0; s < S; ++s) gks[s * nx + r * TP + c] = dts[c] * coef_b(a.method, ks, nx, s) * g1;
             }
         }
+        if constexpr (Bd::lag) {
+            if (si.first()) { TILE_LOOP(nzv) { gn[r * TP + c] = 0.0f; gn[(nzv + r) * TP + c] = 0.0f; gn[(2 * nzv + r) * TP + c] = 0.0f; gn[(3 * nzv + r) * TP + c] = 0.0f; } }
+        } else
         if constexpr (Bd::lin) { if (si.first()) { TILE_LOOP(nzv) gexr[r * TP + c] = 0.0f; } }
         if constexpr (Bd::sub) { TILE_LOOP(ne) if (r >= nzv || si.first()) gext[r * TP + c] = 0.0f; }
         else { TILE_LOOP(ne) gext[r * TP + c] = 0.0f; }
@@ -527,6 +577,8 @@
                                               : g_vjp<gg>(a.de, acts, dA, dB, gacc_l, gacc_g, wbuf, ActCtx{act.de, upre}));
             [[maybe_unused]] float th_s = 0.0f;
             if constexpr (Bd::lin) th_s = theta(s);
+            [[maybe_unused]] LagW lw_s{};
+            if constexpr (Bd::lag) lw_s = lag_weights(lag_st.off, lag_st.q, th_s);
             TILE_LOOP(n) {
                 const float gs = gu[(n + r) * TP + c] + gu[(2 * n + r) * TP + c];
                 ga0s[r * TP + c] += gu[r * TP + c] - gu[(n + r) * TP + c];
@@ -537,6 +589,15 @@
                         else gks[j * nx + r * TP + c] += dts[c] * coef_a(a.method, ks, nx, s, j) * gs;
                     }
                 } else {
+                    if constexpr (Bd::lag) {
+                        if (r - xd < nzv) {      // w = sum_m l_m(u) node_m: the stage's external adjoint goes to the q nodes
+#pragma unroll
+                            for (int m = 0; m < 4; ++m)
+                                if (m < lag_st.q) gn[(m * nzv + r - xd) * TP + c] += lw_s.w[m] * gs;
+                        } else {
+                            gext[(r - xd) * TP + c] += gs;
+                        }
+                    } else
                     if constexpr (Bd::lin) {
                         if (r - xd < nzv) {      // w = w_L + theta (w_R - w_L): the stage's external adjoint goes to both ends
                             gext[(r - xd) * TP + c] += (1.0f - th_s) * gs;
@@ -573,6 +634,18 @@
             const int d_ = isz ? r : r - zd, w_ = isz ? zd : vd;
             float* dst = isz ? a.gz : a.gv;
             float* dj = isz ? a.gzj : a.gvj;
+            if constexpr (Bd::lag) {
+                // node m's sum: ADDED to row s + m -- zeroed up front, this thread's alone -- or, for a jumped node s, to the jump gradient of
+                // the event at step s (gext's z | v rows stay zero in this build)
+#pragma unroll
+                for (int m = 0; m < 4; ++m) {
+                    if (m >= lag_st.q) continue;
+                    const float gm = gn[(m * nzv + r) * TP + c];
+                    if (m == 0 && lag_evs >= 0) { if (dj) dj[((b0 + c) * a.n_events + lag_evs) * w_ + d_] += gm; }
+                    else if (dst) dst[((lag_st.s + m) * a.B + b0 + c) * w_ + d_] += gm;
+                }
+                continue;
+            }
             if (ev >= 0) {
                 if (dj) dj[((b0 + c) * a.n_events + ev) * w_ + d_] = g;
                 if (dst) dst[(k * a.B + b0 + c) * w_ + d_] = 0.0f;

@@ -670,8 +670,8 @@ template <bool PRE> void place_u_region(GBwdT<PRE>& a, size_t lds_floats, size_t
 }
 
 // pre (here and below): count the u region, as the builds that keep the pre-activations lay LDS out (Bd::pre at a launch); lin: count the
-// linear-externals build's three z | v regions (both ends of the interval, the right end's adjoint)
-size_t gbwd_lds_floats(const GBwd& a, bool pre, bool lin = false) {
+// linear-externals build's three z | v regions (both ends of the interval, the right end's adjoint; 2: the Lagrange build's eight -- four node rows, their adjoints)
+size_t gbwd_lds_floats(const GBwd& a, bool pre, int lin = 0) {
     const int vd = a.dae ? a.vd : 0, id = a.dae ? a.id : 0, ne = a.zd + vd + id, n = a.xd + ne;
     const bool de_tm = a.de_reg || a.str == 2, ae_tm = a.str >= 1;
     const size_t de_acc = a.gacc_global == 1 ? 0 : (size_t)(de_tm ? tm_total(a.de) : a.de.np);
@@ -681,7 +681,7 @@ size_t gbwd_lds_floats(const GBwd& a, bool pre, bool lin = false) {
     if (de_tm) q = (size_t)q_offsets(a.de).total;
     if (a.dae && ae_tm && (size_t)q_offsets(a.ae).total > q) q = (size_t)q_offsets(a.ae).total;
     return (size_t)a.act_rows * TP + 2 * (size_t)a.maxw * TP + 2 * (size_t)n * TP + 2 * (size_t)ne * TP + (size_t)a.xd * TP * (1 + 12 + 2) +
-           (size_t)id * TP + TP + (lin ? 3 * (size_t)(a.zd + vd) * TP : 0) + (stages ? kWBuf : 0) + ((np_all + 3) & ~(size_t)3) + q + (pre ? pre_floats(a) : 0);
+           (size_t)id * TP + TP + (lin == 2 ? 8 : (lin ? 3 : 0)) * (size_t)(a.zd + vd) * TP + (stages ? kWBuf : 0) + ((np_all + 3) & ~(size_t)3) + q + (pre ? pre_floats(a) : 0);
 }
 // the DE's shape class of the register path
 bool de_reg_class(const psnode_mlp_f32& de) {
@@ -752,7 +752,7 @@ __global__ void msp_fold_kernel(float* __restrict__ ga0, const float* __restrict
 
 // 1: everything in LDS; 2: only with the parameter-gradient accumulators in global memory; 0: does not fit.  a.de_reg (the DE's class
 // allows the register path) is kept when its quad-row buffers fit next to the LDS accumulators, else dropped.
-int gbwd_mode(GBwd& a, bool pre, bool lin = false) {
+int gbwd_mode(GBwd& a, bool pre, int lin = 0) {
     const int want_reg = a.de_reg;
     // paths in order of preference: register DE (+ streamed AE head), everything streamed, then the staged paths; for each, the accumulators
     // in LDS, the AE's in the global slice, both there
@@ -826,9 +826,9 @@ int generic_backward_launch(const GenericBwdCall& c, const ActPair* act, float* 
         L = gbwd_layout(*de, ae, B, a, A);
     }
     for (int l = 0; l < kMaxLayers; ++l) { a.fimg[l] = L.img[0][l]; a.timg[l] = L.imgT[0][l]; a.fimgA[l] = L.img[1][l]; a.timgA[l] = L.imgT[1][l]; }
-    if (!gbwd_mode(a, Pol::pre, Pol::lin)) return PSNODE_ERR_UNSUPPORTED;
-    const size_t lds = gbwd_lds_floats(a, Pol::pre, Pol::lin) * sizeof(float);
-    place_u_region<Pol::pre>(a, gbwd_lds_floats(a, Pol::pre, Pol::lin), pre_floats(a));
+    if (!gbwd_mode(a, Pol::pre, Pol::lin_layout)) return PSNODE_ERR_UNSUPPORTED;
+    const size_t lds = gbwd_lds_floats(a, Pol::pre, Pol::lin_layout) * sizeof(float);
+    place_u_region<Pol::pre>(a, gbwd_lds_floats(a, Pol::pre, Pol::lin_layout), pre_floats(a));
     // transposed weights for the forward recomputation
     MlpDev mde, mae;
     memset(&mde, 0, sizeof(mde));
@@ -856,7 +856,7 @@ int generic_backward_launch(const GenericBwdCall& c, const ActPair* act, float* 
     };
     hipError_t e;
     if constexpr (Pol::par) e = go(*act, *c.rk, build_sub<Pol>(c.substeps, const_cast<float*>(c.x_sub), 0, c.ms_every, c.ms_x_true, c.ms_per_group, ga0_part, border));
-    else if constexpr (Pol::sub) e = go(*act, *c.rk, build_sub<Pol>(c.substeps, const_cast<float*>(c.x_sub), c.ab_pt ? 1 : 0, c.ms_every, c.ms_x_true));
+    else if constexpr (Pol::sub) e = go(*act, *c.rk, build_sub<Pol>(c.substeps, const_cast<float*>(c.x_sub), c.ab_pt ? 1 : 0, c.ms_every, c.ms_x_true, 1, nullptr, nullptr, c.stencil));
     else if constexpr (Pol::rk) e = go(*act, *c.rk);
     else if constexpr (Pol::act) e = go(*act);
     else e = go();

@@ -12,7 +12,7 @@
 //   _msp: the _ms family's sequence with psnode_segment_groups_f32 in the segments struct's place; more than 65535 chunks (the grid's second
 //   dimension) are PSNODE_ERR_UNSUPPORTED with the route; [K5] its workspace is its own layout's (gbwd_msp_layout).
 //   _tf [K5; K0 has no such wrapper]: flags == 0 is the plain entry point, in front of all of it.  _rk, _ab and _ab3 do not read `method` (K0's copy
-//   of the args carries EULER); _pev's event_idx is the [T-1, B] table (event-less calls take the other families), _ab's and _ab3's may be NULL.
+//   of the args carries EULER); _lag is _lin's sequence (the stencil table is not checked: NULL is valid); _pev's event_idx is the [T-1, B] table (event-less calls take the other families), _ab's and _ab3's may be NULL.
 //   [K0] route (k0_route_ok): kernel AUTO / GENERIC and no training side outputs -- the _act family looks at save_act alone (a lone
 //   save_xstage is fill_*'s status); _ms needs the DAE's x view (the restarts read its rows).  A call without a tableau leaves a bad method
 //   to fill_*, its query refuses it in front; _act_supported with an ELU(1) pair answers from method and dims alone.
@@ -30,7 +30,7 @@
 
 namespace psnode {
 
-enum Family { kFamTf, kFamAct, kFamRk, kFamSub, kFamLin, kFamPev, kFamAb, kFamMs, kFamMsp, kFamAb3 };
+enum Family { kFamTf, kFamAct, kFamRk, kFamSub, kFamLin, kFamPev, kFamAb, kFamMs, kFamMsp, kFamAb3, kFamLag };
 // the tableau: no argument, `method` is read | NULL is PSNODE_ERR_NULL | NULL is the args' method as one | no argument, always one stage
 enum Tab { kTabNone, kTabRequired, kTabOrMethod, kTabOneStage };
 // the sub-steps struct: no argument | NULL is PSNODE_ERR_NULL | NULL is one sub-step
@@ -44,7 +44,7 @@ struct FamilyRow {
     bool needs_events;      // event_idx NULL: PSNODE_ERR_NULL
     bool no_tf;             // refuses every teacher-forcing flag
     bool saved_all;         // refuses every saved_* row / side output; false: the _act family's own rule, which differs by direction
-    bool pre, lin;          // the LDS fit of its build: the pre-activations kept (K5; kBuildPre's too), the linear-externals layout
+    bool pre; int lin;      // the LDS fit of its build: the pre-activations kept (K5; kBuildPre's too), the linear-externals layout (2: the Lagrange build's)
     bool par;               // the segments struct is psnode_segment_groups_f32: the grid is tiles x chunks, K5's workspace its own layout
 };
 constexpr FamilyRow kFamilies[] = {
@@ -59,6 +59,7 @@ constexpr FamilyRow kFamilies[] = {
     /* _ms  */ {kBuildMs,   false, kTabOrMethod, kSubOrOne,    false,  true,  false, true,  true,  true,  false},      // (every teacher-forced step restarts already)
     /* _msp */ {kBuildMsp,  false, kTabOrMethod, kSubOrOne,    false,  true,  false, true,  true,  true,  false, true},      // (_ms over a tiles x chunks grid)
     /* _ab3 */ {kBuildAb3,  false, kTabOneStage, kSubNone,     false,  false, false, true,  true,  true,  false},      // (_ab's row: the same arguments, checks and fit)
+    /* _lag */ {kBuildLag,  false, kTabOrMethod, kSubOrOne,    false,  false, false, false, true,  true,  2},          // (_lin's row and the stencil table, which may be NULL; its own layout)
 };
 struct CallOpts {      // what a call carries behind its args; a family's wrappers leave what it does not take at NULL / 0
     const psnode_act_f32 *de_act, *ae_act;
@@ -67,6 +68,7 @@ struct CallOpts {      // what a call carries behind its args; a family's wrappe
     const psnode_segments_f32* seg;
     int per_trajectory;      // _ab, _ab3: a non-NULL event_idx is the [T-1, B] table (else the shared [T-1])
     const psnode_segment_groups_f32* grp;      // _msp: in seg's place
+    const psnode_ext_stencil_f32* stencil;     // _lag: the stencil table [T-1, B], or NULL (one piece 0 .. T - 1 for every trajectory)
     // what a family with segments reads, from whichever of the two structs it takes
     bool has_seg() const { return seg || grp; }
     int every() const { return grp ? grp->every : seg->every; }

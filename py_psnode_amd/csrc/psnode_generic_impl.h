@@ -566,7 +566,7 @@ template <class B, class... Extra>
 hipError_t launch_generic_build(const IntegrateDev& a_in, bool dae, unsigned chunks, hipStream_t stream_, const Extra&... extra) {
     using K = GenericKernels<B, Extra...>;
     IntegrateDev a = a_in;
-    const size_t lds = generic_plan(a, dae, a.k0_res, B::lin);
+    const size_t lds = generic_plan(a, dae, a.k0_res, B::lin_layout);
     const unsigned grid = (unsigned)((a.B + TB - 1) / TB);
     unsigned all = (1u << a.de.n_layers) - 1u;
     if (dae) all |= ((1u << a.ae.n_layers) - 1u) << 8;
@@ -598,7 +598,8 @@ hipError_t launch_generic(const IntegrateDev& a, bool dae, const K0Call& call, h
         return launch_generic_build<B>(a, dae, (unsigned)msp_chunks(a.T, call.ms_every, call.per_group), stream, call.act, call.rk,
                                        build_sub<B>(call.sub.n, call.sub.x_sub, call.ev_pt, call.ms_every, nullptr, call.per_group));
     } else if constexpr (B::sub) {
-        return launch_generic_build<B>(a, dae, 1u, stream, call.act, call.rk, build_sub<B>(call.sub.n, call.sub.x_sub, call.ev_pt, call.ms_every, nullptr));
+        return launch_generic_build<B>(a, dae, 1u, stream, call.act, call.rk,
+                                       build_sub<B>(call.sub.n, call.sub.x_sub, call.ev_pt, call.ms_every, nullptr, 1, nullptr, nullptr, call.stencil));
     } else if constexpr (B::rk) return launch_generic_build<B>(a, dae, 1u, stream, call.act, call.rk);
     else if constexpr (B::act) return launch_generic_build<B>(a, dae, 1u, stream, call.act);
     else return launch_generic_build<B>(a, dae, 1u, stream);

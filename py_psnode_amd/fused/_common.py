@@ -115,14 +115,63 @@ def builtin_method(method, what: str):
     return METHOD_ID[method], STAGES[method]
 
 
-EXTERNALS = ("hold", "linear")      # z | v inside a grid interval: the left grid point's rows held (the reference), or interpolated to the right one's
+# z | v inside a grid interval: the left grid point's rows held (the reference), interpolated linearly to the right one's, or by the
+# polynomial through the up to four neighbouring dataset rows of the interval's piece (four-point Lagrange, `lagrange_stencils`)
+EXTERNALS = ("hold", "linear", "lagrange")
 
 
 def is_linear(externals: str) -> bool:
-    """True for externals="linear", False for "hold"; ValueError for anything else."""
-    if externals not in EXTERNALS:
+    """True for the interpolated externals ("linear", "lagrange"), False for "hold"; ValueError for anything else."""
+    if not isinstance(externals, str) or externals not in EXTERNALS:
         raise ValueError(f"externals must be one of {EXTERNALS}, got {externals!r}")
-    return externals == "linear"
+    return externals != "hold"
+
+
+def is_lagrange(externals: str) -> bool:
+    """True for externals="lagrange", False for "hold" / "linear"; ValueError for anything else."""
+    return is_linear(externals) and externals == "lagrange"
+
+
+def _externals_text(externals: str) -> str:
+    """The option as the subject of a refusal."""
+    return ("four-point Lagrange interpolated external inputs (externals='lagrange')" if externals == "lagrange"
+            else "linearly interpolated external inputs (externals='linear')")
+
+
+def stencil_code(off: int, q: int) -> int:
+    """The code byte of a stencil (PSNODE_STENCIL_CODE, include/psnode_hip.h): off = k - s in bits 0-1, the node count q in bits 2-4."""
+    return off | (q << 2)
+
+
+def lagrange_stencils(t: torch.Tensor, event_idx: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The stencil table of externals="lagrange": int8 [T-1, B], one code byte (`stencil_code`) per grid interval and trajectory.
+    t: the clocks [T, B] (or [T, B, 1]; [T, 1] / [T] is one shared clock, B = 1); event_idx: None or the shared event table, int [T-1]
+    (an entry >= 0: an event step).  Interval k is valid if t[k+1] - t[k] > 0.  A piece is a maximal run of consecutive valid intervals
+    with no event step in its interior; an invalid interval is a two-node piece of its own.  Interval k of piece [a, e] reads
+    q = min(4, e - a + 1) nodes from s = clamp(k - 1, a, e - q + 1) on; off = k - s.  Tensor ops on t's device, no host synchronisation."""
+    if t.dim() == 3:
+        t = t[..., 0]
+    if t.dim() == 1:
+        t = t[:, None]
+    T, B = t.shape
+    dev = t.device
+    if T < 2:
+        return torch.empty((0, B), dtype=torch.int8, device=dev)
+    valid = (t[1:] - t[:-1]) > 0                                             # [T-1, B]
+    k = torch.arange(T - 1, device=dev)[:, None]                             # interval index = its left node
+    start = ~valid                                                           # node k starts a piece: an invalid interval, ...
+    start[1:] |= ~valid[:-1]                                                 # ... the interval behind one, ...
+    start[0] = True                                                          # ... the first, ...
+    if event_idx is not None:
+        start |= (event_idx.to(dev).reshape(T - 1, 1) >= 0)                  # ... an event step
+    a = torch.cummax(torch.where(start, k, torch.zeros_like(k)), 0).values   # the piece's first node
+    # the piece's last node: the next piece start behind k, else T - 1; an invalid interval ends at k + 1
+    nxt = torch.where(start, k, torch.full_like(k, T - 1)).expand(T - 1, B)
+    nxt = torch.cat((nxt[1:], torch.full((1, B), T - 1, device=dev, dtype=nxt.dtype)), 0)
+    e = torch.flip(torch.cummin(torch.flip(nxt, (0,)), 0).values, (0,))
+    q = (e - a + 1).clamp(max=4)
+    s = torch.minimum(torch.maximum(k - 1, a), e - q + 1)
+    return ((k - s) | (q << 2)).to(torch.int8)
 
 
 KERNEL_ID = {"auto": _lib.KERNEL_AUTO, "generic": _lib.KERNEL_GENERIC, "mfma": _lib.KERNEL_MFMA, "wide": _lib.KERNEL_MFMA_WIDE,
@@ -209,7 +258,8 @@ def _act_ptrs(acts):
 # psnode_dae_bwd_tf_args_f32; x_sub: a forward call that saves for K5 keeps sub-state rows; workspace: the query that sizes its dae_backward -- "plain",
 # its "own", or the "rk" family's (the same policy, so the same fit, checks and layout for any sub-steps).  par: the segments struct is
 # psnode_segment_groups_f32, and both backward stems size their workspace with the family's own psnode_<stem>_<family>_workspace_size.
-Family = collections.namedtuple("Family", "acts tab sub seg pt tf_args x_sub workspace par", defaults=(True, False, False, False, False, True, False, "own", False))
+# stencil: behind the structs comes the device pointer of the int8 [T-1, B] stencil table (`lagrange_stencils`), or NULL.
+Family = collections.namedtuple("Family", "acts tab sub seg pt tf_args x_sub workspace par stencil", defaults=(True, False, False, False, False, True, False, "own", False, False))
 # The Python counterpart of kFamilies (csrc/psnode_generic_family.h): `GenericOpts`, `call_generic` and the prototypes of _lib.load read it.
 # "plain": the entry points without a family in their name; "none": no entry point at all; "tf": the "plain" dae_backward with dataset rows.
 FAMILIES = {
@@ -220,6 +270,7 @@ FAMILIES = {
     "rk": Family(tab=True),
     "sub": Family(tab=True, sub=True, x_sub=True),
     "lin": Family(tab=True, sub=True, x_sub=True),
+    "lag": Family(tab=True, sub=True, x_sub=True, stencil=True),
     "pev": Family(tab=True, sub=True, x_sub=True, workspace="rk"),
     "ab": Family(pt=True, x_sub=True, workspace="rk"),
     "ab3": Family(pt=True, x_sub=True, workspace="rk"),
@@ -311,8 +362,9 @@ class GenericOpts:
     def __post_init__(self, segment_parallel=None):
         """Validates substeps and externals, and names the entry-point family: "ab" (two-step Adams-Bashforth, with or without
         per-trajectory events; a ValueError together with a Tableau, sub-steps or interpolated externals), else "pev" (per-trajectory events, every substeps >= 1; together
-        with interpolated externals "none": no kernel carries both, `require_generic` refuses the call), else "lin" (interpolated
-        externals, every substeps >= 1), else "sub" (substeps > 1), else "rk" (a Tableau), else "act" (an activation other than ELU(1)),
+        with interpolated externals "none": no kernel carries both, `require_generic` refuses the call), else "lin" (linearly interpolated
+        externals, every substeps >= 1) or "lag" (externals="lagrange": the same rules and refusals, its own entry points, which take the
+        stencil table), else "sub" (substeps > 1), else "rk" (a Tableau), else "act" (an activation other than ELU(1)),
         else "plain"."""
         if isinstance(self.substeps, bool) or not isinstance(self.substeps, int) or not 1 <= self.substeps <= _lib.MAX_SUBSTEPS:
             raise ValueError(f"substeps must be an int in 1..{_lib.MAX_SUBSTEPS}, got {self.substeps!r}")
@@ -338,18 +390,18 @@ class GenericOpts:
             fam = "none" if (is_linear(self.externals) or self.per_trajectory) else ("ms" if sp is None else "msp")
         elif self.ab and ab_order == 3:
             if self.substeps != 1 or is_linear(self.externals) or self.tab is not None:
-                raise ValueError("Adams-Bashforth 3 reads the right-hand side at grid points only: substeps != 1 and externals='linear' would "
+                raise ValueError(f"Adams-Bashforth 3 reads the right-hand side at grid points only: substeps != 1 and externals='{'lagrange' if self.externals == 'lagrange' else 'linear'}' would "
                                  f"need inputs between the dataset rows (got substeps={self.substeps}, externals={self.externals!r})")
             fam = "ab3"
         elif self.ab:
             if self.substeps != 1 or is_linear(self.externals) or self.tab is not None:
-                raise ValueError("Adams-Bashforth 2 reads the right-hand side at grid points only: substeps != 1 and externals='linear' would "
+                raise ValueError(f"Adams-Bashforth 2 reads the right-hand side at grid points only: substeps != 1 and externals='{'lagrange' if self.externals == 'lagrange' else 'linear'}' would "
                                  f"need inputs between the dataset rows (got substeps={self.substeps}, externals={self.externals!r})")
             fam = "ab"
         elif self.per_trajectory:
             fam = "none" if is_linear(self.externals) else "pev"
         elif is_linear(self.externals):
-            fam = "lin"
+            fam = "lag" if is_lagrange(self.externals) else "lin"
         elif self.substeps > 1:
             fam = "sub"
         elif self.tab is not None:
@@ -373,9 +425,10 @@ class GenericOpts:
             return None
         return max(1, -(-(-(-(T - 1) // self.segment)) // self.segment_parallel)) if T > 1 else 1
 
-    def c_args(self, x_sub=None, x_true=None, family: Optional[str] = None) -> list:
+    def c_args(self, x_sub=None, x_true=None, family: Optional[str] = None, stencil=None) -> list:
         """The C arguments behind the args struct that the family's row of FAMILIES lists: the acts, the tableau or NULL (= the args' method),
-        the sub-steps struct with `x_sub` or NULL, the segments struct with a backward call's `x_true` or NULL, per_trajectory.  The list
+        the sub-steps struct with `x_sub` or NULL, the segments struct with a backward call's `x_true` or NULL, the stencil table (`stencil`, an int8 [T-1, B] tensor) or NULL,
+        per_trajectory.  The list
         owns the structs: keep it until the call has returned.  family: the entry point's, where it is not the options' own."""
         f = self.takes if family is None else FAMILIES[family]
         out = _act_ptrs(self.acts) if f.acts else []
@@ -390,6 +443,8 @@ class GenericOpts:
                 out.append(ctypes.byref(_lib.SegmentGroupsF32(every, rows, min(self.segment_parallel or 1, 0x7fffffff))))
             else:
                 out.append(ctypes.byref(_lib.SegmentsF32(every, rows)))
+        if f.stencil:
+            out.append(ctypes.c_void_p(stencil.data_ptr() if stencil is not None and stencil.numel() else None))
         if f.pt:      # (handed to the query too, which does not declare it and never reads it)
             out.append(ctypes.c_int32(1 if self.per_trajectory else 0))
         return out
@@ -408,8 +463,8 @@ class GenericOpts:
             return f"a Runge-Kutta tableau ({self.tab.name}) runs"
         if self.substeps != 1:
             return f"sub-steps per grid interval (substeps={self.substeps}) run"
-        if self.externals == "linear":
-            return "linearly interpolated external inputs (externals='linear') run"
+        if self.externals != "hold":
+            return _externals_text(self.externals) + " run"
         if self.per_trajectory:
             return "per-trajectory events (per_trajectory=True) run"
         if self.segment is not None:
@@ -426,12 +481,12 @@ class GenericOpts:
         self.no_teacher_forcing(what, teacher_forced)
         if self.family == "none" and self.segment is not None:
             raise _lib.UnsupportedShapeError(f"{what}: multiple-shooting segments (segment={self.segment}) together with "
-                                             + ("linearly interpolated external inputs (externals='linear')" if is_linear(self.externals)
+                                             + (_externals_text(self.externals) if is_linear(self.externals)
                                                 else "per-trajectory events (per_trajectory=True)")
                                              + " have no fused form: the multiple-shooting build of K0 / K5 holds the externals and takes the shared event table")
         if self.family == "none":
-            raise _lib.UnsupportedShapeError(f"{what}: per-trajectory events (per_trajectory=True) together with linearly interpolated external "
-                                             "inputs (externals='linear') have no fused form: K0 / K5 carry either, not both")
+            raise _lib.UnsupportedShapeError(f"{what}: per-trajectory events (per_trajectory=True) together with {_externals_text(self.externals)} "
+                                             "have no fused form: K0 / K5 carry either, not both")
         if kernel not in ("auto", "generic") or saved:
             raise _lib.UnsupportedShapeError(f"{what}: {self._first_option()} on the generic kernels K0 / K5 only (kernel 'auto' / 'generic', no saved rows); "
                                              f"got kernel={kernel!r}, saved rows={saved}")
@@ -457,8 +512,8 @@ class GenericOpts:
         if self.substeps != 1:
             raise _lib.UnsupportedShapeError(f"{what}: sub-steps per grid interval (substeps={self.substeps}) run on the generic kernels K0 / K5 only "
                                              "(kernel 'auto' / 'generic', no saved rows); this entry point takes one step per interval")
-        if self.externals == "linear":
-            raise _lib.UnsupportedShapeError(f"{what}: linearly interpolated external inputs (externals='linear') run on the generic kernels "
+        if self.externals != "hold":
+            raise _lib.UnsupportedShapeError(f"{what}: {_externals_text(self.externals)} run on the generic kernels "
                                              "K0 / K5 only (kernel 'auto' / 'generic', no saved rows); this entry point holds them over a step")
         if self.tab is not None:
             builtin_method(self.tab, what)
@@ -478,7 +533,7 @@ class GenericOpts:
         return self.method_id, self.stages
 
 
-def call_generic(lib, stem: str, kind: str, args, opts: GenericOpts, *tail, x_sub=None, x_true=None):
+def call_generic(lib, stem: str, kind: str, args, opts: GenericOpts, *tail, x_sub=None, x_true=None, stencil=None):
     """The one place that picks an entry point of the generic-kernel families and calls it: psnode_<stem>[_<family>]_<kind>(args, the
     family's `c_args`, *tail).  stem: "ode_integrate", "dae_integrate", "ode_backward", "dae_backward"; kind: "f32" (tail: workspace
     pointer, its size, stream), "supported" or, for the backward stems, "workspace_bytes".  A dae_backward whose `args` is a
@@ -493,9 +548,12 @@ def call_generic(lib, stem: str, kind: str, args, opts: GenericOpts, *tail, x_su
     if isinstance(args, _lib.DaeBwdTfArgsF32):
         assert stem == "dae_backward" and fam != "act", f"{stem}: no entry point takes dataset rows and the acts {opts.acts} alone"
         fam = "tf" if fam == "plain" else fam
+    if kind == "workspace_bytes" and FAMILIES[fam].stencil and stem == "dae_backward":      # (the family's own query, under this name)
+        name = f"psnode_{stem}_{fam}_workspace_size"
+        return getattr(lib, name)(ctypes.byref(args), *opts.c_args(x_sub, x_true, fam, stencil), *tail), name
     if kind == "workspace_bytes" and FAMILIES[fam].par:      # (the segment-parallel family sizes both backward stems itself)
         name = f"psnode_{stem}_{fam}_workspace_size"
-        return getattr(lib, name)(ctypes.byref(args), *opts.c_args(x_sub, x_true, fam), *tail), name
+        return getattr(lib, name)(ctypes.byref(args), *opts.c_args(x_sub, x_true, fam, stencil), *tail), name
     if kind == "workspace_bytes":
         assert stem in ("ode_backward", "dae_backward"), f"{stem} has no workspace query of its own"
         query = "plain" if stem == "ode_backward" else FAMILIES[fam].workspace
@@ -512,7 +570,7 @@ def call_generic(lib, stem: str, kind: str, args, opts: GenericOpts, *tail, x_su
         name = f"psnode_{stem}_{kind}"
         return getattr(lib, name)(ctypes.byref(args), *tail), name
     name = f"psnode_{stem}_{fam}_{kind}"
-    return getattr(lib, name)(ctypes.byref(args), *opts.c_args(x_sub, x_true, fam), *tail), name
+    return getattr(lib, name)(ctypes.byref(args), *opts.c_args(x_sub, x_true, fam, stencil), *tail), name
 
 
 def act_of_module(m) -> Optional[object]:

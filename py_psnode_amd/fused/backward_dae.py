@@ -7,7 +7,7 @@ import types
 import torch
 
 from .. import _lib
-from ._common import (KERNEL_ID, GenericOpts, Layers, _aligned16, _bind_jumps, _check_saved, _check_x_sub, _empty, _f32_dev, _mlp, _pad_rows, _padded_hidden, _split_grads, _view, _workspace_of, call_generic, check_event_idx, dae_acts, _ms_rows, check_segment_parallel, resolve_segment_parallel)
+from ._common import (KERNEL_ID, GenericOpts, Layers, _aligned16, _bind_jumps, _check_saved, _check_x_sub, _empty, _f32_dev, _mlp, _pad_rows, _padded_hidden, _split_grads, _view, _workspace_of, call_generic, check_event_idx, dae_acts, lagrange_stencils, _ms_rows, check_segment_parallel, resolve_segment_parallel)
 from .latent import latent_backward_wide, latent_wide_shape
 
 def dae_backward_supported(method, de_layers: Layers, ae_layers: Layers, x_dim, z_dim, v_dim, i_dim, act=None, kernel: str = "auto",
@@ -333,6 +333,7 @@ def dae_backward(method, de_layers: Layers, ae_layers: Layers, t, z, v, all_init
     method: "euler" | "midpoint" | "rk4", or a fused.Tableau -- K5 only (kernel "auto" / "generic", no saved rows).
     substeps > 1: backward of `dae_integrate(..., substeps=, save_sub=True)` with the x_sub it returned -- K5 only, the same rules.
     externals="linear": backward of `dae_integrate(..., externals="linear")` -- K5's linear-externals build only, the same rules.
+    externals="lagrange": backward of `dae_integrate(..., externals="lagrange")` -- K5's Lagrange build only, the same rules.
     per_trajectory=True: backward of `dae_integrate(..., per_trajectory=True)`; `event_idx` is the int32 [T-1, B] table -- K5's
     per-trajectory build only, the same rules (x_sub where substeps > 1).  Without an event table the flag means nothing.
     segment (an int w >= 1): backward of `dae_integrate(..., segment=w)` -- K5's multiple-shooting build only, the same rules; x_true
@@ -449,7 +450,9 @@ def _dae_backward_entry(opts, de_layers, ae_layers, t, z, v, all_initial, xs, is
                 a.saved_ev_act, a.saved_ev_i = s_ev.data_ptr(), s_evi.data_ptr()
         nbytes = call_generic(lib, "dae_backward", "workspace_bytes", args, opts, x_sub=x_sub, x_true=ms_x_true)[0]
         ws, wp, wn = _workspace_of(nbytes, dev)
-        rc, entry = call_generic(lib, "dae_backward", "f32", args, opts, wp, wn, torch.cuda.current_stream(dev).cuda_stream, x_sub=x_sub, x_true=ms_x_true)
+        stencil = lagrange_stencils(t.detach(), event_idx) if opts.takes.stencil else None      # (externals="lagrange": the forward's table again)
+        rc, entry = call_generic(lib, "dae_backward", "f32", args, opts, wp, wn, torch.cuda.current_stream(dev).cuda_stream, x_sub=x_sub, x_true=ms_x_true,
+                                 stencil=stencil)
     _lib.check(rc, entry)
     g["de"], g["ae"] = _split_grads(gde, de_layers), _split_grads(gae, ae_layers)
     return g

@@ -5,7 +5,7 @@ import ctypes
 import torch
 
 from .. import _lib
-from ._common import (KERNEL_ID, GenericOpts, Layers, _aligned16, _bind_jumps, _check_saved, _check_x_sub, _empty, _f32_dev, _mlp, _split_grads, _view, _workspace_of, call_generic, check_event_idx, _ms_rows, check_segment_parallel, resolve_segment_parallel)
+from ._common import (KERNEL_ID, GenericOpts, Layers, _aligned16, _bind_jumps, _check_saved, _check_x_sub, _empty, _f32_dev, _mlp, _split_grads, _view, _workspace_of, call_generic, check_event_idx, lagrange_stencils, _ms_rows, check_segment_parallel, resolve_segment_parallel)
 from .latent import latent_backward_wide, latent_wide_shape
 
 def _bwd_args(opts, de_layers, x_dim, z_dim, T, B, dev, keep, kernel="auto"):
@@ -51,6 +51,8 @@ def ode_backward(method, de_layers: Layers, t, z, all_initial, xs, grad_xs, even
     method: "euler" | "midpoint" | "rk4", or a fused.Tableau -- K5 only (kernel "auto" / "generic", no saved rows).
     substeps > 1: backward of `ode_integrate(..., substeps=, save_sub=True)`, with the x_sub [T-1, substeps-1, B, xd] it returned -- K5 only
     (kernel "auto" / "generic", no saved rows; teacher forcing with ELU(1) only).
+    externals="lagrange": backward of `ode_integrate(..., externals="lagrange")` -- K5's Lagrange build, the same rules; node m's share of a
+    stage's external adjoint is added to row s + m of grad_z (a jumped node's to grad_z_jump); the kernel zeroes every row itself.
     externals="linear": backward of `ode_integrate(..., externals="linear")` -- K5's linear-externals build, the same rules; grad_z row k + 1
     also receives the right-hand share theta g of interval k's stages.
     per_trajectory=True: backward of `ode_integrate(..., per_trajectory=True)`; `event_idx` is the int32 [T-1, B] table -- K5's
@@ -117,6 +119,8 @@ def ode_backward(method, de_layers: Layers, t, z, all_initial, xs, grad_xs, even
             a.saved_act, a.saved_xstage = saved[0].data_ptr(), saved[1].data_ptr()
         nbytes = call_generic(lib, "ode_backward", "workspace_bytes", a, opts, x_sub=x_sub)[0]
         ws, wp, wn = _workspace_of(nbytes, dev)
-        rc, entry = call_generic(lib, "ode_backward", "f32", a, opts, wp, wn, torch.cuda.current_stream(dev).cuda_stream, x_sub=x_sub, x_true=x_true)
+        stencil = lagrange_stencils(t.detach(), event_idx) if opts.takes.stencil else None      # (externals="lagrange": the forward's table again)
+        rc, entry = call_generic(lib, "ode_backward", "f32", a, opts, wp, wn, torch.cuda.current_stream(dev).cuda_stream, x_sub=x_sub, x_true=x_true,
+                                 stencil=stencil)
     _lib.check(rc, entry)
     return gx0, gz, gzj, ga0, _split_grads(gpar, de_layers)

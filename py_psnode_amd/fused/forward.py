@@ -6,7 +6,7 @@ from typing import Optional
 import torch
 
 from .. import _lib
-from ._common import (KERNEL_ID, GenericOpts, resolve_segment_parallel, Layers, Tableau, builtin_method, _aligned16, _bind_events, _check_tb, _empty, _f32_dev, _mlp, _view, _workspace_of, call_generic, dae_acts, has_events, is_linear)
+from ._common import (KERNEL_ID, GenericOpts, resolve_segment_parallel, Layers, Tableau, builtin_method, _aligned16, _bind_events, _check_tb, _empty, _f32_dev, _mlp, _view, _workspace_of, call_generic, dae_acts, has_events, is_linear, lagrange_stencils)
 
 _MFMA_CLASSES = ("MFMA integrators K1 / K2 cover `in -> H -> H -> H -> out` ELU-MLPs with H <= 128 (any x_dim <= 16 for the ODE, "
                  "x_dim <= 8 and z+v+i <= 8 for the DAE), and -- weights streamed from L2 -- the ODE up to H = 192 at any x_dim <= 16 and "
@@ -61,6 +61,8 @@ def ode_integrate(method, de_layers: Layers, t, x, z, all_initial, event_t=None,
     externals: "hold" (the left grid point's z feeds every stage of an interval) or "linear": stage s of sub-step j reads
     z[k] + theta (z[k+1] - z[k]) at theta = (j + c_s) / substeps, z[k] being the jumped row behind an event; the generic kernel K0 in its
     linear-externals build for every substeps >= 1 (kernel "auto" / "generic"; save=True is refused; save_sub then always returns a tensor).
+    "lagrange": the polynomial through the up to four neighbouring dataset rows of the interval's piece at the same theta -- the Lagrange
+    build, the same rules; the stencil table (`lagrange_stencils`) is built here from t and the shared event table.
 
     per_trajectory=True: trajectory b jumps where ITS clock t[k, b] equals one of ITS event times event_t[b, :] (exact equality, lowest
     matching column; NaN entries never fire) -- it is computed as the shared rule computes it in a batch of b alone.  `event_idx`, if
@@ -120,7 +122,7 @@ def ode_integrate(method, de_layers: Layers, t, x, z, all_initial, event_t=None,
     keep.append(a0)
     a.all_initial = a0.data_ptr()
     with torch.cuda.device(dev):
-        _bind_events(a, t, event_t, event_idx, check_events, (("z_jump", z_jump, zd),), B, dev, keep, per_trajectory)
+        event_idx = _bind_events(a, t, event_t, event_idx, check_events, (("z_jump", z_jump, zd),), B, dev, keep, per_trajectory)
         if out is None:
             out = _empty((T, B, xd), dtype=torch.float32, device=dev)
         elif out.shape != (T, B, xd) or not out.is_contiguous() or out.dtype != torch.float32 or out.device != dev:
@@ -138,7 +140,8 @@ def ode_integrate(method, de_layers: Layers, t, x, z, all_initial, event_t=None,
                 a.save_act, a.save_xstage = saved[0].data_ptr(), saved[1].data_ptr()
         x_sub = _empty((max(T - 1, 0), substeps - 1, B, xd), dtype=torch.float32, device=dev) if save_sub and opts.takes.x_sub else None
         ws, wp, wn = _workspace_of(lib.psnode_workspace_bytes(ctypes.byref(a.de), None), dev)
-        rc, entry = call_generic(lib, "ode_integrate", "f32", a, opts, wp, wn, torch.cuda.current_stream(dev).cuda_stream, x_sub=x_sub)
+        stencil = lagrange_stencils(t.detach(), event_idx) if opts.takes.stencil else None      # (externals="lagrange": int8 [T-1, B])
+        rc, entry = call_generic(lib, "ode_integrate", "f32", a, opts, wp, wn, torch.cuda.current_stream(dev).cuda_stream, x_sub=x_sub, stencil=stencil)
     _mfma_miss(rc, kernel, entry, de_layers)
     _lib.check(rc, entry)
     if kernel == "auto" and opts.family == "plain":
@@ -175,7 +178,8 @@ def dae_integrate(method, de_layers: Layers, ae_layers: Layers, x_init, t, x, z,
     save_sub=True (training forward): returns (xs, is, x_sub), x_sub [T-1, substeps-1, B, xd] for the backward (None for substeps == 1).
     externals: "hold", or "linear" -- every stage reads z | v interpolated between grid points k (the jumped rows behind an event) and k + 1
     at theta = (j + c_s) / substeps, as does the head in front of sub-step j >= 1 (theta = j / substeps); i is never interpolated.  K0's
-    linear-externals build for every substeps >= 1 (kernel "auto" / "generic", no save).
+    linear-externals build for every substeps >= 1 (kernel "auto" / "generic", no save); "lagrange": the four-point polynomial of the
+    interval's piece in the straight line's place (the Lagrange build, the same rules; `lagrange_stencils`).
     per_trajectory=True: as `ode_integrate`, for z | v together; the event-time head i0 = g(x_k; z_jump, v_jump) replaces the carried
     algebraic variable of the trajectories with a hit at step k only, the others keep theirs.  K0's per-trajectory build for every
     substeps >= 1 (kernel "auto" / "generic", no save, not with externals="linear").
@@ -265,7 +269,8 @@ def dae_integrate(method, de_layers: Layers, ae_layers: Layers, x_init, t, x, z,
                 a.save_ev_act, a.save_ev_i = saved[3].data_ptr(), saved[4].data_ptr()
         x_sub = _empty((max(T - 1, 0), substeps - 1, B, xd), dtype=torch.float32, device=dev) if save_sub and opts.takes.x_sub else None
         ws, wp, wn = _workspace_of(lib.psnode_workspace_bytes(ctypes.byref(a.de), ctypes.byref(a.ae)), dev)
-        rc, entry = call_generic(lib, "dae_integrate", "f32", a, opts, wp, wn, torch.cuda.current_stream(dev).cuda_stream, x_sub=x_sub)
+        stencil = lagrange_stencils(t.detach(), event_idx) if opts.takes.stencil else None      # (externals="lagrange": int8 [T-1, B])
+        rc, entry = call_generic(lib, "dae_integrate", "f32", a, opts, wp, wn, torch.cuda.current_stream(dev).cuda_stream, x_sub=x_sub, stencil=stencil)
     _mfma_miss(rc, kernel, entry, de_layers)
     _lib.check(rc, entry)
     if kernel == "auto" and opts.family == "plain":

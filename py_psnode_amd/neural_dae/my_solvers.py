@@ -32,6 +32,55 @@ def _autograd():
     return autograd
 
 
+class _LagWalk:
+    """externals='lagrange' of one walk: hits[k] / jumped[k] -- is step k an event step, and its jumped rows (a tuple like `rows`) --, the
+    stencil table's off / q per interval and trajectory, and ext_at(k, j, n): c -> the externals of interval k at theta = (j + c) / n,
+        w = sum_{m < q} l_m(off + theta) node_{s+m} in increasing m,   l_m(u) = (prod_{r != m, r < q} (u - r)) / (prod_{r != m, r < q} (m - r)),
+    both products in increasing r from 1,
+    in the rows' dtype, as written (the device function lag_weights / lag_eval of the kernels has this order).  At theta = 0 and 1 the
+    weights are exactly 0 / 1."""
+
+    def __init__(self, t, event_fn, jump_change_fn, rows):
+        T = t.shape[0]
+        self.rows = rows
+        self.hits = [event_fn is not None and bool(event_fn(t[k]) == True) for k in range(T - 1)]  # noqa: E712 (callbacks may return tensors)
+        self.jumped = {}
+        for k in range(T - 1):
+            if self.hits[k]:
+                res = jump_change_fn(t[k], *(w[k] for w in rows))
+                self.jumped[k] = tuple(res) if isinstance(res, (tuple, list)) else (res,)
+        ev = torch.tensor([0 if h else -1 for h in self.hits], dtype=torch.int32, device=t.device) if any(self.hits) else None
+        codes = _fused.lagrange_stencils(t.detach(), ev).long()      # [T-1, B or 1]
+        self.off, self.q = codes & 3, (codes >> 2) & 7
+        # node 0 of a stencil reads these: the dataset rows with the jumped rows at the event steps
+        self.rows_j = tuple(torch.stack([self.jumped[k][n] if k in self.jumped else w[k] for k in range(T)]) if self.jumped else w
+                            for n, w in enumerate(rows))
+
+    def ext_at(self, k, j, n):
+        T, B = self.rows[0].shape[0], self.rows[0].shape[1]
+        off, q = self.off[k].expand(B), self.q[k].expand(B)
+        s, ar = k - off, torch.arange(B, device=off.device)
+        nodes = [[(wj if m == 0 else w)[(s + m).clamp(max=T - 1), ar] for m in range(4)] for w, wj in zip(self.rows, self.rows_j)]
+
+        def at(c):
+            theta = (j + c) / n
+            out = []
+            for nd in nodes:
+                u = off.to(nd[0].dtype).unsqueeze(-1) + theta
+                one, acc = torch.ones_like(u), None
+                for m in range(4):
+                    num, den = one, one
+                    for r in range(4):
+                        if r != m:
+                            num = num * torch.where((q > r).unsqueeze(-1), u - r, one)
+                            den = den * torch.where((q > r).unsqueeze(-1), torch.full_like(u, m - r), one)
+                    term = torch.where((q > m).unsqueeze(-1), num / den, torch.zeros_like(u)) * nd[m]
+                    acc = term if acc is None else acc + term
+                out.append(acc)
+            return tuple(out)
+        return at
+
+
 class FixedGridODESolver(metaclass=abc.ABCMeta):
     order: int
     method = ""        # "euler" | "midpoint" | "rk4", a fused.Tableau (my_fixed_grid.ExplicitRK), "ab2" (my_fixed_grid.AB2) or "ab3" (my_fixed_grid.AB3): the formula the fused kernels run
@@ -51,12 +100,21 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
         point stay the previous segment's prediction.  Only sub-step 0 of the interval starts from x[k].  The dataset x gets no gradient
         (`_walk_ode` / `_walk_dae` are the definition; fused on the generic kernels K0 / K5, kernel 'auto' / 'generic').  Not together with
         input_true_x / input_true_i (every step restarts already), and a DAE needs its dataset x: ValueError.
-        externals ("hold", the default and the reference's behaviour, or "linear"): what the stages of a grid interval read of the
+        externals ("hold", the default and the reference's behaviour, "linear" or "lagrange"): what the stages of a grid interval read of the
         external inputs z | v.  "hold": the left grid point's rows (the jumped ones behind an event) for every stage and sub-step -- which
         leaves an O(interval) error that no method order and no number of sub-steps removes.  "linear": stage s (abscissa c_s) of sub-step j
         reads w_L + theta (w_R - w_L) at theta = (j + c_s) / substeps, w_L the left rows (jumped behind an event), w_R the dataset's rows of
         the next grid point (`_walk_ode` / `_walk_dae` are the definition; fused on the generic kernels K0 / K5, kernel 'auto' / 'generic').
         `interp` cannot carry this: the reference passes interp="linear" by default and holds.
+        "lagrange": the same walk with the cubic through the four neighbouring dataset rows in the straight line's place (quadratic /
+        linear where a piece has three / two rows) -- an O(H^4) floor in the data's interval H where "linear" has O(H^2), so RK4Classic is
+        fourth order on sampled inputs.  Per trajectory and per column of z | v: a piece is a maximal run of intervals with t[k+1] > t[k]
+        and no event step inside; interval k of piece [a, e] reads q = min(4, e - a + 1) nodes from s = clamp(k - 1, a, e - q + 1) on, node s
+        the jumped row where step s has an event, and w = sum_m l_m(k - s + theta) node_{s+m} with the same theta (`_LagWalk`,
+        fused.lagrange_stencils).  The nodes are taken as equally spaced (each trajectory its own spacing): on a clock that is not, the
+        interpolant is still continuous and exact at the grid points, and promises nothing beyond what "linear" gives.  Everything else
+        is "linear"'s contract.  The walk asks event_fn / jump_change_fn for every grid point in front of its loop; per-trajectory events
+        next to it: ValueError.
         substeps (an int >= 1, default 1): every grid interval [t[k], t[k+1]] is integrated in that many equal sub-steps of
         h = (t[k+1] - t[k]) / substeps, with the interval's external inputs held over all of them and the outputs staying on the grid of t
         (`_walk_ode` / `_walk_dae` are the definition; more than 1 runs fused on the generic kernels K0 / K5, kernel 'auto' / 'generic').
@@ -111,13 +169,13 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
             self._walk_warned = True
             warnings.warn(f"{what}: this call is not fusable (needs fp32 HIP tensors, DE_Func/AE_Func-style MLPs with one activation "
                           "of ELU / Tanh / Sigmoid / ReLU / LeakyReLU / Softplus / SiLU / GELU / Mish -- other than ELU(1) on kernel 'auto' / 'generic' only --, "
-                          "ODE_Event/DAE_Event callbacks -- with per_trajectory=True on kernel 'auto' / 'generic' only and not together with externals='linear' --; "
-                          "an ExplicitRK tableau, substeps > 1 or externals='linear' on kernel 'auto' / 'generic' only (substeps <= 1024); segment= on kernel 'auto' / 'generic' only, with held externals and shared events, dataset x without grad; under autograd also a shape with a backward kernel; teacher-forced "
+                          "ODE_Event/DAE_Event callbacks -- with per_trajectory=True on kernel 'auto' / 'generic' only and not together with interpolated externals --; "
+                          "an ExplicitRK tableau, substeps > 1 or externals='linear' / 'lagrange' on kernel 'auto' / 'generic' only (substeps <= 1024); segment= on kernel 'auto' / 'generic' only, with held externals and shared events, dataset x without grad; under autograd also a shape with a backward kernel; teacher-forced "
                           "training: ELU(1), dataset rows without grad) -- stepping through the Python callables instead", RuntimeWarning, stacklevel=3)
 
     def _generic_only_ok(self, what, acts, per_trajectory=False) -> bool:
         """An activation other than ELU(1), a Runge-Kutta tableau (ExplicitRK: `method` is a fused.Tableau), sub-steps per grid interval
-        (up to 1024), linearly interpolated externals and per-trajectory events (`per_trajectory`: the call has events and its event
+        (up to 1024), interpolated externals ("linear", "lagrange") and per-trajectory events (`per_trajectory`: the call has events and its event
         object applies them per trajectory) run on the generic kernels K0 / K5 only: kernel 'wave' / 'tile' / 'mfma' / 'wide'
         with one of them walks under fused='auto' and raises under 'require', naming the first in the order act, tableau, sub-steps,
         externals, events (fused.GenericOpts.require_generic's).  Per-trajectory events together with externals='linear' have no kernel."""
@@ -136,13 +194,13 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
         elif not fits and self.substeps != 1:
             text = f"with substeps={self.substeps} has no fused form: sub-steps per grid interval run on the generic kernels {limits}"
         elif not fits and self.externals != "hold":
-            text = f"with externals='linear' has no fused form: interpolated external inputs run on the generic kernels {limits}"
+            text = f"with externals={self.externals!r} has no fused form: interpolated external inputs run on the generic kernels {limits}"
         elif lin_pt:
-            text = "with per-trajectory events and externals='linear' has no fused form: the generic kernels carry either, not both"
+            text = f"with per-trajectory events and externals={self.externals!r} has no fused form: the generic kernels carry either, not both"
         elif not generic and per_trajectory:
             text = "has no form for per-trajectory events (per_trajectory=True): they run on the generic kernels (kernel 'auto' / 'generic')"
         elif ms_none:
-            text = (f"with segment={self.segment} next to " + ("externals='linear'" if self.externals != "hold" else "per-trajectory events")
+            text = (f"with segment={self.segment} next to " + (f"externals={self.externals!r}" if self.externals != "hold" else "per-trajectory events")
                     + " has no fused form: the multiple-shooting build of the generic kernels holds the externals and takes the shared event table")
         elif not generic and self.segment is not None:
             text = f"has no form for multiple-shooting segments (segment={self.segment}): they run on the generic kernels (kernel 'auto' / 'generic')"
@@ -180,6 +238,16 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
             theta = (j + c) / n
             return tuple(wl + theta * (wr - wl) for wl, wr in zip(left, right))
         return ext_at
+
+    def _lag_walk(self, what, t, event_fn, jump_change_fn, rows):
+        """The set-up of externals='lagrange' in front of a walk's loop (None for every other value): the events and jumped rows of every
+        grid point, the stencil table, the node rows.  rows: (z,) or (z, v)."""
+        if self.externals != "lagrange":
+            return None
+        if event_fn is not None and _fused.per_trajectory_events(event_fn):
+            raise ValueError(f"{what}: externals='lagrange' together with per-trajectory events is not defined (a piece ends at an event "
+                             "step of the shared table)")
+        return _LagWalk(t, event_fn, jump_change_fn, rows)
 
     def _check_segment(self, what, teacher_forced, x=None):
         """The refusals of `segment`: teacher forcing (every step restarts already) and, for a DAE (`x` given), no dataset x."""
@@ -268,20 +336,24 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
         xs = torch.zeros(x.shape, dtype=x.dtype, device=x.device)
         cur = x[0] if x_init is None else x_init
         xs[0] = cur
+        lag = self._lag_walk("integrate_ODE", t, event_fn, jump_change_fn, (z,))
         for k in range(n_grid - 1):
             t0, t1, zk = t[k], t[k + 1], z[k]
-            if event_fn is not None and event_fn(t0) == True:  # noqa: E712 (callbacks may return tensors)
+            if lag is not None:      # (asked in front of the loop: a piece's end lies in the future)
+                if lag.hits[k]:
+                    zk = lag.jumped[k][0]
+            elif event_fn is not None and event_fn(t0) == True:  # noqa: E712 (callbacks may return tensors)
                 zk = jump_change_fn(t0, zk)
             start = x[k] if input_true_x else cur
             if self.segment is not None:
                 self._check_segment("integrate_ODE", input_true_x)
                 if self._restart(k):      # multiple shooting: this segment starts from the dataset row, which gets no gradient
                     start = x[k].detach()
-            if self.externals == "linear":      # stage s of sub-step j reads zk + theta (z[k + 1] - zk), theta = (j + c_s) / n; zk jumped behind an event
-                h = (t1 - t0) / self.substeps
+            if self.externals != "hold":      # stage s of sub-step j reads zk + theta (z[k + 1] - zk), theta = (j + c_s) / n; zk jumped behind an event
+                h = (t1 - t0) / self.substeps   # ("lagrange": the polynomial through the stencil's nodes at the same theta)
                 cur = start
                 for j in range(self.substeps):
-                    ext_at = self._lin_ext(j, self.substeps, (zk,), (z[k + 1],))
+                    ext_at = self._lin_ext(j, self.substeps, (zk,), (z[k + 1],)) if lag is None else lag.ext_at(k, j, self.substeps)
                     cur = cur + self._step_func_lin(func=x_func, t0=t0 + j * h if j else t0, dt=h, x0=cur, ext_at=lambda c: ext_at(c) + (None,),
                                                     all_initial=all_initial)
             elif self.substeps == 1:
@@ -353,10 +425,11 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
         xs = torch.zeros(x_shape, dtype=x_init.dtype if x.shape[-1] == 0 else x.dtype, device=x.device)
         is_ = torch.zeros(i.shape, dtype=i.dtype, device=i.device)
         xs[0], is_[0] = cur_x, cur_i
+        lag = self._lag_walk("integrate_DAE", t, event_fn, jump_change_fn, (z, v))
         for k in range(n_grid - 1):
             t0, t1, zk, vk = t[k], t[k + 1], z[k], v[k]
-            if event_fn is not None and event_fn(t0) == True:  # noqa: E712
-                zk, vk = jump_change_fn(t0, zk, vk)
+            if lag.hits[k] if lag is not None else (event_fn is not None and event_fn(t0) == True):  # noqa: E712
+                zk, vk = lag.jumped[k] if lag is not None else jump_change_fn(t0, zk, vk)
                 if _fused.per_trajectory_events(event_fn):      # the event-time head replaces the carried i of the hit trajectories only
                     hit = event_fn.__self__.hit_mask(t0)
                     cur_i = torch.where(hit.view(-1, 1), i_func(xt=cur_x, zt=zk, vt=vk, all_initial=all_initial), cur_i)
@@ -369,11 +442,11 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
                 if self._restart(k):      # multiple shooting: the DE starts from the dataset row and reads the head AT that row (zk | vk: the
                     start = x[k].detach()      # jumped rows behind an event); xs[k] / is[k] stay the previous segment's prediction
                     i_in = i_func(xt=start, zt=zk, vt=vk, all_initial=all_initial)
-            if self.externals == "linear":      # as the ODE, for z | v; i is frozen over a sub-step's stages and never interpolated; the head in
+            if self.externals != "hold":      # as the ODE, for z | v; i is frozen over a sub-step's stages and never interpolated; the head in
                 h = (t1 - t0) / self.substeps   # front of sub-step j >= 1 sees the state and the z | v of theta = j / n
                 cur_x = start
                 for j in range(self.substeps):
-                    ext_at = self._lin_ext(j, self.substeps, (zk, vk), (z[k + 1], v[k + 1]))
+                    ext_at = self._lin_ext(j, self.substeps, (zk, vk), (z[k + 1], v[k + 1])) if lag is None else lag.ext_at(k, j, self.substeps)
                     if j > 0 and not input_true_i:
                         zj_, vj_ = ext_at(0.0)
                         i_in = i_func(xt=cur_x, zt=zj_, vt=vj_, all_initial=all_initial)
