@@ -1076,6 +1076,47 @@ int32_t psnode_dae_backward_lag_f32(const psnode_dae_bwd_tf_args_f32* args, cons
                                     const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, const psnode_ext_stencil_f32* stencil,
                                     void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Stabilised explicit steps (Runge-Kutta-Chebyshev recurrences) on the generic kernels (additive to ABI 10; DESIGN.md
+ * "Runge-Kutta-Chebyshev steps on K0 / K5").  Every grid interval is ONE step of `stages` right-hand-side evaluations, h = t[k+1] - t[k]:
+ *     Y_0 = the step's start state, F_0 = F(Y_0);   Y_1 = Y_0 + (mu_t[0] h) F_0;
+ *     Y_j = kappa[j-1] Y_0 + mu[j-1] Y_{j-1} + nu[j-1] Y_{j-2} + (mu_t[j-1] h) F(Y_{j-1}) + (gamma_t[j-1] h) F_0,   j = 2 .. stages
+ * summed in the order written, a coefficient that is exactly 0 skipped, fp32, not contracted; the new state is Y_stages.  The externals are
+ * held (the jumped rows behind an event); a DAE that integrates its own i evaluates the head at (Y_{j-1}; z_k, v_k) in front of every
+ * stage j >= 2, as the _sub family does in front of its sub-steps; F_0 is the first stage's evaluation, reused.  x_stage keeps Y_1 ..
+ * Y_{stages-1} of every interval (row (k, j - 1): Y_j), written by a forward call where the pointer is not NULL, read by a backward call.
+ * The entry points take what their _sub siblings take with this struct in the sub-steps struct's place and no tableau; the order of the
+ * checks and the statuses are that family's: a NULL struct is PSNODE_ERR_NULL, stages outside 1..PSNODE_RKC_MAX_STAGES PSNODE_ERR_DIMS
+ * (the coefficients are not looked at: index 0 of kappa / mu / nu / gamma_t is never read); a backward call with stages > 1, T >= 2 and a
+ * NULL x_stage is PSNODE_ERR_NULL; every check returns before a launch.  No stage count forwards to another family.  The backward runs
+ * the recurrence's adjoint stage by stage, last to first; no atomics, bitwise repeatable.  Workspaces: those of the _rk entry points
+ * (psnode_dae_backward_rkc_workspace_size for the DAE backward, in bytes). */
+#define PSNODE_RKC_MAX_STAGES 32
+typedef struct {
+    int32_t stages;                          /* 1..PSNODE_RKC_MAX_STAGES */
+    float kappa[PSNODE_RKC_MAX_STAGES];      /* entry j - 1: the coefficient of stage j */
+    float mu[PSNODE_RKC_MAX_STAGES];
+    float nu[PSNODE_RKC_MAX_STAGES];
+    float mu_t[PSNODE_RKC_MAX_STAGES];
+    float gamma_t[PSNODE_RKC_MAX_STAGES];
+    float* x_stage;                          /* [T-1, stages-1, B, x_dim] or NULL (forward); required by a backward call with stages > 1 */
+} psnode_rkc_f32;
+int32_t psnode_ode_integrate_rkc_supported(const psnode_ode_args_f32* args, const psnode_act_f32* de_act, const psnode_rkc_f32* rkc);
+int32_t psnode_ode_integrate_rkc_f32(const psnode_ode_args_f32* args, const psnode_act_f32* de_act, const psnode_rkc_f32* rkc, void* workspace,
+                                     size_t workspace_bytes, void* stream);
+int32_t psnode_dae_integrate_rkc_supported(const psnode_dae_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                           const psnode_rkc_f32* rkc);
+int32_t psnode_dae_integrate_rkc_f32(const psnode_dae_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                     const psnode_rkc_f32* rkc, void* workspace, size_t workspace_bytes, void* stream);
+int32_t psnode_ode_backward_rkc_supported(const psnode_ode_bwd_args_f32* args, const psnode_act_f32* de_act, const psnode_rkc_f32* rkc);
+int32_t psnode_ode_backward_rkc_f32(const psnode_ode_bwd_args_f32* args, const psnode_act_f32* de_act, const psnode_rkc_f32* rkc, void* workspace,
+                                    size_t workspace_bytes, void* stream);
+int32_t psnode_dae_backward_rkc_supported(const psnode_dae_bwd_tf_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                          const psnode_rkc_f32* rkc);
+size_t psnode_dae_backward_rkc_workspace_size(const psnode_dae_bwd_tf_args_f32* args, const psnode_act_f32* de_act,
+                                              const psnode_act_f32* ae_act, const psnode_rkc_f32* rkc);
+int32_t psnode_dae_backward_rkc_f32(const psnode_dae_bwd_tf_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                    const psnode_rkc_f32* rkc, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -43,6 +43,8 @@ ABI_VERSION = 10         # == PSNODE_ABI_VERSION of include/psnode_hip.h (2: rou
                          #     Adams-Bashforth on K0 / K5;
                          #     additive, same version: the psnode_{ode,dae}_{integrate,backward}_lag_* entry points -- z | v interpolated by the
                          #     polynomial through the up to four neighbouring dataset rows (a stencil table int8 [T-1, B]) on K0 / K5;
+                         #     additive, same version: psnode_rkc_f32 and the psnode_{ode,dae}_{integrate,backward}_rkc_* entry points -- one
+                         #     Runge-Kutta-Chebyshev step per grid interval on K0 / K5;
                          #     additive, same version: the psnode_{ode,dae}_{integrate,backward}_ab3_* entry points -- three-step
                          #     Adams-Bashforth with a predictor-corrector restart step on K0 / K5;
                          #     additive, same version: psnode_segments_f32 and the psnode_{ode,dae}_{integrate,backward}_ms_* entry points --
@@ -97,6 +99,9 @@ EXPORTS = (
     "psnode_ode_integrate_lag_supported", "psnode_ode_integrate_lag_f32", "psnode_dae_integrate_lag_supported", "psnode_dae_integrate_lag_f32",
     "psnode_ode_backward_lag_supported", "psnode_ode_backward_lag_f32",
     "psnode_dae_backward_lag_supported", "psnode_dae_backward_lag_workspace_size", "psnode_dae_backward_lag_f32",
+    "psnode_ode_integrate_rkc_supported", "psnode_ode_integrate_rkc_f32", "psnode_dae_integrate_rkc_supported", "psnode_dae_integrate_rkc_f32",
+    "psnode_ode_backward_rkc_supported", "psnode_ode_backward_rkc_f32",
+    "psnode_dae_backward_rkc_supported", "psnode_dae_backward_rkc_workspace_size", "psnode_dae_backward_rkc_f32",
     "psnode_ode_integrate_ab3_supported", "psnode_ode_integrate_ab3_f32", "psnode_dae_integrate_ab3_supported", "psnode_dae_integrate_ab3_f32",
     "psnode_ode_backward_ab3_supported", "psnode_ode_backward_ab3_f32",
     "psnode_dae_backward_ab3_supported", "psnode_dae_backward_ab3_f32",
@@ -153,6 +158,14 @@ class SubstepsF32(ctypes.Structure):
 
 
 MAX_SUBSTEPS = 1024
+RKC_MAX_STAGES = 32      # == PSNODE_RKC_MAX_STAGES
+
+
+class RkcF32(ctypes.Structure):
+    """psnode_rkc_f32: one Runge-Kutta-Chebyshev step of `stages` evaluations per grid interval -- the five coefficient arrays of the
+    recurrence (entry j - 1: stage j) and the stage rows [T-1, stages-1, B, x_dim] (NULL: a forward call keeps none)."""
+    _fields_ = [("stages", c_int32), ("kappa", ctypes.c_float * RKC_MAX_STAGES), ("mu", ctypes.c_float * RKC_MAX_STAGES), ("nu", ctypes.c_float * RKC_MAX_STAGES),
+                ("mu_t", ctypes.c_float * RKC_MAX_STAGES), ("gamma_t", ctypes.c_float * RKC_MAX_STAGES), ("x_stage", c_void_p)]
 ACT_ELU, ACT_TANH, ACT_SIGMOID, ACT_RELU, ACT_LEAKY_RELU, ACT_SOFTPLUS = 0, 1, 2, 3, 4, 5
 # the pre-activation family (bit 5): derivatives that need the pre-activation u, kept by K5's pre build
 ACT_SILU, ACT_GELU, ACT_GELU_TANH, ACT_MISH = 32, 33, 34, 35
@@ -371,10 +384,10 @@ def load():
                 continue
             query = [ptr(DaeBwdTfArgsF32 if stem == "dae_backward" and f.tf_args else args_t)] + [ptr(ActF32)] * (n_act if f.acts else 0) + \
                     [ptr(RkTableauF32)] * f.tab + [ptr(SubstepsF32)] * f.sub + [ptr(SegmentGroupsF32 if f.par else SegmentsF32)] * f.seg + \
-                    [c_void_p] * f.stencil      # (the device pointer of the int8 [T-1, B] stencil table, or NULL)
+                    [c_void_p] * f.stencil + [ptr(RkcF32)] * f.rkc      # (the device pointer of the int8 [T-1, B] stencil table, or NULL)
             protos = {"supported": (c_int32, query), "f32": (c_int32, query + [c_int32] * f.pt + [c_void_p, c_size_t, c_void_p])}
             if stem == "dae_backward" and f.workspace == "own" and not f.par:      # (the family with a stencil table names its query _workspace_size)
-                protos["workspace_size" if f.stencil else "workspace_bytes"] = (c_size_t, query)
+                protos["workspace_size" if f.stencil or f.rkc else "workspace_bytes"] = (c_size_t, query)
             if f.par and stem in ("ode_backward", "dae_backward"):      # (both directions of the family size their own workspace)
                 protos["workspace_size"] = (c_size_t, query)
             for kind, (restype, argtypes) in protos.items():

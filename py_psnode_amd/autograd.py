@@ -24,7 +24,7 @@ _warned_generic_override = False
 
 def _is_tableau(method) -> bool:
     """A fused.Tableau method trains on K0 + K5 alone: nothing is saved, no specialised or latent kernel is asked."""
-    return isinstance(method, fused.Tableau)
+    return isinstance(method, (fused.Tableau, fused.Recurrence))
 
 
 def _rows_fit(need: int, dev) -> bool:
@@ -318,7 +318,7 @@ class _FusedOdeGeneric(torch.autograd.Function):
 
 # fused.GenericOpts.family ("ab": with per_trajectory) -> the name of its Function: `_FusedOde<name>` / `_FusedDae<name>`, an empty subclass of
 # the model's one body, is what xs.grad_fn reports.  A further family of K0 / K5 that saves sub-state rows adds a row here, not a class.
-_FAMILY_CLASSES = {"sub": "Sub", "lin": "Lin", "lag": "Lag", "pev": "Pev", ("ab", False): "Ab", ("ab", True): "AbPev", ("ab3", False): "Ab3", ("ab3", True): "Ab3Pev", "ms": "Ms", "msp": "Msp"}
+_FAMILY_CLASSES = {"sub": "Sub", "lin": "Lin", "lag": "Lag", "pev": "Pev", ("ab", False): "Ab", ("ab", True): "AbPev", ("ab3", False): "Ab3", ("ab3", True): "Ab3Pev", "ms": "Ms", "msp": "Msp", "rkc": "Rkc"}
 # the families that go to _FusedOde / _FusedDae / _FusedDaeTeacherForced
 _OWN_CLASS = ("plain", "act", "rk")
 # ... and those whose forward (fused.ode_integrate / fused.dae_integrate) is the first to check the call

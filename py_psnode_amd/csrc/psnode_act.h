@@ -282,6 +282,7 @@ struct K0Call {
     int ev_pt, ms_every;           // kBuildAb: the event table is [T-1, B]; kBuildMs: grid point k > 0 with k % ms_every == 0 restarts from row k of x
     int per_group;                 // kBuildMsp: segments per time chunk (the grid is tiles x msp_chunks(T, ms_every, per_group))
     const signed char* stencil;    // kBuildLag: the stencil table int8 [T-1, B], or null (one piece 0 .. T - 1)
+    const psnode_rkc_f32* rkc;     // kBuildRkc: the recurrence's coefficients (sub.n is its stage count, sub.x_sub its stage buffer)
 };
 // K0's launcher (psnode_generic_impl.h), instantiated once per build policy in that policy's object, as K5's generic_backward_launch<B>
 // (psnode_common.h) is: reads of `call` what B's kernels take.  BuildPev: a.ev is the [T-1, B] table and not null; BuildMs, BuildMsp: a.x has all T rows.

@@ -103,6 +103,7 @@ int generic_backward(BuildId build, const GenericBwdCall& c, const ActPair* act,
         case kBuildMsp: return generic_backward_launch<BuildMsp>(c, act, ws, s);
         case kBuildAb3: return generic_backward_launch<BuildAb3>(c, act, ws, s);
         case kBuildLag: return generic_backward_launch<BuildLag>(c, act, ws, s);
+        case kBuildRkc: return generic_backward_launch<BuildRkc>(c, act, ws, s);
     }
     return PSNODE_ERR_UNSUPPORTED;      // (no such build)
 }
@@ -218,7 +219,7 @@ extern "C" int32_t psnode_dae_backward_f32(const psnode_dae_bwd_args_f32* a, voi
     return generic_backward(kBuildElu1, generic_bwd_call(*a), nullptr, workspace, stream);
 }
 
-// ---- The K5 entry-point families psnode_dae_backward_tf_* and psnode_{ode,dae}_backward_{act,rk,sub,lin,lag,pev,ab,ab3,ms,msp}_*: one checked call path
+// ---- The K5 entry-point families psnode_dae_backward_tf_* and psnode_{ode,dae}_backward_{act,rk,sub,lin,lag,pev,ab,ab3,ms,msp,rkc}_*: one checked call path
 // (k5_backward), one query (k5_supported) over the family table of psnode_generic_family.h, which also holds the order of the checks per family.
 namespace {
 constexpr uint32_t kTfFlags = PSNODE_FLAG_INPUT_TRUE_X | PSNODE_FLAG_INPUT_TRUE_I;
@@ -310,6 +311,7 @@ int k5_backward(Family fam, const Args* a, const CallOpts& o, void* workspace, s
     c.substeps = nsub;
     c.x_sub = o.sub ? o.sub->x_sub : nullptr;
     c.stencil = o.stencil;
+    c.rkc = o.rkc;
     c.ab_pt = o.per_trajectory != 0;
     if (f.seg) { c.ms_every = o.every(); c.ms_x_true = o.x_true(); c.ms_per_group = o.per_group(); }
     return generic_backward(family_build(f, act_pair_keeps_u(p)), c, &p, workspace, stream);
@@ -501,6 +503,32 @@ extern "C" int32_t psnode_dae_backward_lag_f32(const psnode_dae_bwd_tf_args_f32*
                                                const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, const psnode_ext_stencil_f32* st,
                                                void* ws, size_t bytes, void* stream) {
     return k5_backward(kFamLag, a, {de_act, ae_act, tab, sub, nullptr, 0, nullptr, st}, ws, bytes, stream);
+}
+
+// (Runge-Kutta-Chebyshev: the adjoint of the recurrence, stage by stage; the _sub family's checks with the stage count in the sub-steps' place)
+extern "C" int32_t psnode_ode_backward_rkc_supported(const psnode_ode_bwd_args_f32* a, const psnode_act_f32* de_act, const psnode_rkc_f32* rkc) {
+    psnode_substeps_f32 s;
+    return k5_supported(kFamRkc, a, {de_act, nullptr, nullptr, rkc_as_sub(rkc, s), nullptr, 0, nullptr, nullptr, rkc});
+}
+extern "C" int32_t psnode_ode_backward_rkc_f32(const psnode_ode_bwd_args_f32* a, const psnode_act_f32* de_act, const psnode_rkc_f32* rkc, void* ws,
+                                               size_t bytes, void* stream) {
+    psnode_substeps_f32 s;
+    return k5_backward(kFamRkc, a, {de_act, nullptr, nullptr, rkc_as_sub(rkc, s), nullptr, 0, nullptr, nullptr, rkc}, ws, bytes, stream);
+}
+extern "C" int32_t psnode_dae_backward_rkc_supported(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act,
+                                                     const psnode_act_f32* ae_act, const psnode_rkc_f32* rkc) {
+    psnode_substeps_f32 s;
+    return k5_supported(kFamRkc, a, {de_act, ae_act, nullptr, rkc_as_sub(rkc, s), nullptr, 0, nullptr, nullptr, rkc});
+}
+extern "C" size_t psnode_dae_backward_rkc_workspace_size(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act,
+                                                         const psnode_act_f32* ae_act, const psnode_rkc_f32* rkc) {
+    psnode_substeps_f32 s;
+    return k5_workspace_bytes(kFamRkc, a, {de_act, ae_act, nullptr, rkc_as_sub(rkc, s), nullptr, 0, nullptr, nullptr, rkc});
+}
+extern "C" int32_t psnode_dae_backward_rkc_f32(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                               const psnode_rkc_f32* rkc, void* ws, size_t bytes, void* stream) {
+    psnode_substeps_f32 s;
+    return k5_backward(kFamRkc, a, {de_act, ae_act, nullptr, rkc_as_sub(rkc, s), nullptr, 0, nullptr, nullptr, rkc}, ws, bytes, stream);
 }
 
 // (three-step Adams-Bashforth with the Heun restart step: the _ab family's prototypes and order of checks)

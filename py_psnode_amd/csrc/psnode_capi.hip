@@ -111,6 +111,7 @@ int dispatch(IntegrateDev& d, bool dae, int kernel, const psnode_mlp_f32* de, co
         case kBuildMsp: e = launch_generic<BuildMsp>(d, dae, call, stream); break;
         case kBuildAb3: e = launch_generic<BuildAb3>(d, dae, call, stream); break;
         case kBuildLag: e = launch_generic<BuildLag>(d, dae, call, stream); break;
+        case kBuildRkc: e = launch_generic<BuildRkc>(d, dae, call, stream); break;
     }
     return ok_or_hip(e);
 }
@@ -198,7 +199,7 @@ int fill_dae(const psnode_dae_args_f32* a, IntegrateDev& d) {
     return PSNODE_OK;
 }
 
-// ---- The K0 entry-point families psnode_{ode,dae}_integrate_{act,rk,sub,lin,lag,pev,ab,ab3,ms,msp}_*: one checked call path (k0_integrate) and one query
+// ---- The K0 entry-point families psnode_{ode,dae}_integrate_{act,rk,sub,lin,lag,pev,ab,ab3,ms,msp,rkc}_*: one checked call path (k0_integrate) and one query
 // (k0_supported) over the family table of psnode_generic_family.h, which also holds the order of the checks per family.
 // the ODE / DAE difference: the side outputs, the recipe widths, fill_*, the AE, the plain entry point
 bool side_outputs(const psnode_ode_args_f32& a) { return a.save_act || a.save_xstage; }
@@ -252,6 +253,7 @@ int k0_integrate(Family fam, const Args* args, const CallOpts& o, void* workspac
     call.per_group = o.per_group();
     call.sub = SubDev{family_substeps(f, o), o.sub ? o.sub->x_sub : nullptr};
     call.stencil = o.stencil;
+    call.rkc = o.rkc;
     return dispatch(d, ae_of(c) != nullptr, c.kernel, &c.de, ae_of(c), workspace, workspace_bytes, static_cast<hipStream_t>(stream), call);
 }
 
@@ -534,6 +536,27 @@ int32_t psnode_dae_integrate_ab3_supported(const psnode_dae_args_f32* a, const p
 int32_t psnode_dae_integrate_ab3_f32(const psnode_dae_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
                                     int32_t per_trajectory, void* ws, size_t bytes, void* stream) {
     return k0_integrate(kFamAb3, args, {de_act, ae_act, nullptr, nullptr, nullptr, per_trajectory}, ws, bytes, stream);
+}
+
+// (Runge-Kutta-Chebyshev: one s-stage step per grid interval; the _sub family's checks with the stage count in the sub-steps' place)
+int32_t psnode_ode_integrate_rkc_supported(const psnode_ode_args_f32* a, const psnode_act_f32* de_act, const psnode_rkc_f32* rkc) {
+    psnode_substeps_f32 s;
+    return k0_supported(kFamRkc, a, {de_act, nullptr, nullptr, rkc_as_sub(rkc, s), nullptr, 0, nullptr, nullptr, rkc});
+}
+int32_t psnode_ode_integrate_rkc_f32(const psnode_ode_args_f32* args, const psnode_act_f32* de_act, const psnode_rkc_f32* rkc, void* ws, size_t bytes,
+                                     void* stream) {
+    psnode_substeps_f32 s;
+    return k0_integrate(kFamRkc, args, {de_act, nullptr, nullptr, rkc_as_sub(rkc, s), nullptr, 0, nullptr, nullptr, rkc}, ws, bytes, stream);
+}
+int32_t psnode_dae_integrate_rkc_supported(const psnode_dae_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                           const psnode_rkc_f32* rkc) {
+    psnode_substeps_f32 s;
+    return k0_supported(kFamRkc, a, {de_act, ae_act, nullptr, rkc_as_sub(rkc, s), nullptr, 0, nullptr, nullptr, rkc});
+}
+int32_t psnode_dae_integrate_rkc_f32(const psnode_dae_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                     const psnode_rkc_f32* rkc, void* ws, size_t bytes, void* stream) {
+    psnode_substeps_f32 s;
+    return k0_integrate(kFamRkc, args, {de_act, ae_act, nullptr, rkc_as_sub(rkc, s), nullptr, 0, nullptr, nullptr, rkc}, ws, bytes, stream);
 }
 
 // (multiple shooting: grid point k > 0 with k % seg->every == 0 restarts from row k of the args' x, which then holds all T rows)

@@ -322,6 +322,7 @@ struct GenericBwdCall {
     const float* ms_x_true;    //   k % ms_every == 0 restarted from the dataset row ms_x_true[k] ([T, B, xd]; may be null where T - 1 <= ms_every)
     int ms_per_group;          // generic_backward_launch<BuildMsp> (BuildMs's call): segments per time chunk of its tiles x chunks grid
     const signed char* stencil;      // generic_backward_launch<BuildLag> (BuildLin's call): the stencil table int8 [T-1, B], or null
+    const psnode_rkc_f32* rkc;       // generic_backward_launch<BuildRkc> (BuildSub's call with a one-stage rk): the recurrence's coefficients; substeps is its stage count
 };
 struct ActPair;     // psnode_act.h: the DE's and the AE's activation of a non-ELU(1) call
 size_t generic_bwd_workspace_floats(const psnode_mlp_f32* de, const psnode_mlp_f32* ae, long long B);

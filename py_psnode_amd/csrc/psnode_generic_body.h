@@ -246,7 +246,7 @@
                     kbuf[nx + tid] = restart ? 0.0f : -(h * half_rho);
                     hp = h;
                 }
-            } else if constexpr (Bd::sub) { if (tid < TB) dts[tid] = (tn - tc) / (float)nsub; }
+            } else if constexpr (Bd::sub) { if (tid < TB) dts[tid] = Bd::rkc ? tn - tc : (tn - tc) / (float)nsub; }
             else { if (tid < TB) dts[tid] = tn - tc; }
             for (int idx = tid; idx < nzv * TB; idx += NT) {
                 const int r = idx / TB, c = idx % TB;
@@ -413,6 +413,11 @@
             }
             const int s_ = e - 1;
             const bool final_stage = s_ + 1 == nstage;
+            // Runge-Kutta-Chebyshev (Bd::rkc; one evaluation per pass, nsub = the stage count): pass si.i forms Y_j, j = si.i + 1, from Y_0, Y_{j-1},
+            // Y_{j-2}, F_0 and the fresh slope.  Y_{j-1} is where a sub-step's start state lives (xsrc); Y_0, Y_{j-2} and F_0 take kbuf's slots
+            // 0, 1 and 2, which a one-stage pass never writes -- each element written and read by the thread that owns it.
+            [[maybe_unused]] RkcCoef rc{};
+            if constexpr (Bd::rkc) rc = rkc_coef(sub, si.i);
             float c0 = 0.0f, c1 = 0.0f, c2 = 0.0f, c3 = 0.0f;
             if constexpr (Bd::rk) {
             // the tableau row this pass applies to k_0 .. k_s (uniform): a[s + 1][.] -- the next stage's argument -- or, behind the last
@@ -481,6 +486,21 @@
                 const float x0 = xsrc[idx];
                 const float ks = lds[f + qi(r, c)];
                 float v;
+                if constexpr (Bd::rkc) {
+                    // the terms in the order written, a coefficient that is exactly 0 skipped (psnode_rkc_f32); x0 is Y_{j-1}
+                    if (si.first()) {
+                        kbuf[idx] = x0;
+                        kbuf[2 * nx + idx] = ks;
+                        v = x0 + (rc.mut * h) * ks;
+                    } else {
+                        v = rc.mu * x0;
+                        if (rc.kap != 0.0f) v = rc.kap * kbuf[idx] + v;
+                        if (rc.nu != 0.0f) v = v + rc.nu * kbuf[nx + idx];
+                        v = v + (rc.mut * h) * ks;
+                        if (rc.gam != 0.0f) v = v + (rc.gam * h) * kbuf[2 * nx + idx];
+                    }
+                    kbuf[nx + idx] = x0;
+                } else
                 if constexpr (Bd::rk) {
                 // v = x0 + h * sum_j c_j k_j in increasing j, zero coefficients skipped (psnode_rk_tableau_f32); k_s is this stage's slope
                 if (s_ < 3 && !final_stage) kbuf[s_ * nx + idx] = ks;

@@ -8,6 +8,8 @@
 #include <hip/hip_runtime.h>
 #include <type_traits>
 
+#include "psnode_hip.h"
+
 namespace psnode {
 
 // Sub-steps per grid interval (psnode_substeps_f32, include/psnode_hip.h), as the sub-step builds of K0 / K5 take them: one further kernel
@@ -47,6 +49,16 @@ struct LagDev {
     const signed char* stencil;
 };
 __host__ __device__ inline int ev_table_pt(const LagDev&) { return 0; }
+// What the Runge-Kutta-Chebyshev builds of K0 / K5 take in SubDev's place (psnode_rkc_f32, include/psnode_hip.h): n is the stage count of the
+// ONE step every grid interval takes, x_sub [T-1, n-1, B, xd] keeps Y_1 .. Y_{n-1} of every interval (row (k, j - 1): Y_j), and the five
+// coefficient arrays of the recurrence (entry j - 1: stage j) travel with the argument -- a stage pass reads its row through rkc_coef.
+constexpr int kRkcMaxStages = 32;
+struct RkcDev {
+    int n;
+    float* x_sub;
+    float kap[kRkcMaxStages], mu[kRkcMaxStages], nu[kRkcMaxStages], mut[kRkcMaxStages], gam[kRkcMaxStages];
+};
+__host__ __device__ inline int ev_table_pt(const RkcDev&) { return 0; }
 template <class S> __host__ __device__ inline const signed char* lag_table(const S&) { return nullptr; }
 __host__ __device__ inline const signed char* lag_table(const LagDev& s) { return s.stencil; }
 // (asked through overloads for the reason above)
@@ -153,8 +165,19 @@ __device__ __forceinline__ float lag_eval(const LagW& w, int q, float n0, float 
     return acc;
 }
 
+// The coefficients of stage j = j0 + 1 of the Runge-Kutta-Chebyshev builds (Bd::rkc), wave-uniform: Y_j = kap Y_0 + mu Y_{j-1} + nu Y_{j-2} +
+// (mut h) F(Y_{j-1}) + (gam h) F_0; stage 1 reads mut alone.  One function for K0 and K5: the same values, read the same way.  j0 is
+// launch-uniform (the stage loop's counter), so the reads are scalar loads from the kernel's argument segment.
+struct RkcCoef { float kap, mu, nu, mut, gam; };
+template <class S> __device__ __forceinline__ RkcCoef rkc_coef(const S&, int) { return RkcCoef{0.0f, 0.0f, 0.0f, 0.0f, 0.0f}; }
+__device__ __forceinline__ RkcCoef rkc_coef(const RkcDev& s, int j0) {
+    auto u = [](float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); };
+    const int j = __builtin_amdgcn_readfirstlane(j0) & (kRkcMaxStages - 1);      // (the host checks the stage count; the mask keeps any index inside the arrays)
+    return RkcCoef{u(s.kap[j]), u(s.mu[j]), u(s.nu[j]), u(s.mut[j]), u(s.gam[j])};
+}
+
 template <bool ACT, bool PRE, bool RK, bool SUB = false, bool LIN = false, bool PEV = false, bool AB = false, bool MS = false, bool PAR = false,
-          bool AB3 = false, bool LAG = false>
+          bool AB3 = false, bool LAG = false, bool RKC = false>
 struct GenericBuild {
     static constexpr bool act = ACT;      // the hidden-layer activation is a kernel argument (ActPair, psnode_act.h), not ELU(1)
     static constexpr bool pre = PRE;      // the hidden layers' pre-activations u are kept next to h (SiLU / GELU / Mish differentiate from u)
@@ -171,13 +194,15 @@ struct GenericBuild {
                                           // point k + 1 (AbDev; needs ab)
     static constexpr bool lag = LAG;      // the interpolant of lin is the polynomial through the up to four neighbouring dataset rows of the interval's
                                           // piece, by the stencil table (LagDev; needs lin)
+    static constexpr bool rkc = RKC;      // every grid interval is one s-stage Runge-Kutta-Chebyshev step: the sub-step loop with one evaluation per pass, the
+                                          // three-term recurrence in the sub-step update's place, h undivided (RkcDev; needs sub, a one-stage tableau)
     static constexpr int lin_layout = LAG ? 2 : (LIN ? 1 : 0);      // the LDS layout the fit queries count: none, lin's regions, lag's
     static constexpr bool par = PAR;      // segments in parallel: the launch grid is tiles x chunks, workgroup (tile, c) runs the segments of time chunk c
                                           // alone (MspDev; needs ms)
     // The kernels' arguments behind the args struct, each a by-value parameter of its own: ActPair (act) | psnode_rk_tableau_f32 (rk) | Sub (sub).
     // A kernel without one of them names the never-read default of kernel_arg in its place.
     static constexpr int n_extra = SUB ? 3 : (RK ? 2 : (ACT ? 1 : 0));
-    using Sub = std::conditional_t<LAG, LagDev, std::conditional_t<AB, AbDev, std::conditional_t<PAR, MspDev, std::conditional_t<MS, MsDev, SubDev>>>>;
+    using Sub = std::conditional_t<RKC, RkcDev, std::conditional_t<LAG, LagDev, std::conditional_t<AB, AbDev, std::conditional_t<PAR, MspDev, std::conditional_t<MS, MsDev, SubDev>>>>>;
     // K5's waves per SIMD: the fully streamed instances (STR 2) that fitted 256 registers keep two workgroups per CU -- every one of the
     // act build, the ELU(1) build's with the accumulators in LDS, none of the builds that keep u
     static constexpr int two_waves(bool gg, int str) { return PRE ? 1 : (str == 2 && (ACT || !gg) ? 2 : 1); }
@@ -208,7 +233,15 @@ __host__ __device__ constexpr decltype(auto) kernel_arg(const D& dflt, const E0&
 // The policy's Sub argument from what a call carries, for both directions (K0 writes x_sub and has no x_true; K5 reads both)
 template <class B>
 typename B::Sub build_sub(int n, float* x_sub, int ev_pt, int ms_every, const float* x_true, int per_group = 1, float* ga0_part = nullptr,
-                          float* border = nullptr, const signed char* stencil = nullptr) {
+                          float* border = nullptr, const signed char* stencil = nullptr, const psnode_rkc_f32* rkc = nullptr) {
+    if constexpr (B::rkc) {
+        RkcDev r{};
+        r.n = n;
+        r.x_sub = x_sub;
+        if (rkc)
+            for (int j = 0; j < kRkcMaxStages; ++j) { r.kap[j] = rkc->kappa[j]; r.mu[j] = rkc->mu[j]; r.nu[j] = rkc->nu[j]; r.mut[j] = rkc->mu_t[j]; r.gam[j] = rkc->gamma_t[j]; }
+        return r;
+    } else
     if constexpr (B::lag) return LagDev{n, x_sub, stencil};
     else if constexpr (B::ab) return AbDev{1, nullptr, ev_pt};
     else if constexpr (B::par) return MspDev{n, x_sub, ms_every, x_true, per_group, ga0_part, border};
@@ -228,6 +261,7 @@ using BuildMs = GenericBuild<true, true, true, true, false, false, false, true>;
 using BuildMsp = GenericBuild<true, true, true, true, false, false, false, true, true>;      // BuildMs's policy with the segments spread over workgroups: a tiles x chunks grid
 using BuildAb3 = GenericBuild<true, true, true, true, false, true, true, false, false, true>;      // BuildAb's policy as Adams-Bashforth 3 with the Heun restart step
 using BuildLag = GenericBuild<true, true, true, true, true, false, false, false, false, false, true>;      // BuildLin's policy with the four-point Lagrange interpolant of the stencil table
-enum BuildId { kBuildElu1, kBuildAct, kBuildPre, kBuildRk, kBuildSub, kBuildLin, kBuildPev, kBuildAb, kBuildMs, kBuildMsp, kBuildAb3, kBuildLag };      // what a call names its build with
+using BuildRkc = GenericBuild<true, true, true, true, false, false, false, false, false, false, false, true>;      // BuildSub's policy as one Runge-Kutta-Chebyshev step per interval: the stage count in the sub-steps' place
+enum BuildId { kBuildElu1, kBuildAct, kBuildPre, kBuildRk, kBuildSub, kBuildLin, kBuildPev, kBuildAb, kBuildMs, kBuildMsp, kBuildAb3, kBuildLag, kBuildRkc };      // what a call names its build with
 
 }  // namespace psnode

@@ -321,7 +321,7 @@
             h_n = h;
             la_tm = a.t.p[(k >= 2 ? k - 2 : 0) * a.t.st + gb(tid % TB) * a.t.sb];      // t[(k - 1) - 1], for the next step of the sweep
             ev_n = ev;
-        } else if constexpr (Bd::sub) { if (tid < TB) dts[tid] = (la_tn - la_t) / (float)nsub; }
+        } else if constexpr (Bd::sub) { if (tid < TB) dts[tid] = Bd::rkc ? la_tn - la_t : (la_tn - la_t) / (float)nsub; }
         else { if (tid < TB) dts[tid] = la_tn - la_t; }
         [[maybe_unused]] bool ms_rs = false;         // (Bd::ms) this step left a restart point
         if constexpr (Bd::ms) {
@@ -548,6 +548,26 @@
                 gks[r * TP + c] = phi;
                 gks[3 * nx + r * TP + c] = gks[nx + r * TP + c];      // g_{k+2} -> g_{k+3}, g_{k+1} -> g_{k+2} for step k - 1: this thread's alone
                 gks[nx + r * TP + c] = g1;
+            } else if constexpr (Bd::rkc) {
+                // Runge-Kutta-Chebyshev (Bd::rkc; one stage per pass, nsub = the stage count): this pass is stage j = nsub - si.i, g1 the adjoint
+                // lam of Y_j.  The DE's VJP at Y_{j-1} takes (mut_j h) lam, at j = 1 plus the adjoint of F_0; gx0, the adjoint of Y_{j-1}, starts
+                // from what the later stages left it (nu_{j+1} lam_{j+1}, in gks' slot 1) plus mu_j lam, and the VJP and the head add to it; slot 1
+                // then takes nu_j lam for Y_{j-2}, slots 2 / 3 collect the adjoints of Y_0 (kap_j lam) and F_0 ((gam_j h) lam).  Stage 1's Y_{j-1}
+                // is Y_0: its adjoint takes slot 2 and lam.  The slots are unwritten in front of the interval's first pass, which reads none.
+                const RkcCoef rc = rkc_coef(sub, nsub - 1 - si.i);
+                const bool top = si.first();
+                const float pj = top ? 0.0f : gks[nx + r * TP + c], gy0 = top ? 0.0f : gks[2 * nx + r * TP + c], gf0 = top ? 0.0f : gks[3 * nx + r * TP + c];
+                const float hl = (rc.mut * dts[c]) * g1;
+                if (!si.last()) {
+                    gks[r * TP + c] = hl;
+                    gx0[r * TP + c] = pj + rc.mu * g1;
+                    gks[nx + r * TP + c] = rc.nu * g1;
+                    gks[2 * nx + r * TP + c] = gy0 + rc.kap * g1;
+                    gks[3 * nx + r * TP + c] = gf0 + (rc.gam * dts[c]) * g1;
+                } else {
+                    gks[r * TP + c] = hl + gf0;
+                    gx0[r * TP + c] = (pj + gy0) + g1;
+                }
             } else if constexpr (Bd::ab) {      // phi_k; g_{k+2}'s slot is unwritten at the first step of the sweep, where c1 is 0
                 const float c1n = gks[2 * nx + c];
                 float phi = dts[c] * g1;

@@ -856,7 +856,7 @@ int generic_backward_launch(const GenericBwdCall& c, const ActPair* act, float* 
     };
     hipError_t e;
     if constexpr (Pol::par) e = go(*act, *c.rk, build_sub<Pol>(c.substeps, const_cast<float*>(c.x_sub), 0, c.ms_every, c.ms_x_true, c.ms_per_group, ga0_part, border));
-    else if constexpr (Pol::sub) e = go(*act, *c.rk, build_sub<Pol>(c.substeps, const_cast<float*>(c.x_sub), c.ab_pt ? 1 : 0, c.ms_every, c.ms_x_true, 1, nullptr, nullptr, c.stencil));
+    else if constexpr (Pol::sub) e = go(*act, *c.rk, build_sub<Pol>(c.substeps, const_cast<float*>(c.x_sub), c.ab_pt ? 1 : 0, c.ms_every, c.ms_x_true, 1, nullptr, nullptr, c.stencil, c.rkc));
     else if constexpr (Pol::rk) e = go(*act, *c.rk);
     else if constexpr (Pol::act) e = go(*act);
     else e = go();

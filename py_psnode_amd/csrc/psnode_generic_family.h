@@ -11,7 +11,7 @@
 //   workspace | [K0, in dispatch] T, B, LDS fit of the build.
 //   _msp: the _ms family's sequence with psnode_segment_groups_f32 in the segments struct's place; more than 65535 chunks (the grid's second
 //   dimension) are PSNODE_ERR_UNSUPPORTED with the route; [K5] its workspace is its own layout's (gbwd_msp_layout).
-//   _tf [K5; K0 has no such wrapper]: flags == 0 is the plain entry point, in front of all of it.  _rk, _ab and _ab3 do not read `method` (K0's copy
+//   _tf [K5; K0 has no such wrapper]: flags == 0 is the plain entry point, in front of all of it.  _rk, _ab, _ab3 and _rkc do not read `method` (K0's copy
 //   of the args carries EULER); _lag is _lin's sequence (the stencil table is not checked: NULL is valid); _pev's event_idx is the [T-1, B] table (event-less calls take the other families), _ab's and _ab3's may be NULL.
 //   [K0] route (k0_route_ok): kernel AUTO / GENERIC and no training side outputs -- the _act family looks at save_act alone (a lone
 //   save_xstage is fill_*'s status); _ms needs the DAE's x view (the restarts read its rows).  A call without a tableau leaves a bad method
@@ -30,7 +30,7 @@
 
 namespace psnode {
 
-enum Family { kFamTf, kFamAct, kFamRk, kFamSub, kFamLin, kFamPev, kFamAb, kFamMs, kFamMsp, kFamAb3, kFamLag };
+enum Family { kFamTf, kFamAct, kFamRk, kFamSub, kFamLin, kFamPev, kFamAb, kFamMs, kFamMsp, kFamAb3, kFamLag, kFamRkc };
 // the tableau: no argument, `method` is read | NULL is PSNODE_ERR_NULL | NULL is the args' method as one | no argument, always one stage
 enum Tab { kTabNone, kTabRequired, kTabOrMethod, kTabOneStage };
 // the sub-steps struct: no argument | NULL is PSNODE_ERR_NULL | NULL is one sub-step
@@ -60,6 +60,7 @@ constexpr FamilyRow kFamilies[] = {
     /* _msp */ {kBuildMsp,  false, kTabOrMethod, kSubOrOne,    false,  true,  false, true,  true,  true,  false, true},      // (_ms over a tiles x chunks grid)
     /* _ab3 */ {kBuildAb3,  false, kTabOneStage, kSubNone,     false,  false, false, true,  true,  true,  false},      // (_ab's row: the same arguments, checks and fit)
     /* _lag */ {kBuildLag,  false, kTabOrMethod, kSubOrOne,    false,  false, false, false, true,  true,  2},          // (_lin's row and the stencil table, which may be NULL; its own layout)
+    /* _rkc */ {kBuildRkc,  false, kTabOneStage, kSubRequired, false,  false, false, false, true,  true,  false},      // (_sub's row without a tableau and without the demotion: the stage count in the sub-steps' place, rkc_as_sub)
 };
 struct CallOpts {      // what a call carries behind its args; a family's wrappers leave what it does not take at NULL / 0
     const psnode_act_f32 *de_act, *ae_act;
@@ -69,12 +70,21 @@ struct CallOpts {      // what a call carries behind its args; a family's wrappe
     int per_trajectory;      // _ab, _ab3: a non-NULL event_idx is the [T-1, B] table (else the shared [T-1])
     const psnode_segment_groups_f32* grp;      // _msp: in seg's place
     const psnode_ext_stencil_f32* stencil;     // _lag: the stencil table [T-1, B], or NULL (one piece 0 .. T - 1 for every trajectory)
+    const psnode_rkc_f32* rkc;                 // _rkc: the recurrence; its wrappers hand `sub` what rkc_as_sub makes of it
     // what a family with segments reads, from whichever of the two structs it takes
     bool has_seg() const { return seg || grp; }
     int every() const { return grp ? grp->every : seg->every; }
     const float* x_true() const { return grp ? grp->x_true : seg->x_true; }
     int per_group() const { return grp ? grp->per_group : 1; }
 };
+// The _rkc family's struct as the sub-steps struct the shared checks read: NULL stays NULL (PSNODE_ERR_NULL), a stage count outside
+// 1 .. PSNODE_RKC_MAX_STAGES becomes the sub-step count 0 (PSNODE_ERR_DIMS, what a bad sub-step count gets), x_stage is x_sub.
+inline const psnode_substeps_f32* rkc_as_sub(const psnode_rkc_f32* r, psnode_substeps_f32& s) {
+    if (!r) return nullptr;
+    s.substeps = r->stages >= 1 && r->stages <= PSNODE_RKC_MAX_STAGES ? r->stages : 0;
+    s.x_sub = r->x_stage;
+    return &s;
+}
 // the time chunks of a segment-parallel call (1 for every other family)
 inline long long family_chunks(const FamilyRow& f, const CallOpts& o, long long T) { return f.par ? msp_chunks(T, o.every(), o.per_group()) : 1; }
 constexpr long long kMaxChunks = 65535;      // (the launch grid's second dimension)

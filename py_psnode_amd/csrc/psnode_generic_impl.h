@@ -599,7 +599,7 @@ hipError_t launch_generic(const IntegrateDev& a, bool dae, const K0Call& call, h
                                        build_sub<B>(call.sub.n, call.sub.x_sub, call.ev_pt, call.ms_every, nullptr, call.per_group));
     } else if constexpr (B::sub) {
         return launch_generic_build<B>(a, dae, 1u, stream, call.act, call.rk,
-                                       build_sub<B>(call.sub.n, call.sub.x_sub, call.ev_pt, call.ms_every, nullptr, 1, nullptr, nullptr, call.stencil));
+                                       build_sub<B>(call.sub.n, call.sub.x_sub, call.ev_pt, call.ms_every, nullptr, 1, nullptr, nullptr, call.stencil, call.rkc));
     } else if constexpr (B::rk) return launch_generic_build<B>(a, dae, 1u, stream, call.act, call.rk);
     else if constexpr (B::act) return launch_generic_build<B>(a, dae, 1u, stream, call.act);
     else return launch_generic_build<B>(a, dae, 1u, stream);

@@ -7,6 +7,7 @@ import dataclasses
 import functools
 import math
 import os
+import struct
 import weakref
 from typing import List, Optional, Sequence, Tuple
 
@@ -81,6 +82,112 @@ class Tableau:
         return self.name
 
 
+@dataclasses.dataclass(frozen=True)
+class Recurrence:
+    """A stabilised explicit step given by a three-term recurrence (Runge-Kutta-Chebyshev), the `method` of neural_dae.RKC1 / RKC2 and a
+    sibling of Tableau: one step of `stages` right-hand-side evaluations per grid interval,
+        Y_1 = Y_0 + (mu_t[0] h) F_0;   Y_j = kappa[j-1] Y_0 + mu[j-1] Y_{j-1} + nu[j-1] Y_{j-2} + (mu_t[j-1] h) F(Y_{j-1}) + (gamma_t[j-1] h) F_0
+    summed in the order written, a coefficient that is exactly 0 skipped.  `table` is `rkc_table`'s dict: the fp32-rounded coefficients (as
+    Python floats; THEY are the method, the walk and the kernels read the same values), the nodes c and the real stability boundary beta.
+    Frozen and hashable (by name, stages, order and the coefficient tuples)."""
+    name: str
+    stages: int
+    order: int
+    kappa: tuple
+    mu: tuple
+    nu: tuple
+    mu_t: tuple
+    gamma_t: tuple
+    c: tuple = dataclasses.field(compare=False, default=())
+    beta: float = dataclasses.field(compare=False, default=0.0)
+
+    def abi(self, x_stage=None) -> "_lib.RkcF32":
+        r = _lib.RkcF32()
+        r.stages = self.stages
+        for j in range(self.stages):
+            r.kappa[j], r.mu[j], r.nu[j], r.mu_t[j], r.gamma_t[j] = self.kappa[j], self.mu[j], self.nu[j], self.mu_t[j], self.gamma_t[j]
+        r.x_stage = x_stage
+        return r
+
+    def __str__(self):
+        return self.name
+
+
+def _f32(q: float) -> float:
+    """q rounded once to fp32, as a Python float."""
+    return struct.unpack("f", struct.pack("f", q))[0]
+
+
+def rkc_table(stages, order, damping=None) -> Recurrence:
+    """The Runge-Kutta-Chebyshev method of `stages` stages (1..32; order 2: 2..32) and `order` 1 or 2 with damping eps (default 0.05 /
+    2/13): the coefficients from the Chebyshev recurrences T_j, T_j', T_j'' at w0 = 1 + eps / s^2 in fp64, rounded once to fp32.
+    order 1: w1 = T_s / T_s', mu_t_1 = w1 / w0, mu_j = 2 w0 T_{j-1} / T_j, nu_j = -T_{j-2} / T_j, mu_t_j = 2 w1 T_{j-1} / T_j, gamma_t = kappa = 0,
+    c_j = T_s T_j' / (T_s' T_j), beta = (1 + w0) T_s' / T_s.   order 2: w1 = T_s' / T_s'', b_j = T_j'' / T_j'^2 (b_0 = b_1 = b_2),
+    a_j = 1 - b_j T_j, mu_t_1 = b_1 w1, mu_j = 2 b_j w0 / b_{j-1}, nu_j = -b_j / b_{j-2}, mu_t_j = 2 b_j w1 / b_{j-1}, gamma_t_j = -a_{j-1} mu_t_j,
+    kappa_j = 1 - mu_j - nu_j, c_1 = c_2 / T_2', c_j = T_s' T_j'' / (T_s'' T_j'), beta = (1 + w0) T_s'' / T_s'.  Entry j - 1 of a tuple is
+    stage j; entry 0 of kappa / mu / nu / gamma_t is 0 and never read.  kappa_j + mu_j + nu_j = 1 holds exactly for the ROUNDED values: the
+    last of the three is taken from the rounded others (nu_j = 1 - mu_j at order 1, kappa_j = 1 - mu_j - nu_j at order 2)."""
+    if isinstance(stages, bool) or not isinstance(stages, int):
+        raise ValueError(f"stages must be an int, got {stages!r}")
+    if order not in (1, 2) or isinstance(order, bool):
+        raise ValueError(f"order must be 1 or 2, got {order!r}")
+    if not (1 if order == 1 else 2) <= stages <= _lib.RKC_MAX_STAGES:
+        raise ValueError(f"RKC{order}: stages must be in {1 if order == 1 else 2}..{_lib.RKC_MAX_STAGES}, got {stages!r}")
+    if damping is not None and (isinstance(damping, bool) or not isinstance(damping, (int, float))):
+        raise ValueError(f"damping must be a finite number > 0, got {damping!r}")
+    eps = (0.05 if order == 1 else 2.0 / 13.0) if damping is None else float(damping)
+    if not (eps > 0.0 and math.isfinite(eps)):
+        raise ValueError(f"damping must be a finite number > 0, got {damping!r}")
+    return _rkc_table(stages, order, eps)      # (validated first: the cache hashes its arguments)
+
+
+@functools.lru_cache(maxsize=128)
+def _rkc_table(s: int, order: int, eps: float) -> Recurrence:
+    w0 = 1.0 + eps / (s * s)
+    T, dT, ddT = [1.0, w0], [0.0, 1.0], [0.0, 0.0]
+    for j in range(2, s + 1):
+        T.append(2.0 * w0 * T[j - 1] - T[j - 2])
+        dT.append(2.0 * T[j - 1] + 2.0 * w0 * dT[j - 1] - dT[j - 2])
+        ddT.append(4.0 * dT[j - 1] + 2.0 * w0 * ddT[j - 1] - ddT[j - 2])
+    kappa, mu, nu, mu_t, gamma_t, c = [0.0] * s, [0.0] * s, [0.0] * s, [0.0] * s, [0.0] * s, [0.0] * s
+    if order == 1:
+        w1 = T[s] / dT[s]
+        mu_t[0] = w1 / w0
+        for j in range(2, s + 1):
+            mu[j - 1] = 2.0 * w0 * T[j - 1] / T[j]
+            nu[j - 1] = -T[j - 2] / T[j]
+            mu_t[j - 1] = 2.0 * w1 * T[j - 1] / T[j]
+        for j in range(1, s + 1):
+            c[j - 1] = T[s] * dT[j] / (dT[s] * T[j])
+        beta = (1.0 + w0) * dT[s] / T[s]
+    else:
+        w1 = dT[s] / ddT[s]
+        b = [0.0, 0.0] + [ddT[j] / (dT[j] * dT[j]) for j in range(2, s + 1)]
+        b[0] = b[1] = b[2]
+        a = [1.0 - b[j] * T[j] for j in range(s + 1)]
+        mu_t[0] = b[1] * w1
+        for j in range(2, s + 1):
+            mu[j - 1] = 2.0 * b[j] * w0 / b[j - 1]
+            nu[j - 1] = -b[j] / b[j - 2]
+            mu_t[j - 1] = 2.0 * b[j] * w1 / b[j - 1]
+            gamma_t[j - 1] = -a[j - 1] * mu_t[j - 1]
+            kappa[j - 1] = 1.0 - mu[j - 1] - nu[j - 1]
+            c[j - 1] = dT[s] * ddT[j] / (ddT[s] * dT[j])
+        c[0] = c[1] / dT[2]
+        beta = (1.0 + w0) * ddT[s] / dT[s]
+    # The rounded values are the method, so the consistency condition kappa_j + mu_j + nu_j = 1 (a constant state stays constant: R(0) = 1,
+    # not 1 + 6e-8) is made to hold FOR them: the last of the three is 1 minus the rounded others -- nu_j at order 1, where kappa_j is 0 by
+    # definition, kappa_j at order 2 -- which is exact in fp32 (a multiple of 2^-24 below 1 in magnitude) and moves it by a rounding error.
+    mu = [_f32(q) for q in mu]
+    if order == 1:
+        nu = [0.0] + [1.0 - mu[j] for j in range(1, s)]
+    else:
+        nu = [_f32(q) for q in nu]
+        kappa = [0.0] + [1.0 - mu[j] - nu[j] for j in range(1, s)]
+    r32 = lambda q: tuple(_f32(v) for v in q)
+    return Recurrence(f"RKC{order}(stages={s})", s, order, r32(kappa), r32(mu), r32(nu), r32(mu_t), r32(gamma_t), tuple(c), beta)
+
+
 AB2 = "ab2"      # the `method` value of two-step Adams-Bashforth (neural_dae.AB2): the _ab entry points of K0 / K5, no other kernel
 
 
@@ -102,6 +209,8 @@ def method_info(method):
     evaluation per step; its calls go to the _ab entry points, which do not read the id either)."""
     if isinstance(method, Tableau):
         return _lib.EULER, method.stages, method
+    if isinstance(method, Recurrence):      # (one evaluation per stage pass; the stage count travels in the sub-steps' place: GenericOpts.of)
+        return _lib.EULER, 1, method
     if is_ab(method):
         return _lib.EULER, 1, None
     return METHOD_ID[method], STAGES[method], None
@@ -109,6 +218,9 @@ def method_info(method):
 
 def builtin_method(method, what: str):
     """(method id, stages) for the specialised kernels, which carry the three built-in formulas only: a Tableau is refused."""
+    if isinstance(method, Recurrence):
+        raise _lib.UnsupportedShapeError(f"{what}: a Runge-Kutta-Chebyshev recurrence ({method.name}) runs on the generic kernels K0 / K5 only "
+                                         "(kernel 'auto' / 'generic', no saved rows); this entry point carries euler / midpoint / rk4")
     if isinstance(method, Tableau):
         raise _lib.UnsupportedShapeError(f"{what}: a Runge-Kutta tableau ({method.name}) runs on the generic kernels K0 / K5 only "
                                          "(kernel 'auto' / 'generic', no saved rows); this entry point carries euler / midpoint / rk4")
@@ -259,7 +371,8 @@ def _act_ptrs(acts):
 # its "own", or the "rk" family's (the same policy, so the same fit, checks and layout for any sub-steps).  par: the segments struct is
 # psnode_segment_groups_f32, and both backward stems size their workspace with the family's own psnode_<stem>_<family>_workspace_size.
 # stencil: behind the structs comes the device pointer of the int8 [T-1, B] stencil table (`lagrange_stencils`), or NULL.
-Family = collections.namedtuple("Family", "acts tab sub seg pt tf_args x_sub workspace par stencil", defaults=(True, False, False, False, False, True, False, "own", False, False))
+# rkc: behind the acts comes the psnode_rkc_f32 alone (the recurrence with the stage rows, `Recurrence.abi`); its dae_backward query is _workspace_size.
+Family = collections.namedtuple("Family", "acts tab sub seg pt tf_args x_sub workspace par stencil rkc", defaults=(True, False, False, False, False, True, False, "own", False, False, False))
 # The Python counterpart of kFamilies (csrc/psnode_generic_family.h): `GenericOpts`, `call_generic` and the prototypes of _lib.load read it.
 # "plain": the entry points without a family in their name; "none": no entry point at all; "tf": the "plain" dae_backward with dataset rows.
 FAMILIES = {
@@ -276,6 +389,7 @@ FAMILIES = {
     "ab3": Family(pt=True, x_sub=True, workspace="rk"),
     "ms": Family(tab=True, sub=True, seg=True, x_sub=True, workspace="rk"),
     "msp": Family(tab=True, sub=True, seg=True, x_sub=True, workspace="own", par=True),
+    "rkc": Family(x_sub=True, rkc=True),
 }
 
 MAX_CHUNKS = 65535      # the launch grid's second dimension (csrc/psnode_generic_family.h: kMaxChunks)
@@ -386,7 +500,15 @@ class GenericOpts:
         if sp is not None and (isinstance(sp, bool) or not isinstance(sp, int) or sp < 1 or self.segment is None):
             raise ValueError(f"segment_parallel must be None or the segments per chunk (an int >= 1) of a call with segment, got {sp!r} "
                              f"(segment={self.segment!r})")
-        if self.segment is not None:
+        if isinstance(self.tab, Recurrence):
+            # a Runge-Kutta-Chebyshev recurrence rides in the tableau's field, told apart by type; `substeps` then holds its stage count (`of`
+            # puts it there: the stage rows are sized and checked as the sub-state rows are), never sub-steps of the caller's
+            if self.substeps != self.tab.stages or is_linear(self.externals) or self.segment is not None or self.ab:
+                raise ValueError(f"{self.tab.name} takes one step per grid interval with held externals: no sub-steps (raise the stage count "
+                                 f"instead), no interpolated externals, no segments (got substeps={self.substeps}, externals={self.externals!r}, "
+                                 f"segment={self.segment!r})")
+            fam = "none" if self.per_trajectory else "rkc"
+        elif self.segment is not None:
             fam = "none" if (is_linear(self.externals) or self.per_trajectory) else ("ms" if sp is None else "msp")
         elif self.ab and ab_order == 3:
             if self.substeps != 1 or is_linear(self.externals) or self.tab is not None:
@@ -416,6 +538,11 @@ class GenericOpts:
     def of(method, acts: tuple, substeps: int = 1, externals: str = "hold", per_trajectory: bool = False, segment=None,
            segment_parallel=None) -> "GenericOpts":
         method_id, stages, tab = method_info(method)
+        if isinstance(tab, Recurrence):      # (substeps: 1, the caller's, or the stage count a GenericOpts of this method hands on)
+            if substeps not in (1, tab.stages):
+                raise ValueError(f"{tab.name} takes one step per grid interval: substeps != 1 has no form here, raise the stage count instead "
+                                 f"(got substeps={substeps!r})")
+            substeps = tab.stages
         return GenericOpts(acts, tab, substeps, externals, method_id, stages, per_trajectory, segment, 3 if ab_order(method) == 3 else is_ab(method), segment_parallel)
 
     def chunks(self, T: int) -> Optional[int]:
@@ -432,6 +559,8 @@ class GenericOpts:
         owns the structs: keep it until the call has returned.  family: the entry point's, where it is not the options' own."""
         f = self.takes if family is None else FAMILIES[family]
         out = _act_ptrs(self.acts) if f.acts else []
+        if f.rkc:
+            out.append(ctypes.byref(self.tab.abi(x_sub.data_ptr() if x_sub is not None and x_sub.numel() else None)))
         if f.tab:
             out.append(ctypes.byref(self.tab.abi()) if self.tab is not None else None)
         if f.sub:
@@ -459,6 +588,8 @@ class GenericOpts:
         """The first option the call carries, in the fixed order act, tableau, sub-steps, externals, as the subject of a refusal."""
         if any(a is not None for a in self.acts):
             return "an activation other than ELU(alpha=1) runs"
+        if isinstance(self.tab, Recurrence):
+            return f"a Runge-Kutta-Chebyshev recurrence ({self.tab.name}) runs"
         if self.tab is not None:
             return f"a Runge-Kutta tableau ({self.tab.name}) runs"
         if self.substeps != 1:
@@ -479,6 +610,9 @@ class GenericOpts:
         if self.family == "plain":
             return
         self.no_teacher_forcing(what, teacher_forced)
+        if self.family == "none" and isinstance(self.tab, Recurrence):
+            raise _lib.UnsupportedShapeError(f"{what}: per-trajectory events (per_trajectory=True) together with a Runge-Kutta-Chebyshev "
+                                             f"recurrence ({self.tab.name}) have no fused form: the recurrence build of K0 / K5 takes the shared event table")
         if self.family == "none" and self.segment is not None:
             raise _lib.UnsupportedShapeError(f"{what}: multiple-shooting segments (segment={self.segment}) together with "
                                              + (_externals_text(self.externals) if is_linear(self.externals)
@@ -509,6 +643,8 @@ class GenericOpts:
     def require_plain(self, what: str):
         """(method id, stages) for the specialised, latent, encoded and saved-row entries, which carry the three built-in formulas with one
         step per grid interval and held externals: UnsupportedShapeError for sub-steps, interpolated externals or a Tableau."""
+        if isinstance(self.tab, Recurrence):
+            builtin_method(self.tab, what)
         if self.substeps != 1:
             raise _lib.UnsupportedShapeError(f"{what}: sub-steps per grid interval (substeps={self.substeps}) run on the generic kernels K0 / K5 only "
                                              "(kernel 'auto' / 'generic', no saved rows); this entry point takes one step per interval")
@@ -548,7 +684,7 @@ def call_generic(lib, stem: str, kind: str, args, opts: GenericOpts, *tail, x_su
     if isinstance(args, _lib.DaeBwdTfArgsF32):
         assert stem == "dae_backward" and fam != "act", f"{stem}: no entry point takes dataset rows and the acts {opts.acts} alone"
         fam = "tf" if fam == "plain" else fam
-    if kind == "workspace_bytes" and FAMILIES[fam].stencil and stem == "dae_backward":      # (the family's own query, under this name)
+    if kind == "workspace_bytes" and (FAMILIES[fam].stencil or FAMILIES[fam].rkc) and stem == "dae_backward":      # (the family's own query, under this name)
         name = f"psnode_{stem}_{fam}_workspace_size"
         return getattr(lib, name)(ctypes.byref(args), *opts.c_args(x_sub, x_true, fam, stencil), *tail), name
     if kind == "workspace_bytes" and FAMILIES[fam].par:      # (the segment-parallel family sizes both backward stems itself)

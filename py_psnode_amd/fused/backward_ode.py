@@ -78,7 +78,7 @@ def ode_backward(method, de_layers: Layers, t, z, all_initial, xs, grad_xs, even
     x_true = _ms_rows("ode_backward", segment, x_true, T, B, xd, dev)
     if per_trajectory:
         check_event_idx(event_idx, T, B, True, dev)
-    _check_x_sub("ode_backward", substeps, x_sub, T, B, xd, dev)
+    _check_x_sub("ode_backward", opts.substeps, x_sub, T, B, xd, dev)
     if saved is not None and not input_true_x and latent_wide_shape(de_layers, None, xd, zd):
         g = latent_backward_wide(method, de_layers, None, t, z, None, all_initial, xs, None, grad_xs, None, event_idx=event_idx,
                                  z_jump=z_jump, saved=saved, need_grad_z=need_grad_z)

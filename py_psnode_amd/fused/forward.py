@@ -6,7 +6,7 @@ from typing import Optional
 import torch
 
 from .. import _lib
-from ._common import (KERNEL_ID, GenericOpts, resolve_segment_parallel, Layers, Tableau, builtin_method, _aligned16, _bind_events, _check_tb, _empty, _f32_dev, _mlp, _view, _workspace_of, call_generic, dae_acts, has_events, is_linear, lagrange_stencils)
+from ._common import (KERNEL_ID, GenericOpts, resolve_segment_parallel, Layers, Tableau, Recurrence, builtin_method, _aligned16, _bind_events, _check_tb, _empty, _f32_dev, _mlp, _view, _workspace_of, call_generic, dae_acts, has_events, is_linear, lagrange_stencils)
 
 _MFMA_CLASSES = ("MFMA integrators K1 / K2 cover `in -> H -> H -> H -> out` ELU-MLPs with H <= 128 (any x_dim <= 16 for the ODE, "
                  "x_dim <= 8 and z+v+i <= 8 for the DAE), and -- weights streamed from L2 -- the ODE up to H = 192 at any x_dim <= 16 and "
@@ -138,7 +138,7 @@ def ode_integrate(method, de_layers: Layers, t, x, z, all_initial, event_t=None,
                      _empty((max(T - 1, 0), opts.stages, B, xd), dtype=torch.float32, device=dev))
             if T >= 2:
                 a.save_act, a.save_xstage = saved[0].data_ptr(), saved[1].data_ptr()
-        x_sub = _empty((max(T - 1, 0), substeps - 1, B, xd), dtype=torch.float32, device=dev) if save_sub and opts.takes.x_sub else None
+        x_sub = _empty((max(T - 1, 0), opts.substeps - 1, B, xd), dtype=torch.float32, device=dev) if save_sub and opts.takes.x_sub else None
         ws, wp, wn = _workspace_of(lib.psnode_workspace_bytes(ctypes.byref(a.de), None), dev)
         stencil = lagrange_stencils(t.detach(), event_idx) if opts.takes.stencil else None      # (externals="lagrange": int8 [T-1, B])
         rc, entry = call_generic(lib, "ode_integrate", "f32", a, opts, wp, wn, torch.cuda.current_stream(dev).cuda_stream, x_sub=x_sub, stencil=stencil)
@@ -155,7 +155,7 @@ def ode_integrate(method, de_layers: Layers, t, x, z, all_initial, event_t=None,
 def ode_save_hidden(method, de_layers: Layers, x_dim: int, z_dim: int, kernel: str = "auto", substeps: int = 1, externals: str = "hold") -> int:
     """Row width of the saved activations if the forward for these dims can save them (K1 proper), else 0 (always for a Tableau, for
     substeps > 1 and for externals="linear")."""
-    if is_linear(externals) or substeps != 1 or isinstance(method, Tableau) or de_layers[0][0].device.type != "cuda" or len(de_layers) > _lib.MAX_LAYERS:
+    if is_linear(externals) or substeps != 1 or isinstance(method, (Tableau, Recurrence)) or de_layers[0][0].device.type != "cuda" or len(de_layers) > _lib.MAX_LAYERS:
         return 0
     lib = _lib.load()
     a = _lib.OdeArgsF32()
@@ -267,7 +267,7 @@ def dae_integrate(method, de_layers: Layers, ae_layers: Layers, x_init, t, x, z,
                 a.save_act = a.save_xstage = dummy.data_ptr()
             if n_ev:
                 a.save_ev_act, a.save_ev_i = saved[3].data_ptr(), saved[4].data_ptr()
-        x_sub = _empty((max(T - 1, 0), substeps - 1, B, xd), dtype=torch.float32, device=dev) if save_sub and opts.takes.x_sub else None
+        x_sub = _empty((max(T - 1, 0), opts.substeps - 1, B, xd), dtype=torch.float32, device=dev) if save_sub and opts.takes.x_sub else None
         ws, wp, wn = _workspace_of(lib.psnode_workspace_bytes(ctypes.byref(a.de), ctypes.byref(a.ae)), dev)
         stencil = lagrange_stencils(t.detach(), event_idx) if opts.takes.stencil else None      # (externals="lagrange": int8 [T-1, B])
         rc, entry = call_generic(lib, "dae_integrate", "f32", a, opts, wp, wn, torch.cuda.current_stream(dev).cuda_stream, x_sub=x_sub, stencil=stencil)
@@ -284,7 +284,7 @@ def dae_save_hidden(method, de_layers: Layers, ae_layers: Layers, x_dim: int, z_
                     kernel: str = "auto", substeps: int = 1, externals: str = "hold") -> int:
     """Row width of the saved activations if the forward for these dims can save them (K2 proper), else 0 (always for a Tableau, for
     substeps > 1 and for externals="linear")."""
-    if is_linear(externals) or substeps != 1 or isinstance(method, Tableau) or de_layers[0][0].device.type != "cuda" or max(len(de_layers), len(ae_layers)) > _lib.MAX_LAYERS:
+    if is_linear(externals) or substeps != 1 or isinstance(method, (Tableau, Recurrence)) or de_layers[0][0].device.type != "cuda" or max(len(de_layers), len(ae_layers)) > _lib.MAX_LAYERS:
         return 0
     lib = _lib.load()
     a = _lib.DaeArgsF32()

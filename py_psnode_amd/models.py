@@ -274,7 +274,7 @@ class ODE_Model(nn.Module):
             return None
         if getattr(solver, "kernel", "auto") == "generic":        # PSNODE_KERNEL=generic asks for K0: row kernels + solver route
             return None
-        if isinstance(solver.method, fused.Tableau) or fused.is_ab(solver.method):      # a Runge-Kutta tableau and Adams-Bashforth 2 / 3 run on K0 / K5: row kernels + solver route
+        if isinstance(solver.method, (fused.Tableau, fused.Recurrence)) or fused.is_ab(solver.method):      # a Runge-Kutta tableau, a Runge-Kutta-Chebyshev recurrence and Adams-Bashforth 2 / 3 run on K0 / K5: row kernels + solver route
             return None
         if getattr(solver, "substeps", 1) > 1 or getattr(solver, "externals", "hold") != "hold":      # so do sub-steps and linear externals
             return None
@@ -391,7 +391,7 @@ class DAE_Model(nn.Module):
         solver = self.solver
         if not isinstance(solver, FixedGridODESolver) or getattr(solver, "fused", "off") == "off" or not solver.method:
             return None
-        if getattr(solver, "kernel", "auto") == "generic" or isinstance(solver.method, fused.Tableau) or fused.is_ab(solver.method):      # (a tableau and Adams-Bashforth 2 / 3 run on K0 / K5)
+        if getattr(solver, "kernel", "auto") == "generic" or isinstance(solver.method, (fused.Tableau, fused.Recurrence)) or fused.is_ab(solver.method):      # (a tableau, a Runge-Kutta-Chebyshev recurrence and Adams-Bashforth 2 / 3 run on K0 / K5)
             return None
         if getattr(solver, "substeps", 1) > 1 or getattr(solver, "externals", "hold") != "hold" or (getattr(self.event, "per_trajectory", False) and event_t is not None) or getattr(solver, "segment", None) is not None:      # (so do sub-steps, linear externals, per-trajectory events of a call that has events and multiple-shooting segments)
             return None

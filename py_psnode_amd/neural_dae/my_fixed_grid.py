@@ -427,3 +427,82 @@ class AB3(AB2):
             cur_i = i_func(xt=cur_x, zt=z[k + 1], vt=v[k + 1], all_initial=all_initial)
             xs[k + 1], is_[k + 1] = cur_x, cur_i
         return xs, is_
+
+
+class _RKC(FixedGridODESolver):
+    """A stabilised explicit (Runge-Kutta-Chebyshev) step: every grid interval is ONE step of `stages` right-hand-side evaluations whose real
+    stability interval grows with stages^2 -- about 1.94 s^2 (RKC1) / 0.65 s^2 (RKC2) where `Euler(substeps=s)` has 2 s.  `method` is the
+    fused.Recurrence of `fused.rkc_table(stages, order, damping)`: its fp32-rounded coefficients are the method, for this walk and for the
+    generic kernels K0 / K5 (kernel 'auto' / 'generic') alike.  With h = t[k+1] - t[k], Y_0 the step's start and F_0 = F(Y_0):
+        Y_1 = Y_0 + (mu_t_1 h) F_0;   Y_j = kappa_j Y_0 + mu_j Y_{j-1} + nu_j Y_{j-2} + (mu_t_j h) F(Y_{j-1}) + (gamma_t_j h) F_0,  j = 2 .. s
+    summed in the order written, a coefficient that is exactly 0 skipped, in the tensors' dtype; the new state is Y_s.  The externals are
+    held (the jumped rows behind an event).  A DAE that integrates its own i evaluates i = g(Y_{j-1}; z_k, v_k) in front of every stage
+    j >= 2 -- the sub-step rule, which is what lets the method stabilise the coupled system --; the first stage uses the carried i or the
+    event-time head, and F_0 is that first evaluation, reused.  Under input_true_i every stage reads i[k]; under input_true_x the step
+    starts from x[k].  The base walks run it through the `_step_state` hook.  No sub-steps (raise the stage count), no interpolated
+    externals, no segments -- ValueError.  Per-trajectory events walk (no kernel)."""
+    _order = 1
+
+    def __init__(self, stages, damping=None, **kw):
+        name = type(self).__name__
+        if isinstance(stages, bool) or not isinstance(stages, int):
+            raise ValueError(f"{name}: stages must be an int, got {stages!r}")
+        if kw.get("substeps", 1) != 1:
+            raise ValueError(f"{name} takes one step per grid interval: substeps != 1 has no form here, raise the stage count instead "
+                             f"(got substeps={kw.get('substeps')!r})")
+        if kw.get("externals", "hold") != "hold":
+            raise ValueError(f"{name} holds the external inputs over its stages: externals={kw.get('externals')!r} has no form here")
+        if kw.get("segment") is not None or kw.get("segment_parallel") is not None:
+            raise ValueError(f"{name} has no multiple-shooting form (got segment={kw.get('segment')!r}, "
+                             f"segment_parallel={kw.get('segment_parallel')!r})")
+        if damping is not None and (isinstance(damping, bool) or not isinstance(damping, (int, float)) or not damping > 0):
+            raise ValueError(f"{name}: damping must be a number > 0, got {damping!r}")
+        self.method = _fused.rkc_table(stages, self._order, None if damping is None else float(damping))
+        self.order = self._order
+        self.stages = stages
+        super().__init__(**kw)
+
+    def _step_state(self, func, t0, dt, t1, x0, z0=None, v0=None, i0=None, all_initial=None, head=None):
+        m = self.method
+        f0 = _rhs(func, z0, v0, i0, all_initial)(t0, x0)
+        y_prev, y = x0, x0 + (m.mu_t[0] * dt) * f0
+        for j in range(1, m.stages):
+            i_j = i0 if head is None else head(y)
+            fj = _rhs(func, z0, v0, i_j, all_initial)(t0 + m.c[j - 1] * dt, y)
+            new = m.mu[j] * y
+            if m.kappa[j] != 0.0:
+                new = m.kappa[j] * x0 + new
+            if m.nu[j] != 0.0:
+                new = new + m.nu[j] * y_prev
+            new = new + (m.mu_t[j] * dt) * fj
+            if m.gamma_t[j] != 0.0:
+                new = new + (m.gamma_t[j] * dt) * f0
+            y_prev, y = y, new
+        return y
+
+    def _step_func(self, func, t0, dt, t1, x0, z0=None, v0=None, i0=None, all_initial=None):
+        """(Y_s - x0, F_0) with i frozen over the stages: `step_integrate` alone knows no head; the walks go through `_step_state`."""
+        f0 = _rhs(func, z0, v0, i0, all_initial)(t0, x0)
+        return self._step_state(func, t0, dt, t1, x0, z0, v0, i0, all_initial) - x0, f0
+
+    def _generic_only_ok(self, what, acts, per_trajectory=False) -> bool:
+        """The recurrence runs on the generic kernels K0 / K5 only, with the shared event table: kernel 'wave' / 'tile' / 'mfma' / 'wide' and
+        per-trajectory events walk under fused='auto' and raise under 'require'."""
+        if self.kernel in ("auto", "generic") and not per_trajectory:
+            return True
+        if self.fused == "require":
+            raise _fused._lib.UnsupportedShapeError(
+                f"{what}: " + (f"per-trajectory events (per_trajectory=True) next to {self.method.name} have no kernel" if per_trajectory
+                               else f"kernel={self.kernel!r} has no form for the Runge-Kutta-Chebyshev recurrence {self.method.name}")
+                + ": it runs on the generic kernels (kernel 'auto' / 'generic') with the shared event table")
+        return False
+
+
+class RKC1(_RKC):
+    """First-order Runge-Kutta-Chebyshev, stages 1..32 (default damping 0.05): real stability interval about 1.94 stages^2; stages=1 is Euler."""
+    _order = 1
+
+
+class RKC2(_RKC):
+    """Second-order Runge-Kutta-Chebyshev, stages 2..32 (default damping 2/13): real stability interval about 0.65 stages^2."""
+    _order = 2

@@ -83,7 +83,11 @@ class _LagWalk:
 
 class FixedGridODESolver(metaclass=abc.ABCMeta):
     order: int
-    method = ""        # "euler" | "midpoint" | "rk4", a fused.Tableau (my_fixed_grid.ExplicitRK), "ab2" (my_fixed_grid.AB2) or "ab3" (my_fixed_grid.AB3): the formula the fused kernels run
+    method = ""        # "euler" | "midpoint" | "rk4", a fused.Tableau (my_fixed_grid.ExplicitRK), "ab2" (my_fixed_grid.AB2), "ab3" (my_fixed_grid.AB3) or a fused.Recurrence (my_fixed_grid.RKC1 / RKC2): the formula the fused kernels run
+    # A solver whose ONE step per interval re-evaluates a DAE's algebraic variable between its stages (my_fixed_grid.RKC1 / RKC2) sets this private
+    # hook: _step_state(func=, t0=, dt=, t1=, x0=, z0=, v0=, i0=, all_initial=, head=) -> the new state, with head(x) -> i at the interval's held
+    # z | v, or None where i is not re-evaluated (an ODE, input_true_i).  The base walks call it where they call step_integrate.
+    _step_state = None
 
     def __init__(self, step_size=None, grid_constructor=None, interp="linear", substeps=1, externals="hold", segment=None,
                  segment_parallel=None):
@@ -189,6 +193,8 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
         if not generic and any(a is not None for a in acts):
             names = ", ".join(repr(a) for a in acts if a is not None)
             text = f"has no form for the activation {names}: activations other than ELU(alpha=1) run on the generic kernels (kernel 'auto' / 'generic')"
+        elif not generic and isinstance(self.method, _fused.Recurrence):
+            text = f"has no form for the Runge-Kutta-Chebyshev recurrence {self.method.name}: it runs on the generic kernels (kernel 'auto' / 'generic')"
         elif not generic and isinstance(self.method, _fused.Tableau):
             text = f"has no form for the Runge-Kutta tableau {self.method.name}: tableaus run on the generic kernels (kernel 'auto' / 'generic')"
         elif not fits and self.substeps != 1:
@@ -356,6 +362,8 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
                     ext_at = self._lin_ext(j, self.substeps, (zk,), (z[k + 1],)) if lag is None else lag.ext_at(k, j, self.substeps)
                     cur = cur + self._step_func_lin(func=x_func, t0=t0 + j * h if j else t0, dt=h, x0=cur, ext_at=lambda c: ext_at(c) + (None,),
                                                     all_initial=all_initial)
+            elif self._step_state is not None:
+                cur = self._step_state(func=x_func, t0=t0, dt=t1 - t0, t1=t1, x0=start, z0=zk, all_initial=all_initial)
             elif self.substeps == 1:
                 cur, _ = self.step_integrate(func=x_func, t0=t0, dt=t1 - t0, t1=t1, x0=start, z0=zk, all_initial=all_initial)
             else:       # n equal sub-steps of h = (t1 - t0) / n with the interval's z held; only sub-step 0 starts from the dataset row
@@ -452,6 +460,9 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
                         i_in = i_func(xt=cur_x, zt=zj_, vt=vj_, all_initial=all_initial)
                     cur_x = cur_x + self._step_func_lin(func=x_func, t0=t0 + j * h if j else t0, dt=h, x0=cur_x, ext_at=ext_at, i0=i_in,
                                                         all_initial=all_initial)
+            elif self._step_state is not None:      # (the head in front of a stage sees the interval's held rows, as a sub-step's does)
+                head = None if input_true_i else (lambda xx, zk=zk, vk=vk: i_func(xt=xx, zt=zk, vt=vk, all_initial=all_initial))
+                cur_x = self._step_state(func=x_func, t0=t0, dt=t1 - t0, t1=t1, x0=start, z0=zk, v0=vk, i0=i_in, all_initial=all_initial, head=head)
             elif self.substeps == 1:
                 cur_x, _ = self.step_integrate(func=x_func, t0=t0, dt=t1 - t0, t1=t1, x0=start, z0=zk, v0=vk, i0=i_in,
                                                all_initial=all_initial)
