@@ -21,10 +21,14 @@
 //       per pass.  20 = the 16-block form (two dim-tiles, permlane32 + permlane16 folds, the RK operations on two scalars); 21 = the
 //       8-block form (B-operand lane-group broadcast BLGP 1 / 2, two chains merged by packed adds, permlane16 fold, packed RK operations).
 //       The 8-block form also gets a mapping check against a double-precision matvec (does BLGP broadcast what the ISA text says?).
+//   30 / 31  the seam behind K1x's first layer (`ubench_4x4 l1` runs these two alone): 30 = mapping check of BLGP 4 .. 7 (the B operand's row
+//       broadcast) and of the whole first layer with the roles swapped (A = weights, B = state), against double precision and, as raw words,
+//       against today's form; 31 = the stage head (L1 -> merge -> ELU [-> transpose]) in both forms, as ticks per head.
 // It also checks, bit for bit over 2^24 inputs, that the round-5 ELU form equals round 3's.
 // Grid: 1024 single-wave workgroups (= B 4096: one wave per SIMD), and 2048 (two per SIMD) for reference.
 #include <hip/hip_runtime.h>
 #include <cstdio>
+#include <cstring>
 
 typedef float f4 __attribute__((ext_vector_type(4)));
 typedef float f2 __attribute__((ext_vector_type(2)));
@@ -604,6 +608,163 @@ bool check_waist() {
     return all_ok;
 }
 
+// ---- the seam behind the first layer (modes 30 / 31; profiles/k1x_l1_seam_ab.txt).  The state sits replicated over the four blocks of a
+// 16-lane row; BLGP 4 + rho hands row rho of the B operand to all four rows, so with A = weights and B = state L1's accumulator comes out
+// with register <-> unit-in-quad, lane <-> (block, trajectory): the A layout of the next layer, no transpose behind the ELU.
+//   30  mapping check: BLGP 4..7 alone (one MFMA of distinct values per lane) and the whole swapped first layer, against double precision
+//   31  the stage head, ticks per pass: L1 with CBSZ = 4 / ABID = 4 rho, merge, ELU, transpose   against   L1 with BLGP 4 + rho, merge, ELU
+constexpr int l1_dim(int m) { return 4 * ((m & 3) >> 1) + 2 * ((m & 3) & 1) + (m >= 4 ? 1 : 0); }
+template <int BLGP>
+__global__ void check_blgp(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ res) {
+    const int l = threadIdx.x;
+    const f4 d = mfl<BLGP>(a[l], b[l], f4{0.f, 0.f, 0.f, 0.f});
+#pragma unroll
+    for (int r = 0; r < 4; ++r) res[r * 64 + l] = d[r];
+}
+// L1 in the swapped form: chain A starts from the constant and takes m = 0, 2, 4, 6, chain B m = 1, 3, 5, 7 (the order of today's form)
+__device__ __forceinline__ f4 l1_swapped(const float (&w1x)[8], const f2 s, const f4 cz) {
+    f4 accA = cz, accB = f4{0.f, 0.f, 0.f, 0.f};
+    accA = mfl<4>(w1x[0], s[0], accA);  accB = mfl<5>(w1x[1], s[0], accB);
+    accA = mfl<6>(w1x[2], s[0], accA);  accB = mfl<7>(w1x[3], s[0], accB);
+    accA = mfl<4>(w1x[4], s[1], accA);  accB = mfl<5>(w1x[5], s[1], accB);
+    accA = mfl<6>(w1x[6], s[1], accA);  accB = mfl<7>(w1x[7], s[1], accB);
+    return accA + accB;
+}
+__device__ __forceinline__ f4 l1_today(const float (&w1x)[8], const f2 s, const f4 cz) {
+    f4 accA = cz, accB = f4{0.f, 0.f, 0.f, 0.f};
+    accA = mf<0>(s[0], w1x[0], accA);  accB = mf<4>(s[0], w1x[1], accB);
+    accA = mf<8>(s[0], w1x[2], accA);  accB = mf<12>(s[0], w1x[3], accB);
+    accA = mf<0>(s[1], w1x[4], accA);  accB = mf<4>(s[1], w1x[5], accB);
+    accA = mf<8>(s[1], w1x[6], accA);  accB = mf<12>(s[1], w1x[7], accB);
+    return accA + accB;
+}
+// out[unit][traj] = sum_d W1[unit][d] x[d][traj], reported in the A layout (lane (b, t) register cc = unit 4b + cc): the swapped form as it
+// is, today's form through the in-quad transpose.  img = the 8 weight registers [m][lane = unit]; x = [8 dims][4 trajectories]
+template <bool SWAPPED>
+__global__ void check_l1(const float* __restrict__ img, const float* __restrict__ x, float* __restrict__ res) {
+    const int l = threadIdx.x, b = l >> 2, t = l & 3, rho = l >> 4, d01 = 4 * (rho >> 1) + 2 * (rho & 1);
+    float w1x[8];
+#pragma unroll
+    for (int m = 0; m < 8; ++m) w1x[m] = img[m * 64 + l];
+    const f2 s = f2{x[d01 * 4 + t], x[(d01 + 1) * 4 + t]};     // the state layout: a row's two adjacent dims, in every block of the row
+    const f4 z = f4{0.f, 0.f, 0.f, 0.f};
+    const f4 h = SWAPPED ? l1_swapped(w1x, s, z) : quad_transpose(l1_today(w1x, s, z), l);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) res[(4 * b + c) * 4 + t] = h[c];
+}
+bool check_l1_seam() {
+    bool all_ok = true;
+    float ha[64], hb[64], hd[4 * 64], *da, *db, *dd;
+    for (int i = 0; i < 64; ++i) { ha[i] = 1.0f + (float)i; hb[i] = 0.5f + 0.25f * (float)((i * 37) % 64); }     // (exact products)
+    hipMalloc(&da, sizeof(ha)); hipMalloc(&db, sizeof(hb)); hipMalloc(&dd, sizeof(hd));
+    hipMemcpy(da, ha, sizeof(ha), hipMemcpyHostToDevice); hipMemcpy(db, hb, sizeof(hb), hipMemcpyHostToDevice);
+    for (int blgp = 4; blgp < 8; ++blgp) {
+        hipMemset(dd, 0, sizeof(hd));
+        if (blgp == 4) check_blgp<4><<<1, 64>>>(da, db, dd); else if (blgp == 5) check_blgp<5><<<1, 64>>>(da, db, dd);
+        else if (blgp == 6) check_blgp<6><<<1, 64>>>(da, db, dd); else check_blgp<7><<<1, 64>>>(da, db, dd);
+        hipMemcpy(hd, dd, sizeof(hd), hipMemcpyDeviceToHost);
+        int bad = 0;
+        for (int lane = 0; lane < 64; ++lane)
+            for (int r = 0; r < 4; ++r) {
+                const int blk = lane >> 2, c = lane & 3;
+                // D_b[r][c] = A_b[r] B_src[c]: A from the block's own lanes, B from block (blk & 3) of row blgp - 4
+                const double ref = (double)ha[4 * blk + r] * (double)hb[16 * (blgp - 4) + 4 * (blk & 3) + c];
+                bad += ref != (double)hd[r * 64 + lane];
+            }
+        printf("BLGP %d on v_mfma_f32_4x4x1_16b_f32 (B row %d to all four rows), 64 lanes x 4 registers vs a double-precision product: %d mismatches %s\n",
+               blgp, blgp - 4, bad, bad ? "WRONG" : "OK");
+        all_ok = all_ok && !bad;
+    }
+    float W1[64 * 8], x[8 * 4], img[8 * 64], hr[64 * 4], *dimg, *dx, *dres;
+    for (int i = 0; i < 64 * 8; ++i) W1[i] = (float)((i * 7919 + 13) % 1000) * 1e-3f - 0.5f;
+    for (int i = 0; i < 8 * 4; ++i) x[i] = (float)((i * 104729 + 7) % 1000) * 1e-3f - 0.5f;
+    for (int m = 0; m < 8; ++m) for (int u = 0; u < 64; ++u) img[m * 64 + u] = W1[u * 8 + l1_dim(m)];
+    hipMalloc(&dimg, sizeof(img)); hipMalloc(&dx, sizeof(x)); hipMalloc(&dres, sizeof(hr));
+    hipMemcpy(dimg, img, sizeof(img), hipMemcpyHostToDevice); hipMemcpy(dx, x, sizeof(x), hipMemcpyHostToDevice);
+    float first[64 * 4];
+    for (int form = 0; form < 2; ++form) {
+        hipMemset(dres, 0, sizeof(hr));
+        if (form) check_l1<true><<<1, 64>>>(dimg, dx, dres); else check_l1<false><<<1, 64>>>(dimg, dx, dres);
+        hipMemcpy(hr, dres, sizeof(hr), hipMemcpyDeviceToHost);
+        double worst = 0;
+        for (int u = 0; u < 64; ++u)
+            for (int t = 0; t < 4; ++t) {
+                double ref = 0;
+                for (int d = 0; d < 8; ++d) ref += (double)W1[u * 8 + d] * x[d * 4 + t];
+                const double df = fabs(ref - hr[u * 4 + t]);
+                if (df > worst) worst = df;
+            }
+        printf("first layer mapping check, %s, 64 units x 4 trajectories vs a double-precision matvec: max abs diff %.3g %s\n",
+               form ? "swapped (A = weights, B = state on BLGP 4 + rho), no transpose" : "today's (A = state on CBSZ 4 / ABID 4 rho) + in-quad transpose",
+               worst, worst < 1e-5 ? "OK" : "WRONG");
+        all_ok = all_ok && worst < 1e-5;
+        if (form == 0) { for (int i = 0; i < 64 * 4; ++i) first[i] = hr[i]; }
+        else {
+            int nd = 0;
+            for (int i = 0; i < 64 * 4; ++i) { unsigned p, q; memcpy(&p, &first[i], 4); memcpy(&q, &hr[i], 4); nd += p != q; }
+            printf("first layer, swapped against today's form as raw 32-bit words: %d of 256 differ %s\n", nd, nd ? "(NOT bit-exact)" : "(bit-exact)");
+            all_ok = all_ok && nd == 0;
+        }
+    }
+    hipFree(da); hipFree(db); hipFree(dd); hipFree(dimg); hipFree(dx); hipFree(dres);
+    return all_ok;
+}
+// the stage head as K1x runs it: L1 (8 MFMAs, two chains) -> merge -> scaled-domain ELU -> (today: in-quad transpose, the order alternating as
+// in a sequence of seams) -> hA.  Two heads per iteration; what closes the loop (hA -> the next stage input) is the same in both forms.
+template <bool SWAPPED>
+__global__ __launch_bounds__(64) void bench_head(float* out, long long* cyc, int niter, const float* __restrict__ wsrc) {
+    const int l = threadIdx.x;
+    float w1x[8];
+#pragma unroll
+    for (int m = 0; m < 8; ++m) w1x[m] = wsrc[m * 64 + l];
+    const f4 cz = f4{0.01f, 0.02f, 0.03f, 0.04f};
+    f2 s = f2{0.1f + 0.001f * l, 0.2f};
+    unsigned long long vmask = 0x5555555555555555ull;
+    const long long t0 = __builtin_readcyclecounter();
+    for (int it = 0; it < niter; it += 2) {
+#pragma unroll
+        for (int ly = 0; ly < 2; ++ly) {
+            f4 h;
+            if constexpr (SWAPPED) {
+                h = elu_quad_scaled(l1_swapped(w1x, s, cz));
+            } else {
+                h = elu_quad_scaled(l1_today(w1x, s, cz));
+                if (ly == 0) h = quad_transpose_seq<0>(h, vmask); else h = quad_transpose_seq<1>(h, vmask);
+            }
+            s = f2{h[0], h[1]} * 1e-3f + f2{h[2], h[3]};       // (two packed operations: stands in for the layers behind)
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    const long long t1 = __builtin_readcyclecounter();
+    out[blockIdx.x * 64 + l] = s[0] + s[1] + (float)(vmask & 1);
+    if (blockIdx.x == 0 && l == 0) *cyc = t1 - t0;
+}
+template <bool SWAPPED>
+void run_head(const char* name, int nwg, float* out, long long* cyc, const float* w) {
+    const int niter = 4000;
+    hipEvent_t e0, e1;
+    hipEventCreate(&e0); hipEventCreate(&e1);
+    bench_head<SWAPPED><<<nwg, 64>>>(out, cyc, 10, w);
+    hipEventRecord(e0);
+    bench_head<SWAPPED><<<nwg, 64>>>(out, cyc, niter, w);
+    hipEventRecord(e1);
+    hipDeviceSynchronize();
+    float ms; hipEventElapsedTime(&ms, e0, e1);
+    long long c; hipMemcpy(&c, cyc, sizeof(c), hipMemcpyDeviceToHost);
+    printf("%-58s waves/SIMD=%d : %7.1f ns per head (wall), s_memtime %.2f ticks\n", name, nwg / 1024, ms * 1e6 / niter, (double)c / niter);
+}
+// the gate of the first-layer seam: mapping, then three alternating runs of each form of the head.  `ubench_4x4 l1` runs this alone.
+bool l1_seam_gate(float* out, long long* cyc, const float* w) {
+    const bool ok = check_l1_seam();
+    run_head<false>("stage head, L1 on CBSZ 4 / ABID, ELU, transpose", 1024, out, cyc, w);
+    run_head<true>("stage head, L1 swapped on BLGP 4 + rho, ELU", 1024, out, cyc, w);
+    run_head<false>("stage head, today's (again)", 1024, out, cyc, w);
+    run_head<true>("stage head, swapped (again)", 1024, out, cyc, w);
+    run_head<false>("stage head, today's (third)", 1024, out, cyc, w);
+    run_head<true>("stage head, swapped (third)", 1024, out, cyc, w);
+    return ok;
+}
+
 template <int MODE>
 void run(const char* name, int nwg, float* out, long long* cyc, const float* w) {
     const int niter = 4000;
@@ -619,7 +780,7 @@ void run(const char* name, int nwg, float* out, long long* cyc, const float* w) 
     printf("%-58s waves/SIMD=%d : %7.1f ns per layer (wall), s_memtime %.2f ticks\n", name, nwg / 1024, ms * 1e6 / niter, (double)c / niter);
 }
 
-int main() {
+int main(int argc, char** argv) {
     float *out, *w, *act, *res; long long* cyc;
     hipMalloc(&out, 2048 * 64 * sizeof(float)); hipMalloc(&cyc, 8);
     hipMalloc(&w, 64 * 64 * 4); hipMalloc(&act, 64 * 4 * 4); hipMalloc(&res, 64 * 4 * 4);
@@ -628,6 +789,7 @@ int main() {
     for (int i = 0; i < 64 * 4; ++i) ha[i] = (float)((i * 104729) % 1000) * 1e-3f - 0.5f;
     hipMemcpy(w, hw, sizeof(hw), hipMemcpyHostToDevice);
     hipMemcpy(act, ha, sizeof(ha), hipMemcpyHostToDevice);
+    if (argc > 1 && !strcmp(argv[1], "l1")) return l1_seam_gate(out, cyc, w) ? 0 : 1;
     check<<<1, 64>>>(w, act, res);
     hipMemcpy(hr, res, sizeof(hr), hipMemcpyDeviceToHost);
     double worst = 0;
@@ -648,6 +810,7 @@ int main() {
         hipFree(nb);
     }
     check_waist();
+    l1_seam_gate(out, cyc, w);
     run_waist<false>("waist 64 -> 8 -> 64, 16-block fold, scalar RK", 1024, out, cyc, w);
     run_waist<true>("waist 64 -> 8 -> 64, 8-block fold (BLGP), packed RK", 1024, out, cyc, w);
     run_waist<false>("waist, 16-block fold, scalar RK (again)", 1024, out, cyc, w);

@@ -12,7 +12,7 @@ namespace {
 typedef float f4 __attribute__((ext_vector_type(4)));
 typedef float f2 __attribute__((ext_vector_type(2)));
 
-// dim that MFMA m of L1 multiplies: register X01 (m < 4) or X23, ABID = 4 (m & 3)
+// dim that MFMA m of L1 multiplies: register X01 (m < 4) or X23 of row m & 3 (K1x / K2x's DE: BLGP 4 + (m & 3); K2x's AE head: ABID = 4 (m & 3))
 __host__ __device__ constexpr int l1_dim(int m) { return 4 * ((m & 3) >> 1) + 2 * ((m & 3) & 1) + (m >= 4 ? 1 : 0); }
 
 // A image of K1x's output layer (l4_out below).  Weight register m = 4 half + cc multiplies, in block b = lane >> 2, the activation row
@@ -26,6 +26,7 @@ template <int ABID>
 __device__ __forceinline__ f4 mfx(float a, float b, f4 c) { return __builtin_amdgcn_mfma_f32_4x4x1f32(a, b, c, 4, ABID, 0); }
 __device__ __forceinline__ f4 mfn(float a, float b, f4 c) { return __builtin_amdgcn_mfma_f32_4x4x1f32(a, b, c, 0, 0, 0); }
 // BLGP 1: every block reads its B row from lanes 0..31 (block b from block b & 7's lanes); 2: from lanes 32..63 (block 8 + (b & 7))
+// BLGP 4 + rho: every row of 16 lanes reads its B operand from row rho (block b from block 4 rho + (b & 3)'s lanes)
 template <int BLGP>
 __device__ __forceinline__ f4 mfl(float a, float b, f4 c) { return __builtin_amdgcn_mfma_f32_4x4x1f32(a, b, c, 0, 0, BLGP); }
 
@@ -230,6 +231,29 @@ __device__ __forceinline__ f4 ext_mfmas(const float (&we)[16], const float eA, f
     if constexpr (NQ > 0) {
         acc = mfx<Q0>(eA, we[Q0], acc);
         return ext_mfmas<Q0 + 1, NQ - 1>(we, eA, acc);
+    } else {
+        return acc;
+    }
+}
+
+// K1x's first layer with the roles swapped (A = weights, lane = unit; B = what sits replicated over the four blocks of a 16-lane row, handed to
+// all 16 blocks by BLGP 4 + rho): the accumulator comes out with register <-> unit-in-quad, lane <-> (block, trajectory) -- the A layout of the
+// next layer, no transpose behind the ELU.  The state's 8 MFMAs on two chains, in the order of the form they replace (chain A: m = 0, 2, 4, 6
+// on top of the per-step constant, chain B: m = 1, 3, 5, 7); the same products, added in the same order.
+__device__ __forceinline__ f4 l1_swapped(const float (&w1x)[8], const f2 s, const f4 cz) {
+    f4 accA = cz, accB = f4{0.f, 0.f, 0.f, 0.f};
+    accA = mfl<4>(w1x[0], s[0], accA);  accB = mfl<5>(w1x[1], s[0], accB);
+    accA = mfl<6>(w1x[2], s[0], accA);  accB = mfl<7>(w1x[3], s[0], accB);
+    accA = mfl<4>(w1x[4], s[1], accA);  accB = mfl<5>(w1x[5], s[1], accB);
+    accA = mfl<6>(w1x[6], s[1], accA);  accB = mfl<7>(w1x[7], s[1], accB);
+    return accA + accB;
+}
+// ... and the external slots' terms of its per-step constant: slot q = 4 j + rho sits in row rho of register eA[j]; one chain, q ascending
+template <int Q0, int NQ, int NE>
+__device__ __forceinline__ f4 ext_mfmas_swapped(const float (&we)[16], const float (&eA)[NE], f4 acc) {
+    if constexpr (NQ > 0) {
+        acc = mfl<4 + (Q0 & 3)>(we[Q0], eA[Q0 >> 2], acc);
+        return ext_mfmas_swapped<Q0 + 1, NQ - 1, NE>(we, eA, acc);
     } else {
         return acc;
     }

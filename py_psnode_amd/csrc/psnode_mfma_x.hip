@@ -19,9 +19,14 @@
 //       the RK update is one register pair wide and feeds L1 without any data movement.
 //   State layout: the pair X = {X01, X23}, lane in row rho = l >> 4, trajectory t = l & 3:  X01 = x[4 (rho >> 1) + 2 (rho & 1)][t],  X23 = the
 //       NEXT dim (adjacent dims: a row's two state values are one 8-byte store; the RK arithmetic is packed, v_pk_mul_f32 / v_pk_add_f32).
-//       L1 reads dim d with ABID = 4 rho(d) from X01 or X23 (8 MFMAs per stage, folded image as K1).
-// External inputs: slot q (K1's order: q < ne -> ext[q] - a0, ne <= q < 2 ne -> ext[q - ne]) lives in block q of ONE register (lane (q, t));
-// the per-step constant of L1 is 4 NZM MFMAs with ABID = q.  Hidden layers run in the log2e-scaled domain (psnode_common.h:
+//   L1 (x_dim -> 64), roles swapped as well (A = weights: the register image w1x, lane = unit, unchanged; B = the state): a row's value sits
+//       in all four blocks of the row (row_sum2 leaves it there), and BLGP 4 + rho hands row rho of B to all four rows, so
+//       D[unit 4b + r][traj c] (block b) += W1[4b + r][d] * x[d][c]      8 MFMAs per stage (dim d: row rho(d), register X01 or X23)
+//       comes out with register r = unit-in-quad, lane (b, c) = (block, trajectory): the A layout of the next layer.  ELU is elementwise,
+//       so NO transpose follows L1: a stage has two seams (behind L2 and L3), not three (profiles/k1x_l1_seam_ab.txt).
+// External inputs: slot q (K1's order: q < ne -> ext[q] - a0, ne <= q < 2 ne -> ext[q - ne]) lives in row q & 3 of register q >> 2 (every
+// block of the row; one load per lane, step and register); the per-step constant of L1 is 4 NZM MFMAs with BLGP 4 + (q & 3), on top of the
+// per-launch constant c0 (bias + a0 terms: computed in the D layout as before, transposed ONCE).  Hidden layers run in the log2e-scaled domain (psnode_common.h:
 // elu_quad_scaled).  Inference only (no saved activations); teacher forcing (input_true_x) is a uniform runtime branch.
 #include <string.h>
 
@@ -86,7 +91,7 @@ __global__ void pack_x_kernel(const PackX p) {
 // step (which prefetches nothing) instead of clamping every row pointer every step.
 // SAVE: the training forward (a.sact / a.sxst: what autograd would keep -- the three ELU layers' outputs [T-1,S,3,B,Hp] and the stage inputs
 // [T-1,S,B,xd], the rows K4f reads; Hp = the padded width of the backward's tile, 32 or 64).  Plain ELU domain (the pack image is unscaled).
-// The A layout after the in-quad transpose holds, per lane (b, t), units 4b .. 4b+3 of trajectory t: ONE 16-byte store per layer.
+// The A layout (L1's accumulator as it stands, L2 / L3 after the in-quad transpose) holds, per lane (b, t), units 4b .. 4b+3 of trajectory t: ONE 16-byte store per layer.
 #ifndef PSNODE_K1X_SAVE_ABL
 #define PSNODE_K1X_SAVE_ABL 0     // timing-only ablations of the saving forward (saved rows WRONG): 1 = no saved-row store is issued, 2 = every stage
 #endif                            // stores to the rows of (step 0, stage 0) (the same instructions, no HBM traffic)
@@ -187,11 +192,20 @@ __global__ __launch_bounds__(64 * kXWaves * (ROLES ? 2 : 1)) void integrate_x_ke
         float wa[16];
 #pragma unroll
         for (int q = 0; q < 16; ++q) wa[q] = pw[(XRegs::W1A + q) * 64];
-        c0 = ext_mfmas<0, 16>(wa, a0A, c0);
+        c0 = quad_transpose(ext_mfmas<0, 16>(wa, a0A, c0));         // into the A layout L1 accumulates in: once per launch
     }
-    const int ecol = b < ne ? b : (b < 2 * ne ? b - ne : 0);        // z column of this lane's ext slot (slot q = block b)
-    const float a0e = b < ne ? a0p[xd + b] : 0.0f;
-    const bool eon = b < 2 * ne;
+    // External slots in the swapped form: register j carries slot q = 4 j + rho in every block of row rho (BLGP 4 + rho hands it to all rows)
+    constexpr int NE = NZM > 0 ? NZM : 1;                           // (z_dim 0: one register on the clock, as a load that meets no MFMA)
+    int ecol[NE];                                                   // z column of the lane's slot in register j
+    float a0e[NE];                                                  // what the slot subtracts: a0's z entry (q < ne), nothing (ne <= q < 2 ne)
+    bool eon[NE];
+#pragma unroll
+    for (int j = 0; j < NE; ++j) {
+        const int q = 4 * j + rho;
+        ecol[j] = q < ne ? q : (q < 2 * ne ? q - ne : 0);
+        a0e[j] = q < ne ? a0p[xd + q] : 0.0f;
+        eon[j] = q < 2 * ne;
+    }
     f2 X = f2{0.0f, 0.0f};                                          // the state {X01, X23}: one register pair through the RK arithmetic
     {
         const float* x0 = a.x.p + tr * a.x.sb;
@@ -214,8 +228,12 @@ __global__ __launch_bounds__(64 * kXWaves * (ROLES ? 2 : 1)) void integrate_x_ke
     const bool has_z = zd > 0, has_zj = has_z && a.zj != nullptr;
     const long long zst = has_z ? a.z.st : 0, zje = has_zj ? a.zje : 0;
     const unsigned toff = (unsigned)(tr * a.t.sb) * 4u;
-    const unsigned zoff = has_z ? (unsigned)(tr * a.z.sb + ecol) * 4u : toff;          // absent source: the trajectory's clock (meets a zero weight)
-    const unsigned zjoff = has_zj ? (unsigned)(tr * a.zjb + ecol) * 4u : toff;
+    unsigned zoff[NE], zjoff[NE];
+#pragma unroll
+    for (int j = 0; j < NE; ++j) {
+        zoff[j] = has_z ? (unsigned)(tr * a.z.sb + ecol[j]) * 4u : toff;               // absent source: the trajectory's clock (meets a zero weight)
+        zjoff[j] = has_zj ? (unsigned)(tr * a.zjb + ecol[j]) * 4u : toff;
+    }
     const float* zbase = has_z ? a.z.p : a.t.p;
     const float* zjbase = has_zj ? a.zj : a.t.p;
     const int d01c = d01 < xd ? d01 : 0, d23c = d23 < xd ? d23 : 0;
@@ -257,7 +275,10 @@ __global__ __launch_bounds__(64 * kXWaves * (ROLES ? 2 : 1)) void integrate_x_ke
     int evb = FAST ? -1 : load_evb(0);
     int ev_cur = FAST ? -1 : __builtin_amdgcn_readlane(evb, 0);
     float t_cur = ldg<float>(as_g(a.t.p), toff), t_nxt = ldg<float>(as_g(a.t.p + tst), toff);
-    float e_nxt = (!FAST && ev_cur >= 0) ? ldg<float>(as_g(zjbase + (long long)ev_cur * zje), zjoff) : ldg<float>(as_g(zbase), zoff);
+    float e_nxt[NE];
+#pragma unroll
+    for (int j = 0; j < NE; ++j)
+        e_nxt[j] = (!FAST && ev_cur >= 0) ? ldg<float>(as_g(zjbase + (long long)ev_cur * zje), zjoff[j]) : ldg<float>(as_g(zbase), zoff[j]);
     const float* trun = a.t.p + 2 * tst;                              // uniform running row bases: the clock entry / z row the next prefetch reads
     const float* zrun = zbase + zst;
     float* xo_run = a.xo;                                             // step k stores row k (the previous step's result; step 0: the start row)
@@ -274,19 +295,13 @@ __global__ __launch_bounds__(64 * kXWaves * (ROLES ? 2 : 1)) void integrate_x_ke
         }
     };
 
-    // The mask the next in-quad transpose starts on (psnode_mfma_x.h: quad_transpose_seq).  A stage has three seams, so consecutive stages
-    // alternate their parity P; an even number of stages per step hands the next step the mask it starts with.
+    // The mask the next in-quad transpose starts on (psnode_mfma_x.h: quad_transpose_seq).  A stage has two seams (orders 0, 1: L1 leaves the
+    // A layout by itself), so every stage hands the next one the mask it started with.
     XMask vm = xmask_even();
-    // DE right-hand side in the state layout: k({X01, X23}).  P: the transpose order of the stage's first seam (orders P, !P, P)
-    auto rhs = [&](auto par_tag, const f2 s, const f4 cz) -> f2 {
+    // DE right-hand side in the state layout: k({X01, X23}); cz in the A layout
+    auto rhs = [&](const f2 s, const f4 cz) -> f2 {
         const float s01 = s[0], s23 = s[1];
-        constexpr int P = decltype(par_tag)::value;
-        f4 accA = cz, accB = f4{0.f, 0.f, 0.f, 0.f};
-        accA = mfx<0>(s01, w1x[0], accA);  accB = mfx<4>(s01, w1x[1], accB);
-        accA = mfx<8>(s01, w1x[2], accA);  accB = mfx<12>(s01, w1x[3], accB);
-        accA = mfx<0>(s23, w1x[4], accA);  accB = mfx<4>(s23, w1x[5], accB);
-        accA = mfx<8>(s23, w1x[6], accA);  accB = mfx<12>(s23, w1x[7], accB);
-        f4 hA = quad_transpose_seq<P>(elu_x<!SAVE>(accA + accB), vm);
+        f4 hA = elu_x<!SAVE>(l1_swapped(w1x, s, cz));
         float* slot = ROLES ? ring_mine + (ring_half * 4 + ring_sl) * kXSlotFloats : nullptr;
         if constexpr (ROLES) {                                       // the stage's rows into the ring slot; the partner wave stores them
             *reinterpret_cast<f2*>(slot + 768 + 2 * l) = s;
@@ -301,10 +316,10 @@ __global__ __launch_bounds__(64 * kXWaves * (ROLES ? 2 : 1)) void integrate_x_ke
             if constexpr (PSNODE_K1X_SAVE_ABL != 2) sx_run += xo_step;
             if (sa_on) stg<f4>((gptr<float>)(uintptr_t)sa_run, saoff, hA);
         }
-        hA = hh_layer<!SAVE, 1 - P>(w2, b2, hA, vm);
+        hA = hh_layer<!SAVE, 0>(w2, b2, hA, vm);
         if constexpr (ROLES) *reinterpret_cast<f4*>(slot + 256 + 4 * l) = hA;
         else if constexpr (SAVE) { if (sa_on) stg<f4>((gptr<float>)(uintptr_t)(sa_run + sa_layer), saoff, hA); }
-        hA = hh_layer<!SAVE, P>(w3, b3, hA, vm);
+        hA = hh_layer<!SAVE, 1>(w3, b3, hA, vm);
         if constexpr (ROLES) {
             *reinterpret_cast<f4*>(slot + 512 + 4 * l) = hA;
             if (++ring_sl == 4) { lds_barrier(); ring_sl = 0; ring_half ^= 1; }       // a half is complete: hand it over, fill the other one
@@ -317,31 +332,33 @@ __global__ __launch_bounds__(64 * kXWaves * (ROLES ? 2 : 1)) void integrate_x_ke
 
     // One step.  `tuse` / `euse`: the registers that hold t[k + 1] and the external value of step k; with PF the step re-issues loads INTO
     // them (the clock entry / z row `trun` / `zrun` point at).  WAITN = the vmcnt the step may start at: what was issued, in program order,
-    // BEHIND the loads of tuse / euse -- per step two loads and, last, one store (even x_dim; otherwise the count is 0: wait for everything).
+    // BEHIND the loads of tuse / euse -- per step 1 + NE loads and, last, one store (even x_dim; otherwise the count is 0: wait for everything).
     //   one step of look-ahead (general form):  store(k-1)                                  -> vmcnt(1)
-    //   two steps (FAST, Euler / Midpoint):     store(k-2), load t, load e, store(k-1)     -> vmcnt(4)
+    //   two steps (FAST, Euler / Midpoint):     store(k-2), load t, NE loads e, store(k-1) -> vmcnt(3 + NE)
     // A 1 us Euler step does not cover a clock / z row that misses the caches (SQ_WAIT_ANY 28 % of the wave's cycles with one step of
     // look-ahead, profiles/r05g_k1x_euler_pmc_sq.txt); RK4's 3 us step does.
     //   one step, two clock slots (FAST, RK4):  store(k-1)                                  -> vmcnt(1)
     // `tprev`: the register that holds t[k].  The forms above keep it in t_cur and copy tuse there; with LAG (lag_tag) it is the OTHER clock
     // slot, which is dead once h is formed -- the prefetch of t[k + 2] lands in IT, the next step uses the two slots with their roles swapped,
     // and the source has no register to move at the end of a step.
-    auto step = [&](const int k, float& tprev, float& tuse, float& euse, auto pf_tag, auto wait_tag, auto lag_tag) {
+    auto step = [&](const int k, float& tprev, float& tuse, float (&euse)[NE], auto pf_tag, auto wait_tag, auto lag_tag) {
         constexpr bool PF = decltype(pf_tag)::value;
         constexpr int WAITN = decltype(wait_tag)::value;
         constexpr bool LAG = decltype(lag_tag)::value;
         // SAVE: a step also issued 4 stores per stage (xstage + three layers, every one from at least one lane of every wave) behind its prefetch
         constexpr int NSAVE = (SAVE && !ROLES) ? 4 * (METHOD == PSNODE_EULER ? 1 : (METHOD == PSNODE_MIDPOINT ? 2 : 4)) : 0;
         // ring of R steps of look-ahead (wait tag 100 + R): behind the loads in hand sit the rest of their own step (row store + saved rows) and
-        // R - 1 whole steps (2 loads + row store + saved rows each); the legacy tags 1 / 4 are R = 1 / 2.  6 bits: [3:0], [15:14]
+        // R - 1 whole steps (1 + NE loads + row store + saved rows each); the legacy tags 1 / 4 are R = 1 / 2.  6 bits: [3:0], [15:14]
         constexpr int RDEPTH = WAITN >= 100 ? WAITN - 100 : (WAITN == 4 ? 2 : 1);
-        constexpr int WN = WAITN == 0 ? 0 : (1 + NSAVE) + (RDEPTH - 1) * (3 + NSAVE);
+        constexpr int WN = WAITN == 0 ? 0 : (1 + NSAVE) + (RDEPTH - 1) * (2 + NE + NSAVE);
         static_assert(WN <= 63, "vmcnt is 6 bits");
         if (pair_ok && WN > 0) __builtin_amdgcn_s_waitcnt(0x0F70 | (WN & 15) | ((WN >> 4) << 14));
         else __builtin_amdgcn_s_waitcnt(0x0F70);                              // vmcnt(0)
         const float h_ = tuse - tprev;
         if constexpr (!LAG) tprev = tuse;
-        const float eA = eon ? (b < ne ? euse - a0e : euse) : 0.0f;
+        float eA[NE];
+#pragma unroll
+        for (int j = 0; j < NE; ++j) eA[j] = eon[j] ? euse[j] - a0e[j] : 0.0f;       // (a slot of the second group subtracts 0: the value itself)
         f2 s = X;
         if constexpr (!FAST) {
             if (true_x) {                                            // teacher forcing: the step starts from the dataset's x[k] (uniform branch)
@@ -355,35 +372,37 @@ __global__ __launch_bounds__(64 * kXWaves * (ROLES ? 2 : 1)) void integrate_x_ke
             if constexpr (LAG) tprev = ldg<float>(as_g(trun), toff);
             else tuse = ldg<float>(as_g(trun), toff);
             if constexpr (FAST) {
-                euse = ldg<float>(as_g(zrun), zoff);
+#pragma unroll
+                for (int j = 0; j < NE; ++j) euse[j] = ldg<float>(as_g(zrun), zoff[j]);
             } else {
                 if (((k + 1) & 63) == 0) evb = load_evb((k + 1) >> 6);
                 ev_cur = __builtin_amdgcn_readlane(evb, (k + 1) & 63);
                 const bool jump = __builtin_amdgcn_readfirstlane(ev_cur) >= 0;
                 const float* zr = jump ? zjbase + (long long)ev_cur * zje : zrun;      // an event step takes the jump row (uniform select)
-                euse = ldg<float>(as_g(zr), jump ? zjoff : zoff);
+#pragma unroll
+                for (int j = 0; j < NE; ++j) {
+                    const unsigned zo = zoff[j], zjo = zjoff[j];     // (values, not a choice between two array elements: that one goes through scratch)
+                    euse[j] = ldg<float>(as_g(zr), jump ? zjo : zo);
+                }
             }
             trun += tst;
             zrun += zst;
         }
         store_row(xo_run);                                           // deferred store of the previous step's result, BEHIND the prefetch (above)
         xo_run += xo_step;
-        const f4 cz = ext_mfmas<0, 4 * NZM>(w1e, eA, c0);            // per-step constant of L1
+        const f4 cz = ext_mfmas_swapped<0, 4 * NZM, NE>(w1e, eA, c0);       // per-step constant of L1, in the A layout
         // (the RK arithmetic is elementwise on the pair: the same multiplies and adds, in the same order, as on two scalars -- packed)
-        using P0 = std::integral_constant<int, 0>;
-        using P1 = std::integral_constant<int, 1>;
-        if constexpr (METHOD == PSNODE_EULER) vm = xmask_even();     // (one stage per step: its three seams leave the other mask)
-        const f2 k1 = rhs(P0{}, s, cz);
+        const f2 k1 = rhs(s, cz);
         if constexpr (METHOD == PSNODE_EULER) {
             X = s + h_ * k1;
         } else if constexpr (METHOD == PSNODE_MIDPOINT) {
             const float hh = 0.5f * h_;
-            const f2 k2 = rhs(P1{}, s + k1 * hh, cz);
+            const f2 k2 = rhs(s + k1 * hh, cz);
             X = s + h_ * k2;
         } else {
-            const f2 k2 = rhs(P1{}, s + h_ * k1 * kOneThird, cz);
-            const f2 k3 = rhs(P0{}, s + h_ * (k2 - k1 * kOneThird), cz);
-            const f2 k4 = rhs(P1{}, s + h_ * (k1 - k2 + k3), cz);
+            const f2 k2 = rhs(s + h_ * k1 * kOneThird, cz);
+            const f2 k3 = rhs(s + h_ * (k2 - k1 * kOneThird), cz);
+            const f2 k4 = rhs(s + h_ * (k1 - k2 + k3), cz);
             X = s + (k1 + 3.0f * (k2 + k3) + k4) * h_ * 0.125f;
         }
         if constexpr (SAVE && PSNODE_K1X_SAVE_ABL == 4) sa_run += 3 * (size_t)a.B * hp * kStg - (size_t)768 * kStg;
@@ -405,13 +424,16 @@ __global__ __launch_bounds__(64 * kXWaves * (ROLES ? 2 : 1)) void integrate_x_ke
     constexpr int RING = (SAVE && !ROLES && FAST) ? (METHOD == PSNODE_RK4_38 ? 3 : (METHOD == PSNODE_MIDPOINT ? 4 : 4)) : 0;
     if constexpr (RING > 0) {
         using WR = std::integral_constant<int, 100 + RING>;
-        float tq[RING], eq[RING];                    // slot j: t[k + 1] and the external value of step k, k = j (mod RING)
-        tq[0] = t_nxt; eq[0] = e_nxt;
+        float tq[RING], eq[RING][NE];                // slot j: t[k + 1] and the external values of step k, k = j (mod RING)
+        tq[0] = t_nxt;
+#pragma unroll
+        for (int i = 0; i < NE; ++i) eq[0][i] = e_nxt[i];
 #pragma unroll
         for (int j = 1; j < RING; ++j) {
             const int rt = j + 1 < nT ? j + 1 : nT - 1, rz = j < nT ? j : nT - 1;
             tq[j] = ldg<float>(as_g(a.t.p + (long long)rt * tst), toff);
-            eq[j] = ldg<float>(as_g(zbase + (long long)rz * zst), zoff);
+#pragma unroll
+            for (int i = 0; i < NE; ++i) eq[j][i] = ldg<float>(as_g(zbase + (long long)rz * zst), zoff[i]);
         }
         trun = a.t.p + (long long)(RING + 1) * tst;   // the next refill: t[RING + 1], row RING -- requested by step 0
         zrun = zbase + (long long)RING * zst;
@@ -437,7 +459,9 @@ __global__ __launch_bounds__(64 * kXWaves * (ROLES ? 2 : 1)) void integrate_x_ke
     } else if constexpr (TWO_AHEAD) {
         // ring of two register pairs: (t_nxt, e_nxt) serve the even steps, (t_n2, e_n2) the odd ones; a step reloads the pair it used
         float t_n2 = ldg<float>(as_g(a.t.p + (nT > 2 ? 2 : 1) * tst), toff);            // t[2]
-        float e_n2 = ldg<float>(as_g(zbase + zst), zoff);                                 // external row of step 1 (row 1 exists: T >= 2)
+        float e_n2[NE];                                                                   // external row of step 1 (row 1 exists: T >= 2)
+#pragma unroll
+        for (int j = 0; j < NE; ++j) e_n2[j] = ldg<float>(as_g(zbase + zst), zoff[j]);
         trun = a.t.p + 3 * tst;                                                           // next: t[3], row 2 -- loaded by step 0
         zrun = zbase + 2 * zst;
         __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)

@@ -226,18 +226,14 @@ __global__ __launch_bounds__(64 * kXWaves) void integrate_xd_kernel(const Integr
     float* sae_run = SAVE ? a.saeact : nullptr;                     // the AE head's rows of the NEXT grid point to be evaluated
     const unsigned saoff = SAVE ? (unsigned)(tr * hp + 4 * b) * 4u : 0u;
     const bool sa_on = SAVE && valid && 4 * b < hp;
-    // The mask the next in-quad transpose starts on (psnode_mfma_x.h: quad_transpose_seq).  Every sequence of seams -- the DE stages of a step, one
-    // AE head (its own XMask) -- starts from xmask_even() and alternates the order from seam to seam: 3 mask moves per seam instead of 4.
+    // The mask the next in-quad transpose starts on (psnode_mfma_x.h: quad_transpose_seq).  Every sequence of seams -- the DE's of a step (the
+    // per-step constant's, then two per stage), one AE head (its own XMask) -- starts from xmask_even() and alternates the order from seam to
+    // seam: 3 mask moves per seam instead of 4.
     XMask vm = xmask_even();
-    // DE right-hand side in the state layout (K1x's rhs).  P: the transpose order of the stage's first seam (orders P, !P, P)
-    auto rhs = [&](auto par_tag, const float s01, const float s23, const f4 cz, float& k01, float& k23) {
-        constexpr int P = decltype(par_tag)::value;
-        f4 accA = cz, accB = f4{0.f, 0.f, 0.f, 0.f};
-        accA = mfx<0>(s01, w1x[0], accA);  accB = mfx<4>(s01, w1x[1], accB);
-        accA = mfx<8>(s01, w1x[2], accA);  accB = mfx<12>(s01, w1x[3], accB);
-        accA = mfx<0>(s23, w1x[4], accA);  accB = mfx<4>(s23, w1x[5], accB);
-        accA = mfx<8>(s23, w1x[6], accA);  accB = mfx<12>(s23, w1x[7], accB);
-        f4 hA = quad_transpose_seq<P>(elu_x<!SAVE>(accA + accB), vm);
+    // DE right-hand side in the state layout (K1x's rhs): L1 with the roles swapped (psnode_mfma_x.h: l1_swapped -- its accumulator is the A
+    // layout, no transpose behind its ELU); cz in the A layout.  The stage's two seams run in the orders 1, 0 (the step's first seam is cz's).
+    auto rhs = [&](const float s01, const float s23, const f4 cz, float& k01, float& k23) {
+        f4 hA = elu_x<!SAVE>(l1_swapped(w1x, f2{s01, s23}, cz));
         if constexpr (SAVE) {                                        // rows (step, stage): the stage input, then the three layers as they appear
             if (pair_ok) {
                 if (st01) stg<f2>((gptr<float>)(uintptr_t)sx_run, xooff, f2{s01, s23});
@@ -248,9 +244,9 @@ __global__ __launch_bounds__(64 * kXWaves) void integrate_xd_kernel(const Integr
             sx_run += xo_step;
             if (sa_on) stg<f4>((gptr<float>)(uintptr_t)sa_run, saoff, hA);
         }
-        hA = hh_layer<!SAVE, 1 - P>(w2, b2, hA, vm);
+        hA = hh_layer<!SAVE, 1>(w2, b2, hA, vm);
         if constexpr (SAVE) { if (sa_on) stg<f4>((gptr<float>)(uintptr_t)(sa_run + sa_layer), saoff, hA); }
-        hA = hh_layer<!SAVE, P>(w3, b3, hA, vm);
+        hA = hh_layer<!SAVE, 0>(w3, b3, hA, vm);
         if constexpr (SAVE) {
             if (sa_on) stg<f4>((gptr<float>)(uintptr_t)(sa_run + 2 * sa_layer), saoff, hA);
             sa_run += 3 * sa_layer;
@@ -394,25 +390,25 @@ __global__ __launch_bounds__(64 * kXWaves) void integrate_xd_kernel(const Integr
         store_rows(xo_run, io_run, i_k);      // deferred store of grid point k (the previous step's result)
         xo_run += xo_step;
         io_run += io_step;
-        const f4 cz = ext_mfmas<0, 16>(w1e, eA, c0);
+        // per-step constant of L1: the external slots keep their placement (block b = slot_of_block(b), which the i -> DE feedback is built on),
+        // so it is formed in the D layout as before and transposed ONCE per step into the A layout L1 accumulates in
+        vm = xmask_even();                                           // (the AE head in front of this step used vcc for its own sequence)
+        const f4 cz = quad_transpose_seq<0>(ext_mfmas<0, 16>(w1e, eA, c0), vm);
         const float s01 = X01, s23 = X23;
         float k1a, k1b;
-        using P0 = std::integral_constant<int, 0>;
-        using P1 = std::integral_constant<int, 1>;
-        vm = xmask_even();                                           // (the AE head in front of this step used vcc for its own sequence)
-        rhs(P0{}, s01, s23, cz, k1a, k1b);
+        rhs(s01, s23, cz, k1a, k1b);
         if constexpr (METHOD == PSNODE_EULER) {
             X01 = s01 + h_ * k1a; X23 = s23 + h_ * k1b;
         } else if constexpr (METHOD == PSNODE_MIDPOINT) {
             const float hh = 0.5f * h_;
             float k2a, k2b;
-            rhs(P1{}, s01 + k1a * hh, s23 + k1b * hh, cz, k2a, k2b);
+            rhs(s01 + k1a * hh, s23 + k1b * hh, cz, k2a, k2b);
             X01 = s01 + h_ * k2a; X23 = s23 + h_ * k2b;
         } else {
             float k2a, k2b, k3a, k3b, k4a, k4b;
-            rhs(P1{}, s01 + h_ * k1a * kOneThird, s23 + h_ * k1b * kOneThird, cz, k2a, k2b);
-            rhs(P0{}, s01 + h_ * (k2a - k1a * kOneThird), s23 + h_ * (k2b - k1b * kOneThird), cz, k3a, k3b);
-            rhs(P1{}, s01 + h_ * (k1a - k2a + k3a), s23 + h_ * (k1b - k2b + k3b), cz, k4a, k4b);
+            rhs(s01 + h_ * k1a * kOneThird, s23 + h_ * k1b * kOneThird, cz, k2a, k2b);
+            rhs(s01 + h_ * (k2a - k1a * kOneThird), s23 + h_ * (k2b - k1b * kOneThird), cz, k3a, k3b);
+            rhs(s01 + h_ * (k1a - k2a + k3a), s23 + h_ * (k1b - k2b + k3b), cz, k4a, k4b);
             X01 = s01 + (k1a + 3.0f * (k2a + k3a) + k4a) * h_ * 0.125f;
             X23 = s23 + (k1b + 3.0f * (k2b + k3b) + k4b) * h_ * 0.125f;
         }
