@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define PSNODE_ABI_VERSION 10    /* 10 also carries the additive psnode_act_f32 / *_act_*, psnode_rk_tableau_f32 / *_rk_*, psnode_substeps_f32 / *_sub_*, *_lin_*, *_pev_* / psnode_event_table_pt_f32, *_ab_*, *_ab3_* and *_lag_* / psnode_ext_stencil_f32 entry points (end of this file), and psnode_loss_fn_f32 / psnode_masked_loss_* / psnode_loss_per_sample_f32 (next to psnode_masked_mse_f32) */
+#define PSNODE_ABI_VERSION 10    /* 10 also carries the additive psnode_act_f32 / *_act_*, psnode_rk_tableau_f32 / *_rk_*, psnode_substeps_f32 / *_sub_*, *_lin_*, *_pev_* / psnode_event_table_pt_f32, *_ab_*, *_ab3_*, *_lag_* / psnode_ext_stencil_f32 and psnode_dae_*_sth_* entry points (end of this file), and psnode_loss_fn_f32 / psnode_masked_loss_* / psnode_loss_per_sample_f32 (next to psnode_masked_mse_f32) */
 #define PSNODE_MAX_LAYERS 8      /* Linear layers per MLP */
 #define PSNODE_MAX_WIDTH 1024    /* widest layer OUTPUT the kernels accept */
 #define PSNODE_MAX_IN_WIDTH 2048 /* widest first-layer INPUT (the latent DE of DAE_02 at --hidden 128 is 12 x 128 = 1536 wide) */
@@ -1116,6 +1116,44 @@ size_t psnode_dae_backward_rkc_workspace_size(const psnode_dae_bwd_tf_args_f32* 
                                               const psnode_act_f32* ae_act, const psnode_rkc_f32* rkc);
 int32_t psnode_dae_backward_rkc_f32(const psnode_dae_bwd_tf_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
                                     const psnode_rkc_f32* rkc, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- Stage-wise algebraic heads for Runge-Kutta DAE steps on the generic kernels (additive to ABI 10; DESIGN.md "Stage-wise algebraic
+ * heads on K0 / K5").  The _lin / _lag families freeze a DAE's algebraic variable i over the stages of a (sub-)step, as the reference does;
+ * this family evaluates it at every stage, the standard treatment of an index-1 DAE.  Interval k, n sub-steps, sub-step j, stage s with
+ * abscissa c_s and theta_s = (j + c_s) / n:
+ *     stage 0 reads the i it reads in _lin / _lag: the carried head of grid point k, the event-time head on the jumped rows, and for
+ *     j >= 1 the in-interval head at theta = j / n;
+ *     stage s >= 1, X_s = x + h sum_{j' < s} a[s][j'] k_j', (z_s, v_s) the interpolant at theta_s (the rows its DE stage reads):
+ *         i_s = g(X_s, z_s, v_s, all_initial),   k_s = f(X_s, z_s, v_s, i_s)   -- one more AE evaluation per stage, no output row.
+ * The head at grid point k + 1, both outputs, h, the event table, theta and the interpolants are untouched.  Under
+ * PSNODE_FLAG_INPUT_TRUE_I every stage reads i_true[k] and no head runs inside an interval, and a one-stage tableau has no stage s >= 1:
+ * both calls compute what their _lin / _lag siblings compute.  A DAE only: an ODE has no head.
+ * The entry points take what their _lag siblings take plus `interp` behind the stencil table, which picks the interpolant:
+ * PSNODE_EXT_LINEAR (the straight line of the _lin family; the table is not read) or PSNODE_EXT_LAGRANGE (the polynomial of the _lag family
+ * through the table's stencils; NULL: one piece).  Any other value is PSNODE_ERR_METHOD in front of every other check (the queries: 0);
+ * behind it the order of the checks and the statuses are the _lin / _lag family's, and every check returns before a launch.  LDS fit and
+ * workspaces are those siblings' (no LDS of its own: K5 recomputes a stage's i in front of its VJP); psnode_dae_backward_sth_workspace_size is
+ * the family's workspace query (bytes; named as psnode_dae_backward_lag_workspace_size is).  The backward sends the i part of the
+ * DE's VJP of a stage s >= 1 through the head's VJP at (X_s, the externals at theta_s): its x part joins the adjoint of X_s, its z | v part
+ * goes where the stage's own external adjoint goes, all_initial and the AE's parameters where the in-interval head's go.  Fixed
+ * ownership, no atomics, bitwise repeatable.  The clock gets no gradient. */
+#define PSNODE_EXT_LINEAR 1
+#define PSNODE_EXT_LAGRANGE 2
+int32_t psnode_dae_integrate_sth_supported(const psnode_dae_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                           const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub,
+                                           const psnode_ext_stencil_f32* stencil, int32_t interp);
+int32_t psnode_dae_integrate_sth_f32(const psnode_dae_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                     const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, const psnode_ext_stencil_f32* stencil,
+                                     int32_t interp, void* workspace, size_t workspace_bytes, void* stream);
+int32_t psnode_dae_backward_sth_supported(const psnode_dae_bwd_tf_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                          const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub,
+                                          const psnode_ext_stencil_f32* stencil, int32_t interp);
+size_t psnode_dae_backward_sth_workspace_size(const psnode_dae_bwd_tf_args_f32* args, const psnode_act_f32* de_act,
+                                              const psnode_act_f32* ae_act, const psnode_rk_tableau_f32* tab,
+                                               const psnode_substeps_f32* sub, const psnode_ext_stencil_f32* stencil, int32_t interp);
+int32_t psnode_dae_backward_sth_f32(const psnode_dae_bwd_tf_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                    const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, const psnode_ext_stencil_f32* stencil,
+                                    int32_t interp, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

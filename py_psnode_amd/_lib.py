@@ -51,6 +51,8 @@ ABI_VERSION = 10         # == PSNODE_ABI_VERSION of include/psnode_hip.h (2: rou
                          #     multiple-shooting segments on K0 / K5;
                          #     additive, same version: psnode_segment_groups_f32 and the psnode_{ode,dae}_{integrate,backward}_msp_* entry points
                          #     (with psnode_{ode,dae}_backward_msp_workspace_size) -- those segments spread over a tiles x chunks launch grid;
+                         #     additive, same version: the psnode_dae_{integrate,backward}_sth_* entry points -- a DAE's algebraic head evaluated
+                         #     at every Runge-Kutta stage on the linear / Lagrange builds of K0 / K5;
                          #     additive, same version: psnode_loss_fn_f32 and psnode_masked_loss_* / psnode_loss_per_sample_f32 -- L1, SmoothL1 and
                          #     Huber on K6, and the per-sample evaluation table of all four kinds)
 LIB_NAME = "libpsnode_hip.so"
@@ -111,6 +113,8 @@ EXPORTS = (
     "psnode_ode_integrate_msp_supported", "psnode_ode_integrate_msp_f32", "psnode_dae_integrate_msp_supported", "psnode_dae_integrate_msp_f32",
     "psnode_ode_backward_msp_supported", "psnode_ode_backward_msp_workspace_size", "psnode_ode_backward_msp_f32",
     "psnode_dae_backward_msp_supported", "psnode_dae_backward_msp_workspace_size", "psnode_dae_backward_msp_f32",
+    "psnode_dae_integrate_sth_supported", "psnode_dae_integrate_sth_f32",
+    "psnode_dae_backward_sth_supported", "psnode_dae_backward_sth_workspace_size", "psnode_dae_backward_sth_f32",
 )
 
 
@@ -380,11 +384,11 @@ def load():
     for stem, args_t, n_act in (("ode_integrate", OdeArgsF32, 1), ("dae_integrate", DaeArgsF32, 2), ("ode_backward", OdeBwdArgsF32, 1),
                                 ("dae_backward", DaeBwdArgsF32, 2)):
         for fam, f in FAMILIES.items():
-            if fam in ("plain", "none") or (fam == "tf" and stem != "dae_backward"):
+            if fam in ("plain", "none") or (fam == "tf" and stem != "dae_backward") or (f.dae_only and not stem.startswith("dae_")):
                 continue
             query = [ptr(DaeBwdTfArgsF32 if stem == "dae_backward" and f.tf_args else args_t)] + [ptr(ActF32)] * (n_act if f.acts else 0) + \
                     [ptr(RkTableauF32)] * f.tab + [ptr(SubstepsF32)] * f.sub + [ptr(SegmentGroupsF32 if f.par else SegmentsF32)] * f.seg + \
-                    [c_void_p] * f.stencil + [ptr(RkcF32)] * f.rkc      # (the device pointer of the int8 [T-1, B] stencil table, or NULL)
+                    [c_void_p] * f.stencil + [c_int32] * f.interp + [ptr(RkcF32)] * f.rkc      # (the device pointer of the int8 [T-1, B] stencil table, or NULL; the interpolant)
             protos = {"supported": (c_int32, query), "f32": (c_int32, query + [c_int32] * f.pt + [c_void_p, c_size_t, c_void_p])}
             if stem == "dae_backward" and f.workspace == "own" and not f.par:      # (the family with a stencil table names its query _workspace_size)
                 protos["workspace_size" if f.stencil or f.rkc else "workspace_bytes"] = (c_size_t, query)

@@ -90,24 +90,35 @@ def _dae_tf_on_k7f(method, kernel, de, ae, x_dim, z_dim, v_dim, i_dim) -> bool:
     return not _is_tableau(method) and kernel in ("auto", "mfma") and fused.dae_backward_wide_supported(method, de, ae, x_dim, z_dim, v_dim, i_dim)
 
 
+def _dae_algebraic(algebraic, input_true_i):
+    """The `algebraic` a DAE call runs with: under input_true_i every stage reads i[k] and no head runs inside an interval, so "stage"
+    (validated) is the "step" call."""
+    if not isinstance(algebraic, str) or algebraic not in fused.ALGEBRAIC:
+        raise ValueError(f"algebraic must be one of {fused.ALGEBRAIC}, got {algebraic!r}")
+    return "step" if input_true_i else algebraic
+
+
 def dae_training_supported(method, de, ae, x_dim, z_dim, v_dim, i_dim, T, B, act=None, kernel="auto", input_true_x=False,
-                           input_true_i=False, substeps=1, externals="hold", per_trajectory=False, segment=None, segment_parallel=None) -> bool:
-    """act: None (both MLPs ELU(1)) or (de_act, ae_act); an activation other than ELU(1) trains on K0 + K5 alone, so K5 answers.
+                           input_true_i=False, substeps=1, externals="hold", per_trajectory=False, segment=None, segment_parallel=None,
+                           algebraic="step") -> bool:
+    """algebraic="stage" (with input_true_i the "step" call): K0 + K5 in their stage-heads builds, under the interpolant's rules.
+    act: None (both MLPs ELU(1)) or (de_act, ae_act); an activation other than ELU(1) trains on K0 + K5 alone, so K5 answers.
     input_true_x / input_true_i: teacher-forced training (T >= 2, ELU(1) only) -- K7f's recompute form on kernel "auto" / "mfma" where the
     shape is its, else K5 on "auto" / "generic".  method a fused.Tableau: K0 + K5 on kernel "auto" / "generic", the same rules.
     substeps > 1: K0 + K5 in their sub-step builds on kernel "auto" / "generic", the same rules.
     externals="linear" / "lagrange": K0 + K5 in their linear-externals / Lagrange builds for every substeps >= 1, the same rules.
     per_trajectory=True (a call WITH events): K0 + K5 in their per-trajectory builds for every substeps >= 1, the same rules.
     segment (an int >= 1): K0 + K5 in their multiple-shooting builds, as ode_training_supported; segment_parallel: as there."""
+    algebraic = _dae_algebraic(algebraic, input_true_i)
     opts = fused.GenericOpts.of(method, fused.dae_acts(act), substeps, externals, bool(per_trajectory), segment,
-                                fused.resolve_segment_parallel(segment_parallel, segment, T, B, de[0][0].device))
+                                fused.resolve_segment_parallel(segment_parallel, segment, T, B, de[0][0].device), algebraic)
     teacher_forced = input_true_x or input_true_i
     if opts.family != "plain":
         if opts.family == "act":      # (an activation alone: asked without the caller's kernel, as the ELU(1) call at the bottom is)
             kernel = "auto"
         return _generic_only_training(opts, kernel, teacher_forced, T) and fused.dae_backward_supported(
             method, de, ae, x_dim, z_dim, v_dim, i_dim, act=act, kernel=kernel, substeps=substeps, externals=externals,
-            per_trajectory=per_trajectory, segment=segment, segment_parallel=opts.chunks(T))
+            per_trajectory=per_trajectory, segment=segment, segment_parallel=opts.chunks(T), algebraic=algebraic)
     if teacher_forced:
         if T < 2:
             return False
@@ -318,11 +329,11 @@ class _FusedOdeGeneric(torch.autograd.Function):
 
 # fused.GenericOpts.family ("ab": with per_trajectory) -> the name of its Function: `_FusedOde<name>` / `_FusedDae<name>`, an empty subclass of
 # the model's one body, is what xs.grad_fn reports.  A further family of K0 / K5 that saves sub-state rows adds a row here, not a class.
-_FAMILY_CLASSES = {"sub": "Sub", "lin": "Lin", "lag": "Lag", "pev": "Pev", ("ab", False): "Ab", ("ab", True): "AbPev", ("ab3", False): "Ab3", ("ab3", True): "Ab3Pev", "ms": "Ms", "msp": "Msp", "rkc": "Rkc"}
+_FAMILY_CLASSES = {"sub": "Sub", "lin": "Lin", "lag": "Lag", "pev": "Pev", ("ab", False): "Ab", ("ab", True): "AbPev", ("ab3", False): "Ab3", ("ab3", True): "Ab3Pev", "ms": "Ms", "msp": "Msp", "rkc": "Rkc", "sth": "Sth"}
 # the families that go to _FusedOde / _FusedDae / _FusedDaeTeacherForced
 _OWN_CLASS = ("plain", "act", "rk")
 # ... and those whose forward (fused.ode_integrate / fused.dae_integrate) is the first to check the call
-_CHECKED_BY_FORWARD = _OWN_CLASS + ("sub", "lin", "lag")
+_CHECKED_BY_FORWARD = _OWN_CLASS + ("sub", "lin", "lag", "sth")
 
 
 def _family_classes(body, prefix) -> dict:
@@ -460,7 +471,7 @@ class _FusedDaeGeneric(torch.autograd.Function):
         xs, is_, x_sub = fused.dae_integrate(method, de, ae, x_init, t, x, z, v, i, all_initial, z_jump=z_jump, v_jump=v_jump, event_idx=event_idx,
                                              kernel=kernel, input_true_x=tx, input_true_i=ti, act=act, substeps=opts.substeps, save_sub=True,
                                              externals=opts.externals, per_trajectory=opts.per_trajectory, segment=opts.segment,
-                                             segment_parallel=opts.chunks(t.shape[0]))
+                                             segment_parallel=opts.chunks(t.shape[0]), algebraic=opts.algebraic)
         global last_saved_bytes
         last_saved_bytes = x_sub.numel() * x_sub.element_size()
         ctx.method, ctx.opts, ctx.kernel, ctx.act, ctx.tx, ctx.ti, ctx.n_de, ctx.event_idx = method, opts, kernel, act, tx, ti, n_de, event_idx
@@ -473,7 +484,7 @@ class _FusedDaeGeneric(torch.autograd.Function):
         de, ae = _layers(params, ctx.n_de)
         opts = ctx.opts
         common = dict(event_idx=ctx.event_idx, kernel=ctx.kernel, substeps=opts.substeps, x_sub=x_sub, externals=opts.externals,
-                      per_trajectory=opts.per_trajectory, **opt)
+                      per_trajectory=opts.per_trajectory, algebraic=opts.algebraic, **opt)
         if ctx.tx or ctx.ti:
             g = fused.dae_backward_tf(ctx.method, de, ae, t, z, v, a0, xs, is_, grad_xs, grad_is, x_true=x if ctx.tx else None,
                                       i_true=i if ctx.ti else None, **common)
@@ -489,8 +500,9 @@ globals().update({cls.__name__: cls for cls in _DAE_CLASSES.values()})      # _F
 
 def fused_dae_integrate(method, kernel, de_layers, ae_layers, x_init, t, z, v, i, all_initial, event_t=None, z_jump=None, v_jump=None,
                         check_events=False, x=None, input_true_x=False, input_true_i=False, act=None, substeps=1, externals="hold",
-                        per_trajectory=False, segment=None, segment_parallel=None):
-    """Differentiable fused integrate_DAE: gradients flow to x_init, z, v, all_initial, the jump inputs and both MLPs.  Without teacher
+                        per_trajectory=False, segment=None, segment_parallel=None, algebraic="step"):
+    """algebraic="stage": the stage-heads family (the "step" call under input_true_i); gradients reach everything listed below.
+    Differentiable fused integrate_DAE: gradients flow to x_init, z, v, all_initial, the jump inputs and both MLPs.  Without teacher
     forcing `i` only provides the width of the algebraic variable.  input_true_x / input_true_i: `x` / `i` are the dataset rows the DE
     and the heads are fed (my_solvers.py:111-121); they get no gradient.  act: None or (de_act, ae_act) (fused.Act, None = ELU(1)); an
     activation other than ELU(1) trains on K0 + K5 (no teacher forcing).  per_trajectory: as fused_ode_integrate.  segment: multiple
@@ -505,7 +517,8 @@ def fused_dae_integrate(method, kernel, de_layers, ae_layers, x_init, t, z, v, i
     params = [p for wb in list(de_layers) + list(ae_layers) for p in wb]
     tx, ti = bool(input_true_x), bool(input_true_i)
     opts = fused.GenericOpts.of(method, fused.dae_acts(act), substeps, externals, bool(per_trajectory) and event_idx is not None, segment,
-                                fused.resolve_segment_parallel(segment_parallel, segment, t.shape[0], t.shape[1], t.device))
+                                fused.resolve_segment_parallel(segment_parallel, segment, t.shape[0], t.shape[1], t.device),
+                                _dae_algebraic(algebraic, ti))
     _refuse("fused_dae_integrate", opts, kernel, tx or ti)
     if opts.segment is not None and (x is None or x.shape[-1] == 0):
         raise ValueError(f"fused_dae_integrate: segment={segment} restarts from the dataset rows x[k]; this call has none")

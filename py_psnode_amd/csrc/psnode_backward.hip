@@ -104,6 +104,8 @@ int generic_backward(BuildId build, const GenericBwdCall& c, const ActPair* act,
         case kBuildAb3: return generic_backward_launch<BuildAb3>(c, act, ws, s);
         case kBuildLag: return generic_backward_launch<BuildLag>(c, act, ws, s);
         case kBuildRkc: return generic_backward_launch<BuildRkc>(c, act, ws, s);
+        case kBuildLinSth: return generic_backward_launch<BuildLinSth>(c, act, ws, s);
+        case kBuildLagSth: return generic_backward_launch<BuildLagSth>(c, act, ws, s);
     }
     return PSNODE_ERR_UNSUPPORTED;      // (no such build)
 }
@@ -498,6 +500,26 @@ extern "C" size_t psnode_dae_backward_lag_workspace_size(const psnode_dae_bwd_tf
                                                          const psnode_act_f32* ae_act, const psnode_rk_tableau_f32* tab,
                                                          const psnode_substeps_f32* sub, const psnode_ext_stencil_f32* st) {
     return k5_workspace_bytes(kFamLag, a, {de_act, ae_act, tab, sub, nullptr, 0, nullptr, st});
+}
+// (stage-wise algebraic heads, DAE only: the _lag family's prototypes and order of checks plus `interp`, which picks the interpolant)
+extern "C" int32_t psnode_dae_backward_sth_supported(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act,
+                                                     const psnode_act_f32* ae_act, const psnode_rk_tableau_f32* tab,
+                                                     const psnode_substeps_f32* sub, const psnode_ext_stencil_f32* st, int32_t interp) {
+    Family fam;
+    return sth_family(interp, fam) ? k5_supported(fam, a, {de_act, ae_act, tab, sub, nullptr, 0, nullptr, st}) : 0;
+}
+extern "C" size_t psnode_dae_backward_sth_workspace_size(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act,
+                                                          const psnode_act_f32* ae_act, const psnode_rk_tableau_f32* tab,
+                                                          const psnode_substeps_f32* sub, const psnode_ext_stencil_f32* st, int32_t interp) {
+    Family fam;
+    return sth_family(interp, fam) ? k5_workspace_bytes(fam, a, {de_act, ae_act, tab, sub, nullptr, 0, nullptr, st}) : 0;
+}
+extern "C" int32_t psnode_dae_backward_sth_f32(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                               const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, const psnode_ext_stencil_f32* st,
+                                               int32_t interp, void* ws, size_t bytes, void* stream) {
+    Family fam;
+    if (!sth_family(interp, fam)) return PSNODE_ERR_METHOD;
+    return k5_backward(fam, a, {de_act, ae_act, tab, sub, nullptr, 0, nullptr, st}, ws, bytes, stream);
 }
 extern "C" int32_t psnode_dae_backward_lag_f32(const psnode_dae_bwd_tf_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
                                                const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, const psnode_ext_stencil_f32* st,

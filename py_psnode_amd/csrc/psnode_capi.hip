@@ -95,7 +95,7 @@ int dispatch(IntegrateDev& d, bool dae, int kernel, const psnode_mlp_f32* de, co
     if (d.T < 1 || d.B < 1) return PSNODE_ERR_DIMS;
     if (use_mfma) return ok_or_hip(launch_mfma(d, dae, pack, stream));
 
-    if (generic_lds_bytes(d, dae, call.build == kBuildLag ? 2 : (call.build == kBuildLin ? 1 : 0)) > 160 * 1024) return PSNODE_ERR_UNSUPPORTED;
+    if (generic_lds_bytes(d, dae, (call.build == kBuildLag || call.build == kBuildLagSth) ? 2 : ((call.build == kBuildLin || call.build == kBuildLinSth) ? 1 : 0)) > 160 * 1024) return PSNODE_ERR_UNSUPPORTED;
     hipError_t e = launch_pack_image(d.de, dae ? &d.ae : nullptr, d.xd, d.xd + d.zd + (dae ? d.vd + d.id : 0), d.zd + (dae ? d.vd : 0), stream);
     if (e != hipSuccess) return PSNODE_ERR_HIP;
     switch (call.build) {
@@ -112,6 +112,8 @@ int dispatch(IntegrateDev& d, bool dae, int kernel, const psnode_mlp_f32* de, co
         case kBuildAb3: e = launch_generic<BuildAb3>(d, dae, call, stream); break;
         case kBuildLag: e = launch_generic<BuildLag>(d, dae, call, stream); break;
         case kBuildRkc: e = launch_generic<BuildRkc>(d, dae, call, stream); break;
+        case kBuildLinSth: e = launch_generic<BuildLinSth>(d, dae, call, stream); break;
+        case kBuildLagSth: e = launch_generic<BuildLagSth>(d, dae, call, stream); break;
     }
     return ok_or_hip(e);
 }
@@ -199,7 +201,7 @@ int fill_dae(const psnode_dae_args_f32* a, IntegrateDev& d) {
     return PSNODE_OK;
 }
 
-// ---- The K0 entry-point families psnode_{ode,dae}_integrate_{act,rk,sub,lin,lag,pev,ab,ab3,ms,msp,rkc}_*: one checked call path (k0_integrate) and one query
+// ---- The K0 entry-point families psnode_{ode,dae}_integrate_{act,rk,sub,lin,lag,pev,ab,ab3,ms,msp,rkc}_* and psnode_dae_integrate_sth_*: one checked call path (k0_integrate) and one query
 // (k0_supported) over the family table of psnode_generic_family.h, which also holds the order of the checks per family.
 // the ODE / DAE difference: the side outputs, the recipe widths, fill_*, the AE, the plain entry point
 bool side_outputs(const psnode_ode_args_f32& a) { return a.save_act || a.save_xstage; }
@@ -515,6 +517,21 @@ int32_t psnode_ode_integrate_lag_f32(const psnode_ode_args_f32* args, const psno
 int32_t psnode_dae_integrate_lag_supported(const psnode_dae_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
                                            const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, const psnode_ext_stencil_f32* st) {
     return k0_supported(kFamLag, a, {de_act, ae_act, tab, sub, nullptr, 0, nullptr, st});
+}
+// (stage-wise algebraic heads, DAE only: the _lag family's prototypes and order of checks plus `interp`, which picks the interpolant and
+//  with it the _lin or the _lag row on the stage-heads builds; the table is read under PSNODE_EXT_LAGRANGE alone)
+int32_t psnode_dae_integrate_sth_supported(const psnode_dae_args_f32* a, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                           const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, const psnode_ext_stencil_f32* st,
+                                           int32_t interp) {
+    Family fam;
+    return sth_family(interp, fam) ? k0_supported(fam, a, {de_act, ae_act, tab, sub, nullptr, 0, nullptr, st}) : 0;
+}
+int32_t psnode_dae_integrate_sth_f32(const psnode_dae_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
+                                     const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, const psnode_ext_stencil_f32* st,
+                                     int32_t interp, void* ws, size_t bytes, void* stream) {
+    Family fam;
+    if (!sth_family(interp, fam)) return PSNODE_ERR_METHOD;
+    return k0_integrate(fam, args, {de_act, ae_act, tab, sub, nullptr, 0, nullptr, st}, ws, bytes, stream);
 }
 int32_t psnode_dae_integrate_lag_f32(const psnode_dae_args_f32* args, const psnode_act_f32* de_act, const psnode_act_f32* ae_act,
                                      const psnode_rk_tableau_f32* tab, const psnode_substeps_f32* sub, const psnode_ext_stencil_f32* st, void* ws,

@@ -190,6 +190,10 @@
     if constexpr (Bd::ms) ms_w = __builtin_amdgcn_readfirstlane(ms_every(sub));
     if constexpr (Bd::par) { if (k_lo > 0) ms_cnt = ms_w; }      // (a later chunk's first step leaves a restart point)
 
+    // Stage-wise algebraic heads (Bd::sth, on Bd::lin's policy; DAE): behind a stage pass that is not the (sub-)step's last the head runs at the
+    // next stage's argument and externals -- the pass writes both into the AE input as well -- and its result becomes the i columns of the DE
+    // input, the way the in-interval head in front of a sub-step does.  sth_hd: the evaluation about to run is such a head (workgroup-uniform).
+    [[maybe_unused]] bool sth_hd = false;
     float pz[PF];
     // Linear externals (Bd::lin): stage s of sub-step j reads z | v at theta = (j + c_s) / nsub between the interval's left rows (wl) and the
     // dataset's rows of grid point k + 1 (zvn, which the first stage pass of the interval fills from the look-ahead registers).  th_in: the
@@ -322,13 +326,19 @@
         const int e_end = Bd::ab3 ? (DAE ? 4 : (any_rs ? 3 : 1)) : ((DAE && si.last()) ? nstage + 1 : nstage);
         for (int e = k < 0 ? (Bd::ab3 ? 4 : nstage + 1) : ((DAE && (si.first() ? (Bd::pev ? any_ev : (ev >= 0 || (Bd::ms && ms_rs))) : !true_i)) ? 0 : 1); e <= e_end; ++e) {
             if constexpr (Bd::ab3) { if ((e == 2 && !(DAE && any_rs)) || (e == 3 && !any_rs)) continue; }
-            const bool is_ae = DAE && (e == 0 || e == (Bd::ab3 ? 4 : nstage + 1) || (Bd::ab3 && e == 2));
-            const bool ae_next = Bd::ab3 ? (DAE && (e == 1 || e == 3)) : (DAE && e == nstage && (si.last() || !true_i));
+            // (a constant selects the arm: the builds without stage heads keep the expression they had)
+            const bool is_ae = Bd::sth ? (DAE && (e == 0 || e == nstage + 1 || sth_hd))
+                                       : (DAE && (e == 0 || e == (Bd::ab3 ? 4 : nstage + 1) || (Bd::ab3 && e == 2)));
+            // (Bd::sth: a stage head stands between the stages s and s + 1, so the AE follows every DE stage and the DE every stage head)
+            const bool ae_next = Bd::ab3 ? (DAE && (e == 1 || e == 3))
+                                         : (Bd::sth ? (DAE && !sth_hd && e >= 1 && (e == nstage ? (si.last() || !true_i) : !true_i))
+                                                    : (DAE && e == nstage && (si.last() || !true_i)));
             int f;
             if constexpr (MODE == 0 || MODE == 3) {
                 // (sub-steps: the externals change inside an interval only where the DAE's own i does)
                 // (linear externals: and in front of every stage whose theta is not the one folded)
-                if ((e == 1 && (si.first() || (DAE && !true_i))) || (Bd::lin && !is_ae && th_in != th_fd) || (Bd::ab3 && e == 3)) {       // the step's externals are in place (behind an event's AE evaluation too): the DE's per-step constant
+                if ((e == 1 && (si.first() || (DAE && !true_i))) || (Bd::lin && !is_ae && th_in != th_fd) || (Bd::ab3 && e == 3) ||
+                    (Bd::sth && DAE && !is_ae && e > 1 && !true_i)) {      // (Bd::sth: the i columns changed in front of this stage)       // the step's externals are in place (behind an event's AE evaluation too): the DE's per-step constant
                     const int nt0 = tab_tiles(tde.dims[0]);
                     if (wv < nt0) cde = fold0<ML>(tde, lds, inDE, wv);
                     if (MODE == 3 && wv + 4 < nt0) cde2 = fold0<ML>(tde, lds, inDE, wv + 4);
@@ -347,6 +357,16 @@
             }
             K0_PROF(2)
             if (is_ae) {
+                if constexpr (DAE && Bd::sth) {
+                    if (sth_hd) {      // i_s = g(X_s; z | v at theta_s): the algebraic input of stage e, no output row; the loop comes back to e
+                        for (int idx = tid; idx < id * TB; idx += NT) put_ext(nzv + idx / TB, idx % TB, lds[f + qi(idx / TB, idx % TB)]);
+                        lds_barrier();
+                        sth_hd = false;
+                        --e;
+                        K0_PROF(4)
+                        continue;
+                    }
+                }
                 if constexpr (DAE) {
                     for (int idx = tid; idx < id * TB; idx += NT) {
                         const int r = idx / TB, c = idx % TB;
@@ -475,7 +495,7 @@
                         v = l_ + th * (zvn[idx] - l_);
                         }
                         put_ext(r, c, v);
-                        if constexpr (DAE) if (final_stage) lds[inAE + qi(xd + r, c)] = v;
+                        if constexpr (DAE) if (final_stage || Bd::sth) lds[inAE + qi(xd + r, c)] = v;      // (Bd::sth: the stage head's rows)
                     }
                     th_in = th;
                 }
@@ -531,6 +551,7 @@
                 }
                 if (!final_stage) {
                     put_x(r, c, v);
+                    if constexpr (DAE && Bd::sth) lds[inAE + qi(r, c)] = v;      // X_{s + 1}, the stage head's state
                 } else {
                     if constexpr (Bd::sub) {
                         if (!si.last()) {      // the start state of sub-step si.i + 1: nothing of grid point k + 1 is touched
@@ -562,6 +583,7 @@
                     if constexpr (DAE) lds[inAE + qi(xd + idx / TB, idx % TB)] = v;
                 }
             }
+            if constexpr (DAE && Bd::sth) { if (!final_stage && !true_i) sth_hd = true; }
             lds_barrier();
             K0_PROF(3)
         }

@@ -1,4 +1,4 @@
-// The build policy of the generic kernels K0 (psnode_generic_impl.h) and K5 (psnode_generic_bwd_impl.h): what separates the eleven objects each
+// The build policy of the generic kernels K0 (psnode_generic_impl.h) and K5 (psnode_generic_bwd_impl.h): what separates the objects each
 // is compiled into, as constants the language can see.  Each object is one file that names its policy and includes the impl header:
 //   #define PSNODE_BUILD BuildAct
 //   #include "psnode_generic_impl.h"
@@ -177,7 +177,7 @@ __device__ __forceinline__ RkcCoef rkc_coef(const RkcDev& s, int j0) {
 }
 
 template <bool ACT, bool PRE, bool RK, bool SUB = false, bool LIN = false, bool PEV = false, bool AB = false, bool MS = false, bool PAR = false,
-          bool AB3 = false, bool LAG = false, bool RKC = false>
+          bool AB3 = false, bool LAG = false, bool RKC = false, bool STH = false>
 struct GenericBuild {
     static constexpr bool act = ACT;      // the hidden-layer activation is a kernel argument (ActPair, psnode_act.h), not ELU(1)
     static constexpr bool pre = PRE;      // the hidden layers' pre-activations u are kept next to h (SiLU / GELU / Mish differentiate from u)
@@ -196,6 +196,8 @@ struct GenericBuild {
                                           // piece, by the stencil table (LagDev; needs lin)
     static constexpr bool rkc = RKC;      // every grid interval is one s-stage Runge-Kutta-Chebyshev step: the sub-step loop with one evaluation per pass, the
                                           // three-term recurrence in the sub-step update's place, h undivided (RkcDev; needs sub, a one-stage tableau)
+    static constexpr bool sth = STH;      // stage-wise algebraic heads: a DAE's head i = g(X_s; z | v at theta_s) is evaluated in front of every stage s >= 1 of a
+                                          // (sub-)step instead of being frozen over the stages (needs lin; DAE instances only; the layouts are lin's / lag's)
     static constexpr int lin_layout = LAG ? 2 : (LIN ? 1 : 0);      // the LDS layout the fit queries count: none, lin's regions, lag's
     static constexpr bool par = PAR;      // segments in parallel: the launch grid is tiles x chunks, workgroup (tile, c) runs the segments of time chunk c
                                           // alone (MspDev; needs ms)
@@ -262,6 +264,8 @@ using BuildMsp = GenericBuild<true, true, true, true, false, false, false, true,
 using BuildAb3 = GenericBuild<true, true, true, true, false, true, true, false, false, true>;      // BuildAb's policy as Adams-Bashforth 3 with the Heun restart step
 using BuildLag = GenericBuild<true, true, true, true, true, false, false, false, false, false, true>;      // BuildLin's policy with the four-point Lagrange interpolant of the stencil table
 using BuildRkc = GenericBuild<true, true, true, true, false, false, false, false, false, false, false, true>;      // BuildSub's policy as one Runge-Kutta-Chebyshev step per interval: the stage count in the sub-steps' place
-enum BuildId { kBuildElu1, kBuildAct, kBuildPre, kBuildRk, kBuildSub, kBuildLin, kBuildPev, kBuildAb, kBuildMs, kBuildMsp, kBuildAb3, kBuildLag, kBuildRkc };      // what a call names its build with
+using BuildLinSth = GenericBuild<true, true, true, true, true, false, false, false, false, false, false, false, true>;      // BuildLin's policy with a head evaluation in front of every stage s >= 1
+using BuildLagSth = GenericBuild<true, true, true, true, true, false, false, false, false, false, true, false, true>;      // BuildLag's policy with the same
+enum BuildId { kBuildElu1, kBuildAct, kBuildPre, kBuildRk, kBuildSub, kBuildLin, kBuildPev, kBuildAb, kBuildMs, kBuildMsp, kBuildAb3, kBuildLag, kBuildRkc, kBuildLinSth, kBuildLagSth };      // what a call names its build with
 
 }  // namespace psnode

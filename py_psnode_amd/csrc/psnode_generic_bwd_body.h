@@ -39,6 +39,13 @@
     // dropped; ti -- the DE reads i_true[k], its algebraic adjoint is dropped and the event-time head feeds nothing
     const bool tx = (a.flags & PSNODE_FLAG_INPUT_TRUE_X) != 0, ti = dae && (a.flags & PSNODE_FLAG_INPUT_TRUE_I) != 0;
     const float* __restrict__ xsrc = tx ? a.xt : a.xs;
+    // Stage-wise algebraic heads (Bd::sth, on Bd::lin's policy): K0 evaluated i_s = g(X_s; z | v at theta_s) in front of every stage s >= 1 of a
+    // (sub-)step.  (3a) recomputes them in K0's order and expressions; (3b) recomputes i_s in front of stage s's VJP (no LDS keeps them) and
+    // sends the i part of that VJP through the head's VJP at (X_s, ext(theta_s)) -- its x part is the adjoint of X_s, its z | v part goes where
+    // the stage's own external adjoint goes, a0 and the AE's parameters where the in-interval head's go.  gic (free between (1) and (4)) keeps
+    // stage 0's i meanwhile, gxc (spent once (3b) has read it) takes the head VJP's x part.  Fixed ownership: every element is added by the
+    // thread that owns it in the loops around.
+    [[maybe_unused]] const bool sth_on = Bd::sth && dae && !ti && S > 1;
 
     float* acts = lds;                            // [act_rows][TP]
     float* dA = acts + a.act_rows * TP;           // [maxw][TP]
@@ -448,6 +455,7 @@
             } else {
                 TILE_LOOP(id) ext[(nzv + r) * TP + c] = a.is_[(k * a.B + gb(c)) * id + r];
             }
+            if constexpr (Bd::sth) { if (sth_on) { TILE_LOOP(id) gic[r * TP + c] = ext[(nzv + r) * TP + c]; } }      // stage 0's i (each thread copies what it wrote)
             __syncthreads();
         }
         // (3a) stage inputs and slopes
@@ -462,6 +470,15 @@
             }
             if constexpr (Bd::lin) lin_ext(theta(s));      // (behind the loop ext holds the last stage's rows, (3b)'s first)
             __syncthreads();
+            if constexpr (Bd::sth) {
+                if (sth_on && s > 0) {      // i_s = g(X_s; z | v at theta_s), K0's evaluation between the stages s - 1 and s
+                    ae_input(xst + s * nx, -1);
+                    if constexpr (STR >= 1) g_forward_str(a.ae, a.fimgA, acts, qb, qoA, ActCtx{act.ae, upre}); else g_forward(a.ae, acts, wbuf, ActCtx{act.ae, upre});
+                    const float* out = acts + a.ae.act[a.ae.L] * TP;
+                    TILE_LOOP(id) ext[(nzv + r) * TP + c] = out[r * TP + c];
+                    __syncthreads();
+                }
+            }
             if (s + 1 < S) {               // (the last stage's slope feeds no stage input: its evaluation is (3b)'s first, not done here)
                 de_input(xst + s * nx);
                 if constexpr (REG) g_forward_reg(a, acts, qb, qo, rfw, ActCtx{act.de, upre});
@@ -628,6 +645,33 @@
                     } else {
                         gext[(r - xd) * TP + c] += gs;
                     }
+                }
+            }
+            if constexpr (Bd::sth) {
+                if (sth_on && s > 0) {
+                    // gext's i rows hold stage s's algebraic adjoint alone: through the head at (X_s; ext's rows, still theta_s's)
+                    TILE_LOOP(xd) gxc[r * TP + c] = 0.0f;
+                    __syncthreads();
+                    th_head = theta(s);
+                    ae_vjp(xst + s * nx, -1, -2, gext + nzv * TP, gxc);
+                    TILE_LOOP(xd) {      // the x part is one more share of X_s's adjoint: onto the start state and over k_j by a[s][j]
+                        const float g = gxc[r * TP + c];
+                        gx0[r * TP + c] += g;
+                        for (int j = 0; j < s; ++j) { const float cf = coef_a(a.method, ks, nx, s, j); if (cf != 0.0f) gks[j * nx + r * TP + c] += dts[c] * cf * g; }
+                    }
+                    TILE_LOOP(id) gext[(nzv + r) * TP + c] = 0.0f;
+                    lin_ext(theta(s - 1));
+                    __syncthreads();
+                    if (s > 1) {      // stage s - 1's algebraic input, recomputed
+                        ae_input(xst + (s - 1) * nx, -1);
+                        if constexpr (STR >= 1) g_forward_str(a.ae, a.fimgA, acts, qb, qoA, ActCtx{act.ae, upre}); else g_forward(a.ae, acts, wbuf, ActCtx{act.ae, upre});
+                        const float* out = acts + a.ae.act[a.ae.L] * TP;
+                        TILE_LOOP(id) ext[(nzv + r) * TP + c] = out[r * TP + c];
+                    } else {
+                        TILE_LOOP(id) ext[(nzv + r) * TP + c] = gic[r * TP + c];
+                    }
+                    __syncthreads();
+                    continue;
                 }
             }
             if constexpr (Bd::lin) { if (s > 0) lin_ext(theta(s - 1)); }      // (ext was copied into the DE input before the VJP)

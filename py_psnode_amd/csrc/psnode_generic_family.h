@@ -9,6 +9,8 @@
 //   or the args' method as one; K5, no tableau: the method] | [K5] T, B | route | [K0] fill_* (method, dims, pointers), then [event_idx] |
 //   [K5] pointers, among them [x_sub where substeps > 1 and T >= 2], [event_idx], [x_true where a step restarts: T - 1 > every] |
 //   workspace | [K0, in dispatch] T, B, LDS fit of the build.
+//   _sth (DAE only): an `interp` that is neither PSNODE_EXT_LINEAR nor PSNODE_EXT_LAGRANGE is PSNODE_ERR_METHOD in front of all of it (its query: 0);
+//   behind that it is _lin's / _lag's sequence, row for row (sth_family picks the row).
 //   _msp: the _ms family's sequence with psnode_segment_groups_f32 in the segments struct's place; more than 65535 chunks (the grid's second
 //   dimension) are PSNODE_ERR_UNSUPPORTED with the route; [K5] its workspace is its own layout's (gbwd_msp_layout).
 //   _tf [K5; K0 has no such wrapper]: flags == 0 is the plain entry point, in front of all of it.  _rk, _ab, _ab3 and _rkc do not read `method` (K0's copy
@@ -30,7 +32,7 @@
 
 namespace psnode {
 
-enum Family { kFamTf, kFamAct, kFamRk, kFamSub, kFamLin, kFamPev, kFamAb, kFamMs, kFamMsp, kFamAb3, kFamLag, kFamRkc };
+enum Family { kFamTf, kFamAct, kFamRk, kFamSub, kFamLin, kFamPev, kFamAb, kFamMs, kFamMsp, kFamAb3, kFamLag, kFamRkc, kFamSthLin, kFamSthLag };
 // the tableau: no argument, `method` is read | NULL is PSNODE_ERR_NULL | NULL is the args' method as one | no argument, always one stage
 enum Tab { kTabNone, kTabRequired, kTabOrMethod, kTabOneStage };
 // the sub-steps struct: no argument | NULL is PSNODE_ERR_NULL | NULL is one sub-step
@@ -61,6 +63,8 @@ constexpr FamilyRow kFamilies[] = {
     /* _ab3 */ {kBuildAb3,  false, kTabOneStage, kSubNone,     false,  false, false, true,  true,  true,  false},      // (_ab's row: the same arguments, checks and fit)
     /* _lag */ {kBuildLag,  false, kTabOrMethod, kSubOrOne,    false,  false, false, false, true,  true,  2},          // (_lin's row and the stencil table, which may be NULL; its own layout)
     /* _rkc */ {kBuildRkc,  false, kTabOneStage, kSubRequired, false,  false, false, false, true,  true,  false},      // (_sub's row without a tableau and without the demotion: the stage count in the sub-steps' place, rkc_as_sub)
+    /* _sth */ {kBuildLinSth, false, kTabOrMethod, kSubOrOne,  false,  false, false, false, true,  true,  true},       // (interp PSNODE_EXT_LINEAR: _lin's row on the stage-heads build; DAE only)
+    /* _sth */ {kBuildLagSth, false, kTabOrMethod, kSubOrOne,  false,  false, false, false, true,  true,  2},          // (interp PSNODE_EXT_LAGRANGE: _lag's row on the stage-heads build; DAE only)
 };
 struct CallOpts {      // what a call carries behind its args; a family's wrappers leave what it does not take at NULL / 0
     const psnode_act_f32 *de_act, *ae_act;
@@ -84,6 +88,12 @@ inline const psnode_substeps_f32* rkc_as_sub(const psnode_rkc_f32* r, psnode_sub
     s.substeps = r->stages >= 1 && r->stages <= PSNODE_RKC_MAX_STAGES ? r->stages : 0;
     s.x_sub = r->x_stage;
     return &s;
+}
+// the row of an _sth call by its interpolant; false: no such interpolant
+inline bool sth_family(int32_t interp, Family& fam) {
+    if (interp != PSNODE_EXT_LINEAR && interp != PSNODE_EXT_LAGRANGE) return false;
+    fam = interp == PSNODE_EXT_LAGRANGE ? kFamSthLag : kFamSthLin;
+    return true;
 }
 // the time chunks of a segment-parallel call (1 for every other family)
 inline long long family_chunks(const FamilyRow& f, const CallOpts& o, long long T) { return f.par ? msp_chunks(T, o.every(), o.per_group()) : 1; }

@@ -580,6 +580,13 @@ hipError_t launch_generic_build(const IntegrateDev& a_in, bool dae, unsigned chu
     auto go = [&](auto kern) { return launch_attr(true, kern, dim3(grid, chunks), dim3(NT), lds_launch, stream_, a, extra...); };
     const int qm = generic_reg_mode(a, dae);
     const bool deep = a.de.n_layers > 4 || (dae && a.ae.n_layers > 4);      // the layer loop is unrolled 4 or kMaxLayers times
+    if constexpr (B::sth) {      // stage heads exist in a DAE alone: its instances only (register QM 4 / 8, resident, streamed, each deep form)
+        if (!dae) return hipErrorInvalidValue;
+        if (qm == 4) return go(K::template get<true, 0, 4, 4>());
+        if (qm == 8) return go(K::template get<true, 0, 4, 8>());
+        if (deep) return stream ? go(K::template get<true, 2, kMaxLayers>()) : go(K::template get<true, 1, kMaxLayers>());
+        return stream ? go(K::template get<true, 2, 4>()) : go(K::template get<true, 1, 4>());
+    } else {
     if (qm && deep) return qm == 4 ? go(K::template get<false, 0, kMaxLayers, 4>()) : go(K::template get<false, 0, kMaxLayers, 8>());
     if (qm == 4) return dae ? go(K::template get<true, 0, 4, 4>()) : go(K::template get<false, 0, 4, 4>());
     if (qm == 8) return dae ? go(K::template get<true, 0, 4, 8>()) : go(K::template get<false, 0, 4, 8>());
@@ -590,6 +597,7 @@ hipError_t launch_generic_build(const IntegrateDev& a_in, bool dae, unsigned chu
     }
     if (dae) return stream ? go(K::template get<true, 2, 4>()) : go(K::template get<true, 1, 4>());
     return stream ? go(K::template get<false, 2, 4>()) : go(K::template get<false, 1, 4>());
+    }
 }
 
 template <class B>

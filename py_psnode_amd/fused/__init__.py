@@ -11,7 +11,7 @@ Nothing here computes on the CPU and nothing here imports oracle/.  One module p
 """
 from .. import _lib  # noqa: F401
 from . import _common, backward_dae, backward_ode, encoded, forward, latent, plan, rows  # noqa: F401
-from ._common import (Layers, METHOD_ID, STAGES, Tableau, Recurrence, rkc_table, AB2, AB3, is_ab, ab_order, method_info, builtin_method, EXTERNALS, is_linear, is_lagrange, lagrange_stencils, stencil_code, GenericOpts, FAMILIES, check_segment_parallel, segment_chunks, auto_segment_groups, resolve_segment_parallel, call_generic, dae_acts, KERNEL_ID, _POISON, _empty, sequential_layers, de_layers_of, ae_layers_of, Act, act_of_module, sequential_mlp, pre_act_of_module, sequential_mlp_any, de_mlp_of, ae_mlp_of, _mlp_eval, _recipe_ok, _overrides_forward_hooks, _only_params_of, _f32_dev, _view, _aligned16, _mlp, _check_tb, _ms_rows, _check_jump, _jump, event_table, has_events, check_event_idx, _DUP_OK, _dup_key, _dup_check_known, _dup_check_remember, _workspace_of, _padded_hidden, _pad_rows, _gemm_tn, _check_saved, _split_grads)  # noqa: F401
+from ._common import (Layers, METHOD_ID, STAGES, Tableau, Recurrence, rkc_table, AB2, AB3, is_ab, ab_order, method_info, builtin_method, EXTERNALS, ALGEBRAIC, EXT_LINEAR, EXT_LAGRANGE, is_linear, is_lagrange, lagrange_stencils, stencil_code, GenericOpts, FAMILIES, check_segment_parallel, segment_chunks, auto_segment_groups, resolve_segment_parallel, call_generic, dae_acts, KERNEL_ID, _POISON, _empty, sequential_layers, de_layers_of, ae_layers_of, Act, act_of_module, sequential_mlp, pre_act_of_module, sequential_mlp_any, de_mlp_of, ae_mlp_of, _mlp_eval, _recipe_ok, _overrides_forward_hooks, _only_params_of, _f32_dev, _view, _aligned16, _mlp, _check_tb, _ms_rows, _check_jump, _jump, event_table, has_events, check_event_idx, _DUP_OK, _dup_key, _dup_check_known, _dup_check_remember, _workspace_of, _padded_hidden, _pad_rows, _gemm_tn, _check_saved, _split_grads)  # noqa: F401
 from .forward import (_MFMA_CLASSES, _k0_warned, _mfma_miss, _note_k0, ode_integrate, ode_save_hidden, dae_integrate, dae_save_hidden)  # noqa: F401
 from .backward_ode import (_bwd_args, ode_backward_supported, ode_backward)  # noqa: F401
 from .backward_dae import (dae_backward_supported, dae_backward_wide_supported, dae_backward_wide, _dae_backward_wide_sliced, dae_backward, dae_backward_tf)  # noqa: F401

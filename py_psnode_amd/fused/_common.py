@@ -230,6 +230,9 @@ def builtin_method(method, what: str):
 # z | v inside a grid interval: the left grid point's rows held (the reference), interpolated linearly to the right one's, or by the
 # polynomial through the up to four neighbouring dataset rows of the interval's piece (four-point Lagrange, `lagrange_stencils`)
 EXTERNALS = ("hold", "linear", "lagrange")
+# Where a DAE's algebraic variable is evaluated: "step" (once per (sub-)step, frozen over its stages: the reference's rule) or "stage" (in
+# front of every stage s >= 1 at that stage's argument and interpolated externals: neural_dae.FixedGridODESolver)
+ALGEBRAIC = ("step", "stage")
 
 
 def is_linear(externals: str) -> bool:
@@ -372,7 +375,8 @@ def _act_ptrs(acts):
 # psnode_segment_groups_f32, and both backward stems size their workspace with the family's own psnode_<stem>_<family>_workspace_size.
 # stencil: behind the structs comes the device pointer of the int8 [T-1, B] stencil table (`lagrange_stencils`), or NULL.
 # rkc: behind the acts comes the psnode_rkc_f32 alone (the recurrence with the stage rows, `Recurrence.abi`); its dae_backward query is _workspace_size.
-Family = collections.namedtuple("Family", "acts tab sub seg pt tf_args x_sub workspace par stencil rkc", defaults=(True, False, False, False, False, True, False, "own", False, False, False))
+# interp: behind the stencil table comes the int32 that picks the interpolant (1 linear, 2 Lagrange); dae_only: the family has no ODE entry points.
+Family = collections.namedtuple("Family", "acts tab sub seg pt tf_args x_sub workspace par stencil rkc interp dae_only", defaults=(True, False, False, False, False, True, False, "own", False, False, False, False, False))
 # The Python counterpart of kFamilies (csrc/psnode_generic_family.h): `GenericOpts`, `call_generic` and the prototypes of _lib.load read it.
 # "plain": the entry points without a family in their name; "none": no entry point at all; "tf": the "plain" dae_backward with dataset rows.
 FAMILIES = {
@@ -390,7 +394,9 @@ FAMILIES = {
     "ms": Family(tab=True, sub=True, seg=True, x_sub=True, workspace="rk"),
     "msp": Family(tab=True, sub=True, seg=True, x_sub=True, workspace="own", par=True),
     "rkc": Family(x_sub=True, rkc=True),
+    "sth": Family(tab=True, sub=True, x_sub=True, stencil=True, interp=True, dae_only=True),
 }
+EXT_LINEAR, EXT_LAGRANGE = 1, 2      # == PSNODE_EXT_LINEAR / PSNODE_EXT_LAGRANGE
 
 MAX_CHUNKS = 65535      # the launch grid's second dimension (csrc/psnode_generic_family.h: kMaxChunks)
 
@@ -461,6 +467,10 @@ class GenericOpts:
     stages: int = 1
     per_trajectory: bool = False
     segment: Optional[int] = None
+    # (init-only, like segment_parallel below and in front of `ab` for the reason given there: "stage" -- stage-wise algebraic heads, a DAE
+    #  call with interpolated externals, more than one stage and its own i -- is the family "sth" in "lin" / "lag"'s place, so the compared
+    #  value tells the two apart; an attribute of the value like every option)
+    algebraic: dataclasses.InitVar[str] = "step"
     ab: bool = False      # (or 3: Adams-Bashforth 3, `ab_order`)
     # (init-only: behind `ab` in the constructor and an attribute of the value like every option, but no entry of dataclasses.fields() --
     #  the recorded field lists end with ab, family; the family, which is compared, tells "ms" from "msp")
@@ -473,7 +483,7 @@ class GenericOpts:
         True for "ab2", 3 for "ab3" -- because the recorded lists of fields and of constructor arguments end with ab / ab, segment_parallel.)"""
         return 3 if self.ab == 3 else 2
 
-    def __post_init__(self, segment_parallel=None):
+    def __post_init__(self, algebraic="step", segment_parallel=None):
         """Validates substeps and externals, and names the entry-point family: "ab" (two-step Adams-Bashforth, with or without
         per-trajectory events; a ValueError together with a Tableau, sub-steps or interpolated externals), else "pev" (per-trajectory events, every substeps >= 1; together
         with interpolated externals "none": no kernel carries both, `require_generic` refuses the call), else "lin" (linearly interpolated
@@ -489,6 +499,19 @@ class GenericOpts:
         if self.ab not in (False, True, 3):
             raise ValueError(f"ab must be False, True (Adams-Bashforth 2) or 3 (Adams-Bashforth 3), got {self.ab!r}")
         ab_order = self.ab_order
+        if not isinstance(algebraic, str) or algebraic not in ALGEBRAIC:
+            raise ValueError(f"algebraic must be one of {ALGEBRAIC}, got {algebraic!r}")
+        object.__setattr__(self, "algebraic", algebraic)
+        if algebraic == "stage":
+            if self.ab:
+                raise ValueError(f"Adams-Bashforth {ab_order} reads the right-hand side at grid points only: algebraic='stage' has no stages to act on")
+            if isinstance(self.tab, Recurrence):
+                raise ValueError(f"{self.tab.name} already evaluates the algebraic head in front of every stage: algebraic='stage' has nothing to add")
+            if not is_linear(self.externals):
+                raise ValueError("algebraic='stage' needs interpolated externals (externals='linear' / 'lagrange'): held rows cap every "
+                                 "Runge-Kutta option at first order, and no build carries the pair")
+        # (an ODE has no head, a one-stage method no stage s >= 1: the option is inert there and the call is the "step" call)
+        sth = algebraic == "stage" and len(self.acts) == 2 and self.stages > 1
         if self.ab and ab_order == 3 and self.segment is not None:
             raise ValueError("Adams-Bashforth 3 carries the previous slopes from step to step: a multiple-shooting restart (segment=) has no "
                              f"form here (got segment={self.segment!r})")
@@ -523,7 +546,7 @@ class GenericOpts:
         elif self.per_trajectory:
             fam = "none" if is_linear(self.externals) else "pev"
         elif is_linear(self.externals):
-            fam = "lag" if is_lagrange(self.externals) else "lin"
+            fam = "sth" if sth else ("lag" if is_lagrange(self.externals) else "lin")
         elif self.substeps > 1:
             fam = "sub"
         elif self.tab is not None:
@@ -536,14 +559,15 @@ class GenericOpts:
     @staticmethod
     @functools.lru_cache(maxsize=256, typed=True)      # (a loop asks for the same immutable value call after call; typed: 2.0 and True are not 2 and 1)
     def of(method, acts: tuple, substeps: int = 1, externals: str = "hold", per_trajectory: bool = False, segment=None,
-           segment_parallel=None) -> "GenericOpts":
+           segment_parallel=None, algebraic: str = "step") -> "GenericOpts":
         method_id, stages, tab = method_info(method)
         if isinstance(tab, Recurrence):      # (substeps: 1, the caller's, or the stage count a GenericOpts of this method hands on)
             if substeps not in (1, tab.stages):
                 raise ValueError(f"{tab.name} takes one step per grid interval: substeps != 1 has no form here, raise the stage count instead "
                                  f"(got substeps={substeps!r})")
             substeps = tab.stages
-        return GenericOpts(acts, tab, substeps, externals, method_id, stages, per_trajectory, segment, 3 if ab_order(method) == 3 else is_ab(method), segment_parallel)
+        return GenericOpts(acts, tab, substeps, externals, method_id, stages, per_trajectory, segment, algebraic=algebraic,
+                           ab=3 if ab_order(method) == 3 else is_ab(method), segment_parallel=segment_parallel)
 
     def chunks(self, T: int) -> Optional[int]:
         """The time chunks of a record of T grid points under these options (None without segment_parallel): as `segment_parallel=` of a
@@ -574,6 +598,8 @@ class GenericOpts:
                 out.append(ctypes.byref(_lib.SegmentsF32(every, rows)))
         if f.stencil:
             out.append(ctypes.c_void_p(stencil.data_ptr() if stencil is not None and stencil.numel() else None))
+        if f.interp:
+            out.append(ctypes.c_int32(EXT_LAGRANGE if is_lagrange(self.externals) else EXT_LINEAR))
         if f.pt:      # (handed to the query too, which does not declare it and never reads it)
             out.append(ctypes.c_int32(1 if self.per_trajectory else 0))
         return out

@@ -7,12 +7,14 @@ import types
 import torch
 
 from .. import _lib
-from ._common import (KERNEL_ID, GenericOpts, Layers, _aligned16, _bind_jumps, _check_saved, _check_x_sub, _empty, _f32_dev, _mlp, _pad_rows, _padded_hidden, _split_grads, _view, _workspace_of, call_generic, check_event_idx, dae_acts, lagrange_stencils, _ms_rows, check_segment_parallel, resolve_segment_parallel)
+from ._common import (is_lagrange, KERNEL_ID, GenericOpts, Layers, _aligned16, _bind_jumps, _check_saved, _check_x_sub, _empty, _f32_dev, _mlp, _pad_rows, _padded_hidden, _split_grads, _view, _workspace_of, call_generic, check_event_idx, dae_acts, lagrange_stencils, _ms_rows, check_segment_parallel, resolve_segment_parallel)
 from .latent import latent_backward_wide, latent_wide_shape
 
 def dae_backward_supported(method, de_layers: Layers, ae_layers: Layers, x_dim, z_dim, v_dim, i_dim, act=None, kernel: str = "auto",
-                           substeps: int = 1, externals: str = "hold", per_trajectory: bool = False, segment=None, segment_parallel=None) -> bool:
-    """act: None (both MLPs ELU(1)) or (de_act, ae_act); an activation other than ELU(1) is K5's alone.  kernel="generic": does K5 take
+                           substeps: int = 1, externals: str = "hold", per_trajectory: bool = False, segment=None, segment_parallel=None,
+                           algebraic: str = "step") -> bool:
+    """algebraic="stage": K5's stage-heads builds only (the family "sth"; their fit is the interpolant's build's).
+    act: None (both MLPs ELU(1)) or (de_act, ae_act); an activation other than ELU(1) is K5's alone.  kernel="generic": does K5 take
     the shape (the question a teacher-forced call outside K7f's class asks).  method a fused.Tableau: K5's tableau build only (kernel
     "auto" / "generic"; it answers for its own LDS fit).  substeps > 1: K5's sub-step build only, under the same rules.
     externals="linear": K5's linear-externals build only (every substeps >= 1; it answers for its own LDS fit).
@@ -22,7 +24,7 @@ def dae_backward_supported(method, de_layers: Layers, ae_layers: Layers, x_dim, 
     if de_layers[0][0].device.type != "cuda" or max(len(de_layers), len(ae_layers)) > _lib.MAX_LAYERS:
         return False
     opts = GenericOpts.of(method, dae_acts(act), substeps, externals, bool(per_trajectory), segment,      # (segment: K5's multiple-shooting build only)
-                          None if segment_parallel is None else 1)
+                          None if segment_parallel is None else 1, algebraic)
     if opts.family == "plain" and kernel != "generic" and latent_wide_shape(de_layers, ae_layers, x_dim, z_dim, v_dim, i_dim):
         return True                          # K3w (saving) + K9w + library GEMMs
     args = opts.dae_backward_args(rows=False)
@@ -324,8 +326,10 @@ def _dae_backward_wide_sliced(step, method, de_layers, ae_layers, t, z, v, all_i
 
 def dae_backward(method, de_layers: Layers, ae_layers: Layers, t, z, v, all_initial, xs, is_, grad_xs, grad_is, event_idx=None,
                  z_jump=None, v_jump=None, kernel: str = "auto", saved=None, act=None, substeps: int = 1, x_sub=None, externals: str = "hold",
-                 per_trajectory: bool = False, segment=None, x_true=None, segment_parallel=None):
-    """Backward pass of `dae_integrate` (no teacher forcing): the one-launch K7f (`dae_backward_wide`) for the DAE_01 shape class at
+                 per_trajectory: bool = False, segment=None, x_true=None, segment_parallel=None, algebraic: str = "step"):
+    """algebraic="stage": backward of `dae_integrate(..., algebraic="stage")` -- K5's stage-heads builds only, under the interpolant's rules:
+    the i part of the DE's VJP of a stage s >= 1 goes through the head's VJP at that stage's argument and externals.
+    Backward pass of `dae_integrate` (no teacher forcing): the one-launch K7f (`dae_backward_wide`) for the DAE_01 shape class at
     hidden <= 128, K9 / K8 / K9w for the latent shapes of the direct_encode models, else the generic backward kernel (K5);
     `kernel` = "auto" | "mfma" | "generic" | "wide" (K7f or an error).
     saved = what `dae_integrate(save=True)` returned (read by K7f, K9 and K9w; K8 / K5 recompute and refuse them).
@@ -345,7 +349,7 @@ def dae_backward(method, de_layers: Layers, ae_layers: Layers, t, z, v, all_init
     T, B, xd = xs.shape
     zd, vd, idim = z.shape[-1], v.shape[-1], is_.shape[-1]
     opts = GenericOpts.of(method, dae_acts(act), substeps, externals, bool(per_trajectory) and event_idx is not None, segment,
-                          resolve_segment_parallel(segment_parallel, segment, T, B, xs.device))
+                          resolve_segment_parallel(segment_parallel, segment, T, B, xs.device), algebraic)
     opts.require_generic("dae_backward", kernel, saved is not None)
     if opts.family != "plain":      # K5 alone (an activation other than ELU(1) asks for it by name, as it always did)
         return _dae_backward_entry(opts, de_layers, ae_layers, t, z, v, all_initial, xs, is_, grad_xs, grad_is, event_idx, z_jump, v_jump,
@@ -366,8 +370,9 @@ def dae_backward(method, de_layers: Layers, ae_layers: Layers, t, z, v, all_init
 
 def dae_backward_tf(method, de_layers: Layers, ae_layers: Layers, t, z, v, all_initial, xs, is_, grad_xs, grad_is, event_idx=None,
                     z_jump=None, v_jump=None, kernel: str = "auto", x_true=None, i_true=None, substeps: int = 1, x_sub=None,
-                    externals: str = "hold", per_trajectory: bool = False):
-    """Backward of a teacher-forced `dae_integrate` (input_true_x / input_true_i, my_solvers.py:111-121) on the generic backward K5
+                    externals: str = "hold", per_trajectory: bool = False, algebraic: str = "step"):
+    """algebraic="stage": with x_true alone (with i_true every stage read i_true[k]: the "step" call).
+    Backward of a teacher-forced `dae_integrate` (input_true_x / input_true_i, my_solvers.py:111-121) on the generic backward K5
     (psnode_dae_backward_tf_f32): every shape K5 takes untied.  x_true [T,B,x_dim] / i_true [T,B,i_dim]: the dataset rows the forward call
     fed the DE / the heads (None = that flag was not set; both None = `dae_backward` on K5's entry point); they get no gradient.  xs / is_:
     the forward results (an event step's recomputed head reads the running state xs[k]).  kernel: "auto" | "generic".  substeps > 1: with the
@@ -381,7 +386,9 @@ def dae_backward_tf(method, de_layers: Layers, ae_layers: Layers, t, z, v, all_i
     for name, q, w in (("x_true", x_true, xd), ("i_true", i_true, is_.shape[-1])):
         if q is not None and tuple(q.shape) != (T, B, w):
             raise ValueError(f"{name} must be [T,B,{w}], got {tuple(q.shape)}")
-    opts = GenericOpts.of(method, (None, None), substeps, externals, bool(per_trajectory) and event_idx is not None)
+    opts = GenericOpts.of(method, (None, None), substeps, externals, bool(per_trajectory) and event_idx is not None, None, None, algebraic)
+    if i_true is not None and algebraic == "stage":      # (validated above)
+        opts = GenericOpts.of(method, (None, None), substeps, externals, bool(per_trajectory) and event_idx is not None)
     opts.require_generic("dae_backward_tf", kernel, False)
     opts.no_teacher_forcing("dae_backward_tf", x_true is not None or i_true is not None)
     return _dae_backward_entry(opts, de_layers, ae_layers, t, z, v, all_initial, xs, is_, grad_xs,
@@ -450,7 +457,7 @@ def _dae_backward_entry(opts, de_layers, ae_layers, t, z, v, all_initial, xs, is
                 a.saved_ev_act, a.saved_ev_i = s_ev.data_ptr(), s_evi.data_ptr()
         nbytes = call_generic(lib, "dae_backward", "workspace_bytes", args, opts, x_sub=x_sub, x_true=ms_x_true)[0]
         ws, wp, wn = _workspace_of(nbytes, dev)
-        stencil = lagrange_stencils(t.detach(), event_idx) if opts.takes.stencil else None      # (externals="lagrange": the forward's table again)
+        stencil = lagrange_stencils(t.detach(), event_idx) if opts.takes.stencil and is_lagrange(opts.externals) else None      # (externals="lagrange": the forward's table again)
         rc, entry = call_generic(lib, "dae_backward", "f32", args, opts, wp, wn, torch.cuda.current_stream(dev).cuda_stream, x_sub=x_sub, x_true=ms_x_true,
                                  stencil=stencil)
     _lib.check(rc, entry)

@@ -6,7 +6,7 @@ from typing import Optional
 import torch
 
 from .. import _lib
-from ._common import (KERNEL_ID, GenericOpts, resolve_segment_parallel, Layers, Tableau, Recurrence, builtin_method, _aligned16, _bind_events, _check_tb, _empty, _f32_dev, _mlp, _view, _workspace_of, call_generic, dae_acts, has_events, is_linear, lagrange_stencils)
+from ._common import (is_lagrange, KERNEL_ID, GenericOpts, resolve_segment_parallel, Layers, Tableau, Recurrence, builtin_method, _aligned16, _bind_events, _check_tb, _empty, _f32_dev, _mlp, _view, _workspace_of, call_generic, dae_acts, has_events, is_linear, lagrange_stencils)
 
 _MFMA_CLASSES = ("MFMA integrators K1 / K2 cover `in -> H -> H -> H -> out` ELU-MLPs with H <= 128 (any x_dim <= 16 for the ODE, "
                  "x_dim <= 8 and z+v+i <= 8 for the DAE), and -- weights streamed from L2 -- the ODE up to H = 192 at any x_dim <= 16 and "
@@ -168,7 +168,7 @@ def dae_integrate(method, de_layers: Layers, ae_layers: Layers, x_init, t, x, z,
                   event_t=None, z_jump=None, v_jump=None, input_true_x: bool = False, input_true_i: bool = False,
                   kernel: str = "auto", event_idx: Optional[torch.Tensor] = None, check_events: bool = False, out=None,
                   save: bool = False, act=None, substeps: int = 1, save_sub: bool = False, externals: str = "hold",
-                  per_trajectory: bool = False, segment=None, segment_parallel=None):
+                  per_trajectory: bool = False, segment=None, segment_parallel=None, algebraic: str = "step"):
     """Fused integrate_DAE (replaces my_solvers.py:82-131 + step functions + DE_Func/AE_Func forwards).
     method: "euler" | "midpoint" | "rk4", or a fused.Tableau (generic kernel K0 only: kernel "auto" / "generic"; save=True is refused).
     act: None (both MLPs ELU(1)) or (de_act, ae_act), each a fused.Act or None = ELU(1); an activation other than ELU(1) runs on the
@@ -180,6 +180,10 @@ def dae_integrate(method, de_layers: Layers, ae_layers: Layers, x_init, t, x, z,
     at theta = (j + c_s) / substeps, as does the head in front of sub-step j >= 1 (theta = j / substeps); i is never interpolated.  K0's
     linear-externals build for every substeps >= 1 (kernel "auto" / "generic", no save); "lagrange": the four-point polynomial of the
     interval's piece in the straight line's place (the Lagrange build, the same rules; `lagrange_stencils`).
+    algebraic: "step" (i frozen over the stages of a (sub-)step) or "stage" -- in front of every stage s >= 1 the head is evaluated at that
+    stage's argument and interpolated externals, i_s = g(X_s; z | v at theta_s), and feeds the stage's DE evaluation (no output row).  Needs
+    interpolated externals (ValueError with "hold"); K0's stage-heads builds (the family "sth": kernel "auto" / "generic", no save) under the
+    rules of the interpolant.  With input_true_i (every stage reads i[k]) or a one-stage method it is the "step" call, bit for bit.
     per_trajectory=True: as `ode_integrate`, for z | v together; the event-time head i0 = g(x_k; z_jump, v_jump) replaces the carried
     algebraic variable of the trajectories with a hit at step k only, the others keep theirs.  K0's per-trajectory build for every
     substeps >= 1 (kernel "auto" / "generic", no save, not with externals="linear").
@@ -198,7 +202,9 @@ def dae_integrate(method, de_layers: Layers, ae_layers: Layers, x_init, t, x, z,
         raise ValueError("fused integrator needs tensors on a HIP device")
     per_trajectory = bool(per_trajectory) and has_events(t, event_t, event_idx)
     per_group = resolve_segment_parallel(segment_parallel, segment, t.shape[0], t.shape[1], dev)
-    opts = GenericOpts.of(method, dae_acts(act), substeps, externals, per_trajectory, segment, per_group)
+    opts = GenericOpts.of(method, dae_acts(act), substeps, externals, per_trajectory, segment, per_group, algebraic)
+    if input_true_i and algebraic == "stage":      # (validated above; no head runs inside an interval: the "step" call)
+        opts = GenericOpts.of(method, dae_acts(act), substeps, externals, per_trajectory, segment, per_group)
     opts.require_generic("dae_integrate", kernel, save)
     opts.no_teacher_forcing("dae_integrate", input_true_x or input_true_i)
     if segment is not None and x.shape[-1] == 0:
@@ -269,7 +275,7 @@ def dae_integrate(method, de_layers: Layers, ae_layers: Layers, x_init, t, x, z,
                 a.save_ev_act, a.save_ev_i = saved[3].data_ptr(), saved[4].data_ptr()
         x_sub = _empty((max(T - 1, 0), opts.substeps - 1, B, xd), dtype=torch.float32, device=dev) if save_sub and opts.takes.x_sub else None
         ws, wp, wn = _workspace_of(lib.psnode_workspace_bytes(ctypes.byref(a.de), ctypes.byref(a.ae)), dev)
-        stencil = lagrange_stencils(t.detach(), event_idx) if opts.takes.stencil else None      # (externals="lagrange": int8 [T-1, B])
+        stencil = lagrange_stencils(t.detach(), event_idx) if opts.takes.stencil and is_lagrange(opts.externals) else None      # (externals="lagrange": int8 [T-1, B])
         rc, entry = call_generic(lib, "dae_integrate", "f32", a, opts, wp, wn, torch.cuda.current_stream(dev).cuda_stream, x_sub=x_sub, stencil=stencil)
     _mfma_miss(rc, kernel, entry, de_layers)
     _lib.check(rc, entry)

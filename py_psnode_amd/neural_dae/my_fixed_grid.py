@@ -6,7 +6,8 @@ the callback walk (user callables / autograd).  Callback convention (my_fixed_gr
 `func(t0=, xt=, zt=, all_initial=)` when v0 is None, else `func(t0=, xt=, zt=, vt=, it=, all_initial=)`.
 
 `_step_func_lin` is each class's formula once more for `externals="linear"` (my_solvers.py): the stage at abscissa c reads the externals
-`ext_at(c)` instead of the step's frozen ones.  `_step_func`, its signature and the "hold" path are untouched by it.
+`ext_at(c)` instead of the step's frozen ones.  `_step_func`, its signature and the "hold" path are untouched by it.  Its keyword `head` (None: every statement as it was) is the
+solver option algebraic="stage": called as head(xx, z, v) in front of every stage s >= 1, it gives that stage its own algebraic variable.
 """
 import torch
 
@@ -17,13 +18,30 @@ _one_third = 1 / 3
 _two_thirds = 2 / 3
 
 
-def _rhs_at(func, ext_at, i0, all_initial):
-    """f(c, t, x): the right-hand side whose externals are those of abscissa c, ext_at(c) = (z, v | None) (externals='linear')."""
+def _rhs_at(func, ext_at, i0, all_initial, head=None):
+    """f(c, t, x): the right-hand side whose externals are those of abscissa c, ext_at(c) = (z, v | None) (externals='linear').
+    head (algebraic='stage'; a DAE): the first call of f -- stage 0 -- reads i0, every later one i = head(x, z, v) at its own argument and
+    externals."""
+    if head is not None:
+        return _rhs_at_heads(func, ext_at, i0, all_initial, head)
+
     def f(c, tt, xx):
         z0, v0 = ext_at(c)
         if v0 is None:
             return func(t0=tt, xt=xx, zt=z0, all_initial=all_initial)
         return func(t0=tt, xt=xx, zt=z0, vt=v0, it=i0, all_initial=all_initial)
+    return f
+
+
+def _rhs_at_heads(func, ext_at, i0, all_initial, head):
+    """`_rhs_at` with stage-wise algebraic heads: stage s >= 1 evaluates i_s = head(X_s, z_s, v_s) in front of its DE evaluation."""
+    first = [True]
+
+    def f(c, tt, xx):
+        z0, v0 = ext_at(c)
+        it = i0 if first[0] else head(xx, z0, v0)
+        first[0] = False
+        return func(t0=tt, xt=xx, zt=z0, vt=v0, it=it, all_initial=all_initial)
     return f
 
 
@@ -42,8 +60,8 @@ class Euler(FixedGridODESolver):
         f0 = _rhs(func, z0, v0, i0, all_initial)(t0, x0)
         return dt * f0, f0
 
-    def _step_func_lin(self, func, t0, dt, x0, ext_at, i0=None, all_initial=None):
-        return dt * _rhs_at(func, ext_at, i0, all_initial)(0.0, t0, x0)
+    def _step_func_lin(self, func, t0, dt, x0, ext_at, i0=None, all_initial=None, head=None):
+        return dt * _rhs_at(func, ext_at, i0, all_initial, head)(0.0, t0, x0)
 
 
 class Midpoint(FixedGridODESolver):
@@ -56,8 +74,8 @@ class Midpoint(FixedGridODESolver):
         f0 = f(t0, x0)
         return dt * f(t0 + half_dt, x0 + f0 * half_dt), f0
 
-    def _step_func_lin(self, func, t0, dt, x0, ext_at, i0=None, all_initial=None):
-        f = _rhs_at(func, ext_at, i0, all_initial)
+    def _step_func_lin(self, func, t0, dt, x0, ext_at, i0=None, all_initial=None, head=None):
+        f = _rhs_at(func, ext_at, i0, all_initial, head)
         half_dt = 0.5 * dt
         return dt * f(0.5, t0 + half_dt, x0 + f(0.0, t0, x0) * half_dt)
 
@@ -80,9 +98,9 @@ class RK4(FixedGridODESolver):
         return self.rk4_alt_step_func(func=func, t0=t0, dt=dt, t1=t1, x0=x0, z0=z0, v0=v0, i0=i0,
                                       all_initial=all_initial, f0=f0), f0
 
-    def _step_func_lin(self, func, t0, dt, x0, ext_at, i0=None, all_initial=None):
+    def _step_func_lin(self, func, t0, dt, x0, ext_at, i0=None, all_initial=None, head=None):
         """The 3/8 rule with the externals of c = 0, 1/3, 2/3, 1."""
-        f = _rhs_at(func, ext_at, i0, all_initial)
+        f = _rhs_at(func, ext_at, i0, all_initial, head)
         k1 = f(0.0, t0, x0)
         k2 = f(_one_third, t0 + dt * _one_third, x0 + dt * k1 * _one_third)
         k3 = f(_two_thirds, t0 + dt * _two_thirds, x0 + dt * (k2 - k1 * _one_third))
@@ -119,8 +137,8 @@ class ExplicitRK(FixedGridODESolver):
             ks.append(f(t0 + tab.c[s] * dt if s else t0, x0 if inc is None else x0 + dt * inc))
         return dt * self._combine(tab.b, ks), ks[0]
 
-    def _step_func_lin(self, func, t0, dt, x0, ext_at, i0=None, all_initial=None):
-        f = _rhs_at(func, ext_at, i0, all_initial)
+    def _step_func_lin(self, func, t0, dt, x0, ext_at, i0=None, all_initial=None, head=None):
+        f = _rhs_at(func, ext_at, i0, all_initial, head)
         tab = self.method
         ks = []
         for s in range(tab.stages):
@@ -189,6 +207,9 @@ class AB2(FixedGridODESolver):
         if kw.get("externals", "hold") != "hold":
             raise ValueError("AB2 reads the right-hand side at grid points only: externals='linear' would need inputs between the dataset rows "
                              f"(got externals={kw.get('externals')!r})")
+        if kw.get("algebraic", "step") == "stage":
+            raise ValueError("AB2 reads the right-hand side at grid points only, where the head is evaluated anyway: it has no stages for "
+                             f"algebraic={kw.get('algebraic')!r} to act on")
         if kw.get("segment") is not None:
             raise ValueError("AB2 carries the previous slope from step to step: a multiple-shooting restart (segment=) has no form here "
                              f"(got segment={kw.get('segment')!r})")
@@ -316,6 +337,9 @@ class AB3(AB2):
         if kw.get("externals", "hold") != "hold":
             raise ValueError("AB3 reads the right-hand side at grid points only: externals='linear' would need inputs between the dataset rows "
                              f"(got externals={kw.get('externals')!r})")
+        if kw.get("algebraic", "step") == "stage":
+            raise ValueError("AB3 reads the right-hand side at grid points only, where the head is evaluated anyway: it has no stages for "
+                             f"algebraic={kw.get('algebraic')!r} to act on")
         if kw.get("segment") is not None:
             raise ValueError("AB3 carries the previous slopes from step to step: a multiple-shooting restart (segment=) has no form here "
                              f"(got segment={kw.get('segment')!r})")
@@ -455,6 +479,9 @@ class _RKC(FixedGridODESolver):
         if kw.get("segment") is not None or kw.get("segment_parallel") is not None:
             raise ValueError(f"{name} has no multiple-shooting form (got segment={kw.get('segment')!r}, "
                              f"segment_parallel={kw.get('segment_parallel')!r})")
+        if kw.get("algebraic", "step") == "stage":
+            raise ValueError(f"{name} already evaluates the algebraic head in front of every stage: algebraic={kw.get('algebraic')!r} has "
+                             "nothing to add")
         if damping is not None and (isinstance(damping, bool) or not isinstance(damping, (int, float)) or not damping > 0):
             raise ValueError(f"{name}: damping must be a number > 0, got {damping!r}")
         self.method = _fused.rkc_table(stages, self._order, None if damping is None else float(damping))

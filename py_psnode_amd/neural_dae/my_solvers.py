@@ -13,6 +13,7 @@ LOUDLY if libpsnode_hip.so is missing -- never a silent substitute; a call on a 
 says so once with a RuntimeWarning), "require" (raise if the call is not fusable), "off" (always the walk).
 """
 import abc
+import inspect
 import os
 import warnings
 
@@ -90,8 +91,22 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
     _step_state = None
 
     def __init__(self, step_size=None, grid_constructor=None, interp="linear", substeps=1, externals="hold", segment=None,
-                 segment_parallel=None):
-        """segment_parallel (None, the default: the call it was; "auto" or an int g >= 1; needs segment): where a fused call with segments
+                 segment_parallel=None, algebraic="step"):
+        """algebraic ("step", the default and the reference's rule, or "stage"): where a DAE's algebraic variable i = g(x, z, v) is evaluated.
+        "step": once per (sub-)step, frozen over its Runge-Kutta stages -- which caps every Runge-Kutta option at first order on a DAE.
+        "stage": the standard treatment of an index-1 DAE -- stage s >= 1 of sub-step j, with X_s = x + h sum_{j' < s} a[s][j'] k_j' and
+        (z_s, v_s) the interpolated externals at theta_s = (j + c_s) / substeps (the rows its DE evaluation reads), evaluates
+        i_s = g(X_s, z_s, v_s, all_initial) and k_s = f(X_s, z_s, v_s, i_s): one more AE evaluation per stage, no output row, so that the method
+        integrates x' = f(x, w(t), g(x, w(t))) and reaches its own order -- RK4Classic(externals="lagrange", algebraic="stage") is fourth order
+        on a DAE, Heun2(externals="linear", algebraic="stage") second.  Stage 0 reads the i it reads under "step" (the carried head of grid point
+        k, the event-time head on the jumped rows, for j >= 1 the in-interval head at theta = j / substeps); the head at grid point k + 1,
+        both outputs, h, the events, theta and the interpolants are untouched.  input_true_x: sub-step 0 starts from x[k], the stage heads
+        still see X_s.  input_true_i: every stage reads i[k] and no head runs inside an interval -- the "step" call, bit for bit; so is a
+        one-stage method's (Euler), and every integrate_ODE call (no head).  `_walk_dae` is the definition (through the keyword `head` of
+        `_step_func_lin`); fused on the generic kernels K0 / K5 (kernel 'auto' / 'generic') under the rules of interpolated externals.
+        Needs externals="linear" / "lagrange" (held rows cap every Runge-Kutta option at order one, and no build carries the pair); AB2 / AB3
+        (grid points only) and RKC1 / RKC2 (they evaluate the head at every stage already) refuse it: ValueError.
+        segment_parallel (None, the default: the call it was; "auto" or an int g >= 1; needs segment): where a fused call with segments
         runs, never what it computes -- the segments of a record get no gradient through the dataset rows, so they are independent, and the
         generic kernels K0 / K5 then run them side by side: the n_seg = ceil((T - 1) / w) segments in up to g time chunks of
         ceil(n_seg / min(g, n_seg)) consecutive ones, on a launch grid of tiles x chunks workgroups.  "auto": g = max(1, CUs // tiles) with
@@ -130,6 +145,12 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
         if externals not in _fused.EXTERNALS:
             raise ValueError(f"externals must be one of {_fused.EXTERNALS}, got {externals!r}")
         self.externals = externals
+        if not isinstance(algebraic, str) or algebraic not in _fused.ALGEBRAIC:
+            raise ValueError(f"algebraic must be one of {_fused.ALGEBRAIC}, got {algebraic!r}")
+        if algebraic == "stage" and externals == "hold":
+            raise ValueError("algebraic='stage' needs interpolated externals (externals='linear' / 'lagrange'): held rows cap every "
+                             "Runge-Kutta option at first order whatever the head does, and no kernel build carries the pair")
+        self.algebraic = algebraic
         if segment is not None and (isinstance(segment, bool) or not isinstance(segment, int) or segment < 1):
             raise ValueError(f"segment must be None or an int >= 1, got {segment!r}")
         self.segment = segment
@@ -216,10 +237,22 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
             raise UnsupportedShapeError(f"{what}: kernel={self.kernel!r} {text}")
         return False
 
-    def _generic_kwargs(self, per_trajectory=False) -> dict:
-        """substeps= / externals= / per_trajectory= for the fused calls, left out at 1 / "hold" / False: those calls are then the ones they
-        always were."""
+    def _stage_heads(self, input_true_i=False) -> bool:
+        """Does a DAE call of this solver evaluate the head in front of its stages s >= 1?  algebraic="stage", the call integrates its own
+        i and the method has more than one stage; every other call is the "step" call and takes its route."""
+        if self.algebraic != "stage" or input_true_i:
+            return False
+        try:
+            return _fused.method_info(self.method)[1] > 1
+        except (KeyError, TypeError):      # (a user's solver class without a `method` the kernels know: its own formula decides)
+            return True
+
+    def _generic_kwargs(self, per_trajectory=False, stage_heads=False) -> dict:
+        """substeps= / externals= / per_trajectory= / algebraic= for the fused calls, left out at 1 / "hold" / False / "step" (stage_heads:
+        `_stage_heads` of a DAE call): those calls are then the ones they always were."""
         kw = dict(substeps=self.substeps) if self.substeps != 1 else {}
+        if stage_heads:
+            kw["algebraic"] = "stage"
         if self.externals != "hold":
             kw["externals"] = self.externals
         if per_trajectory:
@@ -384,7 +417,7 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
             per_traj = plan is not None and plan[2] is not None and _fused.per_trajectory_events(event_fn)
             if plan is not None and not self._generic_only_ok("integrate_DAE", plan[6:], per_traj):
                 plan = None
-            sub = self._generic_kwargs(per_traj)
+            sub = self._generic_kwargs(per_traj, self._stage_heads(input_true_i))
             if plan is not None:
                 de, ae, event_t, z_jump, v_jump, needs_grad, de_act, ae_act = plan
                 act = None if de_act is None and ae_act is None else (de_act, ae_act)
@@ -434,6 +467,12 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
         is_ = torch.zeros(i.shape, dtype=i.dtype, device=i.device)
         xs[0], is_[0] = cur_x, cur_i
         lag = self._lag_walk("integrate_DAE", t, event_fn, jump_change_fn, (z, v))
+        heads = {}      # algebraic="stage": the head a stage s >= 1 evaluates at its own argument and externals
+        if self._stage_heads(input_true_i):
+            if "head" not in inspect.signature(self._step_func_lin).parameters:
+                raise NotImplementedError(f"{type(self).__name__}._step_func_lin has no keyword `head`: algebraic='stage' needs the step "
+                                          "formula to call head(xx, z, v) in front of every stage s >= 1")
+            heads = dict(head=lambda xx, zz, vv: i_func(xt=xx, zt=zz, vt=vv, all_initial=all_initial))
         for k in range(n_grid - 1):
             t0, t1, zk, vk = t[k], t[k + 1], z[k], v[k]
             if lag.hits[k] if lag is not None else (event_fn is not None and event_fn(t0) == True):  # noqa: E712
@@ -459,7 +498,7 @@ class FixedGridODESolver(metaclass=abc.ABCMeta):
                         zj_, vj_ = ext_at(0.0)
                         i_in = i_func(xt=cur_x, zt=zj_, vt=vj_, all_initial=all_initial)
                     cur_x = cur_x + self._step_func_lin(func=x_func, t0=t0 + j * h if j else t0, dt=h, x0=cur_x, ext_at=ext_at, i0=i_in,
-                                                        all_initial=all_initial)
+                                                        all_initial=all_initial, **heads)
             elif self._step_state is not None:      # (the head in front of a stage sees the interval's held rows, as a sub-step's does)
                 head = None if input_true_i else (lambda xx, zk=zk, vk=vk: i_func(xt=xx, zt=zk, vt=vk, all_initial=all_initial))
                 cur_x = self._step_state(func=x_func, t0=t0, dt=t1 - t0, t1=t1, x0=start, z0=zk, v0=vk, i0=i_in, all_initial=all_initial, head=head)
